@@ -1,14 +1,22 @@
 #!/usr/bin/env python3
 """Headline benchmark: synthetic patients/sec for a full T=1000 reverse sample (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one complete T-step reverse sample (models/diffusion.py:427-449 incl. the mutation
 threshold of utils/generate.py:135) of `--patients` conditional patients per GPU at the BASELINE
 shape (D = 50 + 1900 + 50, hidden [256,512,256], cond 3, cosine schedule, three scenario
 condition rows of config.yaml:124-141), on synthetic inputs already resident in HBM.  Rows are
 sharded over ranks with no collective ("weak" scaling: per-GPU patients fixed).  Rank 0 prints ONE
-JSON line:
+JSON line.  A plain run sets up, runs W warm-up and K timed steps and prints the headline (`value`,
+`ms_per_step` = wall time of the K timed steps / K); the legs below are null in it.
+
+`--dump-outputs DIR` writes what the last timed step returned (samples [n, D] and the mutation mask
+[n, 50], float32) as DIR/samples.npy and DIR/mutation_mask.npy, restricted to a fixed seeded sample
+of DUMP_ROWS rows of rank 0 (global rows, so the same for any GPU count); the inputs depend only on
+the arguments, so two builds can be compared output for output.
+
+`--full` adds the legs (each `--*-only` option runs one of them on its own):
   * `roofline`      the dominant kernel of the timed region, measured live with HIP events;
   * `train`         the secondary metric (BASELINE config 2 at N = 1, config 4 = data-parallel at N > 1):
                     utils/train.py:204-250 per step (mixup, fused forward/backward, bucketed gradient
@@ -40,6 +48,7 @@ HBM_PEAK_GBPS = 8000.0
 FLOP_PER_PATIENT_STEP = 5_193_728      # 2 x 2 596 864 MAC, GEMMs only
 TRAIN_FLOP_PER_SAMPLE = 14.56e6        # fwd 5.194 + dgrad 4.170 + wgrad 5.194 MFLOP
 TRAIN_BATCH = 4096                     # per GPU (BASELINE configs 2 and 4)
+DUMP_ROWS = 4096                       # --dump-outputs: 4096 x (2000 + 50) x 4 B = 33.6 MB
 
 CONF = {"model": {"latent_dim": 128, "hidden_dims": [256, 512, 256], "gnn": {"dropout": 0.2},
                   "diffusion": {"num_steps": 1000, "beta_schedule": "cosine"},
@@ -79,7 +88,16 @@ def parse_args():
     ap.add_argument("--no-validate", action="store_true", help="skip the config-5 share leg (3 x 125 000 patients + on-device validation)")
     ap.add_argument("--validate-only", action="store_true")
     ap.add_argument("--validate-patients", type=int, default=125_000)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the headline also run the roofline, training, reference-workload, "
+                    "validation and CPU-baseline legs (each --no-* option drops one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed seeded sample of the last timed step's outputs as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    only = args.profile_only or args.train_only or args.validate_only or args.reference_workload_only
+    if args.dump_outputs and (only or args.steps < 1):
+        ap.error("--dump-outputs needs the timed steps: --steps >= 1 and no --*-only option")
+    args.full = args.full or only              # a --*-only option runs one leg of the full run
+    return args
 
 
 def self_launch(args):
@@ -101,6 +119,20 @@ def scenario_conditions(n, offset):
                          for s in SCENARIOS], dtype=torch.float32)
     idx = (torch.arange(n) + offset) % 3
     return rows[idx]
+
+
+def dump_outputs(dirname, out, mask):
+    """--dump-outputs: the arrays sample() handed back in the last timed step, on DUMP_ROWS rows drawn once with a fixed seed
+    (every row when there are no more than that)."""
+    import numpy as np
+    import torch
+    n = out.shape[0]
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+    idx = torch.from_numpy(rows).to(out.device)
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "samples.npy", out.index_select(0, idx).cpu().numpy().astype(np.float32))
+    np.save(d / "mutation_mask.npy", mask.index_select(0, idx).cpu().numpy().astype(np.float32))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -523,6 +555,8 @@ def main():
     if args.steps:
         if not os.environ.get("OSD_BENCH_TIMING_ONLY"):     # timing experiments with garbage-producing diagnostic builds
             assert torch.isfinite(out).all().item()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out, mask)
         del out, mask
     total_patients = n * world * args.steps
     value = total_patients / elapsed
@@ -530,20 +564,20 @@ def main():
 
     roof, cpu = None, None
     sample_ms = [a.elapsed_time(b) for a, b in evs] if args.steps else []
-    if rank == 0:
+    if rank == 0 and args.full:
         roof = roofline_leg(model, args, cond, offset, dev, engine_used, sample_ms, step)
     train = None
-    if not args.no_train and not args.profile_only:
+    if args.full and not args.no_train and not args.profile_only:
         train = train_leg(dev, dist, world, rank, args.train_steps, backend)
         if world == 1 and not args.no_split:
             train["split_bf16"] = train_split_leg(dev, args.train_steps)
     refw = None
-    if rank == 0 and world == 1 and not args.no_reference_workload and not args.profile_only:
+    if args.full and rank == 0 and world == 1 and not args.no_reference_workload and not args.profile_only:
         refw = reference_workload_leg(dev)
     vleg = None
-    if rank == 0 and world == 1 and not args.no_validate and not args.profile_only:
+    if args.full and rank == 0 and world == 1 and not args.no_validate and not args.profile_only:
         vleg = validate_leg(model, dev, args.validate_patients)
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and not args.profile_only:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1 and not args.profile_only:
         cpu = cpu_baseline(model.state_dict(), full_sample=not args.no_cpu_full_sample)   # N = 1 only (one host, one CPU timing)
 
     if rank == 0:
@@ -561,7 +595,7 @@ def main():
             "rccl_ranks": comm_ranks if (world > 1 and backend == "nccl") else None,       # only when the all-reduce really ran over RCCL
             "achieved_tflops_end_to_end": round(value * 1000 * FLOP_PER_PATIENT_STEP / 1e12 / world, 2),
             "frac_of_fp32_mfma_peak_end_to_end": round(value * 1000 * FLOP_PER_PATIENT_STEP / 1e12 / world / FP32_MFMA_PEAK_TFLOPS, 4),
-            "roofline": roof, "train": train, "reference_workload": refw, "validate": vleg, "cpu_baseline": cpu,
+            "full": args.full, "roofline": roof, "train": train, "reference_workload": refw, "validate": vleg, "cpu_baseline": cpu,
         }
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -25,6 +25,10 @@ from pathlib import Path
 
 sys.dont_write_bytecode = True
 os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
+# MKL's code path for torch's float32 sqrt / cos / exp and BLAS calls depends on the CPU model unless it is pinned; the
+# fixtures are recorded on the COMPATIBLE path, which every x86 host runs (tests/conftest.py pins the same one).  MKL reads
+# this when torch first calls into it.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
 
 import numpy as np
 import torch

@@ -1,7 +1,7 @@
 #!/bin/bash
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/gap; rm -rf $out; mkdir -p $out
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $out/tr -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train > $out/log.txt 2>&1
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $out/tr -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train > $out/log.txt 2>&1
 python3 - <<'PY'
 import csv, glob
 f = sorted(glob.glob("gpurun_out/gap/tr/**/*kernel_trace.csv", recursive=True))[-1]

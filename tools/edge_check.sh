@@ -1,5 +1,5 @@
-timeout -k 10 200 python bench.py --gpus 1 --steps 1 --warmup 0 --patients 1000 --no-cpu-baseline 2>&1 | tail -1 | cut -c1-300
-timeout -k 10 200 python bench.py --steps 1 --warmup 0 --patients 20000 --no-graph --no-cpu-baseline 2>&1 | tail -1 | cut -c1-200
+timeout -k 10 200 python bench.py --full --gpus 1 --steps 1 --warmup 0 --patients 1000 --no-cpu-baseline 2>&1 | tail -1 | cut -c1-300
+timeout -k 10 200 python bench.py --full --steps 1 --warmup 0 --patients 20000 --no-graph --no-cpu-baseline 2>&1 | tail -1 | cut -c1-200
 timeout -k 10 100 python - <<'PY'
 import torch
 from osteosarcoma_diffusionmodel_amd import BiologyAwareDiffusionModel, SyntheticPatientGenerator

@@ -4,9 +4,9 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/prof_final
 rm -rf $out; mkdir -p $out
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench100k -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-train --no-validate --no-reference-workload --no-mid-size --no-split > $out/bench100k.log 2>&1; echo "bench100k (chain engine) rc=$?"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench100k_graph -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-train --no-validate --no-reference-workload --no-mid-size --no-split --sampler graph > $out/bench100k_graph.log 2>&1; echo "bench100k_graph rc=$?"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_mid -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-train --no-validate --no-reference-workload --no-split > $out/bench_mid.log 2>&1; echo "bench_mid (with the 32 768-patient leg: LDS-resident chain) rc=$?"
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench100k -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-train --no-validate --no-reference-workload --no-mid-size --no-split > $out/bench100k.log 2>&1; echo "bench100k (chain engine) rc=$?"
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench100k_graph -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-train --no-validate --no-reference-workload --no-mid-size --no-split --sampler graph > $out/bench100k_graph.log 2>&1; echo "bench100k_graph rc=$?"
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_mid -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-train --no-validate --no-reference-workload --no-split > $out/bench_mid.log 2>&1; echo "bench_mid (with the 32 768-patient leg: LDS-resident chain) rc=$?"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/train -- python3 bench.py --train-only --train-steps 40 --no-split > $out/train.log 2>&1; echo "train rc=$?"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/train_bf16x3 -- python3 bench.py --train-only --train-steps 40 --train-precision bf16x3 > $out/train_bf16x3.log 2>&1; echo "train (weight gradients on the bf16 pipe) rc=$?"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/validate -- python3 bench.py --validate-only > $out/validate.log 2>&1; echo "validate rc=$?"
