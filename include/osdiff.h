@@ -85,40 +85,55 @@ int osd_destroy(osd_handle *h);
 /* Bind the HIP stream (hipStream_t, e.g. torch.cuda.current_stream().cuda_stream). */
 int osd_set_stream(osd_handle *h, void *hip_stream);
 
-/* Tunables: "sampler" (0 auto, 1 persistent chain kernel wherever the architecture allows it, 2 per-layer kernels),
- * "chunk_rows" / "n_streams" (per-layer path: rows per sampling chunk, chunks in flight), "chain_grid" (cap on the chain
- * kernel's workgroups), "chain_steps_per_launch" (0 = the whole chain in one launch), "chain_stagger" (shader cycles
- * between the starts of the two workgroups of a CU), "train_streams" (1 | 2: weight-gradient leaves on a side stream),
- * "grouped_wgrad" (1: every weight gradient of a backward pass in one grouped launch), "wgrad_mid_flush" (1: the decoder
- * half's weight gradients already mid-pass; always on under data parallel), "fused_gn_bwd" (1: GroupNorm backward inside
- * the dgrad epilogue), "chain_variant" (which chain kernel: 1 the workspace chain, 128-row tiles whose activations
- * pass through a private workspace -- the faster one from 65 536 rows on; 2 the LDS-resident chain, 64 patients per workgroup
- * with every activation in LDS, bit-identical, for architectures whose panels fit -- hidden_dims[0] = 256 = the last block's
- * width --, others fall back to 1; it runs at its full rate from 16 384 rows on; 3 the squad chain, the small-batch kernel: eight
- * workgroups per 32 patients for the whole chain, for models it decomposes ("squad_chain_supported") and batches whose squads are all
- * resident -- 3 072 rows on 256 CUs --, others run what auto would; it agrees with the other engines to fp32 rounding, not bitwise
- * ("squad_panel": its patients per panel, 0 auto = 16 up to 1 024 rows and 32 above, or 16 / 32; "last_squad_panel" reads back);
- * 0 auto: 1 from 65 536 rows on, 2 from 10 240 rows on, 3 for resident batches when "input_splitk" != 0), "dual_dgrad" / "train_ksplit" /
- * "train_input_splitk" (training-step experiments), "train_squad" (from 2 048 rows on: 2, the default, runs the ten
- * Linear+GroupNorm+SiLU layers of a training forward pass as one launch of squads, csrc/train_squad.h, and the dgrad chain of the backward
- * pass as another, csrc/train_squad_bwd.h -- the backward one in single-process steps only: bucket events or a mid-pass flush keep the
- * per-layer dgrads --; 1: the forward only; 0: per-layer launches), "cond_bwd_fused" (1, the default: the conditioning branch's backward
- * below h0 -- time-table scatter, two 64-wide dgrads, SiLU backward, the first embedding Linear's weight gradient -- as one launch,
- * k_cond_bwd in csrc/k_train.hip, for hidden_dims[0] <= 256 and a multiple of 32; 0: five launches),
- * "input_splitk" (the small-batch mode of sampling: 0 off --
- * the default: a row's result does not depend on the batch it is in, bit for bit --, -1 auto, n > 0 slices: small batches run
- * input_proj and the deep layers split over K, or, where chain_variant 3 applies, the squad chain; another fp32 summation order,
- * chain tolerance against the default).  Auto sampler: the chain kernel when the batch has at least as many 128-row tiles as the device
- * holds resident workgroups (65 536 rows on an MI355X) or falls into the LDS-resident kernel's window (above), and the model is
- * in eval mode; else the per-layer kernels. */
+/* Options: name -- accepted values (default) -- meaning.  osd_get_option reads each of them back.
+ *
+ * "sampler"                -- 0 | 1 | 2 (0) -- engine of the reverse chain: 0 auto (the chain kernel when the batch has at least as
+ *                             many 128-row tiles as the device holds resident workgroups -- 65 536 rows on an MI355X -- or falls
+ *                             into the window of the LDS-resident or squad chain, see "chain_variant", and the model is in eval
+ *                             mode; else the per-layer kernels), 1 the persistent chain kernel wherever the architecture allows
+ *                             it, 2 the per-layer kernels.
+ * "chunk_rows"             -- >= 1 (65 536) -- per-layer path: rows per sampling chunk.
+ * "n_streams"              -- 1..8 (2) -- per-layer path: chunks in flight.
+ * "chain_variant"          -- 0..3 (0) -- which chain kernel: 1 the workspace chain, 128-row tiles whose activations pass through a
+ *                             private workspace (the faster one from 65 536 rows on); 2 the LDS-resident chain, 64 patients per
+ *                             workgroup with every activation in LDS, bit-identical, for architectures whose panels fit
+ *                             (hidden_dims[0] = 256 = the last block's width; others fall back to 1), at its full rate from 16 384
+ *                             rows on; 3 the squad chain, the small-batch kernel: eight workgroups per 32 patients for the whole
+ *                             chain, for models it decomposes ("squad_chain_supported") and batches whose squads are all resident
+ *                             (3 072 rows on 256 CUs), others run what auto would; it agrees with the other engines to fp32
+ *                             rounding, not bitwise; 0 auto: 1 from 65 536 rows on, 2 from 10 240 rows on, 3 for resident batches
+ *                             when "input_splitk" != 0.
+ * "squad_panel"            -- 0 | 16 | 32 (0) -- patients per panel of the squad chain: 0 auto (16 up to 1 024 rows, 32 above).
+ * "chain_grid"             -- 0..65 536 (0) -- cap on the chain kernel's workgroups; 0 = min(row tiles, resident slots).
+ * "chain_steps_per_launch" -- >= 0 (0) -- steps of the chain per launch; 0 = the whole chain in one launch.
+ * "chain_stagger"          -- 0..1e8 (30 000) -- shader cycles between the starts of the two workgroups of a CU; 0 = off.
+ * "chain_spin_budget"      -- >= 0 (500 000 000 = 5 s) -- ticks of the 100 MHz s_memrealtime counter a dependency wait inside the
+ *                             chain kernel may take.
+ * "chain_wall_budget_ms"   -- >= 0 (0) -- host-side budget of a synchronous chain; 0 = 10 x the estimated run time + 2 s.
+ * "input_splitk"           -- -1..64 (0) -- the small-batch mode of sampling: 0 off (a row's result does not depend on the batch it
+ *                             is in, bit for bit), -1 auto, n > 0 slices: small batches run input_proj and the deep layers split
+ *                             over K, or, where chain_variant 3 applies, the squad chain; another fp32 summation order, chain
+ *                             tolerance against the default.
+ * "precision"              -- 0 | 1 (0) -- 0 fp32 MFMA (the reference's arithmetic); 1 bf16x3 split on the bf16 matrix pipe (fp32
+ *                             accuracy) for eval-mode sampling / forward of 256 / 512 wide trunks, OSD_EUNSUPPORTED elsewhere.
+ * "train_streams"          -- 1 | 2 (2) -- 2: the weight-gradient leaves of a backward pass on a side stream; 1: one stream.
+ * "train_squad"            -- 0..2 (2) -- from 2 048 rows on: 2 runs the ten Linear+GroupNorm+SiLU layers of a training forward pass
+ *                             as one launch of squads (csrc/train_squad.h) and the dgrad chain of the backward pass as another
+ *                             (csrc/train_squad_bwd.h; single-process steps only: bucket events keep the per-layer dgrads);
+ *                             1 the forward only; 0 per-layer launches.
+ * "cond_bwd_fused"         -- 0 | 1 (1) -- 1: the conditioning branch's backward below h0 (time-table scatter, two 64-wide dgrads,
+ *                             SiLU backward, the first embedding Linear's weight gradient) as one launch, k_cond_bwd in
+ *                             csrc/k_train.hip, for hidden_dims[0] <= 256 and a multiple of 32; 0: five launches.
+ *
+ * Any other name: OSD_EINVAL. */
 int osd_set_option(osd_handle *h, const char *name, int64_t value);
 
-/* Reads an option back, or one of the read-only counters "chain_fallbacks" (chains that gave up -- see osd_sample_chain --
- * and were re-run on the per-layer kernels), "last_engine" (0 per-layer kernels, 1 chain kernel), "last_chain_variant" (1 | 2 | 3,
- * the chain kernel that ran last), "panel_chain_supported" / "squad_chain_supported" (1 when "chain_variant" 2 / 3 applies to this
- * model).  Further options:
- * "chain_spin_budget" (ticks of the 100 MHz s_memrealtime counter a dependency wait inside the chain kernel may take, default
- * 5 s), "chain_wall_budget_ms" (host-side budget of a synchronous chain; 0 = 10 x the estimated run time + 2 s). */
+/* Reads an option back (see osd_set_option), or one of the read-only counters: "chain_fallbacks" (chains that gave up -- see
+ * osd_sample_chain -- and were re-run on the per-layer kernels), "last_engine" (0 per-layer kernels, 1 chain kernel),
+ * "last_chain_variant" (1 | 2 | 3, the chain kernel that ran last), "last_squad_panel" (patients per panel of the squad chain
+ * that ran last), "last_precision" (0 | 1, what the most recent forward / p_sample / sample computed in), "split_supported"
+ * (1 when "precision" 1 applies to this model), "panel_chain_supported" / "squad_chain_supported" (1 when "chain_variant"
+ * 2 / 3 applies to this model).  Any other name: OSD_EINVAL. */
 int osd_get_option(osd_handle *h, const char *name, int64_t *value);
 
 /* Schedule + time-embedding tables, computed by the host with the reference's own

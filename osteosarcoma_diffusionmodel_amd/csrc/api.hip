@@ -4,7 +4,6 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
-#include <stdlib.h>
 #include <algorithm>
 #include <new>
 #include "handle.h"
@@ -26,14 +25,6 @@ void set_error(const char* fmt, ...) {
 std::vector<KernelReg>& kernel_registry() {
   static std::vector<KernelReg> r;
   return r;
-}
-int persist_mode() {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("OSD_PERSIST");
-    mode = e ? atoi(e) : 0;       // measured: with two chunks in flight the one-tile-per-workgroup grid is faster
-  }
-  return mode;
 }
 hipError_t prepare_kernels() {
   for (const KernelReg& k : kernel_registry()) {
@@ -332,6 +323,61 @@ int sanitize_t(osd_handle* h, hipStream_t s, const int32_t* t_index, int64_t n, 
   return OSD_OK;
 }
 
+// ---- osd_set_option / osd_get_option (include/osdiff.h documents each option) ----
+template <class T, T osd_handle::*F> static void store_field(osd_handle* h, int64_t v) { h->*F = (T)v; }
+template <class T, T osd_handle::*F> static int64_t load_field(osd_handle* h) { return (int64_t)(h->*F); }
+#define OSD_FIELD(f) &store_field<decltype(osd_handle::f), &osd_handle::f>, &load_field<decltype(osd_handle::f), &osd_handle::f>
+
+// A settable option: its values are [lo, hi], or -- n_only > 0 -- those of only[] within it; `err` is the message for any other
+struct Option {
+  const char* name;
+  void (*store)(osd_handle*, int64_t);
+  int64_t (*load)(osd_handle*);
+  int64_t lo, hi;
+  const char* err;
+  int n_only;
+  int64_t only[3];
+};
+static const Option OPTIONS[] = {
+    {"chunk_rows", OSD_FIELD(chunk_rows), 1, INT64_MAX, "chunk_rows must be >= 1"},
+    {"n_streams", OSD_FIELD(n_streams), 1, 8, "n_streams must be in [1,8]"},
+    {"sampler", OSD_FIELD(sampler), 0, 2, "sampler must be 0 (auto), 1 (chain kernel) or 2 (per-layer kernels)"},
+    {"train_squad", OSD_FIELD(train_squad), 0, 2,
+     "train_squad must be 0 (per-layer launches), 1 (forward trunk as squads) or 2 (forward and the dgrad chain)"},
+    {"squad_panel", OSD_FIELD(squad_panel), 0, 32, "squad_panel must be 0 (auto), 16 or 32", 3, {0, 16, 32}},
+    {"chain_variant", OSD_FIELD(chain_variant), 0, 3,
+     "chain_variant must be 0 (auto), 1 (workspace chain), 2 (LDS-resident chain) or 3 (squad chain)"},
+    {"precision", OSD_FIELD(precision), 0, 1, "precision must be 0 (fp32) or 1 (bf16x3 split)"},
+    {"chain_grid", OSD_FIELD(chain_grid), 0, 65536, "chain_grid must be in [0,65536]"},
+    {"input_splitk", OSD_FIELD(input_splitk), -1, 64, "input_splitk must be in [-1,64]"},
+    {"cond_bwd_fused", OSD_FIELD(cond_bwd_fused), 0, 1, "cond_bwd_fused must be 0 or 1"},
+    {"chain_spin_budget", OSD_FIELD(chain_spin_budget), 0, INT64_MAX, "chain_spin_budget must be >= 0"},
+    {"chain_wall_budget_ms", OSD_FIELD(chain_wall_budget_ms), 0, INT64_MAX, "chain_wall_budget_ms must be >= 0"},
+    {"chain_steps_per_launch", OSD_FIELD(chain_steps_per_launch), 0, INT64_MAX, "chain_steps_per_launch must be >= 0"},
+    {"chain_stagger", OSD_FIELD(chain_stagger), 0, 100000000, "chain_stagger must be in [0,1e8] cycles"},
+    {"train_streams", OSD_FIELD(train_streams), 1, 2, "train_streams must be 1 or 2"},
+};
+#undef OSD_FIELD
+
+static const Option* find_option(const char* name) {
+  for (const Option& o : OPTIONS)
+    if (!strcmp(name, o.name)) return &o;
+  return nullptr;
+}
+
+// read-only counters (osd_get_option only)
+struct Counter { const char* name; int64_t (*load)(osd_handle*); };
+static const Counter COUNTERS[] = {
+    {"last_precision", [](osd_handle* h) -> int64_t { return h->last_precision; }},
+    {"split_supported", [](osd_handle* h) -> int64_t { return split_supported(h->arch); }},
+    {"chain_fallbacks", [](osd_handle* h) -> int64_t { return h->chain_fallbacks; }},
+    {"last_engine", [](osd_handle* h) -> int64_t { return h->last_engine; }},
+    {"last_chain_variant", [](osd_handle* h) -> int64_t { return h->last_chain_variant; }},
+    {"panel_chain_supported", [](osd_handle* h) -> int64_t { return panel_chain_supported(h); }},
+    {"squad_chain_supported", [](osd_handle* h) -> int64_t { return squad_chain_supported(h); }},
+    {"last_squad_panel", [](osd_handle* h) -> int64_t { return h->last_squad_rp; }},
+};
+
 }  // namespace osd
 
 using namespace osd;
@@ -397,14 +443,6 @@ int osd_create(const osd_config* cfg, osd_handle** out) {
   if (!h) { set_error("out of host memory"); return OSD_ENOMEM; }
   h->cfg = *cfg;
   h->arch = a;
-  if (const char* e = getenv("OSD_GROUPED_WGRAD")) h->grouped_wgrad = atoi(e) != 0;      // A/B knobs, see osd_set_option
-  if (const char* e = getenv("OSD_WGRAD_MID_FLUSH")) h->wgrad_mid_flush = atoi(e) != 0;
-  if (const char* e = getenv("OSD_FUSED_GN_BWD")) h->fused_gn_bwd = atoi(e) != 0;
-  if (const char* e = getenv("OSD_TRAIN_INPUT_SPLITK")) h->train_input_splitk = atoi(e);
-  if (const char* e = getenv("OSD_DUAL_DGRAD")) h->dual_dgrad = atoi(e) != 0;
-  if (const char* e = getenv("OSD_TRAIN_KSPLIT")) h->train_ksplit = atoi(e) != 0;
-  if (const char* e = getenv("OSD_COND_BWD_FUSED")) h->cond_bwd_fused = atoi(e) != 0;
-  if (const char* e = getenv("OSD_TWO_STREAM_BWD")) h->two_stream_bwd = atoi(e) != 0;
   const int rc = create_device_state(h);
   if (rc != OSD_OK) {                 // nothing of a half-built handle survives (osd_destroy frees what was allocated)
     osd_destroy(h);
@@ -458,131 +496,24 @@ int osd_set_stream(osd_handle* h, void* hip_stream) {
 
 int osd_set_option(osd_handle* h, const char* name, int64_t value) {
   if (!h || !name) { set_error("null argument"); return OSD_EINVAL; }
-  if (!strcmp(name, "chunk_rows")) {
-    if (value < 1) { set_error("chunk_rows must be >= 1"); return OSD_EINVAL; }
-    h->chunk_rows = value;
-    return OSD_OK;
+  const Option* o = find_option(name);
+  if (!o) { set_error("unknown option '%s'", name); return OSD_EINVAL; }
+  bool ok = value >= o->lo && value <= o->hi;
+  if (ok && o->n_only) ok = std::find(o->only, o->only + o->n_only, value) != o->only + o->n_only;
+  if (!ok) { set_error("%s", o->err); return OSD_EINVAL; }
+  if (!strcmp(name, "precision") && value == 1 && !split_supported(h->arch)) {
+    set_error("precision 1 (bf16x3 split) covers trunks of width 256 / 512 only");
+    return OSD_EUNSUPPORTED;
   }
-  if (!strcmp(name, "n_streams")) {
-    if (value < 1 || value > 8) { set_error("n_streams must be in [1,8]"); return OSD_EINVAL; }
-    h->n_streams = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "sampler")) {                 // 0 auto, 1 persistent chain kernel where supported, 2 per-layer kernels
-    if (value < 0 || value > 2) { set_error("sampler must be 0 (auto), 1 (chain kernel) or 2 (per-layer kernels)"); return OSD_EINVAL; }
-    h->sampler = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "train_squad")) {             // from 2 048 rows on: 2 (default) the trunk of a training forward pass AND the dgrad chain each as one launch of squads (train_squad.h, train_squad_bwd.h; the backward one in single-process steps), 1 the forward only, 0 per-layer launches
-    if (value < 0 || value > 2) { set_error("train_squad must be 0 (per-layer launches), 1 (forward trunk as squads) or 2 (forward and the dgrad chain)"); return OSD_EINVAL; }
-    h->train_squad = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "squad_panel")) {             // the squad chain's panel: 0 auto, 16 (chain_squad16.h) wherever its squads fit two per CU, 32 (chain_squad.h)
-    if (value != 0 && value != 16 && value != 32) { set_error("squad_panel must be 0 (auto), 16 or 32"); return OSD_EINVAL; }
-    h->squad_panel = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "chain_variant")) {           // 0 auto, 1 workspace chain (chain.h), 2 LDS-resident chain (chain_panel.h) where the architecture fits
-    if (value < 0 || value > 3) { set_error("chain_variant must be 0 (auto), 1 (workspace chain), 2 (LDS-resident chain) or 3 (squad chain)"); return OSD_EINVAL; }
-    h->chain_variant = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "precision")) {               // 0 fp32 MFMA (default), 1 bf16x3 split: fp32 accuracy on the bf16 matrix pipe (gemm_bf3.h)
-    if (value < 0 || value > 1) { set_error("precision must be 0 (fp32) or 1 (bf16x3 split)"); return OSD_EINVAL; }
-    if (value == 1 && !split_supported(h->arch)) { set_error("precision 1 (bf16x3 split) covers trunks of width 256 / 512 only"); return OSD_EUNSUPPORTED; }
-    h->precision = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "chain_grid")) {
-    if (value < 0 || value > 65536) { set_error("chain_grid must be in [0,65536]"); return OSD_EINVAL; }
-    h->chain_grid = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "input_splitk")) {            // per-layer sampling engine: 0 off (default), -1 auto (batches with < 128 input_proj tiles), n slices
-    if (value < -1 || value > 64) { set_error("input_splitk must be in [-1,64]"); return OSD_EINVAL; }
-    h->input_splitk = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "train_ksplit")) {            // 1: the training forward's GEMMs use two wave groups per workgroup (gemm_glds.h, NG = 2)
-    if (value < 0 || value > 1) { set_error("train_ksplit must be 0 or 1"); return OSD_EINVAL; }
-    h->train_ksplit = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "dual_dgrad")) {
-    if (value < 0 || value > 1) { set_error("dual_dgrad must be 0 or 1"); return OSD_EINVAL; }
-    h->dual_dgrad = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "cond_bwd_fused")) {
-    if (value < 0 || value > 1) { set_error("cond_bwd_fused must be 0 or 1"); return OSD_EINVAL; }
-    h->cond_bwd_fused = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "train_input_splitk")) {
-    if (value < 0 || value > 16) { set_error("train_input_splitk must be in [0,16]"); return OSD_EINVAL; }
-    h->train_input_splitk = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "chain_spin_budget")) {       // s_memrealtime ticks (100 MHz) a dependency wait inside the chain kernel may take
-    if (value < 0) { set_error("chain_spin_budget must be >= 0"); return OSD_EINVAL; }
-    h->chain_spin_budget = (unsigned long long)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "chain_wall_budget_ms")) {    // host-side budget of a synchronous chain; 0 = 10 x the estimated run time + 2 s
-    if (value < 0) { set_error("chain_wall_budget_ms must be >= 0"); return OSD_EINVAL; }
-    h->chain_wall_budget_ms = value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "chain_steps_per_launch")) {
-    if (value < 0) { set_error("chain_steps_per_launch must be >= 0"); return OSD_EINVAL; }
-    h->chain_steps_per_launch = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "chain_stagger")) {
-    if (value < 0 || value > 100000000) { set_error("chain_stagger must be in [0,1e8] cycles"); return OSD_EINVAL; }
-    h->chain_stagger = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "grouped_wgrad")) {           // 1 (default): the weight gradients of a backward pass in two grouped launches
-    if (value < 0 || value > 1) { set_error("grouped_wgrad must be 0 or 1"); return OSD_EINVAL; }
-    h->grouped_wgrad = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "fused_gn_bwd")) {
-    if (value < 0 || value > 1) { set_error("fused_gn_bwd must be 0 or 1"); return OSD_EINVAL; }
-    h->fused_gn_bwd = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "wgrad_mid_flush")) {         // 1: the decoder + bottleneck weight gradients are launched (one workgroup per CU)
-    if (value < 0 || value > 1) { set_error("wgrad_mid_flush must be 0 or 1"); return OSD_EINVAL; }    // while the encoder half of backward runs
-    h->wgrad_mid_flush = (int)value;
-    return OSD_OK;
-  }
-  if (!strcmp(name, "train_streams")) {
-    if (value < 1 || value > 2) { set_error("train_streams must be 1 or 2"); return OSD_EINVAL; }
-    h->two_stream_bwd = value == 2;
-    return OSD_OK;
-  }
-  set_error("unknown option '%s'", name);
-  return OSD_EINVAL;
+  o->store(h, value);
+  return OSD_OK;
 }
 
 int osd_get_option(osd_handle* h, const char* name, int64_t* value) {
   if (!h || !name || !value) { set_error("null argument"); return OSD_EINVAL; }
-  struct { const char* n; int64_t v; } tab[] = {
-      {"chunk_rows", h->chunk_rows}, {"n_streams", h->n_streams}, {"sampler", h->sampler}, {"chain_grid", h->chain_grid},
-      {"chain_steps_per_launch", h->chain_steps_per_launch}, {"chain_stagger", h->chain_stagger},
-      {"chain_spin_budget", (int64_t)h->chain_spin_budget}, {"chain_wall_budget_ms", h->chain_wall_budget_ms},
-      {"grouped_wgrad", h->grouped_wgrad}, {"fused_gn_bwd", h->fused_gn_bwd}, {"wgrad_mid_flush", h->wgrad_mid_flush},
-      {"input_splitk", h->input_splitk}, {"train_streams", h->two_stream_bwd ? 2 : 1}, 
-      // read-only counters
-      {"precision", h->precision}, {"last_precision", h->last_precision}, {"split_supported", split_supported(h->arch) ? 1 : 0},
-      {"chain_fallbacks", h->chain_fallbacks}, {"last_engine", h->last_engine},
-      {"chain_variant", h->chain_variant}, {"last_chain_variant", h->last_chain_variant}, {"panel_chain_supported", panel_chain_supported(h) ? 1 : 0},
-      {"squad_chain_supported", squad_chain_supported(h) ? 1 : 0}, {"last_squad_panel", h->last_squad_rp}, {"squad_panel", h->squad_panel}, {"train_squad", h->train_squad}, {"cond_bwd_fused", h->cond_bwd_fused}};
-  for (const auto& e : tab)
-    if (!strcmp(name, e.n)) { *value = e.v; return OSD_OK; }
+  if (const Option* o = find_option(name)) { *value = o->load(h); return OSD_OK; }
+  for (const Counter& c : COUNTERS)
+    if (!strcmp(name, c.name)) { *value = c.load(h); return OSD_OK; }
   set_error("unknown option '%s'", name);
   return OSD_EINVAL;
 }
@@ -743,12 +674,12 @@ static int chain_chunk(osd_handle* h, Slot& sl, const float* cond, int64_t n_tot
   const int64_t need_pad = (need + 63) / 64 * 64;
   // small batches: input_proj split-K (k_fused.hip) -- few output tiles, each a long sequential K loop
   int in_slices = 0;
-  static const int64_t splitk_target = [] { const char* e = getenv("OSD_INPUT_SPLITK_TARGET"); return e ? atol(e) : 768L; }();
+  constexpr int64_t INPUT_SPLITK_TARGET = 768;      // workgroups the auto mode (-1) aims at: slices = this / output tiles
   {
     const int64_t tiles = (int64_t)((a.H0 + 63) / 64) * ((m + 63) / 64);
     if (h->input_splitk > 0 && !h->splitk_suspended) in_slices = h->input_splitk;
     else if (h->input_splitk < 0 && !h->splitk_suspended && ldx >= 1024 && tiles < 384)      // fewer tiles than 1.5 per CU
-      in_slices = (int)std::min<int64_t>(16, std::max<int64_t>(2, (splitk_target + tiles / 2) / tiles));
+      in_slices = (int)std::min<int64_t>(16, std::max<int64_t>(2, (INPUT_SPLITK_TARGET + tiles / 2) / tiles));
     in_slices = std::min(in_slices, ldx / 128);
     if (in_slices < 2) in_slices = 0;
   }

@@ -98,11 +98,8 @@ struct osd_handle {
   // whose rows are padded to Dp = roundup(D, 4) floats, so that every operand is 16-byte aligned and the LDS-DMA / FAST tile code
   // and the chain kernel apply; the pad columns carry finite values that only ever meet zero weights
   int Dp = 0;
-  int train_ksplit = 1;              // osd_set_option("train_ksplit", 0|1): two wave groups per workgroup in the training forward's GEMMs (gemm_glds.h)
-  int dual_dgrad = 1;                // osd_set_option("dual_dgrad", 0|1): a decoder block's two input dgrads in one launch (k_gnbwd.hip)
   int cond_bwd_fused = 1;            // osd_set_option("cond_bwd_fused", 0|1): the conditioning branch's backward below h0 as one launch (k_cond_bwd, k_train.hip)
   bool sq_wpk_t_fresh = false;       // the backward squads' transposed weight copies were packed by this step's forward launch (chain_squad.hip)
-  int train_input_splitk = 0;        // osd_set_option("train_input_splitk"): K slices of input_proj in the training forward (0 / 1 = single pass)
   bool splitk_suspended = false;     // a chain-kernel fallback re-run in progress: no split-K (bit-identical to the chain kernel)
   int input_splitk = 0;              // osd_set_option("input_splitk"): 0 off (default: a row's result does not depend on how rows are chunked / sharded),
                                      // -1 auto (chunks with < 128 input_proj tiles), n = slices
@@ -125,7 +122,7 @@ struct osd_handle {
   // weight-gradient side stream of the backward pass and its fork/join events
   hipStream_t wgrad_stream = nullptr;
   std::vector<hipEvent_t> ev_pool;
-  int two_stream_bwd = 1;            // osd_set_option("train_streams", 1|2)
+  int train_streams = 2;             // osd_set_option("train_streams", 1|2): 2 = weight-gradient leaves of the backward pass on a side stream
   osd::BatchSrc batch_src{}; bool have_batch_src = false;      // osd_train_batch_source: one-shot source of the next training call's rows
   int64_t saved_rows = -1;           // rows of the last osd_denoiser_forward_train whose activations are still in the arena
   // constraint losses (osd_set_constraints); parts_dev = (mse, L_pc, L_me) of the last training call
@@ -133,9 +130,6 @@ struct osd_handle {
   double w_pathway = 0.0, w_mutexpr = 0.0;
   float* parts_dev = nullptr;
   std::vector<void*> wg_plans;       // grouped weight-gradient launches (wgrad_group.hip): one cached work list per flush point
-  int fused_gn_bwd = 1;              // osd_set_option("fused_gn_bwd", 0|1): GroupNorm backward inside the dgrad epilogue (group widths 32 / 64)
-  int wgrad_mid_flush = 0;           // osd_set_option("wgrad_mid_flush", 0|1): also launch the decoder-half weight gradients mid-pass
-  int grouped_wgrad = 1;             // osd_set_option("grouped_wgrad", 0|1)
   // persistent reverse-chain kernel (chain.h / chain.hip)
   int sampler = 0;                   // osd_set_option("sampler"): 0 auto, 1 chain kernel whenever the architecture allows, 2 per-layer kernels
   int chain_grid = 0;                // 0 = min(row tiles, resident slots); > 0 caps the workgroup count (tests: force cross-workgroup hand-offs)

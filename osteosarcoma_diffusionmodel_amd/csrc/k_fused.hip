@@ -1,5 +1,4 @@
 // k_fused.hip -- input_proj (+t_emb +c_proj), output_proj (+posterior), output_proj (+MSE).
-#include <stdlib.h>
 #include "kernels.h"
 #include "launch.h"
 
@@ -142,9 +141,9 @@ hipError_t launch_gn_silu_splitk(hipStream_t s, const GemmArgs& g, const GnArgs&
 
 hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const EpiPosterior::Args& a) {
   // below one full round of 128 x 128 tiles (512 workgroup slots) the 64 x 128 tile spreads the same work over twice the workgroups
-  static const long big_from = [] { const char* e = getenv("OSD_POST_BIG_FROM"); return e ? atol(e) : 512L; }();
+  constexpr long POST_BIG_FROM = 512;
   const long big_tiles = (long)((g.F + 127) / 128) * ((g.P + 127) / 128);
-  if (big_tiles >= big_from) return launch_gemm<TileBig, true, true, EpiPosterior>(s, g, a);
+  if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosterior>(s, g, a);
   return launch_gemm<TileSmall, true, true, EpiPosterior>(s, g, a);
 }
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a) {

@@ -98,30 +98,22 @@ struct GldsRegistrar {
 template <class T, class Epi, int NG>
 GldsRegistrar<T, Epi, NG> GldsRegistrar<T, Epi, NG>::instance;
 
-int persist_mode();   // OSD_PERSIST env: 0 (default) one tile per workgroup; 1 / 2: persistent tile walk on 512 / 256 workgroups
-
 template <class T, class Epi>
 hipError_t launch_gemm_glds(hipStream_t s, const GemmArgs& g0, const typename Epi::Args& ea) {
   (void)&GldsRegistrar<T, Epi>::instance;
   GemmArgs g = g0;
-  int grid = gemm_grid(g.F, g.P, T::BF, T::BP);
+  g.persist = 0;      // one tile per workgroup (measured: with two chunks in flight it beats the kernel's persistent tile walk)
+  const int grid = gemm_grid(g.F, g.P, T::BF, T::BP);
   if constexpr (epi_ksplit2<Epi>::value && T::BF * T::BP <= 64 * 128) {
     // two wave groups: only worth it when the launch has about one tile per CU and a LONG K loop to split -- measured at the
     // training batch: input_proj (63 K steps) 58 -> 49 us, the 1024-deep decoder layer 32 -> 28 us, but 8-16 K steps +-0 (the
     // second group's prologue, the hand-over through LDS and its barrier cost what the shorter loop saves)
     if (g.ksplit && grid <= 320 && g.K >= 32 * BK) {
       (void)&GldsRegistrar<T, Epi, 2>::instance;
-      g.persist = 0;
       hipLaunchKernelGGL((gemm_glds_kernel<T, Epi, 2>), dim3(grid), dim3(2 * NTHREADS), 2 * GldsTile<T>::LDS_BYTES, s, g, ea);
       return hipGetLastError();
     }
   }
-  // persistent patient-tile walk: 512 workgroups (2 per CU), each keeping one feature tile
-  const int nft = (g.F + T::BF - 1) / T::BF;
-  g.persist = 0;
-  const int pm = persist_mode();          // 1: 512 workgroups, 2: 256 (leaves room for a second stream's kernel)
-  const int pgrid = pm == 2 ? 256 : 512;
-  if (pm && !g.tri && grid > pgrid && nft <= pgrid / 8 && (pgrid / 8) % nft == 0) { g.persist = 1; grid = pgrid; }
   hipLaunchKernelGGL((gemm_glds_kernel<T, Epi>), dim3(grid), dim3(NTHREADS), GldsTile<T>::LDS_BYTES, s, g, ea);
   return hipGetLastError();
 }

@@ -2,7 +2,6 @@
 // fused forward + backward of the eps-prediction MSE loss, mixup lives in api.hip,
 // clip_grad_norm_ + AdamW over flat buffers.
 #include <math.h>
-#include <stdlib.h>
 #include <algorithm>
 #include "handle.h"
 #include "kernels.h"
@@ -100,8 +99,8 @@ static hipError_t wgrad(hipStream_t s, const TrainWs& w, const float* x, int ldx
   GemmArgs g{};
   g.A = x; g.lda = ldx; g.B0 = gz; g.ldb0 = ldg; g.K0 = (int)rows; g.F = kin; g.P = nout; g.K = (int)rows;
   const long tiles = (long)((kin + 63) / 64) * ((nout + 63) / 64);
-  static const int target = [] { const char* e = getenv("OSD_WGRAD_TARGET"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
-  int slices = (int)((target + tiles - 1) / tiles);
+  constexpr int WGRAD_TARGET = 512;
+  int slices = (int)((WGRAD_TARGET + tiles - 1) / tiles);
   const int max_slices = (int)((rows + 127) / 128);
   if (slices > max_slices) slices = max_slices;
   const int64_t numel = (int64_t)nout * kin;
@@ -193,7 +192,7 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
   // lower-priority side stream that fills the CUs the small dgrad launches leave idle.  fork() orders the side
   // stream behind what the main stream has produced so far; the side stream owns the slab workspace.
   hipStream_t s2 = s;
-  if (h->two_stream_bwd) OSD_TRY(side_stream(h, &s2));
+  if (h->train_streams == 2) OSD_TRY(side_stream(h, &s2));
   size_t ev_used = 0;
   auto next_event = [&](hipEvent_t* out) -> int {
     if (ev_used == h->ev_pool.size()) {
@@ -216,14 +215,9 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
   // bottleneck half of the backward pass, and at its end) instead of ~17 launches of a few tiles each.  A gradient bucket is
   // final once the flush that carries its weight gradients has been enqueued, so bucket events are recorded there.
   std::vector<WgPending> pend;
-  std::vector<WgPending>* grp = h->grouped_wgrad ? &pend : nullptr;
   int ev = 0, ev_closed = 0, n_flush = 0;
   bool s2_slabs_busy = false;          // an immediate split-K weight gradient on the side stream may still be using W.slabs
-  auto record = [&]() -> int {        // bucket complete up to the pending weight gradients
-    ++ev_closed;
-    if (!grp) { if (events) OSD_HIP(hipEventRecord((hipEvent_t)events[ev], s2)); ++ev; }
-    return OSD_OK;
-  };
+  auto record = [&] { ++ev_closed; };  // bucket complete up to the pending weight gradients
   // a weight gradient: deferred to the next grouped launch when eligible, else launched now on the side stream (which then
   // has to see what the main stream produced: each fork costs the main stream a few microseconds, so only then)
   // b0..b2: bias gradients equal to the column sums of gz (the Linear's own bias and tensors that share it); they ride along
@@ -234,7 +228,7 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
   auto wg = [&](const float* x, int ldx, int kin, const float* gz, int ldg, int nout, int64_t rows, float* dw, int lddw,
                 float* b0 = nullptr, float* b1 = nullptr, float* b2 = nullptr) -> int {
     const WgPending wp{x, ldx, kin, gz, ldg, nout, rows, dw, lddw, {b0, b1, b2}};
-    if (grp && kin >= 16 && wgrad_group_ok(wp)) { pend.push_back(wp); return OSD_OK; }
+    if (kin >= 16 && wgrad_group_ok(wp)) { pend.push_back(wp); return OSD_OK; }
     const bool small = small_wgrad_ok(kin, nout, lddw);
     if (small && !events) {            // a 5 us kernel whose inputs are on the main stream: run it there (no fork, no event)
       OSD_HIP(wgrad(s, W, x, ldx, kin, gz, ldg, nout, rows, dw, lddw, b0));
@@ -255,10 +249,9 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
   // stream (a full-width launch starved it: a 16 us dgrad took 104 us)
   hipEvent_t mid_done = nullptr;       // the side stream is through with the slab workspace
   auto flush_mid = [&]() -> int {
-    if (!grp) return OSD_OK;
     OSD_TRY(fork());                  // the side stream sees every gz produced so far
-    static const int mid_cap = [] { const char* e = getenv("OSD_WGRAD_MID_CAP"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();
-    OSD_TRY(wgrad_group_flush(h, s2, n_flush++, pend, W.slabs, W.slab_floats, s2 != s ? mid_cap : 0));
+    constexpr int WGRAD_MID_CAP = 256;
+    OSD_TRY(wgrad_group_flush(h, s2, n_flush++, pend, W.slabs, W.slab_floats, s2 != s ? WGRAD_MID_CAP : 0));
     pend.clear();
     for (; ev < ev_closed; ++ev)
       if (events) OSD_HIP(hipEventRecord((hipEvent_t)events[ev], s2));
@@ -266,12 +259,11 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
     return OSD_OK;
   };
   // GroupNorm backward: inside the epilogue of the dgrad that produces the layer's upstream gradient (group widths 32 / 64), or
-  // -- option off, other widths -- as its own pass between the GEMMs
-  bool fuse = h->fused_gn_bwd != 0;
-  fuse = fuse && grp != nullptr;       // the fused path's bias / affine gradients ride with the grouped launches
+  // -- other widths -- as its own pass between the GEMMs
+  bool fuse = true;
   for (const LayerDesc& l : a.layers) fuse = fuse && dgrad_gnbwd_supported(l.gw);
   // single-GPU steps: the dgrad chain between the first launch (output_proj) and the last (into h0) as one launch of squads
-  const bool squad_bwd = fuse && !events && !h->wgrad_mid_flush && W.sq_gact && loss_poison && h->train_squad >= 2 && train_squad_ok(h, n);
+  const bool squad_bwd = fuse && !events && W.sq_gact && loss_poison && h->train_squad >= 2 && train_squad_ok(h, n);
   const float keep_scale = (float)(1.0 / (1.0 - (double)h->cfg.dropout_p));
   std::vector<GnColItem> cols;
   // d gamma / d beta of the layers whose backward ran in a dgrad epilogue: memory-bound leaves, one launch per call.  They
@@ -298,7 +290,7 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
     if (s2 != s) {
       if (!cols.empty()) { OSD_TRY(fork()); OSD_TRY(side_leaves(s2)); }
       if (mid_done) OSD_HIP(hipStreamWaitEvent(s, mid_done, 0));     // slab workspace handed back by the mid-pass flush
-      if (s2_slabs_busy && grp && !pend.empty()) {                    // ... and by immediate split-K weight gradients (e.g. the
+      if (s2_slabs_busy && !pend.empty()) {                           // ... and by immediate split-K weight gradients (e.g. the
         hipEvent_t e;                                                 // ConditionalEmbedding's first Linear at cond_dim 8 or 12)
         OSD_TRY(next_event(&e));
         OSD_HIP(hipEventRecord(e, s2));
@@ -308,10 +300,8 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
     } else {
       OSD_TRY(side_leaves(s));
     }
-    if (grp) {
-      OSD_TRY(wgrad_group_flush(h, s, n_flush++, pend, W.slabs, W.slab_floats, 0));
-      pend.clear();
-    }
+    OSD_TRY(wgrad_group_flush(h, s, n_flush++, pend, W.slabs, W.slab_floats, 0));
+    pend.clear();
     if (s2 != s) {
       hipEvent_t e;
       OSD_TRY(next_event(&e));
@@ -334,7 +324,7 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
     }
     GemmArgs g{};
     g.A = w; g.lda = ldw; g.B0 = gz_next; g.ldb0 = ldg; g.K0 = nout; g.F = kin; g.P = (int)n; g.K = nout;
-    g.ksplit = h->train_ksplit != 0;       // launch.h: two wave groups where a launch has ~one tile per CU and >= 32 K tiles (the first dgrad)
+    g.ksplit = 1;                          // launch.h: two wave groups where a launch has ~one tile per CU and >= 32 K tiles (the first dgrad)
     GnBwdEpi e{};
     e.z = z; e.ldz = kin; e.stats = stats; e.gamma = h->params[ln.gamma]; e.beta = h->params[ln.beta];
     e.gz = gz_out; e.ldg = kin; e.gy = gy_buf; e.ldy = kin; e.accumulate = accumulate ? 1 : 0;
@@ -343,7 +333,7 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
     e.seed = seed; e.row_offset = roff; e.step = 0; e.tag = TAG_DROPOUT + (uint32_t)blk;
     {
       bool launched = false;
-      if (w_skip && h->dual_dgrad) {
+      if (w_skip) {
         // the skip connection's share of the same gz (plain dX = gz W_skip) rides in the same launch
         GemmArgs g2{};
         g2.A = w_skip; g2.lda = ldw; g2.B0 = gz_next; g2.ldb0 = ldg; g2.K0 = nout; g2.F = kin_skip; g2.P = (int)n; g2.K = nout;
@@ -364,7 +354,7 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
   };
   // output_proj
   OSD_TRY(wg(W.f.out[last], Hl, Hl, d_out, D, D, n, grads[pm.out_w], Hl, grads[pm.out_b]));
-  OSD_TRY(record());
+  record();
   if (fuse) {
     const LayerDesc& lz = a.layers[2 * last + 1];
     OSD_TRY(dgrad_fused(h->params[pm.out_w], Hl, Hl, d_out, D, D, lz, W.f.z2[last], W.f.st2[last], W.g_z2[last], W.g_out[last], false, false, last));
@@ -394,8 +384,8 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
                           nullptr, 0, nullptr, nullptr, !squad_bwd));
       OSD_TRY(wg(xin, l1.K1, l1.K1, W.g_z1[b], C, C, n, grads[l1.w], Kt, grads[l1.b]));
       if (l1.K2 > 0) OSD_TRY(wg(W.f.out[skip_block], l1.K2, l1.K2, W.g_z1[b], C, C, n, grads[l1.w] + l1.K1, Kt));
-      OSD_TRY(record());
-      if (b == a.n_enc && (h->wgrad_mid_flush || events)) OSD_TRY(flush_all(true));
+      record();
+      if (b == a.n_enc && events) OSD_TRY(flush_all(true));
       if (b == 0) {
         if (!squad_bwd) OSD_TRY(dgrad_plain(h->params[l1.w], Kt, l1.K1, W.g_z1[b], C, C, gdst, l1.K1));
       } else {
@@ -427,8 +417,8 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
     OSD_HIP(launch_gn_silu_bwd(s, l1.gw, gb));
     OSD_TRY(wg(xin, l1.K1, l1.K1, W.g_z1[b], C, C, n, grads[l1.w], Kt));
     if (l1.K2 > 0) OSD_TRY(wg(W.f.out[skip_block], l1.K2, l1.K2, W.g_z1[b], C, C, n, grads[l1.w] + l1.K1, Kt));
-    OSD_TRY(record());
-    if (b == a.n_enc && (h->wgrad_mid_flush || events)) OSD_TRY(flush_all(true));    // decoder blocks + bottleneck done: first half of the weight gradients
+    record();
+    if (b == a.n_enc && events) OSD_TRY(flush_all(true));    // decoder blocks + bottleneck done: first half of the weight gradients
     // dgrad into the producer of the main input
     OSD_HIP(dgrad(s, h->params[l1.w], Kt, l1.K1, W.g_z1[b], C, C, n, gdst, l1.K1, acc));
     if (l1.K2 > 0) OSD_HIP(dgrad(s, h->params[l1.w] + l1.K1, Kt, l1.K2, W.g_z1[b], C, C, n, W.g_out[skip_block], l1.K2, false));
@@ -467,7 +457,7 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
     OSD_HIP(launch_silu_bwd(s, W.u0, W.g_ce1, W.g_u, n * 64));
   }
   if (!ce0_fused) OSD_TRY(wg(cond, a.cond_dim, a.cond_dim, W.g_u, 64, 64, n, grads[pm.ce0_w], a.cond_dim, grads[pm.ce0_b]));
-  OSD_TRY(record());
+  record();
   OSD_TRY(flush_all(false));          // ends with the side stream joined: the caller's stream owns every result again
   return OSD_OK;
 }
@@ -543,8 +533,7 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
   // ---- forward (models/diffusion.py:361-377) ----
   // x_t rows are padded to whole K steps with zeros when nothing else reads them with the dense stride: input_proj then takes
   // input_proj.weight as it is (clamped at D) and the per-step packed copy of that weight is not made
-  const bool split_in = h->train_input_splitk > 1 && (int64_t)h->train_input_splitk * n * a.H0 <= w.slab_floats;
-  const bool unpacked = w.xld > D && !split_in;
+  const bool unpacked = w.xld > D;
   // the t_emb table (and, unless input_proj reads the weight itself, its padded copy) follow the current parameters
   OSD_TRY(refresh_derived(h, s, !unpacked));
   const int* t_idx = nullptr;
@@ -565,17 +554,14 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
   OSD_TRY(cond_embed_fwd(h, s, cond, n, w));
   TrainWs& W = w;
   TrunkIn in{};
-  in.x = W.x_t; in.ldx = W.xld; in.kx = unpacked ? W.xld : D; in.a_unpacked = unpacked; in.ksplit = h->train_ksplit != 0;
+  in.x = W.x_t; in.ldx = W.xld; in.kx = unpacked ? W.xld : D; in.a_unpacked = unpacked; in.ksplit = true;
   in.n = n; in.t_index = t_idx; in.train = train; in.save = grads != nullptr;
   in.masks = masks; in.seed = seed; in.row_offset = roff; in.drop_step = 0;
-  // input_proj at the training batch: 256 output tiles of 63 sequential K steps, one workgroup per CU -- optionally K in slices
-  // over more workgroups (k_fused.hip: partial tiles to slabs, then sum + epilogue); the slab workspace is idle during forward
-  if (split_in) { in.in_slabs = W.slabs; in.in_slices = h->train_input_splitk; }
   if (W.sq_act && train_squad_ok(h, n)) {
     in.input_only = true;
     OSD_TRY(run_trunk(h, s, W.f, in));
     // the step's backward as squads as well (backward_from's condition): both weight repacks in the forward's launch
-    const bool squad_bwd_next = grads && h->fused_gn_bwd && !events && !h->wgrad_mid_flush && W.sq_gact && h->train_squad >= 2;
+    const bool squad_bwd_next = grads && !events && W.sq_gact && h->train_squad >= 2;
     OSD_TRY(train_squad_forward(h, s, W.f, in, W.sq_act, W.sq_wpk, W.sq_bar, W.sq_panels, loss_out, squad_bwd_next ? W.sq_wpk_t : nullptr));
   } else {
     OSD_TRY(run_trunk(h, s, W.f, in));

@@ -119,8 +119,8 @@ int wgrad_group_flush(osd_handle* h, hipStream_t s, int plan_index, const std::v
   // row range per item: about two workgroups per CU over the whole list, never fewer than 8 K steps per item
   long total = 0;
   for (const WgPending& w : pend) total += (long)((w.kin + 127) / 128) * ((w.nout + 127) / 128) * (w.rows / WG_BK);
-  static const int target_items = [] { const char* e = getenv("OSD_WGRAD_ITEMS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
-  const long per_item = std::max<long>(8, (total + target_items - 1) / target_items);
+  constexpr int WGRAD_ITEMS = 512;
+  const long per_item = std::max<long>(8, (total + WGRAD_ITEMS - 1) / WGRAD_ITEMS);
   std::vector<WgItem> items;
   std::vector<WgReduce> reds;
   int64_t slab_off = 0;

@@ -191,6 +191,46 @@ class _Engine:
             self._sig = sig
 
 
+def _if_truthy(v):
+    return int(v) if v else None
+
+
+def _if_set(v):
+    return None if v is None else int(v)
+
+
+def _choice(values: dict, message: str):
+    def encode(v):
+        try:
+            return values[v]
+        except (KeyError, TypeError):
+            raise ValueError(f"{message}, got {v!r}") from None
+    return encode
+
+
+# The model's library tunables, applied in this order by every engine lookup: (model attribute, osd_set_option name, encoder).
+# The encoder turns the attribute into the option's value, or None to leave the library's own value; a value it does not know
+# raises ValueError.
+ENGINE_OPTIONS = (
+    ("sample_chunk_rows", "chunk_rows", _if_truthy),
+    ("sample_streams", "n_streams", _if_truthy),
+    ("train_streams", "train_streams", _if_truthy),
+    ("train_squad", "train_squad", _if_set),
+    ("cond_bwd_fused", "cond_bwd_fused", lambda v: None if v is None else int(bool(v))),
+    ("sampler", "sampler", _choice({"auto": 0, "chain": 1, "graph": 2, "layers": 2}, "sampler must be 'auto', 'chain' or 'graph'")),
+    ("chain_variant", "chain_variant", _choice({None: 0, "auto": 0, "workspace": 1, "panel": 2, "squad": 3},
+                                               "chain_variant must be None, 'auto', 'workspace', 'panel' or 'squad'")),
+    ("squad_panel", "squad_panel", _choice({None: 0, 0: 0, 16: 16, 32: 32}, "squad_panel must be None, 16 or 32")),
+    ("precision", "precision", _choice({None: 0, "fp32": 0, "f32": 0, "bf16x3": 1}, "precision must be None, 'fp32' or 'bf16x3'")),
+    ("chain_grid", "chain_grid", _if_set),
+    ("chain_steps_per_launch", "chain_steps_per_launch", _if_set),
+    ("chain_stagger", "chain_stagger", _if_set),
+    ("chain_spin_budget", "chain_spin_budget", _if_set),
+    ("chain_wall_budget_ms", "chain_wall_budget_ms", _if_set),
+    ("input_splitk", "input_splitk", _if_set),
+)
+
+
 class BiologyAwareDiffusionModel(nn.Module):
     """Drop-in for models/diffusion.py:259 -- see module docstring."""
 
@@ -351,39 +391,10 @@ class BiologyAwareDiffusionModel(nn.Module):
         if eng.constraints_version != self._constraints_version:
             eng.set_constraints(self._constraints)
             eng.constraints_version = self._constraints_version
-        if self.sample_chunk_rows:
-            L.check(L.lib().osd_set_option(eng.handle, b"chunk_rows", int(self.sample_chunk_rows)))
-        if self.sample_streams:
-            L.check(L.lib().osd_set_option(eng.handle, b"n_streams", int(self.sample_streams)))
-        if self.train_streams:
-            L.check(L.lib().osd_set_option(eng.handle, b"train_streams", int(self.train_streams)))
-        if self.train_squad is not None:
-            L.check(L.lib().osd_set_option(eng.handle, b"train_squad", int(self.train_squad)))
-        if self.cond_bwd_fused is not None:
-            L.check(L.lib().osd_set_option(eng.handle, b"cond_bwd_fused", int(bool(self.cond_bwd_fused))))
-        try:
-            mode = {"auto": 0, "chain": 1, "graph": 2, "layers": 2}[self.sampler]
-        except KeyError:
-            raise ValueError(f"sampler must be 'auto', 'chain' or 'graph', got {self.sampler!r}")
-        L.check(L.lib().osd_set_option(eng.handle, b"sampler", mode))
-        try:
-            variant = {None: 0, "auto": 0, "workspace": 1, "panel": 2, "squad": 3}[self.chain_variant]
-        except KeyError:
-            raise ValueError(f"chain_variant must be None, 'auto', 'workspace', 'panel' or 'squad', got {self.chain_variant!r}")
-        L.check(L.lib().osd_set_option(eng.handle, b"chain_variant", variant))
-        if self.squad_panel not in (None, 0, 16, 32):
-            raise ValueError(f"squad_panel must be None, 16 or 32, got {self.squad_panel!r}")
-        L.check(L.lib().osd_set_option(eng.handle, b"squad_panel", int(self.squad_panel or 0)))
-        try:
-            prec = {None: 0, "fp32": 0, "f32": 0, "bf16x3": 1}[self.precision]
-        except KeyError:
-            raise ValueError(f"precision must be None, 'fp32' or 'bf16x3', got {self.precision!r}")
-        L.check(L.lib().osd_set_option(eng.handle, b"precision", prec))
-        for name, val in (("chain_grid", self.chain_grid), ("chain_steps_per_launch", self.chain_steps_per_launch),
-                          ("chain_stagger", self.chain_stagger), ("chain_spin_budget", self.chain_spin_budget),
-                          ("chain_wall_budget_ms", self.chain_wall_budget_ms), ("input_splitk", self.input_splitk)):
-            if val is not None:
-                L.check(L.lib().osd_set_option(eng.handle, name.encode(), int(val)))
+        for attr, option, encode in ENGINE_OPTIONS:
+            value = encode(getattr(self, attr))
+            if value is not None:
+                L.check(L.lib().osd_set_option(eng.handle, option.encode(), value))
         return eng
 
     def _prep(self, t: torch.Tensor, cols: Optional[int] = None, name: str = "tensor") -> torch.Tensor:

@@ -28,7 +28,7 @@ import torch.nn as nn
 from torch.utils.data import DataLoader, Dataset
 
 from . import _lib as L
-from .diffusion import BiologyAwareDiffusionModel, _draw_seed
+from .diffusion import ENGINE_OPTIONS, BiologyAwareDiffusionModel, _draw_seed
 from .parallel import RcclGradComm, allreduce_buckets, bucket_slices
 
 logger = logging.getLogger(__name__)
@@ -601,7 +601,7 @@ class Trainer:
 
     def _option_state(self):
         m = self.model
-        return tuple(getattr(m, k, None) for k in ("train_streams", "sampler", "input_splitk", "precision"))
+        return tuple(getattr(m, attr, None) for attr, _, _ in ENGINE_OPTIONS)
 
     def _bcast(self, t: torch.Tensor):
         """Broadcast from rank 0 in place (staged through the host when the backend is gloo)."""

@@ -338,6 +338,20 @@ def test_c_abi_error_codes():
         cfg.hidden_dims[i] = v
     h = C.c_void_p()
     assert lib.osd_create(C.byref(cfg), C.byref(h)) == L.OSD_OK
+    # every settable option reads back its default, and setting that default reads back the same value
+    defaults = {"chunk_rows": 65536, "n_streams": 2, "sampler": 0, "train_squad": 2, "squad_panel": 0, "chain_variant": 0, "precision": 0,
+                "chain_grid": 0, "input_splitk": 0, "cond_bwd_fused": 1, "chain_spin_budget": 500_000_000, "chain_wall_budget_ms": 0,
+                "chain_steps_per_launch": 0, "chain_stagger": 30000, "train_streams": 2}
+    v = C.c_int64()
+    for name, default in defaults.items():
+        assert lib.osd_get_option(h, name.encode(), C.byref(v)) == L.OSD_OK and v.value == default, name
+        assert lib.osd_set_option(h, name.encode(), default) == L.OSD_OK, name
+        v.value = -7
+        assert lib.osd_get_option(h, name.encode(), C.byref(v)) == L.OSD_OK and v.value == default, name
+    # retired A/B switches are unknown names to both calls
+    for name in ("train_ksplit", "dual_dgrad", "train_input_splitk", "grouped_wgrad", "fused_gn_bwd", "wgrad_mid_flush"):
+        assert lib.osd_set_option(h, name.encode(), 1) == L.OSD_EINVAL, name
+        assert lib.osd_get_option(h, name.encode(), C.byref(v)) == L.OSD_EINVAL, name
     x = torch.zeros(4, 40, device="cuda")
     c = torch.zeros(4, 3, device="cuda")
     # weights before schedule, compute before weights

@@ -371,7 +371,7 @@ def test_fallback_groupnorm_backward_is_deterministic_and_trainer_follows_option
     """(i) Block widths other than 256 / 512 (here 64 / 128: GroupNorm groups of 8 / 16 channels) take the stand-alone GroupNorm
     backward kernel; its dgamma / dbeta / dbias come from a fixed-order partial reduce, so two passes over the same inputs agree bit
     for bit (round-2 advisor finding: they were float atomics).  (ii) A tunable changed on the model after the Trainer was built
-    (here train_streams) reaches the Trainer's fast path."""
+    (train_streams, train_squad, cond_bwd_fused) reaches the Trainer's fast path."""
     H = [64, 128, 64]
     dims = dict(mutation_dim=8, expression_dim=48, pathway_dim=8, condition_dim=3)
     conf = config(H)
@@ -403,6 +403,12 @@ def test_fallback_groupnorm_backward_is_deterministic_and_trainer_follows_option
     tr.train_step(x, c, t=t, noise=nz, seed=5)
     L.check(L.lib().osd_get_option(tr._engine.handle, b"train_streams", C.byref(v)))
     assert v.value == 2
+    for attr, flips in (("train_squad", ((0, 0), (2, 2))), ("cond_bwd_fused", ((False, 0), (True, 1)))):
+        for value, expect in flips:
+            setattr(m, attr, value)
+            tr.train_step(x, c, t=t, noise=nz, seed=5)
+            L.check(L.lib().osd_get_option(tr._engine.handle, attr.encode(), C.byref(v)))
+            assert v.value == expect, (attr, value)
 
 
 def test_batch_source_with_constraint_losses(golden_dir):
