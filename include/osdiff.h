@@ -133,8 +133,22 @@ int osd_set_option(osd_handle *h, const char *name, int64_t value);
  * "last_chain_variant" (1 | 2 | 3, the chain kernel that ran last), "last_squad_panel" (patients per panel of the squad chain
  * that ran last), "last_precision" (0 | 1, what the most recent forward / p_sample / sample computed in), "split_supported"
  * (1 when "precision" 1 applies to this model), "panel_chain_supported" / "squad_chain_supported" (1 when "chain_variant"
- * 2 / 3 applies to this model).  Any other name: OSD_EINVAL. */
+ * 2 / 3 applies to this model), "last_train_path" (what the most recent osd_train_loss_fwd_bwd or osd_denoiser_backward call on
+ * the handle ran, an OR of the OSD_TP_* bits below; cleared at the start of either call).  Any other name: OSD_EINVAL. */
 int osd_get_option(osd_handle *h, const char *name, int64_t *value);
+
+/* "last_train_path" bits */
+#define OSD_TP_SQUAD_FWD     (1 << 0)   /* the forward trunk ran as one launch of squads (csrc/train_squad.h) */
+#define OSD_TP_SQUAD_BWD     (1 << 1)   /* the backward dgrad chain ran as one launch of squads (csrc/train_squad_bwd.h) */
+#define OSD_TP_FUSED_GN_BWD  (1 << 2)   /* GroupNorm backward inside the dgrad epilogues (else the stand-alone GroupNorm backward) */
+#define OSD_TP_DUAL_DGRAD    (1 << 3)   /* at least one dgrad carried a skip connection's share in the same launch */
+#define OSD_TP_COND_BWD      (1 << 4)   /* the conditioning branch's backward as one launch (k_cond_bwd; else five launches) */
+#define OSD_TP_COND_BWD_CE0  (1 << 5)   /* ... with the first embedding Linear's weight gradient inside it */
+#define OSD_TP_X_PADDED      (1 << 6)   /* x_t rows padded to whole K steps; input_proj read input_proj.weight itself */
+#define OSD_TP_INPUT_REPACK  (1 << 7)   /* ... which it refused (unaligned weight): the padded copy was packed after all */
+#define OSD_TP_WGRAD_DIRECT  (1 << 8)   /* at least one weight gradient launched on its own, outside the grouped launch */
+#define OSD_TP_WGRAD_GROUP   (1 << 9)   /* at least one grouped weight-gradient launch */
+#define OSD_TP_MSE_BF16      (1 << 10)  /* output_proj + MSE on the bf16 matrix pipe ("precision" 1) */
 
 /* Schedule + time-embedding tables, computed by the host with the reference's own
  * fp32 expressions so they are bit-identical (models/diffusion.py:299-326, 131-137,

@@ -176,6 +176,7 @@ int run_trunk(osd_handle* h, hipStream_t s, const FwdWs& ws, const TrunkIn& in) 
         OSD_HIP(launch_copy2d(s, h->params[pm.in_w], a.D, h->w_in_packed, h->w_in_ld, a.H0, a.D));
         g.A = h->w_in_packed; g.lda = h->w_in_ld; g.a_kmax = 0;
         e = launch_input(s, g, ea, true);
+        if (in.path) *in.path |= OSD_TP_INPUT_REPACK;
       }
       OSD_HIP(e);
     }
@@ -376,6 +377,7 @@ static const Counter COUNTERS[] = {
     {"panel_chain_supported", [](osd_handle* h) -> int64_t { return panel_chain_supported(h); }},
     {"squad_chain_supported", [](osd_handle* h) -> int64_t { return squad_chain_supported(h); }},
     {"last_squad_panel", [](osd_handle* h) -> int64_t { return h->last_squad_rp; }},
+    {"last_train_path", [](osd_handle* h) -> int64_t { return h->last_train_path; }},
 };
 
 }  // namespace osd

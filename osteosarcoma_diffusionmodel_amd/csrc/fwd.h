@@ -22,6 +22,7 @@ struct TrunkIn {
   bool save;                     // keep pre-norm activations + GroupNorm statistics for backward
   const float* const* masks;     // injected keep-masks per block, or null -> Philox
   uint64_t seed; uint32_t row_offset; uint32_t drop_step; const int* drop_step_dev;
+  int* path;                     // training calls: OSD_TP_* bits of what ran are OR-ed in (handle.h: last_train_path), else null
 };
 
 int ensure_arena(Slot* s, int64_t floats);

@@ -167,6 +167,7 @@ struct osd_handle {
   int precision = 0;                 // osd_set_option("precision"): 0 fp32 MFMA (default; the reference's arithmetic), 1 bf16x3 split on the bf16 matrix pipe
                                      // (fp32 accuracy, eval-mode sampling / forward of 256 / 512 wide trunks; everything else stays fp32)
   int last_precision = 0;            // precision the most recent forward / p_sample / sample call computed in (osd_get_option)
+  int last_train_path = 0;           // OSD_TP_* bits: what the most recent osd_train_loss_fwd_bwd / osd_denoiser_backward ran (osd_get_option)
   void* split_plan = nullptr;        // weight planes (split.hip)
   bool split_valid = false;          // false after anything that may have changed the parameters: repacked by the next split-precision call
   // osd_profile_step: when non-null, run_trunk records prof_events[prof_i++] after every launch

@@ -228,7 +228,8 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
   auto wg = [&](const float* x, int ldx, int kin, const float* gz, int ldg, int nout, int64_t rows, float* dw, int lddw,
                 float* b0 = nullptr, float* b1 = nullptr, float* b2 = nullptr) -> int {
     const WgPending wp{x, ldx, kin, gz, ldg, nout, rows, dw, lddw, {b0, b1, b2}};
-    if (kin >= 16 && wgrad_group_ok(wp)) { pend.push_back(wp); return OSD_OK; }
+    if (kin >= 16 && wgrad_group_ok(wp)) { pend.push_back(wp); h->last_train_path |= OSD_TP_WGRAD_GROUP; return OSD_OK; }
+    h->last_train_path |= OSD_TP_WGRAD_DIRECT;
     const bool small = small_wgrad_ok(kin, nout, lddw);
     if (small && !events) {            // a 5 us kernel whose inputs are on the main stream: run it there (no fork, no event)
       OSD_HIP(wgrad(s, W, x, ldx, kin, gz, ldg, nout, rows, dw, lddw, b0));
@@ -264,6 +265,8 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
   for (const LayerDesc& l : a.layers) fuse = fuse && dgrad_gnbwd_supported(l.gw);
   // single-GPU steps: the dgrad chain between the first launch (output_proj) and the last (into h0) as one launch of squads
   const bool squad_bwd = fuse && !events && W.sq_gact && loss_poison && h->train_squad >= 2 && train_squad_ok(h, n);
+  if (fuse) h->last_train_path |= OSD_TP_FUSED_GN_BWD;
+  if (squad_bwd) h->last_train_path |= OSD_TP_SQUAD_BWD;
   const float keep_scale = (float)(1.0 / (1.0 - (double)h->cfg.dropout_p));
   std::vector<GnColItem> cols;
   // d gamma / d beta of the layers whose backward ran in a dgrad epilogue: memory-bound leaves, one launch per call.  They
@@ -338,7 +341,7 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
         GemmArgs g2{};
         g2.A = w_skip; g2.lda = ldw; g2.B0 = gz_next; g2.ldb0 = ldg; g2.K0 = nout; g2.F = kin_skip; g2.P = (int)n; g2.K = nout;
         const hipError_t de = launch_dgrad_gnbwd_dual(s, g, ln.gw, e, g2, out_skip, kin_skip);
-        if (de == hipSuccess) { launched = true; if (skip_done) *skip_done = true; }
+        if (de == hipSuccess) { launched = true; if (skip_done) *skip_done = true; h->last_train_path |= OSD_TP_DUAL_DGRAD; }
         else if (de != hipErrorInvalidValue) OSD_HIP(de);
         else (void)hipGetLastError();
       }
@@ -442,6 +445,8 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
   const bool cond_fused = h->cond_bwd_fused && cond_bwd_ok(a.H0, W.g_h0, W.u0, W.g_ce2, W.g_u);
   // ... and, where the first embedding Linear has at most four inputs (k_small_wgrad's case), its weight gradient rides along
   const bool ce0_fused = cond_fused && a.cond_dim <= 4 && small_wgrad_ok(a.cond_dim, 64, a.cond_dim);
+  if (cond_fused) h->last_train_path |= OSD_TP_COND_BWD;
+  if (ce0_fused) h->last_train_path |= OSD_TP_COND_BWD_CE0;
   if (cond_fused) {
     OSD_HIP(launch_cond_bwd(s, W.g_h0, a.H0, t_idx, W.g_temb, h->params[pm.cp_w], h->params[pm.ce2_w], W.u0, n, W.g_ce2, W.g_u,
                             ce0_fused ? cond : nullptr, a.cond_dim, W.g_temb + (int64_t)t_pad(a.T) * a.H0, grads[pm.ce0_w], grads[pm.ce0_b]));
@@ -487,6 +492,7 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
                            const float* const* masks, uint64_t seed, int64_t row_offset, int flags, float* loss_out,
                            float* const* grads, double loss_scale, void* const* events, int n_events) {
   OSD_TRY(check_ready(h));
+  h->last_train_path = 0;
   OSD_TRY(check_rows(n));
   const bool from_src = h && h->have_batch_src;          // one-shot: consumed (or dropped) by this call
   if (h) h->have_batch_src = false;
@@ -534,6 +540,7 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
   // x_t rows are padded to whole K steps with zeros when nothing else reads them with the dense stride: input_proj then takes
   // input_proj.weight as it is (clamped at D) and the per-step packed copy of that weight is not made
   const bool unpacked = w.xld > D;
+  if (unpacked) h->last_train_path |= OSD_TP_X_PADDED;
   // the t_emb table (and, unless input_proj reads the weight itself, its padded copy) follow the current parameters
   OSD_TRY(refresh_derived(h, s, !unpacked));
   const int* t_idx = nullptr;
@@ -556,8 +563,9 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
   TrunkIn in{};
   in.x = W.x_t; in.ldx = W.xld; in.kx = unpacked ? W.xld : D; in.a_unpacked = unpacked; in.ksplit = true;
   in.n = n; in.t_index = t_idx; in.train = train; in.save = grads != nullptr;
-  in.masks = masks; in.seed = seed; in.row_offset = roff; in.drop_step = 0;
+  in.masks = masks; in.seed = seed; in.row_offset = roff; in.drop_step = 0; in.path = &h->last_train_path;
   if (W.sq_act && train_squad_ok(h, n)) {
+    h->last_train_path |= OSD_TP_SQUAD_FWD;
     in.input_only = true;
     OSD_TRY(run_trunk(h, s, W.f, in));
     // the step's backward as squads as well (backward_from's condition): both weight repacks in the forward's launch
@@ -575,6 +583,7 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
     ea.gscale = (float)(2.0 * (double)loss_scale / ((double)n * (double)D));
     // precision = 1: output_proj + MSE on the bf16 matrix pipe, operands split where they are staged (gemm_b3t.h)
     hipError_t me = h->precision == 1 ? launch_mse_b3t(s, g, ea) : hipErrorInvalidValue;
+    if (me == hipSuccess) h->last_train_path |= OSD_TP_MSE_BF16;
     if (me == hipErrorInvalidValue) { (void)hipGetLastError(); me = launch_mse(s, g, ea); }
     OSD_HIP(me);
   }
@@ -646,6 +655,7 @@ int osd_denoiser_backward(osd_handle* h, const float* x_t, const int32_t* t_inde
                           const float* const* masks, uint64_t seed, int64_t row_offset, int flags, float* const* grads, float* dx_t,
                           void* const* events, int n_events) {
   OSD_TRY(check_ready(h));
+  h->last_train_path = 0;
   OSD_TRY(check_rows(n));
   if (!x_t || !t_index || !cond || !dout || !grads || n == 0) { set_error("null tensor or empty batch"); return OSD_EINVAL; }
   if (h->saved_rows != n) { set_error("osd_denoiser_backward needs the activations of an osd_denoiser_forward_train call on the same %lld rows", (long long)n); return OSD_ESTATE; }

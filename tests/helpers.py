@@ -125,3 +125,48 @@ def philox_normals(seed, rows, cols, step, tag, row_offset=0):
     r0, r1 = np.sqrt(-2 * np.log(u1a)), np.sqrt(-2 * np.log(u1b))
     out = np.stack([r0 * np.cos(2 * np.pi * a0), r0 * np.sin(2 * np.pi * a0), r1 * np.cos(2 * np.pi * a1), r1 * np.sin(2 * np.pi * a1)], axis=-1)
     return out.reshape(rows, -1)[:, :cols]
+
+
+# ---- the training step in float64, in row chunks -----------------------------------------------------------------------
+ORACLE_CHUNK = 4096
+_oracle_cache = {}
+
+
+def block_widths(hidden):
+    """Output widths of the blocks in execution order: the widths of the dropout keep-masks."""
+    H = list(hidden)
+    return H[1:] + [H[-1]] + H[-2::-1]
+
+
+def oracle_train_fp64(sd, x0, cond, t, noise, hidden, masks=None, p=0.0, *, key=None, rows=None, T=1000, time_dim=128,
+                      chunk=ORACLE_CHUNK):
+    """Loss and the gradient of every entry of ``sd`` for one eps-MSE training step, in float64: ``O.training_forward`` and
+    autograd over row chunks of at most ``chunk`` rows.  Rows are independent up to the final mean (GroupNorm normalises per
+    row; the embeddings and q_sample are per row), so each chunk's MSE is weighted by chunk / n and the chunks' gradients are
+    summed.  ``masks``: 0/1 keep-masks per block (train mode) or None (eval).  ``rows``: only the first ``rows`` rows
+    contribute, still divided by n (negative controls).  Results are cached under ``key``."""
+    if key is not None and key in _oracle_cache:
+        return _oracle_cache[key]
+    from oracle import diffusion_oracle as O
+    n = x0.shape[0]
+    stop = n if rows is None else rows
+    bufs = {k: v.double() for k, v in O.schedule_buffers("cosine", T).items()}
+    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in O.to_dtype(sd, torch.float64).items()}
+    grads = {k: torch.zeros_like(v) for k, v in leaves.items()}
+    loss = 0.0
+    for r0 in range(0, stop, chunk):
+        r1 = min(r0 + chunk, stop)
+        nz = noise[r0:r1].double()
+        mk = None if masks is None else [m[r0:r1].double() for m in masks]
+        pred = O.training_forward(leaves, bufs, x0[r0:r1].double(), cond[r0:r1].double(), t[r0:r1], nz, len(hidden), time_dim, mk, p,
+                                  return_loss=False)
+        part = torch.nn.functional.mse_loss(pred, nz) * ((r1 - r0) / n)
+        g = torch.autograd.grad(part, list(leaves.values()), allow_unused=True)
+        for k, gk in zip(leaves, g):
+            if gk is not None:
+                grads[k] += gk
+        loss += part.item()
+    out = (loss, grads)
+    if key is not None:
+        _oracle_cache[key] = out
+    return out

@@ -1,0 +1,458 @@
+"""GPU: the training step against a float64 oracle across the library's dispatch branches.
+
+The training step chooses its path from the model's dims and widths, the batch size, the options and the alignment of the
+tensors it is handed (x_t at stride D or padded, the guarded MSE epilogue, grouped or immediate weight gradients, training
+squads, the fused or stand-alone GroupNorm backward, the dual dgrad, the one-launch conditioning backward, the bf16 pipe).  Each
+case below names the branches it reaches, asserts them through the ``last_train_path`` counter (include/osdiff.h: OSD_TP_*),
+and holds loss and every gradient to ``helpers.oracle_train_fp64`` at the project's training tolerances: loss 1e-5 relative,
+each gradient tensor max|d| <= 5e-5 * max|ref| + 1e-9, and the same bound on the tail columns of input_proj.weight's gradient
+and the tail rows of output_proj's (the ragged edges of the feature tiles), each against its own max.  Negative controls show
+that the tolerances can tell a wrong input from a right one."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import constraints_oracle as CO
+from oracle import diffusion_oracle as O
+from osteosarcoma_diffusionmodel_amd import BiologyAwareDiffusionModel
+from osteosarcoma_diffusionmodel_amd import _lib as L
+from osteosarcoma_diffusionmodel_amd.train import Trainer, _loss_fwd_bwd
+from helpers import assert_close, block_widths, config, oracle_train_fp64, philox_keep_mask
+
+pytestmark = pytest.mark.gpu
+
+GRAD_RTOL = 5e-5
+LOSS_RTOL = 1e-5
+P = 0.2
+SEED = (5 << 33) + 977
+LR, WD = 1e-4, 1e-5
+
+# last_train_path bits (include/osdiff.h)
+SQ_FWD, SQ_BWD, FUSE, DUAL, COND, CE0, XPAD, REPACK, WG_DIRECT, WG_GROUP, MSE_BF16 = (1 << i for i in range(11))
+
+REAL = (62, 5054, 26, 4)        # the reference's real feature dims: D = 5142 (D % 4 == 2), four conditions
+FULL = (50, 1900, 50, 3)        # D = 2000
+H3 = [256, 512, 256]
+
+# name: dims, hidden, n, draws ("injected" | "philox" | "eval"), library options, precision, row offset, expected path bits
+CASES = {
+    "real16": dict(dims=REAL, hidden=H3, n=16, draw="injected",
+                   path=FUSE | DUAL | COND | CE0 | WG_DIRECT | WG_GROUP),
+    "real16-eval": dict(dims=REAL, hidden=H3, n=16, draw="eval",
+                        path=FUSE | DUAL | COND | CE0 | WG_DIRECT | WG_GROUP),
+    "real2049": dict(dims=REAL, hidden=H3, n=2049, draw="philox",
+                     path=SQ_FWD | SQ_BWD | FUSE | COND | CE0 | WG_DIRECT | WG_GROUP),
+    "real4096-b3": dict(dims=REAL, hidden=H3, n=4096, draw="philox", precision="bf16x3",
+                        path=SQ_FWD | SQ_BWD | FUSE | COND | CE0 | WG_DIRECT | WG_GROUP),
+    "full2048-off": dict(dims=FULL, hidden=H3, n=2048, draw="philox", roff=3 * 2048, opts=dict(train_streams=1),
+                         path=SQ_FWD | SQ_BWD | FUSE | COND | CE0 | XPAD | WG_GROUP),
+    "full2111-s2-c1": dict(dims=FULL, hidden=H3, n=2111, draw="injected", opts=dict(train_squad=2, cond_bwd_fused=True),
+                           path=SQ_FWD | SQ_BWD | FUSE | COND | CE0 | XPAD | WG_DIRECT | WG_GROUP),
+    "full2111-s2-c0": dict(dims=FULL, hidden=H3, n=2111, draw="injected", opts=dict(train_squad=2, cond_bwd_fused=False),
+                           path=SQ_FWD | SQ_BWD | FUSE | XPAD | WG_DIRECT | WG_GROUP),
+    "full2111-s1-c1": dict(dims=FULL, hidden=H3, n=2111, draw="injected", opts=dict(train_squad=1, cond_bwd_fused=True),
+                           path=SQ_FWD | FUSE | DUAL | COND | CE0 | XPAD | WG_DIRECT | WG_GROUP),
+    "full2111-s1-c0": dict(dims=FULL, hidden=H3, n=2111, draw="injected", opts=dict(train_squad=1, cond_bwd_fused=False),
+                           path=SQ_FWD | FUSE | DUAL | XPAD | WG_DIRECT | WG_GROUP),
+    "full8192": dict(dims=FULL, hidden=H3, n=8192, draw="philox",
+                     path=SQ_FWD | SQ_BWD | FUSE | COND | CE0 | XPAD | WG_GROUP),
+    "full8192-b3": dict(dims=FULL, hidden=H3, n=8192, draw="philox", precision="bf16x3",
+                        path=SQ_FWD | SQ_BWD | FUSE | COND | CE0 | XPAD | WG_GROUP | MSE_BF16),
+    "full10000-s2": dict(dims=FULL, hidden=H3, n=10000, draw="philox", opts=dict(train_squad=2),
+                         path=SQ_FWD | SQ_BWD | FUSE | COND | CE0 | XPAD | WG_DIRECT | WG_GROUP),
+    "full10000-s0": dict(dims=FULL, hidden=H3, n=10000, draw="philox", opts=dict(train_squad=0),
+                         path=FUSE | DUAL | COND | CE0 | XPAD | WG_DIRECT | WG_GROUP),
+    "deep2560": dict(dims=(16, 480, 16, 3), hidden=[256, 256, 512, 256], n=2560, draw="philox",
+                     path=SQ_FWD | SQ_BWD | FUSE | COND | CE0 | WG_GROUP),
+    "deep300": dict(dims=(16, 480, 16, 3), hidden=[256, 256, 512, 256], n=300, draw="philox",
+                    path=FUSE | DUAL | COND | CE0 | WG_DIRECT | WG_GROUP),
+    "skip1": dict(dims=(5, 30, 2, 3), hidden=[256, 256], n=4096, draw="eval",
+                  path=FUSE | DUAL | COND | CE0 | WG_DIRECT | WG_GROUP),
+    "h512-1024": dict(dims=(50, 1900, 50, 8), hidden=[512, 256, 512], n=1024, draw="philox",
+                      path=FUSE | DUAL | XPAD | WG_DIRECT | WG_GROUP),
+    "h512-4096": dict(dims=(50, 1900, 50, 8), hidden=[512, 256, 512], n=4096, draw="philox",
+                      path=FUSE | DUAL | XPAD | WG_DIRECT | WG_GROUP),
+    "mixed": dict(dims=(16, 224, 16, 3), hidden=[256, 128, 256], n=4096, draw="injected",
+                  path=COND | CE0 | WG_GROUP),
+}
+
+_cache = {}
+
+
+def _report(case, **kw):
+    """One JSON line per case into $TRAIN_MATRIX_REPORT when it is set (the path value and the error / tolerance ratios)."""
+    path = os.environ.get("TRAIN_MATRIX_REPORT")
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps(dict(case=case, **kw)) + "\n")
+
+
+def _inputs(dims, hidden, n, seed=17):
+    """Weights (non-trivial GroupNorm affines), binary mutation columns, host-drawn t / noise and injected keep-masks."""
+    key = ("in", dims, tuple(hidden), n, seed)
+    if key not in _cache:
+        mut, expr, pw, cd = dims
+        D = mut + expr + pw
+        sd = O.init_state_dict(O.param_shapes(mut, expr, pw, cd, hidden, 128), seed=seed)
+        gen = torch.Generator().manual_seed(seed + 1)
+        for k in sd:
+            if k.endswith((".1.weight", ".5.weight")):
+                sd[k] = 1 + 0.2 * torch.randn(sd[k].shape, generator=gen)
+            if k.endswith((".1.bias", ".5.bias")):
+                sd[k] = 0.1 * torch.randn(sd[k].shape, generator=gen)
+        x = torch.randn(n, D, generator=gen)
+        x[:, :mut] = (x[:, :mut] > 0).float()
+        cond = torch.randn(n, cd, generator=gen)
+        t = torch.randint(0, 1000, (n,), generator=gen)
+        noise = torch.randn(n, D, generator=gen)
+        injected = [(torch.rand(n, w, generator=gen) >= P).float() for w in block_widths(hidden)]
+        _cache[key] = (sd, x, cond, t, noise, injected)
+    return _cache[key]
+
+
+def _masks(c, injected, roff=None):
+    """The keep-masks the oracle sees: injected, the host restatement of the in-kernel Philox draws, or None (eval)."""
+    if c["draw"] == "injected":
+        return injected
+    if c["draw"] == "philox":
+        roff = c.get("roff", 0) if roff is None else roff
+        return [torch.from_numpy(philox_keep_mask(SEED, c["n"], w, b, P, roff)) for b, w in enumerate(block_widths(c["hidden"]))]
+    return None
+
+
+def _oracle(c, roff=None, rows=None):
+    """The case's fp64 loss and gradients; cached per inputs unless a negative control changes them (roff, rows)."""
+    sd, x, cond, t, noise, injected = _inputs(c["dims"], c["hidden"], c["n"])
+    masks = _masks(c, injected, roff)
+    key = None if roff is not None or rows is not None else (c["dims"], tuple(c["hidden"]), c["n"], c["draw"], c.get("roff", 0))
+    return oracle_train_fp64(sd, x, cond, t, noise, c["hidden"], masks, P if masks is not None else 0.0, key=key, rows=rows)
+
+
+def _model(c, sd, p=P):
+    mut, expr, pw, cd = c["dims"]
+    m = BiologyAwareDiffusionModel(config=config(c["hidden"], p=p), mutation_dim=mut, expression_dim=expr, pathway_dim=pw, condition_dim=cd)
+    m.load_state_dict(sd, strict=False)
+    m = m.cuda()
+    m = m.eval() if c["draw"] == "eval" else m.train()
+    for k, v in c.get("opts", {}).items():
+        setattr(m, k, v)
+    m.precision = c.get("precision")
+    return m
+
+
+def _path(m):
+    v = C.c_int64(-1)
+    L.check(L.lib().osd_get_option(m._engine().handle, b"last_train_path", C.byref(v)))
+    return int(v.value)
+
+
+def _device(name):
+    """Loss, gradients (host, by parameter name) and last_train_path of the case's training call (cached)."""
+    key = ("dev", name)
+    if key not in _cache:
+        c = CASES[name]
+        sd, x, cond, t, noise, injected = _inputs(c["dims"], c["hidden"], c["n"])
+        m = _model(c, sd)
+        grads = [torch.empty_like(p) for p in m.parameters()]
+        kw = dict(t=t.cuda(), noise=noise.cuda(), seed=SEED, row_offset=c.get("roff", 0))
+        if c["draw"] == "injected":
+            kw["dropout_masks"] = [k.cuda() for k in injected]
+        loss = _loss_fwd_bwd(m, x.cuda(), cond.cuda(), L.ptr_array(grads), **kw)
+        torch.cuda.synchronize()
+        names = [k for k, _ in m.named_parameters()]
+        _cache[key] = (loss.item(), {k: g.cpu() for k, g in zip(names, grads)}, _path(m), c["dims"])
+    return _cache[key]
+
+
+def _check(loss, grads, ref_loss, ref_grads, D):
+    """Every comparison of a case; returns the largest error / tolerance ratio over them (<= 1 when all pass) and the failures."""
+    worst, bad = 0.0, []
+
+    def one(what, a, b, rtol, atol=1e-9):
+        nonlocal worst
+        a = np.asarray(a, dtype=np.float64)
+        b = np.asarray(b.detach().double().numpy() if isinstance(b, torch.Tensor) else b, dtype=np.float64)
+        tol = atol + rtol * np.abs(b).max()
+        err = np.abs(a - b).max() if np.isfinite(a).all() else np.inf
+        worst = max(worst, err / tol)
+        if not err <= tol:
+            bad.append(f"{what}: max|d|={err:.3e} > tol={tol:.3e}")
+
+    one("loss", loss, ref_loss, LOSS_RTOL, 0.0)
+    for k, g in grads.items():
+        one(f"grad {k}", g.double().numpy(), ref_grads[k], GRAD_RTOL)
+    tail = D % 32 + 4
+    one("grad input_proj.weight tail columns", grads["unet.input_proj.weight"][:, -tail:].double().numpy(),
+        ref_grads["unet.input_proj.weight"][:, -tail:], GRAD_RTOL)
+    one("grad output_proj.weight tail rows", grads["unet.output_proj.weight"][-tail:].double().numpy(),
+        ref_grads["unet.output_proj.weight"][-tail:], GRAD_RTOL)
+    one("grad output_proj.bias tail", grads["unet.output_proj.bias"][-tail:].double().numpy(), ref_grads["unet.output_proj.bias"][-tail:], GRAD_RTOL)
+    return worst, bad
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_train_step_vs_fp64_oracle(name):
+    """Loss, every gradient and the tail slices against the fp64 oracle; the path taken, bit for bit (the CASES table)."""
+    c = CASES[name]
+    loss, grads, path, dims = _device(name)
+    ref_loss, ref_grads = _oracle(c)
+    worst, bad = _check(loss, grads, ref_loss, ref_grads, sum(dims[:3]))
+    _report(name, path=path, worst_ratio=worst)
+    assert not bad, "\n".join(bad)
+    assert path == c["path"], f"last_train_path {path:#x} ({path}), expected {c['path']:#x} ({c['path']})"
+
+
+def test_negative_control_row_offset_shifted_by_one_panel():
+    """full2048-off against masks drawn one 64-row panel away: the gradients must disagree beyond tolerance."""
+    c = CASES["full2048-off"]
+    loss, grads, _, dims = _device("full2048-off")
+    ref_loss, ref_grads = _oracle(c, roff=c["roff"] + 64)
+    _, bad = _check(loss, grads, ref_loss, ref_grads, sum(dims[:3]))
+    assert any(b.startswith("grad") for b in bad), "the shifted masks went unnoticed"
+
+
+def test_negative_control_last_row_left_out():
+    """real2049 against an oracle without the last row's contribution (the other 2 048 rows, still divided by 2 049)."""
+    c = CASES["real2049"]
+    loss, grads, _, dims = _device("real2049")
+    ref_loss, ref_grads = _oracle(c, rows=c["n"] - 1)
+    _, bad = _check(loss, grads, ref_loss, ref_grads, sum(dims[:3]))
+    assert any(b.startswith("grad") for b in bad), "a missing row went unnoticed"
+
+
+def test_negative_control_one_timestep_moved():
+    """real16 against an oracle whose row 5 sits 50 diffusion steps away: the loss or some gradient must miss."""
+    c = CASES["real16"]
+    loss, grads, _, dims = _device("real16")
+    sd, x, cond, t, noise, injected = _inputs(c["dims"], c["hidden"], c["n"])
+    t2 = t.clone()
+    t2[5] = (t2[5] + 50) % 1000
+    ref_loss, ref_grads = oracle_train_fp64(sd, x, cond, t2, noise, c["hidden"], injected, P)
+    _, bad = _check(loss, grads, ref_loss, ref_grads, sum(dims[:3]))
+    assert bad, "a moved timestep went unnoticed"
+
+
+def _assert_params_close(got, want, gclip, name):
+    """test_gpu_config2._assert_params_close: 2e-5 * max|p| plus the gradient tolerance propagated through the first AdamW
+    update (steep where the clipped gradient is comparable to eps = 1e-8), never more than the 2 lr of a flipped sign."""
+    got, want, g = got.double().numpy(), want.double().numpy(), np.abs(gclip.double().numpy())
+    d = np.abs(got - want)
+    assert np.isfinite(got).all(), name
+    eps = 1e-8
+    sens = LR * eps / (g + eps) ** 2
+    allowed = 2e-5 * np.abs(want).max() + 1e-8 + np.minimum(sens * GRAD_RTOL * g.max(), 2.0 * LR)
+    worst = (d - allowed).max()
+    assert worst <= 0, f"param {name}: an element exceeds its propagated tolerance by {worst:.3e} (max|d|={d.max():.3e})"
+
+
+def _train_conf(hidden, tmp_path, p=P, **extra):
+    conf = config(hidden, p=p)
+    conf["training"] = {"learning_rate": LR, "weight_decay": WD, "patience": 10, "min_delta": 1e-4, "augmentation": {"mixup_alpha": 0.0},
+                        "save_dir": str(tmp_path), "num_epochs": 1, "save_frequency": 10, "val_split": 0.2, "random_seed": 42,
+                        "batch_size": 16, **extra}
+    return conf
+
+
+def test_real16_trainer_step_vs_fp64_oracle(tmp_path):
+    """real16-step: one Trainer.train_step (flat gradients -> fused clip + AdamW) against O.clip_grad_norm + O.adamw_step on the
+    fp64 gradients: parameters, exp_avg, exp_avg_sq and step (test_gpu_config2's tolerances and propagation rule)."""
+    c = CASES["real16"]
+    sd, x, cond, t, noise, injected = _inputs(c["dims"], c["hidden"], c["n"])
+    ref_loss, ref_grads = _oracle(c)
+    names = list(sd)
+    clipped, norm = O.clip_grad_norm([ref_grads[k] for k in names], 1.0)
+    p1 = [sd[k].double().clone() for k in names]
+    m1 = [torch.zeros_like(v) for v in p1]
+    v1 = [torch.zeros_like(v) for v in p1]
+    O.adamw_step(p1, clipped, m1, v1, 1, lr=LR, weight_decay=WD)
+    m = _model(c, sd)
+    conf = _train_conf(c["hidden"], tmp_path)
+    mut, expr, pw, cd = c["dims"]
+    tr = Trainer(m, [], [], conf, device="cuda")
+    loss = tr.train_step(x.cuda(), cond.cuda(), t=t.cuda(), noise=noise.cuda(), dropout_masks=[k.cuda() for k in injected])
+    assert_close(loss.item(), ref_loss, LOSS_RTOL, what="train_step loss")
+    assert_close(tr.optimizer.grad_norm.item(), norm.item(), 2e-5, what="pre-clip gradient norm")
+    assert _path(m) == c["path"]
+    osd = tr.optimizer.state_dict()
+    for i, (k, p) in enumerate(m.named_parameters()):
+        j = names.index(k)
+        _assert_params_close(p.detach().cpu(), p1[j], clipped[j], k)
+        assert_close(osd["state"][i]["exp_avg"].cpu(), m1[j], 1e-4, atol=1e-12, what=f"exp_avg {k}")
+        assert_close(osd["state"][i]["exp_avg_sq"].cpu(), v1[j], 2e-4, atol=1e-16, what=f"exp_avg_sq {k}")
+        assert float(osd["state"][i]["step"]) == 1.0
+
+
+def test_unaligned_parameters_and_gradients_vs_fp64_oracle():
+    """Parameters as views of one flat buffer at a +4-byte offset, gradients into another: the training squads refuse them
+    (16-byte fragment loads), input_proj re-packs its weight after the clamped-weight launch refuses it, and the grouped
+    weight-gradient launch refuses every tensor -- the numbers must still be the oracle's.  Both buffers keep 64 spare
+    floats at the end, so no vector access leaves the allocation."""
+    c = dict(dims=FULL, hidden=H3, n=2048, draw="philox")
+    sd, x, cond, t, noise, _ = _inputs(c["dims"], c["hidden"], c["n"])
+    m = _model(c, sd)
+    params = list(m.parameters())
+    total = sum(p.numel() for p in params)
+    pbuf = torch.zeros(total + 1 + 64, device="cuda")
+    gbuf = torch.zeros(total + 1 + 64, device="cuda")
+    grads, off = [], 1
+    with torch.no_grad():
+        for p in params:
+            v = pbuf[off:off + p.numel()].view_as(p)
+            v.copy_(p.data)
+            p.data = v
+            grads.append(gbuf[off:off + p.numel()].view_as(p))
+            off += p.numel()
+    assert all(p.data_ptr() % 16 == 4 for p in params) and all(g.data_ptr() % 16 == 4 for g in grads)
+    loss = _loss_fwd_bwd(m, x.cuda(), cond.cuda(), L.ptr_array(grads), t=t.cuda(), noise=noise.cuda(), seed=SEED)
+    torch.cuda.synchronize()
+    path = _path(m)
+    ref_loss, ref_grads = _oracle(c)
+    names = [k for k, _ in m.named_parameters()]
+    worst, bad = _check(loss.item(), {k: g.cpu() for k, g in zip(names, grads)}, ref_loss, ref_grads, 2000)
+    _report("unaligned", path=path, worst_ratio=worst)
+    assert not bad, "\n".join(bad)
+    assert path == FUSE | COND | CE0 | XPAD | REPACK | WG_DIRECT, f"last_train_path {path:#x}"
+    assert float(gbuf[0]) == 0.0 and float(gbuf[off:].abs().max()) == 0.0       # nothing written outside the views
+
+
+@pytest.mark.parametrize("dims", [FULL, (62, 5054, 26, 3)], ids=["D2000", "D5142"])
+def test_constraint_losses_full_size_vs_fp64_oracle(dims):
+    """cons: the composite loss mse + w_pc L_pc(x0_hat) + w_me L_me(x0_hat, x0) on a full-size model in eval mode (x_t at stride D,
+    the squads at 2 048 rows) against fp64 autograd, exactly as test_gpu_constraints.py, at that test's tolerances."""
+    n, hidden = 2048, H3
+    sd, x0, cond, t, noise, _ = _inputs(dims, hidden, n)
+    mut, expr, pw_dim, cd = dims
+    D = mut + expr + pw_dim
+    pw = [[mut + 1, mut + 7, mut + 100, mut + 801], [mut + 3, mut + expr - 1, D - 2], [mut + 5, mut + 6, mut + 9, D - 1]]
+    ca, cb = list(range(0, 16)), list(range(mut + expr - 16, mut + expr))
+    w_pc, w_me = 0.7, 1.3
+    c = dict(dims=dims, hidden=hidden, n=n, draw="eval")
+    m = _model(c, sd)
+    m.set_constraints(pw, ca, cb, pathway_weight=w_pc, mutexpr_weight=w_me)
+    bufs = {k: v.double() for k, v in O.schedule_buffers("cosine", 1000).items()}
+    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in O.to_dtype(sd, torch.float64).items()}
+    pred = O.training_forward(leaves, bufs, x0.double(), cond.double(), t, noise.double(), len(hidden), 128, None, 0.0, return_loss=False)
+    mse = torch.nn.functional.mse_loss(pred, noise.double())
+    x_t = O.q_sample(bufs, x0.double(), t, noise.double())
+    xh = CO.x0_hat(x_t, pred, t, bufs["sqrt_alphas_cumprod"], bufs["sqrt_one_minus_alphas_cumprod"])
+    l_pc = CO.pathway_coherence_loss(xh, pw)
+    l_me = CO.mutation_expression_correlation_loss(xh, x0.double(), ca, cb)
+    total = mse + w_pc * l_pc + w_me * l_me
+    ref = torch.autograd.grad(total, list(leaves.values()))
+    loss = m(x0.cuda(), cond.cuda(), t=t.cuda(), noise=noise.cuda())
+    loss.backward()
+    path = _path(m)
+    assert_close(loss.item(), total.item(), 2e-5, what="total loss")
+    parts = m.last_loss_parts()
+    assert_close(parts[0], mse.item(), 2e-5, what="mse part")
+    assert_close(parts[1], l_pc.item(), 2e-5, atol=1e-7, what="L_pc part")
+    assert_close(parts[2], l_me.item(), 2e-5, atol=1e-7, what="L_me part")
+    named = dict(m.named_parameters())
+    for k, gr in zip(leaves, ref):
+        assert_close(named[k].grad.cpu(), gr, 1e-4, atol=1e-9, what=f"grad {k}")
+    want = SQ_FWD | SQ_BWD | FUSE | COND | CE0 | WG_GROUP | (WG_DIRECT if D % 4 else 0)
+    _report(f"cons-D{D}", path=path)
+    assert path == want, f"last_train_path {path:#x}, expected {want:#x}"
+
+
+def test_predict_noise_backward_with_dx_t_vs_fp64_oracle():
+    """pn: predict_noise under autograd (osd_denoiser_forward_train + osd_denoiser_backward) on an x_t that requires grad, at the real
+    dims and a ragged 2 049 rows, loss (eps * R).sum() for a fixed random R: eps, every parameter gradient and dL/dx_t against the
+    oracle at the training tolerances."""
+    c = dict(dims=REAL, hidden=H3, n=2049, draw="injected")
+    sd, x0, cond, t, noise, injected = _inputs(c["dims"], c["hidden"], c["n"])
+    gen = torch.Generator().manual_seed(5)
+    x_t = torch.randn(c["n"], 5142, generator=gen)
+    R = torch.randn(c["n"], 5142, generator=gen)
+    bufs = {k: v.double() for k, v in O.schedule_buffers("cosine", 1000).items()}
+    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in O.to_dtype(sd, torch.float64).items()}
+    xl = x_t.double().requires_grad_(True)
+    c_emb = O.condition_embed(leaves, cond.double())
+    eps_ref = O.unet_forward(leaves, xl, t.double() / 1000, c_emb, 3, 128, [k.double() for k in injected], P)
+    ref = torch.autograd.grad((eps_ref * R.double()).sum(), [xl] + list(leaves.values()))
+    m = _model(c, sd)
+    xd = x_t.cuda().requires_grad_(True)
+    eps = m.predict_noise(xd, t.cuda(), cond.cuda(), dropout_masks=[k.cuda() for k in injected])
+    (eps * R.cuda()).sum().backward()
+    path = _path(m)
+    assert_close(eps.detach().cpu(), eps_ref.detach(), GRAD_RTOL, atol=1e-9, what="eps")
+    assert_close(xd.grad.cpu(), ref[0], GRAD_RTOL, atol=1e-9, what="dx_t")
+    named = dict(m.named_parameters())
+    for k, gr in zip(leaves, ref[1:]):
+        assert_close(named[k].grad.cpu(), gr, GRAD_RTOL, atol=1e-9, what=f"grad {k}")
+    _report("pn", path=path)
+    assert path == FUSE | DUAL | COND | CE0 | WG_DIRECT | WG_GROUP, f"last_train_path {path:#x}"
+
+
+def test_resident_epoch_at_real_dims_vs_fp64_oracle(tmp_path):
+    """resident: Trainer.train_epoch over 64 rows at the real dims (four steps of 16, p = 0), replayed from HBM
+    (osd_train_batch_source) and through the DataLoader, with lam / perm / t / noise injected.  The epoch loss of either path is
+    the oracle's (O.mixup -> loss and gradients -> clip -> AdamW, four times, in fp64) within 1e-5, and the two paths land on
+    the same parameters within 2e-5 * max|p|.
+
+    The post-epoch parameters are not held to the fp64 oracle element by element: AdamW's update m_hat / (sqrt(v_hat) + eps) is
+    steep wherever a step's gradient is small against its tensor's largest, so after four steps a gradient error of 1e-6 *
+    max|g| (a twentieth of the gradient tolerance) already moves hundreds of input_proj.weight elements of this model past
+    2e-5 * max|p|.  The epoch loss reads every step's parameters through a well-conditioned map instead."""
+    from osteosarcoma_diffusionmodel_amd.train import OsteosarcomaDataset
+    dims, hidden, rows, bs = REAL, H3, 64, 16
+    mut, expr, pw, cd = dims
+    D = mut + expr + pw
+    sd, data, cond, _, _, _ = _inputs(dims, hidden, rows)
+    gen = torch.Generator().manual_seed(99)
+    surv = torch.rand(rows, generator=gen) * 1000
+    lams = [0.9, 0.35, 0.6, 0.75]
+    perms = [torch.randperm(bs, generator=gen) for _ in range(4)]
+    ts = [torch.randint(0, 1000, (bs,), generator=gen) for _ in range(4)]
+    noises = [torch.randn(bs, D, generator=gen) for _ in range(4)]
+    names = list(sd)
+    p64 = {k: v.double().clone() for k, v in sd.items()}
+    m1 = [torch.zeros_like(p64[k]) for k in names]
+    v1 = [torch.zeros_like(p64[k]) for k in names]
+    ref_losses = []
+    for i in range(4):
+        sl = slice(i * bs, (i + 1) * bs)
+        d, cc, _ = O.mixup(data[sl].double(), cond[sl].double(), surv[sl].double(), lams[i], perms[i])
+        loss_i, g = oracle_train_fp64(p64, d, cc, ts[i], noises[i], hidden)
+        ref_losses.append(loss_i)
+        gl, _ = O.clip_grad_norm([g[k] for k in names], 1.0)
+        O.adamw_step([p64[k] for k in names], gl, m1, v1, i + 1, lr=LR, weight_decay=WD)
+    out = {}
+    for resident in (True, False):
+        conf = _train_conf(hidden, tmp_path, p=0.0, resident_dataset=resident)
+        conf["training"]["augmentation"] = {"mixup_alpha": 0.2}
+        ds = object.__new__(OsteosarcomaDataset)
+        ds.data, ds.conditions, ds.survival_days = data.clone(), cond.clone(), surv.clone()
+        loader = torch.utils.data.DataLoader(ds, batch_size=bs, shuffle=False, num_workers=0, drop_last=True)
+        m = BiologyAwareDiffusionModel(config=conf, mutation_dim=mut, expression_dim=expr, pathway_dim=pw, condition_dim=cd)
+        m.load_state_dict(sd, strict=False)
+        m = m.cuda()
+        tr = Trainer(m, loader, loader, conf, device="cuda")
+        step = {"i": 0}
+        tr.mixup.draw = lambda n, device: (lams[step["i"]], perms[step["i"]].to(device))
+        tr.mixup.draw_epoch = lambda sizes, device, seed_fn=None: (lams[:len(sizes)], [q.to(device) for q in perms[:len(sizes)]],
+                                                                   [None] * len(sizes))
+        orig = tr.train_step
+
+        def injected(*a, **k):
+            i = step["i"]
+            res = orig(*a, t=ts[i].cuda(), noise=noises[i].cuda(), **k)
+            step["i"] += 1
+            return res
+
+        tr.train_step = injected
+        avg = tr.train_epoch()
+        assert step["i"] == 4 and bool(tr.resident) == resident
+        path = _path(m)
+        assert_close(avg, float(np.mean(ref_losses)), LOSS_RTOL, what=f"epoch loss (resident={resident})")
+        _report(f"resident-{resident}", path=path)
+        assert path == FUSE | DUAL | COND | CE0 | WG_DIRECT | WG_GROUP, f"last_train_path {path:#x}"
+        out[resident] = {k: v.detach().cpu() for k, v in m.named_parameters()}
+    for k in out[True]:
+        assert_close(out[True][k], out[False][k], 2e-5, atol=1e-8, what=f"param {k}, resident vs DataLoader epoch")
+    # the epoch moved the parameters (the loss check is not vacuous)
+    assert not torch.equal(out[True]["unet.input_proj.weight"], sd["unet.input_proj.weight"])
