@@ -210,6 +210,26 @@ int osd_sample_chain(osd_handle *h, const float *cond, int64_t n, const float *x
  * OSD_EHIP from a synchronous call means the kernel did not even react to the abort flag (device hung). */
 int osd_sample_engine(osd_handle *h, int64_t n, int flags);
 
+/* osd_sample_chain over a caller-supplied step plan of n_steps <= T steps (strided DDIM sampling, Song et al. 2021).  Both
+ * arrays are on the host:
+ *   timesteps  [n_steps]     tau_s, the schedule timestep step s evaluates the denoiser at (its time-embedding row)
+ *   step_coef  [n_steps][4]  (A_s, B_s, C_s, 0): step s computes x' = A_s*x + B_s*eps + C_s*z with eps = denoiser(x, tau_s)
+ * The chain runs s = n_steps-1 first, down to s = 0.  x_T comes from the same Philox stream as osd_sample_chain's (step counter
+ * T), so the same seed / row_offset starts both from the same x_T; z of step s uses step counter s (so does train-mode dropout),
+ * and step 0 draws no z.  noises: dev [n_steps-1][n][D] in draw order s = n_steps-1 .. 1, or NULL -> Philox.  mut_mask_out is
+ * written by step 0.  Rows, chunks, engines and the OSD_F_SYNC re-run of a chain that gave up are those of osd_sample_chain;
+ * the identity plan (tau_s = s, the schedule's own A_t, B_t, C_t) computes its bits.  The library folds nothing: for DDIM from
+ * tau = tau_s to tau' = tau_{s-1} (abar' = 1 at s = 0) with abar = alphas_cumprod,
+ *   x0^ = (x - sqrt(1-abar)*eps) / sqrt(abar),  x' = sqrt(abar')*x0^ + sqrt(1 - abar' - sigma^2)*eps + sigma*z
+ *   sigma = eta * sqrt((1-abar') / (1-abar)) * sqrt(1 - abar/abar')
+ *   =>  A = sqrt(abar'/abar),  B = sqrt(1 - abar' - sigma^2) - sqrt(abar')*sqrt(1-abar)/sqrt(abar),  C = sigma
+ * (osteosarcoma_diffusionmodel_amd/ddim.py builds this plan).  OSD_EINVAL: n_steps outside [1, T], a tau outside [0, T), a
+ * non-finite coefficient, or C_0 != 0. */
+int osd_sample_chain_steps(osd_handle *h, const float *cond, int64_t n, const float *x_T,
+                           const float *noises, uint64_t seed, int64_t row_offset, float *x_out,
+                           float *mut_mask_out, int flags, const int32_t *timesteps,
+                           const float *step_coef, int32_t n_steps);
+
 /* Device-resident epoch path (utils/train.py:204-250 hands every batch over from host memory; here the dataset of
  * OsteosarcomaDataset (utils/train.py:22-82) stays in HBM).  The NEXT osd_train_loss_fwd_bwd on this handle takes its n rows
  * from the dataset instead of its x0 / cond arguments (pass NULL there):

@@ -3,8 +3,10 @@
 // Training entry points live in train.hip.
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <cmath>
 #include <new>
 #include "handle.h"
 #include "kernels.h"
@@ -159,7 +161,7 @@ int run_trunk(osd_handle* h, hipStream_t s, const FwdWs& ws, const TrunkIn& in) 
     g.F = a.H0; g.P = n; g.K = kx;
     if (in.a_unpacked) { g.A = h->params[pm.in_w]; g.lda = a.D; g.a_kmax = a.D; }
     g.ksplit = in.ksplit ? 1 : 0;
-    EpiInput::Args ea{h->params[pm.in_b], h->d_temb, a.H0, in.t_index, in.t_dev, in.t_imm, ws.cproj, a.H0, ws.h0, a.H0};
+    EpiInput::Args ea{h->params[pm.in_b], in.temb ? in.temb : h->d_temb, a.H0, in.t_index, in.t_dev, in.t_imm, ws.cproj, a.H0, ws.h0, a.H0};
     bool done = false;
     if (in.in_slices > 1 && in.in_slabs) {
       const hipError_t e = launch_input_splitk(s, g, ea, in.in_slabs, in.in_slices);
@@ -473,8 +475,12 @@ int osd_destroy(osd_handle* h) {
   e = hipDeviceSynchronize();
   for (auto& s : h->slots) free_slot(s, true);
   free_slot(h->main, false);
-  float* bufs[] = {h->w_in_packed, h->w_out_packed, h->b_out_packed, h->chain_xpad, h->d_sqrt_ac, h->d_sqrt_1m, h->d_coef, h->d_time_emb, h->d_temb, h->train_arena, h->loss_dev};
+  float* bufs[] = {h->w_in_packed, h->w_out_packed, h->b_out_packed, h->chain_xpad, h->d_sqrt_ac, h->d_sqrt_1m, h->d_coef, h->d_time_emb, h->d_temb, h->train_arena, h->loss_dev,
+                   h->plan_temb, h->plan_coef};
   for (float* p : bufs) if (p) e = hipFree(p);
+  if (h->plan_t) e = hipFree(h->plan_t);
+  if (h->plan_ev) e = hipEventDestroy(h->plan_ev);
+  free(h->plan_host);
   if (h->normsq_dev) e = hipFree(h->normsq_dev);
   if (h->parts_dev) e = hipFree(h->parts_dev);
   if (h->t_san) e = hipFree(h->t_san);
@@ -660,16 +666,16 @@ static int release_graph(Slot& sl) {
 }
 
 // One chunk of the reverse chain on one slot: rows [r0, r0+m).
-static int chain_chunk(osd_handle* h, Slot& sl, const float* cond, int64_t n_total, int64_t r0, int64_t m, const float* x_T,
-                       const float* noises, uint64_t seed, int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
+static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const float* cond, int64_t n_total, int64_t r0, int64_t m,
+                       const float* x_T, const float* noises, uint64_t seed, int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
   const Arch& a = h->arch;
-  const int D = a.D, T = a.T;
+  const int D = a.D, S = plan.n_steps;
   hipStream_t s = sl.stream;
   OSD_TRY(release_graph(sl));
   FwdWs ws;
   const int64_t need = carve_fwd(a, nullptr, m, false, &ws);
   // D % 4 != 0 with device-generated draws: the state of the chunk lives in a padded buffer behind the activations (rows of Dp
-  // floats, pad columns zero at the start) and is copied to the caller's rows at the end; injected draws ([T-1][n][D], rows not
+  // floats, pad columns zero at the start) and is copied to the caller's rows at the end; injected draws ([S-1][n][D], rows not
   // 16-byte aligned) keep the guarded kernels on the caller's tensor
   const bool padded = h->w_out_packed != nullptr && !noises;
   const int ldx = padded ? h->Dp : D;
@@ -706,21 +712,21 @@ static int chain_chunk(osd_handle* h, Slot& sl, const float* cond, int64_t n_tot
   // conditioning is loop-invariant in eval mode (no dropout inside the embedding MLP): hoisted
   OSD_TRY(run_cond(h, s, cond + r0 * a.cond_dim, m, ws));
   if (x_T) OSD_HIP(launch_copy2d(s, x_T + r0 * D, D, x, ldx, m, D));
-  else OSD_HIP(launch_fill_randn(s, x, ldx, m, D, seed, roff, (uint32_t)T, TAG_POSTERIOR));
-  OSD_HIP(launch_set_int(s, sl.t_dev, T - 1));
+  else OSD_HIP(launch_fill_randn(s, x, ldx, m, D, seed, roff, (uint32_t)a.T, TAG_POSTERIOR));
+  OSD_HIP(launch_set_int(s, sl.t_dev, S - 1));
 
   auto enqueue_step = [&](void) -> int {
     TrunkIn in{};
-    in.x = x; in.ldx = ldx; in.kx = ldx; in.n = m; in.t_dev = sl.t_dev; in.in_slabs = in_slabs; in.in_slices = in_slices;
+    in.x = x; in.ldx = ldx; in.kx = ldx; in.n = m; in.t_dev = sl.t_dev; in.temb = plan.temb; in.in_slabs = in_slabs; in.in_slices = in_slices;
     in.gn_slabs = in_slabs; in.gn_slices = gn_slices;
     in.ksplit = in_slices > 1;             // the small-batch mode already trades bit-equality with the chain kernel for latency: long-K layers on two wave groups
     in.train = train; in.seed = seed; in.row_offset = roff; in.drop_step_dev = sl.t_dev;
     OSD_TRY(run_trunk(h, s, ws, in));
     GemmArgs g = output_proj_args(h, ws, m, padded);
     EpiPosterior::Args ea{};
-    ea.bias = padded ? h->b_out_packed : h->params[a.pm.out_b]; ea.xin = x; ea.ldx = ldx; ea.xout = x; ea.ldo = ldx; ea.coef = h->d_coef;
+    ea.bias = padded ? h->b_out_packed : h->params[a.pm.out_b]; ea.xin = x; ea.ldx = ldx; ea.xout = x; ea.ldo = ldx; ea.coef = plan.coef;
     ea.t_dev = sl.t_dev; ea.t_imm = 0;
-    ea.z = noises ? noises + r0 * D : nullptr; ea.ldzz = D; ea.z_step_stride = (long long)n_total * D; ea.t_first = T - 1;
+    ea.z = noises ? noises + r0 * D : nullptr; ea.ldzz = D; ea.z_step_stride = (long long)n_total * D; ea.t_first = S - 1;
     ea.seed = seed; ea.row_offset = roff;
     ea.mut_mask = mut_mask_out ? mut_mask_out + r0 * h->cfg.mutation_dim : nullptr; ea.mutation_dim = h->cfg.mutation_dim;
     OSD_HIP(launch_posterior(s, g, ea));
@@ -740,24 +746,18 @@ static int chain_chunk(osd_handle* h, Slot& sl, const float* cond, int64_t n_tot
     // the exec object must outlive its launches: the slot keeps it until its next use
     sl.graph = graph;
     sl.exec = exec;
-    for (int it = 0; it < T; ++it) OSD_HIP(hipGraphLaunch(exec, s));
+    for (int it = 0; it < S; ++it) OSD_HIP(hipGraphLaunch(exec, s));
   } else {
-    for (int it = 0; it < T; ++it) OSD_TRY(enqueue_step());
+    for (int it = 0; it < S; ++it) OSD_TRY(enqueue_step());
   }
   if (padded) OSD_HIP(launch_copy2d(s, x, ldx, x_out + r0 * D, D, m, D));
   return OSD_OK;
 }
 
-int osd_sample_chain(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
-                     int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
-  OSD_TRY(check_ready(h));
-  OSD_TRY(check_rows(n));
-  if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
-  OSD_TRY(check_row_offset(row_offset, n));
-  if (n == 0) return OSD_OK;
-  OSD_HIP(hipSetDevice(h->cfg.device));
-  OSD_TRY(chain_check_status(h));            // a previous chain-kernel run that gave up is reported here at the latest
-  OSD_TRY(ensure_packed(h, h->stream));
+// The reverse chain of `plan` over n rows: osd_sample_chain and osd_sample_chain_steps after their argument checks, chain_check_status
+// and ensure_packed.
+static int sample_plan(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                       int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
   // bf16x3 split precision: eval-mode chains on the per-layer launches of split.hip (dropout inside the chain stays fp32)
   const bool split = h->precision == 1 && !((flags & OSD_F_TRAIN_MODE) && h->cfg.dropout_p > 0.f);
   h->last_precision = split ? 1 : 0;
@@ -766,7 +766,7 @@ int osd_sample_chain(osd_handle* h, const float* cond, int64_t n, const float* x
   if (h->last_engine == 1 && noises && h->w_out_packed && !chain_uses_squad(h, n)) h->last_engine = 0;      // injected draws at D % 4 != 0: guarded per-layer kernels (the squad chain reads any layout)
   bool fell_back = false;
   if (h->last_engine == 1) {
-    OSD_TRY(chain_run(h, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out));
+    OSD_TRY(chain_run(h, plan, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out));
     if (!(flags & OSD_F_SYNC)) return OSD_OK;       // asynchronous: a chain that gives up is reported by the next call on this handle
     int gave_up = 0;
     OSD_TRY(chain_finish(h, &gave_up));
@@ -802,8 +802,8 @@ int osd_sample_chain(osd_handle* h, const float* cond, int64_t n, const float* x
   for (int64_t c = 0; c < n_chunks && rc == OSD_OK; ++c) {
     const int64_t r0 = c * chunk;
     const int64_t m = std::min<int64_t>(chunk, n - r0);
-    if (split) rc = split_chain_chunk(h, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
-    else rc = chain_chunk(h, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
+    if (split) rc = split_chain_chunk(h, plan, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
+    else rc = chain_chunk(h, plan, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
   }
   // join
   for (int i = 0; i < n_slots; ++i) {
@@ -818,6 +818,69 @@ int osd_sample_chain(osd_handle* h, const float* cond, int64_t n, const float* x
     set_error("warning: the reverse-chain kernel gave up in a dependency wait; the chain was re-run on the per-layer kernels (%s)",
               h->last_chain_variant == 3 ? "results agree with the squad chain's to fp32 rounding" : "same results");
   return OSD_OK;
+}
+
+int osd_sample_chain(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                     int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
+  OSD_TRY(check_ready(h));
+  OSD_TRY(check_rows(n));
+  if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
+  OSD_TRY(check_row_offset(row_offset, n));
+  if (n == 0) return OSD_OK;
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  OSD_TRY(chain_check_status(h));            // a previous chain-kernel run that gave up is reported here at the latest
+  OSD_TRY(ensure_packed(h, h->stream));
+  return sample_plan(h, StepPlan{h->arch.T, h->d_temb, h->d_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
+}
+
+// The tables of osd_sample_chain_steps' plan, on the handle's stream: coefficients and timesteps uploaded from the handle's host
+// staging, temb rows gathered from d_temb (which ensure_packed has just brought up to date with the parameters).  An earlier call's
+// chunks on the slot streams have joined h->stream, so nothing still reads the tables this overwrites.
+static int upload_plan(osd_handle* h, const int32_t* timesteps, const float* step_coef, int S) {
+  const Arch& a = h->arch;
+  hipStream_t s = h->stream;
+  if (!h->plan_host) {
+    h->plan_host = malloc((size_t)a.T * 5 * 4);                    // [T][4] coefficients, then [T] timesteps
+    if (!h->plan_host) { set_error("out of host memory"); return OSD_ENOMEM; }
+    OSD_HIP(hipEventCreateWithFlags(&h->plan_ev, hipEventDisableTiming));
+    OSD_HIP(hipMalloc((void**)&h->plan_temb, (size_t)a.T * a.H0 * 4));
+    OSD_HIP(hipMalloc((void**)&h->plan_coef, (size_t)a.T * 4 * 4));
+    OSD_HIP(hipMalloc((void**)&h->plan_t, (size_t)a.T * 4));
+  }
+  OSD_HIP(hipEventSynchronize(h->plan_ev));          // the previous call's upload has read the staging
+  float* hc = static_cast<float*>(h->plan_host);
+  int32_t* ht = reinterpret_cast<int32_t*>(hc + (size_t)a.T * 4);
+  memcpy(hc, step_coef, (size_t)S * 4 * 4);
+  memcpy(ht, timesteps, (size_t)S * 4);
+  OSD_HIP(hipMemcpyAsync(h->plan_coef, hc, (size_t)S * 4 * 4, hipMemcpyHostToDevice, s));
+  OSD_HIP(hipMemcpyAsync(h->plan_t, ht, (size_t)S * 4, hipMemcpyHostToDevice, s));
+  OSD_HIP(hipEventRecord(h->plan_ev, s));
+  OSD_HIP(launch_gather_rows(s, h->d_temb, a.H0, h->plan_t, S, h->plan_temb));
+  return OSD_OK;
+}
+
+int osd_sample_chain_steps(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                           int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
+                           const float* step_coef, int32_t n_steps) {
+  OSD_TRY(check_ready(h));
+  OSD_TRY(check_rows(n));
+  if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
+  if (!timesteps || !step_coef) { set_error("null step plan"); return OSD_EINVAL; }
+  const Arch& a = h->arch;
+  if (n_steps < 1 || n_steps > a.T) { set_error("n_steps=%d outside [1,%d]", n_steps, a.T); return OSD_EINVAL; }
+  for (int s = 0; s < n_steps; ++s) {
+    if (timesteps[s] < 0 || timesteps[s] >= a.T) { set_error("timesteps[%d]=%d outside [0,%d)", s, timesteps[s], a.T); return OSD_EINVAL; }
+    for (int k = 0; k < 4; ++k)
+      if (!std::isfinite(step_coef[4 * s + k])) { set_error("step_coef[%d] is not finite", 4 * s + k); return OSD_EINVAL; }
+  }
+  if (step_coef[2] != 0.f) { set_error("step_coef[2] = C_0 = %g: the last step draws no z, so C_0 must be 0", (double)step_coef[2]); return OSD_EINVAL; }
+  OSD_TRY(check_row_offset(row_offset, n));
+  if (n == 0) return OSD_OK;
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  OSD_TRY(chain_check_status(h));
+  OSD_TRY(ensure_packed(h, h->stream));
+  OSD_TRY(upload_plan(h, timesteps, step_coef, n_steps));
+  return sample_plan(h, StepPlan{n_steps, h->plan_temb, h->plan_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
 }
 
 int osd_sample_engine(osd_handle* h, int64_t n, int flags) {

@@ -262,7 +262,7 @@ __device__ __forceinline__ void chain_posterior(f32x16 (&acc)[NFB][NPB], const f
         const float4 xq = xp.get(pb, q, l31, h);
         const float xv[4] = {xq.x, xq.y, xq.z, xq.w};
         float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (t > 0) {
+        if (t > 0 && cC != 0.f) {           // C = 0: no draw (EpiPosterior)
           if (zrow) {
             const int fc = (!GUARD || fo < pcol - 4) ? fo : pcol - 4;
             zz = ldg4(zrow + (size_t)pc * ldzz + fc);

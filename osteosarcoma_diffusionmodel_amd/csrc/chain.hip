@@ -200,19 +200,19 @@ int chain_finish(osd_handle* h, int* gave_up) {
   return OSD_OK;
 }
 
-int chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed, int64_t row_offset,
+int chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed, int64_t row_offset,
               float* x_out, float* mut_mask_out) {
   const Arch& a = h->arch;
-  const int T = a.T, H0 = a.H0;
+  const int S = plan.n_steps, H0 = a.H0;
   hipStream_t s = h->stream;
   OSD_TRY(chain_check_status(h));
   if (chain_uses_squad(h, n)) {
     h->last_chain_variant = 3;
-    return squad_chain_run(h, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out);
+    return squad_chain_run(h, plan, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out);
   }
   if (chain_use_panel(h, n)) {
     h->last_chain_variant = 2;
-    return panel_chain_run(h, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out);
+    return panel_chain_run(h, plan, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out);
   }
   h->last_chain_variant = 1;
   // D % 4 != 0: the kernel works on an internal copy of the state with rows of Dp = roundup(D, 4) floats (pad columns start at
@@ -229,7 +229,7 @@ int chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_T, con
   // chain_grid > 0 sets the workgroup count (tests): below the tile count it forces every hand-off across workgroups, above it
   // the surplus workgroups start on later steps of a tile and wait for the earlier ones
   int grid = std::min(n_tiles, max_grid);
-  if (h->chain_grid > 0) grid = (int)std::min<int64_t>(std::min(h->chain_grid, max_grid), (int64_t)n_tiles * T);
+  if (h->chain_grid > 0) grid = (int)std::min<int64_t>(std::min(h->chain_grid, max_grid), (int64_t)n_tiles * S);
 
   // ---- per-slot activation workspace.  Buffers: h0, and (mid, out) of every block, each [128][C]; a buffer is live from the
   // layer that writes it to the last layer that reads it (block outputs of the encoder live on until their decoder block pops
@@ -287,7 +287,7 @@ int chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_T, con
     OSD_HIP(hipMemsetAsync(xs, 0, (size_t)n * D * 4, s));
   }
   if (x_T) OSD_HIP(launch_copy2d(s, x_T, a.D, xs, D, n, a.D));
-  else OSD_HIP(launch_fill_randn(s, xs, D, n, a.D, seed, (uint32_t)row_offset, (uint32_t)T, TAG_POSTERIOR));
+  else OSD_HIP(launch_fill_randn(s, xs, D, n, a.D, seed, (uint32_t)row_offset, (uint32_t)a.T, TAG_POSTERIOR));
 
   OSD_TRY(chain_ensure_sync(h, n_tiles, s));
   ca.status = h->chain_sync;
@@ -335,14 +335,14 @@ int chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_T, con
   }
   ca.n_layers = nl;
   ca.x = xs; ca.D = D; ca.n = (int)n; ca.n_tiles = n_tiles;
-  ca.cproj = cw.cproj; ca.ldc = H0; ca.temb = h->d_temb; ca.ldt = H0; ca.coef = h->d_coef;
-  ca.z = noises; ca.ldzz = D; ca.z_step_stride = (long long)n * D; ca.z_t_first = T - 1;
+  ca.cproj = cw.cproj; ca.ldc = H0; ca.temb = plan.temb; ca.ldt = H0; ca.coef = plan.coef;
+  ca.z = noises; ca.ldzz = D; ca.z_step_stride = (long long)n * D; ca.z_t_first = S - 1;
   ca.seed = seed; ca.row_offset = (uint32_t)row_offset;
   ca.mut_mask = mut_mask_out; ca.mutation_dim = h->cfg.mutation_dim;
 
   // ---- launches: the whole chain in one, or segments of chain_steps_per_launch steps (progress carries over) ----
-  const int seg = h->chain_steps_per_launch > 0 ? h->chain_steps_per_launch : T;
-  const int n_launch = (T + seg - 1) / seg;
+  const int seg = h->chain_steps_per_launch > 0 ? h->chain_steps_per_launch : S;
+  const int n_launch = (S + seg - 1) / seg;
   OSD_HIP(hipStreamSynchronize(s));        // the host copies are about to be rewritten: earlier uploads must have been consumed
   if (h->chain_args_cap < n_launch) {
     if (h->chain_args_dev) { OSD_HIP(hipFree(h->chain_args_dev)); h->chain_args_dev = nullptr; }
@@ -355,9 +355,9 @@ int chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_T, con
   }
   ChainArgs* const host_args = static_cast<ChainArgs*>(h->chain_args_host);
   int launch = 0;
-  for (int done = 0; done < T; done += seg) {
-    ca.t_first = T - 1 - done;
-    ca.n_steps = std::min(seg, T - done);
+  for (int done = 0; done < S; done += seg) {
+    ca.t_first = S - 1 - done;
+    ca.n_steps = std::min(seg, S - done);
     ca.base_done = (unsigned)done;
     if (done > 0) {                       // per-launch words: the unit queue and the CU arrival counters (status and progress carry over)
       OSD_HIP(hipMemsetAsync(ca.queue, 0, 4, s));
@@ -383,8 +383,8 @@ int chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_T, con
     double flop_row = 0;
     for (int l = 0; l < nl; ++l) flop_row += 2.0 * ca.L[l].K * ca.L[l].F;
     const double unit_ms = 128.0 * flop_row / 0.237e12 * 1e3;
-    double rounds = (double)(((int64_t)n_tiles * T + grid - 1) / grid);
-    if (grid >= n_tiles) rounds = std::max(rounds, (double)T);        // the steps of a tile are serial
+    double rounds = (double)(((int64_t)n_tiles * S + grid - 1) / grid);
+    if (grid >= n_tiles) rounds = std::max(rounds, (double)S);        // the steps of a tile are serial
     h->chain_expected_ms = rounds * unit_ms;
   }
   return OSD_OK;

@@ -231,10 +231,10 @@ int panel_chain_slots(osd_handle* h) {
   return panel_device_limits(h->cfg.device, &g) == OSD_OK ? g : 0;
 }
 
-int panel_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed, int64_t row_offset,
-                    float* x_out, float* mut_mask_out) {
+int panel_chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                    int64_t row_offset, float* x_out, float* mut_mask_out) {
   const Arch& a = h->arch;
-  const int T = a.T, H0 = a.H0;
+  const int S = plan.n_steps, H0 = a.H0;
   hipStream_t s = h->stream;
   const bool padded = h->w_out_packed != nullptr;
   if (padded && noises) { set_error("internal: injected draws with D %% 4 != 0 run on the per-layer kernels"); return OSD_EUNSUPPORTED; }
@@ -247,7 +247,7 @@ int panel_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_
   if (max_grid < 1) { set_error("the LDS-resident chain kernel does not fit this device"); return OSD_EUNSUPPORTED; }
   const int n_tiles = (int)((n + PC_BP - 1) / PC_BP);
   int grid = std::min(n_tiles, max_grid);
-  if (h->chain_grid > 0) grid = (int)std::min<int64_t>(std::min(h->chain_grid, max_grid), (int64_t)n_tiles * T);
+  if (h->chain_grid > 0) grid = (int)std::min<int64_t>(std::min(h->chain_grid, max_grid), (int64_t)n_tiles * S);
 
   PanelArgs pa{};
   pa.ws_stride = p.ws_stride;
@@ -271,7 +271,7 @@ int panel_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_
     OSD_HIP(hipMemsetAsync(xs, 0, (size_t)n * D * 4, s));
   }
   if (x_T) OSD_HIP(launch_copy2d(s, x_T, a.D, xs, D, n, a.D));
-  else OSD_HIP(launch_fill_randn(s, xs, D, n, a.D, seed, (uint32_t)row_offset, (uint32_t)T, TAG_POSTERIOR));
+  else OSD_HIP(launch_fill_randn(s, xs, D, n, a.D, seed, (uint32_t)row_offset, (uint32_t)a.T, TAG_POSTERIOR));
 
   OSD_TRY(chain_ensure_sync(h, n_tiles, s));
   pa.status = h->chain_sync;
@@ -294,14 +294,14 @@ int panel_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_
   }
   pa.n_layers = p.n_layers;
   pa.x = xs; pa.ldx = D; pa.D = D; pa.n = (int)n; pa.n_tiles = n_tiles;
-  pa.cproj = cw.cproj; pa.ldc = H0; pa.temb = h->d_temb; pa.ldt = H0; pa.coef = h->d_coef;
-  pa.z = noises; pa.ldzz = D; pa.z_step_stride = (long long)n * D; pa.z_t_first = T - 1;
+  pa.cproj = cw.cproj; pa.ldc = H0; pa.temb = plan.temb; pa.ldt = H0; pa.coef = plan.coef;
+  pa.z = noises; pa.ldzz = D; pa.z_step_stride = (long long)n * D; pa.z_t_first = S - 1;
   pa.seed = seed; pa.row_offset = (uint32_t)row_offset;
   pa.mut_mask = mut_mask_out; pa.mutation_dim = h->cfg.mutation_dim;
   pa.cp_base = p.cp_base; pa.xp_base = p.xp_base;
 
-  const int seg = h->chain_steps_per_launch > 0 ? h->chain_steps_per_launch : T;
-  const int n_launch = (T + seg - 1) / seg;
+  const int seg = h->chain_steps_per_launch > 0 ? h->chain_steps_per_launch : S;
+  const int n_launch = (S + seg - 1) / seg;
   OSD_HIP(hipStreamSynchronize(s));
   if (h->panel_args_cap < n_launch) {
     if (h->panel_args_dev) { OSD_HIP(hipFree(h->panel_args_dev)); h->panel_args_dev = nullptr; }
@@ -314,9 +314,9 @@ int panel_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_
   }
   PanelArgs* const host_args = static_cast<PanelArgs*>(h->panel_args_host);
   int launch = 0;
-  for (int done = 0; done < T; done += seg) {
-    pa.t_first = T - 1 - done;
-    pa.n_steps = std::min(seg, T - done);
+  for (int done = 0; done < S; done += seg) {
+    pa.t_first = S - 1 - done;
+    pa.n_steps = std::min(seg, S - done);
     pa.base_done = (unsigned)done;
     if (done > 0) OSD_HIP(hipMemsetAsync(pa.queue, 0, 4, s));
     host_args[launch] = pa;
@@ -337,8 +337,8 @@ int panel_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_
     double flop_row = 0;
     for (int l = 0; l < p.n_layers; ++l) flop_row += 2.0 * p.L[l].K8 * 8 * p.L[l].F;
     const double unit_ms = 64.0 * flop_row / 0.5e12 * 1e3;
-    double rounds = (double)(((int64_t)n_tiles * T + grid - 1) / grid);
-    if (grid >= n_tiles) rounds = std::max(rounds, (double)T);
+    double rounds = (double)(((int64_t)n_tiles * S + grid - 1) / grid);
+    if (grid >= n_tiles) rounds = std::max(rounds, (double)S);
     h->chain_expected_ms = rounds * unit_ms;
   }
   return OSD_OK;

@@ -434,7 +434,7 @@ __global__ __launch_bounds__(SQ_THREADS, WPC) void squad_chain_kernel(const Squa
         const float e[4] = {e0 + bv.x, e1 + bv.y, e2 + bv.z, e3 + bv.w};
         const float xv[4] = {xv4.x, xv4.y, xv4.z, xv4.w};
         float zv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (t > 0) {
+        if (t > 0 && cC != 0.f) {           // C = 0: no draw (EpiPosterior)
           if (zbase) {
             const float* zr = zbase + (size_t)rowc * a.ldzz;
 #pragma unroll

@@ -196,10 +196,10 @@ static int squad_pack(osd_handle* h, hipStream_t s, const SquadPlan& p, int rp) 
   return OSD_OK;
 }
 
-int squad_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed, int64_t row_offset,
-                    float* x_out, float* mut_mask_out) {
+int squad_chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                    int64_t row_offset, float* x_out, float* mut_mask_out) {
   const Arch& a = h->arch;
-  const int T = a.T, H0 = a.H0, D = a.D;
+  const int S = plan.n_steps, H0 = a.H0, D = a.D;
   hipStream_t s = h->stream;
   const int wpc = squad_wpc(h, n);
   if (wpc < 1) { set_error("internal: %lld rows are more than the squad chain keeps resident", (long long)n); return OSD_EUNSUPPORTED; }
@@ -220,7 +220,7 @@ int squad_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_
 
   // the chain state lives in the caller's rows between launches (any D: the kernel reads and writes it element-wise)
   if (x_T) { if (x_T != x_out) OSD_HIP(launch_copy2d(s, x_T, D, x_out, D, n, D)); }
-  else OSD_HIP(launch_fill_randn(s, x_out, D, n, D, seed, (uint32_t)row_offset, (uint32_t)T, TAG_POSTERIOR));
+  else OSD_HIP(launch_fill_randn(s, x_out, D, n, D, seed, (uint32_t)row_offset, (uint32_t)a.T, TAG_POSTERIOR));
 
   SquadArgs sa{};
   const int64_t xs_stride = (int64_t)p.T32 * rp * rp;              // tiles of rp features x rp patients
@@ -249,13 +249,13 @@ int squad_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_
   sa.out_off = (int)p.out_off; sa.bias_out = h->squad_wpk[slot] + p.bias_off;
   sa.T32 = p.T32; sa.h0_out = p.h0_out; sa.last_in = p.last_in; sa.K8_out = p.K8_out;
   sa.x = x_out; sa.ldx = D; sa.D = D; sa.n = (int)n;
-  sa.cproj = cw.cproj; sa.ldc = H0; sa.temb = h->d_temb; sa.ldt = H0; sa.coef = h->d_coef;
-  sa.z = noises; sa.ldzz = D; sa.z_step_stride = (long long)n * D; sa.z_t_first = T - 1;
+  sa.cproj = cw.cproj; sa.ldc = H0; sa.temb = plan.temb; sa.ldt = H0; sa.coef = plan.coef;
+  sa.z = noises; sa.ldzz = D; sa.z_step_stride = (long long)n * D; sa.z_t_first = S - 1;
   sa.seed = seed; sa.row_offset = (uint32_t)row_offset;
   sa.mut_mask = mut_mask_out; sa.mutation_dim = h->cfg.mutation_dim;
 
-  const int seg = h->chain_steps_per_launch > 0 ? h->chain_steps_per_launch : T;
-  const int n_launch = (T + seg - 1) / seg;
+  const int seg = h->chain_steps_per_launch > 0 ? h->chain_steps_per_launch : S;
+  const int n_launch = (S + seg - 1) / seg;
   OSD_HIP(hipStreamSynchronize(s));
   if (h->squad_args_cap < n_launch) {
     if (h->squad_args_dev) { OSD_HIP(hipFree(h->squad_args_dev)); h->squad_args_dev = nullptr; }
@@ -270,9 +270,9 @@ int squad_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_
   const int grid = n_panels * SQ_S;
   const int lds = rp == 32 ? sq_lds_bytes(p.n_layers) : sq16_lds_bytes(p.n_layers);
   int launch = 0;
-  for (int done = 0; done < T; done += seg) {
-    sa.t_first = T - 1 - done;
-    sa.n_steps = std::min(seg, T - done);
+  for (int done = 0; done < S; done += seg) {
+    sa.t_first = S - 1 - done;
+    sa.n_steps = std::min(seg, S - done);
     if (done > 0) OSD_HIP(hipMemsetAsync(sa.bar, 0, (size_t)n_panels * 16 * 4, s));      // a launch counts its barriers from zero
     host_args[launch] = sa;
     const SquadArgs* dargs = static_cast<const SquadArgs*>(h->squad_args_dev) + launch;
@@ -293,7 +293,7 @@ int squad_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_
   }
   h->chain_pending = true;
   h->last_squad_rp = rp;
-  h->chain_expected_ms = (double)T * 0.5 * wpc;       // measured: 0.1-0.2 ms per step; generous (chain.hip multiplies by 10 and adds 2 s)
+  h->chain_expected_ms = (double)S * 0.5 * wpc;       // measured: 0.1-0.2 ms per step; generous (chain.hip multiplies by 10 and adds 2 s)
   return OSD_OK;
 }
 

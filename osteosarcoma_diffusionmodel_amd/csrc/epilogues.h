@@ -420,6 +420,7 @@ struct EpiPosterior {
     uint64_t seed; uint32_t row_offset;
     float* mut_mask; int mutation_dim;   // written at t == 0 when non-null: (x' > 0.5)
   };
+  // a step whose C is 0 (DDIM at eta = 0, and t == 0) draws no z: the Philox generator bounds this launch
   static bool fast_ok(const Args& a, int F) {
     return F % 4 == 0 && al16(a.bias) && al16(a.xin) && al16(a.xout) && a.ldx % 4 == 0 && a.ldo % 4 == 0 &&
            (!a.z || (al16(a.z) && a.ldzz % 4 == 0 && a.z_step_stride % 4 == 0));
@@ -471,7 +472,7 @@ struct EpiPosterior {
           const float e[4] = {acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w};
           const float xv[4] = {x.x, x.y, x.z, x.w};
           float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (t > 0) {
+          if (t > 0 && cC != 0.f) {          // C = 0 (eta = 0 DDIM steps; t = 0): no draw.  Uniform: the step's table row
             if (zbase) zz = ldq<FAST>(zbase + (size_t)pc * a.ldzz, f, F);
             else zz = randn4(a.seed, a.row_offset + (uint32_t)p, (uint32_t)(f >> 2), (uint32_t)t, TAG_POSTERIOR);
           }

@@ -17,6 +17,7 @@ struct TrunkIn {
   int kx;                        // K extent of input_proj: 0 = D; Dp when x is the padded chain state (handle.h)
   const int* t_index;            // per-row t (training) or null
   const int* t_dev; int t_imm;   // shared t: device counter (sampling chain) or immediate
+  const float* temb;             // rows a shared t reads: null = the handle's [T][H0] table (d_temb), else a chain's step plan (StepPlan)
   bool input_only;               // stop after input_proj (the blocks run elsewhere: train_squad.h)
   bool train;                    // dropout active
   bool save;                     // keep pre-norm activations + GroupNorm statistics for backward
@@ -38,7 +39,7 @@ int check_rows(int64_t n);
 bool chain_supported(const Arch& a);
 int chain_pick_engine(osd_handle* h, int64_t n, int flags);
 bool chain_uses_squad(osd_handle* h, int64_t n);
-int chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed, int64_t row_offset,
+int chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed, int64_t row_offset,
               float* x_out, float* mut_mask_out);
 int chain_check_status(osd_handle* h);
 int chain_finish(osd_handle* h, int* gave_up);
@@ -49,14 +50,14 @@ int chain_ensure_sync(osd_handle* h, int64_t n_tiles, hipStream_t s);
 bool panel_chain_supported(const osd_handle* h);
 int panel_chain_slots(osd_handle* h);
 int panel_chain_pack(osd_handle* h, hipStream_t s);
-int panel_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed, int64_t row_offset,
+int panel_chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed, int64_t row_offset,
                     float* x_out, float* mut_mask_out);
 void panel_chain_free(osd_handle* h);
 hipError_t launch_pack_fragments(hipStream_t s, const float* w, int ldw, int F, int K, int nfbg, int K8, float* dst);
 // chain_squad.hip
 bool squad_chain_supported(const osd_handle* h);
 bool squad_window(osd_handle* h, int64_t n);
-int squad_chain_run(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed, int64_t row_offset,
+int squad_chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed, int64_t row_offset,
                     float* x_out, float* mut_mask_out);
 void squad_chain_free(osd_handle* h);
 // train_squad.h (host side in chain_squad.hip): the training forward trunk as one launch of squads

@@ -296,7 +296,8 @@ struct EpiB3Post : EpiB3Base {
     const int f = c.f0 + c.fl + 32 * fb + 8 * q + 4 * (c.lane >> 5);
     return randn4(a.seed, a.row_offset + (uint32_t)p, (uint32_t)(f >> 2), (uint32_t)t, TAG_POSTERIOR);
   }
-  static __device__ __forceinline__ bool rng_on(const Args& a, const State& st) { return st.t > 0 && !a.z; }      // uniform
+  // uniform; C = 0 (eta = 0 DDIM steps) draws no z (EpiPosterior)
+  static __device__ __forceinline__ bool rng_on(const Args& a, const State& st) { return st.t > 0 && !a.z && a.coef[4 * st.t + 2] != 0.f; }
   static __device__ __forceinline__ void kstep(State& st, const Args& a, const B3Ctx& c, int i) { st.z[i] = draw(a, c, st.t, i); }
   // x_t tile of the wave -> LDS: piece i = rows 4 i .. 4 i + 3, 256 bytes each; lane L holds position L % 16 of row 4 i + L / 16,
   // which is source chunk (L % 16) ^ (row & 15).  Rows beyond P / chunks beyond F re-read valid ones (never stored).
@@ -338,7 +339,7 @@ struct EpiB3Post : EpiB3Base {
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb) {
           float zv[4] = {0.f, 0.f, 0.f, 0.f};
-          if (t > 0) {
+          if (t > 0 && cC != 0.f) {
             if (zbase) {
               const int p = c.p0w + 32 * pb + l31;
               const size_t zo = (size_t)(p < c.P ? p : c.P - 1) * a.ldzz;

@@ -60,6 +60,16 @@ struct Arch {
 
 int build_arch(const osd_config& cfg, Arch* a);
 
+// What one reverse chain runs: n_steps steps t = n_steps - 1 .. 0, step t reading row t of temb [n_steps][H0]
+// (time_proj(TimeEmbedding(tau / T)) of the step's timestep tau) and of coef [n_steps][4] = (A, B, C, 0), x' = A x + B eps + C z.
+// Philox draws of step t use step counter t, injected draws sit at noises[n_steps - 1 - t].  The DDPM chain of osd_sample_chain
+// is {T, d_temb, d_coef}; osd_sample_chain_steps gathers a strided plan into the handle's plan_temb / plan_coef.
+struct StepPlan {
+  int n_steps;
+  const float* temb;
+  const float* coef;
+};
+
 // Forward activations of one row chunk (all device pointers into one arena).
 struct FwdWs {
   float* ce1;     // [n][64]   SiLU(Linear(cond))
@@ -107,6 +117,10 @@ struct osd_handle {
   float* b_out_packed = nullptr;     // [Dp]
   float* chain_xpad = nullptr; int64_t chain_xpad_floats = 0;     // padded chain state of the chain kernel [n][Dp]
   float *d_sqrt_ac = nullptr, *d_sqrt_1m = nullptr, *d_coef = nullptr, *d_time_emb = nullptr, *d_temb = nullptr;
+  // the step plan of osd_sample_chain_steps (StepPlan): gathered temb rows [T][H0], coefficients [T][4], timesteps [T] (allocated on
+  // first use); plan_host stages the coefficient + timestep upload and is rewritten only after plan_ev says the copy was consumed
+  float* plan_temb = nullptr; float* plan_coef = nullptr; int* plan_t = nullptr;
+  void* plan_host = nullptr; hipEvent_t plan_ev = nullptr;
   int64_t chunk_rows = 65536;
   int n_streams = 2;
   std::vector<osd::Slot> slots;

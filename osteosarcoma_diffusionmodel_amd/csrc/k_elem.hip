@@ -8,6 +8,18 @@ __global__ void k_add_int(int* p, int d) { *p += d; }
 hipError_t launch_set_int(hipStream_t s, int* p, int v) { hipLaunchKernelGGL(k_set_int, 1, 1, 0, s, p, v); return hipGetLastError(); }
 hipError_t launch_add_int(hipStream_t s, int* p, int d) { hipLaunchKernelGGL(k_add_int, 1, 1, 0, s, p, d); return hipGetLastError(); }
 
+// dst[r][:] = src[idx[r]][:], one workgroup per row (the caller keeps idx inside src's rows)
+__global__ void k_gather_rows(const float* src, int cols, const int* idx, float* dst) {
+  const float* s = src + (size_t)idx[blockIdx.x] * cols;
+  float* d = dst + (size_t)blockIdx.x * cols;
+  for (int c = threadIdx.x; c < cols; c += blockDim.x) d[c] = s[c];
+}
+hipError_t launch_gather_rows(hipStream_t s, const float* src, int cols, const int* idx, int rows, float* dst) {
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gather_rows, rows, 256, 0, s, src, cols, idx, dst);
+  return hipGetLastError();
+}
+
 static inline int ew_grid(int64_t work) {
   int64_t b = (work + 255) / 256;
   if (b > 8192) b = 8192;

@@ -41,6 +41,7 @@ hipError_t launch_gn_silu_splitk(hipStream_t s, const GemmArgs& g, const GnArgs&
 // k_elem.hip -----------------------------------------------------------------------
 hipError_t launch_set_int(hipStream_t s, int* p, int v);
 hipError_t launch_add_int(hipStream_t s, int* p, int d);
+hipError_t launch_gather_rows(hipStream_t s, const float* src, int cols, const int* idx, int rows, float* dst);   // dst[r] = src[idx[r]]
 hipError_t launch_fill_randn(hipStream_t s, float* out, int ld, int64_t rows, int cols, uint64_t seed,
                              uint32_t row_offset, uint32_t step, uint32_t tag);
 hipError_t launch_copy2d(hipStream_t s, const float* src, int lds, float* dst, int ldd, int64_t rows, int cols);

@@ -130,6 +130,7 @@ static int64_t carve_split(const Arch& a, float* base, int64_t n, SplitWs* ws) {
 
 struct SplitStep {
   const int* t_index; const int* t_dev; int t_imm;
+  const float* temb;             // rows the step index reads: the handle's [T][H0] table, or a chain's step plan (StepPlan)
 };
 
 // input_proj + blocks on planes; result in ws.out[n_blocks - 1]
@@ -140,7 +141,7 @@ static int split_trunk(osd_handle* h, hipStream_t s, const SplitWs& ws, int64_t 
   {
     const int nkb = b3_nkb(a.D);
     Bf3Args g{p.w_in, nkb, ws.xpl, nkb, nullptr, 0, a.H0, (int)n, nullptr};
-    EpiB3Input::Args ea{h->params[pm.in_b], h->d_temb, a.H0, st.t_index, st.t_dev, st.t_imm, ws.cond.cproj, a.H0, B3Out{ws.h0, b3_nkb(a.H0)}};
+    EpiB3Input::Args ea{h->params[pm.in_b], st.temb, a.H0, st.t_index, st.t_dev, st.t_imm, ws.cond.cproj, a.H0, B3Out{ws.h0, b3_nkb(a.H0)}};
     OSD_HIP(launch_b3<EpiB3Input>(s, g, ea));
   }
   const uint4* cur = ws.h0;
@@ -184,7 +185,7 @@ int split_denoiser_forward(osd_handle* h, const float* x, const int* t_idx, int3
   carve_split(a, h->main.arena, n, &ws);
   OSD_TRY(run_cond(h, s, cond, n, ws.cond));
   OSD_HIP(launch_pack(s, x, a.D, n, a.D, ws.xpl));
-  OSD_TRY(split_trunk(h, s, ws, n, SplitStep{t_idx, nullptr, t_all}));
+  OSD_TRY(split_trunk(h, s, ws, n, SplitStep{t_idx, nullptr, t_all, h->d_temb}));
   OSD_HIP(launch_b3<EpiB3Bias>(s, split_out_args(h, ws, n), EpiB3Bias::Args{h->params[a.pm.out_b], eps, a.D}));
   h->last_precision = 1;
   return OSD_OK;
@@ -202,7 +203,7 @@ int split_p_sample_step(osd_handle* h, const float* x_t, int32_t t, const float*
   OSD_TRY(run_cond(h, s, cond, n, ws.cond));
   OSD_HIP(launch_pack(s, x_t, a.D, n, a.D, ws.xpl));
   if (x_out != x_t) OSD_HIP(hipMemcpyAsync(x_out, x_t, (size_t)n * a.D * 4, hipMemcpyDeviceToDevice, s));
-  OSD_TRY(split_trunk(h, s, ws, n, SplitStep{nullptr, nullptr, t}));
+  OSD_TRY(split_trunk(h, s, ws, n, SplitStep{nullptr, nullptr, t, h->d_temb}));
   EpiB3Post::Args ea{};
   ea.bias = h->params[a.pm.out_b]; ea.x = x_out; ea.ldx = a.D; ea.coef = h->d_coef; ea.t_dev = nullptr; ea.t_imm = t;
   ea.z = z; ea.ldzz = a.D; ea.z_step_stride = 0; ea.t_first = t; ea.seed = seed; ea.row_offset = (uint32_t)row_offset;
@@ -223,10 +224,10 @@ static int release_graph(Slot& sl) {
 }
 
 // One chunk of the reverse chain on one slot: rows [r0, r0 + m).  The fp32 state lives in the caller's output rows.
-int split_chain_chunk(osd_handle* h, Slot& sl, const float* cond, int64_t n_total, int64_t r0, int64_t m, const float* x_T, const float* noises,
-                      uint64_t seed, int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
+int split_chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const float* cond, int64_t n_total, int64_t r0, int64_t m, const float* x_T,
+                      const float* noises, uint64_t seed, int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
   const Arch& a = h->arch;
-  const int D = a.D, T = a.T;
+  const int D = a.D, S = plan.n_steps;
   hipStream_t s = sl.stream;
   OSD_TRY(release_graph(sl));
   SplitWs ws;
@@ -237,15 +238,15 @@ int split_chain_chunk(osd_handle* h, Slot& sl, const float* cond, int64_t n_tota
   const uint32_t roff = (uint32_t)(row_offset + r0);
   OSD_TRY(run_cond(h, s, cond + r0 * a.cond_dim, m, ws.cond));       // loop-invariant in eval mode: hoisted (api.hip: chain_chunk)
   if (x_T) { if (x_T + r0 * D != x) OSD_HIP(launch_copy2d(s, x_T + r0 * D, D, x, D, m, D)); }
-  else OSD_HIP(launch_fill_randn(s, x, D, m, D, seed, roff, (uint32_t)T, TAG_POSTERIOR));
+  else OSD_HIP(launch_fill_randn(s, x, D, m, D, seed, roff, (uint32_t)a.T, TAG_POSTERIOR));
   OSD_HIP(launch_pack(s, x, D, m, D, ws.xpl));
-  OSD_HIP(launch_set_int(s, sl.t_dev, T - 1));
+  OSD_HIP(launch_set_int(s, sl.t_dev, S - 1));
 
   auto enqueue_step = [&](void) -> int {
-    OSD_TRY(split_trunk(h, s, ws, m, SplitStep{nullptr, sl.t_dev, 0}));
+    OSD_TRY(split_trunk(h, s, ws, m, SplitStep{nullptr, sl.t_dev, 0, plan.temb}));
     EpiB3Post::Args ea{};
-    ea.bias = h->params[a.pm.out_b]; ea.x = x; ea.ldx = D; ea.coef = h->d_coef; ea.t_dev = sl.t_dev; ea.t_imm = 0;
-    ea.z = noises ? noises + r0 * D : nullptr; ea.ldzz = D; ea.z_step_stride = (long long)n_total * D; ea.t_first = T - 1;
+    ea.bias = h->params[a.pm.out_b]; ea.x = x; ea.ldx = D; ea.coef = plan.coef; ea.t_dev = sl.t_dev; ea.t_imm = 0;
+    ea.z = noises ? noises + r0 * D : nullptr; ea.ldzz = D; ea.z_step_stride = (long long)n_total * D; ea.t_first = S - 1;
     ea.seed = seed; ea.row_offset = roff;
     ea.mut_mask = mut_mask_out ? mut_mask_out + r0 * h->cfg.mutation_dim : nullptr; ea.mutation_dim = h->cfg.mutation_dim;
     ea.o = B3Out{ws.xpl, b3_nkb(D)};
@@ -264,9 +265,9 @@ int split_chain_chunk(osd_handle* h, Slot& sl, const float* cond, int64_t n_tota
     OSD_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
     sl.graph = graph;
     sl.exec = exec;
-    for (int it = 0; it < T; ++it) OSD_HIP(hipGraphLaunch(exec, s));
+    for (int it = 0; it < S; ++it) OSD_HIP(hipGraphLaunch(exec, s));
   } else {
-    for (int it = 0; it < T; ++it) OSD_TRY(enqueue_step());
+    for (int it = 0; it < S; ++it) OSD_TRY(enqueue_step());
   }
   return OSD_OK;
 }

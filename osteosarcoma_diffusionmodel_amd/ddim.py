@@ -1,0 +1,53 @@
+"""Strided DDIM sampling (Song et al., 2021): the step plan that ``osd_sample_chain_steps`` runs.
+
+A plan of S steps evaluates the denoiser at timesteps tau_0 < ... < tau_{S-1} = T - 1 and runs s = S-1 first, down to s = 0.
+Step s goes from tau = tau_s to tau' = tau_{s-1} (abar' = 1 at s = 0) and, like every reverse step of the library, is one affine
+update x' = A*x + B*eps + C*z:
+
+    x0^ = (x - sqrt(1 - abar)*eps) / sqrt(abar),   x' = sqrt(abar')*x0^ + sqrt(1 - abar' - sigma^2)*eps + sigma*z
+    sigma = eta * sqrt((1 - abar') / (1 - abar)) * sqrt(1 - abar / abar')
+    =>  A = sqrt(abar' / abar),  B = sqrt(1 - abar' - sigma^2) - sqrt(abar')*sqrt(1 - abar) / sqrt(abar),  C = sigma
+
+With eta = 1 and S = T this is the reference's DDPM chain; eta = 0 is deterministic after x_T.  Pure host code.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+
+def ddim_timesteps(T: int, S: int) -> np.ndarray:
+    """int32 [S]: tau_s = floor((s + 1) * T / S) - 1, strictly increasing, tau_{S-1} = T - 1 (S = T: tau_s = s)."""
+    T, S = int(T), int(S)
+    if not 1 <= S <= T:
+        raise ValueError(f"num_inference_steps={S} outside [1, {T}]")
+    s = np.arange(1, S + 1, dtype=np.int64)
+    return (s * T // S - 1).astype(np.int32)
+
+
+def ddim_step_table(alphas_cumprod, timesteps, eta: float):
+    """(int32 [S] timesteps, fp32 [S][4] rows (A_s, B_s, C_s, 0)) for ``osd_sample_chain_steps``.
+
+    The coefficients are formed in float64 from the fp32 ``alphas_cumprod`` buffer and rounded once to fp32, as
+    ``osd_set_schedule`` folds the DDPM posterior.  The radicand of B is clamped at 0; x0^ is not clamped (as in the reference)."""
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"eta={eta} outside [0, 1]")
+    if hasattr(alphas_cumprod, "detach"):
+        alphas_cumprod = alphas_cumprod.detach().cpu().float().numpy()
+    abar = np.asarray(alphas_cumprod, dtype=np.float32).astype(np.float64)
+    tau = np.asarray(timesteps, dtype=np.int64).reshape(-1)
+    T = abar.shape[0]
+    if tau.size < 1 or tau.min() < 0 or tau.max() >= T:
+        raise ValueError(f"timesteps must be a non-empty list inside [0, {T})")
+    coef = np.zeros((tau.size, 4), dtype=np.float64)
+    for s in range(tau.size):
+        a = abar[tau[s]]
+        ap = abar[tau[s - 1]] if s > 0 else 1.0
+        ratio = (1.0 - ap) / (1.0 - a) if a < 1.0 else 0.0
+        sigma = eta * math.sqrt(ratio) * math.sqrt(max(1.0 - a / ap, 0.0))
+        coef[s, 0] = math.sqrt(ap / a)
+        coef[s, 1] = math.sqrt(max(1.0 - ap - sigma * sigma, 0.0)) - math.sqrt(ap) * math.sqrt(1.0 - a) / math.sqrt(a)
+        coef[s, 2] = sigma
+    return tau.astype(np.int32), coef.astype(np.float32)

@@ -507,9 +507,28 @@ class BiologyAwareDiffusionModel(nn.Module):
 
     @torch.no_grad()
     def sample(self, conditions, num_samples: int = 1, *, x_T=None, noise=None, seed: Optional[int] = None,
-               row_offset: int = 0, return_mutation_mask: bool = False):
+               row_offset: int = 0, return_mutation_mask: bool = False, num_inference_steps: Optional[int] = None,
+               eta: float = 0.0):
         """Full reverse chain.  ``x_T`` [N,D] and ``noise`` [T-1,N,D] (draw order t = T-1..1) inject the
-        random draws; otherwise Philox(seed, row_offset + row) generates them on the device."""
+        random draws; otherwise Philox(seed, row_offset + row) generates them on the device.
+
+        ``num_inference_steps=S`` runs the strided DDIM sampler instead (ddim.py: S of the T timesteps, ``eta`` in [0, 1]
+        scales its noise; 0 is deterministic after x_T, 1 with S = T is the DDPM chain).  x_T is the DDPM chain's for the same
+        seed / row_offset; ``noise`` is then [S-1,N,D] (draw order s = S-1..1) and needs eta > 0."""
+        plan = None
+        if num_inference_steps is not None:
+            from .ddim import ddim_step_table, ddim_timesteps
+            if not 0.0 <= float(eta) <= 1.0:
+                raise ValueError(f"eta={eta} outside [0, 1]")
+            steps = int(num_inference_steps)
+            if not 1 <= steps <= self.num_steps:
+                raise ValueError(f"num_inference_steps={steps} outside [1, {self.num_steps}]")
+            if noise is not None and float(eta) == 0.0:
+                raise ValueError("noise: eta = 0 draws no z (pass eta > 0 or leave noise out)")
+            plan = ddim_step_table(self.alphas_cumprod, ddim_timesteps(self.num_steps, steps), eta)
+        elif float(eta) != 0.0:
+            raise ValueError("eta applies to the DDIM sampler: pass num_inference_steps as well")
+        n_draws = self.num_steps - 1 if plan is None else plan[0].size - 1
         eng = self._engine()
         conditions = self._prep(conditions, self.condition_dim, "conditions")
         n = int(num_samples)
@@ -521,8 +540,8 @@ class BiologyAwareDiffusionModel(nn.Module):
         zs = None
         if noise is not None:
             zs = noise.to(torch.float32).contiguous()
-            if tuple(zs.shape) != (self.num_steps - 1, n, self.data_dim):
-                raise RuntimeError(f"noise: expected shape [{self.num_steps - 1}, {n}, {self.data_dim}]")
+            if tuple(zs.shape) != (n_draws, n, self.data_dim):
+                raise RuntimeError(f"noise: expected shape [{n_draws}, {n}, {self.data_dim}]")
         mask = torch.empty(n, self.mutation_dim, device=out.device, dtype=torch.float32) if return_mutation_mask else None
         if seed is None:
             seed = _draw_seed()
@@ -541,8 +560,13 @@ class BiologyAwareDiffusionModel(nn.Module):
             return int(v.value)
 
         gave_up_before = counter(b"chain_fallbacks")
-        L.check(L.lib().osd_sample_chain(eng.handle, L.ptr(conditions), n, L.ptr(xT), L.ptr(zs), seed, int(row_offset),
-                                         L.ptr(out), L.ptr(mask), flags))
+        if plan is None:
+            L.check(L.lib().osd_sample_chain(eng.handle, L.ptr(conditions), n, L.ptr(xT), L.ptr(zs), seed, int(row_offset),
+                                             L.ptr(out), L.ptr(mask), flags))
+        else:
+            tau, coef = plan
+            L.check(L.lib().osd_sample_chain_steps(eng.handle, L.ptr(conditions), n, L.ptr(xT), L.ptr(zs), seed, int(row_offset),
+                                                   L.ptr(out), L.ptr(mask), flags, tau.ctypes.data, coef.ctypes.data, int(tau.size)))
         used = L.lib().osd_sample_engine(eng.handle, -1, 0)      # the engine that produced the result
         if used < 0:
             L.check(used)

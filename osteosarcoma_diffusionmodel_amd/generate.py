@@ -62,9 +62,12 @@ class SyntheticPatientGenerator:
 
     @torch.no_grad()
     def generate(self, num_samples: int, scenario: Optional[Dict] = None, guidance_scale: float = 1.0,
-                 *, seed: Optional[int] = None, row_offset: int = 0, x_T=None, noise=None) -> Dict[str, np.ndarray]:
+                 *, seed: Optional[int] = None, row_offset: int = 0, x_T=None, noise=None, sampling_steps: Optional[int] = None,
+                 eta: float = 0.0) -> Dict[str, np.ndarray]:
         """utils/generate.py:96-144.  ``guidance_scale`` is accepted and ignored, as in the reference.
-        Keyword-only extras inject the random draws / shard the Philox stream."""
+        Keyword-only extras inject the random draws / shard the Philox stream.  ``sampling_steps=S`` runs the strided DDIM
+        sampler (``model.sample(num_inference_steps=S, eta=eta)``); the config's ``generation.sampling_steps`` is not read
+        implicitly: ``generate(n, sc, sampling_steps=config["generation"]["sampling_steps"])`` honours it."""
         logger.info(f"Generating {num_samples} synthetic patients...")
         if scenario:
             logger.info(f"Scenario: {scenario}")
@@ -76,11 +79,14 @@ class SyntheticPatientGenerator:
             if seed is not None or row_offset or x_T is not None or noise is not None:
                 raise ValueError("seed / row_offset / x_T / noise drive the diffusion sampler's Philox stream and are not "
                                  "accepted for a cVAE model (pass z= to model.sample directly)")
+            if sampling_steps is not None or eta:
+                raise ValueError("sampling_steps / eta select the diffusion model's DDIM sampler and are not accepted for a cVAE model")
             samples = self.model.sample(conditions, num_samples=num_samples).cpu().numpy()
             mutations = (samples[:, :md] > 0.5).astype(float)
         else:
             samples, mask = self.model.sample(conditions, num_samples=num_samples, seed=seed, row_offset=row_offset,
-                                              x_T=x_T, noise=noise, return_mutation_mask=True)
+                                              x_T=x_T, noise=noise, return_mutation_mask=True, num_inference_steps=sampling_steps,
+                                              eta=eta)
             samples = samples.cpu().numpy()
             # (mutations > 0.5).astype(float), evaluated by the last reverse step's epilogue on the device
             mutations = mask.cpu().numpy().astype(float)
@@ -91,20 +97,23 @@ class SyntheticPatientGenerator:
                 "conditions": conditions.cpu().numpy()}
 
     def generate_scenarios(self, scenarios: List[Dict], samples_per_scenario: int, *, seed: Optional[int] = None,
-                           batched: bool = True) -> Dict[str, Dict[str, np.ndarray]]:
+                           batched: bool = True, sampling_steps: Optional[int] = None,
+                           eta: float = 0.0) -> Dict[str, Dict[str, np.ndarray]]:
         """utils/generate.py:146-175: one result dict per scenario name.
 
         The reference runs the scenarios one after the other, each a chain of T sequential steps.  Rows never interact and the
         conditions are per row, so here all scenarios form ONE batch (scenario k = rows k*N .. (k+1)*N-1) and the chain runs
         once: at the reference's default size (3 scenarios x 1000 patients, config.yaml:119-141) a reverse step is bound by
         launch latency, not by rows, and T steps over 3000 rows cost about what T steps over 1000 do.  ``batched=False`` restores
-        the reference's loop (one chain, and one freshly drawn Philox seed, per scenario)."""
+        the reference's loop (one chain, and one freshly drawn Philox seed, per scenario).  ``sampling_steps`` / ``eta`` select the
+        strided DDIM sampler, as in ``generate``."""
         if not batched or hasattr(self.model, "vae") or len(scenarios) < 2:
             out = {}
             for scenario in scenarios:
                 name = scenario["name"]
                 logger.info(f"\nGenerating scenario: {name}")
-                out[name] = self.generate(num_samples=samples_per_scenario, scenario=scenario["conditions"])
+                out[name] = self.generate(num_samples=samples_per_scenario, scenario=scenario["conditions"],
+                                          sampling_steps=sampling_steps, eta=eta)
             return out
         n = int(samples_per_scenario)
         for scenario in scenarios:
@@ -113,7 +122,8 @@ class SyntheticPatientGenerator:
         logger.info(f"Generating {len(scenarios)} x {n} synthetic patients in one batch...")
         conditions = torch.cat([self.create_conditions(n, sc["conditions"]) for sc in scenarios], dim=0)
         with torch.no_grad():
-            samples, mask = self.model.sample(conditions, num_samples=conditions.shape[0], seed=seed, return_mutation_mask=True)
+            samples, mask = self.model.sample(conditions, num_samples=conditions.shape[0], seed=seed, return_mutation_mask=True,
+                                              num_inference_steps=sampling_steps, eta=eta)
         samples, mask, cond_np = samples.cpu().numpy(), mask.cpu().numpy().astype(float), conditions.cpu().numpy()
         md, ed = self.mutation_dim, self.expression_dim
         out = {}
