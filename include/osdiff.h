@@ -230,6 +230,44 @@ int osd_sample_chain_steps(osd_handle *h, const float *cond, int64_t n, const fl
                            float *mut_mask_out, int flags, const int32_t *timesteps,
                            const float *step_coef, int32_t n_steps);
 
+/* Classifier-free guidance (Ho & Salimans 2022) -- the guidance_scale of SyntheticPatientGenerator.generate (utils/generate.py:97-110:
+ * "Guidance strength for conditional generation"; config/config.yaml:120 ships 7.5), which the reference accepts and never uses.
+ * With the null condition c0 = null_cond_host (host, [condition_dim]; it goes through the unchanged ConditionalEmbedding and cond_proj,
+ * models/diffusion.py:101-114, 226, like any other condition) and w = guidance_scale, every step of the chain steps on
+ *   eps_g(x, t, c) = eps(x, t, c0) + w * (eps(x, t, c) - eps(x, t, c0))
+ * in place of eps(x, t, c): w = 1 is osd_sample_chain / osd_sample_chain_steps, w = 0 the unconditional sampler.  timesteps == NULL:
+ * the DDPM chain (step_coef / n_steps ignored); otherwise the arguments and checks of osd_sample_chain_steps.  x_T and every z come
+ * from the Philox addresses of the unguided chain.  Per chunk of m rows a step is one input_proj product with two outputs (it does
+ * not depend on the condition), the Linear+GroupNorm+SiLU layers on 2 m rows, the combination h_u + w * (h_c - h_u) on the last
+ * hidden activation (output_proj is linear) and ONE output_proj + posterior launch over m rows.  Per-layer kernels only, whatever
+ * "sampler" says (osd_sample_engine(h, -1, 0) then reports 0; no warning, "chain_fallbacks" untouched); a row's result does not
+ * depend on the chunk or shard it is in ("input_splitk" = 0).  guidance_scale == 1.0f exactly takes the unguided entry point's
+ * path: any engine, its bits.  OSD_EINVAL: non-finite guidance_scale or null_cond, OSD_F_TRAIN_MODE (no dropout inside a guided
+ * chain); OSD_EUNSUPPORTED: "precision" = 1. */
+int osd_sample_chain_guided(osd_handle *h, const float *cond, int64_t n, const float *x_T,
+                            const float *noises, uint64_t seed, int64_t row_offset, float *x_out,
+                            float *mut_mask_out, int flags, const int32_t *timesteps,
+                            const float *step_coef, int32_t n_steps, const float *null_cond_host,
+                            float guidance_scale);
+
+/* eps_g of ONE guided evaluation (DiffusionUNet.forward twice, models/diffusion.py:210-256, combined as above), eval mode only:
+ * osd_denoiser_forward's x / t_index / t_all / cond / eps, osd_sample_chain_guided's null_cond_host / guidance_scale and errors. */
+int osd_denoiser_forward_guided(osd_handle *h, const float *x, const int32_t *t_index, int32_t t_all,
+                                const float *cond, int64_t n, float *eps, int flags,
+                                const float *null_cond_host, float guidance_scale);
+
+/* Condition dropout, the training side of classifier-free guidance (utils/train.py:230-236 hands the batch's conditions to the model
+ * as they are; the unconditional branch of a guided sampler needs a model that has seen the null condition).  One-shot like
+ * osd_train_batch_source: in the NEXT osd_train_loss_fwd_bwd on this handle, row i's condition is replaced by null_cond_host
+ * (host, [condition_dim]) unless the row keeps it -- after the mixup of a resident batch source, before anything else reads it:
+ *   keep_dev != NULL  dev float[n]: row i keeps its condition iff keep_dev[i] != 0
+ *   keep_dev == NULL  row i keeps it iff u >= p, u = (w >> 8) * 2^-24 of word 0 of the Philox block at counter
+ *                     (row_offset + i, 0, 0, tag 0x44524f80), key = that call's seed: the dropout keep-mask's construction with
+ *                     one column per row, independent of sharding and predictable from the host
+ * p == 0 with keep_dev == NULL clears the option: the next call draws nothing and launches nothing new.  Pure data movement: forward,
+ * backward and the constraint losses see the replaced conditions and are otherwise unchanged. */
+int osd_train_condition_dropout(osd_handle *h, const float *null_cond_host, double p, const float *keep_dev);
+
 /* Device-resident epoch path (utils/train.py:204-250 hands every batch over from host memory; here the dataset of
  * OsteosarcomaDataset (utils/train.py:22-82) stays in HBM).  The NEXT osd_train_loss_fwd_bwd on this handle takes its n rows
  * from the dataset instead of its x0 / cond arguments (pass NULL there):

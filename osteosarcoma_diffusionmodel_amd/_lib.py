@@ -54,6 +54,10 @@ _SIGNATURES = {
     "osd_sample_chain": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_int64, _P, _P, C.c_int]),
     "osd_sample_engine": (C.c_int, [_P, C.c_int64, C.c_int]),
     "osd_sample_chain_steps": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_int64, _P, _P, C.c_int, _P, _P, C.c_int32]),
+    "osd_sample_chain_guided": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_int64, _P, _P, C.c_int, _P, _P, C.c_int32, _P,
+                                          C.c_float]),
+    "osd_denoiser_forward_guided": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, _P, C.c_int, _P, C.c_float]),
+    "osd_train_condition_dropout": (C.c_int, [_P, _P, C.c_double, _P]),
     "osd_train_loss_fwd_bwd": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.POINTER(_P), C.c_uint64, C.c_int64, C.c_int,
                                          _P, C.POINTER(_P), C.c_double, C.POINTER(_P), C.c_int]),
     "osd_train_batch_source": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_double]),

@@ -154,7 +154,25 @@ int run_trunk(osd_handle* h, hipStream_t s, const FwdWs& ws, const TrunkIn& in) 
   const Arch& a = h->arch;
   const ParamMap& pm = a.pm;
   const int n = (int)in.n;
-  {
+  if (in.guide_m > 0) {
+    // one input_proj GEMM over the state rows, both branches' h0 from its epilogue -- or, for small batches, from the split-K reduce
+    GemmArgs g{};
+    const int kx = in.kx > 0 ? in.kx : a.D;
+    g.A = h->w_in_packed; g.lda = h->w_in_ld; g.B0 = in.x; g.ldb0 = in.ldx; g.K0 = kx;
+    g.F = a.H0; g.P = (int)in.guide_m; g.K = kx;
+    g.ksplit = in.ksplit ? 1 : 0;
+    EpiInputGuided::Args ea{h->params[pm.in_b], in.temb ? in.temb : h->d_temb, a.H0, in.t_index, in.t_dev, in.t_imm, ws.cproj, a.H0, in.cproj0,
+                            ws.h0, a.H0, (long long)in.guide_m * a.H0};
+    bool done = false;
+    if (in.in_slices > 1 && in.in_slabs) {
+      const hipError_t e = launch_input_guided_splitk(s, g, ea, in.in_slabs, in.in_slices);
+      if (e == hipSuccess) done = true;
+      else if (e != hipErrorInvalidValue) OSD_HIP(e);
+      else (void)hipGetLastError();
+    }
+    if (!done) OSD_HIP(launch_input_guided(s, g, ea, true));
+    OSD_TRY(prof_mark(h, s));
+  } else {
     GemmArgs g{};
     const int kx = in.kx > 0 ? in.kx : a.D;
     g.A = h->w_in_packed; g.lda = h->w_in_ld; g.B0 = in.x; g.ldb0 = in.ldx; g.K0 = kx;
@@ -288,6 +306,31 @@ GemmArgs output_proj_args(osd_handle* h, const FwdWs& ws, int64_t n, bool padded
   g.B0 = ws.out[last]; g.ldb0 = a.block_out[last]; g.K0 = a.block_out[last];
   g.F = padded ? h->Dp : a.D; g.P = (int)n; g.K = a.block_out[last];
   return g;
+}
+
+// The null condition of classifier-free guidance, host -> device slot (handle.h: d_null_cond) on the handle's stream.  The caller has
+// checked that the vector is there and finite.
+int upload_null_cond(osd_handle* h, int slot, const float* null_cond_host, const float** dev) {
+  const int cd = h->arch.cond_dim;
+  const size_t stride = (size_t)(cd + 63) / 64 * 64;
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  if (!h->null_host) {
+    h->null_host = static_cast<float*>(malloc(2 * stride * 4));
+    if (!h->null_host) { set_error("out of host memory"); return OSD_ENOMEM; }
+  }
+  if (!h->null_ev) OSD_HIP(hipEventCreateWithFlags(&h->null_ev, hipEventDisableTiming));
+  if (!h->d_null_cond) OSD_HIP(hipMalloc((void**)&h->d_null_cond, 2 * stride * 4));
+  *dev = h->d_null_cond + slot * stride;
+  // the vector rarely changes between calls (a training run, a generation run): the slot keeps what it holds and a call with the
+  // same bits uploads nothing -- no host wait on the previous step, no copy on the hot stream
+  if (h->null_valid[slot] && !memcmp(h->null_host + slot * stride, null_cond_host, (size_t)cd * 4)) return OSD_OK;
+  OSD_HIP(hipEventSynchronize(h->null_ev));          // the previous upload has read the staging
+  h->null_valid[slot] = false;
+  memcpy(h->null_host + slot * stride, null_cond_host, (size_t)cd * 4);
+  OSD_HIP(hipMemcpyAsync(h->d_null_cond + slot * stride, h->null_host + slot * stride, (size_t)cd * 4, hipMemcpyHostToDevice, h->stream));
+  OSD_HIP(hipEventRecord(h->null_ev, h->stream));
+  h->null_valid[slot] = true;
+  return OSD_OK;
 }
 
 int check_ready(osd_handle* h) {
@@ -481,6 +524,9 @@ int osd_destroy(osd_handle* h) {
   if (h->plan_t) e = hipFree(h->plan_t);
   if (h->plan_ev) e = hipEventDestroy(h->plan_ev);
   free(h->plan_host);
+  if (h->d_null_cond) e = hipFree(h->d_null_cond);
+  if (h->null_ev) e = hipEventDestroy(h->null_ev);
+  free(h->null_host);
   if (h->normsq_dev) e = hipFree(h->normsq_dev);
   if (h->parts_dev) e = hipFree(h->parts_dev);
   if (h->t_san) e = hipFree(h->t_san);
@@ -665,15 +711,33 @@ static int release_graph(Slot& sl) {
   return OSD_OK;
 }
 
-// One chunk of the reverse chain on one slot: rows [r0, r0+m).
+// Classifier-free guidance of a chain / an evaluation (osd_sample_chain_guided): eps = eps(c0) + w * (eps(c) - eps(c0)).
+struct Guide {
+  const float* null_cond;      // dev [cond_dim]
+  float w;
+};
+
+// The condition batch of a guided chunk: the m rows' conditions and, as row m, the null condition -- so that c_proj of the null
+// condition comes out of the same launches, with the bits it has as a row of any batch.  stage: [m + 1][cond_dim].
+static int guided_cond(osd_handle* h, hipStream_t s, const Guide& gd, const float* cond, int64_t m, float* stage, const FwdWs& ws) {
+  const int cd = h->arch.cond_dim;
+  OSD_HIP(hipMemcpyAsync(stage, cond, (size_t)m * cd * 4, hipMemcpyDeviceToDevice, s));
+  OSD_HIP(hipMemcpyAsync(stage + m * cd, gd.null_cond, (size_t)cd * 4, hipMemcpyDeviceToDevice, s));
+  return run_cond(h, s, stage, m + 1, ws);
+}
+
+// One chunk of the reverse chain on one slot: rows [r0, r0+m).  gd != null: a guided chain -- the trunk runs on 2 m rows (rows
+// [0, m) with the patients' conditions, [m, 2 m) with the null condition), input_proj and output_proj on m.
 static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const float* cond, int64_t n_total, int64_t r0, int64_t m,
-                       const float* x_T, const float* noises, uint64_t seed, int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
+                       const float* x_T, const float* noises, uint64_t seed, int64_t row_offset, float* x_out, float* mut_mask_out, int flags,
+                       const Guide* gd = nullptr) {
   const Arch& a = h->arch;
   const int D = a.D, S = plan.n_steps;
   hipStream_t s = sl.stream;
   OSD_TRY(release_graph(sl));
   FwdWs ws;
-  const int64_t need = carve_fwd(a, nullptr, m, false, &ws);
+  const int64_t mt = gd ? 2 * m : m;            // rows of the trunk
+  const int64_t need = carve_fwd(a, nullptr, mt, false, &ws);
   // D % 4 != 0 with device-generated draws: the state of the chunk lives in a padded buffer behind the activations (rows of Dp
   // floats, pad columns zero at the start) and is copied to the caller's rows at the end; injected draws ([S-1][n][D], rows not
   // 16-byte aligned) keep the guarded kernels on the caller's tensor
@@ -697,31 +761,40 @@ static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const floa
   int gn_slices = 0, max_c = a.H0;
   for (int c : a.block_out) max_c = std::max(max_c, c);
   if (in_slices > 0 && !(flags & OSD_F_TRAIN_MODE)) {
-    const int64_t tiles = (int64_t)((max_c + 63) / 64) * ((m + 63) / 64);
+    const int64_t tiles = (int64_t)((max_c + 63) / 64) * ((mt + 63) / 64);
     gn_slices = (int)std::min<int64_t>(4, (640 + tiles / 2) / tiles);
     if (gn_slices < 4) gn_slices = 0;      // measured (dims 62 / 5054 / 26): 999 rows 257 -> 238 us per step with 4 slices; 3000 rows 351 -> 385 us with 2
   }
-  const int64_t slab_floats = std::max<int64_t>((int64_t)in_slices * m * a.H0, gn_slices ? (int64_t)(gn_slices + 1) * m * max_c : 0);
-  OSD_TRY(ensure_arena(&sl, need_pad + x_floats + slab_floats));
-  carve_fwd(a, sl.arena, m, false, &ws);
+  // a guided chunk in the small-batch mode: input_proj split over K as for m rows (its reduce kernel writes both halves), the deep
+  // layers' K slices and the two-wave-group GEMMs as for 2 m unguided rows.  The slabs end on a 64-float boundary so that whatever is
+  // carved behind them (a guided chunk's condition staging) stays aligned
+  const int64_t slab_floats = align_up(std::max<int64_t>((int64_t)in_slices * m * a.H0, gn_slices ? (int64_t)(gn_slices + 1) * mt * max_c : 0), 64);
+  const int64_t stage_floats = gd ? (m + 1) * (int64_t)a.cond_dim : 0;
+  OSD_TRY(ensure_arena(&sl, need_pad + x_floats + slab_floats + stage_floats));
+  carve_fwd(a, sl.arena, mt, false, &ws);
   float* x = padded ? sl.arena + need_pad : x_out + r0 * D;       // else the chain state lives in the output rows
   float* in_slabs = in_slices ? sl.arena + need_pad + x_floats : nullptr;
+  float* cond_stage = sl.arena + need_pad + x_floats + slab_floats;
   if (padded) OSD_HIP(hipMemsetAsync(x, 0, (size_t)m * ldx * 4, s));
   const uint32_t roff = (uint32_t)(row_offset + r0);
   const bool train = (flags & OSD_F_TRAIN_MODE) != 0;
   // conditioning is loop-invariant in eval mode (no dropout inside the embedding MLP): hoisted
-  OSD_TRY(run_cond(h, s, cond + r0 * a.cond_dim, m, ws));
+  if (gd) OSD_TRY(guided_cond(h, s, *gd, cond + r0 * a.cond_dim, m, cond_stage, ws));
+  else OSD_TRY(run_cond(h, s, cond + r0 * a.cond_dim, m, ws));
   if (x_T) OSD_HIP(launch_copy2d(s, x_T + r0 * D, D, x, ldx, m, D));
   else OSD_HIP(launch_fill_randn(s, x, ldx, m, D, seed, roff, (uint32_t)a.T, TAG_POSTERIOR));
   OSD_HIP(launch_set_int(s, sl.t_dev, S - 1));
 
   auto enqueue_step = [&](void) -> int {
     TrunkIn in{};
-    in.x = x; in.ldx = ldx; in.kx = ldx; in.n = m; in.t_dev = sl.t_dev; in.temb = plan.temb; in.in_slabs = in_slabs; in.in_slices = in_slices;
+    in.x = x; in.ldx = ldx; in.kx = ldx; in.n = mt; in.t_dev = sl.t_dev; in.temb = plan.temb; in.in_slabs = in_slabs; in.in_slices = in_slices;
+    if (gd) { in.guide_m = m; in.cproj0 = ws.cproj + m * a.H0; }
     in.gn_slabs = in_slabs; in.gn_slices = gn_slices;
     in.ksplit = in_slices > 1;             // the small-batch mode already trades bit-equality with the chain kernel for latency: long-K layers on two wave groups
     in.train = train; in.seed = seed; in.row_offset = roff; in.drop_step_dev = sl.t_dev;
     OSD_TRY(run_trunk(h, s, ws, in));
+    // guidance on the last hidden activation, in place over the conditional rows: output_proj + posterior then run once, on m rows
+    if (gd) OSD_HIP(launch_guide_combine(s, ws.out[a.n_blocks - 1], m, a.block_out[a.n_blocks - 1], gd->w));
     GemmArgs g = output_proj_args(h, ws, m, padded);
     EpiPosterior::Args ea{};
     ea.bias = padded ? h->b_out_packed : h->params[a.pm.out_b]; ea.xin = x; ea.ldx = ldx; ea.xout = x; ea.ldo = ldx; ea.coef = plan.coef;
@@ -757,12 +830,13 @@ static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const floa
 // The reverse chain of `plan` over n rows: osd_sample_chain and osd_sample_chain_steps after their argument checks, chain_check_status
 // and ensure_packed.
 static int sample_plan(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
-                       int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
+                       int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const Guide* gd = nullptr) {
   // bf16x3 split precision: eval-mode chains on the per-layer launches of split.hip (dropout inside the chain stays fp32)
-  const bool split = h->precision == 1 && !((flags & OSD_F_TRAIN_MODE) && h->cfg.dropout_p > 0.f);
+  const bool split = !gd && h->precision == 1 && !((flags & OSD_F_TRAIN_MODE) && h->cfg.dropout_p > 0.f);
   h->last_precision = split ? 1 : 0;
   if (split) OSD_TRY(split_prepare(h, h->stream));
-  h->last_engine = split ? 0 : chain_pick_engine(h, n, flags);
+  // a guided chain runs on the per-layer kernels whatever "sampler" says: the chain kernels' tiles are sized for m trunk rows
+  h->last_engine = (split || gd) ? 0 : chain_pick_engine(h, n, flags);
   if (h->last_engine == 1 && noises && h->w_out_packed && !chain_uses_squad(h, n)) h->last_engine = 0;      // injected draws at D % 4 != 0: guarded per-layer kernels (the squad chain reads any layout)
   bool fell_back = false;
   if (h->last_engine == 1) {
@@ -803,7 +877,7 @@ static int sample_plan(osd_handle* h, const StepPlan& plan, const float* cond, i
     const int64_t r0 = c * chunk;
     const int64_t m = std::min<int64_t>(chunk, n - r0);
     if (split) rc = split_chain_chunk(h, plan, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
-    else rc = chain_chunk(h, plan, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
+    else rc = chain_chunk(h, plan, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, gd);
   }
   // join
   for (int i = 0; i < n_slots; ++i) {
@@ -881,6 +955,89 @@ int osd_sample_chain_steps(osd_handle* h, const float* cond, int64_t n, const fl
   OSD_TRY(ensure_packed(h, h->stream));
   OSD_TRY(upload_plan(h, timesteps, step_coef, n_steps));
   return sample_plan(h, StepPlan{n_steps, h->plan_temb, h->plan_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
+}
+
+// What both guided entry points refuse; *unguided: guidance_scale == 1 exactly -- the caller takes the unguided entry point's path.
+static int check_guidance(osd_handle* h, const float* null_cond_host, float guidance_scale, int flags, bool* unguided) {
+  if (!std::isfinite(guidance_scale)) { set_error("guidance_scale is not finite"); return OSD_EINVAL; }
+  if (!null_cond_host) { set_error("null_cond is null"); return OSD_EINVAL; }
+  for (int i = 0; i < h->arch.cond_dim; ++i)
+    if (!std::isfinite(null_cond_host[i])) { set_error("null_cond[%d] is not finite", i); return OSD_EINVAL; }
+  *unguided = guidance_scale == 1.0f;
+  if (*unguided) return OSD_OK;
+  if (flags & OSD_F_TRAIN_MODE) { set_error("guided sampling is eval mode only (no dropout inside a guided evaluation)"); return OSD_EINVAL; }
+  if (h->precision == 1) { set_error("precision = bf16x3 does not run guided evaluations: set precision to fp32 or guidance_scale to 1"); return OSD_EUNSUPPORTED; }
+  return OSD_OK;
+}
+
+int osd_sample_chain_guided(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                            int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
+                            const float* step_coef, int32_t n_steps, const float* null_cond_host, float guidance_scale) {
+  OSD_TRY(check_ready(h));
+  bool unguided = false;
+  OSD_TRY(check_guidance(h, null_cond_host, guidance_scale, flags, &unguided));
+  if (unguided) {
+    if (!timesteps) return osd_sample_chain(h, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
+    return osd_sample_chain_steps(h, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, timesteps, step_coef, n_steps);
+  }
+  OSD_TRY(check_rows(n));
+  if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
+  const Arch& a = h->arch;
+  if (timesteps) {
+    if (!step_coef) { set_error("null step plan"); return OSD_EINVAL; }
+    if (n_steps < 1 || n_steps > a.T) { set_error("n_steps=%d outside [1,%d]", n_steps, a.T); return OSD_EINVAL; }
+    for (int s = 0; s < n_steps; ++s) {
+      if (timesteps[s] < 0 || timesteps[s] >= a.T) { set_error("timesteps[%d]=%d outside [0,%d)", s, timesteps[s], a.T); return OSD_EINVAL; }
+      for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(step_coef[4 * s + k])) { set_error("step_coef[%d] is not finite", 4 * s + k); return OSD_EINVAL; }
+    }
+    if (step_coef[2] != 0.f) { set_error("step_coef[2] = C_0 = %g: the last step draws no z, so C_0 must be 0", (double)step_coef[2]); return OSD_EINVAL; }
+  }
+  OSD_TRY(check_row_offset(row_offset, n));
+  if (n == 0) return OSD_OK;
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  OSD_TRY(chain_check_status(h));
+  OSD_TRY(ensure_packed(h, h->stream));
+  Guide gd{nullptr, guidance_scale};
+  OSD_TRY(upload_null_cond(h, 0, null_cond_host, &gd.null_cond));
+  if (!timesteps) return sample_plan(h, StepPlan{a.T, h->d_temb, h->d_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, &gd);
+  OSD_TRY(upload_plan(h, timesteps, step_coef, n_steps));
+  return sample_plan(h, StepPlan{n_steps, h->plan_temb, h->plan_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, &gd);
+}
+
+int osd_denoiser_forward_guided(osd_handle* h, const float* x, const int32_t* t_index, int32_t t_all, const float* cond, int64_t n,
+                                float* eps, int flags, const float* null_cond_host, float guidance_scale) {
+  OSD_TRY(check_ready(h));
+  bool unguided = false;
+  OSD_TRY(check_guidance(h, null_cond_host, guidance_scale, flags, &unguided));
+  if (unguided) return osd_denoiser_forward(h, x, t_index, t_all, cond, n, eps, flags, nullptr, 0);
+  OSD_TRY(check_rows(n));
+  if (!x || !cond || !eps) { set_error("null tensor"); return OSD_EINVAL; }
+  const Arch& a = h->arch;
+  if (!t_index && (t_all < 0 || t_all >= a.T)) { set_error("t=%d outside [0,%d)", t_all, a.T); return OSD_EINVAL; }
+  if (n == 0) return OSD_OK;
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  hipStream_t s = h->stream;
+  OSD_TRY(ensure_packed(h, s));
+  const int* t_idx = nullptr;
+  OSD_TRY(sanitize_t(h, s, t_index, n, &t_idx));
+  Guide gd{nullptr, guidance_scale};
+  OSD_TRY(upload_null_cond(h, 0, null_cond_host, &gd.null_cond));
+  h->last_precision = 0;
+  FwdWs ws;
+  const int64_t need = align_up(carve_fwd(a, nullptr, 2 * n, false, &ws), 64);
+  OSD_TRY(ensure_arena(&h->main, need + (n + 1) * (int64_t)a.cond_dim));
+  carve_fwd(a, h->main.arena, 2 * n, false, &ws);
+  OSD_TRY(guided_cond(h, s, gd, cond, n, h->main.arena + need, ws));
+  TrunkIn in{};
+  in.x = x; in.ldx = a.D; in.n = 2 * n; in.t_index = t_idx; in.t_imm = t_all;
+  in.guide_m = n; in.cproj0 = ws.cproj + n * a.H0;
+  OSD_TRY(run_trunk(h, s, ws, in));
+  OSD_HIP(launch_guide_combine(s, ws.out[a.n_blocks - 1], n, a.block_out[a.n_blocks - 1], guidance_scale));
+  GemmArgs g = output_proj_args(h, ws, n);
+  OSD_HIP(launch_linear(s, g, true, true, h->params[a.pm.out_b], eps, a.D, false, false));
+  if (flags & OSD_F_SYNC) OSD_HIP(hipStreamSynchronize(s));
+  return OSD_OK;
 }
 
 int osd_sample_engine(osd_handle* h, int64_t n, int flags) {

@@ -135,6 +135,79 @@ struct EpiInput {
   }
 };
 
+// ---- input_proj of a classifier-free-guidance step: one product, two outputs ----
+// x W^T does not depend on the condition, so the conditional and the unconditional branch of a guided evaluation
+// (utils/generate.py:97-110, guidance_scale) share the GEMM: row p of the m state rows leaves as
+//   out[p]     = ((acc + b) + t_emb[t]) + c_proj[p]      the row's own condition
+//   out[m + p] = ((acc + b) + t_emb[t]) + c_proj0        the null condition, one [F] row for every patient
+// Each half is EpiInput's arithmetic operation for operation: a row whose condition IS the null condition gets two
+// bit-identical halves.
+struct EpiInputGuided {
+  static constexpr bool KSPLIT2 = true;
+  static constexpr bool COUNTED_STORES = true;     // two float4 stores per accumulator quad on a full tile: the count the kernel waits on is a lower bound
+  static constexpr bool XBUF = false;
+  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
+  struct Args {
+    const float* bias;
+    const float* temb; int ldt;
+    const int* t_index;
+    const int* t_dev; int t_imm;
+    const float* cproj; int ldc;  // [P][F]
+    const float* cproj0;          // [F]
+    float* out; int ldo;          // [2 P][F]
+    long long half;               // floats between out[p] and out[P + p] (= P * ldo)
+  };
+  static bool fast_ok(const Args& a, int F) {
+    return F % 4 == 0 && al16(a.bias) && al16(a.temb) && al16(a.cproj) && al16(a.cproj0) && al16(a.out) && a.ldt % 4 == 0 && a.ldc % 4 == 0 &&
+           a.ldo % 4 == 0 && a.half % 4 == 0;
+  }
+  template <int NFB> struct Pre { float4 bias[NFB][4]; };
+  template <int NFB, bool FAST>
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
+    Pre<NFB> r;
+    const int h = lane >> 5;
+#pragma unroll
+    for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r.bias[fb][q] = ldq<FAST>(a.bias, fw + 32 * fb + 8 * q + 4 * h, F);
+    return r;
+  }
+  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
+                                               Sync&& sync = Sync()) {
+    const int l31 = lane & 31, h = lane >> 5;
+    const int t_shared = a.t_dev ? *a.t_dev : a.t_imm;
+#pragma unroll
+    for (int pb = 0; pb < NPB; ++pb) {
+      const int p = pw + 32 * pb + l31;
+      const int pc = p < P ? p : P - 1;
+      const int t = a.t_index ? a.t_index[pc] : t_shared;
+      const float* trow = a.temb + (size_t)t * a.ldt;
+      const float* crow = a.cproj + (size_t)pc * a.ldc;
+      float* orow = a.out + (size_t)pc * a.ldo;
+#pragma unroll
+      for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int f = fw + 32 * fb + 8 * q + 4 * h;
+          const float4 bv = pre.bias[fb][q], tv = ldq<FAST>(trow, f, F), cv = ldq<FAST>(crow, f, F), nv = ldq<FAST>(a.cproj0, f, F);
+          float4 s, v, u;
+          s.x = (acc[fb][pb][4 * q] + bv.x) + tv.x;
+          s.y = (acc[fb][pb][4 * q + 1] + bv.y) + tv.y;
+          s.z = (acc[fb][pb][4 * q + 2] + bv.z) + tv.z;
+          s.w = (acc[fb][pb][4 * q + 3] + bv.w) + tv.w;
+          v.x = s.x + cv.x; v.y = s.y + cv.y; v.z = s.z + cv.z; v.w = s.w + cv.w;
+          u.x = s.x + nv.x; u.y = s.y + nv.y; u.z = s.z + nv.z; u.w = s.w + nv.w;
+          if (p < P) {
+            stq<FAST>(orow, f, F, v);
+            stq<FAST>(orow + a.half, f, F, u);
+          }
+          sync.tick();
+        }
+    }
+  }
+};
+
 // ---- Linear -> GroupNorm(8) -> SiLU [-> Dropout]   (models/diffusion.py:200-204) ----
 // GW = channels per group (C/8), a power of two in [4,128]; the wave's feature extent
 // covers whole groups, so a group's statistics are a sum over this lane's registers plus

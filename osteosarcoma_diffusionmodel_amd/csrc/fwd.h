@@ -18,6 +18,8 @@ struct TrunkIn {
   const int* t_index;            // per-row t (training) or null
   const int* t_dev; int t_imm;   // shared t: device counter (sampling chain) or immediate
   const float* temb;             // rows a shared t reads: null = the handle's [T][H0] table (d_temb), else a chain's step plan (StepPlan)
+  int64_t guide_m;               // > 0: a classifier-free-guidance step.  x holds guide_m state rows, n == 2 * guide_m: input_proj runs once over the
+  const float* cproj0;           // state rows and writes h0[r] with the row's c_proj and h0[guide_m + r] with cproj0 [H0] (EpiInputGuided)
   bool input_only;               // stop after input_proj (the blocks run elsewhere: train_squad.h)
   bool train;                    // dropout active
   bool save;                     // keep pre-norm activations + GroupNorm statistics for backward
@@ -33,6 +35,7 @@ int run_trunk(osd_handle* h, hipStream_t s, const FwdWs& ws, const TrunkIn& in);
 int refresh_derived(osd_handle* h, hipStream_t s, bool pack_in_w = true);
 int ensure_packed(osd_handle* h, hipStream_t s);
 GemmArgs output_proj_args(osd_handle* h, const FwdWs& ws, int64_t n, bool padded = false);
+int upload_null_cond(osd_handle* h, int slot, const float* null_cond_host, const float** dev);
 int check_ready(osd_handle* h);
 int check_rows(int64_t n);
 // chain.hip

@@ -242,7 +242,8 @@ __global__ __launch_bounds__(NTHREADS * NG, NG == 1 ? 2 : 1) void gemm_glds_kern
   }
   // stores of a FULL tile's epilogue: a lower bound on the vector-memory operations a wave issues after
   // the prefetch DMA of the next tile, so vmcnt(that many) proves the (older) DMA has landed while the
-  // stores stay in flight.  Edge tiles may skip stores under an empty exec mask: they wait for vmcnt(0).
+  // stores stay in flight.  Edge tiles may skip stores under an empty exec mask: they wait for vmcnt(0).  An epilogue with
+  // COUNTED_STORES may issue MORE vector-memory operations than this (EpiInputGuided stores two quads per accumulator quad), never fewer.
   constexpr int FULL_TILE_STORES = T::NFB * T::NPB * 4;
   bool counted_wait = false;
   for (; pt < npt; pt += pstride) {

@@ -138,6 +138,12 @@ struct osd_handle {
   std::vector<hipEvent_t> ev_pool;
   int train_streams = 2;             // osd_set_option("train_streams", 1|2): 2 = weight-gradient leaves of the backward pass on a side stream
   osd::BatchSrc batch_src{}; bool have_batch_src = false;      // osd_train_batch_source: one-shot source of the next training call's rows
+  // classifier-free guidance: the null condition on the device -- slot 0 of the current guided sampling / forward call, slot 1 of the
+  // next training call's condition dropout (each cond_dim floats, 64-float stride) --, its host staging and the event that says
+  // the last upload has read the staging (api.hip: upload_null_cond)
+  float* d_null_cond = nullptr; float* null_host = nullptr; hipEvent_t null_ev = nullptr;
+  bool null_valid[2] = {false, false};      // the device slot holds the staging's vector: a call with the same bits uploads nothing
+  bool have_cond_drop = false; float cond_drop_p = 0.f; const float* cond_drop_keep = nullptr;   // osd_train_condition_dropout: one-shot
   int64_t saved_rows = -1;           // rows of the last osd_denoiser_forward_train whose activations are still in the arena
   // constraint losses (osd_set_constraints); parts_dev = (mse, L_pc, L_me) of the last training call
   osd::ConsPlan cons;

@@ -227,6 +227,48 @@ hipError_t launch_q_sample_src(hipStream_t s, const BatchSrc& b, const int* t, c
   return hipGetLastError();
 }
 
+// Classifier-free guidance (utils/generate.py:97-110, guidance_scale) on the last hidden activation: output_proj is linear, so
+// eps_u + w (eps_c - eps_u) = output_proj(h_u + w (h_c - h_u)) and the combination costs a pass over [m][256], not over [m][D].
+// h: [2 m][cols], rows [0, m) the conditional branch, rows [m, 2 m) the unconditional one; row r < m is overwritten with
+// h_u + w * (h_c - h_u): one subtract, one fma (h_c == h_u leaves h_u exactly, whatever w).
+__global__ void k_guide_combine(float* h, int64_t quads, float w) {
+  float4* hc = reinterpret_cast<float4*>(h);
+  const float4* hu = hc + quads;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < quads; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 c = hc[i], u = hu[i];
+    float4 o;
+    o.x = fmaf(w, c.x - u.x, u.x); o.y = fmaf(w, c.y - u.y, u.y);
+    o.z = fmaf(w, c.z - u.z, u.z); o.w = fmaf(w, c.w - u.w, u.w);
+    hc[i] = o;
+  }
+}
+hipError_t launch_guide_combine(hipStream_t s, float* h, int64_t m, int cols, float w) {
+  if (m <= 0) return hipSuccess;
+  if (cols % 4 || (reinterpret_cast<uintptr_t>(h) & 15)) return hipErrorInvalidValue;
+  const int64_t quads = m * (cols / 4);
+  hipLaunchKernelGGL(k_guide_combine, ew_grid(quads), 256, 0, s, h, quads, w);
+  return hipGetLastError();
+}
+
+// Condition dropout of a training batch (classifier-free guidance, Ho & Salimans 2022): out[r] = keep(r) ? cond[r] : null_cond.
+// keep(r) = keep[r] != 0 when a keep vector is injected, else u01(word 0 of the Philox block (row_offset + r, 0, 0, TAG_COND_DROP))
+// >= p -- the dropout keep-mask's construction (epilogues.h: EpiGnSilu) with one column per row.
+__global__ void k_cond_dropout(const float* cond, const float* null_cond, const float* keep, float p, int64_t rows, int cd, uint64_t seed,
+                               uint32_t row_offset, float* out) {
+  const int64_t total = rows * cd;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / cd;
+    const int c = (int)(i - r * cd);
+    out[i] = cond_kept(keep, p, seed, row_offset, r) ? cond[i] : null_cond[c];
+  }
+}
+hipError_t launch_cond_dropout(hipStream_t s, const float* cond, const float* null_cond, const float* keep, float p, int64_t rows, int cd,
+                               uint64_t seed, uint32_t row_offset, float* out) {
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cond_dropout, ew_grid(rows * cd), 256, 0, s, cond, null_cond, keep, p, rows, cd, seed, row_offset, out);
+  return hipGetLastError();
+}
+
 // caller-supplied timestep indices clamped into [lo, hi]: an index outside [0, T) is a caller error (the Python
 // shim raises IndexError as the reference's buffer gather would); the clamp only keeps the table gathers in bounds
 __global__ void k_clamp_int(const int* in, int64_t n, int lo, int hi, int* out) {

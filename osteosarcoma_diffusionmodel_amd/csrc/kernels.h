@@ -17,6 +17,9 @@ hipError_t launch_wgrad_splitk(hipStream_t s, const GemmArgs& g, float* slabs, i
 
 // k_fused.hip ----------------------------------------------------------------------
 hipError_t launch_input(hipStream_t s, const GemmArgs& g, const EpiInput::Args& a, bool a_zero_padded);
+// a classifier-free-guidance step's input_proj: g.P = m state rows, 2 m output rows (EpiInputGuided); launch_input's tile choice
+hipError_t launch_input_guided(hipStream_t s, const GemmArgs& g, const EpiInputGuided::Args& a, bool a_zero_padded);
+hipError_t launch_input_guided_splitk(hipStream_t s, const GemmArgs& g, const EpiInputGuided::Args& a, float* slabs, int slices);
 hipError_t launch_input_splitk(hipStream_t s, const GemmArgs& g, const EpiInput::Args& a, float* slabs, int slices);
 hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const EpiPosterior::Args& a);
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a);
@@ -51,6 +54,11 @@ hipError_t launch_q_sample(hipStream_t s, const float* x0, const int* t, const f
 hipError_t launch_q_sample_src(hipStream_t s, const BatchSrc& b, const int* t, const float* sqrt_ac, const float* sqrt_1m, const float* noise_in,
                                int64_t rows, int cols, int cd, uint64_t seed, uint32_t row_offset, float* x_t, float* noise_out, int* t_out, int T,
                                float* cond_out, float* x0_out, int ldxt = 0, const ZeroList* zl = nullptr);
+// classifier-free guidance on the last hidden activation: h[r] = h[m + r] + w * (h[r] - h[m + r]) for r < m, in place (h: [2 m][cols])
+hipError_t launch_guide_combine(hipStream_t s, float* h, int64_t m, int cols, float w);
+// condition dropout of a caller-supplied batch: out[r] = row r keeps its condition (rng.h: cond_kept) ? cond[r] : null_cond
+hipError_t launch_cond_dropout(hipStream_t s, const float* cond, const float* null_cond, const float* keep, float p, int64_t rows, int cd,
+                               uint64_t seed, uint32_t row_offset, float* out);
 hipError_t launch_clamp_int(hipStream_t s, const int* in, int64_t n, int lo, int hi, int* out);
 hipError_t launch_randint(hipStream_t s, int* out, int64_t n, int hi, uint64_t seed, uint32_t row_offset);
 hipError_t launch_mixup(hipStream_t s, const float* v, const int64_t* perm, double lam, int64_t rows, int cols, float* out);

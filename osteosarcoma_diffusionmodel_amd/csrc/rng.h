@@ -12,6 +12,7 @@ enum : uint32_t {
   TAG_QNOISE = 0x514e5300u,     // eps of q_sample
   TAG_TSTEP = 0x54535400u,      // randint timesteps
   TAG_DROPOUT = 0x44524f00u,    // + block index in the low byte
+  TAG_COND_DROP = TAG_DROPOUT + 0x80u,   // condition dropout of a training batch: one draw per row (block indices stay below 0x80)
   TAG_USER = 0x55535200u,
 };
 
@@ -39,6 +40,13 @@ __device__ __forceinline__ uint4 philox_at(uint64_t seed, uint32_t row, uint32_t
 __device__ __forceinline__ float u01_open(uint32_t x) { return fmaf((float)x, 2.3283064365386963e-10f, 1.1641532182693481e-10f); }
 // u in [0,1): top 24 bits
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-08f; }
+
+// Condition dropout (osd_train_condition_dropout): does batch row r keep its condition?  An injected keep vector decides, else the
+// row's uniform under TAG_COND_DROP -- the dropout keep-mask's construction with one column per row, addressed by the global row id.
+__device__ __forceinline__ bool cond_kept(const float* keep, float p, uint64_t seed, uint32_t row_offset, int64_t r) {
+  if (keep) return keep[r] != 0.f;
+  return u01(philox_at(seed, row_offset + (uint32_t)r, 0u, 0u, TAG_COND_DROP).x) >= p;
+}
 
 // 4 standard normals from one Philox block (two Box-Muller pairs).
 // v_sin_f32 / v_cos_f32 take their argument in revolutions, so sin(2*pi*u) is one op.

@@ -2,6 +2,7 @@
 // fused forward + backward of the eps-prediction MSE loss, mixup lives in api.hip,
 // clip_grad_norm_ + AdamW over flat buffers.
 #include <math.h>
+#include <cmath>
 #include <algorithm>
 #include "handle.h"
 #include "kernels.h"
@@ -496,6 +497,8 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
   OSD_TRY(check_rows(n));
   const bool from_src = h && h->have_batch_src;          // one-shot: consumed (or dropped) by this call
   if (h) h->have_batch_src = false;
+  const bool cond_drop = h && h->have_cond_drop;        // one-shot as well (osd_train_condition_dropout)
+  if (h) h->have_cond_drop = false;
   if ((!from_src && (!x0 || !cond)) || !loss_out) { set_error("null tensor"); return OSD_EINVAL; }
   if (n == 0) { set_error("empty batch"); return OSD_EINVAL; }
   OSD_TRY(check_row_offset(row_offset, n));
@@ -554,8 +557,17 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
                                 w.noise, t_draw, a.T, w.cond_mix, cp ? w.x0_mix : nullptr, w.xld, &zl));
     cond = w.cond_mix;
     x0 = cp ? w.x0_mix : nullptr;
+    // condition dropout after the mix: the null condition into the rows that drop theirs, in place (one tiny launch, only when asked for)
+    if (cond_drop)
+      OSD_HIP(launch_cond_dropout(s, w.cond_mix, h->d_null_cond + (size_t)(a.cond_dim + 63) / 64 * 64, h->cond_drop_keep, h->cond_drop_p, n,
+                                  a.cond_dim, seed, roff, w.cond_mix));
   } else {
     OSD_HIP(launch_q_sample(s, x0, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, seed, roff, w.x_t, w.noise, t_draw, a.T, w.xld, &zl));
+    if (cond_drop) {       // condition dropout of a caller-supplied batch: the replaced rows land in the workspace
+      OSD_HIP(launch_cond_dropout(s, cond, h->d_null_cond + (size_t)(a.cond_dim + 63) / 64 * 64, h->cond_drop_keep, h->cond_drop_p, n, a.cond_dim,
+                                  seed, roff, w.cond_mix));
+      cond = w.cond_mix;
+    }
   }
   const float* eps_true = noise ? noise : w.noise;
   OSD_TRY(cond_embed_fwd(h, s, cond, n, w));
@@ -621,6 +633,21 @@ int osd_train_batch_source(osd_handle* h, const float* data, int64_t ld_data, co
   b.lam = (float)lam; b.oml = (float)(1.0 - lam);
   h->batch_src = b;
   h->have_batch_src = true;
+  return OSD_OK;
+}
+
+int osd_train_condition_dropout(osd_handle* h, const float* null_cond_host, double p, const float* keep_dev) {
+  if (!h) { set_error("null handle"); return OSD_EINVAL; }
+  if (!(p >= 0.0 && p <= 1.0)) { set_error("condition dropout p must be in [0,1]"); return OSD_EINVAL; }
+  h->have_cond_drop = false;
+  if (p == 0.0 && !keep_dev) return OSD_OK;          // nothing to drop: the next training call is the plain one
+  if (!null_cond_host) { set_error("null_cond is null"); return OSD_EINVAL; }
+  for (int i = 0; i < h->arch.cond_dim; ++i)
+    if (!std::isfinite(null_cond_host[i])) { set_error("null_cond[%d] is not finite", i); return OSD_EINVAL; }
+  const float* dev = nullptr;
+  OSD_TRY(upload_null_cond(h, 1, null_cond_host, &dev));
+  h->cond_drop_p = (float)p; h->cond_drop_keep = keep_dev;
+  h->have_cond_drop = true;
   return OSD_OK;
 }
 

@@ -306,6 +306,11 @@ class BiologyAwareDiffusionModel(nn.Module):
         # the conditioning branch's backward below h0 (time-table scatter, two 64-wide dgrads, SiLU backward) as one launch
         # (k_cond_bwd, csrc/k_train.hip): None / True (library default) or False (four launches)
         self.cond_bwd_fused = None
+        # classifier-free guidance: the null condition c0 (condition_dim floats), the condition the model saw in the rows condition dropout
+        # replaced (train.py: training.condition_dropout) and the unconditional branch of guided sampling (sample / predict_noise:
+        # guidance_scale).  A plain attribute -- no parameter, no buffer: it goes through condition_embed / cond_proj like any condition,
+        # and state_dict() keeps the reference's keys.  None: the model has none (every reference checkpoint)
+        self.null_condition = m.get("null_condition")
         # optional constraint losses (set_constraints); None = the reference's eps-MSE only
         self._constraints = None
         self._constraints_version = 0
@@ -425,6 +430,27 @@ class BiologyAwareDiffusionModel(nn.Module):
     def _flags(self) -> int:
         return L.OSD_F_TRAIN_MODE if self.training else 0
 
+    def _guidance(self, guidance_scale):
+        """(w, c0 as a host float32 array) of a guided call, or None when guidance_scale == 1 (the unguided paths)."""
+        w = float(guidance_scale)
+        if not np.isfinite(w):
+            raise ValueError(f"guidance_scale={guidance_scale} is not finite")
+        if np.float32(w) == np.float32(1.0):
+            return None
+        if self.null_condition is None:
+            raise ValueError("guidance_scale != 1 needs the model's null condition: set config['model']['null_condition'] "
+                             "(or model.null_condition) to condition_dim floats, the vector condition dropout trained the model on")
+        c0 = self.null_condition
+        c0 = c0.detach().cpu().numpy() if isinstance(c0, torch.Tensor) else np.asarray(c0)
+        c0 = np.ascontiguousarray(c0, dtype=np.float32).reshape(-1)
+        if c0.size != self.condition_dim:
+            raise ValueError(f"null_condition has {c0.size} entries, condition_dim is {self.condition_dim}")
+        if not np.isfinite(c0).all():
+            raise ValueError("null_condition is not finite")
+        if self.training:
+            raise ValueError("guided sampling is eval mode only (model.eval()): no dropout inside a guided evaluation")
+        return w, c0
+
     # -- q_sample (models/diffusion.py:328-342) -------------------------------------------------
     def q_sample(self, x_0, t, noise=None, *, seed: Optional[int] = None):
         eng = self._engine()
@@ -459,9 +485,30 @@ class BiologyAwareDiffusionModel(nn.Module):
         return self.predict_noise(x_t, t, conditions, dropout_masks=dropout_masks, seed=seed)
 
     def predict_noise(self, x_t, t, conditions, *, dropout_masks: Optional[Sequence[torch.Tensor]] = None,
-                      seed: Optional[int] = None):
+                      seed: Optional[int] = None, guidance_scale: float = 1.0):
         """DiffusionUNet.forward(x_t, t/T, condition_embed(c)) (models/diffusion.py:370-373); ``t`` is an
-        int (shared) or an integer tensor of per-row timestep indices."""
+        int (shared) or an integer tensor of per-row timestep indices.
+
+        ``guidance_scale=w`` != 1: the classifier-free-guidance prediction eps(c0) + w * (eps(c) - eps(c0)) with the model's
+        ``null_condition`` c0 (eval mode, inference only)."""
+        guide = self._guidance(guidance_scale)
+        if guide is not None:
+            if dropout_masks is not None:
+                raise ValueError("guided prediction is eval mode only: no dropout masks")
+            if isinstance(x_t, torch.Tensor) and x_t.requires_grad or isinstance(conditions, torch.Tensor) and conditions.requires_grad:
+                raise ValueError("guided prediction is inference only: inputs must not require grad")
+            eng = self._engine()
+            x_t = self._prep(x_t, self.data_dim, "x_t")
+            conditions = self._prep(conditions, self.condition_dim, "conditions")
+            n = x_t.shape[0]
+            if conditions.shape[0] != n:
+                raise RuntimeError(f"conditions has {conditions.shape[0]} rows but x_t has {n}")
+            eps = torch.empty_like(x_t)
+            t_idx, t_all = (None, t) if isinstance(t, int) else (self._t32(t, n, x_t.device), 0)
+            L.check(L.lib().osd_denoiser_forward_guided(eng.handle, L.ptr(x_t), L.ptr(t_idx), t_all, L.ptr(conditions), n, L.ptr(eps), 0,
+                                                        guide[1].ctypes.data, guide[0]))
+            self._note_precision(eng)
+            return eps
         eng = self._engine()
         x_t = self._prep(x_t, self.data_dim, "x_t")
         conditions = self._prep(conditions, self.condition_dim, "conditions")
@@ -508,13 +555,18 @@ class BiologyAwareDiffusionModel(nn.Module):
     @torch.no_grad()
     def sample(self, conditions, num_samples: int = 1, *, x_T=None, noise=None, seed: Optional[int] = None,
                row_offset: int = 0, return_mutation_mask: bool = False, num_inference_steps: Optional[int] = None,
-               eta: float = 0.0):
+               eta: float = 0.0, guidance_scale: float = 1.0):
         """Full reverse chain.  ``x_T`` [N,D] and ``noise`` [T-1,N,D] (draw order t = T-1..1) inject the
         random draws; otherwise Philox(seed, row_offset + row) generates them on the device.
 
         ``num_inference_steps=S`` runs the strided DDIM sampler instead (ddim.py: S of the T timesteps, ``eta`` in [0, 1]
         scales its noise; 0 is deterministic after x_T, 1 with S = T is the DDPM chain).  x_T is the DDPM chain's for the same
-        seed / row_offset; ``noise`` is then [S-1,N,D] (draw order s = S-1..1) and needs eta > 0."""
+        seed / row_offset; ``noise`` is then [S-1,N,D] (draw order s = S-1..1) and needs eta > 0.
+
+        ``guidance_scale=w`` != 1 runs the classifier-free-guidance chain (DDPM or DDIM alike): every step uses
+        eps(c0) + w * (eps(c) - eps(c0)), c0 the model's ``null_condition``; the draws are the unguided chain's.  Per-layer kernels
+        (``last_sampler == "graph"``), fp32, eval mode."""
+        guide = self._guidance(guidance_scale)
         plan = None
         if num_inference_steps is not None:
             from .ddim import ddim_step_table, ddim_timesteps
@@ -546,7 +598,7 @@ class BiologyAwareDiffusionModel(nn.Module):
         if seed is None:
             seed = _draw_seed()
         flags = self._flags() | (L.OSD_F_GRAPH if self.use_graph else 0)
-        engine = L.lib().osd_sample_engine(eng.handle, n, flags)
+        engine = 0 if guide is not None else L.lib().osd_sample_engine(eng.handle, n, flags)
         if engine < 0:
             L.check(engine)
         if engine == 1:
@@ -560,7 +612,13 @@ class BiologyAwareDiffusionModel(nn.Module):
             return int(v.value)
 
         gave_up_before = counter(b"chain_fallbacks")
-        if plan is None:
+        if guide is not None:
+            tau, coef = plan if plan is not None else (None, None)
+            L.check(L.lib().osd_sample_chain_guided(eng.handle, L.ptr(conditions), n, L.ptr(xT), L.ptr(zs), seed, int(row_offset),
+                                                    L.ptr(out), L.ptr(mask), flags, None if tau is None else tau.ctypes.data,
+                                                    None if coef is None else coef.ctypes.data, 0 if tau is None else int(tau.size),
+                                                    guide[1].ctypes.data, guide[0]))
+        elif plan is None:
             L.check(L.lib().osd_sample_chain(eng.handle, L.ptr(conditions), n, L.ptr(xT), L.ptr(zs), seed, int(row_offset),
                                              L.ptr(out), L.ptr(mask), flags))
         else:

@@ -60,11 +60,23 @@ class SyntheticPatientGenerator:
         row = torch.tensor([values], dtype=torch.float32, device=self.device)
         return row.repeat(num_samples, 1)
 
+    def _guidance_scale(self, guidance_scale: float) -> float:
+        """The scale handed to model.sample: the caller's when the model has a null condition, else 1 (today's behaviour)."""
+        if float(guidance_scale) != 1.0 and getattr(self.model, "null_condition", None) is None:
+            logger.info(f"guidance_scale={guidance_scale} ignored: the model has no null condition "
+                        "(config['model']['null_condition']; train with training.condition_dropout > 0)")
+            return 1.0
+        return float(guidance_scale)
+
     @torch.no_grad()
     def generate(self, num_samples: int, scenario: Optional[Dict] = None, guidance_scale: float = 1.0,
                  *, seed: Optional[int] = None, row_offset: int = 0, x_T=None, noise=None, sampling_steps: Optional[int] = None,
                  eta: float = 0.0) -> Dict[str, np.ndarray]:
-        """utils/generate.py:96-144.  ``guidance_scale`` is accepted and ignored, as in the reference.
+        """utils/generate.py:96-144.  ``guidance_scale`` is the classifier-free-guidance strength (``model.sample(guidance_scale=w)``:
+        1 the plain conditional sampler, larger values follow the scenario more strongly) when the model has a null condition
+        (``model.null_condition``: trained with ``training.condition_dropout``).  A model without one -- every reference
+        checkpoint -- ignores the value, as the reference does.  The config's ``generation.guidance_scale`` is not read implicitly,
+        for the reason ``sampling_steps`` is not.
         Keyword-only extras inject the random draws / shard the Philox stream.  ``sampling_steps=S`` runs the strided DDIM
         sampler (``model.sample(num_inference_steps=S, eta=eta)``); the config's ``generation.sampling_steps`` is not read
         implicitly: ``generate(n, sc, sampling_steps=config["generation"]["sampling_steps"])`` honours it."""
@@ -81,12 +93,14 @@ class SyntheticPatientGenerator:
                                  "accepted for a cVAE model (pass z= to model.sample directly)")
             if sampling_steps is not None or eta:
                 raise ValueError("sampling_steps / eta select the diffusion model's DDIM sampler and are not accepted for a cVAE model")
+            if float(guidance_scale) != 1.0:
+                raise ValueError("guidance_scale != 1 selects the diffusion model's guided sampler and is not accepted for a cVAE model")
             samples = self.model.sample(conditions, num_samples=num_samples).cpu().numpy()
             mutations = (samples[:, :md] > 0.5).astype(float)
         else:
             samples, mask = self.model.sample(conditions, num_samples=num_samples, seed=seed, row_offset=row_offset,
                                               x_T=x_T, noise=noise, return_mutation_mask=True, num_inference_steps=sampling_steps,
-                                              eta=eta)
+                                              eta=eta, guidance_scale=self._guidance_scale(guidance_scale))
             samples = samples.cpu().numpy()
             # (mutations > 0.5).astype(float), evaluated by the last reverse step's epilogue on the device
             mutations = mask.cpu().numpy().astype(float)
@@ -98,7 +112,7 @@ class SyntheticPatientGenerator:
 
     def generate_scenarios(self, scenarios: List[Dict], samples_per_scenario: int, *, seed: Optional[int] = None,
                            batched: bool = True, sampling_steps: Optional[int] = None,
-                           eta: float = 0.0) -> Dict[str, Dict[str, np.ndarray]]:
+                           eta: float = 0.0, guidance_scale: float = 1.0) -> Dict[str, Dict[str, np.ndarray]]:
         """utils/generate.py:146-175: one result dict per scenario name.
 
         The reference runs the scenarios one after the other, each a chain of T sequential steps.  Rows never interact and the
@@ -106,14 +120,14 @@ class SyntheticPatientGenerator:
         once: at the reference's default size (3 scenarios x 1000 patients, config.yaml:119-141) a reverse step is bound by
         launch latency, not by rows, and T steps over 3000 rows cost about what T steps over 1000 do.  ``batched=False`` restores
         the reference's loop (one chain, and one freshly drawn Philox seed, per scenario).  ``sampling_steps`` / ``eta`` select the
-        strided DDIM sampler, as in ``generate``."""
+        strided DDIM sampler, ``guidance_scale`` the guided one, as in ``generate``."""
         if not batched or hasattr(self.model, "vae") or len(scenarios) < 2:
             out = {}
             for scenario in scenarios:
                 name = scenario["name"]
                 logger.info(f"\nGenerating scenario: {name}")
                 out[name] = self.generate(num_samples=samples_per_scenario, scenario=scenario["conditions"],
-                                          sampling_steps=sampling_steps, eta=eta)
+                                          sampling_steps=sampling_steps, eta=eta, guidance_scale=guidance_scale)
             return out
         n = int(samples_per_scenario)
         for scenario in scenarios:
@@ -123,7 +137,8 @@ class SyntheticPatientGenerator:
         conditions = torch.cat([self.create_conditions(n, sc["conditions"]) for sc in scenarios], dim=0)
         with torch.no_grad():
             samples, mask = self.model.sample(conditions, num_samples=conditions.shape[0], seed=seed, return_mutation_mask=True,
-                                              num_inference_steps=sampling_steps, eta=eta)
+                                              num_inference_steps=sampling_steps, eta=eta,
+                                              guidance_scale=self._guidance_scale(guidance_scale))
         samples, mask, cond_np = samples.cpu().numpy(), mask.cpu().numpy().astype(float), conditions.cpu().numpy()
         md, ed = self.mutation_dim, self.expression_dim
         out = {}
@@ -177,6 +192,10 @@ def load_trained_model(checkpoint_path: Path, config: dict, device: str):
         model = BiologyConstrainedVAE(mutation_dim=dims[0], expression_dim=dims[1], pathway_dim=dims[2],
                                       condition_dim=saved_cond_dim, config=config)
     model.load_state_dict(state_dict)
+    # the null condition of classifier-free guidance is no parameter: it travels in the checkpoint's own config
+    saved_null = (checkpoint.get("config") or {}).get("model", {}).get("null_condition")
+    if arch == "diffusion" and model.null_condition is None and saved_null is not None:
+        model.null_condition = [float(v) for v in saved_null]
     model.to(device)
     model.eval()
     logger.info("Model loaded successfully!")

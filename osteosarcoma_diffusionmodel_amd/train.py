@@ -77,15 +77,21 @@ class FlatParams:
 
 
 def _loss_fwd_bwd(model: BiologyAwareDiffusionModel, x0, cond, grad_ptrs, *, t=None, noise=None, dropout_masks=None,
-                  seed=None, row_offset=0, loss_scale=1.0, events=None, engine=None, source=None) -> torch.Tensor:
+                  seed=None, row_offset=0, loss_scale=1.0, events=None, engine=None, source=None, cond_drop=None) -> torch.Tensor:
     """One call of osd_train_loss_fwd_bwd; returns the 1-element device loss tensor.  ``engine``: the Trainer hands over
     its engine, whose parameter pointers are the flat buffer's views (checked by the Trainer), so the per-call option /
-    signature round of ``model._engine()`` is skipped; the call itself re-derives the tables that follow the weights."""
+    signature round of ``model._engine()`` is skipped; the call itself re-derives the tables that follow the weights.
+    ``cond_drop`` = (null condition as a host float32 array, p, keep vector or None): condition dropout of this call's batch
+    (osd_train_condition_dropout: rows that do not keep their condition get the null condition, after the mixup)."""
     if engine is None:
         eng = model._engine()
     else:
         eng = engine
         L.check(L.lib().osd_set_stream(eng.handle, C.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream)))
+    if cond_drop is not None and cond_drop[2] is not None:       # checked before anything one-shot is armed on the handle
+        rows = source[2].shape[0] if source is not None else x0.shape[0]
+        if cond_drop[2].numel() != rows:
+            raise RuntimeError("cond_keep must have one entry per row")
     if source is not None:
         # rows of a device-resident dataset (ResidentSplit): gathered, mixed up and noised by the library in one pass
         data, conds, idx_a, idx_b, lam = source
@@ -110,6 +116,12 @@ def _loss_fwd_bwd(model: BiologyAwareDiffusionModel, x0, cond, grad_ptrs, *, t=N
         flags |= L.OSD_F_TRAIN_MODE
     seed = _draw_seed() if seed is None else seed
     loss = torch.empty(1, device=dev_, dtype=torch.float32)
+    keep_vec = None
+    if cond_drop is not None:
+        c0, p_drop, keep_vec = cond_drop
+        if keep_vec is not None:
+            keep_vec = keep_vec.to(device=dev_, dtype=torch.float32).contiguous()
+        L.check(L.lib().osd_train_condition_dropout(eng.handle, c0.ctypes.data, float(p_drop), L.ptr(keep_vec)))
     ev_arr, n_ev = None, 0
     if events is not None:
         ev_arr = (C.c_void_p * len(events))(*[e.cuda_event for e in events])
@@ -535,6 +547,19 @@ class Trainer:
         self.early_stopping = EarlyStopping(patience=tc["patience"], min_delta=tc["min_delta"])
         alpha = tc["augmentation"]["mixup_alpha"]
         self.mixup = MixupAugmentation(alpha=alpha, model=self.model) if alpha > 0 else None
+        # condition dropout (classifier-free guidance): each batch row's condition is replaced by the model's null condition with this
+        # probability, after mixup; 0 (the default) is the reference's training step.  A model without a null condition gets the
+        # zero vector, and the config -- hence every checkpoint -- carries it
+        self.condition_dropout = float(tc.get("condition_dropout", 0.0))
+        if not 0.0 <= self.condition_dropout <= 1.0:
+            raise ValueError(f"training.condition_dropout={self.condition_dropout} outside [0, 1]")
+        if self.condition_dropout > 0.0:
+            if self.is_vae:
+                raise ValueError("training.condition_dropout trains the diffusion model's null condition and is not accepted for a cVAE model")
+            if self.model.null_condition is None:
+                self.model.null_condition = [0.0] * self.model.condition_dim
+            c0 = self.model.null_condition
+            self.config["model"]["null_condition"] = [float(v) for v in (c0.tolist() if hasattr(c0, "tolist") else c0)]
         self.save_dir = Path(tc["save_dir"])
         self.save_dir.mkdir(parents=True, exist_ok=True)
         self.history = {"train_loss": [], "val_loss": []}
@@ -614,10 +639,11 @@ class Trainer:
 
     # one optimisation step on an already device-resident (and mixed) batch
     def train_step(self, data, conditions, survival=None, *, t=None, noise=None, dropout_masks=None, seed=None, comm_events=None,
-                   source=None, **vae_kw) -> torch.Tensor:
+                   source=None, cond_keep=None, **vae_kw) -> torch.Tensor:
         """``comm_events``: an optional pair of timing ``torch.cuda.Event``s recorded on the current stream when its own
         backward has been enqueued and again once it has waited for the gradient exchange -- their distance is the
-        exposed (not overlapped) communication time of the step (bench.py)."""
+        exposed (not overlapped) communication time of the step (bench.py).  ``cond_keep``: float 0/1 per row, injects which rows
+        keep their condition under condition dropout (default: drawn on the device from the step's seed and global row ids)."""
         if not self.flat.is_current(quick=True):
             raise RuntimeError("model parameters were re-allocated after Trainer construction (e.g. model.to()); rebuild the Trainer")
         if self._engine is not None and (self._engine.constraints_version != self.model._constraints_version or
@@ -638,9 +664,18 @@ class Trainer:
             self.global_step += 1
             return loss.detach()
         rows = source[3].shape[0] if source is not None else data.shape[0]
+        cond_drop = None
+        if self.condition_dropout > 0.0 or cond_keep is not None:
+            c0 = self.model.null_condition
+            if c0 is None:
+                raise ValueError("cond_keep needs the model's null condition (config['model']['null_condition'])")
+            c0 = c0.detach().cpu().numpy() if isinstance(c0, torch.Tensor) else np.asarray(c0)
+            cond_drop = (np.ascontiguousarray(c0, dtype=np.float32).reshape(-1), self.condition_dropout, cond_keep)
+            if cond_drop[0].size != self.model.condition_dim:
+                raise ValueError(f"null_condition has {cond_drop[0].size} entries, condition_dim is {self.model.condition_dim}")
         loss = _loss_fwd_bwd(self.model, data, conditions, self._grad_ptrs, t=t, noise=noise, dropout_masks=dropout_masks, seed=seed,
                              row_offset=self.rank * rows, loss_scale=1.0 / self.world, events=self._events, engine=self._engine,
-                             source=None if source is None else (source[0], source[1], source[3], source[4], source[5]))
+                             source=None if source is None else (source[0], source[1], source[3], source[4], source[5]), cond_drop=cond_drop)
         if comm_events is not None:
             comm_events[0].record()
         if self.dist:
