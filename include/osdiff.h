@@ -250,6 +250,33 @@ int osd_sample_chain_guided(osd_handle *h, const float *cond, int64_t n, const f
                             const float *step_coef, int32_t n_steps, const float *null_cond_host,
                             float guidance_scale);
 
+/* Known-feature conditioning: the chain samples around observed values (the replacement method of Song et al. 2021; RePaint without
+ * its resampling loops).  known: dev [n][ld_known], a finite value is an observation of that element, NaN leaves it to the chain.
+ * Step s of the plan goes from tau_s to tau' = tau_{s-1} (abar' = 1 at s = 0); with La_s = sqrt(abar'), Ls_s = sqrt(1 - abar'):
+ *   free  element:  x' = A_s*x + B_s*eps + C_s*z          the unconstrained step, operation for operation
+ *   known element:  x' = fmaf(La_s, known, Ls_s*z)        s > 0;   s == 0:  x' = known, bit for bit
+ * z is the step's posterior draw at the element's own address: Philox (seed, row_offset + row, f/4, step counter s), or the caller's
+ * noises[n_steps-1-s] -- a replaced element has no other use for it.  Every step with s > 0 draws z, also where C_s == 0 (eta = 0: the
+ * free elements add exactly zero there), so noises is read at eta = 0 too and an all-NaN known gives the unconstrained per-layer
+ * chain's bits.  Step 0 draws nothing; x_T is the unconstrained chain's and is not replaced (abar_{T-1} ~ 0).  mut_mask_out is
+ * (x_out > 0.5) as ever: for an observed mutation of 0 or 1, the observation.
+ *   timesteps == NULL   the DDPM chain (step_coef / known_level / n_steps ignored); the levels are the schedule's own buffers,
+ *                       (sqrt_ac[s-1], sqrt_1m_ac[s-1]) as osd_set_schedule received them
+ *   otherwise           osd_sample_chain_steps' plan and, host, known_level [n_steps][2] = (La_s, Ls_s), row 0 = (1, 0).  The library
+ *                       folds nothing (ddim.py: known_level_table gathers the rows from the fp32 schedule buffers)
+ *   null_cond_host == NULL  unguided (guidance_scale ignored); otherwise osd_sample_chain_guided's guided step, same output launch
+ * One fused output_proj + posterior launch per step (EpiPosteriorKnown); per-layer kernels only, whatever "sampler" says
+ * (osd_sample_engine(h, -1, 0) then reports 0; no warning, "chain_fallbacks" untouched); a row's result does not depend on the chunk
+ * or shard it is in ("input_splitk" = 0).  OSD_F_TRAIN_MODE is allowed for unguided chains (the trunk is the unconstrained chain's).
+ * OSD_EINVAL: known == NULL, ld_known < D, known_level[0] != (1, 0), a non-finite level, and everything osd_sample_chain_steps /
+ * osd_sample_chain_guided reject; OSD_EUNSUPPORTED: "precision" = 1. */
+int osd_sample_chain_known(osd_handle *h, const float *cond, int64_t n, const float *x_T,
+                           const float *noises, uint64_t seed, int64_t row_offset, float *x_out,
+                           float *mut_mask_out, int flags, const int32_t *timesteps,
+                           const float *step_coef, const float *known_level, int32_t n_steps,
+                           const float *null_cond_host, float guidance_scale, const float *known,
+                           int64_t ld_known);
+
 /* eps_g of ONE guided evaluation (DiffusionUNet.forward twice, models/diffusion.py:210-256, combined as above), eval mode only:
  * osd_denoiser_forward's x / t_index / t_all / cond / eps, osd_sample_chain_guided's null_cond_host / guidance_scale and errors. */
 int osd_denoiser_forward_guided(osd_handle *h, const float *x, const int32_t *t_index, int32_t t_all,

@@ -527,6 +527,9 @@ int osd_destroy(osd_handle* h) {
   if (h->d_null_cond) e = hipFree(h->d_null_cond);
   if (h->null_ev) e = hipEventDestroy(h->null_ev);
   free(h->null_host);
+  if (h->known_level) e = hipFree(h->known_level);
+  if (h->known_ev) e = hipEventDestroy(h->known_ev);
+  free(h->known_level_host);
   if (h->normsq_dev) e = hipFree(h->normsq_dev);
   if (h->parts_dev) e = hipFree(h->parts_dev);
   if (h->t_san) e = hipFree(h->t_san);
@@ -597,6 +600,8 @@ int osd_set_schedule(osd_handle* h, const float* sqrt_ac, const float* sqrt_1m_a
     OSD_HIP(hipMemcpy(h->d_coef, abc.data(), abc.size() * 4, hipMemcpyHostToDevice));
   }
   OSD_HIP(hipMemcpy(h->d_time_emb, time_emb, (size_t)a.T * a.time_dim * 4, hipMemcpyHostToDevice));
+  h->sched_sqrt_ac.assign(sqrt_ac, sqrt_ac + a.T);
+  h->sched_sqrt_1m.assign(sqrt_1m_ac, sqrt_1m_ac + a.T);
   h->have_schedule = true;
   return OSD_OK;
 }
@@ -717,6 +722,13 @@ struct Guide {
   float w;
 };
 
+// Known-feature conditioning of a chain (osd_sample_chain_known): observed elements are overwritten after every step (EpiPosteriorKnown).
+struct Known {
+  const float* known;          // dev [n][ld], NaN = free
+  int64_t ld;
+  const float* level;          // dev [S][2]
+};
+
 // The condition batch of a guided chunk: the m rows' conditions and, as row m, the null condition -- so that c_proj of the null
 // condition comes out of the same launches, with the bits it has as a row of any batch.  stage: [m + 1][cond_dim].
 static int guided_cond(osd_handle* h, hipStream_t s, const Guide& gd, const float* cond, int64_t m, float* stage, const FwdWs& ws) {
@@ -730,7 +742,7 @@ static int guided_cond(osd_handle* h, hipStream_t s, const Guide& gd, const floa
 // [0, m) with the patients' conditions, [m, 2 m) with the null condition), input_proj and output_proj on m.
 static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const float* cond, int64_t n_total, int64_t r0, int64_t m,
                        const float* x_T, const float* noises, uint64_t seed, int64_t row_offset, float* x_out, float* mut_mask_out, int flags,
-                       const Guide* gd = nullptr) {
+                       const Guide* gd = nullptr, const Known* kn = nullptr) {
   const Arch& a = h->arch;
   const int D = a.D, S = plan.n_steps;
   hipStream_t s = sl.stream;
@@ -770,12 +782,22 @@ static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const floa
   // carved behind them (a guided chunk's condition staging) stays aligned
   const int64_t slab_floats = align_up(std::max<int64_t>((int64_t)in_slices * m * a.H0, gn_slices ? (int64_t)(gn_slices + 1) * mt * max_c : 0), 64);
   const int64_t stage_floats = gd ? (m + 1) * (int64_t)a.cond_dim : 0;
-  OSD_TRY(ensure_arena(&sl, need_pad + x_floats + slab_floats + stage_floats));
+  // a padded state reads its observations from rows of Dp floats too: the chunk's known rows, copied once, pad columns NaN (free)
+  const int64_t known_floats = kn && padded ? m * (int64_t)ldx : 0;
+  OSD_TRY(ensure_arena(&sl, need_pad + x_floats + slab_floats + align_up(stage_floats, 64) + known_floats));
   carve_fwd(a, sl.arena, mt, false, &ws);
   float* x = padded ? sl.arena + need_pad : x_out + r0 * D;       // else the chain state lives in the output rows
   float* in_slabs = in_slices ? sl.arena + need_pad + x_floats : nullptr;
   float* cond_stage = sl.arena + need_pad + x_floats + slab_floats;
   if (padded) OSD_HIP(hipMemsetAsync(x, 0, (size_t)m * ldx * 4, s));
+  const float* known = kn ? kn->known + r0 * kn->ld : nullptr;
+  int ldk = kn ? (int)kn->ld : 0;
+  if (kn && padded) {
+    float* kpad = cond_stage + align_up(stage_floats, 64);
+    OSD_HIP(hipMemsetAsync(kpad, 0xff, (size_t)m * ldx * 4, s));          // all bits set: a NaN
+    OSD_HIP(launch_copy2d(s, known, ldk, kpad, ldx, m, D));
+    known = kpad; ldk = ldx;
+  }
   const uint32_t roff = (uint32_t)(row_offset + r0);
   const bool train = (flags & OSD_F_TRAIN_MODE) != 0;
   // conditioning is loop-invariant in eval mode (no dropout inside the embedding MLP): hoisted
@@ -802,7 +824,8 @@ static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const floa
     ea.z = noises ? noises + r0 * D : nullptr; ea.ldzz = D; ea.z_step_stride = (long long)n_total * D; ea.t_first = S - 1;
     ea.seed = seed; ea.row_offset = roff;
     ea.mut_mask = mut_mask_out ? mut_mask_out + r0 * h->cfg.mutation_dim : nullptr; ea.mutation_dim = h->cfg.mutation_dim;
-    OSD_HIP(launch_posterior(s, g, ea));
+    if (kn) OSD_HIP(launch_posterior_known(s, g, EpiPosteriorKnown::Args{ea, known, ldk, kn->level}));
+    else OSD_HIP(launch_posterior(s, g, ea));
     OSD_HIP(launch_add_int(s, sl.t_dev, -1));
     return OSD_OK;
   };
@@ -830,13 +853,14 @@ static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const floa
 // The reverse chain of `plan` over n rows: osd_sample_chain and osd_sample_chain_steps after their argument checks, chain_check_status
 // and ensure_packed.
 static int sample_plan(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
-                       int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const Guide* gd = nullptr) {
+                       int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const Guide* gd = nullptr, const Known* kn = nullptr) {
   // bf16x3 split precision: eval-mode chains on the per-layer launches of split.hip (dropout inside the chain stays fp32)
-  const bool split = !gd && h->precision == 1 && !((flags & OSD_F_TRAIN_MODE) && h->cfg.dropout_p > 0.f);
+  const bool split = !gd && !kn && h->precision == 1 && !((flags & OSD_F_TRAIN_MODE) && h->cfg.dropout_p > 0.f);
   h->last_precision = split ? 1 : 0;
   if (split) OSD_TRY(split_prepare(h, h->stream));
-  // a guided chain runs on the per-layer kernels whatever "sampler" says: the chain kernels' tiles are sized for m trunk rows
-  h->last_engine = (split || gd) ? 0 : chain_pick_engine(h, n, flags);
+  // a guided chain runs on the per-layer kernels whatever "sampler" says: the chain kernels' tiles are sized for m trunk rows; so does
+  // a chain around known values, whose epilogue only the per-layer output_proj launch has
+  h->last_engine = (split || gd || kn) ? 0 : chain_pick_engine(h, n, flags);
   if (h->last_engine == 1 && noises && h->w_out_packed && !chain_uses_squad(h, n)) h->last_engine = 0;      // injected draws at D % 4 != 0: guarded per-layer kernels (the squad chain reads any layout)
   bool fell_back = false;
   if (h->last_engine == 1) {
@@ -877,7 +901,7 @@ static int sample_plan(osd_handle* h, const StepPlan& plan, const float* cond, i
     const int64_t r0 = c * chunk;
     const int64_t m = std::min<int64_t>(chunk, n - r0);
     if (split) rc = split_chain_chunk(h, plan, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
-    else rc = chain_chunk(h, plan, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, gd);
+    else rc = chain_chunk(h, plan, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, gd, kn);
   }
   // join
   for (int i = 0; i < n_slots; ++i) {
@@ -933,14 +957,9 @@ static int upload_plan(osd_handle* h, const int32_t* timesteps, const float* ste
   return OSD_OK;
 }
 
-int osd_sample_chain_steps(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
-                           int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
-                           const float* step_coef, int32_t n_steps) {
-  OSD_TRY(check_ready(h));
-  OSD_TRY(check_rows(n));
-  if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
+// What every entry point that takes a step plan rejects in it.
+static int check_plan(const Arch& a, const int32_t* timesteps, const float* step_coef, int32_t n_steps) {
   if (!timesteps || !step_coef) { set_error("null step plan"); return OSD_EINVAL; }
-  const Arch& a = h->arch;
   if (n_steps < 1 || n_steps > a.T) { set_error("n_steps=%d outside [1,%d]", n_steps, a.T); return OSD_EINVAL; }
   for (int s = 0; s < n_steps; ++s) {
     if (timesteps[s] < 0 || timesteps[s] >= a.T) { set_error("timesteps[%d]=%d outside [0,%d)", s, timesteps[s], a.T); return OSD_EINVAL; }
@@ -948,6 +967,16 @@ int osd_sample_chain_steps(osd_handle* h, const float* cond, int64_t n, const fl
       if (!std::isfinite(step_coef[4 * s + k])) { set_error("step_coef[%d] is not finite", 4 * s + k); return OSD_EINVAL; }
   }
   if (step_coef[2] != 0.f) { set_error("step_coef[2] = C_0 = %g: the last step draws no z, so C_0 must be 0", (double)step_coef[2]); return OSD_EINVAL; }
+  return OSD_OK;
+}
+
+int osd_sample_chain_steps(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                           int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
+                           const float* step_coef, int32_t n_steps) {
+  OSD_TRY(check_ready(h));
+  OSD_TRY(check_rows(n));
+  if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
+  OSD_TRY(check_plan(h->arch, timesteps, step_coef, n_steps));
   OSD_TRY(check_row_offset(row_offset, n));
   if (n == 0) return OSD_OK;
   OSD_HIP(hipSetDevice(h->cfg.device));
@@ -983,16 +1012,7 @@ int osd_sample_chain_guided(osd_handle* h, const float* cond, int64_t n, const f
   OSD_TRY(check_rows(n));
   if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
   const Arch& a = h->arch;
-  if (timesteps) {
-    if (!step_coef) { set_error("null step plan"); return OSD_EINVAL; }
-    if (n_steps < 1 || n_steps > a.T) { set_error("n_steps=%d outside [1,%d]", n_steps, a.T); return OSD_EINVAL; }
-    for (int s = 0; s < n_steps; ++s) {
-      if (timesteps[s] < 0 || timesteps[s] >= a.T) { set_error("timesteps[%d]=%d outside [0,%d)", s, timesteps[s], a.T); return OSD_EINVAL; }
-      for (int k = 0; k < 4; ++k)
-        if (!std::isfinite(step_coef[4 * s + k])) { set_error("step_coef[%d] is not finite", 4 * s + k); return OSD_EINVAL; }
-    }
-    if (step_coef[2] != 0.f) { set_error("step_coef[2] = C_0 = %g: the last step draws no z, so C_0 must be 0", (double)step_coef[2]); return OSD_EINVAL; }
-  }
+  if (timesteps) OSD_TRY(check_plan(a, timesteps, step_coef, n_steps));
   OSD_TRY(check_row_offset(row_offset, n));
   if (n == 0) return OSD_OK;
   OSD_HIP(hipSetDevice(h->cfg.device));
@@ -1003,6 +1023,68 @@ int osd_sample_chain_guided(osd_handle* h, const float* cond, int64_t n, const f
   if (!timesteps) return sample_plan(h, StepPlan{a.T, h->d_temb, h->d_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, &gd);
   OSD_TRY(upload_plan(h, timesteps, step_coef, n_steps));
   return sample_plan(h, StepPlan{n_steps, h->plan_temb, h->plan_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, &gd);
+}
+
+// The level table of a chain around known values, host -> handle-owned device table on the handle's stream.  level_host: the plan's
+// [S][2], or null for the DDPM identity plan, whose rows are the schedule's own: (sqrt_ac[s - 1], sqrt_1m_ac[s - 1]), (1, 0) at s = 0.
+static int upload_known_level(osd_handle* h, const float* level_host, int S, const float** dev) {
+  const Arch& a = h->arch;
+  if (!h->known_level_host) {
+    h->known_level_host = static_cast<float*>(malloc((size_t)a.T * 2 * 4));
+    if (!h->known_level_host) { set_error("out of host memory"); return OSD_ENOMEM; }
+  }
+  if (!h->known_ev) OSD_HIP(hipEventCreateWithFlags(&h->known_ev, hipEventDisableTiming));
+  if (!h->known_level) OSD_HIP(hipMalloc((void**)&h->known_level, (size_t)a.T * 2 * 4));
+  OSD_HIP(hipEventSynchronize(h->known_ev));         // the previous call's upload has read the staging
+  float* hl = h->known_level_host;
+  if (level_host) {
+    memcpy(hl, level_host, (size_t)S * 2 * 4);
+  } else {
+    hl[0] = 1.f; hl[1] = 0.f;
+    for (int s = 1; s < S; ++s) { hl[2 * s] = h->sched_sqrt_ac[s - 1]; hl[2 * s + 1] = h->sched_sqrt_1m[s - 1]; }
+  }
+  OSD_HIP(hipMemcpyAsync(h->known_level, hl, (size_t)S * 2 * 4, hipMemcpyHostToDevice, h->stream));
+  OSD_HIP(hipEventRecord(h->known_ev, h->stream));
+  *dev = h->known_level;
+  return OSD_OK;
+}
+
+int osd_sample_chain_known(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                           int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
+                           const float* step_coef, const float* known_level, int32_t n_steps, const float* null_cond_host,
+                           float guidance_scale, const float* known, int64_t ld_known) {
+  OSD_TRY(check_ready(h));
+  bool unguided = true;
+  if (null_cond_host) OSD_TRY(check_guidance(h, null_cond_host, guidance_scale, flags, &unguided));
+  if (h->precision == 1) { set_error("precision = bf16x3 does not run chains around known values: set precision to fp32"); return OSD_EUNSUPPORTED; }
+  OSD_TRY(check_rows(n));
+  if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
+  const Arch& a = h->arch;
+  if (!known) { set_error("known is null"); return OSD_EINVAL; }
+  if (ld_known < a.D || ld_known > 0x7fffffff) { set_error("ld_known=%lld outside [D=%d, 2^31)", (long long)ld_known, a.D); return OSD_EINVAL; }
+  if (timesteps) {
+    OSD_TRY(check_plan(a, timesteps, step_coef, n_steps));
+    if (!known_level) { set_error("null known_level"); return OSD_EINVAL; }
+    for (int i = 0; i < 2 * n_steps; ++i)
+      if (!std::isfinite(known_level[i])) { set_error("known_level[%d] is not finite", i); return OSD_EINVAL; }
+    if (known_level[0] != 1.f || known_level[1] != 0.f) {
+      set_error("known_level[0] = (%g, %g): the last step returns the observations themselves, so it must be (1, 0)", (double)known_level[0], (double)known_level[1]);
+      return OSD_EINVAL;
+    }
+  }
+  OSD_TRY(check_row_offset(row_offset, n));
+  if (n == 0) return OSD_OK;
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  OSD_TRY(chain_check_status(h));
+  OSD_TRY(ensure_packed(h, h->stream));
+  Guide gd{nullptr, guidance_scale};
+  if (!unguided) OSD_TRY(upload_null_cond(h, 0, null_cond_host, &gd.null_cond));
+  const Guide* g = unguided ? nullptr : &gd;
+  Known kn{known, ld_known, nullptr};
+  OSD_TRY(upload_known_level(h, timesteps ? known_level : nullptr, timesteps ? n_steps : a.T, &kn.level));
+  if (!timesteps) return sample_plan(h, StepPlan{a.T, h->d_temb, h->d_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, g, &kn);
+  OSD_TRY(upload_plan(h, timesteps, step_coef, n_steps));
+  return sample_plan(h, StepPlan{n_steps, h->plan_temb, h->plan_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, g, &kn);
 }
 
 int osd_denoiser_forward_guided(osd_handle* h, const float* x, const int32_t* t_index, int32_t t_all, const float* cond, int64_t n,

@@ -566,6 +566,92 @@ struct EpiPosterior {
   }
 };
 
+// ---- output_proj + posterior update around observed values (the replacement method) ----
+// known [P][F]: a finite value is an observation of that element, NaN leaves it to the chain.  Per element of step t (the plan's
+// step counter, as in EpiPosterior):
+//   free  element:  x' = A_t x + B_t eps + C_t z                       EpiPosterior's arithmetic, operation for operation
+//   known element:  x' = La_t * known + Ls_t * z   (t > 0);   x' = known, bit for bit   (t == 0)
+// level [S][2] = (La_t, Ls_t) = (sqrt(abar), sqrt(1 - abar)) of the timestep the step arrives at, (1, 0) at t = 0.  z is the step's
+// posterior draw at the element's own address -- a replaced element has no other use for it -- so every step with t > 0 draws, also
+// where C_t = 0; the free elements then add the zero EpiPosterior adds (a select on the wave-uniform C_t, not a product with the
+// draw), and an all-NaN `known` gives the unconstrained chain's bits.
+// The !WIDE form only: the x_t and the known quads of one 32 x 32 block at a time (32 registers).  All x_t quads up front
+// (EpiPosterior's WIDE form, 64 registers) with the known quads beside them do not fit the 128 x 128 tile's 256 VGPRs.
+struct EpiPosteriorKnown {
+  static constexpr bool COUNTED_STORES = true;
+  static constexpr bool XBUF = false;
+  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
+  struct Args {
+    EpiPosterior::Args p;
+    const float* known; int ldk;    // [P][F], row stride ldk; NaN = free
+    const float* level;             // dev [S][2] = (La_t, Ls_t)
+  };
+  static bool fast_ok(const Args& a, int F) { return EpiPosterior::fast_ok(a.p, F) && al16(a.known) && a.ldk % 4 == 0; }
+  template <int NFB> using Pre = EpiPosterior::Pre<NFB>;
+  template <int NFB, bool FAST>
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
+    return EpiPosterior::prefetch<NFB, FAST>(a.p, fw, lane, F);
+  }
+  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& ak, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
+                                               Sync&& sync = Sync()) {
+    const EpiPosterior::Args& a = ak.p;
+    const int l31 = lane & 31, h = lane >> 5;
+    const int t = a.t_dev ? *a.t_dev : a.t_imm;
+    const float* c = a.coef + 4 * t;
+    const float cA = c[0], cB = c[1], cC = c[2];
+    const float La = ak.level[2 * t], Ls = ak.level[2 * t + 1];
+    const float* zbase = a.z ? a.z + (long long)(a.t_first - t) * a.z_step_stride : nullptr;
+#pragma unroll
+    for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+      for (int pb = 0; pb < NPB; ++pb) {
+        const int p = pw + 32 * pb + l31;
+        const int pc = p < P ? p : P - 1;
+        float4 xq[4], kq[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          xq[q] = ldq<FAST>(a.xin + (size_t)pc * a.ldx, fw + 32 * fb + 8 * q + 4 * h, F);
+          kq[q] = ldq<FAST>(ak.known + (size_t)pc * ak.ldk, fw + 32 * fb + 8 * q + 4 * h, F);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int f = fw + 32 * fb + 8 * q + 4 * h;
+          const bool ok = p < P && f < F;
+          const float4 bv = pre.bias[fb][q];
+          const float e[4] = {acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w};
+          const float xv[4] = {xq[q].x, xq[q].y, xq[q].z, xq[q].w};
+          const float kv[4] = {kq[q].x, kq[q].y, kq[q].z, kq[q].w};
+          const bool cz = cC != 0.f;         // uniform: the step's table row
+          // every step but the last draws, also where C = 0: the known elements use z there.  A quad without an observation has no
+          // use for the draw then, and its lanes skip the generator (which bounds this launch)
+          const bool any_known = kv[0] == kv[0] || kv[1] == kv[1] || kv[2] == kv[2] || kv[3] == kv[3];
+          float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (t > 0 && (cz || any_known)) {
+            if (zbase) zz = ldq<FAST>(zbase + (size_t)pc * a.ldzz, f, F);
+            else zz = randn4(a.seed, a.row_offset + (uint32_t)p, (uint32_t)(f >> 2), (uint32_t)t, TAG_POSTERIOR);
+          }
+          const float zv[4] = {zz.x, zz.y, zz.z, zz.w};
+          float o[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float fr = fmaf(cA, xv[r], fmaf(cB, e[r], cC * (cz ? zv[r] : 0.f)));
+            const float kn = t > 0 ? fmaf(La, kv[r], Ls * zv[r]) : kv[r];
+            o[r] = (kv[r] == kv[r]) ? kn : fr;      // NaN: free
+          }
+          if (t == 0 && a.mut_mask && ok && f < a.mutation_dim) {
+            float* mrow = a.mut_mask + (size_t)p * a.mutation_dim;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (f + r < a.mutation_dim) mrow[f + r] = (o[r] > 0.5f) ? 1.0f : 0.0f;
+          }
+          if (p < P) stq<FAST>(a.xout + (size_t)pc * a.ldo, f, F, make_float4(o[0], o[1], o[2], o[3]));
+          sync.tick();
+        }
+      }
+  }
+};
+
 // ---- output_proj fused with the MSE loss (models/diffusion.py:373-377) and its gradient ----
 // d = (acc + bias) - noise;  loss += sum d^2 * inv_count;  dout = d * gscale
 struct EpiMse {

@@ -143,6 +143,10 @@ struct osd_handle {
   // the last upload has read the staging (api.hip: upload_null_cond)
   float* d_null_cond = nullptr; float* null_host = nullptr; hipEvent_t null_ev = nullptr;
   bool null_valid[2] = {false, false};      // the device slot holds the staging's vector: a call with the same bits uploads nothing
+  // known-feature conditioning (osd_sample_chain_known): the schedule's two level buffers as osd_set_schedule received them, and the
+  // current call's level table [S][2] on the device with its host staging and the event that says the upload has read it
+  std::vector<float> sched_sqrt_ac, sched_sqrt_1m;
+  float* known_level = nullptr; float* known_level_host = nullptr; hipEvent_t known_ev = nullptr;
   bool have_cond_drop = false; float cond_drop_p = 0.f; const float* cond_drop_keep = nullptr;   // osd_train_condition_dropout: one-shot
   int64_t saved_rows = -1;           // rows of the last osd_denoiser_forward_train whose activations are still in the arena
   // constraint losses (osd_set_constraints); parts_dev = (mse, L_pc, L_me) of the last training call

@@ -197,6 +197,13 @@ hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const EpiPosterior
   if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosterior>(s, g, a);
   return launch_gemm<TileSmall, true, true, EpiPosterior>(s, g, a);
 }
+// launch_posterior's tile choice
+hipError_t launch_posterior_known(hipStream_t s, const GemmArgs& g, const EpiPosteriorKnown::Args& a) {
+  constexpr long POST_BIG_FROM = 512;
+  const long big_tiles = (long)((g.F + 127) / 128) * ((g.P + 127) / 128);
+  if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorKnown>(s, g, a);
+  return launch_gemm<TileSmall, true, true, EpiPosteriorKnown>(s, g, a);
+}
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a) {
   if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiMse>(s, g, a);
   return launch_gemm<TileSmall, true, true, EpiMse>(s, g, a);

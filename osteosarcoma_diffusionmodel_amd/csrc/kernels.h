@@ -22,6 +22,8 @@ hipError_t launch_input_guided(hipStream_t s, const GemmArgs& g, const EpiInputG
 hipError_t launch_input_guided_splitk(hipStream_t s, const GemmArgs& g, const EpiInputGuided::Args& a, float* slabs, int slices);
 hipError_t launch_input_splitk(hipStream_t s, const GemmArgs& g, const EpiInput::Args& a, float* slabs, int slices);
 hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const EpiPosterior::Args& a);
+// output_proj + posterior around observed values (EpiPosteriorKnown); launch_posterior's tile choice
+hipError_t launch_posterior_known(hipStream_t s, const GemmArgs& g, const EpiPosteriorKnown::Args& a);
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a);
 // k_b3t.hip: precision = 1 (hipErrorInvalidValue: outside the kernel's preconditions -- run the fp32 launch)
 hipError_t launch_mse_b3t(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a);

@@ -9,6 +9,9 @@ update x' = A*x + B*eps + C*z:
     =>  A = sqrt(abar' / abar),  B = sqrt(1 - abar' - sigma^2) - sqrt(abar')*sqrt(1 - abar) / sqrt(abar),  C = sigma
 
 With eta = 1 and S = T this is the reference's DDPM chain; eta = 0 is deterministic after x_T.  Pure host code.
+
+``known_level_table`` is the second table of a chain around observed values (``osd_sample_chain_known``): the noise level each
+step arrives at, at which the observations are put back.
 """
 from __future__ import annotations
 
@@ -51,3 +54,26 @@ def ddim_step_table(alphas_cumprod, timesteps, eta: float):
         coef[s, 1] = math.sqrt(max(1.0 - ap - sigma * sigma, 0.0)) - math.sqrt(ap) * math.sqrt(1.0 - a) / math.sqrt(a)
         coef[s, 2] = sigma
     return tau.astype(np.int32), coef.astype(np.float32)
+
+
+def known_level_table(sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, timesteps) -> np.ndarray:
+    """fp32 [S][2] rows (La_s, Ls_s) for ``osd_sample_chain_known``: the level step s arrives at, tau' = tau_{s-1}.
+
+    Row s > 0 gathers (sqrt_alphas_cumprod[tau_{s-1}], sqrt_one_minus_alphas_cumprod[tau_{s-1}]) from the model's fp32 buffers --
+    nothing is recomputed --, row 0 is (1, 0): the last step returns the observations themselves."""
+    def host(b):
+        if hasattr(b, "detach"):
+            b = b.detach().cpu().float().numpy()
+        return np.asarray(b, dtype=np.float32).reshape(-1)
+    sa, s1 = host(sqrt_alphas_cumprod), host(sqrt_one_minus_alphas_cumprod)
+    tau = np.asarray(timesteps, dtype=np.int64).reshape(-1)
+    T = sa.shape[0]
+    if s1.shape[0] != T:
+        raise ValueError("the two schedule buffers differ in length")
+    if tau.size < 1 or tau.min() < 0 or tau.max() >= T:
+        raise ValueError(f"timesteps must be a non-empty list inside [0, {T})")
+    level = np.empty((tau.size, 2), dtype=np.float32)
+    level[0] = (1.0, 0.0)
+    level[1:, 0] = sa[tau[:-1]]
+    level[1:, 1] = s1[tau[:-1]]
+    return level

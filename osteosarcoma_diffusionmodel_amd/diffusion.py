@@ -555,7 +555,7 @@ class BiologyAwareDiffusionModel(nn.Module):
     @torch.no_grad()
     def sample(self, conditions, num_samples: int = 1, *, x_T=None, noise=None, seed: Optional[int] = None,
                row_offset: int = 0, return_mutation_mask: bool = False, num_inference_steps: Optional[int] = None,
-               eta: float = 0.0, guidance_scale: float = 1.0):
+               eta: float = 0.0, guidance_scale: float = 1.0, known=None):
         """Full reverse chain.  ``x_T`` [N,D] and ``noise`` [T-1,N,D] (draw order t = T-1..1) inject the
         random draws; otherwise Philox(seed, row_offset + row) generates them on the device.
 
@@ -565,8 +565,24 @@ class BiologyAwareDiffusionModel(nn.Module):
 
         ``guidance_scale=w`` != 1 runs the classifier-free-guidance chain (DDPM or DDIM alike): every step uses
         eps(c0) + w * (eps(c) - eps(c0)), c0 the model's ``null_condition``; the draws are the unguided chain's.  Per-layer kernels
-        (``last_sampler == "graph"``), fp32, eval mode."""
+        (``last_sampler == "graph"``), fp32, eval mode.
+
+        ``known`` [N,D] samples around observed values (the replacement method): a finite element is an observation and comes
+        back exactly, NaN leaves the element to the chain (Inf raises ValueError).  After every step the observed elements are
+        overwritten with the observation noised to the level the state has reached, sqrt(abar')*known + sqrt(1 - abar')*z, z the
+        step's own draw at that element -- so ``noise`` is accepted at eta = 0 too, where it feeds only the observed elements.
+        Works with the DDPM chain, ``num_inference_steps`` / ``eta`` and ``guidance_scale``; per-layer kernels
+        (``last_sampler == "graph"``), fp32.  ``known=None`` or all-NaN is the unconstrained call."""
         guide = self._guidance(guidance_scale)
+        kn = None
+        if known is not None:
+            kn = self._prep(known, self.data_dim, "known")
+            if kn.shape[0] != int(num_samples):
+                raise RuntimeError(f"known has {kn.shape[0]} rows but num_samples is {int(num_samples)}")
+            if bool(torch.isinf(kn).any()):
+                raise ValueError("known holds Inf: an observation is finite, NaN marks a free element")
+            if bool(torch.isnan(kn).all()):
+                kn = None                       # nothing observed: today's entry points, any engine, their bits
         plan = None
         if num_inference_steps is not None:
             from .ddim import ddim_step_table, ddim_timesteps
@@ -575,7 +591,7 @@ class BiologyAwareDiffusionModel(nn.Module):
             steps = int(num_inference_steps)
             if not 1 <= steps <= self.num_steps:
                 raise ValueError(f"num_inference_steps={steps} outside [1, {self.num_steps}]")
-            if noise is not None and float(eta) == 0.0:
+            if noise is not None and float(eta) == 0.0 and kn is None:
                 raise ValueError("noise: eta = 0 draws no z (pass eta > 0 or leave noise out)")
             plan = ddim_step_table(self.alphas_cumprod, ddim_timesteps(self.num_steps, steps), eta)
         elif float(eta) != 0.0:
@@ -598,7 +614,7 @@ class BiologyAwareDiffusionModel(nn.Module):
         if seed is None:
             seed = _draw_seed()
         flags = self._flags() | (L.OSD_F_GRAPH if self.use_graph else 0)
-        engine = 0 if guide is not None else L.lib().osd_sample_engine(eng.handle, n, flags)
+        engine = 0 if (guide is not None or kn is not None) else L.lib().osd_sample_engine(eng.handle, n, flags)
         if engine < 0:
             L.check(engine)
         if engine == 1:
@@ -612,7 +628,17 @@ class BiologyAwareDiffusionModel(nn.Module):
             return int(v.value)
 
         gave_up_before = counter(b"chain_fallbacks")
-        if guide is not None:
+        if kn is not None:
+            from .ddim import known_level_table
+            tau, coef = plan if plan is not None else (None, None)
+            level = None if tau is None else known_level_table(self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, tau)
+            L.check(L.lib().osd_sample_chain_known(eng.handle, L.ptr(conditions), n, L.ptr(xT), L.ptr(zs), seed, int(row_offset),
+                                                   L.ptr(out), L.ptr(mask), flags, None if tau is None else tau.ctypes.data,
+                                                   None if coef is None else coef.ctypes.data,
+                                                   None if level is None else level.ctypes.data, 0 if tau is None else int(tau.size),
+                                                   None if guide is None else guide[1].ctypes.data, 1.0 if guide is None else guide[0],
+                                                   L.ptr(kn), self.data_dim))
+        elif guide is not None:
             tau, coef = plan if plan is not None else (None, None)
             L.check(L.lib().osd_sample_chain_guided(eng.handle, L.ptr(conditions), n, L.ptr(xT), L.ptr(zs), seed, int(row_offset),
                                                     L.ptr(out), L.ptr(mask), flags, None if tau is None else tau.ctypes.data,

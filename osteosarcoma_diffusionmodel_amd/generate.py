@@ -18,6 +18,44 @@ import torch
 logger = logging.getLogger(__name__)
 
 
+def assemble_known(known, n: int, mutation_dim: int, expression_dim: int, pathway_dim: int) -> np.ndarray:
+    """float32 [n, D] observation array of ``model.sample(known=...)``: a finite value is observed, NaN is left to the sampler.
+
+    ``known`` is an [n or 1, D] array / tensor, or a dict with any of ``mutations`` / ``expression`` / ``pathways``, each
+    [n or 1, its width] (a missing key: the whole block is free).  One row broadcasts to all n.  ValueError on a wrong width, a
+    row count other than 1 or n, and on Inf."""
+    n = int(n)
+    widths = {"mutations": int(mutation_dim), "expression": int(expression_dim), "pathways": int(pathway_dim)}
+    D = sum(widths.values())
+
+    def block(v, width, name):
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        v = np.asarray(v, dtype=np.float32)
+        if v.ndim == 1:
+            v = v[None, :]
+        if v.ndim != 2 or v.shape[1] != width:
+            raise ValueError(f"known {name}: expected [{n} or 1, {width}], got {tuple(v.shape)}")
+        if v.shape[0] not in (1, n):
+            raise ValueError(f"known {name}: {v.shape[0]} rows, expected 1 or {n}")
+        if np.isinf(v).any():
+            raise ValueError(f"known {name} holds Inf: an observation is finite, NaN marks a free element")
+        return np.broadcast_to(v, (n, width))
+
+    if isinstance(known, dict):
+        extra = set(known) - set(widths)
+        if extra:
+            raise ValueError(f"known: unknown block(s) {sorted(extra)}; expected any of {list(widths)}")
+        out = np.full((n, D), np.nan, dtype=np.float32)
+        c0 = 0
+        for name, width in widths.items():
+            if known.get(name) is not None:
+                out[:, c0:c0 + width] = block(known[name], width, name)
+            c0 += width
+        return out
+    return np.array(block(known, D, "features"), dtype=np.float32)        # a copy: the caller's array stays the caller's
+
+
 class SyntheticPatientGenerator:
     """Generate synthetic patients using a trained model (utils/generate.py:19)."""
 
@@ -68,10 +106,16 @@ class SyntheticPatientGenerator:
             return 1.0
         return float(guidance_scale)
 
+    def _known(self, known, n: int):
+        """``known`` of generate / generate_scenarios as the device tensor model.sample takes, or None."""
+        if known is None:
+            return None
+        return torch.from_numpy(assemble_known(known, n, self.mutation_dim, self.expression_dim, self.pathway_dim)).to(self.device)
+
     @torch.no_grad()
     def generate(self, num_samples: int, scenario: Optional[Dict] = None, guidance_scale: float = 1.0,
                  *, seed: Optional[int] = None, row_offset: int = 0, x_T=None, noise=None, sampling_steps: Optional[int] = None,
-                 eta: float = 0.0) -> Dict[str, np.ndarray]:
+                 eta: float = 0.0, known=None) -> Dict[str, np.ndarray]:
         """utils/generate.py:96-144.  ``guidance_scale`` is the classifier-free-guidance strength (``model.sample(guidance_scale=w)``:
         1 the plain conditional sampler, larger values follow the scenario more strongly) when the model has a null condition
         (``model.null_condition``: trained with ``training.condition_dropout``).  A model without one -- every reference
@@ -79,7 +123,10 @@ class SyntheticPatientGenerator:
         for the reason ``sampling_steps`` is not.
         Keyword-only extras inject the random draws / shard the Philox stream.  ``sampling_steps=S`` runs the strided DDIM
         sampler (``model.sample(num_inference_steps=S, eta=eta)``); the config's ``generation.sampling_steps`` is not read
-        implicitly: ``generate(n, sc, sampling_steps=config["generation"]["sampling_steps"])`` honours it."""
+        implicitly: ``generate(n, sc, sampling_steps=config["generation"]["sampling_steps"])`` honours it.
+        ``known`` (``assemble_known``: an [n or 1, D] array, or a dict of ``mutations`` / ``expression`` / ``pathways`` blocks, NaN =
+        free) holds part of every patient fixed: the returned blocks carry the observed values exactly and the rest is sampled
+        around them (``model.sample(known=...)``)."""
         logger.info(f"Generating {num_samples} synthetic patients...")
         if scenario:
             logger.info(f"Scenario: {scenario}")
@@ -95,12 +142,15 @@ class SyntheticPatientGenerator:
                 raise ValueError("sampling_steps / eta select the diffusion model's DDIM sampler and are not accepted for a cVAE model")
             if float(guidance_scale) != 1.0:
                 raise ValueError("guidance_scale != 1 selects the diffusion model's guided sampler and is not accepted for a cVAE model")
+            if known is not None:
+                raise ValueError("known conditions the diffusion model's reverse chain and is not accepted for a cVAE model")
             samples = self.model.sample(conditions, num_samples=num_samples).cpu().numpy()
             mutations = (samples[:, :md] > 0.5).astype(float)
         else:
             samples, mask = self.model.sample(conditions, num_samples=num_samples, seed=seed, row_offset=row_offset,
                                               x_T=x_T, noise=noise, return_mutation_mask=True, num_inference_steps=sampling_steps,
-                                              eta=eta, guidance_scale=self._guidance_scale(guidance_scale))
+                                              eta=eta, guidance_scale=self._guidance_scale(guidance_scale),
+                                              known=self._known(known, num_samples))
             samples = samples.cpu().numpy()
             # (mutations > 0.5).astype(float), evaluated by the last reverse step's epilogue on the device
             mutations = mask.cpu().numpy().astype(float)
@@ -112,7 +162,7 @@ class SyntheticPatientGenerator:
 
     def generate_scenarios(self, scenarios: List[Dict], samples_per_scenario: int, *, seed: Optional[int] = None,
                            batched: bool = True, sampling_steps: Optional[int] = None,
-                           eta: float = 0.0, guidance_scale: float = 1.0) -> Dict[str, Dict[str, np.ndarray]]:
+                           eta: float = 0.0, guidance_scale: float = 1.0, known=None) -> Dict[str, Dict[str, np.ndarray]]:
         """utils/generate.py:146-175: one result dict per scenario name.
 
         The reference runs the scenarios one after the other, each a chain of T sequential steps.  Rows never interact and the
@@ -120,14 +170,15 @@ class SyntheticPatientGenerator:
         once: at the reference's default size (3 scenarios x 1000 patients, config.yaml:119-141) a reverse step is bound by
         launch latency, not by rows, and T steps over 3000 rows cost about what T steps over 1000 do.  ``batched=False`` restores
         the reference's loop (one chain, and one freshly drawn Philox seed, per scenario).  ``sampling_steps`` / ``eta`` select the
-        strided DDIM sampler, ``guidance_scale`` the guided one, as in ``generate``."""
+        strided DDIM sampler, ``guidance_scale`` the guided one, as in ``generate``.  ``known`` ([samples_per_scenario or 1, D] or a
+        dict of blocks, as in ``generate``) holds the same observed values in every scenario: the counterfactual question."""
         if not batched or hasattr(self.model, "vae") or len(scenarios) < 2:
             out = {}
             for scenario in scenarios:
                 name = scenario["name"]
                 logger.info(f"\nGenerating scenario: {name}")
                 out[name] = self.generate(num_samples=samples_per_scenario, scenario=scenario["conditions"],
-                                          sampling_steps=sampling_steps, eta=eta, guidance_scale=guidance_scale)
+                                          sampling_steps=sampling_steps, eta=eta, guidance_scale=guidance_scale, known=known)
             return out
         n = int(samples_per_scenario)
         for scenario in scenarios:
@@ -135,10 +186,13 @@ class SyntheticPatientGenerator:
             logger.info(f"Scenario: {scenario['conditions']}")
         logger.info(f"Generating {len(scenarios)} x {n} synthetic patients in one batch...")
         conditions = torch.cat([self.create_conditions(n, sc["conditions"]) for sc in scenarios], dim=0)
+        kn = self._known(known, n)
+        if kn is not None:
+            kn = kn.repeat(len(scenarios), 1)
         with torch.no_grad():
             samples, mask = self.model.sample(conditions, num_samples=conditions.shape[0], seed=seed, return_mutation_mask=True,
                                               num_inference_steps=sampling_steps, eta=eta,
-                                              guidance_scale=self._guidance_scale(guidance_scale))
+                                              guidance_scale=self._guidance_scale(guidance_scale), known=kn)
         samples, mask, cond_np = samples.cpu().numpy(), mask.cpu().numpy().astype(float), conditions.cpu().numpy()
         md, ed = self.mutation_dim, self.expression_dim
         out = {}
@@ -148,6 +202,30 @@ class SyntheticPatientGenerator:
                                      "conditions": cond_np[rows]}
         logger.info("Generation complete!")
         return out
+
+    def impute(self, features, conditions, *, seed: Optional[int] = None, sampling_steps: Optional[int] = None, eta: float = 0.0,
+               guidance_scale: float = 1.0) -> Dict[str, np.ndarray]:
+        """Fill the holes of real rows: ``features`` [n, D] with NaN where a value is missing, ``conditions`` [n, condition_dim] the
+        rows' own.  Observed values come back exactly, the holes are sampled around them; returns ``generate``'s dictionary."""
+        if hasattr(self.model, "vae"):
+            raise ValueError("impute conditions the diffusion model's reverse chain and is not accepted for a cVAE model")
+        if isinstance(conditions, torch.Tensor):
+            cond = conditions.detach().to(device=self.device, dtype=torch.float32)
+        else:
+            cond = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device=self.device)
+        if cond.dim() != 2 or cond.shape[1] != self.condition_dim:
+            raise ValueError(f"conditions: expected [n, {self.condition_dim}], got {tuple(cond.shape)}")
+        n = cond.shape[0]
+        rows = features.shape[0] if hasattr(features, "shape") and len(features.shape) == 2 else None
+        if rows != n:
+            raise ValueError(f"features: expected [{n}, D] (one row per condition row)")
+        md, ed = self.mutation_dim, self.expression_dim
+        with torch.no_grad():
+            samples, mask = self.model.sample(cond, num_samples=n, seed=seed, return_mutation_mask=True, num_inference_steps=sampling_steps,
+                                              eta=eta, guidance_scale=self._guidance_scale(guidance_scale), known=self._known(features, n))
+        samples = samples.cpu().numpy()
+        return {"mutations": mask.cpu().numpy().astype(float), "expression": samples[:, md:md + ed], "pathways": samples[:, md + ed:],
+                "conditions": cond.cpu().numpy()}
 
     def save_synthetic_data(self, synthetic_data: Dict[str, np.ndarray], output_dir: Path,
                             gene_names: Dict[str, List[str]], prefix: str = "synthetic"):
