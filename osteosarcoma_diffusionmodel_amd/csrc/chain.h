@@ -71,7 +71,7 @@ struct ChainArgs {
   unsigned long long spin_budget;            // s_memrealtime ticks (100 MHz) a dependency wait may take
   unsigned long long* stamps;                // diagnostic (null in production): per workgroup 32 counters of shader cycles --
                                              // dependency wait, tile prologue, K loop, epilogue + drain, whole kernel, units run,
-                                             // placement x 2, then 6 per layer kind (see kcnt in the kernel)
+                                             // placement x 2, then CHAIN_KCNT per layer kind (see kcnt in the kernel)
 };
 
 typedef __attribute__((address_space(1))) unsigned gu32;
@@ -303,8 +303,17 @@ constexpr int CHAIN_WPS = 2;                         // workgroups per CU = wave
 typedef Tile<128, 64, 64, 32> ChainTile;
 constexpr int CHAIN_WPS = 3;
 #endif
-// tiles | flag word (16 B) | 40 per-kind counters of the diagnostic builds | two per-feature parameter blocks (double-buffered over tiles)
-constexpr int CHAIN_PRM_OFF = 2 * (ChainTile::BF * BK + ChainTile::BP * BK) + 4 + 80;      // floats
+// tiles | flag word (16 B) | per-kind counters of the diagnostic builds | two per-feature parameter blocks (double-buffered over tiles)
+// The product library keeps room for 40 counters (its LDS footprint is part of the occupancy contract); a diagnostic library
+// (make DIAG=1) carries 12 per layer kind.
+#ifdef OSD_DIAG
+constexpr int CHAIN_KCNT = 12;
+constexpr int CHAIN_STAMP_FLOATS = 2 * 4 * CHAIN_KCNT;
+#else
+constexpr int CHAIN_KCNT = 10;
+constexpr int CHAIN_STAMP_FLOATS = 80;
+#endif
+constexpr int CHAIN_PRM_OFF = 2 * (ChainTile::BF * BK + ChainTile::BP * BK) + 4 + CHAIN_STAMP_FLOATS;      // floats
 constexpr int CHAIN_LDS_BYTES = (CHAIN_PRM_OFF + 2 * CHAIN_PRM_FLOATS) * 4;
 static_assert(CHAIN_PRM_OFF % 4 == 0, "parameter blocks are read as float4");
 
@@ -369,10 +378,11 @@ __global__ __launch_bounds__(NTHREADS, CHAIN_WPS) void chain_kernel(const ChainA
   }
 
   unsigned long long c_dep = 0, c_pro = 0, c_k = 0, c_epi = 0, c_units = 0;
-  // STAMP: per layer kind {K loop, epilogue until its last store is issued, store drain, barrier, layer-boundary first stage, tiles}
+  // STAMP: per layer kind {K loop, epilogue until its last store is issued, store drain, barrier, layer-boundary first stage, tiles,
+  // four GroupNorm epilogue phases, then -- of the K loop's cycles -- the K steps' closing vmcnt waits and their barriers}
   unsigned long long* const kcnt = reinterpret_cast<unsigned long long*>(smem + 2 * (G::A_ELEMS + G::B_ELEMS) + 4);
   if constexpr (STAMP) {
-    if (tid < 40) kcnt[tid] = 0;
+    if (tid < 4 * CHAIN_KCNT) kcnt[tid] = 0;
     __syncthreads();
   }
   const unsigned long long c_start = STAMP ? __builtin_amdgcn_s_memtime() : 0;
@@ -518,31 +528,6 @@ __global__ __launch_bounds__(NTHREADS, CHAIN_WPS) void chain_kernel(const ChainA
           offB[j] = (unsigned)(rb * Lld0 + st_k4[j]) * 4u;
         }
         int b_panel = 0;                          // which input panel offB was built for
-        auto stage = [&](int k0, float* As, float* Bs, int j) {
-          const unsigned la = __builtin_amdgcn_readfirstlane(lds_addr(As) + (unsigned)wave * 1024u);
-          const unsigned lb = __builtin_amdgcn_readfirstlane(lds_addr(Bs) + (unsigned)wave * 1024u);
-          if (j < NPW) {
-            glds16s(LA + __builtin_amdgcn_readfirstlane(k0), offA[j], __builtin_amdgcn_readfirstlane(la + (unsigned)j * PBYTES));
-          } else {
-            const int jb = j - NPW;
-            const bool first = k0 < LK0;            // uniform: K0 is a multiple of BK (or >= K)
-            const int kend = first ? (LK0 < K ? LK0 : K) : K - LK0;
-            const int kl = first ? k0 : k0 - LK0;   // k inside the panel
-            if (kl + BK <= kend) {
-              glds16s((first ? B0 : B1) + __builtin_amdgcn_readfirstlane(kl), offB[jb], __builtin_amdgcn_readfirstlane(lb + (unsigned)jb * PBYTES));
-            } else {
-              // K tail of a panel whose width is not a multiple of 32 (input_proj, K = D): per-lane clamp to valid floats; the
-              // weights are zero there, so the re-read values do not matter as long as they are finite
-              const float* bb = first ? B0g : B1g;
-              const int ld = first ? Lld0 : Lld1;
-              int k = kl + st_k4[jb];
-              k = k < kend - 4 ? k : kend - 4;
-              int rg = st_row[jb];
-              rg = rg < rowsB ? rg : rowsB - 1;
-              glds16(bb + (size_t)rg * ld + k, __builtin_amdgcn_readfirstlane(lb + (unsigned)jb * PBYTES));
-            }
-          }
-        };
         // the B offsets follow the panel: re-derived (uniform branch, four multiplies) when the K loop crosses K0
         auto b_offsets_for = [&](int k0) {
           const int want = k0 < LK0 ? 0 : 1;
@@ -557,8 +542,50 @@ __global__ __launch_bounds__(NTHREADS, CHAIN_WPS) void chain_kernel(const ChainA
             }
           }
         };
+        // One K stage = NPW weight pieces + NPWB activation pieces per wave.  stage_begin derives the wave-uniform part once (the
+        // panel switch at K0 precedes every DMA that uses the new offsets); a piece is then two scalar moves and one DMA.
+        struct StageCtx { gfloat_ptr sa, sb; unsigned la, lb; int k0; bool tail; };
+        auto stage_begin = [&](int k0, float* As, float* Bs) {
+          b_offsets_for(k0);
+          const bool first = k0 < LK0;              // uniform: K0 is a multiple of BK (or >= K)
+          const int kend = first ? (LK0 < K ? LK0 : K) : K - LK0;
+          const int kl = first ? k0 : k0 - LK0;     // k inside the panel
+          StageCtx c;
+          c.sa = LA + __builtin_amdgcn_readfirstlane(k0);
+          c.sb = (first ? B0 : B1) + __builtin_amdgcn_readfirstlane(kl);
+          c.la = __builtin_amdgcn_readfirstlane(lds_addr(As) + (unsigned)wave * 1024u);
+          c.lb = __builtin_amdgcn_readfirstlane(lds_addr(Bs) + (unsigned)wave * 1024u);
+          c.k0 = k0;
+          c.tail = kl + BK > kend;                  // a panel width that is no multiple of 32 (input_proj, K = D): stage_tail
+          return c;
+        };
+        auto piece = [&](const StageCtx& c, int j) {
+          if (j < NPW) glds16s(c.sa, offA[j], __builtin_amdgcn_readfirstlane(c.la + (unsigned)j * PBYTES));
+          else glds16s(c.sb, offB[j - NPW], __builtin_amdgcn_readfirstlane(c.lb + (unsigned)(j - NPW) * PBYTES));
+        };
+        // K tail of a panel: the activation pieces clamp per lane to valid floats; the weights are zero there, so the re-read
+        // values do not matter as long as they are finite.  Rare (once per unit), so all pieces go out in one block.
+        auto stage_tail = [&](const StageCtx& c) {
+#pragma unroll
+          for (int j = 0; j < NPW; ++j) piece(c, j);
+          const bool first = c.k0 < LK0;
+          const int kend = first ? (LK0 < K ? LK0 : K) : K - LK0;
+          const int kl = first ? c.k0 : c.k0 - LK0;
+          const float* bb = first ? B0g : B1g;
+          const int ld = first ? Lld0 : Lld1;
+#pragma unroll
+          for (int jb = 0; jb < NPWB; ++jb) {
+            int k = kl + st_k4[jb];
+            k = k < kend - 4 ? k : kend - 4;
+            int rg = st_row[jb];
+            rg = rg < rowsB ? rg : rowsB - 1;
+            glds16(bb + (size_t)rg * ld + k, __builtin_amdgcn_readfirstlane(c.lb + (unsigned)jb * PBYTES));
+          }
+        };
         const unsigned long long tt1 = STAMP ? __builtin_amdgcn_s_memtime() : 0;     // buffer 0 holds this tile's first K stage
 
+        unsigned long long c_kw = 0, c_kb = 0;      // STAMP: this tile's cycles in the K steps' closing vmcnt waits / barriers
+        (void)c_kw; (void)c_kb;
         f32x16 acc[T::NFB][T::NPB];
 #pragma unroll
         for (int i = 0; i < T::NFB; ++i)
@@ -567,46 +594,80 @@ __global__ __launch_bounds__(NTHREADS, CHAIN_WPS) void chain_kernel(const ChainA
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-        for (int kt = 0; kt < nk; ++kt) {
-          const float* Ac = (kt & 1) ? As1 : As0;
-          const float* Bc = (kt & 1) ? Bs1 : Bs0;
-          float* An = (kt & 1) ? As0 : As1;
-          float* Bn = (kt & 1) ? Bs0 : Bs1;
-          const bool more = kt + 1 < nk;
-          const int kn = (kt + 1) * BK;
-          if (more) b_offsets_for(kn);
+        // ---- the K loop, hand-scheduled.  A step's barrier sits between its third and its fourth quarter: when it releases, every
+        // wave has read ALL fragments of step kt (the fourth quarter's sit in registers), so the buffer of step kt is free, and
+        // stage kt + 1 has landed.  What follows the barrier, in this order: every DMA piece of stage kt + 2 into the freed buffer
+        // (eight back-to-back wave-instructions: a whole step of MFMAs to land instead of three quarters minus the issue spread),
+        // the first-quarter fragment reads of step kt + 1, and only then the sixteen MFMAs of step kt's fourth quarter, which
+        // cover both latencies.  Two fragment register sets alternate (the compiler kept two alive before, too); the MFMA order
+        // per accumulator is q0 .. q3 of step 0, 1, ... as ever, so the sums keep their bits.
+        float fa0[T::NFB][4], fb0[T::NPB][4], fa1[T::NFB][4], fb1[T::NPB][4];
+        auto frags = [&](const float* Ac, const float* Bc, int i, float (&fa)[T::NFB][4], float (&fb)[T::NPB][4]) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float av[T::NFB][4], bv[T::NPB][4];
-#pragma unroll
-            for (int fb = 0; fb < T::NFB; ++fb) {
-              const float4 tq = *reinterpret_cast<const float4*>(&Ac[a_rd[fb] + 4 * (a_sw[fb] ^ (2 * i))]);
-              av[fb][0] = tq.x; av[fb][1] = tq.y; av[fb][2] = tq.z; av[fb][3] = tq.w;
-            }
-#pragma unroll
-            for (int pb = 0; pb < T::NPB; ++pb) {
-              const float4 tq = *reinterpret_cast<const float4*>(&Bc[b_rd[pb] + 4 * (b_sw[pb] ^ (2 * i))]);
-              bv[pb][0] = tq.x; bv[pb][1] = tq.y; bv[pb][2] = tq.z; bv[pb][3] = tq.w;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#pragma unroll
-              for (int fb = 0; fb < T::NFB; ++fb)
-#pragma unroll
-                for (int pb = 0; pb < T::NPB; ++pb)
-                  acc[fb][pb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[fb][e], bv[pb][e], acc[fb][pb], 0, 0, 0);
-              // the DMA of the next K tile goes out in the first quarter of the step (two pieces per k-pair group): it then
-              // has three quarters of the step to land before the barrier (gemm_glds.h)
-              if (i == 0 && more && 2 * e < NPW + NPWB) {
-                __builtin_amdgcn_sched_barrier(0);
-                stage(kn, An, Bn, 2 * e);
-                if (2 * e + 1 < NPW + NPWB) stage(kn, An, Bn, 2 * e + 1);
-                __builtin_amdgcn_sched_barrier(0);
-              }
-            }
+          for (int fb_ = 0; fb_ < T::NFB; ++fb_) {
+            const float4 tq = *reinterpret_cast<const float4*>(&Ac[a_rd[fb_] + 4 * (a_sw[fb_] ^ (2 * i))]);
+            fa[fb_][0] = tq.x; fa[fb_][1] = tq.y; fa[fb_][2] = tq.z; fa[fb_][3] = tq.w;
           }
+#pragma unroll
+          for (int pb = 0; pb < T::NPB; ++pb) {
+            const float4 tq = *reinterpret_cast<const float4*>(&Bc[b_rd[pb] + 4 * (b_sw[pb] ^ (2 * i))]);
+            fb[pb][0] = tq.x; fb[pb][1] = tq.y; fb[pb][2] = tq.z; fb[pb][3] = tq.w;
+          }
+        };
+        auto quarter = [&](const float (&fa)[T::NFB][4], const float (&fb)[T::NPB][4]) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int fb_ = 0; fb_ < T::NFB; ++fb_)
+#pragma unroll
+              for (int pb = 0; pb < T::NPB; ++pb)
+                acc[fb_][pb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[fb_][e], fb[pb][e], acc[fb_][pb], 0, 0, 0);
+        };
+        // tile head (buffer 0 holds stage 0 behind a barrier; buffer 1 is free: the transposer's last user passed that barrier)
+        __builtin_amdgcn_sched_barrier(0);
+        if (nk > 1) {
+          const StageCtx c = stage_begin(BK, As1, Bs1);
+          if (c.tail) stage_tail(c);
+          else {
+#pragma unroll
+            for (int j = 0; j < NPW + NPWB; ++j) piece(c, j);
+          }
+        }
+        frags(As0, Bs0, 0, fa0, fb0);
+        __builtin_amdgcn_sched_barrier(0);
+        for (int kt = 0; kt < nk; ++kt) {
+          float* Ac = (kt & 1) ? As1 : As0;
+          float* Bc = (kt & 1) ? Bs1 : Bs0;
+          const float* An = (kt & 1) ? As0 : As1;
+          const float* Bn = (kt & 1) ? Bs0 : Bs1;
+          frags(Ac, Bc, 1, fa1, fb1);
+          quarter(fa0, fb0);
+          frags(Ac, Bc, 2, fa0, fb0);
+          quarter(fa1, fb1);
+          frags(Ac, Bc, 3, fa1, fb1);
+          // the wave-uniform part of stage kt + 2 (scalar work, and the panel switch's four multiplies): under this quarter's MFMAs
+          const bool ahead = kt + 2 < nk;
+          StageCtx c{};
+          if (ahead) c = stage_begin((kt + 2) * BK, Ac, Bc);
+          const bool whole = ahead && !c.tail;      // uniform: a whole-width stage, its pieces go out right behind the barrier
+          quarter(fa0, fb0);
+          __builtin_amdgcn_sched_barrier(0);
+          // stage kt + 1 has landed (the asm DMAs are invisible to hipcc's counters) and this wave's reads of step kt are complete
+          const unsigned long long tw0 = STAMP ? __builtin_amdgcn_s_memtime() : 0;
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          const unsigned long long tw1 = STAMP ? __builtin_amdgcn_s_memtime() : 0;
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __syncthreads();
+          if constexpr (STAMP) { const unsigned long long tw2 = __builtin_amdgcn_s_memtime(); c_kw += tw1 - tw0; c_kb += tw2 - tw1; }
+          __builtin_amdgcn_sched_barrier(0);
+          if (ahead && c.tail) stage_tail(c);
+          if (whole) {
+#pragma unroll
+            for (int j = 0; j < NPW + NPWB; ++j) piece(c, j);
+          }
+          if (kt + 1 < nk) frags(An, Bn, 0, fa0, fb0);
+          __builtin_amdgcn_sched_barrier(0);
+          quarter(fa1, fb1);
         }
 
         // ---- epilogue (the per-layer kernels' own, on local row coordinates of the tile) ----
@@ -684,8 +745,9 @@ __global__ __launch_bounds__(NTHREADS, CHAIN_WPS) void chain_kernel(const ChainA
           c_pro += tt1 - tt0; c_k += tt2 - tt1; c_epi += tt3 - tt2;
           tt0 = tt3;
           if (tid == 0) {
-            unsigned long long* kc = kcnt + 10 * L.kind;
+            unsigned long long* kc = kcnt + CHAIN_KCNT * L.kind;
             kc[0] += tt2 - tt1; kc[1] += te1 - tt2; kc[2] += te2 - te1; kc[3] += te3 - te2; kc[4] += te4 - te3; kc[5] += 1;
+            if constexpr (CHAIN_KCNT >= 12) { kc[10] += c_kw; kc[11] += c_kb; }
             if (ets[0]) { kc[6] += ets[0] - tt2; kc[7] += ets[1] - ets[0]; kc[8] += ets[2] - ets[1]; kc[9] += te1 - ets[2]; }
           }
         }
@@ -704,7 +766,7 @@ __global__ __launch_bounds__(NTHREADS, CHAIN_WPS) void chain_kernel(const ChainA
     o[0] = c_dep; o[1] = c_pro; o[2] = c_k; o[3] = c_epi; o[4] = __builtin_amdgcn_s_memtime() - c_start; o[5] = c_units;
     o[6] = __builtin_amdgcn_s_getreg(0xF804);      // HW_REG_HW_ID: where this workgroup ran
     o[7] = __builtin_amdgcn_s_getreg(0xF814) & 7;  // HW_REG_XCC_ID
-    for (int i = 0; i < 40; ++i) o[8 + i] = kcnt[i];
+    for (int i = 0; i < 4 * CHAIN_KCNT; ++i) o[8 + i] = kcnt[i];
   }
 }
 

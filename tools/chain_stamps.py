@@ -33,11 +33,13 @@ print(f"  kernel cycles / unit {tot.mean()/s[:,5].mean():.0f}; clock ~ {tot.mean
 
 # per layer kind: cycles per tile in each phase (workgroup mean)
 print("  per tile, by epilogue kind:   K loop | epilogue to last store issued | store drain | barrier | boundary first stage | tiles/unit")
+KCNT = 12                                       # counters per layer kind (CHAIN_KCNT of a diagnostic library)
 for kind, name in enumerate(("input_proj", "GroupNorm 32", "GroupNorm 64", "posterior")):
-    c = s[:, 8 + 10 * kind: 18 + 10 * kind].astype(float).sum(axis=0)
+    c = s[:, 8 + KCNT * kind: 8 + KCNT * (kind + 1)].astype(float).sum(axis=0)
     if c[5] == 0:
         continue
     print(f"    {name:14s}" + "".join(f"{c[i] / c[5]:10.0f}" for i in range(5)) + f"   {c[5] / s[:, 5].sum():6.1f}")
+    print(f"        of the K loop: closing vmcnt waits {c[10] / c[5]:9.0f}   barriers {c[11] / c[5]:9.0f}   ({100 * (c[10] + c[11]) / c[0]:.1f} % of the K loop)")
     if c[6]:
         print("        GroupNorm epilogue: first-stage A issue + bias loads landed | statistics | gamma/beta landed | normalise + SiLU + stores issued:"
               + "".join(f"{c[i] / c[5]:9.0f}" for i in range(6, 10)))
@@ -53,7 +55,8 @@ sizes = collections.Counter(len(v) for v in per_cu.values())
 tot = np.array([sum(v) for v in per_cu.values()])
 print(f"  CUs used {len(per_cu)}; workgroups per CU {dict(sizes)}; units per CU min {tot.min()} mean {tot.mean():.1f} max {tot.max()}")
 split = [abs(v[0] - v[1]) for v in per_cu.values() if len(v) == 2]
-print(f"  |difference| between the two workgroups of a CU: mean {np.mean(split):.1f} max {np.max(split)}")
+if split:                                       # (one workgroup per CU, chain_grid = 256: nothing to compare)
+    print(f"  |difference| between the two workgroups of a CU: mean {np.mean(split):.1f} max {np.max(split)}")
 per_x = collections.defaultdict(int)
 for (x, _), v in per_cu.items():
     per_x[x] += sum(v)
