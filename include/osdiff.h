@@ -396,6 +396,12 @@ int osd_val_mmd(void *stream, int device, const float *X, int64_t n, const float
 /* One block of the above for row-sharded data (multi-GPU validation): sum_out = sum_{i<n, j<m} exp(-gamma |a_i - b_j|^2). */
 int osd_val_rbf_sum(void *stream, int device, const float *A, int64_t n, const float *B, int64_t m, int D,
                     double gamma, double *sum_out);
+/* For every row of Q dev [nq][D]: the nearest row of R dev [nr][D] in squared Euclidean distance, skipping row exclude[i]
+ * (dev int32 [nq] or NULL; values outside [0, nr) exclude nothing).  idx_out dev int32 [nq]: the smallest index among the
+ * minimisers of the fp32 expanded form; d2_out dev float [nq]: sum_k (Q[i][k] - R[idx][k])^2 recomputed directly.
+ * No candidate: idx -1, d2 +inf.  Inputs must be finite.  Synchronous, like the other osd_val_* calls. */
+int osd_val_nearest(void *stream, int device, const float *Q, int64_t nq, const float *R, int64_t nr, int D,
+                    const int32_t *exclude, float *d2_out, int32_t *idx_out);
 /* scipy.stats.ks_2samp as used at utils/validation.py:238-245, for features 0..nf-1 of real dev [n1][ld]
  * and synth dev [n2][ld]: exact integer extremes of cnt(real<=v)*n2 - cnt(synth<=v)*n1 over all sample
  * points v; the statistic is max(dmax, -dmin, 0) / (n1*n2) (p-values follow on the host). */

@@ -812,4 +812,68 @@ struct EpiRbfSum {
   }
 };
 
+// ---- nearest reference row of every query row (the privacy audit) ----------------------------
+// A = reference rows (the tile's feature side, f), B = query rows (the patient side, p).  acc = r_f . q_p;
+// d2 = max(|r_f|^2 + |q_p|^2 - 2 acc, 0).  Per query the minimum of the unsigned 64-bit key (float_bits(d2) << 32) | f is kept:
+// bits of non-negative floats order like the floats, so the minimum key is the minimum distance and ties go to the smallest
+// index -- whatever order the workgroups finish in.  f >= F, p >= P and f == exclude[p] never enter.  A lane holds one query and
+// 16 * NFB reference rows in increasing f: the running minimum is a 32-bit compare on the distance bits (strict, so the first --
+// smallest -- f of a tie stays); the two half-waves that share a query meet through lane^32, and one 64-bit atomicMin per query
+// and wave goes out, skipped when the key already stored is not larger (a stale read only costs the atomic it failed to skip).
+struct EpiNearest {
+  static constexpr bool COUNTED_STORES = false;   // stores nothing but the atomics
+  static constexpr bool XBUF = false;
+  static constexpr unsigned long long NO_KEY = ~0ull;   // the key array's initial value: no candidate
+  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
+  struct Args { const float* sqr; const float* sqq; const int* exclude; unsigned long long* keys; };
+  static bool fast_ok(const Args& a, int F) { return F % 4 == 0 && al16(a.sqr); }
+  template <int NFB> struct Pre { float4 sqr[NFB][4]; };
+  template <int NFB, bool FAST>
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
+    Pre<NFB> r;
+    const int h = lane >> 5;
+#pragma unroll
+    for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r.sqr[fb][q] = ldq<FAST>(a.sqr, fw + 32 * fb + 8 * q + 4 * h, F);
+    return r;
+  }
+  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
+                                               Sync&& sync = Sync()) {
+    const int l31 = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int pb = 0; pb < NPB; ++pb) {
+      const int p = pw + 32 * pb + l31;
+      const int pc = p < P ? p : P - 1;
+      const float sq = a.sqq[pc];
+      const int ex = a.exclude ? a.exclude[pc] : -1;
+      unsigned best = 0xffffffffu;                 // above the bits of every non-negative float, +inf included
+      int best_f = 0;
+#pragma unroll
+      for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int f = fw + 32 * fb + 8 * q + 4 * h;
+          const float4 sr = pre.sqr[fb][q];
+          const float srv[4] = {sr.x, sr.y, sr.z, sr.w};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float d2 = fmaxf(srv[r] + sq - 2.0f * acc[fb][pb][4 * q + r], 0.f);
+            const unsigned bits = (f + r < F && f + r != ex) ? __float_as_uint(d2) : 0xffffffffu;
+            if (bits < best) { best = bits; best_f = f + r; }
+          }
+        }
+      unsigned long long key = best == 0xffffffffu ? NO_KEY : ((unsigned long long)best << 32) | (unsigned)best_f;
+      const unsigned long long other = __shfl_xor(key, 32);
+      key = other < key ? other : key;
+      if (h == 0 && p < P && key != NO_KEY) {
+        unsigned long long* slot = a.keys + p;
+        if (key < __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(slot, key);
+      }
+      sync.tick();
+    }
+  }
+};
+
 }  // namespace osd

@@ -135,6 +135,40 @@ static hipError_t rbf_sum(hipStream_t s, const float* X, int64_t n, const float*
   return launch_gemm<TileBig, true, true, EpiRbfSum>(s, g, ea);
 }
 
+// The key array of EpiNearest after the Gram pass, one wavefront per query: the index out of the key, and the distance to
+// that row recomputed as sum_k (q_k - r_k)^2 -- differences in fp32, the sum in double.  The expanded form |r|^2 + |q|^2 - 2 r.q
+// the keys were ranked by cancels (its error is the size of a near copy's whole distance); this one returns an exact copy as 0.0f.
+__global__ void k_nearest_refine(const float* Q, int64_t nq, const float* R, int D, const unsigned long long* keys, float* d2_out,
+                                 int32_t* idx_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t i = wave; i < nq; i += nw) {
+    const unsigned long long key = keys[i];
+    if (key == EpiNearest::NO_KEY) {               // uniform over the wave
+      if (lane == 0) { idx_out[i] = -1; d2_out[i] = INFINITY; }
+      continue;
+    }
+    const int64_t j = (int64_t)(key & 0xffffffffull);
+    const float* q = Q + i * D;
+    const float* r = R + j * D;
+    double s = 0.0;
+    for (int c = lane; c < D; c += 64) { const float d = q[c] - r[c]; s += (double)d * (double)d; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) { idx_out[i] = (int32_t)j; d2_out[i] = (float)s; }
+  }
+}
+
+// keys[p] = min over the reference rows f != exclude[p] of (float_bits(d2(p, f)) << 32) | f; keys must hold all-ones on entry
+static hipError_t nearest_keys(hipStream_t s, const float* R, int64_t nr, const float* sqr, const float* Q, int64_t nq, const float* sqq, int D,
+                               const int32_t* exclude, unsigned long long* keys) {
+  GemmArgs g{};
+  g.A = R; g.lda = D; g.B0 = Q; g.ldb0 = D; g.K0 = D; g.F = (int)nr; g.P = (int)nq; g.K = D;
+  EpiNearest::Args ea{sqr, sqq, exclude, keys};
+  return launch_gemm<TileBig, true, true, EpiNearest>(s, g, ea);
+}
+
 struct DevBuf {
   void* p = nullptr;
   hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
@@ -199,6 +233,30 @@ int osd_val_rbf_sum(void* stream, int device, const float* A, int64_t n, const f
   double t = 0.0;
   for (double v : slots) t += v;
   *sum_out = t;
+  return OSD_OK;
+}
+
+int osd_val_nearest(void* stream, int device, const float* Q, int64_t nq, const float* R, int64_t nr, int D, const int32_t* exclude,
+                    float* d2_out, int32_t* idx_out) {
+  if (!Q || !R || !d2_out || !idx_out || nq <= 0 || nr <= 0 || D <= 0 || nq > INT_MAX / 2 || nr > INT_MAX / 2) { set_error("bad argument"); return OSD_EINVAL; }
+  OSD_HIP(hipSetDevice(device));
+  OSD_HIP(prepare_kernels());
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf sq, keys;                                     // O(nq + nr): nothing here scales with nq * nr
+  OSD_HIP(sq.alloc((size_t)(nq + nr) * 4));
+  OSD_HIP(keys.alloc((size_t)nq * sizeof(unsigned long long)));
+  float* sqr = (float*)sq.p;
+  float* sqq = sqr + nr;
+  OSD_HIP(hipMemsetAsync(keys.p, 0xff, (size_t)nq * sizeof(unsigned long long), s));      // EpiNearest::NO_KEY
+  hipLaunchKernelGGL(k_rowsumsq, 1024, 256, 0, s, R, nr, D, sqr);
+  if (Q == R && nq == nr) sqq = sqr;
+  else hipLaunchKernelGGL(k_rowsumsq, 1024, 256, 0, s, Q, nq, D, sqq);
+  OSD_HIP(nearest_keys(s, R, nr, sqr, Q, nq, sqq, D, exclude, (unsigned long long*)keys.p));
+  int blocks = (int)((nq + 3) / 4);                    // 4 wavefronts per workgroup, one query each
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(k_nearest_refine, blocks, 256, 0, s, Q, nq, R, D, (const unsigned long long*)keys.p, d2_out, idx_out);
+  OSD_HIP(hipGetLastError());
+  OSD_HIP(hipStreamSynchronize(s));
   return OSD_OK;
 }
 

@@ -133,6 +133,21 @@ class DeviceKernels:
                                         C.byref(out)))
         return float(out.value)
 
+    def nearest(self, q: torch.Tensor, r: torch.Tensor, exclude: Optional[torch.Tensor] = None):
+        """(d2 float32 [nq], idx int32 [nq]) device tensors: each row of q against the rows of r, row ``exclude[i]`` skipped."""
+        if q.shape[1] != r.shape[1]:
+            raise ValueError("q and r must have the same number of features")
+        nq = q.shape[0]
+        d2 = torch.empty(nq, dtype=torch.float32, device=q.device)
+        idx = torch.empty(nq, dtype=torch.int32, device=q.device)
+        if exclude is not None:
+            exclude = exclude.to(device=q.device, dtype=torch.int32).contiguous()
+            if exclude.shape != (nq,):
+                raise ValueError("exclude must hold one index per query row")
+        L.check(L.lib().osd_val_nearest(self._stream(), self.index, L.ptr(q), nq, L.ptr(r), r.shape[0], q.shape[1], L.ptr(exclude),
+                                        L.ptr(d2), L.ptr(idx)))
+        return d2, idx
+
     def ks_extremes(self, real: torch.Tensor, synth: torch.Tensor, nf: int):
         dmax, dmin = (C.c_int64 * nf)(), (C.c_int64 * nf)()
         L.check(L.lib().osd_val_ks_extremes(self._stream(), self.index, L.ptr(real), real.shape[0], L.ptr(synth), synth.shape[0],
@@ -224,6 +239,62 @@ def sharded_pearson(comm: ShardComm, k, a_local, col_a: int, b_local, col_b: int
     n = h[5]
     cov, va, vb = h[4] - h[0] * h[1] / n, h[2] - h[0] * h[0] / n, h[3] - h[1] * h[1] / n
     return float(cov / np.sqrt(va * vb))
+
+
+def sharded_nearest_records(comm: ShardComm, k, train, synth_local, holdout=None) -> Dict[str, np.ndarray]:
+    """Per-row nearest-record distances of the privacy audit: the synthetic rows are this rank's shard, the real cohorts are
+    replicated.  Every rank returns the arrays of the concatenated rows (float64 distances, int64 indices):
+    ``dcr`` / ``match`` distance to and index of the nearest train row, ``second`` distance to the second nearest (a second pass
+    that excludes the first match), ``real_nn`` each train row's distance to its nearest OTHER train row (the train rows are
+    split over the ranks as queries), ``dcr_holdout`` distance to the nearest holdout row (only with a holdout)."""
+    from .parallel import shard_rows
+
+    def nearest(q, r, exclude=None):
+        if q.shape[0] == 0:                              # an empty shard asks nothing of the kernel
+            return torch.empty(0, dtype=torch.float32, device=q.device), torch.empty(0, dtype=torch.int32, device=q.device)
+        return k.nearest(q, r, exclude)
+
+    def dist(d2):
+        return np.sqrt(comm.gather_rows(d2).detach().cpu().numpy().astype(np.float64))
+
+    d2, match = nearest(synth_local, train)
+    d2_second, _ = nearest(synth_local, train, match)
+    lo, cnt = shard_rows(train.shape[0], comm.rank, comm.world)
+    own = torch.arange(lo, lo + cnt, dtype=torch.int32, device=train.device)
+    d2_real, _ = nearest(train[lo:lo + cnt].contiguous(), train, own)
+    rows = {"dcr": dist(d2), "match": comm.gather_rows(match).detach().cpu().numpy().astype(np.int64), "second": dist(d2_second),
+            "real_nn": dist(d2_real)}
+    if holdout is not None:
+        rows["dcr_holdout"] = dist(nearest(synth_local, holdout)[0])
+    return rows
+
+
+def privacy_summary(rows: Dict[str, np.ndarray]) -> Dict[str, float]:
+    """The privacy figures from the per-row arrays of ``sharded_nearest_records`` (float64, numpy.quantile's default)."""
+    dcr = np.asarray(rows["dcr"], dtype=np.float64)
+    second = np.asarray(rows["second"], dtype=np.float64)
+    real_nn = np.asarray(rows["real_nn"], dtype=np.float64)
+    match = np.asarray(rows["match"], dtype=np.int64)
+    if dcr.size == 0:
+        raise ValueError("a privacy summary needs at least one synthetic row")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nndr = dcr / second                              # an infinite second neighbour (a one-row cohort) gives 0.0
+    nndr[np.isnan(nndr)] = 0.0                           # 0/0: a row that copies two identical records
+    out = {
+        "privacy_dcr_min": float(dcr.min()),
+        "privacy_dcr_p05": float(np.quantile(dcr, 0.05)),
+        "privacy_dcr_median": float(np.median(dcr)),
+        "privacy_exact_copy_fraction": float(np.mean(dcr == 0)),
+        "privacy_nndr_p05": float(np.quantile(nndr, 0.05)),
+        "privacy_nndr_median": float(np.median(nndr)),
+        "privacy_real_nn_median": float(np.median(real_nn)),
+        "privacy_closer_than_real_nn_fraction": float(np.mean(dcr < real_nn[match])),
+    }
+    if "dcr_holdout" in rows:
+        dh = np.asarray(rows["dcr_holdout"], dtype=np.float64)
+        out["privacy_holdout_dcr_median"] = float(np.median(dh))
+        out["privacy_closer_to_train_fraction"] = float(np.mean((dcr < dh) + 0.5 * (dcr == dh)))
+    return out
 
 
 class BiologicalValidator:
@@ -320,6 +391,27 @@ class BiologicalValidator:
         results["wasserstein_distance_mean"] = float(np.mean([stats.wasserstein_distance(real_pca[:, i], synth_pca[:, i]) for i in range(10)]))
         logger.info(f"Mean Wasserstein distance: {results['wasserstein_distance_mean']:.3f}")
         return self._agree(results)
+
+    # -- privacy: distances to the nearest real record (no counterpart in the reference) ---------
+    def privacy_audit(self, real_train, synthetic, real_holdout=None, return_rows: bool = False):
+        """Distance-to-closest-record figures of ``synthetic`` (this rank's shard when sharded) against the cohort the model was
+        trained on, and against a holdout cohort when one is given: the ``privacy_*`` keys of ``privacy_summary``.  Distances
+        are plain Euclidean over the columns as given -- callers scale their inputs.  ``return_rows=True`` also returns the
+        per-row arrays of ``sharded_nearest_records``."""
+        tr, sy = _dev(real_train, self.device), _dev(synthetic, self.device)
+        ho = None if real_holdout is None else _dev(real_holdout, self.device)
+        for name, t in (("real_train", tr), ("synthetic", sy), ("real_holdout", ho)):
+            if t is None:
+                continue
+            if t.dim() != 2 or t.shape[1] != tr.shape[1]:
+                raise ValueError(f"{name} must be [rows, {tr.shape[1]}]: the cohorts must have the same features")
+            if not bool(torch.isfinite(t).all().item()):
+                raise ValueError(f"{name} holds non-finite values")
+        if tr.shape[0] == 0 or (ho is not None and ho.shape[0] == 0):
+            raise ValueError("the real cohorts must not be empty")
+        rows = sharded_nearest_records(self.comm, self.k, tr, sy, ho)
+        summary = self._agree(privacy_summary(rows))
+        return (summary, rows) if return_rows else summary
 
     # -- utils/validation.py:27-121 ----------------------------------------------------------------
     def _column_sums(self, t: torch.Tensor) -> np.ndarray:
@@ -421,7 +513,9 @@ class BiologicalValidator:
 
     # -- utils/validation.py:300-383 ---------------------------------------------------------------
     def validate_all(self, real_mutations, real_expression, real_pathways, synth_mutations, synth_expression, synth_pathways,
-                     pathway_gene_matrix=None) -> Dict[str, float]:
+                     pathway_gene_matrix=None, privacy: bool = False, holdout=None) -> Dict[str, float]:
+        """``privacy=True`` adds ``privacy_audit``'s keys, on the same combined matrices as the statistical tests; ``holdout`` is
+        then an optional (mutations, expression, pathways) triple of real patients the model never saw."""
         logger.info("=" * 50)
         logger.info("BIOLOGICAL VALIDATION")
         logger.info("=" * 50)
@@ -438,6 +532,15 @@ class BiologicalValidator:
             real_combined = np.concatenate([_host(p) for p in parts_r], axis=1)
             synth_combined = np.concatenate([_host(p) for p in parts_s], axis=1)
         all_results.update(self.statistical_tests(real_combined, synth_combined))
+        if privacy:
+            hold_combined = None
+            if holdout is not None:
+                parts_h = [p.values for p in holdout]
+                if all(isinstance(p, torch.Tensor) for p in parts_h):
+                    hold_combined = torch.cat(parts_h, dim=1)
+                else:
+                    hold_combined = np.concatenate([_host(p) for p in parts_h], axis=1)
+            all_results.update(self.privacy_audit(real_combined, synth_combined, hold_combined))
         logger.info("=" * 50)
         logger.info("VALIDATION SUMMARY")
         logger.info("=" * 50)
