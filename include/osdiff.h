@@ -149,6 +149,7 @@ int osd_get_option(osd_handle *h, const char *name, int64_t *value);
 #define OSD_TP_WGRAD_DIRECT  (1 << 8)   /* at least one weight gradient launched on its own, outside the grouped launch */
 #define OSD_TP_WGRAD_GROUP   (1 << 9)   /* at least one grouped weight-gradient launch */
 #define OSD_TP_MSE_BF16      (1 << 10)  /* output_proj + MSE on the bf16 matrix pipe ("precision" 1) */
+#define OSD_TP_LOSS_EPI      (1 << 11)  /* output_proj ran the configurable loss epilogue (osd_set_loss); never set on the default path */
 
 /* Schedule + time-embedding tables, computed by the host with the reference's own
  * fp32 expressions so they are bit-identical (models/diffusion.py:299-326, 131-137,
@@ -314,7 +315,8 @@ int osd_train_batch_source(osd_handle *h, const float *data, int64_t ld_data, co
  *   loss_scale  multiplies the gradients (1.0 for plain backward)
  *   events/n_events  optional hipEvent_t array recorded on the handle's stream as
  *             each gradient bucket (see osd_grad_bucket) becomes final, for
- *             overlapping the RCCL all-reduce with the rest of backward */
+ *             overlapping the RCCL all-reduce with the rest of backward
+ * The loss is the MSE of the predicted noise unless osd_set_loss chose another one (L1, Huber, per-timestep weights). */
 int osd_train_loss_fwd_bwd(osd_handle *h, const float *x0, const float *cond, int64_t n,
                            const int32_t *t_index, const float *noise, const float *const *masks,
                            uint64_t seed, int64_t row_offset, int flags, float *loss_out,
@@ -456,8 +458,27 @@ typedef struct osd_constraints {
  * x0_hat = (x_t - sqrt(1-ac_t) eps_hat) / sqrt(ac_t) (models/diffusion.py:405) against x0 of the batch:
  * loss = mse + pathway_weight * L_pc + mutexpr_weight * L_me, gradients flow into eps_hat. */
 int osd_set_constraints(osd_handle *h, const osd_constraints *c);
-/* (mse, L_pc, L_me) of the last osd_train_loss_fwd_bwd call; synchronises the handle's stream. */
+/* (mse, L_pc, L_me) of the last osd_train_loss_fwd_bwd call; synchronises the handle's stream.  With osd_set_loss, parts[0] is the
+ * configured eps-loss. */
 int osd_get_loss_parts(osd_handle *h, float *parts_host3);
+
+/* ---- the eps-loss of osd_train_loss_fwd_bwd ------------------------------------------------------------------------
+ * With d = eps_hat - eps, row r at timestep t_r, n rows and D features:
+ *   loss = 1/(n D) * sum_r w[t_r] * sum_f rho(d_rf),      dL/d eps_hat_rf = loss_scale/(n D) * w[t_r] * rho'(d_rf)
+ *   OSD_LOSS_L2     rho = d^2                                                rho' = 2 d              (F.mse_loss; the default)
+ *   OSD_LOSS_L1     rho = |d|                                                rho' = sign(d), 0 at 0  (F.l1_loss)
+ *   OSD_LOSS_HUBER  rho = d^2 / 2 if |d| <= delta, else delta (|d| - delta/2)  rho' = clamp(d, -delta, delta)  (F.huber_loss)
+ * t_weights_host: T non-negative finite per-timestep weights (host memory, copied), gathered by each row's timestep index (the
+ * caller's t_index or the one drawn inside the call), or NULL: every row weighs 1.  The mean is over n D; it is NOT renormalised by
+ * the sum of the weights.  huber_delta must be positive and finite for every kind (1.0 is the conventional default).
+ * Persistent on the handle until the next osd_set_loss; synchronises the handle's stream.  OSD_LOSS_L2 with NULL weights is the state
+ * of a new handle and runs exactly the kernels of a handle that never called this; anything else runs the loss epilogue (EpiLoss,
+ * csrc/epilogues.h) in the same launch and sets OSD_TP_LOSS_EPI.  The constraint losses are added on top as before.
+ * OSD_EINVAL: unknown kind, huber_delta <= 0 or not finite, a negative or non-finite weight. */
+#define OSD_LOSS_L2    0
+#define OSD_LOSS_L1    1
+#define OSD_LOSS_HUBER 2
+int osd_set_loss(osd_handle *h, int kind, double huber_delta, const float *t_weights_host);
 /* Stand-alone ops (stream/device based, synchronous): loss_out (dev float[1]) += weight * L and, when
  * dx != NULL, dx (dev [rows][ld]) += weight * dL/dx.  x, x_recon, x_true: dev [rows][ld], cols <= ld. */
 int osd_loss_pathway_coherence(void *stream, int device, const float *x, int64_t rows, int ld, int cols,

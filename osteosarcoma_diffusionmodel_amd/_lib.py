@@ -13,6 +13,8 @@ OSD_MAX_HIDDEN = 8
 OSD_F_GRAPH, OSD_F_TRAIN_MODE, OSD_F_SYNC = 1, 2, 4
 OSD_OK, OSD_EINVAL, OSD_ENOMEM, OSD_EHIP, OSD_ESTATE, OSD_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 OSD_COMM_ID_BYTES = 128
+OSD_LOSS_L2, OSD_LOSS_L1, OSD_LOSS_HUBER = 0, 1, 2
+OSD_TP_LOSS_EPI = 1 << 11
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libosdiff.so"
 
@@ -90,6 +92,7 @@ _SIGNATURES = {
     "osd_val_pearson": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int64, C.POINTER(C.c_double)]),
     "osd_set_constraints": (C.c_int, [_P, C.POINTER(OsdConstraints)]),
     "osd_get_loss_parts": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "osd_set_loss": (C.c_int, [_P, C.c_int, C.c_double, _P]),
     "osd_loss_pathway_coherence": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                              C.c_double, _P, _P]),
     "osd_loss_mutation_expression": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,

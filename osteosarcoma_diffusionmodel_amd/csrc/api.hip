@@ -532,6 +532,7 @@ int osd_destroy(osd_handle* h) {
   free(h->known_level_host);
   if (h->normsq_dev) e = hipFree(h->normsq_dev);
   if (h->parts_dev) e = hipFree(h->parts_dev);
+  if (h->loss_tw) e = hipFree(h->loss_tw);
   if (h->t_san) e = hipFree(h->t_san);
   for (hipEvent_t ev : h->ev_pool) e = hipEventDestroy(ev);
   if (h->wgrad_stream) e = hipStreamDestroy(h->wgrad_stream);

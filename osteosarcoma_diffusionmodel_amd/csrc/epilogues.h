@@ -750,6 +750,130 @@ struct EpiMse {
   }
 };
 
+// ---- output_proj fused with a configurable eps-loss (osd_set_loss) and its gradient ----
+// d = (acc + bias) - noise;  loss += w[t_row] * sum rho(d) * inv_count;  dout = w[t_row] * rho'(d) * gscale
+//   kind 0 (l2):     rho = d^2                                         rho' = d               (the host folds the 2 into gscale, as EpiMse)
+//   kind 1 (l1):     rho = |d|                                         rho' = sign(d), 0 at 0
+//   kind 2 (huber):  rho = 1/2 d^2 if |d| <= delta else delta (|d| - 1/2 delta)   rho' = clamp(d, -delta, delta)
+// w = tw[t_index[row]] (one gathered load per row) or 1 when tw is null.  kind is uniform over the launch: a scalar branch around a
+// handful of VALU operations per element (tile loops compiled per kind behind one branch were tried: the 128 x 128 LDS-DMA kernel then
+// spills 22 VGPRs).  EpiMse's structure otherwise, path for path: the transposer on full row segments when
+// FAST, the guarded form elsewhere; padding rows and columns carry d = 0, and rho(0) = rho'(0) = 0 for every kind; one reduction
+// per workgroup and one float atomic on the transposer path.
+struct EpiLoss {
+  static constexpr bool COUNTED_STORES = false;   // dout / pred are optional
+  static constexpr bool XBUF = true;
+  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
+  struct Args {
+    EpiMse::Args m;               // bias, noise, dout, pred, loss, inv_count, gscale: EpiMse's meaning
+    const float* tw;              // dev [T] per-timestep weights, or null (every row weighs 1)
+    const int* t_index;           // dev [P] timestep index of each row, in [0, T); read only when tw is non-null
+    int kind; float delta;
+  };
+  static bool fast_ok(const Args& a, int F) { return EpiMse::fast_ok(a.m, F); }
+  template <int NFB> using Pre = EpiMse::Pre<NFB>;
+  template <int NFB, bool FAST>
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
+    return EpiMse::prefetch<NFB, FAST>(a.m, fw, lane, F);
+  }
+  // rho(d) into `part`, rho'(d) back into d; d = 0 gives 0 and 0
+  static __device__ __forceinline__ void point(int kind, float delta, float& d, float& part) {
+    const float ad = fabsf(d);
+    if (kind == 0) {
+      part += d * d;
+    } else if (kind == 1) {
+      part += ad;
+      d = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    } else {
+      const float c = fminf(ad, delta);
+      part += c * (ad - 0.5f * c);
+      d = fminf(fmaxf(d, -delta), delta);
+    }
+  }
+  // (rho' * w) * gscale per element rather than a per-row w * gscale kept next to w: the 128 x 128 LDS-DMA tile has no register to spare
+  static __device__ __forceinline__ void quad(int kind, float delta, float w, float gs, float4& d, float& part) {
+    float q = 0.f;
+    point(kind, delta, d.x, q); point(kind, delta, d.y, q); point(kind, delta, d.z, q); point(kind, delta, d.w, q);
+    part += w * q;
+    d.x = d.x * w * gs; d.y = d.y * w * gs; d.z = d.z * w * gs; d.w = d.w * w * gs;
+  }
+  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& al, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
+                                               float* xbuf = nullptr, Sync&& sync = Sync()) {
+    const EpiMse::Args& a = al.m;
+    const int l31 = lane & 31, h = lane >> 5;
+    const int kind = al.kind;
+    const float delta = al.delta;
+    float wrow[NPB];
+#pragma unroll
+    for (int pb = 0; pb < NPB; ++pb) {
+      const int p = pw + 32 * pb + l31;
+      wrow[pb] = al.tw ? al.tw[al.t_index[p < P ? p : P - 1]] : 1.0f;
+    }
+    float part = 0.f;
+    if (FAST && xbuf) {
+      const WaveXpose<NPB> xp{xbuf};
+      const int rows = P - pw;                         // valid rows of the wave's block (uniform)
+#pragma unroll
+      for (int fb = 0; fb < NFB; ++fb) {
+        const int cols = F - (fw + 32 * fb);            // valid features of this block (uniform)
+        if (rows <= 0 || cols <= 0) continue;
+        xp.template load_rows<true>(a.noise + (size_t)pw * a.ldn + fw + 32 * fb, a.ldn, lane, rows, cols);
+#pragma unroll
+        for (int pb = 0; pb < NPB; ++pb)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int fo = 8 * q + 4 * h;
+            const int p = 32 * pb + l31;
+            const bool prow = p < rows;
+            const float4 bv = pre.bias[fb][q];
+            const float4 nz = xp.get(pb, q, l31, h);
+            const float4 e = make_float4(acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w);
+            if (a.pred && prow) stq<FAST>(a.pred + (size_t)(pw + p) * a.ldp, fw + 32 * fb + fo, F, e);
+            float4 d = make_float4(e.x - nz.x, e.y - nz.y, e.z - nz.z, e.w - nz.w);
+            if (!prow || fo >= cols) d.x = 0.f;
+            if (!prow || fo + 1 >= cols) d.y = 0.f;
+            if (!prow || fo + 2 >= cols) d.z = 0.f;
+            if (!prow || fo + 3 >= cols) d.w = 0.f;
+            quad(kind, delta, wrow[pb], a.gscale, d, part);
+            xp.put(pb, q, l31, h, d);
+          }
+        if (a.dout) xp.template store_rows<true>(a.dout + (size_t)pw * a.ldd + fw + 32 * fb, a.ldd, lane, rows, cols);
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+      // one atomic per workgroup, as EpiMse
+      __shared__ float wave_part[4];               // 16 bytes: keeps the dynamic LDS base 16-byte aligned
+      const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+      if (lane == 0) wave_part[wv] = part;
+      __syncthreads();
+      if (threadIdx.x == 0) atomicAdd(a.loss, ((wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3])) * a.inv_count);
+      return;
+    }
+    OSD_FOR_QUADS(fb, pb, q) {
+      const int f = fw + 32 * fb + 8 * q + 4 * h;
+      const int p = pw + 32 * pb + l31;
+      const int pc = p < P ? p : P - 1;
+      const bool prow = p < P;
+      const float4 bv = pre.bias[fb][q];
+      const float4 nz = ldq<FAST>(a.noise + (size_t)pc * a.ldn, f, F);
+      const float4 e = make_float4(acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w);
+      if (a.pred && prow) stq<FAST>(a.pred + (size_t)p * a.ldp, f, F, e);
+      float4 d = make_float4(e.x - nz.x, e.y - nz.y, e.z - nz.z, e.w - nz.w);
+      if (!prow || f >= F) d.x = 0.f;
+      if (!prow || f + 1 >= F) d.y = 0.f;
+      if (!prow || f + 2 >= F) d.z = 0.f;
+      if (!prow || f + 3 >= F) d.w = 0.f;
+      quad(kind, delta, wrow[pb], a.gscale, d, part);
+      if (a.dout && prow) stq<FAST>(a.dout + (size_t)p * a.ldd, f, F, d);
+      sync.tick();
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+    if (lane == 0) atomicAdd(a.loss, part * a.inv_count);
+  }
+};
+
 // ---- RBF-kernel sum for the MMD metric (utils/validation.py:287-296) -------------------------------
 // acc = x_f . y_p;  d2 = |x_f|^2 + |y_p|^2 - 2 acc;  sum += exp(-gamma * max(d2, 0)) over the valid tile
 struct EpiRbfSum {

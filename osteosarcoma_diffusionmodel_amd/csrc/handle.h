@@ -153,6 +153,10 @@ struct osd_handle {
   osd::ConsPlan cons;
   double w_pathway = 0.0, w_mutexpr = 0.0;
   float* parts_dev = nullptr;
+  // the eps-loss of the training step (osd_set_loss): persistent.  loss_kind OSD_LOSS_*, loss_tw = per-timestep weights [T] on the device while
+  // a table is set (loss_tw_set), else every row weighs 1.  OSD_LOSS_L2 without a table is the default and runs EpiMse
+  int loss_kind = 0; float loss_delta = 1.0f;
+  float* loss_tw = nullptr; bool loss_tw_set = false;
   std::vector<void*> wg_plans;       // grouped weight-gradient launches (wgrad_group.hip): one cached work list per flush point
   // persistent reverse-chain kernel (chain.h / chain.hip)
   int sampler = 0;                   // osd_set_option("sampler"): 0 auto, 1 chain kernel whenever the architecture allows, 2 per-layer kernels

@@ -1,4 +1,4 @@
-// k_fused.hip -- input_proj (+t_emb +c_proj), output_proj (+posterior), output_proj (+MSE).
+// k_fused.hip -- input_proj (+t_emb +c_proj), output_proj (+posterior), output_proj (+MSE), output_proj (+configurable loss).
 #include "kernels.h"
 #include "launch.h"
 
@@ -207,6 +207,11 @@ hipError_t launch_posterior_known(hipStream_t s, const GemmArgs& g, const EpiPos
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a) {
   if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiMse>(s, g, a);
   return launch_gemm<TileSmall, true, true, EpiMse>(s, g, a);
+}
+// launch_mse's tile choice
+hipError_t launch_loss(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a) {
+  if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiLoss>(s, g, a);
+  return launch_gemm<TileSmall, true, true, EpiLoss>(s, g, a);
 }
 
 }  // namespace osd

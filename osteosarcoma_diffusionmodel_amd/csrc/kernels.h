@@ -27,6 +27,9 @@ hipError_t launch_posterior_known(hipStream_t s, const GemmArgs& g, const EpiPos
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a);
 // k_b3t.hip: precision = 1 (hipErrorInvalidValue: outside the kernel's preconditions -- run the fp32 launch)
 hipError_t launch_mse_b3t(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a);
+// output_proj + the loss of osd_set_loss (EpiLoss): launch_mse's / launch_mse_b3t's tile choices and return values
+hipError_t launch_loss(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a);
+hipError_t launch_loss_b3t(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a);
 
 // k_gn.hip / k_gn_drop.hip ------------------------------------------------------------
 // Arguments common to every GW; the wrappers copy them into EpiGnSilu<GW,DROP>::Args.

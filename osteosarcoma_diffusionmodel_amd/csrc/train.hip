@@ -592,11 +592,23 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
     ea.bias = h->params[pm.out_b]; ea.noise = eps_true; ea.ldn = D;
     ea.dout = grads ? W.d_out : nullptr; ea.ldd = D; ea.pred = cp ? W.pred : nullptr; ea.ldp = D; ea.loss = loss_out;
     ea.inv_count = (float)(1.0 / ((double)n * (double)D));
-    ea.gscale = (float)(2.0 * (double)loss_scale / ((double)n * (double)D));
-    // precision = 1: output_proj + MSE on the bf16 matrix pipe, operands split where they are staged (gemm_b3t.h)
-    hipError_t me = h->precision == 1 ? launch_mse_b3t(s, g, ea) : hipErrorInvalidValue;
-    if (me == hipSuccess) h->last_train_path |= OSD_TP_MSE_BF16;
-    if (me == hipErrorInvalidValue) { (void)hipGetLastError(); me = launch_mse(s, g, ea); }
+    hipError_t me;
+    if (h->loss_kind == OSD_LOSS_L2 && !h->loss_tw_set) {
+      ea.gscale = (float)(2.0 * (double)loss_scale / ((double)n * (double)D));
+      // precision = 1: output_proj + MSE on the bf16 matrix pipe, operands split where they are staged (gemm_b3t.h)
+      me = h->precision == 1 ? launch_mse_b3t(s, g, ea) : hipErrorInvalidValue;
+      if (me == hipSuccess) h->last_train_path |= OSD_TP_MSE_BF16;
+      if (me == hipErrorInvalidValue) { (void)hipGetLastError(); me = launch_mse(s, g, ea); }
+    } else {
+      // osd_set_loss: the same launch with EpiLoss; rho' of l2 is 2 d, of the other kinds rho' itself
+      ea.gscale = (float)((h->loss_kind == OSD_LOSS_L2 ? 2.0 : 1.0) * (double)loss_scale / ((double)n * (double)D));
+      EpiLoss::Args el{};
+      el.m = ea; el.tw = h->loss_tw_set ? h->loss_tw : nullptr; el.t_index = t_idx; el.kind = h->loss_kind; el.delta = h->loss_delta;
+      h->last_train_path |= OSD_TP_LOSS_EPI;
+      me = h->precision == 1 ? launch_loss_b3t(s, g, el) : hipErrorInvalidValue;
+      if (me == hipSuccess) h->last_train_path |= OSD_TP_MSE_BF16;
+      if (me == hipErrorInvalidValue) { (void)hipGetLastError(); me = launch_loss(s, g, el); }
+    }
     OSD_HIP(me);
   }
   if (cp) {
@@ -719,6 +731,29 @@ int osd_set_constraints(osd_handle* h, const osd_constraints* c) {
   h->cons = fresh;
   h->w_pathway = c ? c->pathway_weight : 0.0;
   h->w_mutexpr = c ? c->mutexpr_weight : 0.0;
+  return OSD_OK;
+}
+
+int osd_set_loss(osd_handle* h, int kind, double huber_delta, const float* t_weights_host) {
+  if (!h) { set_error("null handle"); return OSD_EINVAL; }
+  if (kind != OSD_LOSS_L2 && kind != OSD_LOSS_L1 && kind != OSD_LOSS_HUBER) { set_error("unknown loss kind %d (OSD_LOSS_L2, OSD_LOSS_L1 or OSD_LOSS_HUBER)", kind); return OSD_EINVAL; }
+  if (!(huber_delta > 0.0) || !std::isfinite(huber_delta) || !((float)huber_delta > 0.f) || !std::isfinite((float)huber_delta)) {
+    set_error("huber_delta must be positive and finite, got %g", huber_delta);
+    return OSD_EINVAL;
+  }
+  const int T = h->arch.T;
+  if (t_weights_host)
+    for (int i = 0; i < T; ++i)
+      if (!std::isfinite(t_weights_host[i]) || t_weights_host[i] < 0.f) { set_error("loss weight [%d] = %g is negative or not finite", i, (double)t_weights_host[i]); return OSD_EINVAL; }
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  if (h->stream) OSD_HIP(hipStreamSynchronize(h->stream));       // a training call in flight may still read the table
+  if (t_weights_host) {
+    if (!h->loss_tw) OSD_HIP(hipMalloc((void**)&h->loss_tw, (size_t)T * sizeof(float)));
+    OSD_HIP(hipMemcpy(h->loss_tw, t_weights_host, (size_t)T * sizeof(float), hipMemcpyHostToDevice));
+  }
+  h->loss_tw_set = t_weights_host != nullptr;
+  h->loss_kind = kind;
+  h->loss_delta = (float)huber_delta;
   return OSD_OK;
 }
 

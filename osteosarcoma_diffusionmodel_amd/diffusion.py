@@ -145,6 +145,7 @@ class _Engine:
         L.check(lib.osd_set_schedule(self.handle, L.ptr(sa), L.ptr(s1), L.ptr(coef.contiguous()), L.ptr(temb)))
         self._sig = None
         self.constraints_version = 0
+        self.loss_state = None          # the model's _loss_state() this handle was last configured with (None: the library's default)
         self.serial = 0                 # bumped by every call that rewrites the handle's training workspace
 
     def set_constraints(self, spec):
@@ -163,6 +164,15 @@ class _Engine:
         c.cols_a, c.cols_b, c.n_a, c.n_b = ca.ctypes.data_as(i32p), cb.ctypes.data_as(i32p), len(ca), len(cb)
         c.mutexpr_weight = spec["w_me"]
         L.check(lib.osd_set_constraints(self.handle, C.byref(c)))
+
+    def set_loss(self, model: "BiologyAwareDiffusionModel"):
+        """Validate the model's objective attributes and hand them to the handle (osd_set_loss: persistent)."""
+        from . import objective as OB
+        kind = OB.LOSS_KINDS[OB.check_loss_type(model.loss_type)]
+        delta = OB.check_huber_delta(model.huber_delta)
+        table = OB.loss_table(OB.check_loss_weighting(model.loss_weighting), OB.check_gamma(model.min_snr_gamma), model.alphas_cumprod,
+                              model._loss_weights)
+        L.check(L.lib().osd_set_loss(self.handle, kind, delta, None if table is None else table.ctypes.data))
 
     def close(self):
         if self.handle:
@@ -314,6 +324,31 @@ class BiologyAwareDiffusionModel(nn.Module):
         # optional constraint losses (set_constraints); None = the reference's eps-MSE only
         self._constraints = None
         self._constraints_version = 0
+        # the eps-loss of the training step (objective.py): config['model']['diffusion'] keys loss_type ("l2" -- the reference's MSE and
+        # the default --, "l1", "huber"), huber_delta, loss_weighting (None | "min_snr") and min_snr_gamma.  Plain attributes: assigning
+        # one takes effect at the next training call (an unknown value raises ValueError there); checkpoints carry them in the config
+        from . import objective as OB
+        dm = m["diffusion"]
+        self.loss_type: str = OB.check_loss_type(dm.get("loss_type", "l2"))
+        self.huber_delta: float = OB.check_huber_delta(dm.get("huber_delta", 1.0))
+        self.loss_weighting: Optional[str] = OB.check_loss_weighting(dm.get("loss_weighting"))
+        self.min_snr_gamma: float = OB.check_gamma(dm.get("min_snr_gamma", 5.0))
+        self._loss_weights = None         # set_loss_weights: a custom per-timestep table (host float32 [T]); wins over loss_weighting
+        self._loss_version = 0
+
+    # -- training objective (objective.py) ----------------------------------------
+    def set_loss_weights(self, weights=None):
+        """Install a custom per-timestep loss-weight table: ``num_steps`` non-negative finite values, gathered by each row's timestep
+        (loss = 1/(n D) * sum_r w[t_r] * sum_f rho(d_rf): a mean over n D, not renormalised by the weights).  It takes precedence over
+        ``loss_weighting``; ``None`` removes it.  The table is NOT persisted: neither ``state_dict()`` nor the config of a checkpoint
+        carries it, so install it again after ``load_trained_model`` (``loss_weighting: min_snr`` is a config key and is restored)."""
+        from . import objective as OB
+        self._loss_weights = None if weights is None else OB.check_weight_table(weights, self.num_steps)
+        self._loss_version += 1
+
+    def _loss_state(self):
+        """What the engine's loss setting follows: the objective attributes and the custom table's version counter."""
+        return (self.loss_type, self.huber_delta, self.loss_weighting, self.min_snr_gamma, self._loss_version)
 
     # -- constraint losses (north_star; stubs at models/cvae.py:262-302) -----------------------------
     def set_constraints(self, pathways=None, mutation_columns=None, target_columns=None, *, pathway_weight: Optional[float] = None,
@@ -339,7 +374,8 @@ class BiologyAwareDiffusionModel(nn.Module):
         self._constraints_version += 1
 
     def last_loss_parts(self):
-        """(mse, L_pc, L_me) of the most recent training ``forward`` with constraints configured."""
+        """(eps-loss, L_pc, L_me) of the most recent training ``forward`` with constraints configured; the eps-loss is the configured
+        one (``loss_type`` / ``loss_weighting``: the MSE by default)."""
         eng = self._engine()
         out = (C.c_float * 3)()
         L.check(L.lib().osd_get_loss_parts(eng.handle, out))
@@ -396,6 +432,10 @@ class BiologyAwareDiffusionModel(nn.Module):
         if eng.constraints_version != self._constraints_version:
             eng.set_constraints(self._constraints)
             eng.constraints_version = self._constraints_version
+        state = self._loss_state()
+        if eng.loss_state != state:
+            eng.set_loss(self)          # raises ValueError on an unknown value; the handle then keeps its previous setting
+            eng.loss_state = state
         for attr, option, encode in ENGINE_OPTIONS:
             value = encode(getattr(self, attr))
             if value is not None:

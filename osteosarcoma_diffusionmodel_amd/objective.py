@@ -1,0 +1,98 @@
+"""The training objective's options: which eps-loss the fused training step computes and how its rows are weighted.
+
+Pure host code (like ``ddim.py``): the argument checks and the per-timestep weight tables.  The arithmetic itself runs in the
+output_proj epilogue of ``osd_train_loss_fwd_bwd`` (csrc/epilogues.h: ``EpiLoss``, configured through ``osd_set_loss``).
+
+With d = eps_hat - eps, row r at timestep t_r, n rows and D features::
+
+    loss = 1/(n D) * sum_r w[t_r] * sum_f rho(d_rf)
+
+    l2      rho = d^2                                                    F.mse_loss (the reference's loss and the default)
+    l1      rho = |d|                                                    F.l1_loss
+    huber   rho = d^2 / 2 if |d| <= delta else delta (|d| - delta / 2)     F.huber_loss(delta=delta)
+
+``w`` is an optional table of T non-negative weights; without one every row weighs 1.  The mean is over n D and is NOT renormalised
+by the sum of the weights: a table scales the loss (and the gradients) with it, as the usual min-SNR formulation does.
+
+The reference declares ``model.diffusion.loss_type`` in its config.yaml and never reads it; here the key is honoured.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+LOSS_KINDS = {"l2": 0, "l1": 1, "huber": 2}         # include/osdiff.h: OSD_LOSS_*
+LOSS_WEIGHTINGS = (None, "min_snr")
+
+
+def check_loss_type(loss_type) -> str:
+    if not isinstance(loss_type, str) or loss_type not in LOSS_KINDS:
+        raise ValueError(f"loss_type must be 'l2', 'l1' or 'huber', got {loss_type!r}")
+    return loss_type
+
+
+def check_huber_delta(delta) -> float:
+    try:
+        d = float(delta)
+    except (TypeError, ValueError):
+        raise ValueError(f"huber_delta must be a positive finite number, got {delta!r}") from None
+    if not (d > 0.0 and math.isfinite(d)):
+        raise ValueError(f"huber_delta must be a positive finite number, got {delta!r}")
+    return d
+
+
+def check_loss_weighting(weighting) -> Optional[str]:
+    if weighting in ("none", "None", ""):
+        weighting = None
+    if weighting not in LOSS_WEIGHTINGS:
+        raise ValueError(f"loss_weighting must be None or 'min_snr', got {weighting!r}")
+    return weighting
+
+
+def check_gamma(gamma) -> float:
+    try:
+        g = float(gamma)
+    except (TypeError, ValueError):
+        raise ValueError(f"min_snr_gamma must be a positive finite number, got {gamma!r}") from None
+    if not (g > 0.0 and math.isfinite(g)):
+        raise ValueError(f"min_snr_gamma must be a positive finite number, got {gamma!r}")
+    return g
+
+
+def check_weight_table(weights, num_steps: int) -> np.ndarray:
+    """A custom per-timestep table as a contiguous host float32 array of ``num_steps`` non-negative finite entries."""
+    w = weights.detach().cpu().numpy() if isinstance(weights, torch.Tensor) else np.asarray(weights)
+    if w.ndim != 1 or w.shape[0] != num_steps:
+        raise ValueError(f"loss weights must have shape [{num_steps}] (one per timestep), got {tuple(w.shape)}")
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if not np.isfinite(w).all():
+        raise ValueError("loss weights must be finite")
+    if (w < 0).any():
+        raise ValueError("loss weights must be non-negative")
+    return w
+
+
+def min_snr_weights(alphas_cumprod, gamma: float = 5.0) -> torch.Tensor:
+    """min-SNR-gamma weights for eps-prediction (Hang et al. 2023): fp32 [T], w_t = min(SNR_t, gamma) / SNR_t with
+    SNR_t = abar_t / (1 - abar_t).  Formed in float64 from the (fp32) ``alphas_cumprod`` buffer and rounded once.
+    w_t = 1 wherever SNR_t <= gamma (the noisy end of the chain), gamma / SNR_t towards t = 0."""
+    g = check_gamma(gamma)
+    ab = alphas_cumprod.detach().cpu() if isinstance(alphas_cumprod, torch.Tensor) else torch.as_tensor(np.asarray(alphas_cumprod))
+    ab = ab.to(torch.float64).reshape(-1)
+    if ab.numel() == 0 or not bool(((ab > 0) & (ab < 1)).all()):
+        raise ValueError("alphas_cumprod must lie strictly inside (0, 1)")
+    snr = ab / (1.0 - ab)
+    w = torch.clamp(snr, max=g) / snr
+    return w.to(torch.float32)
+
+
+def loss_table(weighting: Optional[str], gamma: float, alphas_cumprod, custom: Optional[np.ndarray]) -> Optional[np.ndarray]:
+    """The table handed to ``osd_set_loss``: a custom one wins, then the configured weighting, else None (every row weighs 1)."""
+    if custom is not None:
+        return custom
+    if weighting == "min_snr":
+        return np.ascontiguousarray(min_snr_weights(alphas_cumprod, gamma).numpy())
+    return None

@@ -647,8 +647,8 @@ class Trainer:
         if not self.flat.is_current(quick=True):
             raise RuntimeError("model parameters were re-allocated after Trainer construction (e.g. model.to()); rebuild the Trainer")
         if self._engine is not None and (self._engine.constraints_version != self.model._constraints_version or
-                                         self._opts != self._option_state()):
-            # set_constraints() or a tunable (train_streams, ...) changed after construction: let the model's own
+                                         self._engine.loss_state != self.model._loss_state() or self._opts != self._option_state()):
+            # set_constraints(), the objective (loss_type, ...) or a tunable (train_streams, ...) changed after construction: let the model's own
             # engine lookup re-apply them once (it also re-derives the tables), then keep using the fast path
             self._engine = self.model._engine()
             self._opts = self._option_state()
