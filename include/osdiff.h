@@ -382,6 +382,20 @@ int osd_nn_clip_adamw_step(void *stream, int device, double *normsq_ws, float *p
                            double beta2, double eps, double weight_decay, double max_norm, int64_t step,
                            float *grad_norm_out);
 
+/* Both steps with an exponential moving average of the parameters kept in the same pass: after the AdamW update of an element,
+ *   ema = ema + w * (param_new - ema),   w = (float)(1.0 - ema_decay)        (ema.lerp_(param, 1 - ema_decay), three fp32 roundings)
+ * ema is a device float[numel] holding the running average (the caller initialises it, usually as a copy of param).  The library
+ * knows nothing about warm-up: the caller passes each step's decay.  ema_decay 0 leaves ema == param, 1 leaves ema untouched.
+ * OSD_EINVAL for a NULL ema and for ema_decay outside [0, 1] (checked before any device call).  param, grad, the moments and
+ * grad_norm_out receive exactly what the plain step writes. */
+int osd_clip_adamw_ema_step(osd_handle *h, float *param, float *grad, float *exp_avg, float *exp_avg_sq, float *ema,
+                            int64_t numel, double lr, double beta1, double beta2, double eps, double weight_decay,
+                            double max_norm, int64_t step, double ema_decay, float *grad_norm_out);
+int osd_nn_clip_adamw_ema_step(void *stream, int device, double *normsq_ws, float *param, float *grad,
+                               float *exp_avg, float *exp_avg_sq, float *ema, int64_t numel, double lr,
+                               double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                               int64_t step, double ema_decay, float *grad_norm_out);
+
 /* Measurement aid for bench.py: per-launch HIP-event timing of one reverse step on n rows
  * (eager launches on the handle's stream, averaged over reps after one warm-up pass).
  * Entry 0 = input_proj, 1..2*n_blocks = the Linear+GroupNorm+SiLU halves in execution order,

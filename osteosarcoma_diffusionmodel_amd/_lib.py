@@ -77,6 +77,8 @@ _SIGNATURES = {
     "osd_mixup": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, C.c_int64, _P, _P, _P]),
     "osd_clip_adamw_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
                                       C.c_double, C.c_double, C.c_int64, _P]),
+    "osd_clip_adamw_ema_step": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          C.c_double, C.c_double, C.c_int64, C.c_double, _P]),
     "osd_val_mmd": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "osd_val_ks_extremes": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "osd_val_mean_offdiag_corr": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double)]),
@@ -107,6 +109,8 @@ _SIGNATURES = {
     "osd_nn_reparameterize_bwd": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P]),
     "osd_nn_clip_adamw_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_double, C.c_double, C.c_int64, _P]),
+    "osd_nn_clip_adamw_ema_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                             C.c_double, C.c_double, C.c_int64, C.c_double, _P]),
     "osd_nn_vae_loss": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "osd_nn_mixup": (C.c_int, [_P, C.c_int, _P, _P, C.c_double, C.c_int64, C.c_int, _P]),
     "osd_nn_mixup3": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_double, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),

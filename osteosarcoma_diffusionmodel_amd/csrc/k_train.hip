@@ -579,9 +579,16 @@ __device__ __forceinline__ void adamw_one(float& pi, float& gi, float& mi, float
   pi = __fadd_rn(pi, __fmul_rn(a.neg_step_size, __fdiv_rn(mi, denom)));   // addcdiv_(m, denom, -lr/bc1)
 }
 // HBM-bound: 7 streams of n floats (read p, g, m, v; write p, m, v; g is written back only when clipping is on).  16-byte
-// accesses when the four arrays are 16-byte aligned (flat parameter buffers are), scalar tail / fallback otherwise.
-__global__ __launch_bounds__(256) void k_adamw(float* p, float* g, float* m, float* v, int64_t n, AdamArgs a, const double* parts, int nparts,
-                                               float* norm_out) {
+// accesses when the arrays are 16-byte aligned (flat parameter buffers are), scalar tail / fallback otherwise.
+// EMA: the running average of the parameters rides along, e.lerp_(p_new, ema_w) on the value adamw_one has just produced while
+// it is still in a register: two more streams (read e, write e) instead of a second launch that reads p again.  The <false>
+// instantiation never touches `e` / `ema_w`: it is the kernel without the average.
+__device__ __forceinline__ void ema_one(float& ei, float pi, float ema_w) {
+  ei = __fadd_rn(ei, __fmul_rn(ema_w, __fsub_rn(pi, ei)));              // e.lerp_(p, 1 - decay): three roundings, no FMA
+}
+template <bool EMA>
+__global__ __launch_bounds__(256) void k_adamw(float* p, float* g, float* m, float* v, float* e, float ema_w, int64_t n, AdamArgs a,
+                                               const double* parts, int nparts, float* norm_out) {
   __shared__ double sh[4];
   {
     double s = (int)threadIdx.x < nparts ? parts[threadIdx.x] : 0.0;
@@ -597,34 +604,53 @@ __global__ __launch_bounds__(256) void k_adamw(float* p, float* g, float* m, flo
     if (coef > 1.0f) coef = 1.0f;
   }
   if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = norm;
-  const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+  uintptr_t bits = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v);
+  if (EMA) bits |= reinterpret_cast<uintptr_t>(e);
+  const bool al = (bits & 15) == 0;
   const int64_t n4 = al ? n >> 2 : 0;
   float4* p4 = reinterpret_cast<float4*>(p); float4* g4 = reinterpret_cast<float4*>(g);
   float4* m4 = reinterpret_cast<float4*>(m); float4* v4 = reinterpret_cast<float4*>(v);
+  float4* e4 = reinterpret_cast<float4*>(e);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     float4 pi = p4[i], gi = g4[i], mi = m4[i], vi = v4[i];
+    float4 ei;
+    if (EMA) ei = e4[i];
     adamw_one(pi.x, gi.x, mi.x, vi.x, a, coef);
     adamw_one(pi.y, gi.y, mi.y, vi.y, a, coef);
     adamw_one(pi.z, gi.z, mi.z, vi.z, a, coef);
     adamw_one(pi.w, gi.w, mi.w, vi.w, a, coef);
     if (a.max_norm > 0.f) g4[i] = gi;
     p4[i] = pi; m4[i] = mi; v4[i] = vi;
+    if (EMA) {
+      ema_one(ei.x, pi.x, ema_w); ema_one(ei.y, pi.y, ema_w); ema_one(ei.z, pi.z, ema_w); ema_one(ei.w, pi.w, ema_w);
+      e4[i] = ei;
+    }
   }
   for (int64_t i = 4 * n4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float pi = p[i], gi = g[i], mi = m[i], vi = v[i];
     adamw_one(pi, gi, mi, vi, a, coef);
     if (a.max_norm > 0.f) g[i] = gi;
     p[i] = pi; m[i] = mi; v[i] = vi;
+    if (EMA) {
+      float ei = e[i];
+      ema_one(ei, pi, ema_w);
+      e[i] = ei;
+    }
   }
 }
 
-// norm_ws: device scratch of NORM_PARTS (256) doubles, no initial state required
-hipError_t launch_clip_adamw(hipStream_t s, float* p, float* g, float* m, float* v, int64_t n, const AdamArgs& a, double* norm_ws, float* norm_out) {
+// norm_ws: device scratch of NORM_PARTS (256) doubles, no initial state required.  ema == nullptr: k_sumsq + k_adamw<false>;
+// otherwise k_sumsq + k_adamw<true>, ema <- ema + ema_w * (p_new - ema).
+hipError_t launch_clip_adamw(hipStream_t s, float* p, float* g, float* m, float* v, int64_t n, const AdamArgs& a, double* norm_ws, float* norm_out,
+                             float* ema, float ema_w) {
   if (n <= 0) return hipSuccess;
   int grid = ew_grid(n, 256 * 8);
   if (grid > NORM_PARTS) grid = NORM_PARTS;
   hipLaunchKernelGGL(k_sumsq, grid, 256, 0, s, g, n, norm_ws);
-  hipLaunchKernelGGL(k_adamw, ew_grid(n, 256 * 4), 256, 0, s, p, g, m, v, n, a, norm_ws, grid, norm_out);      // one float4 per thread
+  if (ema)      // one float4 per thread
+    hipLaunchKernelGGL(k_adamw<true>, ew_grid(n, 256 * 4), 256, 0, s, p, g, m, v, ema, ema_w, n, a, norm_ws, grid, norm_out);
+  else
+    hipLaunchKernelGGL(k_adamw<false>, ew_grid(n, 256 * 4), 256, 0, s, p, g, m, v, (float*)nullptr, 0.f, n, a, norm_ws, grid, norm_out);
   return hipGetLastError();
 }
 

@@ -67,6 +67,8 @@ struct AdamArgs {
   float bc2_sqrt, eps, neg_step_size;
   float max_norm;
 };
-hipError_t launch_clip_adamw(hipStream_t s, float* p, float* g, float* m, float* v, int64_t n, const AdamArgs& a, double* norm_ws, float* norm_out);
+// ema (optional, dev float[n]): running average of the parameters, updated in the same pass: ema += ema_w * (p_new - ema)
+hipError_t launch_clip_adamw(hipStream_t s, float* p, float* g, float* m, float* v, int64_t n, const AdamArgs& a, double* norm_ws, float* norm_out,
+                             float* ema = nullptr, float ema_w = 0.f);
 
 }  // namespace osd

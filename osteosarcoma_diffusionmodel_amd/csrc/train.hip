@@ -767,7 +767,8 @@ int osd_get_loss_parts(osd_handle* h, float* parts_host3) {
 }
 
 static int clip_adamw(hipStream_t stream, double* norm_ws, float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
-                      double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, int64_t step, float* grad_norm_out) {
+                      double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, int64_t step, float* grad_norm_out,
+                      float* ema = nullptr, double ema_decay = 0.0) {
   AdamArgs a{};
   const double bc1 = 1.0 - pow(beta1, (double)step);
   const double bc2 = 1.0 - pow(beta2, (double)step);
@@ -779,7 +780,7 @@ static int clip_adamw(hipStream_t stream, double* norm_ws, float* param, float* 
   a.eps = (float)eps;
   a.neg_step_size = (float)(-(lr / bc1));
   a.max_norm = (float)max_norm;
-  OSD_HIP(launch_clip_adamw(stream, param, grad, exp_avg, exp_avg_sq, numel, a, norm_ws, grad_norm_out));
+  OSD_HIP(launch_clip_adamw(stream, param, grad, exp_avg, exp_avg_sq, numel, a, norm_ws, grad_norm_out, ema, (float)(1.0 - ema_decay)));
   return OSD_OK;
 }
 
@@ -804,6 +805,37 @@ int osd_nn_clip_adamw_step(void* stream, int device, double* normsq_ws, float* p
   OSD_HIP(hipSetDevice(device));
   return clip_adamw((hipStream_t)stream, normsq_ws, param, grad, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, max_norm, step,
                     grad_norm_out);
+}
+
+// the ema argument checks shared by both entry points: before any HIP call
+static bool ema_args_ok(const float* ema, double ema_decay) {
+  if (!ema) { set_error("null argument"); return false; }
+  if (!(ema_decay >= 0.0 && ema_decay <= 1.0)) { set_error("ema_decay must be in [0, 1]"); return false; }
+  return true;
+}
+
+int osd_clip_adamw_ema_step(osd_handle* h, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel, double lr,
+                            double beta1, double beta2, double eps, double weight_decay, double max_norm, int64_t step, double ema_decay,
+                            float* grad_norm_out) {
+  if (!h || !param || !grad || !exp_avg || !exp_avg_sq) { set_error("null argument"); return OSD_EINVAL; }
+  if (!ema_args_ok(ema, ema_decay)) return OSD_EINVAL;
+  if (numel <= 0 || step < 1) { set_error("numel and step must be positive"); return OSD_EINVAL; }
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  if (!h->normsq_dev) OSD_HIP(hipMalloc((void**)&h->normsq_dev, 256 * sizeof(double)));
+  h->w_packed_stale = true;      // as osd_clip_adamw_step
+  return clip_adamw(h->stream, h->normsq_dev, param, grad, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, max_norm, step,
+                    grad_norm_out, ema, ema_decay);
+}
+
+int osd_nn_clip_adamw_ema_step(void* stream, int device, double* normsq_ws, float* param, float* grad, float* exp_avg, float* exp_avg_sq,
+                               float* ema, int64_t numel, double lr, double beta1, double beta2, double eps, double weight_decay,
+                               double max_norm, int64_t step, double ema_decay, float* grad_norm_out) {
+  if (!normsq_ws || !param || !grad || !exp_avg || !exp_avg_sq) { set_error("null argument"); return OSD_EINVAL; }
+  if (!ema_args_ok(ema, ema_decay)) return OSD_EINVAL;
+  if (numel <= 0 || step < 1) { set_error("numel and step must be positive"); return OSD_EINVAL; }
+  OSD_HIP(hipSetDevice(device));
+  return clip_adamw((hipStream_t)stream, normsq_ws, param, grad, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, max_norm, step,
+                    grad_norm_out, ema, ema_decay);
 }
 
 }  // extern "C"

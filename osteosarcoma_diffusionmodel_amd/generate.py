@@ -244,13 +244,25 @@ class SyntheticPatientGenerator:
         logger.info(f"Saved conditions to {cond_path}")
 
 
-def load_trained_model(checkpoint_path: Path, config: dict, device: str):
+def load_trained_model(checkpoint_path: Path, config: dict, device: str, use_ema: Optional[bool] = None):
     """Checkpoint -> model (utils/generate.py:238-298): condition width from the saved
-    ``condition_embed.mlp.0.weight``, feature dims from the processed CSV headers."""
+    ``condition_embed.mlp.0.weight``, feature dims from the processed CSV headers.
+    ``use_ema``: which weights of a checkpoint written with ``training.ema_decay`` -- None (default) the averaged ones
+    (``ema_state_dict``) when the file has them, else ``model_state_dict``; False always ``model_state_dict`` (the last iterate);
+    True the averaged ones, KeyError when the file has none."""
     from .diffusion import BiologyAwareDiffusionModel
     logger.info(f"Loading model from {checkpoint_path}")
     checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
-    state_dict = checkpoint["model_state_dict"]
+    has_ema = "ema_state_dict" in checkpoint
+    if use_ema and not has_ema:
+        raise KeyError(f"use_ema=True but {checkpoint_path} has no ema_state_dict (train with training.ema_decay)")
+    if has_ema and (use_ema is None or use_ema):
+        from .train import ParamEMA
+        state_dict = ParamEMA.model_state(checkpoint["ema_state_dict"])
+        logger.info(f"Loaded the EMA weights (ema_state_dict, {int(checkpoint['ema_state_dict'].get('num_updates', 0))} updates)")
+    else:
+        state_dict = checkpoint["model_state_dict"]
+        logger.info("Loaded the last iterate (model_state_dict)" + ("; the checkpoint also has EMA weights" if has_ema else ""))
     arch = config["model"]["architecture"]
     if arch not in ("diffusion", "cvae"):
         raise ValueError(f"Unknown architecture: {arch}")
@@ -281,10 +293,10 @@ def load_trained_model(checkpoint_path: Path, config: dict, device: str):
 
 
 def generate_patients(model_or_checkpoint, config: dict, num_samples: int, scenario: Optional[Dict] = None,
-                      device: Optional[str] = None, **kw) -> Dict[str, np.ndarray]:
-    """north_star name: load (if given a path) and run SyntheticPatientGenerator.generate."""
+                      device: Optional[str] = None, use_ema: Optional[bool] = None, **kw) -> Dict[str, np.ndarray]:
+    """north_star name: load (if given a path; ``use_ema`` as in ``load_trained_model``) and run SyntheticPatientGenerator.generate."""
     device = device or "cuda"
     model = model_or_checkpoint
     if isinstance(model_or_checkpoint, (str, Path)):
-        model = load_trained_model(Path(model_or_checkpoint), config, device)
+        model = load_trained_model(Path(model_or_checkpoint), config, device, use_ema=use_ema)
     return SyntheticPatientGenerator(model, config, device).generate(num_samples, scenario, **kw)

@@ -15,6 +15,7 @@ libosdiff.so:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import logging
 import time
@@ -203,16 +204,74 @@ def diffusion_loss(model: BiologyAwareDiffusionModel, x_0, conditions, *, t=None
     return _DiffusionLoss.apply(model, x_0, conditions, t, noise, dropout_masks, seed, *params)
 
 
+class ParamEMA:
+    """Exponential moving average of a model's parameters: the weights diffusion samplers are normally pointed at (DDPM, improved
+    DDPM, EDM).  ``shadow`` is ONE flat fp32 buffer with ``FlatParams``' layout, a copy of the parameters at construction; the
+    fused clip + AdamW kernel updates it in the pass that produces the new parameters (``FusedAdamW(..., ema=...)``,
+    ``osd_nn_clip_adamw_ema_step``): ``shadow += (1 - decay_k) * (p_new - shadow)``.  Buffers (schedule tables, BatchNorm running
+    statistics) are not averaged: ``state_dict()`` takes them from the live model."""
+
+    META_KEYS = ("decay", "warmup", "num_updates")
+
+    def __init__(self, model: nn.Module, flat: FlatParams, decay: float, warmup: bool = True):
+        decay = float(decay)
+        if not 0.0 < decay < 1.0:
+            raise ValueError(f"ema decay={decay} outside (0, 1)")
+        self.model, self.flat = model, flat
+        self.decay, self.warmup = decay, bool(warmup)
+        self.num_updates = 0
+        self.shadow = flat.flat.detach().clone()
+
+    def decay_at(self, k: int) -> float:
+        """Decay of the k-th update (1-based): with warm-up min(decay, (1 + k) / (10 + k)), so that the average forgets the random
+        initialisation quickly (2/11 at the first update, ``decay`` from k = (10 decay - 1) / (1 - decay) on)."""
+        k = int(k)
+        return min(self.decay, (1.0 + k) / (10.0 + k)) if self.warmup else self.decay
+
+    def views(self) -> Dict[str, torch.Tensor]:
+        """name -> view of the shadow, shaped as the parameter."""
+        names = [k for k, _ in self.model.named_parameters()]
+        return {k: self.shadow[o:o + n].view_as(p) for k, p, o, n in zip(names, self.flat.params, self.flat.offsets[:-1], self.flat.numels)}
+
+    def state_dict(self) -> dict:
+        """The model's ``state_dict`` keys -- parameters from the shadow (copies), buffers from the live model -- plus ``decay``,
+        ``warmup`` and ``num_updates``; tensors and plain numbers only (``torch.load(weights_only=True)``)."""
+        avg = self.views()
+        out = {k: (avg[k].detach().clone() if k in avg else v.detach().clone()) for k, v in self.model.state_dict().items()}
+        out.update(decay=self.decay, warmup=self.warmup, num_updates=int(self.num_updates))
+        return out
+
+    @classmethod
+    def model_state(cls, state_dict: dict) -> dict:
+        """``state_dict()`` without the three bookkeeping keys: what ``nn.Module.load_state_dict`` takes."""
+        return {k: v for k, v in state_dict.items() if k not in cls.META_KEYS}
+
+    def load_state_dict(self, state_dict: dict):
+        """Restore the shadow and the update counter (``decay`` / ``warmup`` stay this object's: they are configuration)."""
+        avg = self.views()
+        missing = [k for k in avg if k not in state_dict]
+        if missing:
+            raise KeyError(f"ema state dict lacks {missing[:3]}{'...' if len(missing) > 3 else ''}")
+        with torch.no_grad():
+            for k, view in avg.items():
+                view.copy_(state_dict[k])
+        self.num_updates = int(state_dict.get("num_updates", 0))
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """AdamW whose ``step`` is ONE pass of the fused clip_grad_norm_ + AdamW kernel over the flat
     parameter / gradient buffers (utils/train.py:169-173, 242-244).  ``state_dict()`` has the
     layout of ``torch.optim.AdamW`` (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``), so
-    checkpoints interchange with the reference's."""
+    checkpoints interchange with the reference's.  With ``ema`` (a ``ParamEMA`` over the same ``flat``) the same pass also
+    updates the running average, with the decay of this step (``ema.decay_at``)."""
 
     def __init__(self, model: nn.Module, flat: FlatParams, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=1e-2, max_norm: float = 0.0, overwrites_grads: bool = True):
+                 weight_decay=1e-2, max_norm: float = 0.0, overwrites_grads: bool = True, ema: Optional[ParamEMA] = None):
         super().__init__(flat.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.model, self.flat, self.max_norm = model, flat, float(max_norm)
+        if ema is not None and (ema.flat is not flat or ema.shadow.numel() != flat.flat.numel() or ema.shadow.device != flat.flat.device):
+            raise ValueError("ema must be a ParamEMA over this optimizer's FlatParams")
+        self.ema = ema
         self.overwrites_grads = overwrites_grads      # the fused diffusion backward overwrites; autograd accumulates
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
@@ -229,10 +288,19 @@ class FusedAdamW(torch.optim.Optimizer):
         self._step += 1
         dev = self.flat.flat.device
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        L.check(L.lib().osd_nn_clip_adamw_step(stream, dev.index if dev.index is not None else torch.cuda.current_device(),
-                                               L.ptr(self._normsq), L.ptr(self.flat.flat), L.ptr(self.flat.grad), L.ptr(self.exp_avg),
-                                               L.ptr(self.exp_avg_sq), self.flat.flat.numel(), g["lr"], g["betas"][0], g["betas"][1],
-                                               g["eps"], g["weight_decay"], self.max_norm, self._step, L.ptr(self.grad_norm)))
+        dev_i = dev.index if dev.index is not None else torch.cuda.current_device()
+        if self.ema is None:
+            L.check(L.lib().osd_nn_clip_adamw_step(stream, dev_i,
+                                                   L.ptr(self._normsq), L.ptr(self.flat.flat), L.ptr(self.flat.grad), L.ptr(self.exp_avg),
+                                                   L.ptr(self.exp_avg_sq), self.flat.flat.numel(), g["lr"], g["betas"][0], g["betas"][1],
+                                                   g["eps"], g["weight_decay"], self.max_norm, self._step, L.ptr(self.grad_norm)))
+        else:
+            L.check(L.lib().osd_nn_clip_adamw_ema_step(stream, dev_i, L.ptr(self._normsq), L.ptr(self.flat.flat), L.ptr(self.flat.grad),
+                                                       L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), L.ptr(self.ema.shadow),
+                                                       self.flat.flat.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                                                       g["weight_decay"], self.max_norm, self._step, self.ema.decay_at(self._step),
+                                                       L.ptr(self.grad_norm)))
+            self.ema.num_updates += 1
         for e in getattr(self.model, "_engines", {}).values():   # weights changed behind autograd's back: the
             e._sig = None                                        # engine must refresh its derived tables
         return None
@@ -528,21 +596,35 @@ class Trainer:
     own shard; gradients are averaged with one bucketed RCCL all-reduce per step, launched on a
     side stream as backward finalises each bucket (no other collective on the data path).
     Mixup permutes within the local shard (a documented deviation from a single-process
-    permutation of the global batch)."""
+    permutation of the global batch).
+
+    Weight averaging (``training.ema_decay`` in (0, 1); absent or 0: off, and nothing below exists): a ``ParamEMA`` rides in the
+    fused optimizer step.  It is created AFTER the data-parallel broadcast of the initial parameters and every rank applies the
+    same update to the same all-reduced gradients, so all ranks keep the same average with no extra collective.
+    ``training.ema_warmup`` (default true) ramps the decay as ``ParamEMA.decay_at``; ``training.ema_validate`` (default false) runs
+    ``validate()`` -- and with it the LR scheduler, the best-model choice and early stopping -- on the averaged weights.
+    Checkpoints then carry ``ema_state_dict``; ``load_checkpoint`` resumes a run."""
 
     def __init__(self, model: nn.Module, train_loader: DataLoader, val_loader: DataLoader, config: dict,
                  device: str = "cuda", *, comm: Optional[str] = None):
         """``comm``: how the data-parallel gradient exchange is driven -- "torch" (``torch.distributed.all_reduce``
         per bucket on a side stream; any backend, the default) or "rccl" (the library's own RCCL communicator,
         ``osd_allreduce_grads_begin/end``; needs one GPU per rank).  ``OSD_COMM`` in the environment sets the default."""
+        tc = config["training"]
+        ema_decay = tc.get("ema_decay")                     # checked before anything touches the device
+        ema_decay = 0.0 if ema_decay is None else float(ema_decay)
+        if ema_decay != 0.0 and not 0.0 < ema_decay < 1.0:
+            raise ValueError(f"training.ema_decay={ema_decay} outside (0, 1) (absent or 0 switches the average off)")
         self.model = model.to(device)
         self.train_loader, self.val_loader = train_loader, val_loader
         self.config, self.device = config, device
         self.is_vae = hasattr(self.model, "vae")            # the reference's dispatch (utils/train.py:233)
-        tc = config["training"]
         self.flat = FlatParams(self.model)
         self.optimizer = FusedAdamW(self.model, self.flat, lr=tc["learning_rate"], weight_decay=tc["weight_decay"], max_norm=1.0,
                                     overwrites_grads=not self.is_vae)
+        self.ema: Optional[ParamEMA] = None
+        self.ema_validate = bool(tc.get("ema_validate", False))
+        self._ema_depth = 0                                 # > 0 inside ema_weights(): the flat buffer holds the average
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="min", factor=0.5, patience=10)
         self.early_stopping = EarlyStopping(patience=tc["patience"], min_delta=tc["min_delta"])
         alpha = tc["augmentation"]["mixup_alpha"]
@@ -597,6 +679,10 @@ class Trainer:
                         self._bcast(b)
             for e in getattr(self.model, "_engines", {}).values():
                 e._sig = None
+        if ema_decay > 0.0:
+            # after the broadcast: the shadow starts from the parameters every rank now shares
+            self.ema = ParamEMA(self.model, self.flat, ema_decay, warmup=bool(tc.get("ema_warmup", True)))
+            self.optimizer.ema = self.ema
         if self.dist and not self.is_vae:
             self._events = [torch.cuda.Event() for _ in self.buckets]
             for e in self._events:
@@ -637,6 +723,38 @@ class Trainer:
             torch.distributed.broadcast(h, src=0)
             t.copy_(h)
 
+    def _engines_stale(self):
+        """The parameters changed behind the engines' backs: they re-hand the pointers and re-derive their tables at the next use."""
+        for e in getattr(self.model, "_engines", {}).values():
+            e._sig = None
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model holds the averaged weights: the shadow is copied into the flat parameter buffer (device
+        copies; the buffer and every parameter view keep their addresses) and the live weights are copied back on exit.  Sampling,
+        validation and ``state_dict()`` inside see the average; ``train_step`` refuses to run.  Re-entering is a no-op."""
+        if self.ema is None:
+            raise RuntimeError("ema_weights() needs training.ema_decay in (0, 1): this Trainer keeps no average")
+        if self._ema_depth > 0:
+            self._ema_depth += 1
+            try:
+                yield self.model
+            finally:
+                self._ema_depth -= 1
+            return
+        with torch.no_grad():
+            live = self.flat.flat.clone()
+            self.flat.flat.copy_(self.ema.shadow)
+        self._engines_stale()
+        self._ema_depth = 1
+        try:
+            yield self.model
+        finally:
+            with torch.no_grad():
+                self.flat.flat.copy_(live)
+            self._engines_stale()
+            self._ema_depth = 0
+
     # one optimisation step on an already device-resident (and mixed) batch
     def train_step(self, data, conditions, survival=None, *, t=None, noise=None, dropout_masks=None, seed=None, comm_events=None,
                    source=None, cond_keep=None, **vae_kw) -> torch.Tensor:
@@ -646,6 +764,8 @@ class Trainer:
         keep their condition under condition dropout (default: drawn on the device from the step's seed and global row ids)."""
         if not self.flat.is_current(quick=True):
             raise RuntimeError("model parameters were re-allocated after Trainer construction (e.g. model.to()); rebuild the Trainer")
+        if self._ema_depth:
+            raise RuntimeError("train_step inside ema_weights(): the model holds the averaged weights, not the ones being trained")
         if self._engine is not None and (self._engine.constraints_version != self.model._constraints_version or
                                          self._engine.loss_state != self.model._loss_state() or self._opts != self._option_state()):
             # set_constraints(), the objective (loss_type, ...) or a tunable (train_streams, ...) changed after construction: let the model's own
@@ -726,9 +846,15 @@ class Trainer:
             total += self.train_step(data, conditions, survival)
         return float(total.item()) / len(self.train_loader)
 
-    @torch.no_grad()
     def validate(self):
-        """utils/train.py:252-273 (eval mode, still random t / noise)."""
+        """utils/train.py:252-273 (eval mode, still random t / noise); on the averaged weights under ``training.ema_validate``."""
+        if self.ema is not None and self.ema_validate:
+            with self.ema_weights():
+                return self._validate()
+        return self._validate()
+
+    @torch.no_grad()
+    def _validate(self):
         self.model.eval()
         total = torch.zeros(1, device=self.device)
         _, res = self._resident_splits()
@@ -765,11 +891,38 @@ class Trainer:
             return
         ckpt = {"epoch": epoch, "model_state_dict": self.model.state_dict(), "optimizer_state_dict": self.optimizer.state_dict(),
                 "val_loss": val_loss, "config": self.config}
+        if self.ema is not None:
+            if self._ema_depth:
+                raise RuntimeError("save_checkpoint inside ema_weights(): model_state_dict would hold the averaged weights")
+            ckpt["ema_state_dict"] = self.ema.state_dict()
         torch.save(ckpt, self.save_dir / f"checkpoint_epoch_{epoch}.pt")
         if is_best:
             best = self.save_dir / "best_model.pt"
             torch.save(ckpt, best)
             logger.info(f"Saved best model to {best}")
+
+    def load_checkpoint(self, path) -> int:
+        """Resume from a file ``save_checkpoint`` wrote: the model (in place, the flat buffer keeps its address), the optimizer
+        (moments, step count and learning rate, through ``FusedAdamW.load_state_dict``) and -- when this Trainer keeps an average
+        and the file has one -- the EMA.  Returns the saved epoch.  The LR scheduler's and early stopping's counters are not in
+        the file (its keys are the reference's) and start afresh."""
+        if self._ema_depth:
+            raise RuntimeError("load_checkpoint inside ema_weights()")
+        ckpt = torch.load(path, map_location="cpu", weights_only=True)
+        self.model.load_state_dict(ckpt["model_state_dict"])
+        if not self.flat.is_current():
+            raise RuntimeError("loading the checkpoint re-allocated the model's parameters; rebuild the Trainer")
+        self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
+        if self.ema is not None:
+            if "ema_state_dict" in ckpt:
+                self.ema.load_state_dict(ckpt["ema_state_dict"])
+            else:
+                logger.info(f"{path} has no ema_state_dict: the average restarts from the loaded weights")
+                with torch.no_grad():
+                    self.ema.shadow.copy_(self.flat.flat)
+                self.ema.num_updates = 0
+        self._engines_stale()
+        return int(ckpt["epoch"])
 
     def train(self):
         """utils/train.py:296-339."""
