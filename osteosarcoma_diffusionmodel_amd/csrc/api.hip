@@ -1,5 +1,7 @@
 // api.hip -- C ABI of libosdiff.so (include/osdiff.h): handle management, the denoiser
-// forward pass, q_sample / p_sample / the hipGraph-replayed reverse chain.
+// forward pass (forward_request), q_sample / p_sample / the reverse chain.  sample_request
+// validates an osd_sample_chain* call into a ChainJob (handle.h), sample_plan picks the engine
+// and chain_chunk drives the per-layer kernels (eager or hipGraph-replayed).
 // Training entry points live in train.hip.
 #include <stdarg.h>
 #include <stdio.h>
@@ -94,14 +96,18 @@ int build_arch(const osd_config& c, Arch* a) {
   return OSD_OK;
 }
 
-static int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+int device_alloc(void** p, size_t bytes) {
+  if (hipMalloc(p, bytes) == hipSuccess) return OSD_OK;
+  (void)hipGetLastError();
+  *p = nullptr;
+  set_error("hipMalloc of %lld bytes failed", (long long)bytes);
+  return OSD_ENOMEM;
+}
 
 int ensure_arena(Slot* s, int64_t floats) {
   if (s->arena_floats >= floats) return OSD_OK;
   if (s->arena) { hipError_t e = hipFree(s->arena); (void)e; s->arena = nullptr; s->arena_floats = 0; }
-  void* p = nullptr;
-  if (hipMalloc(&p, (size_t)floats * 4) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc of %lld bytes failed", (long long)floats * 4); return OSD_ENOMEM; }
-  s->arena = (float*)p;
+  OSD_TRY(device_alloc((void**)&s->arena, (size_t)floats * 4));
   s->arena_floats = floats;
   return OSD_OK;
 }
@@ -109,7 +115,7 @@ int ensure_arena(Slot* s, int64_t floats) {
 // Carve forward activations for n rows out of `base`; returns floats used.
 int64_t carve_fwd(const Arch& a, float* base, int64_t n, bool train, FwdWs* ws) {
   int64_t off = 0;
-  auto take = [&](int64_t floats) { float* p = base ? base + off : nullptr; off += align_up(floats, 64); return p; };
+  auto take = [&](int64_t floats) { float* p = base ? base + off : nullptr; off += up64(floats); return p; };
   ws->ce1 = take(n * 64); ws->ce2 = take(n * 64);
   ws->cproj = take(n * a.H0); ws->h0 = take(n * a.H0);
   ws->mid.resize(a.n_blocks); ws->out.resize(a.n_blocks);
@@ -149,116 +155,98 @@ static int prof_mark(osd_handle* h, hipStream_t s) {
   return OSD_OK;
 }
 
+static hipError_t launch_in(hipStream_t s, const GemmArgs& g, const EpiInput::Args& ea) { return launch_input(s, g, ea, true); }
+static hipError_t launch_in(hipStream_t s, const GemmArgs& g, const EpiInputGuided::Args& ea) { return launch_input_guided(s, g, ea, true); }
+static hipError_t launch_in_splitk(hipStream_t s, const GemmArgs& g, const EpiInput::Args& ea, float* slabs, int slices) {
+  return launch_input_splitk(s, g, ea, slabs, slices);
+}
+static hipError_t launch_in_splitk(hipStream_t s, const GemmArgs& g, const EpiInputGuided::Args& ea, float* slabs, int slices) {
+  return launch_input_guided_splitk(s, g, ea, slabs, slices);
+}
+
+// input_proj with either epilogue (EpiInput / EpiInputGuided): K in slices over workgroups where the caller provides slabs and the
+// shape allows (k_fused.hip), else one pass
+template <class EpiArgs>
+static int run_input_proj(osd_handle* h, hipStream_t s, const TrunkIn& in, GemmArgs g, const EpiArgs& ea) {
+  const Arch& a = h->arch;
+  if (in.in_slices > 1 && in.in_slabs) {
+    const hipError_t e = launch_in_splitk(s, g, ea, in.in_slabs, in.in_slices);
+    if (e == hipSuccess) return prof_mark(h, s);
+    if (e != hipErrorInvalidValue) OSD_HIP(e);
+    (void)hipGetLastError();
+  }
+  hipError_t e = launch_in(s, g, ea);
+  if (e == hipErrorInvalidValue && g.a_kmax > 0) {
+    // the clamped-weight path needs 16-byte aligned parameter pointers (launch.h: glds_ok / fast_ok), which the caller of
+    // osd_load_weights does not owe us: pack the padded copy after all and read that (x already has zero pad columns)
+    (void)hipGetLastError();
+    OSD_HIP(launch_copy2d(s, h->params[a.pm.in_w], a.D, h->w_in_packed, h->w_in_ld, a.H0, a.D));
+    g.A = h->w_in_packed; g.lda = h->w_in_ld; g.a_kmax = 0;
+    e = launch_in(s, g, ea);
+    if (in.path) *in.path |= OSD_TP_INPUT_REPACK;
+  }
+  OSD_HIP(e);
+  return prof_mark(h, s);
+}
+
 // input_proj + blocks (models/diffusion.py:229-251); result in ws.out[n_blocks-1].
 int run_trunk(osd_handle* h, hipStream_t s, const FwdWs& ws, const TrunkIn& in) {
   const Arch& a = h->arch;
   const ParamMap& pm = a.pm;
   const int n = (int)in.n;
-  if (in.guide_m > 0) {
-    // one input_proj GEMM over the state rows, both branches' h0 from its epilogue -- or, for small batches, from the split-K reduce
+  const bool guided = in.guide_m > 0;      // one input_proj GEMM over the state rows, both branches' h0 from its epilogue (or the split-K reduce)
+  {
     GemmArgs g{};
     const int kx = in.kx > 0 ? in.kx : a.D;
     g.A = h->w_in_packed; g.lda = h->w_in_ld; g.B0 = in.x; g.ldb0 = in.ldx; g.K0 = kx;
-    g.F = a.H0; g.P = (int)in.guide_m; g.K = kx;
+    g.F = a.H0; g.P = guided ? (int)in.guide_m : n; g.K = kx;
+    if (in.a_unpacked && !guided) { g.A = h->params[pm.in_w]; g.lda = a.D; g.a_kmax = a.D; }
     g.ksplit = in.ksplit ? 1 : 0;
-    EpiInputGuided::Args ea{h->params[pm.in_b], in.temb ? in.temb : h->d_temb, a.H0, in.t_index, in.t_dev, in.t_imm, ws.cproj, a.H0, in.cproj0,
-                            ws.h0, a.H0, (long long)in.guide_m * a.H0};
-    bool done = false;
-    if (in.in_slices > 1 && in.in_slabs) {
-      const hipError_t e = launch_input_guided_splitk(s, g, ea, in.in_slabs, in.in_slices);
-      if (e == hipSuccess) done = true;
-      else if (e != hipErrorInvalidValue) OSD_HIP(e);
-      else (void)hipGetLastError();
+    const EpiInput::Args ea{h->params[pm.in_b], in.temb ? in.temb : h->d_temb, a.H0, in.t_index, in.t_dev, in.t_imm, ws.cproj, a.H0, ws.h0, a.H0};
+    if (guided) {
+      OSD_TRY(run_input_proj(h, s, in, g, EpiInputGuided::Args{ea.bias, ea.temb, ea.ldt, ea.t_index, ea.t_dev, ea.t_imm, ea.cproj, ea.ldc, in.cproj0,
+                                                              ea.out, ea.ldo, (long long)in.guide_m * a.H0}));
+    } else {
+      OSD_TRY(run_input_proj(h, s, in, g, ea));
     }
-    if (!done) OSD_HIP(launch_input_guided(s, g, ea, true));
-    OSD_TRY(prof_mark(h, s));
-  } else {
-    GemmArgs g{};
-    const int kx = in.kx > 0 ? in.kx : a.D;
-    g.A = h->w_in_packed; g.lda = h->w_in_ld; g.B0 = in.x; g.ldb0 = in.ldx; g.K0 = kx;
-    g.F = a.H0; g.P = n; g.K = kx;
-    if (in.a_unpacked) { g.A = h->params[pm.in_w]; g.lda = a.D; g.a_kmax = a.D; }
-    g.ksplit = in.ksplit ? 1 : 0;
-    EpiInput::Args ea{h->params[pm.in_b], in.temb ? in.temb : h->d_temb, a.H0, in.t_index, in.t_dev, in.t_imm, ws.cproj, a.H0, ws.h0, a.H0};
-    bool done = false;
-    if (in.in_slices > 1 && in.in_slabs) {
-      const hipError_t e = launch_input_splitk(s, g, ea, in.in_slabs, in.in_slices);
-      if (e == hipSuccess) done = true;
-      else if (e != hipErrorInvalidValue) OSD_HIP(e);
-      else (void)hipGetLastError();
-    }
-    if (!done) {
-      hipError_t e = launch_input(s, g, ea, true);
-      if (e == hipErrorInvalidValue && in.a_unpacked) {
-        // the clamped-weight path needs 16-byte aligned parameter pointers (launch.h: glds_ok / fast_ok), which the caller of
-        // osd_load_weights does not owe us: pack the padded copy after all and read that (x already has zero pad columns)
-        (void)hipGetLastError();
-        OSD_HIP(launch_copy2d(s, h->params[pm.in_w], a.D, h->w_in_packed, h->w_in_ld, a.H0, a.D));
-        g.A = h->w_in_packed; g.lda = h->w_in_ld; g.a_kmax = 0;
-        e = launch_input(s, g, ea, true);
-        if (in.path) *in.path |= OSD_TP_INPUT_REPACK;
-      }
-      OSD_HIP(e);
-    }
-    OSD_TRY(prof_mark(h, s));
   }
   if (in.input_only) return OSD_OK;
-  const float* cur = ws.h0;
-  int cur_w = a.H0;
-  for (int b = 0; b < a.n_blocks; ++b) {
-    const LayerDesc& l1 = a.layers[2 * b];
-    const LayerDesc& l2 = a.layers[2 * b + 1];
+  const bool drop = in.train && h->cfg.dropout_p > 0.f;
+  // one Linear + GroupNorm + SiLU launch: the first half of a block (dropout behind it, the decoder's skip input beside x) or the second
+  auto layer = [&](const LayerDesc& l, const float* x, float* out, float* z, float* stats) -> int {
+    const int b = l.block;
     GemmArgs g{};
-    g.A = h->params[l1.w]; g.lda = l1.K1 + l1.K2;
-    g.B0 = cur; g.ldb0 = cur_w; g.K0 = l1.K1;
-    if (l1.K2 > 0) {
-      const int skip_block = a.n_enc - 1 - (b - a.n_enc - 1);   // LIFO: decoder j pops encoder n_enc-1-j
-      g.B1 = ws.out[skip_block]; g.ldb1 = a.block_out[skip_block];
-    }
-    g.F = l1.N; g.P = n; g.K = l1.K1 + l1.K2; g.ksplit = in.ksplit ? 1 : 0;
+    g.A = h->params[l.w]; g.lda = l.K1 + l.K2; g.B0 = x; g.ldb0 = l.K1; g.K0 = l.K1;
+    if (l.K2 > 0) { g.B1 = ws.out[a.skip_of(b)]; g.ldb1 = a.block_out[a.skip_of(b)]; }
+    g.F = l.N; g.P = n; g.K = l.K1 + l.K2; g.ksplit = in.ksplit ? 1 : 0;
     GnArgs ga{};
-    ga.bias = h->params[l1.b]; ga.gamma = h->params[l1.gamma]; ga.beta = h->params[l1.beta];
-    ga.out = ws.mid[b]; ga.ldo = l1.N;
-    ga.z_out = in.save ? ws.z1[b] : nullptr; ga.ldz = l1.N; ga.stats = in.save ? ws.st1[b] : nullptr;
-    const bool drop = in.train && h->cfg.dropout_p > 0.f;
-    // small batches: a deep layer is a few dozen tiles of 16-32 sequential K steps -- K in slices over workgroups + a reduce kernel
-    auto gn_split = [&](const GemmArgs& gg, const GnArgs& aa) -> int {      // 1 = launched, 0 = not applicable, < 0 = error
-      if (in.gn_slices < 2 || !in.gn_slabs || in.save || gg.K < 512) return 0;
-      const hipError_t e = launch_gn_silu_splitk(s, gg, aa, in.gn_slabs, in.gn_slices);
-      if (e == hipSuccess) return 1;
-      (void)hipGetLastError();
-      if (e == hipErrorInvalidValue) return 0;
-      set_error("launch_gn_silu_splitk failed: %s", hipGetErrorString(e));
-      return OSD_EHIP;
-    };
-    if (drop) {
+    ga.bias = h->params[l.b]; ga.gamma = h->params[l.gamma]; ga.beta = h->params[l.beta];
+    ga.out = out; ga.ldo = l.N;
+    ga.z_out = in.save ? z : nullptr; ga.ldz = l.N; ga.stats = in.save ? stats : nullptr;
+    if (drop && l.half == 0) {
       ga.drop_mode = in.masks ? 1 : 2;
-      ga.mask = in.masks ? in.masks[b] : nullptr; ga.ldm = l1.N;
+      ga.mask = in.masks ? in.masks[b] : nullptr; ga.ldm = l.N;
       ga.keep_scale = (float)(1.0 / (1.0 - (double)h->cfg.dropout_p)); ga.p_drop = h->cfg.dropout_p;
       ga.seed = in.seed; ga.row_offset = in.row_offset; ga.step = in.drop_step; ga.tag = TAG_DROPOUT + (uint32_t)b;
       ga.step_dev = in.drop_step_dev;
-      OSD_HIP(launch_gn_silu_drop(s, g, l1.gw, ga));
-    } else {
-      const int sp = gn_split(g, ga);
-      if (sp < 0) return sp;
-      if (!sp) OSD_HIP(launch_gn_silu(s, g, l1.gw, ga));
+      OSD_HIP(launch_gn_silu_drop(s, g, l.gw, ga));
+      return prof_mark(h, s);
     }
-    OSD_TRY(prof_mark(h, s));
-    GemmArgs g2{};
-    g2.A = h->params[l2.w]; g2.lda = l2.K1; g2.B0 = ws.mid[b]; g2.ldb0 = l1.N; g2.K0 = l2.K1;
-    g2.F = l2.N; g2.P = n; g2.K = l2.K1; g2.ksplit = in.ksplit ? 1 : 0;
-    GnArgs gb{};
-    gb.bias = h->params[l2.b]; gb.gamma = h->params[l2.gamma]; gb.beta = h->params[l2.beta];
-    gb.out = ws.out[b]; gb.ldo = l2.N;
-    gb.z_out = in.save ? ws.z2[b] : nullptr; gb.ldz = l2.N; gb.stats = in.save ? ws.st2[b] : nullptr;
-    {
-      const int sp = gn_split(g2, gb);
-      if (sp < 0) return sp;
-      if (!sp) OSD_HIP(launch_gn_silu(s, g2, l2.gw, gb));
+    // small batches: a deep layer is a few dozen tiles of 16-32 sequential K steps -- K in slices over workgroups + a reduce kernel
+    if (in.gn_slices >= 2 && in.gn_slabs && !in.save && g.K >= 512) {
+      const hipError_t e = launch_gn_silu_splitk(s, g, ga, in.gn_slabs, in.gn_slices);
+      if (e == hipSuccess) return prof_mark(h, s);
+      (void)hipGetLastError();
+      if (e != hipErrorInvalidValue) { set_error("launch_gn_silu_splitk failed: %s", hipGetErrorString(e)); return OSD_EHIP; }
     }
-    OSD_TRY(prof_mark(h, s));
+    OSD_HIP(launch_gn_silu(s, g, l.gw, ga));
+    return prof_mark(h, s);
+  };
+  const float* cur = ws.h0;
+  for (int b = 0; b < a.n_blocks; ++b) {
+    OSD_TRY(layer(a.layers[2 * b], cur, ws.mid[b], ws.z1[b], ws.st1[b]));
+    OSD_TRY(layer(a.layers[2 * b + 1], ws.mid[b], ws.out[b], ws.z2[b], ws.st2[b]));
     cur = ws.out[b];
-    cur_w = l2.N;
   }
   return OSD_OK;
 }
@@ -312,7 +300,7 @@ GemmArgs output_proj_args(osd_handle* h, const FwdWs& ws, int64_t n, bool padded
 // checked that the vector is there and finite.
 int upload_null_cond(osd_handle* h, int slot, const float* null_cond_host, const float** dev) {
   const int cd = h->arch.cond_dim;
-  const size_t stride = (size_t)(cd + 63) / 64 * 64;
+  const size_t stride = (size_t)up64(cd);
   OSD_HIP(hipSetDevice(h->cfg.device));
   if (!h->null_host) {
     h->null_host = static_cast<float*>(malloc(2 * stride * 4));
@@ -361,11 +349,28 @@ int sanitize_t(osd_handle* h, hipStream_t s, const int32_t* t_index, int64_t n, 
   if (h->t_san_cap < n) {
     if (h->t_san) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(h->t_san)); h->t_san = nullptr; h->t_san_cap = 0; }
     const int64_t cap = (n + 1023) / 1024 * 1024;
-    if (hipMalloc((void**)&h->t_san, (size_t)cap * 4) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc of %lld bytes failed", (long long)cap * 4); return OSD_ENOMEM; }
+    OSD_TRY(device_alloc((void**)&h->t_san, (size_t)cap * 4));
     h->t_san_cap = cap;
   }
   OSD_HIP(launch_clamp_int(s, t_index, n, 0, h->arch.T - 1, h->t_san));
   *out = h->t_san;
+  return OSD_OK;
+}
+
+// ---- shared by the chunk drivers (chain_chunk below, split.hip: split_chain_chunk) and the chain kernels' host files (fwd.h) ----
+int release_graph(Slot& sl) {
+  if (!sl.exec && !sl.graph) return OSD_OK;
+  OSD_HIP(hipStreamSynchronize(sl.stream));
+  if (sl.exec) OSD_HIP(hipGraphExecDestroy(sl.exec));
+  if (sl.graph) OSD_HIP(hipGraphDestroy(sl.graph));
+  sl.exec = nullptr;
+  sl.graph = nullptr;
+  return OSD_OK;
+}
+
+int chain_init_state(osd_handle* h, hipStream_t s, const ChainJob& job, float* x, int ldx, bool keep_aliased) {
+  if (!job.x_T) OSD_HIP(launch_fill_randn(s, x, ldx, job.n, job.D, job.seed, (uint32_t)job.row_offset, (uint32_t)h->arch.T, TAG_POSTERIOR));
+  else if (!(keep_aliased && job.x_T == x)) OSD_HIP(launch_copy2d(s, job.x_T, job.D, x, ldx, job.n, job.D));
   return OSD_OK;
 }
 
@@ -621,38 +626,87 @@ int osd_load_weights(osd_handle* h, const float* const* params, int n) {
   return OSD_OK;
 }
 
-int osd_denoiser_forward(osd_handle* h, const float* x, const int32_t* t_index, int32_t t_all, const float* cond, int64_t n,
-                         float* eps, int flags, const float* const* masks, uint64_t seed) {
+// What both guided entry points refuse; *unguided: guidance_scale == 1 exactly -- the caller takes the unguided entry point's path.
+static int check_guidance(osd_handle* h, const float* null_cond_host, float guidance_scale, int flags, bool* unguided) {
+  if (!std::isfinite(guidance_scale)) { set_error("guidance_scale is not finite"); return OSD_EINVAL; }
+  if (!null_cond_host) { set_error("null_cond is null"); return OSD_EINVAL; }
+  for (int i = 0; i < h->arch.cond_dim; ++i)
+    if (!std::isfinite(null_cond_host[i])) { set_error("null_cond[%d] is not finite", i); return OSD_EINVAL; }
+  *unguided = guidance_scale == 1.0f;
+  if (*unguided) return OSD_OK;
+  if (flags & OSD_F_TRAIN_MODE) { set_error("guided sampling is eval mode only (no dropout inside a guided evaluation)"); return OSD_EINVAL; }
+  if (h->precision == 1) { set_error("precision = bf16x3 does not run guided evaluations: set precision to fp32 or guidance_scale to 1"); return OSD_EUNSUPPORTED; }
+  return OSD_OK;
+}
+
+// The condition batch of a guided chunk: the m rows' conditions and, as row m, the null condition -- so that c_proj of the null
+// condition comes out of the same launches, with the bits it has as a row of any batch.  stage: [m + 1][cond_dim].
+static int guided_cond(osd_handle* h, hipStream_t s, const Guide& gd, const float* cond, int64_t m, float* stage, const FwdWs& ws) {
+  const int cd = h->arch.cond_dim;
+  OSD_HIP(hipMemcpyAsync(stage, cond, (size_t)m * cd * 4, hipMemcpyDeviceToDevice, s));
+  OSD_HIP(hipMemcpyAsync(stage + m * cd, gd.null_cond, (size_t)cd * 4, hipMemcpyDeviceToDevice, s));
+  return run_cond(h, s, stage, m + 1, ws);
+}
+
+// A denoiser evaluation in the caller's terms: what osd_denoiser_forward and osd_denoiser_forward_guided receive, absent parts null.
+struct ForwardRequest {
+  const float* x; const int32_t* t_index; int32_t t_all; const float* cond; int64_t n; float* eps; int flags;
+  const float* const* masks; uint64_t seed;
+  bool guide;                     // check (and, unless guidance_scale == 1, apply) classifier-free guidance
+  const float* null_cond; float guidance_scale;
+};
+
+// The one path of both entry points: a guided evaluation stages the null condition behind the batch's, runs the trunk on 2 n rows
+// and combines the two halves in front of output_proj.
+static int forward_request(osd_handle* h, const ForwardRequest& r) {
+  const int64_t n = r.n;
+  bool guided = r.guide;
   OSD_TRY(check_ready(h));
+  if (guided) {
+    bool unguided = false;
+    OSD_TRY(check_guidance(h, r.null_cond, r.guidance_scale, r.flags, &unguided));
+    guided = !unguided;
+  }
   OSD_TRY(check_rows(n));
-  if (!x || !cond || !eps) { set_error("null tensor"); return OSD_EINVAL; }
+  if (!r.x || !r.cond || !r.eps) { set_error("null tensor"); return OSD_EINVAL; }
   const Arch& a = h->arch;
-  if (!t_index && (t_all < 0 || t_all >= a.T)) { set_error("t=%d outside [0,%d)", t_all, a.T); return OSD_EINVAL; }
+  if (!r.t_index && (r.t_all < 0 || r.t_all >= a.T)) { set_error("t=%d outside [0,%d)", r.t_all, a.T); return OSD_EINVAL; }
   if (n == 0) return OSD_OK;
   OSD_HIP(hipSetDevice(h->cfg.device));
   hipStream_t s = h->stream;
   OSD_TRY(ensure_packed(h, s));
   const int* t_idx = nullptr;
-  OSD_TRY(sanitize_t(h, s, t_index, n, &t_idx));
-  if (h->precision == 1 && !(flags & OSD_F_TRAIN_MODE) && !masks) {      // eval mode on the bf16 matrix pipe; dropout stays fp32
-    OSD_TRY(split_denoiser_forward(h, x, t_idx, t_all, cond, n, eps));
-    if (flags & OSD_F_SYNC) OSD_HIP(hipStreamSynchronize(s));
+  OSD_TRY(sanitize_t(h, s, r.t_index, n, &t_idx));
+  Guide gd{nullptr, r.guidance_scale};
+  if (guided) OSD_TRY(upload_null_cond(h, 0, r.null_cond, &gd.null_cond));
+  if (h->precision == 1 && !(r.flags & OSD_F_TRAIN_MODE) && !r.masks) {      // eval mode on the bf16 matrix pipe; dropout stays fp32
+    OSD_TRY(split_denoiser_forward(h, r.x, t_idx, r.t_all, r.cond, n, r.eps));
+    if (r.flags & OSD_F_SYNC) OSD_HIP(hipStreamSynchronize(s));
     return OSD_OK;
   }
   h->last_precision = 0;
+  const int64_t nt = guided ? 2 * n : n;        // rows of the trunk
   FwdWs ws;
-  const int64_t need = carve_fwd(a, nullptr, n, false, &ws);
-  OSD_TRY(ensure_arena(&h->main, need));
-  carve_fwd(a, h->main.arena, n, false, &ws);
-  OSD_TRY(run_cond(h, s, cond, n, ws));
+  const int64_t need = up64(carve_fwd(a, nullptr, nt, false, &ws));
+  OSD_TRY(ensure_arena(&h->main, need + (guided ? (n + 1) * (int64_t)a.cond_dim : 0)));
+  carve_fwd(a, h->main.arena, nt, false, &ws);
+  if (guided) OSD_TRY(guided_cond(h, s, gd, r.cond, n, h->main.arena + need, ws));
+  else OSD_TRY(run_cond(h, s, r.cond, n, ws));
   TrunkIn in{};
-  in.x = x; in.ldx = a.D; in.n = n; in.t_index = t_idx; in.t_imm = t_all;
-  in.train = (flags & OSD_F_TRAIN_MODE) != 0; in.masks = masks; in.seed = seed;
+  in.x = r.x; in.ldx = a.D; in.n = nt; in.t_index = t_idx; in.t_imm = r.t_all;
+  in.train = (r.flags & OSD_F_TRAIN_MODE) != 0; in.masks = r.masks; in.seed = r.seed;
+  if (guided) { in.guide_m = n; in.cproj0 = ws.cproj + n * a.H0; }
   OSD_TRY(run_trunk(h, s, ws, in));
+  if (guided) OSD_HIP(launch_guide_combine(s, ws.out[a.n_blocks - 1], n, a.block_out[a.n_blocks - 1], gd.w));
   GemmArgs g = output_proj_args(h, ws, n);
-  OSD_HIP(launch_linear(s, g, true, true, h->params[a.pm.out_b], eps, a.D, false, false));
-  if (flags & OSD_F_SYNC) OSD_HIP(hipStreamSynchronize(s));
+  OSD_HIP(launch_linear(s, g, true, true, h->params[a.pm.out_b], r.eps, a.D, false, false));
+  if (r.flags & OSD_F_SYNC) OSD_HIP(hipStreamSynchronize(s));
   return OSD_OK;
+}
+
+int osd_denoiser_forward(osd_handle* h, const float* x, const int32_t* t_index, int32_t t_all, const float* cond, int64_t n,
+                         float* eps, int flags, const float* const* masks, uint64_t seed) {
+  return forward_request(h, ForwardRequest{x, t_index, t_all, cond, n, eps, flags, masks, seed});
 }
 
 int osd_q_sample(osd_handle* h, const float* x0, const int32_t* t_index, const float* noise_in, int64_t n, uint64_t seed,
@@ -706,46 +760,14 @@ int osd_p_sample_step(osd_handle* h, const float* x_t, int32_t t, const float* c
   return OSD_OK;
 }
 
-// Drop the slot's previous graph once everything replayed from it has finished.
-static int release_graph(Slot& sl) {
-  if (!sl.exec && !sl.graph) return OSD_OK;
-  OSD_HIP(hipStreamSynchronize(sl.stream));
-  if (sl.exec) OSD_HIP(hipGraphExecDestroy(sl.exec));
-  if (sl.graph) OSD_HIP(hipGraphDestroy(sl.graph));
-  sl.exec = nullptr;
-  sl.graph = nullptr;
-  return OSD_OK;
-}
-
-// Classifier-free guidance of a chain / an evaluation (osd_sample_chain_guided): eps = eps(c0) + w * (eps(c) - eps(c0)).
-struct Guide {
-  const float* null_cond;      // dev [cond_dim]
-  float w;
-};
-
-// Known-feature conditioning of a chain (osd_sample_chain_known): observed elements are overwritten after every step (EpiPosteriorKnown).
-struct Known {
-  const float* known;          // dev [n][ld], NaN = free
-  int64_t ld;
-  const float* level;          // dev [S][2]
-};
-
-// The condition batch of a guided chunk: the m rows' conditions and, as row m, the null condition -- so that c_proj of the null
-// condition comes out of the same launches, with the bits it has as a row of any batch.  stage: [m + 1][cond_dim].
-static int guided_cond(osd_handle* h, hipStream_t s, const Guide& gd, const float* cond, int64_t m, float* stage, const FwdWs& ws) {
-  const int cd = h->arch.cond_dim;
-  OSD_HIP(hipMemcpyAsync(stage, cond, (size_t)m * cd * 4, hipMemcpyDeviceToDevice, s));
-  OSD_HIP(hipMemcpyAsync(stage + m * cd, gd.null_cond, (size_t)cd * 4, hipMemcpyDeviceToDevice, s));
-  return run_cond(h, s, stage, m + 1, ws);
-}
-
-// One chunk of the reverse chain on one slot: rows [r0, r0+m).  gd != null: a guided chain -- the trunk runs on 2 m rows (rows
-// [0, m) with the patients' conditions, [m, 2 m) with the null condition), input_proj and output_proj on m.
-static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const float* cond, int64_t n_total, int64_t r0, int64_t m,
-                       const float* x_T, const float* noises, uint64_t seed, int64_t row_offset, float* x_out, float* mut_mask_out, int flags,
-                       const Guide* gd = nullptr, const Known* kn = nullptr) {
+// One chunk of the reverse chain on one slot: rows [r0, r0+m).  A guided chain runs the trunk on 2 m rows (rows [0, m) with the
+// patients' conditions, [m, 2 m) with the null condition), input_proj and output_proj on m.
+static int chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r0, int64_t m) {
   const Arch& a = h->arch;
-  const int D = a.D, S = plan.n_steps;
+  const ChainJob job = whole.chunk(r0, m);
+  const Guide* gd = job.guide.null_cond ? &job.guide : nullptr;
+  const Known* kn = job.known.known ? &job.known : nullptr;
+  const int D = a.D, S = job.plan.n_steps;
   hipStream_t s = sl.stream;
   OSD_TRY(release_graph(sl));
   FwdWs ws;
@@ -754,9 +776,9 @@ static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const floa
   // D % 4 != 0 with device-generated draws: the state of the chunk lives in a padded buffer behind the activations (rows of Dp
   // floats, pad columns zero at the start) and is copied to the caller's rows at the end; injected draws ([S-1][n][D], rows not
   // 16-byte aligned) keep the guarded kernels on the caller's tensor
-  const bool padded = h->w_out_packed != nullptr && !noises;
+  const bool padded = h->w_out_packed != nullptr && !job.noises;
   const int ldx = padded ? h->Dp : D;
-  const int64_t need_pad = (need + 63) / 64 * 64;
+  const int64_t need_pad = up64(need);
   // small batches: input_proj split-K (k_fused.hip) -- few output tiles, each a long sequential K loop
   int in_slices = 0;
   constexpr int64_t INPUT_SPLITK_TARGET = 768;      // workgroups the auto mode (-1) aims at: slices = this / output tiles
@@ -768,12 +790,12 @@ static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const floa
     in_slices = std::min(in_slices, ldx / 128);
     if (in_slices < 2) in_slices = 0;
   }
-  const int64_t x_floats = padded ? (m * (int64_t)ldx + 63) / 64 * 64 : 0;
+  const int64_t x_floats = padded ? up64(m * (int64_t)ldx) : 0;
   // ... and the deep Linear+GroupNorm layers likewise (same switch: the small-batch mode): slices so that a 512-wide layer has ~640
   // workgroups (64 x 64 tiles)
   int gn_slices = 0, max_c = a.H0;
   for (int c : a.block_out) max_c = std::max(max_c, c);
-  if (in_slices > 0 && !(flags & OSD_F_TRAIN_MODE)) {
+  if (in_slices > 0 && !(job.flags & OSD_F_TRAIN_MODE)) {
     const int64_t tiles = (int64_t)((max_c + 63) / 64) * ((mt + 63) / 64);
     gn_slices = (int)std::min<int64_t>(4, (640 + tiles / 2) / tiles);
     if (gn_slices < 4) gn_slices = 0;      // measured (dims 62 / 5054 / 26): 999 rows 257 -> 238 us per step with 4 slices; 3000 rows 351 -> 385 us with 2
@@ -781,98 +803,80 @@ static int chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const floa
   // a guided chunk in the small-batch mode: input_proj split over K as for m rows (its reduce kernel writes both halves), the deep
   // layers' K slices and the two-wave-group GEMMs as for 2 m unguided rows.  The slabs end on a 64-float boundary so that whatever is
   // carved behind them (a guided chunk's condition staging) stays aligned
-  const int64_t slab_floats = align_up(std::max<int64_t>((int64_t)in_slices * m * a.H0, gn_slices ? (int64_t)(gn_slices + 1) * mt * max_c : 0), 64);
+  const int64_t slab_floats = up64(std::max<int64_t>((int64_t)in_slices * m * a.H0, gn_slices ? (int64_t)(gn_slices + 1) * mt * max_c : 0));
   const int64_t stage_floats = gd ? (m + 1) * (int64_t)a.cond_dim : 0;
   // a padded state reads its observations from rows of Dp floats too: the chunk's known rows, copied once, pad columns NaN (free)
   const int64_t known_floats = kn && padded ? m * (int64_t)ldx : 0;
-  OSD_TRY(ensure_arena(&sl, need_pad + x_floats + slab_floats + align_up(stage_floats, 64) + known_floats));
+  OSD_TRY(ensure_arena(&sl, need_pad + x_floats + slab_floats + up64(stage_floats) + known_floats));
   carve_fwd(a, sl.arena, mt, false, &ws);
-  float* x = padded ? sl.arena + need_pad : x_out + r0 * D;       // else the chain state lives in the output rows
+  float* x = padded ? sl.arena + need_pad : job.x_out;       // else the chain state lives in the output rows
   float* in_slabs = in_slices ? sl.arena + need_pad + x_floats : nullptr;
   float* cond_stage = sl.arena + need_pad + x_floats + slab_floats;
   if (padded) OSD_HIP(hipMemsetAsync(x, 0, (size_t)m * ldx * 4, s));
-  const float* known = kn ? kn->known + r0 * kn->ld : nullptr;
-  int ldk = kn ? (int)kn->ld : 0;
+  const float* known = job.known.known;
+  int ldk = (int)job.known.ld;
   if (kn && padded) {
-    float* kpad = cond_stage + align_up(stage_floats, 64);
+    float* kpad = cond_stage + up64(stage_floats);
     OSD_HIP(hipMemsetAsync(kpad, 0xff, (size_t)m * ldx * 4, s));          // all bits set: a NaN
     OSD_HIP(launch_copy2d(s, known, ldk, kpad, ldx, m, D));
     known = kpad; ldk = ldx;
   }
-  const uint32_t roff = (uint32_t)(row_offset + r0);
-  const bool train = (flags & OSD_F_TRAIN_MODE) != 0;
+  const uint32_t roff = (uint32_t)job.row_offset;
+  const bool train = (job.flags & OSD_F_TRAIN_MODE) != 0;
   // conditioning is loop-invariant in eval mode (no dropout inside the embedding MLP): hoisted
-  if (gd) OSD_TRY(guided_cond(h, s, *gd, cond + r0 * a.cond_dim, m, cond_stage, ws));
-  else OSD_TRY(run_cond(h, s, cond + r0 * a.cond_dim, m, ws));
-  if (x_T) OSD_HIP(launch_copy2d(s, x_T + r0 * D, D, x, ldx, m, D));
-  else OSD_HIP(launch_fill_randn(s, x, ldx, m, D, seed, roff, (uint32_t)a.T, TAG_POSTERIOR));
-  OSD_HIP(launch_set_int(s, sl.t_dev, S - 1));
+  if (gd) OSD_TRY(guided_cond(h, s, *gd, job.cond, m, cond_stage, ws));
+  else OSD_TRY(run_cond(h, s, job.cond, m, ws));
+  OSD_TRY(chain_init_state(h, s, job, x, ldx, false));
 
-  auto enqueue_step = [&](void) -> int {
+  OSD_TRY(run_steps(sl, S, job.flags, [&](void) -> int {
     TrunkIn in{};
-    in.x = x; in.ldx = ldx; in.kx = ldx; in.n = mt; in.t_dev = sl.t_dev; in.temb = plan.temb; in.in_slabs = in_slabs; in.in_slices = in_slices;
+    in.x = x; in.ldx = ldx; in.kx = ldx; in.n = mt; in.t_dev = sl.t_dev; in.temb = job.plan.temb; in.in_slabs = in_slabs; in.in_slices = in_slices;
     if (gd) { in.guide_m = m; in.cproj0 = ws.cproj + m * a.H0; }
     in.gn_slabs = in_slabs; in.gn_slices = gn_slices;
     in.ksplit = in_slices > 1;             // the small-batch mode already trades bit-equality with the chain kernel for latency: long-K layers on two wave groups
-    in.train = train; in.seed = seed; in.row_offset = roff; in.drop_step_dev = sl.t_dev;
+    in.train = train; in.seed = job.seed; in.row_offset = roff; in.drop_step_dev = sl.t_dev;
     OSD_TRY(run_trunk(h, s, ws, in));
     // guidance on the last hidden activation, in place over the conditional rows: output_proj + posterior then run once, on m rows
     if (gd) OSD_HIP(launch_guide_combine(s, ws.out[a.n_blocks - 1], m, a.block_out[a.n_blocks - 1], gd->w));
     GemmArgs g = output_proj_args(h, ws, m, padded);
     EpiPosterior::Args ea{};
-    ea.bias = padded ? h->b_out_packed : h->params[a.pm.out_b]; ea.xin = x; ea.ldx = ldx; ea.xout = x; ea.ldo = ldx; ea.coef = plan.coef;
+    ea.bias = padded ? h->b_out_packed : h->params[a.pm.out_b]; ea.xin = x; ea.ldx = ldx; ea.xout = x; ea.ldo = ldx; ea.coef = job.plan.coef;
     ea.t_dev = sl.t_dev; ea.t_imm = 0;
-    ea.z = noises ? noises + r0 * D : nullptr; ea.ldzz = D; ea.z_step_stride = (long long)n_total * D; ea.t_first = S - 1;
-    ea.seed = seed; ea.row_offset = roff;
-    ea.mut_mask = mut_mask_out ? mut_mask_out + r0 * h->cfg.mutation_dim : nullptr; ea.mutation_dim = h->cfg.mutation_dim;
+    ea.z = job.noises; ea.ldzz = D; ea.z_step_stride = (long long)job.n_total * D; ea.t_first = S - 1;
+    ea.seed = job.seed; ea.row_offset = roff;
+    ea.mut_mask = job.mut_mask_out; ea.mutation_dim = job.mutation_dim;
     if (kn) OSD_HIP(launch_posterior_known(s, g, EpiPosteriorKnown::Args{ea, known, ldk, kn->level}));
     else OSD_HIP(launch_posterior(s, g, ea));
     OSD_HIP(launch_add_int(s, sl.t_dev, -1));
     return OSD_OK;
-  };
-
-  if (flags & OSD_F_GRAPH) {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    OSD_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_step();
-    hipError_t ce = hipStreamEndCapture(s, &graph);
-    if (rc != OSD_OK) { if (graph) { hipError_t e = hipGraphDestroy(graph); (void)e; } return rc; }
-    OSD_HIP(ce);
-    OSD_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    // the exec object must outlive its launches: the slot keeps it until its next use
-    sl.graph = graph;
-    sl.exec = exec;
-    for (int it = 0; it < S; ++it) OSD_HIP(hipGraphLaunch(exec, s));
-  } else {
-    for (int it = 0; it < S; ++it) OSD_TRY(enqueue_step());
-  }
-  if (padded) OSD_HIP(launch_copy2d(s, x, ldx, x_out + r0 * D, D, m, D));
+  }));
+  if (padded) OSD_HIP(launch_copy2d(s, x, ldx, job.x_out, D, m, D));
   return OSD_OK;
 }
 
-// The reverse chain of `plan` over n rows: osd_sample_chain and osd_sample_chain_steps after their argument checks, chain_check_status
-// and ensure_packed.
-static int sample_plan(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
-                       int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const Guide* gd = nullptr, const Known* kn = nullptr) {
+// The reverse chain of one validated request: sample_request after its argument checks, chain_check_status and ensure_packed.
+static int sample_plan(osd_handle* h, const ChainJob& job) {
+  const int64_t n = job.n;
+  const int flags = job.flags;
+  const bool gd = job.guide.null_cond != nullptr, kn = job.known.known != nullptr;
   // bf16x3 split precision: eval-mode chains on the per-layer launches of split.hip (dropout inside the chain stays fp32)
   const bool split = !gd && !kn && h->precision == 1 && !((flags & OSD_F_TRAIN_MODE) && h->cfg.dropout_p > 0.f);
   h->last_precision = split ? 1 : 0;
-  if (split) OSD_TRY(split_prepare(h, h->stream));
+  if (split) OSD_TRY(split_pack_weights(h, h->stream));
   // a guided chain runs on the per-layer kernels whatever "sampler" says: the chain kernels' tiles are sized for m trunk rows; so does
   // a chain around known values, whose epilogue only the per-layer output_proj launch has
   h->last_engine = (split || gd || kn) ? 0 : chain_pick_engine(h, n, flags);
-  if (h->last_engine == 1 && noises && h->w_out_packed && !chain_uses_squad(h, n)) h->last_engine = 0;      // injected draws at D % 4 != 0: guarded per-layer kernels (the squad chain reads any layout)
+  if (h->last_engine == 1 && job.noises && h->w_out_packed && !chain_uses_squad(h, n)) h->last_engine = 0;      // injected draws at D % 4 != 0: guarded per-layer kernels (the squad chain reads any layout)
   bool fell_back = false;
   if (h->last_engine == 1) {
-    OSD_TRY(chain_run(h, plan, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out));
+    OSD_TRY(chain_run(h, job));
     if (!(flags & OSD_F_SYNC)) return OSD_OK;       // asynchronous: a chain that gives up is reported by the next call on this handle
     int gave_up = 0;
     OSD_TRY(chain_finish(h, &gave_up));
     if (!gave_up) return OSD_OK;
     // models/diffusion.py:427-449 cannot fail: the chain is re-run on the per-layer kernels, which compute the same bits from
     // the same x_T / seed (the chain state lives in x_out, so an aliased x_T is gone)
-    if (x_T == x_out) {
+    if (job.x_T == job.x_out) {
       set_error("the reverse-chain kernel gave up and x_T aliases x_out: nothing left to re-run the chain from");
       return OSD_EHIP;
     }
@@ -901,8 +905,7 @@ static int sample_plan(osd_handle* h, const StepPlan& plan, const float* cond, i
   for (int64_t c = 0; c < n_chunks && rc == OSD_OK; ++c) {
     const int64_t r0 = c * chunk;
     const int64_t m = std::min<int64_t>(chunk, n - r0);
-    if (split) rc = split_chain_chunk(h, plan, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
-    else rc = chain_chunk(h, plan, h->slots[c % n_slots], cond, n, r0, m, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, gd, kn);
+    rc = split ? split_chain_chunk(h, job, h->slots[c % n_slots], r0, m) : chain_chunk(h, job, h->slots[c % n_slots], r0, m);
   }
   // join
   for (int i = 0; i < n_slots; ++i) {
@@ -917,19 +920,6 @@ static int sample_plan(osd_handle* h, const StepPlan& plan, const float* cond, i
     set_error("warning: the reverse-chain kernel gave up in a dependency wait; the chain was re-run on the per-layer kernels (%s)",
               h->last_chain_variant == 3 ? "results agree with the squad chain's to fp32 rounding" : "same results");
   return OSD_OK;
-}
-
-int osd_sample_chain(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
-                     int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
-  OSD_TRY(check_ready(h));
-  OSD_TRY(check_rows(n));
-  if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
-  OSD_TRY(check_row_offset(row_offset, n));
-  if (n == 0) return OSD_OK;
-  OSD_HIP(hipSetDevice(h->cfg.device));
-  OSD_TRY(chain_check_status(h));            // a previous chain-kernel run that gave up is reported here at the latest
-  OSD_TRY(ensure_packed(h, h->stream));
-  return sample_plan(h, StepPlan{h->arch.T, h->d_temb, h->d_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
 }
 
 // The tables of osd_sample_chain_steps' plan, on the handle's stream: coefficients and timesteps uploaded from the handle's host
@@ -971,61 +961,6 @@ static int check_plan(const Arch& a, const int32_t* timesteps, const float* step
   return OSD_OK;
 }
 
-int osd_sample_chain_steps(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
-                           int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
-                           const float* step_coef, int32_t n_steps) {
-  OSD_TRY(check_ready(h));
-  OSD_TRY(check_rows(n));
-  if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
-  OSD_TRY(check_plan(h->arch, timesteps, step_coef, n_steps));
-  OSD_TRY(check_row_offset(row_offset, n));
-  if (n == 0) return OSD_OK;
-  OSD_HIP(hipSetDevice(h->cfg.device));
-  OSD_TRY(chain_check_status(h));
-  OSD_TRY(ensure_packed(h, h->stream));
-  OSD_TRY(upload_plan(h, timesteps, step_coef, n_steps));
-  return sample_plan(h, StepPlan{n_steps, h->plan_temb, h->plan_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
-}
-
-// What both guided entry points refuse; *unguided: guidance_scale == 1 exactly -- the caller takes the unguided entry point's path.
-static int check_guidance(osd_handle* h, const float* null_cond_host, float guidance_scale, int flags, bool* unguided) {
-  if (!std::isfinite(guidance_scale)) { set_error("guidance_scale is not finite"); return OSD_EINVAL; }
-  if (!null_cond_host) { set_error("null_cond is null"); return OSD_EINVAL; }
-  for (int i = 0; i < h->arch.cond_dim; ++i)
-    if (!std::isfinite(null_cond_host[i])) { set_error("null_cond[%d] is not finite", i); return OSD_EINVAL; }
-  *unguided = guidance_scale == 1.0f;
-  if (*unguided) return OSD_OK;
-  if (flags & OSD_F_TRAIN_MODE) { set_error("guided sampling is eval mode only (no dropout inside a guided evaluation)"); return OSD_EINVAL; }
-  if (h->precision == 1) { set_error("precision = bf16x3 does not run guided evaluations: set precision to fp32 or guidance_scale to 1"); return OSD_EUNSUPPORTED; }
-  return OSD_OK;
-}
-
-int osd_sample_chain_guided(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
-                            int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
-                            const float* step_coef, int32_t n_steps, const float* null_cond_host, float guidance_scale) {
-  OSD_TRY(check_ready(h));
-  bool unguided = false;
-  OSD_TRY(check_guidance(h, null_cond_host, guidance_scale, flags, &unguided));
-  if (unguided) {
-    if (!timesteps) return osd_sample_chain(h, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags);
-    return osd_sample_chain_steps(h, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, timesteps, step_coef, n_steps);
-  }
-  OSD_TRY(check_rows(n));
-  if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
-  const Arch& a = h->arch;
-  if (timesteps) OSD_TRY(check_plan(a, timesteps, step_coef, n_steps));
-  OSD_TRY(check_row_offset(row_offset, n));
-  if (n == 0) return OSD_OK;
-  OSD_HIP(hipSetDevice(h->cfg.device));
-  OSD_TRY(chain_check_status(h));
-  OSD_TRY(ensure_packed(h, h->stream));
-  Guide gd{nullptr, guidance_scale};
-  OSD_TRY(upload_null_cond(h, 0, null_cond_host, &gd.null_cond));
-  if (!timesteps) return sample_plan(h, StepPlan{a.T, h->d_temb, h->d_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, &gd);
-  OSD_TRY(upload_plan(h, timesteps, step_coef, n_steps));
-  return sample_plan(h, StepPlan{n_steps, h->plan_temb, h->plan_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, &gd);
-}
-
 // The level table of a chain around known values, host -> handle-owned device table on the handle's stream.  level_host: the plan's
 // [S][2], or null for the DDPM identity plan, whose rows are the schedule's own: (sqrt_ac[s - 1], sqrt_1m_ac[s - 1]), (1, 0) at s = 0.
 static int upload_known_level(osd_handle* h, const float* level_host, int S, const float** dev) {
@@ -1050,77 +985,99 @@ static int upload_known_level(osd_handle* h, const float* level_host, int S, con
   return OSD_OK;
 }
 
+// A reverse-chain request in the caller's terms: what the four osd_sample_chain* entry points receive, absent parts null.
+struct SampleRequest {
+  const float* cond; int64_t n; const float* x_T; const float* noises; uint64_t seed; int64_t row_offset;
+  float* x_out; float* mut_mask_out; int flags;
+  bool need_plan;                 // osd_sample_chain_steps: a step plan is required; elsewhere timesteps == null means the DDPM chain
+  const int32_t* timesteps; const float* step_coef; int32_t n_steps;
+  bool guide;                     // check (and, unless guidance_scale == 1, apply) classifier-free guidance
+  const float* null_cond; float guidance_scale;
+  bool around_known;              // osd_sample_chain_known
+  const float* known; int64_t ld_known; const float* known_level;
+};
+
+// The one path of the osd_sample_chain* entry points: validation (in the order the entry points document: the first bad argument
+// names the error), the device prologue, the request's uploads, the chain.
+static int sample_request(osd_handle* h, const SampleRequest& r) {
+  OSD_TRY(check_ready(h));
+  const Arch& a = h->arch;
+  bool unguided = true;
+  if (r.guide) OSD_TRY(check_guidance(h, r.null_cond, r.guidance_scale, r.flags, &unguided));
+  if (r.around_known && h->precision == 1) { set_error("precision = bf16x3 does not run chains around known values: set precision to fp32"); return OSD_EUNSUPPORTED; }
+  OSD_TRY(check_rows(r.n));
+  if (!r.cond || !r.x_out) { set_error("null tensor"); return OSD_EINVAL; }
+  if (r.around_known) {
+    if (!r.known) { set_error("known is null"); return OSD_EINVAL; }
+    if (r.ld_known < a.D || r.ld_known > 0x7fffffff) { set_error("ld_known=%lld outside [D=%d, 2^31)", (long long)r.ld_known, a.D); return OSD_EINVAL; }
+  }
+  const bool plan = r.need_plan || r.timesteps;
+  if (plan) OSD_TRY(check_plan(a, r.timesteps, r.step_coef, r.n_steps));
+  if (plan && r.around_known) {
+    if (!r.known_level) { set_error("null known_level"); return OSD_EINVAL; }
+    for (int i = 0; i < 2 * r.n_steps; ++i)
+      if (!std::isfinite(r.known_level[i])) { set_error("known_level[%d] is not finite", i); return OSD_EINVAL; }
+    if (r.known_level[0] != 1.f || r.known_level[1] != 0.f) {
+      set_error("known_level[0] = (%g, %g): the last step returns the observations themselves, so it must be (1, 0)", (double)r.known_level[0], (double)r.known_level[1]);
+      return OSD_EINVAL;
+    }
+  }
+  OSD_TRY(check_row_offset(r.row_offset, r.n));
+  if (r.n == 0) return OSD_OK;
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  OSD_TRY(chain_check_status(h));            // a previous chain-kernel run that gave up is reported here at the latest
+  OSD_TRY(ensure_packed(h, h->stream));
+  ChainJob job{};
+  job.plan = StepPlan{a.T, h->d_temb, h->d_coef};
+  job.cond = r.cond; job.n = job.n_total = r.n; job.x_T = r.x_T; job.noises = r.noises; job.seed = r.seed; job.row_offset = r.row_offset;
+  job.x_out = r.x_out; job.mut_mask_out = r.mut_mask_out; job.flags = r.flags;
+  job.D = a.D; job.cond_dim = a.cond_dim; job.mutation_dim = h->cfg.mutation_dim;
+  job.guide.w = r.guidance_scale;
+  if (!unguided) OSD_TRY(upload_null_cond(h, 0, r.null_cond, &job.guide.null_cond));
+  if (r.around_known) {
+    job.known.known = r.known; job.known.ld = r.ld_known;
+    OSD_TRY(upload_known_level(h, plan ? r.known_level : nullptr, plan ? r.n_steps : a.T, &job.known.level));
+  }
+  if (plan) {
+    OSD_TRY(upload_plan(h, r.timesteps, r.step_coef, r.n_steps));
+    job.plan = StepPlan{r.n_steps, h->plan_temb, h->plan_coef};
+  }
+  return sample_plan(h, job);
+}
+
+int osd_sample_chain(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                     int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
+  SampleRequest r{cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags};
+  return sample_request(h, r);
+}
+
+int osd_sample_chain_steps(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                           int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
+                           const float* step_coef, int32_t n_steps) {
+  SampleRequest r{cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, true, timesteps, step_coef, n_steps};
+  return sample_request(h, r);
+}
+
+int osd_sample_chain_guided(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                            int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
+                            const float* step_coef, int32_t n_steps, const float* null_cond_host, float guidance_scale) {
+  SampleRequest r{cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, false, timesteps, step_coef, n_steps,
+                  true, null_cond_host, guidance_scale};
+  return sample_request(h, r);
+}
+
 int osd_sample_chain_known(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
                            int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
                            const float* step_coef, const float* known_level, int32_t n_steps, const float* null_cond_host,
                            float guidance_scale, const float* known, int64_t ld_known) {
-  OSD_TRY(check_ready(h));
-  bool unguided = true;
-  if (null_cond_host) OSD_TRY(check_guidance(h, null_cond_host, guidance_scale, flags, &unguided));
-  if (h->precision == 1) { set_error("precision = bf16x3 does not run chains around known values: set precision to fp32"); return OSD_EUNSUPPORTED; }
-  OSD_TRY(check_rows(n));
-  if (!cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
-  const Arch& a = h->arch;
-  if (!known) { set_error("known is null"); return OSD_EINVAL; }
-  if (ld_known < a.D || ld_known > 0x7fffffff) { set_error("ld_known=%lld outside [D=%d, 2^31)", (long long)ld_known, a.D); return OSD_EINVAL; }
-  if (timesteps) {
-    OSD_TRY(check_plan(a, timesteps, step_coef, n_steps));
-    if (!known_level) { set_error("null known_level"); return OSD_EINVAL; }
-    for (int i = 0; i < 2 * n_steps; ++i)
-      if (!std::isfinite(known_level[i])) { set_error("known_level[%d] is not finite", i); return OSD_EINVAL; }
-    if (known_level[0] != 1.f || known_level[1] != 0.f) {
-      set_error("known_level[0] = (%g, %g): the last step returns the observations themselves, so it must be (1, 0)", (double)known_level[0], (double)known_level[1]);
-      return OSD_EINVAL;
-    }
-  }
-  OSD_TRY(check_row_offset(row_offset, n));
-  if (n == 0) return OSD_OK;
-  OSD_HIP(hipSetDevice(h->cfg.device));
-  OSD_TRY(chain_check_status(h));
-  OSD_TRY(ensure_packed(h, h->stream));
-  Guide gd{nullptr, guidance_scale};
-  if (!unguided) OSD_TRY(upload_null_cond(h, 0, null_cond_host, &gd.null_cond));
-  const Guide* g = unguided ? nullptr : &gd;
-  Known kn{known, ld_known, nullptr};
-  OSD_TRY(upload_known_level(h, timesteps ? known_level : nullptr, timesteps ? n_steps : a.T, &kn.level));
-  if (!timesteps) return sample_plan(h, StepPlan{a.T, h->d_temb, h->d_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, g, &kn);
-  OSD_TRY(upload_plan(h, timesteps, step_coef, n_steps));
-  return sample_plan(h, StepPlan{n_steps, h->plan_temb, h->plan_coef}, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, g, &kn);
+  SampleRequest r{cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, false, timesteps, step_coef, n_steps,
+                  null_cond_host != nullptr, null_cond_host, guidance_scale, true, known, ld_known, known_level};
+  return sample_request(h, r);
 }
 
 int osd_denoiser_forward_guided(osd_handle* h, const float* x, const int32_t* t_index, int32_t t_all, const float* cond, int64_t n,
                                 float* eps, int flags, const float* null_cond_host, float guidance_scale) {
-  OSD_TRY(check_ready(h));
-  bool unguided = false;
-  OSD_TRY(check_guidance(h, null_cond_host, guidance_scale, flags, &unguided));
-  if (unguided) return osd_denoiser_forward(h, x, t_index, t_all, cond, n, eps, flags, nullptr, 0);
-  OSD_TRY(check_rows(n));
-  if (!x || !cond || !eps) { set_error("null tensor"); return OSD_EINVAL; }
-  const Arch& a = h->arch;
-  if (!t_index && (t_all < 0 || t_all >= a.T)) { set_error("t=%d outside [0,%d)", t_all, a.T); return OSD_EINVAL; }
-  if (n == 0) return OSD_OK;
-  OSD_HIP(hipSetDevice(h->cfg.device));
-  hipStream_t s = h->stream;
-  OSD_TRY(ensure_packed(h, s));
-  const int* t_idx = nullptr;
-  OSD_TRY(sanitize_t(h, s, t_index, n, &t_idx));
-  Guide gd{nullptr, guidance_scale};
-  OSD_TRY(upload_null_cond(h, 0, null_cond_host, &gd.null_cond));
-  h->last_precision = 0;
-  FwdWs ws;
-  const int64_t need = align_up(carve_fwd(a, nullptr, 2 * n, false, &ws), 64);
-  OSD_TRY(ensure_arena(&h->main, need + (n + 1) * (int64_t)a.cond_dim));
-  carve_fwd(a, h->main.arena, 2 * n, false, &ws);
-  OSD_TRY(guided_cond(h, s, gd, cond, n, h->main.arena + need, ws));
-  TrunkIn in{};
-  in.x = x; in.ldx = a.D; in.n = 2 * n; in.t_index = t_idx; in.t_imm = t_all;
-  in.guide_m = n; in.cproj0 = ws.cproj + n * a.H0;
-  OSD_TRY(run_trunk(h, s, ws, in));
-  OSD_HIP(launch_guide_combine(s, ws.out[a.n_blocks - 1], n, a.block_out[a.n_blocks - 1], guidance_scale));
-  GemmArgs g = output_proj_args(h, ws, n);
-  OSD_HIP(launch_linear(s, g, true, true, h->params[a.pm.out_b], eps, a.D, false, false));
-  if (flags & OSD_F_SYNC) OSD_HIP(hipStreamSynchronize(s));
-  return OSD_OK;
+  return forward_request(h, ForwardRequest{x, t_index, t_all, cond, n, eps, flags, nullptr, 0, true, null_cond_host, guidance_scale});
 }
 
 int osd_sample_engine(osd_handle* h, int64_t n, int flags) {
@@ -1157,7 +1114,7 @@ int osd_profile_step(osd_handle* h, const float* cond, int64_t n, int reps, floa
   OSD_TRY(ensure_packed(h, s));
   FwdWs ws;
   const int64_t fwd = carve_fwd(a, nullptr, n, false, &ws);
-  const int64_t need = fwd + align_up(n * a.D, 64);
+  const int64_t need = fwd + up64(n * a.D);
   OSD_TRY(ensure_arena(&h->main, need));
   carve_fwd(a, h->main.arena, n, false, &ws);
   float* x = h->main.arena + fwd;

@@ -1,5 +1,6 @@
 // chain.hip -- host side of the persistent reverse-chain kernel (chain.h): eligibility, workspace, launch, status.
 #include <stdlib.h>
+#include <string.h>
 #include <time.h>
 #include <unistd.h>
 #include <algorithm>
@@ -10,8 +11,6 @@
 #include "fwd.h"
 
 namespace osd {
-
-static int64_t up64(int64_t v) { return (v + 63) / 64 * 64; }
 
 // The chain kernel covers the 128 x 128 tile with GroupNorm groups of 32 or 64 channels (block widths 256 / 512, the
 // BASELINE shape and its neighbours) in eval mode; everything else runs on the per-layer kernels.
@@ -26,27 +25,33 @@ bool chain_supported(const Arch& a) {
   return true;
 }
 
-struct ChainDev { int occ = 0; int cus = 0; bool ready = false; };
-static ChainDev g_chain_dev[16];
-
-static int chain_device_limits(int device, int* max_grid) {
+int kernel_slots(KernelSlots* cache, int device, const void* kernel, const void* kernel_diag, int threads, int lds_bytes, int cap, int* max_grid) {
   if (device < 0 || device >= 16) { set_error("device %d out of range", device); return OSD_EINVAL; }
-  ChainDev& d = g_chain_dev[device];
+  KernelSlots& d = cache[device];
   if (!d.ready) {
-    OSD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, CHAIN_LDS_BYTES));
-#ifdef OSD_DIAG
-    OSD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, CHAIN_LDS_BYTES));
-#endif
+    OSD_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    if (kernel_diag) OSD_HIP(hipFuncSetAttribute(kernel_diag, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     int occ = 0;
-    OSD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, chain_kernel<false>, NTHREADS, CHAIN_LDS_BYTES));
+    OSD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds_bytes));
     hipDeviceProp_t prop;
     OSD_HIP(hipGetDeviceProperties(&prop, device));
-    d.occ = occ < CHAIN_WPS ? occ : CHAIN_WPS;      // two 64 KB tiles per CU by design
+    d.occ = std::min(occ, cap);
     d.cus = prop.multiProcessorCount;
     d.ready = true;
   }
   *max_grid = d.occ * d.cus;
   return OSD_OK;
+}
+
+static int chain_device_limits(int device, int* max_grid) {
+  static KernelSlots cache[16];
+#ifdef OSD_DIAG
+  const void* diag = reinterpret_cast<const void*>(chain_kernel<true>);
+#else
+  const void* diag = nullptr;
+#endif
+  return kernel_slots(cache, device, reinterpret_cast<const void*>(chain_kernel<false>), diag, NTHREADS, CHAIN_LDS_BYTES,
+                      CHAIN_WPS /* two 64 KB tiles per CU by design */, max_grid);
 }
 
 // Which chain kernel.  Measured on MI355X (tools/probes/engine_sizes.py, D = 2000, T = 200, M patient-steps/s):
@@ -115,9 +120,7 @@ int chain_pick_engine(osd_handle* h, int64_t n, int flags) {
 int chain_ensure_buf(float** p, int64_t* cap, int64_t floats, hipStream_t s) {
   if (*cap >= floats) return OSD_OK;
   if (*p) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(*p)); *p = nullptr; *cap = 0; }
-  void* q = nullptr;
-  if (hipMalloc(&q, (size_t)floats * 4) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc of %lld bytes failed", (long long)floats * 4); return OSD_ENOMEM; }
-  *p = (float*)q;
+  OSD_TRY(device_alloc((void**)p, (size_t)floats * 4));
   *cap = floats;
   return OSD_OK;
 }
@@ -127,7 +130,7 @@ int chain_ensure_sync(osd_handle* h, int64_t n_tiles, hipStream_t s) {
   const int64_t words = 4 + 2048 + ((n_tiles + 3) / 4) * 4;
   if (h->chain_sync_words < words) {
     if (h->chain_sync) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(h->chain_sync)); h->chain_sync = nullptr; h->chain_sync_words = 0; }
-    if (hipMalloc((void**)&h->chain_sync, (size_t)words * 4) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc failed"); return OSD_ENOMEM; }
+    OSD_TRY(device_alloc((void**)&h->chain_sync, (size_t)words * 4));
     h->chain_sync_words = words;
   }
   OSD_HIP(hipMemsetAsync(h->chain_sync, 0, (size_t)words * 4, s));
@@ -200,27 +203,86 @@ int chain_finish(osd_handle* h, int* gave_up) {
   return OSD_OK;
 }
 
-int chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed, int64_t row_offset,
-              float* x_out, float* mut_mask_out) {
+// ---- host skeleton common to the three chain kernels ----
+int chain_hoist_cond(osd_handle* h, hipStream_t s, const float* cond, int64_t n, int64_t rows_pad, FwdWs* cw) {
+  const int H0 = h->arch.H0;
+  const int64_t c_off_ce2 = up64(n * 64), c_off_cp = c_off_ce2 + up64(n * 64);
+  OSD_TRY(chain_ensure_buf(&h->chain_cond, &h->chain_cond_floats, c_off_cp + up64(rows_pad * H0), s));
+  cw->ce1 = h->chain_cond; cw->ce2 = h->chain_cond + c_off_ce2; cw->cproj = h->chain_cond + c_off_cp;
+  OSD_TRY(run_cond(h, s, cond, n, *cw));
+  if (rows_pad > n) OSD_HIP(hipMemsetAsync(cw->cproj + n * H0, 0, (size_t)(rows_pad - n) * H0 * 4, s));
+  return OSD_OK;
+}
+
+int chain_state(osd_handle* h, hipStream_t s, const ChainJob& job, int state_cols, float** xs) {
+  const int64_t n = job.n;
+  *xs = job.x_out;
+  if (state_cols != job.D) {
+    OSD_TRY(chain_ensure_buf(&h->chain_xpad, &h->chain_xpad_floats, n * (int64_t)state_cols, s));
+    *xs = h->chain_xpad;
+    OSD_HIP(hipMemsetAsync(*xs, 0, (size_t)n * state_cols * 4, s));
+  }
+  return chain_init_state(h, s, job, *xs, state_cols, false);
+}
+
+int chain_state_out(hipStream_t s, const ChainJob& job, int state_cols, const float* xs) {
+  if (state_cols != job.D) OSD_HIP(launch_copy2d(s, xs, state_cols, job.x_out, job.D, job.n, job.D));
+  return OSD_OK;
+}
+
+int chain_args_ring(osd_handle* h, hipStream_t s, int S, size_t bytes) {
+  OSD_HIP(hipStreamSynchronize(s));        // the host copies are about to be rewritten: earlier uploads must have been consumed
+  const int seg = chain_segment_steps(h, S);
+  const size_t need = (size_t)((S + seg - 1) / seg) * bytes;
+  if (h->chain_args_bytes >= need) return OSD_OK;
+  if (h->chain_args_dev) { OSD_HIP(hipFree(h->chain_args_dev)); h->chain_args_dev = nullptr; }
+  free(h->chain_args_host);
+  h->chain_args_bytes = 0;
+  h->chain_args_host = malloc(need);
+  if (!h->chain_args_host) { set_error("out of host memory"); return OSD_ENOMEM; }
+  OSD_TRY(device_alloc(&h->chain_args_dev, need));
+  h->chain_args_bytes = need;
+  return OSD_OK;
+}
+
+int chain_args_upload(osd_handle* h, hipStream_t s, int l, const void* args, size_t bytes, const void** dev) {
+  char* const host = static_cast<char*>(h->chain_args_host) + (size_t)l * bytes;
+  *dev = static_cast<char*>(h->chain_args_dev) + (size_t)l * bytes;
+  memcpy(host, args, bytes);
+  OSD_HIP(hipMemcpyAsync(const_cast<void*>(*dev), host, bytes, hipMemcpyHostToDevice, s));
+  return OSD_OK;
+}
+
+double chain_rounds(int64_t n_tiles, int S, int grid) {
+  const double rounds = (double)((n_tiles * S + grid - 1) / grid);
+  return grid >= n_tiles ? std::max(rounds, (double)S) : rounds;
+}
+
+void chain_launched(osd_handle* h, double expected_ms) {
+  h->chain_pending = true;
+  h->chain_expected_ms = expected_ms;
+}
+
+int chain_run(osd_handle* h, const ChainJob& job) {
   const Arch& a = h->arch;
-  const int S = plan.n_steps, H0 = a.H0;
+  const int S = job.plan.n_steps, H0 = a.H0;
+  const int64_t n = job.n;
   hipStream_t s = h->stream;
   OSD_TRY(chain_check_status(h));
   if (chain_uses_squad(h, n)) {
     h->last_chain_variant = 3;
-    return squad_chain_run(h, plan, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out);
+    return squad_chain_run(h, job);
   }
   if (chain_use_panel(h, n)) {
     h->last_chain_variant = 2;
-    return panel_chain_run(h, plan, cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out);
+    return panel_chain_run(h, job);
   }
   h->last_chain_variant = 1;
   // D % 4 != 0: the kernel works on an internal copy of the state with rows of Dp = roundup(D, 4) floats (pad columns start at
   // zero, meet zero weights in input_proj and get zero eps from the packed output_proj) and the result is copied out at the end
   const bool padded = h->w_out_packed != nullptr;
-  if (padded && noises) { set_error("internal: injected draws with D %% 4 != 0 run on the per-layer kernels"); return OSD_EUNSUPPORTED; }
+  if (padded && job.noises) { set_error("internal: injected draws with D %% 4 != 0 run on the per-layer kernels"); return OSD_EUNSUPPORTED; }
   const int D = padded ? h->Dp : a.D;
-  float* const x_state = padded ? nullptr : x_out;
   int max_grid = 0;
   OSD_TRY(chain_device_limits(h->cfg.device, &max_grid));
   if (max_grid < 1) { set_error("the chain kernel does not fit this device"); return OSD_EUNSUPPORTED; }
@@ -242,10 +304,7 @@ int chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n,
   for (int b = 0; b < a.n_blocks; ++b) {
     width[1 + 2 * b] = a.block_out[b]; def[1 + 2 * b] = 1 + 2 * b; last[1 + 2 * b] = 2 + 2 * b;
     width[2 + 2 * b] = a.block_out[b]; def[2 + 2 * b] = 2 + 2 * b; last[2 + 2 * b] = 3 + 2 * b;     // next block's first half, or output_proj
-    if (a.layers[2 * b].K2 > 0) {
-      const int skip_block = a.n_enc - 1 - (b - a.n_enc - 1);
-      last[2 + 2 * skip_block] = std::max(last[2 + 2 * skip_block], 1 + 2 * b);
-    }
+    if (a.layers[2 * b].K2 > 0) last[2 + 2 * a.skip_of(b)] = std::max(last[2 + 2 * a.skip_of(b)], 1 + 2 * b);
   }
   std::vector<int64_t> boff(nbuf, -1);
   int64_t off = 0;
@@ -270,24 +329,10 @@ int chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n,
   OSD_TRY(chain_ensure_buf(&h->chain_ws, &h->chain_ws_floats, (int64_t)max_grid * off, s));
   ca.ws = h->chain_ws;
 
-  // ---- conditioning for all rows, hoisted out of the chain (loop-invariant in eval mode): ce1, ce2, cproj padded to whole tiles ----
-  const int64_t rows_pad = (int64_t)n_tiles * BP;
-  const int64_t c_off_ce2 = up64(n * 64), c_off_cp = c_off_ce2 + up64(n * 64);
-  OSD_TRY(chain_ensure_buf(&h->chain_cond, &h->chain_cond_floats, c_off_cp + up64(rows_pad * H0), s));
   FwdWs cw;
-  cw.ce1 = h->chain_cond; cw.ce2 = h->chain_cond + c_off_ce2; cw.cproj = h->chain_cond + c_off_cp;
-  OSD_TRY(run_cond(h, s, cond, n, cw));
-  if (rows_pad > n) OSD_HIP(hipMemsetAsync(cw.cproj + n * H0, 0, (size_t)(rows_pad - n) * H0 * 4, s));
-
-  // ---- x_T ----
-  float* xs = x_state;
-  if (padded) {
-    OSD_TRY(chain_ensure_buf(&h->chain_xpad, &h->chain_xpad_floats, n * (int64_t)D, s));
-    xs = h->chain_xpad;
-    OSD_HIP(hipMemsetAsync(xs, 0, (size_t)n * D * 4, s));
-  }
-  if (x_T) OSD_HIP(launch_copy2d(s, x_T, a.D, xs, D, n, a.D));
-  else OSD_HIP(launch_fill_randn(s, xs, D, n, a.D, seed, (uint32_t)row_offset, (uint32_t)a.T, TAG_POSTERIOR));
+  OSD_TRY(chain_hoist_cond(h, s, job.cond, n, (int64_t)n_tiles * BP, &cw));
+  float* xs = nullptr;
+  OSD_TRY(chain_state(h, s, job, D, &xs));
 
   OSD_TRY(chain_ensure_sync(h, n_tiles, s));
   ca.status = h->chain_sync;
@@ -314,10 +359,7 @@ int chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n,
     ChainLayer& A1 = ca.L[nl++];
     A1.A = h->params[l1.w]; A1.lda = l1.K1 + l1.K2; A1.K = l1.K1 + l1.K2; A1.K0 = l1.K2 > 0 ? l1.K1 : l1.K1 + l1.K2; A1.F = l1.N;
     A1.in0 = cur; A1.ld0 = cur_w; A1.in1 = 0; A1.ld1 = 0;
-    if (l1.K2 > 0) {
-      const int skip_block = a.n_enc - 1 - (b - a.n_enc - 1);      // LIFO: decoder j pops encoder n_enc-1-j
-      A1.in1 = o_out[skip_block]; A1.ld1 = a.block_out[skip_block];
-    }
+    if (l1.K2 > 0) { A1.in1 = o_out[a.skip_of(b)]; A1.ld1 = a.block_out[a.skip_of(b)]; }
     A1.out = o_mid[b]; A1.ldo = l1.N; A1.kind = l1.gw == 64 ? CK_GN64 : CK_GN32;
     A1.bias = h->params[l1.b]; A1.gamma = h->params[l1.gamma]; A1.beta = h->params[l1.beta];
     ChainLayer& A2 = ca.L[nl++];
@@ -334,59 +376,36 @@ int chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n,
     L.bias = padded ? h->b_out_packed : h->params[pm.out_b]; L.gamma = nullptr; L.beta = nullptr;
   }
   ca.n_layers = nl;
-  ca.x = xs; ca.D = D; ca.n = (int)n; ca.n_tiles = n_tiles;
-  ca.cproj = cw.cproj; ca.ldc = H0; ca.temb = plan.temb; ca.ldt = H0; ca.coef = plan.coef;
-  ca.z = noises; ca.ldzz = D; ca.z_step_stride = (long long)n * D; ca.z_t_first = S - 1;
-  ca.seed = seed; ca.row_offset = (uint32_t)row_offset;
-  ca.mut_mask = mut_mask_out; ca.mutation_dim = h->cfg.mutation_dim;
+  ca.n_tiles = n_tiles;
+  chain_fill_request(ca, h, job, xs, D, cw.cproj);
 
   // ---- launches: the whole chain in one, or segments of chain_steps_per_launch steps (progress carries over) ----
-  const int seg = h->chain_steps_per_launch > 0 ? h->chain_steps_per_launch : S;
-  const int n_launch = (S + seg - 1) / seg;
-  OSD_HIP(hipStreamSynchronize(s));        // the host copies are about to be rewritten: earlier uploads must have been consumed
-  if (h->chain_args_cap < n_launch) {
-    if (h->chain_args_dev) { OSD_HIP(hipFree(h->chain_args_dev)); h->chain_args_dev = nullptr; }
-    free(h->chain_args_host);
-    h->chain_args_cap = 0;
-    h->chain_args_host = malloc((size_t)n_launch * sizeof(ChainArgs));
-    if (!h->chain_args_host) { set_error("out of host memory"); return OSD_ENOMEM; }
-    if (hipMalloc(&h->chain_args_dev, (size_t)n_launch * sizeof(ChainArgs)) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc failed"); return OSD_ENOMEM; }
-    h->chain_args_cap = n_launch;
-  }
-  ChainArgs* const host_args = static_cast<ChainArgs*>(h->chain_args_host);
-  int launch = 0;
-  for (int done = 0; done < S; done += seg) {
+  OSD_TRY(chain_args_ring(h, s, S, sizeof(ChainArgs)));
+  OSD_TRY(for_each_segment(h, S, [&](int launch, int done, int n_steps) -> int {
     ca.t_first = S - 1 - done;
-    ca.n_steps = std::min(seg, S - done);
+    ca.n_steps = n_steps;
     ca.base_done = (unsigned)done;
     if (done > 0) {                       // per-launch words: the unit queue and the CU arrival counters (status and progress carry over)
       OSD_HIP(hipMemsetAsync(ca.queue, 0, 4, s));
       if (ca.cu_arrivals) OSD_HIP(hipMemsetAsync(ca.cu_arrivals, 0, 2048 * 4, s));
     }
-    // the argument block of this launch: host copy kept alive in the handle, device copy read by the kernel
-    host_args[launch] = ca;
-    const ChainArgs* dargs = static_cast<const ChainArgs*>(h->chain_args_dev) + launch;
-    OSD_HIP(hipMemcpyAsync(const_cast<ChainArgs*>(dargs), &host_args[launch], sizeof(ChainArgs), hipMemcpyHostToDevice, s));
-    ++launch;
+    const void* dev = nullptr;
+    OSD_TRY(chain_args_upload(h, s, launch, &ca, sizeof(ChainArgs), &dev));
+    const ChainArgs* dargs = static_cast<const ChainArgs*>(dev);
 #ifdef OSD_DIAG
     if (ca.stamps) hipLaunchKernelGGL(chain_kernel<true>, dim3(grid), dim3(NTHREADS), CHAIN_LDS_BYTES, s, dargs);
     else
 #endif
     hipLaunchKernelGGL(chain_kernel<false>, dim3(grid), dim3(NTHREADS), CHAIN_LDS_BYTES, s, dargs);
     OSD_HIP(hipGetLastError());
-  }
-  if (padded) OSD_HIP(launch_copy2d(s, xs, D, x_out, a.D, n, a.D));
-  h->chain_pending = true;
+    return OSD_OK;
+  }));
+  OSD_TRY(chain_state_out(s, job, D, xs));
   // run-time estimate for the host's wall-clock budget: a unit (128 rows through every layer) runs at ~0.24 TFLOP/s per
   // resident workgroup when two share a CU (2.8 ms at the BASELINE shape)
-  {
-    double flop_row = 0;
-    for (int l = 0; l < nl; ++l) flop_row += 2.0 * ca.L[l].K * ca.L[l].F;
-    const double unit_ms = 128.0 * flop_row / 0.237e12 * 1e3;
-    double rounds = (double)(((int64_t)n_tiles * S + grid - 1) / grid);
-    if (grid >= n_tiles) rounds = std::max(rounds, (double)S);        // the steps of a tile are serial
-    h->chain_expected_ms = rounds * unit_ms;
-  }
+  double flop_row = 0;
+  for (int l = 0; l < nl; ++l) flop_row += 2.0 * ca.L[l].K * ca.L[l].F;
+  chain_launched(h, chain_rounds(n_tiles, S, grid) * (128.0 * flop_row / 0.237e12 * 1e3));
   return OSD_OK;
 }
 
@@ -402,7 +421,7 @@ void chain_free(osd_handle* h) {
   h->chain_args_dev = nullptr;
   free(h->chain_args_host);
   h->chain_args_host = nullptr;
-  h->chain_args_cap = 0;
+  h->chain_args_bytes = 0;
   (void)e;
   h->chain_ws = h->chain_cond = nullptr;
   h->chain_sync = nullptr;

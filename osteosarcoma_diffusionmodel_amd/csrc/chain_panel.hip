@@ -1,6 +1,6 @@
 // chain_panel.hip -- host side of the LDS-resident reverse-chain kernel (chain_panel.h): fragment-ordered weight copies, the
-// per-layer panel layout, eligibility, launch.  Shares the sync words, the conditioning buffers, the status protocol and the
-// failure handling with chain.hip.
+// per-layer panel layout, eligibility, launch.  Shares the sync words, the status protocol, the failure handling and the host
+// skeleton of a chain (conditioning, state, argument ring, launch segments: fwd.h) with chain.hip.
 #include <stdlib.h>
 #include <algorithm>
 #include <vector>
@@ -89,7 +89,7 @@ static PanelPlan make_plan(const Arch& a, int Dk /* columns of the chain state =
   std::vector<Skip> skip(a.n_blocks);
   for (int b = 0; b < a.n_blocks; ++b)
     if (a.layers[2 * b].K2 > 0) {
-      const int sb = a.n_enc - 1 - (b - a.n_enc - 1);
+      const int sb = a.skip_of(b);
       if (sb < 0 || sb >= a.n_blocks) return p;
       skip[sb].width = a.block_out[sb];
       skip[sb].consumer = b;
@@ -118,7 +118,7 @@ static PanelPlan make_plan(const Arch& a, int Dk /* columns of the chain state =
       L.in_base = cur_base; L.in_ld = cur_ld;
       L.nseg = 1; L.seg[0] = {cur_col, ld.K1 / 8, -1}; L.seg[1] = {0, 0, -1};
       if (ld.K2 > 0) {
-        const int sb = a.n_enc - 1 - (b - a.n_enc - 1);
+        const int sb = a.skip_of(b);
         L.nseg = 2;
         if (skip[sb].kept) {
           if (cur_col != 0 || cur_ld != 516 || ld.K1 != 256) return p;
@@ -180,7 +180,7 @@ int panel_chain_pack(osd_handle* h, hipStream_t s) {
   if (!p.ok) return OSD_OK;
   if (h->panel_wpk_floats < p.wpk_floats) {
     if (h->panel_wpk) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(h->panel_wpk)); h->panel_wpk = nullptr; h->panel_wpk_floats = 0; }
-    if (hipMalloc((void**)&h->panel_wpk, (size_t)p.wpk_floats * 4) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc failed"); return OSD_ENOMEM; }
+    OSD_TRY(device_alloc((void**)&h->panel_wpk, (size_t)p.wpk_floats * 4));
     h->panel_wpk_floats = p.wpk_floats;
   }
   const bool padded = h->w_out_packed != nullptr;
@@ -194,36 +194,20 @@ int panel_chain_pack(osd_handle* h, hipStream_t s) {
       const LayerDesc& ld = a.layers[l - 1];
       w = h->params[ld.w]; ldw = ld.K1 + ld.K2; F = ld.N; K = ld.K1 + ld.K2;
     }
-    const long long total = (long long)p.nfbg[l] * p.L[l].K8 * 64;
-    const int grid = (int)std::min<long long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_pack_fragments, dim3(grid), dim3(256), 0, s, w, ldw, F, K, p.nfbg[l], p.L[l].K8, h->panel_wpk + p.wpk_off[l]);
-    OSD_HIP(hipGetLastError());
+    OSD_HIP(launch_pack_fragments(s, w, ldw, F, K, p.nfbg[l], p.L[l].K8, h->panel_wpk + p.wpk_off[l]));
   }
   h->panel_wpk_valid = true;
   return OSD_OK;
 }
 
-struct PanelDev { int occ = 0; int cus = 0; bool ready = false; };
-static PanelDev g_panel_dev[16];
-
 static int panel_device_limits(int device, int* max_grid) {
-  if (device < 0 || device >= 16) { set_error("device %d out of range", device); return OSD_EINVAL; }
-  PanelDev& d = g_panel_dev[device];
-  if (!d.ready) {
-    OSD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_chain_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS_BYTES));
+  static KernelSlots cache[16];
 #ifdef OSD_DIAG
-    OSD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_chain_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS_BYTES));
+  const void* diag = reinterpret_cast<const void*>(panel_chain_kernel<true>);
+#else
+  const void* diag = nullptr;
 #endif
-    int occ = 0;
-    OSD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, panel_chain_kernel<false>, PC_THREADS, PC_LDS_BYTES));
-    hipDeviceProp_t prop;
-    OSD_HIP(hipGetDeviceProperties(&prop, device));
-    d.occ = occ < 1 ? occ : 1;
-    d.cus = prop.multiProcessorCount;
-    d.ready = true;
-  }
-  *max_grid = d.occ * d.cus;
-  return OSD_OK;
+  return kernel_slots(cache, device, reinterpret_cast<const void*>(panel_chain_kernel<false>), diag, PC_THREADS, PC_LDS_BYTES, 1, max_grid);
 }
 
 int panel_chain_slots(osd_handle* h) {
@@ -231,13 +215,13 @@ int panel_chain_slots(osd_handle* h) {
   return panel_device_limits(h->cfg.device, &g) == OSD_OK ? g : 0;
 }
 
-int panel_chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
-                    int64_t row_offset, float* x_out, float* mut_mask_out) {
+int panel_chain_run(osd_handle* h, const ChainJob& job) {
   const Arch& a = h->arch;
-  const int S = plan.n_steps, H0 = a.H0;
+  const int S = job.plan.n_steps;
+  const int64_t n = job.n;
   hipStream_t s = h->stream;
   const bool padded = h->w_out_packed != nullptr;
-  if (padded && noises) { set_error("internal: injected draws with D %% 4 != 0 run on the per-layer kernels"); return OSD_EUNSUPPORTED; }
+  if (padded && job.noises) { set_error("internal: injected draws with D %% 4 != 0 run on the per-layer kernels"); return OSD_EUNSUPPORTED; }
   const int D = state_cols(h);
   PanelPlan p = make_plan(a, D);
   if (!p.ok) { set_error("internal: the LDS-resident chain is not available for this model"); return OSD_EUNSUPPORTED; }
@@ -254,24 +238,10 @@ int panel_chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int6
   OSD_TRY(chain_ensure_buf(&h->chain_ws, &h->chain_ws_floats, (int64_t)max_grid * p.ws_stride, s));
   pa.ws = h->chain_ws;
 
-  // conditioning for all rows, hoisted (as chain.hip), cproj padded to whole 64-row tiles
-  const int64_t rows_pad = (int64_t)n_tiles * PC_BP;
-  auto up64 = [](int64_t v) { return (v + 63) / 64 * 64; };
-  const int64_t c_off_ce2 = up64(n * 64), c_off_cp = c_off_ce2 + up64(n * 64);
-  OSD_TRY(chain_ensure_buf(&h->chain_cond, &h->chain_cond_floats, c_off_cp + up64(rows_pad * H0), s));
   FwdWs cw;
-  cw.ce1 = h->chain_cond; cw.ce2 = h->chain_cond + c_off_ce2; cw.cproj = h->chain_cond + c_off_cp;
-  OSD_TRY(run_cond(h, s, cond, n, cw));
-  if (rows_pad > n) OSD_HIP(hipMemsetAsync(cw.cproj + n * H0, 0, (size_t)(rows_pad - n) * H0 * 4, s));
-
-  float* xs = padded ? nullptr : x_out;
-  if (padded) {
-    OSD_TRY(chain_ensure_buf(&h->chain_xpad, &h->chain_xpad_floats, n * (int64_t)D, s));
-    xs = h->chain_xpad;
-    OSD_HIP(hipMemsetAsync(xs, 0, (size_t)n * D * 4, s));
-  }
-  if (x_T) OSD_HIP(launch_copy2d(s, x_T, a.D, xs, D, n, a.D));
-  else OSD_HIP(launch_fill_randn(s, xs, D, n, a.D, seed, (uint32_t)row_offset, (uint32_t)a.T, TAG_POSTERIOR));
+  OSD_TRY(chain_hoist_cond(h, s, job.cond, n, (int64_t)n_tiles * PC_BP, &cw));      // cproj padded to whole 64-row tiles
+  float* xs = nullptr;
+  OSD_TRY(chain_state(h, s, job, D, &xs));
 
   OSD_TRY(chain_ensure_sync(h, n_tiles, s));
   pa.status = h->chain_sync;
@@ -293,65 +263,40 @@ int panel_chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int6
     pa.L[l] = L;
   }
   pa.n_layers = p.n_layers;
-  pa.x = xs; pa.ldx = D; pa.D = D; pa.n = (int)n; pa.n_tiles = n_tiles;
-  pa.cproj = cw.cproj; pa.ldc = H0; pa.temb = plan.temb; pa.ldt = H0; pa.coef = plan.coef;
-  pa.z = noises; pa.ldzz = D; pa.z_step_stride = (long long)n * D; pa.z_t_first = S - 1;
-  pa.seed = seed; pa.row_offset = (uint32_t)row_offset;
-  pa.mut_mask = mut_mask_out; pa.mutation_dim = h->cfg.mutation_dim;
+  pa.ldx = D; pa.n_tiles = n_tiles;
+  chain_fill_request(pa, h, job, xs, D, cw.cproj);
   pa.cp_base = p.cp_base; pa.xp_base = p.xp_base;
 
-  const int seg = h->chain_steps_per_launch > 0 ? h->chain_steps_per_launch : S;
-  const int n_launch = (S + seg - 1) / seg;
-  OSD_HIP(hipStreamSynchronize(s));
-  if (h->panel_args_cap < n_launch) {
-    if (h->panel_args_dev) { OSD_HIP(hipFree(h->panel_args_dev)); h->panel_args_dev = nullptr; }
-    free(h->panel_args_host);
-    h->panel_args_cap = 0;
-    h->panel_args_host = malloc((size_t)n_launch * sizeof(PanelArgs));
-    if (!h->panel_args_host) { set_error("out of host memory"); return OSD_ENOMEM; }
-    if (hipMalloc(&h->panel_args_dev, (size_t)n_launch * sizeof(PanelArgs)) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc failed"); return OSD_ENOMEM; }
-    h->panel_args_cap = n_launch;
-  }
-  PanelArgs* const host_args = static_cast<PanelArgs*>(h->panel_args_host);
-  int launch = 0;
-  for (int done = 0; done < S; done += seg) {
+  OSD_TRY(chain_args_ring(h, s, S, sizeof(PanelArgs)));
+  OSD_TRY(for_each_segment(h, S, [&](int launch, int done, int n_steps) -> int {
     pa.t_first = S - 1 - done;
-    pa.n_steps = std::min(seg, S - done);
+    pa.n_steps = n_steps;
     pa.base_done = (unsigned)done;
     if (done > 0) OSD_HIP(hipMemsetAsync(pa.queue, 0, 4, s));
-    host_args[launch] = pa;
-    const PanelArgs* dargs = static_cast<const PanelArgs*>(h->panel_args_dev) + launch;
-    OSD_HIP(hipMemcpyAsync(const_cast<PanelArgs*>(dargs), &host_args[launch], sizeof(PanelArgs), hipMemcpyHostToDevice, s));
-    ++launch;
+    const void* dev = nullptr;
+    OSD_TRY(chain_args_upload(h, s, launch, &pa, sizeof(PanelArgs), &dev));
+    const PanelArgs* dargs = static_cast<const PanelArgs*>(dev);
 #ifdef OSD_DIAG
     if (pa.stamps) hipLaunchKernelGGL(panel_chain_kernel<true>, dim3(grid), dim3(PC_THREADS), PC_LDS_BYTES, s, dargs);
     else
 #endif
     hipLaunchKernelGGL(panel_chain_kernel<false>, dim3(grid), dim3(PC_THREADS), PC_LDS_BYTES, s, dargs);
     OSD_HIP(hipGetLastError());
-  }
-  if (padded) OSD_HIP(launch_copy2d(s, xs, D, x_out, a.D, n, a.D));
-  h->chain_pending = true;
-  {
-    // a unit (64 rows through every layer) alone on its CU: ~0.5 TFLOP/s
-    double flop_row = 0;
-    for (int l = 0; l < p.n_layers; ++l) flop_row += 2.0 * p.L[l].K8 * 8 * p.L[l].F;
-    const double unit_ms = 64.0 * flop_row / 0.5e12 * 1e3;
-    double rounds = (double)(((int64_t)n_tiles * S + grid - 1) / grid);
-    if (grid >= n_tiles) rounds = std::max(rounds, (double)S);
-    h->chain_expected_ms = rounds * unit_ms;
-  }
+    return OSD_OK;
+  }));
+  OSD_TRY(chain_state_out(s, job, D, xs));
+  // a unit (64 rows through every layer) alone on its CU: ~0.5 TFLOP/s
+  double flop_row = 0;
+  for (int l = 0; l < p.n_layers; ++l) flop_row += 2.0 * p.L[l].K8 * 8 * p.L[l].F;
+  chain_launched(h, chain_rounds(n_tiles, S, grid) * (64.0 * flop_row / 0.5e12 * 1e3));
   return OSD_OK;
 }
 
 void panel_chain_free(osd_handle* h) {
   hipError_t e = hipSuccess;
   if (h->panel_wpk) e = hipFree(h->panel_wpk);
-  if (h->panel_args_dev) e = hipFree(h->panel_args_dev);
   (void)e;
-  free(h->panel_args_host);
   h->panel_wpk = nullptr; h->panel_wpk_floats = 0; h->panel_wpk_valid = false;
-  h->panel_args_dev = nullptr; h->panel_args_host = nullptr; h->panel_args_cap = 0;
 }
 
 }  // namespace osd

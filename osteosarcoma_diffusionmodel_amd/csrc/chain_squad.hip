@@ -1,5 +1,6 @@
 // chain_squad.hip -- host side of the small-batch reverse-chain kernel (chain_squad.h): eligibility, fragment-ordered weight
-// copies, the per-panel buffers, launch.  Shares the status word, the conditioning buffers and the failure handling with chain.hip.
+// copies, the per-panel buffers, launch.  Shares the status word, the failure handling and the host skeleton of a chain (conditioning,
+// argument ring, launch segments: fwd.h) with chain.hip.
 #include <stdlib.h>
 #include <algorithm>
 #include <vector>
@@ -53,7 +54,7 @@ static SquadPlan make_plan(const Arch& a, int rp = SQ_RP) {
       if (ld.K1 != cur_w || K % 128 || ld.K1 % 16 || ld.K2 % 16) return p;
       L.K8 = K / kblk; L.F = ld.N; L.in0 = cur; L.n8_0 = ld.K1 / kblk; L.in1 = -1;
       if (ld.K2 > 0) {
-        const int sb = a.n_enc - 1 - (b - a.n_enc - 1);
+        const int sb = a.skip_of(b);
         if (sb < 0 || sb >= b || a.block_out[sb] != ld.K2) return p;
         L.in1 = buf_of_layer[2 * sb + 1];
       }
@@ -72,7 +73,7 @@ static SquadPlan make_plan(const Arch& a, int rp = SQ_RP) {
   p.bias_off = woff; woff += (int64_t)p.T32 * tile;
   p.wpk_floats = woff;
   if (woff * 4 >= (int64_t)1 << 31) return p;                  // byte offsets into the packed weights are ints
-  p.act_floats = (off + 63) / 64 * 64;
+  p.act_floats = up64(off);
   p.ok = true;
   return p;
 }
@@ -179,7 +180,7 @@ static int squad_pack(osd_handle* h, hipStream_t s, const SquadPlan& p, int rp) 
   float*& buf = h->squad_wpk[slot];
   if (h->squad_wpk_floats[slot] < p.wpk_floats) {
     if (buf) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(buf)); buf = nullptr; h->squad_wpk_floats[slot] = 0; }
-    if (hipMalloc((void**)&buf, (size_t)p.wpk_floats * 4) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc failed"); return OSD_ENOMEM; }
+    OSD_TRY(device_alloc((void**)&buf, (size_t)p.wpk_floats * 4));
     h->squad_wpk_floats[slot] = p.wpk_floats;
   }
   for (int l = 0; l < p.n_layers; ++l) {
@@ -196,10 +197,10 @@ static int squad_pack(osd_handle* h, hipStream_t s, const SquadPlan& p, int rp) 
   return OSD_OK;
 }
 
-int squad_chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
-                    int64_t row_offset, float* x_out, float* mut_mask_out) {
+int squad_chain_run(osd_handle* h, const ChainJob& job) {
   const Arch& a = h->arch;
-  const int S = plan.n_steps, H0 = a.H0, D = a.D;
+  const int S = job.plan.n_steps, H0 = a.H0, D = a.D;
+  const int64_t n = job.n;
   hipStream_t s = h->stream;
   const int wpc = squad_wpc(h, n);
   if (wpc < 1) { set_error("internal: %lld rows are more than the squad chain keeps resident", (long long)n); return OSD_EUNSUPPORTED; }
@@ -210,17 +211,10 @@ int squad_chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int6
   if (!h->squad_wpk_valid[slot]) OSD_TRY(squad_pack(h, s, p, rp));
   const int n_panels = (int)((n + rp - 1) / rp);
 
-  // conditioning for all rows, hoisted (as chain.hip)
-  auto up64 = [](int64_t v) { return (v + 63) / 64 * 64; };
-  const int64_t c_off_ce2 = up64(n * 64), c_off_cp = c_off_ce2 + up64(n * 64);
-  OSD_TRY(chain_ensure_buf(&h->chain_cond, &h->chain_cond_floats, c_off_cp + up64(n * H0), s));
   FwdWs cw;
-  cw.ce1 = h->chain_cond; cw.ce2 = h->chain_cond + c_off_ce2; cw.cproj = h->chain_cond + c_off_cp;
-  OSD_TRY(run_cond(h, s, cond, n, cw));
-
+  OSD_TRY(chain_hoist_cond(h, s, job.cond, n, n, &cw));
   // the chain state lives in the caller's rows between launches (any D: the kernel reads and writes it element-wise)
-  if (x_T) { if (x_T != x_out) OSD_HIP(launch_copy2d(s, x_T, D, x_out, D, n, D)); }
-  else OSD_HIP(launch_fill_randn(s, x_out, D, n, D, seed, (uint32_t)row_offset, (uint32_t)a.T, TAG_POSTERIOR));
+  OSD_TRY(chain_init_state(h, s, job, job.x_out, D, true));
 
   SquadArgs sa{};
   const int64_t xs_stride = (int64_t)p.T32 * rp * rp;              // tiles of rp features x rp patients
@@ -248,36 +242,19 @@ int squad_chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int6
   sa.in_off = (int)p.in_off; sa.bias_in = h->params[a.pm.in_b]; sa.H0 = H0;
   sa.out_off = (int)p.out_off; sa.bias_out = h->squad_wpk[slot] + p.bias_off;
   sa.T32 = p.T32; sa.h0_out = p.h0_out; sa.last_in = p.last_in; sa.K8_out = p.K8_out;
-  sa.x = x_out; sa.ldx = D; sa.D = D; sa.n = (int)n;
-  sa.cproj = cw.cproj; sa.ldc = H0; sa.temb = plan.temb; sa.ldt = H0; sa.coef = plan.coef;
-  sa.z = noises; sa.ldzz = D; sa.z_step_stride = (long long)n * D; sa.z_t_first = S - 1;
-  sa.seed = seed; sa.row_offset = (uint32_t)row_offset;
-  sa.mut_mask = mut_mask_out; sa.mutation_dim = h->cfg.mutation_dim;
+  sa.ldx = D;
+  chain_fill_request(sa, h, job, job.x_out, D, cw.cproj);
 
-  const int seg = h->chain_steps_per_launch > 0 ? h->chain_steps_per_launch : S;
-  const int n_launch = (S + seg - 1) / seg;
-  OSD_HIP(hipStreamSynchronize(s));
-  if (h->squad_args_cap < n_launch) {
-    if (h->squad_args_dev) { OSD_HIP(hipFree(h->squad_args_dev)); h->squad_args_dev = nullptr; }
-    free(h->squad_args_host);
-    h->squad_args_cap = 0;
-    h->squad_args_host = malloc((size_t)n_launch * sizeof(SquadArgs));
-    if (!h->squad_args_host) { set_error("out of host memory"); return OSD_ENOMEM; }
-    if (hipMalloc(&h->squad_args_dev, (size_t)n_launch * sizeof(SquadArgs)) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc failed"); return OSD_ENOMEM; }
-    h->squad_args_cap = n_launch;
-  }
-  SquadArgs* const host_args = static_cast<SquadArgs*>(h->squad_args_host);
+  OSD_TRY(chain_args_ring(h, s, S, sizeof(SquadArgs)));
   const int grid = n_panels * SQ_S;
   const int lds = rp == 32 ? sq_lds_bytes(p.n_layers) : sq16_lds_bytes(p.n_layers);
-  int launch = 0;
-  for (int done = 0; done < S; done += seg) {
+  OSD_TRY(for_each_segment(h, S, [&](int launch, int done, int n_steps) -> int {
     sa.t_first = S - 1 - done;
-    sa.n_steps = std::min(seg, S - done);
+    sa.n_steps = n_steps;
     if (done > 0) OSD_HIP(hipMemsetAsync(sa.bar, 0, (size_t)n_panels * 16 * 4, s));      // a launch counts its barriers from zero
-    host_args[launch] = sa;
-    const SquadArgs* dargs = static_cast<const SquadArgs*>(h->squad_args_dev) + launch;
-    OSD_HIP(hipMemcpyAsync(const_cast<SquadArgs*>(dargs), &host_args[launch], sizeof(SquadArgs), hipMemcpyHostToDevice, s));
-    ++launch;
+    const void* dev = nullptr;
+    OSD_TRY(chain_args_upload(h, s, launch, &sa, sizeof(SquadArgs), &dev));
+    const SquadArgs* dargs = static_cast<const SquadArgs*>(dev);
 #ifdef OSD_DIAG
     if (rp == 16) hipLaunchKernelGGL(squad16_chain_kernel<false>, dim3(grid), dim3(SQ_THREADS), lds, s, dargs);
     else if (sa.stamps && wpc == 1) hipLaunchKernelGGL((squad_chain_kernel<1, true>), dim3(grid), dim3(SQ_THREADS), lds, s, dargs);
@@ -290,10 +267,10 @@ int squad_chain_run(osd_handle* h, const StepPlan& plan, const float* cond, int6
     else if (wpc == 2) hipLaunchKernelGGL(squad_chain_kernel<2>, dim3(grid), dim3(SQ_THREADS), lds, s, dargs);
     else hipLaunchKernelGGL(squad_chain_kernel<3>, dim3(grid), dim3(SQ_THREADS), lds, s, dargs);
     OSD_HIP(hipGetLastError());
-  }
-  h->chain_pending = true;
+    return OSD_OK;
+  }));
   h->last_squad_rp = rp;
-  h->chain_expected_ms = (double)S * 0.5 * wpc;       // measured: 0.1-0.2 ms per step; generous (chain.hip multiplies by 10 and adds 2 s)
+  chain_launched(h, (double)S * 0.5 * wpc);       // measured: 0.1-0.2 ms per step; generous (chain.hip multiplies by 10 and adds 2 s)
   return OSD_OK;
 }
 
@@ -486,8 +463,7 @@ int train_squad_backward(osd_handle* h, hipStream_t s, const FwdWs& f, const Tra
       P.accumulate = (b - 1 < a.n_enc) ? 1 : 0;
       P.drop_mode = 0;
       if (l1.K2 > 0) {
-        const int skip_block = a.n_enc - 1 - (b - a.n_enc - 1);
-        P.skip_w_off = pack(h->params[l1.w], Kt, l1.K1, l1.K2, C); P.skip_F = l1.K2; P.skip_out = B.g_out[skip_block];
+        P.skip_w_off = pack(h->params[l1.w], Kt, l1.K1, l1.K2, C); P.skip_F = l1.K2; P.skip_out = B.g_out[a.skip_of(b)];
       }
       (void)lp;
     }
@@ -524,10 +500,7 @@ void squad_chain_free(osd_handle* h) {
     if (h->squad_wpk[i]) e = hipFree(h->squad_wpk[i]);
     h->squad_wpk[i] = nullptr; h->squad_wpk_floats[i] = 0; h->squad_wpk_valid[i] = false;
   }
-  if (h->squad_args_dev) e = hipFree(h->squad_args_dev);
   (void)e;
-  free(h->squad_args_host);
-  h->squad_args_dev = nullptr; h->squad_args_host = nullptr; h->squad_args_cap = 0;
 }
 
 }  // namespace osd

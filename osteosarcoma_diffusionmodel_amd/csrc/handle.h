@@ -28,6 +28,10 @@ void set_error(const char* fmt, ...);
     if (r__ != OSD_OK) return r__;  \
   } while (0)
 
+inline int64_t up64(int64_t v) { return (v + 63) / 64 * 64; }      // buffers are carved in whole 64-float (256-byte) granules
+// hipMalloc that reports: OSD_ENOMEM with the byte count in osd_last_error(), the sticky HIP error cleared
+int device_alloc(void** p, size_t bytes);
+
 // One Linear of the denoiser trunk (with or without GroupNorm+SiLU behind it).
 struct LayerDesc {
   int K1, K2;          // input panel widths (K2 > 0: concat-free decoder input)
@@ -56,6 +60,8 @@ struct Arch {
   std::vector<int> block_out;      // output width of block i
   ParamMap pm;
   int64_t act_floats_per_row;      // forward workspace per row
+  // the encoder block whose output decoder block b concatenates (LIFO: decoder j pops encoder n_enc - 1 - j)
+  int skip_of(int b) const { return n_enc - 1 - (b - n_enc - 1); }
 };
 
 int build_arch(const osd_config& cfg, Arch* a);
@@ -68,6 +74,42 @@ struct StepPlan {
   int n_steps;
   const float* temb;
   const float* coef;
+};
+
+// Classifier-free guidance of a chain / an evaluation (osd_sample_chain_guided): eps = eps(c0) + w * (eps(c) - eps(c0)).
+struct Guide {
+  const float* null_cond;      // dev [cond_dim]; null = unguided
+  float w;
+};
+
+// Known-feature conditioning of a chain (osd_sample_chain_known): observed elements are overwritten after every step (EpiPosteriorKnown).
+struct Known {
+  const float* known;          // dev [n][ld], NaN = free; null = nothing known
+  int64_t ld;
+  const float* level;          // dev [S][2]
+};
+
+// One reverse-chain request, as every sampler engine receives it (api.hip: sample_request fills it from an entry point's arguments).
+struct ChainJob {
+  StepPlan plan;
+  const float* cond; int64_t n; const float* x_T; const float* noises; uint64_t seed; int64_t row_offset;
+  float* x_out; float* mut_mask_out; int flags;
+  Guide guide;
+  Known known;
+  int D, cond_dim, mutation_dim;   // row widths of x_T / noises / x_out, of cond and of mut_mask_out
+  int64_t n_total;                 // rows of the whole request: injected draws of consecutive steps lie n_total * D floats apart
+  // rows [r0, r0 + m) of the request as a job of their own
+  ChainJob chunk(int64_t r0, int64_t m) const {
+    ChainJob c = *this;
+    c.n = m; c.row_offset = row_offset + r0;
+    c.cond = cond + r0 * cond_dim;
+    c.x_out = x_out + r0 * D;
+    if (x_T) c.x_T = x_T + r0 * D;
+    if (noises) c.noises = noises + r0 * D;
+    if (mut_mask_out) c.mut_mask_out = mut_mask_out + r0 * mutation_dim;
+    if (known.known) c.known.known = known.known + r0 * known.ld;
+    return c;
+  }
 };
 
 // Forward activations of one row chunk (all device pointers into one arena).
@@ -166,9 +208,9 @@ struct osd_handle {
   float* chain_ws = nullptr; int64_t chain_ws_floats = 0;
   float* chain_cond = nullptr; int64_t chain_cond_floats = 0;
   unsigned* chain_sync = nullptr; int64_t chain_sync_words = 0;
-  void* chain_args_dev = nullptr;    // device copies of the launches' argument blocks (ChainArgs, chain.h)
-  void* chain_args_host = nullptr;   // host copies of the same (kept alive while their uploads may be pending)
-  int chain_args_cap = 0;
+  // argument blocks of the chain kernels' launches (ChainArgs / PanelArgs / SquadArgs), one per launch of the current chain: device
+  // copies the kernels read and host copies kept alive while their uploads may be pending (chain.hip: chain_args_ring)
+  void* chain_args_dev = nullptr; void* chain_args_host = nullptr; size_t chain_args_bytes = 0;
   bool chain_pending = false;        // a chain was launched whose status word has not been read yet
   unsigned long long chain_spin_budget = 500000000ull;   // osd_set_option("chain_spin_budget"): s_memrealtime ticks (100 MHz) a dependency wait may take (5 s)
   int64_t chain_wall_budget_ms = 0;  // osd_set_option("chain_wall_budget_ms"): host-side budget of a synchronous chain; 0 = 10 x the expected run time + 2 s
@@ -183,14 +225,12 @@ struct osd_handle {
   int last_chain_variant = 0;        // variant the most recent chain-kernel run used (osd_get_option)
   float* panel_wpk = nullptr; int64_t panel_wpk_floats = 0;   // fragment-ordered copies of the weights
   bool panel_wpk_valid = false;      // false after anything that may have changed the parameters: repacked by the next chain
-  void* panel_args_dev = nullptr; void* panel_args_host = nullptr; int panel_args_cap = 0;
   // small-batch variant (chain_squad.h / chain_squad.hip)
   float* squad_wpk[2] = {nullptr, nullptr}; int64_t squad_wpk_floats[2] = {0, 0};      // fragment-ordered weights: [0] 32-patient panels, [1] 16-patient panels
   bool squad_wpk_valid[2] = {false, false};
   int last_squad_rp = 0;             // patients per panel of the squad chain that ran last (osd_get_option "last_squad_panel")
   int train_squad = 2;               // osd_set_option("train_squad"): the training forward trunk as one launch of squads (train_squad.h) from 2 048 rows on
   int squad_panel = 0;               // osd_set_option("squad_panel"): 0 auto (16-patient panels up to one 32-patient workgroup per CU), 16, 32
-  void* squad_args_dev = nullptr; void* squad_args_host = nullptr; int squad_args_cap = 0;
   // bf16x3 split precision (gemm_bf3.h / split.hip)
   int precision = 0;                 // osd_set_option("precision"): 0 fp32 MFMA (default; the reference's arithmetic), 1 bf16x3 split on the bf16 matrix pipe
                                      // (fp32 accuracy, eval-mode sampling / forward of 256 / 512 wide trunks; everything else stays fp32)

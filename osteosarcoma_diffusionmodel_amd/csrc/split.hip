@@ -77,7 +77,7 @@ void split_free(osd_handle* h) {
 }
 
 // weight planes follow the current parameters: rebuilt by the first split-precision call after anything changed them
-static int split_pack_weights(osd_handle* h, hipStream_t s) {
+int split_pack_weights(osd_handle* h, hipStream_t s) {
   const Arch& a = h->arch;
   SplitPlan* p = static_cast<SplitPlan*>(h->split_plan);
   if (!p) {
@@ -86,9 +86,8 @@ static int split_pack_weights(osd_handle* h, hipStream_t s) {
     h->split_plan = p;
     int64_t units = b3_units(a.H0, a.D) + b3_units(a.D, a.block_out[a.n_blocks - 1]);
     for (const LayerDesc& l : a.layers) units += b3_units(l.N, l.K1 + l.K2);
-    void* q = nullptr;
-    if (hipMalloc(&q, (size_t)units * 16) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc of %lld bytes failed", (long long)units * 16); return OSD_ENOMEM; }
-    p->w = (uint4*)q; p->units = units;
+    OSD_TRY(device_alloc((void**)&p->w, (size_t)units * 16));
+    p->units = units;
     int64_t off = 0;
     p->w_in = p->w + off; off += b3_units(a.H0, a.D);
     p->w_layer.clear();
@@ -115,7 +114,6 @@ struct SplitWs {
   uint4* xpl; uint4* h0;
   std::vector<uint4*> mid, out;
 };
-static int64_t up64(int64_t v) { return (v + 63) / 64 * 64; }
 static int64_t carve_split(const Arch& a, float* base, int64_t n, SplitWs* ws) {
   int64_t off = 0;
   auto take = [&](int64_t floats) { float* q = base ? base + off : nullptr; off += up64(floats); return q; };
@@ -145,16 +143,11 @@ static int split_trunk(osd_handle* h, hipStream_t s, const SplitWs& ws, int64_t 
     OSD_HIP(launch_b3<EpiB3Input>(s, g, ea));
   }
   const uint4* cur = ws.h0;
-  int cur_w = a.H0;
   for (int b = 0; b < a.n_blocks; ++b) {
     const LayerDesc& l1 = a.layers[2 * b];
     const LayerDesc& l2 = a.layers[2 * b + 1];
     Bf3Args g{p.w_layer[2 * b], b3_nkb(l1.K1 + l1.K2), cur, b3_nkb(l1.K1), nullptr, 0, l1.N, (int)n, nullptr};
-    if (l1.K2 > 0) {
-      const int skip_block = a.n_enc - 1 - (b - a.n_enc - 1);   // LIFO: decoder j pops encoder n_enc-1-j (api.hip: run_trunk)
-      g.B1 = ws.out[skip_block]; g.nkb1 = b3_nkb(a.block_out[skip_block]);
-    }
-    (void)cur_w;
+    if (l1.K2 > 0) { g.B1 = ws.out[a.skip_of(b)]; g.nkb1 = b3_nkb(a.block_out[a.skip_of(b)]); }
     const B3Out o1{ws.mid[b], b3_nkb(l1.N)}, o2{ws.out[b], b3_nkb(l2.N)};
     if (l1.gw == 64) OSD_HIP(launch_b3<EpiB3Gn<64>>(s, g, EpiB3Gn<64>::Args{h->params[l1.b], h->params[l1.gamma], h->params[l1.beta], o1}));
     else OSD_HIP(launch_b3<EpiB3Gn<32>>(s, g, EpiB3Gn<32>::Args{h->params[l1.b], h->params[l1.gamma], h->params[l1.beta], o1}));
@@ -162,7 +155,6 @@ static int split_trunk(osd_handle* h, hipStream_t s, const SplitWs& ws, int64_t 
     if (l2.gw == 64) OSD_HIP(launch_b3<EpiB3Gn<64>>(s, g2, EpiB3Gn<64>::Args{h->params[l2.b], h->params[l2.gamma], h->params[l2.beta], o2}));
     else OSD_HIP(launch_b3<EpiB3Gn<32>>(s, g2, EpiB3Gn<32>::Args{h->params[l2.b], h->params[l2.gamma], h->params[l2.beta], o2}));
     cur = ws.out[b];
-    cur_w = l2.N;
   }
   return OSD_OK;
 }
@@ -213,63 +205,33 @@ int split_p_sample_step(osd_handle* h, const float* x_t, int32_t t, const float*
   return OSD_OK;
 }
 
-static int release_graph(Slot& sl) {
-  if (!sl.exec && !sl.graph) return OSD_OK;
-  OSD_HIP(hipStreamSynchronize(sl.stream));
-  if (sl.exec) OSD_HIP(hipGraphExecDestroy(sl.exec));
-  if (sl.graph) OSD_HIP(hipGraphDestroy(sl.graph));
-  sl.exec = nullptr;
-  sl.graph = nullptr;
-  return OSD_OK;
-}
-
 // One chunk of the reverse chain on one slot: rows [r0, r0 + m).  The fp32 state lives in the caller's output rows.
-int split_chain_chunk(osd_handle* h, const StepPlan& plan, Slot& sl, const float* cond, int64_t n_total, int64_t r0, int64_t m, const float* x_T,
-                      const float* noises, uint64_t seed, int64_t row_offset, float* x_out, float* mut_mask_out, int flags) {
+int split_chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r0, int64_t m) {
   const Arch& a = h->arch;
-  const int D = a.D, S = plan.n_steps;
+  const ChainJob job = whole.chunk(r0, m);
+  const int D = a.D, S = job.plan.n_steps;
   hipStream_t s = sl.stream;
   OSD_TRY(release_graph(sl));
   SplitWs ws;
   const int64_t need = carve_split(a, nullptr, m, &ws);
   OSD_TRY(ensure_arena(&sl, need));
   carve_split(a, sl.arena, m, &ws);
-  float* x = x_out + r0 * D;
-  const uint32_t roff = (uint32_t)(row_offset + r0);
-  OSD_TRY(run_cond(h, s, cond + r0 * a.cond_dim, m, ws.cond));       // loop-invariant in eval mode: hoisted (api.hip: chain_chunk)
-  if (x_T) { if (x_T + r0 * D != x) OSD_HIP(launch_copy2d(s, x_T + r0 * D, D, x, D, m, D)); }
-  else OSD_HIP(launch_fill_randn(s, x, D, m, D, seed, roff, (uint32_t)a.T, TAG_POSTERIOR));
+  float* x = job.x_out;
+  OSD_TRY(run_cond(h, s, job.cond, m, ws.cond));       // loop-invariant in eval mode: hoisted (api.hip: chain_chunk)
+  OSD_TRY(chain_init_state(h, s, job, x, D, true));
   OSD_HIP(launch_pack(s, x, D, m, D, ws.xpl));
-  OSD_HIP(launch_set_int(s, sl.t_dev, S - 1));
-
-  auto enqueue_step = [&](void) -> int {
-    OSD_TRY(split_trunk(h, s, ws, m, SplitStep{nullptr, sl.t_dev, 0, plan.temb}));
+  return run_steps(sl, S, job.flags, [&](void) -> int {
+    OSD_TRY(split_trunk(h, s, ws, m, SplitStep{nullptr, sl.t_dev, 0, job.plan.temb}));
     EpiB3Post::Args ea{};
-    ea.bias = h->params[a.pm.out_b]; ea.x = x; ea.ldx = D; ea.coef = plan.coef; ea.t_dev = sl.t_dev; ea.t_imm = 0;
-    ea.z = noises ? noises + r0 * D : nullptr; ea.ldzz = D; ea.z_step_stride = (long long)n_total * D; ea.t_first = S - 1;
-    ea.seed = seed; ea.row_offset = roff;
-    ea.mut_mask = mut_mask_out ? mut_mask_out + r0 * h->cfg.mutation_dim : nullptr; ea.mutation_dim = h->cfg.mutation_dim;
+    ea.bias = h->params[a.pm.out_b]; ea.x = x; ea.ldx = D; ea.coef = job.plan.coef; ea.t_dev = sl.t_dev; ea.t_imm = 0;
+    ea.z = job.noises; ea.ldzz = D; ea.z_step_stride = (long long)job.n_total * D; ea.t_first = S - 1;
+    ea.seed = job.seed; ea.row_offset = (uint32_t)job.row_offset;
+    ea.mut_mask = job.mut_mask_out; ea.mutation_dim = job.mutation_dim;
     ea.o = B3Out{ws.xpl, b3_nkb(D)};
     OSD_HIP(launch_post(s, split_out_args(h, ws, m), ea));
     OSD_HIP(launch_add_int(s, sl.t_dev, -1));
     return OSD_OK;
-  };
-  if (flags & OSD_F_GRAPH) {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    OSD_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_step();
-    hipError_t ce = hipStreamEndCapture(s, &graph);
-    if (rc != OSD_OK) { if (graph) { hipError_t e = hipGraphDestroy(graph); (void)e; } return rc; }
-    OSD_HIP(ce);
-    OSD_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    sl.graph = graph;
-    sl.exec = exec;
-    for (int it = 0; it < S; ++it) OSD_HIP(hipGraphLaunch(exec, s));
-  } else {
-    for (int it = 0; it < S; ++it) OSD_TRY(enqueue_step());
-  }
-  return OSD_OK;
+  });
 }
 
 // y = x W^T + b on the bf16 matrix pipe (osd_op_linear under precision 1): both operands are split here, per call
@@ -285,7 +247,5 @@ int split_op_linear(osd_handle* h, const float* x, const float* w, const float* 
   OSD_HIP(launch_b3<EpiB3Bias>(s, Bf3Args{pw, nkb, px, nkb, nullptr, 0, N, (int)n, nullptr}, EpiB3Bias::Args{b, y, N}));
   return OSD_OK;
 }
-
-int split_prepare(osd_handle* h, hipStream_t s) { return split_pack_weights(h, s); }
 
 }  // namespace osd

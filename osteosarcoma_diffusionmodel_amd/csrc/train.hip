@@ -11,7 +11,6 @@
 
 namespace osd {
 
-static int64_t align_up64(int64_t v) { return (v + 63) / 64 * 64; }
 static int t_pad(int T) { return (T + 31) / 32 * 32; }
 
 
@@ -44,10 +43,10 @@ static int x_t_stride(const Arch& a, const ConsPlan* cp) { return (cp || a.D % 4
 
 static int64_t carve_train(const Arch& a, float* base, int64_t n, const ConsPlan* cp, TrainWs* w) {
   int64_t off = 0;
-  auto take = [&](int64_t floats) { float* p = base ? base + off : nullptr; off += align_up64(floats); return p; };
+  auto take = [&](int64_t floats) { float* p = base ? base + off : nullptr; off += up64(floats); return p; };
   float* fbase = base;
   const int64_t fwd = carve_fwd(a, fbase, n, true, &w->f);
-  off = align_up64(fwd);
+  off = up64(fwd);
   w->xld = x_t_stride(a, cp);
   w->x_t = take(n * (int64_t)w->xld); w->noise = take(n * a.D); w->d_out = take(n * a.D);
   w->u0 = take(n * 64);
@@ -127,9 +126,7 @@ static int ensure_train_ws(osd_handle* h, hipStream_t s, int64_t n, const ConsPl
   const int64_t need = carve_train(a, nullptr, n, cp, w);
   if (h->train_arena_floats < need) {
     if (h->train_arena) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(h->train_arena)); h->train_arena = nullptr; h->train_arena_floats = 0; }
-    void* p = nullptr;
-    if (hipMalloc(&p, (size_t)need * 4) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc of %lld bytes failed", (long long)need * 4); return OSD_ENOMEM; }
-    h->train_arena = (float*)p;
+    OSD_TRY(device_alloc((void**)&h->train_arena, (size_t)need * 4));
     h->train_arena_floats = need;
   }
   carve_train(a, h->train_arena, n, cp, w);
@@ -377,7 +374,7 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
     const int Kt = l1.K1 + l1.K2;
     const float* xin = (b == 0) ? W.f.h0 : W.f.out[b - 1];
     int skip_block = -1;
-    if (l1.K2 > 0) skip_block = a.n_enc - 1 - (b - a.n_enc - 1);
+    if (l1.K2 > 0) skip_block = a.skip_of(b);
     float* gdst = (b == 0) ? W.g_h0 : W.g_out[b - 1];
     const bool acc = (b >= 1) && (b - 1 < a.n_enc);      // encoder outputs already hold their skip gradient
     if (fuse) {
@@ -559,12 +556,12 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
     x0 = cp ? w.x0_mix : nullptr;
     // condition dropout after the mix: the null condition into the rows that drop theirs, in place (one tiny launch, only when asked for)
     if (cond_drop)
-      OSD_HIP(launch_cond_dropout(s, w.cond_mix, h->d_null_cond + (size_t)(a.cond_dim + 63) / 64 * 64, h->cond_drop_keep, h->cond_drop_p, n,
+      OSD_HIP(launch_cond_dropout(s, w.cond_mix, h->d_null_cond + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n,
                                   a.cond_dim, seed, roff, w.cond_mix));
   } else {
     OSD_HIP(launch_q_sample(s, x0, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, seed, roff, w.x_t, w.noise, t_draw, a.T, w.xld, &zl));
     if (cond_drop) {       // condition dropout of a caller-supplied batch: the replaced rows land in the workspace
-      OSD_HIP(launch_cond_dropout(s, cond, h->d_null_cond + (size_t)(a.cond_dim + 63) / 64 * 64, h->cond_drop_keep, h->cond_drop_p, n, a.cond_dim,
+      OSD_HIP(launch_cond_dropout(s, cond, h->d_null_cond + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n, a.cond_dim,
                                   seed, roff, w.cond_mix));
       cond = w.cond_mix;
     }
