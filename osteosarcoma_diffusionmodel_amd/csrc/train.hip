@@ -148,19 +148,28 @@ static int cond_embed_fwd(osd_handle* h, hipStream_t s, const float* cond, int64
   return OSD_OK;
 }
 
+static void zero_add(ZeroList* zl, float* p, int64_t c) { zl->ptr[zl->n] = p; zl->count[zl->n] = c; ++zl->n; }
+
 // zeroes what the backward accumulates atomically (time-embedding table gradient, the small bias gradients)
 static void add_backward_zeros(const Arch& a, const TrainWs& w, float* const* grads, ZeroList* zl) {
   const ParamMap& pm = a.pm;
-  auto add = [&](float* p, int64_t c) { zl->ptr[zl->n] = p; zl->count[zl->n] = c; ++zl->n; };
-  add(w.g_temb, (int64_t)t_pad(a.T) * a.H0 + COND_BWD_PART_FLOATS);
+  zero_add(zl, w.g_temb, (int64_t)t_pad(a.T) * a.H0 + COND_BWD_PART_FLOATS);
   const int small[] = {pm.ce0_b, pm.ce2_b, pm.in_b, pm.cp_b, pm.tp_b, pm.out_b};
-  for (int i : small) add(grads[i], pm.numel[i]);
-  if (small_wgrad_ok(a.cond_dim, 64, a.cond_dim)) add(grads[pm.ce0_w], pm.numel[pm.ce0_w]);     // k_small_wgrad adds into it
+  for (int i : small) zero_add(zl, grads[i], pm.numel[i]);
+  if (small_wgrad_ok(a.cond_dim, 64, a.cond_dim)) zero_add(zl, grads[pm.ce0_w], pm.numel[pm.ce0_w]);     // k_small_wgrad adds into it
   for (const LayerDesc& l : a.layers) {          // GroupNorm backward adds its per-block column sums atomically
-    add(grads[l.b], pm.numel[l.b]); add(grads[l.gamma], pm.numel[l.gamma]); add(grads[l.beta], pm.numel[l.beta]);
+    zero_add(zl, grads[l.b], pm.numel[l.b]); zero_add(zl, grads[l.gamma], pm.numel[l.gamma]); zero_add(zl, grads[l.beta], pm.numel[l.beta]);
   }
 }
 
+// Does the step's dgrad chain -- everything between the first dgrad (output_proj) and the last (into h0) -- run as one launch of
+// squads (train_squad_bwd.h)?  Single-GPU steps only: bucket events want the per-layer launches, whose weight gradients can
+// be flushed mid-pass.  The one answer serves the forward (the transposed weights ride in its pack launch) and the backward
+// (which consumes them).  train_squad_ok admits only layers of width 256 / 512 in eight groups, i.e. group widths 32 / 64 --
+// exactly those of dgrad_gnbwd_supported -- so squads imply the fused GroupNorm backward; BackwardPass::run checks it.
+static bool squad_backward(const osd_handle* h, int64_t n, bool want_grads, bool want_events) {
+  return want_grads && !want_events && h->train_squad >= 2 && train_squad_ok(h, n);
+}
 
 // the handle's side stream (memory-bound leaves of the backward pass: GroupNorm affine gradients, small weight gradients).
 // Default priority: a LOW-priority stream makes the HIP runtime open a low-priority hardware queue, and streams created later
@@ -173,26 +182,52 @@ static int side_stream(osd_handle* h, hipStream_t* out) {
   return OSD_OK;
 }
 
+// dW[nout][kin] (row stride lddw) = sum over rows of gz[row][nout] x[row][kin], both operands dense; `bias`: a gradient equal to gz's column sums
+static WgPending wg_item(const float* x, int kin, const float* gz, int nout, int64_t rows, float* dw, int lddw, float* bias = nullptr) {
+  return WgPending{x, kin, kin, gz, nout, nout, rows, dw, lddw, {bias, nullptr, nullptr}};
+}
+// dX[n][kin] = gz[n][nout] W[nout][kin], W at row stride ldw, gz dense
+struct DgradOp { const float* w; int ldw, kin; const float* gz; int nout; };
+// one GroupNorm+SiLU(+dropout) layer as its backward sees it: pre-norm activations and statistics in, dL/dz and dL/dy out
+struct GnLayer { const LayerDesc& l; const float* z; const float* stats; float* gz; float* gy; int blk; bool with_drop; };
+// what every variant of one block's backward reads
+struct Block {
+  int b; const LayerDesc& l1; const LayerDesc& l2;
+  int C, Kt;                // width, and input width of the first Linear (main input + skip)
+  const float* xin;         // the block's main input
+  float* gdst; bool acc;    // ... its gradient; an encoder output already holds its skip gradient
+  int skip_block;           // the encoder block whose output is the skip input, or -1
+};
+struct DgradResult {        // an OSD_* code; skip_carried: the launch also produced the skip connection's share
+  int rc; bool skip_carried;
+  DgradResult(int rc_, bool carried = false) : rc(rc_), skip_carried(carried) {}
+};
+
 // The backward pass from dL/d eps_hat (d_out [n][D]) to every parameter gradient (and optionally dL/dx_t), over the
 // activations a training-mode forward left in W.
-static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* x_t, int x_ld, const int* t_idx, const float* cond, int64_t n,
-                         const float* d_out, bool train, const float* const* masks, uint64_t seed, uint32_t roff, float* const* grads,
-                         float* dx_t, void* const* events, float* loss_poison = nullptr) {
-  const Arch& a = h->arch;
-  const ParamMap& pm = a.pm;
-  const int D = a.D;
-  const bool drop = train && h->cfg.dropout_p > 0.f;
-  const int last = a.n_blocks - 1;
-  const int Hl = a.block_out[last];
-  // ---- backward ----
-  // Two streams: the chain  GroupNorm/SiLU backward -> dgrad -> next layer  is the critical path and stays on the
-  // handle's stream; every weight/bias gradient (wgrad, split-K slab sums, column sums) is a leaf and goes to a
-  // lower-priority side stream that fills the CUs the small dgrad launches leave idle.  fork() orders the side
-  // stream behind what the main stream has produced so far; the side stream owns the slab workspace.
-  hipStream_t s2 = s;
-  if (h->train_streams == 2) OSD_TRY(side_stream(h, &s2));
-  size_t ev_used = 0;
-  auto next_event = [&](hipEvent_t* out) -> int {
+// Two streams: the chain  GroupNorm/SiLU backward -> dgrad -> next layer  is the critical path and stays on the
+// handle's stream; every weight/bias gradient (wgrad, split-K slab sums, column sums) is a leaf and goes to a
+// lower-priority side stream that fills the CUs the small dgrad launches leave idle.  fork() orders the side
+// stream behind what the main stream has produced so far; the side stream owns the slab workspace.
+struct BackwardPass {
+  osd_handle* h; const Arch& a; hipStream_t s, s2; TrainWs& W; int64_t n; float* const* grads; void* const* events;
+  const float* const* masks; uint64_t seed; uint32_t roff; bool drop; float keep_scale;
+  bool squads;                         // squad_backward(): the dgrad chain is one launch
+  bool fuse = true;                    // GroupNorm backward inside the dgrad epilogues
+  std::vector<WgPending> pend;         // weight gradients waiting for the next grouped launch
+  std::vector<GnColItem> cols;         // d gamma / d beta column sums waiting for side_leaves()
+  int ev = 0, ev_closed = 0;           // bucket events recorded / buckets complete up to the pending weight gradients
+  int n_flush = 0, n_cols_flush = 0;   // plan slots of the grouped launches / of the column-sum lists
+  size_t ev_used = 0;                  // cursor into the handle's pool of internal events
+  bool s2_slabs_busy = false;          // an immediate split-K weight gradient on the side stream may still be using W.slabs
+  hipEvent_t mid_done = nullptr;       // the side stream is through with the slab workspace
+
+  BackwardPass(osd_handle* h_, hipStream_t s_, TrainWs& W_, int64_t n_, bool train, const float* const* masks_, uint64_t seed_, uint32_t roff_,
+               float* const* grads_, void* const* events_, bool squads_)
+      : h(h_), a(h_->arch), s(s_), s2(s_), W(W_), n(n_), grads(grads_), events(events_), masks(masks_), seed(seed_), roff(roff_),
+        drop(train && h_->cfg.dropout_p > 0.f), keep_scale((float)(1.0 / (1.0 - (double)h_->cfg.dropout_p))), squads(squads_) {}
+
+  int next_event(hipEvent_t* out) {
     if (ev_used == h->ev_pool.size()) {
       hipEvent_t e;
       OSD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -200,102 +235,91 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
     }
     *out = h->ev_pool[ev_used++];
     return OSD_OK;
-  };
-  auto fork = [&]() -> int {          // side stream waits for everything enqueued on the main stream so far
+  }
+  int fork() {          // side stream waits for everything enqueued on the main stream so far
     if (s2 == s) return OSD_OK;
     hipEvent_t e;
     OSD_TRY(next_event(&e));
     OSD_HIP(hipEventRecord(e, s));
     OSD_HIP(hipStreamWaitEvent(s2, e, 0));
     return OSD_OK;
-  };
+  }
+  int join() {          // main stream waits for everything enqueued on the side stream so far
+    hipEvent_t e;
+    OSD_TRY(next_event(&e));
+    OSD_HIP(hipEventRecord(e, s2));
+    OSD_HIP(hipStreamWaitEvent(s, e, 0));
+    return OSD_OK;
+  }
   // Weight gradients are leaves: they are collected and launched as ONE grouped GEMM per flush point (after the decoder +
   // bottleneck half of the backward pass, and at its end) instead of ~17 launches of a few tiles each.  A gradient bucket is
   // final once the flush that carries its weight gradients has been enqueued, so bucket events are recorded there.
-  std::vector<WgPending> pend;
-  int ev = 0, ev_closed = 0, n_flush = 0;
-  bool s2_slabs_busy = false;          // an immediate split-K weight gradient on the side stream may still be using W.slabs
-  auto record = [&] { ++ev_closed; };  // bucket complete up to the pending weight gradients
+  void bucket_closed() { ++ev_closed; }      // bucket complete up to the pending weight gradients
+  int record_closed_buckets(hipStream_t st) {
+    for (; ev < ev_closed; ++ev)
+      if (events) OSD_HIP(hipEventRecord((hipEvent_t)events[ev], st));
+    return OSD_OK;
+  }
   // a weight gradient: deferred to the next grouped launch when eligible, else launched now on the side stream (which then
   // has to see what the main stream produced: each fork costs the main stream a few microseconds, so only then)
-  // b0..b2: bias gradients equal to the column sums of gz (the Linear's own bias and tensors that share it); they ride along
+  // bias[0..2]: bias gradients equal to the column sums of gz (the Linear's own bias and tensors that share it); they ride along
   // with the grouped launch, with the small kernel, or -- immediate GEMM path -- take a column-sum launch
   // (Round 3 also built the whole trunk backward as ONE persistent launch -- dgrad tiles and weight-gradient items as work units
   // ordered by dependency counters.  Parity-green and slower, 800 vs 539 us: a wave streaming fp32 MFMAs starves the co-resident
   // wave's VALU epilogue, so the dgrad chain stretched.  Removed in round 4; the stamps and the verdict are profiles/r03_bwd_persist.md.)
-  auto wg = [&](const float* x, int ldx, int kin, const float* gz, int ldg, int nout, int64_t rows, float* dw, int lddw,
-                float* b0 = nullptr, float* b1 = nullptr, float* b2 = nullptr) -> int {
-    const WgPending wp{x, ldx, kin, gz, ldg, nout, rows, dw, lddw, {b0, b1, b2}};
-    if (kin >= 16 && wgrad_group_ok(wp)) { pend.push_back(wp); h->last_train_path |= OSD_TP_WGRAD_GROUP; return OSD_OK; }
+  int weight_grad(const WgPending& wp) {
+    if (wp.kin >= 16 && wgrad_group_ok(wp)) { pend.push_back(wp); h->last_train_path |= OSD_TP_WGRAD_GROUP; return OSD_OK; }
     h->last_train_path |= OSD_TP_WGRAD_DIRECT;
-    const bool small = small_wgrad_ok(kin, nout, lddw);
+    float* const b0 = wp.bias[0];
+    const bool small = small_wgrad_ok(wp.kin, wp.nout, wp.lddw);
     if (small && !events) {            // a 5 us kernel whose inputs are on the main stream: run it there (no fork, no event)
-      OSD_HIP(wgrad(s, W, x, ldx, kin, gz, ldg, nout, rows, dw, lddw, b0));
+      OSD_HIP(wgrad(s, W, wp.x, wp.ldx, wp.kin, wp.gz, wp.ldg, wp.nout, wp.rows, wp.dw, wp.lddw, b0));
       return OSD_OK;
     }
     OSD_TRY(fork());
-    OSD_HIP(wgrad(s2, W, x, ldx, kin, gz, ldg, nout, rows, dw, lddw, b0));
+    OSD_HIP(wgrad(s2, W, wp.x, wp.ldx, wp.kin, wp.gz, wp.ldg, wp.nout, wp.rows, wp.dw, wp.lddw, b0));
     if (!small && s2 != s) s2_slabs_busy = true;
-    if (b0 && !small) OSD_HIP(launch_colsum(s2, gz, ldg, rows, nout, b0));
-    if (b0 && small && (b1 || b2)) { set_error("internal: shared bias on the small weight-gradient path"); return OSD_EINVAL; }
+    if (b0 && !small) OSD_HIP(launch_colsum(s2, wp.gz, wp.ldg, wp.rows, wp.nout, b0));
+    if (b0 && small && (wp.bias[1] || wp.bias[2])) { set_error("internal: shared bias on the small weight-gradient path"); return OSD_EINVAL; }
     if (b0 && !small)
-      for (float* bx : {b1, b2})
-        if (bx) OSD_HIP(hipMemcpyAsync(bx, b0, (size_t)nout * 4, hipMemcpyDeviceToDevice, s2));
+      for (float* bx : {wp.bias[1], wp.bias[2]})
+        if (bx) OSD_HIP(hipMemcpyAsync(bx, b0, (size_t)wp.nout * 4, hipMemcpyDeviceToDevice, s2));
     return OSD_OK;
-  };
-  // mid-pass flush (data parallel: the decoder half's buckets can go to the wire early): grouped weight gradients on the side
-  // stream, one workgroup per CU walking the list so that the other slot of every CU stays with the dgrad chain of the main
-  // stream (a full-width launch starved it: a 16 us dgrad took 104 us)
-  hipEvent_t mid_done = nullptr;       // the side stream is through with the slab workspace
-  auto flush_mid = [&]() -> int {
-    OSD_TRY(fork());                  // the side stream sees every gz produced so far
-    constexpr int WGRAD_MID_CAP = 256;
-    OSD_TRY(wgrad_group_flush(h, s2, n_flush++, pend, W.slabs, W.slab_floats, s2 != s ? WGRAD_MID_CAP : 0));
-    pend.clear();
-    for (; ev < ev_closed; ++ev)
-      if (events) OSD_HIP(hipEventRecord((hipEvent_t)events[ev], s2));
-    if (s2 != s) { OSD_TRY(next_event(&mid_done)); OSD_HIP(hipEventRecord(mid_done, s2)); }
-    return OSD_OK;
-  };
-  // GroupNorm backward: inside the epilogue of the dgrad that produces the layer's upstream gradient (group widths 32 / 64), or
-  // -- other widths -- as its own pass between the GEMMs
-  bool fuse = true;
-  for (const LayerDesc& l : a.layers) fuse = fuse && dgrad_gnbwd_supported(l.gw);
-  // single-GPU steps: the dgrad chain between the first launch (output_proj) and the last (into h0) as one launch of squads
-  const bool squad_bwd = fuse && !events && W.sq_gact && loss_poison && h->train_squad >= 2 && train_squad_ok(h, n);
-  if (fuse) h->last_train_path |= OSD_TP_FUSED_GN_BWD;
-  if (squad_bwd) h->last_train_path |= OSD_TP_SQUAD_BWD;
-  const float keep_scale = (float)(1.0 / (1.0 - (double)h->cfg.dropout_p));
-  std::vector<GnColItem> cols;
+  }
   // d gamma / d beta of the layers whose backward ran in a dgrad epilogue: memory-bound leaves, one launch per call.  They
   // go to the side stream as soon as the block loop is through (beside the last small GEMMs of the main stream), not next to
   // the grouped weight-gradient launch, whose 512 workgroups would keep them off the CUs until it ends.
-  int n_cols_flush = 0;
-  auto side_leaves = [&](hipStream_t st) -> int {
+  int side_leaves(hipStream_t st) {
     if (!cols.empty()) {
       OSD_TRY(gn_colsums_flush(h, st, 8 + n_cols_flush++, cols));      // plan slots 8.. hold the column-sum lists
       cols.clear();
     }
     return OSD_OK;
-  };
-  auto flush_all = [&](bool mid) -> int {
-    if (mid) {
-      // the events flush_mid() records behind the weight gradients must cover the affine gradients too: those go first
-      if (s2 != s && !cols.empty()) OSD_TRY(fork());
-      OSD_TRY(side_leaves(s2));
-      return flush_mid();
-    }
-    // End of the pass.  The grouped weight-gradient GEMM (the long pole, ~200 us at batch 4096) stays on the MAIN stream: no
-    // stream hop in front of it or between it and the optimizer.  The memory-bound leaves run beside it on the side stream and
-    // are long done when the main stream joins.
+  }
+  // mid-pass flush (data parallel: the decoder half's buckets can go to the wire early): grouped weight gradients on the side
+  // stream, one workgroup per CU walking the list so that the other slot of every CU stays with the dgrad chain of the main
+  // stream (a full-width launch starved it: a 16 us dgrad took 104 us)
+  int flush_mid() {
+    // the events recorded behind the weight gradients must cover the affine gradients too: those go first
+    if (s2 != s && !cols.empty()) OSD_TRY(fork());
+    OSD_TRY(side_leaves(s2));
+    OSD_TRY(fork());                  // the side stream sees every gz produced so far
+    constexpr int WGRAD_MID_CAP = 256;
+    OSD_TRY(wgrad_group_flush(h, s2, n_flush++, pend, W.slabs, W.slab_floats, s2 != s ? WGRAD_MID_CAP : 0));
+    pend.clear();
+    OSD_TRY(record_closed_buckets(s2));
+    if (s2 != s) { OSD_TRY(next_event(&mid_done)); OSD_HIP(hipEventRecord(mid_done, s2)); }
+    return OSD_OK;
+  }
+  // End-of-pass flush.  The grouped weight-gradient GEMM (the long pole, ~200 us at batch 4096) stays on the MAIN stream: no
+  // stream hop in front of it or between it and the optimizer.  The memory-bound leaves run beside it on the side stream and
+  // are long done when the main stream joins.
+  int flush_end() {
     if (s2 != s) {
       if (!cols.empty()) { OSD_TRY(fork()); OSD_TRY(side_leaves(s2)); }
       if (mid_done) OSD_HIP(hipStreamWaitEvent(s, mid_done, 0));     // slab workspace handed back by the mid-pass flush
       if (s2_slabs_busy && !pend.empty()) {                           // ... and by immediate split-K weight gradients (e.g. the
-        hipEvent_t e;                                                 // ConditionalEmbedding's first Linear at cond_dim 8 or 12)
-        OSD_TRY(next_event(&e));
-        OSD_HIP(hipEventRecord(e, s2));
-        OSD_HIP(hipStreamWaitEvent(s, e, 0));
+        OSD_TRY(join());                                              // ConditionalEmbedding's first Linear at cond_dim 8 or 12)
         s2_slabs_busy = false;
       }
     } else {
@@ -303,167 +327,370 @@ static int backward_from(osd_handle* h, hipStream_t s, TrainWs& W, const float* 
     }
     OSD_TRY(wgrad_group_flush(h, s, n_flush++, pend, W.slabs, W.slab_floats, 0));
     pend.clear();
-    if (s2 != s) {
-      hipEvent_t e;
-      OSD_TRY(next_event(&e));
-      OSD_HIP(hipEventRecord(e, s2));
-      OSD_HIP(hipStreamWaitEvent(s, e, 0));
-    }
-    for (; ev < ev_closed; ++ev)
-      if (events) OSD_HIP(hipEventRecord((hipEvent_t)events[ev], s));
-    return OSD_OK;
-  };
-  // dgrad whose epilogue is the GroupNorm+SiLU(+dropout) backward of `ln` (z / stats of that layer): writes dL/dz and dL/dy
-  auto dgrad_fused = [&](const float* w, int ldw, int kin, const float* gz_next, int ldg, int nout, const LayerDesc& ln, const float* z,
-                         const float* stats, float* gz_out, float* gy_buf, bool accumulate, bool with_drop, int blk,
-                         const float* w_skip = nullptr, int kin_skip = 0, float* out_skip = nullptr, bool* skip_done = nullptr,
-                         bool launch = true) -> int {
-    if (!launch) {      // the squad launch (train_squad_bwd.h) has produced gz_out / gy_buf (and the skip share): only the column sums are left to queue
-      if (skip_done && w_skip) *skip_done = true;
-      cols.push_back({gy_buf, kin, z, kin, stats, kin, ln.gw, n, grads[ln.gamma], grads[ln.beta]});
-      return OSD_OK;
-    }
+    if (s2 != s) OSD_TRY(join());
+    return record_closed_buckets(s);
+  }
+
+  GnLayer gn_layer(int b, int half) const {      // half 0: the block's first Linear (dropout sits behind it), 1: its second
+    if (half) return GnLayer{a.layers[2 * b + 1], W.f.z2[b], W.f.st2[b], W.g_z2[b], W.g_out[b], b, false};
+    return GnLayer{a.layers[2 * b], W.f.z1[b], W.f.st1[b], W.g_z1[b], W.g_mid[b], b, drop};
+  }
+  // this layer's d gamma / d beta column sums, from the dL/dy and z that a dgrad epilogue (or the squad launch) has left
+  void queue_colsums(const GnLayer& t, int C) {
+    cols.push_back({t.gy, C, t.z, C, t.stats, C, t.l.gw, n, grads[t.l.gamma], grads[t.l.beta]});
+  }
+  // dgrad whose epilogue is the GroupNorm+SiLU(+dropout) backward of `t` (z / stats of that layer): writes dL/dz and dL/dy.
+  // `skip`: the skip connection's share of the same gz (plain dX = gz W_skip into out_skip) rides in the same launch where the
+  // dual kernel takes the shapes.
+  DgradResult dgrad_gnbwd(const DgradOp& op, const GnLayer& t, bool accumulate, const DgradOp* skip = nullptr, float* out_skip = nullptr) {
     GemmArgs g{};
-    g.A = w; g.lda = ldw; g.B0 = gz_next; g.ldb0 = ldg; g.K0 = nout; g.F = kin; g.P = (int)n; g.K = nout;
+    g.A = op.w; g.lda = op.ldw; g.B0 = op.gz; g.ldb0 = op.nout; g.K0 = op.nout; g.F = op.kin; g.P = (int)n; g.K = op.nout;
     g.ksplit = 1;                          // launch.h: two wave groups where a launch has ~one tile per CU and >= 32 K tiles (the first dgrad)
     GnBwdEpi e{};
-    e.z = z; e.ldz = kin; e.stats = stats; e.gamma = h->params[ln.gamma]; e.beta = h->params[ln.beta];
-    e.gz = gz_out; e.ldg = kin; e.gy = gy_buf; e.ldy = kin; e.accumulate = accumulate ? 1 : 0;
-    e.drop_mode = with_drop ? (masks ? 1 : 2) : 0;
-    e.mask = (with_drop && masks) ? masks[blk] : nullptr; e.ldm = kin; e.keep_scale = keep_scale; e.p_drop = h->cfg.dropout_p;
-    e.seed = seed; e.row_offset = roff; e.step = 0; e.tag = TAG_DROPOUT + (uint32_t)blk;
-    {
-      bool launched = false;
-      if (w_skip) {
-        // the skip connection's share of the same gz (plain dX = gz W_skip) rides in the same launch
-        GemmArgs g2{};
-        g2.A = w_skip; g2.lda = ldw; g2.B0 = gz_next; g2.ldb0 = ldg; g2.K0 = nout; g2.F = kin_skip; g2.P = (int)n; g2.K = nout;
-        const hipError_t de = launch_dgrad_gnbwd_dual(s, g, ln.gw, e, g2, out_skip, kin_skip);
-        if (de == hipSuccess) { launched = true; if (skip_done) *skip_done = true; h->last_train_path |= OSD_TP_DUAL_DGRAD; }
-        else if (de != hipErrorInvalidValue) OSD_HIP(de);
-        else (void)hipGetLastError();
-      }
-      if (!launched) OSD_HIP(launch_dgrad_gnbwd(s, g, ln.gw, e));
+    e.z = t.z; e.ldz = op.kin; e.stats = t.stats; e.gamma = h->params[t.l.gamma]; e.beta = h->params[t.l.beta];
+    e.gz = t.gz; e.ldg = op.kin; e.gy = t.gy; e.ldy = op.kin; e.accumulate = accumulate ? 1 : 0;
+    e.drop_mode = t.with_drop ? (masks ? 1 : 2) : 0;
+    e.mask = (t.with_drop && masks) ? masks[t.blk] : nullptr; e.ldm = op.kin; e.keep_scale = keep_scale; e.p_drop = h->cfg.dropout_p;
+    e.seed = seed; e.row_offset = roff; e.step = 0; e.tag = TAG_DROPOUT + (uint32_t)t.blk;
+    bool carried = false;
+    if (skip) {
+      GemmArgs g2{};
+      g2.A = skip->w; g2.lda = skip->ldw; g2.B0 = skip->gz; g2.ldb0 = skip->nout; g2.K0 = skip->nout; g2.F = skip->kin; g2.P = (int)n; g2.K = skip->nout;
+      const hipError_t de = launch_dgrad_gnbwd_dual(s, g, t.l.gw, e, g2, out_skip, skip->kin);
+      if (de == hipSuccess) { carried = true; h->last_train_path |= OSD_TP_DUAL_DGRAD; }
+      else if (de != hipErrorInvalidValue) OSD_HIP(de);
+      else (void)hipGetLastError();
     }
-    cols.push_back({gy_buf, kin, z, kin, stats, kin, ln.gw, n, grads[ln.gamma], grads[ln.beta]});
+    if (!carried) OSD_HIP(launch_dgrad_gnbwd(s, g, t.l.gw, e));
+    queue_colsums(t, op.kin);
+    return DgradResult(OSD_OK, carried);
+  }
+  int dgrad_plain(const DgradOp& op, float* dx, bool accumulate = false) {      // dX (+)= gz W, no epilogue
+    OSD_HIP(dgrad(s, op.w, op.ldw, op.kin, op.gz, op.nout, op.nout, n, dx, op.kin, accumulate));
     return OSD_OK;
-  };
-  // plain dgrad dX = gz W (no epilogue)
-  auto dgrad_plain = [&](const float* w, int ldw, int kin, const float* gz, int ldg, int nout, float* dx, int lddx) -> int {
-    OSD_HIP(dgrad(s, w, ldw, kin, gz, ldg, nout, n, dx, lddx, false));
-    return OSD_OK;
-  };
-  // output_proj
-  OSD_TRY(wg(W.f.out[last], Hl, Hl, d_out, D, D, n, grads[pm.out_w], Hl, grads[pm.out_b]));
-  record();
-  if (fuse) {
-    const LayerDesc& lz = a.layers[2 * last + 1];
-    OSD_TRY(dgrad_fused(h->params[pm.out_w], Hl, Hl, d_out, D, D, lz, W.f.z2[last], W.f.st2[last], W.g_z2[last], W.g_out[last], false, false, last));
-    if (squad_bwd) {      // every dgrad between this one and the last (into h0) in one launch of squads
+  }
+
+  // output_proj: its weight gradient, the first dgrad, and -- squads -- every dgrad between that one and the last (into h0) in one launch
+  int head(const float* d_out, float* loss_poison) {
+    const ParamMap& pm = a.pm;
+    const int last = a.n_blocks - 1, Hl = a.block_out[last], D = a.D;
+    OSD_TRY(weight_grad(wg_item(W.f.out[last], Hl, d_out, D, n, grads[pm.out_w], Hl, grads[pm.out_b])));
+    bucket_closed();
+    const DgradOp op{h->params[pm.out_w], Hl, Hl, d_out, D};
+    if (!fuse) return dgrad_plain(op, W.g_out[last]);
+    OSD_TRY(dgrad_gnbwd(op, gn_layer(last, 1), false).rc);
+    if (squads) {
       TrainSquadBwdBufs B{W.g_out.data(), W.g_z2.data(), W.g_mid.data(), W.g_z1.data(), W.g_h0, masks, drop, seed, roff};
       OSD_TRY(train_squad_backward(h, s, W.f, B, n, W.sq_gact, W.sq_wpk_t, W.sq_bar2, W.sq_panels, loss_poison));
     }
-  } else {
-    OSD_HIP(dgrad(s, h->params[pm.out_w], Hl, Hl, d_out, D, D, n, W.g_out[last], Hl, false));
+    return OSD_OK;
   }
-
-  for (int b = a.n_blocks - 1; b >= 0; --b) {
+  Block block(int b) const {
     const LayerDesc& l1 = a.layers[2 * b];
-    const LayerDesc& l2 = a.layers[2 * b + 1];
-    const int C = l1.N;
-    const int Kt = l1.K1 + l1.K2;
-    const float* xin = (b == 0) ? W.f.h0 : W.f.out[b - 1];
-    int skip_block = -1;
-    if (l1.K2 > 0) skip_block = a.skip_of(b);
-    float* gdst = (b == 0) ? W.g_h0 : W.g_out[b - 1];
-    const bool acc = (b >= 1) && (b - 1 < a.n_enc);      // encoder outputs already hold their skip gradient
-    if (fuse) {
-      // dL/dz of the second half is in g_z2[b] (left by the dgrad above it); bias gradients ride with the weight gradients
-      bool skip_done = false;
-      OSD_TRY(wg(W.f.mid[b], C, C, W.g_z2[b], C, C, n, grads[l2.w], C, grads[l2.b]));
-      OSD_TRY(dgrad_fused(h->params[l2.w], C, C, W.g_z2[b], C, C, l1, W.f.z1[b], W.f.st1[b], W.g_z1[b], W.g_mid[b], false, drop, b,
-                          nullptr, 0, nullptr, nullptr, !squad_bwd));
-      OSD_TRY(wg(xin, l1.K1, l1.K1, W.g_z1[b], C, C, n, grads[l1.w], Kt, grads[l1.b]));
-      if (l1.K2 > 0) OSD_TRY(wg(W.f.out[skip_block], l1.K2, l1.K2, W.g_z1[b], C, C, n, grads[l1.w] + l1.K1, Kt));
-      record();
-      if (b == a.n_enc && events) OSD_TRY(flush_all(true));
-      if (b == 0) {
-        if (!squad_bwd) OSD_TRY(dgrad_plain(h->params[l1.w], Kt, l1.K1, W.g_z1[b], C, C, gdst, l1.K1));
-      } else {
-        const LayerDesc& lp = a.layers[2 * (b - 1) + 1];      // the layer that produced this block's main input
-        // an encoder output already holds its skip gradient (written by the decoder block that popped it): second dependency
-        OSD_TRY(dgrad_fused(h->params[l1.w], Kt, l1.K1, W.g_z1[b], C, C, lp, W.f.z2[b - 1], W.f.st2[b - 1], W.g_z2[b - 1], W.g_out[b - 1], acc,
-                            false, b - 1, l1.K2 > 0 ? h->params[l1.w] + l1.K1 : nullptr, l1.K2, l1.K2 > 0 ? W.g_out[skip_block] : nullptr, &skip_done,
-                            !squad_bwd));
-      }
-      if (l1.K2 > 0 && !skip_done) OSD_TRY(dgrad_plain(h->params[l1.w] + l1.K1, Kt, l1.K2, W.g_z1[b], C, C, W.g_out[skip_block], l1.K2));
-      continue;
-    }
-    // second half: GroupNorm+SiLU backward, wgrad, dgrad
-    GnBwdArgs ga{};
-    ga.g = W.g_out[b]; ga.z = W.f.z2[b]; ga.stats = W.f.st2[b]; ga.gamma = h->params[l2.gamma]; ga.beta = h->params[l2.beta];
-    ga.gz = W.g_z2[b]; ga.dgamma = grads[l2.gamma]; ga.dbeta = grads[l2.beta]; ga.dbias = grads[l2.b];
-    ga.rows = n; ga.C = C; ga.drop_mode = 0; ga.partials = W.partials; ga.atomic_cols = 0;      // fixed-order partial reduce: deterministic
-    OSD_HIP(launch_gn_silu_bwd(s, l2.gw, ga));
-    OSD_TRY(wg(W.f.mid[b], C, C, W.g_z2[b], C, C, n, grads[l2.w], C));
-    OSD_HIP(dgrad(s, h->params[l2.w], C, C, W.g_z2[b], C, C, n, W.g_mid[b], C, false));
-    // first half (dropout sits behind it)
-    GnBwdArgs gb{};
-    gb.g = W.g_mid[b]; gb.z = W.f.z1[b]; gb.stats = W.f.st1[b]; gb.gamma = h->params[l1.gamma]; gb.beta = h->params[l1.beta];
-    gb.gz = W.g_z1[b]; gb.dgamma = grads[l1.gamma]; gb.dbeta = grads[l1.beta]; gb.dbias = grads[l1.b];
-    gb.rows = n; gb.C = C; gb.partials = W.partials; gb.atomic_cols = 0;
-    gb.drop_mode = drop ? (masks ? 1 : 2) : 0;
-    gb.mask = (drop && masks) ? masks[b] : nullptr; gb.keep_scale = keep_scale; gb.p_drop = h->cfg.dropout_p;
-    gb.seed = seed; gb.row_offset = roff; gb.step = 0; gb.tag = TAG_DROPOUT + (uint32_t)b;
-    OSD_HIP(launch_gn_silu_bwd(s, l1.gw, gb));
-    OSD_TRY(wg(xin, l1.K1, l1.K1, W.g_z1[b], C, C, n, grads[l1.w], Kt));
-    if (l1.K2 > 0) OSD_TRY(wg(W.f.out[skip_block], l1.K2, l1.K2, W.g_z1[b], C, C, n, grads[l1.w] + l1.K1, Kt));
-    record();
-    if (b == a.n_enc && events) OSD_TRY(flush_all(true));    // decoder blocks + bottleneck done: first half of the weight gradients
-    // dgrad into the producer of the main input
-    OSD_HIP(dgrad(s, h->params[l1.w], Kt, l1.K1, W.g_z1[b], C, C, n, gdst, l1.K1, acc));
-    if (l1.K2 > 0) OSD_HIP(dgrad(s, h->params[l1.w] + l1.K1, Kt, l1.K2, W.g_z1[b], C, C, n, W.g_out[skip_block], l1.K2, false));
+    return Block{b, l1, a.layers[2 * b + 1], l1.N, l1.K1 + l1.K2, b == 0 ? W.f.h0 : W.f.out[b - 1], b == 0 ? W.g_h0 : W.g_out[b - 1],
+                 (b >= 1) && (b - 1 < a.n_enc), l1.K2 > 0 ? a.skip_of(b) : -1};
   }
-  // Data parallel (bucket events requested): the encoder blocks' weight gradients go out NOW, in a grouped launch of their own, so
-  // that their buckets' events fire one launch before the end of the pass -- what stays behind the last launch, and so cannot
-  // overlap with any compute of this step, is the final bucket alone (input_proj + the conditioning branch: 2.1 MB of the 10.66 MB
-  // instead of 5.2 MB).  Two grouped launches of ~250 items each fill the machine less well than one of 500 (the work-item list
-  // is re-cut to the launch, wgrad_group.hip), so a single process keeps the one launch.
-  if (events) OSD_TRY(flush_all(false));
+  // The first Linear's weight gradient (main input, skip share) closes the block's bucket.  Data parallel: once the decoder blocks
+  // and the bottleneck are through, the first half of the weight gradients goes out.  Both variants of a block come through
+  // here between dL/dz of the first half and the dgrads into the block's inputs.
+  int first_linear_wgrads(const Block& B, float* dbias) {
+    const LayerDesc& l1 = B.l1;
+    OSD_TRY(weight_grad(wg_item(B.xin, l1.K1, W.g_z1[B.b], B.C, n, grads[l1.w], B.Kt, dbias)));
+    if (l1.K2 > 0) OSD_TRY(weight_grad(wg_item(W.f.out[B.skip_block], l1.K2, W.g_z1[B.b], B.C, n, grads[l1.w] + l1.K1, B.Kt)));
+    bucket_closed();
+    if (B.b == a.n_enc && events) OSD_TRY(flush_mid());
+    return OSD_OK;
+  }
+  // One block, GroupNorm backward in the dgrad epilogues (group widths 32 / 64).  dL/dz of the second half is in g_z2[b] (left by
+  // the dgrad above it); bias gradients ride with the weight gradients.  Squads: their launch has produced every dgrad result
+  // of the chain, only the column sums are left to queue (a block with a skip input is never block 0 there).
+  int block_fused(const Block& B) {
+    const int b = B.b, C = B.C;
+    const LayerDesc& l1 = B.l1;
+    OSD_TRY(weight_grad(wg_item(W.f.mid[b], C, W.g_z2[b], C, n, grads[B.l2.w], C, grads[B.l2.b])));
+    if (squads) queue_colsums(gn_layer(b, 0), C);
+    else OSD_TRY(dgrad_gnbwd(DgradOp{h->params[B.l2.w], C, C, W.g_z2[b], C}, gn_layer(b, 0), false).rc);
+    OSD_TRY(first_linear_wgrads(B, grads[l1.b]));
+    if (squads) {
+      if (b > 0) queue_colsums(gn_layer(b - 1, 1), l1.K1);
+      return OSD_OK;
+    }
+    const DgradOp main{h->params[l1.w], B.Kt, l1.K1, W.g_z1[b], C}, skip{h->params[l1.w] + l1.K1, B.Kt, l1.K2, W.g_z1[b], C};
+    bool skip_open = l1.K2 > 0;
+    if (b == 0) {
+      OSD_TRY(dgrad_plain(main, B.gdst));
+    } else {
+      // into the layer that produced this block's main input; an encoder output already holds its skip gradient (written by
+      // the decoder block that popped it): second dependency
+      const DgradResult r = dgrad_gnbwd(main, gn_layer(b - 1, 1), B.acc, skip_open ? &skip : nullptr, skip_open ? W.g_out[B.skip_block] : nullptr);
+      OSD_TRY(r.rc);
+      if (r.skip_carried) skip_open = false;
+    }
+    if (skip_open) OSD_TRY(dgrad_plain(skip, W.g_out[B.skip_block]));
+    return OSD_OK;
+  }
+  GnBwdArgs gn_bwd_args(const GnLayer& t, int C, bool first_half) const {
+    GnBwdArgs ga{};
+    ga.g = t.gy; ga.z = t.z; ga.stats = t.stats; ga.gamma = h->params[t.l.gamma]; ga.beta = h->params[t.l.beta];
+    ga.gz = t.gz; ga.dgamma = grads[t.l.gamma]; ga.dbeta = grads[t.l.beta]; ga.dbias = grads[t.l.b];
+    ga.rows = n; ga.C = C; ga.partials = W.partials; ga.atomic_cols = 0;      // fixed-order partial reduce: deterministic
+    if (first_half) {                     // dropout sits behind it
+      ga.drop_mode = drop ? (masks ? 1 : 2) : 0;
+      ga.mask = (drop && masks) ? masks[t.blk] : nullptr; ga.keep_scale = keep_scale; ga.p_drop = h->cfg.dropout_p;
+      ga.seed = seed; ga.row_offset = roff; ga.step = 0; ga.tag = TAG_DROPOUT + (uint32_t)t.blk;
+    }
+    return ga;
+  }
+  // One block, GroupNorm backward as its own pass between the GEMMs (other group widths); it produces the bias gradients too
+  int block_gn_standalone(const Block& B) {
+    const int b = B.b, C = B.C;
+    const LayerDesc& l1 = B.l1;
+    // second half: GroupNorm+SiLU backward, wgrad, dgrad
+    OSD_HIP(launch_gn_silu_bwd(s, B.l2.gw, gn_bwd_args(gn_layer(b, 1), C, false)));
+    OSD_TRY(weight_grad(wg_item(W.f.mid[b], C, W.g_z2[b], C, n, grads[B.l2.w], C)));
+    OSD_TRY(dgrad_plain(DgradOp{h->params[B.l2.w], C, C, W.g_z2[b], C}, W.g_mid[b]));
+    // first half
+    OSD_HIP(launch_gn_silu_bwd(s, l1.gw, gn_bwd_args(gn_layer(b, 0), C, true)));
+    OSD_TRY(first_linear_wgrads(B, nullptr));
+    // dgrad into the producer of the main input, and into the skip input
+    OSD_TRY(dgrad_plain(DgradOp{h->params[l1.w], B.Kt, l1.K1, W.g_z1[b], C}, B.gdst, B.acc));
+    if (l1.K2 > 0) OSD_TRY(dgrad_plain(DgradOp{h->params[l1.w] + l1.K1, B.Kt, l1.K2, W.g_z1[b], C}, W.g_out[B.skip_block]));
+    return OSD_OK;
+  }
   // input_proj, time_proj, cond_proj, ConditionalEmbedding  (h0 = x W^T + b + t_emb[t] + c_proj)
   // h0 = x W^T + b_in + (t_emb W_t^T + b_t)[t] + (c W_c^T + b_c): the three biases share one gradient, the column sums of g_h0
   // (Tried: the conditioning branch's backward -- five dependent launches of 5-13 us -- and the affine-gradient column sums on the
   // side stream BESIDE the grouped weight-gradient launch instead of in front of it.  The grouped launch's older waves starve
   // them: k_gn_colsums took 202 us instead of 44 and the side chain ended after the main one -- 1042 vs 988 us per step.  Dropped.)
-  if (s2 != s && !cols.empty()) { OSD_TRY(fork()); OSD_TRY(side_leaves(s2)); }      // every GroupNorm layer's gy / z is final
-  if (dx_t) OSD_HIP(dgrad(s, h->params[pm.in_w], D, D, W.g_h0, a.H0, a.H0, n, dx_t, D, false));
-  OSD_TRY(wg(x_t, x_ld, D, W.g_h0, a.H0, a.H0, n, grads[pm.in_w], D, grads[pm.in_b], grads[pm.cp_b], grads[pm.tp_b]));
-  OSD_TRY(wg(W.f.ce2, 64, 64, W.g_h0, a.H0, a.H0, n, grads[pm.cp_w], 64));
-  // the branch below h0 (scatter into the time table, cond_proj's and the second embedding Linear's dgrads, SiLU backward): one launch
-  const bool cond_fused = h->cond_bwd_fused && cond_bwd_ok(a.H0, W.g_h0, W.u0, W.g_ce2, W.g_u);
-  // ... and, where the first embedding Linear has at most four inputs (k_small_wgrad's case), its weight gradient rides along
-  const bool ce0_fused = cond_fused && a.cond_dim <= 4 && small_wgrad_ok(a.cond_dim, 64, a.cond_dim);
-  if (cond_fused) h->last_train_path |= OSD_TP_COND_BWD;
-  if (ce0_fused) h->last_train_path |= OSD_TP_COND_BWD_CE0;
-  if (cond_fused) {
-    OSD_HIP(launch_cond_bwd(s, W.g_h0, a.H0, t_idx, W.g_temb, h->params[pm.cp_w], h->params[pm.ce2_w], W.u0, n, W.g_ce2, W.g_u,
-                            ce0_fused ? cond : nullptr, a.cond_dim, W.g_temb + (int64_t)t_pad(a.T) * a.H0, grads[pm.ce0_w], grads[pm.ce0_b]));
-  } else {
-    OSD_HIP(launch_scatter_rows(s, W.g_h0, t_idx, n, a.H0, W.g_temb));
-    OSD_HIP(dgrad(s, h->params[pm.cp_w], 64, 64, W.g_h0, a.H0, a.H0, n, W.g_ce2, 64, false));
+  int stem(const float* x_t, int x_ld, const int* t_idx, const float* cond, float* dx_t) {
+    const ParamMap& pm = a.pm;
+    const int D = a.D, H0 = a.H0;
+    if (s2 != s && !cols.empty()) { OSD_TRY(fork()); OSD_TRY(side_leaves(s2)); }      // every GroupNorm layer's gy / z is final
+    if (dx_t) OSD_TRY(dgrad_plain(DgradOp{h->params[pm.in_w], D, D, W.g_h0, H0}, dx_t));
+    WgPending in = wg_item(x_t, D, W.g_h0, H0, n, grads[pm.in_w], D, grads[pm.in_b]);
+    in.ldx = x_ld; in.bias[1] = grads[pm.cp_b]; in.bias[2] = grads[pm.tp_b];
+    OSD_TRY(weight_grad(in));
+    OSD_TRY(weight_grad(wg_item(W.f.ce2, 64, W.g_h0, H0, n, grads[pm.cp_w], 64)));
+    // the branch below h0 (scatter into the time table, cond_proj's and the second embedding Linear's dgrads, SiLU backward): one launch
+    const bool cond_fused = h->cond_bwd_fused && cond_bwd_ok(H0, W.g_h0, W.u0, W.g_ce2, W.g_u);
+    // ... and, where the first embedding Linear has at most four inputs (k_small_wgrad's case), its weight gradient rides along
+    const bool ce0_fused = cond_fused && a.cond_dim <= 4 && small_wgrad_ok(a.cond_dim, 64, a.cond_dim);
+    if (cond_fused) h->last_train_path |= OSD_TP_COND_BWD;
+    if (ce0_fused) h->last_train_path |= OSD_TP_COND_BWD_CE0;
+    if (cond_fused) {
+      OSD_HIP(launch_cond_bwd(s, W.g_h0, H0, t_idx, W.g_temb, h->params[pm.cp_w], h->params[pm.ce2_w], W.u0, n, W.g_ce2, W.g_u,
+                              ce0_fused ? cond : nullptr, a.cond_dim, W.g_temb + (int64_t)t_pad(a.T) * H0, grads[pm.ce0_w], grads[pm.ce0_b]));
+    } else {
+      OSD_HIP(launch_scatter_rows(s, W.g_h0, t_idx, n, H0, W.g_temb));
+      OSD_TRY(dgrad_plain(DgradOp{h->params[pm.cp_w], 64, 64, W.g_h0, H0}, W.g_ce2));
+    }
+    // both tables carry zero rows up to a multiple of 32 (whole K steps of the grouped kernel): they add nothing
+    OSD_TRY(weight_grad(wg_item(h->d_time_emb, a.time_dim, W.g_temb, H0, t_pad(a.T), grads[pm.tp_w], a.time_dim)));
+    OSD_TRY(weight_grad(wg_item(W.f.ce1, 64, W.g_ce2, 64, n, grads[pm.ce2_w], 64, grads[pm.ce2_b])));
+    if (!cond_fused) {
+      OSD_TRY(dgrad_plain(DgradOp{h->params[pm.ce2_w], 64, 64, W.g_ce2, 64}, W.g_ce1));
+      OSD_HIP(launch_silu_bwd(s, W.u0, W.g_ce1, W.g_u, n * 64));
+    }
+    if (!ce0_fused) OSD_TRY(weight_grad(wg_item(cond, a.cond_dim, W.g_u, 64, n, grads[pm.ce0_w], a.cond_dim, grads[pm.ce0_b])));
+    bucket_closed();
+    return OSD_OK;
   }
-  // both tables carry zero rows up to a multiple of 32 (whole K steps of the grouped kernel): they add nothing
-  OSD_TRY(wg(h->d_time_emb, a.time_dim, a.time_dim, W.g_temb, a.H0, a.H0, t_pad(a.T), grads[pm.tp_w], a.time_dim));
-  OSD_TRY(wg(W.f.ce1, 64, 64, W.g_ce2, 64, 64, n, grads[pm.ce2_w], 64, grads[pm.ce2_b]));
-  if (!cond_fused) {
-    OSD_HIP(dgrad(s, h->params[pm.ce2_w], 64, 64, W.g_ce2, 64, 64, n, W.g_ce1, 64, false));
-    OSD_HIP(launch_silu_bwd(s, W.u0, W.g_ce1, W.g_u, n * 64));
+
+  int run(const float* x_t, int x_ld, const int* t_idx, const float* cond, const float* d_out, float* dx_t, float* loss_poison) {
+    if (h->train_streams == 2) OSD_TRY(side_stream(h, &s2));
+    for (const LayerDesc& l : a.layers) fuse = fuse && dgrad_gnbwd_supported(l.gw);
+    if (squads && !fuse) { set_error("internal: squad backward without the fused GroupNorm backward"); return OSD_EINVAL; }
+    if (fuse) h->last_train_path |= OSD_TP_FUSED_GN_BWD;
+    if (squads) h->last_train_path |= OSD_TP_SQUAD_BWD;
+    OSD_TRY(head(d_out, loss_poison));
+    for (int b = a.n_blocks - 1; b >= 0; --b) OSD_TRY(fuse ? block_fused(block(b)) : block_gn_standalone(block(b)));
+    // Data parallel (bucket events requested): the encoder blocks' weight gradients go out NOW, in a grouped launch of their own, so
+    // that their buckets' events fire one launch before the end of the pass -- what stays behind the last launch, and so cannot
+    // overlap with any compute of this step, is the final bucket alone (input_proj + the conditioning branch: 2.1 MB of the 10.66 MB
+    // instead of 5.2 MB).  Two grouped launches of ~250 items each fill the machine less well than one of 500 (the work-item list
+    // is re-cut to the launch, wgrad_group.hip), so a single process keeps the one launch.
+    if (events) OSD_TRY(flush_end());
+    OSD_TRY(stem(x_t, x_ld, t_idx, cond, dx_t));
+    return flush_end();          // ends with the side stream joined: the caller's stream owns every result again
   }
-  if (!ce0_fused) OSD_TRY(wg(cond, a.cond_dim, a.cond_dim, W.g_u, 64, 64, n, grads[pm.ce0_w], a.cond_dim, grads[pm.ce0_b]));
-  record();
-  OSD_TRY(flush_all(false));          // ends with the side stream joined: the caller's stream owns every result again
-  return OSD_OK;
+};
+
+// What the entry points that touch the training workspace share around their own argument checks; each calls the pieces in its own order.
+struct TrainCall {
+  osd_handle* h; int64_t n; int flags;
+  hipStream_t s = nullptr;
+  const int* t_idx = nullptr;          // the caller's t_index clamped into [0, T), or null when none was given
+
+  int begin(bool reset_path) {
+    OSD_TRY(check_ready(h));
+    if (reset_path) h->last_train_path = 0;
+    return check_rows(n);
+  }
+  int check_outputs(void* const* events, int n_events, float* const* grads) const {      // grads may be null (loss only)
+    const int n_buckets = h->arch.n_blocks + 2;
+    if (events && n_events != n_buckets) { set_error("expected %d events (osd_grad_buckets), got %d", n_buckets, n_events); return OSD_EINVAL; }
+    for (int i = 0; grads && i < h->arch.pm.n_params; ++i)
+      if (!grads[i]) { set_error("grads[%d] is null", i); return OSD_EINVAL; }
+    return OSD_OK;
+  }
+  int enter() {
+    OSD_HIP(hipSetDevice(h->cfg.device));
+    s = h->stream;
+    return OSD_OK;
+  }
+  int timesteps(const int32_t* t_index) { return sanitize_t(h, s, t_index, n, &t_idx); }
+  bool train_mode() const { return (flags & OSD_F_TRAIN_MODE) != 0; }
+  int finish() const {
+    if (flags & OSD_F_SYNC) OSD_HIP(hipStreamSynchronize(s));
+    return OSD_OK;
+  }
+};
+
+// "bf16 pipe if precision == 1 and the launcher accepts, else the fp32 launcher" for output_proj + loss (EpiMse or EpiLoss)
+template <class Args>
+static hipError_t launch_on_b3t_or_fp32(osd_handle* h, hipStream_t s, const GemmArgs& g, const Args& ea,
+                                        hipError_t (*b3t)(hipStream_t, const GemmArgs&, const Args&),
+                                        hipError_t (*fp32)(hipStream_t, const GemmArgs&, const Args&)) {
+  // precision = 1: output_proj + loss on the bf16 matrix pipe, operands split where they are staged (gemm_b3t.h)
+  hipError_t e = h->precision == 1 ? b3t(s, g, ea) : hipErrorInvalidValue;
+  if (e == hipSuccess) h->last_train_path |= OSD_TP_MSE_BF16;
+  if (e == hipErrorInvalidValue) { (void)hipGetLastError(); e = fp32(s, g, ea); }
+  return e;
 }
+
+// One osd_train_loss_fwd_bwd call past its argument checks: zero list, forward, loss, constraint terms, backward.
+struct LossStep {
+  TrainCall& tc; osd_handle* h; const Arch& a; hipStream_t s; int64_t n;
+  const float* x0; const float* cond; const float* noise; const float* const* masks; uint64_t seed; uint32_t roff;
+  float* loss_out; float* const* grads; double loss_scale; void* const* events;
+  bool from_src, cond_drop;            // the handle's one-shots (osd_train_batch_source, osd_train_condition_dropout), consumed by this call
+  bool use_pw = false, use_me = false; const ConsPlan* cp = nullptr;
+  bool squads_bwd = false;             // squad_backward()
+  TrainWs w;
+
+  // everything that is accumulated atomically must start at zero: zeroed by the q_sample kernel's own grid
+  int zero_list(ZeroList* zl) {
+    zero_add(zl, loss_out, 1);
+    if (w.sq_bar && train_squad_ok(h, n)) {      // the squads' barrier counters + status words (forward, backward)
+      zero_add(zl, reinterpret_cast<float*>(w.sq_bar), w.sq_panels * 16 + 16);
+      zero_add(zl, reinterpret_cast<float*>(w.sq_bar2), w.sq_panels * 16 + 16);
+    }
+    if (cp) zero_add(zl, h->parts_dev, 3);
+    if (cp && grads) zero_add(zl, w.g_x0, n * (int64_t)a.D);
+    if (grads) add_backward_zeros(a, w, grads, zl);
+    if (zl->n > 128) { set_error("too many parameter tensors"); return OSD_EUNSUPPORTED; }
+    return OSD_OK;
+  }
+  // q_sample (with the gather + mixup of a resident batch, the draw of t and the zeroing) and condition dropout
+  int noised_batch(const ZeroList& zl) {
+    const int D = a.D;
+    // t ~ randint(0, T) is drawn inside q_sample (one launch less) and kept in w.t_idx for the layers that gather by it
+    int* t_draw = nullptr;
+    if (!tc.t_idx) { t_draw = w.t_idx; tc.t_idx = w.t_idx; }
+    const int* t_idx = tc.t_idx;
+    if (from_src) {
+      // rows gathered from the resident dataset, mixed up and noised in one pass; conditions land in the workspace
+      OSD_HIP(launch_q_sample_src(s, h->batch_src, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, a.cond_dim, seed, roff, w.x_t,
+                                  w.noise, t_draw, a.T, w.cond_mix, cp ? w.x0_mix : nullptr, w.xld, &zl));
+      cond = w.cond_mix;
+      x0 = cp ? w.x0_mix : nullptr;
+      // condition dropout after the mix: the null condition into the rows that drop theirs, in place (one tiny launch, only when asked for)
+      if (cond_drop)
+        OSD_HIP(launch_cond_dropout(s, w.cond_mix, h->d_null_cond + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n,
+                                    a.cond_dim, seed, roff, w.cond_mix));
+    } else {
+      OSD_HIP(launch_q_sample(s, x0, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, seed, roff, w.x_t, w.noise, t_draw, a.T, w.xld, &zl));
+      if (cond_drop) {       // condition dropout of a caller-supplied batch: the replaced rows land in the workspace
+        OSD_HIP(launch_cond_dropout(s, cond, h->d_null_cond + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n, a.cond_dim,
+                                    seed, roff, w.cond_mix));
+        cond = w.cond_mix;
+      }
+    }
+    return OSD_OK;
+  }
+  // forward (models/diffusion.py:361-377) up to the last block's output
+  int forward(const int32_t* t_index) {
+    const int D = a.D;
+    ZeroList zl{};
+    OSD_TRY(zero_list(&zl));
+    // x_t rows are padded to whole K steps with zeros when nothing else reads them with the dense stride: input_proj then takes
+    // input_proj.weight as it is (clamped at D) and the per-step packed copy of that weight is not made
+    const bool unpacked = w.xld > D;
+    if (unpacked) h->last_train_path |= OSD_TP_X_PADDED;
+    // the t_emb table (and, unless input_proj reads the weight itself, its padded copy) follow the current parameters
+    OSD_TRY(refresh_derived(h, s, !unpacked));
+    OSD_TRY(tc.timesteps(t_index));
+    OSD_TRY(noised_batch(zl));
+    OSD_TRY(cond_embed_fwd(h, s, cond, n, w));
+    TrunkIn in{};
+    in.x = w.x_t; in.ldx = w.xld; in.kx = unpacked ? w.xld : D; in.a_unpacked = unpacked; in.ksplit = true;
+    in.n = n; in.t_index = tc.t_idx; in.train = tc.train_mode(); in.save = grads != nullptr;
+    in.masks = masks; in.seed = seed; in.row_offset = roff; in.drop_step = 0; in.path = &h->last_train_path;
+    if (!(w.sq_act && train_squad_ok(h, n))) return run_trunk(h, s, w.f, in);
+    h->last_train_path |= OSD_TP_SQUAD_FWD;
+    in.input_only = true;
+    OSD_TRY(run_trunk(h, s, w.f, in));
+    // the step's backward as squads as well: both weight repacks in the forward's launch
+    return train_squad_forward(h, s, w.f, in, w.sq_act, w.sq_wpk, w.sq_bar, w.sq_panels, loss_out, squads_bwd ? w.sq_wpk_t : nullptr);
+  }
+  // output_proj + loss + dL/d eps_hat in one launch
+  int loss() {
+    const int D = a.D;
+    const double count = (double)n * (double)D;
+    GemmArgs g = output_proj_args(h, w.f, n);
+    EpiMse::Args ea{};
+    ea.bias = h->params[a.pm.out_b]; ea.noise = noise ? noise : w.noise; ea.ldn = D;
+    ea.dout = grads ? w.d_out : nullptr; ea.ldd = D; ea.pred = cp ? w.pred : nullptr; ea.ldp = D; ea.loss = loss_out;
+    ea.inv_count = (float)(1.0 / count);
+    if (h->loss_kind == OSD_LOSS_L2 && !h->loss_tw_set) {
+      ea.gscale = (float)(2.0 * (double)loss_scale / count);
+      OSD_HIP(launch_on_b3t_or_fp32(h, s, g, ea, launch_mse_b3t, launch_mse));
+      return OSD_OK;
+    }
+    // osd_set_loss: the same launch with EpiLoss; rho' of l2 is 2 d, of the other kinds rho' itself
+    ea.gscale = (float)((h->loss_kind == OSD_LOSS_L2 ? 2.0 : 1.0) * (double)loss_scale / count);
+    EpiLoss::Args el{};
+    el.m = ea; el.tw = h->loss_tw_set ? h->loss_tw : nullptr; el.t_index = tc.t_idx; el.kind = h->loss_kind; el.delta = h->loss_delta;
+    h->last_train_path |= OSD_TP_LOSS_EPI;
+    OSD_HIP(launch_on_b3t_or_fp32(h, s, g, el, launch_loss_b3t, launch_loss));
+    return OSD_OK;
+  }
+  // constraint terms on x0_hat (models/diffusion.py:405) against the batch's x0; their gradient joins dL/d eps_hat
+  int constraints() {
+    const int D = a.D;
+    const int* t_idx = tc.t_idx;
+    OSD_HIP(hipMemcpyAsync(h->parts_dev, loss_out, 4, hipMemcpyDeviceToDevice, s));
+    OSD_HIP(launch_x0hat(s, w.x_t, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, n, D, w.pred));
+    OSD_HIP(hipMemsetAsync(w.cw.acc, 0, (size_t)w.cw.acc_doubles * 8, s));
+    OSD_HIP(cons_moments(s, w.pred, D, n, D, w.cw.acc, w.cw.mi_r));
+    float* gx = grads ? w.g_x0 : nullptr;
+    if (use_pw)
+      OSD_HIP(cons_pathway(s, *cp, w.cw, w.pred, D, n, D, (float)h->w_pathway, (float)(h->w_pathway * loss_scale), loss_out, h->parts_dev + 1, gx));
+    if (use_me) {
+      OSD_HIP(cons_moments(s, x0, D, n, D, w.cw.acc + 2 * (int64_t)D, w.cw.mi_t));
+      OSD_HIP(cons_mutexpr(s, *cp, w.cw, w.pred, x0, D, n, D, (float)h->w_mutexpr, (float)(h->w_mutexpr * loss_scale), loss_out, h->parts_dev + 2, gx));
+    }
+    if (grads) OSD_HIP(launch_x0hat_bwd(s, w.g_x0, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, n, D, w.d_out));
+    return OSD_OK;
+  }
+  int run(const int32_t* t_index) {
+    use_pw = h->cons.n_pathways > 0 && h->w_pathway != 0.0;
+    use_me = h->cons.n_a > 0 && h->w_mutexpr != 0.0;
+    cp = (use_pw || use_me) ? &h->cons : nullptr;
+    if (cp && n < 2) { set_error("the constraint losses need at least 2 rows"); return OSD_EINVAL; }
+    if (!h->parts_dev) OSD_HIP(hipMalloc((void**)&h->parts_dev, 64));
+    OSD_TRY(ensure_train_ws(h, s, n, cp, &w));
+    h->saved_rows = -1;                    // the workspace no longer matches an osd_denoiser_forward_train call
+    squads_bwd = w.sq_gact && squad_backward(h, n, grads != nullptr, events != nullptr);
+    OSD_TRY(forward(t_index));
+    OSD_TRY(loss());
+    if (cp) OSD_TRY(constraints());
+    if (!grads) return OSD_OK;
+    BackwardPass bp(h, s, w, n, tc.train_mode(), masks, seed, roff, grads, events, squads_bwd);
+    OSD_TRY(bp.run(w.x_t, w.xld, tc.t_idx, cond, w.d_out, nullptr, loss_out));
+    return tc.finish();
+  }
+};
 
 }  // namespace osd
 
@@ -486,148 +713,23 @@ int osd_grad_buckets(const osd_config* cfg, int32_t* first, int32_t* last, int m
   return n;
 }
 
+// checks in order: ready, rows, (one-shots consumed), null tensors, empty batch, row offset, event count, grads[i], then the device
 int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, int64_t n, const int32_t* t_index, const float* noise,
                            const float* const* masks, uint64_t seed, int64_t row_offset, int flags, float* loss_out,
                            float* const* grads, double loss_scale, void* const* events, int n_events) {
-  OSD_TRY(check_ready(h));
-  h->last_train_path = 0;
-  OSD_TRY(check_rows(n));
-  const bool from_src = h && h->have_batch_src;          // one-shot: consumed (or dropped) by this call
-  if (h) h->have_batch_src = false;
-  const bool cond_drop = h && h->have_cond_drop;        // one-shot as well (osd_train_condition_dropout)
-  if (h) h->have_cond_drop = false;
+  TrainCall tc{h, n, flags};
+  OSD_TRY(tc.begin(true));
+  const bool from_src = h->have_batch_src;          // one-shot: consumed (or dropped) by this call
+  h->have_batch_src = false;
+  const bool cond_drop = h->have_cond_drop;        // one-shot as well (osd_train_condition_dropout)
+  h->have_cond_drop = false;
   if ((!from_src && (!x0 || !cond)) || !loss_out) { set_error("null tensor"); return OSD_EINVAL; }
   if (n == 0) { set_error("empty batch"); return OSD_EINVAL; }
   OSD_TRY(check_row_offset(row_offset, n));
-  const Arch& a = h->arch;
-  const ParamMap& pm = a.pm;
-  const int n_buckets = a.n_blocks + 2;
-  if (events && n_events != n_buckets) { set_error("expected %d events (osd_grad_buckets), got %d", n_buckets, n_events); return OSD_EINVAL; }
-  if (grads)
-    for (int i = 0; i < pm.n_params; ++i)
-      if (!grads[i]) { set_error("grads[%d] is null", i); return OSD_EINVAL; }
-  OSD_HIP(hipSetDevice(h->cfg.device));
-  hipStream_t s = h->stream;
-  const bool train = (flags & OSD_F_TRAIN_MODE) != 0;
-  const int D = a.D;
-  const uint32_t roff = (uint32_t)row_offset;
-
-  const bool use_pw = h->cons.n_pathways > 0 && h->w_pathway != 0.0;
-  const bool use_me = h->cons.n_a > 0 && h->w_mutexpr != 0.0;
-  const ConsPlan* cp = (use_pw || use_me) ? &h->cons : nullptr;
-  if (cp && n < 2) { set_error("the constraint losses need at least 2 rows"); return OSD_EINVAL; }
-  if (!h->parts_dev) OSD_HIP(hipMalloc((void**)&h->parts_dev, 64));
-  TrainWs w;
-  OSD_TRY(ensure_train_ws(h, s, n, cp, &w));
-  h->saved_rows = -1;                    // the workspace no longer matches an osd_denoiser_forward_train call
-
-  // ---- everything that is accumulated atomically must start at zero: zeroed by the q_sample kernel's own grid ----
-  ZeroList zl{};
-  {
-    auto add = [&](float* p, int64_t c) { zl.ptr[zl.n] = p; zl.count[zl.n] = c; ++zl.n; };
-    add(loss_out, 1);
-    if (w.sq_bar && train_squad_ok(h, n)) {      // the squads' barrier counters + status words (forward, backward)
-      add(reinterpret_cast<float*>(w.sq_bar), w.sq_panels * 16 + 16);
-      add(reinterpret_cast<float*>(w.sq_bar2), w.sq_panels * 16 + 16);
-    }
-    if (cp) add(h->parts_dev, 3);
-    if (cp && grads) add(w.g_x0, n * (int64_t)D);
-    if (grads) add_backward_zeros(a, w, grads, &zl);
-    if (zl.n > 128) { set_error("too many parameter tensors"); return OSD_EUNSUPPORTED; }
-  }
-
-  // ---- forward (models/diffusion.py:361-377) ----
-  // x_t rows are padded to whole K steps with zeros when nothing else reads them with the dense stride: input_proj then takes
-  // input_proj.weight as it is (clamped at D) and the per-step packed copy of that weight is not made
-  const bool unpacked = w.xld > D;
-  if (unpacked) h->last_train_path |= OSD_TP_X_PADDED;
-  // the t_emb table (and, unless input_proj reads the weight itself, its padded copy) follow the current parameters
-  OSD_TRY(refresh_derived(h, s, !unpacked));
-  const int* t_idx = nullptr;
-  OSD_TRY(sanitize_t(h, s, t_index, n, &t_idx));
-  // t ~ randint(0, T) is drawn inside q_sample (one launch less) and kept in w.t_idx for the layers that gather by it
-  int* t_draw = nullptr;
-  if (!t_idx) { t_draw = w.t_idx; t_idx = w.t_idx; }
-  if (from_src) {
-    // rows gathered from the resident dataset, mixed up and noised in one pass; conditions land in the workspace
-    OSD_HIP(launch_q_sample_src(s, h->batch_src, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, a.cond_dim, seed, roff, w.x_t,
-                                w.noise, t_draw, a.T, w.cond_mix, cp ? w.x0_mix : nullptr, w.xld, &zl));
-    cond = w.cond_mix;
-    x0 = cp ? w.x0_mix : nullptr;
-    // condition dropout after the mix: the null condition into the rows that drop theirs, in place (one tiny launch, only when asked for)
-    if (cond_drop)
-      OSD_HIP(launch_cond_dropout(s, w.cond_mix, h->d_null_cond + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n,
-                                  a.cond_dim, seed, roff, w.cond_mix));
-  } else {
-    OSD_HIP(launch_q_sample(s, x0, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, seed, roff, w.x_t, w.noise, t_draw, a.T, w.xld, &zl));
-    if (cond_drop) {       // condition dropout of a caller-supplied batch: the replaced rows land in the workspace
-      OSD_HIP(launch_cond_dropout(s, cond, h->d_null_cond + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n, a.cond_dim,
-                                  seed, roff, w.cond_mix));
-      cond = w.cond_mix;
-    }
-  }
-  const float* eps_true = noise ? noise : w.noise;
-  OSD_TRY(cond_embed_fwd(h, s, cond, n, w));
-  TrainWs& W = w;
-  TrunkIn in{};
-  in.x = W.x_t; in.ldx = W.xld; in.kx = unpacked ? W.xld : D; in.a_unpacked = unpacked; in.ksplit = true;
-  in.n = n; in.t_index = t_idx; in.train = train; in.save = grads != nullptr;
-  in.masks = masks; in.seed = seed; in.row_offset = roff; in.drop_step = 0; in.path = &h->last_train_path;
-  if (W.sq_act && train_squad_ok(h, n)) {
-    h->last_train_path |= OSD_TP_SQUAD_FWD;
-    in.input_only = true;
-    OSD_TRY(run_trunk(h, s, W.f, in));
-    // the step's backward as squads as well (backward_from's condition): both weight repacks in the forward's launch
-    const bool squad_bwd_next = grads && !events && W.sq_gact && h->train_squad >= 2;
-    OSD_TRY(train_squad_forward(h, s, W.f, in, W.sq_act, W.sq_wpk, W.sq_bar, W.sq_panels, loss_out, squad_bwd_next ? W.sq_wpk_t : nullptr));
-  } else {
-    OSD_TRY(run_trunk(h, s, W.f, in));
-  }
-  {
-    GemmArgs g = output_proj_args(h, W.f, n);
-    EpiMse::Args ea{};
-    ea.bias = h->params[pm.out_b]; ea.noise = eps_true; ea.ldn = D;
-    ea.dout = grads ? W.d_out : nullptr; ea.ldd = D; ea.pred = cp ? W.pred : nullptr; ea.ldp = D; ea.loss = loss_out;
-    ea.inv_count = (float)(1.0 / ((double)n * (double)D));
-    hipError_t me;
-    if (h->loss_kind == OSD_LOSS_L2 && !h->loss_tw_set) {
-      ea.gscale = (float)(2.0 * (double)loss_scale / ((double)n * (double)D));
-      // precision = 1: output_proj + MSE on the bf16 matrix pipe, operands split where they are staged (gemm_b3t.h)
-      me = h->precision == 1 ? launch_mse_b3t(s, g, ea) : hipErrorInvalidValue;
-      if (me == hipSuccess) h->last_train_path |= OSD_TP_MSE_BF16;
-      if (me == hipErrorInvalidValue) { (void)hipGetLastError(); me = launch_mse(s, g, ea); }
-    } else {
-      // osd_set_loss: the same launch with EpiLoss; rho' of l2 is 2 d, of the other kinds rho' itself
-      ea.gscale = (float)((h->loss_kind == OSD_LOSS_L2 ? 2.0 : 1.0) * (double)loss_scale / ((double)n * (double)D));
-      EpiLoss::Args el{};
-      el.m = ea; el.tw = h->loss_tw_set ? h->loss_tw : nullptr; el.t_index = t_idx; el.kind = h->loss_kind; el.delta = h->loss_delta;
-      h->last_train_path |= OSD_TP_LOSS_EPI;
-      me = h->precision == 1 ? launch_loss_b3t(s, g, el) : hipErrorInvalidValue;
-      if (me == hipSuccess) h->last_train_path |= OSD_TP_MSE_BF16;
-      if (me == hipErrorInvalidValue) { (void)hipGetLastError(); me = launch_loss(s, g, el); }
-    }
-    OSD_HIP(me);
-  }
-  if (cp) {
-    OSD_HIP(hipMemcpyAsync(h->parts_dev, loss_out, 4, hipMemcpyDeviceToDevice, s));
-    // constraint terms on x0_hat (models/diffusion.py:405) against the batch's x0; their gradient joins dL/d eps_hat
-    OSD_HIP(launch_x0hat(s, W.x_t, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, n, D, W.pred));
-    OSD_HIP(hipMemsetAsync(W.cw.acc, 0, (size_t)W.cw.acc_doubles * 8, s));
-    OSD_HIP(cons_moments(s, W.pred, D, n, D, W.cw.acc, W.cw.mi_r));
-    float* gx = grads ? W.g_x0 : nullptr;
-    if (use_pw)
-      OSD_HIP(cons_pathway(s, *cp, W.cw, W.pred, D, n, D, (float)h->w_pathway, (float)(h->w_pathway * loss_scale), loss_out, h->parts_dev + 1, gx));
-    if (use_me) {
-      OSD_HIP(cons_moments(s, x0, D, n, D, W.cw.acc + 2 * (int64_t)D, W.cw.mi_t));
-      OSD_HIP(cons_mutexpr(s, *cp, W.cw, W.pred, x0, D, n, D, (float)h->w_mutexpr, (float)(h->w_mutexpr * loss_scale), loss_out, h->parts_dev + 2, gx));
-    }
-    if (grads) OSD_HIP(launch_x0hat_bwd(s, W.g_x0, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, n, D, W.d_out));
-  }
-  if (!grads) return OSD_OK;
-
-  OSD_TRY(backward_from(h, s, W, W.x_t, W.xld, t_idx, cond, n, W.d_out, train, masks, seed, roff, grads, nullptr, events, loss_out));
-  if (flags & OSD_F_SYNC) OSD_HIP(hipStreamSynchronize(s));
-  return OSD_OK;
+  OSD_TRY(tc.check_outputs(events, n_events, grads));
+  OSD_TRY(tc.enter());
+  LossStep step{tc, h, h->arch, tc.s, n, x0, cond, noise, masks, seed, (uint32_t)row_offset, loss_out, grads, loss_scale, events, from_src, cond_drop};
+  return step.run(t_index);
 }
 
 int osd_train_batch_source(osd_handle* h, const float* data, int64_t ld_data, const float* cond, int64_t ld_cond, const int64_t* idx_a,
@@ -660,59 +762,54 @@ int osd_train_condition_dropout(osd_handle* h, const float* null_cond_host, doub
   return OSD_OK;
 }
 
+// checks in order: ready, rows, null tensors / empty batch, row offset, then the device
 int osd_denoiser_forward_train(osd_handle* h, const float* x_t, const int32_t* t_index, const float* cond, int64_t n,
                                const float* const* masks, uint64_t seed, int64_t row_offset, int flags, float* eps_out) {
-  OSD_TRY(check_ready(h));
-  OSD_TRY(check_rows(n));
+  TrainCall tc{h, n, flags};
+  OSD_TRY(tc.begin(false));
   if (!x_t || !t_index || !cond || !eps_out || n == 0) { set_error("null tensor or empty batch"); return OSD_EINVAL; }
   OSD_TRY(check_row_offset(row_offset, n));
   const Arch& a = h->arch;
-  OSD_HIP(hipSetDevice(h->cfg.device));
-  hipStream_t s = h->stream;
-  TrainWs W;
-  OSD_TRY(ensure_train_ws(h, s, n, nullptr, &W));
+  OSD_TRY(tc.enter());
+  hipStream_t s = tc.s;
+  TrainWs w;
+  OSD_TRY(ensure_train_ws(h, s, n, nullptr, &w));
   h->saved_rows = -1;
-  const int* t_idx = nullptr;
-  OSD_TRY(sanitize_t(h, s, t_index, n, &t_idx));
+  OSD_TRY(tc.timesteps(t_index));
   OSD_TRY(refresh_derived(h, s));
-  OSD_TRY(cond_embed_fwd(h, s, cond, n, W));
+  OSD_TRY(cond_embed_fwd(h, s, cond, n, w));
   TrunkIn in{};
-  in.x = x_t; in.ldx = a.D; in.n = n; in.t_index = t_idx; in.train = (flags & OSD_F_TRAIN_MODE) != 0; in.save = true;
+  in.x = x_t; in.ldx = a.D; in.n = n; in.t_index = tc.t_idx; in.train = tc.train_mode(); in.save = true;
   in.masks = masks; in.seed = seed; in.row_offset = (uint32_t)row_offset; in.drop_step = 0;
-  OSD_TRY(run_trunk(h, s, W.f, in));
-  GemmArgs g = output_proj_args(h, W.f, n);
+  OSD_TRY(run_trunk(h, s, w.f, in));
+  GemmArgs g = output_proj_args(h, w.f, n);
   OSD_HIP(launch_linear(s, g, true, true, h->params[a.pm.out_b], eps_out, a.D, false, false));
   h->saved_rows = n;
-  if (flags & OSD_F_SYNC) OSD_HIP(hipStreamSynchronize(s));
-  return OSD_OK;
+  return tc.finish();
 }
 
+// checks in order: ready, rows, null tensors / empty batch, saved activations, event count, grads[i], row offset, then the device
 int osd_denoiser_backward(osd_handle* h, const float* x_t, const int32_t* t_index, const float* cond, int64_t n, const float* dout,
                           const float* const* masks, uint64_t seed, int64_t row_offset, int flags, float* const* grads, float* dx_t,
                           void* const* events, int n_events) {
-  OSD_TRY(check_ready(h));
-  h->last_train_path = 0;
-  OSD_TRY(check_rows(n));
+  TrainCall tc{h, n, flags};
+  OSD_TRY(tc.begin(true));
   if (!x_t || !t_index || !cond || !dout || !grads || n == 0) { set_error("null tensor or empty batch"); return OSD_EINVAL; }
   if (h->saved_rows != n) { set_error("osd_denoiser_backward needs the activations of an osd_denoiser_forward_train call on the same %lld rows", (long long)n); return OSD_ESTATE; }
-  const Arch& a = h->arch;
-  const int n_buckets = a.n_blocks + 2;
-  if (events && n_events != n_buckets) { set_error("expected %d events (osd_grad_buckets), got %d", n_buckets, n_events); return OSD_EINVAL; }
-  for (int i = 0; i < a.pm.n_params; ++i)
-    if (!grads[i]) { set_error("grads[%d] is null", i); return OSD_EINVAL; }
+  OSD_TRY(tc.check_outputs(events, n_events, grads));
   OSD_TRY(check_row_offset(row_offset, n));
-  OSD_HIP(hipSetDevice(h->cfg.device));
-  hipStream_t s = h->stream;
-  TrainWs W;
-  carve_train(a, h->train_arena, n, nullptr, &W);       // same carving as the forward call: pointers to its activations
-  const int* t_idx = nullptr;
-  OSD_TRY(sanitize_t(h, s, t_index, n, &t_idx));
+  OSD_TRY(tc.enter());
+  const Arch& a = h->arch;
+  TrainWs w;
+  carve_train(a, h->train_arena, n, nullptr, &w);       // same carving as the forward call: pointers to its activations
+  OSD_TRY(tc.timesteps(t_index));
   ZeroList zl{};
-  add_backward_zeros(a, W, grads, &zl);
-  OSD_HIP(launch_zero_many(s, zl));
-  OSD_TRY(backward_from(h, s, W, x_t, a.D, t_idx, cond, n, dout, (flags & OSD_F_TRAIN_MODE) != 0, masks, seed, (uint32_t)row_offset, grads, dx_t, events));
-  if (flags & OSD_F_SYNC) OSD_HIP(hipStreamSynchronize(s));
-  return OSD_OK;
+  add_backward_zeros(a, w, grads, &zl);
+  OSD_HIP(launch_zero_many(tc.s, zl));
+  // per-layer dgrads: the forward call packed no transposed weights and there is no loss word for the squads to poison
+  BackwardPass bp(h, tc.s, w, n, tc.train_mode(), masks, seed, (uint32_t)row_offset, grads, events, false);
+  OSD_TRY(bp.run(x_t, a.D, tc.t_idx, cond, dout, dx_t, nullptr));
+  return tc.finish();
 }
 
 int osd_set_constraints(osd_handle* h, const osd_constraints* c) {
@@ -763,76 +860,68 @@ int osd_get_loss_parts(osd_handle* h, float* parts_host3) {
   return OSD_OK;
 }
 
-static int clip_adamw(hipStream_t stream, double* norm_ws, float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
-                      double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, int64_t step, float* grad_norm_out,
-                      float* ema = nullptr, double ema_decay = 0.0) {
+// The hyper-parameters of one fused clip_grad_norm_ + AdamW step, as the four entry points receive them.
+struct AdamHyper { double lr, beta1, beta2, eps, weight_decay, max_norm; int64_t step; };
+
+// The checked body of the four AdamW entry points.  `h`: the handle-taking variants, whose stream, device and norm workspace are
+// the handle's; null for the stream-taking ones, which bring their own.  `want_ema`: the EMA variants, which reject a null ema and
+// a decay outside [0, 1] before any device call.
+static int clip_adamw_step(osd_handle* h, hipStream_t stream, int device, double* norm_ws, float* param, float* grad, float* exp_avg,
+                           float* exp_avg_sq, int64_t numel, const AdamHyper& hp, float* grad_norm_out, bool want_ema, float* ema, double ema_decay) {
+  if ((!h && !norm_ws) || !param || !grad || !exp_avg || !exp_avg_sq) { set_error("null argument"); return OSD_EINVAL; }
+  if (want_ema && !ema) { set_error("null argument"); return OSD_EINVAL; }
+  if (want_ema && !(ema_decay >= 0.0 && ema_decay <= 1.0)) { set_error("ema_decay must be in [0, 1]"); return OSD_EINVAL; }
+  if (numel <= 0 || hp.step < 1) { set_error("numel and step must be positive"); return OSD_EINVAL; }
+  OSD_HIP(hipSetDevice(h ? h->cfg.device : device));
+  if (h) {
+    if (!h->normsq_dev) OSD_HIP(hipMalloc((void**)&h->normsq_dev, 256 * sizeof(double)));
+    // the handle's own optimizer is about to change parameters it may hold derived copies of (t_emb table, packed input_proj /
+    // output_proj, chain and bf16x3 weight copies): the next forward / sampling entry point refreshes them (api.hip: ensure_packed)
+    h->w_packed_stale = true;
+    stream = h->stream; norm_ws = h->normsq_dev;
+  }
   AdamArgs a{};
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  a.decay = (float)(1.0 - lr * weight_decay);
-  a.one_minus_b1 = (float)(1.0 - beta1);
-  a.b2 = (float)beta2;
-  a.one_minus_b2 = (float)(1.0 - beta2);
+  const double bc1 = 1.0 - pow(hp.beta1, (double)hp.step);
+  const double bc2 = 1.0 - pow(hp.beta2, (double)hp.step);
+  a.decay = (float)(1.0 - hp.lr * hp.weight_decay);
+  a.one_minus_b1 = (float)(1.0 - hp.beta1);
+  a.b2 = (float)hp.beta2;
+  a.one_minus_b2 = (float)(1.0 - hp.beta2);
   a.bc2_sqrt = (float)sqrt(bc2);
-  a.eps = (float)eps;
-  a.neg_step_size = (float)(-(lr / bc1));
-  a.max_norm = (float)max_norm;
+  a.eps = (float)hp.eps;
+  a.neg_step_size = (float)(-(hp.lr / bc1));
+  a.max_norm = (float)hp.max_norm;
   OSD_HIP(launch_clip_adamw(stream, param, grad, exp_avg, exp_avg_sq, numel, a, norm_ws, grad_norm_out, ema, (float)(1.0 - ema_decay)));
   return OSD_OK;
 }
 
 int osd_clip_adamw_step(osd_handle* h, float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel, double lr,
                         double beta1, double beta2, double eps, double weight_decay, double max_norm, int64_t step, float* grad_norm_out) {
-  if (!h || !param || !grad || !exp_avg || !exp_avg_sq) { set_error("null argument"); return OSD_EINVAL; }
-  if (numel <= 0 || step < 1) { set_error("numel and step must be positive"); return OSD_EINVAL; }
-  OSD_HIP(hipSetDevice(h->cfg.device));
-  if (!h->normsq_dev) OSD_HIP(hipMalloc((void**)&h->normsq_dev, 256 * sizeof(double)));
-  // the handle's own optimizer is about to change parameters it may hold derived copies of (t_emb table, packed input_proj /
-  // output_proj, chain and bf16x3 weight copies): the next forward / sampling entry point refreshes them (api.hip: ensure_packed)
-  h->w_packed_stale = true;
-  return clip_adamw(h->stream, h->normsq_dev, param, grad, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, max_norm, step,
-                    grad_norm_out);
+  if (!h) { set_error("null argument"); return OSD_EINVAL; }
+  return clip_adamw_step(h, nullptr, 0, nullptr, param, grad, exp_avg, exp_avg_sq, numel, {lr, beta1, beta2, eps, weight_decay, max_norm, step},
+                         grad_norm_out, false, nullptr, 0.0);
 }
 
 int osd_nn_clip_adamw_step(void* stream, int device, double* normsq_ws, float* param, float* grad, float* exp_avg, float* exp_avg_sq,
                            int64_t numel, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
                            int64_t step, float* grad_norm_out) {
-  if (!normsq_ws || !param || !grad || !exp_avg || !exp_avg_sq) { set_error("null argument"); return OSD_EINVAL; }
-  if (numel <= 0 || step < 1) { set_error("numel and step must be positive"); return OSD_EINVAL; }
-  OSD_HIP(hipSetDevice(device));
-  return clip_adamw((hipStream_t)stream, normsq_ws, param, grad, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, max_norm, step,
-                    grad_norm_out);
-}
-
-// the ema argument checks shared by both entry points: before any HIP call
-static bool ema_args_ok(const float* ema, double ema_decay) {
-  if (!ema) { set_error("null argument"); return false; }
-  if (!(ema_decay >= 0.0 && ema_decay <= 1.0)) { set_error("ema_decay must be in [0, 1]"); return false; }
-  return true;
+  return clip_adamw_step(nullptr, (hipStream_t)stream, device, normsq_ws, param, grad, exp_avg, exp_avg_sq, numel,
+                         {lr, beta1, beta2, eps, weight_decay, max_norm, step}, grad_norm_out, false, nullptr, 0.0);
 }
 
 int osd_clip_adamw_ema_step(osd_handle* h, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel, double lr,
                             double beta1, double beta2, double eps, double weight_decay, double max_norm, int64_t step, double ema_decay,
                             float* grad_norm_out) {
-  if (!h || !param || !grad || !exp_avg || !exp_avg_sq) { set_error("null argument"); return OSD_EINVAL; }
-  if (!ema_args_ok(ema, ema_decay)) return OSD_EINVAL;
-  if (numel <= 0 || step < 1) { set_error("numel and step must be positive"); return OSD_EINVAL; }
-  OSD_HIP(hipSetDevice(h->cfg.device));
-  if (!h->normsq_dev) OSD_HIP(hipMalloc((void**)&h->normsq_dev, 256 * sizeof(double)));
-  h->w_packed_stale = true;      // as osd_clip_adamw_step
-  return clip_adamw(h->stream, h->normsq_dev, param, grad, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, max_norm, step,
-                    grad_norm_out, ema, ema_decay);
+  if (!h) { set_error("null argument"); return OSD_EINVAL; }
+  return clip_adamw_step(h, nullptr, 0, nullptr, param, grad, exp_avg, exp_avg_sq, numel, {lr, beta1, beta2, eps, weight_decay, max_norm, step},
+                         grad_norm_out, true, ema, ema_decay);
 }
 
 int osd_nn_clip_adamw_ema_step(void* stream, int device, double* normsq_ws, float* param, float* grad, float* exp_avg, float* exp_avg_sq,
                                float* ema, int64_t numel, double lr, double beta1, double beta2, double eps, double weight_decay,
                                double max_norm, int64_t step, double ema_decay, float* grad_norm_out) {
-  if (!normsq_ws || !param || !grad || !exp_avg || !exp_avg_sq) { set_error("null argument"); return OSD_EINVAL; }
-  if (!ema_args_ok(ema, ema_decay)) return OSD_EINVAL;
-  if (numel <= 0 || step < 1) { set_error("numel and step must be positive"); return OSD_EINVAL; }
-  OSD_HIP(hipSetDevice(device));
-  return clip_adamw((hipStream_t)stream, normsq_ws, param, grad, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, max_norm, step,
-                    grad_norm_out, ema, ema_decay);
+  return clip_adamw_step(nullptr, (hipStream_t)stream, device, normsq_ws, param, grad, exp_avg, exp_avg_sq, numel,
+                         {lr, beta1, beta2, eps, weight_decay, max_norm, step}, grad_norm_out, true, ema, ema_decay);
 }
 
 }  // extern "C"

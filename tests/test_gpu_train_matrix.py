@@ -206,6 +206,49 @@ def test_train_step_vs_fp64_oracle(name):
     assert path == c["path"], f"last_train_path {path:#x} ({path}), expected {c['path']:#x} ({c['path']})"
 
 
+# The bucket-event path of the backward pass (data parallel: an events array is handed in) in one process.  The pass then forks
+# its side stream, flushes the decoder half's weight gradients mid-pass, records every bucket's event behind the flush that
+# finalises it, and keeps the squads' backward off.  Expected path bits as the library reported them before the host code of the
+# step was folded into BackwardPass.
+EVENT_CASES = {
+    # fused GroupNorm backward, a dual dgrad, a ragged last tile (deep300's shape)
+    "deep300": dict(dims=(16, 480, 16, 3), hidden=[256, 256, 512, 256], n=300, draw="philox",
+                    path=FUSE | DUAL | COND | CE0 | WG_DIRECT | WG_GROUP),
+    # stand-alone GroupNorm backward (group width 16): mixed's model at a small ragged batch
+    "mixed300": dict(dims=(16, 224, 16, 3), hidden=[256, 128, 256], n=300, draw="injected",
+                     path=COND | CE0 | WG_DIRECT | WG_GROUP),
+}
+
+
+@pytest.mark.parametrize("streams", [1, 2])
+@pytest.mark.parametrize("name", list(EVENT_CASES))
+def test_bucket_events_vs_fp64_oracle(name, streams):
+    """One training call with osd_grad_buckets events, on one and on two streams: every event has fired once the device is idle,
+    loss and gradients are the oracle's at the file's tolerances, and the path is the expected one (no SQ_BWD with events)."""
+    c = dict(EVENT_CASES[name], opts=dict(train_streams=streams))
+    sd, x, cond, t, noise, injected = _inputs(c["dims"], c["hidden"], c["n"])
+    m = _model(c, sd)
+    eng = m._engine()
+    events = [torch.cuda.Event() for _ in range(L.lib().osd_grad_buckets(C.byref(eng.cfg), None, None, 0))]
+    for e in events:
+        e.record()            # materialise the hipEvent_t handles (as Trainer.__init__)
+    grads = [torch.empty_like(p) for p in m.parameters()]
+    kw = dict(t=t.cuda(), noise=noise.cuda(), seed=SEED, events=events)
+    if c["draw"] == "injected":
+        kw["dropout_masks"] = [k.cuda() for k in injected]
+    loss = _loss_fwd_bwd(m, x.cuda(), cond.cuda(), L.ptr_array(grads), **kw)
+    torch.cuda.synchronize()
+    assert len(events) >= 3 and all(e.query() for e in events)
+    path = _path(m)
+    ref_loss, ref_grads = _oracle(c)
+    names = [k for k, _ in m.named_parameters()]
+    worst, bad = _check(loss.item(), {k: g.cpu() for k, g in zip(names, grads)}, ref_loss, ref_grads, sum(c["dims"][:3]))
+    _report(f"events-{name}-s{streams}", path=path, worst_ratio=worst)
+    assert not bad, "\n".join(bad)
+    assert not path & SQ_BWD
+    assert path == c["path"], f"last_train_path {path:#x} ({path}), expected {c['path']:#x} ({c['path']})"
+
+
 def test_negative_control_row_offset_shifted_by_one_panel():
     """full2048-off against masks drawn one 64-row panel away: the gradients must disagree beyond tolerance."""
     c = CASES["full2048-off"]
