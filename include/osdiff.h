@@ -278,6 +278,42 @@ int osd_sample_chain_known(osd_handle *h, const float *cond, int64_t n, const fl
                            const float *null_cond_host, float guidance_scale, const float *known,
                            int64_t ld_known);
 
+/* The same chains with the predicted clean sample clipped to per-feature bounds inside the posterior launch (clip_denoised of
+ * improved-diffusion / guided-diffusion, clip_sample of diffusers; static thresholding).  lo_host / hi_host: host [D], -inf / +inf
+ * leave a side free.  Step s of the plan goes from tau_s to tau' = tau_{s-1} (abar' = 1 at s = 0); with abar = alphas_cumprod[tau_s],
+ * sigma as in osd_sample_chain_steps and dir = sqrt(max(1 - abar' - sigma^2, 0)):
+ *   P = 1/sqrt(abar)                               Q = -sqrt(1-abar)/sqrt(abar)
+ *   E = sqrt(abar') - dir*sqrt(abar)/sqrt(1-abar)   F = dir/sqrt(1-abar)          C = sigma
+ *   eps = denoiser(x, tau_s)                       (guided: osd_sample_chain_guided's eps_g)
+ *   x0  = fmaf(P, x, Q*eps)
+ *   x0c = fminf(fmaxf(x0, lo[f]), hi[f])
+ *   x'  = fmaf(E, x0c, fmaf(F, x, C*z))            = sqrt(abar')*x0c + dir*(x - sqrt(abar)*x0c)/sqrt(1-abar) + sigma*z
+ * The direction term uses the eps the CLIPPED x0 implies, not the network's.  Row 0 is (P, Q, 1, 0) with C_0 = 0, so x' = x0c bit for
+ * bit: every returned element lies inside [lo, hi] exactly; mut_mask_out stays (x_out > 0.5).  Clamping the state x' instead is another
+ * (wrong) algorithm, which is why this is an epilogue of the output_proj launch (EpiPosteriorClip, csrc/epilogues.h) and no pass of
+ * its own.  Arguments and checks of osd_sample_chain_known, except:
+ *   known == NULL       nothing is observed (known_level / ld_known ignored); otherwise observed elements are overwritten after the
+ *                       clipped update with osd_sample_chain_known's expressions and draw rule (an observation outside the bounds
+ *                       comes back as observed)
+ *   x0_coef             host [n_steps][4] = (P_s, Q_s, E_s, F_s), row 0 = (., ., 1, 0) (ddim.py: ddim_x0_table).  step_coef supplies C_s
+ *                       in slot 2; its A_s, B_s are validated as ever and not used
+ *   timesteps == NULL   the DDPM chain (step_coef / x0_coef / known_level / n_steps ignored): p_sample (models/diffusion.py:398-425)
+ *                       with x_0_pred clamped.  From osd_set_schedule's post_coef (c0 .. c5), folded in double and rounded once:
+ *                       (P, Q, E, F, C) = (1/c1, -c0/c1, c2/c3, c4/c3, c5), and (1/c1, -c0/c1, 1, 0, 0) at t = 0
+ * One fused output_proj + posterior launch per step; per-layer kernels only, whatever "sampler" says (osd_sample_engine(h, -1, 0) then
+ * reports 0; no warning, "chain_fallbacks" untouched); a row's result does not depend on the chunk or shard it is in ("input_splitk"
+ * = 0).  OSD_F_TRAIN_MODE is allowed for unguided chains.  All-infinite bounds agree with the unclipped chain to fp32 rounding, not
+ * bitwise (another operation order).  OSD_EINVAL, checked on the host before any device call: a NULL bound, a NaN bound, lo[f] > hi[f],
+ * a NULL or non-finite x0_coef, x0_coef[0] != (., ., 1, 0), and everything osd_sample_chain_known (with known != NULL),
+ * osd_sample_chain_guided and osd_sample_chain_steps reject; OSD_EUNSUPPORTED: "precision" = 1. */
+int osd_sample_chain_clipped(osd_handle *h, const float *cond, int64_t n, const float *x_T,
+                             const float *noises, uint64_t seed, int64_t row_offset, float *x_out,
+                             float *mut_mask_out, int flags, const int32_t *timesteps,
+                             const float *step_coef, const float *x0_coef, const float *known_level,
+                             int32_t n_steps, const float *null_cond_host, float guidance_scale,
+                             const float *known, int64_t ld_known, const float *lo_host,
+                             const float *hi_host);
+
 /* eps_g of ONE guided evaluation (DiffusionUNet.forward twice, models/diffusion.py:210-256, combined as above), eval mode only:
  * osd_denoiser_forward's x / t_index / t_all / cond / eps, osd_sample_chain_guided's null_cond_host / guidance_scale and errors. */
 int osd_denoiser_forward_guided(osd_handle *h, const float *x, const int32_t *t_index, int32_t t_all,

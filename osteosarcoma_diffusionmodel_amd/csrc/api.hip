@@ -535,6 +535,9 @@ int osd_destroy(osd_handle* h) {
   if (h->known_level) e = hipFree(h->known_level);
   if (h->known_ev) e = hipEventDestroy(h->known_ev);
   free(h->known_level_host);
+  if (h->clip_dev) e = hipFree(h->clip_dev);
+  if (h->clip_ev) e = hipEventDestroy(h->clip_ev);
+  free(h->clip_host);
   if (h->normsq_dev) e = hipFree(h->normsq_dev);
   if (h->parts_dev) e = hipFree(h->parts_dev);
   if (h->loss_tw) e = hipFree(h->loss_tw);
@@ -604,6 +607,16 @@ int osd_set_schedule(osd_handle* h, const float* sqrt_ac, const float* sqrt_1m_a
       }
     }
     OSD_HIP(hipMemcpy(h->d_coef, abc.data(), abc.size() * 4, hipMemcpyHostToDevice));
+    // ... and, for the chain that clips x0 (EpiPosteriorClip), the same scalars unfolded at x0: x0 = P*x + Q*eps, x' = E*x0 + F*x + C*z
+    h->sched_x0_coef.assign((size_t)a.T * 4, 0.f);
+    for (int t = 0; t < a.T; ++t) {
+      const double c0 = post_coef[6 * t], c1 = post_coef[6 * t + 1], c2 = post_coef[6 * t + 2], c3 = post_coef[6 * t + 3], c4 = post_coef[6 * t + 4];
+      float* r = &h->sched_x0_coef[4 * (size_t)t];
+      r[0] = (float)(1.0 / c1);
+      r[1] = (float)(-c0 / c1);
+      r[2] = t > 0 ? (float)(c2 / c3) : 1.f;
+      r[3] = t > 0 ? (float)(c4 / c3) : 0.f;
+    }
   }
   OSD_HIP(hipMemcpy(h->d_time_emb, time_emb, (size_t)a.T * a.time_dim * 4, hipMemcpyHostToDevice));
   h->sched_sqrt_ac.assign(sqrt_ac, sqrt_ac + a.T);
@@ -767,6 +780,7 @@ static int chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r
   const ChainJob job = whole.chunk(r0, m);
   const Guide* gd = job.guide.null_cond ? &job.guide : nullptr;
   const Known* kn = job.known.known ? &job.known : nullptr;
+  const Clip* cl = job.clip.bounds ? &job.clip : nullptr;
   const int D = a.D, S = job.plan.n_steps;
   hipStream_t s = sl.stream;
   OSD_TRY(release_graph(sl));
@@ -845,7 +859,8 @@ static int chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r
     ea.z = job.noises; ea.ldzz = D; ea.z_step_stride = (long long)job.n_total * D; ea.t_first = S - 1;
     ea.seed = job.seed; ea.row_offset = roff;
     ea.mut_mask = job.mut_mask_out; ea.mutation_dim = job.mutation_dim;
-    if (kn) OSD_HIP(launch_posterior_known(s, g, EpiPosteriorKnown::Args{ea, known, ldk, kn->level}));
+    if (cl) OSD_HIP(launch_posterior_clip(s, g, PosteriorClipArgs{ea, cl->bounds, cl->bounds + cl->ld, cl->x0_coef, kn ? known : nullptr, ldk, kn ? kn->level : nullptr}));
+    else if (kn) OSD_HIP(launch_posterior_known(s, g, EpiPosteriorKnown::Args{ea, known, ldk, kn->level}));
     else OSD_HIP(launch_posterior(s, g, ea));
     OSD_HIP(launch_add_int(s, sl.t_dev, -1));
     return OSD_OK;
@@ -858,14 +873,14 @@ static int chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r
 static int sample_plan(osd_handle* h, const ChainJob& job) {
   const int64_t n = job.n;
   const int flags = job.flags;
-  const bool gd = job.guide.null_cond != nullptr, kn = job.known.known != nullptr;
+  const bool gd = job.guide.null_cond != nullptr, kn = job.known.known != nullptr, cl = job.clip.bounds != nullptr;
   // bf16x3 split precision: eval-mode chains on the per-layer launches of split.hip (dropout inside the chain stays fp32)
-  const bool split = !gd && !kn && h->precision == 1 && !((flags & OSD_F_TRAIN_MODE) && h->cfg.dropout_p > 0.f);
+  const bool split = !gd && !kn && !cl && h->precision == 1 && !((flags & OSD_F_TRAIN_MODE) && h->cfg.dropout_p > 0.f);
   h->last_precision = split ? 1 : 0;
   if (split) OSD_TRY(split_pack_weights(h, h->stream));
   // a guided chain runs on the per-layer kernels whatever "sampler" says: the chain kernels' tiles are sized for m trunk rows; so does
-  // a chain around known values, whose epilogue only the per-layer output_proj launch has
-  h->last_engine = (split || gd || kn) ? 0 : chain_pick_engine(h, n, flags);
+  // a chain around known values or one that clips x0, whose epilogues only the per-layer output_proj launch has
+  h->last_engine = (split || gd || kn || cl) ? 0 : chain_pick_engine(h, n, flags);
   if (h->last_engine == 1 && job.noises && h->w_out_packed && !chain_uses_squad(h, n)) h->last_engine = 0;      // injected draws at D % 4 != 0: guarded per-layer kernels (the squad chain reads any layout)
   bool fell_back = false;
   if (h->last_engine == 1) {
@@ -985,7 +1000,33 @@ static int upload_known_level(osd_handle* h, const float* level_host, int S, con
   return OSD_OK;
 }
 
-// A reverse-chain request in the caller's terms: what the four osd_sample_chain* entry points receive, absent parts null.
+// The two tables of a chain that clips x0, host -> one handle-owned device buffer on the handle's stream: coefficients [S][4] -- the
+// plan's, or null for the DDPM chain, whose rows osd_set_schedule folded --, then the bounds as two rows of Dp floats whose pad columns
+// are (-inf, +inf): a padded chain state and the caller's rows read the same rows.
+static int upload_clip(osd_handle* h, const float* x0_coef_host, int S, const float* lo_host, const float* hi_host, Clip* out) {
+  const Arch& a = h->arch;
+  const size_t coef_floats = (size_t)up64((int64_t)a.T * 4), floats = coef_floats + 2 * (size_t)h->Dp;
+  if (!h->clip_host) {
+    h->clip_host = static_cast<float*>(malloc(floats * 4));
+    if (!h->clip_host) { set_error("out of host memory"); return OSD_ENOMEM; }
+  }
+  if (!h->clip_ev) OSD_HIP(hipEventCreateWithFlags(&h->clip_ev, hipEventDisableTiming));
+  if (!h->clip_dev) OSD_HIP(hipMalloc((void**)&h->clip_dev, floats * 4));
+  OSD_HIP(hipEventSynchronize(h->clip_ev));          // the previous call's upload has read the staging
+  float* hc = h->clip_host;
+  memcpy(hc, x0_coef_host ? x0_coef_host : h->sched_x0_coef.data(), (size_t)S * 4 * 4);
+  float* lo = hc + coef_floats;
+  float* hi = lo + h->Dp;
+  memcpy(lo, lo_host, (size_t)a.D * 4);
+  memcpy(hi, hi_host, (size_t)a.D * 4);
+  for (int f = a.D; f < h->Dp; ++f) { lo[f] = -INFINITY; hi[f] = INFINITY; }
+  OSD_HIP(hipMemcpyAsync(h->clip_dev, hc, floats * 4, hipMemcpyHostToDevice, h->stream));
+  OSD_HIP(hipEventRecord(h->clip_ev, h->stream));
+  *out = Clip{h->clip_dev + coef_floats, h->Dp, h->clip_dev};
+  return OSD_OK;
+}
+
+// A reverse-chain request in the caller's terms: what the osd_sample_chain* entry points receive, absent parts null.
 struct SampleRequest {
   const float* cond; int64_t n; const float* x_T; const float* noises; uint64_t seed; int64_t row_offset;
   float* x_out; float* mut_mask_out; int flags;
@@ -995,6 +1036,8 @@ struct SampleRequest {
   const float* null_cond; float guidance_scale;
   bool around_known;              // osd_sample_chain_known
   const float* known; int64_t ld_known; const float* known_level;
+  bool clipped;                   // osd_sample_chain_clipped
+  const float* x0_coef; const float* lo; const float* hi;
 };
 
 // The one path of the osd_sample_chain* entry points: validation (in the order the entry points document: the first bad argument
@@ -1005,6 +1048,7 @@ static int sample_request(osd_handle* h, const SampleRequest& r) {
   bool unguided = true;
   if (r.guide) OSD_TRY(check_guidance(h, r.null_cond, r.guidance_scale, r.flags, &unguided));
   if (r.around_known && h->precision == 1) { set_error("precision = bf16x3 does not run chains around known values: set precision to fp32"); return OSD_EUNSUPPORTED; }
+  if (r.clipped && h->precision == 1) { set_error("precision = bf16x3 does not run chains that clip x0: set precision to fp32"); return OSD_EUNSUPPORTED; }
   OSD_TRY(check_rows(r.n));
   if (!r.cond || !r.x_out) { set_error("null tensor"); return OSD_EINVAL; }
   if (r.around_known) {
@@ -1020,6 +1064,22 @@ static int sample_request(osd_handle* h, const SampleRequest& r) {
     if (r.known_level[0] != 1.f || r.known_level[1] != 0.f) {
       set_error("known_level[0] = (%g, %g): the last step returns the observations themselves, so it must be (1, 0)", (double)r.known_level[0], (double)r.known_level[1]);
       return OSD_EINVAL;
+    }
+  }
+  if (r.clipped) {
+    if (!r.lo || !r.hi) { set_error("null bound"); return OSD_EINVAL; }
+    for (int f = 0; f < a.D; ++f) {
+      if (std::isnan(r.lo[f]) || std::isnan(r.hi[f])) { set_error("bound %d is NaN", f); return OSD_EINVAL; }
+      if (r.lo[f] > r.hi[f]) { set_error("lo[%d] = %g > hi[%d] = %g", f, (double)r.lo[f], f, (double)r.hi[f]); return OSD_EINVAL; }
+    }
+    if (plan) {
+      if (!r.x0_coef) { set_error("null x0_coef"); return OSD_EINVAL; }
+      for (int i = 0; i < 4 * r.n_steps; ++i)
+        if (!std::isfinite(r.x0_coef[i])) { set_error("x0_coef[%d] is not finite", i); return OSD_EINVAL; }
+      if (r.x0_coef[2] != 1.f || r.x0_coef[3] != 0.f) {
+        set_error("x0_coef[0] = (., ., %g, %g): the last step returns the clipped x0 itself, so E_0, F_0 must be (1, 0)", (double)r.x0_coef[2], (double)r.x0_coef[3]);
+        return OSD_EINVAL;
+      }
     }
   }
   OSD_TRY(check_row_offset(r.row_offset, r.n));
@@ -1038,6 +1098,7 @@ static int sample_request(osd_handle* h, const SampleRequest& r) {
     job.known.known = r.known; job.known.ld = r.ld_known;
     OSD_TRY(upload_known_level(h, plan ? r.known_level : nullptr, plan ? r.n_steps : a.T, &job.known.level));
   }
+  if (r.clipped) OSD_TRY(upload_clip(h, plan ? r.x0_coef : nullptr, plan ? r.n_steps : a.T, r.lo, r.hi, &job.clip));
   if (plan) {
     OSD_TRY(upload_plan(h, r.timesteps, r.step_coef, r.n_steps));
     job.plan = StepPlan{r.n_steps, h->plan_temb, h->plan_coef};
@@ -1072,6 +1133,17 @@ int osd_sample_chain_known(osd_handle* h, const float* cond, int64_t n, const fl
                            float guidance_scale, const float* known, int64_t ld_known) {
   SampleRequest r{cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, false, timesteps, step_coef, n_steps,
                   null_cond_host != nullptr, null_cond_host, guidance_scale, true, known, ld_known, known_level};
+  return sample_request(h, r);
+}
+
+int osd_sample_chain_clipped(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                             int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
+                             const float* step_coef, const float* x0_coef, const float* known_level, int32_t n_steps,
+                             const float* null_cond_host, float guidance_scale, const float* known, int64_t ld_known,
+                             const float* lo_host, const float* hi_host) {
+  SampleRequest r{cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, false, timesteps, step_coef, n_steps,
+                  null_cond_host != nullptr, null_cond_host, guidance_scale, known != nullptr, known, ld_known, known_level,
+                  true, x0_coef, lo_host, hi_host};
   return sample_request(h, r);
 }
 

@@ -652,6 +652,119 @@ struct EpiPosteriorKnown {
   }
 };
 
+// ---- output_proj + posterior update with the predicted x0 clipped to per-feature bounds ----
+// x0coef [S][4] = (P_t, Q_t, E_t, F_t); C_t is slot 2 of EpiPosterior's coef row.  Per element of step t:
+//   eps = acc + bias
+//   x0  = fmaf(P, x, Q*eps)                        P = 1/sqrt(abar), Q = -sqrt(1-abar)/sqrt(abar)
+//   x0c = fminf(fmaxf(x0, lo[f]), hi[f])           -inf / +inf leave a side free
+//   x'  = fmaf(E, x0c, fmaf(F, x, C*z))            the direction term uses the eps the CLIPPED x0 implies, (x - sqrt(abar) x0c)/sqrt(1-abar)
+// Row 0 is (P, Q, 1, 0) with C = 0: x' = x0c bit for bit, so every returned element lies inside [lo, hi].  C*z is a select on the
+// wave-uniform C, as in EpiPosteriorKnown.  lo / hi depend on the feature only: loaded per 32 x 32 block next to the x_t quads (2 x 16
+// float4 per wave tile held from before the K loop, the way the bias is, do not fit).  The !WIDE form only.
+// KNOWN: observed elements (EpiPosteriorKnown's `known`, NaN = free) are overwritten after the clipped update with that epilogue's
+// expressions and draw rule: every step with t > 0 draws, and the lanes of a quad without an observation skip the generator where C = 0.
+struct PosteriorClipArgs {
+  EpiPosterior::Args p;
+  const float* lo; const float* hi;     // dev [F] each
+  const float* x0coef;                  // dev [S][4] = (P_t, Q_t, E_t, F_t)
+  const float* known; int ldk;          // KNOWN: [P][F], row stride ldk; NaN = free
+  const float* level;                   // KNOWN: dev [S][2] = (La_t, Ls_t)
+};
+template <bool KNOWN>
+struct EpiPosteriorClip {
+  static constexpr bool COUNTED_STORES = true;
+  static constexpr bool XBUF = false;
+  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
+  typedef PosteriorClipArgs Args;
+  static bool fast_ok(const Args& a, int F) {
+    return EpiPosterior::fast_ok(a.p, F) && al16(a.lo) && al16(a.hi) && (!KNOWN || (al16(a.known) && a.ldk % 4 == 0));
+  }
+  template <int NFB> using Pre = EpiPosterior::Pre<NFB>;
+  template <int NFB, bool FAST>
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
+    return EpiPosterior::prefetch<NFB, FAST>(a.p, fw, lane, F);
+  }
+  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& ac, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
+                                               Sync&& sync = Sync()) {
+    const EpiPosterior::Args& a = ac.p;
+    const int l31 = lane & 31, h = lane >> 5;
+    const int t = a.t_dev ? *a.t_dev : a.t_imm;
+    const float cC = a.coef[4 * t + 2];
+    const float* c = ac.x0coef + 4 * t;
+    const float cP = c[0], cQ = c[1], cE = c[2], cF = c[3];
+    float La = 1.f, Ls = 0.f;
+    if constexpr (KNOWN) { La = ac.level[2 * t]; Ls = ac.level[2 * t + 1]; }
+    const bool cz = cC != 0.f;           // uniform: the step's table row
+    const float* zbase = a.z ? a.z + (long long)(a.t_first - t) * a.z_step_stride : nullptr;
+    // quads requested ahead of their use: a whole block's (x, lo, hi: 48 registers), or -- KNOWN, whose known quad rides along -- one
+    // quad's (16): in the 128 x 128 LDS-DMA kernel a whole block's 64 spill 31 VGPRs and half a block's 32 still spill one
+    constexpr int QB = KNOWN ? 1 : 4;
+#pragma unroll
+    for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+      for (int pb = 0; pb < NPB; ++pb) {
+        const int p = pw + 32 * pb + l31;
+        const int pc = p < P ? p : P - 1;
+        float4 xq[4], lq[4], hq[4], kq[KNOWN ? 4 : 1];
+#pragma unroll
+        for (int q0 = 0; q0 < 4; q0 += QB) {
+#pragma unroll
+        for (int q = q0; q < q0 + QB; ++q) {
+          const int f = fw + 32 * fb + 8 * q + 4 * h;
+          xq[q] = ldq<FAST>(a.xin + (size_t)pc * a.ldx, f, F);
+          lq[q] = ldq<FAST>(ac.lo, f, F);
+          hq[q] = ldq<FAST>(ac.hi, f, F);
+          if constexpr (KNOWN) kq[q] = ldq<FAST>(ac.known + (size_t)pc * ac.ldk, f, F);
+        }
+#pragma unroll
+        for (int q = q0; q < q0 + QB; ++q) {
+          const int f = fw + 32 * fb + 8 * q + 4 * h;
+          const bool ok = p < P && f < F;
+          const float4 bv = pre.bias[fb][q];
+          const float e[4] = {acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w};
+          const float xv[4] = {xq[q].x, xq[q].y, xq[q].z, xq[q].w};
+          const float lv[4] = {lq[q].x, lq[q].y, lq[q].z, lq[q].w};
+          const float hv[4] = {hq[q].x, hq[q].y, hq[q].z, hq[q].w};
+          float kv[4] = {0.f, 0.f, 0.f, 0.f};
+          bool draw = t > 0 && cz;         // EpiPosterior's rule: C = 0 (eta = 0 DDIM steps; t = 0) draws nothing
+          if constexpr (KNOWN) {
+            kv[0] = kq[q].x; kv[1] = kq[q].y; kv[2] = kq[q].z; kv[3] = kq[q].w;
+            // EpiPosteriorKnown's rule: the known elements use z at every t > 0; a quad without an observation skips the generator where C = 0
+            const bool any_known = kv[0] == kv[0] || kv[1] == kv[1] || kv[2] == kv[2] || kv[3] == kv[3];
+            draw = t > 0 && (cz || any_known);
+          }
+          float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (draw) {
+            if (zbase) zz = ldq<FAST>(zbase + (size_t)pc * a.ldzz, f, F);
+            else zz = randn4(a.seed, a.row_offset + (uint32_t)p, (uint32_t)(f >> 2), (uint32_t)t, TAG_POSTERIOR);
+          }
+          const float zv[4] = {zz.x, zz.y, zz.z, zz.w};
+          float o[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float x0 = fmaf(cP, xv[r], cQ * e[r]);
+            const float x0c = fminf(fmaxf(x0, lv[r]), hv[r]);
+            o[r] = fmaf(cE, x0c, fmaf(cF, xv[r], cC * (cz ? zv[r] : 0.f)));
+            if constexpr (KNOWN) {
+              const float kn = t > 0 ? fmaf(La, kv[r], Ls * zv[r]) : kv[r];
+              o[r] = (kv[r] == kv[r]) ? kn : o[r];      // NaN: free
+            }
+          }
+          if (t == 0 && a.mut_mask && ok && f < a.mutation_dim) {
+            float* mrow = a.mut_mask + (size_t)p * a.mutation_dim;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (f + r < a.mutation_dim) mrow[f + r] = (o[r] > 0.5f) ? 1.0f : 0.0f;
+          }
+          if (p < P) stq<FAST>(a.xout + (size_t)pc * a.ldo, f, F, make_float4(o[0], o[1], o[2], o[3]));
+          sync.tick();
+        }
+        }
+      }
+  }
+};
+
 // ---- output_proj fused with the MSE loss (models/diffusion.py:373-377) and its gradient ----
 // d = (acc + bias) - noise;  loss += sum d^2 * inv_count;  dout = d * gscale
 struct EpiMse {

@@ -89,6 +89,13 @@ struct Known {
   const float* level;          // dev [S][2]
 };
 
+// Clipping of the predicted x0 to per-feature bounds inside the posterior launch (osd_sample_chain_clipped, EpiPosteriorClip).
+struct Clip {
+  const float* bounds;         // dev [2][ld]: the lo row, then the hi row; null = no clipping
+  int ld;
+  const float* x0_coef;        // dev [S][4] = (P, Q, E, F)
+};
+
 // One reverse-chain request, as every sampler engine receives it (api.hip: sample_request fills it from an entry point's arguments).
 struct ChainJob {
   StepPlan plan;
@@ -96,6 +103,7 @@ struct ChainJob {
   float* x_out; float* mut_mask_out; int flags;
   Guide guide;
   Known known;
+  Clip clip;
   int D, cond_dim, mutation_dim;   // row widths of x_T / noises / x_out, of cond and of mut_mask_out
   int64_t n_total;                 // rows of the whole request: injected draws of consecutive steps lie n_total * D floats apart
   // rows [r0, r0 + m) of the request as a job of their own
@@ -189,6 +197,11 @@ struct osd_handle {
   // current call's level table [S][2] on the device with its host staging and the event that says the upload has read it
   std::vector<float> sched_sqrt_ac, sched_sqrt_1m;
   float* known_level = nullptr; float* known_level_host = nullptr; hipEvent_t known_ev = nullptr;
+  // x0 clipping (osd_sample_chain_clipped): the DDPM chain's (P, Q, E, F) rows [T][4] folded by osd_set_schedule, and the current call's
+  // tables on the device -- coefficients [T][4], then bounds [2][Dp] (pad columns (-inf, +inf)) -- with their host staging and the event
+  // that says the upload has read it
+  std::vector<float> sched_x0_coef;
+  float* clip_dev = nullptr; float* clip_host = nullptr; hipEvent_t clip_ev = nullptr;
   bool have_cond_drop = false; float cond_drop_p = 0.f; const float* cond_drop_keep = nullptr;   // osd_train_condition_dropout: one-shot
   int64_t saved_rows = -1;           // rows of the last osd_denoiser_forward_train whose activations are still in the arena
   // constraint losses (osd_set_constraints); parts_dev = (mse, L_pc, L_me) of the last training call

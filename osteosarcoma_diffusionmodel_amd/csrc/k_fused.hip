@@ -1,4 +1,4 @@
-// k_fused.hip -- input_proj (+t_emb +c_proj), output_proj (+posterior), output_proj (+MSE), output_proj (+configurable loss).
+// k_fused.hip -- input_proj (+t_emb +c_proj), output_proj (+posterior, around known values, with x0 clipped), output_proj (+MSE), output_proj (+configurable loss).
 #include "kernels.h"
 #include "launch.h"
 
@@ -203,6 +203,17 @@ hipError_t launch_posterior_known(hipStream_t s, const GemmArgs& g, const EpiPos
   const long big_tiles = (long)((g.F + 127) / 128) * ((g.P + 127) / 128);
   if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorKnown>(s, g, a);
   return launch_gemm<TileSmall, true, true, EpiPosteriorKnown>(s, g, a);
+}
+// launch_posterior's tile choice; a.known selects the instantiation that also puts observed values back
+hipError_t launch_posterior_clip(hipStream_t s, const GemmArgs& g, const PosteriorClipArgs& a) {
+  constexpr long POST_BIG_FROM = 512;
+  const long big_tiles = (long)((g.F + 127) / 128) * ((g.P + 127) / 128);
+  if (a.known) {
+    if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorClip<true>>(s, g, a);
+    return launch_gemm<TileSmall, true, true, EpiPosteriorClip<true>>(s, g, a);
+  }
+  if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorClip<false>>(s, g, a);
+  return launch_gemm<TileSmall, true, true, EpiPosteriorClip<false>>(s, g, a);
 }
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a) {
   if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiMse>(s, g, a);

@@ -10,6 +10,9 @@ update x' = A*x + B*eps + C*z:
 
 With eta = 1 and S = T this is the reference's DDPM chain; eta = 0 is deterministic after x_T.  Pure host code.
 
+``ddim_x0_table`` is the second table of a chain that clips the predicted x0 (``osd_sample_chain_clipped``): the same step unfolded at
+x0^, so that the clamp can sit between the two halves.
+
 ``known_level_table`` is the second table of a chain around observed values (``osd_sample_chain_known``): the noise level each
 step arrives at, at which the observations are put back.
 """
@@ -54,6 +57,39 @@ def ddim_step_table(alphas_cumprod, timesteps, eta: float):
         coef[s, 1] = math.sqrt(max(1.0 - ap - sigma * sigma, 0.0)) - math.sqrt(ap) * math.sqrt(1.0 - a) / math.sqrt(a)
         coef[s, 2] = sigma
     return tau.astype(np.int32), coef.astype(np.float32)
+
+
+def ddim_x0_table(alphas_cumprod, timesteps, eta: float) -> np.ndarray:
+    """fp32 [S][4] rows (P_s, Q_s, E_s, F_s) for ``osd_sample_chain_clipped``: the step of ``ddim_step_table`` unfolded at x0^,
+
+        x0^ = P*x + Q*eps,   x' = E*clip(x0^) + F*x + C*z       (C = sigma: slot 2 of ``ddim_step_table``'s row)
+        P = 1/sqrt(abar),  Q = -sqrt(1 - abar)/sqrt(abar),  dir = sqrt(max(1 - abar' - sigma^2, 0))
+        E = sqrt(abar') - dir*sqrt(abar)/sqrt(1 - abar),  F = dir/sqrt(1 - abar)
+
+    so that the direction term uses the eps the clipped x0^ implies, (x - sqrt(abar)*x0c)/sqrt(1 - abar).  Without a clamp
+    E*P + F = A and E*Q = B.  Formed in float64 from the fp32 buffer and rounded once, like ``ddim_step_table``, and rejecting what it
+    rejects; row 0 has E = 1, F = 0 exactly (the last step returns the clipped x0^ itself)."""
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"eta={eta} outside [0, 1]")
+    if hasattr(alphas_cumprod, "detach"):
+        alphas_cumprod = alphas_cumprod.detach().cpu().float().numpy()
+    abar = np.asarray(alphas_cumprod, dtype=np.float32).astype(np.float64)
+    tau = np.asarray(timesteps, dtype=np.int64).reshape(-1)
+    T = abar.shape[0]
+    if tau.size < 1 or tau.min() < 0 or tau.max() >= T:
+        raise ValueError(f"timesteps must be a non-empty list inside [0, {T})")
+    coef = np.zeros((tau.size, 4), dtype=np.float64)
+    for s in range(tau.size):
+        a = abar[tau[s]]
+        ap = abar[tau[s - 1]] if s > 0 else 1.0
+        ratio = (1.0 - ap) / (1.0 - a) if a < 1.0 else 0.0
+        sigma = eta * math.sqrt(ratio) * math.sqrt(max(1.0 - a / ap, 0.0))
+        direction = math.sqrt(max(1.0 - ap - sigma * sigma, 0.0))
+        f = direction / math.sqrt(1.0 - a) if a < 1.0 else 0.0
+        coef[s] = (1.0 / math.sqrt(a), -math.sqrt(max(1.0 - a, 0.0)) / math.sqrt(a), math.sqrt(ap) - f * math.sqrt(a), f)
+    coef[0, 2:] = (1.0, 0.0)
+    return coef.astype(np.float32)
 
 
 def known_level_table(sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, timesteps) -> np.ndarray:

@@ -321,6 +321,9 @@ class BiologyAwareDiffusionModel(nn.Module):
         # guidance_scale).  A plain attribute -- no parameter, no buffer: it goes through condition_embed / cond_proj like any condition,
         # and state_dict() keeps the reference's keys.  None: the model has none (every reference checkpoint)
         self.null_condition = m.get("null_condition")
+        # per-feature bounds the predicted x0 is clipped to inside every sampling step (sample(x0_bounds=...); generate.assemble_bounds
+        # describes the forms: a (lo, hi) pair or a dict over mutations / expression / pathways).  None: no clipping, today's sampler
+        self.x0_bounds = None
         # optional constraint losses (set_constraints); None = the reference's eps-MSE only
         self._constraints = None
         self._constraints_version = 0
@@ -595,7 +598,7 @@ class BiologyAwareDiffusionModel(nn.Module):
     @torch.no_grad()
     def sample(self, conditions, num_samples: int = 1, *, x_T=None, noise=None, seed: Optional[int] = None,
                row_offset: int = 0, return_mutation_mask: bool = False, num_inference_steps: Optional[int] = None,
-               eta: float = 0.0, guidance_scale: float = 1.0, known=None):
+               eta: float = 0.0, guidance_scale: float = 1.0, known=None, x0_bounds=None):
         """Full reverse chain.  ``x_T`` [N,D] and ``noise`` [T-1,N,D] (draw order t = T-1..1) inject the
         random draws; otherwise Philox(seed, row_offset + row) generates them on the device.
 
@@ -612,8 +615,23 @@ class BiologyAwareDiffusionModel(nn.Module):
         overwritten with the observation noised to the level the state has reached, sqrt(abar')*known + sqrt(1 - abar')*z, z the
         step's own draw at that element -- so ``noise`` is accepted at eta = 0 too, where it feeds only the observed elements.
         Works with the DDPM chain, ``num_inference_steps`` / ``eta`` and ``guidance_scale``; per-layer kernels
-        (``last_sampler == "graph"``), fp32.  ``known=None`` or all-NaN is the unconstrained call."""
+        (``last_sampler == "graph"``), fp32.  ``known=None`` or all-NaN is the unconstrained call.
+
+        ``x0_bounds`` clips the predicted clean sample x0^ = (x - sqrt(1-abar) eps)/sqrt(abar) of every step to per-feature bounds before
+        the posterior update (clip_denoised / clip_sample elsewhere), the direction term using the eps the clipped x0^ implies: a
+        ``(lo, hi)`` pair of scalars or [D] arrays, or a dict over ``mutations`` / ``expression`` / ``pathways`` of such pairs
+        (``generate.assemble_bounds``; a missing block or a ``None`` side is free).  Every returned element lies inside its bounds
+        exactly -- except observed elements of ``known``, which come back as observed.  ``None`` takes ``model.x0_bounds`` (``None`` by
+        default: no clipping, today's entry points on any engine, the same bits); ``False`` ignores the attribute.  Works with the DDPM
+        chain, ``num_inference_steps`` / ``eta``, ``guidance_scale`` and ``known``; per-layer kernels (``last_sampler == "graph"``), fp32
+        (``precision = "bf16x3"`` raises ValueError)."""
         guide = self._guidance(guidance_scale)
+        if x0_bounds is None:
+            x0_bounds = self.x0_bounds
+        bounds = None
+        if x0_bounds is not None and x0_bounds is not False:
+            from .generate import assemble_bounds
+            bounds = assemble_bounds(x0_bounds, self.mutation_dim, self.expression_dim, self.pathway_dim)
         kn = None
         if known is not None:
             kn = self._prep(known, self.data_dim, "known")
@@ -654,7 +672,7 @@ class BiologyAwareDiffusionModel(nn.Module):
         if seed is None:
             seed = _draw_seed()
         flags = self._flags() | (L.OSD_F_GRAPH if self.use_graph else 0)
-        engine = 0 if (guide is not None or kn is not None) else L.lib().osd_sample_engine(eng.handle, n, flags)
+        engine = 0 if (guide is not None or kn is not None or bounds is not None) else L.lib().osd_sample_engine(eng.handle, n, flags)
         if engine < 0:
             L.check(engine)
         if engine == 1:
@@ -668,7 +686,20 @@ class BiologyAwareDiffusionModel(nn.Module):
             return int(v.value)
 
         gave_up_before = counter(b"chain_fallbacks")
-        if kn is not None:
+        if bounds is not None:
+            from .ddim import ddim_x0_table, known_level_table
+            tau, coef = plan if plan is not None else (None, None)
+            x0c = None if tau is None else ddim_x0_table(self.alphas_cumprod, tau, eta)
+            level = None
+            if tau is not None and kn is not None:
+                level = known_level_table(self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, tau)
+            L.check(L.lib().osd_sample_chain_clipped(eng.handle, L.ptr(conditions), n, L.ptr(xT), L.ptr(zs), seed, int(row_offset),
+                                                     L.ptr(out), L.ptr(mask), flags, None if tau is None else tau.ctypes.data,
+                                                     None if coef is None else coef.ctypes.data, None if x0c is None else x0c.ctypes.data,
+                                                     None if level is None else level.ctypes.data, 0 if tau is None else int(tau.size),
+                                                     None if guide is None else guide[1].ctypes.data, 1.0 if guide is None else guide[0],
+                                                     L.ptr(kn), self.data_dim, bounds[0].ctypes.data, bounds[1].ctypes.data))
+        elif kn is not None:
             from .ddim import known_level_table
             tau, coef = plan if plan is not None else (None, None)
             level = None if tau is None else known_level_table(self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, tau)

@@ -56,6 +56,52 @@ def assemble_known(known, n: int, mutation_dim: int, expression_dim: int, pathwa
     return np.array(block(known, D, "features"), dtype=np.float32)        # a copy: the caller's array stays the caller's
 
 
+def assemble_bounds(spec, mutation_dim: int, expression_dim: int, pathway_dim: int):
+    """(lo, hi), two float32 [D] arrays, of ``model.sample(x0_bounds=...)``: the bounds the predicted x0 is clipped to.
+
+    ``spec`` is a ``(lo, hi)`` pair of scalars or [D] arrays, or a dict with any of ``mutations`` / ``expression`` / ``pathways``, each a
+    ``(lo, hi)`` pair of scalars or block-wide arrays, or ``None``.  A missing block is free and a ``None`` side is infinite.
+    ValueError on a wrong width, a NaN, lo > hi, or an unknown key."""
+    widths = {"mutations": int(mutation_dim), "expression": int(expression_dim), "pathways": int(pathway_dim)}
+    D = sum(widths.values())
+
+    def side(v, width, fill, name):
+        if v is None:
+            return np.full(width, fill, dtype=np.float32)
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        v = np.asarray(v, dtype=np.float32)
+        if v.ndim == 0:
+            v = np.full(width, v, dtype=np.float32)
+        if v.ndim != 1 or v.shape[0] != width:
+            raise ValueError(f"x0_bounds {name}: expected a scalar or [{width}] values, got shape {tuple(v.shape)}")
+        if np.isnan(v).any():
+            raise ValueError(f"x0_bounds {name} holds NaN: None (or an infinity) leaves a side free")
+        return v
+
+    def pair(v, width, name):
+        if isinstance(v, (str, bytes, dict)) or not hasattr(v, "__len__") or len(v) != 2:
+            raise ValueError(f"x0_bounds {name}: expected a (lo, hi) pair")
+        lo, hi = side(v[0], width, -np.inf, name + " lo"), side(v[1], width, np.inf, name + " hi")
+        if (lo > hi).any():
+            raise ValueError(f"x0_bounds {name}: lo > hi at index {int(np.argmax(lo > hi))}")
+        return lo, hi
+
+    if isinstance(spec, dict):
+        extra = set(spec) - set(widths)
+        if extra:
+            raise ValueError(f"x0_bounds: unknown block(s) {sorted(extra)}; expected any of {list(widths)}")
+        lo, hi = np.full(D, -np.inf, dtype=np.float32), np.full(D, np.inf, dtype=np.float32)
+        c0 = 0
+        for name, width in widths.items():
+            if spec.get(name) is not None:
+                lo[c0:c0 + width], hi[c0:c0 + width] = pair(spec[name], width, name)
+            c0 += width
+        return lo, hi
+    lo, hi = pair(spec, D, "features")
+    return np.ascontiguousarray(lo, dtype=np.float32).copy(), np.ascontiguousarray(hi, dtype=np.float32).copy()
+
+
 class SyntheticPatientGenerator:
     """Generate synthetic patients using a trained model (utils/generate.py:19)."""
 
@@ -106,6 +152,17 @@ class SyntheticPatientGenerator:
             return 1.0
         return float(guidance_scale)
 
+    def _x0_bounds(self, x0_bounds):
+        """``x0_bounds`` of generate / generate_scenarios / impute as model.sample takes it: the caller's, else the config's
+        ``generation.x0_bounds`` (e.g. ``{mutations: [0, 1], expression: [-4, 4]}``); an absent key changes nothing."""
+        if hasattr(self.model, "vae"):
+            if x0_bounds is not None and x0_bounds is not False:
+                raise ValueError("x0_bounds clips inside the diffusion model's reverse chain and is not accepted for a cVAE model")
+            return None                 # the config's default speaks to the diffusion sampler
+        if x0_bounds is None:
+            x0_bounds = (self.config.get("generation") or {}).get("x0_bounds")
+        return x0_bounds
+
     def _known(self, known, n: int):
         """``known`` of generate / generate_scenarios as the device tensor model.sample takes, or None."""
         if known is None:
@@ -115,7 +172,7 @@ class SyntheticPatientGenerator:
     @torch.no_grad()
     def generate(self, num_samples: int, scenario: Optional[Dict] = None, guidance_scale: float = 1.0,
                  *, seed: Optional[int] = None, row_offset: int = 0, x_T=None, noise=None, sampling_steps: Optional[int] = None,
-                 eta: float = 0.0, known=None) -> Dict[str, np.ndarray]:
+                 eta: float = 0.0, known=None, x0_bounds=None) -> Dict[str, np.ndarray]:
         """utils/generate.py:96-144.  ``guidance_scale`` is the classifier-free-guidance strength (``model.sample(guidance_scale=w)``:
         1 the plain conditional sampler, larger values follow the scenario more strongly) when the model has a null condition
         (``model.null_condition``: trained with ``training.condition_dropout``).  A model without one -- every reference
@@ -126,7 +183,12 @@ class SyntheticPatientGenerator:
         implicitly: ``generate(n, sc, sampling_steps=config["generation"]["sampling_steps"])`` honours it.
         ``known`` (``assemble_known``: an [n or 1, D] array, or a dict of ``mutations`` / ``expression`` / ``pathways`` blocks, NaN =
         free) holds part of every patient fixed: the returned blocks carry the observed values exactly and the rest is sampled
-        around them (``model.sample(known=...)``)."""
+        around them (``model.sample(known=...)``).
+        ``x0_bounds`` (``assemble_bounds``: a ``(lo, hi)`` pair or a dict over ``mutations`` / ``expression`` / ``pathways``) clips the
+        predicted clean patient of every step to per-feature bounds (``model.sample(x0_bounds=...)``) -- the usual companion of a large
+        ``guidance_scale`` and of few ``sampling_steps``; every returned value lies inside its bounds.  Default: the config's
+        ``generation.x0_bounds`` when it has one, else ``model.x0_bounds``; ``False`` switches it off."""
+        x0_bounds = self._x0_bounds(x0_bounds)
         logger.info(f"Generating {num_samples} synthetic patients...")
         if scenario:
             logger.info(f"Scenario: {scenario}")
@@ -150,7 +212,7 @@ class SyntheticPatientGenerator:
             samples, mask = self.model.sample(conditions, num_samples=num_samples, seed=seed, row_offset=row_offset,
                                               x_T=x_T, noise=noise, return_mutation_mask=True, num_inference_steps=sampling_steps,
                                               eta=eta, guidance_scale=self._guidance_scale(guidance_scale),
-                                              known=self._known(known, num_samples))
+                                              known=self._known(known, num_samples), x0_bounds=x0_bounds)
             samples = samples.cpu().numpy()
             # (mutations > 0.5).astype(float), evaluated by the last reverse step's epilogue on the device
             mutations = mask.cpu().numpy().astype(float)
@@ -162,7 +224,8 @@ class SyntheticPatientGenerator:
 
     def generate_scenarios(self, scenarios: List[Dict], samples_per_scenario: int, *, seed: Optional[int] = None,
                            batched: bool = True, sampling_steps: Optional[int] = None,
-                           eta: float = 0.0, guidance_scale: float = 1.0, known=None) -> Dict[str, Dict[str, np.ndarray]]:
+                           eta: float = 0.0, guidance_scale: float = 1.0, known=None,
+                           x0_bounds=None) -> Dict[str, Dict[str, np.ndarray]]:
         """utils/generate.py:146-175: one result dict per scenario name.
 
         The reference runs the scenarios one after the other, each a chain of T sequential steps.  Rows never interact and the
@@ -171,14 +234,17 @@ class SyntheticPatientGenerator:
         launch latency, not by rows, and T steps over 3000 rows cost about what T steps over 1000 do.  ``batched=False`` restores
         the reference's loop (one chain, and one freshly drawn Philox seed, per scenario).  ``sampling_steps`` / ``eta`` select the
         strided DDIM sampler, ``guidance_scale`` the guided one, as in ``generate``.  ``known`` ([samples_per_scenario or 1, D] or a
-        dict of blocks, as in ``generate``) holds the same observed values in every scenario: the counterfactual question."""
+        dict of blocks, as in ``generate``) holds the same observed values in every scenario: the counterfactual question.
+        ``x0_bounds`` as in ``generate``."""
+        x0_bounds = self._x0_bounds(x0_bounds)
         if not batched or hasattr(self.model, "vae") or len(scenarios) < 2:
             out = {}
             for scenario in scenarios:
                 name = scenario["name"]
                 logger.info(f"\nGenerating scenario: {name}")
                 out[name] = self.generate(num_samples=samples_per_scenario, scenario=scenario["conditions"],
-                                          sampling_steps=sampling_steps, eta=eta, guidance_scale=guidance_scale, known=known)
+                                          sampling_steps=sampling_steps, eta=eta, guidance_scale=guidance_scale, known=known,
+                                          x0_bounds=x0_bounds)
             return out
         n = int(samples_per_scenario)
         for scenario in scenarios:
@@ -192,7 +258,7 @@ class SyntheticPatientGenerator:
         with torch.no_grad():
             samples, mask = self.model.sample(conditions, num_samples=conditions.shape[0], seed=seed, return_mutation_mask=True,
                                               num_inference_steps=sampling_steps, eta=eta,
-                                              guidance_scale=self._guidance_scale(guidance_scale), known=kn)
+                                              guidance_scale=self._guidance_scale(guidance_scale), known=kn, x0_bounds=x0_bounds)
         samples, mask, cond_np = samples.cpu().numpy(), mask.cpu().numpy().astype(float), conditions.cpu().numpy()
         md, ed = self.mutation_dim, self.expression_dim
         out = {}
@@ -204,11 +270,13 @@ class SyntheticPatientGenerator:
         return out
 
     def impute(self, features, conditions, *, seed: Optional[int] = None, sampling_steps: Optional[int] = None, eta: float = 0.0,
-               guidance_scale: float = 1.0) -> Dict[str, np.ndarray]:
+               guidance_scale: float = 1.0, x0_bounds=None) -> Dict[str, np.ndarray]:
         """Fill the holes of real rows: ``features`` [n, D] with NaN where a value is missing, ``conditions`` [n, condition_dim] the
-        rows' own.  Observed values come back exactly, the holes are sampled around them; returns ``generate``'s dictionary."""
+        rows' own.  Observed values come back exactly, the holes are sampled around them; returns ``generate``'s dictionary.
+        ``x0_bounds`` as in ``generate``: the holes stay inside the bounds, the observed values are the observed values."""
         if hasattr(self.model, "vae"):
             raise ValueError("impute conditions the diffusion model's reverse chain and is not accepted for a cVAE model")
+        x0_bounds = self._x0_bounds(x0_bounds)
         if isinstance(conditions, torch.Tensor):
             cond = conditions.detach().to(device=self.device, dtype=torch.float32)
         else:
@@ -222,7 +290,8 @@ class SyntheticPatientGenerator:
         md, ed = self.mutation_dim, self.expression_dim
         with torch.no_grad():
             samples, mask = self.model.sample(cond, num_samples=n, seed=seed, return_mutation_mask=True, num_inference_steps=sampling_steps,
-                                              eta=eta, guidance_scale=self._guidance_scale(guidance_scale), known=self._known(features, n))
+                                              eta=eta, guidance_scale=self._guidance_scale(guidance_scale), known=self._known(features, n),
+                                              x0_bounds=x0_bounds)
         samples = samples.cpu().numpy()
         return {"mutations": mask.cpu().numpy().astype(float), "expression": samples[:, md:md + ed], "pathways": samples[:, md + ed:],
                 "conditions": cond.cpu().numpy()}
