@@ -134,7 +134,8 @@ int osd_set_option(osd_handle *h, const char *name, int64_t value);
  * that ran last), "last_precision" (0 | 1, what the most recent forward / p_sample / sample computed in), "split_supported"
  * (1 when "precision" 1 applies to this model), "panel_chain_supported" / "squad_chain_supported" (1 when "chain_variant"
  * 2 / 3 applies to this model), "last_train_path" (what the most recent osd_train_loss_fwd_bwd or osd_denoiser_backward call on
- * the handle ran, an OR of the OSD_TP_* bits below; cleared at the start of either call).  Any other name: OSD_EINVAL. */
+ * the handle ran, an OR of the OSD_TP_* bits below; cleared at the start of either call), "prediction_type" (OSD_PRED_*, what
+ * osd_set_prediction set last; 0 on a new handle).  Any other name: OSD_EINVAL. */
 int osd_get_option(osd_handle *h, const char *name, int64_t *value);
 
 /* "last_train_path" bits */
@@ -150,6 +151,7 @@ int osd_get_option(osd_handle *h, const char *name, int64_t *value);
 #define OSD_TP_WGRAD_GROUP   (1 << 9)   /* at least one grouped weight-gradient launch */
 #define OSD_TP_MSE_BF16      (1 << 10)  /* output_proj + MSE on the bf16 matrix pipe ("precision" 1) */
 #define OSD_TP_LOSS_EPI      (1 << 11)  /* output_proj ran the configurable loss epilogue (osd_set_loss); never set on the default path */
+#define OSD_TP_TARGET        (1 << 12)  /* q_sample wrote a non-eps training target (osd_set_prediction); never set on the default path */
 
 /* Schedule + time-embedding tables, computed by the host with the reference's own
  * fp32 expressions so they are bit-identical (models/diffusion.py:299-326, 131-137,
@@ -183,6 +185,37 @@ int osd_denoiser_forward(osd_handle *h, const float *x, const int32_t *t_index, 
  * noise_in NULL -> Philox(seed, row_offset) normals, written to noise_out. */
 int osd_q_sample(osd_handle *h, const float *x0, const int32_t *t_index, const float *noise_in,
                  int64_t n, uint64_t seed, int64_t row_offset, float *x_t, float *noise_out);
+
+/* ---- what the network predicts ------------------------------------------------------------------------------------------
+ * With a = sqrt_ac[t], b = sqrt_1m_ac[t] and `out` the network's raw output:
+ *   OSD_PRED_EPSILON  target eps                 x0^ = (1/a) x_t - (b/a) out     (the reference's; the state of a new handle)
+ *   OSD_PRED_V        target a*eps - b*x0        x0^ = a x_t - b out             (Salimans & Ho 2022)
+ *   OSD_PRED_SAMPLE   target x0                  x0^ = out
+ * x0^ = P x_t + Q out.  The training target is formed inside the q_sample kernels of osd_train_loss_fwd_bwd (fp32: two rounded
+ * products and one subtraction for v) and the loss compares the output with it; such a call sets OSD_TP_TARGET.  The constraint
+ * losses take x0^ from a device table [T][2] of (P, Q).  Every reverse step is x' = E x0^ + F x_t + C z with E, F, C independent of the
+ * type, so the DDPM rows of osd_p_sample_step / osd_sample_chain* are refolded as A = E P + F, B = E Q (float64 from the schedule's
+ * fp32 scalars, rounded once) together with the (P, Q, E, F) rows of the clipped chain: every engine follows the type through its
+ * tables.  Strided plans (osd_sample_chain_steps and the options' steps arguments) carry the caller's rows: fold them for the same type
+ * (ddim.py).  Guidance combines raw outputs, which is guidance in eps-space for every type (all three readings of eps are affine
+ * in `out`, the x_t term cancels).
+ * Persistent like osd_set_loss; synchronises the handle's stream.  OSD_PRED_EPSILON restores the tables osd_set_schedule folded, bit
+ * for bit; a later osd_set_schedule folds for the current type.  OSD_ESTATE before osd_set_schedule, OSD_EINVAL for an unknown type. */
+#define OSD_PRED_EPSILON 0
+#define OSD_PRED_V       1
+#define OSD_PRED_SAMPLE  2
+int osd_set_prediction(osd_handle *h, int type);
+
+/* osd_q_sample that writes the current type's training target where osd_q_sample writes the noise: target_out dev [n][D], required,
+ * distinct from noise_in and x0.  For OSD_PRED_EPSILON it is osd_q_sample (target_out = the noise). */
+int osd_q_sample_target(osd_handle *h, const float *x0, const int32_t *t_index, const float *noise_in,
+                        int64_t n, uint64_t seed, int64_t row_offset, float *x_t, float *target_out);
+
+/* Row-affine conversion of a raw output of the current type: dst[r] = U[t_r] x_t[r] + V[t_r] out[r], as_kind OSD_PRED_* naming what
+ * dst is (OSD_PRED_SAMPLE: x0^ = P x_t + Q out; OSD_PRED_EPSILON: (x_t - a x0^)/b; OSD_PRED_V: a eps^ - b x0^).  (U, V) are formed in
+ * float64 from the schedule's fp32 buffers and rounded once.  t_index dev int32[n]; dst may alias out. */
+int osd_convert_prediction(osd_handle *h, const float *x_t, const int32_t *t_index, const float *out, int64_t n, int as_kind,
+                           float *dst);
 
 /* p_sample (models/diffusion.py:382-425): one reverse step at python-int t.
  * z NULL -> Philox(seed,row_offset,t).  In-place (x_out == x_t) is allowed. */
@@ -505,7 +538,7 @@ typedef struct osd_constraints {
   double mutexpr_weight;            /* config.yaml:59 mutation_expression_weight */
 } osd_constraints;
 /* Configures (c == NULL: clears) the terms osd_train_loss_fwd_bwd adds to the eps-MSE, evaluated on
- * x0_hat = (x_t - sqrt(1-ac_t) eps_hat) / sqrt(ac_t) (models/diffusion.py:405) against x0 of the batch:
+ * x0_hat = (x_t - sqrt(1-ac_t) eps_hat) / sqrt(ac_t) (models/diffusion.py:405; P x_t + Q out under osd_set_prediction) against x0 of the batch:
  * loss = mse + pathway_weight * L_pc + mutexpr_weight * L_me, gradients flow into eps_hat. */
 int osd_set_constraints(osd_handle *h, const osd_constraints *c);
 /* (mse, L_pc, L_me) of the last osd_train_loss_fwd_bwd call; synchronises the handle's stream.  With osd_set_loss, parts[0] is the

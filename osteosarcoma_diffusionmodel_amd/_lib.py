@@ -15,6 +15,8 @@ OSD_OK, OSD_EINVAL, OSD_ENOMEM, OSD_EHIP, OSD_ESTATE, OSD_EUNSUPPORTED = 0, -1, 
 OSD_COMM_ID_BYTES = 128
 OSD_LOSS_L2, OSD_LOSS_L1, OSD_LOSS_HUBER = 0, 1, 2
 OSD_TP_LOSS_EPI = 1 << 11
+OSD_TP_TARGET = 1 << 12
+OSD_PRED_EPSILON, OSD_PRED_V, OSD_PRED_SAMPLE = 0, 1, 2
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libosdiff.so"
 
@@ -52,6 +54,9 @@ _SIGNATURES = {
     "osd_load_weights": (C.c_int, [_P, C.POINTER(_P), C.c_int]),
     "osd_denoiser_forward": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, _P, C.c_int, C.POINTER(_P), C.c_uint64]),
     "osd_q_sample": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_uint64, C.c_int64, _P, _P]),
+    "osd_set_prediction": (C.c_int, [_P, C.c_int]),
+    "osd_q_sample_target": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_uint64, C.c_int64, _P, _P]),
+    "osd_convert_prediction": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, _P]),
     "osd_p_sample_step": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_uint64, C.c_int64, _P, C.c_int]),
     "osd_sample_chain": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_int64, _P, _P, C.c_int]),
     "osd_sample_engine": (C.c_int, [_P, C.c_int64, C.c_int]),

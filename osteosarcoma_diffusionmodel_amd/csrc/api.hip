@@ -428,6 +428,7 @@ static const Counter COUNTERS[] = {
     {"squad_chain_supported", [](osd_handle* h) -> int64_t { return squad_chain_supported(h); }},
     {"last_squad_panel", [](osd_handle* h) -> int64_t { return h->last_squad_rp; }},
     {"last_train_path", [](osd_handle* h) -> int64_t { return h->last_train_path; }},
+    {"prediction_type", [](osd_handle* h) -> int64_t { return h->pred_type; }},
 };
 
 }  // namespace osd
@@ -460,6 +461,7 @@ static int create_device_state(osd_handle* h) {
   OSD_HIP(hipMalloc((void**)&h->d_sqrt_ac, (size_t)T * 4));
   OSD_HIP(hipMalloc((void**)&h->d_sqrt_1m, (size_t)T * 4));
   OSD_HIP(hipMalloc((void**)&h->d_coef, (size_t)T * 4 * 4));
+  OSD_HIP(hipMalloc((void**)&h->d_pq, (size_t)T * 2 * 4 * 2));      // (P, Q) [T][2], then osd_convert_prediction's (U, V) [T][2]
   const size_t t_rows = (size_t)(T + 31) / 32 * 32;     // zero rows up to whole K steps of the grouped weight-gradient kernel (time_proj.weight)
   OSD_HIP(hipMalloc((void**)&h->d_time_emb, t_rows * a.time_dim * 4));
   OSD_HIP(hipMemset(h->d_time_emb, 0, t_rows * a.time_dim * 4));
@@ -523,7 +525,7 @@ int osd_destroy(osd_handle* h) {
   e = hipDeviceSynchronize();
   for (auto& s : h->slots) free_slot(s, true);
   free_slot(h->main, false);
-  float* bufs[] = {h->w_in_packed, h->w_out_packed, h->b_out_packed, h->chain_xpad, h->d_sqrt_ac, h->d_sqrt_1m, h->d_coef, h->d_time_emb, h->d_temb, h->train_arena, h->loss_dev,
+  float* bufs[] = {h->w_in_packed, h->w_out_packed, h->b_out_packed, h->chain_xpad, h->d_sqrt_ac, h->d_sqrt_1m, h->d_coef, h->d_pq, h->d_time_emb, h->d_temb, h->train_arena, h->loss_dev,
                    h->plan_temb, h->plan_coef};
   for (float* p : bufs) if (p) e = hipFree(p);
   if (h->plan_t) e = hipFree(h->plan_t);
@@ -584,43 +586,66 @@ int osd_get_option(osd_handle* h, const char* name, int64_t* value) {
   return OSD_EINVAL;
 }
 
+// The per-step tables that depend on what the network predicts (osd_set_prediction), from the schedule scalars osd_set_schedule kept:
+// d_coef (A, B, C, 0), sched_x0_coef (P, Q, E, F) and the device (P, Q) table of the constraint losses.  Every type's step is
+// x' = E*x0 + F*x + C*z with x0 = P*x + Q*out; epsilon keeps the expressions it always had.
+static int fold_schedule(osd_handle* h) {
+  const Arch& a = h->arch;
+  const float* post_coef = h->sched_post_coef.data();
+  const int kind = h->pred_type;
+  // fold the reference's six per-step scalars into x' = A*x + B*eps + C*z (see EpiPosterior)
+  std::vector<float> abc((size_t)a.T * 4, 0.f);
+  // ... and, for the chain that clips x0 (EpiPosteriorClip), the same scalars unfolded at x0: x0 = P*x + Q*eps, x' = E*x0 + F*x + C*z
+  h->sched_x0_coef.assign((size_t)a.T * 4, 0.f);
+  std::vector<float> pq((size_t)a.T * 2, 0.f);
+  for (int t = 0; t < a.T; ++t) {
+    const double c0 = post_coef[6 * t], c1 = post_coef[6 * t + 1], c2 = post_coef[6 * t + 2], c3 = post_coef[6 * t + 3],
+                 c4 = post_coef[6 * t + 4], c5 = post_coef[6 * t + 5];
+    float* r = &h->sched_x0_coef[4 * (size_t)t];
+    r[2] = t > 0 ? (float)(c2 / c3) : 1.f;
+    r[3] = t > 0 ? (float)(c4 / c3) : 0.f;
+    abc[4 * t + 2] = t > 0 ? (float)c5 : 0.f;
+    if (kind == OSD_PRED_EPSILON) {
+      if (t > 0) {
+        abc[4 * t] = (float)(c4 / c3 + c2 / (c1 * c3));
+        abc[4 * t + 1] = (float)(-c0 * c2 / (c1 * c3));
+      } else {
+        abc[0] = (float)(1.0 / c1);
+        abc[1] = (float)(-c0 / c1);
+      }
+      r[0] = (float)(1.0 / c1);
+      r[1] = (float)(-c0 / c1);
+      // what k_x0hat / k_x0hat_bwd compute in fp32 (they keep their own arithmetic for this type; the table is for osd_convert_prediction)
+      pq[2 * t] = 1.f / h->sched_sqrt_ac[t];
+      pq[2 * t + 1] = -(h->sched_sqrt_1m[t] / h->sched_sqrt_ac[t]);
+      continue;
+    }
+    // a = sqrt_ac[t], b = sqrt_1m_ac[t]: the model's fp32 buffers
+    const double sa = h->sched_sqrt_ac[t], sb = h->sched_sqrt_1m[t];
+    const double P = kind == OSD_PRED_V ? sa : 0.0, Q = kind == OSD_PRED_V ? -sb : 1.0;
+    const double E = t > 0 ? c2 / c3 : 1.0, F = t > 0 ? c4 / c3 : 0.0;
+    abc[4 * t] = (float)(E * P + F);
+    abc[4 * t + 1] = (float)(E * Q);
+    r[0] = (float)P; r[1] = (float)Q;
+    pq[2 * t] = (float)P; pq[2 * t + 1] = (float)Q;
+  }
+  OSD_HIP(hipMemcpy(h->d_coef, abc.data(), abc.size() * 4, hipMemcpyHostToDevice));
+  OSD_HIP(hipMemcpy(h->d_pq, pq.data(), pq.size() * 4, hipMemcpyHostToDevice));
+  h->conv_kind = -1;          // osd_convert_prediction's cached table belongs to the previous fold
+  return OSD_OK;
+}
+
 int osd_set_schedule(osd_handle* h, const float* sqrt_ac, const float* sqrt_1m_ac, const float* post_coef, const float* time_emb) {
   if (!h || !sqrt_ac || !sqrt_1m_ac || !post_coef || !time_emb) { set_error("null argument"); return OSD_EINVAL; }
   const Arch& a = h->arch;
   OSD_HIP(hipSetDevice(h->cfg.device));
   OSD_HIP(hipMemcpy(h->d_sqrt_ac, sqrt_ac, (size_t)a.T * 4, hipMemcpyHostToDevice));
   OSD_HIP(hipMemcpy(h->d_sqrt_1m, sqrt_1m_ac, (size_t)a.T * 4, hipMemcpyHostToDevice));
-  {
-    // fold the reference's six per-step scalars into x' = A*x + B*eps + C*z (see EpiPosterior)
-    std::vector<float> abc((size_t)a.T * 4, 0.f);
-    for (int t = 0; t < a.T; ++t) {
-      const double c0 = post_coef[6 * t], c1 = post_coef[6 * t + 1], c2 = post_coef[6 * t + 2], c3 = post_coef[6 * t + 3],
-                   c4 = post_coef[6 * t + 4], c5 = post_coef[6 * t + 5];
-      if (t > 0) {
-        abc[4 * t] = (float)(c4 / c3 + c2 / (c1 * c3));
-        abc[4 * t + 1] = (float)(-c0 * c2 / (c1 * c3));
-        abc[4 * t + 2] = (float)c5;
-      } else {
-        abc[0] = (float)(1.0 / c1);
-        abc[1] = (float)(-c0 / c1);
-        abc[2] = 0.f;
-      }
-    }
-    OSD_HIP(hipMemcpy(h->d_coef, abc.data(), abc.size() * 4, hipMemcpyHostToDevice));
-    // ... and, for the chain that clips x0 (EpiPosteriorClip), the same scalars unfolded at x0: x0 = P*x + Q*eps, x' = E*x0 + F*x + C*z
-    h->sched_x0_coef.assign((size_t)a.T * 4, 0.f);
-    for (int t = 0; t < a.T; ++t) {
-      const double c0 = post_coef[6 * t], c1 = post_coef[6 * t + 1], c2 = post_coef[6 * t + 2], c3 = post_coef[6 * t + 3], c4 = post_coef[6 * t + 4];
-      float* r = &h->sched_x0_coef[4 * (size_t)t];
-      r[0] = (float)(1.0 / c1);
-      r[1] = (float)(-c0 / c1);
-      r[2] = t > 0 ? (float)(c2 / c3) : 1.f;
-      r[3] = t > 0 ? (float)(c4 / c3) : 0.f;
-    }
-  }
-  OSD_HIP(hipMemcpy(h->d_time_emb, time_emb, (size_t)a.T * a.time_dim * 4, hipMemcpyHostToDevice));
+  h->sched_post_coef.assign(post_coef, post_coef + (size_t)a.T * 6);
   h->sched_sqrt_ac.assign(sqrt_ac, sqrt_ac + a.T);
   h->sched_sqrt_1m.assign(sqrt_1m_ac, sqrt_1m_ac + a.T);
+  OSD_TRY(fold_schedule(h));
+  OSD_HIP(hipMemcpy(h->d_time_emb, time_emb, (size_t)a.T * a.time_dim * 4, hipMemcpyHostToDevice));
   h->have_schedule = true;
   return OSD_OK;
 }
@@ -733,6 +758,74 @@ int osd_q_sample(osd_handle* h, const float* x0, const int32_t* t_index, const f
   const int* t_idx = nullptr;
   OSD_TRY(sanitize_t(h, h->stream, t_index, n, &t_idx));
   OSD_HIP(launch_q_sample(h->stream, x0, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise_in, n, h->arch.D, seed, (uint32_t)row_offset, x_t, noise_out));
+  return OSD_OK;
+}
+
+int osd_set_prediction(osd_handle* h, int type) {
+  if (!h) { set_error("null handle"); return OSD_EINVAL; }
+  if (type != OSD_PRED_EPSILON && type != OSD_PRED_V && type != OSD_PRED_SAMPLE) {
+    set_error("unknown prediction type %d (OSD_PRED_EPSILON, OSD_PRED_V or OSD_PRED_SAMPLE)", type);
+    return OSD_EINVAL;
+  }
+  if (!h->have_schedule) { set_error("osd_set_schedule must precede osd_set_prediction"); return OSD_ESTATE; }
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  OSD_HIP(hipDeviceSynchronize());       // chains in flight on the handle's own streams may still read the tables
+  const int before = h->pred_type;
+  h->pred_type = type;
+  const int rc = fold_schedule(h);
+  if (rc != OSD_OK) h->pred_type = before;
+  return rc;
+}
+
+int osd_q_sample_target(osd_handle* h, const float* x0, const int32_t* t_index, const float* noise_in, int64_t n, uint64_t seed,
+                        int64_t row_offset, float* x_t, float* target_out) {
+  if (!h || !h->have_schedule) { set_error("schedule not set"); return OSD_ESTATE; }
+  if (h->pred_type == OSD_PRED_EPSILON) {
+    // the target is the noise: osd_q_sample, plus the copy it skips when the caller injected the noise
+    OSD_TRY(osd_q_sample(h, x0, t_index, noise_in, n, seed, row_offset, x_t, noise_in ? nullptr : target_out));
+    if (noise_in && target_out && target_out != noise_in && n > 0)
+      OSD_HIP(hipMemcpyAsync(target_out, noise_in, (size_t)n * h->arch.D * 4, hipMemcpyDeviceToDevice, h->stream));
+    return OSD_OK;
+  }
+  OSD_TRY(check_rows(n));
+  if (!x0 || !t_index || !x_t || !target_out) { set_error("null tensor"); return OSD_EINVAL; }
+  if (target_out == noise_in || target_out == x0 || target_out == x_t) { set_error("target_out must be a buffer of its own"); return OSD_EINVAL; }
+  OSD_TRY(check_row_offset(row_offset, n));
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  const int* t_idx = nullptr;
+  OSD_TRY(sanitize_t(h, h->stream, t_index, n, &t_idx));
+  OSD_HIP(launch_q_sample(h->stream, x0, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise_in, n, h->arch.D, seed, (uint32_t)row_offset, x_t, target_out,
+                          nullptr, 0, 0, nullptr, h->pred_type));
+  return OSD_OK;
+}
+
+int osd_convert_prediction(osd_handle* h, const float* x_t, const int32_t* t_index, const float* out, int64_t n, int as_kind, float* dst) {
+  if (!h || !h->have_schedule) { set_error("schedule not set"); return OSD_ESTATE; }
+  OSD_TRY(check_rows(n));
+  if (!x_t || !t_index || !out || !dst) { set_error("null tensor"); return OSD_EINVAL; }
+  if (as_kind != OSD_PRED_EPSILON && as_kind != OSD_PRED_V && as_kind != OSD_PRED_SAMPLE) { set_error("unknown conversion %d (OSD_PRED_*)", as_kind); return OSD_EINVAL; }
+  OSD_HIP(hipSetDevice(h->cfg.device));
+  const int T = h->arch.T;
+  float* uv_dev = h->d_pq + 2 * (size_t)T;
+  if (h->conv_kind != as_kind) {
+    std::vector<float> uv((size_t)T * 2);
+    for (int t = 0; t < T; ++t) {
+      const double a = h->sched_sqrt_ac[t], b = h->sched_sqrt_1m[t];
+      const double P = h->pred_type == OSD_PRED_EPSILON ? 1.0 / a : h->pred_type == OSD_PRED_V ? a : 0.0;
+      const double Q = h->pred_type == OSD_PRED_EPSILON ? -b / a : h->pred_type == OSD_PRED_V ? -b : 1.0;
+      const double Ue = (1.0 - a * P) / b, Ve = -a * Q / b;      // eps^ = (x_t - a x0^) / b
+      double U = P, V = Q;
+      if (as_kind == OSD_PRED_EPSILON) { U = Ue; V = Ve; }
+      if (as_kind == OSD_PRED_V) { U = a * Ue - b * P; V = a * Ve - b * Q; }
+      uv[2 * t] = (float)U; uv[2 * t + 1] = (float)V;
+    }
+    OSD_HIP(hipStreamSynchronize(h->stream));      // an earlier conversion may still read the table
+    OSD_HIP(hipMemcpy(uv_dev, uv.data(), uv.size() * 4, hipMemcpyHostToDevice));
+    h->conv_kind = as_kind;
+  }
+  const int* t_idx = nullptr;
+  OSD_TRY(sanitize_t(h, h->stream, t_index, n, &t_idx));
+  OSD_HIP(launch_row_affine(h->stream, x_t, t_idx, reinterpret_cast<const float2*>(uv_dev), out, n, h->arch.D, dst));
   return OSD_OK;
 }
 

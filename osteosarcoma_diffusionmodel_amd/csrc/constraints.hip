@@ -314,6 +314,34 @@ hipError_t launch_x0hat_bwd(hipStream_t s, const float* g_x0, const int* t_idx, 
   return hipGetLastError();
 }
 
+// ---- x0_hat of any prediction type (osd_set_prediction) and the conversions of osd_convert_prediction: a row-affine map -----
+// One workgroup walks whole rows (the row's (U, V) is a wave-uniform load, no 64-bit division per element); the products are rounded
+// separately and added, as torch evaluates U*x + V*out.
+__global__ __launch_bounds__(256) void k_row_affine(const float* x_t, const int* t, const float2* pq, const float* out, int64_t rows, int D, float* dst) {
+  for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+    const float2 c = pq[t[r]];
+    const float* xr = x_t + r * D; const float* orow = out + r * D; float* dr = dst + r * D;
+    for (int j = threadIdx.x; j < D; j += 256) dr[j] = __fadd_rn(__fmul_rn(c.x, xr[j]), __fmul_rn(c.y, orow[j]));
+  }
+}
+__global__ __launch_bounds__(256) void k_row_affine_bwd(const float* g, const int* t, const float2* pq, int64_t rows, int D, float* d_out) {
+  for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+    const float q = pq[t[r]].y;
+    const float* gr = g + r * D; float* dr = d_out + r * D;
+    for (int j = threadIdx.x; j < D; j += 256) dr[j] = __fadd_rn(dr[j], __fmul_rn(gr[j], q));
+  }
+}
+hipError_t launch_row_affine(hipStream_t s, const float* x_t, const int* t_idx, const float2* pq, const float* out, int64_t rows, int D, float* dst) {
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_row_affine, (int)(rows > 4096 ? 4096 : rows), 256, 0, s, x_t, t_idx, pq, out, rows, D, dst);
+  return hipGetLastError();
+}
+hipError_t launch_row_affine_bwd(hipStream_t s, const float* g, const int* t_idx, const float2* pq, int64_t rows, int D, float* d_out) {
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_row_affine_bwd, (int)(rows > 4096 ? 4096 : rows), 256, 0, s, g, t_idx, pq, rows, D, d_out);
+  return hipGetLastError();
+}
+
 // ---- host side: plans ------------------------------------------------------------------------------------------
 void cons_free_plan(ConsPlan* p) {
   int* bufs[] = {p->pw_off, p->pw_mem, p->pw_of, p->cols_a, p->cols_b};

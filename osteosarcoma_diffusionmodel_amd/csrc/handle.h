@@ -210,6 +210,11 @@ struct osd_handle {
   float* parts_dev = nullptr;
   // the eps-loss of the training step (osd_set_loss): persistent.  loss_kind OSD_LOSS_*, loss_tw = per-timestep weights [T] on the device while
   // a table is set (loss_tw_set), else every row weighs 1.  OSD_LOSS_L2 without a table is the default and runs EpiMse
+  // what the network predicts (osd_set_prediction): persistent.  pred_type OSD_PRED_*; sched_post_coef = the six per-step scalars as
+  // osd_set_schedule received them, from which fold_schedule (api.hip) refolds d_coef / sched_x0_coef / d_pq for the type.  d_pq: dev
+  // (P, Q) [T][2] of x0^ = P x_t + Q out (the constraint losses), then the (U, V) [T][2] of osd_convert_prediction for conv_kind (-1: none)
+  int pred_type = 0; std::vector<float> sched_post_coef;
+  float* d_pq = nullptr; int conv_kind = -1;
   int loss_kind = 0; float loss_delta = 1.0f;
   float* loss_tw = nullptr; bool loss_tw_set = false;
   std::vector<void*> wg_plans;       // grouped weight-gradient launches (wgrad_group.hip): one cached work list per flush point

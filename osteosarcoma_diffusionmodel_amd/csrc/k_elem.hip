@@ -83,6 +83,26 @@ __device__ __forceinline__ void zero_pad(float* row, int cols, int ldxt, int c) 
     for (int k = cols; k < ldxt; ++k) row[k] = 0.f;
 }
 
+// The training target (osd_set_prediction) in the pass that has eps and x0 in registers: KIND OSD_PRED_EPSILON leaves eps (today's
+// kernel), OSD_PRED_V forms v = a*eps - b*x0 as torch would in fp32 -- two separately rounded products, one subtraction --,
+// OSD_PRED_SAMPLE is x0 itself.  The non-eps kinds store the target where eps went (noise_out), injected noise or not.
+template <int KIND>
+__device__ __forceinline__ float4 q_target(float a, float b, const float4& x, const float4& n) {
+  if constexpr (KIND == OSD_PRED_V) {
+    float4 v;
+    v.x = __fsub_rn(__fmul_rn(a, n.x), __fmul_rn(b, x.x));
+    v.y = __fsub_rn(__fmul_rn(a, n.y), __fmul_rn(b, x.y));
+    v.z = __fsub_rn(__fmul_rn(a, n.z), __fmul_rn(b, x.z));
+    v.w = __fsub_rn(__fmul_rn(a, n.w), __fmul_rn(b, x.w));
+    return v;
+  } else if constexpr (KIND == OSD_PRED_SAMPLE) {
+    return x;
+  } else {
+    return n;
+  }
+}
+
+template <int KIND>
 __global__ void k_q_sample(const float* x0, const int* t, const float* sqrt_ac, const float* sqrt_1m, const float* noise_in,
                            int64_t rows, int cols, uint64_t seed, uint32_t row_offset, float* x_t, int ldxt, float* noise_out, int* t_out, int T,
                            ZeroList zl) {
@@ -111,17 +131,23 @@ __global__ void k_q_sample(const float* x0, const int* t, const float* sqrt_ac, 
     o.w = __fadd_rn(__fmul_rn(a, x.w), __fmul_rn(b, n.w));
     st4g(x_t + r * ldxt, c, cols, o);
     zero_pad(x_t + r * ldxt, cols, ldxt, c);
-    if (noise_out && noise_out != noise_in) st4g(noise_out + r * cols, c, cols, n);
+    if constexpr (KIND == OSD_PRED_EPSILON) {
+      if (noise_out && noise_out != noise_in) st4g(noise_out + r * cols, c, cols, n);
+    } else {
+      if (noise_out) st4g(noise_out + r * cols, c, cols, q_target<KIND>(a, b, x, n));
+    }
   }
 }
 hipError_t launch_q_sample(hipStream_t s, const float* x0, const int* t, const float* sqrt_ac, const float* sqrt_1m,
                            const float* noise_in, int64_t rows, int cols, uint64_t seed, uint32_t row_offset,
-                           float* x_t, float* noise_out, int* t_out, int T, int ldxt, const ZeroList* zl) {
+                           float* x_t, float* noise_out, int* t_out, int T, int ldxt, const ZeroList* zl, int kind) {
   if (rows <= 0) return hipSuccess;
   if (!t && (!t_out || T < 1)) return hipErrorInvalidValue;
+  if (kind != OSD_PRED_EPSILON && (noise_out == noise_in || noise_out == x0)) return hipErrorInvalidValue;   // the target needs a buffer of its own
   ZeroList z{};
   if (zl) z = *zl;
-  hipLaunchKernelGGL(k_q_sample, ew_grid(rows * ((cols + 3) / 4)), 256, 0, s, x0, t, sqrt_ac, sqrt_1m, noise_in, rows, cols, seed,
+  auto k = kind == OSD_PRED_V ? k_q_sample<OSD_PRED_V> : kind == OSD_PRED_SAMPLE ? k_q_sample<OSD_PRED_SAMPLE> : k_q_sample<OSD_PRED_EPSILON>;
+  hipLaunchKernelGGL(k, ew_grid(rows * ((cols + 3) / 4)), 256, 0, s, x0, t, sqrt_ac, sqrt_1m, noise_in, rows, cols, seed,
                      row_offset, x_t, ldxt > 0 ? ldxt : cols, noise_out, t_out, T, z);
   return hipGetLastError();
 }
@@ -136,6 +162,7 @@ hipError_t launch_q_sample(hipStream_t s, const float* x0, const int* t, const f
 // quads per thread in flight at D = 2000.  First version (one quad per thread over a flat index): 37 us = 3.6 TB/s; row by row with
 // the zero list folded in: 40 us; all QS_ROWS rows' loads ahead of the stores: 35.4 us = 3.8 TB/s (QS_ROWS 2: 35.9, 8: 46.8).
 constexpr int QS_ROWS = 4;
+template <int KIND>
 __global__ __launch_bounds__(256) void k_q_sample_src(BatchSrc b, const int* t, const float* sqrt_ac, const float* sqrt_1m, const float* noise_in,
                                                       int64_t rows, int cols, int cd, uint64_t seed, uint32_t row_offset, float* x_t, int ldxt,
                                                       float* noise_out, int* t_out, int T, float* cond_out, float* x0_out, ZeroList zl) {
@@ -205,7 +232,11 @@ __global__ __launch_bounds__(256) void k_q_sample_src(BatchSrc b, const int* t, 
         o.w = __fadd_rn(__fmul_rn(a[rr], xv.w), __fmul_rn(bb[rr], n.w));
         st4g(x_t + r * ldxt, c, cols, o);
         zero_pad(x_t + r * ldxt, cols, ldxt, c);
-        if (noise_out && noise_out != noise_in) st4g(noise_out + r * cols, c, cols, n);
+        if constexpr (KIND == OSD_PRED_EPSILON) {
+          if (noise_out && noise_out != noise_in) st4g(noise_out + r * cols, c, cols, n);
+        } else {
+          if (noise_out) st4g(noise_out + r * cols, c, cols, q_target<KIND>(a[rr], bb[rr], xv, n));
+        }
         if (x0_out) st4g(x0_out + r * cols, c, cols, xv);
       }
     }
@@ -213,16 +244,18 @@ __global__ __launch_bounds__(256) void k_q_sample_src(BatchSrc b, const int* t, 
 }
 hipError_t launch_q_sample_src(hipStream_t s, const BatchSrc& b, const int* t, const float* sqrt_ac, const float* sqrt_1m, const float* noise_in,
                                int64_t rows, int cols, int cd, uint64_t seed, uint32_t row_offset, float* x_t, float* noise_out, int* t_out, int T,
-                               float* cond_out, float* x0_out, int ldxt, const ZeroList* zl) {
+                               float* cond_out, float* x0_out, int ldxt, const ZeroList* zl, int kind) {
   if (rows <= 0) return hipSuccess;
   if (!t && (!t_out || T < 1)) return hipErrorInvalidValue;
+  if (kind != OSD_PRED_EPSILON && noise_out == noise_in) return hipErrorInvalidValue;
   ZeroList z{};
   if (zl) z = *zl;
   if (cd > 256) return hipErrorInvalidValue;
   int64_t blocks = (rows + QS_ROWS - 1) / QS_ROWS;
   if (blocks > 4096) blocks = 4096;
   if (blocks < (zl ? 32 : 1)) blocks = zl ? 32 : 1;      // the zero list is walked by the first 32 workgroups
-  hipLaunchKernelGGL(k_q_sample_src, dim3((unsigned)blocks), 256, 0, s, b, t, sqrt_ac, sqrt_1m, noise_in, rows, cols, cd, seed,
+  auto k = kind == OSD_PRED_V ? k_q_sample_src<OSD_PRED_V> : kind == OSD_PRED_SAMPLE ? k_q_sample_src<OSD_PRED_SAMPLE> : k_q_sample_src<OSD_PRED_EPSILON>;
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), 256, 0, s, b, t, sqrt_ac, sqrt_1m, noise_in, rows, cols, cd, seed,
                      row_offset, x_t, ldxt > 0 ? ldxt : cols, noise_out, t_out, T, cond_out, x0_out, z);
   return hipGetLastError();
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/osdiff.h"
 #include "gemm.h"
 #include "epilogues.h"
 #include "batch_src.h"
@@ -57,10 +58,11 @@ hipError_t launch_fill_randn(hipStream_t s, float* out, int ld, int64_t rows, in
 hipError_t launch_copy2d(hipStream_t s, const float* src, int lds, float* dst, int ldd, int64_t rows, int cols);
 hipError_t launch_q_sample(hipStream_t s, const float* x0, const int* t, const float* sqrt_ac, const float* sqrt_1m,
                            const float* noise_in, int64_t rows, int cols, uint64_t seed, uint32_t row_offset,
-                           float* x_t, float* noise_out, int* t_out = nullptr, int T = 0, int ldxt = 0, const ZeroList* zl = nullptr);
+                           float* x_t, float* noise_out, int* t_out = nullptr, int T = 0, int ldxt = 0, const ZeroList* zl = nullptr,
+                           int kind = OSD_PRED_EPSILON);      // kind != epsilon: noise_out receives the training target (k_elem.hip: q_target)
 hipError_t launch_q_sample_src(hipStream_t s, const BatchSrc& b, const int* t, const float* sqrt_ac, const float* sqrt_1m, const float* noise_in,
                                int64_t rows, int cols, int cd, uint64_t seed, uint32_t row_offset, float* x_t, float* noise_out, int* t_out, int T,
-                               float* cond_out, float* x0_out, int ldxt = 0, const ZeroList* zl = nullptr);
+                               float* cond_out, float* x0_out, int ldxt = 0, const ZeroList* zl = nullptr, int kind = OSD_PRED_EPSILON);
 // classifier-free guidance on the last hidden activation: h[r] = h[m + r] + w * (h[r] - h[m + r]) for r < m, in place (h: [2 m][cols])
 hipError_t launch_guide_combine(hipStream_t s, float* h, int64_t m, int cols, float w);
 // condition dropout of a caller-supplied batch: out[r] = row r keeps its condition (rng.h: cond_kept) ? cond[r] : null_cond

@@ -588,10 +588,12 @@ struct LossStep {
     int* t_draw = nullptr;
     if (!tc.t_idx) { t_draw = w.t_idx; tc.t_idx = w.t_idx; }
     const int* t_idx = tc.t_idx;
+    // a non-eps target (osd_set_prediction) is formed by the same pass and lands in w.noise, injected noise or not
+    if (h->pred_type != OSD_PRED_EPSILON) h->last_train_path |= OSD_TP_TARGET;
     if (from_src) {
       // rows gathered from the resident dataset, mixed up and noised in one pass; conditions land in the workspace
       OSD_HIP(launch_q_sample_src(s, h->batch_src, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, a.cond_dim, seed, roff, w.x_t,
-                                  w.noise, t_draw, a.T, w.cond_mix, cp ? w.x0_mix : nullptr, w.xld, &zl));
+                                  w.noise, t_draw, a.T, w.cond_mix, cp ? w.x0_mix : nullptr, w.xld, &zl, h->pred_type));
       cond = w.cond_mix;
       x0 = cp ? w.x0_mix : nullptr;
       // condition dropout after the mix: the null condition into the rows that drop theirs, in place (one tiny launch, only when asked for)
@@ -599,7 +601,8 @@ struct LossStep {
         OSD_HIP(launch_cond_dropout(s, w.cond_mix, h->d_null_cond + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n,
                                     a.cond_dim, seed, roff, w.cond_mix));
     } else {
-      OSD_HIP(launch_q_sample(s, x0, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, seed, roff, w.x_t, w.noise, t_draw, a.T, w.xld, &zl));
+      OSD_HIP(launch_q_sample(s, x0, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, seed, roff, w.x_t, w.noise, t_draw, a.T, w.xld, &zl,
+                              h->pred_type));
       if (cond_drop) {       // condition dropout of a caller-supplied batch: the replaced rows land in the workspace
         OSD_HIP(launch_cond_dropout(s, cond, h->d_null_cond + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n, a.cond_dim,
                                     seed, roff, w.cond_mix));
@@ -639,7 +642,7 @@ struct LossStep {
     const double count = (double)n * (double)D;
     GemmArgs g = output_proj_args(h, w.f, n);
     EpiMse::Args ea{};
-    ea.bias = h->params[a.pm.out_b]; ea.noise = noise ? noise : w.noise; ea.ldn = D;
+    ea.bias = h->params[a.pm.out_b]; ea.noise = noise && h->pred_type == OSD_PRED_EPSILON ? noise : w.noise; ea.ldn = D;
     ea.dout = grads ? w.d_out : nullptr; ea.ldd = D; ea.pred = cp ? w.pred : nullptr; ea.ldp = D; ea.loss = loss_out;
     ea.inv_count = (float)(1.0 / count);
     if (h->loss_kind == OSD_LOSS_L2 && !h->loss_tw_set) {
@@ -660,7 +663,9 @@ struct LossStep {
     const int D = a.D;
     const int* t_idx = tc.t_idx;
     OSD_HIP(hipMemcpyAsync(h->parts_dev, loss_out, 4, hipMemcpyDeviceToDevice, s));
-    OSD_HIP(launch_x0hat(s, w.x_t, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, n, D, w.pred));
+    const float2* pq = reinterpret_cast<const float2*>(h->d_pq);      // x0^ = P x_t + Q out; epsilon keeps its own kernels (their bits)
+    if (h->pred_type == OSD_PRED_EPSILON) OSD_HIP(launch_x0hat(s, w.x_t, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, n, D, w.pred));
+    else OSD_HIP(launch_row_affine(s, w.x_t, t_idx, pq, w.pred, n, D, w.pred));
     OSD_HIP(hipMemsetAsync(w.cw.acc, 0, (size_t)w.cw.acc_doubles * 8, s));
     OSD_HIP(cons_moments(s, w.pred, D, n, D, w.cw.acc, w.cw.mi_r));
     float* gx = grads ? w.g_x0 : nullptr;
@@ -670,7 +675,8 @@ struct LossStep {
       OSD_HIP(cons_moments(s, x0, D, n, D, w.cw.acc + 2 * (int64_t)D, w.cw.mi_t));
       OSD_HIP(cons_mutexpr(s, *cp, w.cw, w.pred, x0, D, n, D, (float)h->w_mutexpr, (float)(h->w_mutexpr * loss_scale), loss_out, h->parts_dev + 2, gx));
     }
-    if (grads) OSD_HIP(launch_x0hat_bwd(s, w.g_x0, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, n, D, w.d_out));
+    if (grads && h->pred_type == OSD_PRED_EPSILON) OSD_HIP(launch_x0hat_bwd(s, w.g_x0, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, n, D, w.d_out));
+    else if (grads) OSD_HIP(launch_row_affine_bwd(s, w.g_x0, t_idx, pq, n, D, w.d_out));
     return OSD_OK;
   }
   int run(const int32_t* t_index) {

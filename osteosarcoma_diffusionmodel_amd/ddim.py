@@ -13,6 +13,11 @@ With eta = 1 and S = T this is the reference's DDPM chain; eta = 0 is determinis
 ``ddim_x0_table`` is the second table of a chain that clips the predicted x0 (``osd_sample_chain_clipped``): the same step unfolded at
 x0^, so that the clamp can sit between the two halves.
 
+Both tables take ``prediction`` (objective.PREDICTION_TYPES): what the network's output ``out`` is.  Only x0^ = P*x + Q*out depends on
+it -- epsilon: P = 1/sqrt(abar), Q = -sqrt(1 - abar)/sqrt(abar); v_prediction: P = a, Q = -b; sample: P = 0, Q = 1, with a, b the model's
+fp32 ``sqrt_alphas_cumprod`` / ``sqrt_one_minus_alphas_cumprod`` buffers -- while E, F and C = sigma do not, so the folded row of the other
+types is A = E*P + F, B = E*Q.  The default, "epsilon", keeps the expressions above and its arrays, bit for bit.
+
 ``known_level_table`` is the second table of a chain around observed values (``osd_sample_chain_known``): the noise level each
 step arrives at, at which the observations are put back.
 """
@@ -32,8 +37,46 @@ def ddim_timesteps(T: int, S: int) -> np.ndarray:
     return (s * T // S - 1).astype(np.int32)
 
 
-def ddim_step_table(alphas_cumprod, timesteps, eta: float):
+def _host32(b):
+    if hasattr(b, "detach"):
+        b = b.detach().cpu().float().numpy()
+    return np.asarray(b, dtype=np.float32).reshape(-1)
+
+
+def _x0_reading(prediction: str, abar: np.ndarray, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod):
+    """float64 (P [T], Q [T]) of x0^ = P*x + Q*out for v_prediction / sample.  a and b are the model's fp32 buffers when given -- the
+    values the training target was formed with: pass them --, else fp32 square roots of abar and 1 - abar, which equal those buffers up to
+    the last bit of the host's sqrt."""
+    if prediction == "sample":
+        return np.zeros_like(abar), np.ones_like(abar)
+    if prediction != "v_prediction":
+        raise ValueError(f"prediction_type must be 'epsilon', 'v_prediction' or 'sample', got {prediction!r}")
+    ab32 = abar.astype(np.float32)
+    a = np.sqrt(ab32) if sqrt_alphas_cumprod is None else _host32(sqrt_alphas_cumprod)
+    b = np.sqrt(np.float32(1.0) - ab32) if sqrt_one_minus_alphas_cumprod is None else _host32(sqrt_one_minus_alphas_cumprod)
+    if a.shape != abar.shape or b.shape != abar.shape:
+        raise ValueError("the schedule buffers differ in length")
+    return a.astype(np.float64), -b.astype(np.float64)
+
+
+def _unfolded(abar, tau, s, eta):
+    """float64 (E, F, sigma) of step s: x' = E*x0^ + F*x + sigma*z (ddim_x0_table's expressions; row 0: E = 1, F = 0)."""
+    a = abar[tau[s]]
+    ap = abar[tau[s - 1]] if s > 0 else 1.0
+    ratio = (1.0 - ap) / (1.0 - a) if a < 1.0 else 0.0
+    sigma = eta * math.sqrt(ratio) * math.sqrt(max(1.0 - a / ap, 0.0))
+    direction = math.sqrt(max(1.0 - ap - sigma * sigma, 0.0))
+    f = direction / math.sqrt(1.0 - a) if a < 1.0 else 0.0
+    if s == 0:
+        return 1.0, 0.0, sigma
+    return math.sqrt(ap) - f * math.sqrt(a), f, sigma
+
+
+def ddim_step_table(alphas_cumprod, timesteps, eta: float, prediction: str = "epsilon", *, sqrt_alphas_cumprod=None,
+                    sqrt_one_minus_alphas_cumprod=None):
     """(int32 [S] timesteps, fp32 [S][4] rows (A_s, B_s, C_s, 0)) for ``osd_sample_chain_steps``.
+
+    ``prediction`` != "epsilon": A = E*P + F, B = E*Q of the unfolded step (module docstring), in float64, rounded once.
 
     The coefficients are formed in float64 from the fp32 ``alphas_cumprod`` buffer and rounded once to fp32, as
     ``osd_set_schedule`` folds the DDPM posterior.  The radicand of B is clamped at 0; x0^ is not clamped (as in the reference)."""
@@ -48,6 +91,12 @@ def ddim_step_table(alphas_cumprod, timesteps, eta: float):
     if tau.size < 1 or tau.min() < 0 or tau.max() >= T:
         raise ValueError(f"timesteps must be a non-empty list inside [0, {T})")
     coef = np.zeros((tau.size, 4), dtype=np.float64)
+    if prediction != "epsilon":
+        P, Q = _x0_reading(prediction, abar, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod)
+        for s in range(tau.size):
+            e, f, sigma = _unfolded(abar, tau, s, eta)
+            coef[s, :3] = (e * P[tau[s]] + f, e * Q[tau[s]], sigma)
+        return tau.astype(np.int32), coef.astype(np.float32)
     for s in range(tau.size):
         a = abar[tau[s]]
         ap = abar[tau[s - 1]] if s > 0 else 1.0
@@ -59,7 +108,8 @@ def ddim_step_table(alphas_cumprod, timesteps, eta: float):
     return tau.astype(np.int32), coef.astype(np.float32)
 
 
-def ddim_x0_table(alphas_cumprod, timesteps, eta: float) -> np.ndarray:
+def ddim_x0_table(alphas_cumprod, timesteps, eta: float, prediction: str = "epsilon", *, sqrt_alphas_cumprod=None,
+                  sqrt_one_minus_alphas_cumprod=None) -> np.ndarray:
     """fp32 [S][4] rows (P_s, Q_s, E_s, F_s) for ``osd_sample_chain_clipped``: the step of ``ddim_step_table`` unfolded at x0^,
 
         x0^ = P*x + Q*eps,   x' = E*clip(x0^) + F*x + C*z       (C = sigma: slot 2 of ``ddim_step_table``'s row)
@@ -68,7 +118,8 @@ def ddim_x0_table(alphas_cumprod, timesteps, eta: float) -> np.ndarray:
 
     so that the direction term uses the eps the clipped x0^ implies, (x - sqrt(abar)*x0c)/sqrt(1 - abar).  Without a clamp
     E*P + F = A and E*Q = B.  Formed in float64 from the fp32 buffer and rounded once, like ``ddim_step_table``, and rejecting what it
-    rejects; row 0 has E = 1, F = 0 exactly (the last step returns the clipped x0^ itself)."""
+    rejects; row 0 has E = 1, F = 0 exactly (the last step returns the clipped x0^ itself).  ``prediction`` != "epsilon" changes (P, Q)
+    only (module docstring); E and F keep their bits."""
     eta = float(eta)
     if not 0.0 <= eta <= 1.0:
         raise ValueError(f"eta={eta} outside [0, 1]")
@@ -89,6 +140,9 @@ def ddim_x0_table(alphas_cumprod, timesteps, eta: float) -> np.ndarray:
         f = direction / math.sqrt(1.0 - a) if a < 1.0 else 0.0
         coef[s] = (1.0 / math.sqrt(a), -math.sqrt(max(1.0 - a, 0.0)) / math.sqrt(a), math.sqrt(ap) - f * math.sqrt(a), f)
     coef[0, 2:] = (1.0, 0.0)
+    if prediction != "epsilon":
+        P, Q = _x0_reading(prediction, abar, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod)
+        coef[:, 0], coef[:, 1] = P[tau], Q[tau]
     return coef.astype(np.float32)
 
 

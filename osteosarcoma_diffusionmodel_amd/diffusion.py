@@ -146,6 +146,7 @@ class _Engine:
         self._sig = None
         self.constraints_version = 0
         self.loss_state = None          # the model's _loss_state() this handle was last configured with (None: the library's default)
+        self.prediction_type = "epsilon"  # the model's prediction_type this handle's tables were last folded for (the library's default)
         self.serial = 0                 # bumped by every call that rewrites the handle's training workspace
 
     def set_constraints(self, spec):
@@ -165,13 +166,19 @@ class _Engine:
         c.mutexpr_weight = spec["w_me"]
         L.check(lib.osd_set_constraints(self.handle, C.byref(c)))
 
+    def set_prediction(self, model: "BiologyAwareDiffusionModel"):
+        """Validate the model's prediction_type and refold the handle's step tables for it (osd_set_prediction: persistent)."""
+        from . import objective as OB
+        kind = OB.PREDICTION_TYPES[OB.check_prediction_type(model.prediction_type)]
+        L.check(L.lib().osd_set_prediction(self.handle, kind))
+
     def set_loss(self, model: "BiologyAwareDiffusionModel"):
         """Validate the model's objective attributes and hand them to the handle (osd_set_loss: persistent)."""
         from . import objective as OB
         kind = OB.LOSS_KINDS[OB.check_loss_type(model.loss_type)]
         delta = OB.check_huber_delta(model.huber_delta)
         table = OB.loss_table(OB.check_loss_weighting(model.loss_weighting), OB.check_gamma(model.min_snr_gamma), model.alphas_cumprod,
-                              model._loss_weights)
+                              model._loss_weights, OB.check_prediction_type(model.prediction_type))
         L.check(L.lib().osd_set_loss(self.handle, kind, delta, None if table is None else table.ctypes.data))
 
     def close(self):
@@ -336,6 +343,10 @@ class BiologyAwareDiffusionModel(nn.Module):
         self.huber_delta: float = OB.check_huber_delta(dm.get("huber_delta", 1.0))
         self.loss_weighting: Optional[str] = OB.check_loss_weighting(dm.get("loss_weighting"))
         self.min_snr_gamma: float = OB.check_gamma(dm.get("min_snr_gamma", 5.0))
+        # what the network predicts (objective.PREDICTION_TYPES): config['model']['diffusion']['prediction_type'] =
+        # "epsilon" (the reference's and the default: everything as without the key), "v_prediction" or "sample".  The training target, the
+        # constraint losses' x0^, min_snr's form, every sampler and sampling option follow it.  A plain attribute like the loss keys
+        self.prediction_type: str = OB.check_prediction_type(dm.get("prediction_type", "epsilon"))
         self._loss_weights = None         # set_loss_weights: a custom per-timestep table (host float32 [T]); wins over loss_weighting
         self._loss_version = 0
 
@@ -351,7 +362,7 @@ class BiologyAwareDiffusionModel(nn.Module):
 
     def _loss_state(self):
         """What the engine's loss setting follows: the objective attributes and the custom table's version counter."""
-        return (self.loss_type, self.huber_delta, self.loss_weighting, self.min_snr_gamma, self._loss_version)
+        return (self.loss_type, self.huber_delta, self.loss_weighting, self.min_snr_gamma, self._loss_version, self.prediction_type)
 
     # -- constraint losses (north_star; stubs at models/cvae.py:262-302) -----------------------------
     def set_constraints(self, pathways=None, mutation_columns=None, target_columns=None, *, pathway_weight: Optional[float] = None,
@@ -435,6 +446,9 @@ class BiologyAwareDiffusionModel(nn.Module):
         if eng.constraints_version != self._constraints_version:
             eng.set_constraints(self._constraints)
             eng.constraints_version = self._constraints_version
+        if eng.prediction_type != self.prediction_type:
+            eng.set_prediction(self)    # raises ValueError on an unknown value; the handle then keeps its previous type
+            eng.prediction_type = self.prediction_type
         state = self._loss_state()
         if eng.loss_state != state:
             eng.set_loss(self)          # raises ValueError on an unknown value; the handle then keeps its previous setting
@@ -495,12 +509,22 @@ class BiologyAwareDiffusionModel(nn.Module):
         return w, c0
 
     # -- q_sample (models/diffusion.py:328-342) -------------------------------------------------
-    def q_sample(self, x_0, t, noise=None, *, seed: Optional[int] = None):
+    def q_sample(self, x_0, t, noise=None, *, seed: Optional[int] = None, return_target: bool = False):
+        """(x_t, noise).  ``return_target=True``: (x_t, target), the training target of the model's ``prediction_type`` as the training
+        step forms it -- the noise, a*noise - b*x_0 or x_0."""
         eng = self._engine()
         x_0 = self._prep(x_0, self.data_dim, "x_0")
         n = x_0.shape[0]
         t32 = self._t32(t, n, x_0.device)
         x_t = torch.empty_like(x_0)
+        if return_target:
+            target = torch.empty_like(x_0)
+            if noise is None:
+                seed = _draw_seed() if seed is None else seed
+            else:
+                noise, seed = self._prep(noise, self.data_dim, "noise"), 0
+            L.check(L.lib().osd_q_sample_target(eng.handle, L.ptr(x_0), L.ptr(t32), L.ptr(noise), n, seed, 0, L.ptr(x_t), L.ptr(target)))
+            return x_t, target
         if noise is None:
             noise_out = torch.empty_like(x_0)
             seed = _draw_seed() if seed is None else seed
@@ -525,15 +549,51 @@ class BiologyAwareDiffusionModel(nn.Module):
         if t is None:
             t = torch.randint(0, self.num_steps, (n,), device=x_0.device)
         x_t, _ = self.q_sample(x_0, t, noise, seed=seed)
-        return self.predict_noise(x_t, t, conditions, dropout_masks=dropout_masks, seed=seed)
+        return self._raw_output(x_t, t, conditions, dropout_masks=dropout_masks, seed=seed)      # the raw output, whatever the type
+
+    _AS_KINDS = {"eps": L.OSD_PRED_EPSILON, "v": L.OSD_PRED_V, "x0": L.OSD_PRED_SAMPLE}
+    _OWN_AS = {"epsilon": "eps", "v_prediction": "v", "sample": "x0"}
+
+    def predict(self, x_t, t, conditions, as_: str = "raw", *, dropout_masks: Optional[Sequence[torch.Tensor]] = None,
+                seed: Optional[int] = None, guidance_scale: float = 1.0):
+        """The network's prediction at (x_t, t) read as ``as_``: "raw" (the output itself: eps, v or x0 by ``prediction_type``), "x0"
+        (x0^ = P x_t + Q out), "eps" ((x_t - a x0^)/b) or "v" (a eps^ - b x0^), a = sqrt_alphas_cumprod[t], b =
+        sqrt_one_minus_alphas_cumprod[t].  The conversion is one row-affine pass (osd_convert_prediction) with coefficients formed in float64
+        and rounded once; the model's own reading and "raw" are the output unchanged.  ``guidance_scale`` combines raw outputs, which is
+        guidance in eps-space for every type.  Conversions are inference only (no autograd through them)."""
+        if as_ != "raw" and as_ not in self._AS_KINDS:
+            raise ValueError(f"as_ must be 'raw', 'eps', 'x0' or 'v', got {as_!r}")
+        out = self._raw_output(x_t, t, conditions, dropout_masks=dropout_masks, seed=seed, guidance_scale=guidance_scale)
+        from . import objective as OB
+        if as_ == "raw" or as_ == self._OWN_AS[OB.check_prediction_type(self.prediction_type)]:
+            return out
+        if out.requires_grad:
+            raise ValueError("predict(as_=...) converts without autograd: call it under torch.no_grad(), or use as_='raw'")
+        eng = self._engine()
+        x_t = self._prep(x_t, self.data_dim, "x_t")
+        n = x_t.shape[0]
+        t32 = torch.full((n,), int(t), device=x_t.device, dtype=torch.int32) if isinstance(t, int) else self._t32(t, n, x_t.device)
+        if isinstance(t, int) and not 0 <= t < self.num_steps:
+            raise IndexError(f"timestep index out of range [0, {self.num_steps})")
+        L.check(L.lib().osd_convert_prediction(eng.handle, L.ptr(x_t), L.ptr(t32), L.ptr(out), n, self._AS_KINDS[as_], L.ptr(out)))
+        return out
 
     def predict_noise(self, x_t, t, conditions, *, dropout_masks: Optional[Sequence[torch.Tensor]] = None,
                       seed: Optional[int] = None, guidance_scale: float = 1.0):
+        """The predicted noise.  An epsilon model: the network's output (``_raw_output``), as ever.  The other types:
+        ``predict(as_="eps")``, a real eps^, so that code written against this method (``p_sample`` loops) keeps working."""
+        if self.prediction_type == "epsilon":
+            return self._raw_output(x_t, t, conditions, dropout_masks=dropout_masks, seed=seed, guidance_scale=guidance_scale)
+        return self.predict(x_t, t, conditions, "eps", dropout_masks=dropout_masks, seed=seed, guidance_scale=guidance_scale)
+
+    def _raw_output(self, x_t, t, conditions, *, dropout_masks: Optional[Sequence[torch.Tensor]] = None,
+                    seed: Optional[int] = None, guidance_scale: float = 1.0):
         """DiffusionUNet.forward(x_t, t/T, condition_embed(c)) (models/diffusion.py:370-373); ``t`` is an
         int (shared) or an integer tensor of per-row timestep indices.
 
-        ``guidance_scale=w`` != 1: the classifier-free-guidance prediction eps(c0) + w * (eps(c) - eps(c0)) with the model's
-        ``null_condition`` c0 (eval mode, inference only)."""
+        ``guidance_scale=w`` != 1: the classifier-free-guidance prediction out(c0) + w * (out(c) - out(c0)) with the model's
+        ``null_condition`` c0 (eval mode, inference only).  Every type's eps is affine in ``out`` with an x_t term that cancels in the
+        difference, so this is guidance in eps-space whatever ``prediction_type`` is."""
         guide = self._guidance(guidance_scale)
         if guide is not None:
             if dropout_masks is not None:
@@ -617,14 +677,21 @@ class BiologyAwareDiffusionModel(nn.Module):
         Works with the DDPM chain, ``num_inference_steps`` / ``eta`` and ``guidance_scale``; per-layer kernels
         (``last_sampler == "graph"``), fp32.  ``known=None`` or all-NaN is the unconstrained call.
 
-        ``x0_bounds`` clips the predicted clean sample x0^ = (x - sqrt(1-abar) eps)/sqrt(abar) of every step to per-feature bounds before
+        ``x0_bounds`` clips the predicted clean sample x0^ = P x + Q out of every step -- (x - sqrt(1-abar) out)/sqrt(abar) for an epsilon
+        model, sqrt(abar) x - sqrt(1-abar) out for v_prediction, out for sample -- to per-feature bounds before
         the posterior update (clip_denoised / clip_sample elsewhere), the direction term using the eps the clipped x0^ implies: a
         ``(lo, hi)`` pair of scalars or [D] arrays, or a dict over ``mutations`` / ``expression`` / ``pathways`` of such pairs
         (``generate.assemble_bounds``; a missing block or a ``None`` side is free).  Every returned element lies inside its bounds
         exactly -- except observed elements of ``known``, which come back as observed.  ``None`` takes ``model.x0_bounds`` (``None`` by
         default: no clipping, today's entry points on any engine, the same bits); ``False`` ignores the attribute.  Works with the DDPM
         chain, ``num_inference_steps`` / ``eta``, ``guidance_scale`` and ``known``; per-layer kernels (``last_sampler == "graph"``), fp32
-        (``precision = "bf16x3"`` raises ValueError)."""
+        (``precision = "bf16x3"`` raises ValueError).
+
+        The chain follows ``prediction_type``: every step is x' = E x0^ + F x + C z with x0^ = P x + Q out, and only (P, Q) depend on the
+        type, so every engine and every option above runs a v_prediction or sample model from refolded tables, at the same speed."""
+        from . import objective as OB
+        pred = OB.check_prediction_type(self.prediction_type)
+        sched = dict(sqrt_alphas_cumprod=self.sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod=self.sqrt_one_minus_alphas_cumprod)
         guide = self._guidance(guidance_scale)
         if x0_bounds is None:
             x0_bounds = self.x0_bounds
@@ -651,7 +718,7 @@ class BiologyAwareDiffusionModel(nn.Module):
                 raise ValueError(f"num_inference_steps={steps} outside [1, {self.num_steps}]")
             if noise is not None and float(eta) == 0.0 and kn is None:
                 raise ValueError("noise: eta = 0 draws no z (pass eta > 0 or leave noise out)")
-            plan = ddim_step_table(self.alphas_cumprod, ddim_timesteps(self.num_steps, steps), eta)
+            plan = ddim_step_table(self.alphas_cumprod, ddim_timesteps(self.num_steps, steps), eta, pred, **sched)
         elif float(eta) != 0.0:
             raise ValueError("eta applies to the DDIM sampler: pass num_inference_steps as well")
         n_draws = self.num_steps - 1 if plan is None else plan[0].size - 1
@@ -689,7 +756,7 @@ class BiologyAwareDiffusionModel(nn.Module):
         if bounds is not None:
             from .ddim import ddim_x0_table, known_level_table
             tau, coef = plan if plan is not None else (None, None)
-            x0c = None if tau is None else ddim_x0_table(self.alphas_cumprod, tau, eta)
+            x0c = None if tau is None else ddim_x0_table(self.alphas_cumprod, tau, eta, pred, **sched)
             level = None
             if tau is not None and kn is not None:
                 level = known_level_table(self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, tau)

@@ -313,12 +313,29 @@ class SyntheticPatientGenerator:
         logger.info(f"Saved conditions to {cond_path}")
 
 
+def checkpoint_prediction_type(checkpoint: dict, config: dict) -> Optional[str]:
+    """The prediction type a model built from ``config`` must take over from ``checkpoint``: the checkpoint's when ``config`` names
+    none, None when there is nothing to take over.  Both naming different types is a ValueError -- sampling a v-trained network as an
+    epsilon one returns noise without any other sign.  A checkpoint without the key (every reference checkpoint) is an epsilon model."""
+    from .objective import check_prediction_type
+    saved = ((checkpoint.get("config") or {}).get("model") or {}).get("diffusion", {}).get("prediction_type")
+    asked = ((config or {}).get("model") or {}).get("diffusion", {}).get("prediction_type")
+    saved_type = check_prediction_type("epsilon" if saved is None else saved)
+    if asked is None:
+        return None if saved is None else saved_type
+    if check_prediction_type(asked) != saved_type:
+        raise ValueError(f"config['model']['diffusion']['prediction_type'] is {asked!r} but the checkpoint was trained with {saved_type!r}")
+    return None
+
+
 def load_trained_model(checkpoint_path: Path, config: dict, device: str, use_ema: Optional[bool] = None):
     """Checkpoint -> model (utils/generate.py:238-298): condition width from the saved
     ``condition_embed.mlp.0.weight``, feature dims from the processed CSV headers.
     ``use_ema``: which weights of a checkpoint written with ``training.ema_decay`` -- None (default) the averaged ones
     (``ema_state_dict``) when the file has them, else ``model_state_dict``; False always ``model_state_dict`` (the last iterate);
-    True the averaged ones, KeyError when the file has none."""
+    True the averaged ones, KeyError when the file has none.
+    ``prediction_type`` (what the network was trained to predict) travels in the checkpoint's own config: a ``config`` without the key
+    adopts the checkpoint's, one that names a different type than the checkpoint raises ValueError."""
     from .diffusion import BiologyAwareDiffusionModel
     logger.info(f"Loading model from {checkpoint_path}")
     checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
@@ -335,6 +352,7 @@ def load_trained_model(checkpoint_path: Path, config: dict, device: str, use_ema
     arch = config["model"]["architecture"]
     if arch not in ("diffusion", "cvae"):
         raise ValueError(f"Unknown architecture: {arch}")
+    saved_pred = checkpoint_prediction_type(checkpoint, config) if arch == "diffusion" else None
     processed = Path(config["data"]["processed_dir"])
     dims = []
     for fname in ("mutation_matrix_aligned.csv", "expression_matrix_aligned.csv", "pathway_scores.csv"):
@@ -355,6 +373,8 @@ def load_trained_model(checkpoint_path: Path, config: dict, device: str, use_ema
     saved_null = (checkpoint.get("config") or {}).get("model", {}).get("null_condition")
     if arch == "diffusion" and model.null_condition is None and saved_null is not None:
         model.null_condition = [float(v) for v in saved_null]
+    if saved_pred is not None:
+        model.prediction_type = saved_pred
     model.to(device)
     model.eval()
     logger.info("Model loaded successfully!")

@@ -1,4 +1,4 @@
-"""The training objective's options: which eps-loss the fused training step computes and how its rows are weighted.
+"""The training objective's options: what the network predicts, which loss the fused training step computes and how its rows are weighted.
 
 Pure host code (like ``ddim.py``): the argument checks and the per-timestep weight tables.  The arithmetic itself runs in the
 output_proj epilogue of ``osd_train_loss_fwd_bwd`` (csrc/epilogues.h: ``EpiLoss``, configured through ``osd_set_loss``).
@@ -26,6 +26,16 @@ import torch
 
 LOSS_KINDS = {"l2": 0, "l1": 1, "huber": 2}         # include/osdiff.h: OSD_LOSS_*
 LOSS_WEIGHTINGS = (None, "min_snr")
+# what the network predicts (config['model']['diffusion']['prediction_type']; include/osdiff.h: OSD_PRED_*).  With a = sqrt(abar_t),
+# b = sqrt(1 - abar_t): "epsilon" -- target eps, the reference's and the default --, "v_prediction" -- target a*eps - b*x0 (Salimans & Ho
+# 2022) --, "sample" -- target x0.  The loss above then reads d = out - target
+PREDICTION_TYPES = {"epsilon": 0, "v_prediction": 1, "sample": 2}
+
+
+def check_prediction_type(prediction_type) -> str:
+    if not isinstance(prediction_type, str) or prediction_type not in PREDICTION_TYPES:
+        raise ValueError(f"prediction_type must be 'epsilon', 'v_prediction' or 'sample', got {prediction_type!r}")
+    return prediction_type
 
 
 def check_loss_type(loss_type) -> str:
@@ -75,24 +85,35 @@ def check_weight_table(weights, num_steps: int) -> np.ndarray:
     return w
 
 
-def min_snr_weights(alphas_cumprod, gamma: float = 5.0) -> torch.Tensor:
-    """min-SNR-gamma weights for eps-prediction (Hang et al. 2023): fp32 [T], w_t = min(SNR_t, gamma) / SNR_t with
-    SNR_t = abar_t / (1 - abar_t).  Formed in float64 from the (fp32) ``alphas_cumprod`` buffer and rounded once.
-    w_t = 1 wherever SNR_t <= gamma (the noisy end of the chain), gamma / SNR_t towards t = 0."""
+def min_snr_weights(alphas_cumprod, gamma: float = 5.0, prediction: str = "epsilon") -> torch.Tensor:
+    """min-SNR-gamma weights (Hang et al. 2023): fp32 [T] with SNR_t = abar_t / (1 - abar_t), formed in float64 from the (fp32)
+    ``alphas_cumprod`` buffer and rounded once.  The weight of the x0-loss is min(SNR_t, gamma); expressed on each type's own target:
+
+        epsilon        w_t = min(SNR_t, gamma) / SNR_t          1 wherever SNR_t <= gamma (the noisy end), gamma / SNR_t towards t = 0
+        v_prediction   w_t = min(SNR_t, gamma) / (SNR_t + 1)
+        sample         w_t = min(SNR_t, gamma)"""
     g = check_gamma(gamma)
+    prediction = check_prediction_type(prediction)
     ab = alphas_cumprod.detach().cpu() if isinstance(alphas_cumprod, torch.Tensor) else torch.as_tensor(np.asarray(alphas_cumprod))
     ab = ab.to(torch.float64).reshape(-1)
     if ab.numel() == 0 or not bool(((ab > 0) & (ab < 1)).all()):
         raise ValueError("alphas_cumprod must lie strictly inside (0, 1)")
     snr = ab / (1.0 - ab)
-    w = torch.clamp(snr, max=g) / snr
+    if prediction == "epsilon":
+        w = torch.clamp(snr, max=g) / snr
+    elif prediction == "v_prediction":
+        w = torch.clamp(snr, max=g) / (snr + 1.0)
+    else:
+        w = torch.clamp(snr, max=g)
     return w.to(torch.float32)
 
 
-def loss_table(weighting: Optional[str], gamma: float, alphas_cumprod, custom: Optional[np.ndarray]) -> Optional[np.ndarray]:
-    """The table handed to ``osd_set_loss``: a custom one wins, then the configured weighting, else None (every row weighs 1)."""
+def loss_table(weighting: Optional[str], gamma: float, alphas_cumprod, custom: Optional[np.ndarray],
+               prediction: str = "epsilon") -> Optional[np.ndarray]:
+    """The table handed to ``osd_set_loss``: a custom one wins, then the configured weighting in the form of the model's prediction
+    type, else None (every row weighs 1)."""
     if custom is not None:
         return custom
     if weighting == "min_snr":
-        return np.ascontiguousarray(min_snr_weights(alphas_cumprod, gamma).numpy())
+        return np.ascontiguousarray(min_snr_weights(alphas_cumprod, gamma, prediction).numpy())
     return None
