@@ -347,6 +347,42 @@ int osd_sample_chain_clipped(osd_handle *h, const float *cond, int64_t n, const 
                              const float *known, int64_t ld_known, const float *lo_host,
                              const float *hi_host);
 
+/* The DDIM chains at eta = 0 with the DPM-Solver++(2M) multistep update (Lu et al. 2022, the data-prediction form): every step also
+ * uses the previous step's clipped x0, which the chain keeps in a buffer of its own beside the state.  Step s of the plan goes from
+ * tau_s to tau' = tau_{s-1}, s = n_steps - 1 first; with alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = ln(alpha / sigma),
+ * h_s = lambda' - lambda and phi = -alpha' * expm1(-h_s):
+ *   row n_steps-1 (first run), every row when n_steps <= 2:   F = sigma'/sigma,  G = phi,               H = 0
+ *   rows 0 < s < n_steps-1:  r = (lambda_s - lambda_{s+1}) / h_s,  F = sigma'/sigma,  G = phi*(1 + 1/(2r)),  H = -phi/(2r)
+ *   row 0 (lower-order final; h = inf):                       F = 0,             G = 1,                 H = 0
+ *   eps = denoiser(x, tau_s)                       (guided: osd_sample_chain_guided's eps_g)
+ *   x0  = fmaf(P, x, Q*eps)                        (P, Q) as in osd_sample_chain_clipped
+ *   x0c = fminf(fmaxf(x0, lo[f]), hi[f])
+ *   x'  = fmaf(G, x0c, fmaf(F, x, H*x0c_prev))     x0c_prev: the x0c of the step run before this one (never read where H = 0)
+ * G + H and F are the E and F of osd_sample_chain_clipped at eta = 0, so n_steps <= 2 is that chain.  Row 0 returns x0c bit for bit:
+ * every returned element lies inside [lo, hi] exactly; mut_mask_out stays (x_out > 0.5).  Deterministic after x_T: there is no z, and
+ * no step_coef.  The history is an epilogue stream of the output_proj launch (EpiPosteriorHist, csrc/epilogues.h) because neither
+ * x0c nor eps is ever written by it.  Arguments and checks of osd_sample_chain_clipped, except:
+ *   timesteps           required: a solver needs a plan (NULL is OSD_EINVAL)
+ *   x0_coef             host [n_steps][4] = (P_s, Q_s, G_s, F_s), row 0 = (., ., 1, 0);  hist_coef: host [n_steps] = H_s,
+ *                       hist_coef[0] = hist_coef[n_steps-1] = 0 (ddim.py: dpmpp_2m_table)
+ *   lo_host == hi_host == NULL   unbounded: the library fills (-inf, +inf) rows; one of the two NULL is OSD_EINVAL
+ *   known != NULL       observed elements are overwritten after the update with osd_sample_chain_known's expressions and draw rule;
+ *                       the history keeps the clipped network prediction, not the overwritten value.  noises [n_steps-1][n][D] (or
+ *                       Philox) feeds only the observed elements, as in the eta = 0 known chain
+ * One fused output_proj + update launch per step; per-layer kernels only, whatever "sampler" says (osd_sample_engine(h, -1, 0) then
+ * reports 0; no warning, "chain_fallbacks" untouched); a row's result does not depend on the chunk or shard it is in ("input_splitk"
+ * = 0).  OSD_F_TRAIN_MODE is allowed for unguided chains.  OSD_EINVAL, checked on the host before any device call: timesteps == NULL,
+ * a NULL or non-finite x0_coef or hist_coef, x0_coef[0] != (., ., 1, 0), hist_coef[0] != 0, hist_coef[n_steps-1] != 0, exactly one
+ * NULL bound, and everything osd_sample_chain_clipped, osd_sample_chain_known (with known != NULL), osd_sample_chain_guided and
+ * osd_sample_chain_steps reject; OSD_EUNSUPPORTED: "precision" = 1. */
+int osd_sample_chain_multistep(osd_handle *h, const float *cond, int64_t n, const float *x_T,
+                               const float *noises, uint64_t seed, int64_t row_offset, float *x_out,
+                               float *mut_mask_out, int flags, const int32_t *timesteps,
+                               const float *x0_coef, const float *hist_coef, const float *known_level,
+                               int32_t n_steps, const float *null_cond_host, float guidance_scale,
+                               const float *known, int64_t ld_known, const float *lo_host,
+                               const float *hi_host);
+
 /* eps_g of ONE guided evaluation (DiffusionUNet.forward twice, models/diffusion.py:210-256, combined as above), eval mode only:
  * osd_denoiser_forward's x / t_index / t_all / cond / eps, osd_sample_chain_guided's null_cond_host / guidance_scale and errors. */
 int osd_denoiser_forward_guided(osd_handle *h, const float *x, const int32_t *t_index, int32_t t_all,

@@ -67,6 +67,8 @@ _SIGNATURES = {
                                          C.c_float, _P, C.c_int64]),
     "osd_sample_chain_clipped": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int32, _P,
                                            C.c_float, _P, C.c_int64, _P, _P]),
+    "osd_sample_chain_multistep": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int32, _P,
+                                             C.c_float, _P, C.c_int64, _P, _P]),
     "osd_denoiser_forward_guided": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, _P, C.c_int, _P, C.c_float]),
     "osd_train_condition_dropout": (C.c_int, [_P, _P, C.c_double, _P]),
     "osd_train_loss_fwd_bwd": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.POINTER(_P), C.c_uint64, C.c_int64, C.c_int,

@@ -540,6 +540,9 @@ int osd_destroy(osd_handle* h) {
   if (h->clip_dev) e = hipFree(h->clip_dev);
   if (h->clip_ev) e = hipEventDestroy(h->clip_ev);
   free(h->clip_host);
+  if (h->hist_dev) e = hipFree(h->hist_dev);
+  if (h->hist_ev) e = hipEventDestroy(h->hist_ev);
+  free(h->hist_host);
   if (h->normsq_dev) e = hipFree(h->normsq_dev);
   if (h->parts_dev) e = hipFree(h->parts_dev);
   if (h->loss_tw) e = hipFree(h->loss_tw);
@@ -874,6 +877,7 @@ static int chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r
   const Guide* gd = job.guide.null_cond ? &job.guide : nullptr;
   const Known* kn = job.known.known ? &job.known : nullptr;
   const Clip* cl = job.clip.bounds ? &job.clip : nullptr;
+  const Multistep* ms = job.multistep.hist_coef ? &job.multistep : nullptr;
   const int D = a.D, S = job.plan.n_steps;
   hipStream_t s = sl.stream;
   OSD_TRY(release_graph(sl));
@@ -914,7 +918,9 @@ static int chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r
   const int64_t stage_floats = gd ? (m + 1) * (int64_t)a.cond_dim : 0;
   // a padded state reads its observations from rows of Dp floats too: the chunk's known rows, copied once, pad columns NaN (free)
   const int64_t known_floats = kn && padded ? m * (int64_t)ldx : 0;
-  OSD_TRY(ensure_arena(&sl, need_pad + x_floats + slab_floats + up64(stage_floats) + known_floats));
+  // a multistep chain keeps the previous step's clipped x0 beside the state: rows of ldx floats like the state's, zero at the start
+  const int64_t hist_floats = ms ? m * (int64_t)ldx : 0;
+  OSD_TRY(ensure_arena(&sl, need_pad + x_floats + slab_floats + up64(stage_floats) + (ms ? up64(known_floats) : known_floats) + hist_floats));
   carve_fwd(a, sl.arena, mt, false, &ws);
   float* x = padded ? sl.arena + need_pad : job.x_out;       // else the chain state lives in the output rows
   float* in_slabs = in_slices ? sl.arena + need_pad + x_floats : nullptr;
@@ -927,6 +933,11 @@ static int chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r
     OSD_HIP(hipMemsetAsync(kpad, 0xff, (size_t)m * ldx * 4, s));          // all bits set: a NaN
     OSD_HIP(launch_copy2d(s, known, ldk, kpad, ldx, m, D));
     known = kpad; ldk = ldx;
+  }
+  float* hist = nullptr;
+  if (ms) {
+    hist = cond_stage + up64(stage_floats) + up64(known_floats);
+    OSD_HIP(hipMemsetAsync(hist, 0, (size_t)m * ldx * 4, s));
   }
   const uint32_t roff = (uint32_t)job.row_offset;
   const bool train = (job.flags & OSD_F_TRAIN_MODE) != 0;
@@ -952,7 +963,9 @@ static int chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r
     ea.z = job.noises; ea.ldzz = D; ea.z_step_stride = (long long)job.n_total * D; ea.t_first = S - 1;
     ea.seed = job.seed; ea.row_offset = roff;
     ea.mut_mask = job.mut_mask_out; ea.mutation_dim = job.mutation_dim;
-    if (cl) OSD_HIP(launch_posterior_clip(s, g, PosteriorClipArgs{ea, cl->bounds, cl->bounds + cl->ld, cl->x0_coef, kn ? known : nullptr, ldk, kn ? kn->level : nullptr}));
+    if (ms) OSD_HIP(launch_posterior_hist(s, g, PosteriorHistArgs{PosteriorClipArgs{ea, cl->bounds, cl->bounds + cl->ld, cl->x0_coef, kn ? known : nullptr, ldk, kn ? kn->level : nullptr},
+                                                                  hist, ldx, ms->hist_coef}));
+    else if (cl) OSD_HIP(launch_posterior_clip(s, g, PosteriorClipArgs{ea, cl->bounds, cl->bounds + cl->ld, cl->x0_coef, kn ? known : nullptr, ldk, kn ? kn->level : nullptr}));
     else if (kn) OSD_HIP(launch_posterior_known(s, g, EpiPosteriorKnown::Args{ea, known, ldk, kn->level}));
     else OSD_HIP(launch_posterior(s, g, ea));
     OSD_HIP(launch_add_int(s, sl.t_dev, -1));
@@ -1047,7 +1060,8 @@ static int upload_plan(osd_handle* h, const int32_t* timesteps, const float* ste
   OSD_HIP(hipEventSynchronize(h->plan_ev));          // the previous call's upload has read the staging
   float* hc = static_cast<float*>(h->plan_host);
   int32_t* ht = reinterpret_cast<int32_t*>(hc + (size_t)a.T * 4);
-  memcpy(hc, step_coef, (size_t)S * 4 * 4);
+  if (step_coef) memcpy(hc, step_coef, (size_t)S * 4 * 4);
+  else memset(hc, 0, (size_t)S * 4 * 4);           // a multistep plan: no step draws, and its launch reads (P, Q, G, F) and H instead
   memcpy(ht, timesteps, (size_t)S * 4);
   OSD_HIP(hipMemcpyAsync(h->plan_coef, hc, (size_t)S * 4 * 4, hipMemcpyHostToDevice, s));
   OSD_HIP(hipMemcpyAsync(h->plan_t, ht, (size_t)S * 4, hipMemcpyHostToDevice, s));
@@ -1057,15 +1071,15 @@ static int upload_plan(osd_handle* h, const int32_t* timesteps, const float* ste
 }
 
 // What every entry point that takes a step plan rejects in it.
-static int check_plan(const Arch& a, const int32_t* timesteps, const float* step_coef, int32_t n_steps) {
-  if (!timesteps || !step_coef) { set_error("null step plan"); return OSD_EINVAL; }
+static int check_plan(const Arch& a, const int32_t* timesteps, const float* step_coef, int32_t n_steps, bool need_coef = true) {
+  if (!timesteps || (need_coef && !step_coef)) { set_error("null step plan"); return OSD_EINVAL; }
   if (n_steps < 1 || n_steps > a.T) { set_error("n_steps=%d outside [1,%d]", n_steps, a.T); return OSD_EINVAL; }
   for (int s = 0; s < n_steps; ++s) {
     if (timesteps[s] < 0 || timesteps[s] >= a.T) { set_error("timesteps[%d]=%d outside [0,%d)", s, timesteps[s], a.T); return OSD_EINVAL; }
-    for (int k = 0; k < 4; ++k)
+    for (int k = 0; step_coef && k < 4; ++k)
       if (!std::isfinite(step_coef[4 * s + k])) { set_error("step_coef[%d] is not finite", 4 * s + k); return OSD_EINVAL; }
   }
-  if (step_coef[2] != 0.f) { set_error("step_coef[2] = C_0 = %g: the last step draws no z, so C_0 must be 0", (double)step_coef[2]); return OSD_EINVAL; }
+  if (step_coef && step_coef[2] != 0.f) { set_error("step_coef[2] = C_0 = %g: the last step draws no z, so C_0 must be 0", (double)step_coef[2]); return OSD_EINVAL; }
   return OSD_OK;
 }
 
@@ -1110,12 +1124,29 @@ static int upload_clip(osd_handle* h, const float* x0_coef_host, int S, const fl
   memcpy(hc, x0_coef_host ? x0_coef_host : h->sched_x0_coef.data(), (size_t)S * 4 * 4);
   float* lo = hc + coef_floats;
   float* hi = lo + h->Dp;
-  memcpy(lo, lo_host, (size_t)a.D * 4);
-  memcpy(hi, hi_host, (size_t)a.D * 4);
-  for (int f = a.D; f < h->Dp; ++f) { lo[f] = -INFINITY; hi[f] = INFINITY; }
+  if (lo_host) memcpy(lo, lo_host, (size_t)a.D * 4);
+  if (hi_host) memcpy(hi, hi_host, (size_t)a.D * 4);
+  for (int f = lo_host ? a.D : 0; f < h->Dp; ++f) { lo[f] = -INFINITY; hi[f] = INFINITY; }      // no bounds (a multistep chain's may be absent): all free
   OSD_HIP(hipMemcpyAsync(h->clip_dev, hc, floats * 4, hipMemcpyHostToDevice, h->stream));
   OSD_HIP(hipEventRecord(h->clip_ev, h->stream));
   *out = Clip{h->clip_dev + coef_floats, h->Dp, h->clip_dev};
+  return OSD_OK;
+}
+
+// The history coefficients of a multistep chain, host -> handle-owned device table on the handle's stream.
+static int upload_hist_coef(osd_handle* h, const float* hist_coef_host, int S, Multistep* out) {
+  const Arch& a = h->arch;
+  if (!h->hist_host) {
+    h->hist_host = static_cast<float*>(malloc((size_t)a.T * 4));
+    if (!h->hist_host) { set_error("out of host memory"); return OSD_ENOMEM; }
+  }
+  if (!h->hist_ev) OSD_HIP(hipEventCreateWithFlags(&h->hist_ev, hipEventDisableTiming));
+  if (!h->hist_dev) OSD_HIP(hipMalloc((void**)&h->hist_dev, (size_t)a.T * 4));
+  OSD_HIP(hipEventSynchronize(h->hist_ev));          // the previous call's upload has read the staging
+  memcpy(h->hist_host, hist_coef_host, (size_t)S * 4);
+  OSD_HIP(hipMemcpyAsync(h->hist_dev, h->hist_host, (size_t)S * 4, hipMemcpyHostToDevice, h->stream));
+  OSD_HIP(hipEventRecord(h->hist_ev, h->stream));
+  *out = Multistep{h->hist_dev};
   return OSD_OK;
 }
 
@@ -1131,6 +1162,8 @@ struct SampleRequest {
   const float* known; int64_t ld_known; const float* known_level;
   bool clipped;                   // osd_sample_chain_clipped
   const float* x0_coef; const float* lo; const float* hi;
+  bool multistep;                 // osd_sample_chain_multistep: clipped, with no step_coef, optional bounds and hist_coef [n_steps]
+  const float* hist_coef;
 };
 
 // The one path of the osd_sample_chain* entry points: validation (in the order the entry points document: the first bad argument
@@ -1141,6 +1174,7 @@ static int sample_request(osd_handle* h, const SampleRequest& r) {
   bool unguided = true;
   if (r.guide) OSD_TRY(check_guidance(h, r.null_cond, r.guidance_scale, r.flags, &unguided));
   if (r.around_known && h->precision == 1) { set_error("precision = bf16x3 does not run chains around known values: set precision to fp32"); return OSD_EUNSUPPORTED; }
+  if (r.multistep && h->precision == 1) { set_error("precision = bf16x3 does not run the multistep solver: set precision to fp32"); return OSD_EUNSUPPORTED; }
   if (r.clipped && h->precision == 1) { set_error("precision = bf16x3 does not run chains that clip x0: set precision to fp32"); return OSD_EUNSUPPORTED; }
   OSD_TRY(check_rows(r.n));
   if (!r.cond || !r.x_out) { set_error("null tensor"); return OSD_EINVAL; }
@@ -1149,7 +1183,7 @@ static int sample_request(osd_handle* h, const SampleRequest& r) {
     if (r.ld_known < a.D || r.ld_known > 0x7fffffff) { set_error("ld_known=%lld outside [D=%d, 2^31)", (long long)r.ld_known, a.D); return OSD_EINVAL; }
   }
   const bool plan = r.need_plan || r.timesteps;
-  if (plan) OSD_TRY(check_plan(a, r.timesteps, r.step_coef, r.n_steps));
+  if (plan) OSD_TRY(check_plan(a, r.timesteps, r.step_coef, r.n_steps, !r.multistep));
   if (plan && r.around_known) {
     if (!r.known_level) { set_error("null known_level"); return OSD_EINVAL; }
     for (int i = 0; i < 2 * r.n_steps; ++i)
@@ -1160,8 +1194,9 @@ static int sample_request(osd_handle* h, const SampleRequest& r) {
     }
   }
   if (r.clipped) {
-    if (!r.lo || !r.hi) { set_error("null bound"); return OSD_EINVAL; }
-    for (int f = 0; f < a.D; ++f) {
+    const bool unbounded = r.multistep && !r.lo && !r.hi;
+    if (!unbounded && (!r.lo || !r.hi)) { set_error("null bound"); return OSD_EINVAL; }
+    for (int f = 0; !unbounded && f < a.D; ++f) {
       if (std::isnan(r.lo[f]) || std::isnan(r.hi[f])) { set_error("bound %d is NaN", f); return OSD_EINVAL; }
       if (r.lo[f] > r.hi[f]) { set_error("lo[%d] = %g > hi[%d] = %g", f, (double)r.lo[f], f, (double)r.hi[f]); return OSD_EINVAL; }
     }
@@ -1173,6 +1208,16 @@ static int sample_request(osd_handle* h, const SampleRequest& r) {
         set_error("x0_coef[0] = (., ., %g, %g): the last step returns the clipped x0 itself, so E_0, F_0 must be (1, 0)", (double)r.x0_coef[2], (double)r.x0_coef[3]);
         return OSD_EINVAL;
       }
+    }
+  }
+  if (r.multistep) {
+    if (!r.hist_coef) { set_error("null hist_coef"); return OSD_EINVAL; }
+    for (int i = 0; i < r.n_steps; ++i)
+      if (!std::isfinite(r.hist_coef[i])) { set_error("hist_coef[%d] is not finite", i); return OSD_EINVAL; }
+    if (r.hist_coef[0] != 0.f || r.hist_coef[r.n_steps - 1] != 0.f) {
+      set_error("hist_coef[0] = %g, hist_coef[%d] = %g: the last step is first order and the first one has no history, so both must be 0",
+                (double)r.hist_coef[0], r.n_steps - 1, (double)r.hist_coef[r.n_steps - 1]);
+      return OSD_EINVAL;
     }
   }
   OSD_TRY(check_row_offset(r.row_offset, r.n));
@@ -1192,6 +1237,7 @@ static int sample_request(osd_handle* h, const SampleRequest& r) {
     OSD_TRY(upload_known_level(h, plan ? r.known_level : nullptr, plan ? r.n_steps : a.T, &job.known.level));
   }
   if (r.clipped) OSD_TRY(upload_clip(h, plan ? r.x0_coef : nullptr, plan ? r.n_steps : a.T, r.lo, r.hi, &job.clip));
+  if (r.multistep) OSD_TRY(upload_hist_coef(h, r.hist_coef, r.n_steps, &job.multistep));
   if (plan) {
     OSD_TRY(upload_plan(h, r.timesteps, r.step_coef, r.n_steps));
     job.plan = StepPlan{r.n_steps, h->plan_temb, h->plan_coef};
@@ -1237,6 +1283,17 @@ int osd_sample_chain_clipped(osd_handle* h, const float* cond, int64_t n, const 
   SampleRequest r{cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, false, timesteps, step_coef, n_steps,
                   null_cond_host != nullptr, null_cond_host, guidance_scale, known != nullptr, known, ld_known, known_level,
                   true, x0_coef, lo_host, hi_host};
+  return sample_request(h, r);
+}
+
+int osd_sample_chain_multistep(osd_handle* h, const float* cond, int64_t n, const float* x_T, const float* noises, uint64_t seed,
+                               int64_t row_offset, float* x_out, float* mut_mask_out, int flags, const int32_t* timesteps,
+                               const float* x0_coef, const float* hist_coef, const float* known_level, int32_t n_steps,
+                               const float* null_cond_host, float guidance_scale, const float* known, int64_t ld_known,
+                               const float* lo_host, const float* hi_host) {
+  SampleRequest r{cond, n, x_T, noises, seed, row_offset, x_out, mut_mask_out, flags, true, timesteps, nullptr, n_steps,
+                  null_cond_host != nullptr, null_cond_host, guidance_scale, known != nullptr, known, ld_known, known_level,
+                  true, x0_coef, lo_host, hi_host, true, hist_coef};
   return sample_request(h, r);
 }
 

@@ -765,6 +765,119 @@ struct EpiPosteriorClip {
   }
 };
 
+// ---- output_proj + the DPM-Solver++(2M) multistep update (Lu et al. 2022) ----
+// EpiPosteriorClip's deterministic step plus one term: the previous step's clipped x0, kept in hist [P][ldh] (ldh = ldx, the state's
+// row stride), which the lane that owns an element reads and rewrites in place exactly as it does x.  x0coef [S][4] = (P_t, Q_t, G_t,
+// F_t), hcoef [S] = H_t.  Per element of step t:
+//   eps = acc + bias
+//   x0  = fmaf(P, x, Q*eps)
+//   x0c = fminf(fmaxf(x0, lo[f]), hi[f])
+//   hp  = hist[p][f];   hist[p][f] = x0c           the clipped network prediction, not the value after the `known` overwrite
+//   x'  = fmaf(G, x0c, fmaf(F, x, H*hp))
+// H is wave-uniform: where it is 0 (the first step run, whose history is the zeroed buffer, and t = 0) the read is skipped and hp = 0;
+// the store is skipped at t = 0.  Row 0 is (P, Q, 1, 0) with H = 0: x' = x0c bit for bit.  No z: the generator runs only under KNOWN,
+// for quads that hold an observation, at t > 0 (EpiPosteriorKnown's expressions and draw rule, after the update).  a.p.coef is not read.
+// Quads requested ahead of their use: two (x, lo, hi, hist: 32 registers), KNOWN one (20), as EpiPosteriorClip<true>.
+struct PosteriorHistArgs {
+  PosteriorClipArgs c;
+  float* hist; int ldh;                 // [P][ldh]
+  const float* hcoef;                   // dev [S] = H_t
+};
+template <bool KNOWN>
+struct EpiPosteriorHist {
+  static constexpr bool COUNTED_STORES = true;     // one x' quad per accumulator quad and, at t > 0, one history quad more: never fewer
+  static constexpr bool XBUF = false;
+  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
+  typedef PosteriorHistArgs Args;
+  static bool fast_ok(const Args& a, int F) { return EpiPosteriorClip<KNOWN>::fast_ok(a.c, F) && al16(a.hist) && a.ldh % 4 == 0; }
+  template <int NFB> using Pre = EpiPosterior::Pre<NFB>;
+  template <int NFB, bool FAST>
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
+    return EpiPosterior::prefetch<NFB, FAST>(a.c.p, fw, lane, F);
+  }
+  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& ah, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
+                                               Sync&& sync = Sync()) {
+    const PosteriorClipArgs& ac = ah.c;
+    const EpiPosterior::Args& a = ac.p;
+    const int l31 = lane & 31, h = lane >> 5;
+    const int t = a.t_dev ? *a.t_dev : a.t_imm;
+    const float* c = ac.x0coef + 4 * t;
+    const float cP = c[0], cQ = c[1], cG = c[2], cF = c[3];
+    const float cH = ah.hcoef[t];
+    const bool hz = cH != 0.f;           // uniform: the step's table row
+    float La = 1.f, Ls = 0.f;
+    if constexpr (KNOWN) { La = ac.level[2 * t]; Ls = ac.level[2 * t + 1]; }
+    const float* zbase = a.z ? a.z + (long long)(a.t_first - t) * a.z_step_stride : nullptr;
+    constexpr int QB = KNOWN ? 1 : 2;
+#pragma unroll
+    for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+      for (int pb = 0; pb < NPB; ++pb) {
+        const int p = pw + 32 * pb + l31;
+        const int pc = p < P ? p : P - 1;
+        float* hrow = ah.hist + (size_t)pc * ah.ldh;
+        float4 xq[4], lq[4], hq[4], pq[4], kq[KNOWN ? 4 : 1];
+#pragma unroll
+        for (int q0 = 0; q0 < 4; q0 += QB) {
+#pragma unroll
+        for (int q = q0; q < q0 + QB; ++q) {
+          const int f = fw + 32 * fb + 8 * q + 4 * h;
+          xq[q] = ldq<FAST>(a.xin + (size_t)pc * a.ldx, f, F);
+          lq[q] = ldq<FAST>(ac.lo, f, F);
+          hq[q] = ldq<FAST>(ac.hi, f, F);
+          pq[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (hz) pq[q] = ldq<FAST>(hrow, f, F);
+          if constexpr (KNOWN) kq[q] = ldq<FAST>(ac.known + (size_t)pc * ac.ldk, f, F);
+        }
+#pragma unroll
+        for (int q = q0; q < q0 + QB; ++q) {
+          const int f = fw + 32 * fb + 8 * q + 4 * h;
+          const bool ok = p < P && f < F;
+          const float4 bv = pre.bias[fb][q];
+          const float e[4] = {acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w};
+          const float xv[4] = {xq[q].x, xq[q].y, xq[q].z, xq[q].w};
+          const float lv[4] = {lq[q].x, lq[q].y, lq[q].z, lq[q].w};
+          const float hv[4] = {hq[q].x, hq[q].y, hq[q].z, hq[q].w};
+          const float pv[4] = {pq[q].x, pq[q].y, pq[q].z, pq[q].w};
+          float kv[4] = {0.f, 0.f, 0.f, 0.f};
+          float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+          if constexpr (KNOWN) {
+            kv[0] = kq[q].x; kv[1] = kq[q].y; kv[2] = kq[q].z; kv[3] = kq[q].w;
+            // EpiPosteriorKnown's rule at C = 0: the known elements use z at every t > 0; a quad without an observation skips the generator
+            const bool any_known = kv[0] == kv[0] || kv[1] == kv[1] || kv[2] == kv[2] || kv[3] == kv[3];
+            if (t > 0 && any_known) {
+              if (zbase) zz = ldq<FAST>(zbase + (size_t)pc * a.ldzz, f, F);
+              else zz = randn4(a.seed, a.row_offset + (uint32_t)p, (uint32_t)(f >> 2), (uint32_t)t, TAG_POSTERIOR);
+            }
+          }
+          const float zv[4] = {zz.x, zz.y, zz.z, zz.w};
+          float o[4], x0c[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float x0 = fmaf(cP, xv[r], cQ * e[r]);
+            x0c[r] = fminf(fmaxf(x0, lv[r]), hv[r]);
+            o[r] = fmaf(cG, x0c[r], fmaf(cF, xv[r], cH * pv[r]));
+            if constexpr (KNOWN) {
+              const float kn = t > 0 ? fmaf(La, kv[r], Ls * zv[r]) : kv[r];
+              o[r] = (kv[r] == kv[r]) ? kn : o[r];      // NaN: free
+            }
+          }
+          if (t == 0 && a.mut_mask && ok && f < a.mutation_dim) {
+            float* mrow = a.mut_mask + (size_t)p * a.mutation_dim;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (f + r < a.mutation_dim) mrow[f + r] = (o[r] > 0.5f) ? 1.0f : 0.0f;
+          }
+          if (p < P) stq<FAST>(a.xout + (size_t)pc * a.ldo, f, F, make_float4(o[0], o[1], o[2], o[3]));
+          if (t > 0 && p < P) stq<FAST>(hrow, f, F, make_float4(x0c[0], x0c[1], x0c[2], x0c[3]));
+          sync.tick();
+        }
+        }
+      }
+  }
+};
+
 // ---- output_proj fused with the MSE loss (models/diffusion.py:373-377) and its gradient ----
 // d = (acc + bias) - noise;  loss += sum d^2 * inv_count;  dout = d * gscale
 struct EpiMse {

@@ -96,6 +96,12 @@ struct Clip {
   const float* x0_coef;        // dev [S][4] = (P, Q, E, F)
 };
 
+// The DPM-Solver++(2M) multistep update (osd_sample_chain_multistep, EpiPosteriorHist): the chain keeps the previous step's clipped x0.
+// Always with a Clip, whose x0_coef rows are then (P, Q, G, F) and whose bounds may be all-infinite.
+struct Multistep {
+  const float* hist_coef;      // dev [S] = H; null = single-step chains
+};
+
 // One reverse-chain request, as every sampler engine receives it (api.hip: sample_request fills it from an entry point's arguments).
 struct ChainJob {
   StepPlan plan;
@@ -104,6 +110,7 @@ struct ChainJob {
   Guide guide;
   Known known;
   Clip clip;
+  Multistep multistep;
   int D, cond_dim, mutation_dim;   // row widths of x_T / noises / x_out, of cond and of mut_mask_out
   int64_t n_total;                 // rows of the whole request: injected draws of consecutive steps lie n_total * D floats apart
   // rows [r0, r0 + m) of the request as a job of their own
@@ -202,6 +209,9 @@ struct osd_handle {
   // that says the upload has read it
   std::vector<float> sched_x0_coef;
   float* clip_dev = nullptr; float* clip_host = nullptr; hipEvent_t clip_ev = nullptr;
+  // the multistep solver (osd_sample_chain_multistep): the current call's history coefficients [T] on the device, their host staging
+  // and the event that says the upload has read it
+  float* hist_dev = nullptr; float* hist_host = nullptr; hipEvent_t hist_ev = nullptr;
   bool have_cond_drop = false; float cond_drop_p = 0.f; const float* cond_drop_keep = nullptr;   // osd_train_condition_dropout: one-shot
   int64_t saved_rows = -1;           // rows of the last osd_denoiser_forward_train whose activations are still in the arena
   // constraint losses (osd_set_constraints); parts_dev = (mse, L_pc, L_me) of the last training call

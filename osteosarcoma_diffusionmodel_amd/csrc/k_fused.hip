@@ -215,6 +215,17 @@ hipError_t launch_posterior_clip(hipStream_t s, const GemmArgs& g, const Posteri
   if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorClip<false>>(s, g, a);
   return launch_gemm<TileSmall, true, true, EpiPosteriorClip<false>>(s, g, a);
 }
+// launch_posterior's tile choice; a.c.known selects the instantiation that also puts observed values back
+hipError_t launch_posterior_hist(hipStream_t s, const GemmArgs& g, const PosteriorHistArgs& a) {
+  constexpr long POST_BIG_FROM = 512;
+  const long big_tiles = (long)((g.F + 127) / 128) * ((g.P + 127) / 128);
+  if (a.c.known) {
+    if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorHist<true>>(s, g, a);
+    return launch_gemm<TileSmall, true, true, EpiPosteriorHist<true>>(s, g, a);
+  }
+  if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorHist<false>>(s, g, a);
+  return launch_gemm<TileSmall, true, true, EpiPosteriorHist<false>>(s, g, a);
+}
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a) {
   if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiMse>(s, g, a);
   return launch_gemm<TileSmall, true, true, EpiMse>(s, g, a);

@@ -27,6 +27,8 @@ hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const EpiPosterior
 hipError_t launch_posterior_known(hipStream_t s, const GemmArgs& g, const EpiPosteriorKnown::Args& a);
 // output_proj + posterior with the predicted x0 clipped to per-feature bounds (EpiPosteriorClip<a.known != null>); launch_posterior's tile choice
 hipError_t launch_posterior_clip(hipStream_t s, const GemmArgs& g, const PosteriorClipArgs& a);
+// output_proj + the DPM-Solver++(2M) multistep update on the clipped x0 (EpiPosteriorHist<a.c.known != null>); launch_posterior's tile choice
+hipError_t launch_posterior_hist(hipStream_t s, const GemmArgs& g, const PosteriorHistArgs& a);
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a);
 // k_b3t.hip: precision = 1 (hipErrorInvalidValue: outside the kernel's preconditions -- run the fp32 launch)
 hipError_t launch_mse_b3t(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a);

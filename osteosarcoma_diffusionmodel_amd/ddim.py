@@ -18,6 +18,10 @@ it -- epsilon: P = 1/sqrt(abar), Q = -sqrt(1 - abar)/sqrt(abar); v_prediction: P
 fp32 ``sqrt_alphas_cumprod`` / ``sqrt_one_minus_alphas_cumprod`` buffers -- while E, F and C = sigma do not, so the folded row of the other
 types is A = E*P + F, B = E*Q.  The default, "epsilon", keeps the expressions above and its arrays, bit for bit.
 
+``dpmpp_2m_table`` is the plan of the second-order multistep solver DPM-Solver++(2M) (Lu et al., 2022; ``osd_sample_chain_multistep``):
+the eta = 0 step of ``ddim_x0_table`` plus one term in the previous step's clipped x0^.  ``logsnr_timesteps`` spaces a plan uniformly in
+the log-SNR instead of in t; it is a plan like any other, for either solver.
+
 ``known_level_table`` is the second table of a chain around observed values (``osd_sample_chain_known``): the noise level each
 step arrives at, at which the observations are put back.
 """
@@ -144,6 +148,75 @@ def ddim_x0_table(alphas_cumprod, timesteps, eta: float, prediction: str = "epsi
         P, Q = _x0_reading(prediction, abar, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod)
         coef[:, 0], coef[:, 1] = P[tau], Q[tau]
     return coef.astype(np.float32)
+
+
+def _logsnr(abar: np.ndarray) -> np.ndarray:
+    """float64 lambda = ln(alpha / sigma) = (ln abar - ln(1 - abar)) / 2; +-inf where abar is 1 or 0."""
+    with np.errstate(divide="ignore"):
+        return 0.5 * (np.log(abar) - np.log1p(-abar))
+
+
+def dpmpp_2m_table(alphas_cumprod, timesteps, prediction: str = "epsilon", *, sqrt_alphas_cumprod=None,
+                   sqrt_one_minus_alphas_cumprod=None):
+    """(int32 [S] timesteps, fp32 [S][4] rows (P_s, Q_s, G_s, F_s), fp32 [S] H_s) for ``osd_sample_chain_multistep``:
+
+        x0^ = P*x + Q*out,   x' = G*clip(x0^) + F*x + H*clip(x0^)_prev       (prev: the step run before this one, s + 1)
+
+    With alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = ln(alpha / sigma), h_s = lambda' - lambda (' = at tau_{s-1}) and
+    phi = -alpha' * expm1(-h_s):
+
+        row S-1 (run first), and every row when S <= 2:   F = sigma'/sigma,  G = phi,               H = 0
+        rows 0 < s < S-1:   r = (lambda_s - lambda_{s+1}) / h_s,   F = sigma'/sigma,  G = phi*(1 + 1/(2r)),  H = -phi/(2r)
+        row 0 (the lower-order final step; h = inf):      F = 0,     G = 1,               H = 0     exactly
+
+    G + H and F are ``ddim_x0_table(..., eta=0)``'s E and F up to fp32 rounding, so S <= 2 is DDIM at eta = 0; (P, Q) are that table's,
+    bit for bit, for every ``prediction``.  Formed in float64 from the fp32 buffer and rounded once; rejects what the other tables
+    reject, and a plan whose log-SNR does not strictly decrease along it."""
+    pq = ddim_x0_table(alphas_cumprod, timesteps, 0.0, prediction, sqrt_alphas_cumprod=sqrt_alphas_cumprod,
+                       sqrt_one_minus_alphas_cumprod=sqrt_one_minus_alphas_cumprod)
+    abar = np.asarray(_host32(alphas_cumprod), dtype=np.float32).astype(np.float64)
+    tau = np.asarray(timesteps, dtype=np.int64).reshape(-1)
+    S = tau.size
+    lam = _logsnr(abar[tau])
+    if not np.isfinite(lam).all() or not (np.diff(lam) < 0).all():
+        raise ValueError("the log-SNR must be finite and strictly decreasing along the plan")
+    alpha, sigma = np.sqrt(abar[tau]), np.sqrt(1.0 - abar[tau])
+    coef = np.zeros((S, 4), dtype=np.float64)
+    hist = np.zeros(S, dtype=np.float64)
+    coef[0, 2:] = (1.0, 0.0)
+    for s in range(1, S):
+        h = lam[s - 1] - lam[s]
+        phi = -alpha[s - 1] * math.expm1(-h)
+        coef[s, 2:] = (phi, sigma[s - 1] / sigma[s])
+        if s < S - 1 and S > 2:
+            r = (lam[s] - lam[s + 1]) / h
+            coef[s, 2] = phi * (1.0 + 0.5 / r)
+            hist[s] = -0.5 * phi / r
+    out = coef.astype(np.float32)
+    out[:, :2] = pq[:, :2]
+    return tau.astype(np.int32), out, hist.astype(np.float32)
+
+
+def logsnr_timesteps(alphas_cumprod, S: int) -> np.ndarray:
+    """int32 [S]: a plan spaced uniformly in the log-SNR lambda = ln(sqrt(abar) / sqrt(1 - abar)), strictly increasing, tau_{S-1} = T - 1.
+
+    S targets uniform in lambda between lambda(0) and lambda(T - 1), the nearest timestep for each, then made strictly increasing: an
+    upward pass tau_i = max(tau_i, tau_{i-1} + 1), tau_{S-1} = T - 1, a downward pass tau_i = min(tau_i, tau_{i+1} - 1)."""
+    abar = np.asarray(_host32(alphas_cumprod), dtype=np.float32).astype(np.float64)
+    T, S = abar.shape[0], int(S)
+    if not 1 <= S <= T:
+        raise ValueError(f"num_inference_steps={S} outside [1, {T}]")
+    lam = _logsnr(abar)
+    if not np.isfinite(lam).all():
+        raise ValueError("alphas_cumprod must lie strictly inside (0, 1)")
+    targets = np.linspace(lam[0], lam[T - 1], S)
+    tau = np.abs(lam[None, :] - targets[:, None]).argmin(axis=1).astype(np.int64)
+    for i in range(1, S):
+        tau[i] = max(tau[i], tau[i - 1] + 1)
+    tau[S - 1] = T - 1
+    for i in range(S - 2, -1, -1):
+        tau[i] = min(tau[i], tau[i + 1] - 1)
+    return tau.astype(np.int32)
 
 
 def known_level_table(sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, timesteps) -> np.ndarray:

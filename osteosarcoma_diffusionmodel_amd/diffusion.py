@@ -658,7 +658,8 @@ class BiologyAwareDiffusionModel(nn.Module):
     @torch.no_grad()
     def sample(self, conditions, num_samples: int = 1, *, x_T=None, noise=None, seed: Optional[int] = None,
                row_offset: int = 0, return_mutation_mask: bool = False, num_inference_steps: Optional[int] = None,
-               eta: float = 0.0, guidance_scale: float = 1.0, known=None, x0_bounds=None):
+               eta: float = 0.0, guidance_scale: float = 1.0, known=None, x0_bounds=None, solver: Optional[str] = None,
+               timestep_spacing: str = "uniform"):
         """Full reverse chain.  ``x_T`` [N,D] and ``noise`` [T-1,N,D] (draw order t = T-1..1) inject the
         random draws; otherwise Philox(seed, row_offset + row) generates them on the device.
 
@@ -688,11 +689,33 @@ class BiologyAwareDiffusionModel(nn.Module):
         (``precision = "bf16x3"`` raises ValueError).
 
         The chain follows ``prediction_type``: every step is x' = E x0^ + F x + C z with x0^ = P x + Q out, and only (P, Q) depend on the
-        type, so every engine and every option above runs a v_prediction or sample model from refolded tables, at the same speed."""
+        type, so every engine and every option above runs a v_prediction or sample model from refolded tables, at the same speed.
+
+        ``solver`` is ``None`` or ``"ddim"`` (the calls above, any engine, the same bits) or ``"dpmpp_2m"``: DPM-Solver++(2M) (Lu et al.
+        2022), the second-order multistep solver on the predicted x0^ -- the eta = 0 DDIM step plus one term in the previous step's clipped
+        x0^ (``ddim.dpmpp_2m_table``), inside the same launch.  It needs ``num_inference_steps`` and ``eta == 0``, takes ``noise`` only
+        together with ``known`` (whose observed elements it feeds), and runs with ``guidance_scale``, ``known``, ``x0_bounds`` and every
+        ``prediction_type``; per-layer kernels (``last_sampler == "graph"``), fp32 (``precision = "bf16x3"`` raises ValueError).
+
+        ``timestep_spacing`` chooses the S timesteps of ``num_inference_steps``, for either solver: ``"uniform"`` (``ddim.ddim_timesteps``)
+        or ``"logsnr"`` (``ddim.logsnr_timesteps``: uniform in ln(sqrt(abar)/sqrt(1-abar)); better for the multistep solver from about ten
+        steps on, worse for DDIM and at five).  Without ``num_inference_steps`` it must be ``"uniform"``."""
         from . import objective as OB
         pred = OB.check_prediction_type(self.prediction_type)
         sched = dict(sqrt_alphas_cumprod=self.sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod=self.sqrt_one_minus_alphas_cumprod)
         guide = self._guidance(guidance_scale)
+        if solver not in (None, "ddim", "dpmpp_2m"):
+            raise ValueError(f"solver must be None, 'ddim' or 'dpmpp_2m', got {solver!r}")
+        if timestep_spacing not in ("uniform", "logsnr"):
+            raise ValueError(f"timestep_spacing must be 'uniform' or 'logsnr', got {timestep_spacing!r}")
+        multistep = solver == "dpmpp_2m"
+        if num_inference_steps is None:
+            if multistep:
+                raise ValueError("solver='dpmpp_2m' needs num_inference_steps")
+            if timestep_spacing != "uniform":
+                raise ValueError("timestep_spacing applies to num_inference_steps: pass it as well")
+        if multistep and float(eta) != 0.0:
+            raise ValueError("solver='dpmpp_2m' is deterministic: eta must be 0")
         if x0_bounds is None:
             x0_bounds = self.x0_bounds
         bounds = None
@@ -710,7 +733,7 @@ class BiologyAwareDiffusionModel(nn.Module):
                 kn = None                       # nothing observed: today's entry points, any engine, their bits
         plan = None
         if num_inference_steps is not None:
-            from .ddim import ddim_step_table, ddim_timesteps
+            from .ddim import ddim_step_table, ddim_timesteps, dpmpp_2m_table, logsnr_timesteps
             if not 0.0 <= float(eta) <= 1.0:
                 raise ValueError(f"eta={eta} outside [0, 1]")
             steps = int(num_inference_steps)
@@ -718,7 +741,11 @@ class BiologyAwareDiffusionModel(nn.Module):
                 raise ValueError(f"num_inference_steps={steps} outside [1, {self.num_steps}]")
             if noise is not None and float(eta) == 0.0 and kn is None:
                 raise ValueError("noise: eta = 0 draws no z (pass eta > 0 or leave noise out)")
-            plan = ddim_step_table(self.alphas_cumprod, ddim_timesteps(self.num_steps, steps), eta, pred, **sched)
+            taus = ddim_timesteps(self.num_steps, steps) if timestep_spacing == "uniform" else logsnr_timesteps(self.alphas_cumprod, steps)
+            if multistep:
+                plan = dpmpp_2m_table(self.alphas_cumprod, taus, pred, **sched)
+            else:
+                plan = ddim_step_table(self.alphas_cumprod, taus, eta, pred, **sched)
         elif float(eta) != 0.0:
             raise ValueError("eta applies to the DDIM sampler: pass num_inference_steps as well")
         n_draws = self.num_steps - 1 if plan is None else plan[0].size - 1
@@ -739,7 +766,7 @@ class BiologyAwareDiffusionModel(nn.Module):
         if seed is None:
             seed = _draw_seed()
         flags = self._flags() | (L.OSD_F_GRAPH if self.use_graph else 0)
-        engine = 0 if (guide is not None or kn is not None or bounds is not None) else L.lib().osd_sample_engine(eng.handle, n, flags)
+        engine = 0 if (guide is not None or kn is not None or bounds is not None or multistep) else L.lib().osd_sample_engine(eng.handle, n, flags)
         if engine < 0:
             L.check(engine)
         if engine == 1:
@@ -753,7 +780,17 @@ class BiologyAwareDiffusionModel(nn.Module):
             return int(v.value)
 
         gave_up_before = counter(b"chain_fallbacks")
-        if bounds is not None:
+        if multistep:
+            from .ddim import known_level_table
+            tau, x0c, hist = plan
+            level = None if kn is None else known_level_table(self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, tau)
+            L.check(L.lib().osd_sample_chain_multistep(eng.handle, L.ptr(conditions), n, L.ptr(xT), L.ptr(zs), seed, int(row_offset),
+                                                       L.ptr(out), L.ptr(mask), flags, tau.ctypes.data, x0c.ctypes.data, hist.ctypes.data,
+                                                       None if level is None else level.ctypes.data, int(tau.size),
+                                                       None if guide is None else guide[1].ctypes.data, 1.0 if guide is None else guide[0],
+                                                       L.ptr(kn), self.data_dim, None if bounds is None else bounds[0].ctypes.data,
+                                                       None if bounds is None else bounds[1].ctypes.data))
+        elif bounds is not None:
             from .ddim import ddim_x0_table, known_level_table
             tau, coef = plan if plan is not None else (None, None)
             x0c = None if tau is None else ddim_x0_table(self.alphas_cumprod, tau, eta, pred, **sched)

@@ -163,6 +163,17 @@ class SyntheticPatientGenerator:
             x0_bounds = (self.config.get("generation") or {}).get("x0_bounds")
         return x0_bounds
 
+    def _solver(self, solver, timestep_spacing) -> dict:
+        """``solver`` / ``timestep_spacing`` of generate / generate_scenarios / impute as model.sample's keywords: the caller's, else the
+        config's ``generation.solver`` / ``generation.timestep_spacing``; absent keys change nothing."""
+        if hasattr(self.model, "vae"):
+            if solver is not None or timestep_spacing is not None:
+                raise ValueError("solver / timestep_spacing select the diffusion model's sampler and are not accepted for a cVAE model")
+            return {}
+        gen = self.config.get("generation") or {}
+        return {"solver": gen.get("solver") if solver is None else solver,
+                "timestep_spacing": gen.get("timestep_spacing", "uniform") if timestep_spacing is None else timestep_spacing}
+
     def _known(self, known, n: int):
         """``known`` of generate / generate_scenarios as the device tensor model.sample takes, or None."""
         if known is None:
@@ -172,7 +183,8 @@ class SyntheticPatientGenerator:
     @torch.no_grad()
     def generate(self, num_samples: int, scenario: Optional[Dict] = None, guidance_scale: float = 1.0,
                  *, seed: Optional[int] = None, row_offset: int = 0, x_T=None, noise=None, sampling_steps: Optional[int] = None,
-                 eta: float = 0.0, known=None, x0_bounds=None) -> Dict[str, np.ndarray]:
+                 eta: float = 0.0, known=None, x0_bounds=None, solver: Optional[str] = None,
+                 timestep_spacing: Optional[str] = None) -> Dict[str, np.ndarray]:
         """utils/generate.py:96-144.  ``guidance_scale`` is the classifier-free-guidance strength (``model.sample(guidance_scale=w)``:
         1 the plain conditional sampler, larger values follow the scenario more strongly) when the model has a null condition
         (``model.null_condition``: trained with ``training.condition_dropout``).  A model without one -- every reference
@@ -187,8 +199,12 @@ class SyntheticPatientGenerator:
         ``x0_bounds`` (``assemble_bounds``: a ``(lo, hi)`` pair or a dict over ``mutations`` / ``expression`` / ``pathways``) clips the
         predicted clean patient of every step to per-feature bounds (``model.sample(x0_bounds=...)``) -- the usual companion of a large
         ``guidance_scale`` and of few ``sampling_steps``; every returned value lies inside its bounds.  Default: the config's
-        ``generation.x0_bounds`` when it has one, else ``model.x0_bounds``; ``False`` switches it off."""
+        ``generation.x0_bounds`` when it has one, else ``model.x0_bounds``; ``False`` switches it off.
+        ``solver`` (``"ddim"`` or ``"dpmpp_2m"``, the second-order multistep solver: about the accuracy of twice the DDIM steps; needs
+        ``sampling_steps`` and ``eta == 0``) and ``timestep_spacing`` (``"uniform"`` or ``"logsnr"``) as in ``model.sample``.  Defaults:
+        the config's ``generation.solver`` / ``generation.timestep_spacing`` when it has them, else DDIM on uniform steps."""
         x0_bounds = self._x0_bounds(x0_bounds)
+        solver_kw = self._solver(solver, timestep_spacing)
         logger.info(f"Generating {num_samples} synthetic patients...")
         if scenario:
             logger.info(f"Scenario: {scenario}")
@@ -212,7 +228,7 @@ class SyntheticPatientGenerator:
             samples, mask = self.model.sample(conditions, num_samples=num_samples, seed=seed, row_offset=row_offset,
                                               x_T=x_T, noise=noise, return_mutation_mask=True, num_inference_steps=sampling_steps,
                                               eta=eta, guidance_scale=self._guidance_scale(guidance_scale),
-                                              known=self._known(known, num_samples), x0_bounds=x0_bounds)
+                                              known=self._known(known, num_samples), x0_bounds=x0_bounds, **solver_kw)
             samples = samples.cpu().numpy()
             # (mutations > 0.5).astype(float), evaluated by the last reverse step's epilogue on the device
             mutations = mask.cpu().numpy().astype(float)
@@ -225,7 +241,8 @@ class SyntheticPatientGenerator:
     def generate_scenarios(self, scenarios: List[Dict], samples_per_scenario: int, *, seed: Optional[int] = None,
                            batched: bool = True, sampling_steps: Optional[int] = None,
                            eta: float = 0.0, guidance_scale: float = 1.0, known=None,
-                           x0_bounds=None) -> Dict[str, Dict[str, np.ndarray]]:
+                           x0_bounds=None, solver: Optional[str] = None,
+                           timestep_spacing: Optional[str] = None) -> Dict[str, Dict[str, np.ndarray]]:
         """utils/generate.py:146-175: one result dict per scenario name.
 
         The reference runs the scenarios one after the other, each a chain of T sequential steps.  Rows never interact and the
@@ -235,8 +252,9 @@ class SyntheticPatientGenerator:
         the reference's loop (one chain, and one freshly drawn Philox seed, per scenario).  ``sampling_steps`` / ``eta`` select the
         strided DDIM sampler, ``guidance_scale`` the guided one, as in ``generate``.  ``known`` ([samples_per_scenario or 1, D] or a
         dict of blocks, as in ``generate``) holds the same observed values in every scenario: the counterfactual question.
-        ``x0_bounds`` as in ``generate``."""
+        ``x0_bounds``, ``solver`` and ``timestep_spacing`` as in ``generate``."""
         x0_bounds = self._x0_bounds(x0_bounds)
+        solver_kw = self._solver(solver, timestep_spacing)
         if not batched or hasattr(self.model, "vae") or len(scenarios) < 2:
             out = {}
             for scenario in scenarios:
@@ -244,7 +262,7 @@ class SyntheticPatientGenerator:
                 logger.info(f"\nGenerating scenario: {name}")
                 out[name] = self.generate(num_samples=samples_per_scenario, scenario=scenario["conditions"],
                                           sampling_steps=sampling_steps, eta=eta, guidance_scale=guidance_scale, known=known,
-                                          x0_bounds=x0_bounds)
+                                          x0_bounds=x0_bounds, solver=solver, timestep_spacing=timestep_spacing)
             return out
         n = int(samples_per_scenario)
         for scenario in scenarios:
@@ -258,7 +276,8 @@ class SyntheticPatientGenerator:
         with torch.no_grad():
             samples, mask = self.model.sample(conditions, num_samples=conditions.shape[0], seed=seed, return_mutation_mask=True,
                                               num_inference_steps=sampling_steps, eta=eta,
-                                              guidance_scale=self._guidance_scale(guidance_scale), known=kn, x0_bounds=x0_bounds)
+                                              guidance_scale=self._guidance_scale(guidance_scale), known=kn, x0_bounds=x0_bounds,
+                                              **solver_kw)
         samples, mask, cond_np = samples.cpu().numpy(), mask.cpu().numpy().astype(float), conditions.cpu().numpy()
         md, ed = self.mutation_dim, self.expression_dim
         out = {}
@@ -270,13 +289,16 @@ class SyntheticPatientGenerator:
         return out
 
     def impute(self, features, conditions, *, seed: Optional[int] = None, sampling_steps: Optional[int] = None, eta: float = 0.0,
-               guidance_scale: float = 1.0, x0_bounds=None) -> Dict[str, np.ndarray]:
+               guidance_scale: float = 1.0, x0_bounds=None, solver: Optional[str] = None,
+               timestep_spacing: Optional[str] = None) -> Dict[str, np.ndarray]:
         """Fill the holes of real rows: ``features`` [n, D] with NaN where a value is missing, ``conditions`` [n, condition_dim] the
         rows' own.  Observed values come back exactly, the holes are sampled around them; returns ``generate``'s dictionary.
-        ``x0_bounds`` as in ``generate``: the holes stay inside the bounds, the observed values are the observed values."""
+        ``x0_bounds`` as in ``generate``: the holes stay inside the bounds, the observed values are the observed values.  ``solver`` and
+        ``timestep_spacing`` as in ``generate``."""
         if hasattr(self.model, "vae"):
             raise ValueError("impute conditions the diffusion model's reverse chain and is not accepted for a cVAE model")
         x0_bounds = self._x0_bounds(x0_bounds)
+        solver_kw = self._solver(solver, timestep_spacing)
         if isinstance(conditions, torch.Tensor):
             cond = conditions.detach().to(device=self.device, dtype=torch.float32)
         else:
@@ -291,7 +313,7 @@ class SyntheticPatientGenerator:
         with torch.no_grad():
             samples, mask = self.model.sample(cond, num_samples=n, seed=seed, return_mutation_mask=True, num_inference_steps=sampling_steps,
                                               eta=eta, guidance_scale=self._guidance_scale(guidance_scale), known=self._known(features, n),
-                                              x0_bounds=x0_bounds)
+                                              x0_bounds=x0_bounds, **solver_kw)
         samples = samples.cpu().numpy()
         return {"mutations": mask.cpu().numpy().astype(float), "expression": samples[:, md:md + ed], "pathways": samples[:, md + ed:],
                 "conditions": cond.cpu().numpy()}
