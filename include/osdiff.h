@@ -124,6 +124,7 @@ int osd_set_stream(osd_handle *h, void *hip_stream);
  * "cond_bwd_fused"         -- 0 | 1 (1) -- 1: the conditioning branch's backward below h0 (time-table scatter, two 64-wide dgrads,
  *                             SiLU backward, the first embedding Linear's weight gradient) as one launch, k_cond_bwd in
  *                             csrc/k_train.hip, for hidden_dims[0] <= 256 and a multiple of 32; 0: five launches.
+ * "bound_rows"             -- 1..2^30 (32 768) -- rows per launch group of osd_bound_sweep / osd_row_sq_error: caps their workspace.
  *
  * Any other name: OSD_EINVAL. */
 int osd_set_option(osd_handle *h, const char *name, int64_t value);
@@ -598,6 +599,28 @@ int osd_get_loss_parts(osd_handle *h, float *parts_host3);
 #define OSD_LOSS_L1    1
 #define OSD_LOSS_HUBER 2
 int osd_set_loss(osd_handle *h, int kind, double huber_delta, const float *t_weights_host);
+
+/* ---- the per-patient likelihood bound ----------------------------------------------------------
+ * se[r] = sum_d (out[r][d] - target[r][d])^2: an eval-mode forward of q_sample(x0, t_r) and the per-row squared error of the network's
+ * raw output against the training target of the current prediction type (eps, a eps - b x0 or x0), in the launch of output_proj
+ * (EpiRowSq, csrc/epilogues.h).  No float atomics: two calls on the same inputs return equal bits.  Both entry points are the
+ * loss-only training call with that epilogue: no dropout, no gradients; they ignore osd_set_loss and osd_set_constraints and leave
+ * them as they were, and they consume no armed osd_train_batch_source / osd_train_condition_dropout -- OSD_ESTATE while one is armed
+ * (it stays armed).  fp32 kernels only: OSD_EUNSUPPORTED under "precision" 1.  Asynchronous on the handle's stream.
+ * Generated noise (noise_in NULL): the normals of element quad c >> 2 of patient i at timestep t are the Philox block
+ * (seed, row_offset + i, c >> 2, t, q_sample's tag) -- a draw depends on (seed, global patient id, timestep) alone, not on the
+ * chunking, on S, or on how a cohort is split over calls.
+ * OSD_EINVAL: a null tensor, n < 1, S < 1, a timestep outside [0, T), row_offset + n outside the 32-bit id space.
+ *   t_index   dev int32 [n], clamped into [0, T)
+ *   noise_in  dev [n][D], or NULL
+ *   se_out    dev [n] */
+int osd_row_sq_error(osd_handle *h, const float *x0, const float *cond, int64_t n, const int32_t *t_index,
+                     const float *noise_in, uint64_t seed, int64_t row_offset, float *se_out);
+/* The same for every (timestep, patient) pair: se_out dev [S][n], noise_in dev [S][n][D] or NULL, timesteps_host S host values.  The
+ * rows of a launch are pairs in that order, x0 and cond are gathered from the patient (never replicated S times), and at most
+ * "bound_rows" rows go into one launch group, so the workspace is bounded for any n x S; a group may end inside a timestep. */
+int osd_bound_sweep(osd_handle *h, const float *x0, const float *cond, int64_t n, const int32_t *timesteps_host, int S,
+                    const float *noise_in, uint64_t seed, int64_t row_offset, float *se_out);
 /* Stand-alone ops (stream/device based, synchronous): loss_out (dev float[1]) += weight * L and, when
  * dx != NULL, dx (dev [rows][ld]) += weight * dL/dx.  x, x_recon, x_true: dev [rows][ld], cols <= ld. */
 int osd_loss_pathway_coherence(void *stream, int device, const float *x, int64_t rows, int ld, int cols,

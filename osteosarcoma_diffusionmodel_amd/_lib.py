@@ -104,6 +104,8 @@ _SIGNATURES = {
     "osd_set_constraints": (C.c_int, [_P, C.POINTER(OsdConstraints)]),
     "osd_get_loss_parts": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "osd_set_loss": (C.c_int, [_P, C.c_int, C.c_double, _P]),
+    "osd_row_sq_error": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_int64, _P]),
+    "osd_bound_sweep": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int, _P, C.c_uint64, C.c_int64, _P]),
     "osd_loss_pathway_coherence": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                              C.c_double, _P, _P]),
     "osd_loss_mutation_expression": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,

@@ -407,6 +407,7 @@ static const Option OPTIONS[] = {
     {"chain_steps_per_launch", OSD_FIELD(chain_steps_per_launch), 0, INT64_MAX, "chain_steps_per_launch must be >= 0"},
     {"chain_stagger", OSD_FIELD(chain_stagger), 0, 100000000, "chain_stagger must be in [0,1e8] cycles"},
     {"train_streams", OSD_FIELD(train_streams), 1, 2, "train_streams must be 1 or 2"},
+    {"bound_rows", OSD_FIELD(bound_rows), 1, 0x7fffffff / 2, "bound_rows must be in [1, 2^30)"},
 };
 #undef OSD_FIELD
 
@@ -547,6 +548,7 @@ int osd_destroy(osd_handle* h) {
   if (h->parts_dev) e = hipFree(h->parts_dev);
   if (h->loss_tw) e = hipFree(h->loss_tw);
   if (h->t_san) e = hipFree(h->t_san);
+  if (h->bound_ts) e = hipFree(h->bound_ts);
   for (hipEvent_t ev : h->ev_pool) e = hipEventDestroy(ev);
   if (h->wgrad_stream) e = hipStreamDestroy(h->wgrad_stream);
   cons_free_plan(&h->cons);

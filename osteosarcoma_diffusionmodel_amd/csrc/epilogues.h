@@ -1100,6 +1100,96 @@ struct EpiLoss {
   }
 };
 
+// ---- output_proj fused with a PER-ROW squared error against the training target ----
+// d = (acc + bias) - target;  part[slot][row] = sum over the wave's features of d^2
+// EpiMse's operand paths, path for path -- the transposer on full row segments when FAST, the guarded form elsewhere; padding rows
+// and columns carry d = 0 -- without pred, dout or a scalar loss.  No float atomics: a lane holds one row (l31) of each 32-row
+// block and a slice of its features, sums them in-lane over fb and q in that order, and meets the other half-wave once (lane^32:
+// the sum of the two halves is commutative, so both lanes form the same bits).  The wave's (slot, row) partials -- slot = the wave's
+// feature origin / its feature extent, one wave per (slot, row) in the whole grid -- go to part [slots][ld] with ordinary stores, 32
+// consecutive floats per instruction; k_rowsq_reduce adds the slots of a row in slot order.  Equal inputs give equal bits.
+// Nothing needs zeroing: every (slot < ceil(F / extent), row < P) element is written exactly once per launch.
+struct EpiRowSq {
+  static constexpr bool COUNTED_STORES = false;   // one store per row and wave, not per accumulator quad
+  static constexpr bool XBUF = true;              // the target comes in as full row segments
+  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
+  struct Args {
+    const float* bias; const float* target; int ldn;
+    float* part; long long ld;    // [slots][ld], ld >= P
+  };
+  static bool fast_ok(const Args& a, int F) { return F % 4 == 0 && al16(a.bias) && al16(a.target) && a.ldn % 4 == 0; }
+  template <int NFB> using Pre = EpiMse::Pre<NFB>;
+  template <int NFB, bool FAST>
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
+    Pre<NFB> r;
+    const int h = lane >> 5;
+#pragma unroll
+    for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r.bias[fb][q] = ldq<FAST>(a.bias, fw + 32 * fb + 8 * q + 4 * h, F);
+    return r;
+  }
+  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
+                                               float* xbuf = nullptr, Sync&& sync = Sync()) {
+    const int l31 = lane & 31, h = lane >> 5;
+    if (fw >= F || pw >= P) return;                    // uniform over the wave: a slot past the last one, or padding rows only
+    float part[NPB];
+#pragma unroll
+    for (int pb = 0; pb < NPB; ++pb) part[pb] = 0.f;
+    if (FAST && xbuf) {
+      const WaveXpose<NPB> xp{xbuf};
+      const int rows = P - pw;                         // valid rows of the wave's block (uniform)
+#pragma unroll
+      for (int fb = 0; fb < NFB; ++fb) {
+        const int cols = F - (fw + 32 * fb);            // valid features of this block (uniform)
+        if (cols <= 0) continue;
+        xp.template load_rows<true>(a.target + (size_t)pw * a.ldn + fw + 32 * fb, a.ldn, lane, rows, cols);
+#pragma unroll
+        for (int pb = 0; pb < NPB; ++pb)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int fo = 8 * q + 4 * h;
+            const bool prow = 32 * pb + l31 < rows;
+            const float4 bv = pre.bias[fb][q];
+            const float4 nz = xp.get(pb, q, l31, h);
+            float4 d = make_float4((acc[fb][pb][4 * q] + bv.x) - nz.x, (acc[fb][pb][4 * q + 1] + bv.y) - nz.y,
+                                   (acc[fb][pb][4 * q + 2] + bv.z) - nz.z, (acc[fb][pb][4 * q + 3] + bv.w) - nz.w);
+            if (!prow || fo >= cols) d.x = 0.f;
+            if (!prow || fo + 1 >= cols) d.y = 0.f;
+            if (!prow || fo + 2 >= cols) d.z = 0.f;
+            if (!prow || fo + 3 >= cols) d.w = 0.f;
+            part[pb] += d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w;
+          }
+      }
+    } else {
+      OSD_FOR_QUADS(fb, pb, q) {
+        const int f = fw + 32 * fb + 8 * q + 4 * h;
+        const int p = pw + 32 * pb + l31;
+        const int pc = p < P ? p : P - 1;
+        const bool prow = p < P;
+        const float4 bv = pre.bias[fb][q];
+        const float4 nz = ldq<FAST>(a.target + (size_t)pc * a.ldn, f, F);
+        float4 d = make_float4((acc[fb][pb][4 * q] + bv.x) - nz.x, (acc[fb][pb][4 * q + 1] + bv.y) - nz.y,
+                               (acc[fb][pb][4 * q + 2] + bv.z) - nz.z, (acc[fb][pb][4 * q + 3] + bv.w) - nz.w);
+        if (!prow || f >= F) d.x = 0.f;
+        if (!prow || f + 1 >= F) d.y = 0.f;
+        if (!prow || f + 2 >= F) d.z = 0.f;
+        if (!prow || f + 3 >= F) d.w = 0.f;
+        part[pb] += d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w;
+        sync.tick();
+      }
+    }
+    float* slot = a.part + (long long)(fw / (32 * NFB)) * a.ld;
+#pragma unroll
+    for (int pb = 0; pb < NPB; ++pb) {
+      const float s = part[pb] + swap_halves(part[pb]);
+      const int p = pw + 32 * pb + l31;
+      if (h == 0 && p < P) slot[p] = s;
+    }
+  }
+};
+
 // ---- RBF-kernel sum for the MMD metric (utils/validation.py:287-296) -------------------------------
 // acc = x_f . y_p;  d2 = |x_f|^2 + |y_p|^2 - 2 acc;  sum += exp(-gamma * max(d2, 0)) over the valid tile
 struct EpiRbfSum {

@@ -227,6 +227,9 @@ struct osd_handle {
   float* d_pq = nullptr; int conv_kind = -1;
   int loss_kind = 0; float loss_delta = 1.0f;
   float* loss_tw = nullptr; bool loss_tw_set = false;
+  // the likelihood bound (osd_row_sq_error / osd_bound_sweep): rows per launch group of the sweep, and the sweep's timesteps on the device
+  int64_t bound_rows = 32768;        // osd_set_option("bound_rows")
+  int* bound_ts = nullptr; int64_t bound_ts_cap = 0;
   std::vector<void*> wg_plans;       // grouped weight-gradient launches (wgrad_group.hip): one cached work list per flush point
   // persistent reverse-chain kernel (chain.h / chain.hip)
   int sampler = 0;                   // osd_set_option("sampler"): 0 auto, 1 chain kernel whenever the architecture allows, 2 per-layer kernels

@@ -260,6 +260,59 @@ hipError_t launch_q_sample_src(hipStream_t s, const BatchSrc& b, const int* t, c
   return hipGetLastError();
 }
 
+// q_sample for the likelihood bound: the rows of a launch are (timestep, patient) pairs of a [S][n_pat] grid,
+// x0 and the condition row are gathered from the patient -- the cohort is never replicated S times -- and the generated normals of
+// patient i at timestep t come from the Philox block (seed, row_offset + i, quad, t, TAG_QNOISE): t sits where k_q_sample passes 0, so
+// a draw depends on (seed, global patient id, timestep) alone, not on how the pairs were cut into launches.  The arithmetic per
+// element is k_q_sample's.  One workgroup walks whole rows (the row's scalars are wave-uniform); t_out / cond_out receive the row's
+// timestep and condition for the layers that gather by row.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_q_sample_pairs(const float* x0, const float* cond, int cd, PairRows pr, const float* sqrt_ac, const float* sqrt_1m,
+                                                        const float* noise_in, int64_t rows, int cols, uint64_t seed, uint32_t row_offset, float* x_t,
+                                                        int ldxt, float* target_out, int* t_out, float* cond_out, ZeroList zl) {
+  zero_list(zl);
+  const int c4n = (cols + 3) >> 2;
+  for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+    const int64_t pair = pr.pair0 + r;
+    const int64_t i = pair % pr.n_pat;
+    const int tt = pr.t_row ? pr.t_row[r] : pr.t_list[pair / pr.n_pat];
+    const float a = sqrt_ac[tt], b = sqrt_1m[tt];
+    if (threadIdx.x == 0) t_out[r] = tt;
+    if (cond_out && (int)threadIdx.x < cd) cond_out[r * cd + threadIdx.x] = cond[i * cd + threadIdx.x];
+    const float* xrow = x0 + i * cols;
+    for (int q = threadIdx.x; q < c4n; q += 256) {
+      const int c = 4 * q;
+      const float4 x = ld4g(xrow, c, cols);
+      float4 n;
+      if (noise_in) n = ld4g(noise_in + r * cols, c, cols);
+      else n = randn4(seed, row_offset + (uint32_t)i, (uint32_t)q, (uint32_t)tt, TAG_QNOISE);
+      float4 o;
+      o.x = __fadd_rn(__fmul_rn(a, x.x), __fmul_rn(b, n.x));
+      o.y = __fadd_rn(__fmul_rn(a, x.y), __fmul_rn(b, n.y));
+      o.z = __fadd_rn(__fmul_rn(a, x.z), __fmul_rn(b, n.z));
+      o.w = __fadd_rn(__fmul_rn(a, x.w), __fmul_rn(b, n.w));
+      st4g(x_t + r * ldxt, c, cols, o);
+      zero_pad(x_t + r * ldxt, cols, ldxt, c);
+      if (target_out) st4g(target_out + r * cols, c, cols, q_target<KIND>(a, b, x, n));
+    }
+  }
+}
+hipError_t launch_q_sample_pairs(hipStream_t s, const float* x0, const float* cond, int cd, const PairRows& pr, const float* sqrt_ac,
+                                 const float* sqrt_1m, const float* noise_in, int64_t rows, int cols, uint64_t seed, uint32_t row_offset, float* x_t,
+                                 int ldxt, float* target_out, int* t_out, float* cond_out, const ZeroList* zl, int kind) {
+  if (rows <= 0) return hipSuccess;
+  if (!t_out || pr.n_pat < 1 || (!pr.t_row && !pr.t_list) || cd > 256) return hipErrorInvalidValue;
+  if (!target_out && !(kind == OSD_PRED_EPSILON && noise_in)) return hipErrorInvalidValue;      // only injected eps is its own target
+  ZeroList z{};
+  if (zl) z = *zl;
+  int64_t blocks = rows < 16384 ? rows : 16384;
+  if (blocks < (zl ? 32 : 1)) blocks = zl ? 32 : 1;      // the zero list is walked by the first 32 workgroups
+  auto k = kind == OSD_PRED_V ? k_q_sample_pairs<OSD_PRED_V> : kind == OSD_PRED_SAMPLE ? k_q_sample_pairs<OSD_PRED_SAMPLE> : k_q_sample_pairs<OSD_PRED_EPSILON>;
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), 256, 0, s, x0, cond, cd, pr, sqrt_ac, sqrt_1m, noise_in, rows, cols, seed, row_offset, x_t,
+                     ldxt > 0 ? ldxt : cols, target_out, t_out, cond_out, z);
+  return hipGetLastError();
+}
+
 // Classifier-free guidance (utils/generate.py:97-110, guidance_scale) on the last hidden activation: output_proj is linear, so
 // eps_u + w (eps_c - eps_u) = output_proj(h_u + w (h_c - h_u)) and the combination costs a pass over [m][256], not over [m][D].
 // h: [2 m][cols], rows [0, m) the conditional branch, rows [m, 2 m) the unconditional one; row r < m is overwritten with

@@ -1,4 +1,4 @@
-// k_fused.hip -- input_proj (+t_emb +c_proj), output_proj (+posterior, around known values, with x0 clipped), output_proj (+MSE), output_proj (+configurable loss).
+// k_fused.hip -- input_proj (+t_emb +c_proj), output_proj (+posterior, around known values, with x0 clipped), output_proj (+MSE), output_proj (+configurable loss), output_proj (+per-row squared error).
 #include "kernels.h"
 #include "launch.h"
 
@@ -234,6 +234,29 @@ hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a) {
 hipError_t launch_loss(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a) {
   if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiLoss>(s, g, a);
   return launch_gemm<TileSmall, true, true, EpiLoss>(s, g, a);
+}
+
+// se[r] = part[0][r] + part[1][r] + ... in slot order (+ *poison, a word that is 0 unless a squad launch of the same call gave up
+// and stored a NaN there: x + 0 keeps the bits of a sum of squares)
+__global__ __launch_bounds__(256) void k_rowsq_reduce(const float* __restrict__ part, long long ld, int slots, int rows, const float* poison,
+                                                      float* __restrict__ se) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  float s = part[r];
+#pragma unroll 8
+  for (int k = 1; k < slots; ++k) s += part[(long long)k * ld + r];      // loads ahead, adds in slot order
+  if (poison) s += *poison;
+  se[r] = s;
+}
+// output_proj + per-row squared error: launch_mse's tile choice, then the slot sum.  a.part holds rowsq_slots(F) x a.ld floats.
+static_assert(TileBig::WF == ROWSQ_WF && TileSmall::WF == ROWSQ_WF, "rowsq_slots() counts wave feature origins of both tiles");
+hipError_t launch_row_sq(hipStream_t s, const GemmArgs& g, const EpiRowSq::Args& a, const float* poison, float* se) {
+  if (g.F <= 0 || g.P <= 0) return hipSuccess;
+  if (a.ld < g.P) return hipErrorInvalidValue;
+  const hipError_t e = use_big_tile(g.F, g.P) ? launch_gemm<TileBig, true, true, EpiRowSq>(s, g, a) : launch_gemm<TileSmall, true, true, EpiRowSq>(s, g, a);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_rowsq_reduce, dim3((g.P + 255) / 256), 256, 0, s, a.part, a.ld, rowsq_slots(g.F), g.P, poison, se);
+  return hipGetLastError();
 }
 
 }  // namespace osd

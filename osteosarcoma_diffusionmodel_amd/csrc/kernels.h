@@ -35,6 +35,11 @@ hipError_t launch_mse_b3t(hipStream_t s, const GemmArgs& g, const EpiMse::Args& 
 // output_proj + the loss of osd_set_loss (EpiLoss): launch_mse's / launch_mse_b3t's tile choices and return values
 hipError_t launch_loss(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a);
 hipError_t launch_loss_b3t(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a);
+// output_proj + per-row squared error (EpiRowSq), launch_mse's tile choice, then k_rowsq_reduce: se[P].  a.part: rowsq_slots(F) x a.ld
+// floats.  poison: a device word added to every row (0, or the NaN of a squad launch that gave up), or null.  fp32 only.
+constexpr int ROWSQ_WF = 64;      // feature extent of a wave in both tiles of the tile choice
+inline int rowsq_slots(int F) { return (F + ROWSQ_WF - 1) / ROWSQ_WF; }
+hipError_t launch_row_sq(hipStream_t s, const GemmArgs& g, const EpiRowSq::Args& a, const float* poison, float* se);
 
 // k_gn.hip / k_gn_drop.hip ------------------------------------------------------------
 // Arguments common to every GW; the wrappers copy them into EpiGnSilu<GW,DROP>::Args.
@@ -65,6 +70,13 @@ hipError_t launch_q_sample(hipStream_t s, const float* x0, const int* t, const f
 hipError_t launch_q_sample_src(hipStream_t s, const BatchSrc& b, const int* t, const float* sqrt_ac, const float* sqrt_1m, const float* noise_in,
                                int64_t rows, int cols, int cd, uint64_t seed, uint32_t row_offset, float* x_t, float* noise_out, int* t_out, int T,
                                float* cond_out, float* x0_out, int ldxt = 0, const ZeroList* zl = nullptr, int kind = OSD_PRED_EPSILON);
+// q_sample of the likelihood bound's (timestep, patient) pairs (k_elem.hip: k_q_sample_pairs).  Row r of the launch is pair
+// pair0 + r of a [S][n_pat] grid: patient i = pair % n_pat, timestep t_row[r] (t_row non-null) or t_list[pair / n_pat].  x0 / cond rows
+// are gathered from patient i (cond_out null: no condition rows written); noise_in, if given, points at row 0 of the launch.
+struct PairRows { int64_t pair0, n_pat; const int* t_row; const int* t_list; };
+hipError_t launch_q_sample_pairs(hipStream_t s, const float* x0, const float* cond, int cd, const PairRows& pr, const float* sqrt_ac,
+                                 const float* sqrt_1m, const float* noise_in, int64_t rows, int cols, uint64_t seed, uint32_t row_offset, float* x_t,
+                                 int ldxt, float* target_out, int* t_out, float* cond_out, const ZeroList* zl, int kind);
 // classifier-free guidance on the last hidden activation: h[r] = h[m + r] + w * (h[r] - h[m + r]) for r < m, in place (h: [2 m][cols])
 hipError_t launch_guide_combine(hipStream_t s, float* h, int64_t m, int cols, float w);
 // condition dropout of a caller-supplied batch: out[r] = row r keeps its condition (rng.h: cond_kept) ? cond[r] : null_cond

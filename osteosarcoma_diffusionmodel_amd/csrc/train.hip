@@ -566,6 +566,9 @@ struct LossStep {
   bool from_src, cond_drop;            // the handle's one-shots (osd_train_batch_source, osd_train_condition_dropout), consumed by this call
   bool use_pw = false, use_me = false; const ConsPlan* cp = nullptr;
   bool squads_bwd = false;             // squad_backward()
+  // the likelihood bound's row mode (osd_row_sq_error / osd_bound_sweep): the rows are (timestep, patient) pairs gathered by q_sample,
+  // loss() takes the per-row epilogue and writes se_out [n]; loss_out is then the squads' poison word, not a loss
+  const PairRows* pairs = nullptr; float* se_out = nullptr;
   TrainWs w;
 
   // everything that is accumulated atomically must start at zero: zeroed by the q_sample kernel's own grid
@@ -590,6 +593,17 @@ struct LossStep {
     const int* t_idx = tc.t_idx;
     // a non-eps target (osd_set_prediction) is formed by the same pass and lands in w.noise, injected noise or not
     if (h->pred_type != OSD_PRED_EPSILON) h->last_train_path |= OSD_TP_TARGET;
+    if (se_out) {
+      PairRows pr = *pairs;
+      pr.t_row = t_draw ? nullptr : t_idx;          // the caller's per-row timesteps (clamped), else the sweep's list
+      const bool gather = pr.t_row == nullptr;      // a sweep's rows name patients: their conditions land in the workspace
+      const bool own_target = noise && h->pred_type == OSD_PRED_EPSILON;
+      OSD_HIP(launch_q_sample_pairs(s, x0, cond, a.cond_dim, pr, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, seed, roff, w.x_t, w.xld,
+                                    own_target ? nullptr : w.noise, w.t_idx, gather ? w.cond_mix : nullptr, &zl, h->pred_type));
+      if (gather) cond = w.cond_mix;
+      tc.t_idx = w.t_idx;
+      return OSD_OK;
+    }
     if (from_src) {
       // rows gathered from the resident dataset, mixed up and noised in one pass; conditions land in the workspace
       OSD_HIP(launch_q_sample_src(s, h->batch_src, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, a.cond_dim, seed, roff, w.x_t,
@@ -641,6 +655,14 @@ struct LossStep {
     const int D = a.D;
     const double count = (double)n * (double)D;
     GemmArgs g = output_proj_args(h, w.f, n);
+    if (se_out) {
+      // the slot partials take the place of dL/d eps_hat, which a call without gradients never writes: ceil(D / 64) x n <= n x D floats
+      EpiRowSq::Args er{};
+      er.bias = h->params[a.pm.out_b]; er.target = noise && h->pred_type == OSD_PRED_EPSILON ? noise : w.noise; er.ldn = D;
+      er.part = w.d_out; er.ld = n;
+      OSD_HIP(launch_row_sq(s, g, er, loss_out, se_out));
+      return OSD_OK;
+    }
     EpiMse::Args ea{};
     ea.bias = h->params[a.pm.out_b]; ea.noise = noise && h->pred_type == OSD_PRED_EPSILON ? noise : w.noise; ea.ldn = D;
     ea.dout = grads ? w.d_out : nullptr; ea.ldd = D; ea.pred = cp ? w.pred : nullptr; ea.ldp = D; ea.loss = loss_out;
@@ -682,7 +704,7 @@ struct LossStep {
   int run(const int32_t* t_index) {
     use_pw = h->cons.n_pathways > 0 && h->w_pathway != 0.0;
     use_me = h->cons.n_a > 0 && h->w_mutexpr != 0.0;
-    cp = (use_pw || use_me) ? &h->cons : nullptr;
+    cp = (use_pw || use_me) && !se_out ? &h->cons : nullptr;      // the row mode scores the raw output alone
     if (cp && n < 2) { set_error("the constraint losses need at least 2 rows"); return OSD_EINVAL; }
     if (!h->parts_dev) OSD_HIP(hipMalloc((void**)&h->parts_dev, 64));
     OSD_TRY(ensure_train_ws(h, s, n, cp, &w));
@@ -736,6 +758,86 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
   OSD_TRY(tc.enter());
   LossStep step{tc, h, h->arch, tc.s, n, x0, cond, noise, masks, seed, (uint32_t)row_offset, loss_out, grads, loss_scale, events, from_src, cond_drop};
   return step.run(t_index);
+}
+
+// What osd_row_sq_error and osd_bound_sweep check alike, in order: null handle / tensors, rows, row offset, armed one-shots, precision;
+// each then checks its own arguments, and last that the handle is ready.
+static int bound_checks(osd_handle* h, const float* x0, const float* cond, int64_t n, int64_t row_offset, const float* se_out) {
+  if (!h) { set_error("null handle"); return OSD_EINVAL; }
+  if (!x0 || !cond || !se_out) { set_error("null tensor"); return OSD_EINVAL; }
+  if (n < 1) { set_error("need at least one row, got %lld", (long long)n); return OSD_EINVAL; }
+  OSD_TRY(check_rows(n));
+  OSD_TRY(check_row_offset(row_offset, n));
+  if (h->have_batch_src || h->have_cond_drop) {
+    set_error("a batch source or condition dropout is armed for the next training call; the likelihood calls do not consume it");
+    return OSD_ESTATE;
+  }
+  if (h->precision == 1) { set_error("the per-row squared error runs on the fp32 kernels only (precision 0)"); return OSD_EUNSUPPORTED; }
+  return OSD_OK;
+}
+
+// One launch group of the row mode: n rows, pairs pr.pair0 .. pr.pair0 + n of the grid
+static int bound_group(osd_handle* h, hipStream_t s, const float* x0, const float* cond, int64_t n, const PairRows& pr, const int32_t* t_index,
+                       const float* noise, uint64_t seed, uint32_t roff, float* se_out) {
+  if (!h->parts_dev) OSD_HIP(hipMalloc((void**)&h->parts_dev, 64));
+  TrainCall tc{h, n, 0};
+  tc.s = s;
+  LossStep step{tc, h, h->arch, s, n, x0, cond, noise, nullptr, seed, roff, h->parts_dev + 8, nullptr, 1.0, nullptr, false, false};
+  step.pairs = &pr; step.se_out = se_out;
+  return step.run(t_index);
+}
+
+int osd_row_sq_error(osd_handle* h, const float* x0, const float* cond, int64_t n, const int32_t* t_index, const float* noise_in, uint64_t seed,
+                     int64_t row_offset, float* se_out) {
+  OSD_TRY(bound_checks(h, x0, cond, n, row_offset, se_out));
+  if (!t_index) { set_error("t_index is null"); return OSD_EINVAL; }
+  OSD_TRY(check_ready(h));
+  TrainCall tc{h, n, 0};
+  OSD_TRY(tc.enter());
+  h->last_train_path = 0;
+  // groups of at most bound_rows rows, as the sweep: row r of a group is patient p0 + r
+  const int D = h->arch.D, cd = h->arch.cond_dim;
+  for (int64_t p0 = 0; p0 < n; p0 += h->bound_rows) {
+    const int64_t rows = std::min(h->bound_rows, n - p0);
+    const PairRows pr{p0, n, nullptr, nullptr};
+    OSD_TRY(bound_group(h, tc.s, x0, cond + p0 * cd, rows, pr, t_index + p0, noise_in ? noise_in + p0 * D : nullptr, seed, (uint32_t)row_offset,
+                        se_out + p0));
+  }
+  return OSD_OK;
+}
+
+int osd_bound_sweep(osd_handle* h, const float* x0, const float* cond, int64_t n, const int32_t* timesteps_host, int S, const float* noise_in,
+                    uint64_t seed, int64_t row_offset, float* se_out) {
+  OSD_TRY(bound_checks(h, x0, cond, n, row_offset, se_out));
+  if (S < 1 || !timesteps_host) { set_error("need at least one timestep, got %d", S); return OSD_EINVAL; }
+  for (int i = 0; i < S; ++i)
+    if (timesteps_host[i] < 0 || timesteps_host[i] >= h->arch.T) {
+      set_error("timesteps[%d] = %d is outside [0, %d)", i, (int)timesteps_host[i], h->arch.T);
+      return OSD_EINVAL;
+    }
+  OSD_TRY(check_ready(h));
+  TrainCall tc{h, n, 0};
+  OSD_TRY(tc.enter());
+  hipStream_t s = tc.s;
+  h->last_train_path = 0;
+  OSD_HIP(hipStreamSynchronize(s));          // an earlier sweep may still read the list
+  if (h->bound_ts_cap < S) {
+    if (h->bound_ts) { OSD_HIP(hipFree(h->bound_ts)); h->bound_ts = nullptr; h->bound_ts_cap = 0; }
+    const int64_t cap = ((int64_t)S + 1023) / 1024 * 1024;
+    OSD_TRY(device_alloc((void**)&h->bound_ts, (size_t)cap * 4));
+    h->bound_ts_cap = cap;
+  }
+  OSD_HIP(hipMemcpy(h->bound_ts, timesteps_host, (size_t)S * 4, hipMemcpyHostToDevice));
+  // groups of at most bound_rows (timestep, patient) pairs, in pair order: the workspace is bounded whatever n x S is, and a group may
+  // end in the middle of a timestep's patients
+  const int64_t total = n * (int64_t)S, cap = h->bound_rows;
+  const int D = h->arch.D;
+  for (int64_t p0 = 0; p0 < total; p0 += cap) {
+    const int64_t rows = std::min(cap, total - p0);
+    const PairRows pr{p0, n, nullptr, h->bound_ts};
+    OSD_TRY(bound_group(h, s, x0, cond, rows, pr, nullptr, noise_in ? noise_in + p0 * D : nullptr, seed, (uint32_t)row_offset, se_out + p0));
+  }
+  return OSD_OK;
 }
 
 int osd_train_batch_source(osd_handle* h, const float* data, int64_t ld_data, const float* cond, int64_t ld_cond, const int64_t* idx_a,

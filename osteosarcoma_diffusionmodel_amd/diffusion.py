@@ -245,6 +245,7 @@ ENGINE_OPTIONS = (
     ("chain_spin_budget", "chain_spin_budget", _if_set),
     ("chain_wall_budget_ms", "chain_wall_budget_ms", _if_set),
     ("input_splitk", "input_splitk", _if_set),
+    ("bound_rows", "bound_rows", _if_set),
 )
 
 
@@ -310,6 +311,9 @@ class BiologyAwareDiffusionModel(nn.Module):
         # SyntheticPatientGenerator switches None to auto: its per-scenario batches are the reference's default workload
         self.input_splitk: Optional[int] = None
         self.last_sampler: Optional[str] = None           # engine the most recent sample() ran on
+        # rows per launch group of the likelihood sweep (variational_bound / row_sq_error): None = the library's 32 768.  It caps the
+        # training workspace the sweep runs in
+        self.bound_rows: Optional[int] = None
         # arithmetic of the eval-mode forward / p_sample / sample GEMMs: None / "fp32" = v_mfma_f32_32x32x2_f32, the reference's F.linear in
         # fp32 (models/diffusion.py:198-256; the default); "bf16x3" = every fp32 operand as three bf16 planes (exact) and six bf16 MFMAs
         # per product with fp32 accumulation (csrc/gemm_bf3.h): fp32 accuracy -- the same stated tolerances -- at the bf16 matrix rate.
@@ -533,6 +537,103 @@ class BiologyAwareDiffusionModel(nn.Module):
         noise = self._prep(noise, self.data_dim, "noise")
         L.check(L.lib().osd_q_sample(eng.handle, L.ptr(x_0), L.ptr(t32), L.ptr(noise), n, 0, 0, L.ptr(x_t), None))
         return x_t, noise
+
+    # -- the per-patient likelihood bound (likelihood.py) ----------------------------
+    def _bound_inputs(self, x_0, conditions, what: str):
+        if self.training:
+            raise ValueError(f"{what} is eval mode only (model.eval()): the bound is a functional of the deterministic network")
+        if self.precision == "bf16x3":
+            raise ValueError(f"{what} runs on the fp32 kernels: precision='bf16x3' is not accepted")
+        x_0 = self._prep(x_0, self.data_dim, "x_0")
+        conditions = self._prep(conditions, self.condition_dim, "conditions")
+        if conditions.shape[0] != x_0.shape[0]:
+            raise RuntimeError(f"conditions has {conditions.shape[0]} rows but x_0 has {x_0.shape[0]}")
+        if x_0.shape[0] < 1:
+            raise RuntimeError("x_0 has no rows")
+        return x_0, conditions
+
+    @torch.no_grad()
+    def row_sq_error(self, x_0, conditions, t, *, noise=None, seed: Optional[int] = None, row_offset: int = 0):
+        """se [n] (fp32): the squared error sum_d (out - target)^2 of the network's raw output at q_sample(x_0, t) against the training
+        target of ``prediction_type``, per row, in eval mode.  ``t``: one timestep index per row.  ``noise`` [n, D] is injected, else
+        the draws are generated and keyed by (seed, row_offset + row, t) alone.  Deterministic: the same call returns the same bits."""
+        x_0, conditions = self._bound_inputs(x_0, conditions, "row_sq_error")
+        eng = self._engine()
+        n = x_0.shape[0]
+        t32 = self._t32(t, n, x_0.device)
+        nz = None
+        if noise is not None:
+            nz = self._prep(noise, self.data_dim, "noise")
+            if nz.shape[0] != n:
+                raise RuntimeError(f"noise has {nz.shape[0]} rows but x_0 has {n}")
+        seed = (0 if nz is not None else _draw_seed()) if seed is None else seed
+        se = torch.empty(n, device=x_0.device, dtype=torch.float32)
+        L.check(L.lib().osd_row_sq_error(eng.handle, L.ptr(x_0), L.ptr(conditions), n, L.ptr(t32), L.ptr(nz), seed, int(row_offset), L.ptr(se)))
+        eng.serial += 1           # the training workspace now belongs to this call
+        return se
+
+    def _bound_sweep(self, x_0, conditions, ts, noise, seed, row_offset):
+        """se [S][n] (fp32) of osd_bound_sweep over the host int32 array ``ts``."""
+        eng = self._engine()
+        n, S = x_0.shape[0], int(ts.size)
+        nz = None
+        if noise is not None:
+            if noise.device != x_0.device:
+                raise RuntimeError(f"noise is on {noise.device} but the model is on {x_0.device}")
+            nz = noise.to(torch.float32).contiguous()
+            if tuple(nz.shape) != (S, n, self.data_dim):
+                raise RuntimeError(f"noise: expected shape [{S}, {n}, {self.data_dim}], got {tuple(nz.shape)}")
+        seed = (0 if nz is not None else _draw_seed()) if seed is None else seed
+        se = torch.empty(S, n, device=x_0.device, dtype=torch.float32)
+        ts32 = np.ascontiguousarray(ts, dtype=np.int32)
+        L.check(L.lib().osd_bound_sweep(eng.handle, L.ptr(x_0), L.ptr(conditions), n, ts32.ctypes.data_as(C.POINTER(C.c_int32)), S, L.ptr(nz),
+                                        seed, int(row_offset), L.ptr(se)))
+        eng.serial += 1
+        return se
+
+    @torch.no_grad()
+    def variational_bound(self, x_0, conditions, *, num_timesteps: Optional[int] = None, timesteps=None, noise=None,
+                          seed: Optional[int] = None, row_offset: int = 0, decoder_variance: Optional[float] = None):
+        """The DDPM's variational upper bound on -log p(x_0 | c) per patient (Ho et al. 2020, eq. 5; likelihood.py states every term).
+
+        Returns a dict: ``nll`` [n] in nats and ``bpd`` [n] = nll / (D ln 2), float64 on the device; ``prior`` [n] (L_T, float64);
+        ``terms`` [S][n] (float64: row 0 the decoder term L_0, the others the weighted L_t, nll = prior + terms.sum(0));
+        ``sq_error`` [S][n], fp32, the raw per-row squared errors of the sweep; ``timesteps`` (int64, ascending, 0 first).
+
+        The default sweeps all ``num_steps`` timesteps: the bound with one draw per term.  ``num_timesteps=S`` takes t = 0 plus
+        S - 1 timesteps strided over 1..T-1 and weights their sum by (T - 1)/(S - 1); ``timesteps`` names the set (it must contain 0
+        and may not repeat).  ``noise`` [S, n, D] is injected; otherwise the draw of patient ``row_offset + i`` at timestep t depends
+        on (seed, that id, t) alone, so a cohort scored in shards, or with another subset containing t, sees the same draw.
+        ``decoder_variance``: the variance of the Gaussian decoder of the t = 0 term, by default ``betas[0]`` -- a convention.
+
+        The same functional for every ``prediction_type``, ``loss_type`` and weighting, so checkpoints trained with different
+        objectives compare on it.  Mutations are binary, so this continuous density is a RELATIVE score between patients and
+        between models, not a calibrated probability.  Eval mode, fp32 kernels (``precision='bf16x3'`` raises ValueError)."""
+        from . import likelihood as LK
+        from . import objective as OB
+        ptype = OB.check_prediction_type(self.prediction_type)
+        ts = LK.select_timesteps(self.num_steps, num_timesteps, timesteps)        # ValueError for a bad set, before any device work
+        x_0, conditions = self._bound_inputs(x_0, conditions, "variational_bound")
+        D, dev = self.data_dim, x_0.device
+        w, c0, _ = LK.term_weights(ts, self.betas, self.alphas_cumprod, ptype, D, decoder_variance)      # ValueError for a bad variance
+        se = self._bound_sweep(x_0, conditions, ts, noise, seed, row_offset)
+        terms = torch.as_tensor(w, dtype=torch.float64, device=dev)[:, None] * se.double()
+        terms[0] += c0
+        abar = float(self.alphas_cumprod[-1].double())
+        prior = 0.5 * (abar * x_0.double().pow(2).sum(1) - D * abar - D * float(np.log1p(-abar)))
+        nll = prior + terms.sum(0)
+        return {"nll": nll, "bpd": nll / (D * float(np.log(2.0))), "prior": prior, "terms": terms, "sq_error": se,
+                "timesteps": torch.as_tensor(ts.astype(np.int64), device=dev)}
+
+    @torch.no_grad()
+    def loss_profile(self, x_0, conditions, num_timesteps: int = 50, seed: Optional[int] = None):
+        """(timesteps [S] int64, profile [S] float64): the cohort mean of se / D per timestep -- the loss curve of the configured
+        target over t -- from the same sweep as ``variational_bound``."""
+        from . import likelihood as LK
+        ts = LK.select_timesteps(self.num_steps, num_timesteps, None)
+        x_0, conditions = self._bound_inputs(x_0, conditions, "loss_profile")
+        se = self._bound_sweep(x_0, conditions, ts, None, seed, 0)
+        return torch.as_tensor(ts.astype(np.int64), device=x_0.device), se.double().mean(1) / self.data_dim
 
     # -- training forward (models/diffusion.py:344-380) ------------------------------------------
     def forward(self, x_0, conditions, return_loss=True, *, t=None, noise=None, dropout_masks=None,

@@ -589,6 +589,17 @@ class EarlyStopping:
             self.counter = 0
 
 
+VALIDATION_METRICS = ("loss", "bound")
+
+
+def validation_metric_of(training_config: dict) -> str:
+    """``training.validation_metric``: "loss" (the default) or "bound"; anything else raises ValueError."""
+    v = training_config.get("validation_metric", "loss")
+    if v not in VALIDATION_METRICS:
+        raise ValueError(f"training.validation_metric must be one of {VALIDATION_METRICS}, got {v!r}")
+    return v
+
+
 class Trainer:
     """Training pipeline (utils/train.py:151-339) on the fused HIP path.
 
@@ -615,6 +626,15 @@ class Trainer:
         ema_decay = 0.0 if ema_decay is None else float(ema_decay)
         if ema_decay != 0.0 and not 0.0 < ema_decay < 1.0:
             raise ValueError(f"training.ema_decay={ema_decay} outside (0, 1) (absent or 0 switches the average off)")
+        # what validate() returns: "loss" (the default: the reference's noise-driven validation loss, launch for launch) or "bound", the
+        # mean bits per feature of the variational bound over the validation rows (likelihood.py) on training.validation_timesteps
+        # strided timesteps -- a deterministic functional of the weights, comparable across objectives
+        self.validation_metric = validation_metric_of(tc)
+        self.validation_timesteps = int(tc.get("validation_timesteps", 32))
+        if self.validation_timesteps < 2:
+            raise ValueError(f"training.validation_timesteps={self.validation_timesteps}: at least 2 (t = 0 and one more)")
+        if self.validation_metric == "bound" and hasattr(model, "vae"):
+            raise ValueError("training.validation_metric 'bound' scores the diffusion model and is not accepted for a cVAE model")
         self.model = model.to(device)
         self.train_loader, self.val_loader = train_loader, val_loader
         self.config, self.device = config, device
@@ -854,7 +874,35 @@ class Trainer:
         return self._validate()
 
     @torch.no_grad()
+    def _validate_bound(self):
+        """Mean bpd of the validation rows.  The k-th row of the pass is patient k of the draws (its index in the split under the
+        usual unshuffled validation loader) and the seed is training.random_seed, so the same weights give the same float, from
+        the resident split and from the loader alike: same batches, same per-row values, summed in float64 in the same order."""
+        self.model.eval()
+        seed = int(self.config["training"].get("random_seed", 0))
+        total = torch.zeros((), device=self.device, dtype=torch.float64)
+        rows = 0
+        _, res = self._resident_splits()
+        if res is not None:
+            data, cond, _ = res.base
+            batches = ((data[idx], cond[idx]) for idx in res.epoch_indices())
+        else:
+            batches = ((b["data"].to(self.device), b["conditions"].to(self.device)) for b in self.val_loader)
+        for x0, c in batches:
+            out = self.model.variational_bound(x0, c, num_timesteps=self.validation_timesteps, seed=seed, row_offset=rows)
+            total += out["bpd"].sum()
+            rows += x0.shape[0]
+        avg = (total / max(rows, 1)).reshape(1)
+        if self.dist:
+            avg = avg.to(torch.float32)
+            torch.distributed.all_reduce(avg)
+            avg /= self.world
+        return float(avg.item())
+
+    @torch.no_grad()
     def _validate(self):
+        if self.validation_metric == "bound":
+            return self._validate_bound()
         self.model.eval()
         total = torch.zeros(1, device=self.device)
         _, res = self._resident_splits()

@@ -413,6 +413,31 @@ class BiologicalValidator:
         summary = self._agree(privacy_summary(rows))
         return (summary, rows) if return_rows else summary
 
+    # -- privacy: membership inference on the per-record likelihood bound ---------------------
+    def membership_audit(self, model, train, holdout, *, num_timesteps: int = 32, seed: int = 0) -> Dict[str, float]:
+        """The loss-threshold membership-inference attack on a diffusion model: ``train`` and ``holdout`` are (data, conditions)
+        pairs, both cohorts are scored with ``model.variational_bound`` (bits per feature, ``num_timesteps`` strided timesteps, the
+        same ``seed``; holdout ids follow the train ids) and a lower score means "member".  Returns ``auc`` (Mann-Whitney by
+        ranks, ties count half, on the host), ``tpr_at_1pct_fpr``, ``advantage`` (max over thresholds of TPR - FPR),
+        ``mean_bpd_train`` and ``mean_bpd_holdout``.  0.5 / 0 / 0 is what a model that memorised nothing gives up to sampling
+        noise."""
+        from . import likelihood as LK
+        scores = []
+        offset = 0
+        for name, cohort in (("train", train), ("holdout", holdout)):
+            if not isinstance(cohort, (tuple, list)) or len(cohort) != 2:
+                raise ValueError(f"{name} must be a (data, conditions) pair")
+            data, cond = (_dev(v, self.device) for v in cohort)
+            if data.dim() != 2 or data.shape[0] == 0:
+                raise ValueError(f"{name} data must be [rows >= 1, features]")
+            out = model.variational_bound(data, cond, num_timesteps=num_timesteps, seed=seed, row_offset=offset)
+            offset += data.shape[0]
+            scores.append(out["bpd"].cpu().numpy())
+        res = LK.membership_metrics(scores[0], scores[1])
+        res["mean_bpd_train"] = float(scores[0].mean())
+        res["mean_bpd_holdout"] = float(scores[1].mean())
+        return res
+
     # -- utils/validation.py:27-121 ----------------------------------------------------------------
     def _column_sums(self, t: torch.Tensor) -> np.ndarray:
         return self.k.column_sums(t)
@@ -513,9 +538,11 @@ class BiologicalValidator:
 
     # -- utils/validation.py:300-383 ---------------------------------------------------------------
     def validate_all(self, real_mutations, real_expression, real_pathways, synth_mutations, synth_expression, synth_pathways,
-                     pathway_gene_matrix=None, privacy: bool = False, holdout=None) -> Dict[str, float]:
+                     pathway_gene_matrix=None, privacy: bool = False, holdout=None, model=None, membership=None) -> Dict[str, float]:
         """``privacy=True`` adds ``privacy_audit``'s keys, on the same combined matrices as the statistical tests; ``holdout`` is
-        then an optional (mutations, expression, pathways) triple of real patients the model never saw."""
+        then an optional (mutations, expression, pathways) triple of real patients the model never saw.  With a ``model`` (and
+        ``membership`` = ((train data, train conditions), (holdout data, holdout conditions)), the rows as the model was trained
+        on them) it also adds ``membership_audit``'s keys, each prefixed ``membership_``; without ``model`` nothing changes."""
         logger.info("=" * 50)
         logger.info("BIOLOGICAL VALIDATION")
         logger.info("=" * 50)
@@ -541,6 +568,10 @@ class BiologicalValidator:
                 else:
                     hold_combined = np.concatenate([_host(p) for p in parts_h], axis=1)
             all_results.update(self.privacy_audit(real_combined, synth_combined, hold_combined))
+            if model is not None:
+                if membership is None:
+                    raise ValueError("validate_all(model=...) needs membership=((train data, conditions), (holdout data, conditions))")
+                all_results.update({f"membership_{k}": v for k, v in self.membership_audit(model, membership[0], membership[1]).items()})
         logger.info("=" * 50)
         logger.info("VALIDATION SUMMARY")
         logger.info("=" * 50)
