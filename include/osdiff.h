@@ -524,6 +524,24 @@ int osd_val_rbf_sum(void *stream, int device, const float *A, int64_t n, const f
  * No candidate: idx -1, d2 +inf.  Inputs must be finite.  Synchronous, like the other osd_val_* calls. */
 int osd_val_nearest(void *stream, int device, const float *Q, int64_t nq, const float *R, int64_t nr, int D,
                     const int32_t *exclude, float *d2_out, int32_t *idx_out);
+/* osd_val_nearest for the k nearest rows, 1 <= k <= 16 (OSD_EINVAL otherwise), in one pass over the nq x nr rectangle.
+ * d2_out dev float [nq][k], idx_out dev int32 [nq][k]; workspace O(nq k + nr).  The k rows are the k smallest of the key
+ * (float_bits(max(|r|^2 + |q|^2 - 2 r.q, 0)) << 32) | index, so ties of the fp32 expanded form go to the smaller index and the
+ * result is a function of the inputs alone; their distances are recomputed directly as in osd_val_nearest (an exact copy is
+ * 0.0f) and the k pairs of a query are then RE-SORTED by (recomputed distance, index) ascending: d2_out[i][k-1] is the largest of
+ * the list, the row's k-th-neighbour radius.  Fewer than k candidates: the tail is idx -1, d2 +inf.  k = 1 returns
+ * osd_val_nearest's outputs bit for bit.  exclude, the finite inputs and the synchronous return as in osd_val_nearest. */
+int osd_val_knn(void *stream, int device, const float *Q, int64_t nq, const float *R, int64_t nr, int D, int k,
+                const int32_t *exclude, float *d2_out, int32_t *idx_out);
+/* Rows inside a radius, counted over the same rectangle without materialising it.  With d2(p, f) = max(|r_f|^2 + |q_p|^2 - 2 r_f.q_p, 0)
+ * in fp32 (the expanded form: its rounding error scales with the squared norms, so a row AT a radius may fall on either side):
+ *   in_ref_out[p]   = #{f : d2(p, f) <= r2_ref[f]},    r2_ref dev float [nr]: a radius per reference row
+ *   in_query_out[p] = #{f : d2(p, f) <= r2_query[p]},  r2_query dev float [nq]: a radius per query row
+ * both dev int32 [nq], overwritten.  Either radius / output pair may be NULL (a radius without its output, or neither pair, is
+ * OSD_EINVAL).  Radii are squared distances; +inf holds every row, a negative or NaN radius none.  Exact integer counts,
+ * independent of the order of execution.  Inputs must be finite.  Synchronous. */
+int osd_val_ball_counts(void *stream, int device, const float *Q, int64_t nq, const float *R, int64_t nr, int D,
+                        const float *r2_ref, const float *r2_query, int32_t *in_ref_out, int32_t *in_query_out);
 /* scipy.stats.ks_2samp as used at utils/validation.py:238-245, for features 0..nf-1 of real dev [n1][ld]
  * and synth dev [n2][ld]: exact integer extremes of cnt(real<=v)*n2 - cnt(synth<=v)*n1 over all sample
  * points v; the statistic is max(dmax, -dmin, 0) / (n1*n2) (p-values follow on the host). */

@@ -95,6 +95,8 @@ _SIGNATURES = {
     "osd_val_gram": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double)]),
     "osd_val_rbf_sum": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "osd_val_nearest": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int, _P, _P, _P]),
+    "osd_val_knn": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),
+    "osd_val_ball_counts": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int, _P, _P, _P, _P]),
     "osd_val_col_moments": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double),
                                       C.POINTER(C.c_double)]),
     "osd_val_rowz_sq": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double),

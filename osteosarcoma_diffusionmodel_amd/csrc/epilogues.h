@@ -1316,4 +1316,166 @@ struct EpiNearest {
   }
 };
 
+// ---- the k nearest reference rows of every query row (precision / recall / density / coverage) ----------
+// EpiNearest's operands, distance and key.  keys [P][k], all-ones on entry, ends as the k smallest keys of every query in ascending
+// order, whatever order the workgroups, waves and lanes run in:
+//   filter   slot k-1 is the query's current k-th best.  It only ever decreases (every write below is an atomicMin) and ends as the
+//            k-th smallest key, so a candidate whose key is not below ANY value read from it is not among the k smallest and is
+//            dropped.  A stale read can only cost an insertion that was not needed.
+//   insert   a lane carries its key through the slots s = 0 .. k-1:  old = atomicMin(slot[s], key);  key = max(old, key);  it stops
+//            when it carries NO_KEY (the slot was empty) and drops what it carries past slot k-1.
+//   why      each atomic leaves the multiset {slot values} + {carried keys} unchanged, and a carried key only moves forward.  Keys of
+//            one query are distinct (they hold the index).  Every inserted key visits slot 0, so slot 0 ends as the minimum m0 of
+//            them.  Every other key K leaves slot 0 exactly once: either it met a smaller value there and was carried on at once, or it
+//            was stored and the smaller key that later displaced it (one must: the slot ends as m0 < K) carried it on.  So slot 1
+//            sees every inserted key but m0 and ends as their minimum; by induction slot s ends as the s-th smallest.  The inserted
+//            keys are a superset of the k smallest of all candidates (the filter drops nothing that belongs to them).
+// The hot path per element is the distance and one integer minimum; per accumulator quad one signed compare of the quad's smallest
+// distance bits with the threshold (the upper half of the key last read from slot k-1; -1 for a row beyond P, so nothing passes; a
+// candidate that is out of range or excluded carries INT_MAX, above every float's bits and above the largest threshold).  A quad that
+// passes walks its four elements in a rolled loop -- sixteen copies of the insertion code per wave tile, not sixty-four -- and the
+// lane refreshes its threshold after every insertion, so of the candidates a lane holds it inserts the running k best only.
+// f_base: the launch's reference rows are rows f_base.. of the caller's (the host seeds the thresholds with a first launch over the
+// leading rows: 64 workgroups of an XCD start on one query tile together and would otherwise all see empty lists).
+struct EpiKnn {
+  static constexpr bool COUNTED_STORES = false;   // stores nothing but the atomics
+  static constexpr bool XBUF = false;
+  static constexpr unsigned long long NO_KEY = ~0ull;
+  static constexpr int MAX_K = 16;
+  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
+  struct Args { const float* sqr; const float* sqq; const int* exclude; unsigned long long* keys; int k; int f_base; };
+  static bool fast_ok(const Args& a, int F) { return F % 4 == 0 && al16(a.sqr); }
+  template <int NFB> using Pre = EpiNearest::Pre<NFB>;
+  template <int NFB, bool FAST>
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
+    return EpiNearest::prefetch<NFB, FAST>(EpiNearest::Args{a.sqr, a.sqq, a.exclude, a.keys}, fw, lane, F);
+  }
+  // the signed threshold a quad's smallest distance bits are compared with
+  static __device__ __forceinline__ int threshold(unsigned long long kth, bool prow) {
+    const unsigned hi = (unsigned)(kth >> 32);
+    return prow ? (int)(hi < 0x7ffffffeu ? hi : 0x7ffffffeu) : -1;
+  }
+  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
+                                               Sync&& sync = Sync()) {
+    const int l31 = lane & 31, h = lane >> 5;
+    const int k = a.k;
+#pragma unroll
+    for (int pb = 0; pb < NPB; ++pb) {
+      const int p = pw + 32 * pb + l31;
+      const bool prow = p < P;
+      const int pc = prow ? p : P - 1;
+      const float sq = a.sqq[pc];
+      const int ex = a.exclude ? a.exclude[pc] - a.f_base : -1;
+      unsigned long long* const slots = a.keys + (size_t)pc * k;
+      unsigned long long kth = __hip_atomic_load(slots + (k - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      int thr = threshold(kth, prow);
+#pragma unroll
+      for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int f = fw + 32 * fb + 8 * q + 4 * h;
+          const float4 sr = pre.sqr[fb][q];
+          const float srv[4] = {sr.x, sr.y, sr.z, sr.w};
+          int b[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float d2 = fmaxf(srv[r] + sq - 2.0f * acc[fb][pb][4 * q + r], 0.f);
+            b[r] = (f + r < F && f + r != ex) ? (int)__float_as_uint(d2) : 0x7fffffff;
+          }
+          const int m01 = b[0] < b[1] ? b[0] : b[1], m23 = b[2] < b[3] ? b[2] : b[3];
+          if ((m01 < m23 ? m01 : m23) <= thr) {
+#pragma unroll 1
+            for (int r = 0; r < 4; ++r) {
+              const int br = r == 0 ? b[0] : r == 1 ? b[1] : r == 2 ? b[2] : b[3];
+              if (br > thr) continue;
+              unsigned long long key = ((unsigned long long)(unsigned)br << 32) | (unsigned)(a.f_base + f + r);
+              if (key >= kth) continue;            // equal distance bits, larger index
+              for (int s = 0; s < k; ++s) {
+                const unsigned long long old = atomicMin(slots + s, key);
+                key = old > key ? old : key;
+                if (key == NO_KEY) break;
+              }
+              kth = __hip_atomic_load(slots + (k - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              thr = threshold(kth, prow);
+            }
+          }
+        }
+      sync.tick();
+    }
+  }
+};
+
+// ---- how many reference rows lie inside a per-row radius ---------------------------------------------
+// EpiNearest's operands and distance.  Per query p two counts over the reference rows f < F:
+//   in_ref[p]   = #{f : d2(p, f) <= r2_ref[f]}       the reference row's own radius
+//   in_query[p] = #{f : d2(p, f) <= r2_query[p]}     the query row's radius
+// `<=` on floats: a +inf radius holds every row, a negative or NaN one none.  A NULL radius array counts as -1 everywhere and its
+// output is not touched; r2_ref rides in registers from before the K loop beside the reference norms (-1 for f >= F).  A lane holds
+// one query and 16 * NFB reference rows; the two half-waves that share a query meet through lane^32 and one integer atomicAdd per
+// query, count and wave goes out, skipped when the count is zero.  Integer sums: the result does not depend on the order.
+struct EpiBallCount {
+  static constexpr bool COUNTED_STORES = false;   // stores nothing but the atomics
+  static constexpr bool XBUF = false;
+  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
+  struct Args { const float* sqr; const float* sqq; const float* r2_ref; const float* r2_query; int* in_ref; int* in_query; };
+  static bool fast_ok(const Args& a, int F) { return F % 4 == 0 && al16(a.sqr) && al16(a.r2_ref); }
+  template <int NFB> struct Pre { float4 sqr[NFB][4], r2[NFB][4]; };
+  template <int NFB, bool FAST>
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
+    Pre<NFB> r;
+    const int h = lane >> 5;
+#pragma unroll
+    for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int f = fw + 32 * fb + 8 * q + 4 * h;
+        r.sqr[fb][q] = ldq<FAST>(a.sqr, f, F);
+        float4 t = make_float4(-1.f, -1.f, -1.f, -1.f);
+        if (a.r2_ref) {                            // uniform
+          t = ldq<FAST>(a.r2_ref, f, F);
+          t.x = f < F ? t.x : -1.f; t.y = f + 1 < F ? t.y : -1.f; t.z = f + 2 < F ? t.z : -1.f; t.w = f + 3 < F ? t.w : -1.f;
+        }
+        r.r2[fb][q] = t;
+      }
+    return r;
+  }
+  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
+                                               Sync&& sync = Sync()) {
+    const int l31 = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int pb = 0; pb < NPB; ++pb) {
+      const int p = pw + 32 * pb + l31;
+      const int pc = p < P ? p : P - 1;
+      const float sq = a.sqq[pc];
+      const float rq = a.r2_query ? a.r2_query[pc] : -1.f;
+      int cr = 0, cq = 0;
+#pragma unroll
+      for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int f = fw + 32 * fb + 8 * q + 4 * h;
+          const float4 sr = pre.sqr[fb][q], rr = pre.r2[fb][q];
+          const float srv[4] = {sr.x, sr.y, sr.z, sr.w};
+          const float rrv[4] = {rr.x, rr.y, rr.z, rr.w};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float d2 = fmaxf(srv[r] + sq - 2.0f * acc[fb][pb][4 * q + r], 0.f);
+            const bool valid = FAST ? f < F : f + r < F;        // FAST: F % 4 == 0, a quad is inside or outside as a whole
+            cr += d2 <= rrv[r] ? 1 : 0;
+            cq += (valid && d2 <= rq) ? 1 : 0;
+          }
+        }
+      cr += __shfl_xor(cr, 32);
+      cq += __shfl_xor(cq, 32);
+      if (h == 0 && p < P) {
+        if (cr) atomicAdd(a.in_ref + p, cr);       // cr, cq stay 0 where the radius array is NULL
+        if (cq) atomicAdd(a.in_query + p, cq);
+      }
+      sync.tick();
+    }
+  }
+};
+
 }  // namespace osd

@@ -135,31 +135,6 @@ static hipError_t rbf_sum(hipStream_t s, const float* X, int64_t n, const float*
   return launch_gemm<TileBig, true, true, EpiRbfSum>(s, g, ea);
 }
 
-// The key array of EpiNearest after the Gram pass, one wavefront per query: the index out of the key, and the distance to
-// that row recomputed as sum_k (q_k - r_k)^2 -- differences in fp32, the sum in double.  The expanded form |r|^2 + |q|^2 - 2 r.q
-// the keys were ranked by cancels (its error is the size of a near copy's whole distance); this one returns an exact copy as 0.0f.
-__global__ void k_nearest_refine(const float* Q, int64_t nq, const float* R, int D, const unsigned long long* keys, float* d2_out,
-                                 int32_t* idx_out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t i = wave; i < nq; i += nw) {
-    const unsigned long long key = keys[i];
-    if (key == EpiNearest::NO_KEY) {               // uniform over the wave
-      if (lane == 0) { idx_out[i] = -1; d2_out[i] = INFINITY; }
-      continue;
-    }
-    const int64_t j = (int64_t)(key & 0xffffffffull);
-    const float* q = Q + i * D;
-    const float* r = R + j * D;
-    double s = 0.0;
-    for (int c = lane; c < D; c += 64) { const float d = q[c] - r[c]; s += (double)d * (double)d; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) { idx_out[i] = (int32_t)j; d2_out[i] = (float)s; }
-  }
-}
-
 // keys[p] = min over the reference rows f != exclude[p] of (float_bits(d2(p, f)) << 32) | f; keys must hold all-ones on entry
 static hipError_t nearest_keys(hipStream_t s, const float* R, int64_t nr, const float* sqr, const float* Q, int64_t nq, const float* sqq, int D,
                                const int32_t* exclude, unsigned long long* keys) {
@@ -167,6 +142,77 @@ static hipError_t nearest_keys(hipStream_t s, const float* R, int64_t nr, const 
   g.A = R; g.lda = D; g.B0 = Q; g.ldb0 = D; g.K0 = D; g.F = (int)nr; g.P = (int)nq; g.K = D;
   EpiNearest::Args ea{sqr, sqq, exclude, keys};
   return launch_gemm<TileBig, true, true, EpiNearest>(s, g, ea);
+}
+
+// The key arrays of EpiNearest ([nq], k = 1) and EpiKnn ([nq][k]) after the Gram pass, one wavefront per (query, slot): the index out
+// of the key, and the distance to that row recomputed as sum_c (q_c - r_c)^2 -- differences in fp32, the sum in double.  The expanded
+// form |r|^2 + |q|^2 - 2 r.q the keys were ranked by cancels (its error is the size of a near copy's whole distance); this one returns
+// an exact copy as 0.0f.  An empty slot (all-ones: no candidate) gives idx -1, d2 +inf.
+__global__ void k_knn_refine(const float* Q, int64_t nq, const float* R, int D, int k, const unsigned long long* keys, float* d2_out,
+                             int32_t* idx_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t w = wave; w < nq * k; w += nw) {
+    const unsigned long long key = keys[w];
+    if (key == EpiKnn::NO_KEY) {                   // uniform over the wave
+      if (lane == 0) { idx_out[w] = -1; d2_out[w] = INFINITY; }
+      continue;
+    }
+    const int64_t j = (int64_t)(key & 0xffffffffull);
+    const float* q = Q + (w / k) * D;
+    const float* r = R + j * D;
+    double s = 0.0;
+    for (int c = lane; c < D; c += 64) { const float d = q[c] - r[c]; s += (double)d * (double)d; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) { idx_out[w] = (int32_t)j; d2_out[w] = (float)s; }
+  }
+}
+
+// One thread per query: its k (d2, idx) pairs into ascending (refined d2, idx) order, in place.  The Gram pass ranked by the expanded
+// form, whose rounding can order two nearly equidistant rows the other way round than their recomputed distances; the empty slots
+// (+inf, -1) are at the end already and stay there.
+__global__ void k_knn_sort(int64_t nq, int k, float* d2, int32_t* idx) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= nq) return;
+  float* d = d2 + i * k;
+  int32_t* x = idx + i * k;
+  for (int a = 1; a < k; ++a) {
+    const float da = d[a];
+    const int32_t xa = x[a];
+    if (xa < 0) break;
+    int b = a;
+    for (; b > 0 && (d[b - 1] > da || (d[b - 1] == da && x[b - 1] > xa)); --b) { d[b] = d[b - 1]; x[b] = x[b - 1]; }
+    d[b] = da; x[b] = xa;
+  }
+}
+
+// keys [nq][k] = the k smallest keys (float_bits(d2(p, f)) << 32) | f over the reference rows f != exclude[p], ascending; keys must
+// hold all-ones on entry.  One pass over the rectangle in two launches: the leading KNN_SEED reference rows first, so that the
+// workgroups of the second launch find thresholds to filter by (EpiKnn); each launch takes launch_gemm's path for its own extents.
+constexpr int64_t KNN_SEED = 512;
+static hipError_t knn_keys(hipStream_t s, const float* R, int64_t nr, const float* sqr, const float* Q, int64_t nq, const float* sqq, int D,
+                           int k, const int32_t* exclude, unsigned long long* keys) {
+  for (int64_t lo = 0; lo < nr;) {
+    const int64_t cnt = (lo == 0 && nr > KNN_SEED) ? KNN_SEED : nr - lo;
+    GemmArgs g{};
+    g.A = R + lo * D; g.lda = D; g.B0 = Q; g.ldb0 = D; g.K0 = D; g.F = (int)cnt; g.P = (int)nq; g.K = D;
+    EpiKnn::Args ea{sqr + lo, sqq, exclude, keys, k, (int)lo};
+    const hipError_t e = launch_gemm<TileBig, true, true, EpiKnn>(s, g, ea);
+    if (e != hipSuccess) return e;
+    lo += cnt;
+  }
+  return hipSuccess;
+}
+
+// in_ref[p] += #{f : d2(p, f) <= r2_ref[f]}, in_query[p] += #{f : d2(p, f) <= r2_query[p]}; either pair may be null
+static hipError_t ball_counts(hipStream_t s, const float* R, int64_t nr, const float* sqr, const float* Q, int64_t nq, const float* sqq, int D,
+                              const float* r2_ref, const float* r2_query, int32_t* in_ref, int32_t* in_query) {
+  GemmArgs g{};
+  g.A = R; g.lda = D; g.B0 = Q; g.ldb0 = D; g.K0 = D; g.F = (int)nr; g.P = (int)nq; g.K = D;
+  EpiBallCount::Args ea{sqr, sqq, r2_ref, r2_query, in_ref, in_query};
+  return launch_gemm<TileBig, true, true, EpiBallCount>(s, g, ea);
 }
 
 struct DevBuf {
@@ -254,8 +300,58 @@ int osd_val_nearest(void* stream, int device, const float* Q, int64_t nq, const 
   OSD_HIP(nearest_keys(s, R, nr, sqr, Q, nq, sqq, D, exclude, (unsigned long long*)keys.p));
   int blocks = (int)((nq + 3) / 4);                    // 4 wavefronts per workgroup, one query each
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_nearest_refine, blocks, 256, 0, s, Q, nq, R, D, (const unsigned long long*)keys.p, d2_out, idx_out);
+  hipLaunchKernelGGL(k_knn_refine, blocks, 256, 0, s, Q, nq, R, D, 1, (const unsigned long long*)keys.p, d2_out, idx_out);
   OSD_HIP(hipGetLastError());
+  OSD_HIP(hipStreamSynchronize(s));
+  return OSD_OK;
+}
+
+int osd_val_knn(void* stream, int device, const float* Q, int64_t nq, const float* R, int64_t nr, int D, int k, const int32_t* exclude,
+                float* d2_out, int32_t* idx_out) {
+  if (!Q || !R || !d2_out || !idx_out || nq <= 0 || nr <= 0 || D <= 0 || nq > INT_MAX / 2 || nr > INT_MAX / 2) { set_error("bad argument"); return OSD_EINVAL; }
+  if (k < 1 || k > EpiKnn::MAX_K) { set_error("k must lie in [1, %d]", EpiKnn::MAX_K); return OSD_EINVAL; }
+  OSD_HIP(hipSetDevice(device));
+  OSD_HIP(prepare_kernels());
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf sq, keys;                                     // O(nq k + nr): nothing here scales with nq * nr
+  OSD_HIP(sq.alloc((size_t)(nq + nr) * 4));
+  OSD_HIP(keys.alloc((size_t)nq * k * sizeof(unsigned long long)));
+  float* sqr = (float*)sq.p;
+  float* sqq = sqr + nr;
+  OSD_HIP(hipMemsetAsync(keys.p, 0xff, (size_t)nq * k * sizeof(unsigned long long), s));  // EpiKnn::NO_KEY
+  hipLaunchKernelGGL(k_rowsumsq, 1024, 256, 0, s, R, nr, D, sqr);
+  if (Q == R && nq == nr) sqq = sqr;
+  else hipLaunchKernelGGL(k_rowsumsq, 1024, 256, 0, s, Q, nq, D, sqq);
+  OSD_HIP(knn_keys(s, R, nr, sqr, Q, nq, sqq, D, k, exclude, (unsigned long long*)keys.p));
+  int64_t blocks = (nq * k + 3) / 4;                   // 4 wavefronts per workgroup, one (query, slot) each
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(k_knn_refine, (int)blocks, 256, 0, s, Q, nq, R, D, k, (const unsigned long long*)keys.p, d2_out, idx_out);
+  if (k > 1) hipLaunchKernelGGL(k_knn_sort, (int)((nq + 255) / 256), 256, 0, s, nq, k, d2_out, idx_out);
+  OSD_HIP(hipGetLastError());
+  OSD_HIP(hipStreamSynchronize(s));
+  return OSD_OK;
+}
+
+int osd_val_ball_counts(void* stream, int device, const float* Q, int64_t nq, const float* R, int64_t nr, int D, const float* r2_ref,
+                        const float* r2_query, int32_t* in_ref_out, int32_t* in_query_out) {
+  if (!Q || !R || nq <= 0 || nr <= 0 || D <= 0 || nq > INT_MAX / 2 || nr > INT_MAX / 2) { set_error("bad argument"); return OSD_EINVAL; }
+  if ((!r2_ref && !r2_query) || !r2_ref != !in_ref_out || !r2_query != !in_query_out) {
+    set_error("bad argument (a radius array and its output come together, and at least one pair is needed)");
+    return OSD_EINVAL;
+  }
+  OSD_HIP(hipSetDevice(device));
+  OSD_HIP(prepare_kernels());
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf sq;                                           // O(nq + nr)
+  OSD_HIP(sq.alloc((size_t)(nq + nr) * 4));
+  float* sqr = (float*)sq.p;
+  float* sqq = sqr + nr;
+  if (in_ref_out) OSD_HIP(hipMemsetAsync(in_ref_out, 0, (size_t)nq * sizeof(int32_t), s));
+  if (in_query_out) OSD_HIP(hipMemsetAsync(in_query_out, 0, (size_t)nq * sizeof(int32_t), s));
+  hipLaunchKernelGGL(k_rowsumsq, 1024, 256, 0, s, R, nr, D, sqr);
+  if (Q == R && nq == nr) sqq = sqr;
+  else hipLaunchKernelGGL(k_rowsumsq, 1024, 256, 0, s, Q, nq, D, sqq);
+  OSD_HIP(ball_counts(s, R, nr, sqr, Q, nq, sqq, D, r2_ref, r2_query, in_ref_out, in_query_out));
   OSD_HIP(hipStreamSynchronize(s));
   return OSD_OK;
 }

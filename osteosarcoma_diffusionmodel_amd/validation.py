@@ -148,6 +148,41 @@ class DeviceKernels:
                                         L.ptr(d2), L.ptr(idx)))
         return d2, idx
 
+    def knn(self, q: torch.Tensor, r: torch.Tensor, k: int, exclude: Optional[torch.Tensor] = None):
+        """(d2 float32 [nq, k], idx int32 [nq, k]) device tensors: the k nearest rows of r for each row of q in ascending order of
+        the recomputed distance, row ``exclude[i]`` skipped; (+inf, -1) where r has fewer than k candidates.  1 <= k <= 16."""
+        if q.shape[1] != r.shape[1]:
+            raise ValueError("q and r must have the same number of features")
+        nq = q.shape[0]
+        d2 = torch.empty((nq, max(int(k), 0)), dtype=torch.float32, device=q.device)
+        idx = torch.empty((nq, max(int(k), 0)), dtype=torch.int32, device=q.device)
+        if exclude is not None:
+            exclude = exclude.to(device=q.device, dtype=torch.int32).contiguous()
+            if exclude.shape != (nq,):
+                raise ValueError("exclude must hold one index per query row")
+        L.check(L.lib().osd_val_knn(self._stream(), self.index, L.ptr(q), nq, L.ptr(r), r.shape[0], q.shape[1], int(k), L.ptr(exclude),
+                                    L.ptr(d2), L.ptr(idx)))
+        return d2, idx
+
+    def ball_counts(self, q: torch.Tensor, r: torch.Tensor, r2_ref: Optional[torch.Tensor] = None,
+                    r2_query: Optional[torch.Tensor] = None):
+        """(in_ref, in_query) int32 [nq] device tensors, None where the radius is None: for each row of q the number of rows of r
+        within the r row's squared radius ``r2_ref[f]``, and within the q row's own squared radius ``r2_query[p]`` (``<=``)."""
+        if q.shape[1] != r.shape[1]:
+            raise ValueError("q and r must have the same number of features")
+        nq, nr = q.shape[0], r.shape[0]
+        outs = []
+        for name, rad, n in (("r2_ref", r2_ref, nr), ("r2_query", r2_query, nq)):
+            if rad is not None:
+                rad = rad.to(device=q.device, dtype=torch.float32).contiguous()
+                if rad.shape != (n,):
+                    raise ValueError(f"{name} must hold one squared radius per row ({n})")
+            outs.append((rad, None if rad is None else torch.empty(nq, dtype=torch.int32, device=q.device)))
+        (rr, in_ref), (rq, in_query) = outs
+        L.check(L.lib().osd_val_ball_counts(self._stream(), self.index, L.ptr(q), nq, L.ptr(r), nr, q.shape[1], L.ptr(rr), L.ptr(rq),
+                                            L.ptr(in_ref), L.ptr(in_query)))
+        return in_ref, in_query
+
     def ks_extremes(self, real: torch.Tensor, synth: torch.Tensor, nf: int):
         dmax, dmin = (C.c_int64 * nf)(), (C.c_int64 * nf)()
         L.check(L.lib().osd_val_ks_extremes(self._stream(), self.index, L.ptr(real), real.shape[0], L.ptr(synth), synth.shape[0],
@@ -297,6 +332,35 @@ def privacy_summary(rows: Dict[str, np.ndarray]) -> Dict[str, float]:
     return out
 
 
+def prdc_summary(rows: Dict[str, np.ndarray], k: int) -> Dict[str, float]:
+    """Precision and recall (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020) from the per-row counts of
+    ``BiologicalValidator.fidelity_diversity`` (int64 counts, float64 means).  With X the N real rows, Y the M synthetic rows and
+    r_k(.) a row's distance to its k-th nearest neighbour inside its own cohort, itself excluded, the four figures are means over
+
+      ``synth_in_real_balls`` [M]  #{i : d(y_j, x_i) <= r_k(x_i)}      precision = mean(count > 0);  density = sum / (k M)
+      ``real_in_synth_balls`` [N]  #{j : d(x_i, y_j) <= r_k(y_j)}      recall    = mean(count > 0)
+      ``real_ball_synth``     [N]  #{j : d(x_i, y_j) <= r_k(x_i)}      coverage  = mean(count > 0)
+
+    (precision and density read the same array).  Other keys of ``rows`` -- the radii -- are ignored."""
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    a = np.asarray(rows["synth_in_real_balls"], dtype=np.int64)
+    b = np.asarray(rows["real_in_synth_balls"], dtype=np.int64)
+    c = np.asarray(rows["real_ball_synth"], dtype=np.int64)
+    if a.size == 0 or b.size == 0:
+        raise ValueError("a precision / recall summary needs at least one row in each cohort")
+    if b.shape != c.shape:
+        raise ValueError("real_in_synth_balls and real_ball_synth must have one entry per real row")
+    return {
+        "prdc_precision": float(np.mean(a > 0)),
+        "prdc_recall": float(np.mean(b > 0)),
+        "prdc_density": float(a.sum(dtype=np.int64) / (float(k) * a.size)),
+        "prdc_coverage": float(np.mean(c > 0)),
+        "prdc_k": k,
+    }
+
+
 class BiologicalValidator:
     """utils/validation.py:18 -- device versions of the metrics named in the module docstring."""
 
@@ -310,6 +374,7 @@ class BiologicalValidator:
         if self.device.type != "cuda":
             raise RuntimeError("the validation kernels run on a ROCm device; there is no CPU fallback")
         self.k = DeviceKernels(self.device)
+        self.sharded = bool(sharded)
         self.comm = ShardComm(sharded)            # synthetic rows sharded over ranks when active
         self._one = ShardComm(False)              # the replicated real cohort never communicates
 
@@ -411,6 +476,47 @@ class BiologicalValidator:
             raise ValueError("the real cohorts must not be empty")
         rows = sharded_nearest_records(self.comm, self.k, tr, sy, ho)
         summary = self._agree(privacy_summary(rows))
+        return (summary, rows) if return_rows else summary
+
+    # -- diversity: precision / recall / density / coverage (no counterpart in the reference) ------
+    def fidelity_diversity(self, real, synthetic, k: int = 5, return_rows: bool = False):
+        """``prdc_precision``, ``prdc_recall``, ``prdc_density``, ``prdc_coverage`` and ``prdc_k`` of ``prdc_summary``: how much of
+        the synthetic cohort lies where real patients are (precision, density) and how much of the real cohort the synthetic one
+        reaches (recall, coverage) -- a collapsed sampler keeps the first pair and loses the second.  Four passes over distance
+        rectangles that are never stored: the k-th-neighbour radius of every real and of every synthetic row inside its own cohort
+        (``DeviceKernels.knn``, the row itself excluded), then the two count passes (``DeviceKernels.ball_counts``).  Distances
+        are plain Euclidean over the columns as given -- callers scale their inputs.  The counts compare the fp32 expanded form
+        with the recomputed radii, so a row exactly AT a radius may count either way.  1 <= k <= 16 and
+        both cohorts need more than k rows.  ``return_rows=True`` also returns the per-row arrays (the three of ``prdc_summary``
+        plus ``real_radius`` and ``synth_radius``, float64 distances).  Not available on a ``sharded=True`` validator."""
+        if self.sharded:
+            raise NotImplementedError("fidelity_diversity is not implemented for a sharded validator: the synthetic cohort's own "
+                                      "k-th-neighbour radii need every synthetic row against every other (a ring exchange)")
+        k = int(k)
+        if not 1 <= k <= 16:
+            raise ValueError("k must lie in [1, 16]")
+        shapes = [tuple(a.shape) if hasattr(a, "shape") else np.shape(a) for a in (real, synthetic)]      # before anything moves
+        for name, shp in zip(("real", "synthetic"), shapes):
+            if len(shp) != 2 or shp[1] != shapes[0][-1]:
+                raise ValueError(f"{name} must be [rows, features] and the cohorts must have the same features, got {shp}")
+            if shp[0] <= k:
+                raise ValueError(f"{name} has {shp[0]} rows: a k-th-neighbour radius needs more than k = {k}")
+        x, y = _dev(real, self.device), _dev(synthetic, self.device)
+        for name, t in (("real", x), ("synthetic", y)):
+            if not bool(torch.isfinite(t).all().item()):
+                raise ValueError(f"{name} holds non-finite values")
+        r2 = []
+        for t in (x, y):
+            own = torch.arange(t.shape[0], dtype=torch.int32, device=t.device)
+            r2.append(self.k.knn(t, t, k, own)[0][:, k - 1].contiguous())        # the recomputed d2 of the k-th neighbour
+        in_real, _ = self.k.ball_counts(y, x, r2_ref=r2[0])
+        in_synth, cover = self.k.ball_counts(x, y, r2_ref=r2[1], r2_query=r2[0])
+        rows = {"synth_in_real_balls": in_real.cpu().numpy().astype(np.int64),
+                "real_in_synth_balls": in_synth.cpu().numpy().astype(np.int64),
+                "real_ball_synth": cover.cpu().numpy().astype(np.int64),
+                "real_radius": np.sqrt(r2[0].cpu().numpy().astype(np.float64)),
+                "synth_radius": np.sqrt(r2[1].cpu().numpy().astype(np.float64))}
+        summary = prdc_summary(rows, k)
         return (summary, rows) if return_rows else summary
 
     # -- privacy: membership inference on the per-record likelihood bound (DESIGN.md section 3.18) ---------------------
@@ -538,8 +644,10 @@ class BiologicalValidator:
 
     # -- utils/validation.py:300-383 ---------------------------------------------------------------
     def validate_all(self, real_mutations, real_expression, real_pathways, synth_mutations, synth_expression, synth_pathways,
-                     pathway_gene_matrix=None, privacy: bool = False, holdout=None, model=None, membership=None) -> Dict[str, float]:
-        """``privacy=True`` adds ``privacy_audit``'s keys, on the same combined matrices as the statistical tests; ``holdout`` is
+                     pathway_gene_matrix=None, privacy: bool = False, holdout=None, model=None, membership=None,
+                     prdc: bool = False, prdc_k: int = 5) -> Dict[str, float]:
+        """``prdc=True`` adds ``fidelity_diversity``'s keys (``prdc_k`` neighbours), on the same combined matrices as the statistical
+        tests.  ``privacy=True`` adds ``privacy_audit``'s keys, on the same combined matrices as the statistical tests; ``holdout`` is
         then an optional (mutations, expression, pathways) triple of real patients the model never saw.  With a ``model`` (and
         ``membership`` = ((train data, train conditions), (holdout data, holdout conditions)), the rows as the model was trained
         on them) it also adds ``membership_audit``'s keys, each prefixed ``membership_``; without ``model`` nothing changes."""
@@ -572,6 +680,8 @@ class BiologicalValidator:
                 if membership is None:
                     raise ValueError("validate_all(model=...) needs membership=((train data, conditions), (holdout data, conditions))")
                 all_results.update({f"membership_{k}": v for k, v in self.membership_audit(model, membership[0], membership[1]).items()})
+        if prdc:
+            all_results.update(self.fidelity_diversity(real_combined, synth_combined, k=prdc_k))
         logger.info("=" * 50)
         logger.info("VALIDATION SUMMARY")
         logger.info("=" * 50)
