@@ -572,6 +572,30 @@ int osd_val_pearson_sums(void *stream, int device, const float *a, int lda, cons
                          int64_t rows, double *out5_host);
 int osd_val_pearson(void *stream, int device, const float *a, int lda, const float *b, int ldb,
                     int64_t rows, double *out);
+/* Centred Gram matrix of a whole cohort (csrc/corr.hip):
+ *   G[i][j] = sum_r (X[r][i] - c[i]) * (X[r][j] - c[j]),   i, j < D.
+ * X dev float [rows][ld], the first D columns used (any rows >= 1, D >= 1, ld >= D; an X whose base or ld does not suit 16-byte
+ * staging is first copied to a padded device buffer of rows * roundup(D, 4) floats); center_host: host float [D]; G_dev: DEVICE
+ * double [D][D], overwritten, exactly symmetric.  Differences and products are fp32 (the fp32 MFMA), accumulated in fp32 over runs of
+ * at most OSD_COV_SLAB_ROWS rows; every run is folded into double sums owned by one work item (128 x 128 tile on or above the
+ * diagonal x row slice), the slices of a tile are summed in a fixed order: no floating-point atomics, the same inputs give the
+ * same bits.  The number of row slices follows the tile count and the CU count, never rows: workspace O(slices * D^2).
+ * Inputs must be finite.  D <= 32768.  Synchronous. */
+#define OSD_COV_SLAB_ROWS 256
+int osd_val_centered_gram(void *stream, int device, const float *X, int64_t rows, int ld, int D,
+                          const float *center_host, double *G_dev);
+/* Two Gram matrices of osd_val_centered_gram (dev double [D][D], real and synthetic cohort) compared as correlation matrices
+ * without storing either: r = G[i][j] / sqrt(G[i][i] * G[j][j]) in double, delta = r_synth - r_real, over the pairs i < j of
+ * columns that are not constant (G[i][i] <= 0 in either matrix).  bounds_host: host int32 [n_blocks + 1], 0 = b_0 < b_1 < ... <
+ * b_n_blocks = D (OSD_EINVAL otherwise) -- column blocks.  out_host: host double [1 + OSD_CORR_STATS * n_blocks (n_blocks + 1) / 2]:
+ * out[0] the number of constant columns, then for every block pair a <= b in row-major order (0,0), (0,1), ..., (1,1), ... over the
+ * pairs with i in block a and j in block b:
+ *   [0] pairs  [1] sum |delta|  [2] sum delta^2  [3] max |delta|  [4] strong pairs: |r_real| >= strong
+ *   [5] strong pairs with sign(r_synth) == sign(r_real)  [6] sum |delta| over the strong pairs.
+ * Counts and the maximum are exact; the sums are double atomics (last-bit freedom).  Synchronous. */
+#define OSD_CORR_STATS 7
+int osd_val_corr_compare(void *stream, int device, const double *G_real, const double *G_synth, int D,
+                         const int32_t *bounds_host, int n_blocks, double strong, double *out_host);
 
 /* ---- biological constraint losses (north_star) ------------------------------
  * The reference declares them at models/cvae.py:262-302 as stubs that return 0.0 (and the diffusion

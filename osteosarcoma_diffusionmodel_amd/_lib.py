@@ -17,6 +17,7 @@ OSD_LOSS_L2, OSD_LOSS_L1, OSD_LOSS_HUBER = 0, 1, 2
 OSD_TP_LOSS_EPI = 1 << 11
 OSD_TP_TARGET = 1 << 12
 OSD_PRED_EPSILON, OSD_PRED_V, OSD_PRED_SAMPLE = 0, 1, 2
+OSD_CORR_STATS = 7
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libosdiff.so"
 
@@ -103,6 +104,8 @@ _SIGNATURES = {
                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "osd_val_pearson_sums": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int64, C.POINTER(C.c_double)]),
     "osd_val_pearson": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int64, C.POINTER(C.c_double)]),
+    "osd_val_centered_gram": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
+    "osd_val_corr_compare": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_double, _P]),
     "osd_set_constraints": (C.c_int, [_P, C.POINTER(OsdConstraints)]),
     "osd_get_loss_parts": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "osd_set_loss": (C.c_int, [_P, C.c_int, C.c_double, _P]),

@@ -121,6 +121,15 @@ class ShardComm:
         dist.all_reduce(t)
         return t.cpu().numpy()
 
+    def sum_tensor(self, t: torch.Tensor) -> torch.Tensor:
+        """Element-wise SUM over ranks of a tensor too large for a trip through numpy on every rank (a D x D Gram matrix): in
+        place on the device over RCCL, staged through the host over gloo.  Returns the summed tensor on t's device."""
+        if not self.on:
+            return t
+        staged = self._stage(t.contiguous())
+        dist.all_reduce(staged)
+        return staged if staged.device == t.device else staged.to(t.device)
+
     def gather_rows(self, t: torch.Tensor) -> torch.Tensor:
         """Concatenation over ranks (rank order) of [n_r, cols] tensors with ragged n_r, on t's device."""
         if not self.on:

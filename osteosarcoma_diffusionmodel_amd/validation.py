@@ -224,6 +224,55 @@ class DeviceKernels:
         L.check(L.lib().osd_val_gram(self._stream(), self.index, L.ptr(t), t.shape[0], t.shape[1], arr, g, out))
         return np.array(out[:]).reshape(g, g)
 
+    def centered_gram(self, t: torch.Tensor, center) -> torch.Tensor:
+        """float64 [D, D] DEVICE tensor G[i][j] = sum_r (t[r][i] - c[i]) (t[r][j] - c[j]) over all D columns of the fp32 device
+        tensor t (``osd_val_centered_gram``: fp32 differences and products, double sums, exactly symmetric, the same bits on every
+        call).  ``center``: D values, rounded to fp32 -- what the kernel subtracts.  A column-slice view is read in place."""
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError("centered_gram needs a [rows >= 1, features >= 1] tensor")
+        if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+            t = t.to(torch.float32).contiguous()
+        rows, D = t.shape
+        c = np.ascontiguousarray(center, dtype=np.float32)
+        if c.shape != (D,):
+            raise ValueError(f"center must hold one value per column ({D})")
+        g = torch.empty((D, D), dtype=torch.float64, device=t.device)
+        L.check(L.lib().osd_val_centered_gram(self._stream(), self.index, L.ptr(t), rows, max(int(t.stride(0)), D), D,
+                                              C.c_void_p(c.ctypes.data), L.ptr(g)))
+        return g
+
+    def corr_compare(self, g_real: torch.Tensor, g_synth: torch.Tensor, bounds: Sequence[int], strong: float) -> Dict[str, np.ndarray]:
+        """The figures of ``osd_val_corr_compare`` for two float64 [D, D] device Gram matrices: ``constant_columns`` (an int) and,
+        one entry per block pair a <= b in row-major order, ``pairs``, ``strong_pairs``, ``strong_agree`` (int64) and ``sum_abs``,
+        ``sum_sq``, ``max_abs``, ``strong_sum_abs`` (float64).  ``bounds``: 0 = b_0 < ... < b_B = D."""
+        D = g_real.shape[0]
+        for g in (g_real, g_synth):
+            if g.dtype != torch.float64 or tuple(g.shape) != (D, D) or not g.is_contiguous():
+                raise ValueError("the Gram matrices must be contiguous float64 [D, D] tensors of the same size")
+        nb = len(bounds) - 1
+        if nb < 1:
+            raise ValueError("at least one column block")
+        arr = (C.c_int32 * (nb + 1))(*[int(b) for b in bounds])
+        n_pairs = nb * (nb + 1) // 2
+        out = (C.c_double * (1 + L.OSD_CORR_STATS * n_pairs))()
+        L.check(L.lib().osd_val_corr_compare(self._stream(), self.index, L.ptr(g_real), L.ptr(g_synth), D, arr, nb, float(strong), out))
+        return corr_stats_from_flat(np.array(out[:]))
+
+
+COV_SLAB_ROWS = 256       # OSD_COV_SLAB_ROWS of include/osdiff.h: rows one fp32 accumulator run of osd_val_centered_gram covers
+_CORR_FIELDS = ("pairs", "sum_abs", "sum_sq", "max_abs", "strong_pairs", "strong_agree", "strong_sum_abs")
+_CORR_INT_FIELDS = ("pairs", "strong_pairs", "strong_agree")
+
+
+def corr_stats_from_flat(flat: np.ndarray) -> Dict[str, np.ndarray]:
+    """osd_val_corr_compare's host array (1 + 7 figures per block pair) as the dictionary ``DeviceKernels.corr_compare`` returns."""
+    flat = np.asarray(flat, dtype=np.float64)
+    table = flat[1:].reshape(-1, L.OSD_CORR_STATS)
+    out = {"constant_columns": int(round(flat[0]))}
+    for i, name in enumerate(_CORR_FIELDS):
+        out[name] = np.rint(table[:, i]).astype(np.int64) if name in _CORR_INT_FIELDS else table[:, i].copy()
+    return out
+
 
 # ---- combination of per-shard partials (pure host logic; the CPU tests drive it over gloo with numpy kernels) -----------
 def sharded_mmd(comm: ShardComm, k, x, y_local, gamma: float) -> float:
@@ -359,6 +408,117 @@ def prdc_summary(rows: Dict[str, np.ndarray], k: int) -> Dict[str, float]:
         "prdc_coverage": float(np.mean(c > 0)),
         "prdc_k": k,
     }
+
+
+def sharded_centered_gram(comm: ShardComm, k, local_rows):
+    """(n, mu, G): row count, float64 column means (numpy) and the float64 [D, D] centred cross-product sum_r (x_r - mu)(x_r - mu)^T of
+    the concatenated row shards, on ``local_rows``' device.  Column sums and row counts are all-reduced to the double mean mu, every
+    rank runs ``k.centered_gram`` with the centre c = float32(mu) -- the kernel subtracts in fp32 --, G is all-reduced, and the
+    rounding of the centre is taken out in double: sum (x - c)(x - c)^T = sum (x - mu)(x - mu)^T + n (mu - c)(mu - c)^T exactly.
+    An empty shard contributes nothing.  With an inactive ``comm`` this is the unsharded path."""
+    rows, D = int(local_rows.shape[0]), int(local_rows.shape[1])
+    sums = k.column_sums(local_rows) if rows else np.zeros(D, dtype=np.float64)
+    tot = comm.sum(np.concatenate([np.asarray(sums, dtype=np.float64), [float(rows)]]))
+    n = int(round(tot[-1]))
+    if n < 1:
+        raise ValueError("a centred Gram matrix needs at least one row")
+    mu = tot[:D] / n
+    c = mu.astype(np.float32)
+    if rows:
+        g = k.centered_gram(local_rows, c)
+    else:
+        g = torch.zeros((D, D), dtype=torch.float64, device=local_rows.device)
+    g = comm.sum_tensor(g)
+    d = torch.from_numpy(mu - c.astype(np.float64)).to(g.device)
+    g.sub_(torch.outer(d, d).mul_(float(n)))
+    return n, mu, g
+
+
+def frechet_distance(mu1, S1, mu2, S2) -> Dict[str, float]:
+    """Squared Frechet (2-Wasserstein) distance between the Gaussians N(mu1, S1) and N(mu2, S2), as FID reports it:
+    |mu1 - mu2|^2 + tr(S1 + S2 - 2 (S1 S2)^(1/2)).  numpy float64 throughout and symmetric eigen-decompositions only: with
+    A = S1^(1/2) from eigh(S1) (negative eigenvalues clipped to 0), tr (S1 S2)^(1/2) = sum sqrt(eigvalsh(A S2 A)) (clipped), so
+    rank-deficient covariances -- fewer patients than features -- give a finite, non-negative value where a general matrix
+    square root does not.  Keys: ``frechet_distance``, ``frechet_mean_term``, ``frechet_cov_term``."""
+    mu1, mu2 = np.atleast_1d(np.asarray(mu1, dtype=np.float64)), np.atleast_1d(np.asarray(mu2, dtype=np.float64))
+    S1, S2 = np.atleast_2d(np.asarray(S1, dtype=np.float64)), np.atleast_2d(np.asarray(S2, dtype=np.float64))
+    D = mu1.shape[0]
+    if mu1.shape != (D,) or mu2.shape != (D,) or S1.shape != (D, D) or S2.shape != (D, D):
+        raise ValueError("frechet_distance needs two means [D] and two covariances [D, D]")
+    if not (np.isfinite(mu1).all() and np.isfinite(mu2).all() and np.isfinite(S1).all() and np.isfinite(S2).all()):
+        raise ValueError("frechet_distance needs finite moments")
+    S1, S2 = 0.5 * (S1 + S1.T), 0.5 * (S2 + S2.T)
+    def clipped(lam):
+        # negative eigenvalues, and those inside the rounding noise of the largest (numpy.linalg.matrix_rank's tolerance), are zero:
+        # the square root would turn a null eigenvalue's 1e-16 of noise into 1e-8
+        top = float(lam.max(initial=0.0))
+        return np.where(lam > D * np.finfo(np.float64).eps * top, lam, 0.0)
+
+    w, v = np.linalg.eigh(S1)
+    a = (v * np.sqrt(clipped(w))) @ v.T
+    m = a @ S2 @ a
+    lam = clipped(np.linalg.eigvalsh(0.5 * (m + m.T)))
+    diff = mu1 - mu2
+    mean_term = float(diff @ diff)
+    cov_term = max(float(np.trace(S1) + np.trace(S2) - 2.0 * np.sqrt(lam).sum()), 0.0)
+    return {"frechet_distance": max(mean_term + cov_term, 0.0), "frechet_mean_term": mean_term, "frechet_cov_term": cov_term}
+
+
+def corr_block_bounds(blocks, D: int):
+    """(bounds, names) of a ``{name: width}`` mapping in column order (None: one block, "all"); the widths must add up to D."""
+    if blocks is None:
+        return [0, int(D)], ["all"]
+    names, bounds = [], [0]
+    for name, width in blocks.items():
+        width = int(width)
+        if width < 0:
+            raise ValueError(f"block {name!r} has a negative width")
+        if width == 0:
+            continue
+        names.append(str(name))
+        bounds.append(bounds[-1] + width)
+    if bounds[-1] != int(D):
+        raise ValueError(f"the block widths add up to {bounds[-1]}, the cohorts have {D} features")
+    return bounds, names
+
+
+def corr_summary(stats: Dict[str, np.ndarray], bounds: Sequence[int], names: Sequence[str]) -> Dict[str, float]:
+    """The ``corr_*`` figures from the per-block-pair sums of ``DeviceKernels.corr_compare`` (pairs i < j of non-constant columns,
+    delta = r_synth - r_real): mean, root mean square and largest |delta|, the Frobenius norm of the difference of the two correlation
+    matrices (sqrt(2 sum delta^2): both triangles, the diagonals agree), the pair and constant-column counts, and over the STRONG pairs
+    (|r_real| >= the threshold ``corr_compare`` was given) their number, the share whose r_synth has r_real's sign and their mean
+    |delta| -- NaN where there is no strong pair (or no pair at all).  With more than one block also ``corr_mean_abs_diff_<a>_<b>``
+    for every block pair a <= b in row-major order."""
+    nb = len(bounds) - 1
+    if nb < 1 or len(names) != nb:
+        raise ValueError("one name per column block")
+    n_pairs = nb * (nb + 1) // 2
+    pairs = np.asarray(stats["pairs"], dtype=np.int64)
+    if pairs.shape != (n_pairs,):
+        raise ValueError(f"{nb} blocks make {n_pairs} block pairs, the sums hold {pairs.shape}")
+    sum_abs, sum_sq = np.asarray(stats["sum_abs"], dtype=np.float64), np.asarray(stats["sum_sq"], dtype=np.float64)
+    total = int(pairs.sum())
+    strong = int(np.asarray(stats["strong_pairs"], dtype=np.int64).sum())
+    agree = int(np.asarray(stats["strong_agree"], dtype=np.int64).sum())
+    nan = float("nan")
+    out = {
+        "corr_mean_abs_diff": float(sum_abs.sum() / total) if total else nan,
+        "corr_rms_diff": float(np.sqrt(sum_sq.sum() / total)) if total else nan,
+        "corr_max_abs_diff": float(np.max(np.asarray(stats["max_abs"], dtype=np.float64))) if total else nan,
+        "corr_frobenius_diff": float(np.sqrt(2.0 * sum_sq.sum())),
+        "corr_pairs": total,
+        "corr_constant_columns": int(stats["constant_columns"]),
+        "corr_strong_pairs": strong,
+        "corr_strong_sign_agreement": float(agree / strong) if strong else nan,
+        "corr_strong_mean_abs_diff": float(np.asarray(stats["strong_sum_abs"], dtype=np.float64).sum() / strong) if strong else nan,
+    }
+    if nb > 1:
+        p = 0
+        for a in range(nb):
+            for b in range(a, nb):
+                out[f"corr_mean_abs_diff_{names[a]}_{names[b]}"] = float(sum_abs[p] / pairs[p]) if pairs[p] else nan
+                p += 1
+    return out
 
 
 class BiologicalValidator:
@@ -519,6 +679,45 @@ class BiologicalValidator:
         summary = prdc_summary(rows, k)
         return (summary, rows) if return_rows else summary
 
+    # -- second-order structure: correlation matrices and the Frechet distance (no counterpart in the reference)
+    def correlation_fidelity(self, real, synthetic, blocks=None, strong: float = 0.3, frechet: bool = False, return_matrices: bool = False):
+        """How well ``synthetic`` keeps ``real``'s correlation structure: the ``corr_*`` keys of ``corr_summary`` over all pairs of
+        columns (Pearson correlations of both cohorts from ``DeviceKernels.centered_gram``, compared on the device by
+        ``DeviceKernels.corr_compare``; neither correlation matrix is stored).  ``blocks``: an ordered ``{name: width}`` mapping that
+        splits the columns, for per-block-pair figures; ``strong``: |r_real| from which a pair counts as strongly correlated.
+        ``frechet=True`` adds ``frechet_distance``'s keys from the means and G / (n - 1) of both cohorts -- two D x D symmetric
+        eigen-decompositions on the host (seconds at D = 2000, most of a minute at D = 5000), hence off by default.  On a
+        ``sharded=True`` validator ``synthetic`` is this rank's row shard and the real cohort is replicated.
+        ``return_matrices=True`` also returns a dictionary with the device Gram matrices, the means, the row counts and the raw
+        sums."""
+        shapes = [tuple(a.shape) if hasattr(a, "shape") else np.shape(a) for a in (real, synthetic)]      # before anything moves
+        for name, shp in zip(("real", "synthetic"), shapes):
+            if len(shp) != 2 or shp[1] != shapes[0][-1] or shp[1] < 1:
+                raise ValueError(f"{name} must be [rows, features] and the cohorts must have the same features, got {shp}")
+            if shp[0] < 2 and not (self.comm.on and name == "synthetic"):
+                raise ValueError(f"{name} has {shp[0]} rows: a correlation needs at least 2")
+        bounds, names = corr_block_bounds(blocks, shapes[0][1])
+        strong = float(strong)
+        if not strong >= 0.0:
+            raise ValueError("strong must be a non-negative threshold")
+        x, y = _dev(real, self.device), _dev(synthetic, self.device)
+        for name, t in (("real", x), ("synthetic", y)):
+            if not bool(torch.isfinite(t).all().item()):
+                raise ValueError(f"{name} holds non-finite values")
+        n_r, mu_r, g_r = sharded_centered_gram(self._one, self.k, x)
+        n_s, mu_s, g_s = sharded_centered_gram(self.comm, self.k, y)
+        if n_s < 2:
+            raise ValueError(f"synthetic has {n_s} rows: a correlation needs at least 2")
+        stats = self.k.corr_compare(g_r, g_s, bounds, strong)
+        summary = corr_summary(stats, bounds, names)
+        if frechet:
+            summary.update(frechet_distance(mu_r, (g_r / (n_r - 1)).cpu().numpy(), mu_s, (g_s / (n_s - 1)).cpu().numpy()))
+        summary = self._agree(summary)
+        if return_matrices:
+            return summary, {"real_gram": g_r, "synth_gram": g_s, "real_mean": mu_r, "synth_mean": mu_s, "real_rows": n_r,
+                             "synth_rows": n_s, "stats": stats, "bounds": bounds, "names": names}
+        return summary
+
     # -- privacy: membership inference on the per-record likelihood bound (DESIGN.md section 3.18) ---------------------
     def membership_audit(self, model, train, holdout, *, num_timesteps: int = 32, seed: int = 0) -> Dict[str, float]:
         """The loss-threshold membership-inference attack on a diffusion model: ``train`` and ``holdout`` are (data, conditions)
@@ -645,8 +844,11 @@ class BiologicalValidator:
     # -- utils/validation.py:300-383 ---------------------------------------------------------------
     def validate_all(self, real_mutations, real_expression, real_pathways, synth_mutations, synth_expression, synth_pathways,
                      pathway_gene_matrix=None, privacy: bool = False, holdout=None, model=None, membership=None,
-                     prdc: bool = False, prdc_k: int = 5) -> Dict[str, float]:
-        """``prdc=True`` adds ``fidelity_diversity``'s keys (``prdc_k`` neighbours), on the same combined matrices as the statistical
+                     prdc: bool = False, prdc_k: int = 5, correlation: bool = False, frechet: bool = False,
+                     corr_strong: float = 0.3) -> Dict[str, float]:
+        """``correlation=True`` adds ``correlation_fidelity``'s ``corr_*`` keys (blocks ``mutations`` / ``expression`` / ``pathways``
+        from the three frames' widths, strong pairs from |r_real| >= ``corr_strong``) and ``frechet=True`` its ``frechet_*`` keys, on the
+        same combined matrices as the statistical tests.  ``prdc=True`` adds ``fidelity_diversity``'s keys (``prdc_k`` neighbours), on the same combined matrices as the statistical
         tests.  ``privacy=True`` adds ``privacy_audit``'s keys, on the same combined matrices as the statistical tests; ``holdout`` is
         then an optional (mutations, expression, pathways) triple of real patients the model never saw.  With a ``model`` (and
         ``membership`` = ((train data, train conditions), (holdout data, holdout conditions)), the rows as the model was trained
@@ -682,6 +884,10 @@ class BiologicalValidator:
                 all_results.update({f"membership_{k}": v for k, v in self.membership_audit(model, membership[0], membership[1]).items()})
         if prdc:
             all_results.update(self.fidelity_diversity(real_combined, synth_combined, k=prdc_k))
+        if correlation or frechet:
+            widths = {"mutations": parts_r[0].shape[1], "expression": parts_r[1].shape[1], "pathways": parts_r[2].shape[1]}
+            second = self.correlation_fidelity(real_combined, synth_combined, blocks=widths, strong=corr_strong, frechet=frechet)
+            all_results.update({key: v for key, v in second.items() if correlation or key.startswith("frechet_")})
         logger.info("=" * 50)
         logger.info("VALIDATION SUMMARY")
         logger.info("=" * 50)
