@@ -153,6 +153,7 @@ int osd_get_option(osd_handle *h, const char *name, int64_t *value);
 #define OSD_TP_MSE_BF16      (1 << 10)  /* output_proj + MSE on the bf16 matrix pipe ("precision" 1) */
 #define OSD_TP_LOSS_EPI      (1 << 11)  /* output_proj ran the configurable loss epilogue (osd_set_loss); never set on the default path */
 #define OSD_TP_TARGET        (1 << 12)  /* q_sample wrote a non-eps training target (osd_set_prediction); never set on the default path */
+#define OSD_TP_DP_CLIP       (1 << 13)  /* per-row gradient clipping ran (osd_set_dp_clip); never set on the default path */
 
 /* Schedule + time-embedding tables, computed by the host with the reference's own
  * fp32 expressions so they are bit-identical (models/diffusion.py:299-326, 131-137,
@@ -501,6 +502,51 @@ int osd_nn_clip_adamw_ema_step(void *stream, int device, double *normsq_ws, floa
                                float *exp_avg, float *exp_avg_sq, float *ema, int64_t numel, double lr,
                                double beta1, double beta2, double eps, double weight_decay, double max_norm,
                                int64_t step, double ema_decay, float *grad_norm_out);
+
+/* ---- differentially private training (DP-SGD, Abadi et al. 2016) ----
+ * A training call on n rows has loss L = (1/n) sum_r l_r, l_r = (1/D) w[t_r] sum_f rho(d_rf) (osd_set_loss, osd_set_prediction, dropout and
+ * condition dropout as configured).  With g_r = grad l_r over ALL parameter tensors taken as one vector and s_r = |g_r|_2,
+ *   c_r = min(1, C / (s_r + 1e-6)),     G = (1/n) sum_r c_r g_r.
+ * osd_set_dp_clip(h, C) with C > 0 makes every later osd_train_loss_fwd_bwd call with gradients return G in `grads` (the loss stays the
+ * unclipped L) and set OSD_TP_DP_CLIP; persistent like osd_set_loss; C = 0 clears it and restores the default launches bit for bit.
+ * OSD_EINVAL for a negative or non-finite C.  No per-row gradient is formed: every layer is a Linear or a per-row GroupNorm, so s_r^2 is
+ * a sum of row norms of buffers the backward pass already holds; one launch measures them, a second scales the rows of the buffers
+ * that the weight-gradient, column-sum and time-table launches read, and those launches run last.
+ * Such a call returns OSD_EUNSUPPORTED, with the reason in osd_last_error() and before any launch (no gradient buffer is touched), when
+ * bucket events are requested or loss_scale != 1 (data parallel), constraint terms are configured (batch statistics: no per-row
+ * gradient), an armed osd_train_batch_source has idx_b != NULL (mixup: one record in two rows), or a hidden width is not 256 / 512
+ * (GroupNorm groups outside the fused backward).  It never returns unclipped gradients.  Calls without gradients are unaffected;
+ * osd_denoiser_backward (a caller's own loss) returns OSD_EUNSUPPORTED while a bound is set.
+ * Two limits of the guarantee built on this: the (epsilon, delta) account of the Python Trainer assumes Poisson sampling at rate B/N
+ * while batches are shuffled fixed-size ones, and the noise below comes from Philox, which is not a cryptographically secure generator. */
+int osd_set_dp_clip(osd_handle *h, double max_grad_norm);
+/* s_r of the last clipped call's n rows into dst_dev (dev float[n]), asynchronously on the handle's stream.  OSD_ESTATE if there was
+ * none, OSD_EINVAL for another n. */
+int osd_dp_row_norms(osd_handle *h, float *dst_dev, int64_t n);
+/* The AdamW step of osd_clip_adamw_step / ..._ema_step with Gaussian noise in place of the batch clip (which is off: the per-row clip
+ * already bounds |G| <= C): the gradient element at flat position i becomes g + noise_std * z_i, is written back to grad, and goes
+ * through AdamW; one launch, no norm pass.  DP-SGD's noise_std is sigma * C / n.  z_i is a Philox4x32-10 + Box-Muller normal: the four
+ * values of positions 4q .. 4q + 3 come from the block at counter (q / 1024, q % 1024, step, 0x44504e00) under key `seed` -- the flat
+ * buffer read as rows of 4 096 elements.  noise_std 0 adds nothing (and leaves grad unwritten).  There is no grad_norm_out.
+ * OSD_EINVAL for a negative or non-finite noise_std and for step outside [1, 2^32). */
+int osd_dp_adamw_step(osd_handle *h, float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t numel, double lr,
+                      double beta1, double beta2, double eps, double weight_decay, double noise_std, uint64_t seed, int64_t step);
+int osd_nn_dp_adamw_step(void *stream, int device, float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t numel,
+                         double lr, double beta1, double beta2, double eps, double weight_decay, double noise_std, uint64_t seed,
+                         int64_t step);
+int osd_dp_adamw_ema_step(osd_handle *h, float *param, float *grad, float *exp_avg, float *exp_avg_sq, float *ema, int64_t numel,
+                          double lr, double beta1, double beta2, double eps, double weight_decay, double noise_std, uint64_t seed,
+                          int64_t step, double ema_decay);
+int osd_nn_dp_adamw_ema_step(void *stream, int device, float *param, float *grad, float *exp_avg, float *exp_avg_sq, float *ema,
+                             int64_t numel, double lr, double beta1, double beta2, double eps, double weight_decay,
+                             double noise_std, uint64_t seed, int64_t step, double ema_decay);
+
+/* Measurement aid for tools/dp_bench.py: the last clipped training call's row-norm launch (which = 0) or clip-factor launch (1) again, on
+ * the buffers that call left in the workspace; which = 2 sets every clip factor to `fill` first (a launch skips rows whose factor is 1).
+ * OSD_ESTATE if there was no such call, if any call has carved the training workspace since (another batch size may have re-allocated
+ * it), or if that call read its conditions from the caller's tensor and not from the workspace (a batch source or condition dropout
+ * puts them there).  The workspace no longer holds a step's values afterwards. */
+int osd_dp_replay(osd_handle *h, int which, float fill);
 
 /* Measurement aid for bench.py: per-launch HIP-event timing of one reverse step on n rows
  * (eager launches on the handle's stream, averaged over reps after one warm-up pass).

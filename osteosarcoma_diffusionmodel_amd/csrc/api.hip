@@ -15,6 +15,7 @@
 #include "fwd.h"
 #include "launch.h"
 #include "split.h"
+#include "dp.h"
 
 namespace osd {
 
@@ -547,6 +548,7 @@ int osd_destroy(osd_handle* h) {
   if (h->normsq_dev) e = hipFree(h->normsq_dev);
   if (h->parts_dev) e = hipFree(h->parts_dev);
   if (h->loss_tw) e = hipFree(h->loss_tw);
+  dp_free(h);
   if (h->t_san) e = hipFree(h->t_san);
   if (h->bound_ts) e = hipFree(h->bound_ts);
   for (hipEvent_t ev : h->ev_pool) e = hipEventDestroy(ev);

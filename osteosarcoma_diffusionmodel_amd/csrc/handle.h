@@ -227,6 +227,13 @@ struct osd_handle {
   float* d_pq = nullptr; int conv_kind = -1;
   int loss_kind = 0; float loss_delta = 1.0f;
   float* loss_tw = nullptr; bool loss_tw_set = false;
+  // differentially private training (osd_set_dp_clip; dp.h): persistent.  dp_clip = the per-row gradient bound C (0: off, today's launches);
+  // dp_norms = dev [2][dp_norms_cap]: s_r, then the clip factors c_r, of the last clipped call's dp_rows rows (-1: none yet); dp_plan = the
+  // cached item lists of the two launches (k_dp.hip)
+  double dp_clip = 0.0;
+  float* dp_norms = nullptr; int64_t dp_norms_cap = 0; int64_t dp_rows = -1;
+  void* dp_plan = nullptr;
+  bool dp_replay_ok = false;         // osd_dp_replay: the lists still describe the workspace (cleared by whatever carves it again: ensure_train_ws)
   // the likelihood bound (osd_row_sq_error / osd_bound_sweep): rows per launch group of the sweep, and the sweep's timesteps on the device
   int64_t bound_rows = 32768;        // osd_set_option("bound_rows")
   int* bound_ts = nullptr; int64_t bound_ts_cap = 0;

@@ -4,6 +4,7 @@
 #include "kernels_train.h"
 #include "gemm.h"
 #include "rng.h"
+#include "dp.h"
 
 namespace osd {
 
@@ -651,6 +652,71 @@ hipError_t launch_clip_adamw(hipStream_t s, float* p, float* g, float* m, float*
     hipLaunchKernelGGL(k_adamw<true>, ew_grid(n, 256 * 4), 256, 0, s, p, g, m, v, ema, ema_w, n, a, norm_ws, grid, norm_out);
   else
     hipLaunchKernelGGL(k_adamw<false>, ew_grid(n, 256 * 4), 256, 0, s, p, g, m, v, (float*)nullptr, 0.f, n, a, norm_ws, grid, norm_out);
+  return hipGetLastError();
+}
+
+// ---- the DP-SGD variant of the fused step (dp.h): Gaussian noise instead of the batch clip ----
+// The same seven streams (g is always written back: the noised gradient) plus the Philox / Box-Muller ALU work; no k_sumsq pass, since
+// nothing here depends on the batch's norm.  The four normals of float4 group q = i / 4 come from one Philox block at counter
+// (q / 1024, q % 1024, step, TAG_DP_NOISE): the flat buffer read as rows of DP_NOISE_COLS = 4 096 elements, whatever the launch geometry.
+__device__ __forceinline__ float4 dp_noise4(uint64_t seed, int64_t q, uint32_t step) {
+  return randn4(seed, (uint32_t)(q >> 10), (uint32_t)(q & 1023), step, TAG_DP_NOISE);
+}
+template <bool EMA>
+__global__ __launch_bounds__(256) void k_adamw_dp(float* p, float* g, float* m, float* v, float* e, float ema_w, int64_t n, AdamArgs a,
+                                                  float noise_std, uint64_t seed, uint32_t step) {
+  uintptr_t bits = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v);
+  if (EMA) bits |= reinterpret_cast<uintptr_t>(e);
+  const bool al = (bits & 15) == 0;
+  const int64_t n4 = al ? n >> 2 : 0;
+  const bool noisy = noise_std != 0.f;
+  float4* p4 = reinterpret_cast<float4*>(p); float4* g4 = reinterpret_cast<float4*>(g);
+  float4* m4 = reinterpret_cast<float4*>(m); float4* v4 = reinterpret_cast<float4*>(v);
+  float4* e4 = reinterpret_cast<float4*>(e);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    float4 pi = p4[i], gi = g4[i], mi = m4[i], vi = v4[i];
+    float4 ei;
+    if (EMA) ei = e4[i];
+    if (noisy) {
+      const float4 z = dp_noise4(seed, i, step);
+      gi.x = __fadd_rn(gi.x, __fmul_rn(noise_std, z.x)); gi.y = __fadd_rn(gi.y, __fmul_rn(noise_std, z.y));
+      gi.z = __fadd_rn(gi.z, __fmul_rn(noise_std, z.z)); gi.w = __fadd_rn(gi.w, __fmul_rn(noise_std, z.w));
+      g4[i] = gi;
+    }
+    adamw_one(pi.x, gi.x, mi.x, vi.x, a, 1.0f);
+    adamw_one(pi.y, gi.y, mi.y, vi.y, a, 1.0f);
+    adamw_one(pi.z, gi.z, mi.z, vi.z, a, 1.0f);
+    adamw_one(pi.w, gi.w, mi.w, vi.w, a, 1.0f);
+    p4[i] = pi; m4[i] = mi; v4[i] = vi;
+    if (EMA) {
+      ema_one(ei.x, pi.x, ema_w); ema_one(ei.y, pi.y, ema_w); ema_one(ei.z, pi.z, ema_w); ema_one(ei.w, pi.w, ema_w);
+      e4[i] = ei;
+    }
+  }
+  for (int64_t i = 4 * n4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float pi = p[i], gi = g[i], mi = m[i], vi = v[i];
+    if (noisy) {
+      const float4 z = dp_noise4(seed, i >> 2, step);
+      const int k = (int)(i & 3);
+      gi = __fadd_rn(gi, __fmul_rn(noise_std, k == 0 ? z.x : k == 1 ? z.y : k == 2 ? z.z : z.w));
+      g[i] = gi;
+    }
+    adamw_one(pi, gi, mi, vi, a, 1.0f);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+    if (EMA) {
+      float ei = e[i];
+      ema_one(ei, pi, ema_w);
+      e[i] = ei;
+    }
+  }
+}
+
+hipError_t launch_dp_adamw(hipStream_t s, float* p, float* g, float* m, float* v, int64_t n, const AdamArgs& a, float noise_std, uint64_t seed,
+                           uint32_t step, float* ema, float ema_w) {
+  if (n <= 0) return hipSuccess;
+  if (a.max_norm > 0.f) return hipErrorInvalidValue;
+  if (ema) hipLaunchKernelGGL(k_adamw_dp<true>, ew_grid(n, 256 * 4), 256, 0, s, p, g, m, v, ema, ema_w, n, a, noise_std, seed, step);
+  else hipLaunchKernelGGL(k_adamw_dp<false>, ew_grid(n, 256 * 4), 256, 0, s, p, g, m, v, (float*)nullptr, 0.f, n, a, noise_std, seed, step);
   return hipGetLastError();
 }
 

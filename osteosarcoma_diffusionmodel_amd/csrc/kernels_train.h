@@ -71,4 +71,9 @@ struct AdamArgs {
 hipError_t launch_clip_adamw(hipStream_t s, float* p, float* g, float* m, float* v, int64_t n, const AdamArgs& a, double* norm_ws, float* norm_out,
                              float* ema = nullptr, float ema_w = 0.f);
 
+// The DP-SGD step (dp.h): g + noise_std * z instead of the batch clip, z ~ N(0, 1) from Philox keyed by (seed; i / 4096, (i % 4096) / 4, step,
+// TAG_DP_NOISE) for flat position i; the noised gradient is written back to g.  a.max_norm must be 0.  No norm pass: one launch.
+hipError_t launch_dp_adamw(hipStream_t s, float* p, float* g, float* m, float* v, int64_t n, const AdamArgs& a, float noise_std, uint64_t seed,
+                           uint32_t step, float* ema = nullptr, float ema_w = 0.f);
+
 }  // namespace osd

@@ -2,12 +2,14 @@
 // fused forward + backward of the eps-prediction MSE loss, mixup lives in api.hip,
 // clip_grad_norm_ + AdamW over flat buffers.
 #include <math.h>
+#include <string.h>
 #include <cmath>
 #include <algorithm>
 #include "handle.h"
 #include "kernels.h"
 #include "kernels_train.h"
 #include "fwd.h"
+#include "dp.h"
 
 namespace osd {
 
@@ -124,6 +126,7 @@ static hipError_t dgrad(hipStream_t s, const float* w, int ldw, int kin, const f
 static int ensure_train_ws(osd_handle* h, hipStream_t s, int64_t n, const ConsPlan* cp, TrainWs* w) {
   const Arch& a = h->arch;
   const int64_t need = carve_train(a, nullptr, n, cp, w);
+  h->dp_replay_ok = false;               // the workspace is about to be carved (and perhaps re-allocated) for another call
   if (h->train_arena_floats < need) {
     if (h->train_arena) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(h->train_arena)); h->train_arena = nullptr; h->train_arena_floats = 0; }
     OSD_TRY(device_alloc((void**)&h->train_arena, (size_t)need * 4));
@@ -221,6 +224,11 @@ struct BackwardPass {
   size_t ev_used = 0;                  // cursor into the handle's pool of internal events
   bool s2_slabs_busy = false;          // an immediate split-K weight gradient on the side stream may still be using W.slabs
   hipEvent_t mid_done = nullptr;       // the side stream is through with the slab workspace
+  // Differentially private step (osd_set_dp_clip; dp.h): the dgrad chain runs first and every leaf -- weight gradients, column sums, the
+  // time-table scatter -- waits in dp_wg / cols until dp_clip_leaves() has measured each row's gradient norm and scaled the rows of
+  // the buffers the leaves read.  Everything behind the dgrad chain is linear in those rows, so the scaling is exact.
+  bool dp = false, dp_replay = false;
+  std::vector<WgPending> dp_wg;        // the weight gradients in the order the pass met them
 
   BackwardPass(osd_handle* h_, hipStream_t s_, TrainWs& W_, int64_t n_, bool train, const float* const* masks_, uint64_t seed_, uint32_t roff_,
                float* const* grads_, void* const* events_, bool squads_)
@@ -268,6 +276,7 @@ struct BackwardPass {
   // ordered by dependency counters.  Parity-green and slower, 800 vs 539 us: a wave streaming fp32 MFMAs starves the co-resident
   // wave's VALU epilogue, so the dgrad chain stretched.  Removed in round 4; the stamps and the verdict are profiles/r03_bwd_persist.md.)
   int weight_grad(const WgPending& wp) {
+    if (dp && !dp_replay) { dp_wg.push_back(wp); return OSD_OK; }
     if (wp.kin >= 16 && wgrad_group_ok(wp)) { pend.push_back(wp); h->last_train_path |= OSD_TP_WGRAD_GROUP; return OSD_OK; }
     h->last_train_path |= OSD_TP_WGRAD_DIRECT;
     float* const b0 = wp.bias[0];
@@ -465,14 +474,16 @@ struct BackwardPass {
   int stem(const float* x_t, int x_ld, const int* t_idx, const float* cond, float* dx_t) {
     const ParamMap& pm = a.pm;
     const int D = a.D, H0 = a.H0;
-    if (s2 != s && !cols.empty()) { OSD_TRY(fork()); OSD_TRY(side_leaves(s2)); }      // every GroupNorm layer's gy / z is final
+    if (!dp && s2 != s && !cols.empty()) { OSD_TRY(fork()); OSD_TRY(side_leaves(s2)); }      // every GroupNorm layer's gy / z is final
     if (dx_t) OSD_TRY(dgrad_plain(DgradOp{h->params[pm.in_w], D, D, W.g_h0, H0}, dx_t));
     WgPending in = wg_item(x_t, D, W.g_h0, H0, n, grads[pm.in_w], D, grads[pm.in_b]);
     in.ldx = x_ld; in.bias[1] = grads[pm.cp_b]; in.bias[2] = grads[pm.tp_b];
     OSD_TRY(weight_grad(in));
     OSD_TRY(weight_grad(wg_item(W.f.ce2, 64, W.g_h0, H0, n, grads[pm.cp_w], 64)));
     // the branch below h0 (scatter into the time table, cond_proj's and the second embedding Linear's dgrads, SiLU backward): one launch
-    const bool cond_fused = h->cond_bwd_fused && cond_bwd_ok(H0, W.g_h0, W.u0, W.g_ce2, W.g_u);
+    // (a differentially private step takes the unfused branch: the fused launch scatters into the time table and can carry a weight
+    // gradient, both leaves, before any clip factor exists; its scatter waits for dp_clip_leaves())
+    const bool cond_fused = !dp && h->cond_bwd_fused && cond_bwd_ok(H0, W.g_h0, W.u0, W.g_ce2, W.g_u);
     // ... and, where the first embedding Linear has at most four inputs (k_small_wgrad's case), its weight gradient rides along
     const bool ce0_fused = cond_fused && a.cond_dim <= 4 && small_wgrad_ok(a.cond_dim, 64, a.cond_dim);
     if (cond_fused) h->last_train_path |= OSD_TP_COND_BWD;
@@ -481,7 +492,7 @@ struct BackwardPass {
       OSD_HIP(launch_cond_bwd(s, W.g_h0, H0, t_idx, W.g_temb, h->params[pm.cp_w], h->params[pm.ce2_w], W.u0, n, W.g_ce2, W.g_u,
                               ce0_fused ? cond : nullptr, a.cond_dim, W.g_temb + (int64_t)t_pad(a.T) * H0, grads[pm.ce0_w], grads[pm.ce0_b]));
     } else {
-      OSD_HIP(launch_scatter_rows(s, W.g_h0, t_idx, n, H0, W.g_temb));
+      if (!dp) OSD_HIP(launch_scatter_rows(s, W.g_h0, t_idx, n, H0, W.g_temb));
       OSD_TRY(dgrad_plain(DgradOp{h->params[pm.cp_w], 64, 64, W.g_h0, H0}, W.g_ce2));
     }
     // both tables carry zero rows up to a multiple of 32 (whole K steps of the grouped kernel): they add nothing
@@ -496,10 +507,68 @@ struct BackwardPass {
     return OSD_OK;
   }
 
+  // The per-row norms (dp.h: one term per Linear and per GroupNorm layer, from the buffers the dgrad chain has just left), the clip factors
+  // and the scaling of every buffer a leaf reads, then the leaves themselves in the order the pass met them.
+  int dp_clip_leaves(const float* x_t, int x_ld, const int* t_idx, const float* cond, const float* d_out) {
+    std::vector<DpNormItem> ni;
+    std::vector<DpScaleItem> si;
+    auto linear = [&](const float* x0, int ld0, int k0, const float* x1, int k1, const float* d, int nd) {
+      DpNormItem it;
+      memset(&it, 0, sizeof(it));
+      it.kind = 0; it.x[0] = x0; it.ldx[0] = ld0; it.k[0] = k0; it.x[1] = x1; it.ldx[1] = k1; it.k[1] = k1;
+      it.nbias = 1.f; it.d = d; it.ldd = nd; it.nd = nd;
+      ni.push_back(it);
+    };
+    auto scaled = [&](float* p, int cols) {
+      DpScaleItem it;
+      memset(&it, 0, sizeof(it));
+      it.p = p; it.ld = cols; it.cols = cols;
+      si.push_back(it);
+    };
+    const int last = a.n_blocks - 1;
+    linear(W.f.out[last], a.block_out[last], a.block_out[last], nullptr, 0, d_out, a.D);      // output_proj
+    scaled(const_cast<float*>(d_out), a.D);
+    for (int b = a.n_blocks - 1; b >= 0; --b) {
+      const Block B = block(b);
+      linear(W.f.mid[b], B.C, B.C, nullptr, 0, W.g_z2[b], B.C);                                // the block's second Linear
+      linear(B.xin, B.l1.K1, B.l1.K1, B.l1.K2 > 0 ? W.f.out[B.skip_block] : nullptr, B.l1.K2, W.g_z1[b], B.C);      // its first: main input + skip
+      for (int half = 0; half < 2; ++half) {
+        const GnLayer t = gn_layer(b, half);
+        DpNormItem it;
+        memset(&it, 0, sizeof(it));
+        it.kind = 1; it.d = t.gy; it.ldd = B.C; it.nd = B.C; it.z = t.z; it.stats = t.stats; it.gw = t.l.gw;
+        ni.push_back(it);
+      }
+      scaled(W.g_z2[b], B.C); scaled(W.g_z1[b], B.C); scaled(W.g_out[b], B.C); scaled(W.g_mid[b], B.C);
+    }
+    {
+      // h0 = input_proj(x_t) + cond_proj(ce2) + time_proj(temb[t]): three Linears on one output gradient, each with a bias of its own
+      DpNormItem it;
+      memset(&it, 0, sizeof(it));
+      it.kind = 0; it.x[0] = x_t; it.ldx[0] = x_ld; it.k[0] = a.D; it.x[1] = W.f.ce2; it.ldx[1] = 64; it.k[1] = 64;
+      it.x[2] = h->d_time_emb; it.ldx[2] = a.time_dim; it.k[2] = a.time_dim; it.gathered = 1;      // rows t_idx[r]: a launch argument
+      it.nbias = 3.f; it.d = W.g_h0; it.ldd = a.H0; it.nd = a.H0;
+      ni.push_back(it);
+    }
+    linear(W.f.ce1, 64, 64, nullptr, 0, W.g_ce2, 64);                   // ConditionalEmbedding's second Linear
+    linear(nullptr, a.cond_dim, a.cond_dim, nullptr, 0, W.g_u, 64);     // ... and its first, on the batch's conditions: a launch argument
+    ni.back().x0_is_cond = 1;
+    scaled(W.g_h0, a.H0); scaled(W.g_ce2, 64); scaled(W.g_u, 64);
+    // the stored gradients carry the 1/n of the mean over rows (loss_scale is 1 here): a row's own norm is n times what they give
+    OSD_TRY(dp_clip_rows(h, s, ni, si, n, (double)n, cond, t_idx));
+    OSD_HIP(launch_scatter_rows(s, W.g_h0, t_idx, n, a.H0, W.g_temb));
+    dp_replay = true;
+    for (const WgPending& wp : dp_wg) OSD_TRY(weight_grad(wp));
+    dp_wg.clear();
+    return OSD_OK;
+  }
+
   int run(const float* x_t, int x_ld, const int* t_idx, const float* cond, const float* d_out, float* dx_t, float* loss_poison) {
     if (h->train_streams == 2) OSD_TRY(side_stream(h, &s2));
     for (const LayerDesc& l : a.layers) fuse = fuse && dgrad_gnbwd_supported(l.gw);
     if (squads && !fuse) { set_error("internal: squad backward without the fused GroupNorm backward"); return OSD_EINVAL; }
+    if (dp && !fuse) { set_error("internal: per-row clip without the fused GroupNorm backward"); return OSD_EINVAL; }
+    if (dp) h->last_train_path |= OSD_TP_DP_CLIP;
     if (fuse) h->last_train_path |= OSD_TP_FUSED_GN_BWD;
     if (squads) h->last_train_path |= OSD_TP_SQUAD_BWD;
     OSD_TRY(head(d_out, loss_poison));
@@ -511,6 +580,7 @@ struct BackwardPass {
     // is re-cut to the launch, wgrad_group.hip), so a single process keeps the one launch.
     if (events) OSD_TRY(flush_end());
     OSD_TRY(stem(x_t, x_ld, t_idx, cond, dx_t));
+    if (dp) OSD_TRY(dp_clip_leaves(x_t, x_ld, t_idx, cond, d_out));
     return flush_end();          // ends with the side stream joined: the caller's stream owns every result again
   }
 };
@@ -715,6 +785,7 @@ struct LossStep {
     if (cp) OSD_TRY(constraints());
     if (!grads) return OSD_OK;
     BackwardPass bp(h, s, w, n, tc.train_mode(), masks, seed, roff, grads, events, squads_bwd);
+    bp.dp = h->dp_clip > 0.0 && !se_out;
     OSD_TRY(bp.run(w.x_t, w.xld, tc.t_idx, cond, w.d_out, nullptr, loss_out));
     return tc.finish();
   }
@@ -741,6 +812,21 @@ int osd_grad_buckets(const osd_config* cfg, int32_t* first, int32_t* last, int m
   return n;
 }
 
+// What a call with gradients under osd_set_dp_clip cannot be: anything in which a row's own gradient is undefined or would reach a leaf
+// before its clip factor exists.
+static int dp_supported(const osd_handle* h, bool from_src, double loss_scale, void* const* events) {
+  const char* why = nullptr;
+  if (events || loss_scale != 1.0) why = "data parallel (bucket events, loss_scale != 1) is not supported";
+  else if ((h->cons.n_pathways > 0 && h->w_pathway != 0.0) || (h->cons.n_a > 0 && h->w_mutexpr != 0.0))
+    why = "the constraint losses are batch statistics: a row has no gradient of its own (osd_set_constraints(h, NULL) clears them)";
+  else if (from_src && h->batch_src.idx_b) why = "a mixed-up batch source (idx_b) puts one record into two rows";
+  for (const LayerDesc& l : h->arch.layers)
+    if (!why && !dgrad_gnbwd_supported(l.gw)) why = "a GroupNorm group width outside the fused GroupNorm backward (32 / 64: hidden widths 256 / 512)";
+  if (!why) return OSD_OK;
+  set_error("per-row gradient clipping (osd_set_dp_clip): %s", why);
+  return OSD_EUNSUPPORTED;
+}
+
 // checks in order: ready, rows, (one-shots consumed), null tensors, empty batch, row offset, event count, grads[i], then the device
 int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, int64_t n, const int32_t* t_index, const float* noise,
                            const float* const* masks, uint64_t seed, int64_t row_offset, int flags, float* loss_out,
@@ -755,6 +841,7 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
   if (n == 0) { set_error("empty batch"); return OSD_EINVAL; }
   OSD_TRY(check_row_offset(row_offset, n));
   OSD_TRY(tc.check_outputs(events, n_events, grads));
+  if (grads && h->dp_clip > 0.0) OSD_TRY(dp_supported(h, from_src, loss_scale, events));      // before any launch: no gradient buffer is touched
   OSD_TRY(tc.enter());
   LossStep step{tc, h, h->arch, tc.s, n, x0, cond, noise, masks, seed, (uint32_t)row_offset, loss_out, grads, loss_scale, events, from_src, cond_drop};
   return step.run(t_index);
@@ -903,6 +990,9 @@ int osd_denoiser_backward(osd_handle* h, const float* x_t, const int32_t* t_inde
   TrainCall tc{h, n, flags};
   OSD_TRY(tc.begin(true));
   if (!x_t || !t_index || !cond || !dout || !grads || n == 0) { set_error("null tensor or empty batch"); return OSD_EINVAL; }
+  // an upstream gradient of the caller's own loss: whether its rows are per-patient terms is not this call's to know, so it never clips --
+  // and never hands back unclipped gradients while a per-row bound is set
+  if (h->dp_clip > 0.0) { set_error("per-row gradient clipping (osd_set_dp_clip) covers osd_train_loss_fwd_bwd only"); return OSD_EUNSUPPORTED; }
   if (h->saved_rows != n) { set_error("osd_denoiser_backward needs the activations of an osd_denoiser_forward_train call on the same %lld rows", (long long)n); return OSD_ESTATE; }
   OSD_TRY(tc.check_outputs(events, n_events, grads));
   OSD_TRY(check_row_offset(row_offset, n));
@@ -970,19 +1060,24 @@ int osd_get_loss_parts(osd_handle* h, float* parts_host3) {
 
 // The hyper-parameters of one fused clip_grad_norm_ + AdamW step, as the four entry points receive them.
 struct AdamHyper { double lr, beta1, beta2, eps, weight_decay, max_norm; int64_t step; };
+// the DP-SGD variants: Gaussian noise of this standard deviation on every gradient element instead of the batch clip (max_norm is then 0)
+struct DpNoise { double std; uint64_t seed; };
 
 // The checked body of the four AdamW entry points.  `h`: the handle-taking variants, whose stream, device and norm workspace are
 // the handle's; null for the stream-taking ones, which bring their own.  `want_ema`: the EMA variants, which reject a null ema and
 // a decay outside [0, 1] before any device call.
 static int clip_adamw_step(osd_handle* h, hipStream_t stream, int device, double* norm_ws, float* param, float* grad, float* exp_avg,
-                           float* exp_avg_sq, int64_t numel, const AdamHyper& hp, float* grad_norm_out, bool want_ema, float* ema, double ema_decay) {
-  if ((!h && !norm_ws) || !param || !grad || !exp_avg || !exp_avg_sq) { set_error("null argument"); return OSD_EINVAL; }
+                           float* exp_avg_sq, int64_t numel, const AdamHyper& hp, float* grad_norm_out, bool want_ema, float* ema, double ema_decay,
+                           const DpNoise* dp = nullptr) {
+  if ((!h && !norm_ws && !dp) || !param || !grad || !exp_avg || !exp_avg_sq) { set_error("null argument"); return OSD_EINVAL; }
   if (want_ema && !ema) { set_error("null argument"); return OSD_EINVAL; }
   if (want_ema && !(ema_decay >= 0.0 && ema_decay <= 1.0)) { set_error("ema_decay must be in [0, 1]"); return OSD_EINVAL; }
   if (numel <= 0 || hp.step < 1) { set_error("numel and step must be positive"); return OSD_EINVAL; }
+  if (dp && (!(dp->std >= 0.0) || !std::isfinite(dp->std) || !std::isfinite((float)dp->std))) { set_error("noise_std must be finite and >= 0, got %g", dp->std); return OSD_EINVAL; }
+  if (dp && hp.step > 0xffffffffll) { set_error("step does not fit the 32-bit Philox counter"); return OSD_EINVAL; }
   OSD_HIP(hipSetDevice(h ? h->cfg.device : device));
   if (h) {
-    if (!h->normsq_dev) OSD_HIP(hipMalloc((void**)&h->normsq_dev, 256 * sizeof(double)));
+    if (!dp && !h->normsq_dev) OSD_HIP(hipMalloc((void**)&h->normsq_dev, 256 * sizeof(double)));
     // the handle's own optimizer is about to change parameters it may hold derived copies of (t_emb table, packed input_proj /
     // output_proj, chain and bf16x3 weight copies): the next forward / sampling entry point refreshes them (api.hip: ensure_packed)
     h->w_packed_stale = true;
@@ -999,6 +1094,10 @@ static int clip_adamw_step(osd_handle* h, hipStream_t stream, int device, double
   a.eps = (float)hp.eps;
   a.neg_step_size = (float)(-(hp.lr / bc1));
   a.max_norm = (float)hp.max_norm;
+  if (dp) {
+    OSD_HIP(launch_dp_adamw(stream, param, grad, exp_avg, exp_avg_sq, numel, a, (float)dp->std, dp->seed, (uint32_t)hp.step, ema, (float)(1.0 - ema_decay)));
+    return OSD_OK;
+  }
   OSD_HIP(launch_clip_adamw(stream, param, grad, exp_avg, exp_avg_sq, numel, a, norm_ws, grad_norm_out, ema, (float)(1.0 - ema_decay)));
   return OSD_OK;
 }
@@ -1030,6 +1129,38 @@ int osd_nn_clip_adamw_ema_step(void* stream, int device, double* normsq_ws, floa
                                double max_norm, int64_t step, double ema_decay, float* grad_norm_out) {
   return clip_adamw_step(nullptr, (hipStream_t)stream, device, normsq_ws, param, grad, exp_avg, exp_avg_sq, numel,
                          {lr, beta1, beta2, eps, weight_decay, max_norm, step}, grad_norm_out, true, ema, ema_decay);
+}
+
+int osd_dp_adamw_step(osd_handle* h, float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel, double lr, double beta1,
+                      double beta2, double eps, double weight_decay, double noise_std, uint64_t seed, int64_t step) {
+  if (!h) { set_error("null argument"); return OSD_EINVAL; }
+  const DpNoise dp{noise_std, seed};
+  return clip_adamw_step(h, nullptr, 0, nullptr, param, grad, exp_avg, exp_avg_sq, numel, {lr, beta1, beta2, eps, weight_decay, 0.0, step}, nullptr,
+                         false, nullptr, 0.0, &dp);
+}
+
+int osd_nn_dp_adamw_step(void* stream, int device, float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel, double lr,
+                         double beta1, double beta2, double eps, double weight_decay, double noise_std, uint64_t seed, int64_t step) {
+  const DpNoise dp{noise_std, seed};
+  return clip_adamw_step(nullptr, (hipStream_t)stream, device, nullptr, param, grad, exp_avg, exp_avg_sq, numel,
+                         {lr, beta1, beta2, eps, weight_decay, 0.0, step}, nullptr, false, nullptr, 0.0, &dp);
+}
+
+int osd_dp_adamw_ema_step(osd_handle* h, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel, double lr,
+                          double beta1, double beta2, double eps, double weight_decay, double noise_std, uint64_t seed, int64_t step,
+                          double ema_decay) {
+  if (!h) { set_error("null argument"); return OSD_EINVAL; }
+  const DpNoise dp{noise_std, seed};
+  return clip_adamw_step(h, nullptr, 0, nullptr, param, grad, exp_avg, exp_avg_sq, numel, {lr, beta1, beta2, eps, weight_decay, 0.0, step}, nullptr,
+                         true, ema, ema_decay, &dp);
+}
+
+int osd_nn_dp_adamw_ema_step(void* stream, int device, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel,
+                             double lr, double beta1, double beta2, double eps, double weight_decay, double noise_std, uint64_t seed,
+                             int64_t step, double ema_decay) {
+  const DpNoise dp{noise_std, seed};
+  return clip_adamw_step(nullptr, (hipStream_t)stream, device, nullptr, param, grad, exp_avg, exp_avg_sq, numel,
+                         {lr, beta1, beta2, eps, weight_decay, 0.0, step}, nullptr, true, ema, ema_decay, &dp);
 }
 
 }  // extern "C"

@@ -148,6 +148,14 @@ class _Engine:
         self.loss_state = None          # the model's _loss_state() this handle was last configured with (None: the library's default)
         self.prediction_type = "epsilon"  # the model's prediction_type this handle's tables were last folded for (the library's default)
         self.serial = 0                 # bumped by every call that rewrites the handle's training workspace
+        self.dp_clip = 0.0              # the per-row gradient bound this handle was last given (osd_set_dp_clip; 0: off, the library's default)
+
+    def set_dp_clip(self, model: "BiologyAwareDiffusionModel"):
+        """Validate the model's dp_max_grad_norm and hand it to the handle (osd_set_dp_clip: persistent)."""
+        c = getattr(model, "dp_max_grad_norm", None)
+        c = 0.0 if c is None else float(c)
+        L.check(L.lib().osd_set_dp_clip(self.handle, c))        # ValueError for a negative or non-finite bound
+        self.dp_clip = c
 
     def set_constraints(self, spec):
         lib = L.lib()
@@ -351,6 +359,11 @@ class BiologyAwareDiffusionModel(nn.Module):
         # "epsilon" (the reference's and the default: everything as without the key), "v_prediction" or "sample".  The training target, the
         # constraint losses' x0^, min_snr's form, every sampler and sampling option follow it.  A plain attribute like the loss keys
         self.prediction_type: str = OB.check_prediction_type(dm.get("prediction_type", "epsilon"))
+        # differentially private training: None / 0 (the default: today's training call, bit for bit) or the bound C
+        # on every row's (patient's) own gradient norm.  A training call with gradients then returns (1/n) sum_r min(1, C / (|g_r| + 1e-6)) g_r;
+        # the loss stays the unclipped mean.  train.py's Trainer sets it from training.dp; a plain attribute for users of the bare model.
+        # ValueError from the call for what has no per-row gradient (constraint losses, a mixed-up batch source, data parallel)
+        self.dp_max_grad_norm: Optional[float] = None
         self._loss_weights = None         # set_loss_weights: a custom per-timestep table (host float32 [T]); wins over loss_weighting
         self._loss_version = 0
 
@@ -390,6 +403,13 @@ class BiologyAwareDiffusionModel(nn.Module):
                 "w_me": float(mutexpr_weight if mutexpr_weight is not None else cons.get("mutation_expression_weight", 1.0)),
             }
         self._constraints_version += 1
+
+    def last_row_norms(self, n: int) -> torch.Tensor:
+        """|g_r|_2 of the n rows of the most recent training call that ran with ``dp_max_grad_norm`` set: device float32 [n]."""
+        eng = self._engine()
+        out = torch.empty(int(n), device=eng.device, dtype=torch.float32)
+        L.check(L.lib().osd_dp_row_norms(eng.handle, L.ptr(out), int(n)))
+        return out
 
     def last_loss_parts(self):
         """(eps-loss, L_pc, L_me) of the most recent training ``forward`` with constraints configured; the eps-loss is the configured
@@ -457,6 +477,8 @@ class BiologyAwareDiffusionModel(nn.Module):
         if eng.loss_state != state:
             eng.set_loss(self)          # raises ValueError on an unknown value; the handle then keeps its previous setting
             eng.loss_state = state
+        if eng.dp_clip != float(getattr(self, "dp_max_grad_norm", None) or 0.0):
+            eng.set_dp_clip(self)
         for attr, option, encode in ENGINE_OPTIONS:
             value = encode(getattr(self, attr))
             if value is not None:

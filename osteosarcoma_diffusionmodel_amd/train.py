@@ -263,7 +263,12 @@ class FusedAdamW(torch.optim.Optimizer):
     parameter / gradient buffers (utils/train.py:169-173, 242-244).  ``state_dict()`` has the
     layout of ``torch.optim.AdamW`` (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``), so
     checkpoints interchange with the reference's.  With ``ema`` (a ``ParamEMA`` over the same ``flat``) the same pass also
-    updates the running average, with the decay of this step (``ema.decay_at``)."""
+    updates the running average, with the decay of this step (``ema.decay_at``).
+
+    ``dp`` (a dict ``{noise_multiplier, max_grad_norm, seed}``, or None): the DP-SGD step (``osd_nn_dp_adamw_step``).  The gradients
+    are then expected to be the per-row clipped mean of ``dp_rows`` rows (``model.dp_max_grad_norm``); the kernel adds
+    N(0, (noise_multiplier * max_grad_norm / dp_rows)^2) noise to every element, keyed by (seed, position, this step), writes the noised
+    gradient back and applies AdamW with no batch clip (``max_norm`` is ignored; ``grad_norm`` is not produced)."""
 
     def __init__(self, model: nn.Module, flat: FlatParams, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-2, max_norm: float = 0.0, overwrites_grads: bool = True, ema: Optional[ParamEMA] = None):
@@ -272,6 +277,8 @@ class FusedAdamW(torch.optim.Optimizer):
         if ema is not None and (ema.flat is not flat or ema.shadow.numel() != flat.flat.numel() or ema.shadow.device != flat.flat.device):
             raise ValueError("ema must be a ParamEMA over this optimizer's FlatParams")
         self.ema = ema
+        self.dp: Optional[dict] = None
+        self.dp_rows = 0                              # rows of the batch whose gradients the next step consumes (the Trainer sets it)
         self.overwrites_grads = overwrites_grads      # the fused diffusion backward overwrites; autograd accumulates
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
@@ -289,7 +296,19 @@ class FusedAdamW(torch.optim.Optimizer):
         dev = self.flat.flat.device
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         dev_i = dev.index if dev.index is not None else torch.cuda.current_device()
-        if self.ema is None:
+        if self.dp is not None:
+            if self.dp_rows < 1:
+                raise RuntimeError("FusedAdamW.dp needs dp_rows, the number of rows behind the gradients")
+            std = float(self.dp["noise_multiplier"]) * float(self.dp["max_grad_norm"]) / self.dp_rows
+            hyper = (self.flat.flat.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], std, int(self.dp["seed"]), self._step)
+            if self.ema is None:
+                L.check(L.lib().osd_nn_dp_adamw_step(stream, dev_i, L.ptr(self.flat.flat), L.ptr(self.flat.grad), L.ptr(self.exp_avg),
+                                                     L.ptr(self.exp_avg_sq), *hyper))
+            else:
+                L.check(L.lib().osd_nn_dp_adamw_ema_step(stream, dev_i, L.ptr(self.flat.flat), L.ptr(self.flat.grad), L.ptr(self.exp_avg),
+                                                         L.ptr(self.exp_avg_sq), L.ptr(self.ema.shadow), *hyper, self.ema.decay_at(self._step)))
+                self.ema.num_updates += 1
+        elif self.ema is None:
             L.check(L.lib().osd_nn_clip_adamw_step(stream, dev_i,
                                                    L.ptr(self._normsq), L.ptr(self.flat.flat), L.ptr(self.flat.grad), L.ptr(self.exp_avg),
                                                    L.ptr(self.exp_avg_sq), self.flat.flat.numel(), g["lr"], g["betas"][0], g["betas"][1],
@@ -614,7 +633,15 @@ class Trainer:
     same update to the same all-reduced gradients, so all ranks keep the same average with no extra collective.
     ``training.ema_warmup`` (default true) ramps the decay as ``ParamEMA.decay_at``; ``training.ema_validate`` (default false) runs
     ``validate()`` -- and with it the LR scheduler, the best-model choice and early stopping -- on the averaged weights.
-    Checkpoints then carry ``ema_state_dict``; ``load_checkpoint`` resumes a run."""
+    Checkpoints then carry ``ema_state_dict``; ``load_checkpoint`` resumes a run.
+
+    Differentially private training (``training.dp = {max_grad_norm: C, noise_multiplier: sigma | target_epsilon: eps, delta: 1e-5,
+    seed: optional}``; absent: nothing below exists): DP-SGD.  Every patient's gradient is clipped to norm C inside the training call
+    (``model.dp_max_grad_norm``), the optimizer adds N(0, (sigma C / B)^2) noise to the mean and applies no batch clip, and
+    ``privacy_spent()`` keeps the (epsilon, delta) account (privacy.py).  ``target_epsilon`` is turned into sigma for the planned
+    ``num_epochs`` x batches per epoch; early stopping then spends less.  Not with mixup, the constraint losses, a cVAE or data
+    parallel (ValueError at construction).  The account assumes Poisson sampling at rate B / N while the loader shuffles fixed-size
+    batches, and the noise is Philox's, not a cryptographically secure generator's.  Checkpoints then carry ``dp_state``."""
 
     def __init__(self, model: nn.Module, train_loader: DataLoader, val_loader: DataLoader, config: dict,
                  device: str = "cuda", *, comm: Optional[str] = None):
@@ -626,6 +653,14 @@ class Trainer:
         ema_decay = 0.0 if ema_decay is None else float(ema_decay)
         if ema_decay != 0.0 and not 0.0 < ema_decay < 1.0:
             raise ValueError(f"training.ema_decay={ema_decay} outside (0, 1) (absent or 0 switches the average off)")
+        # training.dp (privacy.py): every ValueError of the mode, the planned step count of target_epsilon included, before the device
+        from . import privacy as PV
+        cons = getattr(model, "_constraints", None)
+        world = torch.distributed.get_world_size() if torch.distributed.is_available() and torch.distributed.is_initialized() else 1
+        self.dp = PV.check_dp_config(tc.get("dp"), tc, is_vae=hasattr(model, "vae"),
+                                     constraints=cons is not None and (cons["w_pc"] != 0.0 or cons["w_me"] != 0.0), world=world)
+        if self.dp is not None and self.dp["noise_multiplier"] is None and int(tc["num_epochs"]) * len(train_loader) < 1:
+            raise ValueError("training.dp.target_epsilon needs at least one planned step (num_epochs x batches per epoch)")
         # what validate() returns: "loss" (the default: the reference's noise-driven validation loss, launch for launch) or "bound", the
         # mean bits per feature of the variational bound over the validation rows (likelihood.py) on training.validation_timesteps
         # strided timesteps -- a deterministic functional of the weights, comparable across objectives
@@ -716,6 +751,8 @@ class Trainer:
                 # compute side stream of train.hip, a non-default stream priority upsets this stack's hardware-queue assignment
                 self._comm_stream = torch.cuda.Stream()
         self.global_step = 0
+        if self.dp is not None:
+            self._dp_setup(tc)
         # device-resident epoch path (ResidentSplit): None = decide at the first epoch, False = off (the DataLoader is iterated)
         self.resident = None if tc.get("resident_dataset", True) else False
         self._resident_cache: dict = {}
@@ -732,7 +769,44 @@ class Trainer:
 
     def _option_state(self):
         m = self.model
-        return tuple(getattr(m, attr, None) for attr, _, _ in ENGINE_OPTIONS)
+        return tuple(getattr(m, attr, None) for attr, _, _ in ENGINE_OPTIONS) + (getattr(m, "dp_max_grad_norm", None),)
+
+    # -- differentially private training (privacy.py) -----------------------------
+    def _dp_setup(self, tc: dict):
+        from . import privacy as PV
+        dp = self.dp
+        n_train = len(getattr(self.train_loader, "dataset", self.train_loader))
+        bsz = getattr(self.train_loader, "batch_size", None) or tc["batch_size"]
+        dp["sample_rate"] = min(1.0, float(bsz) / max(n_train, 1))
+        if dp["noise_multiplier"] is None:
+            planned = int(tc["num_epochs"]) * len(self.train_loader)          # >= 1: checked in __init__, before the device
+            dp["noise_multiplier"] = PV.noise_multiplier_for(dp["target_epsilon"], dp["sample_rate"], planned, dp["delta"])
+            logger.info(f"training.dp: noise multiplier {dp['noise_multiplier']:.4f} for epsilon {dp['target_epsilon']} over {planned} steps")
+        if dp["seed"] is None:
+            dp["seed"] = _draw_seed()
+        self._dp_steps = 0
+        self._dp_rows = None                 # rows of the last step's batch (last_row_norms)
+        self.model.dp_max_grad_norm = dp["max_grad_norm"]
+        self.optimizer.max_norm = 0.0        # the per-patient clip bounds the mean's norm by C; clipping a noised gradient only rescales the noise
+        self.optimizer.dp = {"noise_multiplier": dp["noise_multiplier"], "max_grad_norm": dp["max_grad_norm"], "seed": dp["seed"]}
+        self._engine = self.model._engine()
+        self._opts = self._option_state()
+
+    def privacy_spent(self) -> dict:
+        """The (epsilon, delta) spent by the optimizer steps taken so far, for Poisson sampling at rate batch_size / len(train set)."""
+        if self.dp is None:
+            raise RuntimeError("privacy_spent() needs training.dp: this Trainer trains without a privacy guarantee")
+        from . import privacy as PV
+        dp = self.dp
+        return {"epsilon": PV.epsilon(dp["sample_rate"], dp["noise_multiplier"], self._dp_steps, dp["delta"]), "delta": dp["delta"],
+                "steps": self._dp_steps, "sample_rate": dp["sample_rate"], "noise_multiplier": dp["noise_multiplier"]}
+
+    def last_row_norms(self) -> torch.Tensor:
+        """Every patient's gradient norm in the most recent ``train_step`` (device float32, one per row): the number to choose
+        ``max_grad_norm`` by -- the median is the usual pick."""
+        if self.dp is None or self._dp_rows is None:
+            raise RuntimeError("last_row_norms() needs training.dp and a train_step")
+        return self.model.last_row_norms(self._dp_rows)
 
     def _bcast(self, t: torch.Tensor):
         """Broadcast from rank 0 in place (staged through the host when the backend is gloo)."""
@@ -825,6 +899,9 @@ class Trainer:
                 allreduce_buckets(self.flat.grad, self._slices, self._events, self._comm_stream)
         if comm_events is not None:
             comm_events[1].record()
+        if self.dp is not None:
+            self.optimizer.dp_rows = self._dp_rows = rows
+            self._dp_steps += 1
         self.optimizer.step()
         self.global_step += 1
         return loss
@@ -943,6 +1020,10 @@ class Trainer:
             if self._ema_depth:
                 raise RuntimeError("save_checkpoint inside ema_weights(): model_state_dict would hold the averaged weights")
             ckpt["ema_state_dict"] = self.ema.state_dict()
+        if self.dp is not None:
+            ckpt["dp_state"] = {"steps": int(self._dp_steps), "noise_multiplier": float(self.dp["noise_multiplier"]),
+                                "max_grad_norm": float(self.dp["max_grad_norm"]), "delta": float(self.dp["delta"]),
+                                "sample_rate": float(self.dp["sample_rate"])}
         torch.save(ckpt, self.save_dir / f"checkpoint_epoch_{epoch}.pt")
         if is_best:
             best = self.save_dir / "best_model.pt"
@@ -957,6 +1038,16 @@ class Trainer:
         if self._ema_depth:
             raise RuntimeError("load_checkpoint inside ema_weights()")
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
+        if self.dp is not None:
+            # a resumed run keeps its account; a file from a run without training.dp starts it at zero.  privacy_spent() prices every
+            # step at THIS run's sigma and sample rate, so steps taken under other values cannot be carried over: that would report a
+            # wrong, possibly too small, epsilon
+            saved = ckpt.get("dp_state", {})
+            for key in ("noise_multiplier", "sample_rate", "delta"):          # max_grad_norm scales signal and noise alike: epsilon does not see it
+                if key in saved and int(saved.get("steps", 0)) > 0 and abs(float(saved[key]) - float(self.dp[key])) > 1e-9 * abs(float(self.dp[key])):
+                    raise ValueError(f"{path} was trained with training.dp {key} = {saved[key]}, this run has {self.dp[key]}: the privacy "
+                                     f"account of its {saved['steps']} steps cannot be continued under other values")
+            dp_steps = int(saved.get("steps", 0))
         self.model.load_state_dict(ckpt["model_state_dict"])
         if not self.flat.is_current():
             raise RuntimeError("loading the checkpoint re-allocated the model's parameters; rebuild the Trainer")
@@ -969,6 +1060,8 @@ class Trainer:
                 with torch.no_grad():
                     self.ema.shadow.copy_(self.flat.flat)
                 self.ema.num_updates = 0
+        if self.dp is not None:
+            self._dp_steps = dp_steps
         self._engines_stale()
         return int(ckpt["epoch"])
 
@@ -989,7 +1082,11 @@ class Trainer:
             self.history["train_loss"].append(train_loss)
             val_loss = self.validate()
             self.history["val_loss"].append(val_loss)
-            logger.info(f"Train Loss: {train_loss:.4f} | Val Loss: {val_loss:.4f}")
+            spent = ""
+            if self.dp is not None:
+                ps = self.privacy_spent()
+                spent = f" | epsilon {ps['epsilon']:.3f} (delta {ps['delta']:g}, {ps['steps']} steps)"
+            logger.info(f"Train Loss: {train_loss:.4f} | Val Loss: {val_loss:.4f}{spent}")
             self.scheduler.step(val_loss)
             is_best = val_loss < best
             if is_best:
