@@ -301,7 +301,7 @@ int osd_sample_chain_guided(osd_handle *h, const float *cond, int64_t n, const f
  *   otherwise           osd_sample_chain_steps' plan and, host, known_level [n_steps][2] = (La_s, Ls_s), row 0 = (1, 0).  The library
  *                       folds nothing (ddim.py: known_level_table gathers the rows from the fp32 schedule buffers)
  *   null_cond_host == NULL  unguided (guidance_scale ignored); otherwise osd_sample_chain_guided's guided step, same output launch
- * One fused output_proj + posterior launch per step (EpiPosteriorKnown); per-layer kernels only, whatever "sampler" says
+ * One fused output_proj + posterior launch per step (EpiPosterior<POST_PLAIN, true>); per-layer kernels only, whatever "sampler" says
  * (osd_sample_engine(h, -1, 0) then reports 0; no warning, "chain_fallbacks" untouched); a row's result does not depend on the chunk
  * or shard it is in ("input_splitk" = 0).  OSD_F_TRAIN_MODE is allowed for unguided chains (the trunk is the unconstrained chain's).
  * OSD_EINVAL: known == NULL, ld_known < D, known_level[0] != (1, 0), a non-finite level, and everything osd_sample_chain_steps /
@@ -325,7 +325,7 @@ int osd_sample_chain_known(osd_handle *h, const float *cond, int64_t n, const fl
  *   x'  = fmaf(E, x0c, fmaf(F, x, C*z))            = sqrt(abar')*x0c + dir*(x - sqrt(abar)*x0c)/sqrt(1-abar) + sigma*z
  * The direction term uses the eps the CLIPPED x0 implies, not the network's.  Row 0 is (P, Q, 1, 0) with C_0 = 0, so x' = x0c bit for
  * bit: every returned element lies inside [lo, hi] exactly; mut_mask_out stays (x_out > 0.5).  Clamping the state x' instead is another
- * (wrong) algorithm, which is why this is an epilogue of the output_proj launch (EpiPosteriorClip, csrc/epilogues.h) and no pass of
+ * (wrong) algorithm, which is why this is an epilogue of the output_proj launch (EpiPosterior<POST_CLIP>, csrc/epilogues.h) and no pass of
  * its own.  Arguments and checks of osd_sample_chain_known, except:
  *   known == NULL       nothing is observed (known_level / ld_known ignored); otherwise observed elements are overwritten after the
  *                       clipped update with osd_sample_chain_known's expressions and draw rule (an observation outside the bounds
@@ -362,7 +362,7 @@ int osd_sample_chain_clipped(osd_handle *h, const float *cond, int64_t n, const 
  *   x'  = fmaf(G, x0c, fmaf(F, x, H*x0c_prev))     x0c_prev: the x0c of the step run before this one (never read where H = 0)
  * G + H and F are the E and F of osd_sample_chain_clipped at eta = 0, so n_steps <= 2 is that chain.  Row 0 returns x0c bit for bit:
  * every returned element lies inside [lo, hi] exactly; mut_mask_out stays (x_out > 0.5).  Deterministic after x_T: there is no z, and
- * no step_coef.  The history is an epilogue stream of the output_proj launch (EpiPosteriorHist, csrc/epilogues.h) because neither
+ * no step_coef.  The history is an epilogue stream of the output_proj launch (EpiPosterior<POST_HIST>, csrc/epilogues.h) because neither
  * x0c nor eps is ever written by it.  Arguments and checks of osd_sample_chain_clipped, except:
  *   timesteps           required: a solver needs a plan (NULL is OSD_EINVAL)
  *   x0_coef             host [n_steps][4] = (P_s, Q_s, G_s, F_s), row 0 = (., ., 1, 0);  hist_coef: host [n_steps] = H_s,

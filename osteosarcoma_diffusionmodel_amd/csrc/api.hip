@@ -602,7 +602,7 @@ static int fold_schedule(osd_handle* h) {
   const int kind = h->pred_type;
   // fold the reference's six per-step scalars into x' = A*x + B*eps + C*z (see EpiPosterior)
   std::vector<float> abc((size_t)a.T * 4, 0.f);
-  // ... and, for the chain that clips x0 (EpiPosteriorClip), the same scalars unfolded at x0: x0 = P*x + Q*eps, x' = E*x0 + F*x + C*z
+  // ... and, for the chain that clips x0 (EpiPosterior<POST_CLIP>), the same scalars unfolded at x0: x0 = P*x + Q*eps, x' = E*x0 + F*x + C*z
   h->sched_x0_coef.assign((size_t)a.T * 4, 0.f);
   std::vector<float> pq((size_t)a.T * 2, 0.f);
   for (int t = 0; t < a.T; ++t) {
@@ -864,7 +864,7 @@ int osd_p_sample_step(osd_handle* h, const float* x_t, int32_t t, const float* c
   in.train = (flags & OSD_F_TRAIN_MODE) != 0; in.seed = seed; in.row_offset = (uint32_t)row_offset; in.drop_step = (uint32_t)t;
   OSD_TRY(run_trunk(h, s, ws, in));
   GemmArgs g = output_proj_args(h, ws, n);
-  EpiPosterior::Args ea{};
+  PosteriorArgs ea{};
   ea.bias = h->params[a.pm.out_b]; ea.xin = x_t; ea.ldx = a.D; ea.xout = x_out; ea.ldo = a.D; ea.coef = h->d_coef;
   ea.t_dev = nullptr; ea.t_imm = t; ea.z = z; ea.ldzz = a.D; ea.z_step_stride = 0; ea.t_first = t;
   ea.seed = seed; ea.row_offset = (uint32_t)row_offset; ea.mut_mask = nullptr; ea.mutation_dim = 0;
@@ -961,16 +961,17 @@ static int chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r
     // guidance on the last hidden activation, in place over the conditional rows: output_proj + posterior then run once, on m rows
     if (gd) OSD_HIP(launch_guide_combine(s, ws.out[a.n_blocks - 1], m, a.block_out[a.n_blocks - 1], gd->w));
     GemmArgs g = output_proj_args(h, ws, m, padded);
-    EpiPosterior::Args ea{};
+    PosteriorArgs ea{};
     ea.bias = padded ? h->b_out_packed : h->params[a.pm.out_b]; ea.xin = x; ea.ldx = ldx; ea.xout = x; ea.ldo = ldx; ea.coef = job.plan.coef;
     ea.t_dev = sl.t_dev; ea.t_imm = 0;
     ea.z = job.noises; ea.ldzz = D; ea.z_step_stride = (long long)job.n_total * D; ea.t_first = S - 1;
     ea.seed = job.seed; ea.row_offset = roff;
     ea.mut_mask = job.mut_mask_out; ea.mutation_dim = job.mutation_dim;
-    if (ms) OSD_HIP(launch_posterior_hist(s, g, PosteriorHistArgs{PosteriorClipArgs{ea, cl->bounds, cl->bounds + cl->ld, cl->x0_coef, kn ? known : nullptr, ldk, kn ? kn->level : nullptr},
-                                                                  hist, ldx, ms->hist_coef}));
-    else if (cl) OSD_HIP(launch_posterior_clip(s, g, PosteriorClipArgs{ea, cl->bounds, cl->bounds + cl->ld, cl->x0_coef, kn ? known : nullptr, ldk, kn ? kn->level : nullptr}));
-    else if (kn) OSD_HIP(launch_posterior_known(s, g, EpiPosteriorKnown::Args{ea, known, ldk, kn->level}));
+    if (cl) {
+      const PosteriorClipArgs ca{ea, cl->bounds, cl->bounds + cl->ld, cl->x0_coef, kn ? known : nullptr, ldk, kn ? kn->level : nullptr};
+      if (ms) OSD_HIP(launch_posterior(s, g, PosteriorHistArgs{ca, hist, ldx, ms->hist_coef}));
+      else OSD_HIP(launch_posterior(s, g, ca));
+    } else if (kn) OSD_HIP(launch_posterior(s, g, PosteriorKnownArgs{ea, known, ldk, kn->level}));
     else OSD_HIP(launch_posterior(s, g, ea));
     OSD_HIP(launch_add_int(s, sl.t_dev, -1));
     return OSD_OK;
@@ -1359,7 +1360,7 @@ int osd_profile_step(osd_handle* h, const float* cond, int64_t n, int reps, floa
     if (e == hipSuccess) rc = run_trunk(h, s, ws, in);
     if (rc == OSD_OK && e == hipSuccess) {
       GemmArgs g = output_proj_args(h, ws, n);
-      EpiPosterior::Args ea{};
+      PosteriorArgs ea{};
       ea.bias = h->params[a.pm.out_b]; ea.xin = x; ea.ldx = a.D; ea.xout = x; ea.ldo = a.D; ea.coef = h->d_coef;
       ea.t_imm = a.T / 2; ea.ldzz = a.D; ea.seed = 1; ea.t_first = a.T / 2;
       e = launch_posterior(s, g, ea);

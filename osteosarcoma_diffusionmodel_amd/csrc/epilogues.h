@@ -8,6 +8,7 @@
 #include "gemm.h"
 #include "rng.h"
 #include "xpose.h"
+#include <type_traits>
 
 namespace osd {
 
@@ -30,13 +31,6 @@ __device__ __forceinline__ float swap_halves(float v) {
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// Hook called by every epilogue after each unit of work (an accumulator quad, a group statistic): a kernel whose
-// epilogue waves must keep rendezvousing with other waves passes a Sync that turns some calls into barriers; the
-// product kernels pass this no-op.
-struct NoSync {
-  __device__ __forceinline__ void tick() {}
-};
-
 // ---- bias (+ optional SiLU, + optional accumulate into out) -----------------------
 template <bool SILU, bool ACCUM>
 struct EpiBias {
@@ -57,9 +51,8 @@ struct EpiBias {
         r.bias[fb][q] = a.bias ? ldq<FAST>(a.bias, fw + 32 * fb + 8 * q + 4 * h, F) : make_float4(0.f, 0.f, 0.f, 0.f);
     return r;
   }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
+  template <int NFB, int NPB, bool FAST>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     const int l31 = lane & 31, h = lane >> 5;
     OSD_FOR_QUADS(fb, pb, q) {
       const int f = fw + 32 * fb + 8 * q + 4 * h;
@@ -71,7 +64,6 @@ struct EpiBias {
       if (ACCUM) { const float4 o = ldq<FAST>(row, f, F); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
       if (SILU) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
       if (p < P) stq<FAST>(row, f, F, v);
-      sync.tick();
     }
   }
 };
@@ -104,9 +96,8 @@ struct EpiInput {
       for (int q = 0; q < 4; ++q) r.bias[fb][q] = ldq<FAST>(a.bias, fw + 32 * fb + 8 * q + 4 * h, F);
     return r;
   }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
+  template <int NFB, int NPB, bool FAST>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     const int l31 = lane & 31, h = lane >> 5;
     const int t_shared = a.t_dev ? *a.t_dev : a.t_imm;
 #pragma unroll
@@ -129,7 +120,6 @@ struct EpiInput {
           v.z = ((acc[fb][pb][4 * q + 2] + bv.z) + tv.z) + cv.z;
           v.w = ((acc[fb][pb][4 * q + 3] + bv.w) + tv.w) + cv.w;
           if (p < P) stq<FAST>(orow, f, F, v);
-          sync.tick();
         }
     }
   }
@@ -172,9 +162,8 @@ struct EpiInputGuided {
       for (int q = 0; q < 4; ++q) r.bias[fb][q] = ldq<FAST>(a.bias, fw + 32 * fb + 8 * q + 4 * h, F);
     return r;
   }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
+  template <int NFB, int NPB, bool FAST>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     const int l31 = lane & 31, h = lane >> 5;
     const int t_shared = a.t_dev ? *a.t_dev : a.t_imm;
 #pragma unroll
@@ -202,7 +191,6 @@ struct EpiInputGuided {
             stq<FAST>(orow, f, F, v);
             stq<FAST>(orow + a.half, f, F, u);
           }
-          sync.tick();
         }
     }
   }
@@ -253,9 +241,8 @@ struct EpiGnSilu {
       }
     return r;
   }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
+  template <int NFB, int NPB, bool FAST>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     static_assert(NFB * 32 >= GW, "wave must own whole groups");
     constexpr int RPG = (GW >= 8) ? GW / 2 : 4;   // registers of one group in this lane
     constexpr int NG = NFB * 16 / RPG;
@@ -291,7 +278,6 @@ struct EpiGnSilu {
         if (GW >= 8) qs += swap_halves(qs);
         mean[g] = m;
         rstd[g] = 1.0f / sqrtf(qs * (1.0f / GW) + GN_EPS);
-        sync.tick();
       }
       float* orow = a.out + (size_t)pc * a.ldo;
 #pragma unroll
@@ -326,7 +312,6 @@ struct EpiGnSilu {
             y.w *= (u01(r.w) >= a.p_drop) ? a.keep_scale : 0.f;
           }
           if (prow) stq<FAST>(orow, f, F, y);
-          sync.tick();
         }
     }
   }
@@ -377,9 +362,8 @@ struct EpiGnBwd {
       }
     return r;
   }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
+  template <int NFB, int NPB, bool FAST>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     static_assert(GW >= 8 && NFB * 32 >= GW, "wave must own whole groups");
     constexpr int RPG = GW / 2;                 // registers of one group in this lane
     constexpr int NG = NFB * 16 / RPG;
@@ -464,43 +448,121 @@ struct EpiGnBwd {
             o[e] = rstd * (acc[fb][pb][r] * gm[e] - s1[g] - zh[fb][r] * s2[g]);
           }
           if (prow) stq<FAST>(gzrow, f, F, make_float4(o[0], o[1], o[2], o[3]));
-          sync.tick();
         }
     }
   }
 };
 
-// ---- output_proj fused with the DDPM posterior update (models/diffusion.py:398-425) ----
-// eps = acc + bias; the reference's x0 = (x - c0*eps)/c1, mean = c2*x0/c3 + c4*x/c3, x' = mean + c5*z
-// is linear in (x, eps, z):   x' = A_t*x + B_t*eps + C_t*z   with
+// ---- output_proj fused with one step of the reverse chain: EpiPosterior<MODE, KNOWN> ----
+// One quad walk (apply) serves every per-layer sampler.  MODE picks the element formula, KNOWN adds the overwrite of observed values;
+// both are compile-time, so each of the six instantiations is its own kernel with no runtime switch.  t is the plan's step counter.
+//
+// POST_PLAIN, the DDPM / DDIM posterior (models/diffusion.py:398-425).  eps = acc + bias; the reference's x0 = (x - c0*eps)/c1,
+// mean = c2*x0/c3 + c4*x/c3, x' = mean + c5*z is linear in (x, eps, z):   x' = A_t*x + B_t*eps + C_t*z   with
 //   A_t = c4/c3 + c2/(c1*c3),  B_t = -c0*c2/(c1*c3),  C_t = c5        (t > 0)
 //   A_0 = 1/c1,                B_0 = -c0/c1,          C_0 = 0         (t == 0: x' = x0)
-// A, B, C are formed in double on the host from the reference's fp32 scalars and rounded once
-// (osd_set_schedule), which replaces three IEEE divides per element by two FMAs; the result
-// differs from the reference's op order by a few ulp of the same intermediate magnitudes.
+// A, B, C are formed in double on the host from the reference's fp32 scalars and rounded once (osd_set_schedule), which replaces
+// three IEEE divides per element by two FMAs; the result differs from the reference's op order by a few ulp of the same
+// intermediate magnitudes.  coef [T][4] = (A_t, B_t, C_t, 0).  A step whose C is 0 (DDIM at eta = 0, and t == 0) draws no z: the
+// Philox generator bounds this launch.
+//
+// KNOWN, sampling around observed values (the replacement method).  known [P][F]: a finite value is an
+// observation of that element, NaN leaves it to the chain.  After the MODE's update, per element:
+//   known element:  x' = La_t * known + Ls_t * z   (t > 0);   x' = known, bit for bit   (t == 0)
+// level [S][2] = (La_t, Ls_t) = (sqrt(abar), sqrt(1 - abar)) of the timestep the step arrives at, (1, 0) at t = 0.  z is the step's
+// posterior draw at the element's own address -- a replaced element has no other use for it -- so every step with t > 0 draws, also
+// where C_t = 0; a quad without an observation has no use for the draw then, and its lanes skip the generator.  The free elements add
+// the zero the unconstrained chain adds there (a select on the wave-uniform C_t, not a product with the draw), and an all-NaN `known`
+// gives the unconstrained chain's bits.
+//
+// POST_CLIP, the predicted x0 clipped to per-feature bounds.  x0coef [S][4] = (P_t, Q_t, E_t, F_t); C_t is
+// slot 2 of the coef row.  Per element:
+//   x0  = fmaf(P, x, Q*eps)                        P = 1/sqrt(abar), Q = -sqrt(1-abar)/sqrt(abar)
+//   x0c = fminf(fmaxf(x0, lo[f]), hi[f])           -inf / +inf leave a side free
+//   x'  = fmaf(E, x0c, fmaf(F, x, C*z))            the direction term uses the eps the CLIPPED x0 implies, (x - sqrt(abar) x0c)/sqrt(1-abar)
+// Row 0 is (P, Q, 1, 0) with C = 0: x' = x0c bit for bit, so every returned element lies inside [lo, hi].  C*z is the select on the
+// wave-uniform C.  lo / hi depend on the feature only: loaded next to the x_t quads (2 x 16 float4 per wave tile held from before the
+// K loop, the way the bias is, do not fit).
+//
+// POST_HIST, the DPM-Solver++(2M) multistep update (Lu et al. 2022).  POST_CLIP's deterministic step plus one
+// term: the previous step's clipped x0, kept in hist [P][ldh] (ldh = ldx, the state's row stride), which the lane that owns an element
+// reads and rewrites in place exactly as it does x.  x0coef [S][4] = (P_t, Q_t, G_t, F_t), hcoef [S] = H_t.  Per element:
+//   hp  = hist[p][f];   hist[p][f] = x0c           the clipped network prediction, not the value after the `known` overwrite
+//   x'  = fmaf(G, x0c, fmaf(F, x, H*hp))
+// H is wave-uniform: where it is 0 (the first step run, whose history is the zeroed buffer, and t = 0) the read is skipped and hp = 0;
+// the store is skipped at t = 0.  Row 0 is (P, Q, 1, 0) with H = 0: x' = x0c bit for bit.  No z: the generator runs only under KNOWN,
+// for quads that hold an observation, at t > 0.  coef is not read.
+enum PostMode { POST_PLAIN, POST_CLIP, POST_HIST };
+
+struct PosteriorArgs {
+  const float* bias;
+  const float* xin; int ldx;
+  float* xout; int ldo;
+  const float* coef;              // dev [T][4] = (A_t, B_t, C_t, 0)
+  const int* t_dev; int t_imm;
+  const float* z; int ldzz;       // injected noise for draw 0 (t = t_first), [P][F]; null -> Philox
+  long long z_step_stride; int t_first;   // draw for step t sits at z + (t_first - t) * stride
+  uint64_t seed; uint32_t row_offset;
+  float* mut_mask; int mutation_dim;   // written at t == 0 when non-null: (x' > 0.5)
+};
+struct PosteriorKnownArgs {
+  PosteriorArgs p;
+  const float* known; int ldk;    // [P][F], row stride ldk; NaN = free
+  const float* level;             // dev [S][2] = (La_t, Ls_t)
+};
+struct PosteriorClipArgs {
+  PosteriorArgs p;
+  const float* lo; const float* hi;     // dev [F] each
+  const float* x0coef;                  // dev [S][4] = (P_t, Q_t, E_t, F_t)
+  const float* known; int ldk;          // KNOWN: [P][F], row stride ldk; NaN = free
+  const float* level;                   // KNOWN: dev [S][2] = (La_t, Ls_t)
+};
+struct PosteriorHistArgs {
+  PosteriorClipArgs c;
+  float* hist; int ldh;                 // [P][ldh]
+  const float* hcoef;                   // dev [S] = H_t
+};
+// the nested parts of an argument struct: the common fields, the clip fields, and the struct that holds known / ldk / level
+__host__ __device__ inline const PosteriorArgs& post_base(const PosteriorArgs& a) { return a; }
+__host__ __device__ inline const PosteriorArgs& post_base(const PosteriorKnownArgs& a) { return a.p; }
+__host__ __device__ inline const PosteriorArgs& post_base(const PosteriorClipArgs& a) { return a.p; }
+__host__ __device__ inline const PosteriorArgs& post_base(const PosteriorHistArgs& a) { return a.c.p; }
+__host__ __device__ inline const PosteriorClipArgs& post_clip(const PosteriorClipArgs& a) { return a; }
+__host__ __device__ inline const PosteriorClipArgs& post_clip(const PosteriorHistArgs& a) { return a.c; }
+__host__ __device__ inline const PosteriorKnownArgs& post_known(const PosteriorKnownArgs& a) { return a; }
+__host__ __device__ inline const PosteriorClipArgs& post_known(const PosteriorClipArgs& a) { return a; }
+__host__ __device__ inline const PosteriorClipArgs& post_known(const PosteriorHistArgs& a) { return a.c; }
+
+// Quads requested ahead of their use; 0 = every x_t quad of the wave's tile before the first one is used (one latency, not sixteen;
+// 64 registers).  The numbers are what fits: the 128 x 128 LDS-DMA kernels sit at 236 - 254 of the 256 VGPRs that two waves per SIMD
+// allow.  Measured on that kernel:
+//   plain + known: all x_t quads with the known quads beside them do not fit 256 VGPRs; a block's x_t and known quads are 32 registers
+//   clip:          a whole block's x, lo, hi are 48 registers
+//   hist:          two quads' x, lo, hi, hist are 32
+//   clip + known, hist + known (the known quad rides along: 16 and 20 registers a quad): a whole block's 64 spill 31 VGPRs and
+//                  half a block's 32 still spill one
+constexpr int post_quads_ahead(PostMode m, bool known) { return m == POST_PLAIN ? (known ? 4 : 0) : known ? 1 : m == POST_CLIP ? 4 : 2; }
+
+template <PostMode MODE, bool KNOWN>
 struct EpiPosterior {
-  static constexpr bool COUNTED_STORES = true;
+  static constexpr bool COUNTED_STORES = true;     // one x' quad per accumulator quad and, POST_HIST at t > 0, one history quad more: never fewer
   static constexpr bool XBUF = false;
   template <class A> static __device__ __forceinline__ void slice(A&, int) {}
-  struct Args {
-    const float* bias;
-    const float* xin; int ldx;
-    float* xout; int ldo;
-    const float* coef;              // dev [T][4] = (A_t, B_t, C_t, 0)
-    const int* t_dev; int t_imm;
-    const float* z; int ldzz;       // injected noise for draw 0 (t = t_first), [P][F]; null -> Philox
-    long long z_step_stride; int t_first;   // draw for step t sits at z + (t_first - t) * stride
-    uint64_t seed; uint32_t row_offset;
-    float* mut_mask; int mutation_dim;   // written at t == 0 when non-null: (x' > 0.5)
-  };
-  // a step whose C is 0 (DDIM at eta = 0, and t == 0) draws no z: the Philox generator bounds this launch
-  static bool fast_ok(const Args& a, int F) {
-    return F % 4 == 0 && al16(a.bias) && al16(a.xin) && al16(a.xout) && a.ldx % 4 == 0 && a.ldo % 4 == 0 &&
-           (!a.z || (al16(a.z) && a.ldzz % 4 == 0 && a.z_step_stride % 4 == 0));
+  typedef std::conditional_t<MODE == POST_HIST, PosteriorHistArgs,
+                             std::conditional_t<MODE == POST_CLIP, PosteriorClipArgs, std::conditional_t<KNOWN, PosteriorKnownArgs, PosteriorArgs>>> Args;
+  static bool fast_ok(const Args& args, int F) {
+    const PosteriorArgs& a = post_base(args);
+    bool ok = F % 4 == 0 && al16(a.bias) && al16(a.xin) && al16(a.xout) && a.ldx % 4 == 0 && a.ldo % 4 == 0 &&
+              (!a.z || (al16(a.z) && a.ldzz % 4 == 0 && a.z_step_stride % 4 == 0));
+    if constexpr (MODE != POST_PLAIN) ok = ok && al16(post_clip(args).lo) && al16(post_clip(args).hi);
+    if constexpr (KNOWN) ok = ok && al16(post_known(args).known) && post_known(args).ldk % 4 == 0;
+    if constexpr (MODE == POST_HIST) ok = ok && al16(args.hist) && args.ldh % 4 == 0;
+    return ok;
   }
   template <int NFB> struct Pre { float4 bias[NFB][4]; };
   template <int NFB, bool FAST>
-  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& args, int fw, int lane, int F) {
+    const PosteriorArgs& a = post_base(args);
     Pre<NFB> r;
     const int h = lane >> 5;
 #pragma unroll
@@ -509,21 +571,35 @@ struct EpiPosterior {
       for (int q = 0; q < 4; ++q) r.bias[fb][q] = ldq<FAST>(a.bias, fw + 32 * fb + 8 * q + 4 * h, F);
     return r;
   }
-  // WIDE: every x_t quad of the wave's tile is requested before the first one is used (one latency, not sixteen; 64
-  // registers).  !WIDE (the chain kernel, which has fewer registers to spare): the four quads of one 32 x 32 block at a time.
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync, bool WIDE = true>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
+  template <int NFB, int NPB, bool FAST>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& args, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
+    constexpr bool PLAIN = MODE == POST_PLAIN, CLIP = MODE == POST_CLIP, HIST = MODE == POST_HIST;
+    constexpr bool ALL = post_quads_ahead(MODE, KNOWN) == 0;
+    constexpr int QB = ALL ? 4 : post_quads_ahead(MODE, KNOWN);
+    const PosteriorArgs& a = post_base(args);
     const int l31 = lane & 31, h = lane >> 5;
     const int t = a.t_dev ? *a.t_dev : a.t_imm;
-    const float* c = a.coef + 4 * t;
-    const float cA = c[0], cB = c[1], cC = c[2];
+    // the step's table rows (wave-uniform).  PLAIN: A, B, C;  CLIP: C and (P, Q, E, F);  HIST: (P, Q, G, F) and H
+    float cA = 0.f, cB = 0.f, cC = 0.f, cP = 0.f, cQ = 0.f, cE = 0.f, cF = 0.f, cH = 0.f;
+    if constexpr (PLAIN) {
+      const float* c = a.coef + 4 * t;
+      cA = c[0]; cB = c[1]; cC = c[2];
+    } else {
+      if constexpr (CLIP) cC = a.coef[4 * t + 2];
+      const float* c = post_clip(args).x0coef + 4 * t;
+      cP = c[0]; cQ = c[1]; cE = c[2]; cF = c[3];
+      if constexpr (HIST) cH = args.hcoef[t];
+    }
+    const bool hz = cH != 0.f;           // uniform: H = 0 skips the history read
+    float La = 1.f, Ls = 0.f;
+    if constexpr (KNOWN) { La = post_known(args).level[2 * t]; Ls = post_known(args).level[2 * t + 1]; }
+    const bool cz = cC != 0.f;           // uniform: C = 0 draws no z for the free elements
     const float* zbase = a.z ? a.z + (long long)(a.t_first - t) * a.z_step_stride : nullptr;
-    float4 xq[WIDE ? NFB : 1][WIDE ? NPB : 1][4];
-    if constexpr (WIDE) {
+    float4 xall[ALL ? NFB : 1][ALL ? NPB : 1][4];
+    if constexpr (ALL) {
       OSD_FOR_QUADS(fb, pb, q) {
         const int p = pw + 32 * pb + l31;
-        xq[fb][pb][q] = ldq<FAST>(a.xin + (size_t)(p < P ? p : P - 1) * a.ldx, fw + 32 * fb + 8 * q + 4 * h, F);
+        xall[fb][pb][q] = ldq<FAST>(a.xin + (size_t)(p < P ? p : P - 1) * a.ldx, fw + 32 * fb + 8 * q + 4 * h, F);
       }
     }
 #pragma unroll
@@ -532,347 +608,84 @@ struct EpiPosterior {
       for (int pb = 0; pb < NPB; ++pb) {
         const int p = pw + 32 * pb + l31;
         const int pc = p < P ? p : P - 1;
-        if constexpr (!WIDE) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) xq[0][0][q] = ldq<FAST>(a.xin + (size_t)pc * a.ldx, fw + 32 * fb + 8 * q + 4 * h, F);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int f = fw + 32 * fb + 8 * q + 4 * h;
-          const bool ok = p < P && f < F;
-          const float4 bv = pre.bias[fb][q];
-          const float4 x = xq[WIDE ? fb : 0][WIDE ? pb : 0][q];
-          const float e[4] = {acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w};
-          const float xv[4] = {x.x, x.y, x.z, x.w};
-          float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (t > 0 && cC != 0.f) {          // C = 0 (eta = 0 DDIM steps; t = 0): no draw.  Uniform: the step's table row
-            if (zbase) zz = ldq<FAST>(zbase + (size_t)pc * a.ldzz, f, F);
-            else zz = randn4(a.seed, a.row_offset + (uint32_t)p, (uint32_t)(f >> 2), (uint32_t)t, TAG_POSTERIOR);
-          }
-          const float zv[4] = {zz.x, zz.y, zz.z, zz.w};
-          float o[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = fmaf(cA, xv[r], fmaf(cB, e[r], cC * zv[r]));
-          if (t == 0 && a.mut_mask && ok && f < a.mutation_dim) {
-            float* mrow = a.mut_mask + (size_t)p * a.mutation_dim;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (f + r < a.mutation_dim) mrow[f + r] = (o[r] > 0.5f) ? 1.0f : 0.0f;
-          }
-          if (p < P) stq<FAST>(a.xout + (size_t)pc * a.ldo, f, F, make_float4(o[0], o[1], o[2], o[3]));
-          sync.tick();
-        }
-      }
-  }
-};
-
-// ---- output_proj + posterior update around observed values (the replacement method) ----
-// known [P][F]: a finite value is an observation of that element, NaN leaves it to the chain.  Per element of step t (the plan's
-// step counter, as in EpiPosterior):
-//   free  element:  x' = A_t x + B_t eps + C_t z                       EpiPosterior's arithmetic, operation for operation
-//   known element:  x' = La_t * known + Ls_t * z   (t > 0);   x' = known, bit for bit   (t == 0)
-// level [S][2] = (La_t, Ls_t) = (sqrt(abar), sqrt(1 - abar)) of the timestep the step arrives at, (1, 0) at t = 0.  z is the step's
-// posterior draw at the element's own address -- a replaced element has no other use for it -- so every step with t > 0 draws, also
-// where C_t = 0; the free elements then add the zero EpiPosterior adds (a select on the wave-uniform C_t, not a product with the
-// draw), and an all-NaN `known` gives the unconstrained chain's bits.
-// The !WIDE form only: the x_t and the known quads of one 32 x 32 block at a time (32 registers).  All x_t quads up front
-// (EpiPosterior's WIDE form, 64 registers) with the known quads beside them do not fit the 128 x 128 tile's 256 VGPRs.
-struct EpiPosteriorKnown {
-  static constexpr bool COUNTED_STORES = true;
-  static constexpr bool XBUF = false;
-  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
-  struct Args {
-    EpiPosterior::Args p;
-    const float* known; int ldk;    // [P][F], row stride ldk; NaN = free
-    const float* level;             // dev [S][2] = (La_t, Ls_t)
-  };
-  static bool fast_ok(const Args& a, int F) { return EpiPosterior::fast_ok(a.p, F) && al16(a.known) && a.ldk % 4 == 0; }
-  template <int NFB> using Pre = EpiPosterior::Pre<NFB>;
-  template <int NFB, bool FAST>
-  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
-    return EpiPosterior::prefetch<NFB, FAST>(a.p, fw, lane, F);
-  }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& ak, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
-    const EpiPosterior::Args& a = ak.p;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int t = a.t_dev ? *a.t_dev : a.t_imm;
-    const float* c = a.coef + 4 * t;
-    const float cA = c[0], cB = c[1], cC = c[2];
-    const float La = ak.level[2 * t], Ls = ak.level[2 * t + 1];
-    const float* zbase = a.z ? a.z + (long long)(a.t_first - t) * a.z_step_stride : nullptr;
-#pragma unroll
-    for (int fb = 0; fb < NFB; ++fb)
-#pragma unroll
-      for (int pb = 0; pb < NPB; ++pb) {
-        const int p = pw + 32 * pb + l31;
-        const int pc = p < P ? p : P - 1;
-        float4 xq[4], kq[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          xq[q] = ldq<FAST>(a.xin + (size_t)pc * a.ldx, fw + 32 * fb + 8 * q + 4 * h, F);
-          kq[q] = ldq<FAST>(ak.known + (size_t)pc * ak.ldk, fw + 32 * fb + 8 * q + 4 * h, F);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int f = fw + 32 * fb + 8 * q + 4 * h;
-          const bool ok = p < P && f < F;
-          const float4 bv = pre.bias[fb][q];
-          const float e[4] = {acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w};
-          const float xv[4] = {xq[q].x, xq[q].y, xq[q].z, xq[q].w};
-          const float kv[4] = {kq[q].x, kq[q].y, kq[q].z, kq[q].w};
-          const bool cz = cC != 0.f;         // uniform: the step's table row
-          // every step but the last draws, also where C = 0: the known elements use z there.  A quad without an observation has no
-          // use for the draw then, and its lanes skip the generator (which bounds this launch)
-          const bool any_known = kv[0] == kv[0] || kv[1] == kv[1] || kv[2] == kv[2] || kv[3] == kv[3];
-          float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (t > 0 && (cz || any_known)) {
-            if (zbase) zz = ldq<FAST>(zbase + (size_t)pc * a.ldzz, f, F);
-            else zz = randn4(a.seed, a.row_offset + (uint32_t)p, (uint32_t)(f >> 2), (uint32_t)t, TAG_POSTERIOR);
-          }
-          const float zv[4] = {zz.x, zz.y, zz.z, zz.w};
-          float o[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float fr = fmaf(cA, xv[r], fmaf(cB, e[r], cC * (cz ? zv[r] : 0.f)));
-            const float kn = t > 0 ? fmaf(La, kv[r], Ls * zv[r]) : kv[r];
-            o[r] = (kv[r] == kv[r]) ? kn : fr;      // NaN: free
-          }
-          if (t == 0 && a.mut_mask && ok && f < a.mutation_dim) {
-            float* mrow = a.mut_mask + (size_t)p * a.mutation_dim;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (f + r < a.mutation_dim) mrow[f + r] = (o[r] > 0.5f) ? 1.0f : 0.0f;
-          }
-          if (p < P) stq<FAST>(a.xout + (size_t)pc * a.ldo, f, F, make_float4(o[0], o[1], o[2], o[3]));
-          sync.tick();
-        }
-      }
-  }
-};
-
-// ---- output_proj + posterior update with the predicted x0 clipped to per-feature bounds ----
-// x0coef [S][4] = (P_t, Q_t, E_t, F_t); C_t is slot 2 of EpiPosterior's coef row.  Per element of step t:
-//   eps = acc + bias
-//   x0  = fmaf(P, x, Q*eps)                        P = 1/sqrt(abar), Q = -sqrt(1-abar)/sqrt(abar)
-//   x0c = fminf(fmaxf(x0, lo[f]), hi[f])           -inf / +inf leave a side free
-//   x'  = fmaf(E, x0c, fmaf(F, x, C*z))            the direction term uses the eps the CLIPPED x0 implies, (x - sqrt(abar) x0c)/sqrt(1-abar)
-// Row 0 is (P, Q, 1, 0) with C = 0: x' = x0c bit for bit, so every returned element lies inside [lo, hi].  C*z is a select on the
-// wave-uniform C, as in EpiPosteriorKnown.  lo / hi depend on the feature only: loaded per 32 x 32 block next to the x_t quads (2 x 16
-// float4 per wave tile held from before the K loop, the way the bias is, do not fit).  The !WIDE form only.
-// KNOWN: observed elements (EpiPosteriorKnown's `known`, NaN = free) are overwritten after the clipped update with that epilogue's
-// expressions and draw rule: every step with t > 0 draws, and the lanes of a quad without an observation skip the generator where C = 0.
-struct PosteriorClipArgs {
-  EpiPosterior::Args p;
-  const float* lo; const float* hi;     // dev [F] each
-  const float* x0coef;                  // dev [S][4] = (P_t, Q_t, E_t, F_t)
-  const float* known; int ldk;          // KNOWN: [P][F], row stride ldk; NaN = free
-  const float* level;                   // KNOWN: dev [S][2] = (La_t, Ls_t)
-};
-template <bool KNOWN>
-struct EpiPosteriorClip {
-  static constexpr bool COUNTED_STORES = true;
-  static constexpr bool XBUF = false;
-  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
-  typedef PosteriorClipArgs Args;
-  static bool fast_ok(const Args& a, int F) {
-    return EpiPosterior::fast_ok(a.p, F) && al16(a.lo) && al16(a.hi) && (!KNOWN || (al16(a.known) && a.ldk % 4 == 0));
-  }
-  template <int NFB> using Pre = EpiPosterior::Pre<NFB>;
-  template <int NFB, bool FAST>
-  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
-    return EpiPosterior::prefetch<NFB, FAST>(a.p, fw, lane, F);
-  }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& ac, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
-    const EpiPosterior::Args& a = ac.p;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int t = a.t_dev ? *a.t_dev : a.t_imm;
-    const float cC = a.coef[4 * t + 2];
-    const float* c = ac.x0coef + 4 * t;
-    const float cP = c[0], cQ = c[1], cE = c[2], cF = c[3];
-    float La = 1.f, Ls = 0.f;
-    if constexpr (KNOWN) { La = ac.level[2 * t]; Ls = ac.level[2 * t + 1]; }
-    const bool cz = cC != 0.f;           // uniform: the step's table row
-    const float* zbase = a.z ? a.z + (long long)(a.t_first - t) * a.z_step_stride : nullptr;
-    // quads requested ahead of their use: a whole block's (x, lo, hi: 48 registers), or -- KNOWN, whose known quad rides along -- one
-    // quad's (16): in the 128 x 128 LDS-DMA kernel a whole block's 64 spill 31 VGPRs and half a block's 32 still spill one
-    constexpr int QB = KNOWN ? 1 : 4;
-#pragma unroll
-    for (int fb = 0; fb < NFB; ++fb)
-#pragma unroll
-      for (int pb = 0; pb < NPB; ++pb) {
-        const int p = pw + 32 * pb + l31;
-        const int pc = p < P ? p : P - 1;
-        float4 xq[4], lq[4], hq[4], kq[KNOWN ? 4 : 1];
+        float* hrow = nullptr;
+        if constexpr (HIST) hrow = args.hist + (size_t)pc * args.ldh;
+        float4 xq[4], lq[4], hq[4], pq[4], kq[4];
 #pragma unroll
         for (int q0 = 0; q0 < 4; q0 += QB) {
+          if constexpr (!ALL) {
 #pragma unroll
-        for (int q = q0; q < q0 + QB; ++q) {
-          const int f = fw + 32 * fb + 8 * q + 4 * h;
-          xq[q] = ldq<FAST>(a.xin + (size_t)pc * a.ldx, f, F);
-          lq[q] = ldq<FAST>(ac.lo, f, F);
-          hq[q] = ldq<FAST>(ac.hi, f, F);
-          if constexpr (KNOWN) kq[q] = ldq<FAST>(ac.known + (size_t)pc * ac.ldk, f, F);
-        }
-#pragma unroll
-        for (int q = q0; q < q0 + QB; ++q) {
-          const int f = fw + 32 * fb + 8 * q + 4 * h;
-          const bool ok = p < P && f < F;
-          const float4 bv = pre.bias[fb][q];
-          const float e[4] = {acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w};
-          const float xv[4] = {xq[q].x, xq[q].y, xq[q].z, xq[q].w};
-          const float lv[4] = {lq[q].x, lq[q].y, lq[q].z, lq[q].w};
-          const float hv[4] = {hq[q].x, hq[q].y, hq[q].z, hq[q].w};
-          float kv[4] = {0.f, 0.f, 0.f, 0.f};
-          bool draw = t > 0 && cz;         // EpiPosterior's rule: C = 0 (eta = 0 DDIM steps; t = 0) draws nothing
-          if constexpr (KNOWN) {
-            kv[0] = kq[q].x; kv[1] = kq[q].y; kv[2] = kq[q].z; kv[3] = kq[q].w;
-            // EpiPosteriorKnown's rule: the known elements use z at every t > 0; a quad without an observation skips the generator where C = 0
-            const bool any_known = kv[0] == kv[0] || kv[1] == kv[1] || kv[2] == kv[2] || kv[3] == kv[3];
-            draw = t > 0 && (cz || any_known);
-          }
-          float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (draw) {
-            if (zbase) zz = ldq<FAST>(zbase + (size_t)pc * a.ldzz, f, F);
-            else zz = randn4(a.seed, a.row_offset + (uint32_t)p, (uint32_t)(f >> 2), (uint32_t)t, TAG_POSTERIOR);
-          }
-          const float zv[4] = {zz.x, zz.y, zz.z, zz.w};
-          float o[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float x0 = fmaf(cP, xv[r], cQ * e[r]);
-            const float x0c = fminf(fmaxf(x0, lv[r]), hv[r]);
-            o[r] = fmaf(cE, x0c, fmaf(cF, xv[r], cC * (cz ? zv[r] : 0.f)));
-            if constexpr (KNOWN) {
-              const float kn = t > 0 ? fmaf(La, kv[r], Ls * zv[r]) : kv[r];
-              o[r] = (kv[r] == kv[r]) ? kn : o[r];      // NaN: free
+            for (int q = q0; q < q0 + QB; ++q) {
+              const int f = fw + 32 * fb + 8 * q + 4 * h;
+              xq[q] = ldq<FAST>(a.xin + (size_t)pc * a.ldx, f, F);
+              if constexpr (!PLAIN) {
+                lq[q] = ldq<FAST>(post_clip(args).lo, f, F);
+                hq[q] = ldq<FAST>(post_clip(args).hi, f, F);
+              }
+              if constexpr (HIST) {
+                pq[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (hz) pq[q] = ldq<FAST>(hrow, f, F);
+              }
+              if constexpr (KNOWN) kq[q] = ldq<FAST>(post_known(args).known + (size_t)pc * post_known(args).ldk, f, F);
             }
           }
-          if (t == 0 && a.mut_mask && ok && f < a.mutation_dim) {
-            float* mrow = a.mut_mask + (size_t)p * a.mutation_dim;
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (f + r < a.mutation_dim) mrow[f + r] = (o[r] > 0.5f) ? 1.0f : 0.0f;
-          }
-          if (p < P) stq<FAST>(a.xout + (size_t)pc * a.ldo, f, F, make_float4(o[0], o[1], o[2], o[3]));
-          sync.tick();
-        }
-        }
-      }
-  }
-};
-
-// ---- output_proj + the DPM-Solver++(2M) multistep update (Lu et al. 2022) ----
-// EpiPosteriorClip's deterministic step plus one term: the previous step's clipped x0, kept in hist [P][ldh] (ldh = ldx, the state's
-// row stride), which the lane that owns an element reads and rewrites in place exactly as it does x.  x0coef [S][4] = (P_t, Q_t, G_t,
-// F_t), hcoef [S] = H_t.  Per element of step t:
-//   eps = acc + bias
-//   x0  = fmaf(P, x, Q*eps)
-//   x0c = fminf(fmaxf(x0, lo[f]), hi[f])
-//   hp  = hist[p][f];   hist[p][f] = x0c           the clipped network prediction, not the value after the `known` overwrite
-//   x'  = fmaf(G, x0c, fmaf(F, x, H*hp))
-// H is wave-uniform: where it is 0 (the first step run, whose history is the zeroed buffer, and t = 0) the read is skipped and hp = 0;
-// the store is skipped at t = 0.  Row 0 is (P, Q, 1, 0) with H = 0: x' = x0c bit for bit.  No z: the generator runs only under KNOWN,
-// for quads that hold an observation, at t > 0 (EpiPosteriorKnown's expressions and draw rule, after the update).  a.p.coef is not read.
-// Quads requested ahead of their use: two (x, lo, hi, hist: 32 registers), KNOWN one (20), as EpiPosteriorClip<true>.
-struct PosteriorHistArgs {
-  PosteriorClipArgs c;
-  float* hist; int ldh;                 // [P][ldh]
-  const float* hcoef;                   // dev [S] = H_t
-};
-template <bool KNOWN>
-struct EpiPosteriorHist {
-  static constexpr bool COUNTED_STORES = true;     // one x' quad per accumulator quad and, at t > 0, one history quad more: never fewer
-  static constexpr bool XBUF = false;
-  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
-  typedef PosteriorHistArgs Args;
-  static bool fast_ok(const Args& a, int F) { return EpiPosteriorClip<KNOWN>::fast_ok(a.c, F) && al16(a.hist) && a.ldh % 4 == 0; }
-  template <int NFB> using Pre = EpiPosterior::Pre<NFB>;
-  template <int NFB, bool FAST>
-  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
-    return EpiPosterior::prefetch<NFB, FAST>(a.c.p, fw, lane, F);
-  }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& ah, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
-    const PosteriorClipArgs& ac = ah.c;
-    const EpiPosterior::Args& a = ac.p;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int t = a.t_dev ? *a.t_dev : a.t_imm;
-    const float* c = ac.x0coef + 4 * t;
-    const float cP = c[0], cQ = c[1], cG = c[2], cF = c[3];
-    const float cH = ah.hcoef[t];
-    const bool hz = cH != 0.f;           // uniform: the step's table row
-    float La = 1.f, Ls = 0.f;
-    if constexpr (KNOWN) { La = ac.level[2 * t]; Ls = ac.level[2 * t + 1]; }
-    const float* zbase = a.z ? a.z + (long long)(a.t_first - t) * a.z_step_stride : nullptr;
-    constexpr int QB = KNOWN ? 1 : 2;
-#pragma unroll
-    for (int fb = 0; fb < NFB; ++fb)
-#pragma unroll
-      for (int pb = 0; pb < NPB; ++pb) {
-        const int p = pw + 32 * pb + l31;
-        const int pc = p < P ? p : P - 1;
-        float* hrow = ah.hist + (size_t)pc * ah.ldh;
-        float4 xq[4], lq[4], hq[4], pq[4], kq[KNOWN ? 4 : 1];
-#pragma unroll
-        for (int q0 = 0; q0 < 4; q0 += QB) {
-#pragma unroll
-        for (int q = q0; q < q0 + QB; ++q) {
-          const int f = fw + 32 * fb + 8 * q + 4 * h;
-          xq[q] = ldq<FAST>(a.xin + (size_t)pc * a.ldx, f, F);
-          lq[q] = ldq<FAST>(ac.lo, f, F);
-          hq[q] = ldq<FAST>(ac.hi, f, F);
-          pq[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (hz) pq[q] = ldq<FAST>(hrow, f, F);
-          if constexpr (KNOWN) kq[q] = ldq<FAST>(ac.known + (size_t)pc * ac.ldk, f, F);
-        }
-#pragma unroll
-        for (int q = q0; q < q0 + QB; ++q) {
-          const int f = fw + 32 * fb + 8 * q + 4 * h;
-          const bool ok = p < P && f < F;
-          const float4 bv = pre.bias[fb][q];
-          const float e[4] = {acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w};
-          const float xv[4] = {xq[q].x, xq[q].y, xq[q].z, xq[q].w};
-          const float lv[4] = {lq[q].x, lq[q].y, lq[q].z, lq[q].w};
-          const float hv[4] = {hq[q].x, hq[q].y, hq[q].z, hq[q].w};
-          const float pv[4] = {pq[q].x, pq[q].y, pq[q].z, pq[q].w};
-          float kv[4] = {0.f, 0.f, 0.f, 0.f};
-          float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-          if constexpr (KNOWN) {
-            kv[0] = kq[q].x; kv[1] = kq[q].y; kv[2] = kq[q].z; kv[3] = kq[q].w;
-            // EpiPosteriorKnown's rule at C = 0: the known elements use z at every t > 0; a quad without an observation skips the generator
-            const bool any_known = kv[0] == kv[0] || kv[1] == kv[1] || kv[2] == kv[2] || kv[3] == kv[3];
-            if (t > 0 && any_known) {
+          for (int q = q0; q < q0 + QB; ++q) {
+            const int f = fw + 32 * fb + 8 * q + 4 * h;
+            const bool ok = p < P && f < F;
+            const float4 bv = pre.bias[fb][q];
+            float4 x;
+            if constexpr (ALL) x = xall[fb][pb][q];
+            else x = xq[q];
+            const float e[4] = {acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w};
+            const float xv[4] = {x.x, x.y, x.z, x.w};
+            float kv[4] = {0.f, 0.f, 0.f, 0.f};
+            // the draw rule.  C = 0 (eta = 0 DDIM steps; t = 0; HIST) draws nothing; the known elements use z at every t > 0, and a
+            // quad without an observation skips the generator where C = 0.  cz is uniform: the step's table row
+            bool draw = t > 0 && cz;
+            if constexpr (KNOWN) {
+              kv[0] = kq[q].x; kv[1] = kq[q].y; kv[2] = kq[q].z; kv[3] = kq[q].w;
+              const bool any_known = kv[0] == kv[0] || kv[1] == kv[1] || kv[2] == kv[2] || kv[3] == kv[3];
+              draw = t > 0 && (cz || any_known);
+            }
+            float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (draw) {
               if (zbase) zz = ldq<FAST>(zbase + (size_t)pc * a.ldzz, f, F);
               else zz = randn4(a.seed, a.row_offset + (uint32_t)p, (uint32_t)(f >> 2), (uint32_t)t, TAG_POSTERIOR);
             }
-          }
-          const float zv[4] = {zz.x, zz.y, zz.z, zz.w};
-          float o[4], x0c[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float x0 = fmaf(cP, xv[r], cQ * e[r]);
-            x0c[r] = fminf(fmaxf(x0, lv[r]), hv[r]);
-            o[r] = fmaf(cG, x0c[r], fmaf(cF, xv[r], cH * pv[r]));
-            if constexpr (KNOWN) {
-              const float kn = t > 0 ? fmaf(La, kv[r], Ls * zv[r]) : kv[r];
-              o[r] = (kv[r] == kv[r]) ? kn : o[r];      // NaN: free
+            const float zv[4] = {zz.x, zz.y, zz.z, zz.w};
+            float lv[4] = {0.f, 0.f, 0.f, 0.f}, hv[4] = {0.f, 0.f, 0.f, 0.f}, pv[4] = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (!PLAIN) {
+              lv[0] = lq[q].x; lv[1] = lq[q].y; lv[2] = lq[q].z; lv[3] = lq[q].w;
+              hv[0] = hq[q].x; hv[1] = hq[q].y; hv[2] = hq[q].z; hv[3] = hq[q].w;
             }
-          }
-          if (t == 0 && a.mut_mask && ok && f < a.mutation_dim) {
-            float* mrow = a.mut_mask + (size_t)p * a.mutation_dim;
+            if constexpr (HIST) { pv[0] = pq[q].x; pv[1] = pq[q].y; pv[2] = pq[q].z; pv[3] = pq[q].w; }
+            float o[4], x0c[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (f + r < a.mutation_dim) mrow[f + r] = (o[r] > 0.5f) ? 1.0f : 0.0f;
+            for (int r = 0; r < 4; ++r) {
+              if constexpr (PLAIN && !KNOWN) o[r] = fmaf(cA, xv[r], fmaf(cB, e[r], cC * zv[r]));
+              else if constexpr (PLAIN) o[r] = fmaf(cA, xv[r], fmaf(cB, e[r], cC * (cz ? zv[r] : 0.f)));
+              else {
+                const float x0 = fmaf(cP, xv[r], cQ * e[r]);
+                x0c[r] = fminf(fmaxf(x0, lv[r]), hv[r]);
+                if constexpr (CLIP) o[r] = fmaf(cE, x0c[r], fmaf(cF, xv[r], cC * (cz ? zv[r] : 0.f)));
+                else o[r] = fmaf(cE, x0c[r], fmaf(cF, xv[r], cH * pv[r]));      // cE holds G_t
+              }
+              if constexpr (KNOWN) {
+                const float kn = t > 0 ? fmaf(La, kv[r], Ls * zv[r]) : kv[r];
+                o[r] = (kv[r] == kv[r]) ? kn : o[r];      // NaN: free
+              }
+            }
+            if (t == 0 && a.mut_mask && ok && f < a.mutation_dim) {
+              float* mrow = a.mut_mask + (size_t)p * a.mutation_dim;
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (f + r < a.mutation_dim) mrow[f + r] = (o[r] > 0.5f) ? 1.0f : 0.0f;
+            }
+            if (p < P) stq<FAST>(a.xout + (size_t)pc * a.ldo, f, F, make_float4(o[0], o[1], o[2], o[3]));
+            if constexpr (HIST)
+              if (t > 0 && p < P) stq<FAST>(hrow, f, F, make_float4(x0c[0], x0c[1], x0c[2], x0c[3]));
           }
-          if (p < P) stq<FAST>(a.xout + (size_t)pc * a.ldo, f, F, make_float4(o[0], o[1], o[2], o[3]));
-          if (t > 0 && p < P) stq<FAST>(hrow, f, F, make_float4(x0c[0], x0c[1], x0c[2], x0c[3]));
-          sync.tick();
-        }
         }
       }
   }
@@ -908,9 +721,9 @@ struct EpiMse {
   }
   // xbuf (FAST only): the wave's transposer region; the 32-feature blocks of the noise target are read, and those of dL/d eps
   // written, as full 128-byte row segments (xpose.h) instead of 32 rows x 32 bytes per wave-instruction
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  template <int NFB, int NPB, bool FAST>
   static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               float* xbuf = nullptr, Sync&& sync = Sync()) {
+                                               float* xbuf = nullptr) {
     const int l31 = lane & 31, h = lane >> 5;
     float part = 0.f;
     if (FAST && xbuf) {
@@ -968,7 +781,6 @@ struct EpiMse {
       if (!prow || f + 3 >= F) d.w = 0.f;
       part += d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w;
       if (a.dout && prow) stq<FAST>(a.dout + (size_t)p * a.ldd, f, F, make_float4(d.x * a.gscale, d.y * a.gscale, d.z * a.gscale, d.w * a.gscale));
-      sync.tick();
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
@@ -1023,9 +835,9 @@ struct EpiLoss {
     part += w * q;
     d.x = d.x * w * gs; d.y = d.y * w * gs; d.z = d.z * w * gs; d.w = d.w * w * gs;
   }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  template <int NFB, int NPB, bool FAST>
   static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& al, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               float* xbuf = nullptr, Sync&& sync = Sync()) {
+                                               float* xbuf = nullptr) {
     const EpiMse::Args& a = al.m;
     const int l31 = lane & 31, h = lane >> 5;
     const int kind = al.kind;
@@ -1092,7 +904,6 @@ struct EpiLoss {
       if (!prow || f + 3 >= F) d.w = 0.f;
       quad(kind, delta, wrow[pb], a.gscale, d, part);
       if (a.dout && prow) stq<FAST>(a.dout + (size_t)p * a.ldd, f, F, d);
-      sync.tick();
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
@@ -1129,9 +940,9 @@ struct EpiRowSq {
       for (int q = 0; q < 4; ++q) r.bias[fb][q] = ldq<FAST>(a.bias, fw + 32 * fb + 8 * q + 4 * h, F);
     return r;
   }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
+  template <int NFB, int NPB, bool FAST>
   static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               float* xbuf = nullptr, Sync&& sync = Sync()) {
+                                               float* xbuf = nullptr) {
     const int l31 = lane & 31, h = lane >> 5;
     if (fw >= F || pw >= P) return;                    // uniform over the wave: a slot past the last one, or padding rows only
     float part[NPB];
@@ -1177,7 +988,6 @@ struct EpiRowSq {
         if (!prow || f + 2 >= F) d.z = 0.f;
         if (!prow || f + 3 >= F) d.w = 0.f;
         part[pb] += d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w;
-        sync.tick();
       }
     }
     float* slot = a.part + (long long)(fw / (32 * NFB)) * a.ld;
@@ -1215,9 +1025,8 @@ struct EpiRbfSum {
       for (int q = 0; q < 4; ++q) r.sqa[fb][q] = ldq<FAST>(a.sqa, fw + 32 * fb + 8 * q + 4 * h, F);
     return r;
   }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
+  template <int NFB, int NPB, bool FAST>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     const int l31 = lane & 31, h = lane >> 5;
     float part = 0.f;
 #pragma unroll
@@ -1278,9 +1087,8 @@ struct EpiNearest {
       for (int q = 0; q < 4; ++q) r.sqr[fb][q] = ldq<FAST>(a.sqr, fw + 32 * fb + 8 * q + 4 * h, F);
     return r;
   }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
+  template <int NFB, int NPB, bool FAST>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     const int l31 = lane & 31, h = lane >> 5;
 #pragma unroll
     for (int pb = 0; pb < NPB; ++pb) {
@@ -1311,7 +1119,6 @@ struct EpiNearest {
         unsigned long long* slot = a.keys + p;
         if (key < __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(slot, key);
       }
-      sync.tick();
     }
   }
 };
@@ -1355,9 +1162,8 @@ struct EpiKnn {
     const unsigned hi = (unsigned)(kth >> 32);
     return prow ? (int)(hi < 0x7ffffffeu ? hi : 0x7ffffffeu) : -1;
   }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
+  template <int NFB, int NPB, bool FAST>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     const int l31 = lane & 31, h = lane >> 5;
     const int k = a.k;
 #pragma unroll
@@ -1401,7 +1207,6 @@ struct EpiKnn {
             }
           }
         }
-      sync.tick();
     }
   }
 };
@@ -1440,9 +1245,8 @@ struct EpiBallCount {
       }
     return r;
   }
-  template <int NFB, int NPB, bool FAST, class Sync = NoSync>
-  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
-                                               Sync&& sync = Sync()) {
+  template <int NFB, int NPB, bool FAST>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     const int l31 = lane & 31, h = lane >> 5;
 #pragma unroll
     for (int pb = 0; pb < NPB; ++pb) {
@@ -1473,7 +1277,6 @@ struct EpiBallCount {
         if (cr) atomicAdd(a.in_ref + p, cr);       // cr, cq stay 0 where the radius array is NULL
         if (cq) atomicAdd(a.in_query + p, cq);
       }
-      sync.tick();
     }
   }
 };

@@ -82,21 +82,21 @@ struct Guide {
   float w;
 };
 
-// Known-feature conditioning of a chain (osd_sample_chain_known): observed elements are overwritten after every step (EpiPosteriorKnown).
+// Known-feature conditioning of a chain (osd_sample_chain_known): observed elements are overwritten after every step (EpiPosterior<POST_PLAIN, true>).
 struct Known {
   const float* known;          // dev [n][ld], NaN = free; null = nothing known
   int64_t ld;
   const float* level;          // dev [S][2]
 };
 
-// Clipping of the predicted x0 to per-feature bounds inside the posterior launch (osd_sample_chain_clipped, EpiPosteriorClip).
+// Clipping of the predicted x0 to per-feature bounds inside the posterior launch (osd_sample_chain_clipped, EpiPosterior<POST_CLIP>).
 struct Clip {
   const float* bounds;         // dev [2][ld]: the lo row, then the hi row; null = no clipping
   int ld;
   const float* x0_coef;        // dev [S][4] = (P, Q, E, F)
 };
 
-// The DPM-Solver++(2M) multistep update (osd_sample_chain_multistep, EpiPosteriorHist): the chain keeps the previous step's clipped x0.
+// The DPM-Solver++(2M) multistep update (osd_sample_chain_multistep, EpiPosterior<POST_HIST>): the chain keeps the previous step's clipped x0.
 // Always with a Clip, whose x0_coef rows are then (P, Q, G, F) and whose bounds may be all-infinite.
 struct Multistep {
   const float* hist_coef;      // dev [S] = H; null = single-step chains

@@ -190,41 +190,23 @@ hipError_t launch_gn_silu_splitk(hipStream_t s, const GemmArgs& g, const GnArgs&
   return hipGetLastError();
 }
 
-hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const EpiPosterior::Args& a) {
+// output_proj + posterior: the tile choice of every EpiPosterior instantiation
+template <class Epi>
+static hipError_t launch_posterior_as(hipStream_t s, const GemmArgs& g, const typename Epi::Args& a) {
   // below one full round of 128 x 128 tiles (512 workgroup slots) the 64 x 128 tile spreads the same work over twice the workgroups
   constexpr long POST_BIG_FROM = 512;
   const long big_tiles = (long)((g.F + 127) / 128) * ((g.P + 127) / 128);
-  if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosterior>(s, g, a);
-  return launch_gemm<TileSmall, true, true, EpiPosterior>(s, g, a);
+  if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, Epi>(s, g, a);
+  return launch_gemm<TileSmall, true, true, Epi>(s, g, a);
 }
-// launch_posterior's tile choice
-hipError_t launch_posterior_known(hipStream_t s, const GemmArgs& g, const EpiPosteriorKnown::Args& a) {
-  constexpr long POST_BIG_FROM = 512;
-  const long big_tiles = (long)((g.F + 127) / 128) * ((g.P + 127) / 128);
-  if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorKnown>(s, g, a);
-  return launch_gemm<TileSmall, true, true, EpiPosteriorKnown>(s, g, a);
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorArgs& a) { return launch_posterior_as<EpiPosterior<POST_PLAIN, false>>(s, g, a); }
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorKnownArgs& a) { return launch_posterior_as<EpiPosterior<POST_PLAIN, true>>(s, g, a); }
+// a.known (a.c.known) selects the instantiation that also puts observed values back
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorClipArgs& a) {
+  return a.known ? launch_posterior_as<EpiPosterior<POST_CLIP, true>>(s, g, a) : launch_posterior_as<EpiPosterior<POST_CLIP, false>>(s, g, a);
 }
-// launch_posterior's tile choice; a.known selects the instantiation that also puts observed values back
-hipError_t launch_posterior_clip(hipStream_t s, const GemmArgs& g, const PosteriorClipArgs& a) {
-  constexpr long POST_BIG_FROM = 512;
-  const long big_tiles = (long)((g.F + 127) / 128) * ((g.P + 127) / 128);
-  if (a.known) {
-    if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorClip<true>>(s, g, a);
-    return launch_gemm<TileSmall, true, true, EpiPosteriorClip<true>>(s, g, a);
-  }
-  if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorClip<false>>(s, g, a);
-  return launch_gemm<TileSmall, true, true, EpiPosteriorClip<false>>(s, g, a);
-}
-// launch_posterior's tile choice; a.c.known selects the instantiation that also puts observed values back
-hipError_t launch_posterior_hist(hipStream_t s, const GemmArgs& g, const PosteriorHistArgs& a) {
-  constexpr long POST_BIG_FROM = 512;
-  const long big_tiles = (long)((g.F + 127) / 128) * ((g.P + 127) / 128);
-  if (a.c.known) {
-    if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorHist<true>>(s, g, a);
-    return launch_gemm<TileSmall, true, true, EpiPosteriorHist<true>>(s, g, a);
-  }
-  if (big_tiles >= POST_BIG_FROM) return launch_gemm<TileBig, true, true, EpiPosteriorHist<false>>(s, g, a);
-  return launch_gemm<TileSmall, true, true, EpiPosteriorHist<false>>(s, g, a);
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorHistArgs& a) {
+  return a.c.known ? launch_posterior_as<EpiPosterior<POST_HIST, true>>(s, g, a) : launch_posterior_as<EpiPosterior<POST_HIST, false>>(s, g, a);
 }
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a) {
   if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiMse>(s, g, a);

@@ -22,13 +22,13 @@ hipError_t launch_input(hipStream_t s, const GemmArgs& g, const EpiInput::Args& 
 hipError_t launch_input_guided(hipStream_t s, const GemmArgs& g, const EpiInputGuided::Args& a, bool a_zero_padded);
 hipError_t launch_input_guided_splitk(hipStream_t s, const GemmArgs& g, const EpiInputGuided::Args& a, float* slabs, int slices);
 hipError_t launch_input_splitk(hipStream_t s, const GemmArgs& g, const EpiInput::Args& a, float* slabs, int slices);
-hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const EpiPosterior::Args& a);
-// output_proj + posterior around observed values (EpiPosteriorKnown); launch_posterior's tile choice
-hipError_t launch_posterior_known(hipStream_t s, const GemmArgs& g, const EpiPosteriorKnown::Args& a);
-// output_proj + posterior with the predicted x0 clipped to per-feature bounds (EpiPosteriorClip<a.known != null>); launch_posterior's tile choice
-hipError_t launch_posterior_clip(hipStream_t s, const GemmArgs& g, const PosteriorClipArgs& a);
-// output_proj + the DPM-Solver++(2M) multistep update on the clipped x0 (EpiPosteriorHist<a.c.known != null>); launch_posterior's tile choice
-hipError_t launch_posterior_hist(hipStream_t s, const GemmArgs& g, const PosteriorHistArgs& a);
+// output_proj + one step of the reverse chain (EpiPosterior<MODE, KNOWN>), one tile choice.  The argument type picks MODE: plain, around
+// observed values, with the predicted x0 clipped to per-feature bounds (KNOWN = a.known != null), the DPM-Solver++(2M) multistep
+// update on the clipped x0 (KNOWN = a.c.known != null)
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorArgs& a);
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorKnownArgs& a);
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorClipArgs& a);
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorHistArgs& a);
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a);
 // k_b3t.hip: precision = 1 (hipErrorInvalidValue: outside the kernel's preconditions -- run the fp32 launch)
 hipError_t launch_mse_b3t(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a);

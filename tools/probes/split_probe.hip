@@ -228,8 +228,8 @@ static void rate(int K, int N, int P, int kind, int reps) {
       time_b3<EpiB3Post, 0>(grid, reps, g, e, u2);
       printf("     (posterior with direct x accesses and the generator in the epilogue: LD0 %.1f us, LD2 %.1f us)\n", u2[0], u2[1]);
     }
-    EpiPosterior::Args e2{}; e2.bias = dPar; e2.xin = dXs; e2.ldx = N; e2.xout = dXs; e2.ldo = N; e2.coef = dCoef; e2.t_imm = 500; e2.ldzz = N; e2.seed = 1; e2.t_first = 500;
-    us32 = time_kernel(gemm_glds_kernel<TileBig, EpiPosterior>, grid, 256, l32, reps, g32, e2);
+    PosteriorArgs e2{}; e2.bias = dPar; e2.xin = dXs; e2.ldx = N; e2.xout = dXs; e2.ldo = N; e2.coef = dCoef; e2.t_imm = 500; e2.ldzz = N; e2.seed = 1; e2.t_first = 500;
+    us32 = time_kernel(gemm_glds_kernel<TileBig, EpiPosterior<POST_PLAIN, false>>, grid, 256, l32, reps, g32, e2);
   }
   if (kind != 0) {
     Bf3Args gs = g; gs.stamps = dSt;
