@@ -642,6 +642,37 @@ int osd_val_centered_gram(void *stream, int device, const float *X, int64_t rows
 #define OSD_CORR_STATS 7
 int osd_val_corr_compare(void *stream, int device, const double *G_real, const double *G_synth, int D,
                          const int32_t *bounds_host, int n_blocks, double strong, double *out_host);
+/* Loss, gradient and scores of K regularised-linear-model heads over a cohort, in one read of X (csrc/glm.hip; DESIGN.md section
+ * 3.22).  With u_i = (x_i - center) * scale over the first D columns, z_ik = W_k[:D] . u_i + W_k[D] and a_i the row weight:
+ *   loss_host[k]  = sum_i a_i l_k(y_ik, z_ik)            l = softplus(z) - y z (OSD_GLM_LOGISTIC), (z - y)^2 / 2 (OSD_GLM_SQUARED)
+ *   grad_dev[k]   = sum_i a_i dl/dz (u_i, 1)              DEVICE double [K][D + 1], bias last, overwritten; a column with scale 0
+ *                                                         is dropped (gradient exactly 0)
+ *   score_dev     = z_ik                                  dev float [rows][lds]
+ * SUMS, not means, and no penalty: the results of several calls (two cohorts, row shards, row chunks) add up; the host applies 1 / n
+ * and the L2 term.  X dev float [rows][ld] (any base address, any ld >= D: a 16-byte aligned base with ld % 4 == 0 and
+ * ld >= roundup(D, 4) is read 16 bytes per lane, everything else by dwords in place -- never through a copy); center, scale: dev
+ * float [D]; Y: dev float [rows][ldy], the first K columns (logistic targets are used as given: soft labels are legal); row_weight:
+ * dev float [rows] or NULL (= 1); W: dev float [K][D + 1]; kind_host: host int32 [K].  grad_dev == NULL: the predictor -- scores
+ * (and the loss, if asked for) with the bits of the full call and no column accumulation.  loss_host and score_dev may be NULL, Y
+ * too if neither loss nor gradient is asked for; at least one output.
+ * Arithmetic: x - center, the products and the dot are fp32 (the kernel multiplies W by scale once and applies the gradient's factor
+ * scale in double); the logistic loss is max(z, 0) - y z + log1p(exp(-|z|)) and the sigmoid is finite for every finite z.  The
+ * gradient is accumulated in fp32 over runs of at most OSD_GLM_RUN_ROWS rows per work item (a contiguous block of rows), every run
+ * is folded into the item's double sums, and the items are added in a fixed order; the loss is summed in double from fp32 row
+ * terms the same way.  No floating-point atomics: the same inputs give the same bits, and the partition into items depends on
+ * (rows, D, K) alone.  Inputs must be finite.  1 <= K <= 4, rows >= 1, 1 <= D <= 8192 (OSD_EINVAL otherwise).  Synchronous. */
+#define OSD_GLM_LOGISTIC 0
+#define OSD_GLM_SQUARED  1
+#define OSD_GLM_RUN_ROWS 128
+int osd_val_glm_eval(void *stream, int device, const float *X, int64_t rows, int ld, int D,
+                     const float *center, const float *scale, const float *Y, int ldy, const float *row_weight,
+                     const float *W, int K, const int32_t *kind_host, double *loss_host, double *grad_dev,
+                     float *score_dev, int lds);
+/* Per column of the first D: sum_r (X[r][j] - center[j]) and sum_r (X[r][j] - center[j])^2 in double, one streaming pass,
+ * fixed summation order (same inputs, same bits).  center: dev float [D] or NULL (= 0); sum_host, sumsq_host: host double [D].
+ * Partial sums of row shards about one common centre add up; mean and variance follow on the host.  Synchronous. */
+int osd_val_col_centered_moments(void *stream, int device, const float *X, int64_t rows, int ld, int D,
+                                 const float *center, double *sum_host, double *sumsq_host);
 
 /* ---- biological constraint losses (north_star) ------------------------------
  * The reference declares them at models/cvae.py:262-302 as stubs that return 0.0 (and the diffusion

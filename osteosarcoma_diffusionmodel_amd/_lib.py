@@ -20,6 +20,8 @@ OSD_TP_DP_CLIP = 1 << 13
 DP_NOISE_TAG, DP_NOISE_COLS = 0x44504E00, 4096      # csrc/dp.h: the Philox tag and the (rows, 4096) reading of the flat buffer
 OSD_PRED_EPSILON, OSD_PRED_V, OSD_PRED_SAMPLE = 0, 1, 2
 OSD_CORR_STATS = 7
+OSD_GLM_LOGISTIC, OSD_GLM_SQUARED = 0, 1
+OSD_GLM_RUN_ROWS = 128
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libosdiff.so"
 
@@ -108,6 +110,10 @@ _SIGNATURES = {
     "osd_val_pearson": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int64, C.POINTER(C.c_double)]),
     "osd_val_centered_gram": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "osd_val_corr_compare": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_double, _P]),
+    "osd_val_glm_eval": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_double), _P, _P, C.c_int]),
+    "osd_val_col_centered_moments": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, C.POINTER(C.c_double),
+                                               C.POINTER(C.c_double)]),
     "osd_set_constraints": (C.c_int, [_P, C.POINTER(OsdConstraints)]),
     "osd_get_loss_parts": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "osd_set_loss": (C.c_int, [_P, C.c_int, C.c_double, _P]),

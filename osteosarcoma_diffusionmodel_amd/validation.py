@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import utility as U
 from .parallel import ShardComm
 
 logger = logging.getLogger(__name__)
@@ -257,6 +258,63 @@ class DeviceKernels:
         out = (C.c_double * (1 + L.OSD_CORR_STATS * n_pairs))()
         L.check(L.lib().osd_val_corr_compare(self._stream(), self.index, L.ptr(g_real), L.ptr(g_synth), D, arr, nb, float(strong), out))
         return corr_stats_from_flat(np.array(out[:]))
+
+    def col_centered_moments(self, t: torch.Tensor, center=None):
+        """(sum, sumsq) float64 [D] numpy: per column of the fp32 device tensor t the sums of (x - c) and (x - c)^2 in double
+        (``osd_val_col_centered_moments``; one pass, fixed order).  ``center``: D values rounded to fp32, or None for 0.  A
+        column-slice view is read in place."""
+        t = _rows_view(t)
+        rows, D = t.shape
+        c = None if center is None else _f32(center, t.device, (D,), "center")
+        s, q = (C.c_double * D)(), (C.c_double * D)()
+        L.check(L.lib().osd_val_col_centered_moments(self._stream(), self.index, L.ptr(t), rows, max(int(t.stride(0)), D), D, L.ptr(c), s, q))
+        return np.array(s[:]), np.array(q[:])
+
+    def glm_eval(self, x: torch.Tensor, center, scale, y, W, kinds: Sequence[int], row_weight=None, grad: bool = True,
+                 scores: bool = False):
+        """``osd_val_glm_eval`` on the fp32 device tensor x [rows, D] (a column-slice view is read in place): with
+        u = (x - center) * scale and z = W[:, :D] u + W[:, D], returns ``(loss, grad, scores)`` -- loss float64 [K] numpy, the SUM
+        over the rows of a_i l_k(y_ik, z_ik) (None without targets); grad float64 [K, D + 1] numpy, its gradient, bias last (None
+        with ``grad=False``: the predictor); scores the float32 [rows, K] device tensor z (None unless ``scores=True``).
+        ``center``, ``scale`` [D], ``W`` [K, D + 1], ``y`` [rows, K] and ``row_weight`` [rows] (None: 1) are rounded to fp32;
+        ``kinds``: ``utility.LOGISTIC`` / ``utility.SQUARED`` per head, K <= 4.  Sums, not means, and no penalty: the results of
+        several calls add up.  The same inputs give the same bits."""
+        x = _rows_view(x)
+        rows, D = x.shape
+        K = len(kinds)
+        center, scale = _f32(center, x.device, (D,), "center"), _f32(scale, x.device, (D,), "scale")
+        W = _f32(W, x.device, (K, D + 1), "W")
+        y = None if y is None else _f32(y, x.device, (rows, K), "y")
+        a = None if row_weight is None else _f32(row_weight, x.device, (rows,), "row_weight")
+        if y is None and grad:
+            raise ValueError("a gradient needs targets")
+        if y is None and not scores:
+            raise ValueError("nothing to compute: no targets and no scores")
+        arr = (C.c_int32 * max(K, 1))(*[int(v) for v in kinds])
+        loss = (C.c_double * max(K, 1))() if y is not None else None
+        g = torch.empty((K, D + 1), dtype=torch.float64, device=x.device) if grad else None
+        z = torch.empty((rows, K), dtype=torch.float32, device=x.device) if scores else None
+        L.check(L.lib().osd_val_glm_eval(self._stream(), self.index, L.ptr(x), rows, max(int(x.stride(0)), D), D, L.ptr(center),
+                                         L.ptr(scale), L.ptr(y), K, L.ptr(a), L.ptr(W), K, arr, loss, L.ptr(g), L.ptr(z), K))
+        return (None if loss is None else np.array(loss[:K])), (None if g is None else g.cpu().numpy()), z
+
+
+def _rows_view(t: torch.Tensor) -> torch.Tensor:
+    """t as an fp32 [rows >= 1, D >= 1] tensor whose rows are contiguous (stride(1) == 1, stride(0) >= D): itself where it already is."""
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("a [rows >= 1, features >= 1] tensor is needed")
+    if t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.to(torch.float32).contiguous()
+    return t
+
+
+def _f32(a, device, shape, name: str) -> torch.Tensor:
+    """a as a contiguous fp32 tensor of the given shape on the device."""
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    t = t.to(device=device, dtype=torch.float32).contiguous()
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
 
 
 COV_SLAB_ROWS = 256       # OSD_COV_SLAB_ROWS of include/osdiff.h: rows one fp32 accumulator run of osd_val_centered_gram covers
@@ -521,6 +579,148 @@ def corr_summary(stats: Dict[str, np.ndarray], bounds: Sequence[int], names: Seq
     return out
 
 
+# ---- downstream utility: fits of regularised linear heads over row shards -------------------------------
+GLM_RUN_ROWS = L.OSD_GLM_RUN_ROWS       # rows one fp32 gradient run of osd_val_glm_eval covers
+
+
+def pooled_standardisation(k, parts):
+    """(n, center, scale) of the rows of ``parts`` -- a list of (comm, rows): ShardComm(False) for a replicated tensor, the
+    validator's for a row shard -- taken together: n the row count, center the float32 column means the kernel subtracts, scale
+    float32 1 / sd (population sd about the float64 mean; 0 for a constant column, which drops it).  Two passes: column sums, then
+    ``k.col_centered_moments`` about the fp32 centre, each all-reduced and added over the parts."""
+    D = int(parts[0][1].shape[1])
+    tot = np.zeros(D + 1, dtype=np.float64)
+    for comm, t in parts:
+        rows = int(t.shape[0])
+        sums = k.column_sums(t) if rows else np.zeros(D, dtype=np.float64)
+        tot += comm.sum(np.concatenate([np.asarray(sums, dtype=np.float64), [float(rows)]]))
+    n = int(round(tot[-1]))
+    if n < 2:
+        raise ValueError("a standardisation needs at least 2 rows")
+    center = (tot[:D] / n).astype(np.float32)
+    mom = np.zeros(2 * D, dtype=np.float64)
+    for comm, t in parts:
+        if int(t.shape[0]):
+            s, q = k.col_centered_moments(t, center)
+            mom += comm.sum(np.concatenate([s, q]))
+        else:
+            mom += comm.sum(np.zeros(2 * D, dtype=np.float64))
+    shift = mom[:D] / n
+    var = mom[D:] / n - shift * shift
+    with np.errstate(divide="ignore", invalid="ignore"):
+        scale = np.where(var > 0, 1.0 / np.sqrt(np.where(var > 0, var, 1.0)), 0.0)
+    return n, center, scale.astype(np.float32)
+
+
+def glm_sums(k, parts, center, scale, W, kinds):
+    """(loss [K], grad [K, D + 1]) float64: the sums of ``k.glm_eval`` over ``parts`` -- a list of (comm, rows, targets, row weights
+    or None) --, each part's all-reduced over its communicator and the parts added in double; an empty shard contributes zeros.  This
+    is the ``eval_fn`` of ``utility.fit_glm``."""
+    K, D = len(kinds), int(parts[0][1].shape[1])
+    tot = np.zeros(K * (D + 2), dtype=np.float64)
+    for comm, x, y, a in parts:
+        if int(x.shape[0]):
+            loss, grad, _ = k.glm_eval(x, center, scale, y, W, kinds, row_weight=a)
+            flat = np.concatenate([np.asarray(loss, dtype=np.float64), np.asarray(grad, dtype=np.float64).ravel()])
+        else:
+            flat = np.zeros(K * (D + 2), dtype=np.float64)
+        tot += comm.sum(flat)
+    return tot[:K], tot[K:].reshape(K, D + 1)
+
+
+def fit_heads(k, parts, center, scale, kinds, n: float, l2: float, max_iter: int = 200, tol: float = 1e-5):
+    """W float64 [K, D + 1] of ``utility.fit_glm`` over ``parts`` (as ``glm_sums`` takes them), the heads in groups of at most four
+    -- one kernel call per group and iteration --, and the list of the groups' fit reports."""
+    K, D = len(kinds), int(parts[0][1].shape[1])
+    W = np.zeros((K, D + 1), dtype=np.float64)
+    reports = []
+    for lo in range(0, K, U.MAX_HEADS):
+        hi = min(K, lo + U.MAX_HEADS)
+        sub = [(comm, x, y[:, lo:hi].contiguous(), a) for comm, x, y, a in parts]
+        fit = U.fit_glm(lambda w: glm_sums(k, sub, center, scale, w, kinds[lo:hi]), hi - lo, D, kinds[lo:hi], n, l2, max_iter=max_iter,
+                        tol=tol)
+        W[lo:hi] = fit["W"]
+        reports.append(fit)
+    return W, reports
+
+
+def glm_scores(k, x, center, scale, W, kinds) -> np.ndarray:
+    """float64 [rows, K] numpy: the scores z of the rows of x under W, the heads in groups of at most four."""
+    K = len(kinds)
+    out = np.zeros((int(x.shape[0]), K), dtype=np.float64)
+    if int(x.shape[0]) == 0:
+        return out
+    for lo in range(0, K, U.MAX_HEADS):
+        hi = min(K, lo + U.MAX_HEADS)
+        _, _, z = k.glm_eval(x, center, scale, None, W[lo:hi], kinds[lo:hi], grad=False, scores=True)
+        out[:, lo:hi] = z.detach().cpu().numpy().astype(np.float64)
+    return out
+
+
+def utility_metrics(comm: ShardComm, k, x_train, c_train, x_synth, c_synth, x_test, c_test, names, l2: float = 1e-2,
+                    max_iter: int = 200, tol: float = 1e-5) -> Dict[str, float]:
+    """``BiologicalValidator.downstream_utility`` on tensors: the feature matrices on the kernels' device, the condition matrices
+    float64 numpy [rows, K]; ``x_synth`` / ``c_synth`` are this rank's row shard when ``comm`` is active.  ``k`` needs
+    ``column_sums``, ``col_centered_moments`` and ``glm_eval`` (DeviceKernels, or a float64 stand-in in the tests)."""
+    one = ShardComm(False)
+    c_train, c_synth, c_test = (np.asarray(c, dtype=np.float64) for c in (c_train, c_synth, c_test))
+    K = c_train.shape[1]
+    off_binary = comm.sum(np.array([float((~np.isin(c_synth[:, j], (0.0, 1.0))).sum()) for j in range(K)]))
+    kinds = [U.LOGISTIC if off_binary[j] == 0 and h == U.LOGISTIC else U.SQUARED for j, h in enumerate(U.head_kinds([c_train, c_test]))]
+    scores, targets = [], []
+    for label, cm, x, c in (("synthetic", comm, x_synth, c_synth), ("real_train", one, x_train, c_train)):
+        tot = cm.sum(np.concatenate([c.sum(0), [float(c.shape[0])]]))
+        n, mean = tot[-1], tot[:K] / tot[-1]
+        sd = np.sqrt(cm.sum(((c - mean) ** 2).sum(0)) / n)
+        mu, inv = np.zeros(K), np.ones(K)
+        for j, name in enumerate(names):
+            if kinds[j] == U.LOGISTIC:
+                for where, share in ((label, mean[j]), ("real_test", c_test[:, j].mean())):
+                    if share <= 0.0 or share >= 1.0:
+                        raise ValueError(f"condition {name!r} has a single class in the {where} cohort: no AUC can be computed")
+            elif not sd[j] > 0:
+                raise ValueError(f"condition {name!r} is constant in the {label} cohort: it cannot be standardised")
+            else:
+                mu[j], inv[j] = mean[j], 1.0 / sd[j]
+        y = torch.from_numpy(((c - mu) * inv).astype(np.float32)).to(x.device)
+        n_rows, center, scale = pooled_standardisation(k, [(cm, x)])
+        W, _ = fit_heads(k, [(cm, x, y, None)], center, scale, kinds, float(n_rows), l2, max_iter=max_iter, tol=tol)
+        scores.append(glm_scores(k, x_test, center, scale, W, kinds))
+        targets.append((c_test - mu) * inv)
+    return U.utility_summary(names, kinds, scores[0], scores[1], targets[0], targets[1])
+
+
+def c2st_metrics(comm: ShardComm, k, x_real, x_synth, test_fraction: float = 0.3, seed: int = 0, l2: float = 1e-2, max_iter: int = 200,
+                 tol: float = 1e-5) -> Dict[str, float]:
+    """``BiologicalValidator.discriminator_test`` on device tensors; ``x_synth`` is this rank's row shard when ``comm`` is active.
+    The synthetic split is a seeded permutation of the GLOBAL row numbers (rank order), so it does not depend on the sharding."""
+    from .parallel import _one_hot
+    one = ShardComm(False)
+    n_r, local = int(x_real.shape[0]), int(x_synth.shape[0])
+    counts = comm.sum(_one_hot(comm.rank, comm.world) * local).astype(np.int64)
+    n_s, off = int(counts.sum()), int(counts[:comm.rank].sum())
+    tr_r, te_r = U.split_indices(n_r, test_fraction, seed)
+    tr_s, te_s = U.split_indices(n_s, test_fraction, seed + 1)
+
+    def take(t, idx, lo=0, cnt=None):
+        idx = idx[(idx >= lo) & (idx < lo + (t.shape[0] if cnt is None else cnt))] - lo
+        return t.index_select(0, torch.as_tensor(idx, dtype=torch.int64, device=t.device))
+
+    xr_tr, xr_te = take(x_real, tr_r), take(x_real, te_r)
+    xs_tr, xs_te = take(x_synth, tr_s, off, local), take(x_synth, te_s, off, local)
+    n, center, scale = pooled_standardisation(k, [(one, xr_tr), (comm, xs_tr)])
+    # row weights that give the two classes the same total weight, n / 2 each
+    w_r, w_s = n / (2.0 * len(tr_r)), n / (2.0 * len(tr_s))
+    dev = x_real.device
+    parts = [(one, xr_tr, torch.zeros((xr_tr.shape[0], 1), device=dev), torch.full((xr_tr.shape[0],), w_r, device=dev)),
+             (comm, xs_tr, torch.ones((xs_tr.shape[0], 1), device=dev), torch.full((xs_tr.shape[0],), w_s, device=dev))]
+    kinds = [U.LOGISTIC]
+    W, _ = fit_heads(k, parts, center, scale, kinds, float(n), l2, max_iter=max_iter, tol=tol)
+    z_r = glm_scores(k, xr_te, center, scale, W, kinds)
+    z_s = comm.gather_rows(torch.from_numpy(glm_scores(k, xs_te, center, scale, W, kinds))).numpy()
+    return U.c2st_summary(z_r, z_s)
+
+
 class BiologicalValidator:
     """utils/validation.py:18 -- device versions of the metrics named in the module docstring."""
 
@@ -718,6 +918,61 @@ class BiologicalValidator:
                              "synth_rows": n_s, "stats": stats, "bounds": bounds, "names": names}
         return summary
 
+    # -- downstream utility: TSTR and the classifier two-sample test (no counterpart in the reference) ------
+    def downstream_utility(self, real_train, real_train_cond, synthetic, synth_cond, real_test, real_test_cond, names=None,
+                           l2: float = 1e-2, max_iter: int = 200, tol: float = 1e-5) -> Dict[str, float]:
+        """Train on synthetic, test on real: does the synthetic cohort carry the relation between the features and the conditions
+        the patients were generated under?  Each condition column is one head of an L2-regularised linear model of the features
+        (logistic where its values all lie in {0, 1} over the three cohorts, else least squares on the target standardised by the
+        training cohort), fitted once on ``synthetic`` / ``synth_cond`` (TSTR) and once on ``real_train`` / ``real_train_cond`` (TRTR)
+        -- features standardised by the cohort the fit trains on --, and both fits score ``real_test``.  Keys, per head:
+        ``utility_tstr_auc_<name>``, ``utility_trtr_auc_<name>``, ``utility_auc_gap_<name>`` (TRTR - TSTR) or the same with ``r2``;
+        and ``utility_gap_mean``.  ``names``: one per condition column (default: the columns of ``real_train_cond``, else c0, c1,
+        ...).  Every iteration of a fit is one pass of ``DeviceKernels.glm_eval`` over the cohort, four heads at a time.  A logistic
+        head with a single class in a training or the test cohort raises a ValueError naming the column.  On a ``sharded=True``
+        validator ``synthetic`` and ``synth_cond`` are this rank's row shard; the real cohorts are replicated."""
+        if names is None:
+            cols = getattr(real_train_cond, "columns", None)
+            names = [str(c) for c in cols] if cols is not None else None
+        xs = [_dev(a, self.device) for a in (real_train, synthetic, real_test)]
+        cs = [np.asarray(_host(a), dtype=np.float64) for a in (real_train_cond, synth_cond, real_test_cond)]
+        cs = [c.reshape(-1, 1) if c.ndim == 1 else c for c in cs]
+        K = cs[0].shape[1]
+        if names is None:
+            names = [f"c{j}" for j in range(K)]
+        names = [str(v) for v in names]
+        if K < 1 or len(names) != K:
+            raise ValueError("one name per condition column, and at least one condition")
+        for label, x, c in zip(("real_train", "synthetic", "real_test"), xs, cs):
+            if x.dim() != 2 or x.shape[1] != xs[0].shape[1] or x.shape[1] < 1:
+                raise ValueError(f"{label} must be [rows, {xs[0].shape[1]}]: the cohorts must have the same features")
+            if c.ndim != 2 or c.shape != (x.shape[0], K):
+                raise ValueError(f"the conditions of {label} must be [{x.shape[0]}, {K}], got {c.shape}")
+            if not (bool(torch.isfinite(x).all().item()) and np.isfinite(c).all()):
+                raise ValueError(f"{label} holds non-finite values")
+            if x.shape[0] < 2 and not (self.comm.on and label == "synthetic"):
+                raise ValueError(f"{label} has {x.shape[0]} rows: a fit needs at least 2")
+        return self._agree(utility_metrics(self.comm, self.k, xs[0], cs[0], xs[1], cs[1], xs[2], cs[2], names, l2=float(l2),
+                                           max_iter=int(max_iter), tol=float(tol)))
+
+    def discriminator_test(self, real, synthetic, test_fraction: float = 0.3, seed: int = 0, l2: float = 1e-2, max_iter: int = 200,
+                           tol: float = 1e-5) -> Dict[str, float]:
+        """The classifier two-sample test: can an L2-regularised logistic model of the features tell real (0) from synthetic (1)?
+        Each cohort is split by a seeded permutation, the model is fitted on the training parts -- features standardised by the
+        two together, row weights that give both classes the same total weight, the two cohorts evaluated as two
+        ``DeviceKernels.glm_eval`` calls whose sums are added, never concatenated -- and the held-out rows give ``c2st_auc``,
+        ``c2st_accuracy`` (balanced) and ``c2st_pmse``, the mean of (p - 1/2)^2.  0.5, 0.5 and 0 mean the cohorts are
+        indistinguishable; 1, 1 and 1/4 that every held-out row is told apart with certainty.  On a ``sharded=True`` validator
+        ``synthetic`` is this rank's row shard."""
+        x, y = _dev(real, self.device), _dev(synthetic, self.device)
+        for label, t in (("real", x), ("synthetic", y)):
+            if t.dim() != 2 or t.shape[1] != x.shape[1] or t.shape[1] < 1:
+                raise ValueError(f"{label} must be [rows, {x.shape[1]}]: the cohorts must have the same features")
+            if not bool(torch.isfinite(t).all().item()):
+                raise ValueError(f"{label} holds non-finite values")
+        return self._agree(c2st_metrics(self.comm, self.k, x, y, test_fraction=float(test_fraction), seed=int(seed), l2=float(l2),
+                                        max_iter=int(max_iter), tol=float(tol)))
+
     # -- privacy: membership inference on the per-record likelihood bound (DESIGN.md section 3.18) ---------------------
     def membership_audit(self, model, train, holdout, *, num_timesteps: int = 32, seed: int = 0) -> Dict[str, float]:
         """The loss-threshold membership-inference attack on a diffusion model: ``train`` and ``holdout`` are (data, conditions)
@@ -845,8 +1100,11 @@ class BiologicalValidator:
     def validate_all(self, real_mutations, real_expression, real_pathways, synth_mutations, synth_expression, synth_pathways,
                      pathway_gene_matrix=None, privacy: bool = False, holdout=None, model=None, membership=None,
                      prdc: bool = False, prdc_k: int = 5, correlation: bool = False, frechet: bool = False,
-                     corr_strong: float = 0.3) -> Dict[str, float]:
-        """``correlation=True`` adds ``correlation_fidelity``'s ``corr_*`` keys (blocks ``mutations`` / ``expression`` / ``pathways``
+                     corr_strong: float = 0.3, utility=None, c2st: bool = False) -> Dict[str, float]:
+        """``utility=(real_train_cond, synth_cond, real_test, real_test_cond)`` adds ``downstream_utility``'s ``utility_*`` keys: the
+        combined real matrix is the training cohort, ``real_test`` a (mutations, expression, pathways) triple of held-out real
+        patients (or their combined matrix); ``c2st=True`` adds ``discriminator_test``'s ``c2st_*`` keys on the combined matrices.
+        ``correlation=True`` adds ``correlation_fidelity``'s ``corr_*`` keys (blocks ``mutations`` / ``expression`` / ``pathways``
         from the three frames' widths, strong pairs from |r_real| >= ``corr_strong``) and ``frechet=True`` its ``frechet_*`` keys, on the
         same combined matrices as the statistical tests.  ``prdc=True`` adds ``fidelity_diversity``'s keys (``prdc_k`` neighbours), on the same combined matrices as the statistical
         tests.  ``privacy=True`` adds ``privacy_audit``'s keys, on the same combined matrices as the statistical tests; ``holdout`` is
@@ -888,6 +1146,19 @@ class BiologicalValidator:
             widths = {"mutations": parts_r[0].shape[1], "expression": parts_r[1].shape[1], "pathways": parts_r[2].shape[1]}
             second = self.correlation_fidelity(real_combined, synth_combined, blocks=widths, strong=corr_strong, frechet=frechet)
             all_results.update({key: v for key, v in second.items() if correlation or key.startswith("frechet_")})
+        if utility is not None:
+            if not isinstance(utility, (tuple, list)) or len(utility) != 4:
+                raise ValueError("validate_all(utility=...) needs (real_train_cond, synth_cond, real_test, real_test_cond)")
+            train_cond, synth_cond, test, test_cond = utility
+            if isinstance(test, (tuple, list)):
+                parts_t = [p.values for p in test]
+                if all(isinstance(p, torch.Tensor) for p in parts_t):
+                    test = torch.cat(parts_t, dim=1)
+                else:
+                    test = np.concatenate([_host(p) for p in parts_t], axis=1)
+            all_results.update(self.downstream_utility(real_combined, train_cond, synth_combined, synth_cond, test, test_cond))
+        if c2st:
+            all_results.update(self.discriminator_test(real_combined, synth_combined))
         logger.info("=" * 50)
         logger.info("VALIDATION SUMMARY")
         logger.info("=" * 50)
