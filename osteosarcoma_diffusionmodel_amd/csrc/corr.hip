@@ -22,6 +22,7 @@
 #include <vector>
 #include "gemm_glds.h"
 #include "handle.h"
+#include "val_common.h"
 
 namespace osd {
 namespace {
@@ -254,8 +255,7 @@ __global__ __launch_bounds__(256) void corr_compare_kernel(const double* __restr
   int ba, bb;
   tri_decode(blockIdx.y, nb, ba, bb);
   const int ilo = bounds[ba], ihi = bounds[ba + 1], jlo = bounds[bb], jhi = bounds[bb + 1];
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
+  const auto [lane, wave, nw] = wave_rows<int>();
   unsigned long long n = 0, ns = 0, na = 0;
   double s1 = 0.0, s2 = 0.0, mx = 0.0, s3 = 0.0;
   for (int i = ilo + wave; i < ihi; i += nw) {
@@ -272,13 +272,8 @@ __global__ __launch_bounds__(256) void corr_compare_kernel(const double* __restr
       if (fabs(rr) >= strong) { ++ns; na += sgn(rs) == sgn(rr) ? 1 : 0; s3 += ad; }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    n += __shfl_xor(n, o); ns += __shfl_xor(ns, o); na += __shfl_xor(na, o);
-    s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); s3 += __shfl_xor(s3, o);
-    const double m2 = __shfl_xor(mx, o);
-    mx = m2 > mx ? m2 : mx;
-  }
+  wave_sum(n, ns, na, s1, s2, s3);
+  wave_max(mx);
   if (lane == 0 && n > 0) {
     CorrSlot* s = slots + blockIdx.y;
     atomicAdd(&s->pairs, n); atomicAdd(&s->strong, ns); atomicAdd(&s->agree, na);
@@ -286,12 +281,6 @@ __global__ __launch_bounds__(256) void corr_compare_kernel(const double* __restr
     atomicMax(&s->max_bits, (unsigned long long)__double_as_longlong(mx));
   }
 }
-
-struct Buf {
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  ~Buf() { if (p) { hipError_t e = hipFree(p); (void)e; } }
-};
 
 // Row slices of a tile, from the tile count and the CU count alone (the workspace is n_tri * S slabs whatever the number of rows).
 // The kernel holds one workgroup per CU, so a launch of n_tri * S items runs in ceil(n_tri * S / cus) rounds of 1 / S of a tile's
@@ -332,7 +321,7 @@ int osd_val_centered_gram(void* stream, int device, const float* X, int64_t rows
   a.rows = (int)rows; a.D = D; a.Dq = Dq; a.nt = nt;
   a.S = cov_slices(n_tri, cus);
   a.rows_per = (int)(((rows + a.S - 1) / a.S + COV_BK - 1) / COV_BK * COV_BK);
-  Buf cen, slab, pad;
+  DevBuf cen, slab, pad;
   OSD_HIP(cen.alloc((size_t)nt * COV_TILE * sizeof(float)));
   OSD_HIP(slab.alloc((size_t)n_tri * a.S * COV_SLAB_ELEMS * sizeof(double)));
   OSD_HIP(hipMemsetAsync(cen.p, 0, (size_t)nt * COV_TILE * sizeof(float), s));
@@ -343,14 +332,11 @@ int osd_val_centered_gram(void* stream, int device, const float* X, int64_t rows
     a.X = X; a.ld = ld;
   } else {                                                   // 16-byte LDS-DMA cannot read this X in place
     OSD_HIP(pad.alloc((size_t)rows * Dq * sizeof(float)));
-    hipLaunchKernelGGL(cov_pad_copy, 2048, 256, 0, s, X, (long long)ld, (long long)rows, D, Dq, (float*)pad.p);
-    OSD_HIP(hipGetLastError());
+    OSD_HIP(launched(cov_pad_copy, 2048, 256, 0, s, X, (long long)ld, (long long)rows, D, Dq, pad.as<float>()));
     a.X = (const float*)pad.p; a.ld = Dq;
   }
-  hipLaunchKernelGGL(cov_gram_kernel, dim3((unsigned)(n_tri * a.S)), dim3(COV_THREADS), COV_LDS_BYTES, s, a);
-  OSD_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cov_gram_reduce, dim3((unsigned)n_tri), dim3(256), 0, s, (const double*)slab.p, a.S, nt, D, G_dev);
-  OSD_HIP(hipGetLastError());
+  OSD_HIP(launched(cov_gram_kernel, dim3((unsigned)(n_tri * a.S)), dim3(COV_THREADS), COV_LDS_BYTES, s, a));
+  OSD_HIP(launched(cov_gram_reduce, dim3((unsigned)n_tri), dim3(256), 0, s, slab.as<const double>(), a.S, nt, D, G_dev));
   OSD_HIP(hipStreamSynchronize(s));
   return OSD_OK;
 }
@@ -368,7 +354,7 @@ int osd_val_corr_compare(void* stream, int device, const double* G_real, const d
   OSD_HIP(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const int n_pairs = n_blocks * (n_blocks + 1) / 2;
-  Buf diag, flags, bnd, res;
+  DevBuf diag, flags, bnd, res;
   OSD_HIP(diag.alloc((size_t)2 * D * sizeof(double)));
   OSD_HIP(flags.alloc((size_t)D * sizeof(int)));
   OSD_HIP(bnd.alloc((size_t)(n_blocks + 1) * sizeof(int)));
@@ -378,17 +364,14 @@ int osd_val_corr_compare(void* stream, int device, const double* G_real, const d
   double* dr = (double*)diag.p; double* ds = dr + D;
   OSD_HIP(hipMemsetAsync(res.p, 0, sizeof(unsigned long long) + (size_t)n_pairs * sizeof(CorrSlot), s));
   OSD_HIP(hipMemcpyAsync(bnd.p, bounds_host, (size_t)(n_blocks + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(corr_diag, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, G_real, G_synth, D, dr, ds, (int*)flags.p, n_const);
-  OSD_HIP(hipGetLastError());
+  OSD_HIP(launched(corr_diag, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, G_real, G_synth, D, dr, ds, flags.as<int>(), n_const));
   // up to 256 wavefronts walk the rows of a block; one set of atomics per wavefront and block pair
   int gx = (D / n_blocks + 3) / 4;
   gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
-  hipLaunchKernelGGL(corr_compare_kernel, dim3((unsigned)gx, (unsigned)n_pairs), dim3(256), 0, s, G_real, G_synth, D, (const int*)bnd.p,
-                     n_blocks, (const double*)dr, (const double*)ds, (const int*)flags.p, strong, slots);
-  OSD_HIP(hipGetLastError());
+  OSD_HIP(launched(corr_compare_kernel, dim3((unsigned)gx, (unsigned)n_pairs), dim3(256), 0, s, G_real, G_synth, D, bnd.as<const int>(),
+                   n_blocks, dr, ds, flags.as<const int>(), strong, slots));
   std::vector<unsigned long long> raw((size_t)1 + (size_t)n_pairs * OSD_CORR_STATS);
-  OSD_HIP(hipMemcpyAsync(raw.data(), res.p, raw.size() * 8, hipMemcpyDeviceToHost, s));
-  OSD_HIP(hipStreamSynchronize(s));
+  OSD_HIP(read_back(s, raw.data(), res.p, raw.size() * 8));
   out_host[0] = (double)raw[0];
   for (int p = 0; p < n_pairs; ++p) {
     CorrSlot c;

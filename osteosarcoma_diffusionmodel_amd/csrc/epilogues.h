@@ -1000,6 +1000,26 @@ struct EpiRowSq {
   }
 };
 
+// ---- what the four Gram-distance epilogues below share ---------------------------------------------------------------------
+// A = the tile's feature side (rows f), B = its patient side (rows p); acc = a_f . b_p.  The squared norms of the A rows ride in
+// registers from before the K loop, the layout of the accumulator quads: sq[fb][q] holds rows fw + 32 fb + 8 q + 4 h .. + 3.
+template <int NFB> struct GramNorms { float4 sq[NFB][4]; };
+template <int NFB, bool FAST>
+__device__ __forceinline__ GramNorms<NFB> gram_norms(const float* sq, int fw, int lane, int F) {
+  GramNorms<NFB> r;
+  const int h = lane >> 5;
+#pragma unroll
+  for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) r.sq[fb][q] = ldq<FAST>(sq, fw + 32 * fb + 8 * q + 4 * h, F);
+  return r;
+}
+// the expanded squared distance |a|^2 + |b|^2 - 2 a.b, clamped at 0 (it cancels for near copies: callers that report a distance
+// recompute it, k_knn_refine)
+__device__ __forceinline__ float gram_d2(float sa, float sb, float acc) { return fmaxf(sa + sb - 2.0f * acc, 0.f); }
+// FAST reads the A-side norms as aligned quads
+inline bool gram_fast_ok(const float* sq, int F) { return F % 4 == 0 && al16(sq); }
+
 // ---- RBF-kernel sum for the MMD metric (utils/validation.py:287-296) -------------------------------
 // acc = x_f . y_p;  d2 = |x_f|^2 + |y_p|^2 - 2 acc;  sum += exp(-gamma * max(d2, 0)) over the valid tile
 struct EpiRbfSum {
@@ -1013,18 +1033,10 @@ struct EpiRbfSum {
   // strictly above the diagonal stands for its mirror image too and counts twice; the diagonal tiles are computed whole
   // (utils/validation.py:286-296 sums the full matrix, diagonal included)
   struct Args { const float* sqa; const float* sqb; float gamma; double* sum; int tri; };
-  static bool fast_ok(const Args& a, int F) { return F % 4 == 0 && al16(a.sqa); }
-  template <int NFB> struct Pre { float4 sqa[NFB][4]; };
+  static bool fast_ok(const Args& a, int F) { return gram_fast_ok(a.sqa, F); }
+  template <int NFB> using Pre = GramNorms<NFB>;
   template <int NFB, bool FAST>
-  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
-    Pre<NFB> r;
-    const int h = lane >> 5;
-#pragma unroll
-    for (int fb = 0; fb < NFB; ++fb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) r.sqa[fb][q] = ldq<FAST>(a.sqa, fw + 32 * fb + 8 * q + 4 * h, F);
-    return r;
-  }
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) { return gram_norms<NFB, FAST>(a.sqa, fw, lane, F); }
   template <int NFB, int NPB, bool FAST>
   static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     const int l31 = lane & 31, h = lane >> 5;
@@ -1038,11 +1050,11 @@ struct EpiRbfSum {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int f = fw + 32 * fb + 8 * q + 4 * h;
-          const float4 sa = pre.sqa[fb][q];
+          const float4 sa = pre.sq[fb][q];
           const float sav[4] = {sa.x, sa.y, sa.z, sa.w};
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float d2 = fmaxf(sav[r] + sb - 2.0f * acc[fb][pb][4 * q + r], 0.f);
+            const float d2 = gram_d2(sav[r], sb, acc[fb][pb][4 * q + r]);
             const float k = expf(-a.gamma * d2);
             part += (p < P && f + r < F) ? k : 0.f;
           }
@@ -1075,18 +1087,10 @@ struct EpiNearest {
   static constexpr unsigned long long NO_KEY = ~0ull;   // the key array's initial value: no candidate
   template <class A> static __device__ __forceinline__ void slice(A&, int) {}
   struct Args { const float* sqr; const float* sqq; const int* exclude; unsigned long long* keys; };
-  static bool fast_ok(const Args& a, int F) { return F % 4 == 0 && al16(a.sqr); }
-  template <int NFB> struct Pre { float4 sqr[NFB][4]; };
+  static bool fast_ok(const Args& a, int F) { return gram_fast_ok(a.sqr, F); }
+  template <int NFB> using Pre = GramNorms<NFB>;
   template <int NFB, bool FAST>
-  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
-    Pre<NFB> r;
-    const int h = lane >> 5;
-#pragma unroll
-    for (int fb = 0; fb < NFB; ++fb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) r.sqr[fb][q] = ldq<FAST>(a.sqr, fw + 32 * fb + 8 * q + 4 * h, F);
-    return r;
-  }
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) { return gram_norms<NFB, FAST>(a.sqr, fw, lane, F); }
   template <int NFB, int NPB, bool FAST>
   static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     const int l31 = lane & 31, h = lane >> 5;
@@ -1103,11 +1107,11 @@ struct EpiNearest {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int f = fw + 32 * fb + 8 * q + 4 * h;
-          const float4 sr = pre.sqr[fb][q];
+          const float4 sr = pre.sq[fb][q];
           const float srv[4] = {sr.x, sr.y, sr.z, sr.w};
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float d2 = fmaxf(srv[r] + sq - 2.0f * acc[fb][pb][4 * q + r], 0.f);
+            const float d2 = gram_d2(srv[r], sq, acc[fb][pb][4 * q + r]);
             const unsigned bits = (f + r < F && f + r != ex) ? __float_as_uint(d2) : 0xffffffffu;
             if (bits < best) { best = bits; best_f = f + r; }
           }
@@ -1151,12 +1155,10 @@ struct EpiKnn {
   static constexpr int MAX_K = 16;
   template <class A> static __device__ __forceinline__ void slice(A&, int) {}
   struct Args { const float* sqr; const float* sqq; const int* exclude; unsigned long long* keys; int k; int f_base; };
-  static bool fast_ok(const Args& a, int F) { return F % 4 == 0 && al16(a.sqr); }
-  template <int NFB> using Pre = EpiNearest::Pre<NFB>;
+  static bool fast_ok(const Args& a, int F) { return gram_fast_ok(a.sqr, F); }
+  template <int NFB> using Pre = GramNorms<NFB>;
   template <int NFB, bool FAST>
-  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
-    return EpiNearest::prefetch<NFB, FAST>(EpiNearest::Args{a.sqr, a.sqq, a.exclude, a.keys}, fw, lane, F);
-  }
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) { return gram_norms<NFB, FAST>(a.sqr, fw, lane, F); }
   // the signed threshold a quad's smallest distance bits are compared with
   static __device__ __forceinline__ int threshold(unsigned long long kth, bool prow) {
     const unsigned hi = (unsigned)(kth >> 32);
@@ -1181,12 +1183,12 @@ struct EpiKnn {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int f = fw + 32 * fb + 8 * q + 4 * h;
-          const float4 sr = pre.sqr[fb][q];
+          const float4 sr = pre.sq[fb][q];
           const float srv[4] = {sr.x, sr.y, sr.z, sr.w};
           int b[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float d2 = fmaxf(srv[r] + sq - 2.0f * acc[fb][pb][4 * q + r], 0.f);
+            const float d2 = gram_d2(srv[r], sq, acc[fb][pb][4 * q + r]);
             b[r] = (f + r < F && f + r != ex) ? (int)__float_as_uint(d2) : 0x7fffffff;
           }
           const int m01 = b[0] < b[1] ? b[0] : b[1], m23 = b[2] < b[3] ? b[2] : b[3];
@@ -1224,8 +1226,8 @@ struct EpiBallCount {
   static constexpr bool XBUF = false;
   template <class A> static __device__ __forceinline__ void slice(A&, int) {}
   struct Args { const float* sqr; const float* sqq; const float* r2_ref; const float* r2_query; int* in_ref; int* in_query; };
-  static bool fast_ok(const Args& a, int F) { return F % 4 == 0 && al16(a.sqr) && al16(a.r2_ref); }
-  template <int NFB> struct Pre { float4 sqr[NFB][4], r2[NFB][4]; };
+  static bool fast_ok(const Args& a, int F) { return gram_fast_ok(a.sqr, F) && al16(a.r2_ref); }
+  template <int NFB> struct Pre { GramNorms<NFB> n; float4 r2[NFB][4]; };
   template <int NFB, bool FAST>
   static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
     Pre<NFB> r;
@@ -1235,7 +1237,7 @@ struct EpiBallCount {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int f = fw + 32 * fb + 8 * q + 4 * h;
-        r.sqr[fb][q] = ldq<FAST>(a.sqr, f, F);
+        r.n.sq[fb][q] = ldq<FAST>(a.sqr, f, F);           // gram_norms, interleaved with the radii
         float4 t = make_float4(-1.f, -1.f, -1.f, -1.f);
         if (a.r2_ref) {                            // uniform
           t = ldq<FAST>(a.r2_ref, f, F);
@@ -1260,12 +1262,12 @@ struct EpiBallCount {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int f = fw + 32 * fb + 8 * q + 4 * h;
-          const float4 sr = pre.sqr[fb][q], rr = pre.r2[fb][q];
+          const float4 sr = pre.n.sq[fb][q], rr = pre.r2[fb][q];
           const float srv[4] = {sr.x, sr.y, sr.z, sr.w};
           const float rrv[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float d2 = fmaxf(srv[r] + sq - 2.0f * acc[fb][pb][4 * q + r], 0.f);
+            const float d2 = gram_d2(srv[r], sq, acc[fb][pb][4 * q + r]);
             const bool valid = FAST ? f < F : f + r < F;        // FAST: F % 4 == 0, a quad is inside or outside as a whole
             cr += d2 <= rrv[r] ? 1 : 0;
             cq += (valid && d2 <= rq) ? 1 : 0;

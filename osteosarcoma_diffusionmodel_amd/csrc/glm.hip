@@ -26,6 +26,7 @@
 #include <mutex>
 #include <vector>
 #include "handle.h"
+#include "val_common.h"
 
 namespace osd {
 namespace {
@@ -154,8 +155,7 @@ __global__ __launch_bounds__(TMAX, glm_min_waves(TMAX)) void glm_kernel(GlmArgs 
 #pragma unroll
       for (int k = 0; k < K; ++k) {
         float v = p[r][k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        wave_sum(v);
         if (lane == 0) part[par][wave][r * K + k] = v;
       }
     __syncthreads();
@@ -325,9 +325,8 @@ Workspace g_ws[GLM_MAX_DEVICES];
 template <int K, int NV, int TMAX>
 int glm_launch2(bool aligned, bool dry, unsigned items, unsigned T, hipStream_t s, const GlmArgs& a) {
   if (dry) return glm_group_rows(K, NV, TMAX, aligned);      // the rows of a group: what the partition is made from
-  if (aligned) hipLaunchKernelGGL((glm_kernel<K, NV, TMAX, true>), dim3(items), dim3(T), 0, s, a);
-  else hipLaunchKernelGGL((glm_kernel<K, NV, TMAX, false>), dim3(items), dim3(T), 0, s, a);
-  return 0;
+  // not dry: the launch's hipError_t
+  return (int)launched(aligned ? glm_kernel<K, NV, TMAX, true> : glm_kernel<K, NV, TMAX, false>, dim3(items), dim3(T), 0, s, a);
 }
 
 template <int K>
@@ -405,13 +404,10 @@ int osd_val_glm_eval(void* stream, int device, const float* X, int64_t rows, int
   a.slab = grad_dev ? a.loss_slab + (size_t)items * K : nullptr;
 
   const bool grad = grad_dev != nullptr;
-  glm_dispatch(K, NV, aligned, false, items, T, s, a);
-  OSD_HIP(hipGetLastError());
-  if (grad) {
-    hipLaunchKernelGGL(glm_reduce, dim3((unsigned)((D + 1 + 63) / 64), (unsigned)K), dim3(64 * GLM_RED_PARTS), 0, s,
-                       (const double*)a.slab, (int)items, K, D, a.Dl, scale, grad_dev);
-    OSD_HIP(hipGetLastError());
-  }
+  OSD_HIP((hipError_t)glm_dispatch(K, NV, aligned, false, items, T, s, a));
+  if (grad)
+    OSD_HIP(launched(glm_reduce, dim3((unsigned)((D + 1 + 63) / 64), (unsigned)K), dim3(64 * GLM_RED_PARTS), 0, s, a.slab, (int)items, K, D,
+                     a.Dl, scale, grad_dev));
   std::vector<double> part(loss_host ? (size_t)items * K : 0);
   if (loss_host) OSD_HIP(hipMemcpyAsync(part.data(), a.loss_slab, loss_bytes, hipMemcpyDeviceToHost, s));
   OSD_HIP(hipStreamSynchronize(s));
@@ -441,14 +437,11 @@ int osd_val_col_centered_moments(void* stream, int device, const float* X, int64
   OSD_HIP(ws.reserve(((size_t)slices * 2 * D + (size_t)2 * D) * sizeof(double)));
   double* slab = (double*)ws.p;
   double* out = slab + (size_t)slices * 2 * D;
-  hipLaunchKernelGGL(col_moments_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)slices), dim3(256), 0, s, X, (long long)ld,
-                     (long long)rows, D, center, (long long)rows_per, slab);
-  OSD_HIP(hipGetLastError());
-  hipLaunchKernelGGL(col_moments_reduce, dim3((unsigned)((2 * D + 255) / 256)), dim3(256), 0, s, (const double*)slab, (int)slices, D, out);
-  OSD_HIP(hipGetLastError());
+  OSD_HIP(launched(col_moments_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)slices), dim3(256), 0, s, X, (long long)ld,
+                   (long long)rows, D, center, (long long)rows_per, slab));
+  OSD_HIP(launched(col_moments_reduce, dim3((unsigned)((2 * D + 255) / 256)), dim3(256), 0, s, slab, (int)slices, D, out));
   std::vector<double> h((size_t)2 * D);
-  OSD_HIP(hipMemcpyAsync(h.data(), out, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  OSD_HIP(hipStreamSynchronize(s));
+  OSD_HIP(read_back(s, h.data(), out, h.size() * sizeof(double)));
   for (int i = 0; i < D; ++i) { sum_host[i] = h[i]; sumsq_host[i] = h[(size_t)D + i]; }
   return OSD_OK;
 }

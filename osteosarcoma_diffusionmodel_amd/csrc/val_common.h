@@ -1,0 +1,71 @@
+// val_common.h -- what the validator's translation units (validate.hip, corr.hip, glm.hip) share: the RAII device buffer, the
+// wavefront butterflies, the "one wavefront per row" indices, the checked kernel launch, the read-back and the column-list upload.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "handle.h"
+
+namespace osd {
+
+// A device allocation freed on scope exit.  A request for 0 bytes allocates 16: p is never null after a successful alloc.
+struct DevBuf {
+  void* p = nullptr;
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+  template <class T> T* as() const { return static_cast<T*>(p); }
+  ~DevBuf() { if (p) { hipError_t e = hipFree(p); (void)e; } }
+};
+
+// Butterflies over the 64 lanes, in place, xor distances 32, 16, ... 1: every lane ends with the result, and the fixed order gives
+// the same bits on every call.  Several values (float, double, int, long long, unsigned long long, mixed) share one walk, so their
+// exchanges overlap.
+template <class T> __device__ __forceinline__ void lane_max(T& v, int o) { const T x = __shfl_xor(v, o); v = x > v ? x : v; }
+template <class T> __device__ __forceinline__ void lane_min(T& v, int o) { const T x = __shfl_xor(v, o); v = x < v ? x : v; }
+template <class... T> __device__ __forceinline__ void wave_sum(T&... v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ((v += __shfl_xor(v, o)), ...);
+}
+template <class... T> __device__ __forceinline__ void wave_max(T&... v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) (lane_max(v, o), ...);
+}
+template <class... T> __device__ __forceinline__ void wave_min(T&... v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) (lane_min(v, o), ...);
+}
+
+// One wavefront per row over a 1-D grid: the lane, the wavefront's number in the grid (its first row) and the number of wavefronts
+// (its stride).  I: the type the row index is computed in.  Call it as wave_rows(): the default arguments are evaluated in the
+// calling kernel, where the compiler knows that workgroups are uniform and reads blockDim straight from the kernel arguments.
+template <class I> struct WaveRows { int lane; I wave, nw; };
+template <class I = int64_t>
+__device__ __forceinline__ WaveRows<I> wave_rows(unsigned tid = threadIdx.x, unsigned bid = blockIdx.x, unsigned bdim = blockDim.x,
+                                                 unsigned gdim = gridDim.x) {
+  return {(int)(tid & 63), (I)((bid * (I)bdim + tid) >> 6), (I)(((I)gdim * bdim) >> 6)};
+}
+
+// A kernel launch and its launch-error check: OSD_HIP(launched(kernel, grid, block, lds_bytes, stream, args...)).
+template <class... P, class... A>
+inline hipError_t launched(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, args...);
+  return hipGetLastError();
+}
+
+// dev -> host on the stream, then wait for the stream: the end of a synchronous entry point that returns host values
+inline hipError_t read_back(hipStream_t s, void* host, const void* dev, size_t bytes) {
+  const hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s);
+  return e != hipSuccess ? e : hipStreamSynchronize(s);
+}
+
+// A host column list, checked (1 <= g <= limit indices in [0, ld)) before anything touches the device; then the device is
+// selected and the list uploaded into dc on the stream.
+inline int upload_cols(int device, hipStream_t s, const int32_t* cols_host, int g, int ld, int limit, DevBuf& dc) {
+  if (!cols_host || g < 1 || g > limit) { set_error("bad column list (1 <= columns <= %d)", limit); return OSD_EINVAL; }
+  for (int i = 0; i < g; ++i)
+    if (cols_host[i] < 0 || cols_host[i] >= ld) { set_error("column index out of range"); return OSD_EINVAL; }
+  OSD_HIP(hipSetDevice(device));
+  OSD_HIP(dc.alloc((size_t)g * sizeof(int)));
+  OSD_HIP(hipMemcpyAsync(dc.p, cols_host, (size_t)g * sizeof(int), hipMemcpyHostToDevice, s));
+  return OSD_OK;
+}
+
+}  // namespace osd

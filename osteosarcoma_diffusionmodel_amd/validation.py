@@ -136,15 +136,11 @@ class DeviceKernels:
 
     def nearest(self, q: torch.Tensor, r: torch.Tensor, exclude: Optional[torch.Tensor] = None):
         """(d2 float32 [nq], idx int32 [nq]) device tensors: each row of q against the rows of r, row ``exclude[i]`` skipped."""
-        if q.shape[1] != r.shape[1]:
-            raise ValueError("q and r must have the same number of features")
+        _same_features(q, r)
         nq = q.shape[0]
         d2 = torch.empty(nq, dtype=torch.float32, device=q.device)
         idx = torch.empty(nq, dtype=torch.int32, device=q.device)
-        if exclude is not None:
-            exclude = exclude.to(device=q.device, dtype=torch.int32).contiguous()
-            if exclude.shape != (nq,):
-                raise ValueError("exclude must hold one index per query row")
+        exclude = _exclude(exclude, q)
         L.check(L.lib().osd_val_nearest(self._stream(), self.index, L.ptr(q), nq, L.ptr(r), r.shape[0], q.shape[1], L.ptr(exclude),
                                         L.ptr(d2), L.ptr(idx)))
         return d2, idx
@@ -152,15 +148,11 @@ class DeviceKernels:
     def knn(self, q: torch.Tensor, r: torch.Tensor, k: int, exclude: Optional[torch.Tensor] = None):
         """(d2 float32 [nq, k], idx int32 [nq, k]) device tensors: the k nearest rows of r for each row of q in ascending order of
         the recomputed distance, row ``exclude[i]`` skipped; (+inf, -1) where r has fewer than k candidates.  1 <= k <= 16."""
-        if q.shape[1] != r.shape[1]:
-            raise ValueError("q and r must have the same number of features")
+        _same_features(q, r)
         nq = q.shape[0]
         d2 = torch.empty((nq, max(int(k), 0)), dtype=torch.float32, device=q.device)
         idx = torch.empty((nq, max(int(k), 0)), dtype=torch.int32, device=q.device)
-        if exclude is not None:
-            exclude = exclude.to(device=q.device, dtype=torch.int32).contiguous()
-            if exclude.shape != (nq,):
-                raise ValueError("exclude must hold one index per query row")
+        exclude = _exclude(exclude, q)
         L.check(L.lib().osd_val_knn(self._stream(), self.index, L.ptr(q), nq, L.ptr(r), r.shape[0], q.shape[1], int(k), L.ptr(exclude),
                                     L.ptr(d2), L.ptr(idx)))
         return d2, idx
@@ -169,8 +161,7 @@ class DeviceKernels:
                     r2_query: Optional[torch.Tensor] = None):
         """(in_ref, in_query) int32 [nq] device tensors, None where the radius is None: for each row of q the number of rows of r
         within the r row's squared radius ``r2_ref[f]``, and within the q row's own squared radius ``r2_query[p]`` (``<=``)."""
-        if q.shape[1] != r.shape[1]:
-            raise ValueError("q and r must have the same number of features")
+        _same_features(q, r)
         nq, nr = q.shape[0], r.shape[0]
         outs = []
         for name, rad, n in (("r2_ref", r2_ref, nr), ("r2_query", r2_query, nq)):
@@ -191,15 +182,13 @@ class DeviceKernels:
         return np.array(dmax[:], dtype=np.int64), np.array(dmin[:], dtype=np.int64)
 
     def col_moments(self, t: torch.Tensor, cols: Sequence[int]):
-        g = len(cols)
-        arr = (C.c_int32 * g)(*cols)
+        g, arr = _col_array(cols)
         s, q = (C.c_double * g)(), (C.c_double * g)()
         L.check(L.lib().osd_val_col_moments(self._stream(), self.index, L.ptr(t), t.shape[0], t.shape[1], arr, g, s, q))
         return np.array(s[:]), np.array(q[:])
 
     def rowz_sq(self, t: torch.Tensor, cols: Sequence[int], mu: np.ndarray, isd: np.ndarray) -> float:
-        g = len(cols)
-        arr = (C.c_int32 * g)(*cols)
+        g, arr = _col_array(cols)
         out = C.c_double()
         L.check(L.lib().osd_val_rowz_sq(self._stream(), self.index, L.ptr(t), t.shape[0], t.shape[1], arr, g, (C.c_double * g)(*mu),
                                         (C.c_double * g)(*isd), C.byref(out)))
@@ -217,10 +206,9 @@ class DeviceKernels:
         return np.array(out[:])
 
     def gram(self, t: torch.Tensor, cols: Sequence[int]) -> np.ndarray:
-        g = len(cols)
+        g, arr = _col_array(cols)
         if g > 64:
             raise ValueError("at most 64 columns per Gram block")
-        arr = (C.c_int32 * g)(*cols)
         out = (C.c_double * (g * g))()
         L.check(L.lib().osd_val_gram(self._stream(), self.index, L.ptr(t), t.shape[0], t.shape[1], arr, g, out))
         return np.array(out[:]).reshape(g, g)
@@ -229,10 +217,7 @@ class DeviceKernels:
         """float64 [D, D] DEVICE tensor G[i][j] = sum_r (t[r][i] - c[i]) (t[r][j] - c[j]) over all D columns of the fp32 device
         tensor t (``osd_val_centered_gram``: fp32 differences and products, double sums, exactly symmetric, the same bits on every
         call).  ``center``: D values, rounded to fp32 -- what the kernel subtracts.  A column-slice view is read in place."""
-        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-            raise ValueError("centered_gram needs a [rows >= 1, features >= 1] tensor")
-        if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-            t = t.to(torch.float32).contiguous()
+        t = _rows_view(t, "centered_gram needs a [rows >= 1, features >= 1] tensor")
         rows, D = t.shape
         c = np.ascontiguousarray(center, dtype=np.float32)
         if c.shape != (D,):
@@ -299,10 +284,29 @@ class DeviceKernels:
         return (None if loss is None else np.array(loss[:K])), (None if g is None else g.cpu().numpy()), z
 
 
-def _rows_view(t: torch.Tensor) -> torch.Tensor:
+def _same_features(q: torch.Tensor, r: torch.Tensor) -> None:
+    if q.shape[1] != r.shape[1]:
+        raise ValueError("q and r must have the same number of features")
+
+
+def _exclude(exclude: Optional[torch.Tensor], q: torch.Tensor) -> Optional[torch.Tensor]:
+    """``exclude`` as a contiguous int32 tensor on q's device, one index per row of q (None stays None)."""
+    if exclude is not None:
+        exclude = exclude.to(device=q.device, dtype=torch.int32).contiguous()
+        if exclude.shape != (q.shape[0],):
+            raise ValueError("exclude must hold one index per query row")
+    return exclude
+
+
+def _col_array(cols: Sequence[int]):
+    """(g, ctypes int32 [g]): a column list as the library takes it."""
+    return len(cols), (C.c_int32 * len(cols))(*cols)
+
+
+def _rows_view(t: torch.Tensor, what: str = "a [rows >= 1, features >= 1] tensor is needed") -> torch.Tensor:
     """t as an fp32 [rows >= 1, D >= 1] tensor whose rows are contiguous (stride(1) == 1, stride(0) >= D): itself where it already is."""
     if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError("a [rows >= 1, features >= 1] tensor is needed")
+        raise ValueError(what)
     if t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
         t = t.to(torch.float32).contiguous()
     return t
