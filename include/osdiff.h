@@ -136,7 +136,7 @@ int osd_set_option(osd_handle *h, const char *name, int64_t value);
  * (1 when "precision" 1 applies to this model), "panel_chain_supported" / "squad_chain_supported" (1 when "chain_variant"
  * 2 / 3 applies to this model), "last_train_path" (what the most recent osd_train_loss_fwd_bwd or osd_denoiser_backward call on
  * the handle ran, an OR of the OSD_TP_* bits below; cleared at the start of either call), "prediction_type" (OSD_PRED_*, what
- * osd_set_prediction set last; 0 on a new handle).  Any other name: OSD_EINVAL. */
+ * osd_set_prediction set last; 0 on a new handle), "loss_mask" (0 | 1, what osd_set_loss_mask set last).  Any other name: OSD_EINVAL. */
 int osd_get_option(osd_handle *h, const char *name, int64_t *value);
 
 /* "last_train_path" bits */
@@ -154,6 +154,7 @@ int osd_get_option(osd_handle *h, const char *name, int64_t *value);
 #define OSD_TP_LOSS_EPI      (1 << 11)  /* output_proj ran the configurable loss epilogue (osd_set_loss); never set on the default path */
 #define OSD_TP_TARGET        (1 << 12)  /* q_sample wrote a non-eps training target (osd_set_prediction); never set on the default path */
 #define OSD_TP_DP_CLIP       (1 << 13)  /* per-row gradient clipping ran (osd_set_dp_clip); never set on the default path */
+#define OSD_TP_MASKED        (1 << 14)  /* NaN-masked q_sample and loss epilogue ran (osd_set_loss_mask); never set on the default path */
 
 /* Schedule + time-embedding tables, computed by the host with the reference's own
  * fp32 expressions so they are bit-identical (models/diffusion.py:299-326, 131-137,
@@ -209,7 +210,9 @@ int osd_q_sample(osd_handle *h, const float *x0, const int32_t *t_index, const f
 int osd_set_prediction(osd_handle *h, int type);
 
 /* osd_q_sample that writes the current type's training target where osd_q_sample writes the noise: target_out dev [n][D], required,
- * distinct from noise_in and x0.  For OSD_PRED_EPSILON it is osd_q_sample (target_out = the noise). */
+ * distinct from noise_in and x0.  For OSD_PRED_EPSILON it is osd_q_sample (target_out = the noise).  Under osd_set_loss_mask it returns
+ * what the training call forms: x_t of the zero-filled x0 and the target with NaN at the unobserved elements, for every type; target_out
+ * must then be a buffer of its own for OSD_PRED_EPSILON too. */
 int osd_q_sample_target(osd_handle *h, const float *x0, const int32_t *t_index, const float *noise_in,
                         int64_t n, uint64_t seed, int64_t row_offset, float *x_t, float *target_out);
 
@@ -718,6 +721,26 @@ int osd_get_loss_parts(osd_handle *h, float *parts_host3);
 #define OSD_LOSS_L1    1
 #define OSD_LOSS_HUBER 2
 int osd_set_loss(osd_handle *h, int kind, double huber_delta, const float *t_weights_host);
+
+/* ---- training on incomplete rows -----------------------------------------------------------------
+ * enable != 0: a NaN element of x0 means "not observed" (MissDiff, Ouyang et al. 2023).  With m = !isnan(x0), x~0 = m ? x0 : 0:
+ *   x_t    = a_t x~0 + b_t eps                                 (two rounded products, one add: osd_q_sample on x~0)
+ *   target = eps | a_t eps - b_t x~0 | x~0                     (osd_set_prediction), kept in the workspace with NaN where m is false
+ *   loss   = 1/(n D) * sum_r w[t_r] * sum_f m_rf rho(out_rf - target_rf)
+ *   dL/d out_rf = m_rf * loss_scale/(n D) * w[t_r] * rho'(.)   (exactly 0 where m is false)
+ * for every kind and weight table of osd_set_loss.  The NaN in the target buffer is the mask: no mask tensor exists.  The mean stays
+ * over n D -- NOT the number of observed elements -- so every observed element of a dataset weighs the same whichever batch it lands
+ * in, an all-missing batch gives loss 0 and zero gradients, and loss_scale keeps its meaning under data parallel.  A resident batch
+ * source (osd_train_batch_source) is mixed first, NaN propagating: a mixed element is observed iff both parents are.  Inf is not a
+ * marker and conditions must be finite.  With an all-finite batch x_t and the target have the bits of the unmasked call.
+ * Such a call runs the masked q_sample kernels and the masked loss epilogue (EpiLossT<true>, csrc/epilogues.h; the default l2 objective
+ * too) on the fp32 launcher -- also under "precision" 1, whose weight gradients are unaffected --, reads the target from the workspace
+ * even when the caller injected eps, and sets OSD_TP_MASKED | OSD_TP_LOSS_EPI.  osd_q_sample_target follows the setting.
+ * OSD_EUNSUPPORTED, before any launch and before any gradient buffer is touched: osd_train_loss_fwd_bwd with constraint losses
+ * configured (batch statistics over x0^ and x0) or with gradients under osd_set_dp_clip; osd_row_sq_error and osd_bound_sweep.
+ * Persistent on the handle like osd_set_loss; host state only, no synchronisation.  0, the state of a new handle, restores exactly the
+ * launches of a handle that never called this.  OSD_EINVAL: a null handle. */
+int osd_set_loss_mask(osd_handle *h, int enable);
 
 /* ---- the per-patient likelihood bound ----------------------------------------------------------
  * se[r] = sum_d (out[r][d] - target[r][d])^2: an eval-mode forward of q_sample(x0, t_r) and the per-row squared error of the network's

@@ -431,6 +431,7 @@ static const Counter COUNTERS[] = {
     {"last_squad_panel", [](osd_handle* h) -> int64_t { return h->last_squad_rp; }},
     {"last_train_path", [](osd_handle* h) -> int64_t { return h->last_train_path; }},
     {"prediction_type", [](osd_handle* h) -> int64_t { return h->pred_type; }},
+    {"loss_mask", [](osd_handle* h) -> int64_t { return h->loss_mask ? 1 : 0; }},
 };
 
 }  // namespace osd
@@ -787,7 +788,7 @@ int osd_set_prediction(osd_handle* h, int type) {
 int osd_q_sample_target(osd_handle* h, const float* x0, const int32_t* t_index, const float* noise_in, int64_t n, uint64_t seed,
                         int64_t row_offset, float* x_t, float* target_out) {
   if (!h || !h->have_schedule) { set_error("schedule not set"); return OSD_ESTATE; }
-  if (h->pred_type == OSD_PRED_EPSILON) {
+  if (h->pred_type == OSD_PRED_EPSILON && !h->loss_mask) {
     // the target is the noise: osd_q_sample, plus the copy it skips when the caller injected the noise
     OSD_TRY(osd_q_sample(h, x0, t_index, noise_in, n, seed, row_offset, x_t, noise_in ? nullptr : target_out));
     if (noise_in && target_out && target_out != noise_in && n > 0)
@@ -802,7 +803,7 @@ int osd_q_sample_target(osd_handle* h, const float* x0, const int32_t* t_index, 
   const int* t_idx = nullptr;
   OSD_TRY(sanitize_t(h, h->stream, t_index, n, &t_idx));
   OSD_HIP(launch_q_sample(h->stream, x0, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise_in, n, h->arch.D, seed, (uint32_t)row_offset, x_t, target_out,
-                          nullptr, 0, 0, nullptr, h->pred_type));
+                          nullptr, 0, 0, nullptr, h->pred_type, h->loss_mask));
   return OSD_OK;
 }
 

@@ -798,7 +798,11 @@ struct EpiMse {
 // spills 22 VGPRs).  EpiMse's structure otherwise, path for path: the transposer on full row segments when
 // FAST, the guarded form elsewhere; padding rows and columns carry d = 0, and rho(0) = rho'(0) = 0 for every kind; one reduction
 // per workgroup and one float atomic on the transposer path.
-struct EpiLoss {
+// MASKED (osd_set_loss_mask): a NaN component of the target means "not observed" (k_elem.hip: mask_mark);
+// its d is zeroed right after d = e - nz, so it adds rho(0) = 0 to the loss and rho'(0) = 0 to dout -- one compare and one select
+// per element, nothing held across the tile.  pred is not written (only the constraint losses read it, and they are refused).
+template <bool MASKED>
+struct EpiLossT {
   static constexpr bool COUNTED_STORES = false;   // dout / pred are optional
   static constexpr bool XBUF = true;
   template <class A> static __device__ __forceinline__ void slice(A&, int) {}
@@ -835,6 +839,10 @@ struct EpiLoss {
     part += w * q;
     d.x = d.x * w * gs; d.y = d.y * w * gs; d.z = d.z * w * gs; d.w = d.w * w * gs;
   }
+  // MASKED: d = 0 where the target component is NaN
+  static __device__ __forceinline__ void unobserved(const float4& nz, float4& d) {
+    d.x = nz.x != nz.x ? 0.f : d.x; d.y = nz.y != nz.y ? 0.f : d.y; d.z = nz.z != nz.z ? 0.f : d.z; d.w = nz.w != nz.w ? 0.f : d.w;
+  }
   template <int NFB, int NPB, bool FAST>
   static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& al, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
                                                float* xbuf = nullptr) {
@@ -867,8 +875,10 @@ struct EpiLoss {
             const float4 bv = pre.bias[fb][q];
             const float4 nz = xp.get(pb, q, l31, h);
             const float4 e = make_float4(acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w);
-            if (a.pred && prow) stq<FAST>(a.pred + (size_t)(pw + p) * a.ldp, fw + 32 * fb + fo, F, e);
+            if constexpr (!MASKED)
+              if (a.pred && prow) stq<FAST>(a.pred + (size_t)(pw + p) * a.ldp, fw + 32 * fb + fo, F, e);
             float4 d = make_float4(e.x - nz.x, e.y - nz.y, e.z - nz.z, e.w - nz.w);
+            if constexpr (MASKED) unobserved(nz, d);
             if (!prow || fo >= cols) d.x = 0.f;
             if (!prow || fo + 1 >= cols) d.y = 0.f;
             if (!prow || fo + 2 >= cols) d.z = 0.f;
@@ -896,8 +906,10 @@ struct EpiLoss {
       const float4 bv = pre.bias[fb][q];
       const float4 nz = ldq<FAST>(a.noise + (size_t)pc * a.ldn, f, F);
       const float4 e = make_float4(acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w);
-      if (a.pred && prow) stq<FAST>(a.pred + (size_t)p * a.ldp, f, F, e);
+      if constexpr (!MASKED)
+        if (a.pred && prow) stq<FAST>(a.pred + (size_t)p * a.ldp, f, F, e);
       float4 d = make_float4(e.x - nz.x, e.y - nz.y, e.z - nz.z, e.w - nz.w);
+      if constexpr (MASKED) unobserved(nz, d);
       if (!prow || f >= F) d.x = 0.f;
       if (!prow || f + 1 >= F) d.y = 0.f;
       if (!prow || f + 2 >= F) d.z = 0.f;
@@ -910,6 +922,7 @@ struct EpiLoss {
     if (lane == 0) atomicAdd(a.loss, part * a.inv_count);
   }
 };
+using EpiLoss = EpiLossT<false>;
 
 // ---- output_proj fused with a PER-ROW squared error against the training target ----
 // d = (acc + bias) - target;  part[slot][row] = sum over the wave's features of d^2

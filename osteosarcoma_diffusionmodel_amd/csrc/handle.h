@@ -227,6 +227,9 @@ struct osd_handle {
   float* d_pq = nullptr; int conv_kind = -1;
   int loss_kind = 0; float loss_delta = 1.0f;
   float* loss_tw = nullptr; bool loss_tw_set = false;
+  // training on incomplete rows (osd_set_loss_mask): persistent.  NaN in x0 = not observed; the q_sample kernels zero-fill it and mark the
+  // target with NaN, the loss runs EpiLossT<true> on the fp32 launcher.  false: today's launches
+  bool loss_mask = false;
   // differentially private training (osd_set_dp_clip; dp.h): persistent.  dp_clip = the per-row gradient bound C (0: off, today's launches);
   // dp_norms = dev [2][dp_norms_cap]: s_r, then the clip factors c_r, of the last clipped call's dp_rows rows (-1: none yet); dp_plan = the
   // cached item lists of the two launches (k_dp.hip)

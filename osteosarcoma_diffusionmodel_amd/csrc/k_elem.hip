@@ -102,7 +102,19 @@ __device__ __forceinline__ float4 q_target(float a, float b, const float4& x, co
   }
 }
 
-template <int KIND>
+// Training on incomplete rows (osd_set_loss_mask): a NaN element of x0 is "not observed".  MASKED kernels
+// test x != x per element (after the mixup: a mixed element is observed iff both parents are), take 0 in its place for x_t and for
+// the target, and store the target with NaN at the unobserved elements -- the NaN in the target buffer is the mask the loss epilogue
+// reads (epilogues.h: EpiLossT<true>), no mask tensor exists.  With no NaN in x0 the stored bits are the unmasked kernel's.
+__device__ __forceinline__ float4 mask_fill(const float4& x) {
+  return make_float4(x.x != x.x ? 0.f : x.x, x.y != x.y ? 0.f : x.y, x.z != x.z ? 0.f : x.z, x.w != x.w ? 0.f : x.w);
+}
+__device__ __forceinline__ float4 mask_mark(const float4& x, const float4& v) {
+  const float qn = __builtin_nanf("");
+  return make_float4(x.x != x.x ? qn : v.x, x.y != x.y ? qn : v.y, x.z != x.z ? qn : v.z, x.w != x.w ? qn : v.w);
+}
+
+template <int KIND, bool MASKED>
 __global__ void k_q_sample(const float* x0, const int* t, const float* sqrt_ac, const float* sqrt_1m, const float* noise_in,
                            int64_t rows, int cols, uint64_t seed, uint32_t row_offset, float* x_t, int ldxt, float* noise_out, int* t_out, int T,
                            ZeroList zl) {
@@ -120,7 +132,9 @@ __global__ void k_q_sample(const float* x0, const int* t, const float* sqrt_ac, 
       if (c == 0) t_out[r] = tt;
     }
     const float a = sqrt_ac[tt], b = sqrt_1m[tt];
-    const float4 x = ld4g(x0 + r * cols, c, cols);
+    const float4 xr = ld4g(x0 + r * cols, c, cols);
+    float4 x = xr;
+    if constexpr (MASKED) x = mask_fill(xr);
     float4 n;
     if (noise_in) n = ld4g(noise_in + r * cols, c, cols);
     else n = randn4(seed, row_offset + (uint32_t)r, (uint32_t)(c >> 2), 0u, TAG_QNOISE);
@@ -131,22 +145,29 @@ __global__ void k_q_sample(const float* x0, const int* t, const float* sqrt_ac, 
     o.w = __fadd_rn(__fmul_rn(a, x.w), __fmul_rn(b, n.w));
     st4g(x_t + r * ldxt, c, cols, o);
     zero_pad(x_t + r * ldxt, cols, ldxt, c);
-    if constexpr (KIND == OSD_PRED_EPSILON) {
+    if constexpr (MASKED) {
+      if (noise_out) st4g(noise_out + r * cols, c, cols, mask_mark(xr, q_target<KIND>(a, b, x, n)));
+    } else if constexpr (KIND == OSD_PRED_EPSILON) {
       if (noise_out && noise_out != noise_in) st4g(noise_out + r * cols, c, cols, n);
     } else {
       if (noise_out) st4g(noise_out + r * cols, c, cols, q_target<KIND>(a, b, x, n));
     }
   }
 }
+template <bool MASKED>
+static auto pick_q_sample(int kind) {
+  return kind == OSD_PRED_V ? k_q_sample<OSD_PRED_V, MASKED> : kind == OSD_PRED_SAMPLE ? k_q_sample<OSD_PRED_SAMPLE, MASKED> : k_q_sample<OSD_PRED_EPSILON, MASKED>;
+}
 hipError_t launch_q_sample(hipStream_t s, const float* x0, const int* t, const float* sqrt_ac, const float* sqrt_1m,
                            const float* noise_in, int64_t rows, int cols, uint64_t seed, uint32_t row_offset,
-                           float* x_t, float* noise_out, int* t_out, int T, int ldxt, const ZeroList* zl, int kind) {
+                           float* x_t, float* noise_out, int* t_out, int T, int ldxt, const ZeroList* zl, int kind, bool masked) {
   if (rows <= 0) return hipSuccess;
   if (!t && (!t_out || T < 1)) return hipErrorInvalidValue;
-  if (kind != OSD_PRED_EPSILON && (noise_out == noise_in || noise_out == x0)) return hipErrorInvalidValue;   // the target needs a buffer of its own
+  // the target needs a buffer of its own; under the mask (its NaN marks) for every kind
+  if ((kind != OSD_PRED_EPSILON || masked) && (noise_out == noise_in || noise_out == x0)) return hipErrorInvalidValue;
   ZeroList z{};
   if (zl) z = *zl;
-  auto k = kind == OSD_PRED_V ? k_q_sample<OSD_PRED_V> : kind == OSD_PRED_SAMPLE ? k_q_sample<OSD_PRED_SAMPLE> : k_q_sample<OSD_PRED_EPSILON>;
+  auto k = masked ? pick_q_sample<true>(kind) : pick_q_sample<false>(kind);
   hipLaunchKernelGGL(k, ew_grid(rows * ((cols + 3) / 4)), 256, 0, s, x0, t, sqrt_ac, sqrt_1m, noise_in, rows, cols, seed,
                      row_offset, x_t, ldxt > 0 ? ldxt : cols, noise_out, t_out, T, z);
   return hipGetLastError();
@@ -162,7 +183,7 @@ hipError_t launch_q_sample(hipStream_t s, const float* x0, const int* t, const f
 // quads per thread in flight at D = 2000.  First version (one quad per thread over a flat index): 37 us = 3.6 TB/s; row by row with
 // the zero list folded in: 40 us; all QS_ROWS rows' loads ahead of the stores: 35.4 us = 3.8 TB/s (QS_ROWS 2: 35.9, 8: 46.8).
 constexpr int QS_ROWS = 4;
-template <int KIND>
+template <int KIND, bool MASKED>
 __global__ __launch_bounds__(256) void k_q_sample_src(BatchSrc b, const int* t, const float* sqrt_ac, const float* sqrt_1m, const float* noise_in,
                                                       int64_t rows, int cols, int cd, uint64_t seed, uint32_t row_offset, float* x_t, int ldxt,
                                                       float* noise_out, int* t_out, int T, float* cond_out, float* x0_out, ZeroList zl) {
@@ -222,6 +243,8 @@ __global__ __launch_bounds__(256) void k_q_sample_src(BatchSrc b, const int* t, 
           xv.z = __fadd_rn(__fmul_rn(b.lam, xv.z), __fmul_rn(b.oml, y[rr].z));
           xv.w = __fadd_rn(__fmul_rn(b.lam, xv.w), __fmul_rn(b.oml, y[rr].w));
         }
+        float4 xm;                                    // MASKED: the mixed row with its NaN, xv zero-filled
+        if constexpr (MASKED) { xm = xv; xv = mask_fill(xm); }
         float4 n;
         if (noise_in) n = nz[rr];
         else n = randn4(seed, row_offset + (uint32_t)r, (uint32_t)q, 0u, TAG_QNOISE);
@@ -232,7 +255,9 @@ __global__ __launch_bounds__(256) void k_q_sample_src(BatchSrc b, const int* t, 
         o.w = __fadd_rn(__fmul_rn(a[rr], xv.w), __fmul_rn(bb[rr], n.w));
         st4g(x_t + r * ldxt, c, cols, o);
         zero_pad(x_t + r * ldxt, cols, ldxt, c);
-        if constexpr (KIND == OSD_PRED_EPSILON) {
+        if constexpr (MASKED) {
+          if (noise_out) st4g(noise_out + r * cols, c, cols, mask_mark(xm, q_target<KIND>(a[rr], bb[rr], xv, n)));
+        } else if constexpr (KIND == OSD_PRED_EPSILON) {
           if (noise_out && noise_out != noise_in) st4g(noise_out + r * cols, c, cols, n);
         } else {
           if (noise_out) st4g(noise_out + r * cols, c, cols, q_target<KIND>(a[rr], bb[rr], xv, n));
@@ -242,19 +267,23 @@ __global__ __launch_bounds__(256) void k_q_sample_src(BatchSrc b, const int* t, 
     }
   }
 }
+template <bool MASKED>
+static auto pick_q_sample_src(int kind) {
+  return kind == OSD_PRED_V ? k_q_sample_src<OSD_PRED_V, MASKED> : kind == OSD_PRED_SAMPLE ? k_q_sample_src<OSD_PRED_SAMPLE, MASKED> : k_q_sample_src<OSD_PRED_EPSILON, MASKED>;
+}
 hipError_t launch_q_sample_src(hipStream_t s, const BatchSrc& b, const int* t, const float* sqrt_ac, const float* sqrt_1m, const float* noise_in,
                                int64_t rows, int cols, int cd, uint64_t seed, uint32_t row_offset, float* x_t, float* noise_out, int* t_out, int T,
-                               float* cond_out, float* x0_out, int ldxt, const ZeroList* zl, int kind) {
+                               float* cond_out, float* x0_out, int ldxt, const ZeroList* zl, int kind, bool masked) {
   if (rows <= 0) return hipSuccess;
   if (!t && (!t_out || T < 1)) return hipErrorInvalidValue;
-  if (kind != OSD_PRED_EPSILON && noise_out == noise_in) return hipErrorInvalidValue;
+  if ((kind != OSD_PRED_EPSILON || masked) && noise_out == noise_in) return hipErrorInvalidValue;
   ZeroList z{};
   if (zl) z = *zl;
   if (cd > 256) return hipErrorInvalidValue;
   int64_t blocks = (rows + QS_ROWS - 1) / QS_ROWS;
   if (blocks > 4096) blocks = 4096;
   if (blocks < (zl ? 32 : 1)) blocks = zl ? 32 : 1;      // the zero list is walked by the first 32 workgroups
-  auto k = kind == OSD_PRED_V ? k_q_sample_src<OSD_PRED_V> : kind == OSD_PRED_SAMPLE ? k_q_sample_src<OSD_PRED_SAMPLE> : k_q_sample_src<OSD_PRED_EPSILON>;
+  auto k = masked ? pick_q_sample_src<true>(kind) : pick_q_sample_src<false>(kind);
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), 256, 0, s, b, t, sqrt_ac, sqrt_1m, noise_in, rows, cols, cd, seed,
                      row_offset, x_t, ldxt > 0 ? ldxt : cols, noise_out, t_out, T, cond_out, x0_out, z);
   return hipGetLastError();

@@ -217,6 +217,11 @@ hipError_t launch_loss(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a)
   if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiLoss>(s, g, a);
   return launch_gemm<TileSmall, true, true, EpiLoss>(s, g, a);
 }
+// the same on a NaN-marked target (osd_set_loss_mask): fp32 only
+hipError_t launch_loss_masked(hipStream_t s, const GemmArgs& g, const EpiLossT<true>::Args& a) {
+  if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiLossT<true>>(s, g, a);
+  return launch_gemm<TileSmall, true, true, EpiLossT<true>>(s, g, a);
+}
 
 // se[r] = part[0][r] + part[1][r] + ... in slot order (+ *poison, a word that is 0 unless a squad launch of the same call gave up
 // and stored a NaN there: x + 0 keeps the bits of a sum of squares)

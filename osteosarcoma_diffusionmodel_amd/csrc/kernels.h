@@ -35,6 +35,8 @@ hipError_t launch_mse_b3t(hipStream_t s, const GemmArgs& g, const EpiMse::Args& 
 // output_proj + the loss of osd_set_loss (EpiLoss): launch_mse's / launch_mse_b3t's tile choices and return values
 hipError_t launch_loss(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a);
 hipError_t launch_loss_b3t(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a);
+// ... with the unobserved elements of a NaN-marked target left out (EpiLossT<true>; osd_set_loss_mask).  fp32 only.
+hipError_t launch_loss_masked(hipStream_t s, const GemmArgs& g, const EpiLossT<true>::Args& a);
 // output_proj + per-row squared error (EpiRowSq), launch_mse's tile choice, then k_rowsq_reduce: se[P].  a.part: rowsq_slots(F) x a.ld
 // floats.  poison: a device word added to every row (0, or the NaN of a squad launch that gave up), or null.  fp32 only.
 constexpr int ROWSQ_WF = 64;      // feature extent of a wave in both tiles of the tile choice
@@ -66,10 +68,12 @@ hipError_t launch_copy2d(hipStream_t s, const float* src, int lds, float* dst, i
 hipError_t launch_q_sample(hipStream_t s, const float* x0, const int* t, const float* sqrt_ac, const float* sqrt_1m,
                            const float* noise_in, int64_t rows, int cols, uint64_t seed, uint32_t row_offset,
                            float* x_t, float* noise_out, int* t_out = nullptr, int T = 0, int ldxt = 0, const ZeroList* zl = nullptr,
-                           int kind = OSD_PRED_EPSILON);      // kind != epsilon: noise_out receives the training target (k_elem.hip: q_target)
+                           int kind = OSD_PRED_EPSILON,       // kind != epsilon: noise_out receives the training target (k_elem.hip: q_target)
+                           bool masked = false);              // NaN in x0 = not observed: zero-filled for x_t, NaN-marked in the target (any kind)
 hipError_t launch_q_sample_src(hipStream_t s, const BatchSrc& b, const int* t, const float* sqrt_ac, const float* sqrt_1m, const float* noise_in,
                                int64_t rows, int cols, int cd, uint64_t seed, uint32_t row_offset, float* x_t, float* noise_out, int* t_out, int T,
-                               float* cond_out, float* x0_out, int ldxt = 0, const ZeroList* zl = nullptr, int kind = OSD_PRED_EPSILON);
+                               float* cond_out, float* x0_out, int ldxt = 0, const ZeroList* zl = nullptr, int kind = OSD_PRED_EPSILON,
+                               bool masked = false);
 // q_sample of the likelihood bound's (timestep, patient) pairs (k_elem.hip: k_q_sample_pairs).  Row r of the launch is pair
 // pair0 + r of a [S][n_pat] grid: patient i = pair % n_pat, timestep t_row[r] (t_row non-null) or t_list[pair / n_pat].  x0 / cond rows
 // are gathered from patient i (cond_out null: no condition rows written); noise_in, if given, points at row 0 of the launch.

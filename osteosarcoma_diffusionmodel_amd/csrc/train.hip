@@ -663,6 +663,9 @@ struct LossStep {
     const int* t_idx = tc.t_idx;
     // a non-eps target (osd_set_prediction) is formed by the same pass and lands in w.noise, injected noise or not
     if (h->pred_type != OSD_PRED_EPSILON) h->last_train_path |= OSD_TP_TARGET;
+    // osd_set_loss_mask: NaN in x0 = not observed; the target always lands in w.noise, NaN-marked (the row mode was refused before)
+    const bool masked = h->loss_mask;
+    if (masked) h->last_train_path |= OSD_TP_MASKED;
     if (se_out) {
       PairRows pr = *pairs;
       pr.t_row = t_draw ? nullptr : t_idx;          // the caller's per-row timesteps (clamped), else the sweep's list
@@ -677,7 +680,7 @@ struct LossStep {
     if (from_src) {
       // rows gathered from the resident dataset, mixed up and noised in one pass; conditions land in the workspace
       OSD_HIP(launch_q_sample_src(s, h->batch_src, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, a.cond_dim, seed, roff, w.x_t,
-                                  w.noise, t_draw, a.T, w.cond_mix, cp ? w.x0_mix : nullptr, w.xld, &zl, h->pred_type));
+                                  w.noise, t_draw, a.T, w.cond_mix, cp ? w.x0_mix : nullptr, w.xld, &zl, h->pred_type, masked));
       cond = w.cond_mix;
       x0 = cp ? w.x0_mix : nullptr;
       // condition dropout after the mix: the null condition into the rows that drop theirs, in place (one tiny launch, only when asked for)
@@ -686,7 +689,7 @@ struct LossStep {
                                     a.cond_dim, seed, roff, w.cond_mix));
     } else {
       OSD_HIP(launch_q_sample(s, x0, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, seed, roff, w.x_t, w.noise, t_draw, a.T, w.xld, &zl,
-                              h->pred_type));
+                              h->pred_type, masked));
       if (cond_drop) {       // condition dropout of a caller-supplied batch: the replaced rows land in the workspace
         OSD_HIP(launch_cond_dropout(s, cond, h->d_null_cond + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n, a.cond_dim,
                                     seed, roff, w.cond_mix));
@@ -737,6 +740,17 @@ struct LossStep {
     ea.bias = h->params[a.pm.out_b]; ea.noise = noise && h->pred_type == OSD_PRED_EPSILON ? noise : w.noise; ea.ldn = D;
     ea.dout = grads ? w.d_out : nullptr; ea.ldd = D; ea.pred = cp ? w.pred : nullptr; ea.ldp = D; ea.loss = loss_out;
     ea.inv_count = (float)(1.0 / count);
+    if (h->loss_mask) {
+      // osd_set_loss_mask: every kind (the default l2 without a table included) on EpiLossT<true>, against the NaN-marked target in
+      // w.noise whoever supplied eps; the fp32 launcher only, whatever the precision
+      ea.noise = w.noise; ea.pred = nullptr;
+      ea.gscale = (float)((h->loss_kind == OSD_LOSS_L2 ? 2.0 : 1.0) * (double)loss_scale / count);
+      EpiLossT<true>::Args em{};
+      em.m = ea; em.tw = h->loss_tw_set ? h->loss_tw : nullptr; em.t_index = tc.t_idx; em.kind = h->loss_kind; em.delta = h->loss_delta;
+      h->last_train_path |= OSD_TP_LOSS_EPI;
+      OSD_HIP(launch_loss_masked(s, g, em));
+      return OSD_OK;
+    }
     if (h->loss_kind == OSD_LOSS_L2 && !h->loss_tw_set) {
       ea.gscale = (float)(2.0 * (double)loss_scale / count);
       OSD_HIP(launch_on_b3t_or_fp32(h, s, g, ea, launch_mse_b3t, launch_mse));
@@ -827,6 +841,17 @@ static int dp_supported(const osd_handle* h, bool from_src, double loss_scale, v
   return OSD_EUNSUPPORTED;
 }
 
+// What a call under osd_set_loss_mask cannot be: anything that reads x0 or x0^ outside the masked loss, where a NaN would spread.
+static int mask_supported(const osd_handle* h, bool grads) {
+  const char* why = nullptr;
+  if ((h->cons.n_pathways > 0 && h->w_pathway != 0.0) || (h->cons.n_a > 0 && h->w_mutexpr != 0.0))
+    why = "the constraint losses are batch statistics over x0^ and x0, which have no value at an unobserved element (osd_set_constraints(h, NULL) clears them)";
+  else if (grads && h->dp_clip > 0.0) why = "per-row gradient clipping (osd_set_dp_clip) is not supported on incomplete rows";
+  if (!why) return OSD_OK;
+  set_error("masked loss (osd_set_loss_mask): %s", why);
+  return OSD_EUNSUPPORTED;
+}
+
 // checks in order: ready, rows, (one-shots consumed), null tensors, empty batch, row offset, event count, grads[i], then the device
 int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, int64_t n, const int32_t* t_index, const float* noise,
                            const float* const* masks, uint64_t seed, int64_t row_offset, int flags, float* loss_out,
@@ -841,6 +866,7 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
   if (n == 0) { set_error("empty batch"); return OSD_EINVAL; }
   OSD_TRY(check_row_offset(row_offset, n));
   OSD_TRY(tc.check_outputs(events, n_events, grads));
+  if (h->loss_mask) OSD_TRY(mask_supported(h, grads != nullptr));      // before any launch: no gradient buffer is touched
   if (grads && h->dp_clip > 0.0) OSD_TRY(dp_supported(h, from_src, loss_scale, events));      // before any launch: no gradient buffer is touched
   OSD_TRY(tc.enter());
   LossStep step{tc, h, h->arch, tc.s, n, x0, cond, noise, masks, seed, (uint32_t)row_offset, loss_out, grads, loss_scale, events, from_src, cond_drop};
@@ -860,6 +886,10 @@ static int bound_checks(osd_handle* h, const float* x0, const float* cond, int64
     return OSD_ESTATE;
   }
   if (h->precision == 1) { set_error("the per-row squared error runs on the fp32 kernels only (precision 0)"); return OSD_EUNSUPPORTED; }
+  if (h->loss_mask) {
+    set_error("masked loss (osd_set_loss_mask): the per-row squared error (osd_row_sq_error, osd_bound_sweep) has no masked form; osd_set_loss_mask(h, 0) first");
+    return OSD_EUNSUPPORTED;
+  }
   return OSD_OK;
 }
 
@@ -1046,6 +1076,12 @@ int osd_set_loss(osd_handle* h, int kind, double huber_delta, const float* t_wei
   h->loss_tw_set = t_weights_host != nullptr;
   h->loss_kind = kind;
   h->loss_delta = (float)huber_delta;
+  return OSD_OK;
+}
+
+int osd_set_loss_mask(osd_handle* h, int enable) {
+  if (!h) { set_error("null handle"); return OSD_EINVAL; }
+  h->loss_mask = enable != 0;      // host state alone: read when the next call is issued
   return OSD_OK;
 }
 

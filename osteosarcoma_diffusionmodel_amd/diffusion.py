@@ -149,6 +149,13 @@ class _Engine:
         self.prediction_type = "epsilon"  # the model's prediction_type this handle's tables were last folded for (the library's default)
         self.serial = 0                 # bumped by every call that rewrites the handle's training workspace
         self.dp_clip = 0.0              # the per-row gradient bound this handle was last given (osd_set_dp_clip; 0: off, the library's default)
+        self.loss_mask = False          # whether this handle was last told to mask NaN (osd_set_loss_mask; off: the library's default)
+
+    def set_loss_mask(self, model: "BiologyAwareDiffusionModel"):
+        """Validate the model's missing_values and hand it to the handle (osd_set_loss_mask: persistent)."""
+        on = check_missing_values(getattr(model, "missing_values", None)) == "mask"
+        L.check(L.lib().osd_set_loss_mask(self.handle, int(on)))
+        self.loss_mask = on
 
     def set_dp_clip(self, model: "BiologyAwareDiffusionModel"):
         """Validate the model's dp_max_grad_norm and hand it to the handle (osd_set_dp_clip: persistent)."""
@@ -214,6 +221,13 @@ class _Engine:
             arr = L.ptr_array(params)
             L.check(lib.osd_load_weights(self.handle, arr, len(params)))
             self._sig = sig
+
+
+def check_missing_values(v):
+    """``missing_values``: None (the default: NaN is not accepted in x_0) or "mask" (NaN = not observed, masked out of the loss)."""
+    if v is not None and v != "mask":
+        raise ValueError(f"missing_values must be None or 'mask', got {v!r}")
+    return v
 
 
 def _if_truthy(v):
@@ -364,6 +378,11 @@ class BiologyAwareDiffusionModel(nn.Module):
         # the loss stays the unclipped mean.  train.py's Trainer sets it from training.dp; a plain attribute for users of the bare model.
         # ValueError from the call for what has no per-row gradient (constraint losses, a mixed-up batch source, data parallel)
         self.dp_max_grad_norm: Optional[float] = None
+        # training on incomplete patients: None (the default: today's training call, bit for bit) or "mask" --
+        # a NaN element of x_0 is "not observed": zero in x_t, left out of the loss and its gradient (MissDiff), the mean still over n D.
+        # config['training']['missing_values']; a plain attribute like the loss keys.  ValueError from the call with constraint losses,
+        # dp_max_grad_norm, row_sq_error / variational_bound
+        self.missing_values: Optional[str] = check_missing_values((config.get("training") or {}).get("missing_values"))
         self._loss_weights = None         # set_loss_weights: a custom per-timestep table (host float32 [T]); wins over loss_weighting
         self._loss_version = 0
 
@@ -479,6 +498,9 @@ class BiologyAwareDiffusionModel(nn.Module):
             eng.loss_state = state
         if eng.dp_clip != float(getattr(self, "dp_max_grad_norm", None) or 0.0):
             eng.set_dp_clip(self)
+        mv = getattr(self, "missing_values", None)
+        if (mv is not None or eng.loss_mask) and eng.loss_mask != (check_missing_values(mv) == "mask"):
+            eng.set_loss_mask(self)     # check_missing_values raises ValueError on an unknown value; the handle then keeps its setting
         for attr, option, encode in ENGINE_OPTIONS:
             value = encode(getattr(self, attr))
             if value is not None:

@@ -365,16 +365,35 @@ class FusedAdamW(torch.optim.Optimizer):
 # reference-shaped pipeline pieces
 # --------------------------------------------------------------------------------------
 class OsteosarcomaDataset(Dataset):
-    """[mutations | expression | pathways] rows + clinical conditions (utils/train.py:22-82)."""
+    """[mutations | expression | pathways] rows + clinical conditions (utils/train.py:22-82).
+
+    ``incomplete="drop"`` (the default, the reference's): the patients present in all three feature matrices.  ``"keep"``: every
+    patient of the clinical table present in at least one of them; a matrix that lacks a patient contributes a NaN block to that row --
+    "not observed", which ``training.missing_values: mask`` trains on and ``generator.impute`` fills in."""
 
     def __init__(self, mutation_matrix: pd.DataFrame, expression_matrix: pd.DataFrame, pathway_scores: pd.DataFrame,
-                 clinical_data: pd.DataFrame, condition_features: list):
+                 clinical_data: pd.DataFrame, condition_features: list, incomplete: str = "drop"):
+        if incomplete not in ("drop", "keep"):
+            raise ValueError(f"incomplete must be 'drop' or 'keep', got {incomplete!r}")
         clinical = clinical_data.set_index("submitter_id")
-        common = (mutation_matrix.index.intersection(expression_matrix.index)
-                  .intersection(pathway_scores.index).intersection(clinical.index))
-        self.mutations = torch.FloatTensor(mutation_matrix.loc[common].values.astype(np.float32))
-        self.expression = torch.FloatTensor(expression_matrix.loc[common].values.astype(np.float32))
-        self.pathways = torch.FloatTensor(pathway_scores.loc[common].values.astype(np.float32))
+        blocks = (mutation_matrix, expression_matrix, pathway_scores)
+        if incomplete == "keep":
+            common = (mutation_matrix.index.union(expression_matrix.index, sort=False).union(pathway_scores.index, sort=False)
+                      .intersection(clinical.index))
+            # reindex leaves NaN rows for the patients a matrix lacks
+            self.mutations, self.expression, self.pathways = (
+                torch.FloatTensor(m.reindex(common).values.astype(np.float32)) for m in blocks)
+            have = [int(m.index.isin(common).sum()) for m in blocks]
+            full = int((mutation_matrix.index.intersection(expression_matrix.index).intersection(pathway_scores.index)
+                        .intersection(clinical.index)).size)
+            logger.info(f"Incomplete patients kept: {len(common)} samples, {full} complete; with mutations {have[0]}, "
+                        f"expression {have[1]}, pathways {have[2]}")
+        else:
+            common = (mutation_matrix.index.intersection(expression_matrix.index)
+                      .intersection(pathway_scores.index).intersection(clinical.index))
+            self.mutations = torch.FloatTensor(mutation_matrix.loc[common].values.astype(np.float32))
+            self.expression = torch.FloatTensor(expression_matrix.loc[common].values.astype(np.float32))
+            self.pathways = torch.FloatTensor(pathway_scores.loc[common].values.astype(np.float32))
         self.data = torch.cat([self.mutations, self.expression, self.pathways], dim=1)
         aligned = clinical.loc[common]
         cond = aligned[condition_features].values.astype(np.float32)
@@ -665,6 +684,22 @@ class Trainer:
         # mean bits per feature of the variational bound over the validation rows (likelihood.py) on training.validation_timesteps
         # strided timesteps -- a deterministic functional of the weights, comparable across objectives
         self.validation_metric = validation_metric_of(tc)
+        # training.missing_values: mask -- NaN in the data = not observed, masked out of the loss; what has no
+        # masked form is refused here, before the device
+        from .diffusion import check_missing_values
+        self.missing_values = check_missing_values(tc["missing_values"] if "missing_values" in tc else getattr(model, "missing_values", None))
+        if self.missing_values == "mask":
+            if hasattr(model, "vae"):
+                raise ValueError("training.missing_values 'mask' trains the diffusion model and is not accepted for a cVAE model")
+            if self.validation_metric == "bound":
+                raise ValueError("training.missing_values 'mask' has no mask-aware likelihood bound: training.validation_metric must be 'loss'")
+            if tc.get("dp") is not None:
+                raise ValueError("training.missing_values 'mask' is not supported with training.dp (per-patient clipping on incomplete rows)")
+            if cons is not None and (cons["w_pc"] != 0.0 or cons["w_me"] != 0.0):
+                raise ValueError("training.missing_values 'mask' is not supported with the constraint losses: they are batch statistics "
+                                 "over x0, which has no value at an unobserved element (set their weights to 0 or clear them)")
+            self._check_incomplete_data(train_loader, val_loader)
+            model.missing_values = "mask"
         self.validation_timesteps = int(tc.get("validation_timesteps", 32))
         if self.validation_timesteps < 2:
             raise ValueError(f"training.validation_timesteps={self.validation_timesteps}: at least 2 (t = 0 and one more)")
@@ -769,7 +804,27 @@ class Trainer:
 
     def _option_state(self):
         m = self.model
-        return tuple(getattr(m, attr, None) for attr, _, _ in ENGINE_OPTIONS) + (getattr(m, "dp_max_grad_norm", None),)
+        return tuple(getattr(m, attr, None) for attr, _, _ in ENGINE_OPTIONS) + (getattr(m, "dp_max_grad_norm", None),
+                                                                               getattr(m, "missing_values", None))
+
+    @staticmethod
+    def _check_incomplete_data(*loaders):
+        """Once, on the host tensors of an ``OsteosarcomaDataset``: NaN is the only missing marker, so Inf in the data (or anything
+        non-finite in the conditions) is a ValueError; logs the observed fraction, the number to rescale the logged loss by -- the
+        masked loss is a mean over n D, not over the observed elements."""
+        seen = set()
+        for loader in loaders:
+            base, _ = ResidentSplit._base_of(getattr(loader, "dataset", None))
+            if not isinstance(base, OsteosarcomaDataset) or id(base) in seen:
+                continue
+            seen.add(id(base))
+            if bool(torch.isinf(base.data).any()):
+                raise ValueError("training.missing_values 'mask': the data hold Inf; NaN is the only marker of a missing value")
+            if not bool(torch.isfinite(base.conditions).all()):
+                raise ValueError("training.missing_values 'mask': conditions must be finite")
+            observed = 1.0 - float(torch.isnan(base.data).double().mean()) if base.data.numel() else 1.0
+            logger.info(f"Incomplete data: {observed:.4f} of the dataset's elements are observed; the masked loss is a mean over all "
+                        f"n x D elements (divide it by this fraction to compare with a complete-data loss)")
 
     # -- differentially private training (privacy.py; DESIGN.md section 3.21) -----------------------------
     def _dp_setup(self, tc: dict):
@@ -1118,8 +1173,11 @@ def prepare_data(config: dict):
     wanted = ["survival_days_norm", "event_occurred", "age_years", "metastasis_at_diagnosis"]
     condition_features = [f for f in wanted if f in clinical.columns]
     logger.info(f"Condition features: {condition_features}")
-    dataset = OsteosarcomaDataset(mutation_matrix, expression_matrix, pathway_scores, clinical, condition_features)
     tc = config["training"]
+    # training.missing_values: mask keeps the patients that lack a feature matrix (NaN blocks); otherwise the reference's intersection
+    from .diffusion import check_missing_values
+    incomplete = "keep" if check_missing_values(tc.get("missing_values")) == "mask" else "drop"
+    dataset = OsteosarcomaDataset(mutation_matrix, expression_matrix, pathway_scores, clinical, condition_features, incomplete=incomplete)
     val_size = int(len(dataset) * tc["val_split"])
     train_ds, val_ds = torch.utils.data.random_split(dataset, [len(dataset) - val_size, val_size],
                                                      generator=torch.Generator().manual_seed(tc["random_seed"]))
