@@ -136,7 +136,8 @@ int osd_set_option(osd_handle *h, const char *name, int64_t value);
  * (1 when "precision" 1 applies to this model), "panel_chain_supported" / "squad_chain_supported" (1 when "chain_variant"
  * 2 / 3 applies to this model), "last_train_path" (what the most recent osd_train_loss_fwd_bwd or osd_denoiser_backward call on
  * the handle ran, an OR of the OSD_TP_* bits below; cleared at the start of either call), "prediction_type" (OSD_PRED_*, what
- * osd_set_prediction set last; 0 on a new handle), "loss_mask" (0 | 1, what osd_set_loss_mask set last).  Any other name: OSD_EINVAL. */
+ * osd_set_prediction set last; 0 on a new handle), "loss_mask" (0 | 1, what osd_set_loss_mask set last), "output_link" (n_logistic, what
+ * osd_set_output_link set last; 0 on a new handle).  Any other name: OSD_EINVAL. */
 int osd_get_option(osd_handle *h, const char *name, int64_t *value);
 
 /* "last_train_path" bits */
@@ -155,6 +156,7 @@ int osd_get_option(osd_handle *h, const char *name, int64_t *value);
 #define OSD_TP_TARGET        (1 << 12)  /* q_sample wrote a non-eps training target (osd_set_prediction); never set on the default path */
 #define OSD_TP_DP_CLIP       (1 << 13)  /* per-row gradient clipping ran (osd_set_dp_clip); never set on the default path */
 #define OSD_TP_MASKED        (1 << 14)  /* NaN-masked q_sample and loss epilogue ran (osd_set_loss_mask); never set on the default path */
+#define OSD_TP_LINK          (1 << 15)  /* the loss epilogue with the logistic link ran (osd_set_output_link); never set on the default path */
 
 /* Schedule + time-embedding tables, computed by the host with the reference's own
  * fp32 expressions so they are bit-identical (models/diffusion.py:299-326, 131-137,
@@ -741,6 +743,29 @@ int osd_set_loss(osd_handle *h, int kind, double huber_delta, const float *t_wei
  * Persistent on the handle like osd_set_loss; host state only, no synchronisation.  0, the state of a new handle, restores exactly the
  * launches of a handle that never called this.  OSD_EINVAL: a null handle. */
 int osd_set_loss_mask(osd_handle *h, int enable);
+
+/* ---- a logistic link on the leading output columns -------------------------------------------------
+ * Columns [0, n_logistic) of the network's output are logits of a Bernoulli mean E[x0 | x_t] -- the 0/1 mutation block of the feature
+ * vector -- instead of an unbounded x0^.  0, the state of a new handle, turns the link off and restores exactly the launches of a
+ * handle that never called this.  Needs the prediction type OSD_PRED_SAMPLE.  With o the output, y the target, M = n_logistic:
+ *   training   f <  M:  rho = max(o, 0) - o y + log1p(exp(-|o|))       d rho / d o = sigma(o) - y        (cross-entropy on the logit)
+ *              f >= M:  rho(o - y) of osd_set_loss, as without a link
+ *              loss = 1/(n D) * sum_r w[t_r] * sum_f rho_rf;  dL/d out its exact derivative times loss_scale.  The weights, the NaN
+ *              mask of osd_set_loss_mask, a resident batch source and its mixup (y inside [0, 1]) keep their meaning.  One launch, as
+ *              before (EpiLossT<true, true>, csrc/epilogues.h), on the fp32 launcher whatever "precision" says; the call sets
+ *              OSD_TP_LINK | OSD_TP_LOSS_EPI.
+ *   sampling   osd_sample_chain_clipped and osd_sample_chain_multistep: x0 = sigma(P x + Q o) on the columns f < M, in front of the
+ *              clamp; the update, the history store and the known overwrite follow unchanged, so every returned value of those
+ *              columns lies in [0, 1] whatever the bounds.  Guidance combines raw outputs: it acts on the logit there.
+ *   osd_convert_prediction: x0^ = sigma(o) on those columns; eps^ and v^ are derived from that x0^.
+ * OSD_EUNSUPPORTED, before any launch: every entry point that folds x0^ away or reads the output as x0^ -- osd_p_sample_step,
+ * osd_sample_chain, _steps, _guided, _known (the clipped entry points take their arguments; infinite bounds leave a column free);
+ * osd_train_loss_fwd_bwd with constraint losses configured or with gradients under osd_set_dp_clip; osd_row_sq_error and
+ * osd_bound_sweep (no likelihood bound for a Bernoulli block: refused, not approximated).
+ * Host state only, read when the next call is issued, like osd_set_loss_mask.  OSD_EINVAL: a null handle, n_logistic outside [0, D],
+ * or n_logistic > 0 while the handle's type is not OSD_PRED_SAMPLE; as either can be set second, the calls above return OSD_EINVAL
+ * for that combination as well. */
+int osd_set_output_link(osd_handle *h, int n_logistic);
 
 /* ---- the per-patient likelihood bound ----------------------------------------------------------
  * se[r] = sum_d (out[r][d] - target[r][d])^2: an eval-mode forward of q_sample(x0, t_r) and the per-row squared error of the network's

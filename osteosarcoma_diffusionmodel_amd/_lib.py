@@ -18,6 +18,7 @@ OSD_TP_LOSS_EPI = 1 << 11
 OSD_TP_TARGET = 1 << 12
 OSD_TP_DP_CLIP = 1 << 13
 OSD_TP_MASKED = 1 << 14
+OSD_TP_LINK = 1 << 15
 DP_NOISE_TAG, DP_NOISE_COLS = 0x44504E00, 4096      # csrc/dp.h: the Philox tag and the (rows, 4096) reading of the flat buffer
 OSD_PRED_EPSILON, OSD_PRED_V, OSD_PRED_SAMPLE = 0, 1, 2
 OSD_CORR_STATS = 7
@@ -119,6 +120,7 @@ _SIGNATURES = {
     "osd_get_loss_parts": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "osd_set_loss": (C.c_int, [_P, C.c_int, C.c_double, _P]),
     "osd_set_loss_mask": (C.c_int, [_P, C.c_int]),
+    "osd_set_output_link": (C.c_int, [_P, C.c_int]),
     "osd_set_dp_clip": (C.c_int, [_P, C.c_double]),
     "osd_dp_row_norms": (C.c_int, [_P, _P, C.c_int64]),
     "osd_dp_replay": (C.c_int, [_P, C.c_int, C.c_float]),

@@ -322,6 +322,15 @@ int upload_null_cond(osd_handle* h, int slot, const float* null_cond_host, const
   return OSD_OK;
 }
 
+int check_output_link(const osd_handle* h) {
+  if (h->n_link > 0 && h->pred_type != OSD_PRED_SAMPLE) {
+    set_error("output link (osd_set_output_link): %d logistic columns need the prediction type OSD_PRED_SAMPLE, the handle's is %d (osd_set_prediction)",
+              h->n_link, h->pred_type);
+    return OSD_EINVAL;
+  }
+  return OSD_OK;
+}
+
 int check_ready(osd_handle* h) {
   if (!h) { set_error("null handle"); return OSD_EINVAL; }
   if (!h->have_schedule) { set_error("osd_set_schedule has not been called"); return OSD_ESTATE; }
@@ -432,6 +441,7 @@ static const Counter COUNTERS[] = {
     {"last_train_path", [](osd_handle* h) -> int64_t { return h->last_train_path; }},
     {"prediction_type", [](osd_handle* h) -> int64_t { return h->pred_type; }},
     {"loss_mask", [](osd_handle* h) -> int64_t { return h->loss_mask ? 1 : 0; }},
+    {"output_link", [](osd_handle* h) -> int64_t { return h->n_link; }},
 };
 
 }  // namespace osd
@@ -785,6 +795,17 @@ int osd_set_prediction(osd_handle* h, int type) {
   return rc;
 }
 
+int osd_set_output_link(osd_handle* h, int n_logistic) {
+  if (!h) { set_error("null handle"); return OSD_EINVAL; }
+  if (n_logistic < 0 || n_logistic > h->arch.D) { set_error("n_logistic=%d outside [0, D=%d]", n_logistic, h->arch.D); return OSD_EINVAL; }
+  if (n_logistic > 0 && h->pred_type != OSD_PRED_SAMPLE) {
+    set_error("output link (osd_set_output_link): a logistic link needs osd_set_prediction(h, OSD_PRED_SAMPLE): the linked columns are x0^");
+    return OSD_EINVAL;
+  }
+  h->n_link = n_logistic;      // host state alone: read when the next call is issued
+  return OSD_OK;
+}
+
 int osd_q_sample_target(osd_handle* h, const float* x0, const int32_t* t_index, const float* noise_in, int64_t n, uint64_t seed,
                         int64_t row_offset, float* x_t, float* target_out) {
   if (!h || !h->have_schedule) { set_error("schedule not set"); return OSD_ESTATE; }
@@ -811,6 +832,7 @@ int osd_convert_prediction(osd_handle* h, const float* x_t, const int32_t* t_ind
   if (!h || !h->have_schedule) { set_error("schedule not set"); return OSD_ESTATE; }
   OSD_TRY(check_rows(n));
   if (!x_t || !t_index || !out || !dst) { set_error("null tensor"); return OSD_EINVAL; }
+  OSD_TRY(check_output_link(h));
   if (as_kind != OSD_PRED_EPSILON && as_kind != OSD_PRED_V && as_kind != OSD_PRED_SAMPLE) { set_error("unknown conversion %d (OSD_PRED_*)", as_kind); return OSD_EINVAL; }
   OSD_HIP(hipSetDevice(h->cfg.device));
   const int T = h->arch.T;
@@ -833,7 +855,8 @@ int osd_convert_prediction(osd_handle* h, const float* x_t, const int32_t* t_ind
   }
   const int* t_idx = nullptr;
   OSD_TRY(sanitize_t(h, h->stream, t_index, n, &t_idx));
-  OSD_HIP(launch_row_affine(h->stream, x_t, t_idx, reinterpret_cast<const float2*>(uv_dev), out, n, h->arch.D, dst));
+  // osd_set_output_link: x0^ is sigma(out) on the link columns, eps^ and v^ follow from that x0^ (k_train.hip: k_row_affine)
+  OSD_HIP(launch_row_affine(h->stream, x_t, t_idx, reinterpret_cast<const float2*>(uv_dev), out, n, h->arch.D, dst, h->n_link));
   return OSD_OK;
 }
 
@@ -842,6 +865,10 @@ int osd_p_sample_step(osd_handle* h, const float* x_t, int32_t t, const float* c
   OSD_TRY(check_ready(h));
   OSD_TRY(check_rows(n));
   if (!x_t || !cond || !x_out) { set_error("null tensor"); return OSD_EINVAL; }
+  if (h->n_link > 0) {
+    set_error("output link (osd_set_output_link): osd_p_sample_step folds x0^ away and cannot carry the link; osd_sample_chain_clipped does");
+    return OSD_EUNSUPPORTED;
+  }
   const Arch& a = h->arch;
   if (t < 0 || t >= a.T) { set_error("t=%d outside [0,%d)", t, a.T); return OSD_EINVAL; }
   OSD_TRY(check_row_offset(row_offset, n));
@@ -970,7 +997,10 @@ static int chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r
     ea.mut_mask = job.mut_mask_out; ea.mutation_dim = job.mutation_dim;
     if (cl) {
       const PosteriorClipArgs ca{ea, cl->bounds, cl->bounds + cl->ld, cl->x0_coef, kn ? known : nullptr, ldk, kn ? kn->level : nullptr};
-      if (ms) OSD_HIP(launch_posterior(s, g, PosteriorHistArgs{ca, hist, ldx, ms->hist_coef}));
+      if (cl->n_link > 0) {            // osd_set_output_link: the same launch, sigma on the leading columns of x0^
+        if (ms) OSD_HIP(launch_posterior(s, g, PosteriorHistLinkArgs{PosteriorHistArgs{ca, hist, ldx, ms->hist_coef}, cl->n_link}));
+        else OSD_HIP(launch_posterior(s, g, PosteriorClipLinkArgs{ca, cl->n_link}));
+      } else if (ms) OSD_HIP(launch_posterior(s, g, PosteriorHistArgs{ca, hist, ldx, ms->hist_coef}));
       else OSD_HIP(launch_posterior(s, g, ca));
     } else if (kn) OSD_HIP(launch_posterior(s, g, PosteriorKnownArgs{ea, known, ldk, kn->level}));
     else OSD_HIP(launch_posterior(s, g, ea));
@@ -1135,7 +1165,7 @@ static int upload_clip(osd_handle* h, const float* x0_coef_host, int S, const fl
   for (int f = lo_host ? a.D : 0; f < h->Dp; ++f) { lo[f] = -INFINITY; hi[f] = INFINITY; }      // no bounds (a multistep chain's may be absent): all free
   OSD_HIP(hipMemcpyAsync(h->clip_dev, hc, floats * 4, hipMemcpyHostToDevice, h->stream));
   OSD_HIP(hipEventRecord(h->clip_ev, h->stream));
-  *out = Clip{h->clip_dev + coef_floats, h->Dp, h->clip_dev};
+  *out = Clip{h->clip_dev + coef_floats, h->Dp, h->clip_dev, 0};
   return OSD_OK;
 }
 
@@ -1182,6 +1212,14 @@ static int sample_request(osd_handle* h, const SampleRequest& r) {
   if (r.around_known && h->precision == 1) { set_error("precision = bf16x3 does not run chains around known values: set precision to fp32"); return OSD_EUNSUPPORTED; }
   if (r.multistep && h->precision == 1) { set_error("precision = bf16x3 does not run the multistep solver: set precision to fp32"); return OSD_EUNSUPPORTED; }
   if (r.clipped && h->precision == 1) { set_error("precision = bf16x3 does not run chains that clip x0: set precision to fp32"); return OSD_EUNSUPPORTED; }
+  if (h->n_link > 0) {
+    OSD_TRY(check_output_link(h));
+    if (!r.clipped) {
+      set_error("output link (osd_set_output_link): this entry point folds x0^ away and cannot carry the link; osd_sample_chain_clipped and "
+                "osd_sample_chain_multistep do (infinite bounds leave a column free)");
+      return OSD_EUNSUPPORTED;
+    }
+  }
   OSD_TRY(check_rows(r.n));
   if (!r.cond || !r.x_out) { set_error("null tensor"); return OSD_EINVAL; }
   if (r.around_known) {
@@ -1243,6 +1281,7 @@ static int sample_request(osd_handle* h, const SampleRequest& r) {
     OSD_TRY(upload_known_level(h, plan ? r.known_level : nullptr, plan ? r.n_steps : a.T, &job.known.level));
   }
   if (r.clipped) OSD_TRY(upload_clip(h, plan ? r.x0_coef : nullptr, plan ? r.n_steps : a.T, r.lo, r.hi, &job.clip));
+  job.clip.n_link = h->n_link;
   if (r.multistep) OSD_TRY(upload_hist_coef(h, r.hist_coef, r.n_steps, &job.multistep));
   if (plan) {
     OSD_TRY(upload_plan(h, r.timesteps, r.step_coef, r.n_steps));

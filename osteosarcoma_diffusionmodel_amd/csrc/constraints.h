@@ -68,7 +68,8 @@ hipError_t launch_x0hat_bwd(hipStream_t s, const float* g_x0, const int* t_idx, 
 
 // dst = pq[t].x * x_t + pq[t].y * out per row (pq dev [T]: x0^ = P x_t + Q out of osd_set_prediction, or a conversion's (U, V));
 // dst may alias out
-hipError_t launch_row_affine(hipStream_t s, const float* x_t, const int* t_idx, const float2* pq, const float* out, int64_t rows, int D, float* dst);
+hipError_t launch_row_affine(hipStream_t s, const float* x_t, const int* t_idx, const float2* pq, const float* out, int64_t rows, int D, float* dst,
+                             int n_link = 0);      // columns [0, n_link) of out are logits: the map reads sigma(out) there
 // d_out += g * pq[t].y
 hipError_t launch_row_affine_bwd(hipStream_t s, const float* g, const int* t_idx, const float2* pq, int64_t rows, int D, float* d_out);
 

@@ -317,11 +317,17 @@ hipError_t launch_x0hat_bwd(hipStream_t s, const float* g_x0, const int* t_idx, 
 // ---- x0_hat of any prediction type (osd_set_prediction) and the conversions of osd_convert_prediction: a row-affine map -----
 // One workgroup walks whole rows (the row's (U, V) is a wave-uniform load, no 64-bit division per element); the products are rounded
 // separately and added, as torch evaluates U*x + V*out.
-__global__ __launch_bounds__(256) void k_row_affine(const float* x_t, const int* t, const float2* pq, const float* out, int64_t rows, int D, float* dst) {
+// n_link (osd_set_output_link): columns [0, n_link) of `out` are logits; the map then reads sigma(out) there (the arithmetic of epilogues.h: link_sigmoid).
+__global__ __launch_bounds__(256) void k_row_affine(const float* x_t, const int* t, const float2* pq, const float* out, int64_t rows, int D, float* dst,
+                                                    int n_link) {
   for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
     const float2 c = pq[t[r]];
     const float* xr = x_t + r * D; const float* orow = out + r * D; float* dr = dst + r * D;
-    for (int j = threadIdx.x; j < D; j += 256) dr[j] = __fadd_rn(__fmul_rn(c.x, xr[j]), __fmul_rn(c.y, orow[j]));
+    for (int j = threadIdx.x; j < D; j += 256) {
+      float o = orow[j];
+      if (j < n_link) o = fminf(__builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(o * -1.4426950408889634f)), 1.0f);
+      dr[j] = __fadd_rn(__fmul_rn(c.x, xr[j]), __fmul_rn(c.y, o));
+    }
   }
 }
 __global__ __launch_bounds__(256) void k_row_affine_bwd(const float* g, const int* t, const float2* pq, int64_t rows, int D, float* d_out) {
@@ -331,9 +337,10 @@ __global__ __launch_bounds__(256) void k_row_affine_bwd(const float* g, const in
     for (int j = threadIdx.x; j < D; j += 256) dr[j] = __fadd_rn(dr[j], __fmul_rn(gr[j], q));
   }
 }
-hipError_t launch_row_affine(hipStream_t s, const float* x_t, const int* t_idx, const float2* pq, const float* out, int64_t rows, int D, float* dst) {
+hipError_t launch_row_affine(hipStream_t s, const float* x_t, const int* t_idx, const float2* pq, const float* out, int64_t rows, int D, float* dst,
+                             int n_link) {
   if (rows <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_row_affine, (int)(rows > 4096 ? 4096 : rows), 256, 0, s, x_t, t_idx, pq, out, rows, D, dst);
+  hipLaunchKernelGGL(k_row_affine, (int)(rows > 4096 ? 4096 : rows), 256, 0, s, x_t, t_idx, pq, out, rows, D, dst, n_link);
   return hipGetLastError();
 }
 hipError_t launch_row_affine_bwd(hipStream_t s, const float* g, const int* t_idx, const float2* pq, int64_t rows, int D, float* d_out) {

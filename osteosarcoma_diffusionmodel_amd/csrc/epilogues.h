@@ -489,6 +489,10 @@ struct EpiGnBwd {
 // reads and rewrites in place exactly as it does x.  x0coef [S][4] = (P_t, Q_t, G_t, F_t), hcoef [S] = H_t.  Per element:
 //   hp  = hist[p][f];   hist[p][f] = x0c           the clipped network prediction, not the value after the `known` overwrite
 //   x'  = fmaf(G, x0c, fmaf(F, x, H*hp))
+// LINK (osd_set_output_link), POST_CLIP and POST_HIST only: columns f < n_link of the output are logits of a
+// Bernoulli mean.  Right after x0 = fmaf(P, x, Q*eps) (P = 0, Q = 1: the type is OSD_PRED_SAMPLE) they take x0 = sigma(x0); the clamp,
+// the update, the history store and the known overwrite follow unchanged.  A 32-column block at or past n_link takes a wave-uniform
+// branch around the transcendentals.
 // H is wave-uniform: where it is 0 (the first step run, whose history is the zeroed buffer, and t = 0) the read is skipped and hp = 0;
 // the store is skipped at t = 0.  Row 0 is (P, Q, 1, 0) with H = 0: x' = x0c bit for bit.  No z: the generator runs only under KNOWN,
 // for quads that hold an observation, at t > 0.  coef is not read.
@@ -522,11 +526,26 @@ struct PosteriorHistArgs {
   float* hist; int ldh;                 // [P][ldh]
   const float* hcoef;                   // dev [S] = H_t
 };
+// LINK: the same with the logistic link on the columns [0, n_link) of the output (osd_set_output_link).  Types of their own, so that the
+// kernels without a link keep their argument layout
+struct PosteriorClipLinkArgs { PosteriorClipArgs c; int n_link; };
+struct PosteriorHistLinkArgs { PosteriorHistArgs h; int n_link; };
 // the nested parts of an argument struct: the common fields, the clip fields, and the struct that holds known / ldk / level
 __host__ __device__ inline const PosteriorArgs& post_base(const PosteriorArgs& a) { return a; }
 __host__ __device__ inline const PosteriorArgs& post_base(const PosteriorKnownArgs& a) { return a.p; }
 __host__ __device__ inline const PosteriorArgs& post_base(const PosteriorClipArgs& a) { return a.p; }
 __host__ __device__ inline const PosteriorArgs& post_base(const PosteriorHistArgs& a) { return a.c.p; }
+__host__ __device__ inline const PosteriorArgs& post_base(const PosteriorClipLinkArgs& a) { return a.c.p; }
+__host__ __device__ inline const PosteriorArgs& post_base(const PosteriorHistLinkArgs& a) { return a.h.c.p; }
+__host__ __device__ inline const PosteriorClipArgs& post_clip(const PosteriorClipLinkArgs& a) { return a.c; }
+__host__ __device__ inline const PosteriorClipArgs& post_clip(const PosteriorHistLinkArgs& a) { return a.h.c; }
+__host__ __device__ inline const PosteriorClipArgs& post_known(const PosteriorClipLinkArgs& a) { return a.c; }
+__host__ __device__ inline const PosteriorClipArgs& post_known(const PosteriorHistLinkArgs& a) { return a.h.c; }
+template <class A> __host__ __device__ inline int post_n_link(const A&) { return 0; }
+__host__ __device__ inline int post_n_link(const PosteriorClipLinkArgs& a) { return a.n_link; }
+__host__ __device__ inline int post_n_link(const PosteriorHistLinkArgs& a) { return a.n_link; }
+__host__ __device__ inline const PosteriorHistArgs& post_hist(const PosteriorHistArgs& a) { return a; }
+__host__ __device__ inline const PosteriorHistArgs& post_hist(const PosteriorHistLinkArgs& a) { return a.h; }
 __host__ __device__ inline const PosteriorClipArgs& post_clip(const PosteriorClipArgs& a) { return a; }
 __host__ __device__ inline const PosteriorClipArgs& post_clip(const PosteriorHistArgs& a) { return a.c; }
 __host__ __device__ inline const PosteriorKnownArgs& post_known(const PosteriorKnownArgs& a) { return a; }
@@ -541,41 +560,62 @@ __host__ __device__ inline const PosteriorClipArgs& post_known(const PosteriorHi
 //   hist:          two quads' x, lo, hi, hist are 32
 //   clip + known, hist + known (the known quad rides along: 16 and 20 registers a quad): a whole block's 64 spill 31 VGPRs and
 //                  half a block's 32 still spill one
+// the Bernoulli mean of a logit (LINK), inside [0, 1]: hardware exp2 / rcp as silu_f; exp2 = +inf gives 0
+__device__ __forceinline__ float link_sigmoid(float x) {
+  return fminf(__builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)), 1.0f);
+}
+//   link:          the bias quad rides along as well (EpiPosterior::Pre): clip asks for one quad at a time, two still spill one VGPR
 constexpr int post_quads_ahead(PostMode m, bool known) { return m == POST_PLAIN ? (known ? 4 : 0) : known ? 1 : m == POST_CLIP ? 4 : 2; }
 
-template <PostMode MODE, bool KNOWN>
+template <PostMode MODE, bool KNOWN, bool LINK = false>
 struct EpiPosterior {
+  static_assert(!LINK || MODE != POST_PLAIN, "POST_PLAIN folds x0 away: it cannot carry a link");
   static constexpr bool COUNTED_STORES = true;     // one x' quad per accumulator quad and, POST_HIST at t > 0, one history quad more: never fewer
   static constexpr bool XBUF = false;
   template <class A> static __device__ __forceinline__ void slice(A&, int) {}
-  typedef std::conditional_t<MODE == POST_HIST, PosteriorHistArgs,
-                             std::conditional_t<MODE == POST_CLIP, PosteriorClipArgs, std::conditional_t<KNOWN, PosteriorKnownArgs, PosteriorArgs>>> Args;
+  typedef std::conditional_t<MODE == POST_HIST, std::conditional_t<LINK, PosteriorHistLinkArgs, PosteriorHistArgs>,
+                             std::conditional_t<MODE == POST_CLIP, std::conditional_t<LINK, PosteriorClipLinkArgs, PosteriorClipArgs>,
+                                                std::conditional_t<KNOWN, PosteriorKnownArgs, PosteriorArgs>>> Args;
   static bool fast_ok(const Args& args, int F) {
     const PosteriorArgs& a = post_base(args);
     bool ok = F % 4 == 0 && al16(a.bias) && al16(a.xin) && al16(a.xout) && a.ldx % 4 == 0 && a.ldo % 4 == 0 &&
               (!a.z || (al16(a.z) && a.ldzz % 4 == 0 && a.z_step_stride % 4 == 0));
     if constexpr (MODE != POST_PLAIN) ok = ok && al16(post_clip(args).lo) && al16(post_clip(args).hi);
     if constexpr (KNOWN) ok = ok && al16(post_known(args).known) && post_known(args).ldk % 4 == 0;
-    if constexpr (MODE == POST_HIST) ok = ok && al16(args.hist) && args.ldh % 4 == 0;
+    if constexpr (MODE == POST_HIST) ok = ok && al16(post_hist(args).hist) && post_hist(args).ldh % 4 == 0;
     return ok;
   }
-  template <int NFB> struct Pre { float4 bias[NFB][4]; };
+  // LINK: the bias is not held across the K loop; its quads are requested with the x_t quads (32 registers less where the link's
+  // branch needs them)
+  template <int NFB> struct Pre { float4 bias[LINK ? 1 : NFB][LINK ? 1 : 4]; };
   template <int NFB, bool FAST>
   static __device__ __forceinline__ Pre<NFB> prefetch(const Args& args, int fw, int lane, int F) {
     const PosteriorArgs& a = post_base(args);
     Pre<NFB> r;
     const int h = lane >> 5;
+    if constexpr (LINK) { r.bias[0][0] = make_float4(0.f, 0.f, 0.f, 0.f); return r; }
 #pragma unroll
     for (int fb = 0; fb < NFB; ++fb)
 #pragma unroll
       for (int q = 0; q < 4; ++q) r.bias[fb][q] = ldq<FAST>(a.bias, fw + 32 * fb + 8 * q + 4 * h, F);
     return r;
   }
+  // LINK: a wave whose columns start below n_link (uniform) walks its tile with sigma on the unfolded x0 of the columns below n_link; every
+  // other wave runs the walk of the form without a link, so the transcendentals are paid only where link columns are
   template <int NFB, int NPB, bool FAST>
   static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& args, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
+    if constexpr (LINK) {
+      if (fw < post_n_link(args)) walk<NFB, NPB, FAST, true>(acc, args, pre, fw, pw, lane, F, P);
+      else walk<NFB, NPB, FAST, false>(acc, args, pre, fw, pw, lane, F, P);
+    } else walk<NFB, NPB, FAST, false>(acc, args, pre, fw, pw, lane, F, P);
+  }
+  // the quad walk.  LK: the link on the columns below n_link
+  template <int NFB, int NPB, bool FAST, bool LK>
+  static __device__ __forceinline__ void walk(f32x16 (&acc)[NFB][NPB], const Args& args, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P) {
     constexpr bool PLAIN = MODE == POST_PLAIN, CLIP = MODE == POST_CLIP, HIST = MODE == POST_HIST;
     constexpr bool ALL = post_quads_ahead(MODE, KNOWN) == 0;
-    constexpr int QB = ALL ? 4 : post_quads_ahead(MODE, KNOWN);
+    // LINK: the bias quad rides along with the x_t quads; clip then asks for one quad at a time (two still spill one VGPR)
+    constexpr int QB = ALL ? 4 : (LINK && CLIP) ? 1 : post_quads_ahead(MODE, KNOWN);
     const PosteriorArgs& a = post_base(args);
     const int l31 = lane & 31, h = lane >> 5;
     const int t = a.t_dev ? *a.t_dev : a.t_imm;
@@ -588,7 +628,7 @@ struct EpiPosterior {
       if constexpr (CLIP) cC = a.coef[4 * t + 2];
       const float* c = post_clip(args).x0coef + 4 * t;
       cP = c[0]; cQ = c[1]; cE = c[2]; cF = c[3];
-      if constexpr (HIST) cH = args.hcoef[t];
+      if constexpr (HIST) cH = post_hist(args).hcoef[t];
     }
     const bool hz = cH != 0.f;           // uniform: H = 0 skips the history read
     float La = 1.f, Ls = 0.f;
@@ -609,8 +649,8 @@ struct EpiPosterior {
         const int p = pw + 32 * pb + l31;
         const int pc = p < P ? p : P - 1;
         float* hrow = nullptr;
-        if constexpr (HIST) hrow = args.hist + (size_t)pc * args.ldh;
-        float4 xq[4], lq[4], hq[4], pq[4], kq[4];
+        if constexpr (HIST) hrow = post_hist(args).hist + (size_t)pc * post_hist(args).ldh;
+        float4 xq[4], lq[4], hq[4], pq[4], kq[4], bq[4];
 #pragma unroll
         for (int q0 = 0; q0 < 4; q0 += QB) {
           if constexpr (!ALL) {
@@ -618,6 +658,7 @@ struct EpiPosterior {
             for (int q = q0; q < q0 + QB; ++q) {
               const int f = fw + 32 * fb + 8 * q + 4 * h;
               xq[q] = ldq<FAST>(a.xin + (size_t)pc * a.ldx, f, F);
+              if constexpr (LINK) bq[q] = ldq<FAST>(a.bias, f, F);
               if constexpr (!PLAIN) {
                 lq[q] = ldq<FAST>(post_clip(args).lo, f, F);
                 hq[q] = ldq<FAST>(post_clip(args).hi, f, F);
@@ -633,7 +674,9 @@ struct EpiPosterior {
           for (int q = q0; q < q0 + QB; ++q) {
             const int f = fw + 32 * fb + 8 * q + 4 * h;
             const bool ok = p < P && f < F;
-            const float4 bv = pre.bias[fb][q];
+            float4 bv;
+            if constexpr (LINK) bv = bq[q];
+            else bv = pre.bias[fb][q];
             float4 x;
             if constexpr (ALL) x = xall[fb][pb][q];
             else x = xq[q];
@@ -666,7 +709,8 @@ struct EpiPosterior {
               if constexpr (PLAIN && !KNOWN) o[r] = fmaf(cA, xv[r], fmaf(cB, e[r], cC * zv[r]));
               else if constexpr (PLAIN) o[r] = fmaf(cA, xv[r], fmaf(cB, e[r], cC * (cz ? zv[r] : 0.f)));
               else {
-                const float x0 = fmaf(cP, xv[r], cQ * e[r]);
+                float x0 = fmaf(cP, xv[r], cQ * e[r]);
+                if constexpr (LK) x0 = f + r < post_n_link(args) ? link_sigmoid(x0) : x0;
                 x0c[r] = fminf(fmaxf(x0, lv[r]), hv[r]);
                 if constexpr (CLIP) o[r] = fmaf(cE, x0c[r], fmaf(cF, xv[r], cC * (cz ? zv[r] : 0.f)));
                 else o[r] = fmaf(cE, x0c[r], fmaf(cF, xv[r], cH * pv[r]));      // cE holds G_t
@@ -801,22 +845,65 @@ struct EpiMse {
 // MASKED (osd_set_loss_mask): a NaN component of the target means "not observed" (k_elem.hip: mask_mark);
 // its d is zeroed right after d = e - nz, so it adds rho(0) = 0 to the loss and rho'(0) = 0 to dout -- one compare and one select
 // per element, nothing held across the tile.  pred is not written (only the constraint losses read it, and they are refused).
-template <bool MASKED>
+//
+// LINK (osd_set_output_link): columns f < n_link are logits of a Bernoulli mean and carry cross-entropy
+// instead of rho.  With o = acc + bias and y the target (x0 under OSD_PRED_SAMPLE; inside [0, 1] after a mixup):
+//   rho = max(o, 0) - o y + log1p(exp(-|o|))                 d rho / d o = sigma(o) - y = (1 - y) sigma(o) - y sigma(-o)
+// from one hardware exp2 (e = exp(-|o|)), one log2 and one rcp per element; the last form has no cancellation at a confident right
+// call.  rho(0) = ln 2, so the padding invariant above does not hold in these columns: an element enters the sum and dout only when
+// its row < P, its column < F and its target is not NaN (the link form always treats NaN as "not observed": it is the masked form
+// too), by an explicit select.  The host folds l2's 2 into gscale; the link columns take it out again (x 0.5, exact).  A 32-column
+// block that starts at or past n_link (wave-uniform) runs the code of the form without a link, so the transcendentals are paid only
+// where link columns are; a block that holds the boundary selects per element.  pred is not written.
+template <bool LINK> struct LossArgsT;
+template <> struct LossArgsT<false> {
+  EpiMse::Args m;               // bias, noise, dout, pred, loss, inv_count, gscale: EpiMse's meaning
+  const float* tw;              // dev [T] per-timestep weights, or null (every row weighs 1)
+  const int* t_index;           // dev [P] timestep index of each row, in [0, T); read only when tw is non-null
+  int kind; float delta;
+};
+template <> struct LossArgsT<true> : LossArgsT<false> { int n_link; };   // columns [0, n_link) carry the logistic link
+template <bool MASKED, bool LINK = false>
 struct EpiLossT {
+  static_assert(!LINK || MASKED, "the link form is the masked form as well");
   static constexpr bool COUNTED_STORES = false;   // dout / pred are optional
   static constexpr bool XBUF = true;
   template <class A> static __device__ __forceinline__ void slice(A&, int) {}
-  struct Args {
-    EpiMse::Args m;               // bias, noise, dout, pred, loss, inv_count, gscale: EpiMse's meaning
-    const float* tw;              // dev [T] per-timestep weights, or null (every row weighs 1)
-    const int* t_index;           // dev [P] timestep index of each row, in [0, T); read only when tw is non-null
-    int kind; float delta;
-  };
+  typedef LossArgsT<LINK> Args;
   static bool fast_ok(const Args& a, int F) { return EpiMse::fast_ok(a.m, F); }
   template <int NFB> using Pre = EpiMse::Pre<NFB>;
   template <int NFB, bool FAST>
   static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
     return EpiMse::prefetch<NFB, FAST>(a.m, fw, lane, F);
+  }
+  // LINK: one element of a block that holds link columns.  o the logit (or the output), y the target, link: f < n_link, ok: the element
+  // exists and is observed.  Returns the scaled dout; adds the unweighted rho to q
+  static __device__ __forceinline__ float link_point(int kind, float delta, float wg, float wgl, float o, float y, bool link, bool ok, float& q) {
+    if (link) {
+      const float e = __builtin_amdgcn_exp2f(fabsf(o) * -1.4426950408889634f);
+      const float r = __builtin_amdgcn_rcpf(1.0f + e);
+      const float er = e * r;
+      const float sp = o >= 0.f ? r : er, sn = o >= 0.f ? er : r;        // sigma(o), sigma(-o)
+      const float rho = fmaf(-o, y, fmaxf(o, 0.f)) + 0.6931471805599453f * __builtin_amdgcn_logf(1.0f + e);
+      q += ok ? rho : 0.f;
+      return ok ? ((1.0f - y) * sp - y * sn) * wgl : 0.f;
+    }
+    float d = ok ? o - y : 0.f;
+    point(kind, delta, d, q);
+    return d * wg;
+  }
+  // ... and one quad of it: e the outputs, nz the targets, f the quad's first column, cols / prow what exists
+  static __device__ __forceinline__ float4 link_quad(int kind, float delta, float w, float gs, int n_link, int f, int fo, int cols, bool prow,
+                                                     const float4& e, const float4& nz, float& part) {
+    const float wg = w * gs, wgl = w * (kind == 0 ? 0.5f * gs : gs);
+    float q = 0.f;
+    float4 d;
+    d.x = link_point(kind, delta, wg, wgl, e.x, nz.x, f < n_link, prow && fo < cols && nz.x == nz.x, q);
+    d.y = link_point(kind, delta, wg, wgl, e.y, nz.y, f + 1 < n_link, prow && fo + 1 < cols && nz.y == nz.y, q);
+    d.z = link_point(kind, delta, wg, wgl, e.z, nz.z, f + 2 < n_link, prow && fo + 2 < cols && nz.z == nz.z, q);
+    d.w = link_point(kind, delta, wg, wgl, e.w, nz.w, f + 3 < n_link, prow && fo + 3 < cols && nz.w == nz.w, q);
+    part += w * q;
+    return d;
   }
   // rho(d) into `part`, rho'(d) back into d; d = 0 gives 0 and 0
   static __device__ __forceinline__ void point(int kind, float delta, float& d, float& part) {
@@ -877,6 +964,12 @@ struct EpiLossT {
             const float4 e = make_float4(acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w);
             if constexpr (!MASKED)
               if (a.pred && prow) stq<FAST>(a.pred + (size_t)(pw + p) * a.ldp, fw + 32 * fb + fo, F, e);
+            if constexpr (LINK) {
+              if (fw + 32 * fb < al.n_link) {          // uniform: the block holds link columns
+                xp.put(pb, q, l31, h, link_quad(kind, delta, wrow[pb], a.gscale, al.n_link, fw + 32 * fb + fo, fo, cols, prow, e, nz, part));
+                continue;
+              }
+            }
             float4 d = make_float4(e.x - nz.x, e.y - nz.y, e.z - nz.z, e.w - nz.w);
             if constexpr (MASKED) unobserved(nz, d);
             if (!prow || fo >= cols) d.x = 0.f;
@@ -908,6 +1001,13 @@ struct EpiLossT {
       const float4 e = make_float4(acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w);
       if constexpr (!MASKED)
         if (a.pred && prow) stq<FAST>(a.pred + (size_t)p * a.ldp, f, F, e);
+      if constexpr (LINK) {
+        if (fw + 32 * fb < al.n_link) {          // uniform: the block holds link columns
+          const float4 dl = link_quad(kind, delta, wrow[pb], a.gscale, al.n_link, f, f, F, prow, e, nz, part);
+          if (a.dout && prow) stq<FAST>(a.dout + (size_t)p * a.ldd, f, F, dl);
+          continue;
+        }
+      }
       float4 d = make_float4(e.x - nz.x, e.y - nz.y, e.z - nz.z, e.w - nz.w);
       if constexpr (MASKED) unobserved(nz, d);
       if (!prow || f >= F) d.x = 0.f;

@@ -40,6 +40,8 @@ GemmArgs output_proj_args(osd_handle* h, const FwdWs& ws, int64_t n, bool padded
 int upload_null_cond(osd_handle* h, int slot, const float* null_cond_host, const float** dev);
 int check_ready(osd_handle* h);
 int check_rows(int64_t n);
+// osd_set_output_link and osd_set_prediction can be called in either order: every call that uses the link refuses a type other than sample
+int check_output_link(const osd_handle* h);
 
 // ---- the per-layer chunk drivers (api.hip: chain_chunk, split.hip: split_chain_chunk) ----
 // Drop the slot's previous graph once everything replayed from it has finished.

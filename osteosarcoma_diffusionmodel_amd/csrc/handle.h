@@ -94,6 +94,7 @@ struct Clip {
   const float* bounds;         // dev [2][ld]: the lo row, then the hi row; null = no clipping
   int ld;
   const float* x0_coef;        // dev [S][4] = (P, Q, E, F)
+  int n_link;                  // columns [0, n_link) of the output are logits (osd_set_output_link): sigma before the clamp; 0 = none
 };
 
 // The DPM-Solver++(2M) multistep update (osd_sample_chain_multistep, EpiPosterior<POST_HIST>): the chain keeps the previous step's clipped x0.
@@ -230,6 +231,10 @@ struct osd_handle {
   // training on incomplete rows (osd_set_loss_mask): persistent.  NaN in x0 = not observed; the q_sample kernels zero-fill it and mark the
   // target with NaN, the loss runs EpiLossT<true> on the fp32 launcher.  false: today's launches
   bool loss_mask = false;
+  // logistic link on the leading output columns (osd_set_output_link): persistent.  Columns [0, n_link) of the output are logits of a
+  // Bernoulli mean: cross-entropy in the training loss (EpiLossT<true, true>), sigma in front of the clamp of the x0-unfolded posterior
+  // launches and in osd_convert_prediction.  0: today's launches.  Needs OSD_PRED_SAMPLE; either can be set second, so the calls check
+  int n_link = 0;
   // differentially private training (osd_set_dp_clip; dp.h): persistent.  dp_clip = the per-row gradient bound C (0: off, today's launches);
   // dp_norms = dev [2][dp_norms_cap]: s_r, then the clip factors c_r, of the last clipped call's dp_rows rows (-1: none yet); dp_plan = the
   // cached item lists of the two launches (k_dp.hip)

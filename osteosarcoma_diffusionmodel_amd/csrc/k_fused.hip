@@ -208,6 +208,13 @@ hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorCli
 hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorHistArgs& a) {
   return a.c.known ? launch_posterior_as<EpiPosterior<POST_HIST, true>>(s, g, a) : launch_posterior_as<EpiPosterior<POST_HIST, false>>(s, g, a);
 }
+// the same two with the logistic link on the leading columns (osd_set_output_link)
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorClipLinkArgs& a) {
+  return a.c.known ? launch_posterior_as<EpiPosterior<POST_CLIP, true, true>>(s, g, a) : launch_posterior_as<EpiPosterior<POST_CLIP, false, true>>(s, g, a);
+}
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorHistLinkArgs& a) {
+  return a.h.c.known ? launch_posterior_as<EpiPosterior<POST_HIST, true, true>>(s, g, a) : launch_posterior_as<EpiPosterior<POST_HIST, false, true>>(s, g, a);
+}
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a) {
   if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiMse>(s, g, a);
   return launch_gemm<TileSmall, true, true, EpiMse>(s, g, a);
@@ -221,6 +228,11 @@ hipError_t launch_loss(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a)
 hipError_t launch_loss_masked(hipStream_t s, const GemmArgs& g, const EpiLossT<true>::Args& a) {
   if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiLossT<true>>(s, g, a);
   return launch_gemm<TileSmall, true, true, EpiLossT<true>>(s, g, a);
+}
+// ... and with the logistic link on the leading columns (EpiLossT<true, true>; osd_set_output_link): fp32 only
+hipError_t launch_loss_link(hipStream_t s, const GemmArgs& g, const EpiLossT<true, true>::Args& a) {
+  if (use_big_tile(g.F, g.P)) return launch_gemm<TileBig, true, true, EpiLossT<true, true>>(s, g, a);
+  return launch_gemm<TileSmall, true, true, EpiLossT<true, true>>(s, g, a);
 }
 
 // se[r] = part[0][r] + part[1][r] + ... in slot order (+ *poison, a word that is 0 unless a squad launch of the same call gave up

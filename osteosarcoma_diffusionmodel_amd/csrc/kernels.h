@@ -24,11 +24,13 @@ hipError_t launch_input_guided_splitk(hipStream_t s, const GemmArgs& g, const Ep
 hipError_t launch_input_splitk(hipStream_t s, const GemmArgs& g, const EpiInput::Args& a, float* slabs, int slices);
 // output_proj + one step of the reverse chain (EpiPosterior<MODE, KNOWN>), one tile choice.  The argument type picks MODE: plain, around
 // observed values, with the predicted x0 clipped to per-feature bounds (KNOWN = a.known != null), the DPM-Solver++(2M) multistep
-// update on the clipped x0 (KNOWN = a.c.known != null)
+// update on the clipped x0 (KNOWN = a.c.known != null); the Link argument types add the logistic link to the last two
 hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorArgs& a);
 hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorKnownArgs& a);
 hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorClipArgs& a);
 hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorHistArgs& a);
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorClipLinkArgs& a);
+hipError_t launch_posterior(hipStream_t s, const GemmArgs& g, const PosteriorHistLinkArgs& a);
 hipError_t launch_mse(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a);
 // k_b3t.hip: precision = 1 (hipErrorInvalidValue: outside the kernel's preconditions -- run the fp32 launch)
 hipError_t launch_mse_b3t(hipStream_t s, const GemmArgs& g, const EpiMse::Args& a);
@@ -37,6 +39,8 @@ hipError_t launch_loss(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a)
 hipError_t launch_loss_b3t(hipStream_t s, const GemmArgs& g, const EpiLoss::Args& a);
 // ... with the unobserved elements of a NaN-marked target left out (EpiLossT<true>; osd_set_loss_mask).  fp32 only.
 hipError_t launch_loss_masked(hipStream_t s, const GemmArgs& g, const EpiLossT<true>::Args& a);
+// ... and cross-entropy on the logits in columns [0, a.n_link) (EpiLossT<true, true>; osd_set_output_link).  fp32 only.
+hipError_t launch_loss_link(hipStream_t s, const GemmArgs& g, const EpiLossT<true, true>::Args& a);
 // output_proj + per-row squared error (EpiRowSq), launch_mse's tile choice, then k_rowsq_reduce: se[P].  a.part: rowsq_slots(F) x a.ld
 // floats.  poison: a device word added to every row (0, or the NaN of a squad launch that gave up), or null.  fp32 only.
 constexpr int ROWSQ_WF = 64;      // feature extent of a wave in both tiles of the tile choice

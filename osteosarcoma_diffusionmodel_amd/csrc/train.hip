@@ -740,6 +740,19 @@ struct LossStep {
     ea.bias = h->params[a.pm.out_b]; ea.noise = noise && h->pred_type == OSD_PRED_EPSILON ? noise : w.noise; ea.ldn = D;
     ea.dout = grads ? w.d_out : nullptr; ea.ldd = D; ea.pred = cp ? w.pred : nullptr; ea.ldp = D; ea.loss = loss_out;
     ea.inv_count = (float)(1.0 / count);
+    if (h->n_link > 0) {
+      // osd_set_output_link: cross-entropy on the logits in columns [0, n_link), the configured kind elsewhere, on EpiLossT<true, true>
+      // -- the masked form as well: a NaN of the target (osd_set_loss_mask marked it) stays out.  The target is x0 in w.noise (the type
+      // is sample); gscale carries l2's folded 2, which the link columns take out again.  The fp32 launcher only, whatever the precision
+      ea.noise = w.noise; ea.pred = nullptr;
+      ea.gscale = (float)((h->loss_kind == OSD_LOSS_L2 ? 2.0 : 1.0) * (double)loss_scale / count);
+      EpiLossT<true, true>::Args ek{};
+      ek.m = ea; ek.tw = h->loss_tw_set ? h->loss_tw : nullptr; ek.t_index = tc.t_idx; ek.kind = h->loss_kind; ek.delta = h->loss_delta;
+      ek.n_link = h->n_link;
+      h->last_train_path |= OSD_TP_LOSS_EPI | OSD_TP_LINK;
+      OSD_HIP(launch_loss_link(s, g, ek));
+      return OSD_OK;
+    }
     if (h->loss_mask) {
       // osd_set_loss_mask: every kind (the default l2 without a table included) on EpiLossT<true>, against the NaN-marked target in
       // w.noise whoever supplied eps; the fp32 launcher only, whatever the precision
@@ -852,6 +865,18 @@ static int mask_supported(const osd_handle* h, bool grads) {
   return OSD_EUNSUPPORTED;
 }
 
+// What a call under osd_set_output_link cannot be: anything that would read a logit as x0^.
+static int link_supported(const osd_handle* h, bool grads) {
+  OSD_TRY(check_output_link(h));
+  const char* why = nullptr;
+  if ((h->cons.n_pathways > 0 && h->w_pathway != 0.0) || (h->cons.n_a > 0 && h->w_mutexpr != 0.0))
+    why = "the constraint losses read the raw output as x0^ (osd_set_constraints(h, NULL) clears them)";
+  else if (grads && h->dp_clip > 0.0) why = "per-row gradient clipping (osd_set_dp_clip) is not supported with a linked output";
+  if (!why) return OSD_OK;
+  set_error("output link (osd_set_output_link): %s", why);
+  return OSD_EUNSUPPORTED;
+}
+
 // checks in order: ready, rows, (one-shots consumed), null tensors, empty batch, row offset, event count, grads[i], then the device
 int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, int64_t n, const int32_t* t_index, const float* noise,
                            const float* const* masks, uint64_t seed, int64_t row_offset, int flags, float* loss_out,
@@ -867,6 +892,7 @@ int osd_train_loss_fwd_bwd(osd_handle* h, const float* x0, const float* cond, in
   OSD_TRY(check_row_offset(row_offset, n));
   OSD_TRY(tc.check_outputs(events, n_events, grads));
   if (h->loss_mask) OSD_TRY(mask_supported(h, grads != nullptr));      // before any launch: no gradient buffer is touched
+  if (h->n_link > 0) OSD_TRY(link_supported(h, grads != nullptr));
   if (grads && h->dp_clip > 0.0) OSD_TRY(dp_supported(h, from_src, loss_scale, events));      // before any launch: no gradient buffer is touched
   OSD_TRY(tc.enter());
   LossStep step{tc, h, h->arch, tc.s, n, x0, cond, noise, masks, seed, (uint32_t)row_offset, loss_out, grads, loss_scale, events, from_src, cond_drop};
@@ -888,6 +914,10 @@ static int bound_checks(osd_handle* h, const float* x0, const float* cond, int64
   if (h->precision == 1) { set_error("the per-row squared error runs on the fp32 kernels only (precision 0)"); return OSD_EUNSUPPORTED; }
   if (h->loss_mask) {
     set_error("masked loss (osd_set_loss_mask): the per-row squared error (osd_row_sq_error, osd_bound_sweep) has no masked form; osd_set_loss_mask(h, 0) first");
+    return OSD_EUNSUPPORTED;
+  }
+  if (h->n_link > 0) {
+    set_error("output link (osd_set_output_link): the per-row squared error (osd_row_sq_error, osd_bound_sweep) has no Bernoulli form; it is refused, not approximated");
     return OSD_EUNSUPPORTED;
   }
   return OSD_OK;

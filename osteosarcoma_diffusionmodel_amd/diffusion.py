@@ -150,6 +150,11 @@ class _Engine:
         self.serial = 0                 # bumped by every call that rewrites the handle's training workspace
         self.dp_clip = 0.0              # the per-row gradient bound this handle was last given (osd_set_dp_clip; 0: off, the library's default)
         self.loss_mask = False          # whether this handle was last told to mask NaN (osd_set_loss_mask; off: the library's default)
+        self.n_link = 0                 # the logistic columns this handle was last given (osd_set_output_link; 0: off, the library's default)
+
+    def set_output_link(self, n_link: int):
+        L.check(L.lib().osd_set_output_link(self.handle, int(n_link)))
+        self.n_link = int(n_link)
 
     def set_loss_mask(self, model: "BiologyAwareDiffusionModel"):
         """Validate the model's missing_values and hand it to the handle (osd_set_loss_mask: persistent)."""
@@ -373,6 +378,11 @@ class BiologyAwareDiffusionModel(nn.Module):
         # "epsilon" (the reference's and the default: everything as without the key), "v_prediction" or "sample".  The training target, the
         # constraint losses' x0^, min_snr's form, every sampler and sampling option follow it.  A plain attribute like the loss keys
         self.prediction_type: str = OB.check_prediction_type(dm.get("prediction_type", "epsilon"))
+        # how the mutation block of the output is read: config['model']['diffusion']['mutation_link'] = "identity"
+        # (the default: everything as without the key) or "logistic" -- the first mutation_dim outputs are logits of the Bernoulli mean
+        # E[x0 | x_t]: cross-entropy in the training step, sigma inside every sampling step and in predict(as_=...).  Needs
+        # prediction_type "sample" (ValueError otherwise, here and from every call).  A plain attribute like prediction_type
+        self.mutation_link: str = OB.check_mutation_link(dm.get("mutation_link", "identity"), self.prediction_type)
         # differentially private training: None / 0 (the default: today's training call, bit for bit) or the bound C
         # on every row's (patient's) own gradient norm.  A training call with gradients then returns (1/n) sum_r min(1, C / (|g_r| + 1e-6)) g_r;
         # the loss stays the unclipped mean.  train.py's Trainer sets it from training.dp; a plain attribute for users of the bare model.
@@ -474,7 +484,19 @@ class BiologyAwareDiffusionModel(nn.Module):
     def _device(self) -> torch.device:
         return next(self.parameters()).device
 
+    def _linked(self) -> bool:
+        """Whether the mutation block carries the logistic link; ValueError for an unknown value or a prediction_type other than sample."""
+        from . import objective as OB
+        return OB.check_mutation_link(getattr(self, "mutation_link", "identity"), self.prediction_type) == "logistic"
+
+    def _refuse_link(self, what: str) -> None:
+        """What reads the network's output as x0^ (or folds x0^ away) has no form for a linked model: it is refused, by name."""
+        if self._linked():
+            raise ValueError(f"{what} is not available with mutation_link 'logistic': it would read the mutation logits as x0^ "
+                             f"(set mutation_link to 'identity', or use sample() / predict(as_=...), which carry the link)")
+
     def _engine(self) -> _Engine:
+        linked = self._linked()      # before the device: ValueError for mutation_link / prediction_type that do not go together
         dev = self._device()
         if dev.type != "cuda":
             raise RuntimeError("BiologyAwareDiffusionModel (osteosarcoma_diffusionmodel_amd) runs on MI355X only: "
@@ -489,9 +511,14 @@ class BiologyAwareDiffusionModel(nn.Module):
         if eng.constraints_version != self._constraints_version:
             eng.set_constraints(self._constraints)
             eng.constraints_version = self._constraints_version
+        n_link = self.mutation_dim if linked else 0
+        if eng.n_link and not n_link:
+            eng.set_output_link(0)      # off before the type may leave "sample"
         if eng.prediction_type != self.prediction_type:
             eng.set_prediction(self)    # raises ValueError on an unknown value; the handle then keeps its previous type
             eng.prediction_type = self.prediction_type
+        if eng.n_link != n_link:
+            eng.set_output_link(n_link)   # on after the type has become "sample"
         state = self._loss_state()
         if eng.loss_state != state:
             eng.set_loss(self)          # raises ValueError on an unknown value; the handle then keeps its previous setting
@@ -601,6 +628,7 @@ class BiologyAwareDiffusionModel(nn.Module):
         """se [n] (fp32): the squared error sum_d (out - target)^2 of the network's raw output at q_sample(x_0, t) against the training
         target of ``prediction_type``, per row, in eval mode.  ``t``: one timestep index per row.  ``noise`` [n, D] is injected, else
         the draws are generated and keyed by (seed, row_offset + row, t) alone.  Deterministic: the same call returns the same bits."""
+        self._refuse_link("row_sq_error")
         x_0, conditions = self._bound_inputs(x_0, conditions, "row_sq_error")
         eng = self._engine()
         n = x_0.shape[0]
@@ -656,6 +684,7 @@ class BiologyAwareDiffusionModel(nn.Module):
         from . import likelihood as LK
         from . import objective as OB
         ptype = OB.check_prediction_type(self.prediction_type)
+        self._refuse_link("variational_bound")          # no likelihood bound for a Bernoulli block: refused, not approximated
         ts = LK.select_timesteps(self.num_steps, num_timesteps, timesteps)        # ValueError for a bad set, before any device work
         x_0, conditions = self._bound_inputs(x_0, conditions, "variational_bound")
         D, dev = self.data_dim, x_0.device
@@ -674,6 +703,7 @@ class BiologyAwareDiffusionModel(nn.Module):
         """(timesteps [S] int64, profile [S] float64): the cohort mean of se / D per timestep -- the loss curve of the configured
         target over t -- from the same sweep as ``variational_bound``."""
         from . import likelihood as LK
+        self._refuse_link("loss_profile")
         ts = LK.select_timesteps(self.num_steps, num_timesteps, None)
         x_0, conditions = self._bound_inputs(x_0, conditions, "loss_profile")
         se = self._bound_sweep(x_0, conditions, ts, None, seed, 0)
@@ -705,12 +735,16 @@ class BiologyAwareDiffusionModel(nn.Module):
         (x0^ = P x_t + Q out), "eps" ((x_t - a x0^)/b) or "v" (a eps^ - b x0^), a = sqrt_alphas_cumprod[t], b =
         sqrt_one_minus_alphas_cumprod[t].  The conversion is one row-affine pass (osd_convert_prediction) with coefficients formed in float64
         and rounded once; the model's own reading and "raw" are the output unchanged.  ``guidance_scale`` combines raw outputs, which is
-        guidance in eps-space for every type.  Conversions are inference only (no autograd through them)."""
+        guidance in eps-space for every type.  Conversions are inference only (no autograd through them).
+
+        With ``mutation_link = "logistic"`` "raw" holds logits in the mutation columns; "x0" is sigma of them there (and the output
+        elsewhere), "eps" and "v" are derived from that x0^; guidance then acts on the logit in those columns."""
         if as_ != "raw" and as_ not in self._AS_KINDS:
             raise ValueError(f"as_ must be 'raw', 'eps', 'x0' or 'v', got {as_!r}")
+        linked = self._linked()
         out = self._raw_output(x_t, t, conditions, dropout_masks=dropout_masks, seed=seed, guidance_scale=guidance_scale)
         from . import objective as OB
-        if as_ == "raw" or as_ == self._OWN_AS[OB.check_prediction_type(self.prediction_type)]:
+        if as_ == "raw" or (not linked and as_ == self._OWN_AS[OB.check_prediction_type(self.prediction_type)]):
             return out
         if out.requires_grad:
             raise ValueError("predict(as_=...) converts without autograd: call it under torch.no_grad(), or use as_='raw'")
@@ -788,6 +822,7 @@ class BiologyAwareDiffusionModel(nn.Module):
     # -- p_sample / sample (models/diffusion.py:382-449) ------------------------------------------
     @torch.no_grad()
     def p_sample(self, x_t, t, conditions, *, noise=None, seed: Optional[int] = None):
+        self._refuse_link("p_sample")       # the single step folds x0^ away; sample() runs the x0-unfolded steps
         eng = self._engine()
         x_t = self._prep(x_t, self.data_dim, "x_t")
         conditions = self._prep(conditions, self.condition_dim, "conditions")
@@ -844,9 +879,18 @@ class BiologyAwareDiffusionModel(nn.Module):
 
         ``timestep_spacing`` chooses the S timesteps of ``num_inference_steps``, for either solver: ``"uniform"`` (``ddim.ddim_timesteps``)
         or ``"logsnr"`` (``ddim.logsnr_timesteps``: uniform in ln(sqrt(abar)/sqrt(1-abar)); better for the multistep solver from about ten
-        steps on, worse for DDIM and at five).  Without ``num_inference_steps`` it must be ``"uniform"``."""
+        steps on, worse for DDIM and at five).  Without ``num_inference_steps`` it must be ``"uniform"``.
+
+        ``mutation_link = "logistic"``: the mutation columns of the output are logits, and every step takes
+        x0^ = sigma(out) there before the clamp, so every returned mutation value lies in [0, 1] with no ``x0_bounds`` given.  Such a model
+        always runs the x0-unfolded steps -- the ``x0_bounds`` path with infinite bounds where none are given, or ``solver="dpmpp_2m"`` --
+        whatever the other options are: per-layer kernels (``last_sampler == "graph"``), fp32 (``precision = "bf16x3"`` raises
+        ValueError).  ``guidance_scale`` combines raw outputs, so on the mutation columns it acts in logit space."""
         from . import objective as OB
         pred = OB.check_prediction_type(self.prediction_type)
+        linked = self._linked()
+        if linked and self.precision == "bf16x3":
+            raise ValueError("mutation_link 'logistic' samples on the fp32 kernels: precision='bf16x3' is not accepted")
         sched = dict(sqrt_alphas_cumprod=self.sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod=self.sqrt_one_minus_alphas_cumprod)
         guide = self._guidance(guidance_scale)
         if solver not in (None, "ddim", "dpmpp_2m"):
@@ -867,6 +911,9 @@ class BiologyAwareDiffusionModel(nn.Module):
         if x0_bounds is not None and x0_bounds is not False:
             from .generate import assemble_bounds
             bounds = assemble_bounds(x0_bounds, self.mutation_dim, self.expression_dim, self.pathway_dim)
+        elif linked:
+            # the x0-unfolded steps carry the link: all columns free (sigma itself keeps the mutation block inside [0, 1])
+            bounds = (np.full(self.data_dim, -np.inf, dtype=np.float32), np.full(self.data_dim, np.inf, dtype=np.float32))
         kn = None
         if known is not None:
             kn = self._prep(known, self.data_dim, "known")

@@ -350,6 +350,21 @@ def checkpoint_prediction_type(checkpoint: dict, config: dict) -> Optional[str]:
     return None
 
 
+def checkpoint_mutation_link(checkpoint: dict, config: dict) -> Optional[str]:
+    """``checkpoint_prediction_type`` for ``mutation_link``: the checkpoint's link when ``config`` names none, None when there is
+    nothing to take over, ValueError when both name different links -- a logit read as x0^ gives no other sign.  A checkpoint without
+    the key is an identity model."""
+    from .objective import check_mutation_link
+    saved = ((checkpoint.get("config") or {}).get("model") or {}).get("diffusion", {}).get("mutation_link")
+    asked = ((config or {}).get("model") or {}).get("diffusion", {}).get("mutation_link")
+    saved_link = check_mutation_link("identity" if saved is None else saved)
+    if asked is None:
+        return None if saved is None else saved_link
+    if check_mutation_link(asked) != saved_link:
+        raise ValueError(f"config['model']['diffusion']['mutation_link'] is {asked!r} but the checkpoint was trained with {saved_link!r}")
+    return None
+
+
 def load_trained_model(checkpoint_path: Path, config: dict, device: str, use_ema: Optional[bool] = None):
     """Checkpoint -> model (utils/generate.py:238-298): condition width from the saved
     ``condition_embed.mlp.0.weight``, feature dims from the processed CSV headers.
@@ -357,7 +372,7 @@ def load_trained_model(checkpoint_path: Path, config: dict, device: str, use_ema
     (``ema_state_dict``) when the file has them, else ``model_state_dict``; False always ``model_state_dict`` (the last iterate);
     True the averaged ones, KeyError when the file has none.
     ``prediction_type`` (what the network was trained to predict) travels in the checkpoint's own config: a ``config`` without the key
-    adopts the checkpoint's, one that names a different type than the checkpoint raises ValueError."""
+    adopts the checkpoint's, one that names a different type than the checkpoint raises ValueError; ``mutation_link`` likewise."""
     from .diffusion import BiologyAwareDiffusionModel
     logger.info(f"Loading model from {checkpoint_path}")
     checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
@@ -375,14 +390,26 @@ def load_trained_model(checkpoint_path: Path, config: dict, device: str, use_ema
     if arch not in ("diffusion", "cvae"):
         raise ValueError(f"Unknown architecture: {arch}")
     saved_pred = checkpoint_prediction_type(checkpoint, config) if arch == "diffusion" else None
+    saved_link = checkpoint_mutation_link(checkpoint, config) if arch == "diffusion" else None
     processed = Path(config["data"]["processed_dir"])
     dims = []
     for fname in ("mutation_matrix_aligned.csv", "expression_matrix_aligned.csv", "pathway_scores.csv"):
         dims.append(pd.read_csv(processed / fname, index_col=0, nrows=1).shape[1])
     if arch == "diffusion":
         saved_cond_dim = state_dict["condition_embed.mlp.0.weight"].shape[1]
+        build_config = config
+        if saved_pred is not None or saved_link is not None:
+            # what the checkpoint hands over is in place when the constructor checks that link and type go together; the caller's
+            # config is left alone
+            import copy
+            build_config = copy.deepcopy(config)
+            dm = build_config["model"]["diffusion"]
+            if saved_pred is not None:
+                dm["prediction_type"] = saved_pred
+            if saved_link is not None:
+                dm["mutation_link"] = saved_link
         model = BiologyAwareDiffusionModel(mutation_dim=dims[0], expression_dim=dims[1], pathway_dim=dims[2],
-                                           condition_dim=saved_cond_dim, config=config)
+                                           condition_dim=saved_cond_dim, config=build_config)
     else:
         # the reference reads the diffusion key even for a cVAE checkpoint (utils/generate.py:250) and fails on it;
         # here the condition width comes from the encoder's first Linear: in_features = data_dim + condition_dim
@@ -397,6 +424,8 @@ def load_trained_model(checkpoint_path: Path, config: dict, device: str, use_ema
         model.null_condition = [float(v) for v in saved_null]
     if saved_pred is not None:
         model.prediction_type = saved_pred
+    if saved_link is not None:
+        model.mutation_link = saved_link
     model.to(device)
     model.eval()
     logger.info("Model loaded successfully!")

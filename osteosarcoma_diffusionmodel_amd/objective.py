@@ -38,6 +38,27 @@ def check_prediction_type(prediction_type) -> str:
     return prediction_type
 
 
+# how the 0/1 mutation block of the output is read (config['model']['diffusion']['mutation_link']): "identity" --
+# an unbounded x0^ like every other column, the default -- or "logistic" -- the logit of the Bernoulli mean E[x0 | x_t], trained by
+# cross-entropy and sampled through sigma.  "logistic" needs prediction_type "sample": the linked columns are x0^
+MUTATION_LINKS = ("identity", "logistic")
+
+
+def check_mutation_link(mutation_link, prediction_type=None) -> str:
+    if not isinstance(mutation_link, str) or mutation_link not in MUTATION_LINKS:
+        raise ValueError(f"mutation_link must be 'identity' or 'logistic', got {mutation_link!r}")
+    if mutation_link == "logistic" and prediction_type is not None and prediction_type != "sample":
+        raise ValueError(f"mutation_link 'logistic' needs prediction_type 'sample' (the linked columns are x0^), "
+                         f"but prediction_type is {prediction_type!r}")
+    return mutation_link
+
+
+def link_loss(out: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """Per-element cross-entropy of a logit against a target in [0, 1]: max(o, 0) - o y + log1p(exp(-|o|)), the form the training
+    step's epilogue evaluates (``F.binary_cross_entropy_with_logits(reduction="none")``)."""
+    return out.clamp_min(0) - out * target + torch.log1p(torch.exp(-out.abs()))
+
+
 def check_loss_type(loss_type) -> str:
     if not isinstance(loss_type, str) or loss_type not in LOSS_KINDS:
         raise ValueError(f"loss_type must be 'l2', 'l1' or 'huber', got {loss_type!r}")

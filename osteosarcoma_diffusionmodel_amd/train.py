@@ -199,6 +199,12 @@ def denoiser_with_grad(model: BiologyAwareDiffusionModel, x_t, t32, cond, keep, 
 
 def diffusion_loss(model: BiologyAwareDiffusionModel, x_0, conditions, *, t=None, noise=None, dropout_masks=None, seed=None):
     """``model(x_0, conditions, return_loss=True)``: 0-d loss tensor supporting ``.backward()`` and ``.item()``."""
+    if model._linked():       # before the device: what reads the output as x0^ has no form for a linked model
+        cons = getattr(model, "_constraints", None)
+        if cons is not None and (cons["w_pc"] != 0.0 or cons["w_me"] != 0.0):
+            model._refuse_link("a training call with constraint losses")
+        if getattr(model, "dp_max_grad_norm", None):
+            model._refuse_link("a training call with dp_max_grad_norm")
     model._engine()           # raises on CPU: there is no CPU fallback
     params = model._param_list()
     return _DiffusionLoss.apply(model, x_0, conditions, t, noise, dropout_masks, seed, *params)
@@ -700,6 +706,15 @@ class Trainer:
                                  "over x0, which has no value at an unobserved element (set their weights to 0 or clear them)")
             self._check_incomplete_data(train_loader, val_loader)
             model.missing_values = "mask"
+        # model.diffusion.mutation_link: logistic -- what reads the output as x0^ is refused here, before the device
+        if getattr(model, "mutation_link", "identity") != "identity" and model._linked():
+            if self.validation_metric == "bound":
+                raise ValueError("mutation_link 'logistic' has no likelihood bound for the Bernoulli block: training.validation_metric must be 'loss'")
+            if tc.get("dp") is not None:
+                raise ValueError("mutation_link 'logistic' is not supported with training.dp (per-patient clipping)")
+            if cons is not None and (cons["w_pc"] != 0.0 or cons["w_me"] != 0.0):
+                raise ValueError("mutation_link 'logistic' is not supported with the constraint losses: they read the output as x0^ "
+                                 "(set their weights to 0 or clear them)")
         self.validation_timesteps = int(tc.get("validation_timesteps", 32))
         if self.validation_timesteps < 2:
             raise ValueError(f"training.validation_timesteps={self.validation_timesteps}: at least 2 (t = 0 and one more)")
@@ -805,7 +820,8 @@ class Trainer:
     def _option_state(self):
         m = self.model
         return tuple(getattr(m, attr, None) for attr, _, _ in ENGINE_OPTIONS) + (getattr(m, "dp_max_grad_norm", None),
-                                                                               getattr(m, "missing_values", None))
+                                                                               getattr(m, "missing_values", None),
+                                                                               getattr(m, "mutation_link", None))
 
     @staticmethod
     def _check_incomplete_data(*loaders):

@@ -986,6 +986,8 @@ class BiologicalValidator:
         ``mean_bpd_train`` and ``mean_bpd_holdout``.  0.5 / 0 / 0 is what a model that memorised nothing gives up to sampling
         noise."""
         from . import likelihood as LK
+        if hasattr(model, "_refuse_link"):
+            model._refuse_link("membership_audit")      # it scores with variational_bound, which a linked model does not have
         scores = []
         offset = 0
         for name, cohort in (("train", train), ("holdout", holdout)):

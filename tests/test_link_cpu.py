@@ -1,0 +1,304 @@
+"""CPU: the host side of the logistic link on the mutation block: the fp64 restatements the GPU tests rely on
+(link_helpers.py), the option's validation and checkpoint round trip, the ABI, and every refusal -- each a ValueError from the Python
+layer, before any device work."""
+import re
+from pathlib import Path
+
+import numpy as np
+import pandas as pd
+import pytest
+import torch
+import torch.nn.functional as F
+
+from osteosarcoma_diffusionmodel_amd import BiologyAwareDiffusionModel
+from osteosarcoma_diffusionmodel_amd import _lib as L
+from osteosarcoma_diffusionmodel_amd import objective as OB
+from osteosarcoma_diffusionmodel_amd.ddim import ddim_step_table, ddim_timesteps, ddim_x0_table, dpmpp_2m_table
+from osteosarcoma_diffusionmodel_amd.generate import checkpoint_mutation_link, load_trained_model
+from osteosarcoma_diffusionmodel_amd.train import Trainer
+from osteosarcoma_diffusionmodel_amd.validation import BiologicalValidator
+from helpers import SM, SM_H, config
+from link_helpers import LinkOracle, identity_loss_fn, link_columns, link_loss_fn, link_out
+from loss_helpers import Fp64Oracle, inputs
+from mask_helpers import mask_pattern, with_nan
+from pred_helpers import chain64, loss_fn
+from test_known_cpu import PLAN, cpu_model, make_case
+
+ROOT = Path(__file__).resolve().parents[1]
+SM_DIMS, SM_N = (8, 24, 8, 3), 16
+M = SM_DIMS[0]
+
+
+def _small():
+    return inputs(SM_DIMS, SM_H, SM_N, seed=17)
+
+
+def _oracle(x=None):
+    sd, x0, cond, t, noise, injected = _small()
+    return Fp64Oracle(sd, x0 if x is None else x, cond, t, noise, SM_H, injected, 0.2)
+
+
+# ---- the fp64 link loss ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind,delta", [("l2", 1.0), ("l1", 1.0), ("huber", 0.3)])
+def test_link_loss_is_bce_with_logits_on_the_link_columns_and_rho_elsewhere(kind, delta):
+    orc = _oracle()
+    table = torch.rand(1000, generator=torch.Generator().manual_seed(4)) + 0.05
+    pred = orc.pred.detach()
+    n, D = pred.shape
+    w = table.double()[orc.t].view(-1, 1)
+    bce = F.binary_cross_entropy_with_logits(pred[:, :M], orc.x0[:, :M], reduction="none")
+    assert torch.allclose(OB.link_loss(pred[:, :M], orc.x0[:, :M]), bce, rtol=1e-13, atol=1e-15)
+    want_link = (bce * w).sum() / (n * D)
+    # elsewhere: pred_helpers.loss_fn's rho, taken as the whole-row loss minus its own first M columns
+    cont = {"l2": F.mse_loss, "l1": F.l1_loss, "huber": lambda a, b, reduction: F.huber_loss(a, b, reduction=reduction, delta=delta)}[kind]
+    whole = loss_fn(orc, "sample", kind, delta, table)(pred)
+    own_head = (cont(pred[:, :M], orc.x0[:, :M], reduction="none") * w).sum() / (n * D)
+    got = link_loss_fn(orc, M, kind, delta, table)(pred)
+    assert abs(float(got) - float(want_link + whole - own_head)) <= 1e-13 * abs(float(got))
+    assert float(want_link) > 0 and abs(float(got) - float(whole)) > 1e-3 * float(whole)          # the link changes the objective
+    # M = 0 is the objective without a link, exactly
+    assert float(link_loss_fn(orc, 0, kind, delta, table)(pred)) == float(identity_loss_fn(orc, kind, delta, table)(pred))
+
+
+def test_link_gradient_agrees_with_central_differences():
+    orc = _oracle()
+    fn = link_loss_fn(orc, M, "huber", 0.3, None)
+    pd_ = orc.pred.detach().clone().requires_grad_(True)
+    (g,) = torch.autograd.grad(fn(pd_), pd_)
+    n, D = pd_.shape
+    # sigma(o) - y over n D on the link columns
+    want = (torch.sigmoid(pd_.detach()[:, :M]) - orc.x0[:, :M]) / (n * D)
+    assert torch.allclose(g[:, :M], want, rtol=1e-12, atol=1e-18)
+    h = 1e-6
+    for r, f in ((0, 0), (3, M - 1), (5, M), (SM_N - 1, D - 1), (7, 3), (2, M + 11)):
+        up, dn = pd_.detach().clone(), pd_.detach().clone()
+        up[r, f] += h
+        dn[r, f] -= h
+        fd = (float(fn(up)) - float(fn(dn))) / (2 * h)
+        assert abs(fd - float(g[r, f])) <= 1e-6 * abs(float(g[r, f])) + 1e-12, (r, f, fd, float(g[r, f]))
+
+
+def test_unobserved_elements_and_mixed_targets():
+    sd, x0, cond, t, noise, injected = _small()
+    miss = mask_pattern(SM_N, SM_DIMS)
+    orc = LinkOracle(sd, with_nan(x0, miss), cond, t, noise, SM_H, M, injected, 0.2)
+    loss, grads = orc.loss_and_grads("l2")
+    pred = orc.pred.detach()
+    per = torch.where(torch.arange(pred.shape[1]).view(1, -1) < M,
+                      F.binary_cross_entropy_with_logits(pred, orc.inner.x0, reduction="none"), (pred - orc.inner.x0) ** 2)
+    assert abs(loss - float((per * (~miss).double()).sum() / per.numel())) <= 1e-14 * abs(loss)
+    # a leaked ln 2 would show: row 0 is entirely missing, and the unmasked sum is larger by the masked elements' rho
+    assert float(per.sum() / per.numel()) - loss > float(np.log(2.0)) * 0.5 * M / per.numel()
+    # y strictly inside (0, 1): still F.binary_cross_entropy_with_logits
+    y = torch.rand(SM_N, M, generator=torch.Generator().manual_seed(2), dtype=torch.float64) * 0.98 + 0.01
+    assert torch.allclose(OB.link_loss(pred[:, :M], y), F.binary_cross_entropy_with_logits(pred[:, :M], y, reduction="none"), rtol=1e-13)
+
+
+# ---- the link inside the fp64 chain -----------------------------------------------------------------------------------------------------
+def test_chain64_with_the_link_returns_link_columns_inside_the_unit_interval():
+    m = cpu_model()
+    m.prediction_type = "sample"
+    c = make_case(m)
+    md = m.mutation_dim
+    n = 24
+    cond, x_start, zs = c["cond"][:n], c["x_start"][:n], c["zs"][:, :n]
+    out = chain64(m, cond, x_start, lambda s: zs[len(PLAN) - 1 - s], PLAN, 0.5, "sample", out_fn=link_out(md))
+    plain = chain64(m, cond, x_start, lambda s: zs[len(PLAN) - 1 - s], PLAN, 0.5, "sample")
+    assert bool(((out[:, :md] >= 0) & (out[:, :md] <= 1)).all())
+    assert not bool(((plain[:, :md] >= 0) & (plain[:, :md] <= 1)).all())         # the identity chain leaves the interval
+    x = torch.randn(5, 12, dtype=torch.float64)
+    lc = link_columns(x, 7)
+    assert torch.equal(lc[:, 7:], x[:, 7:]) and torch.equal(lc[:, :7], torch.sigmoid(x[:, :7]))
+
+
+def test_step_tables_do_not_depend_on_the_option():
+    conf = config(SM_H, T=50)
+    conf["model"]["diffusion"].update(prediction_type="sample")
+    plain = BiologyAwareDiffusionModel(config=conf, **SM)
+    conf["model"]["diffusion"].update(mutation_link="logistic")
+    linked = BiologyAwareDiffusionModel(config=conf, **SM)
+    assert linked.mutation_link == "logistic" and plain.mutation_link == "identity"
+    taus = ddim_timesteps(50, 10)
+    for m in (plain, linked):
+        m.sched = dict(sqrt_alphas_cumprod=m.sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod=m.sqrt_one_minus_alphas_cumprod)
+    for eta in (0.0, 0.5):
+        a, b = (ddim_step_table(m.alphas_cumprod, taus, eta, "sample", **m.sched) for m in (plain, linked))
+        assert all(np.array_equal(u, v) for u, v in zip(a, b))
+        tau = a[0]
+        assert np.array_equal(ddim_x0_table(plain.alphas_cumprod, tau, eta, "sample", **plain.sched),
+                              ddim_x0_table(linked.alphas_cumprod, tau, eta, "sample", **linked.sched))
+    a, b = (dpmpp_2m_table(m.alphas_cumprod, taus, "sample", **m.sched) for m in (plain, linked))
+    assert all(np.array_equal(u, v) for u, v in zip(a, b))
+    # P = 0, Q = 1: the unfolded x0 of a sample model is its output, which is what the link is applied to
+    x0c = ddim_x0_table(linked.alphas_cumprod, taus, 0.0, "sample", **linked.sched)
+    assert np.all(x0c[:, 0] == 0.0) and np.all(x0c[:, 1] == 1.0)
+
+
+# ---- the option ------------------------------------------------------------------------------------------------------------------------
+def _conf(link=None, pred=None, T=10):
+    conf = config(SM_H, T=T)
+    if link is not None:
+        conf["model"]["diffusion"]["mutation_link"] = link
+    if pred is not None:
+        conf["model"]["diffusion"]["prediction_type"] = pred
+    return conf
+
+
+def test_option_values_and_the_type_it_needs():
+    assert BiologyAwareDiffusionModel(config=_conf(), **SM).mutation_link == "identity"
+    assert BiologyAwareDiffusionModel(config=_conf("identity", "epsilon"), **SM).mutation_link == "identity"
+    assert BiologyAwareDiffusionModel(config=_conf("logistic", "sample"), **SM).mutation_link == "logistic"
+    for bad in ("sigmoid", "Logistic", None, 1, ""):
+        with pytest.raises(ValueError, match="mutation_link"):
+            OB.check_mutation_link(bad)
+    with pytest.raises(ValueError, match="mutation_link"):
+        BiologyAwareDiffusionModel(config=_conf("logit", "sample"), **SM)
+    for pred in (None, "epsilon", "v_prediction"):
+        with pytest.raises(ValueError, match=r"mutation_link.*prediction_type"):
+            BiologyAwareDiffusionModel(config=_conf("logistic", pred), **SM)
+    # plain attributes: the combination is checked by every call, before the device
+    m = BiologyAwareDiffusionModel(config=_conf("logistic", "sample"), **SM).eval()
+    m.prediction_type = "v_prediction"
+    with pytest.raises(ValueError, match=r"mutation_link.*prediction_type"):
+        m.sample(torch.zeros(2, 3), 2)
+    with pytest.raises(ValueError, match=r"mutation_link.*prediction_type"):
+        m(torch.zeros(2, m.data_dim), torch.zeros(2, 3))
+    m.prediction_type, m.mutation_link = "sample", "probit"
+    with pytest.raises(ValueError, match="mutation_link"):
+        m.predict(torch.zeros(2, m.data_dim), 0, torch.zeros(2, 3))
+
+
+def _linked(T=10):
+    return BiologyAwareDiffusionModel(config=_conf("logistic", "sample", T), **SM).eval()
+
+
+def test_refusals_name_the_option_before_any_device_work():
+    m = _linked()
+    x, cond, t = torch.zeros(4, m.data_dim), torch.zeros(4, 3), torch.zeros(4, dtype=torch.long)
+    with pytest.raises(ValueError, match="mutation_link"):
+        m.p_sample(x, 3, cond)
+    with pytest.raises(ValueError, match="mutation_link"):
+        m.row_sq_error(x, cond, t)
+    with pytest.raises(ValueError, match="mutation_link"):
+        m.variational_bound(x, cond, num_timesteps=4)
+    with pytest.raises(ValueError, match="mutation_link"):
+        m.loss_profile(x, cond, 4)
+    v = object.__new__(BiologicalValidator)
+    v.device = "cpu"
+    with pytest.raises(ValueError, match="mutation_link"):
+        v.membership_audit(m, (x, cond), (x, cond), num_timesteps=4)
+    m.precision = "bf16x3"
+    with pytest.raises(ValueError, match=r"mutation_link.*bf16x3"):
+        m.sample(cond, 4)
+    m.precision = None
+    # the constraint losses and per-patient clipping, from the training call
+    m.train()
+    m.set_constraints([[M + 1, M + 2, M + 9]], pathway_weight=0.5)
+    with pytest.raises(ValueError, match="mutation_link"):
+        m(x, cond)
+    m.set_constraints()
+    m.dp_max_grad_norm = 1.0
+    with pytest.raises(ValueError, match="mutation_link"):
+        m(x, cond)
+    m.dp_max_grad_norm = None
+    # an identity model reaches the device check instead (there is no CPU fallback)
+    plain = BiologyAwareDiffusionModel(config=_conf(None, "sample"), **SM).eval()
+    with pytest.raises(RuntimeError, match="MI355X"):
+        plain.p_sample(x, 3, cond)
+
+
+def _loader(n=8):
+    from osteosarcoma_diffusionmodel_amd.train import OsteosarcomaDataset
+    ds = object.__new__(OsteosarcomaDataset)
+    ds.data, ds.conditions, ds.survival_days = torch.randn(n, sum(SM_DIMS[:3])), torch.zeros(n, 3), torch.zeros(n)
+    return torch.utils.data.DataLoader(ds, batch_size=4, shuffle=False, num_workers=0)
+
+
+def test_trainer_refusals_come_before_any_device_work(tmp_path, monkeypatch):
+    moved = []
+    monkeypatch.setattr(BiologyAwareDiffusionModel, "to", lambda self, *a, **k: moved.append(a) or (_ for _ in ()).throw(AssertionError("device")))
+    loader = _loader()
+
+    def build(model=None, **training):
+        conf = _conf("logistic", "sample")
+        conf["training"] = dict({"learning_rate": 1e-4, "weight_decay": 1e-5, "patience": 10, "min_delta": 1e-4,
+                                 "augmentation": {"mixup_alpha": 0.0}, "save_dir": str(tmp_path), "num_epochs": 1, "save_frequency": 10,
+                                 "val_split": 0.2, "random_seed": 42, "batch_size": 4}, **training)
+        return Trainer(model if model is not None else BiologyAwareDiffusionModel(config=conf, **SM), loader, loader, conf, device="cuda")
+
+    with pytest.raises(ValueError, match=r"mutation_link.*validation_metric"):
+        build(validation_metric="bound")
+    with pytest.raises(ValueError, match=r"mutation_link.*training.dp"):
+        build(dp={"max_grad_norm": 1.0, "noise_multiplier": 1.0})
+    cons = _linked().train()
+    cons.set_constraints([[M + 1, M + 2, M + 9]], pathway_weight=0.5)
+    with pytest.raises(ValueError, match=r"mutation_link.*constraint"):
+        build(model=cons)
+    assert not moved
+    # EMA, the mask and mixup need nothing: the constructor reaches the device move
+    with pytest.raises(AssertionError, match="device"):
+        build(ema_decay=0.999, missing_values="mask")
+
+
+# ---- the checkpoint --------------------------------------------------------------------------------------------------------------------
+def _ckpt(link, pred="sample"):
+    return {"config": _conf(link, pred)}
+
+
+def test_checkpoint_link_against_config_link():
+    assert checkpoint_mutation_link(_ckpt("logistic"), _conf()) == "logistic"
+    assert checkpoint_mutation_link(_ckpt("logistic"), {"model": {}}) == "logistic"
+    assert checkpoint_mutation_link(_ckpt(None), _conf()) is None
+    assert checkpoint_mutation_link({}, _conf()) is None
+    assert checkpoint_mutation_link(_ckpt("logistic"), _conf("logistic", "sample")) is None
+    assert checkpoint_mutation_link(_ckpt(None), _conf("identity")) is None
+    for saved, asked in (("logistic", "identity"), (None, "logistic"), ("identity", "logistic")):
+        with pytest.raises(ValueError, match="mutation_link"):
+            checkpoint_mutation_link(_ckpt(saved), _conf(asked, "sample"))
+    with pytest.raises(ValueError):
+        checkpoint_mutation_link(_ckpt("probit"), _conf())
+
+
+def test_load_trained_model_adopts_or_rejects_the_checkpoints_link(tmp_path):
+    conf = _conf("logistic", "sample")
+    torch.manual_seed(0)
+    m = BiologyAwareDiffusionModel(config=conf, **SM)
+    path = tmp_path / "ckpt.pt"
+    torch.save({"epoch": 0, "model_state_dict": m.state_dict(), "val_loss": 0.0, "config": conf}, path)
+    saved = torch.load(path, map_location="cpu", weights_only=True)
+    assert saved["config"]["model"]["diffusion"]["mutation_link"] == "logistic"
+    assert set(saved["model_state_dict"]) == set(BiologyAwareDiffusionModel(config=_conf(), **SM).state_dict())       # no new checkpoint key
+    for fname, width in (("mutation_matrix_aligned.csv", SM["mutation_dim"]), ("expression_matrix_aligned.csv", SM["expression_dim"]),
+                         ("pathway_scores.csv", SM["pathway_dim"])):
+        pd.DataFrame(np.zeros((1, width)), index=["p0"]).to_csv(tmp_path / fname)
+    load_conf = _conf()
+    load_conf["data"] = {"processed_dir": str(tmp_path)}
+    got = load_trained_model(path, load_conf, "cpu")
+    assert got.mutation_link == "logistic" and got.prediction_type == "sample" and not got.training
+    assert "mutation_link" not in load_conf["model"]["diffusion"]              # the caller's config is left alone
+    load_conf["model"]["diffusion"]["mutation_link"] = "logistic"             # names the link, leaves the type to the checkpoint
+    assert load_trained_model(path, load_conf, "cpu").mutation_link == "logistic"
+    load_conf["model"]["diffusion"]["mutation_link"] = "identity"
+    with pytest.raises(ValueError, match="mutation_link"):
+        load_trained_model(path, load_conf, "cpu")
+    # an identity checkpoint against a config that asks for the link
+    plain_conf = _conf(None, "sample")
+    torch.save({"epoch": 0, "model_state_dict": m.state_dict(), "val_loss": 0.0, "config": plain_conf}, path)
+    load_conf["model"]["diffusion"].update(mutation_link="logistic", prediction_type="sample")
+    with pytest.raises(ValueError, match="mutation_link"):
+        load_trained_model(path, load_conf, "cpu")
+    del load_conf["model"]["diffusion"]["mutation_link"]
+    assert load_trained_model(path, load_conf, "cpu").mutation_link == "identity"
+
+
+# ---- the ABI ---------------------------------------------------------------------------------------------------------------------------
+def test_abi_declares_the_output_link():
+    assert "osd_set_output_link" in L.exported_symbols()
+    text = (ROOT / "include" / "osdiff.h").read_text()
+    assert re.search(r"int\s+osd_set_output_link\s*\(\s*osd_handle\s*\*\s*h\s*,\s*int\s+n_logistic\s*\)\s*;", text)
+    assert re.search(r"#define\s+OSD_TP_LINK\s+\(1 << 15\)", text) and L.OSD_TP_LINK == 1 << 15
+    assert '"output_link"' in text
+    fn = L.lib().osd_set_output_link                      # exported by the library, with ctypes argument types
+    assert fn.restype is not None and len(fn.argtypes) == 2
+    assert fn(None, 1) == L.OSD_EINVAL and L.last_error()
+    assert OB.MUTATION_LINKS == ("identity", "logistic")
