@@ -105,14 +105,6 @@ int device_alloc(void** p, size_t bytes) {
   return OSD_ENOMEM;
 }
 
-int ensure_arena(Slot* s, int64_t floats) {
-  if (s->arena_floats >= floats) return OSD_OK;
-  if (s->arena) { hipError_t e = hipFree(s->arena); (void)e; s->arena = nullptr; s->arena_floats = 0; }
-  OSD_TRY(device_alloc((void**)&s->arena, (size_t)floats * 4));
-  s->arena_floats = floats;
-  return OSD_OK;
-}
-
 // Carve forward activations for n rows out of `base`; returns floats used.
 int64_t carve_fwd(const Arch& a, float* base, int64_t n, bool train, FwdWs* ws) {
   int64_t off = 0;
@@ -297,27 +289,22 @@ GemmArgs output_proj_args(osd_handle* h, const FwdWs& ws, int64_t n, bool padded
   return g;
 }
 
-// The null condition of classifier-free guidance, host -> device slot (handle.h: d_null_cond) on the handle's stream.  The caller has
+// The null condition of classifier-free guidance, host -> device slot (handle.h: null_cond) on the handle's stream.  The caller has
 // checked that the vector is there and finite.
 int upload_null_cond(osd_handle* h, int slot, const float* null_cond_host, const float** dev) {
   const int cd = h->arch.cond_dim;
   const size_t stride = (size_t)up64(cd);
   OSD_HIP(hipSetDevice(h->cfg.device));
-  if (!h->null_host) {
-    h->null_host = static_cast<float*>(malloc(2 * stride * 4));
-    if (!h->null_host) { set_error("out of host memory"); return OSD_ENOMEM; }
-  }
-  if (!h->null_ev) OSD_HIP(hipEventCreateWithFlags(&h->null_ev, hipEventDisableTiming));
-  if (!h->d_null_cond) OSD_HIP(hipMalloc((void**)&h->d_null_cond, 2 * stride * 4));
-  *dev = h->d_null_cond + slot * stride;
+  OSD_TRY(h->null_cond.ensure(2 * stride));
+  *dev = h->null_cond.dev() + slot * stride;
   // the vector rarely changes between calls (a training run, a generation run): the slot keeps what it holds and a call with the
   // same bits uploads nothing -- no host wait on the previous step, no copy on the hot stream
-  if (h->null_valid[slot] && !memcmp(h->null_host + slot * stride, null_cond_host, (size_t)cd * 4)) return OSD_OK;
-  OSD_HIP(hipEventSynchronize(h->null_ev));          // the previous upload has read the staging
+  if (h->null_valid[slot] && !memcmp(h->null_cond.host() + slot * stride, null_cond_host, (size_t)cd * 4)) return OSD_OK;
+  float* host = nullptr;
+  OSD_TRY(h->null_cond.staging(2 * stride, &host));
   h->null_valid[slot] = false;
-  memcpy(h->null_host + slot * stride, null_cond_host, (size_t)cd * 4);
-  OSD_HIP(hipMemcpyAsync(h->d_null_cond + slot * stride, h->null_host + slot * stride, (size_t)cd * 4, hipMemcpyHostToDevice, h->stream));
-  OSD_HIP(hipEventRecord(h->null_ev, h->stream));
+  memcpy(host + slot * stride, null_cond_host, (size_t)cd * 4);
+  OSD_TRY(h->null_cond.send(slot * stride, (size_t)cd, h->stream));
   h->null_valid[slot] = true;
   return OSD_OK;
 }
@@ -356,12 +343,7 @@ int check_row_offset(int64_t row_offset, int64_t n) {
 // Caller-supplied per-row timestep indices, clamped into [0, T) in a handle-owned buffer (see k_clamp_int).
 int sanitize_t(osd_handle* h, hipStream_t s, const int32_t* t_index, int64_t n, const int** out) {
   if (!t_index) { *out = nullptr; return OSD_OK; }
-  if (h->t_san_cap < n) {
-    if (h->t_san) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(h->t_san)); h->t_san = nullptr; h->t_san_cap = 0; }
-    const int64_t cap = (n + 1023) / 1024 * 1024;
-    OSD_TRY(device_alloc((void**)&h->t_san, (size_t)cap * 4));
-    h->t_san_cap = cap;
-  }
+  OSD_TRY(h->t_san.reserve((n + 1023) / 1024 * 1024, s));      // 1024-row granules
   OSD_HIP(launch_clamp_int(s, t_index, n, 0, h->arch.T - 1, h->t_san));
   *out = h->t_san;
   return OSD_OK;
@@ -371,10 +353,8 @@ int sanitize_t(osd_handle* h, hipStream_t s, const int32_t* t_index, int64_t n, 
 int release_graph(Slot& sl) {
   if (!sl.exec && !sl.graph) return OSD_OK;
   OSD_HIP(hipStreamSynchronize(sl.stream));
-  if (sl.exec) OSD_HIP(hipGraphExecDestroy(sl.exec));
-  if (sl.graph) OSD_HIP(hipGraphDestroy(sl.graph));
-  sl.exec = nullptr;
-  sl.graph = nullptr;
+  sl.exec.reset();
+  sl.graph.reset();
   return OSD_OK;
 }
 
@@ -446,6 +426,12 @@ static const Counter COUNTERS[] = {
 
 }  // namespace osd
 
+osd_handle::~osd_handle() {
+  osd::split_free(this);
+  osd::dp_free(this);
+  osd::wgrad_group_free(this);
+}
+
 using namespace osd;
 
 extern "C" {
@@ -471,28 +457,28 @@ int64_t osd_param_numel(const osd_config* cfg, int i) {
 static int create_device_state(osd_handle* h) {
   const Arch& a = h->arch;
   const int T = a.T;
-  OSD_HIP(hipMalloc((void**)&h->d_sqrt_ac, (size_t)T * 4));
-  OSD_HIP(hipMalloc((void**)&h->d_sqrt_1m, (size_t)T * 4));
-  OSD_HIP(hipMalloc((void**)&h->d_coef, (size_t)T * 4 * 4));
-  OSD_HIP(hipMalloc((void**)&h->d_pq, (size_t)T * 2 * 4 * 2));      // (P, Q) [T][2], then osd_convert_prediction's (U, V) [T][2]
-  const size_t t_rows = (size_t)(T + 31) / 32 * 32;     // zero rows up to whole K steps of the grouped weight-gradient kernel (time_proj.weight)
-  OSD_HIP(hipMalloc((void**)&h->d_time_emb, t_rows * a.time_dim * 4));
-  OSD_HIP(hipMemset(h->d_time_emb, 0, t_rows * a.time_dim * 4));
-  OSD_HIP(hipMalloc((void**)&h->d_temb, (size_t)T * a.H0 * 4));
+  OSD_TRY(h->d_sqrt_ac.reserve(T));
+  OSD_TRY(h->d_sqrt_1m.reserve(T));
+  OSD_TRY(h->d_coef.reserve((int64_t)T * 4));
+  OSD_TRY(h->d_pq.reserve((int64_t)T * 2 * 2));      // (P, Q) [T][2], then osd_convert_prediction's (U, V) [T][2]
+  const int64_t t_rows = ((int64_t)T + 31) / 32 * 32;     // zero rows up to whole K steps of the grouped weight-gradient kernel (time_proj.weight)
+  OSD_TRY(h->d_time_emb.reserve(t_rows * a.time_dim));
+  OSD_HIP(hipMemset(h->d_time_emb, 0, (size_t)t_rows * a.time_dim * 4));
+  OSD_TRY(h->d_temb.reserve((int64_t)T * a.H0));
   h->w_in_ld = (a.D + BK - 1) / BK * BK;
-  OSD_HIP(hipMalloc((void**)&h->w_in_packed, (size_t)a.H0 * h->w_in_ld * 4));
+  OSD_TRY(h->w_in_packed.reserve((int64_t)a.H0 * h->w_in_ld));
   OSD_HIP(hipMemset(h->w_in_packed, 0, (size_t)a.H0 * h->w_in_ld * 4));
   h->Dp = (a.D + 3) / 4 * 4;
   if (h->Dp != a.D) {
-    const size_t hl = (size_t)a.block_out[a.n_blocks - 1];
-    OSD_HIP(hipMalloc((void**)&h->w_out_packed, (size_t)h->Dp * hl * 4));
+    const int64_t hl = a.block_out[a.n_blocks - 1];
+    OSD_TRY(h->w_out_packed.reserve(h->Dp * hl));
     OSD_HIP(hipMemset(h->w_out_packed, 0, (size_t)h->Dp * hl * 4));
-    OSD_HIP(hipMalloc((void**)&h->b_out_packed, (size_t)h->Dp * 4));
+    OSD_TRY(h->b_out_packed.reserve(h->Dp));
     OSD_HIP(hipMemset(h->b_out_packed, 0, (size_t)h->Dp * 4));
   }
-  OSD_HIP(hipMalloc((void**)&h->main.t_dev, 64));
-  OSD_HIP(hipMalloc((void**)&h->loss_dev, 64));
-  OSD_HIP(hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
+  OSD_TRY(h->main.t_dev.reserve(16));
+  OSD_TRY(h->loss_dev.reserve(16));
+  OSD_HIP(hipEventCreateWithFlags(h->fork_ev.put(), hipEventDisableTiming));
   return OSD_OK;
 }
 
@@ -511,7 +497,7 @@ int osd_create(const osd_config* cfg, osd_handle** out) {
   h->cfg = *cfg;
   h->arch = a;
   const int rc = create_device_state(h);
-  if (rc != OSD_OK) {                 // nothing of a half-built handle survives (osd_destroy frees what was allocated)
+  if (rc != OSD_OK) {                 // nothing of a half-built handle survives (its members release what was allocated)
     osd_destroy(h);
     (void)hipGetLastError();          // the failed call's sticky error must not surface in a later launch check
     return rc;
@@ -520,55 +506,10 @@ int osd_create(const osd_config* cfg, osd_handle** out) {
   return OSD_OK;
 }
 
-static void free_slot(Slot& s, bool own_stream) {
-  hipError_t e;
-  if (s.exec) { e = hipGraphExecDestroy(s.exec); }
-  if (s.graph) { e = hipGraphDestroy(s.graph); }
-  if (s.arena) { e = hipFree(s.arena); }
-  if (s.t_dev) { e = hipFree(s.t_dev); }
-  if (s.done) { e = hipEventDestroy(s.done); }
-  if (own_stream && s.stream) { e = hipStreamDestroy(s.stream); }
-  (void)e;
-  s = Slot();
-}
-
 int osd_destroy(osd_handle* h) {
   if (!h) return OSD_OK;
   hipError_t e = hipSetDevice(h->cfg.device);
   e = hipDeviceSynchronize();
-  for (auto& s : h->slots) free_slot(s, true);
-  free_slot(h->main, false);
-  float* bufs[] = {h->w_in_packed, h->w_out_packed, h->b_out_packed, h->chain_xpad, h->d_sqrt_ac, h->d_sqrt_1m, h->d_coef, h->d_pq, h->d_time_emb, h->d_temb, h->train_arena, h->loss_dev,
-                   h->plan_temb, h->plan_coef};
-  for (float* p : bufs) if (p) e = hipFree(p);
-  if (h->plan_t) e = hipFree(h->plan_t);
-  if (h->plan_ev) e = hipEventDestroy(h->plan_ev);
-  free(h->plan_host);
-  if (h->d_null_cond) e = hipFree(h->d_null_cond);
-  if (h->null_ev) e = hipEventDestroy(h->null_ev);
-  free(h->null_host);
-  if (h->known_level) e = hipFree(h->known_level);
-  if (h->known_ev) e = hipEventDestroy(h->known_ev);
-  free(h->known_level_host);
-  if (h->clip_dev) e = hipFree(h->clip_dev);
-  if (h->clip_ev) e = hipEventDestroy(h->clip_ev);
-  free(h->clip_host);
-  if (h->hist_dev) e = hipFree(h->hist_dev);
-  if (h->hist_ev) e = hipEventDestroy(h->hist_ev);
-  free(h->hist_host);
-  if (h->normsq_dev) e = hipFree(h->normsq_dev);
-  if (h->parts_dev) e = hipFree(h->parts_dev);
-  if (h->loss_tw) e = hipFree(h->loss_tw);
-  dp_free(h);
-  if (h->t_san) e = hipFree(h->t_san);
-  if (h->bound_ts) e = hipFree(h->bound_ts);
-  for (hipEvent_t ev : h->ev_pool) e = hipEventDestroy(ev);
-  if (h->wgrad_stream) e = hipStreamDestroy(h->wgrad_stream);
-  cons_free_plan(&h->cons);
-  chain_free(h);
-  split_free(h);
-  wgrad_group_free(h);
-  if (h->fork_ev) e = hipEventDestroy(h->fork_ev);
   (void)e;
   delete h;
   return OSD_OK;
@@ -744,7 +685,7 @@ static int forward_request(osd_handle* h, const ForwardRequest& r) {
   const int64_t nt = guided ? 2 * n : n;        // rows of the trunk
   FwdWs ws;
   const int64_t need = up64(carve_fwd(a, nullptr, nt, false, &ws));
-  OSD_TRY(ensure_arena(&h->main, need + (guided ? (n + 1) * (int64_t)a.cond_dim : 0)));
+  OSD_TRY(h->main.arena.reserve(need + (guided ? (n + 1) * (int64_t)a.cond_dim : 0)));
   carve_fwd(a, h->main.arena, nt, false, &ws);
   if (guided) OSD_TRY(guided_cond(h, s, gd, r.cond, n, h->main.arena + need, ws));
   else OSD_TRY(run_cond(h, s, r.cond, n, ws));
@@ -883,7 +824,7 @@ int osd_p_sample_step(osd_handle* h, const float* x_t, int32_t t, const float* c
   h->last_precision = 0;
   FwdWs ws;
   const int64_t need = carve_fwd(a, nullptr, n, false, &ws);
-  OSD_TRY(ensure_arena(&h->main, need));
+  OSD_TRY(h->main.arena.reserve(need));
   carve_fwd(a, h->main.arena, n, false, &ws);
   hipStream_t s = h->stream;
   OSD_TRY(run_cond(h, s, cond, n, ws));      // recomputed every step, as models/diffusion.py:395 does
@@ -952,7 +893,7 @@ static int chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r
   const int64_t known_floats = kn && padded ? m * (int64_t)ldx : 0;
   // a multistep chain keeps the previous step's clipped x0 beside the state: rows of ldx floats like the state's, zero at the start
   const int64_t hist_floats = ms ? m * (int64_t)ldx : 0;
-  OSD_TRY(ensure_arena(&sl, need_pad + x_floats + slab_floats + up64(stage_floats) + (ms ? up64(known_floats) : known_floats) + hist_floats));
+  OSD_TRY(sl.arena.reserve(need_pad + x_floats + slab_floats + up64(stage_floats) + (ms ? up64(known_floats) : known_floats) + hist_floats));
   carve_fwd(a, sl.arena, mt, false, &ws);
   float* x = padded ? sl.arena + need_pad : job.x_out;       // else the chain state lives in the output rows
   float* in_slabs = in_slices ? sl.arena + need_pad + x_floats : nullptr;
@@ -1050,10 +991,10 @@ static int sample_plan(osd_handle* h, const ChainJob& job) {
   const int n_slots = (int)std::min<int64_t>(h->n_streams, n_chunks);
   while ((int)h->slots.size() < n_slots) {
     Slot sl;
-    OSD_HIP(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-    OSD_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    OSD_HIP(hipMalloc((void**)&sl.t_dev, 64));
-    h->slots.push_back(sl);
+    OSD_HIP(hipStreamCreateWithFlags(sl.stream.put(), hipStreamNonBlocking));
+    OSD_HIP(hipEventCreateWithFlags(sl.done.put(), hipEventDisableTiming));
+    OSD_TRY(sl.t_dev.reserve(16));
+    h->slots.push_back(std::move(sl));
   }
   // fork: slot streams wait for everything already queued on the caller's stream
   OSD_HIP(hipEventRecord(h->fork_ev, h->stream));
@@ -1079,30 +1020,21 @@ static int sample_plan(osd_handle* h, const ChainJob& job) {
   return OSD_OK;
 }
 
-// The tables of osd_sample_chain_steps' plan, on the handle's stream: coefficients and timesteps uploaded from the handle's host
+// The tables of osd_sample_chain_steps' plan, on the handle's stream: coefficients and timesteps uploaded through the handle's
 // staging, temb rows gathered from d_temb (which ensure_packed has just brought up to date with the parameters).  An earlier call's
 // chunks on the slot streams have joined h->stream, so nothing still reads the tables this overwrites.
-static int upload_plan(osd_handle* h, const int32_t* timesteps, const float* step_coef, int S) {
+static int upload_plan(osd_handle* h, const int32_t* timesteps, const float* step_coef, int S, StepPlan* out) {
   const Arch& a = h->arch;
   hipStream_t s = h->stream;
-  if (!h->plan_host) {
-    h->plan_host = malloc((size_t)a.T * 5 * 4);                    // [T][4] coefficients, then [T] timesteps
-    if (!h->plan_host) { set_error("out of host memory"); return OSD_ENOMEM; }
-    OSD_HIP(hipEventCreateWithFlags(&h->plan_ev, hipEventDisableTiming));
-    OSD_HIP(hipMalloc((void**)&h->plan_temb, (size_t)a.T * a.H0 * 4));
-    OSD_HIP(hipMalloc((void**)&h->plan_coef, (size_t)a.T * 4 * 4));
-    OSD_HIP(hipMalloc((void**)&h->plan_t, (size_t)a.T * 4));
-  }
-  OSD_HIP(hipEventSynchronize(h->plan_ev));          // the previous call's upload has read the staging
-  float* hc = static_cast<float*>(h->plan_host);
-  int32_t* ht = reinterpret_cast<int32_t*>(hc + (size_t)a.T * 4);
+  OSD_TRY(h->plan_temb.reserve((int64_t)a.T * a.H0));
+  float* hc = nullptr;
+  OSD_TRY(h->plan_tab.staging((size_t)a.T * 5, &hc));          // [S][4] coefficients, then [S] timesteps
   if (step_coef) memcpy(hc, step_coef, (size_t)S * 4 * 4);
   else memset(hc, 0, (size_t)S * 4 * 4);           // a multistep plan: no step draws, and its launch reads (P, Q, G, F) and H instead
-  memcpy(ht, timesteps, (size_t)S * 4);
-  OSD_HIP(hipMemcpyAsync(h->plan_coef, hc, (size_t)S * 4 * 4, hipMemcpyHostToDevice, s));
-  OSD_HIP(hipMemcpyAsync(h->plan_t, ht, (size_t)S * 4, hipMemcpyHostToDevice, s));
-  OSD_HIP(hipEventRecord(h->plan_ev, s));
-  OSD_HIP(launch_gather_rows(s, h->d_temb, a.H0, h->plan_t, S, h->plan_temb));
+  memcpy(hc + (size_t)S * 4, timesteps, (size_t)S * 4);
+  OSD_TRY(h->plan_tab.send(0, (size_t)S * 5, s));
+  OSD_HIP(launch_gather_rows(s, h->d_temb, a.H0, reinterpret_cast<const int*>(h->plan_tab.dev() + (size_t)S * 4), S, h->plan_temb));
+  *out = StepPlan{S, h->plan_temb, h->plan_tab.dev()};
   return OSD_OK;
 }
 
@@ -1122,24 +1054,16 @@ static int check_plan(const Arch& a, const int32_t* timesteps, const float* step
 // The level table of a chain around known values, host -> handle-owned device table on the handle's stream.  level_host: the plan's
 // [S][2], or null for the DDPM identity plan, whose rows are the schedule's own: (sqrt_ac[s - 1], sqrt_1m_ac[s - 1]), (1, 0) at s = 0.
 static int upload_known_level(osd_handle* h, const float* level_host, int S, const float** dev) {
-  const Arch& a = h->arch;
-  if (!h->known_level_host) {
-    h->known_level_host = static_cast<float*>(malloc((size_t)a.T * 2 * 4));
-    if (!h->known_level_host) { set_error("out of host memory"); return OSD_ENOMEM; }
-  }
-  if (!h->known_ev) OSD_HIP(hipEventCreateWithFlags(&h->known_ev, hipEventDisableTiming));
-  if (!h->known_level) OSD_HIP(hipMalloc((void**)&h->known_level, (size_t)a.T * 2 * 4));
-  OSD_HIP(hipEventSynchronize(h->known_ev));         // the previous call's upload has read the staging
-  float* hl = h->known_level_host;
+  float* hl = nullptr;
+  OSD_TRY(h->known_level.staging((size_t)h->arch.T * 2, &hl));
   if (level_host) {
     memcpy(hl, level_host, (size_t)S * 2 * 4);
   } else {
     hl[0] = 1.f; hl[1] = 0.f;
     for (int s = 1; s < S; ++s) { hl[2 * s] = h->sched_sqrt_ac[s - 1]; hl[2 * s + 1] = h->sched_sqrt_1m[s - 1]; }
   }
-  OSD_HIP(hipMemcpyAsync(h->known_level, hl, (size_t)S * 2 * 4, hipMemcpyHostToDevice, h->stream));
-  OSD_HIP(hipEventRecord(h->known_ev, h->stream));
-  *dev = h->known_level;
+  OSD_TRY(h->known_level.send(0, (size_t)S * 2, h->stream));
+  *dev = h->known_level.dev();
   return OSD_OK;
 }
 
@@ -1149,40 +1073,26 @@ static int upload_known_level(osd_handle* h, const float* level_host, int S, con
 static int upload_clip(osd_handle* h, const float* x0_coef_host, int S, const float* lo_host, const float* hi_host, Clip* out) {
   const Arch& a = h->arch;
   const size_t coef_floats = (size_t)up64((int64_t)a.T * 4), floats = coef_floats + 2 * (size_t)h->Dp;
-  if (!h->clip_host) {
-    h->clip_host = static_cast<float*>(malloc(floats * 4));
-    if (!h->clip_host) { set_error("out of host memory"); return OSD_ENOMEM; }
-  }
-  if (!h->clip_ev) OSD_HIP(hipEventCreateWithFlags(&h->clip_ev, hipEventDisableTiming));
-  if (!h->clip_dev) OSD_HIP(hipMalloc((void**)&h->clip_dev, floats * 4));
-  OSD_HIP(hipEventSynchronize(h->clip_ev));          // the previous call's upload has read the staging
-  float* hc = h->clip_host;
+  float* hc = nullptr;
+  OSD_TRY(h->clip_tab.staging(floats, &hc));
   memcpy(hc, x0_coef_host ? x0_coef_host : h->sched_x0_coef.data(), (size_t)S * 4 * 4);
   float* lo = hc + coef_floats;
   float* hi = lo + h->Dp;
   if (lo_host) memcpy(lo, lo_host, (size_t)a.D * 4);
   if (hi_host) memcpy(hi, hi_host, (size_t)a.D * 4);
   for (int f = lo_host ? a.D : 0; f < h->Dp; ++f) { lo[f] = -INFINITY; hi[f] = INFINITY; }      // no bounds (a multistep chain's may be absent): all free
-  OSD_HIP(hipMemcpyAsync(h->clip_dev, hc, floats * 4, hipMemcpyHostToDevice, h->stream));
-  OSD_HIP(hipEventRecord(h->clip_ev, h->stream));
-  *out = Clip{h->clip_dev + coef_floats, h->Dp, h->clip_dev, 0};
+  OSD_TRY(h->clip_tab.send(0, floats, h->stream));
+  *out = Clip{h->clip_tab.dev() + coef_floats, h->Dp, h->clip_tab.dev(), 0};
   return OSD_OK;
 }
 
 // The history coefficients of a multistep chain, host -> handle-owned device table on the handle's stream.
 static int upload_hist_coef(osd_handle* h, const float* hist_coef_host, int S, Multistep* out) {
-  const Arch& a = h->arch;
-  if (!h->hist_host) {
-    h->hist_host = static_cast<float*>(malloc((size_t)a.T * 4));
-    if (!h->hist_host) { set_error("out of host memory"); return OSD_ENOMEM; }
-  }
-  if (!h->hist_ev) OSD_HIP(hipEventCreateWithFlags(&h->hist_ev, hipEventDisableTiming));
-  if (!h->hist_dev) OSD_HIP(hipMalloc((void**)&h->hist_dev, (size_t)a.T * 4));
-  OSD_HIP(hipEventSynchronize(h->hist_ev));          // the previous call's upload has read the staging
-  memcpy(h->hist_host, hist_coef_host, (size_t)S * 4);
-  OSD_HIP(hipMemcpyAsync(h->hist_dev, h->hist_host, (size_t)S * 4, hipMemcpyHostToDevice, h->stream));
-  OSD_HIP(hipEventRecord(h->hist_ev, h->stream));
-  *out = Multistep{h->hist_dev};
+  float* hh = nullptr;
+  OSD_TRY(h->hist_coef.staging((size_t)h->arch.T, &hh));
+  memcpy(hh, hist_coef_host, (size_t)S * 4);
+  OSD_TRY(h->hist_coef.send(0, (size_t)S, h->stream));
+  *out = Multistep{h->hist_coef.dev()};
   return OSD_OK;
 }
 
@@ -1283,10 +1193,7 @@ static int sample_request(osd_handle* h, const SampleRequest& r) {
   if (r.clipped) OSD_TRY(upload_clip(h, plan ? r.x0_coef : nullptr, plan ? r.n_steps : a.T, r.lo, r.hi, &job.clip));
   job.clip.n_link = h->n_link;
   if (r.multistep) OSD_TRY(upload_hist_coef(h, r.hist_coef, r.n_steps, &job.multistep));
-  if (plan) {
-    OSD_TRY(upload_plan(h, r.timesteps, r.step_coef, r.n_steps));
-    job.plan = StepPlan{r.n_steps, h->plan_temb, h->plan_coef};
-  }
+  if (plan) OSD_TRY(upload_plan(h, r.timesteps, r.step_coef, r.n_steps, &job.plan));
   return sample_plan(h, job);
 }
 
@@ -1382,7 +1289,7 @@ int osd_profile_step(osd_handle* h, const float* cond, int64_t n, int reps, floa
   FwdWs ws;
   const int64_t fwd = carve_fwd(a, nullptr, n, false, &ws);
   const int64_t need = fwd + up64(n * a.D);
-  OSD_TRY(ensure_arena(&h->main, need));
+  OSD_TRY(h->main.arena.reserve(need));
   carve_fwd(a, h->main.arena, n, false, &ws);
   float* x = h->main.arena + fwd;
   OSD_TRY(run_cond(h, s, cond, n, ws));

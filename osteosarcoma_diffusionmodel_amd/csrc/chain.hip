@@ -117,22 +117,10 @@ int chain_pick_engine(osd_handle* h, int64_t n, int flags) {
   return 0;
 }
 
-int chain_ensure_buf(float** p, int64_t* cap, int64_t floats, hipStream_t s) {
-  if (*cap >= floats) return OSD_OK;
-  if (*p) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(*p)); *p = nullptr; *cap = 0; }
-  OSD_TRY(device_alloc((void**)p, (size_t)floats * 4));
-  *cap = floats;
-  return OSD_OK;
-}
-
 // sync words: [status, queue, pad x2 | cu arrivals x2048 | progress x n_tiles], zeroed before every chain
 int chain_ensure_sync(osd_handle* h, int64_t n_tiles, hipStream_t s) {
   const int64_t words = 4 + 2048 + ((n_tiles + 3) / 4) * 4;
-  if (h->chain_sync_words < words) {
-    if (h->chain_sync) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(h->chain_sync)); h->chain_sync = nullptr; h->chain_sync_words = 0; }
-    OSD_TRY(device_alloc((void**)&h->chain_sync, (size_t)words * 4));
-    h->chain_sync_words = words;
-  }
+  OSD_TRY(h->chain_sync.reserve(words, s));
   OSD_HIP(hipMemsetAsync(h->chain_sync, 0, (size_t)words * 4, s));
   return OSD_OK;
 }
@@ -162,7 +150,7 @@ static int chain_wait_status(osd_handle* h, unsigned* st) {
   hipError_t e = poll(budget_ms);
   if (e == hipErrorNotReady) {
     (void)hipGetLastError();
-    if (!h->abort_stream) OSD_HIP(hipStreamCreateWithFlags(&h->abort_stream, hipStreamNonBlocking));
+    if (!h->abort_stream) OSD_HIP(hipStreamCreateWithFlags(h->abort_stream.put(), hipStreamNonBlocking));
     static const unsigned abort_word = CHAIN_ABORT;
     OSD_HIP(hipMemcpyAsync(h->chain_sync, &abort_word, 4, hipMemcpyHostToDevice, h->abort_stream));
     OSD_HIP(hipStreamSynchronize(h->abort_stream));
@@ -207,7 +195,7 @@ int chain_finish(osd_handle* h, int* gave_up) {
 int chain_hoist_cond(osd_handle* h, hipStream_t s, const float* cond, int64_t n, int64_t rows_pad, FwdWs* cw) {
   const int H0 = h->arch.H0;
   const int64_t c_off_ce2 = up64(n * 64), c_off_cp = c_off_ce2 + up64(n * 64);
-  OSD_TRY(chain_ensure_buf(&h->chain_cond, &h->chain_cond_floats, c_off_cp + up64(rows_pad * H0), s));
+  OSD_TRY(h->chain_cond.reserve(c_off_cp + up64(rows_pad * H0), s));
   cw->ce1 = h->chain_cond; cw->ce2 = h->chain_cond + c_off_ce2; cw->cproj = h->chain_cond + c_off_cp;
   OSD_TRY(run_cond(h, s, cond, n, *cw));
   if (rows_pad > n) OSD_HIP(hipMemsetAsync(cw->cproj + n * H0, 0, (size_t)(rows_pad - n) * H0 * 4, s));
@@ -218,7 +206,7 @@ int chain_state(osd_handle* h, hipStream_t s, const ChainJob& job, int state_col
   const int64_t n = job.n;
   *xs = job.x_out;
   if (state_cols != job.D) {
-    OSD_TRY(chain_ensure_buf(&h->chain_xpad, &h->chain_xpad_floats, n * (int64_t)state_cols, s));
+    OSD_TRY(h->chain_xpad.reserve(n * (int64_t)state_cols, s));
     *xs = h->chain_xpad;
     OSD_HIP(hipMemsetAsync(*xs, 0, (size_t)n * state_cols * 4, s));
   }
@@ -234,20 +222,13 @@ int chain_args_ring(osd_handle* h, hipStream_t s, int S, size_t bytes) {
   OSD_HIP(hipStreamSynchronize(s));        // the host copies are about to be rewritten: earlier uploads must have been consumed
   const int seg = chain_segment_steps(h, S);
   const size_t need = (size_t)((S + seg - 1) / seg) * bytes;
-  if (h->chain_args_bytes >= need) return OSD_OK;
-  if (h->chain_args_dev) { OSD_HIP(hipFree(h->chain_args_dev)); h->chain_args_dev = nullptr; }
-  free(h->chain_args_host);
-  h->chain_args_bytes = 0;
-  h->chain_args_host = malloc(need);
-  if (!h->chain_args_host) { set_error("out of host memory"); return OSD_ENOMEM; }
-  OSD_TRY(device_alloc(&h->chain_args_dev, need));
-  h->chain_args_bytes = need;
-  return OSD_OK;
+  if (h->chain_args_host.size() < need) h->chain_args_host.resize(need);
+  return h->chain_args_dev.reserve((int64_t)need);
 }
 
 int chain_args_upload(osd_handle* h, hipStream_t s, int l, const void* args, size_t bytes, const void** dev) {
-  char* const host = static_cast<char*>(h->chain_args_host) + (size_t)l * bytes;
-  *dev = static_cast<char*>(h->chain_args_dev) + (size_t)l * bytes;
+  char* const host = h->chain_args_host.data() + (size_t)l * bytes;
+  *dev = h->chain_args_dev + (size_t)l * bytes;
   memcpy(host, args, bytes);
   OSD_HIP(hipMemcpyAsync(const_cast<void*>(*dev), host, bytes, hipMemcpyHostToDevice, s));
   return OSD_OK;
@@ -326,7 +307,7 @@ int chain_run(osd_handle* h, const ChainJob& job) {
   std::vector<int> o_mid(a.n_blocks), o_out(a.n_blocks);
   for (int b = 0; b < a.n_blocks; ++b) { o_mid[b] = (int)boff[1 + 2 * b]; o_out[b] = (int)boff[2 + 2 * b]; }
   ca.ws_stride = off;
-  OSD_TRY(chain_ensure_buf(&h->chain_ws, &h->chain_ws_floats, (int64_t)max_grid * off, s));
+  OSD_TRY(h->chain_ws.reserve((int64_t)max_grid * off, s));
   ca.ws = h->chain_ws;
 
   FwdWs cw;
@@ -409,22 +390,5 @@ int chain_run(osd_handle* h, const ChainJob& job) {
   return OSD_OK;
 }
 
-void chain_free(osd_handle* h) {
-  hipError_t e = hipSuccess;
-  if (h->chain_ws) e = hipFree(h->chain_ws);
-  if (h->chain_cond) e = hipFree(h->chain_cond);
-  if (h->chain_sync) e = hipFree(h->chain_sync);
-  if (h->chain_args_dev) e = hipFree(h->chain_args_dev);
-  if (h->abort_stream) { e = hipStreamDestroy(h->abort_stream); h->abort_stream = nullptr; }
-  panel_chain_free(h);
-  squad_chain_free(h);
-  h->chain_args_dev = nullptr;
-  free(h->chain_args_host);
-  h->chain_args_host = nullptr;
-  h->chain_args_bytes = 0;
-  (void)e;
-  h->chain_ws = h->chain_cond = nullptr;
-  h->chain_sync = nullptr;
-}
 
 }  // namespace osd

@@ -178,11 +178,7 @@ int panel_chain_pack(osd_handle* h, hipStream_t s) {
   const Arch& a = h->arch;
   const PanelPlan p = make_plan(a, state_cols(h));
   if (!p.ok) return OSD_OK;
-  if (h->panel_wpk_floats < p.wpk_floats) {
-    if (h->panel_wpk) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(h->panel_wpk)); h->panel_wpk = nullptr; h->panel_wpk_floats = 0; }
-    OSD_TRY(device_alloc((void**)&h->panel_wpk, (size_t)p.wpk_floats * 4));
-    h->panel_wpk_floats = p.wpk_floats;
-  }
+  OSD_TRY(h->panel_wpk.reserve(p.wpk_floats, s));
   const bool padded = h->w_out_packed != nullptr;
   for (int l = 0; l < p.n_layers; ++l) {
     const float* w; int ldw, F, K;
@@ -235,7 +231,7 @@ int panel_chain_run(osd_handle* h, const ChainJob& job) {
 
   PanelArgs pa{};
   pa.ws_stride = p.ws_stride;
-  OSD_TRY(chain_ensure_buf(&h->chain_ws, &h->chain_ws_floats, (int64_t)max_grid * p.ws_stride, s));
+  OSD_TRY(h->chain_ws.reserve((int64_t)max_grid * p.ws_stride, s));
   pa.ws = h->chain_ws;
 
   FwdWs cw;
@@ -290,13 +286,6 @@ int panel_chain_run(osd_handle* h, const ChainJob& job) {
   for (int l = 0; l < p.n_layers; ++l) flop_row += 2.0 * p.L[l].K8 * 8 * p.L[l].F;
   chain_launched(h, chain_rounds(n_tiles, S, grid) * (64.0 * flop_row / 0.5e12 * 1e3));
   return OSD_OK;
-}
-
-void panel_chain_free(osd_handle* h) {
-  hipError_t e = hipSuccess;
-  if (h->panel_wpk) e = hipFree(h->panel_wpk);
-  (void)e;
-  h->panel_wpk = nullptr; h->panel_wpk_floats = 0; h->panel_wpk_valid = false;
 }
 
 }  // namespace osd

@@ -177,12 +177,8 @@ static hipError_t pack_any(hipStream_t s, int rp, const float* w, int ldw, int F
 static int squad_pack(osd_handle* h, hipStream_t s, const SquadPlan& p, int rp) {
   const Arch& a = h->arch;
   const int slot = rp == 32 ? 0 : 1, tile = rp;
-  float*& buf = h->squad_wpk[slot];
-  if (h->squad_wpk_floats[slot] < p.wpk_floats) {
-    if (buf) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(buf)); buf = nullptr; h->squad_wpk_floats[slot] = 0; }
-    OSD_TRY(device_alloc((void**)&buf, (size_t)p.wpk_floats * 4));
-    h->squad_wpk_floats[slot] = p.wpk_floats;
-  }
+  OSD_TRY(h->squad_wpk[slot].reserve(p.wpk_floats, s));
+  float* const buf = h->squad_wpk[slot];
   for (int l = 0; l < p.n_layers; ++l) {
     const LayerDesc& ld = a.layers[l];
     OSD_HIP(pack_any(s, rp, h->params[ld.w], ld.K1 + ld.K2, ld.N, ld.K1 + ld.K2, ld.N / tile, p.L[l].K8, buf + p.wpk_off[l]));
@@ -219,7 +215,7 @@ int squad_chain_run(osd_handle* h, const ChainJob& job) {
   SquadArgs sa{};
   const int64_t xs_stride = (int64_t)p.T32 * rp * rp;              // tiles of rp features x rp patients
   const int64_t slab_stride = (int64_t)SQ_S * H0 * rp;
-  OSD_TRY(chain_ensure_buf(&h->chain_ws, &h->chain_ws_floats, (int64_t)n_panels * (xs_stride + slab_stride + p.act_floats), s));
+  OSD_TRY(h->chain_ws.reserve((int64_t)n_panels * (xs_stride + slab_stride + p.act_floats), s));
   sa.xs = h->chain_ws; sa.xs_stride = xs_stride;
   sa.slab = sa.xs + (int64_t)n_panels * xs_stride; sa.slab_stride = slab_stride;
   sa.act = sa.slab + (int64_t)n_panels * slab_stride; sa.act_stride = p.act_floats;
@@ -492,15 +488,6 @@ int train_squad_backward(osd_handle* h, hipStream_t s, const FwdWs& f, const Tra
   hipLaunchKernelGGL(train_squad_bwd_kernel, dim3((unsigned)(panels * SQ_S)), dim3(SQ_THREADS), ts_lds_bytes(p.n_layers), s, ta);
   OSD_HIP(hipGetLastError());
   return OSD_OK;
-}
-
-void squad_chain_free(osd_handle* h) {
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 2; ++i) {
-    if (h->squad_wpk[i]) e = hipFree(h->squad_wpk[i]);
-    h->squad_wpk[i] = nullptr; h->squad_wpk_floats[i] = 0; h->squad_wpk_valid[i] = false;
-  }
-  (void)e;
 }
 
 }  // namespace osd

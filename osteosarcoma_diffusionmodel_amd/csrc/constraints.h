@@ -8,6 +8,7 @@
 //                         ("MSE on correlation matrices", models/cvae.py:296-297)
 //
 // All kernels are stream-ordered (no host synchronisation); batch statistics accumulate in double.
+// Included by handle.h, behind devmem.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,12 +19,12 @@ constexpr int CONS_MAX_SET = 64;   // columns per side of the mutation-expressio
 
 // Device-resident description of the constraint sets.
 struct ConsPlan {
-  int* pw_off = nullptr;      // [n_pathways + 1]
-  int* pw_mem = nullptr;      // [nnz] member column of entry e
-  int* pw_of = nullptr;       // [nnz] pathway of entry e
+  DevBuf<int> pw_off;         // [n_pathways + 1]
+  DevBuf<int> pw_mem;         // [nnz] member column of entry e
+  DevBuf<int> pw_of;          // [nnz] pathway of entry e
   int n_pathways = 0, nnz = 0;
-  int* cols_a = nullptr; int n_a = 0;
-  int* cols_b = nullptr; int n_b = 0;
+  DevBuf<int> cols_a; int n_a = 0;
+  DevBuf<int> cols_b; int n_b = 0;
   int max_col = -1;           // largest referenced column
 };
 
@@ -44,7 +45,6 @@ int64_t cons_carve(const ConsPlan& p, int64_t rows, int cols, char* base, ConsWs
 // validates the host description and uploads it (on failure the plan is left empty)
 int cons_build_plan(const int32_t* off, const int32_t* mem, int n_pathways, const int32_t* ca, int na, const int32_t* cb, int nb, int cols,
                     ConsPlan* out);
-void cons_free_plan(ConsPlan* p);
 
 // loss_out (dev float[1]) += w_loss * L ; part_out (dev float[1], may be null) += L ; dx (dev [rows][ld], may be null) += w_grad * dL/dx
 hipError_t cons_moments(hipStream_t s, const float* x, int ld, int64_t rows, int cols, double* sum2, float2* mi);

@@ -153,19 +153,19 @@ hipError_t cons_pathway(hipStream_t st, const ConsPlan& p, const ConsWs& w, cons
   double* q = Ssum + up8(2 * (int64_t)P);
   int blocks = (int)((rows + 3) / 4);
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(k_pw_rowsum, blocks, 256, 0, st, x, ld, rows, p.pw_off, p.pw_mem, P, w.mi_r, w.s);
+  hipLaunchKernelGGL(k_pw_rowsum, blocks, 256, 0, st, x, ld, rows, p.pw_off.get(), p.pw_mem.get(), P, w.mi_r, w.s);
   {  // S_P = sum_r s[r][P]^2 through the moments kernel (its sumsq output)
     const int rpb = 256;
     dim3 grid((P + 63) / 64, (unsigned)((rows + rpb - 1) / rpb));
     hipLaunchKernelGGL(k_cons_moments, grid, 256, 0, st, w.s, P, rows, P, rpb, Ssum, Ssum + P);
   }
-  hipLaunchKernelGGL(k_pw_coef, 1, 256, 0, st, Ssum + P, p.pw_off, p.pw_mem, P, w.mi_r, rows, w_loss, w_grad, w.coef, loss_out, part_out);
+  hipLaunchKernelGGL(k_pw_coef, 1, 256, 0, st, Ssum + P, p.pw_off.get(), p.pw_mem.get(), P, w.mi_r, rows, w_loss, w_grad, w.coef, loss_out, part_out);
   if (dx) {
     const int rpb = 128;
     dim3 grid((p.nnz + 255) / 256, (unsigned)((rows + rpb - 1) / rpb));
     if (grid.x > 64) grid.x = 64;
-    hipLaunchKernelGGL(k_pw_q, grid, 256, 0, st, x, ld, rows, rpb, p.pw_mem, p.pw_of, p.nnz, P, w.mi_r, w.s, q);
-    hipLaunchKernelGGL(k_pw_grad, blocks, 256, 0, st, x, ld, rows, p.pw_off, p.pw_mem, P, w.mi_r, w.s, q, w.coef, 1.f / (float)(rows - 1), dx);
+    hipLaunchKernelGGL(k_pw_q, grid, 256, 0, st, x, ld, rows, rpb, p.pw_mem.get(), p.pw_of.get(), p.nnz, P, w.mi_r, w.s, q);
+    hipLaunchKernelGGL(k_pw_grad, blocks, 256, 0, st, x, ld, rows, p.pw_off.get(), p.pw_mem.get(), P, w.mi_r, w.s, q, w.coef, 1.f / (float)(rows - 1), dx);
   }
   return hipGetLastError();
 }
@@ -274,13 +274,13 @@ hipError_t cons_mutexpr(hipStream_t st, const ConsPlan& p, const ConsWs& w, cons
   double* Ct = Cr + CONS_MAX_SET * CONS_MAX_SET;
   const int rpb = 128;
   const int blocks = (int)((rows + rpb - 1) / rpb);
-  hipLaunchKernelGGL(k_me_corr, blocks, 256, 0, st, x_recon, ld, rows, rpb, p.cols_a, p.n_a, p.cols_b, p.n_b, w.mi_r, Cr);
-  hipLaunchKernelGGL(k_me_corr, blocks, 256, 0, st, x_true, ld, rows, rpb, p.cols_a, p.n_a, p.cols_b, p.n_b, w.mi_t, Ct);
+  hipLaunchKernelGGL(k_me_corr, blocks, 256, 0, st, x_recon, ld, rows, rpb, p.cols_a.get(), p.n_a, p.cols_b.get(), p.n_b, w.mi_r, Cr);
+  hipLaunchKernelGGL(k_me_corr, blocks, 256, 0, st, x_true, ld, rows, rpb, p.cols_a.get(), p.n_a, p.cols_b.get(), p.n_b, w.mi_t, Ct);
   hipLaunchKernelGGL(k_me_E, 1, 256, 0, st, Cr, Ct, p.n_a, p.n_b, rows, w_loss, w_grad, w.E, loss_out, part_out);
   if (dx) {
     int gb = (int)((rows + 3) / 4);
     if (gb > 1024) gb = 1024;
-    hipLaunchKernelGGL(k_me_grad, gb, 256, 0, st, x_recon, ld, rows, p.cols_a, p.n_a, p.cols_b, p.n_b, w.mi_r, w.E, 1.f / (float)(rows - 1), dx);
+    hipLaunchKernelGGL(k_me_grad, gb, 256, 0, st, x_recon, ld, rows, p.cols_a.get(), p.n_a, p.cols_b.get(), p.n_b, w.mi_r, w.E, 1.f / (float)(rows - 1), dx);
   }
   return hipGetLastError();
 }
@@ -350,12 +350,6 @@ hipError_t launch_row_affine_bwd(hipStream_t s, const float* g, const int* t_idx
 }
 
 // ---- host side: plans ------------------------------------------------------------------------------------------
-void cons_free_plan(ConsPlan* p) {
-  int* bufs[] = {p->pw_off, p->pw_mem, p->pw_of, p->cols_a, p->cols_b};
-  for (int* b : bufs) if (b) (void)hipFree(b);
-  *p = ConsPlan{};
-}
-
 // Validates and uploads; on failure the plan is left empty.
 int cons_build_plan(const int32_t* off, const int32_t* mem, int n_pathways, const int32_t* ca, int na, const int32_t* cb, int nb, int cols,
                     ConsPlan* out) {
@@ -378,20 +372,20 @@ int cons_build_plan(const int32_t* off, const int32_t* mem, int n_pathways, cons
   }
   for (int i = 0; i < na; ++i) { if (ca[i] < 0 || ca[i] >= cols) { set_error("column %d out of range", ca[i]); return OSD_EINVAL; } maxc = ca[i] > maxc ? ca[i] : maxc; }
   for (int i = 0; i < nb; ++i) { if (cb[i] < 0 || cb[i] >= cols) { set_error("column %d out of range", cb[i]); return OSD_EINVAL; } maxc = cb[i] > maxc ? cb[i] : maxc; }
-  auto up = [&](const int32_t* src, int n, int** dst) -> int {
+  auto up = [&](const int32_t* src, int n, DevBuf<int>& dst) -> int {
     if (n <= 0) return OSD_OK;
-    OSD_HIP(hipMalloc((void**)dst, (size_t)n * 4));
-    OSD_HIP(hipMemcpy(*dst, src, (size_t)n * 4, hipMemcpyHostToDevice));
+    OSD_TRY(dst.reserve(n));
+    OSD_HIP(hipMemcpy(dst, src, (size_t)n * 4, hipMemcpyHostToDevice));
     return OSD_OK;
   };
   int rc = OSD_OK;
   if (n_pathways > 0) {
     std::vector<int32_t> of((size_t)(nnz > 0 ? nnz : 1));
     for (int p = 0; p < n_pathways; ++p) for (int e = off[p]; e < off[p + 1]; ++e) of[e] = p;
-    if ((rc = up(off, n_pathways + 1, &out->pw_off)) != OSD_OK || (rc = up(mem, nnz, &out->pw_mem)) != OSD_OK ||
-        (rc = up(of.data(), nnz, &out->pw_of)) != OSD_OK) { cons_free_plan(out); return rc; }
+    if ((rc = up(off, n_pathways + 1, out->pw_off)) != OSD_OK || (rc = up(mem, nnz, out->pw_mem)) != OSD_OK ||
+        (rc = up(of.data(), nnz, out->pw_of)) != OSD_OK) { *out = ConsPlan{}; return rc; }
   }
-  if ((rc = up(ca, na, &out->cols_a)) != OSD_OK || (rc = up(cb, nb, &out->cols_b)) != OSD_OK) { cons_free_plan(out); return rc; }
+  if ((rc = up(ca, na, out->cols_a)) != OSD_OK || (rc = up(cb, nb, out->cols_b)) != OSD_OK) { *out = ConsPlan{}; return rc; }
   out->n_pathways = n_pathways; out->nnz = nnz; out->n_a = na; out->n_b = nb; out->max_col = maxc;
   return OSD_OK;
 }
@@ -399,13 +393,6 @@ int cons_build_plan(const int32_t* off, const int32_t* mem, int n_pathways, cons
 }  // namespace osd
 
 using namespace osd;
-
-namespace {
-struct Scratch {
-  char* p = nullptr;
-  ~Scratch() { if (p) (void)hipFree(p); }
-};
-}  // namespace
 
 extern "C" {
 
@@ -416,16 +403,14 @@ int osd_loss_pathway_coherence(void* stream, int device, const float* x, int64_t
   hipStream_t s = (hipStream_t)stream;
   ConsPlan plan;
   OSD_TRY(cons_build_plan(offsets_host, members_host, n_pathways, nullptr, 0, nullptr, 0, cols, &plan));
-  Scratch sc;
+  DevBuf<char> sc;
   ConsWs w;
-  const int64_t bytes = cons_carve(plan, rows, cols, nullptr, &w);
-  if (hipMalloc((void**)&sc.p, (size_t)bytes) != hipSuccess) { cons_free_plan(&plan); set_error("hipMalloc of %lld bytes failed", (long long)bytes); return OSD_ENOMEM; }
-  cons_carve(plan, rows, cols, sc.p, &w);
+  OSD_TRY(sc.reserve(cons_carve(plan, rows, cols, nullptr, &w)));
+  cons_carve(plan, rows, cols, sc, &w);
   hipError_t e = hipMemsetAsync(w.acc, 0, (size_t)w.acc_doubles * 8, s);
   if (e == hipSuccess) e = cons_moments(s, x, ld, rows, cols, w.acc, w.mi_r);
   if (e == hipSuccess) e = cons_pathway(s, plan, w, x, ld, rows, cols, (float)weight, (float)weight, loss_out, nullptr, dx);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  cons_free_plan(&plan);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);      // plan and scratch are released behind it
   OSD_HIP(e);
   return OSD_OK;
 }
@@ -438,17 +423,15 @@ int osd_loss_mutation_expression(void* stream, int device, const float* x_recon,
   hipStream_t s = (hipStream_t)stream;
   ConsPlan plan;
   OSD_TRY(cons_build_plan(nullptr, nullptr, 0, cols_a_host, n_a, cols_b_host, n_b, cols, &plan));
-  Scratch sc;
+  DevBuf<char> sc;
   ConsWs w;
-  const int64_t bytes = cons_carve(plan, rows, cols, nullptr, &w);
-  if (hipMalloc((void**)&sc.p, (size_t)bytes) != hipSuccess) { cons_free_plan(&plan); set_error("hipMalloc of %lld bytes failed", (long long)bytes); return OSD_ENOMEM; }
-  cons_carve(plan, rows, cols, sc.p, &w);
+  OSD_TRY(sc.reserve(cons_carve(plan, rows, cols, nullptr, &w)));
+  cons_carve(plan, rows, cols, sc, &w);
   hipError_t e = hipMemsetAsync(w.acc, 0, (size_t)w.acc_doubles * 8, s);
   if (e == hipSuccess) e = cons_moments(s, x_recon, ld, rows, cols, w.acc, w.mi_r);
   if (e == hipSuccess) e = cons_moments(s, x_true, ld, rows, cols, w.acc + 2 * (int64_t)cols, w.mi_t);
   if (e == hipSuccess) e = cons_mutexpr(s, plan, w, x_recon, x_true, ld, rows, cols, (float)weight, (float)weight, loss_out, nullptr, dx);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  cons_free_plan(&plan);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);      // plan and scratch are released behind it
   OSD_HIP(e);
   return OSD_OK;
 }

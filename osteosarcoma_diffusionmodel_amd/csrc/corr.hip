@@ -321,19 +321,19 @@ int osd_val_centered_gram(void* stream, int device, const float* X, int64_t rows
   a.rows = (int)rows; a.D = D; a.Dq = Dq; a.nt = nt;
   a.S = cov_slices(n_tri, cus);
   a.rows_per = (int)(((rows + a.S - 1) / a.S + COV_BK - 1) / COV_BK * COV_BK);
-  DevBuf cen, slab, pad;
-  OSD_HIP(cen.alloc((size_t)nt * COV_TILE * sizeof(float)));
-  OSD_HIP(slab.alloc((size_t)n_tri * a.S * COV_SLAB_ELEMS * sizeof(double)));
-  OSD_HIP(hipMemsetAsync(cen.p, 0, (size_t)nt * COV_TILE * sizeof(float), s));
-  OSD_HIP(hipMemcpyAsync(cen.p, center_host, (size_t)D * sizeof(float), hipMemcpyHostToDevice, s));
-  a.c = (const float*)cen.p;
-  a.slab = (double*)slab.p;
+  ValBuf cen, slab, pad;
+  OSD_TRY(cen.alloc((size_t)nt * COV_TILE * sizeof(float)));
+  OSD_TRY(slab.alloc((size_t)n_tri * a.S * COV_SLAB_ELEMS * sizeof(double)));
+  OSD_HIP(hipMemsetAsync(cen.get(), 0, (size_t)nt * COV_TILE * sizeof(float), s));
+  OSD_HIP(hipMemcpyAsync(cen.get(), center_host, (size_t)D * sizeof(float), hipMemcpyHostToDevice, s));
+  a.c = (const float*)cen.get();
+  a.slab = (double*)slab.get();
   if ((reinterpret_cast<uintptr_t>(X) & 15) == 0 && ld % 4 == 0 && ld >= Dq) {
     a.X = X; a.ld = ld;
   } else {                                                   // 16-byte LDS-DMA cannot read this X in place
-    OSD_HIP(pad.alloc((size_t)rows * Dq * sizeof(float)));
+    OSD_TRY(pad.alloc((size_t)rows * Dq * sizeof(float)));
     OSD_HIP(launched(cov_pad_copy, 2048, 256, 0, s, X, (long long)ld, (long long)rows, D, Dq, pad.as<float>()));
-    a.X = (const float*)pad.p; a.ld = Dq;
+    a.X = (const float*)pad.get(); a.ld = Dq;
   }
   OSD_HIP(launched(cov_gram_kernel, dim3((unsigned)(n_tri * a.S)), dim3(COV_THREADS), COV_LDS_BYTES, s, a));
   OSD_HIP(launched(cov_gram_reduce, dim3((unsigned)n_tri), dim3(256), 0, s, slab.as<const double>(), a.S, nt, D, G_dev));
@@ -354,16 +354,16 @@ int osd_val_corr_compare(void* stream, int device, const double* G_real, const d
   OSD_HIP(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const int n_pairs = n_blocks * (n_blocks + 1) / 2;
-  DevBuf diag, flags, bnd, res;
-  OSD_HIP(diag.alloc((size_t)2 * D * sizeof(double)));
-  OSD_HIP(flags.alloc((size_t)D * sizeof(int)));
-  OSD_HIP(bnd.alloc((size_t)(n_blocks + 1) * sizeof(int)));
-  OSD_HIP(res.alloc(sizeof(unsigned long long) + (size_t)n_pairs * sizeof(CorrSlot)));
-  unsigned long long* n_const = (unsigned long long*)res.p;
+  ValBuf diag, flags, bnd, res;
+  OSD_TRY(diag.alloc((size_t)2 * D * sizeof(double)));
+  OSD_TRY(flags.alloc((size_t)D * sizeof(int)));
+  OSD_TRY(bnd.alloc((size_t)(n_blocks + 1) * sizeof(int)));
+  OSD_TRY(res.alloc(sizeof(unsigned long long) + (size_t)n_pairs * sizeof(CorrSlot)));
+  unsigned long long* n_const = (unsigned long long*)res.get();
   CorrSlot* slots = (CorrSlot*)(n_const + 1);
-  double* dr = (double*)diag.p; double* ds = dr + D;
-  OSD_HIP(hipMemsetAsync(res.p, 0, sizeof(unsigned long long) + (size_t)n_pairs * sizeof(CorrSlot), s));
-  OSD_HIP(hipMemcpyAsync(bnd.p, bounds_host, (size_t)(n_blocks + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+  double* dr = (double*)diag.get(); double* ds = dr + D;
+  OSD_HIP(hipMemsetAsync(res.get(), 0, sizeof(unsigned long long) + (size_t)n_pairs * sizeof(CorrSlot), s));
+  OSD_HIP(hipMemcpyAsync(bnd.get(), bounds_host, (size_t)(n_blocks + 1) * sizeof(int), hipMemcpyHostToDevice, s));
   OSD_HIP(launched(corr_diag, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, G_real, G_synth, D, dr, ds, flags.as<int>(), n_const));
   // up to 256 wavefronts walk the rows of a block; one set of atomics per wavefront and block pair
   int gx = (D / n_blocks + 3) / 4;
@@ -371,7 +371,7 @@ int osd_val_corr_compare(void* stream, int device, const double* G_real, const d
   OSD_HIP(launched(corr_compare_kernel, dim3((unsigned)gx, (unsigned)n_pairs), dim3(256), 0, s, G_real, G_synth, D, bnd.as<const int>(),
                    n_blocks, dr, ds, flags.as<const int>(), strong, slots));
   std::vector<unsigned long long> raw((size_t)1 + (size_t)n_pairs * OSD_CORR_STATS);
-  OSD_HIP(read_back(s, raw.data(), res.p, raw.size() * 8));
+  OSD_HIP(read_back(s, raw.data(), res.get(), raw.size() * 8));
   out_host[0] = (double)raw[0];
   for (int p = 0; p < n_pairs; ++p) {
     CorrSlot c;

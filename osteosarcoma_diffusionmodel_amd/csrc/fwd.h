@@ -30,7 +30,6 @@ struct TrunkIn {
   int* path;                     // training calls: OSD_TP_* bits of what ran are OR-ed in (handle.h: last_train_path), else null
 };
 
-int ensure_arena(Slot* s, int64_t floats);
 int64_t carve_fwd(const Arch& a, float* base, int64_t n, bool train, FwdWs* ws);
 int run_cond(osd_handle* h, hipStream_t s, const float* cond, int64_t n, const FwdWs& ws);
 int run_trunk(osd_handle* h, hipStream_t s, const FwdWs& ws, const TrunkIn& in);
@@ -65,8 +64,8 @@ int run_steps(Slot& sl, int S, int flags, F&& enqueue_step) {
   OSD_HIP(ce);
   OSD_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
   // the exec object must outlive its launches: the slot keeps it until its next use
-  sl.graph = graph;
-  sl.exec = exec;
+  sl.graph.reset(graph);
+  sl.exec.reset(exec);
   for (int it = 0; it < S; ++it) OSD_HIP(hipGraphLaunch(exec, s));
   return OSD_OK;
 }
@@ -78,8 +77,6 @@ bool chain_uses_squad(osd_handle* h, int64_t n);
 int chain_run(osd_handle* h, const ChainJob& job);
 int chain_check_status(osd_handle* h);
 int chain_finish(osd_handle* h, int* gave_up);
-void chain_free(osd_handle* h);
-int chain_ensure_buf(float** p, int64_t* cap, int64_t floats, hipStream_t s);
 int chain_ensure_sync(osd_handle* h, int64_t n_tiles, hipStream_t s);
 // ---- shared by the chunk drivers and the chain kernels' host files (api.hip) ----
 // The state x [job.n][ldx] of a chain (or of one chunk of it) from job.x_T or Philox.  keep_aliased: an x_T that already is x stays
@@ -129,13 +126,11 @@ bool panel_chain_supported(const osd_handle* h);
 int panel_chain_slots(osd_handle* h);
 int panel_chain_pack(osd_handle* h, hipStream_t s);
 int panel_chain_run(osd_handle* h, const ChainJob& job);
-void panel_chain_free(osd_handle* h);
 hipError_t launch_pack_fragments(hipStream_t s, const float* w, int ldw, int F, int K, int nfbg, int K8, float* dst);
 // chain_squad.hip
 bool squad_chain_supported(const osd_handle* h);
 bool squad_window(osd_handle* h, int64_t n);
 int squad_chain_run(osd_handle* h, const ChainJob& job);
-void squad_chain_free(osd_handle* h);
 // train_squad.h (host side in chain_squad.hip): the training forward trunk as one launch of squads
 int64_t train_squad_act_floats(const Arch& a, int64_t* wpk_floats);
 bool train_squad_ok(const osd_handle* h, int64_t n);

@@ -309,18 +309,10 @@ __global__ void col_moments_reduce(const double* __restrict__ slab, int slices, 
 // One grow-only workspace per device, held for the length of a call: a fit calls osd_val_glm_eval hundreds of times.
 struct Workspace {
   std::mutex mu;
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipError_t reserve(size_t want) {
-    if (want <= bytes) return hipSuccess;
-    if (p) { hipError_t e = hipFree(p); p = nullptr; bytes = 0; if (e != hipSuccess) return e; }
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) bytes = want; else p = nullptr;
-    return e;
-  }
+  DevBuf<char> buf;
 };
 constexpr int GLM_MAX_DEVICES = 64;
-Workspace g_ws[GLM_MAX_DEVICES];
+Workspace* const g_ws = new Workspace[GLM_MAX_DEVICES];      // never destroyed: no hipFree from a static destructor at process exit
 
 template <int K, int NV, int TMAX>
 int glm_launch2(bool aligned, bool dry, unsigned items, unsigned T, hipStream_t s, const GlmArgs& a) {
@@ -399,8 +391,8 @@ int osd_val_glm_eval(void* stream, int device, const float* X, int64_t rows, int
   std::lock_guard<std::mutex> hold(ws.mu);
   const size_t loss_bytes = (size_t)items * K * sizeof(double);
   const size_t slab_bytes = grad_dev ? (size_t)items * K * a.Dl * sizeof(double) : 0;
-  OSD_HIP(ws.reserve(loss_bytes + slab_bytes));
-  a.loss_slab = (double*)ws.p;
+  OSD_TRY(ws.buf.reserve((int64_t)(loss_bytes + slab_bytes)));
+  a.loss_slab = (double*)ws.buf.get();
   a.slab = grad_dev ? a.loss_slab + (size_t)items * K : nullptr;
 
   const bool grad = grad_dev != nullptr;
@@ -434,8 +426,8 @@ int osd_val_col_centered_moments(void* stream, int device, const float* X, int64
   slices = (rows + rows_per - 1) / rows_per;
   Workspace& ws = g_ws[device];
   std::lock_guard<std::mutex> hold(ws.mu);
-  OSD_HIP(ws.reserve(((size_t)slices * 2 * D + (size_t)2 * D) * sizeof(double)));
-  double* slab = (double*)ws.p;
+  OSD_TRY(ws.buf.reserve((int64_t)(((size_t)slices * 2 * D + (size_t)2 * D) * sizeof(double))));
+  double* slab = (double*)ws.buf.get();
   double* out = slab + (size_t)slices * 2 * D;
   OSD_HIP(launched(col_moments_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)slices), dim3(256), 0, s, X, (long long)ld,
                    (long long)rows, D, center, (long long)rows_per, slab));

@@ -5,7 +5,6 @@
 #include <string>
 #include <vector>
 #include "../../include/osdiff.h"
-#include "constraints.h"
 #include "batch_src.h"
 
 namespace osd {
@@ -31,6 +30,13 @@ void set_error(const char* fmt, ...);
 inline int64_t up64(int64_t v) { return (v + 63) / 64 * 64; }      // buffers are carved in whole 64-float (256-byte) granules
 // hipMalloc that reports: OSD_ENOMEM with the byte count in osd_last_error(), the sticky HIP error cleared
 int device_alloc(void** p, size_t bytes);
+
+}  // namespace osd
+
+#include "devmem.h"
+#include "constraints.h"
+
+namespace osd {
 
 // One Linear of the denoiser trunk (with or without GroupNorm+SiLU behind it).
 struct LayerDesc {
@@ -69,7 +75,7 @@ int build_arch(const osd_config& cfg, Arch* a);
 // What one reverse chain runs: n_steps steps t = n_steps - 1 .. 0, step t reading row t of temb [n_steps][H0]
 // (time_proj(TimeEmbedding(tau / T)) of the step's timestep tau) and of coef [n_steps][4] = (A, B, C, 0), x' = A x + B eps + C z.
 // Philox draws of step t use step counter t, injected draws sit at noises[n_steps - 1 - t].  The DDPM chain of osd_sample_chain
-// is {T, d_temb, d_coef}; osd_sample_chain_steps gathers a strided plan into the handle's plan_temb / plan_coef.
+// is {T, d_temb, d_coef}; osd_sample_chain_steps gathers a strided plan into the handle's plan_temb / plan_tab.
 struct StepPlan {
   int n_steps;
   const float* temb;
@@ -142,13 +148,12 @@ struct FwdWs {
 };
 
 struct Slot {
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;
-  float* arena = nullptr;
-  int64_t arena_floats = 0;
-  int* t_dev = nullptr;
-  hipGraph_t graph = nullptr;        // graph of the last captured reverse step (kept alive
-  hipGraphExec_t exec = nullptr;     // until its replays have drained)
+  Stream stream;                     // h->main has none: the single-stream entry points run on the caller's
+  Event done;
+  DevBuf<float> arena;
+  DevBuf<int> t_dev;
+  Graph graph;                       // graph of the last captured reverse step (kept alive
+  GraphExec exec;                    // until its replays have drained)
 };
 
 }  // namespace osd
@@ -159,7 +164,7 @@ struct osd_handle {
   hipStream_t stream = nullptr;
   std::vector<const float*> params;
   bool have_schedule = false, have_weights = false;
-  float* w_in_packed = nullptr;      // input_proj.weight zero-padded to [H0][roundup(D,32)] for the LDS-DMA kernel
+  osd::DevBuf<float> w_in_packed;    // input_proj.weight zero-padded to [H0][roundup(D,32)] for the LDS-DMA kernel
   int w_in_ld = 0;
   bool w_packed_stale = false;      // a training step skipped the repack of w_in_packed / w_out_packed: refreshed lazily (api.hip: ensure_packed)
   // D % 4 != 0 (e.g. the reference's real dims 62 + 5054 + 26 = 5142): the reverse chain keeps its state in an internal buffer
@@ -171,63 +176,58 @@ struct osd_handle {
   bool splitk_suspended = false;     // a chain-kernel fallback re-run in progress: no split-K (bit-identical to the chain kernel)
   int input_splitk = 0;              // osd_set_option("input_splitk"): 0 off (default: a row's result does not depend on how rows are chunked / sharded),
                                      // -1 auto (chunks with < 128 input_proj tiles), n = slices
-  float* w_out_packed = nullptr;     // [Dp][H_last]: output_proj.weight + zero rows for the pad columns (allocated iff D % 4)
-  float* b_out_packed = nullptr;     // [Dp]
-  float* chain_xpad = nullptr; int64_t chain_xpad_floats = 0;     // padded chain state of the chain kernel [n][Dp]
-  float *d_sqrt_ac = nullptr, *d_sqrt_1m = nullptr, *d_coef = nullptr, *d_time_emb = nullptr, *d_temb = nullptr;
-  // the step plan of osd_sample_chain_steps (StepPlan): gathered temb rows [T][H0], coefficients [T][4], timesteps [T] (allocated on
-  // first use); plan_host stages the coefficient + timestep upload and is rewritten only after plan_ev says the copy was consumed
-  float* plan_temb = nullptr; float* plan_coef = nullptr; int* plan_t = nullptr;
-  void* plan_host = nullptr; hipEvent_t plan_ev = nullptr;
+  osd::DevBuf<float> w_out_packed;   // [Dp][H_last]: output_proj.weight + zero rows for the pad columns (allocated iff D % 4)
+  osd::DevBuf<float> b_out_packed;   // [Dp]
+  osd::DevBuf<float> chain_xpad;     // padded chain state of the chain kernel [n][Dp]
+  osd::DevBuf<float> d_sqrt_ac, d_sqrt_1m, d_coef, d_time_emb, d_temb;
+  // the step plan of osd_sample_chain_steps (StepPlan): gathered temb rows [T][H0], and the uploaded table of an S-step plan:
+  // coefficients [S][4], then timesteps [S] (as int32)
+  osd::DevBuf<float> plan_temb;
+  osd::Staged<float> plan_tab;
   int64_t chunk_rows = 65536;
   int n_streams = 2;
   std::vector<osd::Slot> slots;
   osd::Slot main;            // workspace used by the single-stream entry points
-  hipEvent_t fork_ev = nullptr;
+  osd::Event fork_ev;
   // training workspace
-  float* train_arena = nullptr;
-  int64_t train_arena_floats = 0;
-  float* loss_dev = nullptr;
-  int* t_san = nullptr;              // clamped copy of a caller-supplied t_index (sanitize_t)
-  int64_t t_san_cap = 0;
-  double* normsq_dev = nullptr;      // 256 per-workgroup partials of the gradient norm (osd_clip_adamw_step)
+  osd::DevBuf<float> train_arena;
+  osd::DevBuf<float> loss_dev;
+  osd::DevBuf<int> t_san;            // clamped copy of a caller-supplied t_index (sanitize_t)
+  osd::DevBuf<double> normsq_dev;    // 256 per-workgroup partials of the gradient norm (osd_clip_adamw_step)
   // weight-gradient side stream of the backward pass and its fork/join events
-  hipStream_t wgrad_stream = nullptr;
-  std::vector<hipEvent_t> ev_pool;
+  osd::Stream wgrad_stream;
+  std::vector<osd::Event> ev_pool;
   int train_streams = 2;             // osd_set_option("train_streams", 1|2): 2 = weight-gradient leaves of the backward pass on a side stream
   osd::BatchSrc batch_src{}; bool have_batch_src = false;      // osd_train_batch_source: one-shot source of the next training call's rows
-  // classifier-free guidance: the null condition on the device -- slot 0 of the current guided sampling / forward call, slot 1 of the
-  // next training call's condition dropout (each cond_dim floats, 64-float stride) --, its host staging and the event that says
-  // the last upload has read the staging (api.hip: upload_null_cond)
-  float* d_null_cond = nullptr; float* null_host = nullptr; hipEvent_t null_ev = nullptr;
+  // classifier-free guidance: the null condition -- slot 0 of the current guided sampling / forward call, slot 1 of the next training
+  // call's condition dropout (each cond_dim floats, 64-float stride) (api.hip: upload_null_cond)
+  osd::Staged<float> null_cond;
   bool null_valid[2] = {false, false};      // the device slot holds the staging's vector: a call with the same bits uploads nothing
   // known-feature conditioning (osd_sample_chain_known): the schedule's two level buffers as osd_set_schedule received them, and the
-  // current call's level table [S][2] on the device with its host staging and the event that says the upload has read it
+  // current call's level table [S][2]
   std::vector<float> sched_sqrt_ac, sched_sqrt_1m;
-  float* known_level = nullptr; float* known_level_host = nullptr; hipEvent_t known_ev = nullptr;
+  osd::Staged<float> known_level;
   // x0 clipping (osd_sample_chain_clipped): the DDPM chain's (P, Q, E, F) rows [T][4] folded by osd_set_schedule, and the current call's
-  // tables on the device -- coefficients [T][4], then bounds [2][Dp] (pad columns (-inf, +inf)) -- with their host staging and the event
-  // that says the upload has read it
+  // tables -- coefficients [T][4], then bounds [2][Dp] (pad columns (-inf, +inf))
   std::vector<float> sched_x0_coef;
-  float* clip_dev = nullptr; float* clip_host = nullptr; hipEvent_t clip_ev = nullptr;
-  // the multistep solver (osd_sample_chain_multistep): the current call's history coefficients [T] on the device, their host staging
-  // and the event that says the upload has read it
-  float* hist_dev = nullptr; float* hist_host = nullptr; hipEvent_t hist_ev = nullptr;
+  osd::Staged<float> clip_tab;
+  // the multistep solver (osd_sample_chain_multistep): the current call's history coefficients [T]
+  osd::Staged<float> hist_coef;
   bool have_cond_drop = false; float cond_drop_p = 0.f; const float* cond_drop_keep = nullptr;   // osd_train_condition_dropout: one-shot
   int64_t saved_rows = -1;           // rows of the last osd_denoiser_forward_train whose activations are still in the arena
   // constraint losses (osd_set_constraints); parts_dev = (mse, L_pc, L_me) of the last training call
   osd::ConsPlan cons;
   double w_pathway = 0.0, w_mutexpr = 0.0;
-  float* parts_dev = nullptr;
+  osd::DevBuf<float> parts_dev;
   // the eps-loss of the training step (osd_set_loss): persistent.  loss_kind OSD_LOSS_*, loss_tw = per-timestep weights [T] on the device while
   // a table is set (loss_tw_set), else every row weighs 1.  OSD_LOSS_L2 without a table is the default and runs EpiMse
   // what the network predicts (osd_set_prediction): persistent.  pred_type OSD_PRED_*; sched_post_coef = the six per-step scalars as
   // osd_set_schedule received them, from which fold_schedule (api.hip) refolds d_coef / sched_x0_coef / d_pq for the type.  d_pq: dev
   // (P, Q) [T][2] of x0^ = P x_t + Q out (the constraint losses), then the (U, V) [T][2] of osd_convert_prediction for conv_kind (-1: none)
   int pred_type = 0; std::vector<float> sched_post_coef;
-  float* d_pq = nullptr; int conv_kind = -1;
+  osd::DevBuf<float> d_pq; int conv_kind = -1;
   int loss_kind = 0; float loss_delta = 1.0f;
-  float* loss_tw = nullptr; bool loss_tw_set = false;
+  osd::DevBuf<float> loss_tw; bool loss_tw_set = false;
   // training on incomplete rows (osd_set_loss_mask): persistent.  NaN in x0 = not observed; the q_sample kernels zero-fill it and mark the
   // target with NaN, the loss runs EpiLossT<true> on the fp32 launcher.  false: today's launches
   bool loss_mask = false;
@@ -236,43 +236,43 @@ struct osd_handle {
   // launches and in osd_convert_prediction.  0: today's launches.  Needs OSD_PRED_SAMPLE; either can be set second, so the calls check
   int n_link = 0;
   // differentially private training (osd_set_dp_clip; dp.h): persistent.  dp_clip = the per-row gradient bound C (0: off, today's launches);
-  // dp_norms = dev [2][dp_norms_cap]: s_r, then the clip factors c_r, of the last clipped call's dp_rows rows (-1: none yet); dp_plan = the
+  // dp_norms = dev [2][dp_norms.cap() / 2]: s_r, then the clip factors c_r, of the last clipped call's dp_rows rows (-1: none yet); dp_plan = the
   // cached item lists of the two launches (k_dp.hip)
   double dp_clip = 0.0;
-  float* dp_norms = nullptr; int64_t dp_norms_cap = 0; int64_t dp_rows = -1;
+  osd::DevBuf<float> dp_norms; int64_t dp_rows = -1;
   void* dp_plan = nullptr;
   bool dp_replay_ok = false;         // osd_dp_replay: the lists still describe the workspace (cleared by whatever carves it again: ensure_train_ws)
   // the likelihood bound (osd_row_sq_error / osd_bound_sweep): rows per launch group of the sweep, and the sweep's timesteps on the device
   int64_t bound_rows = 32768;        // osd_set_option("bound_rows")
-  int* bound_ts = nullptr; int64_t bound_ts_cap = 0;
+  osd::DevBuf<int> bound_ts;
   std::vector<void*> wg_plans;       // grouped weight-gradient launches (wgrad_group.hip): one cached work list per flush point
   // persistent reverse-chain kernel (chain.h / chain.hip)
   int sampler = 0;                   // osd_set_option("sampler"): 0 auto, 1 chain kernel whenever the architecture allows, 2 per-layer kernels
   int chain_grid = 0;                // 0 = min(row tiles, resident slots); > 0 caps the workgroup count (tests: force cross-workgroup hand-offs)
   int chain_steps_per_launch = 0;    // 0 = the whole chain in one launch
   int chain_stagger = 30000;         // shader cycles between the starts of the two workgroups of a CU (0 = off)
-  float* chain_ws = nullptr; int64_t chain_ws_floats = 0;
-  float* chain_cond = nullptr; int64_t chain_cond_floats = 0;
-  unsigned* chain_sync = nullptr; int64_t chain_sync_words = 0;
+  osd::DevBuf<float> chain_ws;
+  osd::DevBuf<float> chain_cond;
+  osd::DevBuf<unsigned> chain_sync;
   // argument blocks of the chain kernels' launches (ChainArgs / PanelArgs / SquadArgs), one per launch of the current chain: device
   // copies the kernels read and host copies kept alive while their uploads may be pending (chain.hip: chain_args_ring)
-  void* chain_args_dev = nullptr; void* chain_args_host = nullptr; size_t chain_args_bytes = 0;
+  osd::DevBuf<char> chain_args_dev; std::vector<char> chain_args_host;
   bool chain_pending = false;        // a chain was launched whose status word has not been read yet
   unsigned long long chain_spin_budget = 500000000ull;   // osd_set_option("chain_spin_budget"): s_memrealtime ticks (100 MHz) a dependency wait may take (5 s)
   int64_t chain_wall_budget_ms = 0;  // osd_set_option("chain_wall_budget_ms"): host-side budget of a synchronous chain; 0 = 10 x the expected run time + 2 s
   double chain_expected_ms = 0.0;    // run-time estimate of the chain launched last (chain_run)
   int64_t chain_fallbacks = 0;       // chains that gave up and were re-run on the per-layer kernels (osd_get_option)
-  hipStream_t abort_stream = nullptr;   // carries the host's abort flag to a chain kernel that overran its wall-clock budget
+  osd::Stream abort_stream;             // carries the host's abort flag to a chain kernel that overran its wall-clock budget
   unsigned long long* chain_stamps = nullptr;   // diagnostic builds (csrc/diag): device buffer of 8 counters per workgroup, else null
   int last_engine = 0;               // engine of the most recent osd_sample_chain (0 per-layer, 1 chain kernel)
   // LDS-resident variant of the chain kernel (chain_panel.h / chain_panel.hip)
   int chain_variant = 0;             // osd_set_option("chain_variant"): 0 auto (chain.hip: chain_use_panel / squad_window), 1 workspace chain (chain.h),
                                      // 2 LDS-resident chain where the architecture fits (else 1), 3 squad chain (chain_squad.h) where model and batch fit (else auto's choice without it)
   int last_chain_variant = 0;        // variant the most recent chain-kernel run used (osd_get_option)
-  float* panel_wpk = nullptr; int64_t panel_wpk_floats = 0;   // fragment-ordered copies of the weights
+  osd::DevBuf<float> panel_wpk;      // fragment-ordered copies of the weights
   bool panel_wpk_valid = false;      // false after anything that may have changed the parameters: repacked by the next chain
   // small-batch variant (chain_squad.h / chain_squad.hip)
-  float* squad_wpk[2] = {nullptr, nullptr}; int64_t squad_wpk_floats[2] = {0, 0};      // fragment-ordered weights: [0] 32-patient panels, [1] 16-patient panels
+  osd::DevBuf<float> squad_wpk[2];   // fragment-ordered weights: [0] 32-patient panels, [1] 16-patient panels
   bool squad_wpk_valid[2] = {false, false};
   int last_squad_rp = 0;             // patients per panel of the squad chain that ran last (osd_get_option "last_squad_panel")
   int train_squad = 2;               // osd_set_option("train_squad"): the training forward trunk as one launch of squads (train_squad.h) from 2 048 rows on
@@ -287,4 +287,5 @@ struct osd_handle {
   // osd_profile_step: when non-null, run_trunk records prof_events[prof_i++] after every launch
   std::vector<hipEvent_t>* prof_events = nullptr;
   int prof_i = 0;
+  ~osd_handle();                     // api.hip: the members release themselves; the opaque plans go through their *_free
 };

@@ -115,66 +115,36 @@ hipError_t launch_dp_scale_rows(hipStream_t s, const DpScaleItem* d_items, int n
   return hipGetLastError();
 }
 
-// the item lists as the device holds them; re-uploaded only when they changed (first step, another batch size, a re-allocated arena):
-// they hold workspace pointers only, so a DataLoader's fresh tensors every batch cost no upload and no synchronise
+// the item lists as the device holds them (devmem.h: DevList)
 struct DpPlan {
   const float* cond = nullptr; const int* gather = nullptr;      // the last launch's arguments (osd_dp_replay)
-  std::vector<DpNormItem> norms; DpNormItem* d_norms = nullptr; size_t cap_norms = 0;
-  std::vector<DpScaleItem> scales; DpScaleItem* d_scales = nullptr; size_t cap_scales = 0;
+  DevList<DpNormItem> norms;
+  DevList<DpScaleItem> scales;
 };
 
-template <class E>
-static int dp_upload(hipStream_t s, const std::vector<E>& fresh, std::vector<E>& kept, E** dev, size_t* cap) {
-  // the callers memset every item before filling it, so padding bytes compare equal
-  if (*dev && fresh.size() == kept.size() && (fresh.empty() || memcmp(fresh.data(), kept.data(), fresh.size() * sizeof(E)) == 0)) return OSD_OK;
-  OSD_HIP(hipStreamSynchronize(s));            // rare: the old list may still be in use
-  if (*cap < fresh.size() || !*dev) {
-    if (*dev) OSD_HIP(hipFree(*dev));
-    *dev = nullptr; *cap = 0;
-    const size_t want = fresh.size() < 64 ? 64 : fresh.size();
-    OSD_TRY(device_alloc((void**)dev, want * sizeof(E)));
-    *cap = want;
-  }
-  kept = fresh;
-  if (!kept.empty()) OSD_HIP(hipMemcpyAsync(*dev, kept.data(), kept.size() * sizeof(E), hipMemcpyHostToDevice, s));
-  return OSD_OK;
-}
+// the callers memset every item before filling it, so padding bytes compare equal
+template <class E> static bool same_bytes(const E& a, const E& b) { return memcmp(&a, &b, sizeof(E)) == 0; }
 
 int dp_clip_rows(osd_handle* h, hipStream_t s, const std::vector<DpNormItem>& norms, const std::vector<DpScaleItem>& scales, int64_t rows, double unscale,
                  const float* cond, const int* gather) {
   if (!h->dp_plan) h->dp_plan = new DpPlan();
   DpPlan* pl = static_cast<DpPlan*>(h->dp_plan);
-  if (h->dp_norms_cap < rows) {
-    OSD_HIP(hipStreamSynchronize(s));
-    if (h->dp_norms) { OSD_HIP(hipFree(h->dp_norms)); h->dp_norms = nullptr; h->dp_norms_cap = 0; }
-    const int64_t cap = (rows + 1023) / 1024 * 1024;
-    OSD_TRY(device_alloc((void**)&h->dp_norms, (size_t)cap * 2 * sizeof(float)));
-    h->dp_norms_cap = cap;
-  }
-  OSD_TRY(dp_upload(s, norms, pl->norms, &pl->d_norms, &pl->cap_norms));
-  OSD_TRY(dp_upload(s, scales, pl->scales, &pl->d_scales, &pl->cap_scales));
-  float* factors = h->dp_norms + h->dp_norms_cap;
-  OSD_HIP(launch_dp_row_norms(s, pl->d_norms, (int)pl->norms.size(), rows, (float)unscale, (float)h->dp_clip, h->dp_norms, factors, cond, gather));
-  OSD_HIP(launch_dp_scale_rows(s, pl->d_scales, (int)pl->scales.size(), rows, factors));
+  OSD_TRY(h->dp_norms.reserve(2 * ((rows + 1023) / 1024 * 1024), s));      // 1024-row granules
+  OSD_TRY(pl->norms.upload(s, norms, same_bytes<DpNormItem>));
+  OSD_TRY(pl->scales.upload(s, scales, same_bytes<DpScaleItem>));
+  float* factors = h->dp_norms + h->dp_norms.cap() / 2;
+  OSD_HIP(launch_dp_row_norms(s, pl->norms.dev, (int)pl->norms.kept.size(), rows, (float)unscale, (float)h->dp_clip, h->dp_norms, factors, cond, gather));
+  OSD_HIP(launch_dp_scale_rows(s, pl->scales.dev, (int)pl->scales.kept.size(), rows, factors));
   h->dp_rows = rows;
   pl->cond = cond; pl->gather = gather;
   // a replay reads `cond` again: only while it is the workspace's own copy (a batch source, condition dropout), never a caller's tensor
-  h->dp_replay_ok = cond >= h->train_arena && cond < h->train_arena + h->train_arena_floats;
+  h->dp_replay_ok = cond >= h->train_arena && cond < h->train_arena + h->train_arena.cap();
   return OSD_OK;
 }
 
 void dp_free(osd_handle* h) {
-  hipError_t e = hipSuccess;
-  if (h->dp_plan) {
-    DpPlan* pl = static_cast<DpPlan*>(h->dp_plan);
-    if (pl->d_norms) e = hipFree(pl->d_norms);
-    if (pl->d_scales) e = hipFree(pl->d_scales);
-    delete pl;
-    h->dp_plan = nullptr;
-  }
-  if (h->dp_norms) e = hipFree(h->dp_norms);
-  h->dp_norms = nullptr; h->dp_norms_cap = 0; h->dp_rows = -1;
-  (void)e;
+  delete static_cast<DpPlan*>(h->dp_plan);
+  h->dp_plan = nullptr;
 }
 
 }  // namespace osd
@@ -209,11 +179,11 @@ int osd_dp_replay(osd_handle* h, int which, float fill) {
     return OSD_ESTATE;
   }
   OSD_HIP(hipSetDevice(h->cfg.device));
-  float* factors = h->dp_norms + h->dp_norms_cap;
+  float* factors = h->dp_norms + h->dp_norms.cap() / 2;
   if (which == 0) {
-    OSD_HIP(launch_dp_row_norms(h->stream, pl->d_norms, (int)pl->norms.size(), h->dp_rows, (float)h->dp_rows, (float)h->dp_clip, h->dp_norms, factors, pl->cond, pl->gather));
+    OSD_HIP(launch_dp_row_norms(h->stream, pl->norms.dev, (int)pl->norms.kept.size(), h->dp_rows, (float)h->dp_rows, (float)h->dp_clip, h->dp_norms, factors, pl->cond, pl->gather));
   } else if (which == 1) {
-    OSD_HIP(launch_dp_scale_rows(h->stream, pl->d_scales, (int)pl->scales.size(), h->dp_rows, factors));
+    OSD_HIP(launch_dp_scale_rows(h->stream, pl->scales.dev, (int)pl->scales.kept.size(), h->dp_rows, factors));
   } else if (which == 2) {          // every clip factor = fill
     unsigned bits;
     memcpy(&bits, &fill, sizeof(bits));

@@ -28,8 +28,7 @@ bool split_supported(const Arch& a) {
 }
 
 struct SplitPlan {
-  uint4* w = nullptr;                 // all weight planes, one allocation
-  int64_t units = 0;
+  DevBuf<uint4> w;                    // all weight planes, one allocation
   uint4* w_in = nullptr; uint4* w_out = nullptr;
   std::vector<uint4*> w_layer;        // 2 per block, execution order
 };
@@ -68,12 +67,8 @@ static hipError_t launch_pack(hipStream_t s, const float* src, int ld, int64_t R
 }
 
 void split_free(osd_handle* h) {
-  SplitPlan* p = static_cast<SplitPlan*>(h->split_plan);
-  if (!p) return;
-  if (p->w) { hipError_t e = hipFree(p->w); (void)e; }
-  delete p;
+  delete static_cast<SplitPlan*>(h->split_plan);
   h->split_plan = nullptr;
-  h->split_valid = false;
 }
 
 // weight planes follow the current parameters: rebuilt by the first split-precision call after anything changed them
@@ -86,8 +81,7 @@ int split_pack_weights(osd_handle* h, hipStream_t s) {
     h->split_plan = p;
     int64_t units = b3_units(a.H0, a.D) + b3_units(a.D, a.block_out[a.n_blocks - 1]);
     for (const LayerDesc& l : a.layers) units += b3_units(l.N, l.K1 + l.K2);
-    OSD_TRY(device_alloc((void**)&p->w, (size_t)units * 16));
-    p->units = units;
+    OSD_TRY(p->w.reserve(units));
     int64_t off = 0;
     p->w_in = p->w + off; off += b3_units(a.H0, a.D);
     p->w_layer.clear();
@@ -173,7 +167,7 @@ int split_denoiser_forward(osd_handle* h, const float* x, const int* t_idx, int3
   OSD_TRY(split_pack_weights(h, s));
   SplitWs ws;
   const int64_t need = carve_split(a, nullptr, n, &ws);
-  OSD_TRY(ensure_arena(&h->main, need));
+  OSD_TRY(h->main.arena.reserve(need));
   carve_split(a, h->main.arena, n, &ws);
   OSD_TRY(run_cond(h, s, cond, n, ws.cond));
   OSD_HIP(launch_pack(s, x, a.D, n, a.D, ws.xpl));
@@ -190,7 +184,7 @@ int split_p_sample_step(osd_handle* h, const float* x_t, int32_t t, const float*
   OSD_TRY(split_pack_weights(h, s));
   SplitWs ws;
   const int64_t need = carve_split(a, nullptr, n, &ws);
-  OSD_TRY(ensure_arena(&h->main, need));
+  OSD_TRY(h->main.arena.reserve(need));
   carve_split(a, h->main.arena, n, &ws);
   OSD_TRY(run_cond(h, s, cond, n, ws.cond));
   OSD_HIP(launch_pack(s, x_t, a.D, n, a.D, ws.xpl));
@@ -214,7 +208,7 @@ int split_chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r0
   OSD_TRY(release_graph(sl));
   SplitWs ws;
   const int64_t need = carve_split(a, nullptr, m, &ws);
-  OSD_TRY(ensure_arena(&sl, need));
+  OSD_TRY(sl.arena.reserve(need));
   carve_split(a, sl.arena, m, &ws);
   float* x = job.x_out;
   OSD_TRY(run_cond(h, s, job.cond, m, ws.cond));       // loop-invariant in eval mode: hoisted (api.hip: chain_chunk)
@@ -238,8 +232,8 @@ int split_chain_chunk(osd_handle* h, const ChainJob& whole, Slot& sl, int64_t r0
 int split_op_linear(osd_handle* h, const float* x, const float* w, const float* b, int64_t n, int K, int N, float* y) {
   hipStream_t s = h->stream;
   const int64_t ux = b3_units(n, K), uw = b3_units(N, K);
-  OSD_TRY(ensure_arena(&h->main, (ux + uw) * 4 + 64));
-  uint4* px = reinterpret_cast<uint4*>(h->main.arena);
+  OSD_TRY(h->main.arena.reserve((ux + uw) * 4 + 64));
+  uint4* px = reinterpret_cast<uint4*>(h->main.arena.get());
   uint4* pw = px + ux;
   OSD_HIP(launch_pack(s, x, K, n, K, px));
   OSD_HIP(launch_pack(s, w, K, N, K, pw));

@@ -127,11 +127,7 @@ static int ensure_train_ws(osd_handle* h, hipStream_t s, int64_t n, const ConsPl
   const Arch& a = h->arch;
   const int64_t need = carve_train(a, nullptr, n, cp, w);
   h->dp_replay_ok = false;               // the workspace is about to be carved (and perhaps re-allocated) for another call
-  if (h->train_arena_floats < need) {
-    if (h->train_arena) { OSD_HIP(hipStreamSynchronize(s)); OSD_HIP(hipFree(h->train_arena)); h->train_arena = nullptr; h->train_arena_floats = 0; }
-    OSD_TRY(device_alloc((void**)&h->train_arena, (size_t)need * 4));
-    h->train_arena_floats = need;
-  }
+  OSD_TRY(h->train_arena.reserve(need, s));
   carve_train(a, h->train_arena, n, cp, w);
   return OSD_OK;
 }
@@ -180,7 +176,7 @@ static bool squad_backward(const osd_handle* h, int64_t n, bool want_grads, bool
 // were seen to land on it: their launch-bound hipGraph replays then ran 3.3x slower (bench.py reference_workload: 3700 -> 1130
 // patients/s).  The leaves no longer need the low priority anyway: the grouped weight-gradient launch runs on the main stream.
 static int side_stream(osd_handle* h, hipStream_t* out) {
-  if (!h->wgrad_stream) OSD_HIP(hipStreamCreateWithFlags(&h->wgrad_stream, hipStreamNonBlocking));
+  if (!h->wgrad_stream) OSD_HIP(hipStreamCreateWithFlags(h->wgrad_stream.put(), hipStreamNonBlocking));
   *out = h->wgrad_stream;
   return OSD_OK;
 }
@@ -237,9 +233,9 @@ struct BackwardPass {
 
   int next_event(hipEvent_t* out) {
     if (ev_used == h->ev_pool.size()) {
-      hipEvent_t e;
-      OSD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      h->ev_pool.push_back(e);
+      Event e;
+      OSD_HIP(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+      h->ev_pool.push_back(std::move(e));
     }
     *out = h->ev_pool[ev_used++];
     return OSD_OK;
@@ -685,13 +681,13 @@ struct LossStep {
       x0 = cp ? w.x0_mix : nullptr;
       // condition dropout after the mix: the null condition into the rows that drop theirs, in place (one tiny launch, only when asked for)
       if (cond_drop)
-        OSD_HIP(launch_cond_dropout(s, w.cond_mix, h->d_null_cond + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n,
+        OSD_HIP(launch_cond_dropout(s, w.cond_mix, h->null_cond.dev() + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n,
                                     a.cond_dim, seed, roff, w.cond_mix));
     } else {
       OSD_HIP(launch_q_sample(s, x0, t_draw ? nullptr : t_idx, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, seed, roff, w.x_t, w.noise, t_draw, a.T, w.xld, &zl,
                               h->pred_type, masked));
       if (cond_drop) {       // condition dropout of a caller-supplied batch: the replaced rows land in the workspace
-        OSD_HIP(launch_cond_dropout(s, cond, h->d_null_cond + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n, a.cond_dim,
+        OSD_HIP(launch_cond_dropout(s, cond, h->null_cond.dev() + up64(a.cond_dim), h->cond_drop_keep, h->cond_drop_p, n, a.cond_dim,
                                     seed, roff, w.cond_mix));
         cond = w.cond_mix;
       }
@@ -782,7 +778,7 @@ struct LossStep {
     const int D = a.D;
     const int* t_idx = tc.t_idx;
     OSD_HIP(hipMemcpyAsync(h->parts_dev, loss_out, 4, hipMemcpyDeviceToDevice, s));
-    const float2* pq = reinterpret_cast<const float2*>(h->d_pq);      // x0^ = P x_t + Q out; epsilon keeps its own kernels (their bits)
+    const float2* pq = reinterpret_cast<const float2*>(h->d_pq.get());      // x0^ = P x_t + Q out; epsilon keeps its own kernels (their bits)
     if (h->pred_type == OSD_PRED_EPSILON) OSD_HIP(launch_x0hat(s, w.x_t, t_idx, h->d_sqrt_ac, h->d_sqrt_1m, n, D, w.pred));
     else OSD_HIP(launch_row_affine(s, w.x_t, t_idx, pq, w.pred, n, D, w.pred));
     OSD_HIP(hipMemsetAsync(w.cw.acc, 0, (size_t)w.cw.acc_doubles * 8, s));
@@ -803,7 +799,7 @@ struct LossStep {
     use_me = h->cons.n_a > 0 && h->w_mutexpr != 0.0;
     cp = (use_pw || use_me) && !se_out ? &h->cons : nullptr;      // the row mode scores the raw output alone
     if (cp && n < 2) { set_error("the constraint losses need at least 2 rows"); return OSD_EINVAL; }
-    if (!h->parts_dev) OSD_HIP(hipMalloc((void**)&h->parts_dev, 64));
+    OSD_TRY(h->parts_dev.reserve(16));
     OSD_TRY(ensure_train_ws(h, s, n, cp, &w));
     h->saved_rows = -1;                    // the workspace no longer matches an osd_denoiser_forward_train call
     squads_bwd = w.sq_gact && squad_backward(h, n, grads != nullptr, events != nullptr);
@@ -926,7 +922,7 @@ static int bound_checks(osd_handle* h, const float* x0, const float* cond, int64
 // One launch group of the row mode: n rows, pairs pr.pair0 .. pr.pair0 + n of the grid
 static int bound_group(osd_handle* h, hipStream_t s, const float* x0, const float* cond, int64_t n, const PairRows& pr, const int32_t* t_index,
                        const float* noise, uint64_t seed, uint32_t roff, float* se_out) {
-  if (!h->parts_dev) OSD_HIP(hipMalloc((void**)&h->parts_dev, 64));
+  OSD_TRY(h->parts_dev.reserve(16));
   TrainCall tc{h, n, 0};
   tc.s = s;
   LossStep step{tc, h, h->arch, s, n, x0, cond, noise, nullptr, seed, roff, h->parts_dev + 8, nullptr, 1.0, nullptr, false, false};
@@ -968,12 +964,7 @@ int osd_bound_sweep(osd_handle* h, const float* x0, const float* cond, int64_t n
   hipStream_t s = tc.s;
   h->last_train_path = 0;
   OSD_HIP(hipStreamSynchronize(s));          // an earlier sweep may still read the list
-  if (h->bound_ts_cap < S) {
-    if (h->bound_ts) { OSD_HIP(hipFree(h->bound_ts)); h->bound_ts = nullptr; h->bound_ts_cap = 0; }
-    const int64_t cap = ((int64_t)S + 1023) / 1024 * 1024;
-    OSD_TRY(device_alloc((void**)&h->bound_ts, (size_t)cap * 4));
-    h->bound_ts_cap = cap;
-  }
+  OSD_TRY(h->bound_ts.reserve(((int64_t)S + 1023) / 1024 * 1024));      // 1024-timestep granules
   OSD_HIP(hipMemcpy(h->bound_ts, timesteps_host, (size_t)S * 4, hipMemcpyHostToDevice));
   // groups of at most bound_rows (timestep, patient) pairs, in pair order: the workspace is bounded whatever n x S is, and a group may
   // end in the middle of a timestep's patients
@@ -1079,8 +1070,7 @@ int osd_set_constraints(osd_handle* h, const osd_constraints* c) {
     if (c->pathway_weight < 0 || c->mutexpr_weight < 0) { set_error("constraint weights must be >= 0"); return OSD_EINVAL; }
     OSD_TRY(cons_build_plan(c->pathway_offsets, c->pathway_members, c->n_pathways, c->cols_a, c->n_a, c->cols_b, c->n_b, h->arch.D, &fresh));
   }
-  cons_free_plan(&h->cons);
-  h->cons = fresh;
+  h->cons = std::move(fresh);      // the old plan goes with `fresh`
   h->w_pathway = c ? c->pathway_weight : 0.0;
   h->w_mutexpr = c ? c->mutexpr_weight : 0.0;
   return OSD_OK;
@@ -1100,7 +1090,7 @@ int osd_set_loss(osd_handle* h, int kind, double huber_delta, const float* t_wei
   OSD_HIP(hipSetDevice(h->cfg.device));
   if (h->stream) OSD_HIP(hipStreamSynchronize(h->stream));       // a training call in flight may still read the table
   if (t_weights_host) {
-    if (!h->loss_tw) OSD_HIP(hipMalloc((void**)&h->loss_tw, (size_t)T * sizeof(float)));
+    OSD_TRY(h->loss_tw.reserve(T));
     OSD_HIP(hipMemcpy(h->loss_tw, t_weights_host, (size_t)T * sizeof(float), hipMemcpyHostToDevice));
   }
   h->loss_tw_set = t_weights_host != nullptr;
@@ -1143,7 +1133,7 @@ static int clip_adamw_step(osd_handle* h, hipStream_t stream, int device, double
   if (dp && hp.step > 0xffffffffll) { set_error("step does not fit the 32-bit Philox counter"); return OSD_EINVAL; }
   OSD_HIP(hipSetDevice(h ? h->cfg.device : device));
   if (h) {
-    if (!dp && !h->normsq_dev) OSD_HIP(hipMalloc((void**)&h->normsq_dev, 256 * sizeof(double)));
+    if (!dp) OSD_TRY(h->normsq_dev.reserve(256));
     // the handle's own optimizer is about to change parameters it may hold derived copies of (t_emb table, packed input_proj /
     // output_proj, chain and bf16x3 weight copies): the next forward / sampling entry point refreshes them (api.hip: ensure_packed)
     h->w_packed_stale = true;

@@ -1,4 +1,4 @@
-// val_common.h -- what the validator's translation units (validate.hip, corr.hip, glm.hip) share: the RAII device buffer, the
+// val_common.h -- what the validator's translation units (validate.hip, corr.hip, glm.hip) share: the scope-lifetime device buffer, the
 // wavefront butterflies, the "one wavefront per row" indices, the checked kernel launch, the read-back and the column-list upload.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,12 +7,10 @@
 
 namespace osd {
 
-// A device allocation freed on scope exit.  A request for 0 bytes allocates 16: p is never null after a successful alloc.
-struct DevBuf {
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <class T> T* as() const { return static_cast<T*>(p); }
-  ~DevBuf() { if (p) { hipError_t e = hipFree(p); (void)e; } }
+// A device allocation of bytes, freed on scope exit (devmem.h).  A request for 0 bytes allocates 16: never null after a successful alloc.
+struct ValBuf : DevBuf<char> {
+  int alloc(size_t bytes) { return reserve((int64_t)(bytes ? bytes : 16)); }
+  template <class T> T* as() const { return reinterpret_cast<T*>(get()); }
 };
 
 // Butterflies over the 64 lanes, in place, xor distances 32, 16, ... 1: every lane ends with the result, and the fixed order gives
@@ -58,13 +56,13 @@ inline hipError_t read_back(hipStream_t s, void* host, const void* dev, size_t b
 
 // A host column list, checked (1 <= g <= limit indices in [0, ld)) before anything touches the device; then the device is
 // selected and the list uploaded into dc on the stream.
-inline int upload_cols(int device, hipStream_t s, const int32_t* cols_host, int g, int ld, int limit, DevBuf& dc) {
+inline int upload_cols(int device, hipStream_t s, const int32_t* cols_host, int g, int ld, int limit, ValBuf& dc) {
   if (!cols_host || g < 1 || g > limit) { set_error("bad column list (1 <= columns <= %d)", limit); return OSD_EINVAL; }
   for (int i = 0; i < g; ++i)
     if (cols_host[i] < 0 || cols_host[i] >= ld) { set_error("column index out of range"); return OSD_EINVAL; }
   OSD_HIP(hipSetDevice(device));
-  OSD_HIP(dc.alloc((size_t)g * sizeof(int)));
-  OSD_HIP(hipMemcpyAsync(dc.p, cols_host, (size_t)g * sizeof(int), hipMemcpyHostToDevice, s));
+  OSD_TRY(dc.alloc((size_t)g * sizeof(int)));
+  OSD_HIP(hipMemcpyAsync(dc.get(), cols_host, (size_t)g * sizeof(int), hipMemcpyHostToDevice, s));
   return OSD_OK;
 }
 

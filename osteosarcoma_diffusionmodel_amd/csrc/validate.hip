@@ -161,7 +161,7 @@ struct GramSide { const float* x; int64_t n; float* sq; };    // rows [n][D] and
 
 struct GramPass {
   hipStream_t s = nullptr;
-  DevBuf norms;                                        // (na + nb) floats: nothing here scales with na * nb
+  ValBuf norms;                                        // (na + nb) floats: nothing here scales with na * nb
   GramSide a{}, b{};                                   // a: the tiles' feature side (GemmArgs::A), b: their patient side
   int D = 0;
 
@@ -174,7 +174,7 @@ struct GramPass {
     OSD_HIP(hipSetDevice(device));
     OSD_HIP(prepare_kernels());
     s = (hipStream_t)stream;
-    OSD_HIP(norms.alloc((size_t)(na + nb) * 4));
+    OSD_TRY(norms.alloc((size_t)(na + nb) * 4));
     a = GramSide{A, na, norms.as<float>()};
     b = GramSide{B, nb, norms.as<float>() + na};
     D = D_;
@@ -239,9 +239,9 @@ static int nearest_rows(void* stream, int device, const float* Q, int64_t nq, co
                         int32_t* idx_out, KeysPass keys_pass) {
   GramPass gp;                                         // a = the reference rows, b = the queries
   OSD_TRY(gp.begin(stream, device, R, nr, Q, nq, D));
-  DevBuf keys;                                         // O(nq k + nr): nothing here scales with nq * nr
-  OSD_HIP(keys.alloc((size_t)nq * k * sizeof(unsigned long long)));
-  OSD_HIP(hipMemsetAsync(keys.p, 0xff, (size_t)nq * k * sizeof(unsigned long long), gp.s));  // EpiNearest::NO_KEY, EpiKnn::NO_KEY
+  ValBuf keys;                                         // O(nq k + nr): nothing here scales with nq * nr
+  OSD_TRY(keys.alloc((size_t)nq * k * sizeof(unsigned long long)));
+  OSD_HIP(hipMemsetAsync(keys.get(), 0xff, (size_t)nq * k * sizeof(unsigned long long), gp.s));  // EpiNearest::NO_KEY, EpiKnn::NO_KEY
   OSD_TRY(gp.compute_norms());
   OSD_HIP(keys_pass(gp, keys.as<unsigned long long>()));
   int64_t blocks = (nq * k + 3) / 4;                   // 4 wavefronts per workgroup, one (query, slot) each
@@ -262,8 +262,8 @@ int osd_val_mmd(void* stream, int device, const float* X, int64_t n, const float
   GramPass gp;
   OSD_TRY(gp.begin(stream, device, X, n, Y, m, D));
   constexpr int NS = EpiRbfSum::RBF_SLOTS;
-  DevBuf sums;
-  OSD_HIP(sums.alloc(3 * NS * sizeof(double)));
+  ValBuf sums;
+  OSD_TRY(sums.alloc(3 * NS * sizeof(double)));
   double* d = sums.as<double>();
   OSD_HIP(hipMemsetAsync(d, 0, 3 * NS * sizeof(double), gp.s));
   OSD_TRY(gp.compute_norms(false));                                 // each operand's norms once, for the three passes below
@@ -282,9 +282,9 @@ int osd_val_rbf_sum(void* stream, int device, const float* A, int64_t n, const f
   OSD_TRY(GramPass::check(A, n, B, m, D, sum_out && gamma > 0, "bad argument (gamma must be > 0)"));
   GramPass gp;
   OSD_TRY(gp.begin(stream, device, A, n, B, m, D));
-  DevBuf sums;
-  OSD_HIP(sums.alloc(EpiRbfSum::RBF_SLOTS * sizeof(double)));
-  OSD_HIP(hipMemsetAsync(sums.p, 0, EpiRbfSum::RBF_SLOTS * sizeof(double), gp.s));
+  ValBuf sums;
+  OSD_TRY(sums.alloc(EpiRbfSum::RBF_SLOTS * sizeof(double)));
+  OSD_HIP(hipMemsetAsync(sums.get(), 0, EpiRbfSum::RBF_SLOTS * sizeof(double), gp.s));
   OSD_TRY(gp.compute_norms());                         // one operand: shared norms, the symmetric (triangular) schedule of rbf_sum
   OSD_HIP(rbf_sum(gp, gp.a, gp.b, (float)gamma, sums.as<double>()));
   return rbf_totals(gp, sums.as<double>(), 1, sum_out);
@@ -330,11 +330,11 @@ int osd_val_ks_extremes(void* stream, int device, const float* real, int64_t n1,
   if ((double)n1 * nf > 2.0e9 || (double)n2 * nf > 2.0e9) { set_error("too many items for one segmented sort"); return OSD_EINVAL; }
   OSD_HIP(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  DevBuf cols, sorted, ext, tmp;
+  ValBuf cols, sorted, ext, tmp;
   const size_t na = (size_t)n1 * nf, nb = (size_t)n2 * nf;
-  OSD_HIP(cols.alloc((na + nb) * 4));
-  OSD_HIP(sorted.alloc((na + nb) * 4));
-  OSD_HIP(ext.alloc((size_t)2 * nf * sizeof(long long)));
+  OSD_TRY(cols.alloc((na + nb) * 4));
+  OSD_TRY(sorted.alloc((na + nb) * 4));
+  OSD_TRY(ext.alloc((size_t)2 * nf * sizeof(long long)));
   float* ca = cols.as<float>(); float* cb = ca + na;
   float* sa = sorted.as<float>(); float* sb = sa + na;
   OSD_HIP(launched(k_gather_cols, 2048, 256, 0, s, real, ld, n1, nf, ca));
@@ -342,7 +342,7 @@ int osd_val_ks_extremes(void* stream, int device, const float* real, int64_t n1,
   // four stable 8-bit passes, ping-pong between the two buffers: the sorted floats end up back in `cols`
   {
     const int wps_a = (int)((n1 + SEG_CHUNK - 1) / SEG_CHUNK), wps_b = (int)((n2 + SEG_CHUNK - 1) / SEG_CHUNK);
-    OSD_HIP(tmp.alloc((size_t)nf * 256 * (size_t)(wps_a > wps_b ? wps_a : wps_b) * sizeof(int)));
+    OSD_TRY(tmp.alloc((size_t)nf * 256 * (size_t)(wps_a > wps_b ? wps_a : wps_b) * sizeof(int)));
     int* cnt = tmp.as<int>();
     auto sort_segments = [&](float* buf0, float* buf1, long long n, int wps) -> int {
       uint32_t* a = (uint32_t*)buf0; uint32_t* b = (uint32_t*)buf1;
@@ -381,13 +381,13 @@ int osd_val_col_moments(void* stream, int device, const float* data, int64_t row
                         double* sum_host, double* sumsq_host) {
   if (!data || !sum_host || !sumsq_host || rows < 1) { set_error("bad argument"); return OSD_EINVAL; }
   hipStream_t s = (hipStream_t)stream;
-  DevBuf dc, dm;
+  ValBuf dc, dm;
   OSD_TRY(upload_cols(device, s, cols_host, g, ld, 512, dc));
-  OSD_HIP(dm.alloc((size_t)2 * g * sizeof(double)));
-  OSD_HIP(hipMemsetAsync(dm.p, 0, (size_t)2 * g * sizeof(double), s));
+  OSD_TRY(dm.alloc((size_t)2 * g * sizeof(double)));
+  OSD_HIP(hipMemsetAsync(dm.get(), 0, (size_t)2 * g * sizeof(double), s));
   OSD_HIP(launched(k_col_moments<8>, col_blocks(rows), 256, 0, s, data, ld, rows, dc.as<const int>(), g, dm.as<double>(), dm.as<double>() + g));
   std::vector<double> hm((size_t)2 * g);
-  OSD_HIP(read_back(s, hm.data(), dm.p, (size_t)2 * g * sizeof(double)));
+  OSD_HIP(read_back(s, hm.data(), dm.get(), (size_t)2 * g * sizeof(double)));
   for (int i = 0; i < g; ++i) { sum_host[i] = hm[i]; sumsq_host[i] = hm[g + i]; }
   return OSD_OK;
 }
@@ -396,9 +396,9 @@ int osd_val_rowz_sq(void* stream, int device, const float* data, int64_t rows, i
                     const double* isd_host, double* S_host) {
   if (!data || !mu_host || !isd_host || !S_host || rows < 1) { set_error("bad argument"); return OSD_EINVAL; }
   hipStream_t s = (hipStream_t)stream;
-  DevBuf dc, dm;
+  ValBuf dc, dm;
   OSD_TRY(upload_cols(device, s, cols_host, g, ld, 512, dc));
-  OSD_HIP(dm.alloc((size_t)(2 * g + 1) * sizeof(double)));
+  OSD_TRY(dm.alloc((size_t)(2 * g + 1) * sizeof(double)));
   double* mu = dm.as<double>(); double* isd = mu + g; double* S = isd + g;
   OSD_HIP(hipMemcpyAsync(mu, mu_host, (size_t)g * sizeof(double), hipMemcpyHostToDevice, s));
   OSD_HIP(hipMemcpyAsync(isd, isd_host, (size_t)g * sizeof(double), hipMemcpyHostToDevice, s));
@@ -429,27 +429,27 @@ int osd_val_column_sums(void* stream, int device, const float* x, int64_t rows, 
   if (!x || !sums_host || rows < 1 || cols < 1 || ld < cols) { set_error("bad argument"); return OSD_EINVAL; }
   OSD_HIP(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  DevBuf d;
-  OSD_HIP(d.alloc((size_t)2 * cols * sizeof(double)));
-  OSD_HIP(hipMemsetAsync(d.p, 0, (size_t)2 * cols * sizeof(double), s));
+  ValBuf d;
+  OSD_TRY(d.alloc((size_t)2 * cols * sizeof(double)));
+  OSD_HIP(hipMemsetAsync(d.get(), 0, (size_t)2 * cols * sizeof(double), s));
   OSD_HIP(cons_column_sums(s, x, ld, rows, cols, d.as<double>()));
-  OSD_HIP(read_back(s, sums_host, d.p, (size_t)cols * sizeof(double)));
+  OSD_HIP(read_back(s, sums_host, d.get(), (size_t)cols * sizeof(double)));
   return OSD_OK;
 }
 
 int osd_val_gram(void* stream, int device, const float* x, int64_t rows, int ld, const int32_t* cols_host, int g, double* gram_host) {
   if (!x || !gram_host || rows < 1) { set_error("bad argument"); return OSD_EINVAL; }
   hipStream_t s = (hipStream_t)stream;
-  DevBuf dc, dm, dC;
+  ValBuf dc, dm, dC;
   OSD_TRY(upload_cols(device, s, cols_host, g, ld, CONS_MAX_SET, dc));
-  OSD_HIP(dm.alloc((size_t)ld * sizeof(float2)));
-  OSD_HIP(dC.alloc((size_t)CONS_MAX_SET * CONS_MAX_SET * sizeof(double)));
+  OSD_TRY(dm.alloc((size_t)ld * sizeof(float2)));
+  OSD_TRY(dC.alloc((size_t)CONS_MAX_SET * CONS_MAX_SET * sizeof(double)));
   std::vector<float2> ident((size_t)ld, make_float2(0.f, 1.f));            // no standardisation: raw products
-  OSD_HIP(hipMemcpyAsync(dm.p, ident.data(), (size_t)ld * sizeof(float2), hipMemcpyHostToDevice, s));
-  OSD_HIP(hipMemsetAsync(dC.p, 0, (size_t)CONS_MAX_SET * CONS_MAX_SET * sizeof(double), s));
+  OSD_HIP(hipMemcpyAsync(dm.get(), ident.data(), (size_t)ld * sizeof(float2), hipMemcpyHostToDevice, s));
+  OSD_HIP(hipMemsetAsync(dC.get(), 0, (size_t)CONS_MAX_SET * CONS_MAX_SET * sizeof(double), s));
   OSD_HIP(cons_gram(s, x, ld, rows, dc.as<const int>(), g, dc.as<const int>(), g, dm.as<const float2>(), dC.as<double>()));
   std::vector<double> full((size_t)CONS_MAX_SET * CONS_MAX_SET);
-  OSD_HIP(read_back(s, full.data(), dC.p, full.size() * sizeof(double)));
+  OSD_HIP(read_back(s, full.data(), dC.get(), full.size() * sizeof(double)));
   for (int i = 0; i < g; ++i)
     for (int j = 0; j < g; ++j) gram_host[(size_t)i * g + j] = full[(size_t)i * CONS_MAX_SET + j];
   return OSD_OK;
@@ -459,13 +459,13 @@ int osd_val_pearson_sums(void* stream, int device, const float* a, int lda, cons
   if (!a || !b || !out5_host || rows < 1) { set_error("bad argument"); return OSD_EINVAL; }
   OSD_HIP(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  DevBuf d;
-  OSD_HIP(d.alloc(5 * sizeof(double)));
-  OSD_HIP(hipMemsetAsync(d.p, 0, 5 * sizeof(double), s));
+  ValBuf d;
+  OSD_TRY(d.alloc(5 * sizeof(double)));
+  OSD_HIP(hipMemsetAsync(d.get(), 0, 5 * sizeof(double), s));
   int blocks = (int)((rows + 255) / 256);
   if (blocks > 1024) blocks = 1024;
   OSD_HIP(launched(k_pearson_sums, blocks, 256, 0, s, a, lda, b, ldb, rows, d.as<double>()));
-  OSD_HIP(read_back(s, out5_host, d.p, 5 * sizeof(double)));
+  OSD_HIP(read_back(s, out5_host, d.get(), 5 * sizeof(double)));
   return OSD_OK;
 }
 

@@ -47,26 +47,15 @@ bool wgrad_group_ok(const WgPending& w) {
 }
 
 struct WgPlanDev {
-  std::vector<WgItem> items;
-  std::vector<WgReduce> reds;
-  WgItem* d_items = nullptr; size_t cap_items = 0;
-  WgReduce* d_reds = nullptr; size_t cap_reds = 0;
-  std::vector<GnColItem> cols;
-  GnColItem* d_cols = nullptr; size_t cap_cols = 0;
+  DevList<WgItem> items;
+  DevList<WgReduce> reds;
+  DevList<GnColItem> cols;
 };
 
 static bool g_wg_attr[16] = {};
 
 void wgrad_group_free(osd_handle* h) {
-  for (void* p : h->wg_plans) {
-    WgPlanDev* pl = static_cast<WgPlanDev*>(p);
-    hipError_t e = hipSuccess;
-    if (pl->d_items) e = hipFree(pl->d_items);
-    if (pl->d_reds) e = hipFree(pl->d_reds);
-    if (pl->d_cols) e = hipFree(pl->d_cols);
-    (void)e;
-    delete pl;
-  }
+  for (void* p : h->wg_plans) delete static_cast<WgPlanDev*>(p);
   h->wg_plans.clear();
 }
 
@@ -83,25 +72,7 @@ static bool same(const GnColItem& a, const GnColItem& b) {
   return a.gy == b.gy && a.ldy == b.ldy && a.z == b.z && a.ldz == b.ldz && a.stats == b.stats && a.C == b.C && a.gw == b.gw && a.rows == b.rows &&
          a.dgamma == b.dgamma && a.dbeta == b.dbeta;
 }
-
-template <class V, class D>
-static int upload(hipStream_t s, const V& fresh, V& kept, D** dev, size_t* cap) {
-  typedef typename V::value_type E;
-  bool unchanged = fresh.size() == kept.size() && *dev;
-  for (size_t i = 0; unchanged && i < fresh.size(); ++i) unchanged = same(fresh[i], kept[i]);
-  if (unchanged) return OSD_OK;
-  OSD_HIP(hipStreamSynchronize(s));            // rare (first step, or the batch / tensors changed): the old list may still be in use
-  if (*cap < fresh.size()) {
-    if (*dev) OSD_HIP(hipFree(*dev));
-    *dev = nullptr; *cap = 0;
-    const size_t want = std::max<size_t>(fresh.size(), 64);
-    if (hipMalloc((void**)dev, want * sizeof(E)) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc failed"); return OSD_ENOMEM; }
-    *cap = want;
-  }
-  kept = fresh;
-  if (!kept.empty()) OSD_HIP(hipMemcpyAsync(*dev, kept.data(), kept.size() * sizeof(E), hipMemcpyHostToDevice, s));
-  return OSD_OK;
-}
+static const auto same_fields = [](const auto& a, const auto& b) { return same(a, b); };
 
 // Launch every pending weight gradient as one grouped GEMM (+ one slab reduction) on stream s.
 // max_grid > 0: at most that many workgroups walk the list (one slot per CU stays free for the kernels of another stream)
@@ -152,16 +123,16 @@ int wgrad_group_flush(osd_handle* h, hipStream_t s, int plan_index, const std::v
   // (tensor, row range), which read the same rows of x and gz, on workgroup indices congruent mod 8 so that they share an L2: 204 vs
   // 205 us; the launch is not waiting for its operands.)
   std::stable_sort(items.begin(), items.end(), [](const WgItem& a, const WgItem& b) { return (a.k1 - a.k0) > (b.k1 - b.k0); });
-  OSD_TRY(upload(s, items, pl->items, &pl->d_items, &pl->cap_items));
-  OSD_TRY(upload(s, reds, pl->reds, &pl->d_reds, &pl->cap_reds));
-  const int n_items = (int)pl->items.size();
+  OSD_TRY(pl->items.upload(s, items, same_fields));
+  OSD_TRY(pl->reds.upload(s, reds, same_fields));
+  const int n_items = (int)pl->items.kept.size();
   const int grid = max_grid > 0 ? std::min(n_items, max_grid) : n_items;
   // precision 1 (bf16x3 split, gemm_bf3.h): the same items with both operands split into bf16 planes as they are staged
-  if (h->precision == 1) hipLaunchKernelGGL(wgrad_group_kernel<1>, dim3((unsigned)grid), dim3(NTHREADS), WG3_LDS_BYTES, s, pl->d_items, n_items);
-  else hipLaunchKernelGGL(wgrad_group_kernel<0>, dim3((unsigned)grid), dim3(NTHREADS), WG_LDS_BYTES, s, pl->d_items, n_items);
+  if (h->precision == 1) hipLaunchKernelGGL(wgrad_group_kernel<1>, dim3((unsigned)grid), dim3(NTHREADS), WG3_LDS_BYTES, s, pl->items.dev.get(), n_items);
+  else hipLaunchKernelGGL(wgrad_group_kernel<0>, dim3((unsigned)grid), dim3(NTHREADS), WG_LDS_BYTES, s, pl->items.dev.get(), n_items);
   OSD_HIP(hipGetLastError());
-  if (!pl->reds.empty()) {
-    hipLaunchKernelGGL(wgrad_group_reduce, dim3(64, (unsigned)pl->reds.size()), dim3(256), 0, s, pl->d_reds);
+  if (!pl->reds.kept.empty()) {
+    hipLaunchKernelGGL(wgrad_group_reduce, dim3(64, (unsigned)pl->reds.kept.size()), dim3(256), 0, s, pl->reds.dev.get());
     OSD_HIP(hipGetLastError());
   }
   return OSD_OK;
@@ -172,10 +143,10 @@ int gn_colsums_flush(osd_handle* h, hipStream_t s, int plan_index, const std::ve
   if (cols.empty()) return OSD_OK;
   while ((int)h->wg_plans.size() <= plan_index) h->wg_plans.push_back(new WgPlanDev());
   WgPlanDev* pl = static_cast<WgPlanDev*>(h->wg_plans[plan_index]);
-  OSD_TRY(upload(s, cols, pl->cols, &pl->d_cols, &pl->cap_cols));
+  OSD_TRY(pl->cols.upload(s, cols, same_fields));
   int64_t max_rows = 0;
   for (const GnColItem& c : cols) max_rows = std::max(max_rows, c.rows);
-  OSD_HIP(launch_gn_colsums(s, pl->d_cols, (int)pl->cols.size(), max_rows));
+  OSD_HIP(launch_gn_colsums(s, pl->cols.dev, (int)pl->cols.kept.size(), max_rows));
   return OSD_OK;
 }
 

@@ -1,6 +1,7 @@
 """GPU: boundary hygiene (round-1 review): resume of the fused optimizer, cVAE generation through the generator, the
 osd_create failure path, the 32-bit row id space, timestep range errors, the library's RCCL entry points on a
-single-rank communicator."""
+single-rank communicator; and what a handle owns on the device: a used handle gives everything back, a buffer that grows is
+reused safely, back-to-back uploads keep their tables."""
 import ctypes as C
 import copy
 
@@ -216,3 +217,279 @@ def test_rccl_entry_points_single_rank():
     finally:
         rh.close()
         assert lib.osd_comm_destroy(comm) == L.OSD_OK
+
+
+# ---- handle-owned device memory (csrc/devmem.h), through the C ABI alone -----------------------------------------------------
+# An architecture every engine accepts -- the three chain kernels, the training squads, bf16x3, the per-row clip: hidden [256, 512, 256],
+# 3 conditions, dims 8 / 504 / 8.  The LDS-resident chain needs a state of at least 512 columns and the squad chain one of at least
+# 225 (chain_panel.hip, chain_squad.hip: make_plan), so the suite's small dims 8 / 24 / 8 would leave both legs out.
+HY_H = (256, 512, 256)
+HY_DIMS, HY_D, HY_CD = (8, 504, 8), 520, 3
+_SCHED = {}
+
+
+def _hy_cfg(T):
+    cfg = L.OsdConfig()
+    cfg.mutation_dim, cfg.expression_dim, cfg.pathway_dim, cfg.condition_dim = *HY_DIMS, HY_CD
+    cfg.time_dim, cfg.n_hidden, cfg.dropout_p, cfg.device = 128, 3, 0.0, torch.cuda.current_device()
+    for i, v in enumerate(HY_H):
+        cfg.hidden_dims[i] = v
+    cfg.num_steps = T
+    return cfg
+
+
+def _hy_schedule(T):
+    """sqrt_ac [T], sqrt_1m_ac [T], post_coef [T][6] (oracle.posterior_coefficients' columns), time_emb [T][128]: whole-array numpy,
+    a linear beta schedule whose abar stays well inside (0, 1) for any T."""
+    if T not in _SCHED:
+        betas = np.linspace(1e-6, 6.0 / T, T)
+        abar = np.cumprod(1.0 - betas)
+        abp = np.concatenate([[1.0], abar[:-1]])
+        pc = np.zeros((T, 6))
+        pc[:, 0], pc[:, 1], pc[:, 3] = np.sqrt(1 - abar), np.sqrt(abar), 1 - abar
+        pc[1:, 2] = (np.sqrt(abp) * betas)[1:]
+        pc[1:, 4] = (np.sqrt(1 - betas) * (1 - abp))[1:]
+        pc[1:, 5] = np.sqrt((1 - abp) / (1 - abar) * betas)[1:]
+        arg = (np.arange(T) / T)[:, None] * np.exp(-np.log(10000.0) * np.arange(64) / 63)[None, :]
+        f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+        _SCHED[T] = (f32(np.sqrt(abar)), f32(np.sqrt(1 - abar)), f32(pc), f32(np.concatenate([np.sin(arg), np.cos(arg)], axis=1)))
+    return _SCHED[T]
+
+
+def _hy_params():
+    """One flat parameter buffer (every tensor 16-byte aligned: all sizes are multiples of 4) and the tensors as views of it."""
+    lib, cfg = L.lib(), _hy_cfg(8)
+    numel = [lib.osd_param_numel(C.byref(cfg), i) for i in range(lib.osd_num_params(C.byref(cfg)))]
+    flat = torch.randn(sum(numel), generator=torch.Generator().manual_seed(11)).mul_(0.05).cuda()
+    return flat, list(flat.split(numel))
+
+
+class _Hy:
+    """A handle with schedule and weights, on torch's current stream."""
+
+    def __init__(self, T, params):
+        self.lib, self.h = L.lib(), C.c_void_p()
+        cfg = _hy_cfg(T)
+        L.check(self.lib.osd_create(C.byref(cfg), C.byref(self.h)))
+        try:
+            L.check(self.lib.osd_set_stream(self.h, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            L.check(self.lib.osd_set_schedule(self.h, *[a.ctypes.data for a in _hy_schedule(T)]))
+            L.check(self.lib.osd_load_weights(self.h, L.ptr_array(params), len(params)))
+        except Exception:
+            self.close()
+            raise
+
+    def set(self, **opts):
+        for k, v in opts.items():
+            L.check(self.lib.osd_set_option(self.h, k.encode(), v))
+
+    def get(self, name):
+        v = C.c_int64()
+        L.check(self.lib.osd_get_option(self.h, name.encode(), C.byref(v)))
+        return v.value
+
+    def close(self):
+        if self.h:
+            L.check(self.lib.osd_destroy(self.h))
+            self.h = C.c_void_p()
+
+
+def _hy_plan(T, S=4, k=0):
+    """An S-step plan (S <= 4 keeps every chain short) and the tables of every kind of chain; k varies the numbers."""
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    s = np.arange(S)
+    ts = np.ascontiguousarray(s * (T - 1) // max(S - 1, 1), dtype=np.int32)
+    coef = f32(np.stack([1 - 0.01 * s, -0.1 - 0.01 * (s + k), 0.05 * (s > 0), 0 * s], axis=1))
+    x0c = f32(np.stack([1 + 0.01 * (s + k), -0.1 - 0.02 * s, np.where(s == 0, 1.0, 0.9 - 0.01 * k), np.where(s == 0, 0.0, 0.1 + 0.01 * k)], axis=1))
+    lvl = f32(np.stack([np.where(s == 0, 1.0, 0.95 - 0.02 * (s + k)), np.where(s == 0, 0.0, 0.2 + 0.03 * (s + k))], axis=1))
+    hist = f32(np.where((s == 0) | (s == S - 1), 0.0, 0.1 + 0.05 * k))
+    return ts, coef, x0c, lvl, hist
+
+
+def _hy_train(hy, W, n, seed=3):
+    lib = hy.lib
+    L.check(lib.osd_train_loss_fwd_bwd(hy.h, L.ptr(W["x"]), L.ptr(W["cond"]), n, None, None, None, seed, 0, L.OSD_F_TRAIN_MODE, L.ptr(W["loss"]),
+                                       W["grad_ptrs"], 1.0, None, 0))
+
+
+def _hy_cycle(W, T, skipped):
+    """One life of a handle that touches every lazily allocated resource."""
+    hy = _Hy(T, W["params"])
+    lib, h = hy.lib, hy.h
+    n, D, S = 64, HY_D, 4
+    ts, coef, x0c, lvl, hist = _hy_plan(T)
+    p = lambda a: a.ctypes.data
+    null, lo, hi = W["null"], W["lo"], W["hi"]
+    head = lambda rows: (h, L.ptr(W["cond"]), rows, None, None, 5, 0, L.ptr(W["out"]), None)
+    try:
+        L.check(lib.osd_sample_chain_guided(*head(n), 0, p(ts), p(coef), S, p(null), 2.0))
+        L.check(lib.osd_sample_chain_known(*head(n), 0, p(ts), p(coef), p(lvl), S, None, 1.0, L.ptr(W["known"]), D))
+        L.check(lib.osd_sample_chain_clipped(*head(n), 0, p(ts), p(coef), p(x0c), None, S, None, 1.0, None, 0, p(lo), p(hi)))
+        L.check(lib.osd_sample_chain_multistep(*head(n), 0, p(ts), p(x0c), p(hist), None, S, None, 1.0, None, 0, None, None))
+        hy.set(sampler=2, n_streams=2, chunk_rows=128)       # two chunks on two slot streams, each step captured and replayed
+        L.check(lib.osd_sample_chain_steps(*head(256), L.OSD_F_GRAPH, p(ts), p(coef), S))
+        for variant, name, rows, ok in ((1, "workspace chain", 256, True), (2, "LDS-resident chain", 256, hy.get("panel_chain_supported")),
+                                        (3, "squad chain", 64, hy.get("squad_chain_supported"))):
+            hy.set(sampler=1, chain_variant=variant)
+            if ok:
+                L.check(lib.osd_sample_chain_steps(*head(rows), 0, p(ts), p(coef), S))
+            if not ok or (lib.osd_sample_engine(h, -1, 0), hy.get("last_chain_variant")) != (1, variant):
+                skipped.add(name)
+        hy.set(sampler=0, chain_variant=0)
+        if hy.get("split_supported"):
+            hy.set(precision=1)
+            L.check(lib.osd_sample_chain_steps(*head(n), 0, p(ts), p(coef), S))
+            L.check(lib.osd_denoiser_forward(h, L.ptr(W["x"]), None, 1, L.ptr(W["cond"]), n, L.ptr(W["out"]), 0, None, 0))
+            if hy.get("last_precision") != 1:
+                skipped.add("bf16x3")
+            hy.set(precision=0)
+        else:
+            skipped.add("bf16x3")
+        # training: a loss-weight table, condition dropout, the side stream, the forward and backward as squads and as per-layer launches
+        L.check(lib.osd_set_loss(h, L.OSD_LOSS_L2, 1.0, p(W["tw"])))
+        hy.set(train_streams=2)
+        for squad in (2, 0):
+            hy.set(train_squad=squad)
+            L.check(lib.osd_train_condition_dropout(h, p(null), 0.5, None))
+            _hy_train(hy, W, 2048)
+        L.check(lib.osd_clip_adamw_step(h, L.ptr(W["flat"]), L.ptr(W["grad"]), L.ptr(W["m"]), L.ptr(W["v"]), W["flat"].numel(), 0.0, 0.9, 0.999,
+                                        1e-8, 0.0, 1.0, 1, None))
+        L.check(lib.osd_set_loss(h, L.OSD_LOSS_L2, 1.0, None))
+        L.check(lib.osd_set_dp_clip(h, 1.0))
+        _hy_train(hy, W, 256)
+        L.check(lib.osd_set_dp_clip(h, 0.0))
+        L.check(lib.osd_bound_sweep(h, L.ptr(W["x"]), L.ptr(W["cond"]), n, ts.ctypes.data_as(C.POINTER(C.c_int32)), S, None, 7, 0, L.ptr(W["se"])))
+        L.check(lib.osd_denoiser_forward(h, L.ptr(W["x"]), L.ptr(W["t"]), 0, L.ptr(W["cond"]), n, L.ptr(W["out"]), 0, None, 0))
+        torch.cuda.synchronize()
+    finally:
+        hy.close()
+
+
+def _hy_tensors(T):
+    g = torch.Generator().manual_seed(2)
+    flat, params = _hy_params()
+    W = {"flat": flat, "params": params, "grad": torch.zeros_like(flat), "m": torch.zeros_like(flat), "v": torch.zeros_like(flat),
+         "x": torch.randn(3000, HY_D, generator=g).cuda(), "cond": torch.randn(3000, HY_CD, generator=g).cuda(),
+         "out": torch.empty(3000, HY_D, device="cuda"), "loss": torch.zeros(1, device="cuda"), "se": torch.empty(4 * 64, device="cuda"),
+         "t": torch.randint(0, T, (3000,), generator=g).to(torch.int32).cuda(),
+         "null": np.zeros(HY_CD, dtype=np.float32), "lo": np.full(HY_D, -1.0, dtype=np.float32), "hi": np.full(HY_D, 1.0, dtype=np.float32),
+         "tw": np.ones(T, dtype=np.float32)}
+    known = torch.randn(3000, HY_D, generator=g)
+    known[:, ::3] = float("nan")
+    W["known"] = known.cuda()
+    W["grad_ptrs"] = L.ptr_array(list(W["grad"].split([q.numel() for q in params])))
+    return W
+
+
+HY_LEAK_T = 262_144               # the smallest lazily allocated table (the history coefficients, T floats) is then 1 MiB
+HY_LEAK_CYCLES = 6
+# Free device memory after the last cycle against free memory after the second.  Measured on one MI355X in one session, 6 cycles:
+# the library before devmem.h (hand-kept release lists) drifts by 0 bytes, this one by 0 bytes; hipMemGetInfo moved in steps of 2 MiB.
+# The tolerance is one such step: at least twice the earlier library's drift, and below (cycles - 2) x 1 MiB = 4 MiB, what one table
+# leaked per cycle costs at the least.  A library whose destructor drops the release of the 1 MiB history-coefficient table alone
+# drifts by 6 291 456 bytes and fails.
+HY_LEAK_TOL = 2 << 20
+
+
+def test_used_handle_gives_everything_back():
+    """osd_destroy returns what a handle allocated lazily: every sampler engine, every uploader, the training workspaces and plans
+    (_hy_cycle lists the legs; one that could not run fails the test by name).  Schedule and weights come from numpy / one flat
+    tensor, every chain carries a 4-step plan, and all torch tensors exist before the first measurement.  The expression block is
+    504 wide, not the suite's 24: below a 512-column state the LDS-resident chain, and below 225 the squad chain, do not exist."""
+    T = HY_LEAK_T
+    W = _hy_tensors(T)
+    skipped, free = set(), []
+    for _ in range(HY_LEAK_CYCLES):
+        _hy_cycle(W, T, skipped)
+        torch.cuda.synchronize()
+        free.append(torch.cuda.mem_get_info()[0])
+    drift = free[1] - free[-1]
+    print(f"free memory after each cycle, relative to the first: {[f - free[0] for f in free]}; drift after cycle 2: {drift} bytes")
+    assert not skipped, f"legs that did not run at {HY_H}: {sorted(skipped)}"
+    assert drift <= HY_LEAK_TOL, f"a used handle leaks: free memory fell by {drift} bytes over {HY_LEAK_CYCLES - 2} create / use / destroy cycles"
+
+
+def _grow_calls(case, hy, W, size, out):
+    """One call of `case` at `size` on hy, its result into out (no synchronisation)."""
+    lib, h, T = hy.lib, hy.h, 16
+    ts, coef, _, _, _ = _hy_plan(T)
+    p = lambda a: a.ctypes.data
+    if case == "t_san":          # the clamped copy of caller-supplied timesteps (some out of range)
+        L.check(lib.osd_q_sample(h, L.ptr(W["x"]), L.ptr(W["t_wild"]), L.ptr(W["cond_as_noise"]), size, 0, 0, L.ptr(out), None))
+    elif case == "dp_norms":
+        L.check(lib.osd_set_dp_clip(h, 1.0))
+        _hy_train(hy, W, size)
+        L.check(lib.osd_dp_row_norms(h, L.ptr(out), size))
+    elif case == "bound_ts":     # size timesteps x 2 patients
+        tl = np.ascontiguousarray(np.arange(size) % T, dtype=np.int32)
+        L.check(lib.osd_bound_sweep(h, L.ptr(W["x"]), L.ptr(W["cond"]), 2, tl.ctypes.data_as(C.POINTER(C.c_int32)), size, None, 7, 0, L.ptr(out)))
+    else:
+        opts = {"slot_arena": dict(sampler=2), "chain_ws1": dict(sampler=1, chain_variant=1), "chain_ws2": dict(sampler=1, chain_variant=2),
+                "chain_ws3": dict(sampler=1, chain_variant=3)}[case]
+        hy.set(**opts)
+        L.check(lib.osd_sample_chain_steps(h, L.ptr(W["cond"]), size, None, None, 5, 0, L.ptr(out), None, 0, p(ts), p(coef), 4))
+        print(f"{case} at {size} rows: engine {lib.osd_sample_engine(h, -1, 0)}, chain variant {hy.get('last_chain_variant')}")
+
+
+@pytest.mark.parametrize("case,sizes", [("t_san", (1000, 3000, 1000)), ("dp_norms", (1000, 3000, 1000)), ("bound_ts", (4, 1500, 4)),
+                                        ("slot_arena", (64, 640, 64)), ("chain_ws1", (128, 1280, 128)), ("chain_ws2", (64, 640, 64)),
+                                        ("chain_ws3", (32, 256, 32))])
+def test_buffer_grows_then_is_reused(case, sizes):
+    """small, large, small on one handle with no synchronisation of the caller's: the re-allocation must wait for the work that
+    still uses the old buffer, and the small call after it must find a valid one.  Bits against the same calls on fresh handles."""
+    W = _hy_tensors(16)
+    W["t_wild"] = (W["t"] * 3 - 8).contiguous()                 # some outside [0, 16)
+    W["cond_as_noise"] = torch.randn(3000, HY_D, generator=torch.Generator().manual_seed(4)).cuda()
+    outs = [torch.zeros(3000 * HY_D, device="cuda") for _ in sizes]
+    hy = _Hy(16, W["params"])
+    try:
+        for size, out in zip(sizes, outs):
+            _grow_calls(case, hy, W, size, out)
+        torch.cuda.synchronize()
+    finally:
+        hy.close()
+    for size, out in zip(sizes, outs):
+        fresh, want = _Hy(16, W["params"]), torch.zeros_like(out)
+        try:
+            _grow_calls(case, fresh, W, size, want)
+            torch.cuda.synchronize()
+        finally:
+            fresh.close()
+        assert torch.isfinite(want).all() and want.abs().sum() > 0
+        assert torch.equal(out, want), f"{case}: the call at size {size} differs from a fresh handle's"
+
+
+def test_back_to_back_uploads_keep_their_tables():
+    """Two clipped multistep chains around known values, guided, queued on one handle with nothing between them: they differ in every
+    uploaded table (x0_coef, hist_coef, known_level, bounds, the null condition), so the second call's uploads must not overwrite the
+    staging or the device tables that the first still reads.  Bits against the same two calls on two fresh handles."""
+    T, n, S = 16, 200, 4
+    W = _hy_tensors(T)
+    p = lambda a: a.ctypes.data
+
+    def call(hy, k, out):
+        ts, _, x0c, lvl, hist = _hy_plan(T, S, k)
+        null = np.full(HY_CD, 0.25 * k, dtype=np.float32)
+        lo, hi = np.full(HY_D, -1.0 - k, dtype=np.float32), np.full(HY_D, 0.5 + k, dtype=np.float32)
+        L.check(hy.lib.osd_sample_chain_multistep(hy.h, L.ptr(W["cond"]), n, None, None, 5, 0, L.ptr(out), None, 0, p(ts), p(x0c), p(hist), p(lvl), S,
+                                                  p(null), 1.5 + k, L.ptr(W["known"]), HY_D, p(lo), p(hi)))
+
+    got = [torch.zeros(n, HY_D, device="cuda") for _ in range(2)]
+    hy = _Hy(T, W["params"])
+    try:
+        for k in range(2):
+            call(hy, k, got[k])
+        torch.cuda.synchronize()
+    finally:
+        hy.close()
+    assert not torch.equal(got[0], got[1])
+    for k in range(2):
+        fresh, want = _Hy(T, W["params"]), torch.zeros(n, HY_D, device="cuda")
+        try:
+            call(fresh, k, want)
+            torch.cuda.synchronize()
+        finally:
+            fresh.close()
+        free = ~torch.isnan(W["known"][:n])
+        assert torch.isfinite(want).all() and (want[free].abs() > 0).any()
+        assert torch.equal(got[k], want), f"call {k} differs from the same call on a fresh handle"
