@@ -828,8 +828,9 @@ int osd_nn_bn_relu_dropout_bwd(void *stream, int device, const float *gy, const 
  * normals, written to eps_out when it is not NULL. */
 int osd_nn_reparameterize(void *stream, int device, const float *mu, const float *logvar, const float *eps_in,
                           uint64_t seed, int64_t n, int Lz, float *z, float *eps_out);
-/* Backward of reparameterize: d_logvar = 0.5 * gz * (z - mu)   (d_mu is gz itself). */
-int osd_nn_reparameterize_bwd(void *stream, int device, const float *gz, const float *mu, const float *z,
+/* Backward of reparameterize: d_logvar = 0.5 * gz * eps * exp(0.5 * logvar)   (d_mu is gz itself).  eps is the noise the
+ * forward used (eps_in, or what it wrote to eps_out); it is never recovered as z - mu, which cancels when |mu| >> std. */
+int osd_nn_reparameterize_bwd(void *stream, int device, const float *gz, const float *eps, const float *logvar,
                               int64_t count, float *d_logvar);
 /* VAE loss (models/cvae.py:178-181): parts3 (dev float[3]) = (recon + kl, recon, kl) with
  * recon = sum (x_recon - x)^2 / n, kl = -0.5 sum(1 + logvar - mu^2 - exp(logvar)) / n, and their

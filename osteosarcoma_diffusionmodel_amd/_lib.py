@@ -145,7 +145,7 @@ _SIGNATURES = {
     "osd_nn_bn_relu_dropout_bwd": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P,
                                              C.c_uint64, C.c_uint32, _P, _P, _P]),
     "osd_nn_reparameterize": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_uint64, C.c_int64, C.c_int, _P, _P]),
-    "osd_nn_reparameterize_bwd": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P]),
+    "osd_nn_reparameterize_bwd": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P]),      # (stream, device, gz, eps, logvar, count, d_logvar)
     "osd_nn_clip_adamw_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_double, C.c_double, C.c_int64, _P]),
     "osd_nn_clip_adamw_ema_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,

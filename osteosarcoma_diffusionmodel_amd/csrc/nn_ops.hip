@@ -128,9 +128,10 @@ __global__ void k_reparam(const float* mu, const float* logvar, const float* eps
   }
 }
 
-__global__ void k_reparam_bwd(const float* gz, const float* mu, const float* z, int64_t count, float* d_lv) {
+// d_lv = 0.5 gz eps exp(0.5 lv): from eps and logvar, never as z - mu (that difference cancels once |mu| >> std)
+__global__ void k_reparam_bwd(const float* gz, const float* eps, const float* logvar, int64_t count, float* d_lv) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)
-    d_lv[i] = 0.5f * gz[i] * (z[i] - mu[i]);
+    d_lv[i] = 0.5f * gz[i] * (eps[i] * expf(0.5f * logvar[i]));
 }
 
 // parts[1] += sum (xr - x)^2 / n ; parts[2] += -0.5 sum(1 + lv - mu^2 - exp(lv)) / n ; parts[0] = their sum
@@ -308,10 +309,10 @@ int osd_nn_reparameterize(void* stream, int device, const float* mu, const float
   return OSD_OK;
 }
 
-int osd_nn_reparameterize_bwd(void* stream, int device, const float* gz, const float* mu, const float* z, int64_t count, float* d_logvar) {
-  if (!gz || !mu || !z || !d_logvar || count < 1) { set_error("bad argument"); return OSD_EINVAL; }
+int osd_nn_reparameterize_bwd(void* stream, int device, const float* gz, const float* eps, const float* logvar, int64_t count, float* d_logvar) {
+  if (!gz || !eps || !logvar || !d_logvar || count < 1) { set_error("bad argument"); return OSD_EINVAL; }
   OSD_HIP(hipSetDevice(device));
-  hipLaunchKernelGGL(k_reparam_bwd, ew_blocks(count), 256, 0, (hipStream_t)stream, gz, mu, z, count, d_logvar);
+  hipLaunchKernelGGL(k_reparam_bwd, ew_blocks(count), 256, 0, (hipStream_t)stream, gz, eps, logvar, count, d_logvar);
   OSD_HIP(hipGetLastError());
   return OSD_OK;
 }

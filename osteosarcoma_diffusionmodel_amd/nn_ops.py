@@ -95,18 +95,20 @@ class _Reparameterize(torch.autograd.Function):
         mu, logvar = _f32(mu), _f32(logvar)
         eps = _f32(eps) if eps is not None else None
         z = torch.empty_like(mu)
+        drawn = torch.empty_like(mu) if eps is None else None      # seeded draw: the kernel hands the noise back for the backward
         stream, dev = _ctx(mu)
-        L.check(L.lib().osd_nn_reparameterize(stream, dev, L.ptr(mu), L.ptr(logvar), L.ptr(eps), int(seed), mu.shape[0], mu.shape[1], L.ptr(z), None))
-        ctx.save_for_backward(mu, z)
+        L.check(L.lib().osd_nn_reparameterize(stream, dev, L.ptr(mu), L.ptr(logvar), L.ptr(eps), int(seed), mu.shape[0], mu.shape[1], L.ptr(z),
+                                              L.ptr(drawn)))
+        ctx.save_for_backward(eps if eps is not None else drawn, logvar)
         return z
 
     @staticmethod
     def backward(ctx, gz):
-        mu, z = ctx.saved_tensors
+        eps, logvar = ctx.saved_tensors
         gz = _f32(gz)
-        dlv = torch.empty_like(mu)
-        stream, dev = _ctx(mu)
-        L.check(L.lib().osd_nn_reparameterize_bwd(stream, dev, L.ptr(gz), L.ptr(mu), L.ptr(z), mu.numel(), L.ptr(dlv)))
+        dlv = torch.empty_like(logvar)
+        stream, dev = _ctx(logvar)
+        L.check(L.lib().osd_nn_reparameterize_bwd(stream, dev, L.ptr(gz), L.ptr(eps), L.ptr(logvar), logvar.numel(), L.ptr(dlv)))
         return gz, dlv, None, None
 
 

@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from osteosarcoma_diffusionmodel_amd import _lib as L
-from helpers import RawHandle, assert_close
+from helpers import RawHandle, assert_close, rel_err
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-5
@@ -33,7 +33,9 @@ def _gemm(rh, A, a_kc, B, b_kc, F_, P, K, C0=None):
 def test_gemm_layouts(rh, F_, P, K, a_kc, b_kc):
     """out[p][f] = sum_k A(f,k) B(p,k) for every operand storage; asymmetric random data, ragged edges."""
     if (F_ % 4 or P % 4) and not (a_kc and b_kc):
-        # row-contiguous (NKC) operands are loaded in 4-element chunks along the row index
+        # a choice of this test, not a precondition of the kernel: row-contiguous (NKC) operands are staged in 4-element chunks along
+        # the row index, and rounding F and P keeps these cases on whole chunks.  Unrounded extents (every chunk guarded per element by
+        # ld4g / st4g) are test_gemm_layouts_ragged's
         F_, P = (F_ + 3) // 4 * 4, (P + 3) // 4 * 4
     g = torch.Generator().manual_seed(F_ * 7 + P * 3 + K)
     Af = torch.randn(F_, K, generator=g, dtype=torch.float64)
@@ -43,6 +45,24 @@ def test_gemm_layouts(rh, F_, P, K, a_kc, b_kc):
     B = (Bf if b_kc else Bf.T).contiguous().float().cuda()
     out = _gemm(rh, A, a_kc, B, b_kc, F_, P, K)
     assert_close(out.cpu(), ref, RTOL, what=f"gemm {F_}x{P}x{K} kc=({a_kc},{b_kc})")
+
+
+@pytest.mark.parametrize("F_,P,K", [(3, 32, 8), (70, 45, 37), (24, 7, 3), (1, 130, 257), (5, 1, 2)])
+@pytest.mark.parametrize("a_kc,b_kc", [(0, 1), (0, 0), (1, 0)])
+def test_gemm_layouts_ragged(rh, F_, P, K, a_kc, b_kc):
+    """The three layouts with a row-contiguous operand at extents that are NOT rounded to multiples of 4: rows of F or P floats start
+    at any 4-byte address, so StageNK::load's chunks fall back to ld4g's per-element guards (i < n for each of the four) and the
+    output rows to st4g's.  (3, 32, 8) with (0, 0) is the cVAE's weight gradient of the three-column condition panel
+    (osd_nn_linear_bwd: dw + K1)."""
+    g = torch.Generator().manual_seed(F_ * 7 + P * 3 + K)
+    Af = torch.randn(F_, K, generator=g, dtype=torch.float64)
+    Bf = torch.randn(P, K, generator=g, dtype=torch.float64)
+    ref = Bf @ Af.T
+    A = (Af if a_kc else Af.T).contiguous().float().cuda()
+    B = (Bf if b_kc else Bf.T).contiguous().float().cuda()
+    out = _gemm(rh, A, a_kc, B, b_kc, F_, P, K)
+    print(f"[ragged gemm] {F_}x{P}x{K} kc=({a_kc},{b_kc}): error / tolerance = {rel_err(out, ref) / RTOL:.3f}")
+    assert_close(out.cpu(), ref, RTOL, what=f"ragged gemm {F_}x{P}x{K} kc=({a_kc},{b_kc})")
 
 
 def test_gemm_identity_asymmetric(rh):
