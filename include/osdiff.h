@@ -678,6 +678,21 @@ int osd_val_glm_eval(void *stream, int device, const float *X, int64_t rows, int
  * Partial sums of row shards about one common centre add up; mean and variance follow on the host.  Synchronous. */
 int osd_val_col_centered_moments(void *stream, int device, const float *X, int64_t rows, int ld, int D,
                                  const float *center, double *sum_host, double *sumsq_host);
+/* Per-label column sums of a cohort, in one read of X (csrc/cluster.hip): the update half of a Lloyd
+ * iteration and the per-subtype mean of any matrix.  Over the rows r with labels[r] == k:
+ *   sums_dev[k][c]     = sum_r X[r][c]          DEVICE double [K][D], overwritten
+ *   counts_dev[k]      = the number of such rows DEVICE int64 [K], exact
+ *   value_sums_dev[k]  = sum_r value[r]          DEVICE double [K]; value: dev float [rows]; both NULL when not wanted (one
+ *                                                without the other is OSD_EINVAL)
+ * X dev float [rows][ld] (any base address, any ld >= D, read by dwords in place -- never through a copy); labels: dev int32
+ * [rows]; a row whose label lies outside [0, K) -- the -1 of osd_val_nearest included -- contributes to nothing.
+ * Arithmetic: every addition is a double addition of a converted float, so a sum is exact up to 2^-53 per add whatever the
+ * partition (and exact on integer data).  A work item is a block of rows times 64 columns with its own double accumulators, added
+ * in row order; the items' sums are added in a fixed order.  No floating-point atomics: the same inputs give the same bits, and
+ * the partition depends on (rows, D, K) alone.  rows >= 1, 1 <= D <= 8192, 1 <= K <= 64 (OSD_EINVAL otherwise).  Synchronous. */
+int osd_val_label_sums(void *stream, int device, const float *X, int64_t rows, int ld, int D,
+                       const int32_t *labels, int K, const float *value,
+                       double *sums_dev, int64_t *counts_dev, double *value_sums_dev);
 
 /* ---- biological constraint losses (north_star) ------------------------------
  * The reference declares them at models/cvae.py:262-302 as stubs that return 0.0 (and the diffusion

@@ -116,6 +116,7 @@ _SIGNATURES = {
                                    C.POINTER(C.c_double), _P, _P, C.c_int]),
     "osd_val_col_centered_moments": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, C.POINTER(C.c_double),
                                                C.POINTER(C.c_double)]),
+    "osd_val_label_sums": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
     "osd_set_constraints": (C.c_int, [_P, C.POINTER(OsdConstraints)]),
     "osd_get_loss_parts": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "osd_set_loss": (C.c_int, [_P, C.c_int, C.c_double, _P]),

@@ -25,7 +25,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import cluster as CL
 from . import utility as U
+from .cluster import subtype_summary      # noqa: F401  (the subtype_* figures: pure NumPy, documented there)
 from .parallel import ShardComm
 
 logger = logging.getLogger(__name__)
@@ -282,6 +284,26 @@ class DeviceKernels:
         L.check(L.lib().osd_val_glm_eval(self._stream(), self.index, L.ptr(x), rows, max(int(x.stride(0)), D), D, L.ptr(center),
                                          L.ptr(scale), L.ptr(y), K, L.ptr(a), L.ptr(W), K, arr, loss, L.ptr(g), L.ptr(z), K))
         return (None if loss is None else np.array(loss[:K])), (None if g is None else g.cpu().numpy()), z
+
+    def label_sums(self, t: torch.Tensor, labels: torch.Tensor, K: int, value: Optional[torch.Tensor] = None):
+        """``osd_val_label_sums`` on the fp32 device tensor t [rows, D] (a column-slice view is read in place) and the int32 labels
+        [rows]: ``(sums, counts, value_sums)`` DEVICE tensors -- sums float64 [K, D], the column sums of the rows of each label;
+        counts int64 [K]; value_sums float64 [K], the per-label sums of ``value`` [rows] (rounded to fp32), or None without one.  A
+        row whose label lies outside [0, K) -- ``nearest``'s -1 included -- contributes to nothing.  Every addition is in double and
+        in a fixed order: the same inputs give the same bits.  1 <= K <= 64, D <= 8192."""
+        t = _rows_view(t)
+        rows, D = t.shape
+        K = int(K)
+        labels = labels.to(device=t.device, dtype=torch.int32).contiguous()
+        if labels.shape != (rows,):
+            raise ValueError(f"labels must hold one label per row ({rows})")
+        v = None if value is None else _f32(value, t.device, (rows,), "value")
+        sums = torch.empty((max(K, 0), D), dtype=torch.float64, device=t.device)
+        counts = torch.empty(max(K, 0), dtype=torch.int64, device=t.device)
+        vs = None if v is None else torch.empty(max(K, 0), dtype=torch.float64, device=t.device)
+        L.check(L.lib().osd_val_label_sums(self._stream(), self.index, L.ptr(t), rows, max(int(t.stride(0)), D), D, L.ptr(labels), K,
+                                           L.ptr(v), L.ptr(sums), L.ptr(counts), L.ptr(vs)))
+        return sums, counts, vs
 
 
 def _same_features(q: torch.Tensor, r: torch.Tensor) -> None:
@@ -977,6 +999,55 @@ class BiologicalValidator:
         return self._agree(c2st_metrics(self.comm, self.k, x, y, test_fraction=float(test_fraction), seed=int(seed), l2=float(l2),
                                         max_iter=int(max_iter), tol=float(tol)))
 
+    # -- subtype structure: k-means on the real cohort, the synthetic rows assigned to its centroids ------
+    def subtype_fidelity(self, real, synthetic, n_clusters: int = 4, *, conditions=None, names=None, seed: int = 0, n_init: int = 4,
+                         max_iter: int = 100, return_rows: bool = False):
+        """Does ``synthetic`` reproduce ``real``'s subtypes, and in the right proportions?  k-means (``cluster.kmeans``: k-means++,
+        ``n_init`` restarts from ``seed``) is fitted on the real cohort after the fp32 column means of ``real`` are subtracted from
+        both, the subtypes are numbered by descending real count, every synthetic row goes to its nearest centroid, and
+        ``subtype_summary`` reports the ``subtype_*`` keys: shares, their Jensen-Shannon divergence and total-variation distance,
+        missing subtypes, per-subtype dispersion ratios (collapse onto a centre) and centroid shifts.  ``conditions=(real_cond,
+        synth_cond)`` adds ``subtype_condition_gap_<name>`` per condition column (``names``: default the columns of ``real_cond``,
+        else c0, c1, ...).  Distances are plain Euclidean over the columns as given -- callers scale their inputs.
+        ``return_rows=True`` also returns the sums behind the figures with the centroids, both label arrays and both d2 arrays.
+        On a ``sharded=True`` validator ``synthetic`` (and ``synth_cond``) is this rank's row shard and the real cohort is
+        replicated: the fit is local and identical on every rank, the synthetic sums are added over the ranks."""
+        K = int(n_clusters)
+        if not 1 <= K <= CL.MAX_CLUSTERS:
+            raise ValueError(f"n_clusters must lie in [1, {CL.MAX_CLUSTERS}], got {K}")
+        x, y = _dev(real, self.device), _dev(synthetic, self.device)
+        for label, t in (("real", x), ("synthetic", y)):
+            if t.dim() != 2 or t.shape[1] != x.shape[1] or t.shape[1] < 1:
+                raise ValueError(f"{label} must be [rows, {x.shape[1]}]: the cohorts must have the same features")
+            if not bool(torch.isfinite(t).all().item()):
+                raise ValueError(f"{label} holds non-finite values")
+        if x.shape[0] < K:
+            raise ValueError(f"real has {x.shape[0]} rows: {K} subtypes need at least as many")
+        if int(self.comm.sum(int(y.shape[0]))[0]) < 1:
+            raise ValueError("synthetic has no rows")
+        cond = None
+        if conditions is not None:
+            if not isinstance(conditions, (tuple, list)) or len(conditions) != 2:
+                raise ValueError("conditions must be a (real_cond, synth_cond) pair")
+            if names is None:
+                cols = getattr(conditions[0], "columns", None)
+                names = [str(c) for c in cols] if cols is not None else None
+            cs = [_dev(c, self.device) for c in conditions]
+            cs = [c.reshape(-1, 1) if c.dim() == 1 else c for c in cs]
+            for label, c, t in zip(("real", "synthetic"), cs, (x, y)):
+                if c.dim() != 2 or c.shape[0] != t.shape[0] or c.shape[1] != cs[0].shape[1] or c.shape[1] < 1:
+                    raise ValueError(f"the conditions of {label} must be [{t.shape[0]}, {cs[0].shape[1]}], got {tuple(c.shape)}")
+                if not bool(torch.isfinite(c).all().item()):
+                    raise ValueError(f"the conditions of {label} hold non-finite values")
+            names = [f"c{j}" for j in range(cs[0].shape[1])] if names is None else [str(v) for v in names]
+            if len(names) != cs[0].shape[1]:
+                raise ValueError("one name per condition column")
+            cond = (cs[0].contiguous(), cs[1].contiguous())
+        rows = CL.subtype_rows(self.comm, self.k, x, y, K, conditions=cond, names=names, seed=int(seed), n_init=int(n_init),
+                               max_iter=int(max_iter))
+        summary = self._agree(subtype_summary(rows))
+        return (summary, rows) if return_rows else summary
+
     # -- privacy: membership inference on the per-record likelihood bound (DESIGN.md section 3.18) ---------------------
     def membership_audit(self, model, train, holdout, *, num_timesteps: int = 32, seed: int = 0) -> Dict[str, float]:
         """The loss-threshold membership-inference attack on a diffusion model: ``train`` and ``holdout`` are (data, conditions)
@@ -1106,8 +1177,11 @@ class BiologicalValidator:
     def validate_all(self, real_mutations, real_expression, real_pathways, synth_mutations, synth_expression, synth_pathways,
                      pathway_gene_matrix=None, privacy: bool = False, holdout=None, model=None, membership=None,
                      prdc: bool = False, prdc_k: int = 5, correlation: bool = False, frechet: bool = False,
-                     corr_strong: float = 0.3, utility=None, c2st: bool = False) -> Dict[str, float]:
-        """``utility=(real_train_cond, synth_cond, real_test, real_test_cond)`` adds ``downstream_utility``'s ``utility_*`` keys: the
+                     corr_strong: float = 0.3, utility=None, c2st: bool = False, subtypes: Optional[int] = None,
+                     subtype_conditions=None) -> Dict[str, float]:
+        """``subtypes=K`` adds ``subtype_fidelity``'s ``subtype_*`` keys for K subtypes of the combined real matrix
+        (``subtype_conditions=(real_cond, synth_cond)``: its ``conditions``).
+        ``utility=(real_train_cond, synth_cond, real_test, real_test_cond)`` adds ``downstream_utility``'s ``utility_*`` keys: the
         combined real matrix is the training cohort, ``real_test`` a (mutations, expression, pathways) triple of held-out real
         patients (or their combined matrix); ``c2st=True`` adds ``discriminator_test``'s ``c2st_*`` keys on the combined matrices.
         ``correlation=True`` adds ``correlation_fidelity``'s ``corr_*`` keys (blocks ``mutations`` / ``expression`` / ``pathways``
@@ -1165,6 +1239,8 @@ class BiologicalValidator:
             all_results.update(self.downstream_utility(real_combined, train_cond, synth_combined, synth_cond, test, test_cond))
         if c2st:
             all_results.update(self.discriminator_test(real_combined, synth_combined))
+        if subtypes is not None:
+            all_results.update(self.subtype_fidelity(real_combined, synth_combined, int(subtypes), conditions=subtype_conditions))
         logger.info("=" * 50)
         logger.info("VALIDATION SUMMARY")
         logger.info("=" * 50)
