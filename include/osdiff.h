@@ -693,6 +693,52 @@ int osd_val_col_centered_moments(void *stream, int device, const float *X, int64
 int osd_val_label_sums(void *stream, int device, const float *X, int64_t rows, int ld, int D,
                        const int32_t *labels, int K, const float *value,
                        double *sums_dev, int64_t *counts_dev, double *value_sums_dev);
+/* Cox proportional hazards over a cohort with follow-up times t_i and event flags delta_i in {0, 1} (csrc/cox.hip; DESIGN.md section
+ * 3.26).  A plan holds what depends on (t, delta) alone and is made once per fit, on the host: the stable descending-time order of
+ * the rows, the first and the last position of every row's tie group (equal times) and the flags in that order, uploaded to
+ * `device` on `stream`; every later osd_val_cox_eval of the plan runs on that device and stream.  time_host, event_host: HOST
+ * double [rows].  OSD_EINVAL, checked on the host before any device call: a non-finite time, a flag other than 0 or 1, rows < 1 or
+ * rows >= 2^31.  The library makes every index the kernels follow, and osd_val_cox_eval refuses another row count than the plan's:
+ * nothing a caller passes later can become an out-of-range index.  osd_val_cox_plan_destroy(NULL) is OSD_OK. */
+int osd_val_cox_plan_create(int device, void *stream, const double *time_host, const double *event_host, int64_t rows,
+                            void **plan);
+int osd_val_cox_plan_destroy(void *plan);
+/* Loss, gradient and scores of the Breslow partial likelihood.  With u_i = (x_i - center) * scale over the first D columns,
+ * eta_i = w . u_i (no intercept: the partial likelihood has none), m = max eta and e_i = exp(eta_i - m):
+ *   S_i        = sum_{k: t_k >= t_i} e_k                              the risk set, tied times included (Breslow)
+ *   *loss_host = -sum_i delta_i (eta_i - m - log S_i)                 HOST double, a SUM over the rows, no penalty
+ *   grad_dev   = sum_j r_j u_j,  r_j = -delta_j + e_j sum_{i: delta_i = 1, t_i <= t_j} 1 / S_i      DEVICE double [D], overwritten;
+ *                                                                     a column with scale 0 is dropped (gradient exactly 0)
+ *   score_dev  = eta_i                                                dev float [rows]
+ * X dev float [rows][ld] with the layouts and the two load paths of osd_val_glm_eval (any base address, any ld >= D, never through
+ * a copy); center, scale, w: dev float [D]; rows must be the plan's.  Any of the three outputs may be NULL, not all: scores alone
+ * read X once and nothing else; a loss without a gradient skips the second read.
+ * A call is two reads of X with 1-D work between them.  (a) eta in fp32 with osd_val_glm_eval's arithmetic -- x - center,
+ * w' = w * scale, the same summation order -- so a score has the bits that call gives for one head with the same weights and a
+ * zero bias.  (b) in double and in a fixed order: the maximum, exp, the prefix sums in descending-time order read at the end of each
+ * tie group, the loss terms, the suffix sums of delta / S read at the start of each tie group, and r, which is rounded to fp32.  A
+ * scan is block sums, a scan of the sums by one workgroup, and an apply pass, as separate launches: no workgroup waits for another
+ * inside a kernel.  (c) the gradient, accumulated in fp32 over runs of at most OSD_GLM_RUN_ROWS rows per work item, every run folded
+ * into the item's double sums, the items added in a fixed order and the factor scale applied once, in double.  No floating-point
+ * atomics: the same inputs give the same bits, and the partition depends on (rows, D) and the load path alone.
+ * Inputs must be finite.  A score range wider than exp can hold (eta - m below about -745) underflows e to 0; where that empties the
+ * risk set of an event, S = 0 and the loss is not finite (+inf or NaN) -- a line search rejects such a step, as utility.fit_glm's
+ * does.  All censored: loss 0 and gradient 0 exactly.  rows >= 1, 1 <= D <= 8192, ld >= D (OSD_EINVAL otherwise, checked on the
+ * host before any device call).  Synchronous; uses a grow-only per-device workspace held for the length of the call. */
+int osd_val_cox_eval(void *plan, const float *X, int64_t rows, int ld, int D, const float *center, const float *scale,
+                     const float *w, double *loss_host, double *grad_dev, float *score_dev);
+/* Harrell's concordance counts of a risk score, exact.  Over the ordered pairs (i, j) with event[i] != 0 and time[i] < time[j]
+ * (strict: equal times are not comparable), counts_host (HOST int64 [4]) receives
+ *   [0] the comparable pairs   [1] those with risk[i] > risk[j] (concordant)   [2] risk[i] < risk[j]   [3] risk[i] == risk[j]
+ * and C = ([1] + [3] / 2) / [0].  time_dev, event_dev, risk_dev: dev float [n]; comparisons are those of the fp32 values.  A lane
+ * owns one i of a tile of OSD_CONC_I_TILE and meets every j once, OSD_CONC_J_CHUNK of them at a time through LDS; its 32-bit
+ * counters are added in 64 bits through the wave and the workgroup's own slab, and the slabs on the host: integer sums, so the
+ * result does not depend on any order, and nothing overflows below n = 2^31.  1 <= n < 2^31 (OSD_EINVAL otherwise, checked on the
+ * host before any device call).  Synchronous. */
+#define OSD_CONC_I_TILE  256
+#define OSD_CONC_J_CHUNK 1024
+int osd_val_concordance(void *stream, int device, const float *time_dev, const float *event_dev, const float *risk_dev,
+                        int64_t n, int64_t *counts_host);
 
 /* ---- biological constraint losses (north_star) ------------------------------
  * The reference declares them at models/cvae.py:262-302 as stubs that return 0.0 (and the diffusion

@@ -24,6 +24,7 @@ OSD_PRED_EPSILON, OSD_PRED_V, OSD_PRED_SAMPLE = 0, 1, 2
 OSD_CORR_STATS = 7
 OSD_GLM_LOGISTIC, OSD_GLM_SQUARED = 0, 1
 OSD_GLM_RUN_ROWS = 128
+OSD_CONC_I_TILE, OSD_CONC_J_CHUNK = 256, 1024
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libosdiff.so"
 
@@ -117,6 +118,10 @@ _SIGNATURES = {
     "osd_val_col_centered_moments": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, C.POINTER(C.c_double),
                                                C.POINTER(C.c_double)]),
     "osd_val_label_sums": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
+    "osd_val_cox_plan_create": (C.c_int, [C.c_int, _P, _P, _P, C.c_int64, C.POINTER(_P)]),
+    "osd_val_cox_plan_destroy": (C.c_int, [_P]),
+    "osd_val_cox_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_double), _P, _P]),
+    "osd_val_concordance": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "osd_set_constraints": (C.c_int, [_P, C.POINTER(OsdConstraints)]),
     "osd_get_loss_parts": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "osd_set_loss": (C.c_int, [_P, C.c_int, C.c_double, _P]),

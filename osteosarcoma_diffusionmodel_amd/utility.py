@@ -13,36 +13,11 @@ LOGISTIC, SQUARED = 0, 1          # OSD_GLM_LOGISTIC / OSD_GLM_SQUARED of includ
 MAX_HEADS = 4                     # heads of one osd_val_glm_eval call
 
 
-def fit_glm(eval_fn: Callable[[np.ndarray], Tuple[np.ndarray, np.ndarray]], K: int, D: int, kinds: Sequence[int], n: float, l2: float,
-            max_iter: int = 200, tol: float = 1e-5, history: int = 10) -> Dict[str, object]:
-    """Minimise  F(W) = sum_k [ loss_k(W) / n + (l2 / 2) |W_k[:D]|^2 ]  over W [K, D + 1] (bias last, unpenalised) by L-BFGS (two-loop
-    recursion, ``history`` pairs) with backtracking Armijo steps, from W = 0.  ``eval_fn(W) -> (loss [K], grad [K, D + 1])`` returns
-    SUMS over the rows, as ``osd_val_glm_eval`` does, and is all the driver knows about the data; ``n`` is the total row weight.  The
-    heads are separable, so one joint vector serves them all.  ``kinds`` (LOGISTIC / SQUARED per head) is checked, not used: the
-    link function lives in ``eval_fn``.
-
-    Returns ``{"W", "iterations", "converged", "grad_inf_norm"}``: converged means the gradient's infinity norm fell to ``tol``.  A
-    line search that finds no Armijo step even along the steepest descent -- an ``eval_fn`` in fp32 has reached its noise floor --
-    ends the fit with ``converged=False``; nothing is raised."""
-    K, D = int(K), int(D)
-    kinds = [int(v) for v in kinds]
-    if K < 1 or D < 1 or len(kinds) != K or any(v not in (LOGISTIC, SQUARED) for v in kinds):
-        raise ValueError("fit_glm needs K >= 1 heads, D >= 1 features and one kind (LOGISTIC / SQUARED) per head")
-    if not (n > 0 and l2 >= 0 and max_iter >= 0 and history >= 1):
-        raise ValueError("fit_glm needs n > 0, l2 >= 0, max_iter >= 0 and history >= 1")
-    n, l2 = float(n), float(l2)
-
-    def objective(w):
-        loss, grad = eval_fn(w.reshape(K, D + 1))
-        loss = np.asarray(loss, dtype=np.float64).reshape(K)
-        grad = np.asarray(grad, dtype=np.float64).reshape(K, D + 1)
-        W = w.reshape(K, D + 1)
-        f = float(loss.sum() / n + 0.5 * l2 * np.sum(W[:, :D] ** 2))
-        g = grad / n
-        g[:, :D] += l2 * W[:, :D]
-        return f, g.ravel()
-
-    w = np.zeros(K * (D + 1), dtype=np.float64)
+def _lbfgs(objective: Callable[[np.ndarray], Tuple[float, np.ndarray]], w: np.ndarray, max_iter: int, tol: float, history: int):
+    """The L-BFGS loop ``fit_glm`` and ``survival.fit_cox`` share: minimises ``objective(w) -> (f, g)`` over a flat float64 vector
+    from ``w`` -- two-loop recursion over ``history`` pairs, backtracking Armijo steps, the steepest descent when the quasi-Newton
+    direction finds no step.  Returns ``(w, iterations, converged, |g|_inf)``; a line search that finds no step at all ends the loop
+    with ``converged=False``."""
     f, g = objective(w)
     pairs = []                                                   # (s, y, 1 / y.s), oldest first
     it, converged = 0, bool(np.abs(g).max() <= tol)
@@ -90,7 +65,40 @@ def fit_glm(eval_fn: Callable[[np.ndarray], Tuple[np.ndarray, np.ndarray]], K: i
         w, f, g = w + s_vec, f_new, g_new
         it += 1
         converged = bool(np.abs(g).max() <= tol)
-    return {"W": w.reshape(K, D + 1).copy(), "iterations": it, "converged": converged, "grad_inf_norm": float(np.abs(g).max())}
+    return w, it, converged, float(np.abs(g).max())
+
+
+def fit_glm(eval_fn: Callable[[np.ndarray], Tuple[np.ndarray, np.ndarray]], K: int, D: int, kinds: Sequence[int], n: float, l2: float,
+            max_iter: int = 200, tol: float = 1e-5, history: int = 10) -> Dict[str, object]:
+    """Minimise  F(W) = sum_k [ loss_k(W) / n + (l2 / 2) |W_k[:D]|^2 ]  over W [K, D + 1] (bias last, unpenalised) by L-BFGS (two-loop
+    recursion, ``history`` pairs) with backtracking Armijo steps, from W = 0.  ``eval_fn(W) -> (loss [K], grad [K, D + 1])`` returns
+    SUMS over the rows, as ``osd_val_glm_eval`` does, and is all the driver knows about the data; ``n`` is the total row weight.  The
+    heads are separable, so one joint vector serves them all.  ``kinds`` (LOGISTIC / SQUARED per head) is checked, not used: the
+    link function lives in ``eval_fn``.
+
+    Returns ``{"W", "iterations", "converged", "grad_inf_norm"}``: converged means the gradient's infinity norm fell to ``tol``.  A
+    line search that finds no Armijo step even along the steepest descent -- an ``eval_fn`` in fp32 has reached its noise floor --
+    ends the fit with ``converged=False``; nothing is raised."""
+    K, D = int(K), int(D)
+    kinds = [int(v) for v in kinds]
+    if K < 1 or D < 1 or len(kinds) != K or any(v not in (LOGISTIC, SQUARED) for v in kinds):
+        raise ValueError("fit_glm needs K >= 1 heads, D >= 1 features and one kind (LOGISTIC / SQUARED) per head")
+    if not (n > 0 and l2 >= 0 and max_iter >= 0 and history >= 1):
+        raise ValueError("fit_glm needs n > 0, l2 >= 0, max_iter >= 0 and history >= 1")
+    n, l2 = float(n), float(l2)
+
+    def objective(w):
+        loss, grad = eval_fn(w.reshape(K, D + 1))
+        loss = np.asarray(loss, dtype=np.float64).reshape(K)
+        grad = np.asarray(grad, dtype=np.float64).reshape(K, D + 1)
+        W = w.reshape(K, D + 1)
+        f = float(loss.sum() / n + 0.5 * l2 * np.sum(W[:, :D] ** 2))
+        g = grad / n
+        g[:, :D] += l2 * W[:, :D]
+        return f, g.ravel()
+
+    w, it, converged, gnorm = _lbfgs(objective, np.zeros(K * (D + 1), dtype=np.float64), max_iter, tol, history)
+    return {"W": w.reshape(K, D + 1).copy(), "iterations": it, "converged": converged, "grad_inf_norm": gnorm}
 
 
 def roc_auc(scores, labels) -> float:

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import logging
+import weakref
 from math import gcd
 from typing import Dict, Optional, Sequence
 
@@ -26,6 +27,7 @@ import torch
 
 from . import _lib as L
 from . import cluster as CL
+from . import survival as SV
 from . import utility as U
 from .cluster import subtype_summary      # noqa: F401  (the subtype_* figures: pure NumPy, documented there)
 from .parallel import ShardComm
@@ -118,6 +120,33 @@ def _chi2_pairs(n: int, gram: np.ndarray) -> np.ndarray:
     with np.errstate(divide="ignore", invalid="ignore"):
         terms = (adj - exp) ** 2 / exp
     return np.where(live, np.where(live[:, None, None], terms, 0.0).sum((1, 2)), 0.0)
+
+
+def _cox_plan_destroy(handle: int) -> None:
+    L.lib().osd_val_cox_plan_destroy(C.c_void_p(handle))
+
+
+class CoxPlan:
+    """What ``osd_val_cox_eval`` needs of a cohort's (time, event) columns, made once per fit by ``DeviceKernels.cox_plan``: the
+    library's plan handle, its row count and the stream its calls run on.  ``close()`` destroys the plan (again: nothing); a
+    finalizer does it for a plan that was never closed."""
+
+    def __init__(self, handle: int, rows: int, stream: Optional[int] = None):
+        self.handle, self.rows, self.stream = C.c_void_p(handle), int(rows), stream
+        self._finalizer = weakref.finalize(self, _cox_plan_destroy, handle)
+
+    @property
+    def closed(self) -> bool:
+        return not self._finalizer.alive
+
+    def close(self) -> None:
+        self._finalizer()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class DeviceKernels:
@@ -304,6 +333,54 @@ class DeviceKernels:
         L.check(L.lib().osd_val_label_sums(self._stream(), self.index, L.ptr(t), rows, max(int(t.stride(0)), D), D, L.ptr(labels), K,
                                            L.ptr(v), L.ptr(sums), L.ptr(counts), L.ptr(vs)))
         return sums, counts, vs
+
+
+    def cox_plan(self, time, event) -> CoxPlan:
+        """``osd_val_cox_plan_create`` for a cohort's follow-up times and event flags (host arrays, one per row): the library sorts
+        the rows by descending time, finds the tie groups and uploads them.  Non-finite times and flags other than 0 or 1 are a
+        ValueError.  The plan belongs to this device and the current stream; ``close()`` it after the fit."""
+        t = np.ascontiguousarray(np.asarray(time, dtype=np.float64).ravel())
+        d = np.ascontiguousarray(np.asarray(event, dtype=np.float64).ravel())
+        if t.shape != d.shape:
+            raise ValueError("one event flag per time")
+        h, stream = C.c_void_p(), self._stream()
+        L.check(L.lib().osd_val_cox_plan_create(self.index, stream, t.ctypes.data, d.ctypes.data, t.size, C.byref(h)))
+        return CoxPlan(h.value, t.size, stream.value)
+
+    def cox_eval(self, x: torch.Tensor, center, scale, w, plan: CoxPlan, grad: bool = True, scores: bool = False):
+        """``osd_val_cox_eval`` on the fp32 device tensor x [rows, D] (a column-slice view is read in place) and the plan of its
+        rows: with u = (x - center) * scale and eta = w . u, returns ``(loss, grad, scores)`` -- loss the negative Breslow partial
+        log-likelihood, a float SUM over the rows; grad float64 [D] numpy, its gradient (None with ``grad=False``); scores the
+        float32 [rows] device tensor eta (None unless ``scores=True``).  ``center``, ``scale`` and ``w`` [D] are rounded to fp32.
+        No penalty and no 1 / n: the host applies them.  The same inputs give the same bits.  The call runs on the stream the plan
+        was made on; under another current stream that stream is waited for first, so the inputs are ready."""
+        if plan.closed:
+            raise ValueError("the plan has been closed")
+        x = _rows_view(x)
+        rows, D = x.shape
+        center, scale, w = (_f32(v, x.device, (D,), name) for v, name in ((center, "center"), (scale, "scale"), (w, "w")))
+        loss = C.c_double()
+        g = torch.empty(D, dtype=torch.float64, device=x.device) if grad else None
+        z = torch.empty(rows, dtype=torch.float32, device=x.device) if scores else None
+        if self._stream().value != plan.stream:
+            torch.cuda.current_stream(self.device).synchronize()
+        L.check(L.lib().osd_val_cox_eval(plan.handle, L.ptr(x), rows, max(int(x.stride(0)), D), D, L.ptr(center), L.ptr(scale), L.ptr(w),
+                                         C.byref(loss), L.ptr(g), L.ptr(z)))
+        return float(loss.value), (None if g is None else g.cpu().numpy()), z
+
+    def concordance(self, time, event, risk):
+        """``osd_val_concordance``: the exact pair counts ``(comparable, concordant, discordant, tied_risk)`` of
+        ``survival.concordance_counts`` as Python integers.  The three columns [n] are rounded to fp32 and compared as such."""
+        cols = []
+        for v, name in ((time, "time"), (event, "event"), (risk, "risk")):
+            v = v.reshape(-1) if isinstance(v, torch.Tensor) else np.asarray(v).ravel()
+            cols.append(_f32(v, self.device, (int(v.shape[0]),), name))
+        n = int(cols[0].shape[0])
+        if any(int(c.shape[0]) != n for c in cols):
+            raise ValueError("time, event and risk must have one value per row")
+        out = (C.c_int64 * 4)()
+        L.check(L.lib().osd_val_concordance(self._stream(), self.index, L.ptr(cols[0]), L.ptr(cols[1]), L.ptr(cols[2]), n, out))
+        return tuple(int(v) for v in out)
 
 
 def _same_features(q: torch.Tensor, r: torch.Tensor) -> None:
@@ -606,7 +683,8 @@ def corr_summary(stats: Dict[str, np.ndarray], bounds: Sequence[int], names: Seq
 
 
 # ---- downstream utility: fits of regularised linear heads over row shards -------------------------------
-GLM_RUN_ROWS = L.OSD_GLM_RUN_ROWS       # rows one fp32 gradient run of osd_val_glm_eval covers
+GLM_RUN_ROWS = L.OSD_GLM_RUN_ROWS       # rows one fp32 gradient run of osd_val_glm_eval (and of osd_val_cox_eval) covers
+CONC_I_TILE, CONC_J_CHUNK = L.OSD_CONC_I_TILE, L.OSD_CONC_J_CHUNK      # rows of a workgroup and partners of an LDS chunk of osd_val_concordance
 
 
 def pooled_standardisation(k, parts):
@@ -745,6 +823,41 @@ def c2st_metrics(comm: ShardComm, k, x_real, x_synth, test_fraction: float = 0.3
     z_r = glm_scores(k, xr_te, center, scale, W, kinds)
     z_s = comm.gather_rows(torch.from_numpy(glm_scores(k, xs_te, center, scale, W, kinds))).numpy()
     return U.c2st_summary(z_r, z_s)
+
+
+# ---- survival utility: Cox fits and concordance ----------------------------------------------------------
+def survival_metrics(k, x_train, s_train, x_synth, s_synth, x_test, s_test, l2: float = 1e-2, max_iter: int = 200, tol: float = 1e-5,
+                     return_fits: bool = False):
+    """``BiologicalValidator.survival_utility`` on tensors: the feature matrices on the kernels' device, the survival matrices float64
+    numpy [rows, 2] = (time, event).  ``k`` needs ``column_sums``, ``col_centered_moments``, ``glm_eval``, ``cox_plan``, ``cox_eval``
+    and ``concordance`` (DeviceKernels, or a float64 stand-in in the tests).  ``return_fits=True`` also returns the two fit reports
+    of ``survival.fit_cox``, each with its ``center`` and ``scale``, synthetic first."""
+    one = ShardComm(False)
+    surv = {"real_train": np.asarray(s_train, dtype=np.float64), "synthetic": np.asarray(s_synth, dtype=np.float64),
+            "real_test": np.asarray(s_test, dtype=np.float64)}
+    shares = {}
+    for label, s in surv.items():
+        if not np.isin(s[:, 1], (0.0, 1.0)).all():
+            raise ValueError(f"the event flags of {label} must be 0 or 1")
+        shares[label] = float(s[:, 1].mean())
+        if not shares[label] > 0.0:
+            raise ValueError(f"the {label} cohort has no event: a Cox model cannot be fitted or scored on it")
+    D = int(x_test.shape[1])
+    coefs, counts, fits = [], [], []
+    for label, x in (("synthetic", x_synth), ("real_train", x_train)):
+        n_rows, center, scale = pooled_standardisation(k, [(one, x)])
+        with k.cox_plan(surv[label][:, 0], surv[label][:, 1]) as plan:
+            fit = SV.fit_cox(lambda w: k.cox_eval(x, center, scale, w, plan)[:2], D, float(n_rows), l2, max_iter=max_iter, tol=tol)
+        W = np.concatenate([fit["w"], [0.0]])[None, :]
+        risk = glm_scores(k, x_test, center, scale, W, [U.SQUARED])[:, 0]
+        c = k.concordance(surv["real_test"][:, 0], surv["real_test"][:, 1], risk)
+        if c[0] <= 0:
+            raise ValueError("the real_test cohort has no comparable pair: no event is followed by a later time")
+        coefs.append(fit["w"] * scale.astype(np.float64))
+        counts.append(c)
+        fits.append(dict(fit, center=center, scale=scale))
+    out = SV.survival_summary(coefs[0], coefs[1], counts[0], counts[1], shares)
+    return (out, fits) if return_fits else out
 
 
 class BiologicalValidator:
@@ -999,6 +1112,37 @@ class BiologicalValidator:
         return self._agree(c2st_metrics(self.comm, self.k, x, y, test_fraction=float(test_fraction), seed=int(seed), l2=float(l2),
                                         max_iter=int(max_iter), tol=float(tol)))
 
+    # -- survival utility: Cox fits on synthetic and on real patients, concordance on held-out real ones ------
+    def survival_utility(self, real_train, real_train_surv, synthetic, synth_surv, real_test, real_test_surv, l2: float = 1e-2,
+                         max_iter: int = 200, tol: float = 1e-5) -> Dict[str, float]:
+        """Train on synthetic, test on real, for the survival conditions: does a proportional-hazards model trained on the synthetic
+        cohort order held-out real patients by risk as well as one trained on real patients?  Each ``*_surv`` is [rows, 2] =
+        (follow-up time, event flag: 1 an event, 0 a censoring), so a censored patient enters every risk set up to their time and no
+        event term -- unlike ``downstream_utility``, which would regress on the time as if it were an event.  One L2-regularised Cox
+        fit (Breslow ties, ``survival.fit_cox`` over ``DeviceKernels.cox_eval``: two reads of the cohort per iteration) on
+        ``synthetic`` (TSTR) and one on ``real_train`` (TRTR), features standardised by the cohort the fit trains on; both score
+        ``real_test`` and Harrell's C is counted exactly on the device (``DeviceKernels.concordance``).  Keys:
+        ``survival_tstr_cindex``, ``survival_trtr_cindex``, ``survival_cindex_gap`` (TRTR - TSTR), ``survival_coef_cosine`` (between
+        the two coefficient vectors in raw-feature units), ``survival_comparable_pairs`` and ``survival_event_share_real_train`` /
+        ``_synthetic`` / ``_real_test``.  A cohort without an event, or a test cohort without a comparable pair, raises a ValueError
+        naming the cohort; so does non-finite input.  Times are compared as fp32 values.  Not available on a ``sharded=True``
+        validator."""
+        if self.sharded:
+            raise NotImplementedError("survival_utility is not implemented for a sharded validator: the risk set of a patient holds "
+                                      "every patient with a later time, so the partial likelihood couples rows across shards")
+        xs = [_dev(a, self.device) for a in (real_train, synthetic, real_test)]
+        ss = [np.asarray(_host(a), dtype=np.float64) for a in (real_train_surv, synth_surv, real_test_surv)]
+        for label, x, s in zip(("real_train", "synthetic", "real_test"), xs, ss):
+            if x.dim() != 2 or x.shape[1] != xs[0].shape[1] or x.shape[1] < 1:
+                raise ValueError(f"{label} must be [rows, {xs[0].shape[1]}]: the cohorts must have the same features")
+            if s.ndim != 2 or s.shape != (x.shape[0], 2):
+                raise ValueError(f"the survival columns of {label} must be [{x.shape[0]}, 2] = (time, event), got {s.shape}")
+            if not (bool(torch.isfinite(x).all().item()) and np.isfinite(s).all()):
+                raise ValueError(f"{label} holds non-finite values")
+            if x.shape[0] < 2:
+                raise ValueError(f"{label} has {x.shape[0]} rows: a fit needs at least 2")
+        return survival_metrics(self.k, xs[0], ss[0], xs[1], ss[1], xs[2], ss[2], l2=float(l2), max_iter=int(max_iter), tol=float(tol))
+
     # -- subtype structure: k-means on the real cohort, the synthetic rows assigned to its centroids (DESIGN.md section 3.25) ------
     def subtype_fidelity(self, real, synthetic, n_clusters: int = 4, *, conditions=None, names=None, seed: int = 0, n_init: int = 4,
                          max_iter: int = 100, return_rows: bool = False):
@@ -1178,8 +1322,11 @@ class BiologicalValidator:
                      pathway_gene_matrix=None, privacy: bool = False, holdout=None, model=None, membership=None,
                      prdc: bool = False, prdc_k: int = 5, correlation: bool = False, frechet: bool = False,
                      corr_strong: float = 0.3, utility=None, c2st: bool = False, subtypes: Optional[int] = None,
-                     subtype_conditions=None) -> Dict[str, float]:
-        """``subtypes=K`` adds ``subtype_fidelity``'s ``subtype_*`` keys for K subtypes of the combined real matrix
+                     subtype_conditions=None, survival=None) -> Dict[str, float]:
+        """``survival=(real_train_surv, synth_surv, real_test, real_test_surv)`` adds ``survival_utility``'s ``survival_*`` keys, the
+        cohorts as for ``utility=``: the combined real matrix trains, ``real_test`` is a (mutations, expression, pathways) triple
+        of held-out real patients (or their combined matrix), each ``*_surv`` is [rows, 2] = (time, event).
+        ``subtypes=K`` adds ``subtype_fidelity``'s ``subtype_*`` keys for K subtypes of the combined real matrix
         (``subtype_conditions=(real_cond, synth_cond)``: its ``conditions``).
         ``utility=(real_train_cond, synth_cond, real_test, real_test_cond)`` adds ``downstream_utility``'s ``utility_*`` keys: the
         combined real matrix is the training cohort, ``real_test`` a (mutations, expression, pathways) triple of held-out real
@@ -1237,6 +1384,17 @@ class BiologicalValidator:
                 else:
                     test = np.concatenate([_host(p) for p in parts_t], axis=1)
             all_results.update(self.downstream_utility(real_combined, train_cond, synth_combined, synth_cond, test, test_cond))
+        if survival is not None:
+            if not isinstance(survival, (tuple, list)) or len(survival) != 4:
+                raise ValueError("validate_all(survival=...) needs (real_train_surv, synth_surv, real_test, real_test_surv)")
+            train_surv, synth_surv, test, test_surv = survival
+            if isinstance(test, (tuple, list)):
+                parts_t = [p.values for p in test]
+                if all(isinstance(p, torch.Tensor) for p in parts_t):
+                    test = torch.cat(parts_t, dim=1)
+                else:
+                    test = np.concatenate([_host(p) for p in parts_t], axis=1)
+            all_results.update(self.survival_utility(real_combined, train_surv, synth_combined, synth_surv, test, test_surv))
         if c2st:
             all_results.update(self.discriminator_test(real_combined, synth_combined))
         if subtypes is not None:
