@@ -740,6 +740,35 @@ int osd_val_cox_eval(void *plan, const float *X, int64_t rows, int ld, int D, co
 int osd_val_concordance(void *stream, int device, const float *time_dev, const float *event_dev, const float *risk_dev,
                         int64_t n, int64_t *counts_host);
 
+/* ---- feature transforms (csrc/transform.hip) ------------------------------
+ * dst[r][f] = map_f(src[r][f]) over the first D columns of `rows` rows; inverse != 0 applies the inverse maps.  kind_dev[f]:
+ *   OSD_XF_IDENTITY         copy
+ *   OSD_XF_STANDARD         forward (x - center[f]) / scale[f]; inverse z * scale[f] + center[f], two roundings (no fma)
+ *   OSD_XF_QUANTILE_NORMAL  a monotone piecewise-linear map between the column's knots k = knots_dev[f][0..Q-1] (fp32, non-decreasing)
+ *                           and the levels zl = levels_dev[0..Q-1] (fp32, strictly increasing, shared by all columns).  NaN -> NaN.
+ *     forward(x): lb = #{k < x}, ub = #{k <= x};  ub == 0 -> zl[0];  lb == Q -> zl[Q-1];  ub > lb (x equals the knots lb..ub-1, a tie
+ *                 plateau) -> the mid-rank level 0.5 * (zl[(lb+ub-1)>>1] + zl[(lb+ub)>>1]);  else j = lb - 1,
+ *                 t = (x - k[j]) / (k[j+1] - k[j]),  z = zl[j] + t * (zl[j+1] - zl[j])
+ *     inverse(z): z <= zl[0] -> k[0];  z >= zl[Q-1] -> k[Q-1];  else j with zl[j] <= z < zl[j+1],
+ *                 t = (z - zl[j]) / (zl[j+1] - zl[j]),  x = k[j] + t * (k[j+1] - k[j])
+ *   Every operation is an fp32 operation in the order written; an interpolated result is then clamped to its bracket [zl[j],
+ *   zl[j+1]] or [k[j], k[j+1]] (a + fl(b - a) can pass b by an ulp), so an inverse value lies inside [k[0], k[Q-1]] bit for bit and a
+ *   plateau's whole z interval returns the tied value exactly.
+ * src, dst: dev float [rows][ld]; src == dst (in place) is allowed, any other overlap is not; ld >= D: a column slice of a wider
+ * matrix, whose other columns are neither read nor written.  knots_dev: dev float [D][Q] (rows of columns that are not quantile
+ * columns are not read); center_dev, scale_dev: dev float [D] (read for standard columns only).  A workgroup owns 32 columns and a
+ * chunk of rows and searches its columns' knots in LDS ([Q][32]: conflict-free); one read and one write of the matrix, no atomics,
+ * no dependence on the launch geometry.  OSD_EINVAL, before any launch: a NULL pointer, Q outside [2, OSD_XF_MAX_Q], D < 1, rows < 0,
+ * ld < D, a kind other than the three (the kinds are read back first).  rows == 0 is OSD_OK without a launch.  The kernel is left
+ * running on `stream`. */
+#define OSD_XF_IDENTITY        0
+#define OSD_XF_STANDARD        1
+#define OSD_XF_QUANTILE_NORMAL 2
+#define OSD_XF_MAX_Q           1024
+int osd_xf_apply(void *stream, int device, const float *src, int64_t ld_src, float *dst, int64_t ld_dst, int64_t rows, int D,
+                 const int32_t *kind_dev, const float *knots_dev, int Q, const float *levels_dev,
+                 const float *center_dev, const float *scale_dev, int inverse);
+
 /* ---- biological constraint losses (north_star) ------------------------------
  * The reference declares them at models/cvae.py:262-302 as stubs that return 0.0 (and the diffusion
  * model has none), so nothing is added unless osd_set_constraints() configures them:

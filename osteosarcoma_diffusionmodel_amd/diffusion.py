@@ -362,6 +362,11 @@ class BiologyAwareDiffusionModel(nn.Module):
         # per-feature bounds the predicted x0 is clipped to inside every sampling step (sample(x0_bounds=...); generate.assemble_bounds
         # describes the forms: a (lo, hi) pair or a dict over mutations / expression / pathways).  None: no clipping, today's sampler
         self.x0_bounds = None
+        # the feature transform the training data went through (transform.FeatureTransform; config['data']['transform'], DESIGN.md section
+        # 3.27).  A plain attribute like null_condition: the Trainer adopts the dataset's, checkpoints carry its tables, and the
+        # generator maps between data units and model units with it.  Everything on this class -- sample, p_sample, predict*,
+        # variational_bound, row_sq_error, loss_profile, x0_bounds, known -- stays in MODEL units.  None: the model sees the data as is
+        self.feature_transform = None
         # optional constraint losses (set_constraints); None = the reference's eps-MSE only
         self._constraints = None
         self._constraints_version = 0
@@ -425,12 +430,16 @@ class BiologyAwareDiffusionModel(nn.Module):
         else:
             if (mutation_columns is None) != (target_columns is None):
                 raise ValueError("mutation_columns and target_columns go together")
-            self._constraints = {
+            new = {
                 "pathways": [list(map(int, p)) for p in (pathways or [])],
                 "cols_a": list(map(int, mutation_columns or [])), "cols_b": list(map(int, target_columns or [])),
                 "w_pc": float(pathway_weight if pathway_weight is not None else cons.get("pathway_coherence_weight", 1.0)),
                 "w_me": float(mutexpr_weight if mutexpr_weight is not None else cons.get("mutation_expression_weight", 1.0)),
             }
+            if getattr(self, "feature_transform", None) is not None:
+                from .transform import check_transform_training
+                check_transform_training(self, new["w_pc"] != 0.0 or new["w_me"] != 0.0)      # ValueError naming data.transform
+            self._constraints = new
         self._constraints_version += 1
 
     def last_row_norms(self, n: int) -> torch.Tensor:
@@ -627,7 +636,8 @@ class BiologyAwareDiffusionModel(nn.Module):
     def row_sq_error(self, x_0, conditions, t, *, noise=None, seed: Optional[int] = None, row_offset: int = 0):
         """se [n] (fp32): the squared error sum_d (out - target)^2 of the network's raw output at q_sample(x_0, t) against the training
         target of ``prediction_type``, per row, in eval mode.  ``t``: one timestep index per row.  ``noise`` [n, D] is injected, else
-        the draws are generated and keyed by (seed, row_offset + row, t) alone.  Deterministic: the same call returns the same bits."""
+        the draws are generated and keyed by (seed, row_offset + row, t) alone.  Deterministic: the same call returns the same bits.
+        ``x_0`` is in model units: with ``feature_transform`` set, ``feature_transform.forward`` of the data."""
         self._refuse_link("row_sq_error")
         x_0, conditions = self._bound_inputs(x_0, conditions, "row_sq_error")
         eng = self._engine()
@@ -667,6 +677,8 @@ class BiologyAwareDiffusionModel(nn.Module):
     def variational_bound(self, x_0, conditions, *, num_timesteps: Optional[int] = None, timesteps=None, noise=None,
                           seed: Optional[int] = None, row_offset: int = 0, decoder_variance: Optional[float] = None):
         """The DDPM's variational upper bound on -log p(x_0 | c) per patient (Ho et al. 2020, eq. 5; likelihood.py states every term).
+        ``x_0`` is in model units: with ``feature_transform`` set the bound is a model-space score of ``feature_transform.forward(data)``
+        and carries no Jacobian term of the map.
 
         Returns a dict: ``nll`` [n] in nats and ``bpd`` [n] = nll / (D ln 2), float64 on the device; ``prior`` [n] (L_T, float64);
         ``terms`` [S][n] (float64: row 0 the decoder term L_0, the others the weighted L_t, nll = prior + terms.sum(0));
@@ -701,7 +713,7 @@ class BiologyAwareDiffusionModel(nn.Module):
     @torch.no_grad()
     def loss_profile(self, x_0, conditions, num_timesteps: int = 50, seed: Optional[int] = None):
         """(timesteps [S] int64, profile [S] float64): the cohort mean of se / D per timestep -- the loss curve of the configured
-        target over t -- from the same sweep as ``variational_bound``."""
+        target over t -- from the same sweep as ``variational_bound``; ``x_0`` in model units, like there."""
         from . import likelihood as LK
         self._refuse_link("loss_profile")
         ts = LK.select_timesteps(self.num_steps, num_timesteps, None)
@@ -731,7 +743,8 @@ class BiologyAwareDiffusionModel(nn.Module):
 
     def predict(self, x_t, t, conditions, as_: str = "raw", *, dropout_masks: Optional[Sequence[torch.Tensor]] = None,
                 seed: Optional[int] = None, guidance_scale: float = 1.0):
-        """The network's prediction at (x_t, t) read as ``as_``: "raw" (the output itself: eps, v or x0 by ``prediction_type``), "x0"
+        """(Model units throughout: a ``feature_transform`` is applied by the generator, never here.)
+        The network's prediction at (x_t, t) read as ``as_``: "raw" (the output itself: eps, v or x0 by ``prediction_type``), "x0"
         (x0^ = P x_t + Q out), "eps" ((x_t - a x0^)/b) or "v" (a eps^ - b x0^), a = sqrt_alphas_cumprod[t], b =
         sqrt_one_minus_alphas_cumprod[t].  The conversion is one row-affine pass (osd_convert_prediction) with coefficients formed in float64
         and rounded once; the model's own reading and "raw" are the output unchanged.  ``guidance_scale`` combines raw outputs, which is
@@ -760,7 +773,7 @@ class BiologyAwareDiffusionModel(nn.Module):
     def predict_noise(self, x_t, t, conditions, *, dropout_masks: Optional[Sequence[torch.Tensor]] = None,
                       seed: Optional[int] = None, guidance_scale: float = 1.0):
         """The predicted noise.  An epsilon model: the network's output (``_raw_output``), as ever.  The other types:
-        ``predict(as_="eps")``, a real eps^, so that code written against this method (``p_sample`` loops) keeps working."""
+        ``predict(as_="eps")``, a real eps^, so that code written against this method (``p_sample`` loops) keeps working.  Model units."""
         if self.prediction_type == "epsilon":
             return self._raw_output(x_t, t, conditions, dropout_masks=dropout_masks, seed=seed, guidance_scale=guidance_scale)
         return self.predict(x_t, t, conditions, "eps", dropout_masks=dropout_masks, seed=seed, guidance_scale=guidance_scale)
@@ -822,6 +835,7 @@ class BiologyAwareDiffusionModel(nn.Module):
     # -- p_sample / sample (models/diffusion.py:382-449) ------------------------------------------
     @torch.no_grad()
     def p_sample(self, x_t, t, conditions, *, noise=None, seed: Optional[int] = None):
+        """One reverse step, in model units (a ``feature_transform`` is applied by the generator, never here)."""
         self._refuse_link("p_sample")       # the single step folds x0^ away; sample() runs the x0-unfolded steps
         eng = self._engine()
         x_t = self._prep(x_t, self.data_dim, "x_t")
@@ -840,7 +854,9 @@ class BiologyAwareDiffusionModel(nn.Module):
                row_offset: int = 0, return_mutation_mask: bool = False, num_inference_steps: Optional[int] = None,
                eta: float = 0.0, guidance_scale: float = 1.0, known=None, x0_bounds=None, solver: Optional[str] = None,
                timestep_spacing: str = "uniform"):
-        """Full reverse chain.  ``x_T`` [N,D] and ``noise`` [T-1,N,D] (draw order t = T-1..1) inject the
+        """Full reverse chain, in MODEL units: with ``feature_transform`` set the samples, ``known`` and ``x0_bounds`` are what
+        ``feature_transform.forward`` makes of data (``SyntheticPatientGenerator`` speaks data units and maps both ways).
+        ``x_T`` [N,D] and ``noise`` [T-1,N,D] (draw order t = T-1..1) inject the
         random draws; otherwise Philox(seed, row_offset + row) generates them on the device.
 
         ``num_inference_steps=S`` runs the strided DDIM sampler instead (ddim.py: S of the T timesteps, ``eta`` in [0, 1]

@@ -161,6 +161,10 @@ class SyntheticPatientGenerator:
             return None                 # the config's default speaks to the diffusion sampler
         if x0_bounds is None:
             x0_bounds = (self.config.get("generation") or {}).get("x0_bounds")
+        ft = self._transform()
+        if ft is not None and x0_bounds is not None and x0_bounds is not False:
+            # the caller speaks data units; the sampler clips in model units (the map is monotone)
+            x0_bounds = ft.map_bounds(*assemble_bounds(x0_bounds, self.mutation_dim, self.expression_dim, self.pathway_dim))
         return x0_bounds
 
     def _solver(self, solver, timestep_spacing) -> dict:
@@ -174,11 +178,31 @@ class SyntheticPatientGenerator:
         return {"solver": gen.get("solver") if solver is None else solver,
                 "timestep_spacing": gen.get("timestep_spacing", "uniform") if timestep_spacing is None else timestep_spacing}
 
+    def _transform(self):
+        """The model's feature transform (``model.feature_transform``) or None.  With one, this class speaks
+        data units: ``known`` / ``features`` / ``x0_bounds`` are mapped forward, the samples are mapped back on the device."""
+        return getattr(self.model, "feature_transform", None)
+
     def _known(self, known, n: int):
-        """``known`` of generate / generate_scenarios as the device tensor model.sample takes, or None."""
+        """``known`` of generate / generate_scenarios as ``(model, data)``: the device tensor model.sample takes (model units) and the
+        caller's values (data units) -- one tensor twice without a feature transform --, or ``(None, None)``.  NaN stays NaN."""
         if known is None:
-            return None
-        return torch.from_numpy(assemble_known(known, n, self.mutation_dim, self.expression_dim, self.pathway_dim)).to(self.device)
+            return None, None
+        data = torch.from_numpy(assemble_known(known, n, self.mutation_dim, self.expression_dim, self.pathway_dim)).to(self.device)
+        ft = self._transform()
+        return (data if ft is None else ft.forward(data)), data
+
+    def _to_data_units(self, samples: torch.Tensor, known_data=None) -> torch.Tensor:
+        """The sampler's output in data units: the inverse map on the device, then the observed elements restored from the caller's
+        own values (the inverse of the forward map of a value between two knots can differ from it in the last bits).  Without a
+        feature transform: ``samples`` itself."""
+        ft = self._transform()
+        if ft is None:
+            return samples
+        samples = ft.inverse(samples, out=samples if samples.dtype == torch.float32 and samples.is_contiguous() else None)
+        if known_data is not None:
+            samples = torch.where(torch.isnan(known_data), samples, known_data)
+        return samples
 
     @torch.no_grad()
     def generate(self, num_samples: int, scenario: Optional[Dict] = None, guidance_scale: float = 1.0,
@@ -202,7 +226,11 @@ class SyntheticPatientGenerator:
         ``generation.x0_bounds`` when it has one, else ``model.x0_bounds``; ``False`` switches it off.
         ``solver`` (``"ddim"`` or ``"dpmpp_2m"``, the second-order multistep solver: about the accuracy of twice the DDIM steps; needs
         ``sampling_steps`` and ``eta == 0``) and ``timestep_spacing`` (``"uniform"`` or ``"logsnr"``) as in ``model.sample``.  Defaults:
-        the config's ``generation.solver`` / ``generation.timestep_spacing`` when it has them, else DDIM on uniform steps."""
+        the config's ``generation.solver`` / ``generation.timestep_spacing`` when it has them, else DDIM on uniform steps.
+        A model that carries a feature transform (``model.feature_transform``, from ``data.transform``) is spoken to in DATA units:
+        ``known`` and ``x0_bounds`` are mapped forward, the samples are mapped back on the device before the download (a quantile
+        column's values lie inside its observed range) and the observed elements are restored from the caller's values.  ``x_T`` /
+        ``noise`` are the chain's own draws and ``model.x0_bounds`` is the model's own attribute: model units."""
         x0_bounds = self._x0_bounds(x0_bounds)
         solver_kw = self._solver(solver, timestep_spacing)
         logger.info(f"Generating {num_samples} synthetic patients...")
@@ -225,11 +253,12 @@ class SyntheticPatientGenerator:
             samples = self.model.sample(conditions, num_samples=num_samples).cpu().numpy()
             mutations = (samples[:, :md] > 0.5).astype(float)
         else:
+            kn, kn_data = self._known(known, num_samples)
             samples, mask = self.model.sample(conditions, num_samples=num_samples, seed=seed, row_offset=row_offset,
                                               x_T=x_T, noise=noise, return_mutation_mask=True, num_inference_steps=sampling_steps,
                                               eta=eta, guidance_scale=self._guidance_scale(guidance_scale),
-                                              known=self._known(known, num_samples), x0_bounds=x0_bounds, **solver_kw)
-            samples = samples.cpu().numpy()
+                                              known=kn, x0_bounds=x0_bounds, **solver_kw)
+            samples = self._to_data_units(samples, kn_data).cpu().numpy()
             # (mutations > 0.5).astype(float), evaluated by the last reverse step's epilogue on the device
             mutations = mask.cpu().numpy().astype(float)
         expression = samples[:, md:md + ed]
@@ -270,14 +299,15 @@ class SyntheticPatientGenerator:
             logger.info(f"Scenario: {scenario['conditions']}")
         logger.info(f"Generating {len(scenarios)} x {n} synthetic patients in one batch...")
         conditions = torch.cat([self.create_conditions(n, sc["conditions"]) for sc in scenarios], dim=0)
-        kn = self._known(known, n)
+        kn, kn_data = self._known(known, n)
         if kn is not None:
-            kn = kn.repeat(len(scenarios), 1)
+            kn, kn_data = kn.repeat(len(scenarios), 1), kn_data.repeat(len(scenarios), 1)
         with torch.no_grad():
             samples, mask = self.model.sample(conditions, num_samples=conditions.shape[0], seed=seed, return_mutation_mask=True,
                                               num_inference_steps=sampling_steps, eta=eta,
                                               guidance_scale=self._guidance_scale(guidance_scale), known=kn, x0_bounds=x0_bounds,
                                               **solver_kw)
+        samples = self._to_data_units(samples, kn_data)
         samples, mask, cond_np = samples.cpu().numpy(), mask.cpu().numpy().astype(float), conditions.cpu().numpy()
         md, ed = self.mutation_dim, self.expression_dim
         out = {}
@@ -311,9 +341,11 @@ class SyntheticPatientGenerator:
             raise ValueError(f"features: expected [{n}, D] (one row per condition row)")
         md, ed = self.mutation_dim, self.expression_dim
         with torch.no_grad():
+            kn, kn_data = self._known(features, n)
             samples, mask = self.model.sample(cond, num_samples=n, seed=seed, return_mutation_mask=True, num_inference_steps=sampling_steps,
-                                              eta=eta, guidance_scale=self._guidance_scale(guidance_scale), known=self._known(features, n),
+                                              eta=eta, guidance_scale=self._guidance_scale(guidance_scale), known=kn,
                                               x0_bounds=x0_bounds, **solver_kw)
+            samples = self._to_data_units(samples, kn_data)
         samples = samples.cpu().numpy()
         return {"mutations": mask.cpu().numpy().astype(float), "expression": samples[:, md:md + ed], "pathways": samples[:, md + ed:],
                 "conditions": cond.cpu().numpy()}
@@ -372,7 +404,9 @@ def load_trained_model(checkpoint_path: Path, config: dict, device: str, use_ema
     (``ema_state_dict``) when the file has them, else ``model_state_dict``; False always ``model_state_dict`` (the last iterate);
     True the averaged ones, KeyError when the file has none.
     ``prediction_type`` (what the network was trained to predict) travels in the checkpoint's own config: a ``config`` without the key
-    adopts the checkpoint's, one that names a different type than the checkpoint raises ValueError; ``mutation_link`` likewise."""
+    adopts the checkpoint's, one that names a different type than the checkpoint raises ValueError; ``mutation_link`` likewise, and
+    ``data.transform`` (the checkpoint's ``feature_transform`` tables become ``model.feature_transform``; a config naming another spec
+    raises ValueError)."""
     from .diffusion import BiologyAwareDiffusionModel
     logger.info(f"Loading model from {checkpoint_path}")
     checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
@@ -391,6 +425,11 @@ def load_trained_model(checkpoint_path: Path, config: dict, device: str, use_ema
         raise ValueError(f"Unknown architecture: {arch}")
     saved_pred = checkpoint_prediction_type(checkpoint, config) if arch == "diffusion" else None
     saved_link = checkpoint_mutation_link(checkpoint, config) if arch == "diffusion" else None
+    # data.transform travels as the checkpoint's own tables; a config that names another spec is refused (the prediction_type rule)
+    from .transform import checkpoint_feature_transform, transform_config
+    if arch == "cvae" and (transform_config(config) is not None or "feature_transform" in checkpoint):
+        raise ValueError("data.transform maps the diffusion model's features and is not accepted for a cVAE model")
+    saved_transform = checkpoint_feature_transform(checkpoint, config) if arch == "diffusion" else None
     processed = Path(config["data"]["processed_dir"])
     dims = []
     for fname in ("mutation_matrix_aligned.csv", "expression_matrix_aligned.csv", "pathway_scores.csv"):
@@ -426,6 +465,10 @@ def load_trained_model(checkpoint_path: Path, config: dict, device: str, use_ema
         model.prediction_type = saved_pred
     if saved_link is not None:
         model.mutation_link = saved_link
+    if saved_transform is not None:
+        if saved_transform.blocks != {"mutations": dims[0], "expression": dims[1], "pathways": dims[2]}:
+            raise ValueError(f"the checkpoint's data.transform was fitted on blocks {saved_transform.blocks}, the processed data has {dims}")
+        model.feature_transform = saved_transform
     model.to(device)
     model.eval()
     logger.info("Model loaded successfully!")

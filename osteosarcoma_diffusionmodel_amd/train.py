@@ -715,6 +715,18 @@ class Trainer:
             if cons is not None and (cons["w_pc"] != 0.0 or cons["w_me"] != 0.0):
                 raise ValueError("mutation_link 'logistic' is not supported with the constraint losses: they read the output as x0^ "
                                  "(set their weights to 0 or clear them)")
+        # data.transform: the dataset behind train_loader carries the map prepare_data fitted; the model adopts
+        # it (a plain attribute, like null_condition) so that checkpoints and the generator speak data units.  What has no meaning
+        # behind the map is refused here, before the device
+        from .transform import check_transform_training, training_transform
+        base, _ = ResidentSplit._base_of(getattr(train_loader, "dataset", None))
+        ds_ft = getattr(base, "feature_transform", None)
+        # a model that already carries a map (a loaded checkpoint) must meet data that went through the same one: ValueError otherwise
+        self._dataset_is_raw = isinstance(base, OsteosarcomaDataset) and ds_ft is None
+        ft = training_transform(getattr(model, "feature_transform", None), ds_ft, self._dataset_is_raw)
+        if ft is not None:
+            check_transform_training(model, cons is not None and (cons["w_pc"] != 0.0 or cons["w_me"] != 0.0))
+            model.feature_transform = ft
         self.validation_timesteps = int(tc.get("validation_timesteps", 32))
         if self.validation_timesteps < 2:
             raise ValueError(f"training.validation_timesteps={self.validation_timesteps}: at least 2 (t = 0 and one more)")
@@ -1095,6 +1107,8 @@ class Trainer:
             ckpt["dp_state"] = {"steps": int(self._dp_steps), "noise_multiplier": float(self.dp["noise_multiplier"]),
                                 "max_grad_norm": float(self.dp["max_grad_norm"]), "delta": float(self.dp["delta"]),
                                 "sample_rate": float(self.dp["sample_rate"])}
+        if getattr(self.model, "feature_transform", None) is not None:
+            ckpt["feature_transform"] = self.model.feature_transform.state_dict()
         torch.save(ckpt, self.save_dir / f"checkpoint_epoch_{epoch}.pt")
         if is_best:
             best = self.save_dir / "best_model.pt"
@@ -1109,6 +1123,17 @@ class Trainer:
         if self._ema_depth:
             raise RuntimeError("load_checkpoint inside ema_weights()")
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
+        # data.transform: the file's map is the one its weights were trained behind, and it must be the one this run's data went
+        # through (training_transform's rule); a file without one does not continue behind a map
+        from .transform import FeatureTransform, check_transform_training, training_transform
+        saved_ft = FeatureTransform.from_state_dict(ckpt["feature_transform"]) if "feature_transform" in ckpt else None
+        own_ft = getattr(self.model, "feature_transform", None)
+        if saved_ft is None and own_ft is not None:
+            raise ValueError(f"{path} was trained without data.transform, this run's data went through {own_ft.spec}")
+        resumed_ft = training_transform(saved_ft, own_ft, self._dataset_is_raw)
+        if resumed_ft is not None:
+            cons = getattr(self.model, "_constraints", None)
+            check_transform_training(self.model, cons is not None and (cons["w_pc"] != 0.0 or cons["w_me"] != 0.0))
         if self.dp is not None:
             # a resumed run keeps its account; a file from a run without training.dp starts it at zero.  privacy_spent() prices every
             # step at THIS run's sigma and sample rate, so steps taken under other values cannot be carried over: that would report a
@@ -1133,6 +1158,8 @@ class Trainer:
                 self.ema.num_updates = 0
         if self.dp is not None:
             self._dp_steps = dp_steps
+        if resumed_ft is not None:
+            self.model.feature_transform = resumed_ft
         self._engines_stale()
         return int(ckpt["epoch"])
 
@@ -1197,6 +1224,22 @@ def prepare_data(config: dict):
     val_size = int(len(dataset) * tc["val_split"])
     train_ds, val_ds = torch.utils.data.random_split(dataset, [len(dataset) - val_size, val_size],
                                                      generator=torch.Generator().manual_seed(tc["random_seed"]))
+    # data.transform (transform.py): fitted on the training split's rows only -- the seeded split is the same
+    # on every rank, so data parallel agrees -- and applied to the whole matrix by the device kernel.  Absent: nothing below happens.
+    from . import transform as XF
+    xf = XF.transform_config(config)
+    if xf is not None:
+        if config.get("model", {}).get("architecture") == "cvae":
+            raise ValueError("data.transform maps the diffusion model's features and is not accepted for a cVAE model")
+        blocks = {"mutations": mutation_matrix.shape[1], "expression": expression_matrix.shape[1], "pathways": pathway_scores.shape[1]}
+        rows = torch.as_tensor(train_ds.indices, dtype=torch.int64)
+        ft = XF.FeatureTransform.fit(dataset.data[rows], blocks, xf[0], **({} if xf[1] is None else {"n_quantiles": xf[1]}))
+        if not torch.cuda.is_available():
+            raise RuntimeError("data.transform maps the dataset on a ROCm device; there is no CPU fallback")
+        dataset.raw_data = dataset.data
+        dataset.data = ft.forward(dataset.data.to("cuda")).cpu()
+        dataset.feature_transform = ft
+        logger.info(f"Feature transform: {ft.spec}, {int(ft.levels.shape[0])} quantile levels, fitted on {rows.numel()} training rows")
     # data parallel (torch.distributed initialised, world > 1): the train split is the same on every rank (seeded), each rank
     # then draws its own 1/world of it per epoch -- `batch_size` is per rank, as in the reference's single process
     sampler = None

@@ -1199,7 +1199,8 @@ class BiologicalValidator:
         same ``seed``; holdout ids follow the train ids) and a lower score means "member".  Returns ``auc`` (Mann-Whitney by
         ranks, ties count half, on the host), ``tpr_at_1pct_fpr``, ``advantage`` (max over thresholds of TPR - FPR),
         ``mean_bpd_train`` and ``mean_bpd_holdout``.  0.5 / 0 / 0 is what a model that memorised nothing gives up to sampling
-        noise."""
+        noise.  A model that carries a feature transform (``model.feature_transform``) takes both cohorts in data units: they are
+        mapped forward on the device first."""
         from . import likelihood as LK
         if hasattr(model, "_refuse_link"):
             model._refuse_link("membership_audit")      # it scores with variational_bound, which a linked model does not have
@@ -1211,6 +1212,8 @@ class BiologicalValidator:
             data, cond = (_dev(v, self.device) for v in cohort)
             if data.dim() != 2 or data.shape[0] == 0:
                 raise ValueError(f"{name} data must be [rows >= 1, features]")
+            if getattr(model, "feature_transform", None) is not None:
+                data = model.feature_transform.forward(data)        # cohorts come in data units; the bound is a model-space score
             out = model.variational_bound(data, cond, num_timesteps=num_timesteps, seed=seed, row_offset=offset)
             offset += data.shape[0]
             scores.append(out["bpd"].cpu().numpy())
