@@ -598,6 +598,30 @@ int osd_val_ball_counts(void *stream, int device, const float *Q, int64_t nq, co
  * points v; the statistic is max(dmax, -dmin, 0) / (n1*n2) (p-values follow on the host). */
 int osd_val_ks_extremes(void *stream, int device, const float *real, int64_t n1, const float *synth,
                         int64_t n2, int ld, int nf, int64_t *dmax_out, int64_t *dmin_out);
+/* Per-feature two-sample statistics over ALL D columns of real dev [n1][ld_real] and synth dev [n2][ld_synth] (fp32, row-major,
+ * any base alignment; a column-slice view is read in place).  With a the real column sorted ascending (n1 values) and b the
+ * synthetic one (n2 values), per feature into HOST arrays of D entries:
+ *   ks_dmax, ks_dmin  the extremes over all pooled sample points v of #{a <= v} n2 - #{b <= v} n1: exact integers, the quantity
+ *                     osd_val_ks_extremes returns; KS = max(dmax, -dmin) / (n1 n2)
+ *   w1                the Wasserstein-1 distance by quantile coupling, (1 / (n1 n2)) sum |a_i - b_j| w_ij with the integer weights
+ *                     w_ij = min((i + 1) n2, (j + 1) n1) - max(i n2, j n1) > 0: differences, products and the sum in double, in an
+ *                     order fixed by (n1, n2) -- the same bits on every call and at every chunk_cols
+ *   below, above      #{b < a_0} and #{b > a_(n1 - 1)}: synthetic values outside the real column's range
+ * The columns are transposed, sorted (the segmented radix sort of osd_val_ks_extremes) and compared chunk_cols at a time, so the
+ * workspace does not grow with D; chunk_cols = 0 picks osd_val_marginals_auto_chunk(n1, n2, D).  OSD_EINVAL for a NULL pointer,
+ * n1, n2 or D below 1, an ld below D, a negative chunk_cols, more than 2 * 10^9 rows, or n1 * n2 > 2^53 (up to there every weight
+ * and KS integer converts to double exactly).  Inputs must be finite.  Synchronous. */
+int osd_val_marginals(void *stream, int device, const float *real, int64_t n1, int ld_real, const float *synth,
+                      int64_t n2, int ld_synth, int D, int chunk_cols, int64_t *ks_dmax, int64_t *ks_dmin, double *w1,
+                      int64_t *below, int64_t *above);
+/* The same call, and into phase_ms[3] (host) the device milliseconds of its three phases summed over the chunks: the transposing
+ * gather, the sort, the statistics pass (tools/marginal_bench.py). */
+int osd_val_marginals_timed(void *stream, int device, const float *real, int64_t n1, int ld_real, const float *synth,
+                            int64_t n2, int ld_synth, int D, int chunk_cols, int64_t *ks_dmax, int64_t *ks_dmin,
+                            double *w1, int64_t *below, int64_t *above, double *phase_ms);
+/* The columns per chunk that chunk_cols = 0 stands for (a negative OSD_E* code on a bad argument): the transposed and the sorted
+ * buffer of both cohorts, 8 (n1 + n2) bytes per column, together within 256 MiB, in whole multiples of 64 columns from 64 up. */
+int osd_val_marginals_auto_chunk(int64_t n1, int64_t n2, int D);
 /* Mean of the strict upper triangle of the Pearson matrix of data[:, cols] (utils/validation.py:156-161);
  * cols: host array of g column indices, 2 <= g <= 512. */
 int osd_val_mean_offdiag_corr(void *stream, int device, const float *data, int64_t rows, int ld,

@@ -100,6 +100,10 @@ _SIGNATURES = {
                                           C.c_double, C.c_double, C.c_int64, C.c_double, _P]),
     "osd_val_mmd": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "osd_val_ks_extremes": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "osd_val_marginals": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "osd_val_marginals_timed": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P,
+                                          C.POINTER(C.c_double)]),
+    "osd_val_marginals_auto_chunk": (C.c_int, [C.c_int64, C.c_int64, C.c_int]),
     "osd_val_mean_offdiag_corr": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double)]),
     "osd_val_column_sums": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "osd_val_gram": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double)]),
