@@ -622,6 +622,30 @@ int osd_val_marginals_timed(void *stream, int device, const float *real, int64_t
 /* The columns per chunk that chunk_cols = 0 stands for (a negative OSD_E* code on a bad argument): the transposed and the sorted
  * buffer of both cohorts, 8 (n1 + n2) bytes per column, together within 256 MiB, in whole multiples of 64 columns from 64 up. */
 int osd_val_marginals_auto_chunk(int64_t n1, int64_t n2, int D);
+/* Per-feature two-GROUP rank statistics inside ONE cohort (csrc/diffexp.hip): X dev float [rows][ld] (fp32,
+ * row-major, any base alignment, any ld >= D; a column-slice view is read in place, once), labels dev int32 [rows]: 1 a case, 0 a
+ * control, any other value a row that is ignored.  With a the feature's case values sorted ascending (na of them), b its control
+ * values (nb of them) and c its centre (center: dev float [D], or NULL for 0), per feature into HOST arrays:
+ *   u2      int64 [D]      sum_i (#{b < a_i} + #{b <= a_i}): exactly twice the Mann-Whitney U of the cases over the controls with ties
+ *                          counted 1/2 -- the per-feature AUC is u2 / (2 na nb)
+ *   ties    int64 [D]      sum over the distinct values v of the pooled column of t_v^3 - t_v, t_v the number of pooled values equal
+ *                          to v: the tie correction of the normal approximation (-0.0 and +0.0 are one value)
+ *   sum, sumsq  double [2][D]   sum (x - c) and sum (x - c)^2 over the cases ([0][j]) and over the controls ([1][j]): the difference
+ *                          and the square in double, summed over the SORTED values in an order fixed by (na, nb)
+ *   na, nb  int64 [1]      the group sizes (written before the group checks below)
+ * Integer results are exact.  No atomics, and the partition of the work depends on (na, nb) alone: the same bits on every call, at
+ * every chunk_cols and for every permutation of the rows.  The columns are gathered by label, sorted (the segmented radix sort of
+ * osd_val_ks_extremes) and compared chunk_cols at a time; chunk_cols = 0 picks osd_val_marginals_auto_chunk(na, nb, D).
+ * OSD_EINVAL for a NULL pointer (center excepted), rows or D below 1, an ld below D, a negative chunk_cols, more than 2 * 10^9 rows,
+ * na == 0 or nb == 0, or na + nb > 2^20 (up to there ties stays below 2^60).  Inputs must be finite.  Synchronous. */
+int osd_val_group_ranks(void *stream, int device, const float *X, int64_t rows, int ld, int D, const int32_t *labels,
+                        const float *center, int chunk_cols, int64_t *u2, int64_t *ties, double *sum, double *sumsq,
+                        int64_t *na, int64_t *nb);
+/* The same call, and into phase_ms[3] (host) the device milliseconds of its three phases summed over the chunks: the
+ * label-partitioned gather, the sort, the statistics pass (tools/diffexp_bench.py). */
+int osd_val_group_ranks_timed(void *stream, int device, const float *X, int64_t rows, int ld, int D, const int32_t *labels,
+                              const float *center, int chunk_cols, int64_t *u2, int64_t *ties, double *sum, double *sumsq,
+                              int64_t *na, int64_t *nb, double *phase_ms);
 /* Mean of the strict upper triangle of the Pearson matrix of data[:, cols] (utils/validation.py:156-161);
  * cols: host array of g column indices, 2 <= g <= 512. */
 int osd_val_mean_offdiag_corr(void *stream, int device, const float *data, int64_t rows, int ld,

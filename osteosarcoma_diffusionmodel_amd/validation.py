@@ -28,6 +28,7 @@ import torch
 
 from . import _lib as L
 from . import cluster as CL
+from . import diffexp as DE
 from . import survival as SV
 from . import utility as U
 from .cluster import subtype_summary      # noqa: F401  (the subtype_* figures: pure NumPy, documented there)
@@ -231,6 +232,35 @@ class DeviceKernels:
         else:
             L.check(L.lib().osd_val_marginals(*args))
         res = dict(zip(MARGINAL_FIELDS, outs))
+        if phases:
+            res["phase_ms"] = np.array(ms[:])
+        return res
+
+    def group_ranks(self, t: torch.Tensor, labels: torch.Tensor, center=None, chunk_cols: int = 0, phases: bool = False):
+        """``osd_val_group_ranks`` on the fp32 device tensor t [rows, D] (a column-slice view is read in place) and the int32 labels
+        [rows] -- 1 a case, 0 a control, anything else ignored: a dictionary of numpy arrays, per feature ``u2`` (int64 [D], twice the
+        Mann-Whitney U of the cases over the controls, ties counted 1/2), ``ties`` (int64 [D], the sum of t^3 - t over the tie groups
+        of the pooled column) and ``sum``, ``sumsq`` (float64 [2, D]: cases, controls; of x - c and its square), plus the group
+        sizes ``na`` and ``nb``.  ``center``: D values rounded to fp32, or None for 0.  ``chunk_cols``: columns sorted at a time (0:
+        the library's choice).  ``phases=True`` adds ``phase_ms``, the device milliseconds of (gather, sort, statistics).  The same
+        bits at every ``chunk_cols``, on every call and for every order of the rows.  An empty group is a ValueError."""
+        t = _rows_view(t)
+        rows, D = t.shape
+        labels = labels.to(device=t.device, dtype=torch.int32).contiguous()
+        if labels.shape != (rows,):
+            raise ValueError(f"labels must hold one label per row ({rows})")
+        c = None if center is None else _f32(center, t.device, (D,), "center")
+        u2, ties = np.zeros(D, dtype=np.int64), np.zeros(D, dtype=np.int64)
+        s, q = np.zeros((2, D), dtype=np.float64), np.zeros((2, D), dtype=np.float64)
+        na, nb = C.c_int64(), C.c_int64()
+        args = [self._stream(), self.index, L.ptr(t), rows, max(int(t.stride(0)), D), D, L.ptr(labels), L.ptr(c), int(chunk_cols)]
+        args += [C.c_void_p(o.ctypes.data) for o in (u2, ties, s, q)] + [C.c_void_p(C.addressof(na)), C.c_void_p(C.addressof(nb))]
+        if phases:
+            ms = (C.c_double * 3)()
+            L.check(L.lib().osd_val_group_ranks_timed(*args, ms))
+        else:
+            L.check(L.lib().osd_val_group_ranks(*args))
+        res = {"u2": u2, "ties": ties, "sum": s, "sumsq": q, "na": int(na.value), "nb": int(nb.value)}
         if phases:
             res["phase_ms"] = np.array(ms[:])
         return res
@@ -1234,6 +1264,53 @@ class BiologicalValidator:
         rows.update(ks=ks, w1_scaled=scaled, worst_ks=np.argsort(-ks, kind="stable")[:10], bounds=bounds, names=names)
         return summary, rows
 
+    # -- differential signal: per-feature rank statistics of two groups inside each cohort -------------------
+    def differential_fidelity(self, real, real_cond, synthetic, synth_cond, names=None, blocks=None, alpha: float = 0.05,
+                              top_k: int = 50, return_rows: bool = False):
+        """Do the features that separate two groups of real patients separate them in ``synthetic`` too, in the same direction and by
+        the same amount?  Every column of the condition matrices is one contrast: a column whose values all lie in {0, 1} in both
+        cohorts is used as it is (1 a case, 0 a control); any other column is split at the REAL cohort's median, and the SAME
+        threshold is applied to the synthetic cohort (a case is a value above it).  Per contrast and cohort one
+        ``DeviceKernels.group_ranks`` call gives every feature's Mann-Whitney U with mid-ranks for ties -- the statistic has to be
+        rank-based: the expression block is zero-inflated --, its tie correction and the groups' moments; ``diffexp.group_statistics``
+        turns them into AUC, rank-biserial effect, z, p, Benjamini-Hochberg q, mean difference, Welch t and Cohen's d, and
+        ``diffexp.contrast_summary`` compares the cohorts.  Keys, per contrast ``de_<key>_<contrast>``: ``effect_pearson``,
+        ``effect_spearman``, ``effect_slope`` (below 1 the signal is flattened, above 1 exaggerated), ``sign_agreement`` over the real
+        hits (q < ``alpha``), ``real_hits``, ``synth_hits``, ``precision``, ``recall``, ``topk_jaccard`` (``top_k`` features by
+        |effect|), ``false_signal_share``, ``max_abs_effect_gap``, ``max_gap_feature`` and, with ``blocks`` (an ordered
+        ``{name: width}`` mapping, as in ``correlation_fidelity``), ``effect_pearson_<block>``; then ``de_<key>_mean`` over the
+        contrasts, ``de_contrasts`` and ``de_skipped``: a contrast with an empty group in either cohort is skipped and counted there.
+        ``names``: one per condition column (default: the columns of ``real_cond``, else c0, c1, ...).  ``return_rows=True`` also
+        returns, per contrast, both cohorts' per-feature arrays and the threshold.  At most 2^20 rows per cohort.  On a
+        ``sharded=True`` validator the method raises a ValueError: the pairs of a U statistic couple rows across shards."""
+        if self.sharded:
+            raise ValueError("differential_fidelity is not available on a sharded validator: a U statistic counts pairs of rows, "
+                             "which couples the rows of different shards")
+        if names is None:
+            cols = getattr(real_cond, "columns", None)
+            names = [str(c) for c in cols] if cols is not None else None
+        x, y = _dev(real, self.device), _dev(synthetic, self.device)
+        cs = [np.asarray(_host(a), dtype=np.float64) for a in (real_cond, synth_cond)]
+        cs = [c.reshape(-1, 1) if c.ndim == 1 else c for c in cs]
+        K = cs[0].shape[1] if cs[0].ndim == 2 else 0
+        if names is None:
+            names = [f"c{j}" for j in range(K)]
+        names = [str(v) for v in names]
+        if K < 1 or len(names) != K or len(set(names)) != K or "mean" in names:
+            raise ValueError("one distinct name per condition column (none of them 'mean'), and at least one condition")
+        for label, t, c in zip(("real", "synthetic"), (x, y), cs):
+            if t.dim() != 2 or t.shape[1] != x.shape[1] or t.shape[1] < 1 or t.shape[0] < 1:
+                raise ValueError(f"{label} must be [rows >= 1, {x.shape[1]}]: the cohorts must have the same features")
+            if c.ndim != 2 or c.shape != (t.shape[0], K):
+                raise ValueError(f"the conditions of {label} must be [{t.shape[0]}, {K}], got {c.shape}")
+            if not (bool(torch.isfinite(t).all().item()) and np.isfinite(c).all()):
+                raise ValueError(f"{label} holds non-finite values")
+        if not 0.0 < float(alpha) <= 1.0 or int(top_k) < 1:
+            raise ValueError("alpha must lie in (0, 1] and top_k must be at least 1")
+        bounds, block_names = corr_block_bounds(blocks, int(x.shape[1]))
+        summary, rows = DE.differential_metrics(self.k, x, cs[0], y, cs[1], names, bounds, block_names, float(alpha), int(top_k))
+        return (summary, rows) if return_rows else summary
+
     # -- downstream utility: TSTR and the classifier two-sample test (no counterpart in the reference; DESIGN.md section 3.22) ------
     def downstream_utility(self, real_train, real_train_cond, synthetic, synth_cond, real_test, real_test_cond, names=None,
                            l2: float = 1e-2, max_iter: int = 200, tol: float = 1e-5) -> Dict[str, float]:
@@ -1502,8 +1579,11 @@ class BiologicalValidator:
                      pathway_gene_matrix=None, privacy: bool = False, holdout=None, model=None, membership=None,
                      prdc: bool = False, prdc_k: int = 5, correlation: bool = False, frechet: bool = False,
                      corr_strong: float = 0.3, utility=None, c2st: bool = False, subtypes: Optional[int] = None,
-                     subtype_conditions=None, survival=None, marginals: bool = False) -> Dict[str, float]:
-        """``marginals=True`` adds ``marginal_fidelity``'s ``marginal_*`` keys over every column of the combined matrices (blocks
+                     subtype_conditions=None, survival=None, marginals: bool = False, differential=None,
+                     differential_names=None) -> Dict[str, float]:
+        """``differential=(real_cond, synth_cond)`` adds ``differential_fidelity``'s ``de_*`` keys on the combined matrices (blocks
+        ``mutations`` / ``expression`` / ``pathways``; ``differential_names``: its ``names``); with the default None nothing changes.
+        ``marginals=True`` adds ``marginal_fidelity``'s ``marginal_*`` keys over every column of the combined matrices (blocks
         ``mutations`` / ``expression`` / ``pathways`` from the three frames' widths).
         ``survival=(real_train_surv, synth_surv, real_test, real_test_surv)`` adds ``survival_utility``'s ``survival_*`` keys, the
         cohorts as for ``utility=``: the combined real matrix trains, ``real_test`` is a (mutations, expression, pathways) triple
@@ -1584,6 +1664,12 @@ class BiologicalValidator:
         if marginals:
             widths = {"mutations": parts_r[0].shape[1], "expression": parts_r[1].shape[1], "pathways": parts_r[2].shape[1]}
             all_results.update(self.marginal_fidelity(real_combined, synth_combined, blocks=widths))
+        if differential is not None:
+            if not isinstance(differential, (tuple, list)) or len(differential) != 2:
+                raise ValueError("validate_all(differential=...) needs (real_cond, synth_cond)")
+            widths = {"mutations": parts_r[0].shape[1], "expression": parts_r[1].shape[1], "pathways": parts_r[2].shape[1]}
+            all_results.update(self.differential_fidelity(real_combined, differential[0], synth_combined, differential[1],
+                                                          names=differential_names, blocks=widths))
         logger.info("=" * 50)
         logger.info("VALIDATION SUMMARY")
         logger.info("=" * 50)
