@@ -646,6 +646,32 @@ int osd_val_group_ranks(void *stream, int device, const float *X, int64_t rows, 
 int osd_val_group_ranks_timed(void *stream, int device, const float *X, int64_t rows, int ld, int D, const int32_t *labels,
                               const float *center, int chunk_cols, int64_t *u2, int64_t *ties, double *sum, double *sumsq,
                               int64_t *na, int64_t *nb, double *phase_ms);
+/* The permutation null of preranked gene-set enrichment analysis (csrc/gsea.hip).  All arrays are HOST
+ * arrays.  weights_host double [D]: the weight of every position of the ranked gene list (|statistic| ** weight; all ones is the
+ * classic Kolmogorov-Smirnov form).  Set s holds the ranked positions set_positions_host[set_offsets_host[s] ..
+ * set_offsets_host[s + 1]) (set_offsets_host int32 [S + 1], starting at 0), in any order, k of them.  With its hit positions
+ * ascending h_0 < ... < h_{k-1}, C_j = w[h_0] + ... + w[h_j] added one after another in double (C_{-1} = 0) and NR = C_{k-1}:
+ *   up_j = C_j / NR - (h_j - j) / (D - k)        dn_j = C_{j-1} / NR - (h_j - j) / (D - k)
+ * (two divisions and one subtraction each; with NR == 0 the ratios are (j + 1) / k and j / k), and
+ *   es_pos_host  double [permutations + 1][S]   max_j up_j
+ *   es_neg_host  double [permutations + 1][S]   min_j dn_j
+ *   lead_host    int32 [S][2]                   row 0 only: the first j that attains the maximum, the first that attains the minimum
+ * Row 0 takes the positions as they are.  Row p >= 1 moves position i to rho_p(i), the rank of the pair (key_p(i), i) among all D
+ * such pairs -- key_p(i) is word 0 of the Philox4x32-10 block at counter (i, p, 0, 0x47534500) under the key (seed) -- so every set
+ * sees the same permutation of the gene labels and overlapping sets stay correlated.  The permutations go through perm_chunk at a
+ * time (0: as many as fill 64 MiB of workspace, which therefore does not grow with `permutations`); no atomics: the same bits at
+ * every perm_chunk and on every call, and equal to the float64 restatement of the definition bit for bit.  The ranks come from a
+ * sort of the keys in LDS; with OSD_GSEA_RANKS=count in the environment they are counted instead (slower, the same bits).
+ * OSD_EINVAL for a NULL pointer, D outside [2, 32768], S < 1, a set with k < 1, k > 1024 or k >= D, a position outside [0, D) or
+ * repeated inside a set, a weight that is negative, not finite or above 1e100, permutations < 0 or perm_chunk < 0.  Synchronous. */
+int osd_val_gsea(void *stream, int device, const double *weights_host, int D, const int32_t *set_offsets_host,
+                 const int32_t *set_positions_host, int S, int permutations, uint64_t seed, int perm_chunk, double *es_pos_host,
+                 double *es_neg_host, int32_t *lead_host);
+/* The same call, and into phase_ms3[3] (host) the device milliseconds of its three phases summed over the chunks: keys and ranks,
+ * the hit sort, the running-sum scan (tools/gsea_bench.py). */
+int osd_val_gsea_timed(void *stream, int device, const double *weights_host, int D, const int32_t *set_offsets_host,
+                       const int32_t *set_positions_host, int S, int permutations, uint64_t seed, int perm_chunk, double *es_pos_host,
+                       double *es_neg_host, int32_t *lead_host, float *phase_ms3);
 /* Mean of the strict upper triangle of the Pearson matrix of data[:, cols] (utils/validation.py:156-161);
  * cols: host array of g column indices, 2 <= g <= 512. */
 int osd_val_mean_offdiag_corr(void *stream, int device, const float *data, int64_t rows, int ld,

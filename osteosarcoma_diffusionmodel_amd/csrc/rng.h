@@ -13,6 +13,7 @@ enum : uint32_t {
   TAG_TSTEP = 0x54535400u,      // randint timesteps
   TAG_DROPOUT = 0x44524f00u,    // + block index in the low byte
   TAG_COND_DROP = TAG_DROPOUT + 0x80u,   // condition dropout of a training batch: one draw per row (block indices stay below 0x80)
+  TAG_GSEA = 0x47534500u,       // sort keys of a gene-label permutation (gsea.hip): row = ranked position, col4 = permutation number
   TAG_USER = 0x55535200u,
 };
 

@@ -29,6 +29,7 @@ import torch
 from . import _lib as L
 from . import cluster as CL
 from . import diffexp as DE
+from . import enrichment as EN
 from . import survival as SV
 from . import utility as U
 from .cluster import subtype_summary      # noqa: F401  (the subtype_* figures: pure NumPy, documented there)
@@ -263,6 +264,42 @@ class DeviceKernels:
         res = {"u2": u2, "ties": ties, "sum": s, "sumsq": q, "na": int(na.value), "nb": int(nb.value)}
         if phases:
             res["phase_ms"] = np.array(ms[:])
+        return res
+
+    def gsea(self, weights, set_positions, permutations: int, seed: int = 0, perm_chunk: int = 0, phases: bool = False):
+        """``osd_val_gsea``: the running-sum extremes of S gene sets under the identity and ``permutations`` gene-label permutations.
+        ``weights``: float64 [D], the weight of every position of the ranked list; ``set_positions``: per set an integer array of
+        its members' ranked positions, in any order.  A dictionary of numpy arrays: ``es_pos`` and ``es_neg`` (float64
+        [permutations + 1, S], row 0 observed) and ``lead`` (int32 [S, 2]: the first hit number, counted along the set's sorted
+        hits, that attains the observed maximum and minimum).  ``perm_chunk``: permutations per workspace chunk (0: the library's
+        choice); ``phases=True`` adds ``phase_ms``, the device milliseconds of (keys and ranks, hit sort, scan).  The same bits at
+        every ``perm_chunk`` and on every call.  A ValueError for what the library refuses: D outside [2, 32768], no set, a set
+        with no member, more than 1024 or all D positions, a position outside [0, D) or repeated in a set, a weight that is
+        negative, not finite or above 1e100, a negative ``permutations`` or ``perm_chunk``."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim != 1:
+            raise ValueError("weights must be a vector")
+        sets = [np.ascontiguousarray(np.asarray(m).reshape(-1), dtype=np.int64) for m in set_positions]
+        D, S, P = int(w.shape[0]), len(sets), int(permutations)
+        if S < 1 or P < 0 or int(perm_chunk) < 0:
+            raise ValueError("at least one set, permutations >= 0 and perm_chunk >= 0 are needed")
+        if any(m.size and (m.min() < -2 ** 31 or m.max() >= 2 ** 31) for m in sets) or sum(m.size for m in sets) >= 2 ** 31:
+            raise ValueError("set positions must fit 32 bits")
+        offsets = np.zeros(S + 1, dtype=np.int32)
+        offsets[1:] = np.cumsum([m.size for m in sets])
+        flat = np.ascontiguousarray(np.concatenate(sets), dtype=np.int32) if offsets[-1] else np.zeros(1, dtype=np.int32)
+        es_pos, es_neg = np.zeros((P + 1, S), dtype=np.float64), np.zeros((P + 1, S), dtype=np.float64)
+        lead = np.zeros((S, 2), dtype=np.int32)
+        args = [self._stream(), self.index, C.c_void_p(w.ctypes.data), D, C.c_void_p(offsets.ctypes.data), C.c_void_p(flat.ctypes.data),
+                S, P, int(seed) & (2 ** 64 - 1), int(perm_chunk)] + [C.c_void_p(o.ctypes.data) for o in (es_pos, es_neg, lead)]
+        if phases:
+            ms = (C.c_float * 3)()
+            L.check(L.lib().osd_val_gsea_timed(*args, ms))
+        else:
+            L.check(L.lib().osd_val_gsea(*args))
+        res = {"es_pos": es_pos, "es_neg": es_neg, "lead": lead}
+        if phases:
+            res["phase_ms"] = np.array(ms[:], dtype=np.float64)
         return res
 
     def col_moments(self, t: torch.Tensor, cols: Sequence[int]):
@@ -1311,6 +1348,60 @@ class BiologicalValidator:
         summary, rows = DE.differential_metrics(self.k, x, cs[0], y, cs[1], names, bounds, block_names, float(alpha), int(top_k))
         return (summary, rows) if return_rows else summary
 
+    # -- pathway enrichment: preranked GSEA with a device permutation null ------------------------------------
+    def enrichment_fidelity(self, real, real_cond, synthetic, synth_cond, gene_sets, names=None, weight: float = 1.0,
+                            permutations: int = 1000, min_size: int = 5, max_size: int = 500, alpha: float = 0.05, seed: int = 0,
+                            return_rows: bool = False):
+        """Is a gene set up or down between two groups of synthetic patients as it is between the real ones?  Preranked gene-set
+        enrichment analysis per cohort and contrast (the contrasts as in ``differential_fidelity``: every column of the condition
+        matrices, a 0/1 column as it is, any other split at the REAL cohort's median): the genes -- the columns of ``real`` and
+        ``synthetic`` -- are ranked by the Mann-Whitney z of ``diffexp.cohort_statistics``, a position weighs |z| ** ``weight``
+        (0: the classic Kolmogorov-Smirnov form), and one ``DeviceKernels.gsea`` call gives every set's enrichment score under the
+        identity and under ``permutations`` gene-label permutations shared by all sets (``seed``); ``enrichment.py`` turns them into
+        ES, NES, p, Benjamini-Hochberg q and the leading-edge size and compares the cohorts.  ``gene_sets``: an ordered
+        ``{name: column indices}`` mapping, or a [D, S] 0/1 matrix or DataFrame whose columns name the sets; members are
+        de-duplicated, and a set with fewer than ``min_size`` or more than min(``max_size``, 1024, D - 1) members is dropped and
+        counted in ``gsea_sets_skipped`` (no set left: a ValueError).  Keys, per contrast ``gsea_<key>_<contrast>``:
+        ``nes_pearson``, ``nes_spearman``, ``nes_slope``, ``sign_agreement`` over the real hits (q < ``alpha``), ``real_hits``,
+        ``synth_hits``, ``precision``, ``recall``, ``false_signal_share``, ``max_abs_nes_gap``, ``max_gap_set`` (an index into the
+        kept sets); then ``gsea_<key>_mean`` over the contrasts, ``gsea_contrasts``, ``gsea_skipped``, ``gsea_sets`` and
+        ``gsea_sets_skipped``.  ``return_rows=True`` also returns, per contrast, both cohorts' per-set arrays, plus ``sets``, the kept
+        sets' names.  At most 32768 columns.  On a ``sharded=True`` validator the method raises a ValueError: the U statistic
+        underneath couples rows across shards."""
+        if self.sharded:
+            raise ValueError("enrichment_fidelity is not available on a sharded validator: the U statistic that ranks the genes "
+                             "counts pairs of rows, which couples the rows of different shards")
+        if names is None:
+            cols = getattr(real_cond, "columns", None)
+            names = [str(c) for c in cols] if cols is not None else None
+        x, y = _dev(real, self.device), _dev(synthetic, self.device)
+        cs = [np.asarray(_host(a), dtype=np.float64) for a in (real_cond, synth_cond)]
+        cs = [c.reshape(-1, 1) if c.ndim == 1 else c for c in cs]
+        K = cs[0].shape[1] if cs[0].ndim == 2 else 0
+        if names is None:
+            names = [f"c{j}" for j in range(K)]
+        names = [str(v) for v in names]
+        if K < 1 or len(names) != K or len(set(names)) != K or "mean" in names:
+            raise ValueError("one distinct name per condition column (none of them 'mean'), and at least one condition")
+        for label, t, c in zip(("real", "synthetic"), (x, y), cs):
+            if t.dim() != 2 or t.shape[1] != x.shape[1] or t.shape[1] < 2 or t.shape[0] < 1:
+                raise ValueError(f"{label} must be [rows >= 1, {x.shape[1]}]: the cohorts must have the same features, two at least")
+            if c.ndim != 2 or c.shape != (t.shape[0], K):
+                raise ValueError(f"the conditions of {label} must be [{t.shape[0]}, {K}], got {c.shape}")
+            if not (bool(torch.isfinite(t).all().item()) and np.isfinite(c).all()):
+                raise ValueError(f"{label} holds non-finite values")
+        if not 0.0 < float(alpha) <= 1.0 or int(permutations) < 0 or not 0.0 <= float(weight) <= 16.0:
+            raise ValueError("alpha must lie in (0, 1], permutations must not be negative and weight must lie in [0, 16]")
+        if x.shape[1] > 32768:
+            raise ValueError("enrichment_fidelity ranks at most 32768 columns")
+        set_names, sets, dropped = EN.select_sets(gene_sets, int(x.shape[1]), int(min_size), int(max_size))
+        if not sets:
+            raise ValueError("no gene set is left between min_size and max_size")
+        summary, rows = EN.enrichment_metrics(self.k, x, cs[0], y, cs[1], names, sets, float(weight), int(permutations), float(alpha),
+                                              int(seed), dropped)
+        rows["sets"] = set_names
+        return (summary, rows) if return_rows else summary
+
     # -- downstream utility: TSTR and the classifier two-sample test (no counterpart in the reference; DESIGN.md section 3.22) ------
     def downstream_utility(self, real_train, real_train_cond, synthetic, synth_cond, real_test, real_test_cond, names=None,
                            l2: float = 1e-2, max_iter: int = 200, tol: float = 1e-5) -> Dict[str, float]:
@@ -1580,8 +1671,13 @@ class BiologicalValidator:
                      prdc: bool = False, prdc_k: int = 5, correlation: bool = False, frechet: bool = False,
                      corr_strong: float = 0.3, utility=None, c2st: bool = False, subtypes: Optional[int] = None,
                      subtype_conditions=None, survival=None, marginals: bool = False, differential=None,
-                     differential_names=None) -> Dict[str, float]:
-        """``differential=(real_cond, synth_cond)`` adds ``differential_fidelity``'s ``de_*`` keys on the combined matrices (blocks
+                     differential_names=None, enrichment=None, enrichment_names=None,
+                     enrichment_permutations: int = 1000) -> Dict[str, float]:
+        """``enrichment=(real_cond, synth_cond)`` adds ``enrichment_fidelity``'s ``gsea_*`` keys on the expression frames; it needs
+        ``pathway_gene_matrix`` (genes x pathways 0/1, a DataFrame), which is reindexed to the expression columns -- genes that are
+        not among them drop out of their sets (``enrichment_names``: its ``names``; ``enrichment_permutations``: its
+        ``permutations``); with the default None nothing changes.
+        ``differential=(real_cond, synth_cond)`` adds ``differential_fidelity``'s ``de_*`` keys on the combined matrices (blocks
         ``mutations`` / ``expression`` / ``pathways``; ``differential_names``: its ``names``); with the default None nothing changes.
         ``marginals=True`` adds ``marginal_fidelity``'s ``marginal_*`` keys over every column of the combined matrices (blocks
         ``mutations`` / ``expression`` / ``pathways`` from the three frames' widths).
@@ -1670,6 +1766,18 @@ class BiologicalValidator:
             widths = {"mutations": parts_r[0].shape[1], "expression": parts_r[1].shape[1], "pathways": parts_r[2].shape[1]}
             all_results.update(self.differential_fidelity(real_combined, differential[0], synth_combined, differential[1],
                                                           names=differential_names, blocks=widths))
+        if enrichment is not None:
+            if not isinstance(enrichment, (tuple, list)) or len(enrichment) != 2:
+                raise ValueError("validate_all(enrichment=...) needs (real_cond, synth_cond)")
+            if pathway_gene_matrix is None or not hasattr(pathway_gene_matrix, "reindex"):
+                raise ValueError("validate_all(enrichment=...) needs pathway_gene_matrix, a genes x pathways DataFrame")
+            genes = [str(c) for c in real_expression.columns]
+            if [str(c) for c in synth_expression.columns] != genes:
+                raise ValueError("validate_all(enrichment=...) needs the same expression columns in both cohorts")
+            membership_matrix = pathway_gene_matrix.reindex(list(real_expression.columns)).fillna(0)
+            all_results.update(self.enrichment_fidelity(real_expression.values, enrichment[0], synth_expression.values, enrichment[1],
+                                                        membership_matrix, names=enrichment_names,
+                                                        permutations=int(enrichment_permutations)))
         logger.info("=" * 50)
         logger.info("VALIDATION SUMMARY")
         logger.info("=" * 50)
