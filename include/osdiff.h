@@ -672,6 +672,39 @@ int osd_val_gsea(void *stream, int device, const double *weights_host, int D, co
 int osd_val_gsea_timed(void *stream, int device, const double *weights_host, int D, const int32_t *set_offsets_host,
                        const int32_t *set_positions_host, int S, int permutations, uint64_t seed, int perm_chunk, double *es_pos_host,
                        double *es_neg_host, int32_t *lead_host, float *phase_ms3);
+/* Per-patient pathway scores (csrc/pathway.hip).  X dev float [rows][ld] (fp32, row-major, any base
+ * alignment, any ld >= D; a column-slice view is read in place, once).  Set s holds the m distinct columns set_members_host[
+ * set_offsets_host[s] .. set_offsets_host[s + 1]) (HOST arrays, set_offsets_host int32 [S + 1] starting at 0).  Every score is a
+ * function of its row alone, into out dev double [rows][S]:
+ *   method 0 (mean)    (sum_j (x_j - c_j) s_j) / m          c = center, s = scale: dev float [D], or NULL for 0 and for 1
+ *   method 1 (zscore)  (sum_j (x_j - c_j) s_j) / sqrt(m)    the combined z-score of Lee et al. 2008 with c the cohort's mean and s 1 / sd
+ *   method 2 (ssgsea)  sum_j r_j T[2 r_j] / sum_j T[2 r_j] - (D (D + 1) / 2 - sum_j r_j) / (D - m)
+ * the differences, products and sums in double.  r_g is the ascending mid-rank of x_g among the row's D values (1 ... D, ties
+ * averaged, -0.0 and +0.0 equal, +-inf ordered as values): 2 r_g = #{x < x_g} + #{x <= x_g} + 1 is an exact integer, and
+ * rank_table_host double [2 D + 1] (HOST; method 2 only, else it may be NULL) holds T[k] = (k / 2)^alpha -- the enrichment score of
+ * Barbie et al. 2009 as the sum over the walk's positions of P_hit - P_miss.  A row that holds a NaN gets NaN for all its ssgsea
+ * scores; the linear methods propagate NaN by IEEE arithmetic.  row_chunk rows go into one launch (0: up to 2^20).  No atomics, a
+ * fixed order of every sum: the same bits on every call, at every row_chunk and from the _timed twin; a permutation of the rows
+ * permutes the outputs and a set listed twice gets the same bits twice.
+ * OSD_EINVAL for a NULL pointer (center and scale excepted), a method outside 0 .. 2, D outside [2, 32768], rows < 1, ld < D, S < 1,
+ * row_chunk < 0, a set with m < 1, m > 1024 or m >= D, a member outside [0, D) or repeated inside a set.  Synchronous. */
+int osd_val_pathway_scores(void *stream, int device, const float *X, int64_t rows, int ld, int D, int method, const float *center,
+                           const float *scale, const int32_t *set_offsets_host, const int32_t *set_members_host, int S,
+                           const double *rank_table_host, int row_chunk, double *out);
+/* The same call, and into phase_ms2[2] (host) the device milliseconds of its two phases: the staging of the tables, the scoring
+ * launches (tools/pathway_bench.py). */
+int osd_val_pathway_scores_timed(void *stream, int device, const float *X, int64_t rows, int ld, int D, int method, const float *center,
+                                 const float *scale, const int32_t *set_offsets_host, const int32_t *set_members_host, int S,
+                                 const double *rank_table_host, int row_chunk, double *out, float *phase_ms2);
+/* A generated pathway block against the scores of the same patients' expression (csrc/pathway.hip): scores dev double [rows][S],
+ * block dev float [rows][ld_b] (its first S columns are used), mu_host and isd_host HOST double [S].  With z = (score - mu) * isd
+ * and g the block's value, over the rows where both are finite, into sums_host HOST double [S][6] per pathway
+ *   sum z, sum g, sum z^2, sum g^2, sum z g, sum (g - z)^2
+ * and into used_host HOST int64 [S] the number of those rows (rows - used_host[s] were left out).  Sums in double, no atomics, in
+ * an order fixed by `rows`: the same bits on every call.
+ * OSD_EINVAL for a NULL pointer, rows < 1, S outside [1, 65535] or ld_b < S.  Synchronous. */
+int osd_val_pathway_agreement(void *stream, int device, const double *scores, int64_t rows, int S, const float *block, int ld_b,
+                              const double *mu_host, const double *isd_host, double *sums_host, int64_t *used_host);
 /* Mean of the strict upper triangle of the Pearson matrix of data[:, cols] (utils/validation.py:156-161);
  * cols: host array of g column indices, 2 <= g <= 512. */
 int osd_val_mean_offdiag_corr(void *stream, int device, const float *data, int64_t rows, int ld,

@@ -110,6 +110,10 @@ _SIGNATURES = {
     "osd_val_gsea": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_uint64, C.c_int, _P, _P, _P]),
     "osd_val_gsea_timed": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_uint64, C.c_int, _P, _P, _P,
                                      C.POINTER(C.c_float)]),
+    "osd_val_pathway_scores": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P]),
+    "osd_val_pathway_scores_timed": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P,
+                                               C.POINTER(C.c_float)]),
+    "osd_val_pathway_agreement": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
     "osd_val_mean_offdiag_corr": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double)]),
     "osd_val_column_sums": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "osd_val_gram": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double)]),

@@ -7,7 +7,7 @@
 // block at (seed; i, p, 0, TAG_GSEA); rho_0 is the identity.  The host de-duplicates the positions that some set uses (U <= D of
 // them) and states every member as an index into that list; the permutations then go through perm_chunk at a time.  Per chunk:
 //   gs_ranks_sort   one workgroup per permutation: the D keys into LDS (padded to a power of two with the largest key) and, unsorted,
-//                   into global memory; a bitonic sort in LDS, two distances per pass on four keys per lane; rho_p of a used
+//                   into global memory; the bitonic sort of lds_sort.h (shared with pathway.hip); rho_p of a used
 //                   position is the lower bound of its key, and where the next sorted key equals it -- a 32-bit collision, or a
 //                   key equal to the padding -- the number of smaller indices that carry the key is added from the unsorted copy.
 //   gs_ranks_count  the alternative (OSD_GSEA_RANKS=count in the environment; DESIGN.md has both timings): the D keys in LDS, one
@@ -27,6 +27,7 @@
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "handle.h"
+#include "lds_sort.h"
 #include "rng.h"
 #include "val_common.h"
 
@@ -43,11 +44,6 @@ constexpr size_t GS_WORKSPACE = 64u << 20; // bytes the automatic perm_chunk fil
 constexpr uint32_t GS_PAD_KEY = 0xFFFFFFFFu;
 
 __device__ __forceinline__ uint32_t gs_key(uint64_t seed, int i, int p) { return philox_at(seed, (uint32_t)i, (uint32_t)p, 0u, TAG_GSEA).x; }
-
-// a and b in ascending (asc) or descending order
-__device__ __forceinline__ void gs_order(uint32_t& a, uint32_t& b, bool asc) {
-  if ((a > b) == asc) { const uint32_t t = a; a = b; b = t; }
-}
 
 // grid (chunk), dynamic LDS N * 4 bytes; N: the power of two >= max(D, 2).  gkeys [chunk][ldk >= D], ranks [chunk][U].
 __global__ __launch_bounds__(GS_RANK_THREADS) void gs_ranks_sort(uint64_t seed, int p0, int D, int N, const int* __restrict__ upos, int U,
@@ -67,30 +63,7 @@ __global__ __launch_bounds__(GS_RANK_THREADS) void gs_ranks_sort(uint64_t seed, 
     if (i < D) gk[i] = key;
   }
   __syncthreads();
-  for (int k = 2; k <= N; k <<= 1) {                           // bitonic: runs of k keys, ascending where bit k of the index is clear
-    int j = k >> 1;
-    for (; j >= 2; j >>= 2) {                                  // the distances j and h = j / 2 in one pass: four keys per lane
-      const int h = j >> 1;
-      for (int t = tid; t < (N >> 2); t += GS_RANK_THREADS) {
-        const int i = ((t & ~(h - 1)) << 2) | (t & (h - 1));   // bits h and j clear: i | j | h < N; bit k is the same in all four
-        const bool asc = (i & k) == 0;
-        uint32_t x0 = s[i], x1 = s[i | h], x2 = s[i | j], x3 = s[i | j | h];
-        gs_order(x0, x2, asc); gs_order(x1, x3, asc);
-        gs_order(x0, x1, asc); gs_order(x2, x3, asc);
-        s[i] = x0; s[i | h] = x1; s[i | j] = x2; s[i | j | h] = x3;
-      }
-      __syncthreads();
-    }
-    if (j == 1) {                                              // an odd number of distances: the last one alone
-      for (int t = tid; t < (N >> 1); t += GS_RANK_THREADS) {
-        const int i = t << 1;
-        uint32_t a = s[i], b = s[i | 1];
-        gs_order(a, b, (i & k) == 0);
-        s[i] = a; s[i | 1] = b;
-      }
-      __syncthreads();
-    }
-  }
+  lds_bitonic_sort(s, N, tid, GS_RANK_THREADS);
   for (int u = tid; u < U; u += GS_RANK_THREADS) {
     const int i = upos[u];                                     // checked by the host: in [0, D)
     const uint32_t key = gk[i];

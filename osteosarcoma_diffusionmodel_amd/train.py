@@ -1201,13 +1201,33 @@ class Trainer:
 
 
 def prepare_data(config: dict):
-    """CSV files -> loaders (utils/train.py:342-444); pathway_scores.csv must already exist (the
-    pathway feature engineering that would create it is outside the hot path)."""
+    """CSV files -> loaders (utils/train.py:342-444); a missing pathway_scores.csv is computed first when ``data.gene_sets_file``
+    names a GMT file (``pathways.compute_pathway_features``; under data parallel by rank 0 alone, the other ranks wait for it), and is
+    an error otherwise."""
     processed = Path(config["data"]["processed_dir"])
     mutation_matrix = pd.read_csv(processed / "mutation_matrix_aligned.csv", index_col=0)
     expression_matrix = pd.read_csv(processed / "expression_matrix_aligned.csv", index_col=0)
     clinical = pd.read_csv(processed / "clinical_aligned.csv")
     path = processed / "pathway_scores.csv"
+    if config["data"].get("gene_sets_file"):
+        # main.py step 3 (pathways.py; DESIGN.md section 3.31): the scores of the expression matrix under data.gene_sets_file.  Under
+        # data parallel rank 0 alone computes and writes (processed_dir is shared by the ranks); the others wait for its word --
+        # None, or the error it met, which every rank then raises -- before any of them reads the file.
+        ranks = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+        word = [None]
+        if not ranks or torch.distributed.get_rank() == 0:
+            try:
+                if not path.exists():
+                    from .pathways import compute_pathway_features
+                    compute_pathway_features(config)
+            except Exception as err:
+                if not ranks:
+                    raise
+                word[0] = f"{type(err).__name__}: {err}"
+        if ranks:
+            torch.distributed.broadcast_object_list(word, src=0)
+            if word[0] is not None:
+                raise RuntimeError(f"rank 0 could not compute the pathway scores: {word[0]}")
     if not path.exists():
         raise FileNotFoundError(f"{path} is missing: compute pathway scores with the reference's utils/pathway_features.py first")
     pathway_scores = pd.read_csv(path, index_col=0)

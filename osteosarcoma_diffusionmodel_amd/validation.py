@@ -30,12 +30,15 @@ from . import _lib as L
 from . import cluster as CL
 from . import diffexp as DE
 from . import enrichment as EN
+from . import pathways as PW
 from . import survival as SV
 from . import utility as U
 from .cluster import subtype_summary      # noqa: F401  (the subtype_* figures: pure NumPy, documented there)
 from .parallel import ShardComm
 
 logger = logging.getLogger(__name__)
+
+PATHWAY_METHODS = PW.METHODS        # the method numbers of osd_val_pathway_scores
 
 
 def _dev(a, device) -> torch.Tensor:
@@ -301,6 +304,70 @@ class DeviceKernels:
         if phases:
             res["phase_ms"] = np.array(ms[:], dtype=np.float64)
         return res
+
+    def pathway_scores(self, t: torch.Tensor, sets, method: str = "mean", center=None, scale=None, rank_table=None,
+                       row_chunk: int = 0, phases: bool = False):
+        """``osd_val_pathway_scores`` on the fp32 device tensor t [rows, D] (a column-slice view is read in place): a float64 DEVICE
+        tensor [rows, S], per row the score of every set -- ``sets``: per set an integer array of its distinct columns.  ``method``:
+        ``mean`` (sum_j (x_j - c_j) s_j / m), ``zscore`` (the same sum / sqrt(m)) or ``ssgsea`` (the closed form over the row's
+        mid-ranks; ``rank_table``: float64 [2 D + 1], ``pathways.rank_table(D, alpha)``).  ``center``, ``scale``: D values rounded to
+        fp32, or None for 0 and for 1.  ``row_chunk``: rows per launch (0: the library's choice); ``phases=True`` returns
+        (scores, phase_ms), the device milliseconds of (staging, scoring).  The same bits at every ``row_chunk`` and on every
+        call.  A ValueError for what the library refuses: D outside [2, 32768], no set, a set with no member, more than 1024 or
+        all D columns, a column outside [0, D) or repeated in a set, a negative ``row_chunk``, ``ssgsea`` without its table."""
+        if method not in PATHWAY_METHODS:
+            raise ValueError(f"method must be one of {PATHWAY_METHODS}, got {method!r}")
+        t = _rows_view(t)
+        rows, D = t.shape
+        sets = [np.ascontiguousarray(np.asarray(m).reshape(-1), dtype=np.int64) for m in sets]
+        S = len(sets)
+        if S < 1 or int(row_chunk) < 0:
+            raise ValueError("at least one set and row_chunk >= 0 are needed")
+        if any(m.size and (m.min() < -2 ** 31 or m.max() >= 2 ** 31) for m in sets) or sum(m.size for m in sets) >= 2 ** 31:
+            raise ValueError("set members must fit 32 bits")
+        offsets = np.zeros(S + 1, dtype=np.int32)
+        offsets[1:] = np.cumsum([m.size for m in sets])
+        flat = np.ascontiguousarray(np.concatenate(sets), dtype=np.int32) if offsets[-1] else np.zeros(1, dtype=np.int32)
+        c = None if center is None else _f32(center, t.device, (D,), "center")
+        s = None if scale is None else _f32(scale, t.device, (D,), "scale")
+        table = None
+        if method == "ssgsea":
+            if rank_table is None:
+                raise ValueError("ssgsea needs rank_table, float64 [2 D + 1]")
+            table = np.ascontiguousarray(rank_table, dtype=np.float64)
+            if table.shape != (2 * D + 1,):
+                raise ValueError(f"rank_table must have shape ({2 * D + 1},), got {table.shape}")
+        out = torch.empty((rows, S), dtype=torch.float64, device=t.device)
+        args = [self._stream(), self.index, L.ptr(t), rows, max(int(t.stride(0)), D), D, PATHWAY_METHODS.index(method), L.ptr(c), L.ptr(s),
+                C.c_void_p(offsets.ctypes.data), C.c_void_p(flat.ctypes.data), S,
+                C.c_void_p(0 if table is None else table.ctypes.data), int(row_chunk), L.ptr(out)]
+        if phases:
+            ms = (C.c_float * 2)()
+            L.check(L.lib().osd_val_pathway_scores_timed(*args, ms))
+            return out, np.array(ms[:], dtype=np.float64)
+        L.check(L.lib().osd_val_pathway_scores(*args))
+        return out
+
+    def pathway_agreement(self, scores: torch.Tensor, block: torch.Tensor, mu, isd) -> Dict[str, np.ndarray]:
+        """``osd_val_pathway_agreement``: ``scores`` a float64 device tensor [rows, S] (``pathway_scores``), ``block`` an fp32 device
+        tensor [rows, >= S] (a column-slice view is read in place; its first S columns are used), ``mu`` and ``isd`` float64 [S].
+        With z = (score - mu) * isd and g the block's value, over the rows where both are finite: ``sums`` float64 [S, 6] (sum z,
+        sum g, sum z^2, sum g^2, sum z g, sum (g - z)^2) and ``used`` int64 [S], the number of those rows.  The same bits on every
+        call."""
+        if scores.dtype != torch.float64 or scores.dim() != 2 or not scores.is_contiguous() or scores.shape[0] < 1 or scores.shape[1] < 1:
+            raise ValueError("scores must be a contiguous float64 [rows >= 1, S >= 1] tensor")
+        rows, S = scores.shape
+        block = _rows_view(block)
+        if block.shape[0] != rows or block.shape[1] < S:
+            raise ValueError(f"block must be [{rows}, >= {S}], got {tuple(block.shape)}")
+        mu, isd = np.ascontiguousarray(mu, dtype=np.float64), np.ascontiguousarray(isd, dtype=np.float64)
+        if mu.shape != (S,) or isd.shape != (S,):
+            raise ValueError(f"mu and isd must hold one value per pathway ({S})")
+        sums, used = np.zeros((S, 6), dtype=np.float64), np.zeros(S, dtype=np.int64)
+        L.check(L.lib().osd_val_pathway_agreement(self._stream(), self.index, L.ptr(scores), rows, S, L.ptr(block),
+                                                  max(int(block.stride(0)), int(block.shape[1])), C.c_void_p(mu.ctypes.data),
+                                                  C.c_void_p(isd.ctypes.data), C.c_void_p(sums.ctypes.data), C.c_void_p(used.ctypes.data)))
+        return {"sums": sums, "used": used}
 
     def col_moments(self, t: torch.Tensor, cols: Sequence[int]):
         g, arr = _col_array(cols)
@@ -1402,6 +1469,31 @@ class BiologicalValidator:
         rows["sets"] = set_names
         return (summary, rows) if return_rows else summary
 
+    # -- pathway consistency: the generated pathway block against the scores of the generated expression -----
+    def pathway_consistency(self, synth_expression, synth_pathways, gene_sets, real_expression, real_pathways=None,
+                            method: str = "mean", alpha: float = 0.25, return_rows: bool = False, min_genes: int = 5):
+        """Does a generated patient's pathway block agree with the pathway scores of that same patient's generated expression?  In
+        the real cohort the block is a function of the expression; shuffling the pathway rows among the synthetic patients leaves
+        every marginal, the MMD and every per-gene contrast as they were -- this check is the one that moves.  A
+        ``pathways.PathwayScorer`` (``method``: ``mean``, ``zscore`` or ``ssgsea`` with the exponent ``alpha``; ``min_genes``) is
+        fitted on ``real_expression``; z = the standardised scores of ``synth_expression`` (``DeviceKernels.pathway_scores``, then
+        (p - mean) / (sd + 1e-8) with the REAL cohort's figures, as ``prepare_data`` standardises), g = ``synth_pathways``; frames
+        are matched by column name, a bare pathway matrix must hold exactly the kept sets.  ``gene_sets``: a name -> gene symbols
+        mapping, a name -> column indices mapping or a genes x sets 0/1 DataFrame.  Per pathway, over the rows where z and g are
+        finite (``DeviceKernels.pathway_agreement``): Pearson r(g, z), ``rmse`` = sqrt(mean (g - z)^2) -- in real-cohort sd units
+        by construction --, ``bias`` = mean g - mean z and ``sd_ratio`` = sd g / sd z.  Keys: ``pwc_pearson_mean`` / ``_min`` /
+        ``_min_pathway``, ``pwc_rmse_mean`` / ``_max`` / ``_max_pathway``, ``pwc_abs_bias_mean``, ``pwc_sd_ratio_mean``, ``pwc_r2``
+        (pooled: 1 - sum (g - z)^2 / sum (z - mean z)^2), ``pwc_pathways``, ``pwc_pathways_skipped``, ``pwc_constant`` (pathways
+        whose z or g is constant: no r) and ``pwc_rows_nonfinite`` (the left-out rows, added over the pathways).  With
+        ``real_pathways`` the same figures of the real cohort as ``pwc_real_*``: r = 1 and rmse = 0 when the block came from this
+        scorer -- the baseline for a block that another method made.  ``return_rows=True`` also returns the per-pathway arrays.
+        On a ``sharded=True`` validator the synthetic arguments are this rank's rows: rows are independent, the six sums add
+        across ranks, the fit is on the replicated real cohort."""
+        summary, rows = PW.pathway_consistency(self.comm, self.k, self.device, synth_expression, synth_pathways, gene_sets,
+                                               real_expression, real_pathways, method=method, alpha=float(alpha), min_genes=int(min_genes))
+        summary, rows = self._agree((summary, rows))
+        return (summary, rows) if return_rows else summary
+
     # -- downstream utility: TSTR and the classifier two-sample test (no counterpart in the reference; DESIGN.md section 3.22) ------
     def downstream_utility(self, real_train, real_train_cond, synthetic, synth_cond, real_test, real_test_cond, names=None,
                            l2: float = 1e-2, max_iter: int = 200, tol: float = 1e-5) -> Dict[str, float]:
@@ -1672,8 +1764,12 @@ class BiologicalValidator:
                      corr_strong: float = 0.3, utility=None, c2st: bool = False, subtypes: Optional[int] = None,
                      subtype_conditions=None, survival=None, marginals: bool = False, differential=None,
                      differential_names=None, enrichment=None, enrichment_names=None,
-                     enrichment_permutations: int = 1000) -> Dict[str, float]:
-        """``enrichment=(real_cond, synth_cond)`` adds ``enrichment_fidelity``'s ``gsea_*`` keys on the expression frames; it needs
+                     enrichment_permutations: int = 1000, consistency: bool = False,
+                     consistency_method: str = "mean") -> Dict[str, float]:
+        """``consistency=True`` adds ``pathway_consistency``'s ``pwc_*`` keys (the real cohort's ``pwc_real_*`` among them): the
+        generated pathway frame against the scores of the generated expression frame, the sets from ``pathway_gene_matrix`` (genes x
+        pathways 0/1, a DataFrame), the method ``consistency_method``; with the default nothing changes.
+        ``enrichment=(real_cond, synth_cond)`` adds ``enrichment_fidelity``'s ``gsea_*`` keys on the expression frames; it needs
         ``pathway_gene_matrix`` (genes x pathways 0/1, a DataFrame), which is reindexed to the expression columns -- genes that are
         not among them drop out of their sets (``enrichment_names``: its ``names``; ``enrichment_permutations``: its
         ``permutations``); with the default None nothing changes.
@@ -1778,11 +1874,16 @@ class BiologicalValidator:
             all_results.update(self.enrichment_fidelity(real_expression.values, enrichment[0], synth_expression.values, enrichment[1],
                                                         membership_matrix, names=enrichment_names,
                                                         permutations=int(enrichment_permutations)))
+        if consistency:
+            if pathway_gene_matrix is None or not hasattr(pathway_gene_matrix, "reindex"):
+                raise ValueError("validate_all(consistency=True) needs pathway_gene_matrix, a genes x pathways DataFrame")
+            all_results.update(self.pathway_consistency(synth_expression, synth_pathways, pathway_gene_matrix, real_expression,
+                                                        real_pathways, method=consistency_method))
         logger.info("=" * 50)
         logger.info("VALIDATION SUMMARY")
         logger.info("=" * 50)
         for key, value in all_results.items():
-            logger.info(f"{key}: {value:.4f}")
+            logger.info(f"{key}: {value}" if isinstance(value, str) else f"{key}: {value:.4f}")
         score = []
         if "mutation_frequency_correlation" in all_results:
             score.append(all_results["mutation_frequency_correlation"])
