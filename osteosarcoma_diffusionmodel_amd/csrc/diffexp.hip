@@ -3,14 +3,14 @@
 //                         sum (t^3 - t) of the normal approximation, and each group's first two centred moments.
 //
 // The labels are read back once and turned into a row -> slot map on the host (case k of the cohort goes to slot k, control k to slot
-// na + k, every other row to -1); the columns then go through in chunks, as in marginal.hip.  Per chunk:
-//   de_gather     the [rows, chunk] column slice of the row-major matrix (any ld, any base alignment: dword loads only) through the
-//                 64 x 64 LDS tile of marg_transpose; a case row's values land in the column-major case segments, a control row's in
-//                 the control segments, an ignored row's nowhere
-//   segsort.h     the four stable 8-bit passes over the case segments, then over the control segments: sorted in place
-//   de_stats      workgroup (x, f) owns elements [x R, (x + 1) R) of BOTH sorted segments of feature f (R = DE_RUN), staged in LDS.
+// na + k, every other row to -1); the columns then go through in chunks, as in marginal.hip, on the shared pieces of val_columns.h
+// (the chunked driver's state, the tile transposer, the binary searches, the phase timer).  Per chunk:
+//   col_tiles<true>   the [rows, chunk] column slice of the row-major matrix through the 64 x 64 LDS tile; a case row's values land
+//                 in the column-major case segments, a control row's in the control segments, an ignored row's nowhere
+//   seg_sort      segsort.h's four stable 8-bit passes over the case segments, then over the control segments: sorted in place
+//   de_stats      workgroup (x, f) owns elements [x R, (x + 1) R) of BOTH sorted segments of feature f (R = COL_RUN), staged in LDS.
 //                 The lower bound of the run's first value and the upper bound of its last one in the OTHER segment enclose every
-//                 bound the run can ask for: that window is staged in LDS and searched there (DE_WINDOW floats; a wider window --
+//                 bound the run can ask for: that window is staged in LDS and searched there (COL_WINDOW floats; a wider window --
 //                 heavy ties, groups of very different size -- is searched in global memory between the same two ends).
 //                 u2: every case value a_i adds #{b < a_i} + #{b <= a_i}; the second is the first unless b holds a_i (one probe).
 //                 ties: a last-of-its-value case element adds t^3 - t with t = its run in a + (upper - lower) in b; a
@@ -29,95 +29,41 @@
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "handle.h"
-#include "val_common.h"
-
-// segsort.h defines its kernels at namespace scope and validate.hip and marginal.hip instantiate them already: this translation
-// unit's copies live in a namespace of their own, so that the objects link.
-namespace osd { namespace dexp {
-#include "segsort.h"
-} }
+#include "val_columns.h"
 
 namespace osd {
 namespace {
 
-namespace seg = dexp::osd;
-
-constexpr int DE_TILE = 64;                // rows and columns of a transposed tile
-constexpr int DE_THREADS = 256;
-constexpr int DE_ITEMS = 4;                // elements of a run per lane
-constexpr int DE_RUN = DE_THREADS * DE_ITEMS;
-constexpr int DE_WINDOW = 4096;            // floats of the other segment a workgroup stages in LDS
-constexpr int DE_MAX_CHUNK = 32768;        // columns of a chunk: the sort's grid.y
 constexpr int64_t DE_MAX_N = 1ll << 20;    // na + nb: up to here ties <= N^3 - N stays under 2^60
-
-// dstA[c][slot] or dstB[c][slot - na] = src[r][c] for c < cols, slot = slot_of[r] >= 0
-__global__ __launch_bounds__(DE_THREADS) void de_gather(const float* __restrict__ src, long long ld, long long rows, int cols,
-                                                        const int* __restrict__ slot_of, long long na, long long nb,
-                                                        float* __restrict__ dstA, float* __restrict__ dstB) {
-  __shared__ float tile[DE_TILE][DE_TILE + 1];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const long long r0 = (long long)blockIdx.x * DE_TILE;
-  const int c0 = (int)blockIdx.y * DE_TILE;
-  if (c0 + tx < cols)
-    for (int y = ty; y < DE_TILE; y += DE_THREADS / 64)
-      if (r0 + y < rows) tile[y][tx] = src[(r0 + y) * ld + c0 + tx];
-  __syncthreads();
-  if (r0 + tx >= rows) return;
-  const long long slot = slot_of[r0 + tx];                     // made by the host: -1 or in [0, na + nb)
-  if (slot < 0) return;
-  const bool is_case = slot < na;
-  float* dst = is_case ? dstA + slot : dstB + (slot - na);
-  const long long n = is_case ? na : nb;
-  for (int y = ty; y < DE_TILE; y += DE_THREADS / 64)
-    if (c0 + y < cols) dst[(long long)(c0 + y) * n] = tile[tx][y];
-}
-
-// p ascending.  lower: the first index in [lo, hi) whose value is not below v, else hi; upper: the first whose value exceeds v
-__device__ __forceinline__ long long de_lower(const float* __restrict__ p, long long lo, long long hi, float v) {
-  while (lo < hi) { const long long mid = (lo + hi) >> 1; if (p[mid] < v) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-__device__ __forceinline__ long long de_upper(const float* __restrict__ p, long long lo, long long hi, float v) {
-  while (lo < hi) { const long long mid = (lo + hi) >> 1; if (p[mid] <= v) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-__device__ __forceinline__ int de_lower_lds(const float* w, int lo, int hi, float v) {
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (w[mid] < v) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-__device__ __forceinline__ int de_upper_lds(const float* w, int lo, int hi, float v) {
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (w[mid] <= v) lo = mid + 1; else hi = mid; }
-  return lo;
-}
 
 struct DeArgs {
   const float* a; const float* b;          // sorted segments [chunk][na], [chunk][nb]
   long long na, nb;
-  int blocks;                              // workgroups of a feature: ceil(max(na, nb) / DE_RUN)
+  int blocks;                              // workgroups of a feature: ceil(max(na, nb) / COL_RUN)
   const float* center;                     // the chunk's first column's centre, or NULL
   long long* pu2; long long* pties;        // [chunk][blocks]
   double* psum; double* psq;               // [2][chunk][blocks]: cases, controls
 };
 
 // The run [i0, i1) of the sorted segment x (nx values) against the other segment y (ny values); CASE: x is the case segment.
-// i0 < i1 <= nx, i1 - i0 <= DE_RUN.  Adds to u2 (CASE only), ties, and the run's centred moments.
+// i0 < i1 <= nx, i1 - i0 <= COL_RUN.  Adds to u2 (CASE only), ties, and the run's centred moments.
 template <bool CASE>
 __device__ __forceinline__ void de_run(const float* __restrict__ x, long long nx, long long i0, long long i1, const float* __restrict__ y,
                                        long long ny, double c, float* own, float* win, long long* ends, long long& u2, long long& ties,
                                        double& sum, double& sq) {
   const int len = (int)(i1 - i0);
-  if (threadIdx.x == 0) ends[0] = de_lower(y, 0, ny, x[i0]);
-  if (threadIdx.x == 64) ends[1] = de_upper(y, 0, ny, x[i1 - 1]);
-  for (int k = threadIdx.x; k < len; k += DE_THREADS) own[k] = x[i0 + k];
+  if (threadIdx.x == 0) ends[0] = lower_bound(y, 0ll, ny, x[i0]);
+  if (threadIdx.x == 64) ends[1] = upper_bound(y, 0ll, ny, x[i1 - 1]);
+  for (int k = threadIdx.x; k < len; k += COL_THREADS) own[k] = x[i0 + k];
   __syncthreads();
   const long long lo = ends[0], hi = ends[1];                  // lo <= hi: x ascending
-  const bool staged = hi - lo <= DE_WINDOW;                    // the same in the whole workgroup
+  const bool staged = hi - lo <= COL_WINDOW;                   // the same in the whole workgroup
   const int wn = staged ? (int)(hi - lo) : 0;
-  for (int k = threadIdx.x; k < wn; k += DE_THREADS) win[k] = y[lo + k];
+  for (int k = threadIdx.x; k < wn; k += COL_THREADS) win[k] = y[lo + k];
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < DE_ITEMS; ++k) {
-    const int j = k * DE_THREADS + threadIdx.x;                // index in the run
+  for (int k = 0; k < COL_ITEMS; ++k) {
+    const int j = k * COL_THREADS + threadIdx.x;               // index in the run
     if (j >= len) continue;
     const long long i = i0 + j;
     const float v = own[j];
@@ -128,12 +74,12 @@ __device__ __forceinline__ void de_run(const float* __restrict__ x, long long nx
     // the upper bound is the lower one unless y holds v: one probe spares the second search on untied data
     long long lb, ub;
     if (staged) {
-      const int l = de_lower_lds(win, 0, wn, v);
+      const int l = lower_bound(win, 0, wn, v);
       lb = lo + l;
-      ub = CASE && l < wn && win[l] == v ? lo + de_upper_lds(win, l + 1, wn, v) : lb;
+      ub = CASE && l < wn && win[l] == v ? lo + upper_bound(win, l + 1, wn, v) : lb;
     } else {
-      lb = de_lower(y, lo, hi, v);
-      ub = CASE && lb < hi && y[lb] == v ? de_upper(y, lb + 1, hi, v) : lb;
+      lb = lower_bound(y, lo, hi, v);
+      ub = CASE && lb < hi && y[lb] == v ? upper_bound(y, lb + 1, hi, v) : lb;
     }
     if (CASE) u2 += lb + ub;
     const bool last = j + 1 < len ? own[j + 1] != v : (i + 1 >= nx || x[i + 1] != v);
@@ -141,9 +87,9 @@ __device__ __forceinline__ void de_run(const float* __restrict__ x, long long nx
     if (!CASE && lb < hi && (staged ? win[lb - lo] : y[lb]) == v) continue;      // the case segment counts this value
     long long first = i;
     if (j == 0 || own[j - 1] == v) {
-      const int l = de_lower_lds(own, 0, j, v);
+      const int l = lower_bound(own, 0, j, v);
       first = i0 + l;
-      if (l == 0 && i0 > 0) first = de_lower(x, 0, i0, v);      // the value reaches the run's start: at most one such element
+      if (l == 0 && i0 > 0) first = lower_bound(x, 0ll, i0, v);      // the value reaches the run's start: at most one such element
     }
     const long long t = (i + 1 - first) + (CASE ? ub - lb : 0);
     ties += t * t * t - t;
@@ -151,18 +97,18 @@ __device__ __forceinline__ void de_run(const float* __restrict__ x, long long nx
   __syncthreads();                                             // own, win and ends are free again
 }
 
-__global__ __launch_bounds__(DE_THREADS) void de_stats(DeArgs g) {
-  __shared__ float win[DE_WINDOW];
-  __shared__ float own[DE_RUN];
+__global__ __launch_bounds__(COL_THREADS) void de_stats(DeArgs g) {
+  __shared__ float win[COL_WINDOW];
+  __shared__ float own[COL_RUN];
   __shared__ long long ends[2];
-  __shared__ long long ru2[DE_THREADS / 64], rties[DE_THREADS / 64];
-  __shared__ double rsum[4][DE_THREADS / 64];
+  __shared__ long long ru2[COL_THREADS / 64], rties[COL_THREADS / 64];
+  __shared__ double rsum[4][COL_THREADS / 64];
   const long long f = blockIdx.y;
   const float* a = g.a + f * g.na;
   const float* b = g.b + f * g.nb;
   const double c = g.center ? (double)g.center[f] : 0.0;
-  const long long i0 = (long long)blockIdx.x * DE_RUN;
-  const long long a1 = min(g.na, i0 + DE_RUN), b1 = min(g.nb, i0 + DE_RUN);
+  const long long i0 = (long long)blockIdx.x * COL_RUN;
+  const long long a1 = min(g.na, i0 + COL_RUN), b1 = min(g.nb, i0 + COL_RUN);
   long long u2 = 0, ties = 0;
   double sa = 0.0, qa = 0.0, sb = 0.0, qb = 0.0;
   // every condition below is the same in the whole workgroup: the barriers inside de_run are met by all or by none
@@ -173,7 +119,7 @@ __global__ __launch_bounds__(DE_THREADS) void de_stats(DeArgs g) {
   if ((threadIdx.x & 63) == 0) { ru2[wv] = u2; rties[wv] = ties; rsum[0][wv] = sa; rsum[1][wv] = qa; rsum[2][wv] = sb; rsum[3][wv] = qb; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int w = 1; w < DE_THREADS / 64; ++w) {
+    for (int w = 1; w < COL_THREADS / 64; ++w) {
       u2 += ru2[w]; ties += rties[w];
       sa += rsum[0][w]; qa += rsum[1][w]; sb += rsum[2][w]; qb += rsum[3][w];
     }
@@ -203,46 +149,6 @@ __global__ __launch_bounds__(64) void de_finish(DeArgs g, int chunk, long long g
   }
 }
 
-// the four passes of segsort.h over `nf` segments of n keys, ping-pong between buf0 and buf1: sorted floats back in buf0
-int de_sort(hipStream_t s, float* buf0, float* buf1, long long n, int nf, int* cnt) {
-  const int wps = (int)((n + seg::SEG_CHUNK - 1) / seg::SEG_CHUNK);
-  uint32_t* a = (uint32_t*)buf0; uint32_t* b = (uint32_t*)buf1;
-  const dim3 grid((unsigned)((wps + seg::SEG_WAVES - 1) / seg::SEG_WAVES), (unsigned)nf), block(64 * seg::SEG_WAVES);
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 8 * pass;
-    OSD_HIP(launched(pass == 0 ? seg::k_seg_count<true> : seg::k_seg_count<false>, grid, block, 0, s, (const uint32_t*)a, n, wps, shift, cnt));
-    OSD_HIP(launched(seg::k_seg_scan, dim3((unsigned)nf), dim3(256), 0, s, cnt, wps));
-    OSD_HIP(launched(pass == 0 ? seg::k_seg_scatter<true, false> : pass == 3 ? seg::k_seg_scatter<false, true> : seg::k_seg_scatter<false, false>,
-                     grid, block, 0, s, (const uint32_t*)a, b, n, wps, shift, (const int*)cnt));
-    uint32_t* t = a; a = b; b = t;
-  }
-  return OSD_OK;
-}
-
-struct PhaseClock {                        // optional: milliseconds of the three phases, summed over the chunks
-  double* ms;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  explicit PhaseClock(double* out) : ms(out) {}
-  ~PhaseClock() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-  hipError_t init() {
-    if (!ms) return hipSuccess;
-    ms[0] = ms[1] = ms[2] = 0.0;
-    for (hipEvent_t& e : ev) { const hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; }
-    return hipSuccess;
-  }
-  hipError_t mark(int i, hipStream_t s) { return ms ? hipEventRecord(ev[i], s) : hipSuccess; }
-  hipError_t add() {                       // after the stream has drained
-    if (!ms) return hipSuccess;
-    for (int i = 0; i < 3; ++i) {
-      float t = 0.f;
-      const hipError_t r = hipEventElapsedTime(&t, ev[i], ev[i + 1]);
-      if (r != hipSuccess) return r;
-      ms[i] += t;
-    }
-    return hipSuccess;
-  }
-};
-
 int group_ranks(void* stream, int device, const float* X, int64_t rows, int ld, int D, const int32_t* labels, const float* center,
                 int chunk_cols, int64_t* u2, int64_t* ties, double* sum, double* sumsq, int64_t* na_out, int64_t* nb_out, double* phase_ms) {
   if (!X || !labels || !u2 || !ties || !sum || !sumsq || !na_out || !nb_out) { set_error("bad argument (NULL pointer)"); return OSD_EINVAL; }
@@ -265,27 +171,18 @@ int group_ranks(void* stream, int device, const float* X, int64_t rows, int ld, 
   int64_t ia = 0, ib = na;
   for (int64_t r = 0; r < rows; ++r) map[r] = map[r] == 1 ? (int32_t)ia++ : map[r] == 0 ? (int32_t)ib++ : -1;
 
-  const int64_t nmax = na > nb ? na : nb;
-  int64_t chunk = chunk_cols ? chunk_cols : osd_val_marginals_auto_chunk(na, nb, D);
-  if (chunk > D) chunk = D;
-  if (chunk > DE_MAX_CHUNK) chunk = DE_MAX_CHUNK;
-  if (chunk > 2000000000ll / nmax) chunk = 2000000000ll / nmax;            // segsort's keys per sort; >= 1: nmax <= 2^20
-
-  const int64_t blocks = (nmax + DE_RUN - 1) / DE_RUN;
-  const int wps = (int)((nmax + seg::SEG_CHUNK - 1) / seg::SEG_CHUNK);
-  ValBuf slot_of, keys, counts, slots, res;
+  ColumnChunks cc;                                             // init's clamp leaves >= 1: na, nb <= 2^20
+  OSD_TRY(cc.init(na, nb, D, chunk_cols ? chunk_cols : osd_val_marginals_auto_chunk(na, nb, D)));
+  const int64_t chunk = cc.chunk, blocks = cc.blocks;
+  ValBuf slot_of, slots, res;
   OSD_TRY(slot_of.alloc((size_t)rows * sizeof(int32_t)));
-  OSD_TRY(keys.alloc((size_t)(2 * (na + nb) * chunk) * sizeof(float)));
-  OSD_TRY(counts.alloc((size_t)chunk * 256 * (size_t)wps * sizeof(int)));
   OSD_TRY(slots.alloc((size_t)(6 * chunk * blocks) * 8));
   OSD_TRY(res.alloc((size_t)(6 * chunk) * 8));
   OSD_HIP(hipMemcpyAsync(slot_of.get(), map.data(), (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  float* ca = keys.as<float>(); float* ta = ca + na * chunk;
-  float* cb = ta + na * chunk;  float* tb = cb + nb * chunk;
   DeArgs g{};
-  g.a = ca; g.b = cb; g.na = na; g.nb = nb; g.blocks = (int)blocks;
+  g.a = cc.ca; g.b = cc.cb; g.na = na; g.nb = nb; g.blocks = (int)blocks;
   std::vector<long long> host((size_t)(6 * chunk));
-  PhaseClock clock(phase_ms);
+  PhaseClock<3, double> clock(phase_ms);                       // gather, sort, statistics: summed over the chunks
   OSD_HIP(clock.init());
 
   for (int64_t c0 = 0; c0 < D; c0 += chunk) {
@@ -295,13 +192,12 @@ int group_ranks(void* stream, int device, const float* X, int64_t rows, int ld, 
     g.pu2 = slots.as<long long>(); g.pties = g.pu2 + group;
     g.psum = (double*)(g.pties + group); g.psq = g.psum + 2 * group;
     OSD_HIP(clock.mark(0, s));
-    OSD_HIP(launched(de_gather, dim3((unsigned)((rows + DE_TILE - 1) / DE_TILE), (unsigned)((c + DE_TILE - 1) / DE_TILE)), DE_THREADS, 0, s,
-                     X + c0, (long long)ld, (long long)rows, c, (const int*)slot_of.as<int>(), (long long)na, (long long)nb, ca, cb));
+    OSD_HIP(launched(col_tiles<true>, dim3((unsigned)((rows + COL_TILE - 1) / COL_TILE), (unsigned)((c + COL_TILE - 1) / COL_TILE)), COL_THREADS, 0,
+                     s, X + c0, (long long)ld, (long long)rows, c, (const int*)slot_of.as<int>(), (long long)na, (long long)nb, cc.ca, cc.cb));
     OSD_HIP(clock.mark(1, s));
-    OSD_TRY(de_sort(s, ca, ta, (long long)na, c, counts.as<int>()));
-    OSD_TRY(de_sort(s, cb, tb, (long long)nb, c, counts.as<int>()));
+    OSD_TRY(cc.sort(s, c));
     OSD_HIP(clock.mark(2, s));
-    OSD_HIP(launched(de_stats, dim3((unsigned)blocks, (unsigned)c), DE_THREADS, 0, s, g));
+    OSD_HIP(launched(de_stats, dim3((unsigned)blocks, (unsigned)c), COL_THREADS, 0, s, g));
     OSD_HIP(launched(de_finish, dim3((unsigned)c), 64, 0, s, g, (int)chunk, group, res.as<long long>()));
     OSD_HIP(clock.mark(3, s));
     OSD_HIP(read_back(s, host.data(), res.get(), (size_t)(6 * chunk) * 8));

@@ -19,6 +19,7 @@
 //                   and one subtraction each -- and the extremes with their first hit numbers come from (value, index) butterflies,
 //                   whose result no order changes.
 // No atomics; a permutation's result depends on (seed, p) alone: the same bits at every perm_chunk and on every call.
+// Host plumbing shared with pathway.hip: check_sets and Packed (val_common.h), PhaseClock and lower_bound (val_columns.h).
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>
@@ -29,7 +30,7 @@
 #include "handle.h"
 #include "lds_sort.h"
 #include "rng.h"
-#include "val_common.h"
+#include "val_columns.h"
 
 namespace osd {
 namespace {
@@ -67,8 +68,7 @@ __global__ __launch_bounds__(GS_RANK_THREADS) void gs_ranks_sort(uint64_t seed, 
   for (int u = tid; u < U; u += GS_RANK_THREADS) {
     const int i = upos[u];                                     // checked by the host: in [0, D)
     const uint32_t key = gk[i];
-    int lo = 0, hi = N;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (s[mid] < key) lo = mid + 1; else hi = mid; }
+    const int lo = lower_bound(s, 0, N, key);
     int r = lo;                                                // the keys below this one: the padding is below none
     if (lo + 1 < N && s[lo + 1] == key)                        // the key occurs again: the smaller index goes first
       for (int j = 0; j < i; ++j) r += gk[j] == key;
@@ -189,30 +189,6 @@ __global__ __launch_bounds__(GS_SET_THREADS) void gs_scan(const int* __restrict_
   }
 }
 
-struct GsClock {                           // optional: milliseconds of the three phases, summed over the chunks
-  float* ms;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  explicit GsClock(float* out) : ms(out) {}
-  ~GsClock() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-  hipError_t init() {
-    if (!ms) return hipSuccess;
-    ms[0] = ms[1] = ms[2] = 0.f;
-    for (hipEvent_t& e : ev) { const hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; }
-    return hipSuccess;
-  }
-  hipError_t mark(int i, hipStream_t s) { return ms ? hipEventRecord(ev[i], s) : hipSuccess; }
-  hipError_t add() {                       // after the stream has drained
-    if (!ms) return hipSuccess;
-    for (int i = 0; i < 3; ++i) {
-      float t = 0.f;
-      const hipError_t r = hipEventElapsedTime(&t, ev[i], ev[i + 1]);
-      if (r != hipSuccess) return r;
-      ms[i] += t;
-    }
-    return hipSuccess;
-  }
-};
-
 int gsea(void* stream, int device, const double* weights, int D, const int32_t* offsets, const int32_t* positions, int S, int permutations,
          uint64_t seed, int perm_chunk, double* es_pos, double* es_neg, int32_t* lead, float* phase_ms) {
   if (!weights || !offsets || !positions || !es_pos || !es_neg || !lead) { set_error("bad argument (NULL pointer)"); return OSD_EINVAL; }
@@ -220,19 +196,9 @@ int gsea(void* stream, int device, const double* weights, int D, const int32_t* 
   if (S < 1 || permutations < 0 || perm_chunk < 0) { set_error("bad argument (S >= 1, permutations >= 0, perm_chunk >= 0)"); return OSD_EINVAL; }
   for (int i = 0; i < D; ++i)
     if (!(weights[i] >= 0.0 && weights[i] <= GS_MAX_WEIGHT)) { set_error("weight %d is negative, not finite or above 1e100", i); return OSD_EINVAL; }
-  if (offsets[0] != 0) { set_error("set_offsets must start at 0"); return OSD_EINVAL; }
   // the positions some set uses, ascending, and every member as an index into them
-  std::vector<int32_t> seen((size_t)D, -1), slot((size_t)D, -1);
-  for (int s = 0; s < S; ++s) {
-    const int64_t k = (int64_t)offsets[s + 1] - offsets[s];
-    if (k < 1 || k > GS_MAX_K || k >= D) { set_error("set %d has %lld members: 1 <= k <= %d and k < D are needed", s, (long long)k, GS_MAX_K); return OSD_EINVAL; }
-    for (int32_t e = offsets[s]; e < offsets[s + 1]; ++e) {
-      const int32_t pos = positions[e];
-      if (pos < 0 || pos >= D) { set_error("set %d holds the position %d outside [0, %d)", s, pos, D); return OSD_EINVAL; }
-      if (seen[pos] == s) { set_error("set %d holds the position %d more than once", s, pos); return OSD_EINVAL; }
-      seen[pos] = s;
-    }
-  }
+  std::vector<int32_t> seen, slot((size_t)D, -1);
+  OSD_TRY(check_sets(offsets, positions, S, D, GS_MAX_K, "position", 'k', seen));
   const int M = offsets[S];
   std::vector<int32_t> upos;
   for (int i = 0; i < D; ++i)
@@ -255,38 +221,31 @@ int gsea(void* stream, int device, const double* weights, int D, const int32_t* 
   if (chunk > GS_MAX_CHUNK) chunk = GS_MAX_CHUNK;
   if (chunk > total) chunk = total;
 
-  // one allocation: the tables (uploaded in one copy), then the chunk's buffers, each at a multiple of 256 bytes
-  size_t bytes = 0;
-  auto take = [&bytes](size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; };
-  const size_t at_w = take((size_t)D * sizeof(double)), at_off = take((size_t)(S + 1) * sizeof(int32_t));
-  const size_t at_upos = take((size_t)U * sizeof(int32_t)), at_mem = take((size_t)M * sizeof(int32_t)), tables = bytes;
-  const size_t at_es = take((size_t)2 * chunk * S * sizeof(double)), at_lead = take((size_t)2 * S * sizeof(int32_t));
-  const size_t at_keys = take(count ? 0 : (size_t)chunk * ldk * sizeof(uint32_t));
-  const size_t at_ranks = take((size_t)chunk * U * sizeof(int32_t)), at_hits = take((size_t)chunk * M * sizeof(int32_t));
-  std::vector<char> host(tables);
-  memcpy(host.data() + at_w, weights, (size_t)D * sizeof(double));
-  memcpy(host.data() + at_off, offsets, (size_t)(S + 1) * sizeof(int32_t));
-  memcpy(host.data() + at_upos, upos.data(), (size_t)U * sizeof(int32_t));
-  memcpy(host.data() + at_mem, members.data(), (size_t)M * sizeof(int32_t));
-  ValBuf ws;
-  OSD_TRY(ws.alloc(bytes));
-  OSD_HIP(hipMemcpyAsync(ws.get(), host.data(), tables, hipMemcpyHostToDevice, st));
-  OSD_HIP(hipStreamSynchronize(st));                           // the staging vector is free to go
-  const double* dw = (const double*)(ws.get() + at_w);
-  const int* doff = (const int*)(ws.get() + at_off);
-  const int* dupos = (const int*)(ws.get() + at_upos);
-  const int* dmem = (const int*)(ws.get() + at_mem);
-  uint32_t* dkeys = (uint32_t*)(ws.get() + at_keys);
-  int* dranks = (int*)(ws.get() + at_ranks);
-  int* dhits = (int*)(ws.get() + at_hits);
-  int* dlead = (int*)(ws.get() + at_lead);
+  // one allocation: the tables (uploaded in one copy), then the chunk's buffers
+  Packed ws;
+  const size_t at_w = ws.put(weights, (size_t)D * sizeof(double)), at_off = ws.put(offsets, (size_t)(S + 1) * sizeof(int32_t));
+  const size_t at_upos = ws.put(upos.data(), (size_t)U * sizeof(int32_t)), at_mem = ws.put(members.data(), (size_t)M * sizeof(int32_t));
+  const size_t at_es = ws.take((size_t)2 * chunk * S * sizeof(double)), at_lead = ws.take((size_t)2 * S * sizeof(int32_t));
+  const size_t at_keys = ws.take(count ? 0 : (size_t)chunk * ldk * sizeof(uint32_t));
+  const size_t at_ranks = ws.take((size_t)chunk * U * sizeof(int32_t)), at_hits = ws.take((size_t)chunk * M * sizeof(int32_t));
+  OSD_TRY(ws.alloc());
+  OSD_HIP(ws.upload(st));
+  OSD_HIP(hipStreamSynchronize(st));                           // the upload has left the staging vector
+  const double* dw = ws.at<const double>(at_w);
+  const int* doff = ws.at<const int>(at_off);
+  const int* dupos = ws.at<const int>(at_upos);
+  const int* dmem = ws.at<const int>(at_mem);
+  uint32_t* dkeys = ws.at<uint32_t>(at_keys);
+  int* dranks = ws.at<int>(at_ranks);
+  int* dhits = ws.at<int>(at_hits);
+  int* dlead = ws.at<int>(at_lead);
   if (count)
     OSD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gs_ranks_count), hipFuncAttributeMaxDynamicSharedMemorySize, GS_MAX_D * 4));
   else
     OSD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gs_ranks_sort), hipFuncAttributeMaxDynamicSharedMemorySize, GS_MAX_D * 4));
-  GsClock clock(phase_ms);
+  PhaseClock<3, float> clock(phase_ms);                        // ranks, hits, scan: summed over the chunks
   OSD_HIP(clock.init());
-  double* dpos = (double*)(ws.get() + at_es);
+  double* dpos = ws.at<double>(at_es);
   double* dneg = dpos + (size_t)chunk * S;
 
   for (int64_t p0 = 0; p0 < total; p0 += chunk) {

@@ -22,6 +22,7 @@
 //               a butterfly adds the lanes, lane 0 adds the four wavefronts; the host adds the tiles in ascending order.
 // No atomics, and nothing depends on which rows share a launch: the same bits on every call and at every row_chunk, a permutation
 // of the rows permutes the outputs, and a set listed twice gets the same bits twice.
+// Host plumbing shared with gsea.hip: check_sets and Packed (val_common.h), PhaseClock and the two searches (val_columns.h).
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -29,7 +30,7 @@
 #include <hip/hip_runtime.h>
 #include "handle.h"
 #include "lds_sort.h"
-#include "val_common.h"
+#include "val_columns.h"
 
 namespace osd {
 namespace {
@@ -131,13 +132,9 @@ __global__ __launch_bounds__(PW_MAX_THREADS) void pw_ssgsea(const float* __restr
     int r2sum = 0;                                             // at most 1024 * 65536
     for (int e = lane; e < m; e += 64) {
       const uint32_t key = pw_key(x[members[lo + e]]);         // checked by the host: in [0, D); not the padding: no NaN here
-      int l = 0, h = N;
-      while (l < h) { const int mid = (l + h) >> 1; if (s[mid] < key) l = mid + 1; else h = mid; }
+      const int l = lower_bound(s, 0, N, key);
       int u = l + 1;                                           // s[l] == key: the key is in the row
-      if (u < N && s[u] == key) {                              // a tie: where the run ends
-        h = N;
-        while (u < h) { const int mid = (u + h) >> 1; if (s[mid] <= key) u = mid + 1; else h = mid; }
-      }
+      if (u < N && s[u] == key) u = upper_bound(s, u, N, key); // a tie: where the run ends
       int r2 = l + u + 1;                                      // twice the mid-rank: 2 ... 2 D
       r2 = r2 < 2 * D ? r2 : 2 * D;                            // stays inside the table even if X changes under the call
       const double t = table[r2];
@@ -189,28 +186,6 @@ __global__ __launch_bounds__(PA_THREADS) void pa_partial(const double* __restric
   }
 }
 
-struct PwClock {                           // optional: milliseconds of the two phases
-  float* ms;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  explicit PwClock(float* out) : ms(out) {}
-  ~PwClock() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-  hipError_t init() {
-    if (!ms) return hipSuccess;
-    ms[0] = ms[1] = 0.f;
-    for (hipEvent_t& e : ev) { const hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; }
-    return hipSuccess;
-  }
-  hipError_t mark(int i, hipStream_t s) { return ms ? hipEventRecord(ev[i], s) : hipSuccess; }
-  hipError_t read() {                      // after the stream has drained
-    if (!ms) return hipSuccess;
-    for (int i = 0; i < 2; ++i) {
-      const hipError_t r = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-      if (r != hipSuccess) return r;
-    }
-    return hipSuccess;
-  }
-};
-
 int pathway_scores(void* stream, int device, const float* X, int64_t rows, int ld, int D, int method, const float* center,
                    const float* scale, const int32_t* offsets, const int32_t* members, int S, const double* table, int row_chunk,
                    double* out, float* phase_ms) {
@@ -219,46 +194,30 @@ int pathway_scores(void* stream, int device, const float* X, int64_t rows, int l
   if (method == PW_SSGSEA && !table) { set_error("bad argument (ssgsea needs the rank table)"); return OSD_EINVAL; }
   if (D < 2 || D > PW_MAX_D) { set_error("bad argument (2 <= D <= %d)", PW_MAX_D); return OSD_EINVAL; }
   if (rows < 1 || ld < D || S < 1 || row_chunk < 0) { set_error("bad argument (rows >= 1, ld >= D, S >= 1, row_chunk >= 0)"); return OSD_EINVAL; }
-  if (offsets[0] != 0) { set_error("set_offsets must start at 0"); return OSD_EINVAL; }
-  std::vector<int32_t> seen((size_t)D, -1);
-  for (int s = 0; s < S; ++s) {
-    const int64_t m = (int64_t)offsets[s + 1] - offsets[s];
-    if (m < 1 || m > PW_MAX_M || m >= D) { set_error("set %d has %lld members: 1 <= m <= %d and m < D are needed", s, (long long)m, PW_MAX_M); return OSD_EINVAL; }
-    for (int32_t e = offsets[s]; e < offsets[s + 1]; ++e) {
-      const int32_t g = members[e];
-      if (g < 0 || g >= D) { set_error("set %d holds the column %d outside [0, %d)", s, g, D); return OSD_EINVAL; }
-      if (seen[g] == s) { set_error("set %d holds the column %d more than once", s, g); return OSD_EINVAL; }
-      seen[g] = s;
-    }
-  }
+  std::vector<int32_t> seen;
+  OSD_TRY(check_sets(offsets, members, S, D, PW_MAX_M, "column", 'm', seen));
   const int M = offsets[S];
   const bool ranked = method == PW_SSGSEA;
 
   OSD_HIP(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
-  PwClock clock(phase_ms);
+  PhaseClock<2, float> clock(phase_ms);                        // upload, scoring
   OSD_HIP(clock.init());
   // one allocation, uploaded in one copy: the table first (doubles), then the offsets and the members
-  size_t bytes = 0;
-  auto take = [&bytes](size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; };
-  const size_t at_tab = take(ranked ? (size_t)(2 * D + 1) * sizeof(double) : 0);
-  const size_t at_off = take((size_t)(S + 1) * sizeof(int32_t)), at_mem = take((size_t)M * sizeof(int32_t)), tables = bytes;
+  Packed ws;
+  const size_t at_tab = ws.put(table, ranked ? (size_t)(2 * D + 1) * sizeof(double) : 0);
+  const size_t at_off = ws.put(offsets, (size_t)(S + 1) * sizeof(int32_t)), at_mem = ws.put(members, (size_t)M * sizeof(int32_t));
   const bool stats = !ranked && (center || scale);
-  const size_t at_cs = take(stats ? (size_t)M * sizeof(float2) : 0);   // filled on the device
-  std::vector<char> host(tables);
-  if (ranked) memcpy(host.data() + at_tab, table, (size_t)(2 * D + 1) * sizeof(double));
-  memcpy(host.data() + at_off, offsets, (size_t)(S + 1) * sizeof(int32_t));
-  memcpy(host.data() + at_mem, members, (size_t)M * sizeof(int32_t));
-  ValBuf ws;
-  OSD_TRY(ws.alloc(bytes));
+  const size_t at_cs = ws.take(stats ? (size_t)M * sizeof(float2) : 0);  // filled on the device
+  OSD_TRY(ws.alloc());
   OSD_HIP(clock.mark(0, st));
-  OSD_HIP(hipMemcpyAsync(ws.get(), host.data(), tables, hipMemcpyHostToDevice, st));
+  OSD_HIP(ws.upload(st));
   OSD_HIP(clock.mark(1, st));
-  OSD_HIP(hipStreamSynchronize(st));                           // the staging vector is free to go
-  const double* dtab = (const double*)(ws.get() + at_tab);
-  const int* doff = (const int*)(ws.get() + at_off);
-  const int* dmem = (const int*)(ws.get() + at_mem);
-  float2* dcs = stats ? (float2*)(ws.get() + at_cs) : nullptr;
+  OSD_HIP(hipStreamSynchronize(st));                           // the upload has left the staging vector
+  const double* dtab = ws.at<const double>(at_tab);
+  const int* doff = ws.at<const int>(at_off);
+  const int* dmem = ws.at<const int>(at_mem);
+  float2* dcs = stats ? ws.at<float2>(at_cs) : nullptr;
   if (stats) OSD_HIP(launched(pw_member_stats, dim3((unsigned)((M + 255) / 256)), 256, 0, st, dmem, M, center, scale, dcs));
 
   int N = 2;
@@ -284,7 +243,7 @@ int pathway_scores(void* stream, int device, const float* X, int64_t rows, int l
   }
   OSD_HIP(clock.mark(2, st));
   OSD_HIP(hipStreamSynchronize(st));                           // the workspace is free to go
-  OSD_HIP(clock.read());
+  OSD_HIP(clock.add());
   return OSD_OK;
 }
 
@@ -318,21 +277,15 @@ int osd_val_pathway_agreement(void* stream, int device, const double* scores, in
   if (tiles > INT32_MAX) { set_error("bad argument (too many rows)"); return OSD_EINVAL; }
   OSD_HIP(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
-  size_t bytes = 0;
-  auto take = [&bytes](size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; };
-  const size_t at_mu = take((size_t)2 * S * sizeof(double));
-  const size_t at_part = take((size_t)tiles * S * PA_SUMS * sizeof(double)), at_used = take((size_t)tiles * S * sizeof(long long));
-  ValBuf ws;
-  OSD_TRY(ws.alloc(bytes));
-  std::vector<double> stats((size_t)2 * S);
-  memcpy(stats.data(), mu_host, (size_t)S * sizeof(double));
-  memcpy(stats.data() + S, isd_host, (size_t)S * sizeof(double));
-  OSD_HIP(hipMemcpyAsync(ws.get() + at_mu, stats.data(), (size_t)2 * S * sizeof(double), hipMemcpyHostToDevice, st));
-  const double* dmu = (const double*)(ws.get() + at_mu);
-  double* dpart = (double*)(ws.get() + at_part);
-  long long* dused = (long long*)(ws.get() + at_used);
-  OSD_HIP(launched(pa_partial, dim3((unsigned)tiles, (unsigned)S), PA_THREADS, 0, st, scores, rows, S, block, ld_b, dmu, dmu + S, dpart,
-                   dused));
+  Packed ws;
+  const size_t at_mu = ws.put(mu_host, (size_t)S * sizeof(double)), at_isd = ws.put(isd_host, (size_t)S * sizeof(double));
+  const size_t at_part = ws.take((size_t)tiles * S * PA_SUMS * sizeof(double)), at_used = ws.take((size_t)tiles * S * sizeof(long long));
+  OSD_TRY(ws.alloc());
+  OSD_HIP(ws.upload(st));
+  double* dpart = ws.at<double>(at_part);
+  long long* dused = ws.at<long long>(at_used);
+  OSD_HIP(launched(pa_partial, dim3((unsigned)tiles, (unsigned)S), PA_THREADS, 0, st, scores, rows, S, block, ld_b, ws.at<const double>(at_mu),
+                   ws.at<const double>(at_isd), dpart, dused));
   std::vector<double> part((size_t)tiles * S * PA_SUMS);
   std::vector<long long> used((size_t)tiles * S);
   OSD_HIP(hipMemcpyAsync(part.data(), dpart, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -1,8 +1,12 @@
-// val_common.h -- what the validator's translation units (validate.hip, corr.hip, glm.hip) share: the scope-lifetime device buffer, the
-// wavefront butterflies, the "one wavefront per row" indices, the checked kernel launch, the read-back and the column-list upload.
+// val_common.h -- what the validator's translation units (validate.hip, corr.hip, glm.hip and the later ones) share: the
+// scope-lifetime device buffer, the wavefront butterflies, the "one wavefront per row" indices, the checked kernel launch, the
+// read-back, the column-list upload, the check of a CSR set list and the packer of host tables into one allocation.  What the
+// sort-based statistics share on top of this is in val_columns.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
+#include <vector>
 #include "handle.h"
 
 namespace osd {
@@ -65,5 +69,47 @@ inline int upload_cols(int device, hipStream_t s, const int32_t* cols_host, int 
   OSD_HIP(hipMemcpyAsync(dc.get(), cols_host, (size_t)g * sizeof(int), hipMemcpyHostToDevice, s));
   return OSD_OK;
 }
+
+// A host list of S sets in CSR form over [0, D), checked before anything touches the device: offsets start at 0, every set has
+// 1 <= members <= max_members and fewer than D, every member lies in [0, D) and occurs once in its set.  The error texts call a
+// member a `noun` ("position", "column") and a set's size `size` ('k', 'm').  seen [D]: the last set that holds each index, or -1.
+inline int check_sets(const int32_t* offsets, const int32_t* members, int S, int D, int max_members, const char* noun, char size,
+                      std::vector<int32_t>& seen) {
+  if (offsets[0] != 0) { set_error("set_offsets must start at 0"); return OSD_EINVAL; }
+  seen.assign((size_t)D, -1);
+  for (int s = 0; s < S; ++s) {
+    const int64_t k = (int64_t)offsets[s + 1] - offsets[s];
+    if (k < 1 || k > max_members || k >= D) {
+      set_error("set %d has %lld members: 1 <= %c <= %d and %c < D are needed", s, (long long)k, size, max_members, size);
+      return OSD_EINVAL;
+    }
+    for (int32_t e = offsets[s]; e < offsets[s + 1]; ++e) {
+      const int32_t g = members[e];
+      if (g < 0 || g >= D) { set_error("set %d holds the %s %d outside [0, %d)", s, noun, g, D); return OSD_EINVAL; }
+      if (seen[g] == s) { set_error("set %d holds the %s %d more than once", s, noun, g); return OSD_EINVAL; }
+      seen[g] = s;
+    }
+  }
+  return OSD_OK;
+}
+
+// One device allocation carved at multiples of 256 bytes.  put() reserves room for a host table and stages it, take() reserves room
+// the device fills; after alloc(), upload() sends every staged table in one copy (put the tables first: the copy ends at the last
+// one).  The staging vector lives as long as the packer, and the caller waits for the stream before it relies on that no longer.
+struct Packed {
+  size_t bytes = 0;
+  std::vector<char> host;
+  ValBuf ws;
+  size_t take(size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; }
+  size_t put(const void* table, size_t n) {
+    const size_t at = take(n);
+    host.resize(bytes);
+    if (n) memcpy(host.data() + at, table, n);
+    return at;
+  }
+  int alloc() { return ws.alloc(bytes); }
+  hipError_t upload(hipStream_t s) { return hipMemcpyAsync(ws.get(), host.data(), host.size(), hipMemcpyHostToDevice, s); }
+  template <class T> T* at(size_t offset) const { return reinterpret_cast<T*>(ws.get() + offset); }
+};
 
 }  // namespace osd

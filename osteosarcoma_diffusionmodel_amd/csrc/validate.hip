@@ -1,14 +1,14 @@
 // validate.hip -- on-GPU validation metrics (utils/validation.py): RBF-MMD as a
 // blocked Gram GEMM with an exp+reduce epilogue, per-feature two-sample Kolmogorov-Smirnov extremes over
-// a hand-written segmented radix sort (segsort.h), within-pathway mean correlation and Pearson correlation as wavefront reductions.
+// a hand-written segmented radix sort (segsort.hip, through seg_sort), within-pathway mean correlation and Pearson correlation as
+// wavefront reductions.
 // Entry points are stream/device based (no model handle) and synchronous: they return host scalars.
 #include <limits.h>
 #include <vector>
 #include "handle.h"
 #include "kernels.h"
 #include "launch.h"
-#include "segsort.h"
-#include "val_common.h"
+#include "val_columns.h"
 
 namespace osd {
 
@@ -32,12 +32,6 @@ __global__ void k_gather_cols(const float* src, int ld, int64_t rows, int nf, fl
   }
 }
 
-__device__ __forceinline__ long long upper_bound_cnt(const float* a, long long n, float v) {   // #{a_i <= v}, a sorted
-  long long lo = 0, hi = n;
-  while (lo < hi) { const long long mid = (lo + hi) >> 1; if (a[mid] <= v) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-
 // extremes over all sample points v of cnt(a<=v)*n2 - cnt(b<=v)*n1 (scipy.stats.ks_2samp's cddiffs, exact integers)
 __global__ void k_ks_extremes(const float* a, const float* b, long long n1, long long n2, long long* omax, long long* omin) {
   const int f = blockIdx.y;
@@ -46,7 +40,7 @@ __global__ void k_ks_extremes(const float* a, const float* b, long long n1, long
   long long mx = LLONG_MIN, mn = LLONG_MAX;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n1 + n2; i += (long long)gridDim.x * blockDim.x) {
     const float v = i < n1 ? af[i] : bf[i - n1];
-    const long long d = upper_bound_cnt(af, n1, v) * n2 - upper_bound_cnt(bf, n2, v) * n1;
+    const long long d = upper_bound(af, 0ll, n1, v) * n2 - upper_bound(bf, 0ll, n2, v) * n1;
     mx = d > mx ? d : mx;
     mn = d < mn ? d : mn;
   }
@@ -336,38 +330,20 @@ int osd_val_ks_extremes(void* stream, int device, const float* real, int64_t n1,
   OSD_TRY(sorted.alloc((na + nb) * 4));
   OSD_TRY(ext.alloc((size_t)2 * nf * sizeof(long long)));
   float* ca = cols.as<float>(); float* cb = ca + na;
-  float* sa = sorted.as<float>(); float* sb = sa + na;
+  float* sa = sorted.as<float>(); float* sb = sa + na;     // the sort's second buffers
   OSD_HIP(launched(k_gather_cols, 2048, 256, 0, s, real, ld, n1, nf, ca));
   OSD_HIP(launched(k_gather_cols, 2048, 256, 0, s, synth, ld, n2, nf, cb));
-  // four stable 8-bit passes, ping-pong between the two buffers: the sorted floats end up back in `cols`
-  {
-    const int wps_a = (int)((n1 + SEG_CHUNK - 1) / SEG_CHUNK), wps_b = (int)((n2 + SEG_CHUNK - 1) / SEG_CHUNK);
-    OSD_TRY(tmp.alloc((size_t)nf * 256 * (size_t)(wps_a > wps_b ? wps_a : wps_b) * sizeof(int)));
-    int* cnt = tmp.as<int>();
-    auto sort_segments = [&](float* buf0, float* buf1, long long n, int wps) -> int {
-      uint32_t* a = (uint32_t*)buf0; uint32_t* b = (uint32_t*)buf1;
-      const dim3 grid((unsigned)((wps + SEG_WAVES - 1) / SEG_WAVES), (unsigned)nf), block(64 * SEG_WAVES);
-      for (int pass = 0; pass < 4; ++pass) {
-        const int shift = 8 * pass;
-        OSD_HIP(launched(pass == 0 ? k_seg_count<true> : k_seg_count<false>, grid, block, 0, s, a, n, wps, shift, cnt));
-        OSD_HIP(launched(k_seg_scan, dim3((unsigned)nf), dim3(256), 0, s, cnt, wps));
-        OSD_HIP(launched(pass == 0 ? k_seg_scatter<true, false> : pass == 3 ? k_seg_scatter<false, true> : k_seg_scatter<false, false>,
-                         grid, block, 0, s, a, b, n, wps, shift, cnt));
-        uint32_t* t = a; a = b; b = t;
-      }
-      return OSD_OK;
-    };
-    OSD_TRY(sort_segments(ca, sa, (long long)n1, wps_a));
-    OSD_TRY(sort_segments(cb, sb, (long long)n2, wps_b));
-    sa = ca; sb = cb;                     // an even number of passes: back in the first buffer
-  }
+  // segsort.h: the sorted floats end up back in `cols`
+  OSD_TRY(tmp.alloc(seg_count_bytes(n1 > n2 ? n1 : n2, nf)));
+  OSD_TRY(seg_sort(s, ca, sa, (long long)n1, nf, tmp.as<int>()));
+  OSD_TRY(seg_sort(s, cb, sb, (long long)n2, nf, tmp.as<int>()));
   std::vector<long long> init((size_t)2 * nf);
   for (int f = 0; f < nf; ++f) { init[f] = LLONG_MIN; init[nf + f] = LLONG_MAX; }
   long long* emax = ext.as<long long>(); long long* emin = emax + nf;
   OSD_HIP(hipMemcpyAsync(emax, init.data(), init.size() * sizeof(long long), hipMemcpyHostToDevice, s));
   int bx = (int)((n1 + n2 + 255) / 256);
   if (bx > 256) bx = 256;
-  OSD_HIP(launched(k_ks_extremes, dim3(bx, nf), 256, 0, s, sa, sb, (long long)n1, (long long)n2, emax, emin));
+  OSD_HIP(launched(k_ks_extremes, dim3(bx, nf), 256, 0, s, ca, cb, (long long)n1, (long long)n2, emax, emin));
   std::vector<long long> res((size_t)2 * nf);
   OSD_HIP(read_back(s, res.data(), emax, res.size() * sizeof(long long)));
   for (int f = 0; f < nf; ++f) { dmax_out[f] = res[f]; dmin_out[f] = res[nf + f]; }

@@ -1,4 +1,4 @@
-"""GPU: ``osd_val_group_ranks`` (csrc/diffexp.hip: de_gather, the segmented sort, de_stats, de_finish), and
+"""GPU: ``osd_val_group_ranks`` (csrc/diffexp.hip: col_tiles<true>, the segmented sort, de_stats, de_finish), and
 ``BiologicalValidator.differential_fidelity`` above it, against the int64 / float64 restatement of tests/diffexp_helpers.py evaluated
 on the same fp32 inputs.
 

@@ -1,4 +1,4 @@
-"""GPU: ``osd_val_marginals`` (csrc/marginal.hip: marg_transpose, the segmented sort, marg_stats, marg_finish), and
+"""GPU: ``osd_val_marginals`` (csrc/marginal.hip: col_tiles<false>, the segmented sort, marg_stats, marg_finish), and
 ``BiologicalValidator.marginal_fidelity`` above it, against the float64 / int64 restatement of tests/marginal_helpers.py evaluated on
 the same fp32 inputs.
 
