@@ -834,6 +834,37 @@ int osd_val_cox_plan_destroy(void *plan);
  * host before any device call).  Synchronous; uses a grow-only per-device workspace held for the length of the call. */
 int osd_val_cox_eval(void *plan, const float *X, int64_t rows, int ld, int D, const float *center, const float *scale,
                      const float *w, double *loss_host, double *grad_dev, float *score_dev);
+/* The univariate Cox screen: one model per column, all columns in one call (csrc/cox_score.hip).  For every
+ * column c on its own, everything in double, with u_ic = ((double) x_ic - center_c) * scale_c, k_c = |beta_c| R_c (R_c = bound_dev[c],
+ * a caller's bound R_c >= max_i |u_ic|; k_c = 0 without bound_dev) and e_ic = exp(beta_c u_ic - k_c) <= 1; over the positions p of
+ * the plan's descending-time order, the risk set of p being every position up to the END of p's tie group (Breslow) and A0, A1, A2
+ * the sums of e, e u, e u^2 over it:
+ *   loglik_dev[c] = sum_p delta_p (beta_c u_pc - k_c - log A0)       the partial log-likelihood (k_c cancels: a shift of the exponent)
+ *   score_dev[c]  = sum_p delta_p (u_pc - A1 / A0)                   its derivative in beta_c
+ *   info_dev[c]   = sum_p delta_p (A2 / A0 - (A1 / A0)^2)            minus its second derivative
+ *   absmax_dev[c] = max_i |u_ic|                                     exact (a maximum of doubles); NULL: not wanted
+ * beta_dev NULL means beta = 0 and takes a path without exp: e = 1 and A0 is the risk set's size, an integer.  At beta = 0 score_dev is
+ * minus the gradient osd_val_cox_eval gives at w = 0, and score^2 / info the log-rank chi-square of the column.
+ * X dev float [rows][ld] with the layouts and the two load paths of osd_val_glm_eval (any base address, any ld >= D, never through a
+ * copy); center, scale: dev float [D]; beta_dev, bound_dev, the outputs: dev double [D]; rows must be the plan's.
+ * A call reads X twice, rows gathered by the plan's order.  A work item is a block of OSD_COXS_ROWS consecutive positions times a
+ * slab of 256 columns; a lane owns four columns of the slab and walks the block's rows in position order.  Pass 1 writes every item's
+ * totals of e, e u, e u^2 (and the block's max |u|); one launch turns the totals into per-column exclusive prefixes over the blocks;
+ * pass 2 re-reads X, carries the running sums from the prefix, adds delta_p (beta u - k) and delta_p u at every position and, at
+ * every position that ends a tie group holding d > 0 events, d log A0, d A1 / A0 and d (A2 / A0 - (A1 / A0)^2); a last launch adds
+ * the items' partial results in block order.  No floating-point atomics, no workgroup waits for another inside a kernel, every sum
+ * has one fixed order: the same inputs give the same bits, the partition depends on (rows, D) and the load path alone, and the
+ * arithmetic of one column depends neither on the other columns of the call nor on the load path.
+ * A column with scale 0 is dropped: its three outputs are exactly 0 (absmax too).  All censored: exact zeros.  Inputs must be finite.
+ * Without a bound, or with one smaller than max |u|, beta u - k can pass what exp holds; and with a valid bound the risk set of an
+ * event whose every beta u - k lies below about -745 sums to A0 = 0: the column's outputs are then not finite (inf or NaN), that
+ * column's alone -- survival.univariate_cox clamps |beta| R so that this cannot happen, and marks a non-finite column failed.
+ * rows >= 1, 1 <= D <= 8192, ld >= D, loglik_dev, score_dev and info_dev all given (OSD_EINVAL otherwise, checked on the host
+ * before any device call).  Synchronous; uses a grow-only per-device workspace held for the length of the call. */
+#define OSD_COXS_ROWS 128
+int osd_val_cox_score(void *plan, const float *X, int64_t rows, int ld, int D, const float *center, const float *scale,
+                      const double *beta_dev, const double *bound_dev, double *loglik_dev, double *score_dev, double *info_dev,
+                      double *absmax_dev);
 /* Harrell's concordance counts of a risk score, exact.  Over the ordered pairs (i, j) with event[i] != 0 and time[i] < time[j]
  * (strict: equal times are not comparable), counts_host (HOST int64 [4]) receives
  *   [0] the comparable pairs   [1] those with risk[i] > risk[j] (concordant)   [2] risk[i] < risk[j]   [3] risk[i] == risk[j]

@@ -29,13 +29,13 @@
 #include <mutex>
 #include <numeric>
 #include <vector>
+#include "cox_plan.h"
 #include "handle.h"
 #include "val_common.h"
 
 namespace osd {
 namespace {
 
-constexpr int COX_MAX_D = 8192;
 constexpr int COX_MAX_ITEMS = 768;       // workgroups of a pass, as osd_val_glm_eval's
 constexpr int COX_MIN_ITEM_ROWS = 16;    // an item writes D doubles: not for fewer rows than this
 constexpr int COX_MAX_WAVES = 8;
@@ -43,7 +43,6 @@ constexpr int COX_R = 4;                 // rows of a group
 constexpr int COX_RED_PARTS = 16;
 constexpr int SCAN_T = 256, SCAN_PER = 4, SCAN_BLOCK = SCAN_T * SCAN_PER;      // a scan block: 256 lanes x 4 consecutive elements
 constexpr int COX_MAX_PARTS = 1024;      // partial maxima of eta
-constexpr int COX_MAX_DEVICES = 64;
 static_assert(OSD_GLM_RUN_ROWS % COX_R == 0, "a run is a whole number of groups");
 
 struct CoxPassArgs {
@@ -399,12 +398,8 @@ __global__ __launch_bounds__(OSD_CONC_I_TILE) void conc_kernel(const float* __re
   }
 }
 
-// One grow-only workspace per device, held for the length of a call: a fit calls osd_val_cox_eval hundreds of times.
-struct Workspace {
-  std::mutex mu;
-  DevBuf<char> buf;
-};
-Workspace* const g_cox_ws = new Workspace[COX_MAX_DEVICES];  // never destroyed: no hipFree from a static destructor at process exit
+// One grow-only workspace per device (cox_plan.h): a fit calls osd_val_cox_eval hundreds of times.
+CoxWorkspace* const g_cox_ws = new CoxWorkspace[COX_MAX_DEVICES];  // never destroyed: no hipFree from a static destructor at process exit
 
 template <int NV, int TMAX>
 hipError_t cox_launch2(bool grad, bool aligned, unsigned items, unsigned T, hipStream_t s, const CoxPassArgs& a) {
@@ -422,17 +417,7 @@ hipError_t cox_launch(int NV, bool grad, bool aligned, unsigned items, unsigned 
   }
 }
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 }  // namespace
-
-struct CoxPlan {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int64_t rows = 0;
-  DevBuf<int> order, gstart, gend;       // by position in descending time: the row, the first and the last position of its tie group
-  DevBuf<unsigned char> ev;              // the event flag of the position
-};
 
 }  // namespace osd
 
@@ -452,6 +437,7 @@ int osd_val_cox_plan_create(int device, void* stream, const double* time_host, c
   }
   const int n = (int)rows;
   std::vector<int> order((size_t)n), gstart((size_t)n), gend((size_t)n);
+  std::vector<int> gev((size_t)n, 0);
   std::vector<unsigned char> ev((size_t)n);
   std::iota(order.begin(), order.end(), 0);
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return time_host[x] > time_host[y]; });
@@ -462,6 +448,7 @@ int osd_val_cox_plan_create(int device, void* stream, const double* time_host, c
     p = e + 1;
   }
   for (int p = 0; p < n; ++p) ev[(size_t)p] = event_host[order[(size_t)p]] == 1.0 ? 1 : 0;
+  for (int p = 0; p < n; ++p) gev[(size_t)gend[(size_t)p]] += ev[(size_t)p];
 
   OSD_HIP(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
@@ -472,10 +459,12 @@ int osd_val_cox_plan_create(int device, void* stream, const double* time_host, c
     OSD_TRY(pl->gstart.reserve(n));
     OSD_TRY(pl->gend.reserve(n));
     OSD_TRY(pl->ev.reserve(n));
+    OSD_TRY(pl->gev.reserve(n));
     OSD_HIP(hipMemcpyAsync(pl->order.get(), order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
     OSD_HIP(hipMemcpyAsync(pl->gstart.get(), gstart.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
     OSD_HIP(hipMemcpyAsync(pl->gend.get(), gend.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
     OSD_HIP(hipMemcpyAsync(pl->ev.get(), ev.data(), (size_t)n, hipMemcpyHostToDevice, s));
+    OSD_HIP(hipMemcpyAsync(pl->gev.get(), gev.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
     OSD_HIP(hipStreamSynchronize(s));                        // the host vectors end with this call
     return OSD_OK;
   };
@@ -530,7 +519,7 @@ int osd_val_cox_eval(void* plan, const float* X, int64_t rows, int ld, int D, co
   a.ld = ld; a.rows = rows; a.rows_per = gpi * COX_R;
   a.D = D; a.Dl = Dq;
 
-  Workspace& ws = g_cox_ws[pl->device];
+  CoxWorkspace& ws = g_cox_ws[pl->device];
   std::lock_guard<std::mutex> hold(ws.mu);
   size_t off = 0;
   auto carve = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };

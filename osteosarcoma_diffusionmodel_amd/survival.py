@@ -1,8 +1,9 @@
 """Survival utility, host side: the driver that fits an L2-regularised Cox proportional-hazards model
 through an ``eval_fn`` -- the device kernels behind ``DeviceKernels.cox_eval`` or a float64 restatement, the driver cannot tell --,
 Harrell's concordance as exact pair counts, and the summary that turns two fits and their counts into the ``survival_*`` result keys
-of ``BiologicalValidator.survival_utility``.  numpy float64 throughout; no device code: this module imports on a machine without a
-GPU."""
+of ``BiologicalValidator.survival_utility``; and, for ``prognostic_fidelity`` (section 3.32), the per-feature Newton driver
+``univariate_cox`` and the screen ``cox_screen`` over ``DeviceKernels.cox_score``.  numpy float64 throughout; no device code: this
+module imports on a machine without a GPU."""
 from __future__ import annotations
 
 from typing import Callable, Dict, Mapping, Sequence, Tuple
@@ -109,4 +110,119 @@ def survival_summary(coef_tstr, coef_trtr, counts_tstr: Sequence[int], counts_tr
            "survival_comparable_pairs": float(int(counts_trtr[0]))}
     for name, share in event_shares.items():
         out[f"survival_event_share_{name}"] = float(share)
+    return out
+
+
+# ---- the univariate Cox screen: one model per feature -----------------------------------------------------
+def _two_sided_p(z: np.ndarray) -> np.ndarray:
+    from scipy.special import ndtr
+    return np.minimum(2.0 * ndtr(-np.abs(z)), 1.0)
+
+
+def univariate_cox(eval_fn: Callable[[np.ndarray], Tuple[np.ndarray, np.ndarray, np.ndarray]], D: int, bound, max_iter: int = 15,
+                   tol: float = 1e-8, max_abs_eta: float = 30.0, start=None) -> Dict[str, np.ndarray]:
+    """D one-parameter Cox fits side by side, by Newton's method from beta = 0.  ``eval_fn(beta [D]) -> (loglik, score, info)``, float64
+    [D] each, returns every column's partial log-likelihood, its derivative and minus its second derivative at that column's own
+    beta, as ``osd_val_cox_score`` does, and is all the driver knows about the data.  ``bound`` [D]: R_c >= max_i |u_ic|.
+    ``start``: the three arrays at beta = 0 where the caller has them already (a screen does), which saves that evaluation.
+
+    One ``eval_fn`` call per iteration serves all columns.  A column proposes beta + step, step = score / info, clamped so that
+    |beta_c| bound_c <= ``max_abs_eta`` (the exponent stays where exp holds it).  Where the log-likelihood did not fall the proposal is
+    accepted and the next step comes from the new score and information; where it fell the column stays and its step is halved.  A
+    column whose NEXT step, score / info at the beta it has just accepted (or at 0), is at most ``tol`` in size is converged and frozen
+    there: that step is not taken.  A column that can no longer move because of the
+    clamp (a feature that separates the events perfectly has no finite maximum) is frozen with ``converged=False`` and a finite
+    beta at the clamp.  A column with info <= 0 or a non-finite value -- at 0: a constant feature, a cohort without events -- is marked
+    ``failed``: beta, se, z and p are NaN.
+
+    Returns float64 / bool / int64 [D] arrays: ``beta``, ``se`` = info^-1/2 at beta, ``z_wald`` = beta / se, ``p_wald`` (two-sided
+    normal), ``loglik`` at beta, ``converged``, ``failed`` and ``iterations`` (the proposals a column made)."""
+    D = int(D)
+    if D < 1 or max_iter < 0 or not tol > 0 or not max_abs_eta > 0:
+        raise ValueError("univariate_cox needs D >= 1, max_iter >= 0, tol > 0 and max_abs_eta > 0")
+    R = np.asarray(bound, dtype=np.float64).reshape(D)
+    if not (R >= 0).all():
+        raise ValueError("bound must hold a non-negative number per column")
+    with np.errstate(divide="ignore"):
+        limit = np.where(R > 0, float(max_abs_eta) / np.where(R > 0, R, 1.0), np.inf)
+
+    def evaluate(b, given=None):
+        ll, sc, info = (np.asarray(v, dtype=np.float64).reshape(D) for v in (eval_fn(b) if given is None else given))
+        return ll, sc, info, np.isfinite(ll) & np.isfinite(sc) & np.isfinite(info) & (info > 0)
+
+    beta = np.zeros(D, dtype=np.float64)
+    ll, sc, info, ok = evaluate(beta, start)
+    ll, sc, info = ll.copy(), sc.copy(), info.copy()
+    failed = ~ok
+    converged = np.zeros(D, dtype=bool)
+    iterations = np.zeros(D, dtype=np.int64)
+    step = np.zeros(D, dtype=np.float64)
+    step[ok] = sc[ok] / info[ok]
+    converged[ok] = np.abs(step[ok]) <= tol                      # nothing to fit: the score is already zero
+    active = ok & ~converged
+    for _ in range(int(max_iter)):
+        if not active.any():
+            break
+        cand = np.where(active, np.clip(beta + step, -limit, limit), beta)
+        stuck = active & (cand == beta)                          # at the clamp and pushed further out
+        active &= ~stuck
+        if not active.any():
+            break
+        iterations[active] += 1
+        ll2, sc2, info2, ok2 = evaluate(cand)
+        broke = active & ~ok2
+        failed |= broke
+        active &= ~broke
+        fell = active & (ll2 < ll - 1e-12 * (1.0 + np.abs(ll)))
+        step[fell] *= 0.5
+        take = active & ~fell
+        beta[take], ll[take], sc[take], info[take] = cand[take], ll2[take], sc2[take], info2[take]
+        step[take] = sc[take] / info[take]
+        done = take & (np.abs(step) <= tol)
+        converged |= done
+        active &= ~done
+    with np.errstate(divide="ignore", invalid="ignore"):
+        se = np.where(failed, np.nan, 1.0 / np.sqrt(np.where(info > 0, info, np.nan)))
+        out_beta = np.where(failed, np.nan, beta)
+        z = out_beta / se
+    return {"beta": out_beta, "se": se, "z_wald": z, "p_wald": np.where(failed, np.nan, _two_sided_p(np.nan_to_num(z))),
+            "loglik": np.where(failed, np.nan, ll), "converged": converged & ~failed, "failed": failed, "iterations": iterations}
+
+
+def cox_screen(k, x, plan, center, scale, mle: bool = True, max_iter: int = 15, tol: float = 1e-8) -> Dict[str, np.ndarray]:
+    """The univariate Cox screen of one cohort: per feature of ``x`` [rows, D] (on ``k``'s device) the score test at beta = 0 and the
+    hazard ratio per unit of u = (x - center) * scale.  ``k.cox_score(x, center, scale, plan, beta=None, bound=None, absmax=False)
+    -> (loglik, score, info, absmax)`` is ``DeviceKernels.cox_score`` or a float64 stand-in; ``plan`` is ``k.cox_plan(time, event)``.
+
+      ``z_score``, ``p_score``  score / sqrt(info) at 0 -- for a 0/1 feature its square is the log-rank chi-square -- and its two-sided
+                                normal p-value
+      ``q``                     ``diffexp.bh_qvalues`` over the features with a finite p; NaN elsewhere
+      ``effect``                the log hazard ratio per unit of u: with ``mle`` the maximum-likelihood beta of ``univariate_cox``
+                                (bound: the call's own max |u|), else the one-step estimate score / info at 0
+      ``hr``                    exp(effect)
+      ``score0``, ``info0``, ``absmax`` and, with ``mle``, every array of ``univariate_cox``
+
+    A dropped feature (scale 0) has info 0: z, p, q and effect are NaN and ``failed`` is True."""
+    from .diffexp import bh_qvalues
+    D = int(x.shape[1])
+    ll0, sc0, info0, absmax = k.cox_score(x, center, scale, plan, absmax=True)
+    ll0, sc0, info0, absmax = (np.asarray(v, dtype=np.float64).reshape(D) for v in (ll0, sc0, info0, absmax))
+    live = np.isfinite(sc0) & np.isfinite(info0) & (info0 > 0)
+    safe = np.where(live, info0, 1.0)
+    z = np.where(live, sc0 / np.sqrt(safe), np.nan)
+    p = np.where(live, _two_sided_p(np.nan_to_num(z)), np.nan)
+    q = np.full(D, np.nan)
+    if live.any():
+        q[live] = bh_qvalues(p[live])
+    out = {"z_score": z, "p_score": p, "q": q, "score0": sc0, "info0": info0, "absmax": absmax}
+    if mle:
+        fit = univariate_cox(lambda b: k.cox_score(x, center, scale, plan, beta=b, bound=absmax)[:3], D, absmax, max_iter=max_iter,
+                             tol=tol, start=(ll0, sc0, info0))
+        out.update(fit)
+        out["effect"] = fit["beta"]
+    else:
+        out["effect"] = np.where(live, sc0 / safe, np.nan)
+        out["failed"], out["converged"] = ~live, live.copy()
+    with np.errstate(over="ignore"):
+        out["hr"] = np.exp(out["effect"])
     return out

@@ -525,6 +525,38 @@ class DeviceKernels:
                                          C.byref(loss), L.ptr(g), L.ptr(z)))
         return float(loss.value), (None if g is None else g.cpu().numpy()), z
 
+    def cox_score(self, x: torch.Tensor, center, scale, plan: CoxPlan, beta=None, bound=None, absmax: bool = False):
+        """``osd_val_cox_score`` on the fp32 device tensor x [rows, D] (a column-slice view is read in place) and the plan of its
+        rows: one Cox model per column, in double.  With u = (x - center) * scale, returns ``(loglik, score, info, absmax)``, float64
+        [D] numpy each: every column's Breslow partial log-likelihood at its own ``beta[c]``, its derivative, minus its second
+        derivative, and max_i |u_ic| (None unless ``absmax=True``).  ``beta`` [D] float64 (None: 0, a path without exp); ``bound``
+        [D] float64, R_c >= max |u_ic|, shifts the exponent to beta u - |beta| R <= 0 (None: no shift); ``center`` and ``scale`` [D]
+        are rounded to fp32.  A column with scale 0 gives exact zeros.  The same inputs give the same bits, and a column gives the
+        same bits whatever other columns the call holds.  Runs on the plan's stream, as ``cox_eval`` does."""
+        if plan.closed:
+            raise ValueError("the plan has been closed")
+        x = _rows_view(x)
+        rows, D = x.shape
+        center, scale = _f32(center, x.device, (D,), "center"), _f32(scale, x.device, (D,), "scale")
+
+        def f64(v, name):
+            if v is None:
+                return None
+            t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64))
+            t = t.to(device=x.device, dtype=torch.float64).contiguous()
+            if tuple(t.shape) != (D,):
+                raise ValueError(f"{name} must have shape ({D},), got {tuple(t.shape)}")
+            return t
+
+        b, r = f64(beta, "beta"), f64(bound, "bound")
+        out = torch.empty((4, D), dtype=torch.float64, device=x.device)
+        if self._stream().value != plan.stream:
+            torch.cuda.current_stream(self.device).synchronize()
+        L.check(L.lib().osd_val_cox_score(plan.handle, L.ptr(x), rows, max(int(x.stride(0)), D), D, L.ptr(center), L.ptr(scale), L.ptr(b),
+                                          L.ptr(r), L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]) if absmax else None))
+        host = out.cpu().numpy()
+        return host[0], host[1], host[2], (host[3] if absmax else None)
+
     def concordance(self, time, event, risk):
         """``osd_val_concordance``: the exact pair counts ``(comparable, concordant, discordant, tied_risk)`` of
         ``survival.concordance_counts`` as Python integers.  The three columns [n] are rounded to fp32 and compared as such."""
@@ -658,18 +690,23 @@ def sharded_marginals(comm: ShardComm, k, real, synth_local, chunk_cols: int = 0
     return out
 
 
-def real_sample_sd(k, real) -> np.ndarray:
-    """float64 [D]: the sample standard deviation (ddof = 1) of every column of ``real``, from two ``k.col_centered_moments`` passes --
-    sums about 0 for the mean, then about the fp32-rounded mean, whose rounding the first moment takes out.  Exactly 0 for a constant
-    column (and for a one-row cohort)."""
+def real_center_and_sd(k, real):
+    """``(center, sd)`` of every column of ``real``: the fp32-rounded mean (float32 [D]) and the sample standard deviation (ddof = 1,
+    float64 [D]), from two ``k.col_centered_moments`` passes -- sums about 0 for the mean, then about the fp32-rounded mean, whose
+    rounding the first moment takes out.  The sd is exactly 0 for a constant column (and for a one-row cohort)."""
     n = int(real.shape[0])
     s0, _ = k.col_centered_moments(real)
     center = (np.asarray(s0, dtype=np.float64) / n).astype(np.float32)
     s, q = k.col_centered_moments(real, center)
     if n < 2:
-        return np.zeros(int(real.shape[1]), dtype=np.float64)
+        return center, np.zeros(int(real.shape[1]), dtype=np.float64)
     var = (np.asarray(q, dtype=np.float64) - np.asarray(s, dtype=np.float64) ** 2 / n) / (n - 1)
-    return np.sqrt(np.maximum(var, 0.0))
+    return center, np.sqrt(np.maximum(var, 0.0))
+
+
+def real_sample_sd(k, real) -> np.ndarray:
+    """float64 [D]: the sample standard deviation of ``real_center_and_sd``."""
+    return real_center_and_sd(k, real)[1]
 
 
 def marginal_ks(rows: Dict[str, np.ndarray]) -> np.ndarray:
@@ -960,6 +997,7 @@ def corr_summary(stats: Dict[str, np.ndarray], bounds: Sequence[int], names: Seq
 # ---- downstream utility: fits of regularised linear heads over row shards -------------------------------
 GLM_RUN_ROWS = L.OSD_GLM_RUN_ROWS       # rows one fp32 gradient run of osd_val_glm_eval (and of osd_val_cox_eval) covers
 CONC_I_TILE, CONC_J_CHUNK = L.OSD_CONC_I_TILE, L.OSD_CONC_J_CHUNK      # rows of a workgroup and partners of an LDS chunk of osd_val_concordance
+COXS_ROWS = L.OSD_COXS_ROWS             # positions of one work item of osd_val_cox_score
 
 
 def pooled_standardisation(k, parts):
@@ -1133,6 +1171,57 @@ def survival_metrics(k, x_train, s_train, x_synth, s_synth, x_test, s_test, l2: 
         fits.append(dict(fit, center=center, scale=scale))
     out = SV.survival_summary(coefs[0], coefs[1], counts[0], counts[1], shares)
     return (out, fits) if return_fits else out
+
+
+# ---- prognostic-gene fidelity: one Cox model per feature and cohort -----------------------------------------
+def prognostic_metrics(k, x, s_real, y, s_synth, bounds=None, block_names=None, alpha: float = 0.05, top_k: int = 50,
+                       mle: bool = True):
+    """``BiologicalValidator.prognostic_fidelity`` on tensors: ``(summary, rows)``, the feature matrices on the kernels' device, the
+    survival matrices float64 numpy [rows, 2] = (time, event).  ``k`` needs ``col_centered_moments``, ``cox_plan`` and ``cox_score``
+    (DeviceKernels, or a float64 stand-in in the tests).  ``rows`` holds both screens over ALL features (``survival.cox_screen``;
+    a constant real column has scale 0 and NaNs), ``center``, ``scale`` and ``live``, the mask of the features the summary is over."""
+    surv = {"real": np.asarray(s_real, dtype=np.float64), "synthetic": np.asarray(s_synth, dtype=np.float64)}
+    D = int(x.shape[1])
+    for label, t in (("real", x), ("synthetic", y)):
+        s = surv[label]
+        if s.ndim != 2 or s.shape != (int(t.shape[0]), 2):
+            raise ValueError(f"the survival matrix of {label} must be [{int(t.shape[0])}, 2] = (time, event), got {s.shape}")
+        if not np.isfinite(s[:, 0]).all() or not np.isin(s[:, 1], (0.0, 1.0)).all():
+            raise ValueError(f"the times of {label} must be finite and its event flags 0 or 1")
+        if not s[:, 1].any():
+            raise ValueError(f"the {label} cohort has no event: no feature can be prognostic in it")
+    center, sd = real_center_and_sd(k, x)
+    live = sd > 0
+    with np.errstate(divide="ignore"):
+        scale = np.where(live, 1.0 / np.where(live, sd, 1.0), 0.0).astype(np.float32)
+    live &= scale > 0                                            # (a spread so large that 1 / sd is no fp32 number drops the column too)
+    if not live.any():
+        raise ValueError("every column of the real cohort is constant")
+    screens = {}
+    for label, t in (("real", x), ("synthetic", y)):
+        with k.cox_plan(surv[label][:, 0], surv[label][:, 1]) as plan:
+            screens[label] = SV.cox_screen(k, t, plan, center, scale, mle=mle)
+    idx = np.nonzero(live)[0]
+    sides = []
+    for label in ("real", "synthetic"):
+        e, q = screens[label]["effect"][idx], screens[label]["q"][idx]
+        dead = ~(np.isfinite(e) & np.isfinite(q))                # no information in this cohort (a constant synthetic column): no signal
+        sides.append({"effect": np.where(dead, 0.0, e), "q": np.where(dead, 1.0, q)})
+    if bounds is not None and len(bounds) > 2:                   # the blocks' bounds among the live features
+        bounds = [int((idx < b).sum()) for b in bounds]
+    one = DE.contrast_summary(sides[0], sides[1], alpha, top_k, bounds, block_names)
+    one["max_gap_feature"] = int(idx[one["max_gap_feature"]])
+    summary = {f"prog_{key}": v for key, v in one.items()}
+    summary["prog_features"] = int(live.sum())
+    summary["prog_constant_features"] = int(D - live.sum())
+    for label, short in (("real", "real"), ("synthetic", "synth")):
+        scr = screens[label]
+        summary[f"prog_not_converged_{short}"] = int((~scr["converged"][idx]).sum())
+        summary[f"prog_events_{short}"] = int(surv[label][:, 1].sum())
+        z = np.abs(scr["z_score"][idx])
+        summary[f"prog_max_abs_z_{short}"] = float(np.nanmax(z)) if np.isfinite(z).any() else float("nan")
+    rows = {"real": screens["real"], "synthetic": screens["synthetic"], "center": center, "scale": scale, "live": live}
+    return summary, rows
 
 
 class BiologicalValidator:
@@ -1413,6 +1502,44 @@ class BiologicalValidator:
             raise ValueError("alpha must lie in (0, 1] and top_k must be at least 1")
         bounds, block_names = corr_block_bounds(blocks, int(x.shape[1]))
         summary, rows = DE.differential_metrics(self.k, x, cs[0], y, cs[1], names, bounds, block_names, float(alpha), int(top_k))
+        return (summary, rows) if return_rows else summary
+
+    # -- prognostic genes: one Cox model per feature and cohort ---------------------------------------------
+    def prognostic_fidelity(self, real, real_surv, synthetic, synth_surv, blocks=None, alpha: float = 0.05, top_k: int = 50,
+                            mle: bool = True, return_rows: bool = False):
+        """Do the features that are prognostic among the real patients stay prognostic among the synthetic ones, in the same
+        direction and by the same hazard ratio?  ``*_surv`` is [rows, 2] = (time, event) as in ``survival_utility``: censoring is
+        respected -- a patient censored at 300 days is at risk until then and never a short survivor, unlike the median split
+        ``differential_fidelity`` would make of the time.  Per cohort one univariate Cox screen over every feature
+        (``survival.cox_screen`` over ``DeviceKernels.cox_score``: Breslow ties, a score test at 0 -- the log-rank test of the
+        feature -- with Benjamini-Hochberg q, and with ``mle`` the per-feature maximum-likelihood log hazard ratio by Newton
+        iterations, each two reads of the cohort; ``mle=False``: the one-step estimate score / info, two reads in all).  BOTH cohorts
+        are standardised with the REAL cohort's column mean and sample standard deviation, so an effect is a log hazard ratio per
+        real standard deviation in either cohort.  A constant real column is left out and counted.
+
+        Keys: ``prog_<key>`` for every key of ``diffexp.contrast_summary`` over the two screens' ``effect`` and ``q`` (a hit is
+        q < ``alpha``; ``prog_effect_slope`` below 1: the prognostic signal is flattened; ``prog_max_gap_feature`` is a column index
+        of ``real``; with ``blocks``, an ordered ``{name: width}`` mapping, ``prog_effect_pearson_<block>``), ``prog_features``,
+        ``prog_constant_features``, ``prog_not_converged_real`` / ``_synth`` (features whose fit hit the clamp, ran out of
+        iterations or has no information in that cohort; such a synthetic feature counts as effect 0, q 1),
+        ``prog_events_real`` / ``_synth`` and ``prog_max_abs_z_real`` / ``_synth``.  ``return_rows=True`` also returns both
+        screens' per-feature arrays.  An all-censored cohort raises a ValueError naming it.  At most 8192 features.  On a
+        ``sharded=True`` validator the method raises a ValueError: a risk set couples the rows of different shards."""
+        if self.sharded:
+            raise ValueError("prognostic_fidelity is not available on a sharded validator: the risk set of a patient holds rows of "
+                             "every shard")
+        x, y = _dev(real, self.device), _dev(synthetic, self.device)
+        for label, t in (("real", x), ("synthetic", y)):
+            if t.dim() != 2 or t.shape[1] != x.shape[1] or t.shape[1] < 1 or t.shape[0] < 2:
+                raise ValueError(f"{label} must be [rows >= 2, {x.shape[1]}]: the cohorts must have the same features")
+            if not bool(torch.isfinite(t).all().item()):
+                raise ValueError(f"{label} holds non-finite values")
+        if not 0.0 < float(alpha) <= 1.0 or int(top_k) < 1:
+            raise ValueError("alpha must lie in (0, 1] and top_k must be at least 1")
+        bounds, block_names = corr_block_bounds(blocks, int(x.shape[1]))
+        summary, rows = prognostic_metrics(self.k, x, np.asarray(_host(real_surv), dtype=np.float64), y,
+                                           np.asarray(_host(synth_surv), dtype=np.float64), bounds, block_names, float(alpha),
+                                           int(top_k), bool(mle))
         return (summary, rows) if return_rows else summary
 
     # -- pathway enrichment: preranked GSEA with a device permutation null (DESIGN.md section 3.30) ------------------------------------
@@ -1765,8 +1892,11 @@ class BiologicalValidator:
                      subtype_conditions=None, survival=None, marginals: bool = False, differential=None,
                      differential_names=None, enrichment=None, enrichment_names=None,
                      enrichment_permutations: int = 1000, consistency: bool = False,
-                     consistency_method: str = "mean") -> Dict[str, float]:
-        """``consistency=True`` adds ``pathway_consistency``'s ``pwc_*`` keys (the real cohort's ``pwc_real_*`` among them): the
+                     consistency_method: str = "mean", prognostic=None) -> Dict[str, float]:
+        """``prognostic=(real_surv, synth_surv)`` adds ``prognostic_fidelity``'s ``prog_*`` keys on the combined matrices (blocks
+        ``mutations`` / ``expression`` / ``pathways``; each ``*_surv`` is [rows, 2] = (time, event)); with the default None nothing
+        changes.
+        ``consistency=True`` adds ``pathway_consistency``'s ``pwc_*`` keys (the real cohort's ``pwc_real_*`` among them): the
         generated pathway frame against the scores of the generated expression frame, the sets from ``pathway_gene_matrix`` (genes x
         pathways 0/1, a DataFrame), the method ``consistency_method``; with the default nothing changes.
         ``enrichment=(real_cond, synth_cond)`` adds ``enrichment_fidelity``'s ``gsea_*`` keys on the expression frames; it needs
@@ -1879,6 +2009,11 @@ class BiologicalValidator:
                 raise ValueError("validate_all(consistency=True) needs pathway_gene_matrix, a genes x pathways DataFrame")
             all_results.update(self.pathway_consistency(synth_expression, synth_pathways, pathway_gene_matrix, real_expression,
                                                         real_pathways, method=consistency_method))
+        if prognostic is not None:
+            if not isinstance(prognostic, (tuple, list)) or len(prognostic) != 2:
+                raise ValueError("validate_all(prognostic=...) needs (real_surv, synth_surv)")
+            widths = {"mutations": parts_r[0].shape[1], "expression": parts_r[1].shape[1], "pathways": parts_r[2].shape[1]}
+            all_results.update(self.prognostic_fidelity(real_combined, prognostic[0], synth_combined, prognostic[1], blocks=widths))
         logger.info("=" * 50)
         logger.info("VALIDATION SUMMARY")
         logger.info("=" * 50)
