@@ -865,7 +865,29 @@ int osd_val_cox_eval(void *plan, const float *X, int64_t rows, int ld, int D, co
 int osd_val_cox_score(void *plan, const float *X, int64_t rows, int ld, int D, const float *center, const float *scale,
                       const double *beta_dev, const double *bound_dev, double *loglik_dev, double *score_dev, double *info_dev,
                       double *absmax_dev);
-/* Harrell's concordance counts of a risk score, exact.  Over the ordered pairs (i, j) with event[i] != 0 and time[i] < time[j]
+/* The two skinny products of a block subspace iteration (csrc/pca.hip): the top principal directions of a
+ * cohort without its D x D Gram matrix.  With u_rc = ((double) x_rc - center_c) * scale_c (scale NULL: 1), everything after the load
+ * in double:
+ *   osd_val_pca_project      Z_dev[r][j] = sum_c u_rc V[c][j]     DEVICE double [rows][l], overwritten
+ *                            norm2_dev[r] = sum_c u_rc^2          DEVICE double [rows]; NULL: not wanted
+ *   osd_val_pca_backproject  W_dev[c][j] = sum_r u_rc Z[r][j]     DEVICE double [D][l], overwritten
+ * X dev float [rows][ld] with the layouts and the two load paths of osd_val_glm_eval (any base address, any ld >= D, a column-slice
+ * view is read in place, never through a copy); center, scale: dev double [D]; V: dev double [D][l]; Z: dev double [rows][l].
+ * One iteration of the subspace method is one call of each, so X is read twice.  A work item is a block of rows times a slab of
+ * columns, one wavefront: project gives a lane one of 64 rows and adds its terms in column order, the slabs are then added in slab
+ * order; backproject gives a lane two columns and adds the block's rows in row order, the blocks are then added in a fixed order.
+ * Vector FMAs in double; the small matrix is read through wave-uniform addresses.  No floating-point atomics, no workgroup waits
+ * for another: the same inputs give the same bits, and the partition depends on (rows, D, l) and the load path alone.  A column with
+ * scale 0 contributes nothing.  Integer data within 2^53 give exact integers.  Inputs must be finite.
+ * 1 <= l <= OSD_PCA_MAX_DIRS, l <= D <= 32768, ld >= D, 1 <= rows < 2^31, no NULL pointer but scale and norm2_dev (OSD_EINVAL
+ * otherwise, checked on the host before any launch).  Synchronous; uses a grow-only per-device workspace held for the length of the
+ * call. */
+#define OSD_PCA_MAX_DIRS 32
+int osd_val_pca_project(void *stream, int device, const float *X, int64_t rows, int ld, int D, const double *center,
+                        const double *scale, const double *V, int l, double *Z_dev, double *norm2_dev);
+int osd_val_pca_backproject(void *stream, int device, const float *X, int64_t rows, int ld, int D, const double *center,
+                            const double *scale, const double *Z_dev, int l, double *W_dev);
+/* Harrell's concordance counts of a risk score, exact. Over the ordered pairs (i, j) with event[i] != 0 and time[i] < time[j]
  * (strict: equal times are not comparable), counts_host (HOST int64 [4]) receives
  *   [0] the comparable pairs   [1] those with risk[i] > risk[j] (concordant)   [2] risk[i] < risk[j]   [3] risk[i] == risk[j]
  * and C = ([1] + [3] / 2) / [0].  time_dev, event_dev, risk_dev: dev float [n]; comparisons are those of the fp32 values.  A lane

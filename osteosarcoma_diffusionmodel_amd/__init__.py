@@ -7,9 +7,10 @@ Host-side mirror of the reference's Python API over the C ABI of libosdiff.so:
 """
 from .diffusion import BiologyAwareDiffusion, BiologyAwareDiffusionModel  # noqa: F401
 from .generate import SyntheticPatientGenerator, generate_patients, load_trained_model  # noqa: F401
+from . import pca  # noqa: F401  (DevicePCA: principal components by subspace iteration on the device)
 
 __all__ = ["BiologyAwareDiffusionModel", "BiologyAwareDiffusion", "SyntheticPatientGenerator",
-           "generate_patients", "load_trained_model"]
+           "generate_patients", "load_trained_model", "pca"]
 
 
 def _respect_cpu_quota():

@@ -26,6 +26,7 @@ OSD_GLM_LOGISTIC, OSD_GLM_SQUARED = 0, 1
 OSD_GLM_RUN_ROWS = 128
 OSD_CONC_I_TILE, OSD_CONC_J_CHUNK = 256, 1024
 OSD_COXS_ROWS = 128
+OSD_PCA_MAX_DIRS = 32
 OSD_XF_IDENTITY, OSD_XF_STANDARD, OSD_XF_QUANTILE_NORMAL = 0, 1, 2
 OSD_XF_MAX_Q = 1024
 
@@ -139,6 +140,8 @@ _SIGNATURES = {
     "osd_val_cox_plan_destroy": (C.c_int, [_P]),
     "osd_val_cox_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_double), _P, _P]),
     "osd_val_cox_score": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "osd_val_pca_project": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P]),
+    "osd_val_pca_backproject": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
     "osd_val_concordance": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "osd_xf_apply": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_int]),
     "osd_set_constraints": (C.c_int, [_P, C.POINTER(OsdConstraints)]),

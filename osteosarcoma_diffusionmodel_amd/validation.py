@@ -7,7 +7,8 @@ Wasserstein-1 distance and the out-of-range share of EVERY feature (``osd_val_ma
 
 Host-side by design, as SURVEY section 8f-1 prescribes: p-values and chi-square statistics from the exact device counts
 (``scipy.stats``), and the Wasserstein distance on 10 principal components (``sklearn`` PCA + ``scipy``, :256-269),
-which the reference itself computes that way.
+which the reference itself computes that way -- by default; ``statistical_tests(..., pca="device")`` takes it from
+``pca.DevicePCA`` without downloading a cohort, and ``embedding_fidelity`` builds the ``pca_*`` checks on the same fit.
 
 Multi-GPU (BASELINE config 5): ``BiologicalValidator(config, sharded=True)`` under an initialised
 ``torch.distributed`` treats every *synthetic* argument as this rank's row shard (the real cohort is small and
@@ -31,6 +32,7 @@ from . import cluster as CL
 from . import diffexp as DE
 from . import enrichment as EN
 from . import pathways as PW
+from . import pca as PC
 from . import survival as SV
 from . import utility as U
 from .cluster import subtype_summary      # noqa: F401  (the subtype_* figures: pure NumPy, documented there)
@@ -556,6 +558,63 @@ class DeviceKernels:
                                           L.ptr(r), L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]) if absmax else None))
         host = out.cpu().numpy()
         return host[0], host[1], host[2], (host[3] if absmax else None)
+
+    def col_moments64(self, t: torch.Tensor, center=None):
+        """``col_centered_moments`` for a row shard that may be empty: (sum, sumsq) float64 [D] numpy of (x - c) and (x - c)^2 over
+        the rows of the fp32 device tensor t [rows >= 0, D], exact zeros without rows.  The partial sums of row shards about one
+        common centre add up, which is how ``pca.DevicePCA`` takes its float64 mean and sample sd."""
+        if t.dim() != 2 or t.shape[1] < 1:
+            raise ValueError("a [rows, features >= 1] tensor is needed")
+        if int(t.shape[0]) == 0:
+            return np.zeros(int(t.shape[1])), np.zeros(int(t.shape[1]))
+        return self.col_centered_moments(t, center)
+
+    def _pca_args(self, x: torch.Tensor, center, scale, m, m_rows: int):
+        """(x view, rows, D, l, center, scale, m) as ``osd_val_pca_*`` take them: float64 contiguous device tensors."""
+        x = _rows_view(x)
+        rows, D = x.shape
+
+        def f64(v, shape, name):
+            t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64))
+            t = t.to(device=x.device, dtype=torch.float64).contiguous()
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+            return t
+
+        if not hasattr(m, "shape") or len(m.shape) != 2:
+            raise ValueError("the directions must be a [*, l] matrix")
+        l = int(m.shape[1])
+        return (x, rows, D, l, f64(center, (D,), "center"), None if scale is None else f64(scale, (D,), "scale"),
+                f64(m, (D if m_rows < 0 else m_rows, l), "the direction matrix"))
+
+    def pca_project(self, x: torch.Tensor, center, scale, V, norm2: bool = False):
+        """``osd_val_pca_project`` on the fp32 device tensor x [rows, D] (a column-slice view is read in place): with
+        u = ((double) x - center) * scale (``scale`` None: 1), returns ``(Z, norm2)`` DEVICE float64 tensors -- Z [rows, l] = u V
+        and norm2 [rows] = sum_c u^2 (None unless ``norm2=True``).  ``center``, ``scale`` [D] and ``V`` [D, l] are float64 (numpy
+        or tensors).  1 <= l <= 32, l <= D <= 32768.  Every sum is in double and in a fixed order: the same inputs give the same
+        bits.  A tensor without rows gives empty results."""
+        if x.dim() == 2 and int(x.shape[0]) == 0 and int(x.shape[1]) >= 1:
+            l = int(V.shape[1])
+            return (torch.empty((0, l), dtype=torch.float64, device=x.device),
+                    torch.empty(0, dtype=torch.float64, device=x.device) if norm2 else None)
+        x, rows, D, l, c, s, v = self._pca_args(x, center, scale, V, -1)
+        z = torch.empty((rows, l), dtype=torch.float64, device=x.device)
+        n2 = torch.empty(rows, dtype=torch.float64, device=x.device) if norm2 else None
+        L.check(L.lib().osd_val_pca_project(self._stream(), self.index, L.ptr(x), rows, max(int(x.stride(0)), D), D, L.ptr(c), L.ptr(s),
+                                            L.ptr(v), l, L.ptr(z), L.ptr(n2)))
+        return z, n2
+
+    def pca_backproject(self, x: torch.Tensor, center, scale, Z) -> torch.Tensor:
+        """``osd_val_pca_backproject`` on the fp32 device tensor x [rows, D] (a column-slice view is read in place): the DEVICE
+        float64 tensor W [D, l] = u^T Z with u as in ``pca_project`` and ``Z`` float64 [rows, l].  The same inputs give the same
+        bits; the results of row shards add up.  A tensor without rows gives zeros."""
+        if x.dim() == 2 and int(x.shape[0]) == 0 and int(x.shape[1]) >= 1:
+            return torch.zeros((int(x.shape[1]), int(Z.shape[1])), dtype=torch.float64, device=x.device)
+        x, rows, D, l, c, s, z = self._pca_args(x, center, scale, Z, int(x.shape[0]))
+        w = torch.empty((D, l), dtype=torch.float64, device=x.device)
+        L.check(L.lib().osd_val_pca_backproject(self._stream(), self.index, L.ptr(x), rows, max(int(x.stride(0)), D), D, L.ptr(c),
+                                                L.ptr(s), L.ptr(z), l, L.ptr(w)))
+        return w
 
     def concordance(self, time, event, risk):
         """``osd_val_concordance``: the exact pair counts ``(comparable, concordant, discordant, tied_risk)`` of
@@ -1268,9 +1327,18 @@ class BiologicalValidator:
         return self._agree(_ks_pvalues(r.shape[0], n2, dmax[:nf], dmin[:nf]))
 
     # -- utils/validation.py:225-271 --------------------------------------------------------------
-    def statistical_tests(self, real_data, synthetic_data) -> Dict[str, float]:
+    def statistical_tests(self, real_data, synthetic_data, pca: str = "host") -> Dict[str, float]:
         """The reference's figures: KS p-values over the first min(D, 100) columns, the MMD and the Wasserstein distance on 10
-        principal components.  The check of EVERY feature's marginal lives in ``marginal_fidelity``."""
+        principal components.  The check of EVERY feature's marginal lives in ``marginal_fidelity``.
+        ``pca="host"`` (the default) is the reference's own route to ``wasserstein_distance_mean``: both cohorts are downloaded and
+        sklearn's ``PCA(10)`` runs on a side thread.  ``pca="device"`` takes the figure from a ``pca.DevicePCA(10)`` fit on the real
+        cohort (block subspace iteration), fp32 scores of both cohorts and one ``DeviceKernels.marginals``
+        call: no cohort is downloaded for it, and the draws from numpy's GLOBAL generator that sklearn's randomized solver makes on
+        the host path are then NOT made (the device fit has its own ``RandomState(0)``), so code that relies on the state of that
+        generator after this call sees another state.  The two routes agree to the rounding of the fp32 scores where sklearn's
+        solver is exact, and to its own approximation error where it is randomized."""
+        if pca not in ("host", "device"):
+            raise ValueError('pca must be "host" or "device"')
         logger.info("Running statistical tests...")
         # The device parts first -- KS extremes (exact integers), then the MMD Gram blocks -- with the reference's own host-side parts
         # BESIDE the MMD on two threads (the ctypes call releases the GIL): the 100 Smirnov p-values (scipy's kstwo.sf: 8 ms each at
@@ -1284,7 +1352,8 @@ class BiologicalValidator:
         r, s = _dev(real_data, self.device), _dev(synthetic_data, self.device)
         nf = min(r.shape[1], 100)
         dmax, dmin, n2 = sharded_ks_extremes(self.comm, self.k, r, s, nf)
-        real_host, synth_host = _host(real_data), _host(synthetic_data)      # device -> host before the MMD kernels occupy the stream
+        if pca == "host":
+            real_host, synth_host = _host(real_data), _host(synthetic_data)      # device -> host before the MMD kernels occupy the stream
         box = {}
 
         def guarded(key, fn):
@@ -1299,7 +1368,7 @@ class BiologicalValidator:
             pca = PCA(n_components=10)
             return pca.fit_transform(real_host), pca.transform(synth_host)
 
-        threads = [guarded("ks", lambda: _ks_pvalues(r.shape[0], n2, dmax[:nf], dmin[:nf])), guarded("pca", fit)]
+        threads = [guarded("ks", lambda: _ks_pvalues(r.shape[0], n2, dmax[:nf], dmin[:nf]))] + ([guarded("pca", fit)] if pca == "host" else [])
         for th in threads:
             th.start()
         results = {}
@@ -1315,10 +1384,16 @@ class BiologicalValidator:
         logger.info(f"KS test mean p-value: {results['ks_test_mean_pvalue']:.3f}")
         logger.info(f"KS test fraction significant: {results['ks_test_fraction_significant']:.3f}")
         logger.info(f"MMD: {results['mmd']:.4f}")
-        real_pca, synth_pca = box["pca"]
-        if self.comm.on:
-            synth_pca = self.comm.gather_rows(torch.from_numpy(np.ascontiguousarray(synth_pca))).numpy()
-        results["wasserstein_distance_mean"] = float(np.mean([stats.wasserstein_distance(real_pca[:, i], synth_pca[:, i]) for i in range(10)]))
+        if pca == "device":
+            fitted = PC.DevicePCA(10).fit(r, kernels=self.k)
+            real_scores = fitted.transform(r, kernels=self.k)
+            synth_scores = self.comm.gather_rows(fitted.transform(s, kernels=self.k).contiguous())
+            results["wasserstein_distance_mean"] = float(np.mean(self.k.marginals(real_scores, synth_scores)["w1"]))
+        else:
+            real_pca, synth_pca = box["pca"]
+            if self.comm.on:
+                synth_pca = self.comm.gather_rows(torch.from_numpy(np.ascontiguousarray(synth_pca))).numpy()
+            results["wasserstein_distance_mean"] = float(np.mean([stats.wasserstein_distance(real_pca[:, i], synth_pca[:, i]) for i in range(10)]))
         logger.info(f"Mean Wasserstein distance: {results['wasserstein_distance_mean']:.3f}")
         return self._agree(results)
 
@@ -1756,6 +1831,37 @@ class BiologicalValidator:
         summary = self._agree(subtype_summary(rows))
         return (summary, rows) if return_rows else summary
 
+    # -- low-dimensional structure: principal components by subspace iteration (no counterpart in the reference)
+    def embedding_fidelity(self, real, synthetic, n_components: int = 10, standardize: bool = False, quantile: float = 0.99,
+                           return_rows: bool = False, **pca_options):
+        """Does ``synthetic`` live on ``real``'s low-dimensional structure?  A ``pca.DevicePCA`` (``n_components`` directions,
+        ``standardize`` and ``pca_options`` -- oversample, max_iter, tol, seed -- as its constructor takes them) is fitted on each
+        cohort, both cohorts are projected onto the REAL components about the real mean, and ``pca.embedding_summary`` reports the
+        ``pca_*`` keys: per-axis variance ratios (a flattened axis is below 1), the mean shift, the Wasserstein-1 and KS distances
+        of the scores (``pca_wasserstein_distance_mean`` is the reference's figure), the residual ratio and the share of synthetic
+        rows farther from the real subspace than the ``quantile``-quantile of the real rows (variance spread off the manifold), and
+        the cosines of the principal angles between the two fitted subspaces (a rotated leading subspace).  ``return_rows=True``
+        also returns the fp32 scores of both cohorts (device tensors), the float64 residuals and both component matrices.  On a
+        ``sharded=True`` validator ``synthetic`` is this rank's row shard and the real cohort is replicated: the synthetic fit goes
+        through the communicator, scores and residuals are gathered before the marginals and the quantile count."""
+        x, y = _dev(real, self.device), _dev(synthetic, self.device)
+        for label, t in (("real", x), ("synthetic", y)):
+            if t.dim() != 2 or t.shape[1] != x.shape[1] or t.shape[1] < 1:
+                raise ValueError(f"{label} must be [rows, {x.shape[1]}]: the cohorts must have the same features")
+            if not bool(torch.isfinite(t).all().item()):
+                raise ValueError(f"{label} holds non-finite values")
+        if x.shape[0] < 2 or int(self.comm.sum(int(y.shape[0]))[0]) < 2:
+            raise ValueError("both cohorts need at least 2 rows")
+        if not 0.0 <= float(quantile) <= 1.0:
+            raise ValueError("quantile must lie in [0, 1]")
+        rows = PC.embedding_rows(self.comm, self.k, x, y, int(n_components), bool(standardize), **pca_options)
+        summary = self._agree(PC.embedding_summary(rows, float(quantile)))
+        if not return_rows:
+            return summary
+        return summary, {"real_scores": rows["real_scores"], "synth_scores": rows["synth_scores"], "real_resid2": rows["real_resid2"],
+                         "synth_resid2": rows["synth_resid2"], "real_components": rows["real"].components_,
+                         "synth_components": rows["synth"].components_, "real_pca": rows["real"], "synth_pca": rows["synth"]}
+
     # -- privacy: membership inference on the per-record likelihood bound (DESIGN.md section 3.18) ---------------------
     def membership_audit(self, model, train, holdout, *, num_timesteps: int = 32, seed: int = 0) -> Dict[str, float]:
         """The loss-threshold membership-inference attack on a diffusion model: ``train`` and ``holdout`` are (data, conditions)
@@ -1892,8 +1998,11 @@ class BiologicalValidator:
                      subtype_conditions=None, survival=None, marginals: bool = False, differential=None,
                      differential_names=None, enrichment=None, enrichment_names=None,
                      enrichment_permutations: int = 1000, consistency: bool = False,
-                     consistency_method: str = "mean", prognostic=None) -> Dict[str, float]:
-        """``prognostic=(real_surv, synth_surv)`` adds ``prognostic_fidelity``'s ``prog_*`` keys on the combined matrices (blocks
+                     consistency_method: str = "mean", prognostic=None, embedding: bool = False,
+                     embedding_components: int = 10) -> Dict[str, float]:
+        """``embedding=True`` adds ``embedding_fidelity``'s ``pca_*`` keys on the combined matrices (``embedding_components``
+        directions); with the default nothing changes.
+        ``prognostic=(real_surv, synth_surv)`` adds ``prognostic_fidelity``'s ``prog_*`` keys on the combined matrices (blocks
         ``mutations`` / ``expression`` / ``pathways``; each ``*_surv`` is [rows, 2] = (time, event)); with the default None nothing
         changes.
         ``consistency=True`` adds ``pathway_consistency``'s ``pwc_*`` keys (the real cohort's ``pwc_real_*`` among them): the
@@ -2014,6 +2123,8 @@ class BiologicalValidator:
                 raise ValueError("validate_all(prognostic=...) needs (real_surv, synth_surv)")
             widths = {"mutations": parts_r[0].shape[1], "expression": parts_r[1].shape[1], "pathways": parts_r[2].shape[1]}
             all_results.update(self.prognostic_fidelity(real_combined, prognostic[0], synth_combined, prognostic[1], blocks=widths))
+        if embedding:
+            all_results.update(self.embedding_fidelity(real_combined, synth_combined, n_components=int(embedding_components)))
         logger.info("=" * 50)
         logger.info("VALIDATION SUMMARY")
         logger.info("=" * 50)
