@@ -124,7 +124,7 @@ int osd_set_stream(osd_handle *h, void *hip_stream);
  * "cond_bwd_fused"         -- 0 | 1 (1) -- 1: the conditioning branch's backward below h0 (time-table scatter, two 64-wide dgrads,
  *                             SiLU backward, the first embedding Linear's weight gradient) as one launch, k_cond_bwd in
  *                             csrc/k_train.hip, for hidden_dims[0] <= 256 and a multiple of 32; 0: five launches.
- * "bound_rows"             -- 1..2^30 (32 768) -- rows per launch group of osd_bound_sweep / osd_row_sq_error: caps their workspace.
+ * "bound_rows"             -- 1..2^30 (32 768) -- rows per launch group of osd_bound_sweep / osd_row_sq_error / osd_noise_map: caps their workspace.
  *
  * Any other name: OSD_EINVAL. */
 int osd_set_option(osd_handle *h, const char *name, int64_t value);
@@ -1038,6 +1038,39 @@ int osd_row_sq_error(osd_handle *h, const float *x0, const float *cond, int64_t 
  * "bound_rows" rows go into one launch group, so the workspace is bounded for any n x S; a group may end inside a timestep. */
 int osd_bound_sweep(osd_handle *h, const float *x0, const float *cond, int64_t n, const int32_t *timesteps_host, int S,
                     const float *noise_in, uint64_t seed, int64_t row_offset, float *se_out);
+
+/* ---- the edit-friendly noise map of a patient -----------------------------------------------------
+ * Turns n patients into a start state and the draws with which osd_sample_chain_steps (and the guided, known and clipped chains), run on
+ * the SAME plan and condition, returns them: the DDPM noise space of Huberman-Spiegelglas et al. 2024.  timesteps_host [n_steps] and
+ * step_coef_host [n_steps][4] = (A_s, B_s, C_s, 0) are exactly that plan; nothing is folded here, so the map inverts the very rows the
+ * chain runs, for every prediction type (the plan's (A, B) carry it).  With a[t], b[t] the buffers of osd_set_schedule and eps_s an
+ * independent normal per (patient, level):
+ *   y_s   = a[tau_s] * x0 + b[tau_s] * eps_s                       s = 0 .. n_steps-1
+ *   out_s = denoiser(y_s, tau_s, cond)                             eval mode, fp32 kernels
+ *   z_s   = (y_{s-1} - (A_s * y_s + B_s * out_s)) / C_s            s = 1 .. n_steps-1
+ *   x_start_out = y_{n_steps-1};   noises_out[n_steps-1-s] = z_s   (the chain's draw order)
+ * z_s is formed as fmaf(-B, out, fmaf(-A, y_s, y_{s-1})) * (1 / C): the chain's step fmaf(A, y, fmaf(B, out, C z)) taken back outermost
+ * operation first, so the chain returns y_{s-1} to rounding.  Level 0 draws nothing (C_0 = 0 stays a requirement) and does not run: the
+ * chain's last step returns A_0 y_0 + B_0 out_0, the model's x0^ at tau_0.
+ * eps_s is noise_in [n_steps][n][D], or for NULL the Philox block (seed, row_offset + i, c >> 2, tau_s, q_sample's tag) of
+ * osd_bound_sweep: a draw depends on (seed, global patient id, timestep) alone.
+ * The call is the loss-only training call of osd_bound_sweep with another q_sample pass and another output_proj epilogue (EpiNoiseMap,
+ * csrc/epilogues.h): rows are (level, patient) pairs of the levels 1 .. n_steps-1 in that order, x0 and cond are gathered, at most
+ * "bound_rows" rows go into one launch group and a group may end inside a level; y_{s-1} is recomputed from x0 in the row that needs it,
+ * so groups are independent.  z is written straight into noises_out; neither the network output nor a posterior mean reaches memory.  No
+ * atomics: two calls return equal bits, and a row's result does not depend on its group, chunk or shard.  Asynchronous on the handle's
+ * stream.  Ignores osd_set_loss, osd_set_constraints and osd_set_loss_mask and leaves them as they were.
+ * OSD_EINVAL, all checked on the host before any device call: a null tensor, n < 1, n_steps outside [1, T], timesteps not strictly
+ * increasing or outside [0, T), a non-finite coefficient, C_0 != 0, C_s <= 0 for some s >= 1 (the map needs eta > 0), row_offset + n
+ * outside the 32-bit id space.  OSD_ESTATE: osd_train_batch_source / osd_train_condition_dropout is armed (it stays armed).
+ * OSD_EUNSUPPORTED: "precision" 1, or an output link (a linked model's step is not the plain affine row: refused, not approximated).
+ *   x0, cond      dev [n][D], [n][condition_dim]
+ *   noise_in      dev [n_steps][n][D], or NULL
+ *   x_start_out   dev [n][D]
+ *   noises_out    dev [n_steps-1][n][D] (may be NULL when n_steps == 1) */
+int osd_noise_map(osd_handle *h, const float *x0, const float *cond, int64_t n, const int32_t *timesteps_host,
+                  const float *step_coef_host, int32_t n_steps, const float *noise_in, uint64_t seed, int64_t row_offset,
+                  float *x_start_out, float *noises_out);
 /* Stand-alone ops (stream/device based, synchronous): loss_out (dev float[1]) += weight * L and, when
  * dx != NULL, dx (dev [rows][ld]) += weight * dL/dx.  x, x_recon, x_true: dev [rows][ld], cols <= ld. */
 int osd_loss_pathway_coherence(void *stream, int device, const float *x, int64_t rows, int ld, int cols,

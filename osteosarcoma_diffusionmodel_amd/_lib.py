@@ -162,6 +162,7 @@ _SIGNATURES = {
                                            C.c_double, C.c_double, C.c_uint64, C.c_int64, C.c_double]),
     "osd_row_sq_error": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_uint64, C.c_int64, _P]),
     "osd_bound_sweep": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int, _P, C.c_uint64, C.c_int64, _P]),
+    "osd_noise_map": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int32, _P, C.c_uint64, C.c_int64, _P, _P]),
     "osd_loss_pathway_coherence": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                              C.c_double, _P, _P]),
     "osd_loss_mutation_expression": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,

@@ -1113,6 +1113,89 @@ struct EpiRowSq {
   }
 };
 
+// ---- output_proj fused with the noise map's solve (osd_noise_map) ----
+// Row p of the launch is a (level s, patient i) pair with s > 0.  The chain's step at that level is x' = fmaf(A, y, fmaf(B, out, C z))
+// (EpiPosterior<POST_PLAIN>); the map wants the z that makes x' the state y_{s-1}, and takes the step's operations back outermost first:
+//   u = fmaf(-A, y_s, y_{s-1})        formed by k_q_sample_map, streamed in where the loss epilogues stream the target
+//   z = fmaf(-B, acc + bias, u) / C   here; 1 / C is a correctly rounded per-row reciprocal (k_q_sample_map), the divide a product
+// z goes straight to noises_out at the row's own offset (row[p].zoff: level-major in the chain's draw order, so rows of one launch are
+// not one stride apart) in place of dL/dout; neither the network output nor a posterior mean is written.  EpiMse's operand paths, path
+// for path: the transposer on full row segments when FAST, the guarded form elsewhere.  No atomics, no reduction: a row's z depends on
+// the row alone.
+struct MapRow { float B, invC; long long zoff; };      // 16 bytes
+struct EpiNoiseMap {
+  static constexpr bool COUNTED_STORES = false;   // rows beyond P store nothing
+  static constexpr bool XBUF = true;              // u comes in, z goes out, as full row segments
+  template <class A> static __device__ __forceinline__ void slice(A&, int) {}
+  struct Args {
+    const float* bias; const float* target; int ldn;
+    const MapRow* row;            // dev [P]
+    float* z;                     // noises_out
+  };
+  static bool fast_ok(const Args& a, int F) { return F % 4 == 0 && al16(a.bias) && al16(a.target) && a.ldn % 4 == 0 && al16(a.z); }
+  template <int NFB> using Pre = EpiMse::Pre<NFB>;
+  template <int NFB, bool FAST>
+  static __device__ __forceinline__ Pre<NFB> prefetch(const Args& a, int fw, int lane, int F) {
+    Pre<NFB> r;
+    const int h = lane >> 5;
+#pragma unroll
+    for (int fb = 0; fb < NFB; ++fb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r.bias[fb][q] = ldq<FAST>(a.bias, fw + 32 * fb + 8 * q + 4 * h, F);
+    return r;
+  }
+  // explicit operations: both operand paths and both tiles form the same bits whatever the compiler would contract
+  static __device__ __forceinline__ float4 solve(const float4& e, const float4& u, float nB, float iC) {
+    return make_float4(__fmul_rn(fmaf(nB, e.x, u.x), iC), __fmul_rn(fmaf(nB, e.y, u.y), iC), __fmul_rn(fmaf(nB, e.z, u.z), iC),
+                       __fmul_rn(fmaf(nB, e.w, u.w), iC));
+  }
+  template <int NFB, int NPB, bool FAST>
+  static __device__ __forceinline__ void apply(f32x16 (&acc)[NFB][NPB], const Args& a, const Pre<NFB>& pre, int fw, int pw, int lane, int F, int P,
+                                               float* xbuf = nullptr) {
+    const int l31 = lane & 31, h = lane >> 5;
+    if (fw >= F || pw >= P) return;                    // uniform over the wave
+    float nB[NPB], iC[NPB];
+    long long zo[NPB];
+#pragma unroll
+    for (int pb = 0; pb < NPB; ++pb) {
+      const int p = pw + 32 * pb + l31;
+      const MapRow r = a.row[p < P ? p : P - 1];
+      nB[pb] = -r.B; iC[pb] = r.invC; zo[pb] = r.zoff;
+    }
+    if (FAST && xbuf) {
+      const WaveXpose<NPB> xp{xbuf};
+      const int rows = P - pw;                         // valid rows of the wave's block (uniform)
+      const MapRow* const wrow = a.row + pw;
+#pragma unroll
+      for (int fb = 0; fb < NFB; ++fb) {
+        const int cols = F - (fw + 32 * fb);            // valid features of this block (uniform)
+        if (cols <= 0) continue;
+        xp.template load_rows<true>(a.target + (size_t)pw * a.ldn + fw + 32 * fb, a.ldn, lane, rows, cols);
+#pragma unroll
+        for (int pb = 0; pb < NPB; ++pb)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float4 bv = pre.bias[fb][q];
+            const float4 u = xp.get(pb, q, l31, h);
+            const float4 e = make_float4(acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w);
+            xp.put(pb, q, l31, h, solve(e, u, nB[pb], iC[pb]));
+          }
+        xp.store_rows_at(a.z + fw + 32 * fb, [wrow](int k) { return wrow[k].zoff; }, lane, rows < 32 * NPB ? rows : 32 * NPB, cols);
+      }
+      return;
+    }
+    OSD_FOR_QUADS(fb, pb, q) {
+      const int f = fw + 32 * fb + 8 * q + 4 * h;
+      const int p = pw + 32 * pb + l31;
+      const int pc = p < P ? p : P - 1;
+      const float4 bv = pre.bias[fb][q];
+      const float4 u = ldq<FAST>(a.target + (size_t)pc * a.ldn, f, F);
+      const float4 e = make_float4(acc[fb][pb][4 * q] + bv.x, acc[fb][pb][4 * q + 1] + bv.y, acc[fb][pb][4 * q + 2] + bv.z, acc[fb][pb][4 * q + 3] + bv.w);
+      if (p < P) stq<FAST>(a.z + zo[pb], f, F, solve(e, u, nB[pb], iC[pb]));
+    }
+  }
+};
+
 // ---- what the four Gram-distance epilogues below share ---------------------------------------------------------------------
 // A = the tile's feature side (rows f), B = its patient side (rows p); acc = a_f . b_p.  The squared norms of the A rows ride in
 // registers from before the K loop, the layout of the accumulator quads: sq[fb][q] holds rows fw + 32 fb + 8 q + 4 h .. + 3.

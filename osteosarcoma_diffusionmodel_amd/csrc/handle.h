@@ -242,9 +242,11 @@ struct osd_handle {
   osd::DevBuf<float> dp_norms; int64_t dp_rows = -1;
   void* dp_plan = nullptr;
   bool dp_replay_ok = false;         // osd_dp_replay: the lists still describe the workspace (cleared by whatever carves it again: ensure_train_ws)
-  // the likelihood bound (osd_row_sq_error / osd_bound_sweep): rows per launch group of the sweep, and the sweep's timesteps on the device
+  // the likelihood bound (osd_row_sq_error / osd_bound_sweep) and the noise map: rows per launch group, and the call's timesteps on the device
   int64_t bound_rows = 32768;        // osd_set_option("bound_rows")
   osd::DevBuf<int> bound_ts;
+  // the noise map (osd_noise_map): the call's step_coef rows on the device, next to its timesteps in bound_ts
+  osd::DevBuf<float> map_coef;
   std::vector<void*> wg_plans;       // grouped weight-gradient launches (wgrad_group.hip): one cached work list per flush point
   // persistent reverse-chain kernel (chain.h / chain.hip)
   int sampler = 0;                   // osd_set_option("sampler"): 0 auto, 1 chain kernel whenever the architecture allows, 2 per-layer kernels

@@ -342,6 +342,86 @@ hipError_t launch_q_sample_pairs(hipStream_t s, const float* x0, const float* co
   return hipGetLastError();
 }
 
+// q_sample for the noise map: k_q_sample_pairs' rows, gather and draw address -- the normals of patient i at
+// level s are the block (seed, row_offset + i, quad, tau_s, TAG_QNOISE) -- with two levels per row.  Row (s, i) forms y_s, the network's
+// input, and, for s > 0, y_{s-1} from that level's OWN draw: recomputed from x0, never fetched from another row, so a launch group needs
+// nothing of its neighbours.  What EpiNoiseMap streams in place of a training target is u = y_{s-1} - A_s y_s (one fma: the outermost
+// operation of the chain's step fmaf(A, y, fmaf(B, out, C z)) taken back first); its per-row record (B_s, 1 / C_s, the offset of
+// noises_out [n_steps-1-s][i]) rides along.  Rows of the last level also write y_s to x_start.  Each product-sum is k_q_sample's.
+__global__ __launch_bounds__(256) void k_q_sample_map(const float* x0, const float* cond, int cd, MapRows mr, const float* sqrt_ac, const float* sqrt_1m,
+                                                      const float* noise_in, int64_t rows, int cols, uint64_t seed, uint32_t row_offset, float* x_t,
+                                                      int ldxt, float* target_out, MapRow* row_out, float* x_start, int* t_out, float* cond_out,
+                                                      ZeroList zl) {
+  zero_list(zl);
+  const int c4n = (cols + 3) >> 2;
+  for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+    const int64_t pair = mr.pair0 + r;
+    const int64_t i = pair % mr.n_pat;
+    const int s = mr.s0 + (int)(pair / mr.n_pat);
+    const int tt = mr.t_list[s];
+    const int tp = mr.t_list[s > 0 ? s - 1 : 0];
+    const float a = sqrt_ac[tt], b = sqrt_1m[tt], ap = sqrt_ac[tp], bp = sqrt_1m[tp];
+    const float cA = mr.coef[4 * s];
+    const bool solve = s > 0 && target_out;          // uniform over the workgroup
+    const bool last = s == mr.n_steps - 1 && x_start;
+    if (threadIdx.x == 0) {
+      if (t_out) t_out[r] = tt;
+      if (solve) {
+        MapRow rec;
+        rec.B = mr.coef[4 * s + 1]; rec.invC = 1.0f / mr.coef[4 * s + 2];
+        rec.zoff = ((long long)(mr.n_steps - 1 - s) * mr.n_pat + i) * cols;
+        row_out[r] = rec;
+      }
+    }
+    if (cond_out && (int)threadIdx.x < cd) cond_out[r * cd + threadIdx.x] = cond[i * cd + threadIdx.x];
+    const float* xrow = x0 + i * cols;
+    const float* nrow = noise_in ? noise_in + ((int64_t)s * mr.n_pat + i) * cols : nullptr;
+    const float* prow = noise_in && s > 0 ? noise_in + ((int64_t)(s - 1) * mr.n_pat + i) * cols : nullptr;
+    for (int q = threadIdx.x; q < c4n; q += 256) {
+      const int c = 4 * q;
+      const float4 x = ld4g(xrow, c, cols);
+      float4 n;
+      if (nrow) n = ld4g(nrow, c, cols);
+      else n = randn4(seed, row_offset + (uint32_t)i, (uint32_t)q, (uint32_t)tt, TAG_QNOISE);
+      float4 y;
+      y.x = __fadd_rn(__fmul_rn(a, x.x), __fmul_rn(b, n.x));
+      y.y = __fadd_rn(__fmul_rn(a, x.y), __fmul_rn(b, n.y));
+      y.z = __fadd_rn(__fmul_rn(a, x.z), __fmul_rn(b, n.z));
+      y.w = __fadd_rn(__fmul_rn(a, x.w), __fmul_rn(b, n.w));
+      if (x_t) {
+        st4g(x_t + r * ldxt, c, cols, y);
+        zero_pad(x_t + r * ldxt, cols, ldxt, c);
+      }
+      if (last) st4g(x_start + i * cols, c, cols, y);
+      if (!solve) continue;
+      float4 m;
+      if (prow) m = ld4g(prow, c, cols);
+      else m = randn4(seed, row_offset + (uint32_t)i, (uint32_t)q, (uint32_t)tp, TAG_QNOISE);
+      float4 u;
+      u.x = fmaf(-cA, y.x, __fadd_rn(__fmul_rn(ap, x.x), __fmul_rn(bp, m.x)));
+      u.y = fmaf(-cA, y.y, __fadd_rn(__fmul_rn(ap, x.y), __fmul_rn(bp, m.y)));
+      u.z = fmaf(-cA, y.z, __fadd_rn(__fmul_rn(ap, x.z), __fmul_rn(bp, m.z)));
+      u.w = fmaf(-cA, y.w, __fadd_rn(__fmul_rn(ap, x.w), __fmul_rn(bp, m.w)));
+      st4g(target_out + r * cols, c, cols, u);
+    }
+  }
+}
+hipError_t launch_q_sample_map(hipStream_t s, const float* x0, const float* cond, int cd, const MapRows& mr, const float* sqrt_ac,
+                               const float* sqrt_1m, const float* noise_in, int64_t rows, int cols, uint64_t seed, uint32_t row_offset, float* x_t,
+                               int ldxt, float* target_out, MapRow* row_out, float* x_start, int* t_out, float* cond_out, const ZeroList* zl) {
+  if (rows <= 0) return hipSuccess;
+  if (mr.n_pat < 1 || !mr.t_list || !mr.coef || mr.s0 < 0 || cd > 256) return hipErrorInvalidValue;
+  if (mr.pair0 < 0 || mr.pair0 + rows > (int64_t)(mr.n_steps - mr.s0) * mr.n_pat) return hipErrorInvalidValue;      // every row names a level of the plan
+  if ((target_out != nullptr) != (row_out != nullptr) || (x_t && !t_out)) return hipErrorInvalidValue;
+  ZeroList z{};
+  if (zl) z = *zl;
+  int64_t blocks = rows < 16384 ? rows : 16384;
+  if (blocks < (zl ? 32 : 1)) blocks = zl ? 32 : 1;      // the zero list is walked by the first 32 workgroups
+  hipLaunchKernelGGL(k_q_sample_map, dim3((unsigned)blocks), 256, 0, s, x0, cond, cd, mr, sqrt_ac, sqrt_1m, noise_in, rows, cols, seed, row_offset,
+                     x_t, ldxt > 0 ? ldxt : cols, target_out, row_out, x_start, t_out, cond_out, z);
+  return hipGetLastError();
+}
+
 // Classifier-free guidance (utils/generate.py:97-110, guidance_scale) on the last hidden activation: output_proj is linear, so
 // eps_u + w (eps_c - eps_u) = output_proj(h_u + w (h_c - h_u)) and the combination costs a pass over [m][256], not over [m][D].
 // h: [2 m][cols], rows [0, m) the conditional branch, rows [m, 2 m) the unconditional one; row r < m is overwritten with

@@ -257,5 +257,11 @@ hipError_t launch_row_sq(hipStream_t s, const GemmArgs& g, const EpiRowSq::Args&
   hipLaunchKernelGGL(k_rowsq_reduce, dim3((g.P + 255) / 256), 256, 0, s, a.part, a.ld, rowsq_slots(g.F), g.P, poison, se);
   return hipGetLastError();
 }
+// output_proj + the noise map's solve: launch_mse's tile choice, nothing behind it
+hipError_t launch_noise_map(hipStream_t s, const GemmArgs& g, const EpiNoiseMap::Args& a) {
+  if (g.F <= 0 || g.P <= 0) return hipSuccess;
+  if (!a.row || !a.z || !a.target) return hipErrorInvalidValue;
+  return use_big_tile(g.F, g.P) ? launch_gemm<TileBig, true, true, EpiNoiseMap>(s, g, a) : launch_gemm<TileSmall, true, true, EpiNoiseMap>(s, g, a);
+}
 
 }  // namespace osd

@@ -46,6 +46,8 @@ hipError_t launch_loss_link(hipStream_t s, const GemmArgs& g, const EpiLossT<tru
 constexpr int ROWSQ_WF = 64;      // feature extent of a wave in both tiles of the tile choice
 inline int rowsq_slots(int F) { return (F + ROWSQ_WF - 1) / ROWSQ_WF; }
 hipError_t launch_row_sq(hipStream_t s, const GemmArgs& g, const EpiRowSq::Args& a, const float* poison, float* se);
+// output_proj + the noise map's solve (EpiNoiseMap), launch_mse's tile choice: row p's z lands at a.z + a.row[p].zoff.  fp32 only.
+hipError_t launch_noise_map(hipStream_t s, const GemmArgs& g, const EpiNoiseMap::Args& a);
 
 // k_gn.hip / k_gn_drop.hip ------------------------------------------------------------
 // Arguments common to every GW; the wrappers copy them into EpiGnSilu<GW,DROP>::Args.
@@ -85,6 +87,15 @@ struct PairRows { int64_t pair0, n_pat; const int* t_row; const int* t_list; };
 hipError_t launch_q_sample_pairs(hipStream_t s, const float* x0, const float* cond, int cd, const PairRows& pr, const float* sqrt_ac,
                                  const float* sqrt_1m, const float* noise_in, int64_t rows, int cols, uint64_t seed, uint32_t row_offset, float* x_t,
                                  int ldxt, float* target_out, int* t_out, float* cond_out, const ZeroList* zl, int kind);
+// q_sample of the noise map's (level, patient) pairs (k_elem.hip: k_q_sample_map).  Row r of the launch is pair
+// pair0 + r of a [n_steps - s0][n_pat] grid: patient i = pair % n_pat, level s = s0 + pair / n_pat of the plan t_list / coef [n_steps][4].
+// noise_in, if given, is the CALL's [n_steps][n_pat][cols] (not the launch's first row: a row reads two levels of it).  The row's
+// y_s goes to x_t (null: not written), y_{s-1} - A_s y_s to target_out and (B_s, 1 / C_s, where z_s goes) to row_out -- both only for
+// s > 0 --, and y_{n_steps-1} of patient i to x_start + i * cols.
+struct MapRows { int64_t pair0, n_pat; const int* t_list; const float* coef; int n_steps, s0; };
+hipError_t launch_q_sample_map(hipStream_t s, const float* x0, const float* cond, int cd, const MapRows& mr, const float* sqrt_ac,
+                               const float* sqrt_1m, const float* noise_in, int64_t rows, int cols, uint64_t seed, uint32_t row_offset, float* x_t,
+                               int ldxt, float* target_out, MapRow* row_out, float* x_start, int* t_out, float* cond_out, const ZeroList* zl);
 // classifier-free guidance on the last hidden activation: h[r] = h[m + r] + w * (h[r] - h[m + r]) for r < m, in place (h: [2 m][cols])
 hipError_t launch_guide_combine(hipStream_t s, float* h, int64_t m, int cols, float w);
 // condition dropout of a caller-supplied batch: out[r] = row r keeps its condition (rng.h: cond_kept) ? cond[r] : null_cond

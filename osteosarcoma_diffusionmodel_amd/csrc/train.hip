@@ -635,12 +635,15 @@ struct LossStep {
   // the likelihood bound's row mode (osd_row_sq_error / osd_bound_sweep): the rows are (timestep, patient) pairs gathered by q_sample,
   // loss() takes the per-row epilogue and writes se_out [n]; loss_out is then the squads' poison word, not a loss
   const PairRows* pairs = nullptr; float* se_out = nullptr;
+  // the noise map (osd_noise_map): the rows are (level, patient) pairs of a step plan, `noise` is the CALL's [n_steps][n_pat][D], loss()
+  // takes EpiNoiseMap and writes z_out (the call's noises_out); the rows' records live where dL/dout would (w.d_out: never written without grads)
+  const MapRows* map = nullptr; float* z_out = nullptr; float* x_start = nullptr;
   TrainWs w;
 
   // everything that is accumulated atomically must start at zero: zeroed by the q_sample kernel's own grid
   int zero_list(ZeroList* zl) {
     zero_add(zl, loss_out, 1);
-    if (w.sq_bar && train_squad_ok(h, n)) {      // the squads' barrier counters + status words (forward, backward)
+    if (w.sq_bar && train_squad_ok(h, n) && !map) {      // the squads' barrier counters + status words (forward, backward)
       zero_add(zl, reinterpret_cast<float*>(w.sq_bar), w.sq_panels * 16 + 16);
       zero_add(zl, reinterpret_cast<float*>(w.sq_bar2), w.sq_panels * 16 + 16);
     }
@@ -657,6 +660,13 @@ struct LossStep {
     int* t_draw = nullptr;
     if (!tc.t_idx) { t_draw = w.t_idx; tc.t_idx = w.t_idx; }
     const int* t_idx = tc.t_idx;
+    if (map) {      // ahead of everything that follows the prediction type or the mask: the plan's (A, B) carry the type, the map ignores the mask
+      OSD_HIP(launch_q_sample_map(s, x0, cond, a.cond_dim, *map, h->d_sqrt_ac, h->d_sqrt_1m, noise, n, D, seed, roff, w.x_t, w.xld, w.noise,
+                                  reinterpret_cast<MapRow*>(w.d_out), x_start, w.t_idx, w.cond_mix, &zl));
+      cond = w.cond_mix;
+      tc.t_idx = w.t_idx;
+      return OSD_OK;
+    }
     // a non-eps target (osd_set_prediction) is formed by the same pass and lands in w.noise, injected noise or not
     if (h->pred_type != OSD_PRED_EPSILON) h->last_train_path |= OSD_TP_TARGET;
     // osd_set_loss_mask: NaN in x0 = not observed; the target always lands in w.noise, NaN-marked (the row mode was refused before)
@@ -709,10 +719,12 @@ struct LossStep {
     OSD_TRY(noised_batch(zl));
     OSD_TRY(cond_embed_fwd(h, s, cond, n, w));
     TrunkIn in{};
-    in.x = w.x_t; in.ldx = w.xld; in.kx = unpacked ? w.xld : D; in.a_unpacked = unpacked; in.ksplit = true;
+    in.x = w.x_t; in.ldx = w.xld; in.kx = unpacked ? w.xld : D; in.a_unpacked = unpacked; in.ksplit = !map;
     in.n = n; in.t_index = tc.t_idx; in.train = tc.train_mode(); in.save = grads != nullptr;
     in.masks = masks; in.seed = seed; in.row_offset = roff; in.drop_step = 0; in.path = &h->last_train_path;
-    if (!(w.sq_act && train_squad_ok(h, n))) return run_trunk(h, s, w.f, in);
+    // the noise map promises a row the same bits in every launch group: neither the two-wave-group K split nor the squads, whose use
+    // (and summation order) follows the row count -- the layers of the per-layer sampler at input_splitk 0
+    if (map || !(w.sq_act && train_squad_ok(h, n))) return run_trunk(h, s, w.f, in);
     h->last_train_path |= OSD_TP_SQUAD_FWD;
     in.input_only = true;
     OSD_TRY(run_trunk(h, s, w.f, in));
@@ -724,6 +736,13 @@ struct LossStep {
     const int D = a.D;
     const double count = (double)n * (double)D;
     GemmArgs g = output_proj_args(h, w.f, n);
+    if (map) {
+      EpiNoiseMap::Args em{};
+      em.bias = h->params[a.pm.out_b]; em.target = w.noise; em.ldn = D;
+      em.row = reinterpret_cast<const MapRow*>(w.d_out); em.z = z_out;
+      OSD_HIP(launch_noise_map(s, g, em));
+      return OSD_OK;
+    }
     if (se_out) {
       // the slot partials take the place of dL/d eps_hat, which a call without gradients never writes: ceil(D / 64) x n <= n x D floats
       EpiRowSq::Args er{};
@@ -797,7 +816,7 @@ struct LossStep {
   int run(const int32_t* t_index) {
     use_pw = h->cons.n_pathways > 0 && h->w_pathway != 0.0;
     use_me = h->cons.n_a > 0 && h->w_mutexpr != 0.0;
-    cp = (use_pw || use_me) && !se_out ? &h->cons : nullptr;      // the row mode scores the raw output alone
+    cp = (use_pw || use_me) && !se_out && !map ? &h->cons : nullptr;      // the row mode and the noise map read the raw output alone
     if (cp && n < 2) { set_error("the constraint losses need at least 2 rows"); return OSD_EINVAL; }
     OSD_TRY(h->parts_dev.reserve(16));
     OSD_TRY(ensure_train_ws(h, s, n, cp, &w));
@@ -974,6 +993,68 @@ int osd_bound_sweep(osd_handle* h, const float* x0, const float* cond, int64_t n
     const int64_t rows = std::min(cap, total - p0);
     const PairRows pr{p0, n, nullptr, h->bound_ts};
     OSD_TRY(bound_group(h, s, x0, cond, rows, pr, nullptr, noise_in ? noise_in + p0 * D : nullptr, seed, (uint32_t)row_offset, se_out + p0));
+  }
+  return OSD_OK;
+}
+
+// checks in order, all on the host: null handle / tensors, rows, the plan, row offset, armed one-shots, precision, output link, ready
+int osd_noise_map(osd_handle* h, const float* x0, const float* cond, int64_t n, const int32_t* timesteps_host, const float* step_coef_host,
+                  int32_t n_steps, const float* noise_in, uint64_t seed, int64_t row_offset, float* x_start_out, float* noises_out) {
+  if (!h) { set_error("null handle"); return OSD_EINVAL; }
+  if (!x0 || !cond || !timesteps_host || !step_coef_host || !x_start_out || (n_steps > 1 && !noises_out)) { set_error("null tensor"); return OSD_EINVAL; }
+  if (n < 1) { set_error("need at least one row, got %lld", (long long)n); return OSD_EINVAL; }
+  OSD_TRY(check_rows(n));
+  const int T = h->arch.T, S = n_steps;
+  if (S < 1 || S > T) { set_error("n_steps=%d outside [1,%d]", S, T); return OSD_EINVAL; }
+  for (int s = 0; s < S; ++s) {
+    if (timesteps_host[s] < 0 || timesteps_host[s] >= T) { set_error("timesteps[%d]=%d outside [0,%d)", s, (int)timesteps_host[s], T); return OSD_EINVAL; }
+    if (s > 0 && timesteps_host[s] <= timesteps_host[s - 1]) { set_error("timesteps[%d]=%d does not exceed timesteps[%d]=%d: the plan must strictly increase", s, (int)timesteps_host[s], s - 1, (int)timesteps_host[s - 1]); return OSD_EINVAL; }
+    for (int k = 0; k < 4; ++k)
+      if (!std::isfinite(step_coef_host[4 * s + k])) { set_error("step_coef[%d] is not finite", 4 * s + k); return OSD_EINVAL; }
+    const float c = step_coef_host[4 * s + 2];
+    if (s == 0 && c != 0.f) { set_error("step_coef[2] = C_0 = %g: the last step draws no z, so C_0 must be 0", (double)c); return OSD_EINVAL; }
+    if (s > 0 && !(c > 0.f)) { set_error("step_coef[%d] = C_%d = %g: the noise map solves every step for its draw and needs C_s > 0 (eta > 0)", 4 * s + 2, s, (double)c); return OSD_EINVAL; }
+  }
+  OSD_TRY(check_row_offset(row_offset, n));
+  if (h->have_batch_src || h->have_cond_drop) {
+    set_error("a batch source or condition dropout is armed for the next training call; the noise map does not consume it");
+    return OSD_ESTATE;
+  }
+  if (h->precision == 1) { set_error("the noise map runs on the fp32 kernels only (precision 0)"); return OSD_EUNSUPPORTED; }
+  if (h->n_link > 0) {
+    set_error("output link (osd_set_output_link): a linked model's step is not the plain affine row the noise map inverts; it is refused, not approximated");
+    return OSD_EUNSUPPORTED;
+  }
+  const int D = h->arch.D;
+  if (D < 4) { set_error("the noise map keeps a 16-byte record per row in a [rows][D] workspace: D=%d < 4", D); return OSD_EUNSUPPORTED; }
+  OSD_TRY(check_ready(h));
+  TrainCall tc{h, n, 0};
+  OSD_TRY(tc.enter());
+  hipStream_t s = tc.s;
+  h->last_train_path = 0;
+  OSD_HIP(hipStreamSynchronize(s));          // an earlier sweep or map may still read the tables
+  OSD_TRY(h->bound_ts.reserve(((int64_t)S + 1023) / 1024 * 1024));      // 1024-level granules, as the sweep
+  OSD_TRY(h->map_coef.reserve(((int64_t)S + 1023) / 1024 * 1024 * 4));
+  OSD_HIP(hipMemcpy(h->bound_ts, timesteps_host, (size_t)S * 4, hipMemcpyHostToDevice));
+  OSD_HIP(hipMemcpy(h->map_coef, step_coef_host, (size_t)S * 16, hipMemcpyHostToDevice));
+  if (S == 1) {      // nothing to solve: x_start = y_0
+    const MapRows mr{0, n, h->bound_ts, h->map_coef, 1, 0};
+    OSD_HIP(launch_q_sample_map(s, x0, cond, h->arch.cond_dim, mr, h->d_sqrt_ac, h->d_sqrt_1m, noise_in, n, D, seed, (uint32_t)row_offset, nullptr, 0,
+                                nullptr, nullptr, x_start_out, nullptr, nullptr, nullptr));
+    return OSD_OK;
+  }
+  // groups of at most bound_rows (level, patient) pairs over the levels 1 .. S-1, in pair order, as the sweep; level 0 draws nothing and
+  // does not run: y_0 is formed by level 1's rows
+  const int64_t total = n * (int64_t)(S - 1), cap = h->bound_rows;
+  OSD_TRY(h->parts_dev.reserve(16));
+  for (int64_t p0 = 0; p0 < total; p0 += cap) {
+    const int64_t rows = std::min(cap, total - p0);
+    const MapRows mr{p0, n, h->bound_ts, h->map_coef, S, 1};
+    TrainCall gc{h, rows, 0};
+    gc.s = s;
+    LossStep step{gc, h, h->arch, s, rows, x0, cond, noise_in, nullptr, seed, (uint32_t)row_offset, h->parts_dev + 8, nullptr, 1.0, nullptr, false, false};
+    step.map = &mr; step.z_out = noises_out; step.x_start = x_start_out;
+    OSD_TRY(step.run(nullptr));
   }
   return OSD_OK;
 }

@@ -52,6 +52,28 @@ struct WaveXpose {
       }
     }
   }
+  // store_rows for rows that do not lie one stride apart: row k of the block goes to g + off(k), k < rows (EpiNoiseMap: a wave's rows
+  // may straddle two levels of the plan).  Always guarded.
+  template <class RowOff>
+  __device__ __forceinline__ void store_rows_at(float* __restrict__ g, RowOff off, int lane, int rows, int cols) const {
+    const int c = lane & 7, r = lane >> 3, cr = c ^ r;
+#pragma unroll
+    for (int i0 = 0; i0 < 4 * NPB; i0 += 4) {
+      float4 v[4];
+      long long o[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int row = 8 * (i0 + j) + r;
+        v[j] = *reinterpret_cast<const float4*>(buf + r * 32 + (i0 + j) * 256 + 4 * (cr ^ ((i0 + j) & 7)));
+        o[j] = off(row < rows ? row : rows - 1);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int row = 8 * (i0 + j) + r;
+        if (row < rows && 4 * c < cols) stg4(g + o[j] + 4 * c, v[j]);
+      }
+    }
+  }
   // rows beyond `rows` / chunks beyond `cols` re-read the last valid ones (finite values that are never stored)
   template <bool GUARD>
   __device__ __forceinline__ void load_rows(const float* __restrict__ g, int ld, int lane, int rows, int cols) const {

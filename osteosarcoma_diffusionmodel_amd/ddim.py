@@ -22,6 +22,9 @@ types is A = E*P + F, B = E*Q.  The default, "epsilon", keeps the expressions ab
 the eta = 0 step of ``ddim_x0_table`` plus one term in the previous step's clipped x0^.  ``logsnr_timesteps`` spaces a plan uniformly in
 the log-SNR instead of in t; it is a plan like any other, for either solver.
 
+``edit_timesteps`` and ``ddim_inversion_table`` are the plans of an edit (``model.invert`` / ``model.edit``):
+the levels a patient is noised to, and DDIM inversion -- the eta = 0 step run upwards -- as rows for ``osd_sample_chain_steps``.
+
 ``known_level_table`` is the second table of a chain around observed values (``osd_sample_chain_known``): the noise level each
 step arrives at, at which the observations are put back.
 """
@@ -217,6 +220,70 @@ def logsnr_timesteps(alphas_cumprod, S: int) -> np.ndarray:
     for i in range(S - 2, -1, -1):
         tau[i] = min(tau[i], tau[i + 1] - 1)
     return tau.astype(np.int32)
+
+
+def edit_timesteps(T: int, S: int, strength: float, alphas_cumprod=None, spacing: str = "uniform") -> np.ndarray:
+    """int32 levels of an edit (``model.invert`` / ``model.edit``): the first K = max(1, round(strength * S)) timesteps of the S-step plan
+    (``ddim_timesteps``, or ``logsnr_timesteps`` for ``spacing="logsnr"``, which needs ``alphas_cumprod``), with timestep 0 put in front
+    when it is not there already, so that a replayed chain ends one tiny step above the clean patient.  Strictly increasing, K or K + 1
+    entries; ``strength`` in (0, 1], and 1 gives the whole plan."""
+    strength = float(strength)
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f"strength={strength} outside (0, 1]")
+    if spacing == "uniform":
+        plan = ddim_timesteps(T, S)
+    elif spacing == "logsnr":
+        if alphas_cumprod is None:
+            raise ValueError("spacing='logsnr' needs alphas_cumprod")
+        if _host32(alphas_cumprod).shape[0] != int(T):
+            raise ValueError(f"alphas_cumprod has {_host32(alphas_cumprod).shape[0]} entries, T is {int(T)}")
+        plan = logsnr_timesteps(alphas_cumprod, S)
+    else:
+        raise ValueError(f"spacing must be 'uniform' or 'logsnr', got {spacing!r}")
+    K = max(1, int(round(strength * int(S))))
+    levels = plan[:K].astype(np.int32)
+    if levels[0] != 0:
+        levels = np.concatenate([np.zeros(1, dtype=np.int32), levels])
+    return levels
+
+
+def ddim_inversion_table(alphas_cumprod, levels, prediction: str = "epsilon", *, sqrt_alphas_cumprod=None,
+                         sqrt_one_minus_alphas_cumprod=None):
+    """(int32 [n] timesteps, fp32 [n][4] rows (A, B, 0, 0)), n = len(levels) - 1: DDIM inversion (Song et al. 2021, the deterministic
+    encoder) as a plan for ``osd_sample_chain_steps`` -- the eta = 0 step run upwards.
+
+    The patient is the state at ``levels[0]`` (pass it as ``x_T``), which must have b = sqrt(1 - abar) > 0; ``levels`` strictly increase.
+    Step j evaluates the denoiser at the level the state is at, ``levels[j]``, and goes to ``levels[j + 1]`` (' = there):
+
+        x0^ = P*x + Q*out,   F = b'/b,   E = a' - F*a,   x' = E*x0^ + F*x      =>   A = E*P + F,  B = E*Q,  C = 0
+
+    with a = sqrt(abar), b = sqrt(1 - abar) and (P, Q) the reading of ``prediction`` (module docstring).  Float64 from the fp32 buffers,
+    rounded once, like the other tables.  The rows come in the order the chain runs them, s = n - 1 first: row n - 1 - j is step j, so
+    the first step run is the one at ``levels[0]`` and row 0 (C = 0, as every row) is the step that arrives at ``levels[-1]``."""
+    abar = np.asarray(_host32(alphas_cumprod), dtype=np.float32).astype(np.float64)
+    lv = np.asarray(levels, dtype=np.int64).reshape(-1)
+    T = abar.shape[0]
+    if lv.size < 2:
+        raise ValueError("an inversion needs at least two levels: where the patient is and where the state goes")
+    if lv.min() < 0 or lv.max() >= T or not (np.diff(lv) > 0).all():
+        raise ValueError(f"levels must strictly increase inside [0, {T})")
+    if not abar[lv[0]] < 1.0:
+        raise ValueError(f"levels[0]={int(lv[0])} has abar = 1: the state there carries no noise to scale (b = 0)")
+    if prediction == "epsilon":
+        a0 = np.sqrt(abar)
+        P, Q = 1.0 / a0, -np.sqrt(np.maximum(1.0 - abar, 0.0)) / a0
+    else:
+        P, Q = _x0_reading(prediction, abar, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod)
+    n = lv.size - 1
+    coef = np.zeros((n, 4), dtype=np.float64)
+    for j in range(n):
+        t, tn = lv[j], lv[j + 1]
+        a, b = math.sqrt(abar[t]), math.sqrt(1.0 - abar[t])
+        an, bn = math.sqrt(abar[tn]), math.sqrt(max(1.0 - abar[tn], 0.0))
+        f = bn / b
+        e = an - f * a
+        coef[n - 1 - j, :2] = (e * P[t] + f, e * Q[t])
+    return lv[:-1][::-1].astype(np.int32).copy(), coef.astype(np.float32)
 
 
 def known_level_table(sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, timesteps) -> np.ndarray:

@@ -338,8 +338,8 @@ class BiologyAwareDiffusionModel(nn.Module):
         # SyntheticPatientGenerator switches None to auto: its per-scenario batches are the reference's default workload
         self.input_splitk: Optional[int] = None
         self.last_sampler: Optional[str] = None           # engine the most recent sample() ran on
-        # rows per launch group of the likelihood sweep (variational_bound / row_sq_error): None = the library's 32 768.  It caps the
-        # training workspace the sweep runs in
+        # rows per launch group of the likelihood sweep (variational_bound / row_sq_error) and of invert(method="ddpm"): None = the
+        # library's 32 768.  It caps the training workspace they run in
         self.bound_rows: Optional[int] = None
         # arithmetic of the eval-mode forward / p_sample / sample GEMMs: None / "fp32" = v_mfma_f32_32x32x2_f32, the reference's F.linear in
         # fp32 (models/diffusion.py:198-256; the default); "bf16x3" = every fp32 operand as three bf16 planes (exact) and six bf16 MFMAs
@@ -853,7 +853,7 @@ class BiologyAwareDiffusionModel(nn.Module):
     def sample(self, conditions, num_samples: int = 1, *, x_T=None, noise=None, seed: Optional[int] = None,
                row_offset: int = 0, return_mutation_mask: bool = False, num_inference_steps: Optional[int] = None,
                eta: float = 0.0, guidance_scale: float = 1.0, known=None, x0_bounds=None, solver: Optional[str] = None,
-               timestep_spacing: str = "uniform"):
+               timestep_spacing: str = "uniform", timesteps=None, _step_plan=None):
         """Full reverse chain, in MODEL units: with ``feature_transform`` set the samples, ``known`` and ``x0_bounds`` are what
         ``feature_transform.forward`` makes of data (``SyntheticPatientGenerator`` speaks data units and maps both ways).
         ``x_T`` [N,D] and ``noise`` [T-1,N,D] (draw order t = T-1..1) inject the
@@ -901,7 +901,12 @@ class BiologyAwareDiffusionModel(nn.Module):
         x0^ = sigma(out) there before the clamp, so every returned mutation value lies in [0, 1] with no ``x0_bounds`` given.  Such a model
         always runs the x0-unfolded steps -- the ``x0_bounds`` path with infinite bounds where none are given, or ``solver="dpmpp_2m"`` --
         whatever the other options are: per-layer kernels (``last_sampler == "graph"``), fp32 (``precision = "bf16x3"`` raises
-        ValueError).  ``guidance_scale`` combines raw outputs, so on the mutation columns it acts in logit space."""
+        ValueError).  ``guidance_scale`` combines raw outputs, so on the mutation columns it acts in logit space.
+
+        ``timesteps`` names the plan itself -- strictly increasing timestep indices, e.g. the ``timesteps`` of an ``invert`` record -- in
+        place of one derived from ``num_inference_steps`` and ``timestep_spacing``, which are then not used: ``x_T`` is the state at
+        ``timesteps[-1]`` and ``noise`` is [len(timesteps)-1, N, D].  Every option above keeps its meaning.  ``None`` keeps every path
+        above and its bits."""
         from . import objective as OB
         pred = OB.check_prediction_type(self.prediction_type)
         linked = self._linked()
@@ -914,6 +919,17 @@ class BiologyAwareDiffusionModel(nn.Module):
         if timestep_spacing not in ("uniform", "logsnr"):
             raise ValueError(f"timestep_spacing must be 'uniform' or 'logsnr', got {timestep_spacing!r}")
         multistep = solver == "dpmpp_2m"
+        taus = None
+        if timesteps is not None:
+            taus = np.asarray(timesteps.detach().cpu().numpy() if isinstance(timesteps, torch.Tensor) else timesteps).reshape(-1)
+            if taus.size < 1 or not np.issubdtype(taus.dtype, np.integer):
+                raise ValueError("timesteps must be a non-empty list of integer timestep indices")
+            if int(taus.min()) < 0 or int(taus.max()) >= self.num_steps or not (np.diff(taus.astype(np.int64)) > 0).all():
+                raise ValueError(f"timesteps must strictly increase inside [0, {self.num_steps})")
+            taus = taus.astype(np.int32)
+            num_inference_steps = int(taus.size)
+        if _step_plan is not None:          # invert(method="ddim"): the rows are given, not derived
+            num_inference_steps = int(_step_plan[0].size)
         if num_inference_steps is None:
             if multistep:
                 raise ValueError("solver='dpmpp_2m' needs num_inference_steps")
@@ -949,8 +965,11 @@ class BiologyAwareDiffusionModel(nn.Module):
                 raise ValueError(f"num_inference_steps={steps} outside [1, {self.num_steps}]")
             if noise is not None and float(eta) == 0.0 and kn is None:
                 raise ValueError("noise: eta = 0 draws no z (pass eta > 0 or leave noise out)")
-            taus = ddim_timesteps(self.num_steps, steps) if timestep_spacing == "uniform" else logsnr_timesteps(self.alphas_cumprod, steps)
-            if multistep:
+            if taus is None:
+                taus = ddim_timesteps(self.num_steps, steps) if timestep_spacing == "uniform" else logsnr_timesteps(self.alphas_cumprod, steps)
+            if _step_plan is not None:
+                plan = _step_plan
+            elif multistep:
                 plan = dpmpp_2m_table(self.alphas_cumprod, taus, pred, **sched)
             else:
                 plan = ddim_step_table(self.alphas_cumprod, taus, eta, pred, **sched)
@@ -1052,6 +1071,110 @@ class BiologyAwareDiffusionModel(nn.Module):
         if return_mutation_mask:
             return out, mask
         return out
+
+    # -- counterfactual patients: inversion and edit ---------------------------------
+    @torch.no_grad()
+    def invert(self, x_0, conditions, *, method: str = "ddpm", num_inference_steps: int = 50, strength: float = 1.0, eta: float = 1.0,
+               timestep_spacing: str = "uniform", noise=None, seed: Optional[int] = None, row_offset: int = 0) -> "Inversion":
+        """Turn patients ``x_0`` [N, D] (model units) under ``conditions`` into what ``sample`` turns back into them: an ``Inversion``
+        record (``timesteps``, ``x_start``, ``noise``, ``eta``, ``method``).  ``sample(conditions, N, x_T=rec.x_start, noise=rec.noise,
+        timesteps=rec.timesteps, eta=rec.eta)`` replays it; under other conditions it is the counterfactual (``edit`` does both).
+
+        The levels are ``ddim.edit_timesteps``: the first ``round(strength * num_inference_steps)`` timesteps of the plan, timestep 0 in
+        front -- ``strength`` in (0, 1] is how far up the patient is noised, i.e. how much of it the edit may change.
+
+        ``method="ddpm"``: the edit-friendly DDPM noise space (Huberman-Spiegelglas et al. 2024), one ``osd_noise_map`` call.  The patient
+        is noised independently to every level (``noise`` [S, N, D] injects those draws; otherwise they are keyed by (seed, row_offset +
+        row, timestep) alone) and every step of the plan is solved for the draw that carries one level's state to the next, so the
+        replay reconstructs the patient by construction: it returns the model's x0^ at ``timesteps[0]`` from a state one tiny step
+        above the patient.  Needs ``eta`` > 0; eval mode, fp32 kernels.  ``rec.noise`` is [S-1, N, D].
+
+        ``method="ddim"``: DDIM inversion (Song et al. 2021), the eta = 0 step run upwards (``ddim.ddim_inversion_table``) from the
+        patient as the state at ``timesteps[0]``: one ``osd_sample_chain_steps`` call on any engine (``last_sampler`` says which).
+        ``rec.noise`` is None and ``rec.eta`` 0; ``eta``, ``noise`` and ``seed`` are not used.
+
+        Inversion is always unguided and unclipped.  ValueError: ``method="ddpm"`` with ``eta <= 0`` or ``precision="bf16x3"``,
+        ``strength`` outside (0, 1], a ``mutation_link`` model (its step is not the affine row either method inverts)."""
+        from . import objective as OB
+        from .ddim import ddim_inversion_table, ddim_step_table, edit_timesteps
+        if method not in ("ddpm", "ddim"):
+            raise ValueError(f"method must be 'ddpm' or 'ddim', got {method!r}")
+        pred = OB.check_prediction_type(self.prediction_type)
+        self._refuse_link("invert")
+        if timestep_spacing not in ("uniform", "logsnr"):
+            raise ValueError(f"timestep_spacing must be 'uniform' or 'logsnr', got {timestep_spacing!r}")
+        steps = int(num_inference_steps)
+        if not 1 <= steps <= self.num_steps:
+            raise ValueError(f"num_inference_steps={steps} outside [1, {self.num_steps}]")
+        levels = edit_timesteps(self.num_steps, steps, strength, self.alphas_cumprod, timestep_spacing)
+        sched = dict(sqrt_alphas_cumprod=self.sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod=self.sqrt_one_minus_alphas_cumprod)
+        if method == "ddpm":
+            if not 0.0 < float(eta) <= 1.0:
+                raise ValueError(f"method='ddpm' solves every step for its draw and needs eta in (0, 1], got eta={eta}")
+            if self.precision == "bf16x3":
+                raise ValueError("invert(method='ddpm') runs on the fp32 kernels: precision='bf16x3' is not accepted")
+        if self.training:
+            raise ValueError("invert is eval mode only (model.eval()): it inverts the deterministic network")
+        x_0 = self._prep(x_0, self.data_dim, "x_0")
+        conditions = self._prep(conditions, self.condition_dim, "conditions")
+        n = x_0.shape[0]
+        if conditions.shape[0] != n:
+            raise RuntimeError(f"conditions has {conditions.shape[0]} rows but x_0 has {n}")
+        if n < 1:
+            raise RuntimeError("x_0 has no rows")
+        if method == "ddim":
+            plan = ddim_inversion_table(self.alphas_cumprod, levels, pred, **sched)
+            x_start = self.sample(conditions, n, x_T=x_0, seed=0, x0_bounds=False, _step_plan=plan)
+            return Inversion(levels, x_start, None, 0.0, "ddim")
+        tau, coef = ddim_step_table(self.alphas_cumprod, levels, eta, pred, **sched)
+        S = int(tau.size)
+        eng = self._engine()
+        nz = None
+        if noise is not None:
+            if noise.device != x_0.device:
+                raise RuntimeError(f"noise is on {noise.device} but the model is on {x_0.device}")
+            nz = noise.to(torch.float32).contiguous()
+            if tuple(nz.shape) != (S, n, self.data_dim):
+                raise RuntimeError(f"noise: expected shape [{S}, {n}, {self.data_dim}], got {tuple(nz.shape)}")
+        seed = (0 if nz is not None else _draw_seed()) if seed is None else seed
+        x_start = torch.empty_like(x_0)
+        zs = torch.empty(S - 1, n, self.data_dim, device=x_0.device, dtype=torch.float32)
+        L.check(L.lib().osd_noise_map(eng.handle, L.ptr(x_0), L.ptr(conditions), n, tau.ctypes.data, coef.ctypes.data, S, L.ptr(nz), seed,
+                                      int(row_offset), L.ptr(x_start), L.ptr(zs) if S > 1 else None))
+        eng.serial += 1           # the training workspace now belongs to this call
+        self.last_precision = "fp32"
+        return Inversion(levels, x_start, zs, float(eta), "ddpm")
+
+    @torch.no_grad()
+    def edit(self, x_0, conditions, new_conditions, *, method: str = "ddpm", num_inference_steps: int = 50, strength: float = 1.0,
+             eta: float = 1.0, timestep_spacing: str = "uniform", noise=None, seed: Optional[int] = None, row_offset: int = 0,
+             guidance_scale: float = 1.0, x0_bounds=None, known=None):
+        """The counterfactual of patients ``x_0`` [N, D]: ``invert`` under ``conditions``, then ``sample`` under ``new_conditions`` from
+        the record -- what the model makes of the same patients' noise under another condition.  Model units, like ``sample``.
+
+        The inversion is always unguided and unclipped; ``guidance_scale``, ``x0_bounds`` and ``known`` (``sample``'s meanings: e.g. hold
+        the observed mutations) apply to the decode, through the guided, clipped and known chains with the record's draws.  With
+        ``new_conditions`` equal to ``conditions`` and ``method="ddpm"`` the result is the model's own x0^ of the patient at level 0."""
+        rec = self.invert(x_0, conditions, method=method, num_inference_steps=num_inference_steps, strength=strength, eta=eta,
+                          timestep_spacing=timestep_spacing, noise=noise, seed=seed, row_offset=row_offset)
+        n = rec.x_start.shape[0]
+        zs = rec.noise if rec.noise is not None and rec.noise.shape[0] > 0 else None
+        return self.sample(new_conditions, n, x_T=rec.x_start, noise=zs, seed=0, row_offset=row_offset, eta=rec.eta,
+                           guidance_scale=guidance_scale, known=known, x0_bounds=x0_bounds, timesteps=rec.timesteps)
+
+
+class Inversion:
+    """What ``BiologyAwareDiffusionModel.invert`` returns: ``timesteps`` (int32 numpy, increasing, the plan ``sample(timesteps=...)``
+    replays), ``x_start`` [N, D] (the state at ``timesteps[-1]``), ``noise`` [len(timesteps)-1, N, D] in the chain's draw order (None for
+    ``"ddim"``), ``eta`` and ``method``."""
+    __slots__ = ("timesteps", "x_start", "noise", "eta", "method")
+
+    def __init__(self, timesteps, x_start, noise, eta, method):
+        self.timesteps, self.x_start, self.noise, self.eta, self.method = timesteps, x_start, noise, eta, method
+
+    def __repr__(self):
+        return (f"Inversion(method={self.method!r}, eta={self.eta}, timesteps={self.timesteps.tolist()}, "
+                f"x_start={tuple(self.x_start.shape)}, noise={None if self.noise is None else tuple(self.noise.shape)})")
 
 
 # north_star alias (there is no class of this name in the reference; SURVEY section 0)

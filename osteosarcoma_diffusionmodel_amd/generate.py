@@ -350,6 +350,98 @@ class SyntheticPatientGenerator:
         return {"mutations": mask.cpu().numpy().astype(float), "expression": samples[:, md:md + ed], "pathways": samples[:, md + ed:],
                 "conditions": cond.cpu().numpy()}
 
+    def counterfactual(self, features, conditions, scenario: Optional[Dict] = None, *, new_conditions=None, keep=None,
+                       method: str = "ddpm", sampling_steps: int = 50, strength: float = 0.6, eta: float = 1.0,
+                       guidance_scale: float = 1.0, x0_bounds=None, seed: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """What would these patients look like under another condition?  ``features`` are real rows in data units -- an [n, D] array or
+        a dict with all of ``mutations`` / ``expression`` / ``pathways`` --, ``conditions`` [n, condition_dim] the rows' own.  Each row
+        is inverted under its own condition and decoded under the new one (``model.edit``), so a row and its
+        counterfactual are a pair: the same patient-specific noise, another condition.
+
+        Exactly one of ``scenario`` (a dict as in ``generate``: the named conditions are overridden in every row, the others keep the
+        row's own values) and ``new_conditions`` ([n, condition_dim], full rows) says what changes.  ``keep`` holds columns at their
+        observed values through the decode (``sample``'s ``known``): a dict over the blocks with ``True`` (the whole block) or a boolean
+        mask of the block's width, or a boolean [D] mask -- ``keep={"mutations": True}`` asks for the same tumour genotype under another
+        outcome.  ``method`` / ``sampling_steps`` / ``strength`` / ``eta`` as in ``model.invert``: ``strength`` is how far up the rows are
+        noised, so how much may change.  ``guidance_scale`` and ``x0_bounds`` apply to the decode, as in ``generate``.
+
+        A model with a feature transform is spoken to in data units, as by ``impute``: forward in front, inverse behind, kept values
+        restored from the caller's.  Returns ``generate``'s dictionary (``conditions``: the new rows) plus ``original_conditions``."""
+        if hasattr(self.model, "vae"):
+            raise ValueError("counterfactual inverts the diffusion model's reverse chain and is not accepted for a cVAE model")
+        if (scenario is None) == (new_conditions is None):
+            raise ValueError("counterfactual: give exactly one of scenario and new_conditions")
+
+        def cond_rows(c, name):
+            if isinstance(c, torch.Tensor):
+                c = c.detach().to(device=self.device, dtype=torch.float32)
+            else:
+                c = torch.as_tensor(np.asarray(c, dtype=np.float32), device=self.device)
+            if c.dim() != 2 or c.shape[1] != self.condition_dim:
+                raise ValueError(f"{name}: expected [n, {self.condition_dim}], got {tuple(c.shape)}")
+            return c.contiguous()
+
+        cond = cond_rows(conditions, "conditions")
+        n = cond.shape[0]
+        if new_conditions is not None:
+            new = cond_rows(new_conditions, "new_conditions")
+            if new.shape[0] != n:
+                raise ValueError(f"new_conditions: {new.shape[0]} rows, conditions has {n}")
+        else:
+            names = list(self.config["model"]["condition_on"])[:self.condition_dim]
+            unknown = set(scenario) - set(names)
+            if unknown:
+                raise ValueError(f"scenario names {sorted(unknown)}, the model is conditioned on {names}")
+            encoded = self.create_conditions(1, scenario)[0]
+            new = cond.clone()
+            for j, name in enumerate(names):
+                if name in scenario:
+                    new[:, j] = encoded[j]
+        md, ed, pd_ = self.mutation_dim, self.expression_dim, self.pathway_dim
+        D = md + ed + pd_
+        data_np = assemble_known(features, n, md, ed, pd_)
+        if np.isnan(data_np).any():
+            raise ValueError("features: a counterfactual needs complete rows (impute fills holes)")
+        data = torch.from_numpy(data_np).to(self.device)
+        keep_mask = np.zeros(D, dtype=bool)
+        if isinstance(keep, dict):
+            widths = {"mutations": md, "expression": ed, "pathways": pd_}
+            extra = set(keep) - set(widths)
+            if extra:
+                raise ValueError(f"keep: unknown block(s) {sorted(extra)}; expected any of {list(widths)}")
+            c0 = 0
+            for name, width in widths.items():
+                v = keep.get(name)
+                if v is not None and v is not False:
+                    m = np.ones(width, dtype=bool) if v is True else np.asarray(v, dtype=bool).reshape(-1)
+                    if m.shape[0] != width:
+                        raise ValueError(f"keep {name}: expected True or a boolean mask of {width} columns")
+                    keep_mask[c0:c0 + width] = m
+                c0 += width
+        elif keep is not None:
+            keep_mask = np.asarray(keep, dtype=bool).reshape(-1)
+            if keep_mask.shape[0] != D:
+                raise ValueError(f"keep: expected a dict over the blocks or a boolean mask of {D} columns")
+        x0_bounds = self._x0_bounds(x0_bounds)
+        ft = self._transform()
+        with torch.no_grad():
+            x_model = data if ft is None else ft.forward(data)
+            kn = kn_data = None
+            if keep_mask.any():
+                km = torch.from_numpy(keep_mask).to(self.device)
+                nan = torch.full_like(data, float("nan"))
+                kn_data = torch.where(km[None, :], data, nan)
+                kn = torch.where(km[None, :], x_model, nan)
+            rec = self.model.invert(x_model, cond, method=method, num_inference_steps=sampling_steps, strength=strength, eta=eta, seed=seed)
+            zs = rec.noise if rec.noise is not None and rec.noise.shape[0] > 0 else None
+            samples, mask = self.model.sample(new, num_samples=n, x_T=rec.x_start, noise=zs, seed=0, return_mutation_mask=True, eta=rec.eta,
+                                              guidance_scale=self._guidance_scale(guidance_scale), known=kn, x0_bounds=x0_bounds,
+                                              timesteps=rec.timesteps)
+            samples = self._to_data_units(samples, kn_data)
+        samples = samples.cpu().numpy()
+        return {"mutations": mask.cpu().numpy().astype(float), "expression": samples[:, md:md + ed], "pathways": samples[:, md + ed:],
+                "conditions": new.cpu().numpy(), "original_conditions": cond.cpu().numpy()}
+
     def save_synthetic_data(self, synthetic_data: Dict[str, np.ndarray], output_dir: Path,
                             gene_names: Dict[str, List[str]], prefix: str = "synthetic"):
         """Four CSVs per scenario (utils/generate.py:177-235)."""

@@ -1579,6 +1579,75 @@ class BiologicalValidator:
         summary, rows = DE.differential_metrics(self.k, x, cs[0], y, cs[1], names, bounds, block_names, float(alpha), int(top_k))
         return (summary, rows) if return_rows else summary
 
+    # -- counterfactual patients against the real cohort's own contrast --------------------------------------
+    def counterfactual_consistency(self, original, counterfactual, real, real_cond, contrast, names=None, blocks=None,
+                                   alpha: float = 0.05):
+        """Does a set of counterfactuals (``SyntheticPatientGenerator.counterfactual``: row r of ``counterfactual`` is row r of
+        ``original`` under the other condition) move the features the way the real cohort's own two groups differ?  ``contrast`` names
+        the condition column (a name of ``names`` / of ``real_cond``'s columns, or an index) that was changed, split as
+        ``differential_fidelity`` splits it: the counterfactuals are taken to move control rows (0, or at or below the real median)
+        to the case side, so the reference is the real cases' mean minus the real controls'.  Both are in units of the real column's
+        standard deviation (ddof = 1; a constant real column counts as 0 in both):
+
+          ``cf_effect_pearson``, ``cf_effect_slope``   over the features, of the mean paired shift against the real mean difference
+                                                       (``diffexp.contrast_summary``; slope below 1: the edit under-shoots)
+          ``cf_sign_agreement``    over the real hits (Mann-Whitney q < ``alpha``), the share whose shift has the real difference's sign
+          ``cf_real_hits``         their number
+          ``cf_mean_abs_shift``    the mean over the features of |mean paired shift| / sd
+          ``cf_rows_changed_mutation_share``   with ``blocks`` naming a ``mutations`` block: the share of rows in which any mutation,
+                                               read at 0.5, differs between the pair; NaN without one
+
+        Host composition over ``DeviceKernels.group_ranks`` and ``col_centered_moments``; no sharded form (as ``differential_fidelity``)."""
+        if self.sharded:
+            raise ValueError("counterfactual_consistency is not available on a sharded validator: it reads the real cohort's U statistics")
+        if names is None:
+            cols = getattr(real_cond, "columns", None)
+            names = [str(c) for c in cols] if cols is not None else None
+        x, o, c = _dev(real, self.device), _dev(original, self.device), _dev(counterfactual, self.device)
+        rc = np.asarray(_host(real_cond), dtype=np.float64)
+        rc = rc.reshape(-1, 1) if rc.ndim == 1 else rc
+        D = int(x.shape[1]) if x.dim() == 2 else 0
+        if x.dim() != 2 or D < 1 or x.shape[0] < 2 or rc.shape[0] != x.shape[0]:
+            raise ValueError("real must be [rows >= 2, D] with one condition row per real row")
+        if o.dim() != 2 or o.shape != c.shape or o.shape[1] != D or o.shape[0] < 1:
+            raise ValueError(f"original and counterfactual must be paired [rows >= 1, {D}] arrays")
+        if not (bool(torch.isfinite(x).all().item()) and bool(torch.isfinite(o).all().item()) and bool(torch.isfinite(c).all().item())
+                and np.isfinite(rc).all()):
+            raise ValueError("counterfactual_consistency: non-finite values")
+        if isinstance(contrast, str):
+            if names is None or contrast not in [str(v) for v in names]:
+                raise ValueError(f"contrast {contrast!r} is not among the condition names {names}")
+            j = [str(v) for v in names].index(contrast)
+        else:
+            j = int(contrast)
+        if not 0 <= j < rc.shape[1]:
+            raise ValueError(f"contrast index {j} outside the {rc.shape[1]} condition columns")
+        if not 0.0 < float(alpha) <= 1.0:
+            raise ValueError("alpha must lie in (0, 1]")
+        bounds, block_names = corr_block_bounds(blocks, D)
+        labels, _, _ = DE.contrast_labels(rc[:, j], rc[:, j])
+        if min(int((labels == 1).sum()), int((labels == 0).sum())) < 1:
+            raise ValueError("the contrast has an empty group in the real cohort")
+        stat = DE.cohort_statistics(self.k, x, labels)
+        n_real, n = int(x.shape[0]), int(o.shape[0])
+        s0, _ = self.k.col_centered_moments(x)
+        center = (np.asarray(s0, dtype=np.float64) / n_real).astype(np.float32)
+        s1, q1 = self.k.col_centered_moments(x, center)
+        sd = np.sqrt(np.maximum(q1 - s1 * s1 / n_real, 0.0) / (n_real - 1.0))
+        ds, _ = self.k.col_centered_moments(c - o)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            shift = np.where(sd > 0, (ds / n) / sd, 0.0)
+            ref = np.where(sd > 0, stat["mean_diff"] / sd, 0.0)
+        one = DE.contrast_summary({"effect": ref, "q": stat["q"]}, {"effect": shift, "q": np.ones(D)}, float(alpha), 1)
+        out = {"cf_effect_pearson": one["effect_pearson"], "cf_effect_slope": one["effect_slope"], "cf_sign_agreement": one["sign_agreement"],
+               "cf_real_hits": one["real_hits"], "cf_mean_abs_shift": float(np.abs(shift).mean()),
+               "cf_rows_changed_mutation_share": float("nan")}
+        if "mutations" in block_names:
+            b = block_names.index("mutations")
+            lo, hi = bounds[b], bounds[b + 1]
+            out["cf_rows_changed_mutation_share"] = float(((o[:, lo:hi] > 0.5) != (c[:, lo:hi] > 0.5)).any(dim=1).double().mean().item())
+        return out
+
     # -- prognostic genes: one Cox model per feature and cohort (DESIGN.md section 3.32) ---------------------------------------------
     def prognostic_fidelity(self, real, real_surv, synthetic, synth_surv, blocks=None, alpha: float = 0.05, top_k: int = 50,
                             mle: bool = True, return_rows: bool = False):
