@@ -16,11 +16,10 @@ import torch
 from oracle import diffusion_oracle as O
 from osteosarcoma_diffusionmodel_amd import BiologyAwareDiffusionModel
 from osteosarcoma_diffusionmodel_amd import _lib as L
-from osteosarcoma_diffusionmodel_amd import objective as OB
-from osteosarcoma_diffusionmodel_amd.ddim import ddim_step_table, ddim_timesteps, ddim_x0_table, known_level_table
+from osteosarcoma_diffusionmodel_amd.ddim import ddim_step_table, ddim_timesteps, ddim_x0_table, dpmpp_2m_table, known_level_table
 from osteosarcoma_diffusionmodel_amd.train import _loss_fwd_bwd
 from helpers import FULL_H, assert_close, config
-from link_helpers import LinkOracle, condition_l1_x0_cont, link_eps_fn, link_out
+from link_helpers import LinkOracle, condition_l1_x0_cont, link_eps_fn, link_out, loss_weights
 from loss_helpers import GRAD_RTOL, L1_MARGIN, LOSS_RTOL, P_DROP, SEED, Fp64Oracle, check, inputs, philox_masks, predict_fp64
 from mask_helpers import DEEP, H4, SHAPES, mask_pattern, mix, with_nan, zero_fill
 from pred_helpers import chain64, guided_out, model_sd64
@@ -38,12 +37,7 @@ _cache = {}
 
 
 # ======== training ======================================================================================================================
-def _weights(weighting):
-    if weighting == "min_snr":
-        return OB.min_snr_weights(O.schedule_buffers("cosine", 1000)["alphas_cumprod"], 5.0, "sample")
-    if weighting == "custom":
-        return torch.rand(1000, generator=torch.Generator().manual_seed(4)) * 2 + 0.05
-    return None
+_weights = loss_weights
 
 
 def _shape(name, masked=False):
@@ -332,6 +326,27 @@ def chain_link(m, cond, *, lo=None, hi=None, x_T=None, zs=None, seed=0, row_offs
                                           None if tau is None else tau.ctypes.data, None if coef is None else coef.ctypes.data,
                                           None if x0c is None else x0c.ctypes.data, None if level is None else level.ctypes.data,
                                           0 if tau is None else int(tau.size), c0, w, L.ptr(known), D, lo.ctypes.data, hi.ctypes.data)
+    assert rc == expect, (rc, L.last_error())
+    torch.cuda.synchronize()
+    return out, mask
+
+
+def chain_link_multistep(m, cond, lo, hi, taus, *, x_T=None, zs=None, seed=0, row_offset=0, known=None, expect=L.OSD_OK):
+    """osd_sample_chain_multistep through ctypes on the model's handle with the tables of a sample model: (x_out, mutation mask).
+    lo = hi = None are infinite bounds."""
+    eng = m._engine()
+    n, D = cond.shape[0], m.data_dim
+    out = torch.empty(n, D, device="cuda")
+    mask = torch.empty(n, m.mutation_dim, device="cuda")
+    tau, x0c, hist = dpmpp_2m_table(m.alphas_cumprod, taus, "sample", sqrt_alphas_cumprod=m.sqrt_alphas_cumprod,
+                                    sqrt_one_minus_alphas_cumprod=m.sqrt_one_minus_alphas_cumprod)
+    level = None if known is None else known_level_table(m.sqrt_alphas_cumprod, m.sqrt_one_minus_alphas_cumprod, tau)
+    flags = L.OSD_F_GRAPH if m.use_graph else 0
+    lo = np.full(D, -np.inf, dtype=np.float32) if lo is None else np.ascontiguousarray(lo, dtype=np.float32)
+    hi = np.full(D, np.inf, dtype=np.float32) if hi is None else np.ascontiguousarray(hi, dtype=np.float32)
+    rc = L.lib().osd_sample_chain_multistep(eng.handle, L.ptr(cond), n, L.ptr(x_T), L.ptr(zs), seed, row_offset, L.ptr(out), L.ptr(mask), flags,
+                                            tau.ctypes.data, x0c.ctypes.data, hist.ctypes.data, None if level is None else level.ctypes.data,
+                                            int(tau.size), None, 1.0, L.ptr(known), D, lo.ctypes.data, hi.ctypes.data)
     assert rc == expect, (rc, L.last_error())
     torch.cuda.synchronize()
     return out, mask
