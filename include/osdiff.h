@@ -508,6 +508,40 @@ int osd_nn_clip_adamw_ema_step(void *stream, int device, double *normsq_ws, floa
                                double beta1, double beta2, double eps, double weight_decay, double max_norm,
                                int64_t step, double ema_decay, float *grad_norm_out);
 
+/* ---- the grouped step: fine-tuning from a pretrained model ----
+ * The flat buffer is cut into n_groups sorted, non-empty, non-overlapping element ranges [begin, end) that together cover
+ * [0, numel); at most OSD_MAX_PARAM_GROUPS of them.  Offsets are element offsets and need no alignment.  Each group scales the
+ * learning rate (lr_scale) and the weight decay (wd_scale) and may pull its parameters toward `anchor` (l2sp, the L2-SP penalty of
+ * Li et al. 2018, decoupled like the weight decay).  The per-group constants are formed in double and rounded once to float:
+ *   decay_s = 1 - lr*lr_scale*weight_decay*wd_scale,   neg_step_size_s = -(lr*lr_scale / bc1),   pull_s = lr*lr_scale*l2sp.
+ * Per element of a group with lr_scale > 0, in fp32 with one rounding per operation:
+ *   g *= coef (when max_norm > 0);  p_old = p;  p = p*decay_s;  if (pull_s != 0) p = p - pull_s*(p_old - anchor);
+ *   then the moments, the addcdiv and (ema != NULL) the lerp of the plain step.  With lr_scale = wd_scale = 1 and l2sp = 0 these are
+ *   the plain step's operations in its order, and the result carries its bits.
+ * A group with lr_scale == 0 is FROZEN: none of param, grad, exp_avg, exp_avg_sq, ema is written there, and its gradient is left out of
+ * the norm by a select (a NaN or 1e30 there does not reach coef or grad_norm_out): clip_grad_norm_ over the parameters that have
+ * gradients.  With no frozen group grad_norm_out carries the plain step's bits.  All groups frozen is legal: norm 0, nothing written.
+ * No atomics, no state between calls; the same bits however a run of equal-setting elements is cut into groups.
+ * ema and anchor are nullable device float[numel]; anchor is read only inside groups with pull_s != 0.  groups_host is host memory,
+ * consumed before the call returns.  normsq_ws (the stream-taking variant): device scratch of OSD_GROUP_WS_DOUBLES doubles -- the
+ * norm partials and room for the group table -- with no initial state required.
+ * OSD_EINVAL, before any device call: a NULL buffer; n_groups outside [1, OSD_MAX_PARAM_GROUPS]; groups unsorted, empty, overlapping
+ * or not covering [0, numel); a negative or non-finite scale; l2sp > 0 in some group with a NULL anchor; ema_decay outside [0, 1]
+ * when ema is given.  The handle variant marks the packed weight copies stale, as the plain handle step does. */
+#define OSD_MAX_PARAM_GROUPS 1024
+#define OSD_GROUP_WS_DOUBLES 3328 /* 256 + 3 * OSD_MAX_PARAM_GROUPS */
+typedef struct { int64_t begin, end; float lr_scale, wd_scale, l2sp; } osd_param_group;
+int osd_group_adamw_step(osd_handle *h, float *param, float *grad, float *exp_avg, float *exp_avg_sq,
+                         float *ema /*nullable*/, const float *anchor /*nullable*/, int64_t numel,
+                         const osd_param_group *groups_host, int n_groups, double lr, double beta1, double beta2,
+                         double eps, double weight_decay, double max_norm, int64_t step, double ema_decay,
+                         float *grad_norm_out);
+int osd_nn_group_adamw_step(void *stream, int device, double *normsq_ws, float *param, float *grad, float *exp_avg,
+                            float *exp_avg_sq, float *ema /*nullable*/, const float *anchor /*nullable*/, int64_t numel,
+                            const osd_param_group *groups_host, int n_groups, double lr, double beta1, double beta2,
+                            double eps, double weight_decay, double max_norm, int64_t step, double ema_decay,
+                            float *grad_norm_out);
+
 /* ---- differentially private training (DP-SGD, Abadi et al. 2016) ----
  * A training call on n rows has loss L = (1/n) sum_r l_r, l_r = (1/D) w[t_r] sum_f rho(d_rf) (osd_set_loss, osd_set_prediction, dropout and
  * condition dropout as configured).  With g_r = grad l_r over ALL parameter tensors taken as one vector and s_r = |g_r|_2,

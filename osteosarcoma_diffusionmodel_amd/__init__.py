@@ -8,9 +8,10 @@ Host-side mirror of the reference's Python API over the C ABI of libosdiff.so:
 from .diffusion import BiologyAwareDiffusion, BiologyAwareDiffusionModel  # noqa: F401
 from .generate import SyntheticPatientGenerator, generate_patients, load_trained_model  # noqa: F401
 from . import pca  # noqa: F401  (DevicePCA: principal components by subspace iteration on the device)
+from .transfer import load_pretrained  # noqa: F401  (a pretrained checkpoint carried onto another feature panel)
 
 __all__ = ["BiologyAwareDiffusionModel", "BiologyAwareDiffusion", "SyntheticPatientGenerator",
-           "generate_patients", "load_trained_model", "pca"]
+           "generate_patients", "load_trained_model", "load_pretrained", "pca"]
 
 
 def _respect_cpu_quota():

@@ -29,6 +29,8 @@ OSD_COXS_ROWS = 128
 OSD_PCA_MAX_DIRS = 32
 OSD_XF_IDENTITY, OSD_XF_STANDARD, OSD_XF_QUANTILE_NORMAL = 0, 1, 2
 OSD_XF_MAX_Q = 1024
+OSD_MAX_PARAM_GROUPS = 1024
+OSD_GROUP_WS_DOUBLES = 256 + 3 * OSD_MAX_PARAM_GROUPS      # osd_nn_group_adamw_step's workspace: the norm partials, then the group table
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libosdiff.so"
 
@@ -49,6 +51,10 @@ class OsdConstraints(C.Structure):
         ("cols_a", C.POINTER(C.c_int32)), ("cols_b", C.POINTER(C.c_int32)), ("n_a", C.c_int32), ("n_b", C.c_int32),
         ("mutexpr_weight", C.c_double),
     ]
+
+
+class OsdParamGroup(C.Structure):
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr_scale", C.c_float), ("wd_scale", C.c_float), ("l2sp", C.c_float)]
 
 
 _P = C.c_void_p
@@ -179,6 +185,10 @@ _SIGNATURES = {
                                          C.c_double, C.c_double, C.c_int64, _P]),
     "osd_nn_clip_adamw_ema_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
                                              C.c_double, C.c_double, C.c_int64, C.c_double, _P]),
+    "osd_group_adamw_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(OsdParamGroup), C.c_int, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_double, _P]),
+    "osd_nn_group_adamw_step": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(OsdParamGroup), C.c_int, C.c_double,
+                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_double, _P]),
     "osd_nn_vae_loss": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "osd_nn_mixup": (C.c_int, [_P, C.c_int, _P, _P, C.c_double, C.c_int64, C.c_int, _P]),
     "osd_nn_mixup3": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_double, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),

@@ -655,6 +655,224 @@ hipError_t launch_clip_adamw(hipStream_t s, float* p, float* g, float* m, float*
   return hipGetLastError();
 }
 
+// ---- the grouped step (kernels_train.h): per-range lr / weight decay / pull toward an anchor, frozen ranges ----
+// How a thread finds its group: the whole table (at most 1024 x 24 bytes, in practice a handful of merged ranges) is copied into LDS by
+// every workgroup ahead of the barrier the norm fold needs anyway, and each thread bisects the `end` column there for the first element
+// of its float4, starting from the group of its previous float4 (positions only grow along the grid-stride walk).  A table of up to
+// GROUPS_INLINE groups arrives in the kernel arguments (scalar loads, no device memory, no copy that could outlive the host array);
+// a larger one is first written into the workspace by k_write_groups, GROUPS_INLINE groups per launch, through the same argument block.
+struct GroupTabArgs { long long end[GROUPS_INLINE]; GroupConst c[GROUPS_INLINE]; };
+constexpr int GROUP_WS_END = 256, GROUP_WS_CONST = 256 + GROUPS_MAX;       // offsets (in doubles) of the two table columns in the workspace
+
+__global__ __launch_bounds__(GROUPS_INLINE) void k_write_groups(GroupTabArgs tab, int count, int first, double* ws) {
+  const int t = threadIdx.x;
+  if (t >= count || first + t >= GROUPS_MAX) return;
+  reinterpret_cast<long long*>(ws + GROUP_WS_END)[first + t] = tab.end[t];
+  reinterpret_cast<GroupConst*>(ws + GROUP_WS_CONST)[first + t] = tab.c[t];
+}
+
+// LDS image of the table: GroupConst c[ng] (16-byte aligned), then long long end[ng].  The caller barriers before reading.
+__device__ __forceinline__ void load_group_table(const GroupTabArgs& tab, const double* ws, int ng, GroupConst* s_c, long long* s_end) {
+  if (ws) {
+    const long long* d_end = reinterpret_cast<const long long*>(ws + GROUP_WS_END);
+    const GroupConst* d_c = reinterpret_cast<const GroupConst*>(ws + GROUP_WS_CONST);
+    for (int k = threadIdx.x; k < ng; k += blockDim.x) { s_end[k] = d_end[k]; s_c[k] = d_c[k]; }
+  } else {
+    for (int k = threadIdx.x; k < ng; k += blockDim.x) { s_end[k] = tab.end[k]; s_c[k] = tab.c[k]; }
+  }
+}
+// first group at or after `lo` whose end lies past element e; always inside [0, ng) whatever the table holds
+__device__ __forceinline__ int find_group(const long long* s_end, int ng, int lo, long long e) {
+  int hi = ng - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (s_end[mid] > e) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+// k_sumsq's walk -- the same grid, float4 grid-stride order, per-workgroup double partials -- with the elements of frozen groups left out:
+// a float4 inside a frozen group is skipped unread (its contribution would be +0.0, and s + 0.0 is s), the frozen lanes of a float4 that
+// straddles a boundary are replaced by +0.0f by a select before they are squared.  A NaN or 1e30 there never enters the sum, and what
+// remains is k_sumsq's expression on k_sumsq's operands in k_sumsq's order, so with nothing frozen the partials carry k_sumsq's bits.
+__global__ __launch_bounds__(256) void k_sumsq_groups(const float* __restrict__ g, int64_t n, double* parts, GroupTabArgs tab, const double* tab_ws,
+                                                      int ng) {
+  extern __shared__ __align__(16) unsigned char s_tab[];
+  GroupConst* s_c = reinterpret_cast<GroupConst*>(s_tab);
+  long long* s_end = reinterpret_cast<long long*>(s_c + ng);
+  load_group_table(tab, tab_ws, ng, s_c, s_end);
+  __syncthreads();
+  double s = 0.0;
+  const int64_t n4 = (reinterpret_cast<uintptr_t>(g) & 15) == 0 ? n >> 2 : 0;
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  int cur = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const long long e0 = 4 * i;
+    cur = find_group(s_end, ng, cur, e0);
+    float4 v;
+    if (s_end[cur] >= e0 + 4) {        // inside one group: a frozen float4 is not even read (s + 0.0 is s)
+      if (s_c[cur].trainable == 0) continue;
+      v = g4[i];
+    } else {
+      v = g4[i];
+      int k = cur;
+      bool t[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        while (k < ng - 1 && s_end[k] <= e0 + j) ++k;
+        t[j] = s_c[k].trainable != 0;
+      }
+      v.x = t[0] ? v.x : 0.f; v.y = t[1] ? v.y : 0.f; v.z = t[2] ? v.z : 0.f; v.w = t[3] ? v.w : 0.f;
+    }
+    s += (double)v.x * (double)v.x + (double)v.y * (double)v.y + (double)v.z * (double)v.z + (double)v.w * (double)v.w;
+  }
+  for (int64_t i = 4 * n4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    cur = find_group(s_end, ng, cur, i);
+    if (s_c[cur].trainable == 0) continue;
+    const float v = g[i];
+    s += (double)v * (double)v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  __shared__ double part[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) part[w] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) parts[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// adamw_one with the group's decay and step size, and the L2-SP pull (Li et al. 2018, decoupled like the weight decay) between the decay
+// and the moments: p <- p*decay - pull*(p_old - anchor), three roundings, no FMA.  With decay, neg_step_size as in AdamArgs and
+// pull == 0 these are adamw_one's operations in adamw_one's order.
+__device__ __forceinline__ void group_adamw_one(float& pi, float& gi, float& mi, float& vi, float anc, const GroupConst& c, const AdamArgs& a, float coef) {
+  if (a.max_norm > 0.f) gi = __fmul_rn(gi, coef);
+  const float p_old = pi;
+  pi = __fmul_rn(pi, c.decay);
+  if (c.pull != 0.f) pi = __fsub_rn(pi, __fmul_rn(c.pull, __fsub_rn(p_old, anc)));
+  mi = __fadd_rn(mi, __fmul_rn(a.one_minus_b1, __fsub_rn(gi, mi)));
+  vi = __fmul_rn(vi, a.b2);
+  vi = __fadd_rn(vi, __fmul_rn(__fmul_rn(a.one_minus_b2, gi), gi));
+  const float denom = __fadd_rn(__fdiv_rn(sqrtf(vi), a.bc2_sqrt), a.eps);
+  pi = __fadd_rn(pi, __fmul_rn(c.neg_step_size, __fdiv_rn(mi, denom)));
+}
+// one element with 4-byte accesses: the lanes of a float4 that straddles a group boundary, the tail, the unaligned fallback.
+// A frozen element is neither read nor written; the anchor is read only where the group pulls.
+template <bool EMA>
+__device__ __forceinline__ void group_adamw_elem(int64_t i, const GroupConst c, float* p, float* g, float* m, float* v, float* e, float ema_w,
+                                                 const float* anc, const AdamArgs& a, float coef) {
+  if (!c.trainable) return;
+  float pi = p[i], gi = g[i], mi = m[i], vi = v[i];
+  const float an = c.pull != 0.f ? anc[i] : 0.f;
+  group_adamw_one(pi, gi, mi, vi, an, c, a, coef);
+  if (a.max_norm > 0.f) g[i] = gi;
+  p[i] = pi; m[i] = mi; v[i] = vi;
+  if (EMA) {
+    float ei = e[i];
+    ema_one(ei, pi, ema_w);
+    e[i] = ei;
+  }
+}
+// HBM-bound like k_adamw: its 7 (EMA: 9) streams over the trainable elements, one more (read anchor) inside groups that pull, nothing
+// at all inside frozen groups.
+template <bool EMA>
+__global__ __launch_bounds__(256) void k_adamw_groups(float* p, float* g, float* m, float* v, float* e, float ema_w, const float* anc, int64_t n,
+                                                      AdamArgs a, const double* parts, int nparts, float* norm_out, GroupTabArgs tab,
+                                                      const double* tab_ws, int ng) {
+  extern __shared__ __align__(16) unsigned char s_tab[];
+  GroupConst* s_c = reinterpret_cast<GroupConst*>(s_tab);
+  long long* s_end = reinterpret_cast<long long*>(s_c + ng);
+  load_group_table(tab, tab_ws, ng, s_c, s_end);
+  __shared__ double sh[4];
+  {
+    double s = (int)threadIdx.x < nparts ? parts[threadIdx.x] : 0.0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+  }
+  float coef = 1.0f;
+  const float norm = (float)sqrt((sh[0] + sh[1]) + (sh[2] + sh[3]));
+  if (a.max_norm > 0.f) {
+    coef = a.max_norm / (norm + 1e-6f);
+    if (coef > 1.0f) coef = 1.0f;
+  }
+  if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = norm;
+  uintptr_t bits = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v);
+  if (EMA) bits |= reinterpret_cast<uintptr_t>(e);
+  if (anc) bits |= reinterpret_cast<uintptr_t>(anc);
+  const bool al = (bits & 15) == 0;
+  const int64_t n4 = al ? n >> 2 : 0;
+  float4* p4 = reinterpret_cast<float4*>(p); float4* g4 = reinterpret_cast<float4*>(g);
+  float4* m4 = reinterpret_cast<float4*>(m); float4* v4 = reinterpret_cast<float4*>(v);
+  float4* e4 = reinterpret_cast<float4*>(e);
+  const float4* a4 = reinterpret_cast<const float4*>(anc);
+  int cur = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const long long e0 = 4 * i;
+    cur = find_group(s_end, ng, cur, e0);
+    if (s_end[cur] >= e0 + 4) {           // the float4 lies inside one group: 16-byte accesses, one set of constants
+      const GroupConst c = s_c[cur];
+      if (!c.trainable) continue;
+      float4 pi = p4[i], gi = g4[i], mi = m4[i], vi = v4[i];
+      float4 ei, an = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (EMA) ei = e4[i];
+      if (c.pull != 0.f) an = a4[i];
+      group_adamw_one(pi.x, gi.x, mi.x, vi.x, an.x, c, a, coef);
+      group_adamw_one(pi.y, gi.y, mi.y, vi.y, an.y, c, a, coef);
+      group_adamw_one(pi.z, gi.z, mi.z, vi.z, an.z, c, a, coef);
+      group_adamw_one(pi.w, gi.w, mi.w, vi.w, an.w, c, a, coef);
+      if (a.max_norm > 0.f) g4[i] = gi;
+      p4[i] = pi; m4[i] = mi; v4[i] = vi;
+      if (EMA) {
+        ema_one(ei.x, pi.x, ema_w); ema_one(ei.y, pi.y, ema_w); ema_one(ei.z, pi.z, ema_w); ema_one(ei.w, pi.w, ema_w);
+        e4[i] = ei;
+      }
+    } else {                               // a boundary inside the float4: each lane with its own group's constants
+      int k = cur;
+      for (int j = 0; j < 4; ++j) {
+        while (k < ng - 1 && s_end[k] <= e0 + j) ++k;
+        group_adamw_elem<EMA>(e0 + j, s_c[k], p, g, m, v, e, ema_w, anc, a, coef);
+      }
+    }
+  }
+  for (int64_t i = 4 * n4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    cur = find_group(s_end, ng, cur, i);
+    group_adamw_elem<EMA>(i, s_c[cur], p, g, m, v, e, ema_w, anc, a, coef);
+  }
+}
+
+hipError_t launch_group_adamw(hipStream_t s, float* p, float* g, float* m, float* v, float* ema, float ema_w, const float* anchor, int64_t n,
+                              const AdamArgs& a, const int64_t* ends, const GroupConst* consts, int n_groups, double* ws, float* norm_out) {
+  if (n <= 0) return hipSuccess;
+  if (n_groups < 1 || n_groups > GROUPS_MAX || ends[n_groups - 1] != n) return hipErrorInvalidValue;
+  GroupTabArgs tab{};
+  const double* tab_ws = nullptr;
+  bool any_frozen = false;
+  for (int k = 0; k < n_groups; ++k) any_frozen |= consts[k].trainable == 0;
+  if (n_groups <= GROUPS_INLINE) {
+    for (int k = 0; k < n_groups; ++k) { tab.end[k] = ends[k]; tab.c[k] = consts[k]; }
+  } else {
+    for (int first = 0; first < n_groups; first += GROUPS_INLINE) {
+      const int count = n_groups - first < GROUPS_INLINE ? n_groups - first : GROUPS_INLINE;
+      for (int k = 0; k < count; ++k) { tab.end[k] = ends[first + k]; tab.c[k] = consts[first + k]; }
+      hipLaunchKernelGGL(k_write_groups, 1, GROUPS_INLINE, 0, s, tab, count, first, ws);
+    }
+    tab_ws = ws;
+  }
+  const size_t lds = (size_t)n_groups * (sizeof(GroupConst) + sizeof(long long));
+  int grid = ew_grid(n, 256 * 8);
+  if (grid > NORM_PARTS) grid = NORM_PARTS;
+  // nothing frozen: the norm is k_sumsq's own launch, so grad_norm and coef carry the plain step's bits by construction
+  if (any_frozen) hipLaunchKernelGGL(k_sumsq_groups, grid, 256, lds, s, g, n, ws, tab, tab_ws, n_groups);
+  else hipLaunchKernelGGL(k_sumsq, grid, 256, 0, s, g, n, ws);
+  if (ema)
+    hipLaunchKernelGGL(k_adamw_groups<true>, ew_grid(n, 256 * 4), 256, lds, s, p, g, m, v, ema, ema_w, anchor, n, a, ws, grid, norm_out, tab, tab_ws, n_groups);
+  else
+    hipLaunchKernelGGL(k_adamw_groups<false>, ew_grid(n, 256 * 4), 256, lds, s, p, g, m, v, (float*)nullptr, 0.f, anchor, n, a, ws, grid, norm_out, tab,
+                       tab_ws, n_groups);
+  return hipGetLastError();
+}
+
 // ---- the DP-SGD variant of the fused step (dp.h): Gaussian noise instead of the batch clip ----
 // The same seven streams (g is always written back: the noised gradient) plus the Philox / Box-Muller ALU work; no k_sumsq pass, since
 // nothing here depends on the batch's norm.  The four normals of float4 group q = i / 4 come from one Philox block at counter

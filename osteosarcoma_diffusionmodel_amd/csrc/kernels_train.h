@@ -76,4 +76,18 @@ hipError_t launch_clip_adamw(hipStream_t s, float* p, float* g, float* m, float*
 hipError_t launch_dp_adamw(hipStream_t s, float* p, float* g, float* m, float* v, int64_t n, const AdamArgs& a, float noise_std, uint64_t seed,
                            uint32_t step, float* ema = nullptr, float ema_w = 0.f);
 
+// ---- the grouped step: per-range learning rate, weight decay and a pull toward an anchor (fine-tuning) ----
+// The flat buffer is cut into n_groups sorted ranges that cover [0, n): group k is [k ? end[k-1] : 0, end[k]).  A group with
+// trainable == 0 is frozen: none of its elements is read for the norm's value or written by the update.  Per element of a trainable
+// group: adamw_one with p <- p*decay, then (pull != 0) p <- p - pull*(p_old - anchor), then the moments and the addcdiv as ever.
+struct GroupConst { float decay, neg_step_size, pull; int trainable; };      // 16 bytes: one LDS / global read per group
+constexpr int GROUPS_MAX = 1024;
+constexpr int GROUPS_INLINE = 128;     // tables up to this size travel in the kernel arguments (3 KB); larger ones through the workspace
+// doubles of device workspace the grouped step needs: the norm partials, then the table (one int64 end and one GroupConst per group)
+constexpr int64_t GROUP_WS_DOUBLES = 256 + 3 * (int64_t)GROUPS_MAX;
+// `a`: the shared constants (a.decay and a.neg_step_size are unused: each group has its own).  ends / consts: host arrays of n_groups.
+// ws: device, GROUP_WS_DOUBLES doubles, no initial state required.  anchor may be null when no group has pull != 0.
+hipError_t launch_group_adamw(hipStream_t s, float* p, float* g, float* m, float* v, float* ema, float ema_w, const float* anchor, int64_t n,
+                              const AdamArgs& a, const int64_t* ends, const GroupConst* consts, int n_groups, double* ws, float* norm_out);
+
 }  // namespace osd

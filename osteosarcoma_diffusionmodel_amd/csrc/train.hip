@@ -5,6 +5,7 @@
 #include <string.h>
 #include <cmath>
 #include <algorithm>
+#include <vector>
 #include "handle.h"
 #include "kernels.h"
 #include "kernels_train.h"
@@ -1266,6 +1267,71 @@ int osd_nn_clip_adamw_ema_step(void* stream, int device, double* normsq_ws, floa
                                double max_norm, int64_t step, double ema_decay, float* grad_norm_out) {
   return clip_adamw_step(nullptr, (hipStream_t)stream, device, normsq_ws, param, grad, exp_avg, exp_avg_sq, numel,
                          {lr, beta1, beta2, eps, weight_decay, max_norm, step}, grad_norm_out, true, ema, ema_decay);
+}
+
+// The checked body of the two grouped entry points (osdiff.h): everything below the last set_error() is the first device call.
+static int group_adamw_step(osd_handle* h, hipStream_t stream, int device, double* norm_ws, float* param, float* grad, float* exp_avg,
+                            float* exp_avg_sq, float* ema, const float* anchor, int64_t numel, const osd_param_group* groups, int n_groups,
+                            const AdamHyper& hp, double ema_decay, float* grad_norm_out) {
+  static_assert(OSD_MAX_PARAM_GROUPS == GROUPS_MAX && OSD_GROUP_WS_DOUBLES == GROUP_WS_DOUBLES, "osdiff.h and kernels_train.h disagree");
+  if ((!h && !norm_ws) || !param || !grad || !exp_avg || !exp_avg_sq || !groups) { set_error("null argument"); return OSD_EINVAL; }
+  if (ema && !(ema_decay >= 0.0 && ema_decay <= 1.0)) { set_error("ema_decay must be in [0, 1]"); return OSD_EINVAL; }
+  if (numel <= 0 || hp.step < 1) { set_error("numel and step must be positive"); return OSD_EINVAL; }
+  if (n_groups < 1 || n_groups > OSD_MAX_PARAM_GROUPS) { set_error("n_groups=%d outside [1, %d]", n_groups, OSD_MAX_PARAM_GROUPS); return OSD_EINVAL; }
+  const double bc1 = 1.0 - pow(hp.beta1, (double)hp.step);
+  const double bc2 = 1.0 - pow(hp.beta2, (double)hp.step);
+  std::vector<int64_t> ends((size_t)n_groups);
+  std::vector<GroupConst> consts((size_t)n_groups);
+  int64_t at = 0;
+  for (int k = 0; k < n_groups; ++k) {
+    const osd_param_group& gr = groups[k];
+    if (gr.begin != at || gr.end <= gr.begin || gr.end > numel) {
+      set_error("group %d is [%lld, %lld): the groups must be sorted, non-empty, non-overlapping and cover [0, %lld) (expected begin %lld)", k,
+                (long long)gr.begin, (long long)gr.end, (long long)numel, (long long)at);
+      return OSD_EINVAL;
+    }
+    at = gr.end;
+    const float sc[3] = {gr.lr_scale, gr.wd_scale, gr.l2sp};
+    for (float x : sc)
+      if (!(x >= 0.f) || !std::isfinite(x)) { set_error("group %d: lr_scale, wd_scale and l2sp must be finite and >= 0, got %g", k, (double)x); return OSD_EINVAL; }
+    if (gr.l2sp > 0.f && !anchor) { set_error("group %d has l2sp=%g but anchor is null", k, (double)gr.l2sp); return OSD_EINVAL; }
+    const double lr_k = hp.lr * (double)gr.lr_scale;
+    ends[(size_t)k] = gr.end;
+    consts[(size_t)k] = {(float)(1.0 - lr_k * hp.weight_decay * (double)gr.wd_scale), (float)(-(lr_k / bc1)), (float)(lr_k * (double)gr.l2sp),
+                         gr.lr_scale != 0.f ? 1 : 0};      // frozen iff lr_scale == 0
+  }
+  if (at != numel) { set_error("the groups end at %lld, not at numel=%lld", (long long)at, (long long)numel); return OSD_EINVAL; }
+  OSD_HIP(hipSetDevice(h ? h->cfg.device : device));
+  if (h) {
+    OSD_TRY(h->normsq_dev.reserve(OSD_GROUP_WS_DOUBLES, h->stream));
+    h->w_packed_stale = true;      // as osd_clip_adamw_step: the next forward / sampling entry point refreshes the derived weight copies
+    stream = h->stream; norm_ws = h->normsq_dev;
+  }
+  AdamArgs a{};
+  a.one_minus_b1 = (float)(1.0 - hp.beta1);
+  a.b2 = (float)hp.beta2;
+  a.one_minus_b2 = (float)(1.0 - hp.beta2);
+  a.bc2_sqrt = (float)sqrt(bc2);
+  a.eps = (float)hp.eps;
+  a.max_norm = (float)hp.max_norm;
+  OSD_HIP(launch_group_adamw(stream, param, grad, exp_avg, exp_avg_sq, ema, (float)(1.0 - ema_decay), anchor, numel, a, ends.data(), consts.data(),
+                             n_groups, norm_ws, grad_norm_out));
+  return OSD_OK;
+}
+
+int osd_group_adamw_step(osd_handle* h, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* ema, const float* anchor, int64_t numel,
+                         const osd_param_group* groups_host, int n_groups, double lr, double beta1, double beta2, double eps, double weight_decay,
+                         double max_norm, int64_t step, double ema_decay, float* grad_norm_out) {
+  if (!h) { set_error("null argument"); return OSD_EINVAL; }
+  return group_adamw_step(h, nullptr, 0, nullptr, param, grad, exp_avg, exp_avg_sq, ema, anchor, numel, groups_host, n_groups,
+                          {lr, beta1, beta2, eps, weight_decay, max_norm, step}, ema_decay, grad_norm_out);
+}
+
+int osd_nn_group_adamw_step(void* stream, int device, double* normsq_ws, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                            const float* anchor, int64_t numel, const osd_param_group* groups_host, int n_groups, double lr, double beta1,
+                            double beta2, double eps, double weight_decay, double max_norm, int64_t step, double ema_decay, float* grad_norm_out) {
+  return group_adamw_step(nullptr, (hipStream_t)stream, device, normsq_ws, param, grad, exp_avg, exp_avg_sq, ema, anchor, numel, groups_host,
+                          n_groups, {lr, beta1, beta2, eps, weight_decay, max_norm, step}, ema_decay, grad_norm_out);
 }
 
 int osd_dp_adamw_step(osd_handle* h, float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel, double lr, double beta1,

@@ -18,6 +18,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import logging
+import math
 import time
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence
@@ -264,6 +265,77 @@ class ParamEMA:
         self.num_updates = int(state_dict.get("num_updates", 0))
 
 
+def merge_param_groups(groups, n_params: int) -> list:
+    """Check a list of ``(first_param, last_param, lr_scale, wd_scale, l2sp)`` (inclusive ends, sorted, covering parameters
+    0 .. n_params - 1) and merge adjacent entries whose three settings are equal."""
+    out: list = []
+    at = 0
+    for first, last, lr_s, wd_s, l2sp in groups:
+        first, last = int(first), int(last)
+        sett = (float(lr_s), float(wd_s), float(l2sp))
+        if first != at or last < first or last >= n_params:
+            raise ValueError(f"parameter groups must be sorted and cover parameters 0..{n_params - 1} without gaps: got ({first}, {last}) "
+                             f"where {at} was expected to start")
+        if not all(math.isfinite(x) and x >= 0.0 for x in sett):
+            raise ValueError(f"lr_scale, wd_scale and l2sp must be finite and >= 0, got {sett}")
+        if out and out[-1][2:] == sett:
+            out[-1] = (out[-1][0], last) + sett
+        else:
+            out.append((first, last) + sett)
+        at = last + 1
+    if at != n_params:
+        raise ValueError(f"parameter groups end at parameter {at - 1}, the model has {n_params}")
+    return out
+
+
+def _parameterless_modules(model: nn.Module) -> list:
+    """Names of the model's own modules that hold no parameters (this model: ``unet.time_embed``, a sinusoidal table): the prefixes
+    ``build_param_groups`` accepts although nothing lies under them.  torch.nn's own parameterless layers (an activation, a Dropout
+    inside a block) are left out, so that a mistyped prefix that happens to land on one is still a ValueError."""
+    return [k for k, m in model.named_modules()
+            if k and not type(m).__module__.startswith("torch.nn") and next(m.parameters(), None) is None]
+
+
+def build_param_groups(names, freeze=(), lr_scale=None, weight_decay_scale=None, l2_sp: float = 0.0, module_names=()) -> list:
+    """The group table of a fine-tune from parameter-name prefixes: one ``(i, i, lr_scale, wd_scale, l2sp)`` per parameter of
+    ``names`` (``named_parameters()`` order), merged by ``merge_param_groups``.  A prefix matches a name equal to it or continuing
+    it with a dot (``unet.encoder`` matches ``unet.encoder.0.weight``, not ``unet.encoder2.weight``); among the prefixes of a mapping
+    the longest match wins.  ``freeze`` sets ``lr_scale`` 0; ``l2_sp`` applies to every trainable tensor (a frozen one cannot move, so
+    it carries none).  ValueError: a prefix that matches no parameter, a prefix in both ``freeze`` and ``lr_scale``, a negative scale.
+    ``module_names`` (the Trainer passes ``_parameterless_modules(model)``): a prefix that names one of these is accepted even when no
+    parameter lies under it -- this model's ``unet.time_embed`` is a parameterless sinusoidal table (the learned part is
+    ``unet.time_proj``) -- and then selects nothing, with a logged warning."""
+    names = list(names)
+    freeze = list(freeze or ())
+    lr_scale, weight_decay_scale = dict(lr_scale or {}), dict(weight_decay_scale or {})
+    l2_sp = float(l2_sp)
+    both = sorted(set(freeze) & set(lr_scale))
+    if both:
+        raise ValueError(f"prefixes {both} appear in both freeze and lr_scale")
+
+    def matches(prefix, name):
+        return name == prefix or name.startswith(prefix + ".")
+
+    module_names = set(module_names)
+    for prefix in list(freeze) + list(lr_scale) + list(weight_decay_scale):
+        if not any(matches(prefix, n) for n in names):
+            if prefix not in module_names:
+                raise ValueError(f"prefix {prefix!r} matches no parameter of the model")
+            logger.warning(f"training.finetune: the module {prefix!r} holds no parameters; the prefix selects nothing")
+
+    def longest(mapping, name, default):
+        hits = [k for k in mapping if matches(k, name)]
+        return float(mapping[max(hits, key=len)]) if hits else default
+
+    lr_map = dict({k: 0.0 for k in freeze}, **lr_scale)
+    groups = []
+    for i, name in enumerate(names):
+        lr_s = longest(lr_map, name, 1.0)
+        wd_s = longest(weight_decay_scale, name, 1.0)
+        groups.append((i, i, lr_s, wd_s, l2_sp if lr_s != 0.0 else 0.0))
+    return merge_param_groups(groups, len(names))
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """AdamW whose ``step`` is ONE pass of the fused clip_grad_norm_ + AdamW kernel over the flat
     parameter / gradient buffers (utils/train.py:169-173, 242-244).  ``state_dict()`` has the
@@ -291,18 +363,59 @@ class FusedAdamW(torch.optim.Optimizer):
         self.grad_norm = torch.zeros(1, device=flat.flat.device)
         self._normsq = torch.zeros(256, device=flat.flat.device, dtype=torch.float64)     # per-workgroup partials of the gradient norm
         self._step = 0
+        self._groups, self._group_table, self._group_ws = None, None, None      # set_groups(): the grouped step
+        self.anchor: Optional[torch.Tensor] = None
         for p, o, n in zip(flat.params, flat.offsets[:-1], flat.numels):
             self.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.exp_avg[o:o + n].view_as(p),
                              "exp_avg_sq": self.exp_avg_sq[o:o + n].view_as(p)}
 
+    def set_groups(self, groups, anchor: Optional[torch.Tensor] = None):
+        """Step ranges of parameters with their own settings (``osd_nn_group_adamw_step``).  ``groups``: a list of
+        ``(first_param, last_param, lr_scale, wd_scale, l2sp)`` over ``FlatParams``' parameter order, both ends inclusive, sorted and
+        covering every parameter; adjacent entries with equal settings are merged.  ``lr_scale == 0`` freezes a range: the step writes
+        nothing there (parameters, gradient, moments, EMA shadow) and leaves its gradient out of the clipping norm.  ``l2sp > 0`` pulls
+        the range toward ``anchor``, a flat tensor with ``flat.flat``'s layout: ``p -= lr * lr_scale * l2sp * (p - anchor)``, decoupled
+        like the weight decay.  ``set_groups(None)`` returns to the plain step.  Not available together with ``dp``."""
+        if groups is None:
+            self._groups, self._group_table, self.anchor = None, None, None
+            return
+        if self.dp is not None:
+            raise ValueError("parameter groups cannot be combined with the DP-SGD step (FusedAdamW.dp)")
+        merged = merge_param_groups(groups, len(self.flat.params))
+        if len(merged) > L.OSD_MAX_PARAM_GROUPS:
+            raise ValueError(f"{len(merged)} parameter groups after merging; the grouped step takes at most {L.OSD_MAX_PARAM_GROUPS}")
+        if anchor is not None and (anchor.shape != self.flat.flat.shape or anchor.dtype != torch.float32 or anchor.device != self.flat.flat.device
+                                   or not anchor.is_contiguous()):
+            raise ValueError("anchor must be a contiguous fp32 tensor with the flat parameter buffer's shape and device")
+        if anchor is None and any(g[4] > 0 for g in merged):
+            raise ValueError("a group has l2sp > 0 but no anchor was given")
+        table = (L.OsdParamGroup * len(merged))()
+        for k, (first, last, lr_s, wd_s, l2sp) in enumerate(merged):
+            table[k] = L.OsdParamGroup(int(self.flat.offsets[first]), int(self.flat.offsets[last + 1]), lr_s, wd_s, l2sp)
+        if self._group_ws is None:
+            self._group_ws = torch.zeros(L.OSD_GROUP_WS_DOUBLES, device=self.flat.flat.device, dtype=torch.float64)
+        self._groups, self._group_table, self.anchor = merged, table, anchor
+
     @torch.no_grad()
     def step(self, closure=None):
         g = self.param_groups[0]
+        if self._groups is not None and self.dp is not None:
+            raise ValueError("parameter groups cannot be combined with the DP-SGD step (FusedAdamW.dp)")
         self._step += 1
         dev = self.flat.flat.device
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         dev_i = dev.index if dev.index is not None else torch.cuda.current_device()
-        if self.dp is not None:
+        if self._groups is not None:
+            ema_decay = self.ema.decay_at(self._step) if self.ema is not None else 0.0
+            L.check(L.lib().osd_nn_group_adamw_step(stream, dev_i, L.ptr(self._group_ws), L.ptr(self.flat.flat), L.ptr(self.flat.grad),
+                                                    L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
+                                                    L.ptr(self.ema.shadow if self.ema is not None else None), L.ptr(self.anchor),
+                                                    self.flat.flat.numel(), self._group_table, len(self._group_table), g["lr"], g["betas"][0],
+                                                    g["betas"][1], g["eps"], g["weight_decay"], self.max_norm, self._step, ema_decay,
+                                                    L.ptr(self.grad_norm)))
+            if self.ema is not None:
+                self.ema.num_updates += 1
+        elif self.dp is not None:
             if self.dp_rows < 1:
                 raise RuntimeError("FusedAdamW.dp needs dp_rows, the number of rows behind the gradients")
             std = float(self.dp["noise_multiplier"]) * float(self.dp["max_grad_norm"]) / self.dp_rows
@@ -644,8 +757,48 @@ def validation_metric_of(training_config: dict) -> str:
     return v
 
 
+FINETUNE_KEYS = ("checkpoint", "use_ema", "source_features", "l2_sp", "freeze", "lr_scale", "weight_decay_scale")
+
+
+def check_finetune_config(ft, tc: dict, *, is_vae: bool, dist_initialised: bool) -> Optional[dict]:
+    """``training.finetune`` normalised (None when absent), with every refusal that needs no model: raised before the device."""
+    if ft is None:
+        return None
+    if not isinstance(ft, dict):
+        raise ValueError(f"training.finetune must be a mapping, got {type(ft).__name__}")
+    unknown = sorted(set(ft) - set(FINETUNE_KEYS))
+    if unknown:
+        raise ValueError(f"training.finetune: unknown keys {unknown} (known: {list(FINETUNE_KEYS)})")
+    if tc.get("dp") is not None:
+        raise ValueError("training.finetune is not supported with training.dp: the DP-SGD step has no parameter groups")
+    if is_vae:
+        raise ValueError("training.finetune carries a diffusion checkpoint and is not accepted for a cVAE model")
+    if dist_initialised:
+        raise ValueError("training.finetune is not supported under torch.distributed: the grouped step is rank-local but untested there")
+    l2_sp = float(ft.get("l2_sp") or 0.0)
+    if not (math.isfinite(l2_sp) and l2_sp >= 0.0):
+        raise ValueError(f"training.finetune.l2_sp={l2_sp} must be finite and >= 0")
+    out = {"checkpoint": None if ft.get("checkpoint") is None else str(ft["checkpoint"]), "use_ema": bool(ft.get("use_ema", True)),
+           "source_features": ft.get("source_features"), "l2_sp": l2_sp, "freeze": [str(k) for k in (ft.get("freeze") or [])],
+           "lr_scale": {str(k): float(v) for k, v in (ft.get("lr_scale") or {}).items()},
+           "weight_decay_scale": {str(k): float(v) for k, v in (ft.get("weight_decay_scale") or {}).items()}}
+    both = sorted(set(out["freeze"]) & set(out["lr_scale"]))
+    if both:
+        raise ValueError(f"prefixes {both} appear in both freeze and lr_scale")
+    return out
+
+
 class Trainer:
     """Training pipeline (utils/train.py:151-339) on the fused HIP path.
+
+    Fine-tuning (``training.finetune``; absent: nothing below exists -- same launches, same bits, same checkpoint keys; DESIGN.md section
+    3.35): the model starts from ``finetune.checkpoint`` carried onto this run's feature panel (``transfer.load_pretrained``), the flat
+    parameters at that point are kept as the anchor, and the optimizer steps parameter groups built from name prefixes (``freeze``,
+    ``lr_scale``, ``weight_decay_scale``; the longest matching prefix wins) with ``l2_sp`` pulling every trainable tensor toward the
+    anchor.  ``ReduceLROnPlateau`` keeps acting on the one learning rate; the scales multiply it.  The backward pass still computes every
+    gradient, frozen tensors' included.  Checkpoints then carry ``finetune_state``.  Not with ``training.dp``, a cVAE or an initialised
+    ``torch.distributed`` world (ValueError at construction).  ``training.save_feature_names: true`` stores the panel's column names
+    (``feature_names``) in every checkpoint, which is what a later fine-tune on another panel matches columns by.
 
     Data parallel: when ``torch.distributed`` is initialised every rank runs this class on its
     own shard; gradients are averaged with one bucketed RCCL all-reduce per step, launched on a
@@ -669,8 +822,10 @@ class Trainer:
     batches, and the noise is Philox's, not a cryptographically secure generator's.  Checkpoints then carry ``dp_state``."""
 
     def __init__(self, model: nn.Module, train_loader: DataLoader, val_loader: DataLoader, config: dict,
-                 device: str = "cuda", *, comm: Optional[str] = None):
-        """``comm``: how the data-parallel gradient exchange is driven -- "torch" (``torch.distributed.all_reduce``
+                 device: str = "cuda", *, comm: Optional[str] = None, feature_names: Optional[dict] = None):
+        """``feature_names``: this run's panel (``{"mutations", "expression", "pathways", "conditions"}`` -> names) for
+        ``training.finetune`` and ``training.save_feature_names``; default: what ``prepare_data`` attached to the dataset.
+        ``comm``: how the data-parallel gradient exchange is driven -- "torch" (``torch.distributed.all_reduce``
         per bucket on a side stream; any backend, the default) or "rccl" (the library's own RCCL communicator,
         ``osd_allreduce_grads_begin/end``; needs one GPU per rank).  ``OSD_COMM`` in the environment sets the default."""
         tc = config["training"]
@@ -682,6 +837,20 @@ class Trainer:
         from . import privacy as PV
         cons = getattr(model, "_constraints", None)
         world = torch.distributed.get_world_size() if torch.distributed.is_available() and torch.distributed.is_initialized() else 1
+        # training.finetune: every refusal before the device, the prefixes against the model's names included
+        self.finetune = check_finetune_config(tc.get("finetune"), tc, is_vae=hasattr(model, "vae"),
+                                              dist_initialised=torch.distributed.is_available() and torch.distributed.is_initialized())
+        if self.finetune is not None:
+            build_param_groups([k for k, _ in model.named_parameters()], self.finetune["freeze"], self.finetune["lr_scale"],
+                               self.finetune["weight_decay_scale"], self.finetune["l2_sp"], _parameterless_modules(model))
+        ds_base, _ = ResidentSplit._base_of(getattr(train_loader, "dataset", None))
+        self.feature_names = feature_names if feature_names is not None else getattr(ds_base, "feature_names", None)
+        self.save_feature_names = bool(tc.get("save_feature_names", False))
+        if self.save_feature_names:
+            if self.feature_names is None:
+                raise ValueError("training.save_feature_names needs the panel's names: a dataset from prepare_data or Trainer(feature_names=...)")
+            from .transfer import check_feature_names
+            self.feature_names = check_feature_names(self.feature_names, "feature_names")
         self.dp = PV.check_dp_config(tc.get("dp"), tc, is_vae=hasattr(model, "vae"),
                                      constraints=cons is not None and (cons["w_pc"] != 0.0 or cons["w_me"] != 0.0), world=world)
         if self.dp is not None and self.dp["noise_multiplier"] is None and int(tc["num_epochs"]) * len(train_loader) < 1:
@@ -732,6 +901,13 @@ class Trainer:
             raise ValueError(f"training.validation_timesteps={self.validation_timesteps}: at least 2 (t = 0 and one more)")
         if self.validation_metric == "bound" and hasattr(model, "vae"):
             raise ValueError("training.validation_metric 'bound' scores the diffusion model and is not accepted for a cVAE model")
+        self.finetune_report = None
+        self.anchor: Optional[torch.Tensor] = None
+        if self.finetune is not None and self.finetune["checkpoint"] is not None:
+            # before FlatParams: the copy goes into the parameters the flat buffer is then built from
+            from .transfer import load_pretrained
+            self.finetune_report = load_pretrained(model, self.finetune["checkpoint"], self.feature_names, self.finetune["source_features"],
+                                                   use_ema=None if self.finetune["use_ema"] else False)
         self.model = model.to(device)
         self.train_loader, self.val_loader = train_loader, val_loader
         self.config, self.device = config, device
@@ -813,6 +989,9 @@ class Trainer:
                 # compute side stream of train.hip, a non-default stream priority upsets this stack's hardware-queue assignment
                 self._comm_stream = torch.cuda.Stream()
         self.global_step = 0
+        if self.finetune is not None:
+            self.anchor = self.flat.flat.detach().clone()        # the starting point L2-SP pulls toward: the Trainer's, handed to the optimizer
+            self._apply_param_groups()
         if self.dp is not None:
             self._dp_setup(tc)
         # device-resident epoch path (ResidentSplit): None = decide at the first epoch, False = off (the DataLoader is iterated)
@@ -853,6 +1032,40 @@ class Trainer:
             observed = 1.0 - float(torch.isnan(base.data).double().mean()) if base.data.numel() else 1.0
             logger.info(f"Incomplete data: {observed:.4f} of the dataset's elements are observed; the masked loss is a mean over all "
                         f"n x D elements (divide it by this fraction to compare with a complete-data loss)")
+
+    # -- fine-tuning (transfer.py) -------------------------------------------------
+    def _apply_param_groups(self):
+        ft = self.finetune
+        names = [k for k, _ in self.model.named_parameters()]
+        groups = build_param_groups(names, ft["freeze"], ft["lr_scale"], ft["weight_decay_scale"], ft["l2_sp"],
+                                    _parameterless_modules(self.model))
+        self.optimizer.set_groups(groups, self.anchor)
+
+    def set_param_groups(self, *, freeze=None, lr_scale=None, weight_decay_scale=None, l2_sp=None):
+        """Change the fine-tune's groups between steps (gradual unfreezing); an argument left None keeps its current setting, and the
+        anchor stays the run's starting point.  A tensor unfrozen late starts from zero moments under the run's GLOBAL bias correction
+        (the step count is shared): its first updates are smaller than a fresh optimizer's by 1 - beta1^k, not larger.  Needs
+        ``training.finetune`` (an empty mapping is enough); the prefix rules and ValueErrors are ``build_param_groups``'."""
+        if self.finetune is None:
+            raise RuntimeError("set_param_groups() needs training.finetune: this Trainer steps one plain group")
+        new = dict(self.finetune)
+        if freeze is not None:
+            new["freeze"] = [str(k) for k in freeze]
+        if lr_scale is not None:
+            new["lr_scale"] = {str(k): float(v) for k, v in dict(lr_scale).items()}
+        if weight_decay_scale is not None:
+            new["weight_decay_scale"] = {str(k): float(v) for k, v in dict(weight_decay_scale).items()}
+        if l2_sp is not None:
+            new["l2_sp"] = float(l2_sp)
+        build_param_groups([k for k, _ in self.model.named_parameters()], new["freeze"], new["lr_scale"], new["weight_decay_scale"], new["l2_sp"],
+                           _parameterless_modules(self.model))
+        self.finetune = new
+        self._apply_param_groups()
+
+    def _anchor_views(self) -> Dict[str, torch.Tensor]:
+        names = [k for k, _ in self.model.named_parameters()]
+        a = self.anchor
+        return {k: a[o:o + n].view_as(p) for k, p, o, n in zip(names, self.flat.params, self.flat.offsets[:-1], self.flat.numels)}
 
     # -- differentially private training (privacy.py; DESIGN.md section 3.21) -----------------------------
     def _dp_setup(self, tc: dict):
@@ -1109,6 +1322,13 @@ class Trainer:
                                 "sample_rate": float(self.dp["sample_rate"])}
         if getattr(self.model, "feature_transform", None) is not None:
             ckpt["feature_transform"] = self.model.feature_transform.state_dict()
+        if self.finetune is not None:
+            ft = self.finetune
+            ckpt["finetune_state"] = {"anchor": {k: v.detach().clone() for k, v in self._anchor_views().items()}, "l2_sp": float(ft["l2_sp"]),
+                                      "freeze": list(ft["freeze"]), "lr_scale": dict(ft["lr_scale"]),
+                                      "weight_decay_scale": dict(ft["weight_decay_scale"])}
+        if self.save_feature_names:
+            ckpt["feature_names"] = {k: list(v) for k, v in self.feature_names.items()}
         torch.save(ckpt, self.save_dir / f"checkpoint_epoch_{epoch}.pt")
         if is_best:
             best = self.save_dir / "best_model.pt"
@@ -1158,6 +1378,17 @@ class Trainer:
                 self.ema.num_updates = 0
         if self.dp is not None:
             self._dp_steps = dp_steps
+        if self.finetune is not None and "finetune_state" in ckpt:
+            # a resumed fine-tune: the anchor is the ORIGINAL starting point and the groups are the ones in force when the file was written
+            st = ckpt["finetune_state"]
+            views = self._anchor_views()
+            missing = [k for k in views if k not in st["anchor"]]
+            if missing:
+                raise KeyError(f"finetune_state's anchor lacks {missing[:3]}{'...' if len(missing) > 3 else ''}")
+            with torch.no_grad():
+                for k, view in views.items():
+                    view.copy_(st["anchor"][k])
+            self.set_param_groups(freeze=st["freeze"], lr_scale=st["lr_scale"], weight_decay_scale=st["weight_decay_scale"], l2_sp=st["l2_sp"])
         if resumed_ft is not None:
             self.model.feature_transform = resumed_ft
         self._engines_stale()
@@ -1241,6 +1472,9 @@ def prepare_data(config: dict):
     from .diffusion import check_missing_values
     incomplete = "keep" if check_missing_values(tc.get("missing_values")) == "mask" else "drop"
     dataset = OsteosarcomaDataset(mutation_matrix, expression_matrix, pathway_scores, clinical, condition_features, incomplete=incomplete)
+    # the panel's column names: what training.save_feature_names stores and a fine-tune on another panel matches columns by (transfer.py)
+    dataset.feature_names = {"mutations": [str(c) for c in mutation_matrix.columns], "expression": [str(c) for c in expression_matrix.columns],
+                             "pathways": [str(c) for c in pathway_scores.columns], "conditions": list(condition_features)}
     val_size = int(len(dataset) * tc["val_split"])
     train_ds, val_ds = torch.utils.data.random_split(dataset, [len(dataset) - val_size, val_size],
                                                      generator=torch.Generator().manual_seed(tc["random_seed"]))
